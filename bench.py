@@ -17,6 +17,9 @@ value = env steps taken by ALL ranks inside the K timed calls / max-over-ranks w
 fill (2000 policy steps per actor, no learning -- the reference's global_t does not advance there
 either, trainer.py:446-448) and W warm-up calls are untimed.
 
+--dump-outputs DIR writes, after the timed calls, what the last timed call handed its caller (see dump_outputs) as
+DIR/<name>.npy: the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
 Extra objects on the JSON line: `roofline` for the dominant kernel (HIP-event timed inside the timed
 region) and `cpu_baseline` (the oracle's threaded restatement of the reference loop on host cores).
 """
@@ -145,6 +148,48 @@ def cpu_baseline(legs, history, extra_history=100):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, tr, net, losses, stats):
+    """What the last timed process() call computed, as DIR/<name>.npy (float32 / float64) + DIR/manifest.json: the
+    updated parameters, the gradient and losses of its update, the rollout's policy / value / actions / rewards /
+    terminals (the last group of actors when --groups > 1), the LSTM state carried into the next call, and the
+    env-step statistics of the timed calls.  If the arrays exceed DUMP_BUDGET_BYTES in all, each is cut to its
+    proportional share by a fixed, seeded sample of its elements (same arguments -> same indices)."""
+    import numpy as np
+    names = ("total_loss", "base_loss", "policy_loss", "value_loss", "entropy", "pc_loss", "vr_loss", "rp_loss")
+    arrays = [
+        ("params", net.params.flat), ("grads", net.grads.flat),
+        ("losses", np.array([losses[k] for k in names], dtype=np.float64)),
+        ("grad_norm", np.array([losses["grad_norm"]], dtype=np.float64)),
+        ("policy", tr.pi), ("value", tr.v), ("actions", tr.actions), ("rewards", tr.rewards),
+        ("terminals", tr.terminals), ("lstm_c", tr.full_lstm_c), ("lstm_h", tr.full_lstm_h),
+        ("timed_env_stats", np.array(stats, dtype=np.float64)),            # env steps, episodes, score sum
+    ]
+    torch.cuda.synchronize()
+    host = []
+    for name, a in arrays:
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else a
+        host.append((name, a if a.dtype == np.float64 else a.astype(np.float32)))
+    total = sum(a.nbytes for _, a in host)
+    budget = DUMP_BUDGET_BYTES - 4096 * (len(host) + 1)                    # .npy headers and the manifest
+    os.makedirs(out_dir, exist_ok=True)
+    manifest = {}
+    for name, a in host:
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": False}
+        if total > budget:
+            keep = int(a.size * budget // total)
+            if keep < a.size:
+                idx = np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))
+                a = a.reshape(-1)[idx]
+                entry.update(sampled=True, sample_size=keep, sample_seed=0)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        manifest[name] = entry
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -160,7 +205,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--timed-kernel", default="unreal_encoder_bwd")
     ap.add_argument("--progress", action="store_true", help="phase markers on stderr (diagnosing a run under a profiler)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed calls, write what the last one "
+                    "computed as DIR/<name>.npy (rank 0; at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     from unreal_amd import parallel
     n_dev = parallel.visible_gpus()                    # from sysfs: the launcher below never initialises HIP / HSA
@@ -245,6 +294,8 @@ def main():
     if rank != 0:
         parallel.shutdown()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, tr, net, losses, (steps_local, episodes, score_sum))
     value = tot_steps / elapsed
     frames_per_launch = kt["units"] / max(kt["launches"], 1)
     mac = ENC_BWD_MAC if "bwd" in args.timed_kernel else ENC_FWD_MAC

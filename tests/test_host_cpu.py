@@ -211,7 +211,7 @@ def test_integration_doc_names_every_entry_point():
     assert not missing, missing
 
 
-def test_smoke_entry_can_import_its_test_helpers():
+def test_smoke_entry_can_import_its_test_helpers(tmp_path):
     """__graft_entry__.smoke() borrows helpers from tests/test_trainer_gpu.py, importing it as `tests.test_trainer_gpu` from a
     process whose sys.path holds the repo root only (the driver's call): every module-level import of that file must
     resolve there (round 4: `import margins` did not)."""
@@ -219,5 +219,5 @@ def test_smoke_entry_can_import_its_test_helpers():
     import sys
     code = ("import sys; sys.path.insert(0, %r); import importlib; "
             "m = importlib.import_module('tests.test_trainer_gpu'); assert hasattr(m, '_build') and hasattr(m.margins, 'record')" % ROOT)
-    r = subprocess.run([sys.executable, "-c", code], cwd="/tmp", stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    r = subprocess.run([sys.executable, "-c", code], cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode == 0, r.stderr.decode()[-2000:]

@@ -23,7 +23,10 @@ RANK_SCRIPT = textwrap.dedent("""
     ok = parallel.all_true(rank != 99, "cpu")
     mx = parallel.max_over_ranks(float(rank), "cpu")
     parallel.barrier()
-    print(json.dumps({"rank": rank, "sum": float(flat[0]), "all_true": ok, "max": mx, "n_gpus": world}), flush=True)
+    # one write() per line: ranks 1.. share the launcher's stderr, and print() under PYTHONUNBUFFERED writes the text and
+    # its newline separately, so two ranks' lines could interleave
+    sys.stdout.write(json.dumps({"rank": rank, "sum": float(flat[0]), "all_true": ok, "max": mx, "n_gpus": world}) + "\\n")
+    sys.stdout.flush()
     parallel.shutdown()
 """) % ROOT
 
