@@ -10,7 +10,8 @@
  *     (the Python host allocates them through PyTorch-ROCm); nothing is allocated or freed here.
  *   - `stream` is a hipStream_t passed as void*; every call is asynchronous on that stream.
  *   - return 0 = OK, -22 = invalid argument (nothing launched), -5 = launch failure.  Never throws.
- *   - No global state; not thread-safe per buffer (one host thread per GPU by contract).
+ *   - No global state apart from a thread-local label of the calling thread's last launch
+ *     (unreal_last_launch); not thread-safe per buffer (one host thread per GPU by contract).
  *   - Frames are uint8 NHWC 84x84x3 (21,168 B); a "frame index" f addresses frames + f*21168.
  *   - Ring: actor b owns H1 = H+1 slots; absolute frame i lives in slot i % H1; per-slot metadata
  *     arrays are [B][H1]; the current observation of actor b is slot count[b] % H1.
@@ -303,6 +304,9 @@ int unreal_rmsprop_step(float* var, float* ms, float* mom, const float* grad, lo
 int unreal_copy_words(long n, const void* src, void* dst, void* stream);
 /* y += alpha * x: the per-call mean of the loss scalars over the G sequential updates of a grouped process() */
 int unreal_axpy_f32(long n, float alpha, const float* x, float* y, void* stream);
+/* buf <- the label of the kernel variant the calling thread's most recent launch used (NUL-terminated, cut to len - 1
+ * characters; "" before the first launch).  Host only: no device work, no sync; `stream` is unused. */
+int unreal_last_launch(char* buf, int len, void* stream);
 
 #ifdef __cplusplus
 }

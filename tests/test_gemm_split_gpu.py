@@ -93,7 +93,11 @@ def test_split_gemm_error_not_above_fp32_mfma(M, N, K, factor):
     assert e16 <= factor * e32, (e16, e32, e16 / e32)
 
 
-@pytest.mark.parametrize("rows", [4096, 5000, 70, 3])
+BPTT_LABEL = {4096: "bptt kw4", 5000: "bptt kw2", 70: "bptt kw4", 3: "bptt kw4",      # KW 4 / 2 / 1 at 256 / 512 tiles
+              4097: "bptt kw2", 8192: "bptt kw2", 8193: "bptt kw1", 12300: "bptt kw1"}
+
+
+@pytest.mark.parametrize("rows", list(BPTT_LABEL))
 def test_fused_bptt_step_is_the_two_kernel_path(rows):
     """unreal_lstm_bptt_step == unreal_gemm_f32_split_nt (dh_rec = d_gates . Wh^T) + unreal_lstm_gates_bwd, bit for bit
     (same tiles, same K dealing, same order of the element-wise arithmetic), and matches a float64 evaluation."""
@@ -113,6 +117,7 @@ def test_fused_bptt_step_is_the_two_kernel_path(rows):
     # fused
     dc_b = dev(dc0).view(-1); dpre_b = torch.full((rows * 1024,), 9.0, device=DEV)
     ops.lstm_bptt_step(rows, dgd, sh, dha, dc_b, gd, cpd, cnd, dpre_b)
+    assert ops.last_launch() == BPTT_LABEL[rows]
     assert torch.equal(dc_a, dc_b) and torch.equal(dpre_a, dpre_b)
     f32 = lambda a: a.astype(np.float32).astype(np.float64)
     dh = f32(dh_above) + f32(d_gates) @ f32(Wh).T
@@ -126,7 +131,13 @@ def test_fused_bptt_step_is_the_two_kernel_path(rows):
         ops.lstm_bptt_step(rows, dgd, ops.SplitWeights(dev(Wh).view(-1), 256, 1024, 1024, True), dha, dc_b, gd, cpd, cnd, dpre_b)
 
 
-@pytest.mark.parametrize("rows,A,obj", [(4096, 4, 0), (8200, 4, 0), (70, 3, 7), (3, 6, 0)])    # 8200: plain 128x128 tiles, ragged
+LSTM_STEP_LABEL = {4096: "lstm_step 128x128 kw2", 8200: "lstm_step 128x128 kw1", 70: "lstm_step 64x64 vec kw4",
+                   3: "lstm_step 64x64 vec kw4", 1024: "lstm_step 64x64 vec kw4", 1025: "lstm_step 64x64 vec kw2",
+                   2047: "lstm_step 64x64 vec kw2", 2048: "lstm_step 128x128 kw2", 4097: "lstm_step 128x128 kw1"}
+
+
+@pytest.mark.parametrize("rows,A,obj", [(4096, 4, 0), (8200, 4, 0), (70, 3, 7), (3, 6, 0),    # 8200: plain 128x128 tiles, ragged
+                                        (1024, 4, 0), (1025, 4, 0), (2047, 4, 0), (2048, 4, 0), (4097, 4, 0)])
 def test_whole_kernel_lstm_step_matches_hoisted_chain_and_fp64(rows, A, obj):
     """unreal_lstm_step_fwd(x=...) -- [x | h] @ kernel in one launch, as a rollout step runs it -- against (a) the
     chain it replaces (input-half GEMM, then the recurrent step) at the fp32 tolerance (the two differ only in the
@@ -148,6 +159,7 @@ def test_whole_kernel_lstm_step_matches_hoisted_chain_and_fp64(rows, A, obj):
     ops.lstm_step_fwd(rows, hd, sh_h, g0, bd, cd, c0, h0)
     g1 = torch.full((rows * 1024,), 5.0, device=DEV); c1 = torch.zeros(rows * 256, device=DEV); h1 = torch.zeros(rows * 256, device=DEV)
     ops.lstm_step_fwd(rows, hd, sh_xh, g1, bd, cd, c1, h1, x=xd, ldx=xld, Kx=K_x)
+    assert ops.last_launch() == LSTM_STEP_LABEL[rows]
     for a, b in ((g0, g1), (c0, c1), (h0, h1)):
         np.testing.assert_allclose(b.cpu().numpy(), a.cpu().numpy(), atol=2e-6, rtol=2e-6)
     f32 = lambda a: a.astype(np.float32).astype(np.float64)

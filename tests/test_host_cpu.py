@@ -221,3 +221,44 @@ def test_smoke_entry_can_import_its_test_helpers(tmp_path):
             "m = importlib.import_module('tests.test_trainer_gpu'); assert hasattr(m, '_build') and hasattr(m.margins, 'record')" % ROOT)
     r = subprocess.run([sys.executable, "-c", code], cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
+
+
+def test_every_launch_label_has_a_dispatch_case():
+    """Each kernel variant a launcher can choose names itself (UNREAL_LAUNCHED in csrc/*.hip); tests/test_dispatch_gpu.py
+    pins each one against float64 on the GPU.  A variant added without a case there fails here, on a machine with no GPU;
+    a case whose label no launcher records any more fails too."""
+    import glob
+    import re
+    from tests.test_dispatch_gpu import CASES, case_labels
+    in_source = set()
+    for path in glob.glob(os.path.join(ROOT, "unreal_amd", "csrc", "*.hip")):
+        src = open(path).read()
+        for m in re.finditer(r"\bUNREAL_LAUNCHED\(((?:[^()]|\([^()]*\))*)\)", src):
+            in_source |= set(re.findall(r'"([^"]*)"', m.group(1)))
+    assert len(in_source) >= 30, sorted(in_source)
+    in_cases = {lab for c in CASES for lab in case_labels(c)}
+    assert not in_source - in_cases, sorted(in_source - in_cases)
+    assert not in_cases - in_source, sorted(in_cases - in_source)
+    assert max(len(l) for l in in_source) < 64                     # ops.last_launch reads through a 64-byte buffer
+
+
+def test_last_launch_is_host_bookkeeping(built):
+    """unreal_last_launch needs no device: before this thread launched anything its label is empty (the label is per
+    thread); a missing or empty buffer is refused."""
+    from unreal_amd import _lib
+    import threading
+    L = _lib.lib()
+    out = {}
+
+    def fresh_thread():
+        buf = ctypes.create_string_buffer(b"x" * 15, 16)
+        L.call("unreal_last_launch", buf, 16, None)
+        out["label"] = buf.value
+    t = threading.Thread(target=fresh_thread)
+    t.start()
+    t.join()
+    assert out["label"] == b""
+    with pytest.raises(_lib.UnrealLibError):
+        L.call("unreal_last_launch", None, 16, None)
+    with pytest.raises(_lib.UnrealLibError):
+        L.call("unreal_last_launch", ctypes.create_string_buffer(4), 0, None)

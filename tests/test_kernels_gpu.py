@@ -853,12 +853,17 @@ def test_policy_step_is_the_three_kernel_path(A):
     assert len(torch.unique(a1)) > 1
 
 
-@pytest.mark.parametrize("B", [4096, 1500, 512, 3])       # 8 actors per workgroup / ragged / 2 per workgroup / tiny
+MAZE_TIER = {4096: "big", 1500: "big", 512: "apg2", 3: "tiny",        # the step's tiers: one actor per workgroup at <= 64,
+             64: "tiny", 65: "apg2", 1024: "apg2", 1025: "big"}      # two at <= 1024, kStepActorsBig above
+
+
+@pytest.mark.parametrize("B", list(MAZE_TIER))
 def test_fused_policy_maze_rollout_step_is_the_two_launch_path(ops, B):
     """unreal_maze_policy_rollout_step == unreal_policy_step + unreal_maze_rollout_step, bit for bit: pi, V, actions,
     rewards / terminals, the loop bookkeeping, the next step's frame indices and last_action_reward columns, and the
     ring itself (frames, metadata, pixel change) over several chained steps with actors finishing on the way."""
     H, A, xld = 6, 4, 264
+    tier = MAZE_TIER[B]
     rs = np.random.RandomState(B)
     Wp = dev(rs.uniform(-.3, .3, 256 * A), torch.float32); bp = dev(rs.uniform(-.1, .1, A), torch.float32)
     Wv = dev(rs.uniform(-.3, .3, 256), torch.float32); bv = dev(rs.uniform(-.1, .1, 1), torch.float32)
@@ -882,9 +887,11 @@ def test_fused_policy_maze_rollout_step_is_the_two_launch_path(ops, B):
         ops.policy_step(B, A, X, 256, Wp, bp, Wv, bv, u, s0["pi"], s0["v"], s0["a"])
         ops.maze_rollout_step(rings[0], s0["a"], s0["r"], s0["t"], s0["active"], s0["log"], s0["n"], s0["te"],
                               next_idx=s0["idx"], next_lar=s0["lar"], lar_ld=xld, lar_col0=256, A=A)
+        assert ops.last_launch() == "maze_rollout_step " + tier
         ops.maze_policy_rollout_step(rings[1], X, 256, Wp, bp, Wv, bv, u, s1["pi"], s1["v"], s1["a"], s1["r"], s1["t"],
                                      s1["active"], s1["log"], s1["n"], s1["te"], next_idx=s1["idx"], next_lar=s1["lar"],
                                      lar_ld=xld, lar_col0=256, A=A)
+        assert ops.last_launch() == "maze_policy_step " + tier
         for k in s0:
             assert torch.equal(s0[k], s1[k]), (step, k)
         for name in ("frames", "r_reward", "r_action", "r_terminal", "r_last_action", "r_last_reward", "pos", "count",

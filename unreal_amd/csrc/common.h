@@ -26,6 +26,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
+// Each launcher names the template instantiation it launched (a static string; unreal_last_launch reads it back).  One
+// thread-local defined in launch.hip; tests/test_dispatch_gpu.py pins every label against a float64 reference.
+extern thread_local const char* unreal_launch_label;
+#define UNREAL_LAUNCHED(label) (unreal_launch_label = (label))
+
 static inline int unreal_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? UNREAL_OK : UNREAL_ELAUNCH;

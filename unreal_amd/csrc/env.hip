@@ -509,6 +509,7 @@ int unreal_maze_step(int B, int H1, const int* actions, const int* active, int* 
              r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward,
              score_out, score_valid, reset_on_terminal, track_score, nullptr, nullptr, nullptr, nullptr, nullptr,
              nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  UNREAL_LAUNCHED(B <= 64 ? "maze_step tiny" : B <= 1024 ? "maze_step apg2" : "maze_step big");
   if (B <= 64) hipLaunchKernelGGL(maze_step_kernel<kStepActorsTiny>, dim3((B + kStepActorsTiny - 1) / kStepActorsTiny), dim3(256), 0, (hipStream_t)stream, p);
   else if (B <= 1024) hipLaunchKernelGGL(maze_step_kernel<2>, dim3((B + 1) / 2), dim3(256), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(maze_step_kernel<kStepActorsBig>, dim3((B + kStepActorsBig - 1) / kStepActorsBig), dim3(256), 0, (hipStream_t)stream, p);
@@ -530,6 +531,7 @@ int unreal_maze_rollout_step(int B, int H1, const int* actions, int* pos, int* l
              r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward,
              score_out, score_valid, 1, 1, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
              lar_col0, A, idx_base_actor, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  UNREAL_LAUNCHED(B <= 64 ? "maze_rollout_step tiny" : B <= 1024 ? "maze_rollout_step apg2" : "maze_rollout_step big");
   if (B <= 64) hipLaunchKernelGGL(maze_step_kernel<kStepActorsTiny>, dim3((B + kStepActorsTiny - 1) / kStepActorsTiny), dim3(256), 0, (hipStream_t)stream, p);
   else if (B <= 1024) hipLaunchKernelGGL(maze_step_kernel<2>, dim3((B + 1) / 2), dim3(256), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(maze_step_kernel<kStepActorsBig>, dim3((B + kStepActorsBig - 1) / kStepActorsBig), dim3(256), 0, (hipStream_t)stream, p);
@@ -555,6 +557,7 @@ int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, cons
              r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward,
              score_out, score_valid, 1, 1, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
              lar_col0, A, idx_base_actor, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
+  UNREAL_LAUNCHED(B <= 64 ? "maze_policy_step tiny" : B <= 1024 ? "maze_policy_step apg2" : "maze_policy_step big");
   if (B <= 64) hipLaunchKernelGGL(maze_step_kernel<kStepActorsTiny>, dim3((B + kStepActorsTiny - 1) / kStepActorsTiny), dim3(256), 0, (hipStream_t)stream, p);
   else if (B <= 1024) hipLaunchKernelGGL(maze_step_kernel<2>, dim3((B + 1) / 2), dim3(256), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(maze_step_kernel<kStepActorsBig>, dim3((B + kStepActorsBig - 1) / kStepActorsBig), dim3(256), 0, (hipStream_t)stream, p);

@@ -237,11 +237,22 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
 
 template <int BM, int BN>
 int launch(int ta, int tb, const GemmArgs& a, int splitk, hipStream_t st) {
+  static_assert(BM == BN && (BM == 128 || BM == 64), "launch labels");
   dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, splitk), block(256);
-  if (!ta && !tb) hipLaunchKernelGGL((gemm_kernel<BM, BN, false, true>), grid, block, 0, st, a);
-  else if (!ta && tb) hipLaunchKernelGGL((gemm_kernel<BM, BN, false, false>), grid, block, 0, st, a);
-  else if (ta && !tb) hipLaunchKernelGGL((gemm_kernel<BM, BN, true, true>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((gemm_kernel<BM, BN, true, false>), grid, block, 0, st, a);
+  // label: tile, then n (as stored) / t (transposed) for A and B
+  if (!ta && !tb) {
+    UNREAL_LAUNCHED(BM == 128 ? "gemm_f32 128x128 nn" : "gemm_f32 64x64 nn");
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, false, true>), grid, block, 0, st, a);
+  } else if (!ta && tb) {
+    UNREAL_LAUNCHED(BM == 128 ? "gemm_f32 128x128 nt" : "gemm_f32 64x64 nt");
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, false, false>), grid, block, 0, st, a);
+  } else if (ta && !tb) {
+    UNREAL_LAUNCHED(BM == 128 ? "gemm_f32 128x128 tn" : "gemm_f32 64x64 tn");
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, true, true>), grid, block, 0, st, a);
+  } else {
+    UNREAL_LAUNCHED(BM == 128 ? "gemm_f32 128x128 tt" : "gemm_f32 64x64 tt");
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, true, false>), grid, block, 0, st, a);
+  }
   return unreal_launch_status();
 }
 

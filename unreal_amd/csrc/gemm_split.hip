@@ -1279,8 +1279,13 @@ static int split_nt_launch(int M, int N, int K, const float* A, int lda, const f
       hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, true, SPLIT_NT_DEEP128 != 0, 0, 1, false, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
     else
 #endif
-    if (a.vecA) hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, true, SPLIT_NT_DEEP128 != 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, false, SPLIT_NT_DEEP128 != 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    if (a.vecA) {
+      UNREAL_LAUNCHED("split_nt 128x128 vec");
+      hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, true, SPLIT_NT_DEEP128 != 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    } else {
+      UNREAL_LAUNCHED("split_nt 128x128 novec");
+      hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, false, SPLIT_NT_DEEP128 != 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    }
   } else {
     a.nbx = (N + 63) / 64; a.nby = (M + 63) / 64;
     const int grid = a.splitk * a.nbx * ((a.nby + 7) / 8 * 8);
@@ -1289,8 +1294,15 @@ static int split_nt_launch(int M, int N, int K, const float* A, int lda, const f
     const int kw = (tiles <= 256 && a.ktiles_per_split >= 8) ? 4 : (tiles <= 512 && a.ktiles_per_split >= 4) ? 2 : 1;
 #define LAUNCH64(VEC_, KW_) hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, VEC_, true, 0, KW_>), dim3(grid), \
                                                dim3(256 * KW_), 0, (hipStream_t)stream, a)
-    if (a.vecA) { if (kw == 4) LAUNCH64(true, 4); else if (kw == 2) LAUNCH64(true, 2); else LAUNCH64(true, 1); }
-    else { if (kw == 4) LAUNCH64(false, 4); else if (kw == 2) LAUNCH64(false, 2); else LAUNCH64(false, 1); }
+    if (a.vecA) {
+      if (kw == 4) { UNREAL_LAUNCHED("split_nt 64x64 vec kw4"); LAUNCH64(true, 4); }
+      else if (kw == 2) { UNREAL_LAUNCHED("split_nt 64x64 vec kw2"); LAUNCH64(true, 2); }
+      else { UNREAL_LAUNCHED("split_nt 64x64 vec kw1"); LAUNCH64(true, 1); }
+    } else {
+      if (kw == 4) { UNREAL_LAUNCHED("split_nt 64x64 novec kw4"); LAUNCH64(false, 4); }
+      else if (kw == 2) { UNREAL_LAUNCHED("split_nt 64x64 novec kw2"); LAUNCH64(false, 2); }
+      else { UNREAL_LAUNCHED("split_nt 64x64 novec kw1"); LAUNCH64(false, 1); }
+    }
 #undef LAUNCH64
   }
   return unreal_launch_status();
@@ -1360,8 +1372,13 @@ int unreal_lstm_step_fwd(int rows, const float* x, int ldx, int Kx, const float*
     a.A = h_prev; a.lda = ld_hprev; a.A2 = nullptr; a.lda2 = 0; a.K1 = 256; a.K1pad = 0;
     a.flags = FLAG_ACCUM;
     a.vecA = vec_h;
-    if (a.vecA) hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, false, true, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    if (a.vecA) {
+      UNREAL_LAUNCHED("lstm_step hoisted vec");
+      hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    } else {
+      UNREAL_LAUNCHED("lstm_step hoisted novec");
+      hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, false, true, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    }
   } else {                               // [x | h_prev] @ the whole kernel in one product
     a.A = x; a.lda = ldx; a.K1 = Kx; a.K1pad = kxpad; a.A2 = h_prev; a.lda2 = ld_hprev;
     a.flags = 0;
@@ -1380,18 +1397,29 @@ int unreal_lstm_step_fwd(int rows, const float* x, int ldx, int Kx, const float*
 #endif
       // more than one tile per CU (the 8192-row steps of the batched replay branches): plain 128 x 128 workgroups, two
       // resident per CU, so one's gate epilogue runs beside the other's K loop
-      if (LSTM_BIG_KW == 1 && (long)a.nbx * a.nby > 256)
+      if (LSTM_BIG_KW == 1 && (long)a.nbx * a.nby > 256) {
+        UNREAL_LAUNCHED("lstm_step 128x128 kw1");
         hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, true, false, 1, 1, true>), dim3(grid128), dim3(256), 0, (hipStream_t)stream, a);
-      else
+      } else {
+        UNREAL_LAUNCHED("lstm_step 128x128 kw2");
         hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, true, false, 1, 2, true>), dim3(grid128), dim3(512), 0, (hipStream_t)stream, a);
+      }
     } else if (a.vecA) {
       // small steps (grouped updates: 512 / 64 rows per launch): 16 x rows/64 tiles of 64 x 64 leave most CUs without a
-      // workgroup and one wave per SIMD on the others -- wave groups share a tile's 17 K tiles (as in the plain products)
+      // workgroup and one wave per SIMD on the others -- wave groups share a tile's 17 K tiles (as in the plain products).
+      // Below 2048 rows there are at most 16 x 32 = 512 tiles, so two wave groups is the fewest this branch needs.
       const long tiles = (long)a.nbx * a.nby;
-      if (tiles <= 256) hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 1, 4, true>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, a);
-      else if (tiles <= 512) hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 1, 2, true>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 1, 1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    } else hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, false, true, 1, 1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+      if (tiles <= 256) {
+        UNREAL_LAUNCHED("lstm_step 64x64 vec kw4");
+        hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 1, 4, true>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, a);
+      } else {
+        UNREAL_LAUNCHED("lstm_step 64x64 vec kw2");
+        hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 1, 2, true>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
+      }
+    } else {
+      UNREAL_LAUNCHED("lstm_step 64x64 novec");
+      hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, false, true, 1, 1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    }
   }
   return unreal_launch_status();
 }
@@ -1422,9 +1450,16 @@ int unreal_lstm_bptt_step(int rows, const float* d_gates, const float* a_absmax,
 #else
   const int kw = tiles <= 256 ? 4 : tiles <= 512 ? 2 : 1;
 #endif
-  if (kw == 4) hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 2, 4>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, a);
-  else if (kw == 2) hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 2, 2>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 2, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  if (kw == 4) {
+    UNREAL_LAUNCHED("bptt kw4");
+    hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 2, 4>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, a);
+  } else if (kw == 2) {
+    UNREAL_LAUNCHED("bptt kw2");
+    hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 2, 2>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
+  } else {
+    UNREAL_LAUNCHED("bptt kw1");
+    hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 2, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  }
   return unreal_launch_status();
 }
 
@@ -1444,8 +1479,13 @@ int unreal_gemm_f32_split_tn(int M, int N, int K, const float* A, int lda, const
   a.splitk = (nk + a.ktiles_per_split - 1) / a.ktiles_per_split;
   const long grid = (long)a.ntx * a.nty * ((a.splitk + 7) / 8 * 8);
   if (grid > 0x7fffffffL) return UNREAL_EINVAL;
-  if (!SPLIT_FORCE_RAGGED && K % BK == 0) hipLaunchKernelGGL(gemm_split_tn_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(gemm_split_tn_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+  if (!SPLIT_FORCE_RAGGED && K % BK == 0) {
+    UNREAL_LAUNCHED("split_tn even");
+    hipLaunchKernelGGL(gemm_split_tn_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+  } else {
+    UNREAL_LAUNCHED("split_tn ragged");
+    hipLaunchKernelGGL(gemm_split_tn_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+  }
   return unreal_launch_status();
 }
 

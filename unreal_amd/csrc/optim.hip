@@ -108,6 +108,7 @@ int unreal_axpy_f32(long n, float alpha, const float* x, float* y, void* stream)
   if (n <= 0 || !x || !y) return UNREAL_EINVAL;
   int blocks = (int)((n + 255) / 256);
   if (blocks > 2048) blocks = 2048;
+  UNREAL_LAUNCHED("axpy");
   hipLaunchKernelGGL(axpy_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, alpha, x, y);
   return unreal_launch_status();
 }
@@ -115,6 +116,7 @@ int unreal_axpy_f32(long n, float alpha, const float* x, float* y, void* stream)
 int unreal_copy_words(long n, const void* src, void* dst, void* stream) {
   if (n <= 0 || !src || !dst || ((((uintptr_t)src) | ((uintptr_t)dst)) & 3)) return UNREAL_EINVAL;
   const int vec = ((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0;
+  UNREAL_LAUNCHED(vec ? "copy_words vec" : "copy_words scalar");
   long work = vec ? (n + 3) / 4 : n;
   int blocks = (int)((work + 255) / 256);
   if (blocks > 2048) blocks = 2048;
@@ -126,6 +128,7 @@ int unreal_copy_words(long n, const void* src, void* dst, void* stream) {
 // norm_out[0] = ||grad||_2 ; scratch must hold 256 floats
 int unreal_grad_norm(const float* grad, long n, float* scratch, float* norm_out, void* stream) {
   if (!grad || n <= 0 || !scratch || !norm_out || (((uintptr_t)grad) & 15)) return UNREAL_EINVAL;
+  UNREAL_LAUNCHED("grad_norm");
   hipLaunchKernelGGL(sumsq_partial_kernel, dim3(NORM_BLOCKS), dim3(256), 0, (hipStream_t)stream, grad, n, scratch);
   hipLaunchKernelGGL(norm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scratch, NORM_BLOCKS, norm_out);
   return unreal_launch_status();

@@ -48,6 +48,15 @@ def _call(name, *a):
     lib().call(name, *a, stream())
 
 
+def last_launch():
+    """Label of the kernel variant the calling thread's most recent launch of this library used ("" before the first),
+    e.g. "split_nt 128x128 vec" or "bptt kw2": host bookkeeping only, no device work and no sync."""
+    import ctypes
+    buf = ctypes.create_string_buffer(64)
+    lib().call("unreal_last_launch", buf, len(buf), None)
+    return buf.value.decode()
+
+
 def kernel_timer_start(name):
     """Bracket every launch of kernel entry point `name` with HIP events on the launch stream."""
     global _TIMER
