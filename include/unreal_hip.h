@@ -75,6 +75,18 @@ int unreal_hostfed_step(int B, int H1, const uint8_t* staged, const int* actions
                         int track_score, int clip_reward, float pc_denom, void* stream);
 int unreal_hostfed_reset(int B, int H1, const int* mask, const uint8_t* staged, int* last_action, float* last_reward,
                          const int* count, uint8_t* frames, void* stream);
+/* gym / Atari environments (environment/gym_environment.py:18-96).  unreal_frame_resize: src [n][Hs][Ws][3] raw uint8
+ * frames -> dst [n][84][84][3], cv2 INTER_LINEAR's half-pixel rule in fp32 rounded to nearest-even (csrc/gym.hip); rows
+ * with mask[i] == 0 are skipped (mask nullable).  unreal_gym_step: unreal_hostfed_step with the gym terminal rule -- the
+ * pixel change of a terminal step is taken against its terminal observation (`staged`), the next slot receives
+ * `reset_staged` (the post-reset observation) where terminal and reset_on_terminal; rewards are stored raw. */
+int unreal_frame_resize(int n, int Hs, int Ws, const uint8_t* src, const int* mask, uint8_t* dst, void* stream);
+int unreal_gym_step(int B, int H1, const uint8_t* staged, const uint8_t* reset_staged, const int* actions,
+                    const float* rewards, const int* terminals, const int* active, int* last_action, float* last_reward,
+                    int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal, int* r_last_action,
+                    float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                    float* score_out, int* score_valid, int reset_on_terminal, int track_score, float pc_denom,
+                    void* stream);
 /* generic _calc_pixel_change on stored uint8 frames: out[n][400] = sum_{4x4x3}|new-old| / denom */
 int unreal_pixel_change_u8(int N, const uint8_t* frames, const int* idx_new, const int* idx_old,
                            float denom, float* out, void* stream);

@@ -19,6 +19,7 @@
 #define C2_CH 32
 #define F2_DIM 2592                                         // 9 * 9 * 32
 #define LSTM_N 256
+#define UNREAL_MAX_ACTIONS 18                               // gym: the full Atari action set
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -71,7 +71,7 @@ __global__ void lstm_gates_bwd_kernel(int rows, const float* __restrict__ dh_abo
   }
 }
 
-// out[row][n] = X[row][:] . W[:, n] + b[n], NOUT <= 8; one wave per row
+// out[row][n] = X[row][:] . W[:, n] + b[n], NOUT <= 19; one wave per row
 template <int NOUT>
 __global__ __launch_bounds__(256) void linear_small_fwd_kernel(int rows, int K, const float* __restrict__ X, int ldx,
                                                                const float* __restrict__ W, const float* __restrict__ b,
@@ -212,6 +212,8 @@ __global__ __launch_bounds__(256) void policy_step_kernel(int rows, const float*
 }
 
 // A3C loss + gradient wrt logits and value.  losses[0..2] += (policy_loss, value_loss, entropy) * loss_scale
+// AMAX bounds A (8: every BASELINE configuration; 18: the full Atari action set)
+template <int AMAX>
 __global__ __launch_bounds__(256) void base_loss_grad_kernel(int rows, int A, const float* __restrict__ pi, int ld_pi,
                                                              const float* __restrict__ v, const int* __restrict__ action,
                                                              const float* __restrict__ adv, const float* __restrict__ R,
@@ -223,7 +225,7 @@ __global__ __launch_bounds__(256) void base_loss_grad_kernel(int rows, int A, co
   if (r < rows) {
     const bool on = active[r] != 0;
     const float* p = pi + (size_t)r * ld_pi;
-    float g[8], lp[8];
+    float g[AMAX], lp[AMAX];
     float dot = 0.f, H = 0.f;
     const int a_t = action[r];
     const float ad = adv[r];
@@ -381,10 +383,12 @@ int unreal_linear_small_fwd(int rows, int K, int NOUT, const float* X, int ldx, 
   if (rows <= 0 || K <= 0 || !X || !W || !b || !out || ldx < K || ldo < NOUT) return UNREAL_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   switch (NOUT) {
-    case 1: return launch_small_fwd<1>(rows, K, X, ldx, W, b, out, ldo, st);
-    case 3: return launch_small_fwd<3>(rows, K, X, ldx, W, b, out, ldo, st);
-    case 4: return launch_small_fwd<4>(rows, K, X, ldx, W, b, out, ldo, st);
-    case 6: return launch_small_fwd<6>(rows, K, X, ldx, W, b, out, ldo, st);
+#define SMALL_FWD(n) case n: return launch_small_fwd<n>(rows, K, X, ldx, W, b, out, ldo, st);
+    SMALL_FWD(1) SMALL_FWD(3) SMALL_FWD(4) SMALL_FWD(6)                    // BASELINE heads: value, rp, A = 3, 4, 6
+    SMALL_FWD(2) SMALL_FWD(5) SMALL_FWD(7) SMALL_FWD(8) SMALL_FWD(9)       // policy logits of any A <= 18 (gym)
+    SMALL_FWD(10) SMALL_FWD(11) SMALL_FWD(12) SMALL_FWD(13) SMALL_FWD(14) SMALL_FWD(15) SMALL_FWD(16) SMALL_FWD(17)
+    SMALL_FWD(18) SMALL_FWD(19)
+#undef SMALL_FWD
     default: return UNREAL_EINVAL;
   }
 }
@@ -396,18 +400,18 @@ int unreal_linear_small_bwd(int rows, int K, int NOUT, const float* X, int ldx, 
   if (dX && !W) return UNREAL_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   switch (NOUT) {
-    case 1: return launch_small_bwd<1>(rows, K, X, ldx, dO, ldo, W, dX, lddx, accumulate_dx, dW, dw_stride_k, dw_stride_n, db, st);
-    case 3: return launch_small_bwd<3>(rows, K, X, ldx, dO, ldo, W, dX, lddx, accumulate_dx, dW, dw_stride_k, dw_stride_n, db, st);
-    case 4: return launch_small_bwd<4>(rows, K, X, ldx, dO, ldo, W, dX, lddx, accumulate_dx, dW, dw_stride_k, dw_stride_n, db, st);
-    case 5: return launch_small_bwd<5>(rows, K, X, ldx, dO, ldo, W, dX, lddx, accumulate_dx, dW, dw_stride_k, dw_stride_n, db, st);
-    case 6: return launch_small_bwd<6>(rows, K, X, ldx, dO, ldo, W, dX, lddx, accumulate_dx, dW, dw_stride_k, dw_stride_n, db, st);
-    case 7: return launch_small_bwd<7>(rows, K, X, ldx, dO, ldo, W, dX, lddx, accumulate_dx, dW, dw_stride_k, dw_stride_n, db, st);
+#define SMALL_BWD(n) \
+    case n: return launch_small_bwd<n>(rows, K, X, ldx, dO, ldo, W, dX, lddx, accumulate_dx, dW, dw_stride_k, dw_stride_n, db, st);
+    SMALL_BWD(1) SMALL_BWD(3) SMALL_BWD(4) SMALL_BWD(5) SMALL_BWD(6) SMALL_BWD(7)
+    SMALL_BWD(2) SMALL_BWD(8) SMALL_BWD(9) SMALL_BWD(10) SMALL_BWD(11) SMALL_BWD(12) SMALL_BWD(13)   // any A <= 18 (gym)
+    SMALL_BWD(14) SMALL_BWD(15) SMALL_BWD(16) SMALL_BWD(17) SMALL_BWD(18) SMALL_BWD(19)
+#undef SMALL_BWD
     default: return UNREAL_EINVAL;
   }
 }
 
 int unreal_softmax_sample(int rows, int A, float* logits_pi, int ld, const double* u, int* action, void* stream) {
-  if (rows <= 0 || A <= 0 || A > 8 || !logits_pi || ld < A) return UNREAL_EINVAL;
+  if (rows <= 0 || A <= 0 || A > UNREAL_MAX_ACTIONS || !logits_pi || ld < A) return UNREAL_EINVAL;
   hipLaunchKernelGGL(softmax_sample_kernel, GRID1(rows), rows, A, logits_pi, ld, u, action);
   return unreal_launch_status();
 }
@@ -418,9 +422,13 @@ int unreal_policy_step(int rows, int A, const float* X, int ldx, const float* Wp
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((rows + 3) / 4), block(256);
   switch (A) {
-    case 3: hipLaunchKernelGGL((policy_step_kernel<3>), grid, block, 0, st, rows, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, action); break;
-    case 4: hipLaunchKernelGGL((policy_step_kernel<4>), grid, block, 0, st, rows, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, action); break;
-    case 6: hipLaunchKernelGGL((policy_step_kernel<6>), grid, block, 0, st, rows, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, action); break;
+#define POLICY_STEP(a) \
+    case a: hipLaunchKernelGGL((policy_step_kernel<a>), grid, block, 0, st, rows, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, action); break;
+    POLICY_STEP(3) POLICY_STEP(4) POLICY_STEP(6)                                                   // BASELINE
+    POLICY_STEP(2) POLICY_STEP(5) POLICY_STEP(7) POLICY_STEP(8) POLICY_STEP(9) POLICY_STEP(10)    // gym, A <= 18
+    POLICY_STEP(11) POLICY_STEP(12) POLICY_STEP(13) POLICY_STEP(14) POLICY_STEP(15) POLICY_STEP(16) POLICY_STEP(17)
+    POLICY_STEP(18)
+#undef POLICY_STEP
     default: return UNREAL_EINVAL;
   }
   return unreal_launch_status();
@@ -429,10 +437,15 @@ int unreal_policy_step(int rows, int A, const float* X, int ldx, const float* Wp
 int unreal_base_loss_grad(int rows, int A, const float* pi, int ld_pi, const float* v, const int* action,
                           const float* adv, const float* R, const int* active, float entropy_beta, float grad_scale,
                           float* dlogits, float* dv, float* losses, void* stream) {
-  if (rows <= 0 || A <= 0 || A > 8 || !pi || !v || !action || !adv || !R || !active || !dlogits || !dv || !losses)
+  if (rows <= 0 || A <= 0 || A > UNREAL_MAX_ACTIONS || !pi || !v || !action || !adv || !R || !active || !dlogits || !dv ||
+      !losses)
     return UNREAL_EINVAL;
-  hipLaunchKernelGGL(base_loss_grad_kernel, GRID1(rows), rows, A, pi, ld_pi, v, action, adv, R, active, entropy_beta,
-                     grad_scale, dlogits, dv, losses);
+  if (A <= 8)
+    hipLaunchKernelGGL(base_loss_grad_kernel<8>, GRID1(rows), rows, A, pi, ld_pi, v, action, adv, R, active, entropy_beta,
+                       grad_scale, dlogits, dv, losses);
+  else
+    hipLaunchKernelGGL(base_loss_grad_kernel<UNREAL_MAX_ACTIONS>, GRID1(rows), rows, A, pi, ld_pi, v, action, adv, R, active,
+                       entropy_beta, grad_scale, dlogits, dv, losses);
   return unreal_launch_status();
 }
 

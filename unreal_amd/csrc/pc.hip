@@ -785,6 +785,347 @@ __global__ __launch_bounds__(256, TrainLds<COT>::WGS) void pc_deconv_train_kerne
   if (gtid == 0) atomicAdd(p.loss, (((red[44] + red[45]) + red[46]) + red[47]) * p.grad_scale);
 }
 
+// ---- 9 <= 1 + A <= 19 output channels (gym: up to the 18 Atari actions) -----------------------------------------------
+// The packed forward above has 2 column tiles (4 CO <= 32) and the backward's d_dec planes hold 8 channels per position;
+// both layouts are built around CO <= 8.  For the wide heads the three passes run in fp32 on the VALU instead, one frame
+// per 256-thread workgroup, every operand of the frame in LDS -- no operand splitting and no power-of-two scales (the
+// absmax slots are still committed for the consumers downstream).  This is a reach path for the Atari action set, not a
+// tuned one: the 19-channel deconvolutions are 4x the MACs of the maze's and about one LDS read per FMA.
+//   forward  thread slot s = gtid + 256h (< 400) <-> output parity par = s / 100, base position m = s % 100: a wave
+//            covers one or two parities, so its weight reads are (nearly) one broadcast address;
+//   dgrad    thread <-> (ci = gtid & 31, positions pg + 8j), weight reads stride 19 over the lanes (odd: no conflicts);
+//   wgrad    thread <-> (ci, (tap, co) entries pg + 8j, j < 38): the dW tile stays in registers across the frames.
+constexpr int WIDE_CO = UNREAL_MAX_ACTIONS + 1;      // 19
+constexpr int WIDE_HS_LD = 33;                       // hp fp32 [82][33]: row 81 = zeros (the out-of-image taps)
+constexpr int WIDE_HS_BYTES = 82 * WIDE_HS_LD * 4;   // 10,824
+constexpr int WIDE_WT_LD = 32 * WIDE_CO;             // weights fp32 [16 taps][32 ci][19 co]
+constexpr int WIDE_WS_BYTES = 16 * WIDE_WT_LD * 4;   // 38,912
+constexpr int WIDE_DD_BYTES = PC_CELLS * WIDE_CO * 4;   // d_dec fp32 [400][19]: 30,400
+constexpr int WIDE_WG_ENTRIES = (16 * WIDE_CO + 7) / 8;  // 38 (tap, co) entries per thread
+// forward: hp + weights = 49.7 KB -> THREE workgroups per CU; training / backward: + d_dec = 80.1 KB -> TWO per CU
+constexpr int WIDE_FWD_BYTES = WIDE_HS_BYTES + WIDE_WS_BYTES;
+constexpr int WIDE_TRAIN_BYTES = WIDE_FWD_BYTES + WIDE_DD_BYTES;
+static_assert(3 * (WIDE_FWD_BYTES + 64) <= 160 * 1024, "three wide forward workgroups must fit one CU's LDS");
+static_assert(2 * (WIDE_TRAIN_BYTES + 192) <= 160 * 1024, "two wide training workgroups must fit one CU's LDS");
+
+__device__ __forceinline__ void wide_stage_weights(const float* __restrict__ Wv, const float* __restrict__ Wa, int A,
+                                                   float* ws) {
+  for (int e = threadIdx.x; e < 16 * 32 * WIDE_CO; e += 256) {
+    const int co = e % WIDE_CO, ci = (e / WIDE_CO) & 31, tap = e / (32 * WIDE_CO);
+    float v = 0.f;
+    if (co == 0) v = Wv[tap * 32 + ci];
+    else if (co <= A) v = Wa[(tap * A + (co - 1)) * 32 + ci];
+    ws[e] = v;
+  }
+}
+
+// hp of one frame [81][32] -> hs rows of 33 (row 81 is zeroed once by the caller)
+__device__ __forceinline__ void wide_stage_hp(const float* __restrict__ src, float* hs) {
+  const f32x4* s4 = reinterpret_cast<const f32x4*>(src);
+  for (int id = threadIdx.x; id < C2_POS * 8; id += 256) {
+    const f32x4 v = s4[id];
+    float* d = hs + (id >> 3) * WIDE_HS_LD + (id & 7) * 4;
+    d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+  }
+}
+
+// pre-activations of output slot s (< 400): out[co] = bias[co] + sum_{4 taps, ci} hp[row][ci] W[tap][co][ci]; returns pos
+__device__ __forceinline__ int wide_deconv_slot(const float* hs, const float* ws, int s, int CO,
+                                                const float (&bias)[WIDE_CO], float (&out)[WIDE_CO]) {
+  const int par = s / 100, m = s - 100 * par, a = m / 10, b = m - 10 * (m / 10);
+  const int pa = par >> 1, pb = par & 1;
+#pragma unroll
+  for (int co = 0; co < WIDE_CO; ++co) out[co] = 0.f;
+#pragma unroll
+  for (int dd = 0; dd < 4; ++dd) {
+    const int da = dd >> 1, db = dd & 1, y = a - da, x = b - db;
+    const int row = (y >= 0 && x >= 0 && y < 9 && x < 9) ? y * 9 + x : C2_POS;
+    const float* h = hs + row * WIDE_HS_LD;
+    const float* w = ws + ((pa + 2 * da) * 4 + pb + 2 * db) * WIDE_WT_LD;
+    for (int ci = 0; ci < 32; ++ci) {
+      const float hv = h[ci];
+#pragma unroll
+      for (int co = 0; co < WIDE_CO; ++co)
+        if (co < CO) out[co] += hv * w[ci * WIDE_CO + co];
+    }
+  }
+#pragma unroll
+  for (int co = 0; co < WIDE_CO; ++co) out[co] += bias[co];
+  return (2 * a + pa) * 20 + 2 * b + pb;
+}
+
+// the dueling combine of pc_deconv_fwd_kernel on one position's pre-activations d[0..A]: Q-max, or loss and d_dec
+__device__ __forceinline__ float wide_dueling(const float (&d)[WIDE_CO], int A, int act, bool on, float tg, float lambda,
+                                              float grad_scale, float* qmax, float& loss_acc, float (&dd)[WIDE_CO]) {
+  const float vpre = d[0];
+  const float V = fmaxf(vpre, 0.f);
+  float mean = 0.f, aact = 0.f;
+#pragma unroll
+  for (int k = 0; k < WIDE_CO - 1; ++k) {
+    const float ad = k < A ? fmaxf(d[1 + k], 0.f) : 0.f;
+    mean += ad;
+    aact = (k == act) ? ad : aact;
+  }
+  mean /= (float)A;
+  if (qmax) {
+    float mx = V + fmaxf(d[1], 0.f) - mean;
+#pragma unroll
+    for (int k = 1; k < WIDE_CO - 1; ++k)
+      if (k < A) mx = fmaxf(mx, V + fmaxf(d[1 + k], 0.f) - mean);
+    *qmax = mx;
+  }
+  const float diff = tg - (V + aact - mean);
+  const float dq = on ? -lambda * diff * grad_scale : 0.f;
+  if (on) loss_acc += 0.5f * lambda * diff * diff;
+  dd[0] = vpre > 0.f ? dq : 0.f;
+#pragma unroll
+  for (int k = 0; k < WIDE_CO - 1; ++k)
+    dd[1 + k] = (k < A && d[1 + k] > 0.f) ? dq * (((k == act) ? 1.f : 0.f) - 1.f / (float)A) : 0.f;
+  return fabsf(dq);                     // |d_dec| <= |dq|
+}
+
+// dgrad of one frame (dds [400][19] and hs staged): d_hp[pos][ci] with the ReLU mask of pc_fc1 (hp > 0); returns max |d_hp|
+__device__ __forceinline__ float wide_dgrad_frame(const float* hs, const float* dds, const float* ws, int CO,
+                                                  float* __restrict__ d_hp_frame, float dhp_max) {
+  const int ci = threadIdx.x & 31, pg = threadIdx.x >> 5;
+  float acc[11];
+#pragma unroll
+  for (int j = 0; j < 11; ++j) acc[j] = 0.f;
+  for (int tap = 0; tap < 16; ++tap) {
+    const int ky = tap >> 2, kx = tap & 3;
+    const float* w = ws + tap * WIDE_WT_LD + ci * WIDE_CO;
+    for (int co = 0; co < CO; ++co) {
+      const float wv = w[co];
+#pragma unroll
+      for (int j = 0; j < 11; ++j) {
+        const int pos = min(pg + 8 * j, C2_POS - 1);
+        const int y = pos / 9, x = pos - 9 * (pos / 9);
+        acc[j] += dds[((2 * y + ky) * 20 + 2 * x + kx) * WIDE_CO + co] * wv;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 11; ++j) {
+    const int pos = pg + 8 * j;
+    if (pos < C2_POS) {
+      const float v = hs[pos * WIDE_HS_LD + ci] > 0.f ? acc[j] : 0.f;
+      d_hp_frame[pos * 32 + ci] = v;
+      dhp_max = fmaxf(dhp_max, fabsf(v));
+    }
+  }
+  return dhp_max;
+}
+
+// wgrad of one frame into aw: aw[j] += sum_pos d_dec[2y+ky][2x+kx][co] hp[pos][ci] for entry e = pg + 8j = tap * CO + co;
+// off[j] = the entry's offset (ky * 20 + kx) * 19 + co into dds (0 for e >= 16 CO: accumulated, never committed)
+__device__ __forceinline__ void wide_wgrad_frame(const float* hs, const float* dds, const int (&off)[WIDE_WG_ENTRIES],
+                                                 float (&aw)[WIDE_WG_ENTRIES]) {
+  const int ci = threadIdx.x & 31;
+  for (int pos = 0; pos < C2_POS; ++pos) {
+    const int y = pos / 9, x = pos - 9 * (pos / 9);
+    const float h = hs[pos * WIDE_HS_LD + ci];
+    const float* d = dds + (2 * y * 20 + 2 * x) * WIDE_CO;
+#pragma unroll
+    for (int j = 0; j < WIDE_WG_ENTRIES; ++j) aw[j] += d[off[j]] * h;
+  }
+}
+
+__device__ __forceinline__ void wide_wgrad_offsets(int CO, int (&off)[WIDE_WG_ENTRIES]) {
+  const int pg = threadIdx.x >> 5;
+#pragma unroll
+  for (int j = 0; j < WIDE_WG_ENTRIES; ++j) {
+    const int e = pg + 8 * j;
+    const int tap = e / CO, co = e - CO * (e / CO);
+    off[j] = e < 16 * CO ? ((tap >> 2) * 20 + (tap & 3)) * WIDE_CO + co : 0;
+  }
+}
+
+// end of a workgroup: dW (one atomic per element), the bias gradient and max |d_hp| (one atomic / commit per workgroup)
+__device__ __forceinline__ void wide_commit_grads(const float (&aw)[WIDE_WG_ENTRIES], const float (&adbk)[WIDE_CO],
+                                                  float dhp_max, int A, float* dWv, float* dWa, float* dbv, float* dba,
+                                                  float* dhp_absmax, float* red) {
+  const int gtid = threadIdx.x, lane = gtid & 63, gw = gtid >> 6, ci = gtid & 31, pg = gtid >> 5, CO = 1 + A;
+#pragma unroll
+  for (int j = 0; j < WIDE_WG_ENTRIES; ++j) {
+    const int e = pg + 8 * j;
+    if (e < 16 * CO) {
+      const int tap = e / CO, co = e - CO * (e / CO);
+      if (co == 0) atomicAdd(dWv + tap * 32 + ci, aw[j]);
+      else atomicAdd(dWa + (tap * A + (co - 1)) * 32 + ci, aw[j]);
+    }
+  }
+  __syncthreads();                       // red may alias operands the other waves were still reading
+#pragma unroll
+  for (int k = 0; k < WIDE_CO; ++k) {
+    const float v = wave_sum(adbk[k]);
+    if (lane == 0) red[gw * WIDE_CO + k] = v;
+  }
+  dhp_max = wave_max(dhp_max);
+  if (lane == 0) red[4 * WIDE_CO + gw] = dhp_max;
+  __syncthreads();
+  if (gtid < CO) {
+    const float v = ((red[gtid] + red[WIDE_CO + gtid]) + red[2 * WIDE_CO + gtid]) + red[3 * WIDE_CO + gtid];
+    if (gtid == 0) atomicAdd(dbv, v);
+    else atomicAdd(dba + (gtid - 1), v);
+  }
+  const float* wmx = red + 4 * WIDE_CO;
+  if (gw == 0) absmax_commit(dhp_absmax, fmaxf(fmaxf(wmx[0], wmx[1]), fmaxf(wmx[2], wmx[3])));
+}
+
+__device__ __forceinline__ void wide_bias(const float* __restrict__ bv, const float* __restrict__ ba, int CO,
+                                          float (&bias)[WIDE_CO]) {
+#pragma unroll
+  for (int co = 0; co < WIDE_CO; ++co) bias[co] = co == 0 ? bv[0] : (co < CO ? ba[co - 1] : 0.f);
+}
+
+__global__ __launch_bounds__(256, 3) void pc_deconv_fwd_wide_kernel(PcFwdArgs p) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[WIDE_FWD_BYTES];
+  __shared__ float s_red[8];
+  float* hs = reinterpret_cast<float*>(smem);
+  float* ws = reinterpret_cast<float*>(smem + WIDE_HS_BYTES);
+  const int gtid = threadIdx.x, lane = gtid & 63, gw = gtid >> 6;
+  const int A = p.A, CO = 1 + p.A;
+  wide_stage_weights(p.Wv, p.Wa, A, ws);
+  for (int e = gtid; e < WIDE_HS_LD; e += 256) hs[C2_POS * WIDE_HS_LD + e] = 0.f;
+  float bias[WIDE_CO];
+  wide_bias(p.bv, p.ba, CO, bias);
+  float loss_acc = 0.f, dd_max = 0.f;
+  for (int n = blockIdx.x; n < p.N; n += gridDim.x) {
+    __syncthreads();  // the previous frame's reads of hs are done
+    wide_stage_hp(p.hp + (size_t)n * F2_DIM, hs);
+    __syncthreads();
+    const int act = p.d_dec ? p.action[n] : 0;
+    const bool on = p.d_dec ? p.mask[n] != 0 : false;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int s = gtid + 256 * h;
+      if (s < PC_CELLS) {
+        float d[WIDE_CO], dd[WIDE_CO];
+        const int pos = wide_deconv_slot(hs, ws, s, CO, bias, d);
+        const float tg = p.d_dec ? p.target[(size_t)n * PC_CELLS + pos] : 0.f;
+        float ignored = 0.f;
+        const float m = wide_dueling(d, A, act, on, tg, p.lambda, p.grad_scale,
+                                     p.qmax ? p.qmax + (size_t)n * PC_CELLS + pos : nullptr, p.d_dec ? loss_acc : ignored, dd);
+        if (p.d_dec) {
+          dd_max = fmaxf(dd_max, m);
+          float* o = p.d_dec + ((size_t)n * PC_CELLS + pos) * CO;
+#pragma unroll
+          for (int k = 0; k < WIDE_CO; ++k)
+            if (k < CO) o[k] = dd[k];
+        }
+      }
+    }
+  }
+  loss_acc = wave_sum(loss_acc);
+  dd_max = wave_max(dd_max);
+  if (lane == 0) { s_red[gw] = loss_acc; s_red[4 + gw] = dd_max; }
+  __syncthreads();
+  if (gw == 0) {
+    if (p.loss && lane == 0) atomicAdd(p.loss, (((s_red[0] + s_red[1]) + s_red[2]) + s_red[3]) * p.grad_scale);
+    if (p.ddec_absmax) absmax_commit(p.ddec_absmax, fmaxf(fmaxf(s_red[4], s_red[5]), fmaxf(s_red[6], s_red[7])));
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void pc_deconv_bwd_wide_kernel(PcBwdArgs p) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[WIDE_TRAIN_BYTES];
+  __shared__ float s_red[5 * WIDE_CO];
+  float* hs = reinterpret_cast<float*>(smem);
+  float* ws = reinterpret_cast<float*>(smem + WIDE_HS_BYTES);
+  float* dds = reinterpret_cast<float*>(smem + WIDE_FWD_BYTES);
+  const int gtid = threadIdx.x;
+  const int A = p.A, CO = 1 + p.A;
+  wide_stage_weights(p.Wv, p.Wa, A, ws);
+  for (int e = gtid; e < WIDE_HS_LD; e += 256) hs[C2_POS * WIDE_HS_LD + e] = 0.f;
+  int off[WIDE_WG_ENTRIES];
+  wide_wgrad_offsets(CO, off);
+  float aw[WIDE_WG_ENTRIES], adbk[WIDE_CO];
+#pragma unroll
+  for (int j = 0; j < WIDE_WG_ENTRIES; ++j) aw[j] = 0.f;
+#pragma unroll
+  for (int k = 0; k < WIDE_CO; ++k) adbk[k] = 0.f;
+  float dhp_max = 0.f;
+  for (int n = blockIdx.x; n < p.N; n += gridDim.x) {
+    __syncthreads();  // the previous frame's reads of hs / dds are done
+    wide_stage_hp(p.hp + (size_t)n * F2_DIM, hs);
+    const float* src = p.d_dec + (size_t)n * PC_CELLS * CO;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int pos = gtid + 256 * h;
+      if (pos < PC_CELLS) {
+#pragma unroll
+        for (int k = 0; k < WIDE_CO; ++k) {
+          const float v = k < CO ? src[pos * CO + k] : 0.f;
+          dds[pos * WIDE_CO + k] = v;
+          adbk[k] += v;
+        }
+      }
+    }
+    __syncthreads();
+    dhp_max = wide_dgrad_frame(hs, dds, ws, CO, p.d_hp + (size_t)n * F2_DIM, dhp_max);
+    wide_wgrad_frame(hs, dds, off, aw);
+  }
+  wide_commit_grads(aw, adbk, dhp_max, A, p.dWv, p.dWa, p.dbv, p.dba, p.dhp_absmax, s_red);
+}
+
+__global__ __launch_bounds__(256, 2) void pc_deconv_train_wide_kernel(PcTrainArgs p) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[WIDE_TRAIN_BYTES];
+  __shared__ float s_red[5 * WIDE_CO];
+  float* hs = reinterpret_cast<float*>(smem);
+  float* ws = reinterpret_cast<float*>(smem + WIDE_HS_BYTES);
+  float* dds = reinterpret_cast<float*>(smem + WIDE_FWD_BYTES);
+  const int gtid = threadIdx.x, lane = gtid & 63, gw = gtid >> 6;
+  const int A = p.A, CO = 1 + p.A;
+  wide_stage_weights(p.Wv, p.Wa, A, ws);
+  for (int e = gtid; e < WIDE_HS_LD; e += 256) hs[C2_POS * WIDE_HS_LD + e] = 0.f;
+  float bias[WIDE_CO];
+  wide_bias(p.bv, p.ba, CO, bias);
+  int off[WIDE_WG_ENTRIES];
+  wide_wgrad_offsets(CO, off);
+  float aw[WIDE_WG_ENTRIES], adbk[WIDE_CO];
+#pragma unroll
+  for (int j = 0; j < WIDE_WG_ENTRIES; ++j) aw[j] = 0.f;
+#pragma unroll
+  for (int k = 0; k < WIDE_CO; ++k) adbk[k] = 0.f;
+  float dhp_max = 0.f, loss_acc = 0.f;
+  for (int n = blockIdx.x; n < p.N; n += gridDim.x) {
+    __syncthreads();  // the previous frame's reads of hs / dds are done
+    wide_stage_hp(p.hp + (size_t)n * F2_DIM, hs);
+    __syncthreads();
+    const int act = p.action[n];
+    const bool on = p.mask[n] != 0;
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {       // not unrolled: the wgrad tile holds 76 registers across the loop
+      const int s = gtid + 256 * h;
+      if (s < PC_CELLS) {
+        float d[WIDE_CO], dd[WIDE_CO];
+        const int pos = wide_deconv_slot(hs, ws, s, CO, bias, d);
+        wide_dueling(d, A, act, on, p.target[(size_t)n * PC_CELLS + pos], p.lambda, p.grad_scale, nullptr, loss_acc, dd);
+#pragma unroll
+        for (int k = 0; k < WIDE_CO; ++k) {
+          dds[pos * WIDE_CO + k] = dd[k];
+          adbk[k] += dd[k];
+        }
+        if (p.d_dec) {
+          float* o = p.d_dec + ((size_t)n * PC_CELLS + pos) * CO;
+#pragma unroll
+          for (int k = 0; k < WIDE_CO; ++k)
+            if (k < CO) o[k] = dd[k];
+        }
+      }
+    }
+    __syncthreads();  // d_dec of the frame staged
+    dhp_max = wide_dgrad_frame(hs, dds, ws, CO, p.d_hp + (size_t)n * F2_DIM, dhp_max);
+    wide_wgrad_frame(hs, dds, off, aw);
+  }
+  loss_acc = wave_sum(loss_acc);
+  __syncthreads();
+  if (lane == 0) s_red[gw] = loss_acc;
+  __syncthreads();
+  const float loss_wg = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+  wide_commit_grads(aw, adbk, dhp_max, A, p.dWv, p.dWa, p.dbv, p.dba, p.dhp_absmax, s_red);
+  if (gtid == 0) atomicAdd(p.loss, loss_wg * p.grad_scale);
+}
+
 }  // namespace
 
 extern "C" {
@@ -793,13 +1134,17 @@ int unreal_pc_deconv_fwd(int N, int A, const float* hp, const float* hp_absmax, 
                          const float* Wa, const float* ba, float* qmax, const int* action, const float* target,
                          const int* mask, float lambda, float grad_scale, float* d_dec, float* ddec_absmax, float* loss,
                          void* stream) {
-  if (N <= 0 || A <= 0 || A > 7 || !hp || !hp_absmax || !Wv || !bv || !Wa || !ba) return UNREAL_EINVAL;
+  if (N <= 0 || A <= 0 || A > UNREAL_MAX_ACTIONS || !hp || !hp_absmax || !Wv || !bv || !Wa || !ba) return UNREAL_EINVAL;
   if (!qmax && !d_dec) return UNREAL_EINVAL;
   if (d_dec && (!action || !target || !mask || !loss)) return UNREAL_EINVAL;
   if ((((uintptr_t)hp) | ((uintptr_t)d_dec)) & 15) return UNREAL_EINVAL;
   PcFwdArgs p{N, A, hp, hp_absmax, Wv, bv, Wa, ba, qmax, action, target, mask, lambda, grad_scale, d_dec,
               d_dec ? ddec_absmax : nullptr, d_dec ? loss : nullptr};
   hipStream_t st = (hipStream_t)stream;
+  if (A > 7) {                     // 9 .. 19 channels: the fp32 wide kernel, three workgroups per CU
+    hipLaunchKernelGGL(pc_deconv_fwd_wide_kernel, dim3(min(N, 256 * 3)), dim3(256), 0, st, p);
+    return unreal_launch_status();
+  }
   // one frame per workgroup at a time; as many workgroups as fit the chip (3 per CU at 1 + A <= 7 channels)
 #define PC_FWD(COT) hipLaunchKernelGGL(pc_deconv_fwd_kernel<COT>, dim3(min(N, 256 * FwdLds<COT>::WGS)), dim3(256), 0, st, p)
   switch (1 + A) {
@@ -815,12 +1160,16 @@ int unreal_pc_deconv_fwd(int N, int A, const float* hp, const float* hp_absmax, 
 int unreal_pc_deconv_bwd(int N, int A, const float* hp, const float* hp_absmax, const float* d_dec, const float* ddec_absmax,
                          const float* Wv, const float* Wa, float* d_hp, float* dhp_absmax, float* dWv, float* dbv, float* dWa,
                          float* dba, void* stream) {
-  if (N <= 0 || A <= 0 || A > 7 || !hp || !hp_absmax || !d_dec || !ddec_absmax || !Wv || !Wa || !d_hp || !dWv || !dbv ||
+  if (N <= 0 || A <= 0 || A > UNREAL_MAX_ACTIONS || !hp || !hp_absmax || !d_dec || !ddec_absmax || !Wv || !Wa || !d_hp || !dWv || !dbv ||
       !dWa || !dba)
     return UNREAL_EINVAL;
   if ((((uintptr_t)hp) | ((uintptr_t)d_dec) | ((uintptr_t)d_hp)) & 15) return UNREAL_EINVAL;
   PcBwdArgs p{N, A, hp, hp_absmax, d_dec, ddec_absmax, Wv, Wa, d_hp, dWv, dbv, dWa, dba, dhp_absmax};
   int blocks = min(N, 512);
+  if (A > 7) {                     // 9 .. 19 channels: the fp32 wide kernel, two workgroups per CU
+    hipLaunchKernelGGL(pc_deconv_bwd_wide_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    return unreal_launch_status();
+  }
   hipLaunchKernelGGL(pc_deconv_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
   return unreal_launch_status();
 }
@@ -831,13 +1180,18 @@ int unreal_pc_deconv_train(int N, int A, const float* hp, const float* hp_absmax
                            const float* Wa, const float* ba, const int* action, const float* target, const int* mask,
                            float lambda, float grad_scale, float* loss, float* d_hp, float* dhp_absmax, float* dWv, float* dbv,
                            float* dWa, float* dba, float* d_dec, void* stream) {
-  if (N <= 0 || A <= 0 || A > 7 || !hp || !hp_absmax || !Wv || !bv || !Wa || !ba || !action || !target || !mask || !loss ||
+  if (N <= 0 || A <= 0 || A > UNREAL_MAX_ACTIONS || !hp || !hp_absmax || !Wv || !bv || !Wa || !ba || !action || !target ||
+      !mask || !loss ||
       !d_hp || !dWv || !dbv || !dWa || !dba)
     return UNREAL_EINVAL;
   if ((((uintptr_t)hp) | ((uintptr_t)d_hp)) & 15) return UNREAL_EINVAL;
   PcTrainArgs p{N, A, hp, hp_absmax, Wv, bv, Wa, ba, action, target, mask, lambda, grad_scale, loss, d_hp, dhp_absmax,
                 dWv, dbv, dWa, dba, d_dec};
   hipStream_t st = (hipStream_t)stream;
+  if (A > 7) {                     // 9 .. 19 channels: the fp32 wide kernel, two workgroups per CU
+    hipLaunchKernelGGL(pc_deconv_train_wide_kernel, dim3(min(N, 256 * 2)), dim3(256), 0, st, p);
+    return unreal_launch_status();
+  }
 #define PC_TRAIN(COT) \
   hipLaunchKernelGGL(pc_deconv_train_kernel<COT>, dim3(min(N, 256 * TrainLds<COT>::WGS)), dim3(256), 0, st, p)
   switch (1 + A) {

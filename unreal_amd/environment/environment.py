@@ -1,7 +1,8 @@
 """Environment factory with the reference's surface (/root/reference/environment/environment.py:11-102).
 
 Only the maze is a device environment; lab / indoor actors are HOST-FED (hostfed_environment.py) by simulator objects
-the caller supplies, because deepmind_lab / minos / gym are not in the image."""
+the caller supplies, because deepmind_lab / minos / gym are not in the image.  Gym actors are host-fed through
+gym_environment.GymBatchSimulator (any object with gym's reset / step API)."""
 
 
 class Environment(object):
@@ -9,10 +10,19 @@ class Environment(object):
     LOG_DIR = None
     # stands in for minos.config.sim_config (indoor_environment.py:27-29): env_name -> {'objective_size': n}
     INDOOR_CONFIG = {}
+    # stands in for gym.make(env_name).action_space.n (gym_environment.py:55-60): env_name -> action count
+    GYM_CONFIG = {}
 
     @staticmethod
     def register_indoor_config(env_name, objective_size):
         Environment.INDOOR_CONFIG[env_name] = {'objective_size': int(objective_size)}
+
+    @staticmethod
+    def register_gym_config(env_name, action_size):
+        a = int(action_size)
+        if not 2 <= a <= 18:
+            raise ValueError("gym action_size %d: the device heads support 2..18 actions" % a)
+        Environment.GYM_CONFIG[env_name] = a
 
     @staticmethod
     def create_environment(env_type, env_name, termination_time=50.0, env_args=None, thread_index=0):
@@ -32,6 +42,10 @@ class Environment(object):
             Environment.action_size = 6      # lab_environment.py:57-73
         elif env_type == 'indoor':
             Environment.action_size = 3      # indoor_environment.py:16-20
+        elif env_type == 'gym':
+            if env_name not in Environment.GYM_CONFIG:
+                raise KeyError("gym env %r: call Environment.register_gym_config(name, action_size) first" % env_name)
+            Environment.action_size = Environment.GYM_CONFIG[env_name]
         else:
             raise NotImplementedError(env_type)
         return Environment.action_size

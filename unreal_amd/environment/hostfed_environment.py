@@ -9,7 +9,13 @@ batched device path: frames are stored as uint8 and the encoder applies frame_sc
 With objective_size > 0 it is the MINOS wrapper contract of /root/reference/environment/indoor_environment.py:63-139
 instead: the simulator also returns a measurement vector per actor (reset -> (frames, objectives),
 step -> (frames, rewards, terminals, objectives)), stored beside the frame in the ring and concatenated into the LSTM
-input; rewards are divided by termination_time (:111) and not clipped."""
+input; rewards are divided by termination_time (:111) and not clipped.
+
+With raw_frame_shape = (Hs, Ws) it is the gym contract of /root/reference/environment/gym_environment.py:18-96 instead
+(gym_environment.GymBatchSimulator): the simulator returns RAW frames [n, Hs, Ws, 3] which are staged as they are and
+resized to 84 x 84 on the device (ops.frame_resize); step returns the TERMINAL observation where terminal, the
+environment then resets those actors (sim.reset(mask)) and commits with the gym terminal rule (ops.gym_step: pixel
+change against the terminal observation, the post-reset observation into the next slot); rewards are not clipped."""
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -62,19 +68,20 @@ STAGE_CHUNKS = int(os.environ.get("UNREAL_STAGE_CHUNKS", 1))
 
 
 def _stage_and_copy(h_frames, frames, staged):
-    """h_frames (pinned [n,84,84,3]) <- frames, staged (device bytes) <- h_frames, piece by piece on the current stream."""
+    """h_frames (pinned [n,H,W,3]) <- frames, staged (device bytes) <- h_frames, piece by piece on the current stream."""
     n = h_frames.shape[0]
+    fb = h_frames[0].numel()
     chunks = max(1, min(STAGE_CHUNKS, n // 64))
     step = (n + chunks - 1) // chunks
     for a in range(0, n, step):
         b = min(n, a + step)
         _stage_frames(h_frames[a:b], frames[a:b])
-        staged[a * ops.FRAME_BYTES:b * ops.FRAME_BYTES].copy_(h_frames[a:b].view(-1), non_blocking=True)
+        staged[a * fb:b * fb].copy_(h_frames[a:b].view(-1), non_blocking=True)
 
 
 class HostFedEnvironment(object):
     def __init__(self, simulator, batch, history_size, device="cuda:0", action_size=6, clip_reward=True,
-                 frame_max=255.0, objective_size=0, reward_divisor=1.0):
+                 frame_max=255.0, objective_size=0, reward_divisor=1.0, raw_frame_shape=None):
         self.B, self.sim = batch, simulator
         self.action_size = action_size
         self.clip_reward = clip_reward
@@ -87,7 +94,20 @@ class HostFedEnvironment(object):
         if self.objective_size:
             self._h_obj = torch.empty((batch, self.objective_size), dtype=torch.float32).pin_memory()
             self._obj = torch.empty(batch * self.objective_size, dtype=torch.float32, device=self.device)
-        self._h_frames = torch.empty((batch, 84, 84, 3), dtype=torch.uint8).pin_memory()
+        # gym: raw frames [Hs, Ws, 3] are staged, the resize to 84 x 84 runs on the device; terminal actors' post-reset
+        # observations go through a second raw staging (only in steps with a terminal)
+        self.raw_shape = None if raw_frame_shape is None else (int(raw_frame_shape[0]), int(raw_frame_shape[1]))
+        self.gym = self.raw_shape is not None
+        fshape = (84, 84) if not self.gym else self.raw_shape
+        self._h_frames = torch.empty((batch,) + fshape + (3,), dtype=torch.uint8).pin_memory()
+        if self.gym:
+            self.raw_bytes = fshape[0] * fshape[1] * 3
+            self._raw = torch.empty(batch * self.raw_bytes, dtype=torch.uint8, device=self.device)
+            self._h_reset = torch.empty((batch,) + fshape + (3,), dtype=torch.uint8).pin_memory()
+            self._raw_reset = torch.empty(batch * self.raw_bytes, dtype=torch.uint8, device=self.device)
+            self._reset84 = torch.zeros(batch * ops.FRAME_BYTES, dtype=torch.uint8, device=self.device)
+            self._h_reset_mask = torch.empty(batch, dtype=torch.int32).pin_memory()
+            self._reset_mask = torch.empty(batch, dtype=torch.int32, device=self.device)
         self._h_rewards = torch.empty(batch, dtype=torch.float32).pin_memory()
         self._h_terminals = torch.empty(batch, dtype=torch.int32).pin_memory()
         self._staged = torch.empty(batch * ops.FRAME_BYTES, dtype=torch.uint8, device=self.device)
@@ -110,7 +130,28 @@ class HostFedEnvironment(object):
         self._h2d_done.record()
 
     def _stage(self, frames):
-        _stage_and_copy(self._h_frames, frames, self._staged)
+        if not self.gym:
+            _stage_and_copy(self._h_frames, frames, self._staged)
+            return
+        _stage_and_copy(self._h_frames, frames, self._raw)
+        ops.frame_resize(self.B, self.raw_shape[0], self.raw_shape[1], self._raw, self._staged)
+
+    def _gym_resets(self, terminals, active, b0, b1, h_reset, raw_reset, h_mask, d_mask, reset84):
+        """Actors [b0, b1) that ended an episode: sim.reset(mask) (the trainer's env.reset(), trainer.py:201-202), their raw
+        post-reset observations staged and resized into reset84 on the current stream.  Call after the step's own frames
+        are staged (the simulator reuses its frame array).  -> whether any actor was reset."""
+        term = np.zeros(self.B, np.int32)
+        term[b0:b1] = np.asarray(terminals[b0:b1]) != 0
+        if active is not None:
+            term[b0:b1] &= np.asarray(active[b0:b1]) != 0
+        if not term.any():
+            return False
+        frames = self.sim.reset(term)
+        _stage_and_copy(h_reset, frames[b0:b1], raw_reset)
+        h_mask.copy_(torch.from_numpy(term[b0:b1]))
+        d_mask.copy_(h_mask, non_blocking=True)
+        ops.frame_resize(b1 - b0, self.raw_shape[0], self.raw_shape[1], raw_reset, reset84, mask=d_mask)
+        return True
 
     def _stage_objective(self, objectives, active):
         self._h_obj.copy_(torch.from_numpy(np.ascontiguousarray(objectives, dtype=np.float32)))
@@ -138,12 +179,19 @@ class HostFedEnvironment(object):
             rewards = (rewards.astype(np.float64) / self.reward_divisor).astype(np.float32)
         self._wait_staging()
         self._stage(frames)
+        if self.gym:
+            self._gym_resets(terminals, act, 0, self.B, self._h_reset, self._raw_reset, self._h_reset_mask,
+                             self._reset_mask, self._reset84)
         self._h_rewards.copy_(torch.from_numpy(rewards))
         self._h_terminals.copy_(torch.from_numpy(terminals))
         self._rewards.copy_(self._h_rewards, non_blocking=True)
         self._terminals.copy_(self._h_terminals, non_blocking=True)
-        ops.hostfed_step(self.ring, self._staged, actions, self._rewards, self._terminals, active, out_reward,
-                         out_terminal, reset_on_terminal, track_score, self.clip_reward, self.pc_denom)
+        if self.gym:
+            ops.gym_step(self.ring, self._staged, self._reset84, actions, self._rewards, self._terminals, active,
+                         out_reward, out_terminal, reset_on_terminal, track_score, self.pc_denom)
+        else:
+            ops.hostfed_step(self.ring, self._staged, actions, self._rewards, self._terminals, active, out_reward,
+                             out_terminal, reset_on_terminal, track_score, self.clip_reward, self.pc_denom)
         if self.objective_size:
             self._stage_objective(out[3], active)
         self._mark_staging()
@@ -159,8 +207,9 @@ class HostFedEnvironment(object):
         self.parts = []
         for k in range(n_parts):
             b0, b1 = k * Bp, (k + 1) * Bp
+            fshape = (84, 84) if not self.gym else self.raw_shape
             part = dict(b0=b0, b1=b1, ring=ops.ring_view(self.ring, b0, b1), stream=torch.cuda.Stream(device=self.device),
-                        h_frames=torch.empty((Bp, 84, 84, 3), dtype=torch.uint8).pin_memory(),
+                        h_frames=torch.empty((Bp,) + fshape + (3,), dtype=torch.uint8).pin_memory(),
                         h_rewards=torch.empty(Bp, dtype=torch.float32).pin_memory(),
                         h_terminals=torch.empty(Bp, dtype=torch.int32).pin_memory(),
                         h_actions=torch.empty(Bp, dtype=torch.int32).pin_memory(),
@@ -168,6 +217,14 @@ class HostFedEnvironment(object):
                         staged=self._staged[b0 * ops.FRAME_BYTES:b1 * ops.FRAME_BYTES],
                         rewards=self._rewards[b0:b1], terminals=self._terminals[b0:b1], h2d_done=None,
                         act_ready=torch.cuda.Event())
+            if self.gym:
+                rb = self.raw_bytes
+                part.update(raw=self._raw[b0 * rb:b1 * rb], staged84=part["staged"],
+                            h_reset=torch.empty((Bp,) + fshape + (3,), dtype=torch.uint8).pin_memory(),
+                            raw_reset=self._raw_reset[b0 * rb:b1 * rb],
+                            reset84=self._reset84[b0 * ops.FRAME_BYTES:b1 * ops.FRAME_BYTES],
+                            h_reset_mask=torch.empty(Bp, dtype=torch.int32).pin_memory(),
+                            reset_mask=self._reset_mask[b0:b1])
             if self.objective_size:
                 part["h_obj"] = torch.empty((Bp, self.objective_size), dtype=torch.float32).pin_memory()
                 part["obj"] = self._obj[b0 * self.objective_size:b1 * self.objective_size]
@@ -200,7 +257,9 @@ class HostFedEnvironment(object):
         if self.reward_divisor != 1.0:                  # indoor_environment.py:111
             rewards = (rewards.astype(np.float64) / self.reward_divisor).astype(np.float32)
         with torch.cuda.stream(p["stream"]):           # H2D of every staged piece starts at once, on the part's own stream
-            _stage_and_copy(p["h_frames"], frames[b0:b1], p["staged"])
+            _stage_and_copy(p["h_frames"], frames[b0:b1], p["raw"] if self.gym else p["staged"])
+            if self.gym:                               # the part's resizes run in part_ingest, behind these copies
+                p["any_reset"] = self._gym_resets_stage(terminals, self._mask_full, b0, b1, p)
         p["h_rewards"].copy_(torch.from_numpy(np.ascontiguousarray(rewards, dtype=np.float32)))
         p["h_terminals"].copy_(torch.from_numpy(np.ascontiguousarray(terminals[b0:b1], dtype=np.int32)))
         if self.objective_size:
@@ -211,14 +270,35 @@ class HostFedEnvironment(object):
         p = self.parts[k]                              # (the frames' H2D copies were issued by part_host_step, piece by piece)
         p["rewards"].copy_(p["h_rewards"], non_blocking=True)
         p["terminals"].copy_(p["h_terminals"], non_blocking=True)
-        ops.hostfed_step(p["ring"], p["staged"], actions, p["rewards"], p["terminals"], active, out_reward, out_terminal,
-                         reset_on_terminal, track_score, self.clip_reward, self.pc_denom)
+        if self.gym:
+            Hs, Ws = self.raw_shape
+            ops.frame_resize(p["b1"] - p["b0"], Hs, Ws, p["raw"], p["staged84"])
+            if p["any_reset"]:
+                ops.frame_resize(p["b1"] - p["b0"], Hs, Ws, p["raw_reset"], p["reset84"], mask=p["reset_mask"])
+            ops.gym_step(p["ring"], p["staged84"], p["reset84"], actions, p["rewards"], p["terminals"], active, out_reward,
+                         out_terminal, reset_on_terminal, track_score, self.pc_denom)
+        else:
+            ops.hostfed_step(p["ring"], p["staged"], actions, p["rewards"], p["terminals"], active, out_reward,
+                             out_terminal, reset_on_terminal, track_score, self.clip_reward, self.pc_denom)
         if self.objective_size:
             p["obj"].copy_(p["h_obj"].view(-1), non_blocking=True)
             ops.objective_put(p["ring"], p["obj"], active)
         if p["h2d_done"] is None:
             p["h2d_done"] = torch.cuda.Event()
         p["h2d_done"].record()
+
+    def _gym_resets_stage(self, terminals, active, b0, b1, p):
+        """part_host_step's half of _gym_resets: reset part k's terminal actors and stage their raw observations (H2D on the
+        current stream); the masked resize follows in part_ingest.  -> whether any actor was reset."""
+        term = np.zeros(self.B, np.int32)
+        term[b0:b1] = (np.asarray(terminals[b0:b1]) != 0) & (np.asarray(active[b0:b1]) != 0)
+        if not term.any():
+            return False
+        frames = self.sim.reset(term)
+        _stage_and_copy(p["h_reset"], frames[b0:b1], p["raw_reset"])
+        p["h_reset_mask"].copy_(torch.from_numpy(term[b0:b1]))
+        p["reset_mask"].copy_(p["h_reset_mask"], non_blocking=True)
+        return True
 
     def stop(self):
         pass

@@ -246,6 +246,30 @@ def hostfed_reset(ring, staged, mask=None):
           ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames))
 
 
+def frame_resize(n, Hs, Ws, src, dst, mask=None):
+    """dst [n,84,84,3] uint8 <- src [n,Hs,Ws,3] uint8 raw frames, bilinear with cv2 INTER_LINEAR's half-pixel rule in fp32,
+    rounded to nearest-even (gym_environment.py:18-23); rows with mask == 0 are left as they are."""
+    if n <= 0 or Hs < 1 or Ws < 1:
+        raise ValueError("frame_resize: n=%d Hs=%d Ws=%d" % (n, Hs, Ws))
+    _chk(src, "u8", n * Hs * Ws * 3, "src"); _chk(dst, "u8", n * FRAME_BYTES, "dst"); _chk(mask, "i32", n, optional=True)
+    _call("unreal_frame_resize", n, Hs, Ws, ptr(src), ptr(mask), ptr(dst))
+
+
+def gym_step(ring, staged, reset_staged, actions, rewards, terminals, active=None, out_reward=None, out_terminal=None,
+             reset_on_terminal=True, track_score=False, pc_denom=48.0 * 255.0):
+    """hostfed_step with the gym terminal rule: `staged` holds the observation after the step (the terminal one where
+    terminal), `reset_staged` the post-reset observation the next slot gets where terminal; rewards are stored raw."""
+    B = ring.B
+    _chk(staged, "u8", B * FRAME_BYTES, "staged"); _chk(reset_staged, "u8", B * FRAME_BYTES, "reset_staged")
+    _chk(actions, "i32", B); _chk(rewards, "f32", B); _chk(terminals, "i32", B); _chk(active, "i32", B, optional=True)
+    _chk(out_reward, "f32", B, optional=True); _chk(out_terminal, "i32", B, optional=True)
+    _call("unreal_gym_step", B, ring.H1, ptr(staged), ptr(reset_staged), ptr(actions), ptr(rewards), ptr(terminals),
+          ptr(active), ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward),
+          ptr(ring.r_action), ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc),
+          ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid),
+          int(reset_on_terminal), int(track_score), float(pc_denom))
+
+
 def base_returns(B, T, rewards, values, n_steps, boot_v, terminal_end, gamma, R_out, adv_out):
     for t in (rewards, values, R_out, adv_out):
         _chk(t, "f32", B * T)

@@ -87,7 +87,7 @@ class Trainer(object):
         self._overlap_request = overlap_host
         # upstream replay semantics for host-fed (Lab-contract) actors: zero / non-zero reward buckets and reward
         # clipping (train/experience_lab_ver.py:14,18,76-80); this fork's buckets for the maze (train/experience.py)
-        self.rp_mode = 1 if env_type == "lab" else 0      # indoor: this fork's train/experience.py, like the maze
+        self.rp_mode = 1 if env_type == "lab" else 0      # indoor, gym: this fork's train/experience.py, like the maze
         self.thread_index = thread_index
         self.learning_rate_input = learning_rate_input
         self.env_type, self.env_name = env_type, env_name
@@ -145,10 +145,14 @@ class Trainer(object):
             if indoor and getattr(self.simulator, "objective_size", 0) != self.objective_size:
                 raise ValueError("simulator.objective_size != Environment.get_objective_size(%r, %r) = %d"
                                  % (self.env_type, self.env_name, self.objective_size))
+            gym = self.env_type == "gym"        # raw frames, resized on the device; rewards unclipped (experience.py)
+            if gym and not hasattr(self.simulator, "frame_shape"):
+                raise ValueError("env_type='gym' needs a simulator with frame_shape (gym_environment.GymBatchSimulator)")
             self.environment = HostFedEnvironment(self.simulator, B, self.experience_history_size, dev,
-                                                  action_size=A, clip_reward=not indoor,
+                                                  action_size=A, clip_reward=not (indoor or gym),
                                                   objective_size=self.objective_size,
-                                                  reward_divisor=termination_time if indoor else 1.0)
+                                                  reward_divisor=termination_time if indoor else 1.0,
+                                                  raw_frame_shape=self.simulator.frame_shape if gym else None)
         self.overlap_host = False
         if self.env_type != "maze":
             want = self._overlap_request if self._overlap_request is not None else (B % 2 == 0 and B >= 2048)
