@@ -75,6 +75,20 @@ int unreal_hostfed_step(int B, int H1, const uint8_t* staged, const int* actions
                         int track_score, int clip_reward, float pc_denom, void* stream);
 int unreal_hostfed_reset(int B, int H1, const int* mask, const uint8_t* staged, int* last_action, float* last_reward,
                          const int* count, uint8_t* frames, void* stream);
+/* indoor environments at any frame size H x W, 20 <= H, W <= 480 (environment/indoor_environment.py:63-139 with the
+ * MINOS config's height / width, main.py:196): unreal_hostfed_step / _reset with `frame_stride` bytes per frame in
+ * `staged` and in the ring (a multiple of 16, >= H * W * 3).  Rewards (divided by termination_time on the host,
+ * indoor_environment.py:111), the replay fields and the terminal rules are those of unreal_hostfed_step; the objective
+ * goes through unreal_objective_put as there.  No pixel change is computed and the ring's r_pc is not an argument: pixel
+ * control is 84 x 84 only (model/model.py:416-430,554). */
+int unreal_hostfed_step_hw(int B, int H1, int H, int W, long frame_stride, const uint8_t* staged, const int* actions,
+                           const float* rewards, const int* terminals, const int* active, int* last_action,
+                           float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                           int* r_terminal, int* r_last_action, float* r_last_reward, float* out_reward,
+                           int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                           int reset_on_terminal, int track_score, int clip_reward, void* stream);
+int unreal_hostfed_reset_hw(int B, int H1, int H, int W, long frame_stride, const int* mask, const uint8_t* staged,
+                            int* last_action, float* last_reward, const int* count, uint8_t* frames, void* stream);
 /* gym / Atari environments (environment/gym_environment.py:18-96).  unreal_frame_resize: src [n][Hs][Ws][3] raw uint8
  * frames -> dst [n][84][84][3], cv2 INTER_LINEAR's half-pixel rule in fp32 rounded to nearest-even (csrc/gym.hip); rows
  * with mask[i] == 0 are skipped (mask nullable).  unreal_gym_step: unreal_hostfed_step with the gym terminal rule -- the
@@ -167,6 +181,21 @@ int unreal_encoder_prepare(const float* W1, const float* b1, const float* W2, fl
 int unreal_encoder_bwd(int N, const uint8_t* frames, const int* frame_idx, float frame_scale, const float* W2,
                        const float* c1_saved, const float* c1_absmax, const float* d2, const float* d2_absmax, float* dW1,
                        float* db1, float* dW2, float* db2, void* stream);
+
+/* the conv encoder at a runtime frame size H x W, 20 <= H, W <= 480 (model/model.py:281-289,786-787 with
+ * image_shape = [height, width], main.py:196; the fc widths that follow, model.py:327-333,480-484): h1 = (H - 8) / 4 + 1,
+ * h2 = (h1 - 4) / 2 + 1 (w1, w2 alike).  frames [pool][H][W][3] uint8, `frame_stride` bytes apart; c1_out [N][h1][w1][16]
+ * (required: conv2 reads it), f2_out [N][h2][w2][32] (the flatten of model.py:331).  fp32 operands on the fp32 matrix
+ * cores (csrc/encoder_hw.hip), so no operand absmax slots; f2_absmax (nullable) receives max f2.  The backward reads d2 =
+ * d(loss)/d(conv2 pre-activation), ADDS into dW1 / db1 / dW2 / db2 in a fixed order (two launches give identical bits)
+ * and needs `work` of unreal_encoder_hw_work_floats(N, H, W) floats (host-only query: *out = that count). */
+int unreal_encoder_hw_fwd(int N, int H, int W, const uint8_t* frames, long frame_stride, const int* frame_idx,
+                          float frame_scale, const float* W1, const float* b1, const float* W2, const float* b2,
+                          float* c1_out, float* f2_out, float* f2_absmax, void* stream);
+int unreal_encoder_hw_bwd(int N, int H, int W, const uint8_t* frames, long frame_stride, const int* frame_idx,
+                          float frame_scale, const float* W2, const float* c1_saved, const float* d2, float* work,
+                          long work_floats, float* dW1, float* db1, float* dW2, float* db2, void* stream);
+int unreal_encoder_hw_work_floats(int N, int H, int W, long* out, void* stream);
 
 /* ---- dense layers: tf.matmul call sites model/model.py:314,334,423 and BasicLSTMCell 110,346-351 -- */
 int unreal_gemm_f32(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B,

@@ -64,6 +64,7 @@ def save(checkpoint_dir, net, applier, global_t, wall_t, best_score=0.0, name=""
     payload = {
         "format": "unreal_amd.flat.v1",
         "global_t": int(global_t),
+        "image_shape": tuple(getattr(net, "image_shape", (84, 84))),
         "best_score": float(best_score),
         "spec": [(n, tuple(s)) for n, s, _ in net.spec],
         "offsets": {k: (o, n) for k, (o, n, _) in net.params.offsets.items()},
@@ -82,6 +83,22 @@ def save(checkpoint_dir, net, applier, global_t, wall_t, best_score=0.0, name=""
     return path
 
 
+def _check_spec(path, saved, net, saved_shape=None):
+    """Raise ValueError naming what differs when the saved variable list is not this network's (the fc widths follow the
+    frame size: W_base_fc1 is [F, 256] and W_rp_fc1 [3F, 3] with F = 32 * h2 * w2)."""
+    want = [(n, tuple(s)) for n, s, _ in net.spec]
+    if saved == want:
+        return
+    have = dict(saved)
+    diff = ["%s: checkpoint %s, network %s" % (n, have[n], s) for n, s in want if n in have and have[n] != s]
+    names = "" if [n for n, _ in saved] == [n for n, _ in want] else \
+        " (variables: checkpoint %s, network %s)" % ([n for n, _ in saved], [n for n, _ in want])
+    shape = "" if saved_shape is None else " checkpoint image_shape %r, network image_shape %r;" % (
+        tuple(saved_shape), tuple(getattr(net, "image_shape", (84, 84))))
+    raise ValueError("checkpoint %s holds a different variable list than this model:%s %s%s"
+                     % (path, shape, "; ".join(diff) if diff else "", names))
+
+
 def restore(checkpoint_dir, net, applier=None, restore_slots=True, name=""):
     """-> (global_t, wall_t, best_score) of the newest checkpoint, or None if there is none."""
     ck = list_checkpoints(checkpoint_dir, name)
@@ -89,8 +106,7 @@ def restore(checkpoint_dir, net, applier=None, restore_slots=True, name=""):
         return None
     global_t, path = ck[-1]
     payload = torch.load(path, map_location="cpu", weights_only=True)
-    if [(n, tuple(s)) for n, s in payload["spec"]] != [(n, tuple(s)) for n, s, _ in net.spec]:
-        raise ValueError("checkpoint %s holds a different variable list than this model" % path)
+    _check_spec(path, [(n, tuple(s)) for n, s in payload["spec"]], net, payload.get("image_shape"))
     net.params.flat.copy_(payload["params"])
     if hasattr(net, "mark_params_changed"):      # derived weight planes must follow the restored parameters
         net.mark_params_changed()

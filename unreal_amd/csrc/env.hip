@@ -447,6 +447,70 @@ __global__ __launch_bounds__(256) void hostfed_reset_kernel(int B, int H1, const
   }
 }
 
+// ---- host-fed step / reset at any frame size (indoor environments): frames of `frame_stride` bytes (a multiple of 16,
+// >= H * W * 3), no pixel change (pixel control is 84 x 84 only, model/model.py:416-430 of the reference) -----------
+__global__ __launch_bounds__(256) void hostfed_step_hw_kernel(HostFedArgs p, long frame_stride) {
+  const int b = blockIdx.x;
+  if (p.active && !p.active[b]) return;
+  const int H1 = p.H1;
+  const int a = p.actions[b];
+  const float reward = p.rewards[b];
+  const bool terminal = p.terminals[b] != 0;
+  const int cnt = p.count[b];
+  const int la = p.last_action[b];
+  const float lr = p.last_reward[b];
+  const int slot = cnt % H1;
+  const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
+  float ep = p.track_score ? p.episode_reward[b] : 0.f;
+  __syncthreads();   // every wave has read count / last_* before thread 0 rewrites them
+  const size_t base = (size_t)b * H1 + slot;
+  const bool discard = terminal && cnt > 0 && prev_term;
+  const int ncnt = discard ? cnt : cnt + 1;
+  const bool reset = terminal && p.reset_on_terminal;
+  const int nslot = ncnt % H1;
+  {
+    const uint4* s4 = reinterpret_cast<const uint4*>(p.staged + (size_t)b * frame_stride);
+    uint4* d4 = reinterpret_cast<uint4*>(p.frames + ((size_t)b * H1 + nslot) * frame_stride);
+    for (long c = threadIdx.x; c < frame_stride / 16; c += blockDim.x) d4[c] = s4[c];
+  }
+  if (threadIdx.x == 0) {
+    p.r_reward[base] = clip1(reward, p.clip_reward);
+    p.r_action[base] = a;
+    p.r_terminal[base] = terminal ? 1 : 0;
+    p.r_last_action[base] = la;
+    p.r_last_reward[base] = clip1(lr, p.clip_reward);
+    p.count[b] = ncnt;
+    p.last_action[b] = reset ? 0 : a;
+    p.last_reward[b] = reset ? 0.f : reward;
+    if (p.out_reward) p.out_reward[b] = reward;
+    if (p.out_terminal) p.out_terminal[b] = terminal ? 1 : 0;
+    if (p.track_score) {
+      ep += reward;
+      if (terminal) {
+        p.score_out[b] = ep;
+        p.score_valid[b] = 1;
+        ep = 0.f;
+      }
+      p.episode_reward[b] = ep;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void hostfed_reset_hw_kernel(int H1, long frame_stride, const int* mask,
+                                                               const uint8_t* staged, int* last_action,
+                                                               float* last_reward, const int* count, uint8_t* frames) {
+  const int b = blockIdx.x;
+  if (mask && !mask[b]) return;
+  const int slot = count[b] % H1;
+  const uint4* s4 = reinterpret_cast<const uint4*>(staged + (size_t)b * frame_stride);
+  uint4* d4 = reinterpret_cast<uint4*>(frames + ((size_t)b * H1 + slot) * frame_stride);
+  for (long c = threadIdx.x; c < frame_stride / 16; c += blockDim.x) d4[c] = s4[c];
+  if (threadIdx.x == 0) {
+    last_action[b] = 0;
+    last_reward[b] = 0.f;
+  }
+}
+
 // ---- Philox4x32-10 counter RNG: key = seed, counter = (index, stream) ------------------------
 __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
@@ -595,6 +659,39 @@ int unreal_hostfed_reset(int B, int H1, const int* mask, const uint8_t* staged, 
   if ((((uintptr_t)staged) | ((uintptr_t)frames)) & 15) return UNREAL_EINVAL;
   hipLaunchKernelGGL(hostfed_reset_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, B, H1, mask, staged,
                      last_action, last_reward, count, frames);
+  return unreal_launch_status();
+}
+
+static bool hw_frame_ok(int H, int W, long frame_stride) {
+  return H >= 20 && H <= 480 && W >= 20 && W <= 480 && frame_stride >= (long)H * W * 3 && frame_stride % 16 == 0;
+}
+
+int unreal_hostfed_step_hw(int B, int H1, int H, int W, long frame_stride, const uint8_t* staged, const int* actions,
+                           const float* rewards, const int* terminals, const int* active, int* last_action,
+                           float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                           int* r_terminal, int* r_last_action, float* r_last_reward, float* out_reward,
+                           int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                           int reset_on_terminal, int track_score, int clip_reward, void* stream) {
+  if (B <= 0 || H1 < 2 || !hw_frame_ok(H, W, frame_stride) || !staged || !actions || !rewards || !terminals || !count ||
+      !frames || !last_action || !last_reward || !r_reward || !r_action || !r_terminal || !r_last_action || !r_last_reward)
+    return UNREAL_EINVAL;
+  if (track_score && (!episode_reward || !score_out || !score_valid)) return UNREAL_EINVAL;
+  if ((((uintptr_t)staged) | ((uintptr_t)frames)) & 15) return UNREAL_EINVAL;
+  HostFedArgs p{B, H1, staged, actions, rewards, terminals, active, last_action, last_reward, count, frames, r_reward,
+                r_action, r_terminal, r_last_action, r_last_reward, nullptr, out_reward, out_terminal, episode_reward,
+                score_out, score_valid, reset_on_terminal, track_score, clip_reward, 1.f};
+  hipLaunchKernelGGL(hostfed_step_hw_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, p, frame_stride);
+  return unreal_launch_status();
+}
+
+int unreal_hostfed_reset_hw(int B, int H1, int H, int W, long frame_stride, const int* mask, const uint8_t* staged,
+                            int* last_action, float* last_reward, const int* count, uint8_t* frames, void* stream) {
+  if (B <= 0 || H1 < 2 || !hw_frame_ok(H, W, frame_stride) || !staged || !count || !frames || !last_action ||
+      !last_reward)
+    return UNREAL_EINVAL;
+  if ((((uintptr_t)staged) | ((uintptr_t)frames)) & 15) return UNREAL_EINVAL;
+  hipLaunchKernelGGL(hostfed_reset_hw_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, H1, frame_stride, mask,
+                     staged, last_action, last_reward, count, frames);
   return unreal_launch_status();
 }
 

@@ -8,14 +8,19 @@ gym_environment.GymBatchSimulator (any object with gym's reset / step API)."""
 class Environment(object):
     action_size = -1          # class-cached: first query wins (environment.py:13,46-47)
     LOG_DIR = None
-    # stands in for minos.config.sim_config (indoor_environment.py:27-29): env_name -> {'objective_size': n}
+    # stands in for minos.config.sim_config (indoor_environment.py:27-29; main.py:196 reads height / width from it):
+    # env_name -> {'objective_size': n, 'height': H, 'width': W}
     INDOOR_CONFIG = {}
     # stands in for gym.make(env_name).action_space.n (gym_environment.py:55-60): env_name -> action count
     GYM_CONFIG = {}
 
     @staticmethod
-    def register_indoor_config(env_name, objective_size):
-        Environment.INDOOR_CONFIG[env_name] = {'objective_size': int(objective_size)}
+    def register_indoor_config(env_name, objective_size, height=84, width=84):
+        from .. import ops
+        h, w = int(height), int(width)
+        if (h, w) != ops.FRAME_SHAPE:
+            ops.frame_dims(h, w)               # raises outside 20 <= H, W <= 480
+        Environment.INDOOR_CONFIG[env_name] = {'objective_size': int(objective_size), 'height': h, 'width': w}
 
     @staticmethod
     def register_gym_config(env_name, action_size):
@@ -55,6 +60,15 @@ class Environment(object):
         if env_type == 'indoor':               # environment.py:68-72 -> indoor_environment.py:26-29
             return Environment.INDOOR_CONFIG.get(env_name, {}).get('objective_size', 0)
         return 0
+
+    @staticmethod
+    def get_image_shape(env_type, env_name):
+        """[height, width] of the environment's frames (main.py:196: the MINOS config's, default 84; every other
+        environment type is 84 x 84)."""
+        if env_type == 'indoor':
+            cfg = Environment.INDOOR_CONFIG.get(env_name, {})
+            return [cfg.get('height', 84), cfg.get('width', 84)]
+        return [84, 84]
 
     def __init__(self):
         pass

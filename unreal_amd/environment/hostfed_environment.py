@@ -79,9 +79,18 @@ def _stage_and_copy(h_frames, frames, staged):
         staged[a * fb:b * fb].copy_(h_frames[a:b].view(-1), non_blocking=True)
 
 
+def _stage_and_copy_hw(h_frames, frames, staged):
+    """_stage_and_copy for frames of any size: h_frames is pinned uint8 [n, stride] with stride >= H * W * 3 (a multiple
+    of 16, ops.frame_stride); each frame goes to the start of its row, rows are copied whole."""
+    n, stride = h_frames.shape
+    src = np.asarray(frames).reshape(n, -1)
+    _stage_frames(h_frames[:, :src.shape[1]], src)
+    staged[:n * stride].copy_(h_frames.view(-1), non_blocking=True)
+
+
 class HostFedEnvironment(object):
     def __init__(self, simulator, batch, history_size, device="cuda:0", action_size=6, clip_reward=True,
-                 frame_max=255.0, objective_size=0, reward_divisor=1.0, raw_frame_shape=None):
+                 frame_max=255.0, objective_size=0, reward_divisor=1.0, raw_frame_shape=None, frame_shape=None):
         self.B, self.sim = batch, simulator
         self.action_size = action_size
         self.clip_reward = clip_reward
@@ -90,7 +99,16 @@ class HostFedEnvironment(object):
         self.pc_denom = 48.0 * frame_max
         self.frame_scale = 1.0 / frame_max          # lab_environment.py:99-102: state = obs / 255
         self.device = torch.device(device)
-        self.ring = ops.Ring(batch, history_size, self.device, objective_size=self.objective_size)
+        # frame_shape (H, W) != (84, 84): the indoor contract at another frame size (frames ring.frame_stride bytes apart,
+        # ingested by ops.hostfed_step_hw / hostfed_reset_hw; no pixel change)
+        self.frame_shape = ops.FRAME_SHAPE if frame_shape is None else (int(frame_shape[0]), int(frame_shape[1]))
+        self.hw = self.frame_shape != ops.FRAME_SHAPE
+        if self.hw and (raw_frame_shape is not None or not objective_size):
+            raise ValueError("frame_shape %r: other frame sizes are the indoor contract only (objective_size > 0, no "
+                             "raw frames)" % (self.frame_shape,))
+        self.ring = ops.Ring(batch, history_size, self.device, objective_size=self.objective_size,
+                             frame_shape=self.frame_shape)
+        self.frame_stride = self.ring.frame_stride
         if self.objective_size:
             self._h_obj = torch.empty((batch, self.objective_size), dtype=torch.float32).pin_memory()
             self._obj = torch.empty(batch * self.objective_size, dtype=torch.float32, device=self.device)
@@ -99,7 +117,8 @@ class HostFedEnvironment(object):
         self.raw_shape = None if raw_frame_shape is None else (int(raw_frame_shape[0]), int(raw_frame_shape[1]))
         self.gym = self.raw_shape is not None
         fshape = (84, 84) if not self.gym else self.raw_shape
-        self._h_frames = torch.empty((batch,) + fshape + (3,), dtype=torch.uint8).pin_memory()
+        self._h_frames = torch.zeros((batch, self.frame_stride) if self.hw else (batch,) + fshape + (3,),
+                                     dtype=torch.uint8).pin_memory()
         if self.gym:
             self.raw_bytes = fshape[0] * fshape[1] * 3
             self._raw = torch.empty(batch * self.raw_bytes, dtype=torch.uint8, device=self.device)
@@ -110,7 +129,7 @@ class HostFedEnvironment(object):
             self._reset_mask = torch.empty(batch, dtype=torch.int32, device=self.device)
         self._h_rewards = torch.empty(batch, dtype=torch.float32).pin_memory()
         self._h_terminals = torch.empty(batch, dtype=torch.int32).pin_memory()
-        self._staged = torch.empty(batch * ops.FRAME_BYTES, dtype=torch.uint8, device=self.device)
+        self._staged = torch.empty(batch * self.frame_stride, dtype=torch.uint8, device=self.device)
         self._rewards = torch.empty(batch, dtype=torch.float32, device=self.device)
         self._terminals = torch.empty(batch, dtype=torch.int32, device=self.device)
         self._h2d_done = None
@@ -130,6 +149,9 @@ class HostFedEnvironment(object):
         self._h2d_done.record()
 
     def _stage(self, frames):
+        if self.hw:
+            _stage_and_copy_hw(self._h_frames, frames, self._staged)
+            return
         if not self.gym:
             _stage_and_copy(self._h_frames, frames, self._staged)
             return
@@ -164,7 +186,10 @@ class HostFedEnvironment(object):
         frames, objectives = out if self.objective_size else (out, None)
         self._wait_staging()
         self._stage(frames)
-        ops.hostfed_reset(self.ring, self._staged, mask)
+        if self.hw:
+            ops.hostfed_reset_hw(self.ring, self._staged, mask)
+        else:
+            ops.hostfed_reset(self.ring, self._staged, mask)
         if self.objective_size:
             self._stage_objective(objectives, mask)
         self._mark_staging()
@@ -189,6 +214,9 @@ class HostFedEnvironment(object):
         if self.gym:
             ops.gym_step(self.ring, self._staged, self._reset84, actions, self._rewards, self._terminals, active,
                          out_reward, out_terminal, reset_on_terminal, track_score, self.pc_denom)
+        elif self.hw:
+            ops.hostfed_step_hw(self.ring, self._staged, actions, self._rewards, self._terminals, active, out_reward,
+                                out_terminal, reset_on_terminal, track_score, self.clip_reward)
         else:
             ops.hostfed_step(self.ring, self._staged, actions, self._rewards, self._terminals, active, out_reward,
                              out_terminal, reset_on_terminal, track_score, self.clip_reward, self.pc_denom)
@@ -209,12 +237,13 @@ class HostFedEnvironment(object):
             b0, b1 = k * Bp, (k + 1) * Bp
             fshape = (84, 84) if not self.gym else self.raw_shape
             part = dict(b0=b0, b1=b1, ring=ops.ring_view(self.ring, b0, b1), stream=torch.cuda.Stream(device=self.device),
-                        h_frames=torch.empty((Bp,) + fshape + (3,), dtype=torch.uint8).pin_memory(),
+                        h_frames=torch.zeros((Bp, self.frame_stride) if self.hw else (Bp,) + fshape + (3,),
+                                             dtype=torch.uint8).pin_memory(),
                         h_rewards=torch.empty(Bp, dtype=torch.float32).pin_memory(),
                         h_terminals=torch.empty(Bp, dtype=torch.int32).pin_memory(),
                         h_actions=torch.empty(Bp, dtype=torch.int32).pin_memory(),
                         h_active=torch.empty(Bp, dtype=torch.int32).pin_memory(),
-                        staged=self._staged[b0 * ops.FRAME_BYTES:b1 * ops.FRAME_BYTES],
+                        staged=self._staged[b0 * self.frame_stride:b1 * self.frame_stride],
                         rewards=self._rewards[b0:b1], terminals=self._terminals[b0:b1], h2d_done=None,
                         act_ready=torch.cuda.Event())
             if self.gym:
@@ -257,7 +286,10 @@ class HostFedEnvironment(object):
         if self.reward_divisor != 1.0:                  # indoor_environment.py:111
             rewards = (rewards.astype(np.float64) / self.reward_divisor).astype(np.float32)
         with torch.cuda.stream(p["stream"]):           # H2D of every staged piece starts at once, on the part's own stream
-            _stage_and_copy(p["h_frames"], frames[b0:b1], p["raw"] if self.gym else p["staged"])
+            if self.hw:
+                _stage_and_copy_hw(p["h_frames"], frames[b0:b1], p["staged"])
+            else:
+                _stage_and_copy(p["h_frames"], frames[b0:b1], p["raw"] if self.gym else p["staged"])
             if self.gym:                               # the part's resizes run in part_ingest, behind these copies
                 p["any_reset"] = self._gym_resets_stage(terminals, self._mask_full, b0, b1, p)
         p["h_rewards"].copy_(torch.from_numpy(np.ascontiguousarray(rewards, dtype=np.float32)))
@@ -277,6 +309,9 @@ class HostFedEnvironment(object):
                 ops.frame_resize(p["b1"] - p["b0"], Hs, Ws, p["raw_reset"], p["reset84"], mask=p["reset_mask"])
             ops.gym_step(p["ring"], p["staged84"], p["reset84"], actions, p["rewards"], p["terminals"], active, out_reward,
                          out_terminal, reset_on_terminal, track_score, self.pc_denom)
+        elif self.hw:
+            ops.hostfed_step_hw(p["ring"], p["staged"], actions, p["rewards"], p["terminals"], active, out_reward,
+                                out_terminal, reset_on_terminal, track_score, self.clip_reward)
         else:
             ops.hostfed_step(p["ring"], p["staged"], actions, p["rewards"], p["terminals"], active, out_reward,
                              out_terminal, reset_on_terminal, track_score, self.clip_reward, self.pc_denom)

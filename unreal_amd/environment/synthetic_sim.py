@@ -61,11 +61,16 @@ class SyntheticBatchSimulator(object):
 class SyntheticIndoorSim(SyntheticActorSim):
     """Stand-in for a MINOS RoomSimulator actor (indoor_environment.py:63-139): also returns a measurement vector
     ('objective') with every observation, and raw rewards that the wrapper divides by termination_time.  Raw rewards are
-    multiples of termination_time / 8 so the scaled reward is exact in fp32."""
+    multiples of termination_time / 8 so the scaled reward is exact in fp32.  height / width: the frame size of the
+    MINOS config (main.py:196), default 84 x 84."""
 
-    def __init__(self, seed, objective_size=5, termination_time=50.0, **kw):
+    def __init__(self, seed, objective_size=5, termination_time=50.0, height=84, width=84, **kw):
         SyntheticActorSim.__init__(self, seed, **kw)
         self.objective_size, self.termination_time = objective_size, termination_time
+        self.frame_shape = (int(height), int(width))
+
+    def _obs(self):
+        return self.rs.randint(0, 256, size=self.frame_shape + (3,)).astype(np.uint8)
 
     def _meas(self):
         return self.rs.uniform(-1.0, 1.0, size=self.objective_size).astype(np.float32)
@@ -87,13 +92,15 @@ class SyntheticIndoorSim(SyntheticActorSim):
 class SyntheticBatchIndoorSimulator(object):
     """B independent SyntheticIndoorSim actors behind the batched host-fed interface (with objectives)."""
 
-    def __init__(self, batch, seed=5, objective_size=5, **kw):
-        self.actors = [SyntheticIndoorSim(seed * 100003 + b, objective_size=objective_size, **kw) for b in range(batch)]
+    def __init__(self, batch, seed=5, objective_size=5, height=84, width=84, **kw):
+        self.actors = [SyntheticIndoorSim(seed * 100003 + b, objective_size=objective_size, height=height, width=width,
+                                          **kw) for b in range(batch)]
         self.B, self.objective_size = batch, objective_size
+        self.image_shape = (int(height), int(width))
         self._obj = np.zeros((batch, objective_size), np.float32)
 
     def reset(self, mask=None):
-        out = np.zeros((self.B, 84, 84, 3), np.uint8)
+        out = np.zeros((self.B,) + self.image_shape + (3,), np.uint8)
         for b, a in enumerate(self.actors):
             if mask is None or mask[b]:
                 out[b], self._obj[b] = a.reset()
@@ -101,7 +108,7 @@ class SyntheticBatchIndoorSimulator(object):
 
     def step(self, actions, active=None):
         """-> frames, rewards (raw), terminals, objectives; where terminal: the post-reset observation and objective."""
-        frames = np.zeros((self.B, 84, 84, 3), np.uint8)
+        frames = np.zeros((self.B,) + self.image_shape + (3,), np.uint8)
         rewards = np.zeros(self.B, np.float32)
         terminals = np.zeros(self.B, np.int32)
         for b, a in enumerate(self.actors):

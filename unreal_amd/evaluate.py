@@ -2,7 +2,8 @@
 (restored) network WITHOUT learning for a number of episodes and report return / success statistics.  The
 reference evaluates one MINOS episode at a time with batch-1 session calls; here B maze actors roll in
 lock-step on the device with the same kernels the trainer uses (policy sampled like `choose_action`, or
-greedy).  The maze has no step limit (maze_environment.py:114-118), so `max_episode_steps` bounds an episode;
+greedy).  With `simulator=` the actors are host-fed indoor (MINOS-contract) simulators instead, at the network's
+image_shape (main.py:196), rewards divided by termination_time.  The maze has no step limit (maze_environment.py:114-118), so `max_episode_steps` bounds an episode;
 such episodes count as failures ("success := terminal")."""
 import torch
 
@@ -13,14 +14,25 @@ from .train.trainer import PhiloxDraws
 
 
 class Evaluate(object):
-    def __init__(self, network, batch_size=64, device="cuda:0", seed=0xE7A1, greedy=False, draws=None):
+    def __init__(self, network, batch_size=64, device="cuda:0", seed=0xE7A1, greedy=False, draws=None, simulator=None,
+                 termination_time=50.0):
         self.net, self.B, self.greedy = network, int(batch_size), greedy
         self.device = torch.device(device)
         self.draws = draws if draws is not None else PhiloxDraws(seed)
         B, A = self.B, network._action_size
-        self.env = BatchedMazeEnvironment(B, 2, self.device)
+        if simulator is None:
+            self.env = BatchedMazeEnvironment(B, 2, self.device)
+        else:
+            from .environment.hostfed_environment import HostFedEnvironment
+            if tuple(getattr(simulator, "image_shape", (84, 84))) != tuple(network.image_shape):
+                raise ValueError("simulator.image_shape %r != the network's image_shape %r"
+                                 % (getattr(simulator, "image_shape", (84, 84)), network.image_shape))
+            self.env = HostFedEnvironment(simulator, B, 2, self.device, action_size=A, clip_reward=False,
+                                          objective_size=network._objective_size, reward_divisor=termination_time,
+                                          frame_shape=network.image_shape)
+            network.lar_bounded = False        # raw rewards and measurement vectors in the LSTM input (Trainer.prepare)
         network.bind_frame_scale(self.env.frame_scale)
-        self.ws = PathWS(B, B, self.device, save_c1=False, lstm=network._use_lstm, xld=network.xld)
+        self.ws = PathWS(B, B, self.device, save_c1=False, lstm=network._use_lstm, xld=network.xld, **network.ws_kw)
         z = lambda n, dt: torch.zeros(n, dtype=dt, device=self.device)
         self.pi, self.v = z(B * A, torch.float32), z(B, torch.float32)
         self.u, self.actions = z(B, torch.float64), z(B, torch.int32)

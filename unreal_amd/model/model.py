@@ -38,14 +38,22 @@ def _small_chunks(n):
     return out
 
 
+def conv_out_dim(image_shape=(84, 84)):
+    """Width F of the flattened conv output of an [H, W] frame: 2592 at 84 x 84, 32 * h2 * w2 in general (model.py:327-333,
+    480-484 derive the fc widths from it).  Raises ValueError outside 20 <= H, W <= 480."""
+    shape = (int(image_shape[0]), int(image_shape[1]))
+    return ops.F2_DIM if shape == ops.FRAME_SHAPE else ops.frame_dims(*shape)[4]
+
+
 def param_spec(action_size, objective_size=0, use_lstm=True, use_pixel_change=True,
-               use_value_replay=True, use_reward_prediction=True):
+               use_value_replay=True, use_reward_prediction=True, image_shape=(84, 84)):
     """(name, shape, fan_in) in the reference's variable-creation order (model.py:106-136)."""
     A = action_size
+    F = conv_out_dim(image_shape)
     lstm_in = 256 + A + 1 + objective_size
     spec = [("W_base_conv1", (8, 8, 3, 16), 192), ("b_base_conv1", (16,), 192),
             ("W_base_conv2", (4, 4, 16, 32), 256), ("b_base_conv2", (32,), 256),
-            ("W_base_fc1", (2592, 256), 2592), ("b_base_fc1", (256,), 2592)]
+            ("W_base_fc1", (F, 256), F), ("b_base_fc1", (256,), F)]
     if use_lstm:
         spec += [("lstm_kernel", (lstm_in + 256, 1024), None), ("lstm_bias", (1024,), 0)]
     spec += [("W_base_fc_p", (256, A), 256), ("b_base_fc_p", (A,), 256),
@@ -55,7 +63,7 @@ def param_spec(action_size, objective_size=0, use_lstm=True, use_pixel_change=Tr
                  ("W_pc_deconv_v", (4, 4, 1, 32), 512), ("b_pc_deconv_v", (1,), 512),
                  ("W_pc_deconv_a", (4, 4, A, 32), 512), ("b_pc_deconv_a", (A,), 512)]
     if use_reward_prediction:
-        spec += [("W_rp_fc1", (7776, 3), 7776), ("b_rp_fc1", (3,), 7776)]
+        spec += [("W_rp_fc1", (3 * F, 3), 3 * F), ("b_rp_fc1", (3,), 3 * F)]
     return spec
 
 
@@ -86,17 +94,21 @@ class FlatParams(object):
 class PathWS(object):
     """Activations of one trunk pass over `rows` frames (time-major rows t*B + b)."""
 
-    def __init__(self, rows, B, device, save_c1=True, lstm=True, xld=XLD):
+    def __init__(self, rows, B, device, save_c1=True, lstm=True, xld=XLD, f2_dim=ops.F2_DIM, c1_dim=ops.C1_DIM):
         f = lambda n: torch.empty(n, dtype=torch.float32, device=device)
         self.rows, self.B, self.xld = rows, B, xld
         self.fc_partials = {}     # stream handle -> K-slab partial products of the fc product at few rows (encode_rows)
+        self.c1_tmp = {}          # stream handle -> conv1 output of a pass that does not save it (frame sizes != 84 x 84)
         self.s_x = self.s_f2 = self.s_x_cur = self.s_c1 = None     # absmax slots of the rows' LSTM input x / conv output (UnrealModel.encode_rows, per pass)
         self.pass_id = None
+        self.f2_dim, self.c1_dim = f2_dim, c1_dim
         self.frame_idx = torch.zeros(rows, dtype=torch.int32, device=device)
-        self.c1 = f(rows * ops.C1_DIM) if save_c1 else None
-        self.f2 = f(rows * ops.F2_DIM)
-        # ReLU pattern of f2, 1 bit per element (written by the encoder, read by the fc dgrad's epilogue instead of f2)
-        self.f2_bits = torch.zeros(rows * ops.RELU_WORDS, dtype=torch.int16, device=device) if save_c1 else None
+        self.c1 = f(rows * c1_dim) if save_c1 else None
+        self.f2 = f(rows * f2_dim)
+        # ReLU pattern of f2, 1 bit per element (written by the encoder, read by the fc dgrad's epilogue instead of f2); the
+        # 84 x 84 encoder only -- at other frame sizes the dgrad masks with f2 itself
+        self.f2_bits = torch.zeros(rows * ops.RELU_WORDS, dtype=torch.int16, device=device) \
+            if save_c1 and f2_dim == ops.F2_DIM and c1_dim == ops.C1_DIM else None
         self.xcat = torch.zeros(rows * xld, dtype=torch.float32, device=device)
         if lstm:
             self.gates = f(rows * 1024)
@@ -109,12 +121,13 @@ class PathWS(object):
 class GradWS(object):
     """Gradient temporaries shared by all paths (sized for the largest)."""
 
-    def __init__(self, rows, B, device, lstm=True, pc=True, A=4, pc_rows=None):
+    def __init__(self, rows, B, device, lstm=True, pc=True, A=4, pc_rows=None, f2_dim=ops.F2_DIM):
         f = lambda n: torch.empty(n, dtype=torch.float32, device=device)
         pc_rows = rows if pc_rows is None else pc_rows
+        self.f2_dim = f2_dim
         self.d_feat = f(rows * 256)
         self.d_fc = f(rows * 256)
-        self.d_f2 = f(rows * ops.F2_DIM)
+        self.d_f2 = f(rows * f2_dim)
         if lstm:
             self.d_gates = f(rows * 1024)
             self.dh_rec = f(B * 256)
@@ -148,7 +161,7 @@ class GradWS(object):
             return
         f = lambda n: torch.empty(n, dtype=torch.float32, device=device)
         self.rows = rows
-        self.d_feat, self.d_fc, self.d_f2 = f(rows * 256), f(rows * 256), f(rows * ops.F2_DIM)
+        self.d_feat, self.d_fc, self.d_f2 = f(rows * 256), f(rows * 256), f(rows * self.f2_dim)
         if self.lstm:
             self.d_gates = f(rows * 1024)
 
@@ -174,8 +187,21 @@ class UnrealModel(object):
             raise ValueError("objective_size must be >= 0")
         if segnet_param_dict is not None and segnet_param_dict.get("segnet_mode", 0) not in (0, None):
             raise NotImplementedError("only the vanilla encoder (segnet_mode == 0) is on the hot path")
-        if tuple(image_shape) != (84, 84):
-            raise ValueError("the conv encoder kernels are specialised for 84x84x3 frames")
+        self.image_shape = (int(image_shape[0]), int(image_shape[1]))
+        self.hw = self.image_shape != ops.FRAME_SHAPE     # conv trunk on the runtime-size kernels (csrc/encoder_hw.hip)
+        if self.hw:
+            h1, w1, _, _, F = ops.frame_dims(*self.image_shape)     # ValueError outside 20 <= H, W <= 480
+            # the reference hard-codes 9 * 9 * 32 = 2592 in these two places, so they exist at 84 x 84 only
+            if not use_lstm:
+                raise ValueError("image_shape %r: the FF trunk's fc reshapes the conv output to 2592 = 9*9*32 "
+                                 "(reference model.py:309-312); use_lstm=False needs 84x84 frames" % (self.image_shape,))
+            if use_pixel_change:
+                raise ValueError("image_shape %r: the pixel-control head is built for a 9x9x32 map = 2592 "
+                                 "(reference model.py:416-430,554); use_pixel_change=True needs 84x84 frames"
+                                 % (self.image_shape,))
+            self.F, self.c1_dim = F, h1 * w1 * 16
+        else:
+            self.F, self.c1_dim = ops.F2_DIM, ops.C1_DIM
         self._device = torch.device(device if device not in (None, "/gpu:0", "/cpu:0") else "cuda:0")
         self._action_size = action_size
         self._objective_size = objective_size
@@ -193,7 +219,7 @@ class UnrealModel(object):
         self._frame_scale_given = frame_scale is not None
         self.frame_scale = 1.0 if frame_scale is None else float(frame_scale)
         self.spec = param_spec(action_size, objective_size, use_lstm, use_pixel_change, use_value_replay,
-                               use_reward_prediction)
+                               use_reward_prediction, self.image_shape)
         self.params = FlatParams(self.spec, self._device)
         self.grads = FlatParams(self.spec, self._device)
         self.p = self.params.views
@@ -205,6 +231,7 @@ class UnrealModel(object):
         self.total_loss = self.base_loss = self.policy_loss = self.value_loss = None
         self.entropy = self.pc_loss = self.vr_loss = self.rp_loss = None
         self._b1 = None
+        self._c1_tmp, self._enc_work = {}, {}      # per-stream conv scratch of the runtime-size encoder (encoder_forward / _backward)
         self._shadow = None
         self._shadow_stale = True
         # absmax slots (fp16x2 GEMM scales, csrc/gemm_split.hip): a pool zeroed once per pass; a constant 1.0 for tensors
@@ -240,8 +267,9 @@ class UnrealModel(object):
             # (ops.ShadowSet; per matrix it was fill + maximum + split: ~28 launches in front of every learner pass)
             ss = ops.ShadowSet(self._device, 12)
             S = lambda *a, **k: ss.add(ops.SplitWeights(*a, wmax=ss.slot(), defer=True, **k))
-            sh = dict(fc1_fwd=S(p["W_base_fc1"], 2592, 256, 256, True),
-                      fc1_dgrad=S(p["W_base_fc1"], 2592, 256, 256, False))
+            F = self.F
+            sh = dict(fc1_fwd=S(p["W_base_fc1"], F, 256, 256, True),
+                      fc1_dgrad=S(p["W_base_fc1"], F, 256, 256, False))
             if self._use_lstm:
                 W = p["lstm_kernel"]
                 sh.update(lstm_xh_fwd=ss.add(ops.LstmKernelShadow(W, K_x, wmax=ss.slot(), defer=True)),   # whole kernel, single-step launches
@@ -255,7 +283,7 @@ class UnrealModel(object):
                           pc_fc1_dgrad=S(p["W_pc_fc1"], 256, 2592, 2592, False))
             self._shadow, self._shadow_set = sh, ss
         self._shadow_set.refresh()
-        if self.prepare_encoder:
+        if self.prepare_encoder and not self.hw:
             # the conv weights' share of encoder_fwd's prologue (scales + MFMA operand fragments), once per update instead
             # of once per workgroup of each of the ~24 encoder launches that follow
             p = self.p
@@ -269,7 +297,7 @@ class UnrealModel(object):
     @property
     def enc_prepared(self):
         """Block of ops.encoder_prepare for the current conv weights and self.frame_scale (None: prepare_encoder off)."""
-        if not self.prepare_encoder:
+        if not self.prepare_encoder or self.hw:
             return None
         if self._enc_prep is None or self._shadow_stale:
             self.refresh_shadows()
@@ -293,6 +321,53 @@ class UnrealModel(object):
             ss.refresh()
         return sh
 
+    # -- frame size -------------------------------------------------------------------------------------
+    @property
+    def ws_kw(self):
+        """Sizes of this network's conv activations, for PathWS / GradWS."""
+        return dict(f2_dim=self.F, c1_dim=self.c1_dim)
+
+    def new_path_ws(self, rows, B, device=None, save_c1=True, lstm=None):
+        return PathWS(rows, B, self._device if device is None else device, save_c1=save_c1,
+                      lstm=self._use_lstm if lstm is None else lstm, xld=self.xld, **self.ws_kw)
+
+    def _stream_buf(self, cache, n, device):
+        """A float buffer of >= n elements owned by the current stream (passes on several streams must not share one)."""
+        key = torch.cuda.current_stream(device).cuda_stream
+        buf = cache.get(key)
+        if buf is None or buf.numel() < n:
+            buf = cache[key] = torch.empty(n, dtype=torch.float32, device=device)
+        return buf
+
+    def encoder_forward(self, ring, idx, f2, c1=None, relu_bits=None, f2_max=None, c1_max=None, ws=None, scale=None):
+        """conv trunk of the frames ring.frames[idx] -> f2 [N, F] (and c1 when given): the 84 x 84 kernels at 84 x 84, the
+        runtime-size kernels otherwise (which need c1: without one the workspace's per-stream scratch is used)."""
+        scale = self.frame_scale if scale is None else scale
+        p = self.p
+        if not self.hw:
+            ops.encoder_fwd(ring.frames, idx, scale, p["W_base_conv1"], p["b_base_conv1"], p["W_base_conv2"],
+                            p["b_base_conv2"], f2, c1, relu_bits=relu_bits, f2_max=f2_max, c1_max=c1_max,
+                            prepared=self.enc_prepared)
+            return
+        if tuple(ring.frame_shape) != self.image_shape:
+            raise ValueError("ring frames are %r, the network's image_shape is %r" % (ring.frame_shape, self.image_shape))
+        if c1 is None:
+            cache = ws.c1_tmp if ws is not None else self._c1_tmp
+            c1 = self._stream_buf(cache, idx.numel() * self.c1_dim, f2.device)
+        ops.encoder_hw_fwd(ring.frames, idx, self.image_shape, ring.frame_stride, scale, p["W_base_conv1"],
+                           p["b_base_conv1"], p["W_base_conv2"], p["b_base_conv2"], c1, f2, f2_max=f2_max)
+
+    def encoder_backward(self, ring, idx, c1, d2, c1_max=None, d2_max=None):
+        """Gradient of encoder_forward into self.g (d2 = d(loss)/d(conv2 pre-activation), [N, F])."""
+        p, g = self.p, self.g
+        if not self.hw:
+            ops.encoder_bwd(ring.frames, idx, self.frame_scale, p["W_base_conv2"], c1, d2, g["W_base_conv1"],
+                            g["b_base_conv1"], g["W_base_conv2"], g["b_base_conv2"], c1_max=c1_max, d2_max=d2_max)
+            return
+        work = self._stream_buf(self._enc_work, ops.encoder_hw_work_floats(idx.numel(), self.image_shape), d2.device)
+        ops.encoder_hw_bwd(ring.frames, idx, self.image_shape, ring.frame_stride, self.frame_scale, p["W_base_conv2"], c1,
+                           d2, g["W_base_conv1"], g["b_base_conv1"], g["W_base_conv2"], g["b_base_conv2"], work)
+
     # -- parameters ---------------------------------------------------------------------------------
     def _init_weights(self, seed):
         """U(+-1/sqrt(fan_in)) for W and b (model.py:31-42,752-783); LSTM kernel glorot_uniform, bias 0."""
@@ -315,6 +390,10 @@ class UnrealModel(object):
         """Load {name: array} (TF layouts), e.g. parameters exported by another implementation."""
         self._shadow_stale = True
         for k, v in named.items():
+            shape = self.params.offsets[k][2]
+            if tuple(np.shape(v)) != tuple(shape) and np.size(v) != int(np.prod(shape)):
+                raise ValueError("%s: got shape %r, this network's is %r (image_shape %r)"
+                                 % (k, tuple(np.shape(v)), tuple(shape), self.image_shape))
             self.p[k].copy_(torch.as_tensor(np.asarray(v, dtype=np.float32).reshape(-1)))
 
     def export_named(self):
@@ -364,9 +443,10 @@ class UnrealModel(object):
         whose lstm_step(fused_x=True) multiplies [x | h] by the whole kernel, so the input half is not hoisted."""
         p = self.p
         idx = ws.frame_idx[row0:row0 + nrows]
-        f2 = ws.f2[row0 * ops.F2_DIM:]
+        F = self.F
+        f2 = ws.f2[row0 * F:]
         xcat = ws.xcat[row0 * self.xld:]
-        c1 = ws.c1[row0 * ops.C1_DIM:] if (save_c1 and ws.c1 is not None) else None
+        c1 = ws.c1[row0 * self.c1_dim:] if (save_c1 and ws.c1 is not None) else None
         bits = ws.f2_bits[row0 * ops.RELU_WORDS:] if (c1 is not None and ws.f2_bits is not None) else None
         # absmax slots: the encoder commits max f2, the fc GEMM reads it and commits max of its own output -- the scale of
         # the product that multiplies the fc row next (LSTM step: [fc | last action, reward, objective | h])
@@ -379,11 +459,10 @@ class UnrealModel(object):
         self.ws_slots(ws)
         own = actor_ring is not None and slots is None
         s_f2, s_fc = slots if slots is not None else ((self.new_slot(), self.new_slot()) if own else (ws.s_f2, ws.s_x))
-        ops.encoder_fwd(ring.frames, idx, self.frame_scale, p["W_base_conv1"], p["b_base_conv1"],
-                        p["W_base_conv2"], p["b_base_conv2"], f2, c1, relu_bits=bits, f2_max=s_f2,
-                        c1_max=ws.s_c1 if c1 is not None else None, prepared=self.enc_prepared)
+        self.encoder_forward(ring, idx, f2, c1, relu_bits=bits, f2_max=s_f2, c1_max=ws.s_c1 if c1 is not None else None,
+                             ws=ws)
         sh = self.shadow
-        nslab = ops.slab_count(nrows, 256, 2592) if self.fc_few_rows_slabs else 0
+        nslab = ops.slab_count(nrows, 256, F) if self.fc_few_rows_slabs else 0
         if nslab:
             # few rows (a group's rollout step, a small update's replay pass): 4-64 tiles of 81 dependent K steps would
             # leave most of the chip idle -- 2-8 K slabs in separate workgroups + an ordered sum (one partials buffer per stream:
@@ -392,10 +471,10 @@ class UnrealModel(object):
             part = ws.fc_partials.get(key)
             if part is None or part.numel() < nslab * nrows * 256:
                 part = ws.fc_partials[key] = torch.empty(nslab * nrows * 256, dtype=torch.float32, device=f2.device)
-            ops.gemm_split_nt_slabs(nrows, 256, 2592, f2, 2592, sh["fc1_fwd"], xcat, self.xld, part, nslab,
+            ops.gemm_split_nt_slabs(nrows, 256, F, f2, F, sh["fc1_fwd"], xcat, self.xld, part, nslab,
                                     bias=p["b_base_fc1"], flags=ops.GEMM_RELU, a_max=s_f2, c_max=s_fc)
         else:
-            ops.gemm_split_nt(nrows, 256, 2592, f2, 2592, sh["fc1_fwd"], xcat, self.xld, bias=p["b_base_fc1"],
+            ops.gemm_split_nt(nrows, 256, F, f2, F, sh["fc1_fwd"], xcat, self.xld, bias=p["b_base_fc1"],
                               flags=ops.GEMM_RELU, a_max=s_f2, c_max=s_fc)
         ws.s_x_cur = s_fc          # max over the fc columns; the other columns of x are added below where they can exceed 1
         if own:
@@ -531,18 +610,17 @@ class UnrealModel(object):
             ops.relu_mask(rows, 256, d_feat, 256, ws.xcat, self.xld)
             d_fc = d_feat
             s_dfc = ops.absmax(rows, 256, d_fc, 256, self.new_slot())
-        ops.gemm_split_tn(2592, 256, rows, ws.f2, 2592, d_fc, 256, g["W_base_fc1"], 256,
-                              splitk=_splitk(2592, 256, rows), colsum=g["b_base_fc1"], a_max=ws.s_f2, b_max=s_dfc)
+        F = self.F
+        ops.gemm_split_tn(F, 256, rows, ws.f2, F, d_fc, 256, g["W_base_fc1"], 256,
+                              splitk=_splitk(F, 256, rows), colsum=g["b_base_fc1"], a_max=ws.s_f2, b_max=s_dfc)
         s_df2 = self.new_slot()            # max |d_f2|: committed by the fc dgrad's epilogue, the d2 scale of the conv backward
         if ws.f2_bits is not None and self.relu_bits:
-            ops.gemm_split_nt(rows, 2592, 256, d_fc, 256, sh["fc1_dgrad"], gws.d_f2, 2592, mask=ws.f2_bits,
+            ops.gemm_split_nt(rows, F, 256, d_fc, 256, sh["fc1_dgrad"], gws.d_f2, F, mask=ws.f2_bits,
                               ldm=ops.RELU_WORDS, flags=ops.GEMM_RELU_BITS, a_max=s_dfc, c_max=s_df2)
         else:
-            ops.gemm_split_nt(rows, 2592, 256, d_fc, 256, sh["fc1_dgrad"], gws.d_f2, 2592, mask=ws.f2, ldm=2592,
+            ops.gemm_split_nt(rows, F, 256, d_fc, 256, sh["fc1_dgrad"], gws.d_f2, F, mask=ws.f2, ldm=F,
                               flags=ops.GEMM_RELU_MASK, a_max=s_dfc, c_max=s_df2)
-        ops.encoder_bwd(ring.frames, ws.frame_idx[:rows], self.frame_scale, p["W_base_conv2"], ws.c1, gws.d_f2,
-                        g["W_base_conv1"], g["b_base_conv1"], g["W_base_conv2"], g["b_base_conv2"],
-                        c1_max=ws.s_c1, d2_max=s_df2)
+        self.encoder_backward(ring, ws.frame_idx[:rows], ws.c1, gws.d_f2, c1_max=ws.s_c1, d2_max=s_df2)
 
     def heads_forward(self, rows, feat, ld, pi_out, v_out):
         p, A = self.p, self._action_size
@@ -575,9 +653,11 @@ class UnrealModel(object):
     def _b1_ws(self):
         if self._b1 is None:
             dev = self._device
-            self._b1 = dict(ring=ops.Ring(3, 1, dev, objective_size=self._objective_size), ws=PathWS(3, 3, dev, save_c1=False, lstm=self._use_lstm, xld=self.xld),
+            self._b1 = dict(ring=ops.Ring(3, 1, dev, objective_size=self._objective_size, frame_shape=self.image_shape),
+                            ws=self.new_path_ws(3, 3, dev, save_c1=False),
                             pi=torch.zeros(self._action_size, device=dev), v=torch.zeros(1, device=dev),
-                            hp=torch.zeros(2592, device=dev), q=torch.zeros(400, device=dev),
+                            hp=torch.zeros(2592, device=dev) if self._use_pixel_change else None,
+                            q=torch.zeros(400, device=dev),
                             z=torch.zeros(3, device=dev))
         return self._b1
 
@@ -586,10 +666,13 @@ class UnrealModel(object):
         b1 = self._b1_ws()
         ring, ws = b1["ring"], b1["ws"]
         n = len(images)
+        fs = ring.frame_stride
         for k, img in enumerate(images):
             a = np.asarray(img, dtype=np.float64)
+            if a.shape[:2] != self.image_shape:
+                raise ValueError("image of shape %r, the network's image_shape is %r" % (a.shape, self.image_shape))
             u8 = np.clip(np.rint(a * 255.0), 0, 255).astype(np.uint8).reshape(-1)
-            ring.frames[k * ops.FRAME_BYTES:(k + 1) * ops.FRAME_BYTES].copy_(torch.from_numpy(u8))
+            ring.frames[k * fs:k * fs + u8.size].copy_(torch.from_numpy(u8))
         ws.frame_idx[:n].copy_(torch.arange(n, dtype=torch.int32))
         if last_action_reward is not None:
             lar = np.asarray(last_action_reward, dtype=np.float32)
@@ -653,8 +736,12 @@ class UnrealModel(object):
         b1 = self._b1_ws()
         ring, ws = self._stage([s['image'] for s in state_history])
         p = self.p
-        ops.encoder_fwd(ring.frames, ws.frame_idx[:3], 1.0 / 255.0, p["W_base_conv1"], p["b_base_conv1"],
-                        p["W_base_conv2"], p["b_base_conv2"], ws.f2, None)
-        ops.linear_small_fwd(1, 7776, 3, ws.f2, 7776, p["W_rp_fc1"], p["b_rp_fc1"], b1["z"], 3)
+        if self.hw:
+            self.encoder_forward(ring, ws.frame_idx[:3], ws.f2, ws=ws, scale=1.0 / 255.0)
+        else:
+            ops.encoder_fwd(ring.frames, ws.frame_idx[:3], 1.0 / 255.0, p["W_base_conv1"], p["b_base_conv1"],
+                            p["W_base_conv2"], p["b_base_conv2"], ws.f2, None)
+        F3 = 3 * self.F
+        ops.linear_small_fwd(1, F3, 3, ws.f2, F3, p["W_rp_fc1"], p["b_rp_fc1"], b1["z"], 3)
         ops.softmax_sample(1, 3, b1["z"], 3)
         return b1["z"].cpu().numpy()

@@ -15,6 +15,27 @@ C1_DIM = 6400
 GEMM_RELU, GEMM_ACCUM, GEMM_ATOMIC, GEMM_RELU_MASK, GEMM_RELU_BITS = 1, 2, 4, 8, 16
 RELU_WORDS = 162                      # uint16 words of ReLU bits per frame (2592 / 16)
 
+FRAME_SHAPE = (84, 84)                # maze, Lab, gym and the default indoor frame
+FRAME_HW_MIN, FRAME_HW_MAX = 20, 480  # frame sizes of the indoor contract (encoder_hw_fwd / hostfed_step_hw)
+
+
+def frame_dims(H, W):
+    """Conv trunk widths of an H x W x 3 frame (model.py:786-787, VALID): (h1, w1, h2, w2, F = 32 * h2 * w2).
+    Raises ValueError outside 20 <= H, W <= 480."""
+    H, W = int(H), int(W)
+    if not (FRAME_HW_MIN <= H <= FRAME_HW_MAX and FRAME_HW_MIN <= W <= FRAME_HW_MAX):
+        raise ValueError("frame size %dx%d: supported are %d <= H, W <= %d" % (H, W, FRAME_HW_MIN, FRAME_HW_MAX))
+    h1, w1 = (H - 8) // 4 + 1, (W - 8) // 4 + 1
+    h2, w2 = (h1 - 4) // 2 + 1, (w1 - 4) // 2 + 1
+    return h1, w1, h2, w2, 32 * h2 * w2
+
+
+def frame_stride(H, W):
+    """Bytes between two H x W x 3 frames of a ring or staging buffer: H * W * 3 rounded up to 16 (the ingest kernels
+    copy 16 B per lane).  84 x 84 gives FRAME_BYTES."""
+    return (int(H) * int(W) * 3 + 15) // 16 * 16
+
+
 _DT = {"f32": torch.float32, "i32": torch.int32, "u8": torch.uint8, "f64": torch.float64, "i16": torch.int16}
 
 
@@ -76,12 +97,16 @@ def kernel_timer_stop():
 class Ring(object):
     """Device replay ring + per-actor environment state (layout: include/unreal_hip.h)."""
 
-    def __init__(self, B, H, device, objective_size=0):
+    def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE):
         self.B, self.H, self.H1 = B, H, H + 1
         self.objective_size = objective_size
+        self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
+        if self.frame_shape != FRAME_SHAPE:
+            frame_dims(*self.frame_shape)                    # raises outside the supported sizes
+        self.frame_stride = frame_stride(*self.frame_shape)
         n = B * self.H1
         z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=device)
-        self.frames = torch.empty(n * FRAME_BYTES, dtype=torch.uint8, device=device)
+        self.frames = torch.empty(n * self.frame_stride, dtype=torch.uint8, device=device)
         self.r_reward = z(n)
         self.r_action = z(n, dt=torch.int32)
         self.r_terminal = z(n, dt=torch.int32)
@@ -112,8 +137,9 @@ def ring_view(ring, b0, b1):
     """The actors [b0, b1) of a ring as a Ring of their own (no copy: frame indices are relative to the view)."""
     v = object.__new__(Ring)
     v.B, v.H, v.H1, v.objective_size = b1 - b0, ring.H, ring.H1, ring.objective_size
-    H1 = ring.H1
-    v.frames = ring.frames[b0 * H1 * FRAME_BYTES:b1 * H1 * FRAME_BYTES]
+    v.frame_shape, v.frame_stride = ring.frame_shape, ring.frame_stride
+    H1, fs = ring.H1, ring.frame_stride
+    v.frames = ring.frames[b0 * H1 * fs:b1 * H1 * fs]
     for name in ("r_reward", "r_action", "r_terminal", "r_last_action", "r_last_reward"):
         setattr(v, name, getattr(ring, name)[b0 * H1:b1 * H1])
     v.r_pc = ring.r_pc[b0 * H1 * PC_CELLS:b1 * H1 * PC_CELLS]
@@ -244,6 +270,32 @@ def hostfed_reset(ring, staged, mask=None):
     _chk(staged, "u8", ring.B * FRAME_BYTES, "staged"); _chk(mask, "i32", ring.B, optional=True)
     _call("unreal_hostfed_reset", ring.B, ring.H1, ptr(mask), ptr(staged), ptr(ring.last_action),
           ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames))
+
+
+def hostfed_step_hw(ring, staged, actions, rewards, terminals, active=None, out_reward=None, out_terminal=None,
+                    reset_on_terminal=True, track_score=False, clip_reward=False):
+    """hostfed_step for a ring of ring.frame_shape frames (the indoor contract at any size): `staged` holds one frame per
+    actor, ring.frame_stride bytes apart; no pixel change (ring.r_pc is not written)."""
+    B = ring.B
+    H, W = ring.frame_shape
+    frame_dims(H, W)
+    _chk(staged, "u8", B * ring.frame_stride, "staged"); _chk(actions, "i32", B, "actions")
+    _chk(rewards, "f32", B, "rewards"); _chk(terminals, "i32", B, "terminals")
+    _chk(active, "i32", B, "active", optional=True)
+    _chk(out_reward, "f32", B, "out_reward", optional=True); _chk(out_terminal, "i32", B, "out_terminal", optional=True)
+    _call("unreal_hostfed_step_hw", B, ring.H1, H, W, ring.frame_stride, ptr(staged), ptr(actions), ptr(rewards),
+          ptr(terminals), ptr(active), ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames),
+          ptr(ring.r_reward), ptr(ring.r_action), ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward),
+          ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid),
+          int(reset_on_terminal), int(track_score), int(clip_reward))
+
+
+def hostfed_reset_hw(ring, staged, mask=None):
+    H, W = ring.frame_shape
+    frame_dims(H, W)
+    _chk(staged, "u8", ring.B * ring.frame_stride, "staged"); _chk(mask, "i32", ring.B, "mask", optional=True)
+    _call("unreal_hostfed_reset_hw", ring.B, ring.H1, H, W, ring.frame_stride, ptr(mask), ptr(staged),
+          ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames))
 
 
 def frame_resize(n, Hs, Ws, src, dst, mask=None):
@@ -392,6 +444,48 @@ def encoder_bwd(frames, frame_idx, scale, W2, c1_saved, d2, dW1, db1, dW2, db2, 
     d2_max = _absmax_of(d2, 1, N * F2_DIM, N * F2_DIM, d2_max)
     _call("unreal_encoder_bwd", N, ptr(frames), ptr(frame_idx), float(scale), ptr(W2), ptr(c1_saved), ptr(c1_max), ptr(d2),
           ptr(d2_max), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2))
+
+
+def encoder_hw_fwd(frames, frame_idx, frame_shape, stride, scale, W1, b1, W2, b2, c1_out, f2_out, f2_max=None):
+    """The conv trunk at frame_shape = (H, W) (csrc/encoder_hw.hip): frames uint8 `stride` bytes apart, c1_out
+    [N, h1, w1, 16] (required), f2_out [N, h2, w2, 32]; f2_max: optional absmax slot that receives max f2."""
+    H, W = int(frame_shape[0]), int(frame_shape[1])
+    h1, w1, h2, w2, F = frame_dims(H, W)
+    N = frame_idx.numel()
+    if stride < H * W * 3:
+        raise ValueError("frame stride %d < %d" % (stride, H * W * 3))
+    _chk(frames, "u8", stride, "frames"); _chk(frame_idx, "i32", N, "frame_idx")
+    _chk(W1, "f32", 3072, "W1"); _chk(b1, "f32", 16, "b1"); _chk(W2, "f32", 8192, "W2"); _chk(b2, "f32", 32, "b2")
+    _chk(c1_out, "f32", N * h1 * w1 * 16, "c1_out"); _chk(f2_out, "f32", N * F, "f2_out")
+    _chk(f2_max, "f32", 1, "f2_max", optional=True)
+    _call("unreal_encoder_hw_fwd", N, H, W, ptr(frames), int(stride), ptr(frame_idx), float(scale), ptr(W1), ptr(b1),
+          ptr(W2), ptr(b2), ptr(c1_out), ptr(f2_out), ptr(f2_max))
+
+
+def encoder_hw_work_floats(N, frame_shape):
+    """Floats of the work buffer encoder_hw_bwd needs for N frames of frame_shape (host-only query)."""
+    import ctypes
+    frame_dims(*frame_shape)
+    out = ctypes.c_long(0)
+    lib().call("unreal_encoder_hw_work_floats", int(N), int(frame_shape[0]), int(frame_shape[1]), ctypes.byref(out), None)
+    return out.value
+
+
+def encoder_hw_bwd(frames, frame_idx, frame_shape, stride, scale, W2, c1_saved, d2, dW1, db1, dW2, db2, work):
+    """Backward of encoder_hw_fwd: d2 = d(loss)/d(conv2 pre-activation) [N, h2, w2, 32]; ADDS into dW1, db1, dW2, db2
+    (deterministic: slab partials summed in a fixed order).  work: fp32, >= encoder_hw_work_floats(N, frame_shape)."""
+    H, W = int(frame_shape[0]), int(frame_shape[1])
+    h1, w1, h2, w2, F = frame_dims(H, W)
+    N = frame_idx.numel()
+    if stride < H * W * 3:
+        raise ValueError("frame stride %d < %d" % (stride, H * W * 3))
+    nw = encoder_hw_work_floats(N, (H, W))
+    _chk(frames, "u8", stride, "frames"); _chk(frame_idx, "i32", N, "frame_idx"); _chk(W2, "f32", 8192, "W2")
+    _chk(c1_saved, "f32", N * h1 * w1 * 16, "c1_saved"); _chk(d2, "f32", N * F, "d2")
+    _chk(dW1, "f32", 3072, "dW1"); _chk(db1, "f32", 16, "db1"); _chk(dW2, "f32", 8192, "dW2"); _chk(db2, "f32", 32, "db2")
+    _chk(work, "f32", nw, "work")
+    _call("unreal_encoder_hw_bwd", N, H, W, ptr(frames), int(stride), ptr(frame_idx), float(scale), ptr(W2), ptr(c1_saved),
+          ptr(d2), ptr(work), work.numel(), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2))
 
 
 def gemm(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias=None, mask=None, ldm=0, flags=0, splitk=1):

@@ -103,6 +103,12 @@ class Trainer(object):
         self.max_global_time_step = max_global_time_step
         self.action_size = Environment.get_action_size(env_type, env_name)
         self.objective_size = Environment.get_objective_size(env_type, env_name)
+        # frame size: the network's image_shape must be the environment's (main.py:196 builds both from the MINOS config)
+        self.image_shape = tuple(int(x) for x in Environment.get_image_shape(env_type, env_name))
+        net_shape = tuple(getattr(global_network, "image_shape", (84, 84)))
+        if net_shape != self.image_shape:
+            raise ValueError("the network's image_shape %r differs from the environment's %r (Environment.get_image_shape"
+                             "(%r, %r))" % (net_shape, self.image_shape, env_type, env_name))
         self.device = torch.device(device if device not in (None, "/gpu:0", "/cpu:0") else "cuda:0")
         self.B = int(batch_size)                     # actors of this rank
         self.groups = int(groups)                    # sequential updates per process() call
@@ -145,6 +151,10 @@ class Trainer(object):
             if indoor and getattr(self.simulator, "objective_size", 0) != self.objective_size:
                 raise ValueError("simulator.objective_size != Environment.get_objective_size(%r, %r) = %d"
                                  % (self.env_type, self.env_name, self.objective_size))
+            if indoor and tuple(getattr(self.simulator, "image_shape", (84, 84))) != self.image_shape:
+                raise ValueError("simulator.image_shape %r != Environment.get_image_shape(%r, %r) = %r"
+                                 % (getattr(self.simulator, "image_shape", (84, 84)), self.env_type, self.env_name,
+                                    self.image_shape))
             gym = self.env_type == "gym"        # raw frames, resized on the device; rewards unclipped (experience.py)
             if gym and not hasattr(self.simulator, "frame_shape"):
                 raise ValueError("env_type='gym' needs a simulator with frame_shape (gym_environment.GymBatchSimulator)")
@@ -152,7 +162,8 @@ class Trainer(object):
                                                   action_size=A, clip_reward=not (indoor or gym),
                                                   objective_size=self.objective_size,
                                                   reward_divisor=termination_time if indoor else 1.0,
-                                                  raw_frame_shape=self.simulator.frame_shape if gym else None)
+                                                  raw_frame_shape=self.simulator.frame_shape if gym else None,
+                                                  frame_shape=self.image_shape if indoor else None)
         self.overlap_host = False
         if self.env_type != "maze":
             want = self._overlap_request if self._overlap_request is not None else (B % 2 == 0 and B >= 2048)
@@ -170,9 +181,10 @@ class Trainer(object):
         lstm = self.use_lstm
         aux = self.use_pixel_change or self.use_value_replay
         xld = self.local_network.xld
-        self.base_ws = PathWS(T * B, B, dev, save_c1=True, lstm=lstm, xld=xld)
-        self.boot_ws = PathWS(B, B, dev, save_c1=False, lstm=lstm, xld=xld)
-        self.rp_ws = PathWS(3 * B, B, dev, save_c1=True, lstm=False, xld=xld) if self.use_reward_prediction else None
+        wkw = self.local_network.ws_kw                # conv activation sizes of the network's frame size
+        self.base_ws = PathWS(T * B, B, dev, save_c1=True, lstm=lstm, xld=xld, **wkw)
+        self.boot_ws = PathWS(B, B, dev, save_c1=False, lstm=lstm, xld=xld, **wkw)
+        self.rp_ws = PathWS(3 * B, B, dev, save_c1=True, lstm=False, xld=xld, **wkw) if self.use_reward_prediction else None
         # pixel control and value replay as ONE batch of 2B replayed sequences (actor 2b = pc sample of b, 2b + 1 = vr
         # sample): see _train_aux_batched.  Decided HERE, once (the class default is read at prepare() time only).
         self.batch_aux = bool(self.batch_aux_default and self.use_pixel_change and self.use_value_replay)
@@ -182,11 +194,11 @@ class Trainer(object):
         self._aux_ws_args = (Ta * B, B, dev, lstm, xld) if aux else None
         per_branch = aux and not self.batch_aux
         rows = max(T, Ta if per_branch else 0, 3 if self.use_reward_prediction else 0) * B
-        self.gws = GradWS(rows, B, dev, lstm=lstm, pc=self.use_pixel_change and per_branch, A=A)
+        self.gws = GradWS(rows, B, dev, lstm=lstm, pc=self.use_pixel_change and per_branch, A=A, f2_dim=wkw["f2_dim"])
         if self.batch_aux:
-            self.aux2_ws = PathWS(Ta * 2 * B, 2 * B, dev, save_c1=True, lstm=lstm, xld=xld)
-            self.boot2_ws = PathWS(2 * B, 2 * B, dev, save_c1=False, lstm=lstm, xld=xld)
-            self.gws2 = GradWS(Ta * 2 * B, 2 * B, dev, lstm=lstm, pc=True, A=A, pc_rows=Ta * B)
+            self.aux2_ws = PathWS(Ta * 2 * B, 2 * B, dev, save_c1=True, lstm=lstm, xld=xld, **wkw)
+            self.boot2_ws = PathWS(2 * B, 2 * B, dev, save_c1=False, lstm=lstm, xld=xld, **wkw)
+            self.gws2 = GradWS(Ta * 2 * B, 2 * B, dev, lstm=lstm, pc=True, A=A, pc_rows=Ta * B, f2_dim=wkw["f2_dim"])
         f = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
         i = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
         d = lambda n: torch.zeros(n, dtype=torch.float64, device=dev)
@@ -238,7 +250,7 @@ class Trainer(object):
         """Workspace of the one-branch-at-a-time replay schedule (lazy: see prepare())."""
         if self._aux_ws is None and self._aux_ws_args is not None:
             rows, B, dev, lstm, xld = self._aux_ws_args
-            self._aux_ws = PathWS(rows, B, dev, save_c1=True, lstm=lstm, xld=xld)
+            self._aux_ws = PathWS(rows, B, dev, save_c1=True, lstm=lstm, xld=xld, **self.local_network.ws_kw)
             self.gws.ensure_rows(rows, B, dev)
         return self._aux_ws
 
@@ -660,18 +672,16 @@ class Trainer(object):
         self.draws.uniform(self.rp_u)
         ops.replay_sample_rp(self.ring, self.rp_coin, self.rp_u, ws.frame_idx[:3 * B], self.rp_class, self.rp_mode)
         s_c1 = net.new_slot()              # max of the conv1 activation: the c1 scale of the conv backward below
-        ops.encoder_fwd(self.ring.frames, ws.frame_idx[:3 * B], net.frame_scale, p["W_base_conv1"],
-                        p["b_base_conv1"], p["W_base_conv2"], p["b_base_conv2"], ws.f2, ws.c1, c1_max=s_c1,
-                        prepared=net.enc_prepared)
-        ops.linear_small_fwd(B, 7776, 3, ws.f2, 7776, p["W_rp_fc1"], p["b_rp_fc1"], self.rp_logits, 3)
+        F = net.F                          # 2592 at 84 x 84; the rp fc is [3F, 3] (model.py:480-484)
+        net.encoder_forward(self.ring, ws.frame_idx[:3 * B], ws.f2, ws.c1, c1_max=s_c1, ws=ws)
+        ops.linear_small_fwd(B, 3 * F, 3, ws.f2, 3 * F, p["W_rp_fc1"], p["b_rp_fc1"], self.rp_logits, 3)
         ops.rp_loss_grad(B, self.rp_logits, self.rp_class, self.grad_scale, None, self.rp_dlogits,
                          self.losses[5:6])
-        ops.linear_small_bwd(B, 7776, 3, ws.f2, 7776, self.rp_dlogits, 3, p["W_rp_fc1"], gws.d_f2, 7776, False,
+        ops.linear_small_bwd(B, 3 * F, 3, ws.f2, 3 * F, self.rp_dlogits, 3, p["W_rp_fc1"], gws.d_f2, 3 * F, False,
                              g["W_rp_fc1"], g["b_rp_fc1"])
-        ops.relu_mask(3 * B, 2592, gws.d_f2, 2592, ws.f2, 2592)
-        ops.encoder_bwd(self.ring.frames, ws.frame_idx[:3 * B], net.frame_scale, p["W_base_conv2"], ws.c1,
-                        gws.d_f2, g["W_base_conv1"], g["b_base_conv1"], g["W_base_conv2"], g["b_base_conv2"],
-                        c1_max=s_c1)           # (d_f2's maximum: reduced by the wrapper, 127 MB at 4096 actors)
+        ops.relu_mask(3 * B, F, gws.d_f2, F, ws.f2, F)
+        net.encoder_backward(self.ring, ws.frame_idx[:3 * B], ws.c1, gws.d_f2,
+                             c1_max=s_c1)      # (d_f2's maximum: reduced by the wrapper, 127 MB at 4096 actors)
 
     # ---------------------------------------------------------------------------------------------------
     def compute_gradients(self):
