@@ -241,13 +241,9 @@ int unreal_gemm_f32_split_nt_slabs(int M, int N, int K, const float* A, int lda,
  * K = 81,920). */
 int unreal_gemm_f32_split_tn(int M, int N, int K, const float* A, int lda, const float* a_absmax, const float* B, int ldb,
                              const float* b_absmax, float* C, int ldc, float* colsum, int splitk, void* stream);
-/* bf16x3 shadow of a weight matrix src[rows][cols]: dst[t][r][c] (transpose = 0) or dst[t][c][r] (transpose = 1),
- * t = 0..2 the bf16 terms (sum of the three == src to 2^-24 relative).  dst padding is left untouched (zero it once).
- * (The round-2 operand format; the trainer's shadows are fp16x2 now.) */
-int unreal_split_bf16x3(int rows, int cols, const float* src, int ld_src, int transpose, int row_perm, uint16_t* dst,
-                        int ld_dst, long plane_stride, void* stream);
-/* fp16x2 shadow: dst[0] = hi, dst[1] = lo of src * 2^k, k from w_absmax (a slot that already holds max |src| over the
- * WHOLE matrix the consuming GEMM multiplies by).  Same layouts / row_perm as above.  Refreshed after every RMSProp step /
+/* fp16x2 shadow of a weight matrix src[rows][cols]: dst[t][r][c] (transpose = 0) or dst[t][c][r] (transpose = 1),
+ * dst[0] = hi, dst[1] = lo of src * 2^k, k from w_absmax (a slot that already holds max |src| over the WHOLE matrix the
+ * consuming GEMM multiplies by).  dst padding is left untouched (zero it once).  Refreshed after every RMSProp step /
  * checkpoint restore. */
 /* Every weight shadow of a network in one pass (round 4): `abs_descs` = n_abs records {const float* src; float* wmax; long n;
  * long block0} (contiguous matrices; block0 = first block of the record in a grid of 8192-float blocks, ascending), `split_descs`
@@ -264,8 +260,8 @@ int unreal_split_f16x2(int rows, int cols, const float* src, int ld_src, int tra
 /* One BasicLSTMCell step (model/model.py:110,346-351; gates i,j,f,o, forget_bias 1) on the split-operand path with the
  * gate math in the GEMM epilogue.  gates [rows][1024]: out = activated gates (saved for the backward).
  *   x == NULL: gates holds the input-half pre-activations (x * Wx, hoisted over all T steps of a training sequence)
- *              on entry; W3 = gate-interleaved bf16x3 shadow of the kernel's recurrent rows [1024][256]
- *              (unreal_split_bf16x3 transpose = 1, row_perm = 1) and only h_prev[rows,256] * Wh is multiplied here;
+ *              on entry; W3 = gate-interleaved fp16x2 shadow of the kernel's recurrent rows [1024][256]
+ *              (unreal_split_f16x2 transpose = 1, row_perm = 1) and only h_prev[rows,256] * Wh is multiplied here;
  *   x != NULL: the cell's own product [x | h_prev] @ kernel in ONE launch (a rollout step, where the input half cannot
  *              be hoisted): x[rows][Kx] (row stride ldx), W3 = gate-interleaved shadow of the WHOLE kernel,
  *              [1024][pad32(Kx) + 256]: columns [0, Kx) the input rows, zeros up to pad32(Kx), then the recurrent rows. */

@@ -384,7 +384,7 @@ def _err_stats(C, R):
 
 
 def test_fullshape_split_gemms_not_worse_than_fp32_mfma_on_live_operands(branches):
-    """The fp16 hi + lo gate as a test (was tools/exp/f16x2_gate.py): the five big products of the base
+    """The fp16 hi + lo gate as a test (was tools/exp/f16x2_gate.py at b4f3617): the five big products of the base
     branch re-launched on the trainer's LIVE 81,920-row operands through both kernels -- rms error and 99.99th-percentile
     error of unreal_gemm_f32_split_nt / _tn against fp64 must not exceed the plain fp32-MFMA kernel's (unreal_gemm_f32)."""
     from unreal_amd import ops

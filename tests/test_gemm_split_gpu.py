@@ -76,7 +76,8 @@ def test_split_gemm_error_not_above_fp32_mfma(M, N, K, factor):
     """The round-3 gate at the trainer's product shapes (fc forward, fc dgrad, LSTM dgrad; 8192 of their 81,920 rows):
     the rms error of the fp16 hi + lo kernel against float64 does not exceed the plain fp32-MFMA kernel's on the same
     data (measured ratios on this synthetic data: 0.44 / 0.66 / 0.45; on the trainer's live operands 0.82 / 0.93 / 0.62).  The
-    live-operand version with maxima and tail percentiles is tools/exp/f16x2_gate.py (profiles/r03_f16x2_gate.log)."""
+    live-operand version is test_fullsize_gpu.py's fp16 hi + lo gate test (maxima and tail percentiles:
+    profiles/r03_f16x2_gate.log)."""
     from unreal_amd import ops
     rs = np.random.RandomState(K)
     A = (rs.standard_normal((M, K)) * rs.choice([1.0, 0.1, 3.0], size=(M, 1))).astype(np.float32)

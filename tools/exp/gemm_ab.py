@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Split-GEMM A/B on the trainer's production shapes (GPU box).  Variants are whole-library builds with extra -D flags
+"""Split-GEMM A/B on the trainer's production shapes (GPU box).  Variants are whole-library builds with extra compiler flags
 (`python tools/exp/gemm_ab.py --build` in the container; they travel with the snapshot); every variant is timed in
 interleaved rounds in ONE process through unreal_amd.ops (the library behind ops is swapped between timings), outputs are
 compared with variant `base`."""
@@ -12,14 +12,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "tools", "exp", "build")
 VARIANTS = {"base": []}
-# round 4 timed: dbuf = -DSPLIT_NT_DBUF=1,-DSPLIT_TN_DBUF=1; occ3 = -DSPLIT_NT_OCC3=1 (adopted); k256 = -DSPLIT_NT_K256=1;
-# n256 = -DSPLIT_NT_N256=1; ragged = -DSPLIT_FORCE_RAGGED=1; and the compiler's scheduling strategies below
+# the compiler's scheduling strategies (the build-knob variants of rounds 3 and 4, profiles/r03_gemm_nt_ablate.log and
+# profiles/r04_gemm_*_ab.log, were timed with this script at b4f3617; the knobs are gone from the kernel)
 for _st in ("gcn-max-ilp", "gcn-max-memory-clause", "gcn-iterative-ilp", "gcn-iterative-minreg"):
     VARIANTS[_st.replace("gcn-", "")] = ["-mllvm", "-amdgpu-sched-strategy=" + _st]
-# earlier rounds of this script (results in profiles/r03_gemm_nt_ablate.log): timing-only ablations "nosplit" / "noload" /
-# "nosplit_noload" = -DSPLIT_ABLATE=2 / 1 / 3 (pass them as name=-DFLAG on the command line); the direct-store epilogue
-# and the 128 x 256 tile variants were removed from the kernel after they lost
-for a in sys.argv[1:]:             # extra variants: name=-DX=1,-DY=2
+for a in sys.argv[1:]:             # extra variants: name=FLAG1,FLAG2 (e.g. name=-mllvm,-amdgpu-sched-strategy=gcn-max-ilp)
     if "=" in a and not a.startswith("--"):
         k, v = a.split("=", 1)
         VARIANTS[k] = v.split(",")

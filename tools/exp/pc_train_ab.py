@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""unreal_pc_deconv_train A/B (GPU box): the product library against whole-library variants built with extra -D flags
-(`python tools/exp/pc_train_ab.py --build name=-DFLAG=V ...` in the container; they travel with the snapshot), timed in
+"""unreal_pc_deconv_train A/B (GPU box): the product library against whole-library variants built with extra compiler flags
+(`python tools/exp/pc_train_ab.py --build name=FLAG1,FLAG2 ...` in the container; they travel with the snapshot), timed in
 interleaved rounds in ONE process at the trainer's 81,920 frames; outputs compared with the product's."""
 import glob
 import os

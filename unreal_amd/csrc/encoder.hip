@@ -1,144 +1,61 @@
 // Fused conv encoder for 84x84x3 uint8 frames on gfx950: conv1 8x8 s4 (3->16) + ReLU -> conv2 4x4 s2
-// (16->32) + ReLU, forward and backward, as implicit GEMMs on v_mfma_f32_16x16x32_bf16 with fp32-grade error:
-// every fp32 operand is split ONCE into three bf16 terms (8+8+8 mantissa bits, residuals exact) and a product tile
-// accumulates the six term pairs of weight >= 2^-16 in fp32 (three where one operand is a uint8 pixel, which is
-// exact in one term) -- the scheme of gemm_split.hip.
+// (16->32) + ReLU, forward and backward, as implicit GEMMs on v_mfma_f32_16x16x32_f16 with fp32-grade error:
+// every fp32 operand is split ONCE into fp16 hi + lo of x * 2^k, k one power of two per tensor, and a product tile
+// accumulates the three term pairs hh, hl, lh in fp32 (two where one operand is a uint8 pixel, which is exact in one
+// term) -- the scheme of gemm_split.hip.
 //
 // Replaces tf.nn.conv2d + bias + relu of /root/reference/model/model.py:281-289,786-787 and their
 // tf.gradients (train/rmsprop_applier.py:100-105).  Weights are in TF HWIO layout:
 //   W1[(ky*8+kx)*3+cin][16], W2[(ky*4+kx)*16+cin][32]; outputs NHWC (flatten = model.py:331).
 //
-// Both kernels process ONE frame per 256-thread workgroup at a time and run TWO workgroups per CU (<= 80 KiB of LDS
-// each), so that one workgroup's staging / epilogue VALU overlaps the other's MFMAs; the uint8 frame reaches LDS by
-// LDS-DMA (global_load_lds, 1 KiB per wave instruction) issued a frame ahead; the frame is read from HBM exactly
-// once and conv1's output never leaves the CU on the inference path.
+// The forward processes ONE frame per 256-thread workgroup at a time and runs TWO workgroups per CU, so that one
+// workgroup's staging / epilogue VALU overlaps the other's MFMAs; the uint8 frame reaches LDS by LDS-DMA
+// (global_load_lds, 1 KiB per wave instruction) issued a frame ahead; the frame is read from HBM exactly once and
+// conv1's output never leaves the CU on the inference path.  The backward is encoder_bwd_roles.h.
 // MFMA operand convention (16x16x32): lane l = (i = l&15, q = l>>4) supplies A[row i][k = 8q + j] and
 // B[k = 8q + j][col i], j = 0..7; C/D: lane holds rows 4q..4q+3 of column i.
 #include "common.h"
 
 namespace {
 
-constexpr int FR_LDS = 21184;            // FRAME_BYTES rounded up to 64
 constexpr int FR_V = (FRAME_BYTES / 16 + 255) / 256;   // 16 B vectors per thread to move one frame (6)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// ---- conv1 forward as EXACT-PRODUCT bf16 MFMAs -----------------------------------------------------
-// The uint8 pixel is exact in bf16 (8 significant bits) and every fp32 weight is split once per kernel into
-// three bf16 terms w = wh + wm + wl (8 + 8 + 8 = 24 mantissa bits, residuals computed exactly in fp32), so
-// three v_mfma_f32_16x16x32_bf16 per 32-deep K chunk give products that are exact in fp32 and are
-// accumulated in fp32 -- fp32-grade numerics at 16/3 of the fp32 MFMA rate.  Lane (i = l&15, q = l>>4)
-// supplies the 8 patch elements k = 32kc + 8q + j of position i and of output channel i; 8 consecutive k never
-// straddle a patch row (24 bytes per ky), so the pixel fragment is two aligned 32-bit LDS reads of the uint8 frame.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef u32x4 u32x4v;
 
-__device__ __forceinline__ uint32_t bf16_rne_bits(float x) {     // fp32 -> bf16 (round to nearest even), as bits
-  uint32_t u = __float_as_uint(x);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
-__device__ __forceinline__ void split3(float w, uint32_t (&t)[3]) {
-  t[0] = bf16_rne_bits(w);
-  float r = w - __uint_as_float(t[0] << 16);
-  t[1] = bf16_rne_bits(r);
-  r = r - __uint_as_float(t[1] << 16);
-  t[2] = bf16_rne_bits(r);                  // exact: at most 8 significant bits are left
-}
-
-// wb[kc][term]: 8 bf16 (k = 32kc + 8q + j) of output channel j_out, packed two per dword
-__device__ __forceinline__ void load_w1_bf16x3(const float* __restrict__ W1, int q, int j_out, u32x4v (&wb)[6][3]) {
-#pragma unroll
-  for (int kc = 0; kc < 6; ++kc) {
-    uint32_t pk[3][4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      uint32_t lo[3], hi[3];
-      split3(W1[(32 * kc + 8 * q + 2 * e) * 16 + j_out], lo);
-      split3(W1[(32 * kc + 8 * q + 2 * e + 1) * 16 + j_out], hi);
-#pragma unroll
-      for (int t = 0; t < 3; ++t) pk[t][e] = lo[t] | (hi[t] << 16);
-    }
-#pragma unroll
-    for (int t = 0; t < 3; ++t) wb[kc][t] = (u32x4v){pk[t][0], pk[t][1], pk[t][2], pk[t][3]};
-  }
-}
-
-// 8 uint8 (two dwords) -> 8 bf16: float(byte) has <= 8 significant bits, so its upper 16 bits ARE the bf16
-__device__ __forceinline__ bf16x8 u8x8_to_bf16(uint32_t w0, uint32_t w1) {
-  float f[8];
-  f[0] = (float)(w0 & 0xffu); f[1] = (float)((w0 >> 8) & 0xffu); f[2] = (float)((w0 >> 16) & 0xffu); f[3] = (float)(w0 >> 24);
-  f[4] = (float)(w1 & 0xffu); f[5] = (float)((w1 >> 8) & 0xffu); f[6] = (float)((w1 >> 16) & 0xffu); f[7] = (float)(w1 >> 24);
-  u32x4v r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    r[e] = __builtin_amdgcn_perm(__float_as_uint(f[2 * e + 1]), __float_as_uint(f[2 * e]), 0x07060302u);
-  return __builtin_bit_cast(bf16x8, r);
-}
-
 // ------------------------------------------------------------------------------------------------
-// Backward (its LDS helpers are shared with the forward kernel below).  Input d2 = dL/d(conv2 pre-activation) [N][81][32] (ReLU mask already applied by the
-// producer), c1 = saved conv1 activation [N][400][16], the uint8 frame.  Produces dW2, dW1 (register
-// accumulators across all frames of the workgroup, flushed once with float atomics), db2, db1.
+// Backward (encoder_bwd_roles.h; it shares the LDS helpers below with the forward kernel).  Input d2 = dL/d(conv2
+// pre-activation) [N][81][32] (ReLU mask already applied by the producer), c1 = saved conv1 activation [N][400][16], the
+// uint8 frame.  Produces dW2, dW1 (register accumulators across all frames of the workgroup, flushed once with float
+// atomics), db2, db1.
 //   (1) dW2[(ky,kx,c)][n] += sum_pos c1[2oy+ky][2ox+kx][c] * d2[pos][n]            M=256 N=32 K=81
 //   (2) d1[2a+pa][2b+pb][c] = sum_{da,db,n} d2[a-da][b-db][n] * W2[pa+2da][pb+2db][c][n]
 //       per output parity (pa,pb): M=16 channels, N=100 positions, K=128; masked by c1 > 0
 //   (3) dW1[(ky,kx,cin)][c] += scale * sum_pos u8[4oy+ky][4ox+kx][cin] * d1[pos][c]  M=192 N=16 K=400
-// ALL three phases run on v_mfma_f32_16x16x32_bf16 with fp32-grade error (the scheme of csrc/gemm_split.hip):
-// every fp32 operand element is split ONCE into three bf16 terms (round-to-nearest, residuals exact: 8+8+8
-// mantissa bits) -- c1 and d2 when the frame is staged into LDS, W2 once per kernel (its fragments stay in
-// registers), d1 in the epilogue of phase (2) -- and each product tile accumulates the six term pairs of weight
-// >= 2^-16 in fp32 (dropped pairs < 2^-24 |ab|); the uint8 pixel is exact in one bf16 term (3 MFMAs per tile).
-// That is 6/16 of the fp32 MFMA's matrix-pipe time for phases (1)-(2).
-//
-// Organisation: one frame per 256-thread workgroup at a time, TWO workgroups per CU (exactly 80 KiB of LDS each) that
-// run independently -- one's staging / epilogue VALU overlaps the other's MFMAs on the same SIMDs.  LDS per workgroup:
-//   Y   [0, 42816): FR = the uint8 frame as it comes from HBM (LDS-DMA, issued at the top of the frame's iteration and
-//       waited for only before phase (3)) | spare | Z = d2 planes [3][111 rows][32 n] bf16 with a ZERO HALO: position
-//       (y,x) lives in row (y+1)*10 + (x+1), rows of y = -1, y = 9 and x = -1 are zero (x = 9 wraps onto the next
-//       row's x = -1), so the tap (a-da, b-db) of output position m = 10a + b is row m + 11 - (10da + db): phase (2)
-//       addresses its operands with compile-time offsets from one lane-constant base, and "outside" taps read zeros.
-//       Between phases (2) and (3) the frame is expanded to bf16 [84][252] over the whole of Y (FR and Z are dead by
-//       then), so phase (3) needs no conversion in its loop.
-//   X   c1 planes [3][400 pos][16 ch] bf16; phase (2) overwrites them IN PLACE with the d1 planes (the ReLU mask of
-//       an element is read from its own c1 hi term just before it is overwritten) + one zero row
+// d2 lives in LDS as planes [111 rows][32 n] with a ZERO HALO: position (y,x) lives in row (y+1)*10 + (x+1), rows of
+// y = -1, y = 9 and x = -1 are zero (x = 9 wraps onto the next row's x = -1), so the tap (a-da, b-db) of output position
+// m = 10a + b is row m + 11 - (10da + db): phase (2) addresses its operands with compile-time offsets from one
+// lane-constant base, and "outside" taps read zeros.
 // Reductions over POSITIONS (phases 1 and 3: the position is the row index of the LDS images) take both operands
 // through ds_read_b64_tr_b16 (a 4-row x 16-column block, transposed in flight; each lane supplies the address of
 // one row, so the strided conv taps need no im2col copy); phase (2) reduces over d2's channel index, contiguous in
 // a row: plain 16-byte fragment reads, and its weight fragments never leave the registers.
-// The NEXT frame's c1 and d2 are fetched into registers behind phase (3) and split into the planes after it.
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2v __attribute__((ext_vector_type(2)));
 typedef short s16x4v __attribute__((ext_vector_type(4)));
 typedef short s16x8v __attribute__((ext_vector_type(8)));
 
-#ifndef BWD_UNROLL_KS     // loop unrolling of the three phases (A/B-tested on the device: tools/exp/ablate_encoder_bwd.py)
-#define BWD_UNROLL_KS 1
-#endif
-#ifndef BWD_UNROLL_T
-#define BWD_UNROLL_T 1
-#endif
-#ifndef BWD_UNROLL_KC
-#define BWD_UNROLL_KC 1
-#endif
 constexpr int C1_V = (C1_POS * 4 + 255) / 256;   // f32x4 per thread for one c1 image (7)
 constexpr int D2_V = (C2_POS * 8 + 255) / 256;   // f32x4 per thread for one d2 image (3)
-constexpr int XROW = 32;                         // bytes per conv1 position in a plane (16 bf16)
+constexpr int XROW = 32;                         // bytes per conv1 position in a plane (16 fp16)
 constexpr int XPL = C1_POS * XROW;               // 12800
-constexpr int X_BYTES = 3 * XPL + 64;            // + 64 zero bytes
-constexpr int ZROW = 64;                         // bytes per conv2 position in a plane (32 bf16)
+constexpr int ZROW = 64;                         // bytes per conv2 position in a plane (32 fp16)
 constexpr int ZROWS = 111;                       // 11 x 10 halo grid + row 110 (tap (9,9) of position 99)
 constexpr int ZPL = ZROWS * ZROW;                // 7104
-constexpr int Z_BYTES = 3 * ZPL;                 // 21312
 constexpr int Z_HALO = 30;                       // zero rows: 0..9 (y = -1), 10,20..90 (x = -1), 100..110 (y = 9)
 constexpr int FR_CHUNKS = FRAME_BYTES / 16;      // 1323 16-byte pieces of a frame
 constexpr int FR_DMA = (FR_CHUNKS + 63) / 64;    // 21 wave-wide LDS-DMA instructions (1 KiB each; the last one overshoots)
-constexpr int Z_OFF = FR_LDS + 320;              // 21504: the DMA overshoot (21504 bytes written) stays in the spare
-constexpr int X_OFF = Z_OFF + Z_BYTES;           // 42816 = size of Y
-constexpr int BWD_LDS = X_OFF + X_BYTES;         // 81280: two workgroups per CU
-static_assert(FR_DMA * 1024 <= Z_OFF && 2 * FRAME_BYTES <= X_OFF, "frame images must fit Y");
-static_assert(2 * BWD_LDS <= 160 * 1024, "two workgroups must fit one CU's LDS");
 
 // workgroup barrier that does NOT drain the vector-memory counter (an LDS-DMA stays in flight across it): LDS
 // writes / reads of this wave are retired first, the compiler may not move memory accesses across it
@@ -147,18 +64,6 @@ static_assert(2 * BWD_LDS <= 160 * 1024, "two workgroups must fit one CU's LDS")
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    \
     __builtin_amdgcn_s_barrier();                         \
     asm volatile("" ::: "memory");                        \
-  } while (0)
-
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-// six term pairs of one product tile, smallest first
-#define SPLIT_MMA(A, B, C)            \
-  do {                                \
-    C = MFMA_BF16(A[2], B[0], C);     \
-    C = MFMA_BF16(A[0], B[2], C);     \
-    C = MFMA_BF16(A[1], B[1], C);     \
-    C = MFMA_BF16(A[1], B[0], C);     \
-    C = MFMA_BF16(A[0], B[1], C);     \
-    C = MFMA_BF16(A[0], B[0], C);     \
   } while (0)
 
 // LDS bank spreading (ds_read_b64_tr_b16 serves a wave as two 32-lane halves over 64 banks = one 256-byte window):
@@ -172,69 +77,10 @@ static_assert(2 * BWD_LDS <= 160 * 1024, "two workgroups must fit one CU's LDS")
 __device__ __forceinline__ int xrow(int p) { return p ^ ((p >> 3) & 1); }
 __device__ __forceinline__ int kdeal(int q, int qq) { return 16 * (q >> 1) + 4 * (q & 1) + qq; }
 
-// 4 fp32 -> three planes of 4 bf16 (round to nearest even; x = pl0 + pl1 + pl2 exactly)
-__device__ __forceinline__ void split4(const f32x4& v, u32x2v (&pl)[3]) {
-  f32x2v x01 = {v[0], v[1]}, x23 = {v[2], v[3]};
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const bf16x2v h01 = __builtin_convertvector(x01, bf16x2v), h23 = __builtin_convertvector(x23, bf16x2v);
-    pl[t] = (u32x2v){__builtin_bit_cast(unsigned int, h01), __builtin_bit_cast(unsigned int, h23)};
-    if (t < 2) {
-      x01 = x01 - __builtin_convertvector(h01, f32x2v);
-      x23 = x23 - __builtin_convertvector(h23, f32x2v);
-    }
-  }
-}
-
-// two transposed 4-row blocks -> the 8 consecutive-k values of one 16x16x32 operand lane.  Lane 4*qq + pp of a
-// 16-lane group passes the address of block row qq (+ 8*pp bytes); it receives column (lane & 15) of the 4 rows.
-__device__ __forceinline__ bf16x8 tr_pair(const unsigned char* a0, const unsigned char* a1) {
-  typedef s16x4v __attribute__((address_space(3))) * lds_p;
-  const s16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a0));
-  const s16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a1));
-  const s16x8v v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-__device__ __forceinline__ void stage_c1_planes(unsigned char* xp, int tid, const f32x4 (&pc1)[C1_V]) {
-#pragma unroll
-  for (int c = 0; c < C1_V; ++c) {
-    const int id = tid + 256 * c;
-    if (id < C1_POS * 4) {
-      u32x2v pl[3];
-      split4(pc1[c], pl);
-#pragma unroll
-      for (int t = 0; t < 3; ++t) *reinterpret_cast<u32x2v*>(xp + t * XPL + xrow(id >> 2) * XROW + (id & 3) * 8) = pl[t];
-    }
-  }
-}
-
-__device__ __forceinline__ void stage_d2_planes(unsigned char* zp, int tid, const f32x4 (&pd2)[D2_V], float (&adb2)[4]) {
-  // the halo rows of the three planes are zero (the bf16 frame image of the previous frame lay over them)
-  for (int e = tid; e < 3 * Z_HALO * 4; e += 256) {
-    const int t = e / (Z_HALO * 4), k = (e >> 2) % Z_HALO;
-    const int r = k < 10 ? k : (k < 19 ? (k - 9) * 10 : 81 + k);
-    *reinterpret_cast<u32x4*>(zp + t * ZPL + r * ZROW + (e & 3) * 16) = (u32x4){0u, 0u, 0u, 0u};
-  }
-#pragma unroll
-  for (int c = 0; c < D2_V; ++c) {
-    const int id = tid + 256 * c;
-    if (id < C2_POS * 8) {
-      u32x2v pl[3];
-      split4(pd2[c], pl);
-      const int pos = id >> 3, r = (pos / 9 + 1) * 10 + pos % 9 + 1;
-#pragma unroll
-      for (int t = 0; t < 3; ++t) *reinterpret_cast<u32x2v*>(zp + t * ZPL + r * ZROW + ((id & 7) ^ (r & 4)) * 8) = pl[t];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) adb2[e] += pd2[c][e];
-    }
-  }
-}
-
 // One wave-wide LDS-DMA: 64 x 16 bytes, lane l's source -> LDS byte address lds_dst + 16 l (M0 = wave-uniform base).
 // Issued from inline asm ON PURPOSE: hipcc orders every later LDS read of the same __shared__ array behind a DMA it
-// can see (s_waitcnt vmcnt(0) at the first ds_read of phase (1)), which would expose the HBM latency the DMA is there
-// to hide.  The kernel waits for it itself (s_waitcnt vmcnt(0) + barrier before phase (3)); no compiler-counted
+// can see (s_waitcnt vmcnt(0) at the first ds_read behind it), which would expose the HBM latency the DMA is there
+// to hide.  The kernel waits for it itself (s_waitcnt vmcnt(0) + barrier before the frame is read); no compiler-counted
 // vector load is in flight while a DMA is (the prefetch loads are issued after that wait and consumed before the next
 // DMA), so the compiler's own vmcnt bookkeeping stays exact.
 __device__ __forceinline__ void glds16(const uint8_t* gsrc, unsigned lds_dst) {
@@ -246,91 +92,59 @@ __device__ __forceinline__ void glds16(const uint8_t* gsrc, unsigned lds_dst) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Forward: conv1 8x8 s4 + ReLU -> conv2 4x4 s2 + ReLU, fused per frame, BOTH on v_mfma_f32_16x16x32_bf16 with
-// fp32-grade error.  conv1 (above): the uint8 pixel is one exact bf16 term, the weights three -> 3 MFMAs per tile
-// and K chunk.  conv2: c1 is split into three bf16 planes as it leaves conv1's accumulators, W2 once per kernel;
-// six term-pair MFMAs per tile and K chunk (6/16 of the fp32 MFMA's matrix-pipe time, which round 1 used here).
-//
-// One frame per 256-thread workgroup at a time, two workgroups per CU (71 KB of LDS each), like the backward:
-//   FR  the uint8 frame, by LDS-DMA (issued for frame n+1 as soon as conv1 of frame n has read FR; lands under conv2)
-//   X   c1 planes [3][400 pos][16 ch] bf16 (row p stored at p ^ ((p>>3)&1), as in the backward)
-//   P   partial conv2 tiles of the waves that own the upper half of K
-// conv1 is evaluated TRANSPOSED (D[channel][position] = W1^T x patches): a lane then holds 4 consecutive channels of
-// one position, i.e. one 16-byte store of the saved fp32 activation and one 8-byte store per bf16 plane.
-// conv2: M = 81 positions (6 tiles), N = 32, K = 256 = 8 chunks of (2 taps x 16 channels).  No LDS is left for
-// W2, so its fragments live in registers and the work is cut so that a wave needs few of them: wave gw owns n-tile
-// gw & 1 and K half gw >> 1 (4 chunks: 48 registers of W2 fragments) for all 6 position tiles; the two halves of K
-// are added in a FIXED order (lower + upper) through P, so the result does not depend on scheduling.
-// ------------------------------------------------------------------------------------------------
-// Operand format (round 3): ENC_FWD_F16 1 = fp16 hi + lo with one power-of-two scale per tensor, like gemm_split.hip:
-// conv1 takes 2 term pairs per tile and K chunk (W1 hi / lo x the exact pixel) instead of 3, conv2 3 (c1 hi / lo x W2
-// hi / lo: hh, hl, lh) instead of 6, and c1 is kept in LDS as two planes instead of three.  W1's and W2's maxima are
-// reduced once per kernel; c1's scale comes from a BOUND (it must be known before the first c1 value exists):
+// Forward: conv1 8x8 s4 + ReLU -> conv2 4x4 s2 + ReLU, fused per frame, BOTH on v_mfma_f32_16x16x32_f16 with
+// fp32-grade error.  Operands are fp16 hi + lo with one power-of-two scale per tensor, like gemm_split.hip: conv1 takes
+// 2 term pairs per tile and K chunk (W1 hi / lo x the exact pixel), conv2 3 (c1 hi / lo x W2 hi / lo: hh, hl, lh), and c1
+// is kept in LDS as two planes.  W1's and W2's maxima are reduced once per weight update (unreal_encoder_prepare) or
+// once per kernel; c1's scale comes from a BOUND (it must be known before the first c1 value exists):
 // |c1[c]| <= 255 * frame_scale * sum_k |W1[k][c]| + |b1[c]| -- loose (by the 255 for the maze's 0 / 1 bytes), which
 // shortens the range over which hi + lo carry 22 bits but keeps the absolute error under 2^-32 of the largest c1.
-// ENC_FWD_F16 0 = round 2's three bf16 terms.
-#ifndef ENC_FWD_F16
-#define ENC_FWD_F16 1
-#endif
-// ENC_FWD_MAGIC 1 (fp16 form only): uint8 pixel -> fp16 with 4 byte permutes + 4 packed adds per 8-deep fragment instead
-// of 8 v_cvt_f32_ubyte + 4 v_cvt_pkrtz: the halfword 0x6400 | b IS 1024 + b (ulp 1 in [1024, 2048)), and subtracting 1024
-// is exact.  (Feeding the byte as an fp16 SUBNORMAL, b * 2^-24, needs the permutes alone, but the MFMA aligns its 32
-// products by their exponent FIELDS: a subnormal's leading zeros are lost bits of the adder -- 5e-4 relative error on 0 / 1
-// bytes, tools/exp/mfma_denorm_probe.py, profiles/r03_mfma_subnormal_probe.log.  Rejected.)
-#ifndef ENC_FWD_MAGIC
-#define ENC_FWD_MAGIC 1
-#endif
+//
+// One frame per 256-thread workgroup at a time, two workgroups per CU (59 KB of LDS each):
+//   FR  the uint8 frame, by LDS-DMA (issued for frame n+1 as soon as conv1 of frame n has read FR; lands under conv2)
+//   X   c1 planes [2][400 pos][16 ch] fp16 (row p stored at p ^ ((p>>3)&1), as in the backward)
+//   P   partial conv2 tiles of the waves that own the upper half of K
+// conv1 is evaluated TRANSPOSED (D[channel][position] = W1^T x patches): a lane then holds 4 consecutive channels of
+// one position, i.e. one 16-byte store of the saved fp32 activation and one 8-byte store per plane.
+// conv2: M = 81 positions (6 tiles), N = 32, K = 256 = 8 chunks of (2 taps x 16 channels).  No LDS is left for
+// W2, so its fragments live in registers and the work is cut so that a wave needs few of them: wave gw owns n-tile
+// gw & 1 and K half gw >> 1 (4 chunks: 32 registers of W2 fragments) for all 6 position tiles; the two halves of K
+// are added in a FIXED order (lower + upper) through P, so the result does not depend on scheduling.
 // conv2's fragment addresses come from a per-lane table built once per kernel (24 sixteen-bit plane offsets in 12
 // registers) instead of ~44 VALU of div / mod / swizzle arithmetic per position tile and frame; every wave finishes 3 of
 // its n-tile's 6 position tiles (it keeps those partial sums in registers and hands the other 3 to its partner through
 // P) instead of the lower-K waves finishing all 6 while the upper-K waves idle at the next barrier; conv2's fragment
-// reads run ENC_FWD_PF steps ahead of the MFMAs that consume them.  (Round 3, tools/exp/fwd_ab.py: 1.45 -> 1.21 ms per
-// 81,920 frames, outputs bit-identical.)
-#ifndef ENC_FWD_PF
-#define ENC_FWD_PF 2
-#endif
-// ENC_FWD_FR2 1: two uint8 frame buffers, the LDS-DMA runs two frames ahead (80,896 B of LDS: still two workgroups per CU).
-// Measured neutral (tools/exp/fwd_ab.py, profiles/r03_encoder_fwd_ab.log: 1.20 vs 1.21 ms; with the magic conversion 1.15 vs
-// 1.12): the wait before [F2] is not the DMA -- vmcnt also counts the 25.6 KB of conv1 activations this wave has stored, and
-// at 4.2 TB/s of HBM traffic (2.6 write + 1.6 read) those drain slowly.  Off.
-#ifndef ENC_FWD_FR2
-#define ENC_FWD_FR2 0
-#endif
-constexpr int NPLF = ENC_FWD_F16 ? 2 : 3;
+// reads run FWD_PF steps ahead of the MFMAs that consume them.  (Round 3: 1.45 -> 1.21 ms per 81,920 frames, outputs
+// bit-identical.)
+// ------------------------------------------------------------------------------------------------
+constexpr int NPLF = 2;                          // planes per operand: hi, lo
+constexpr int FWD_PF = 2;                        // conv2: fragment reads this many steps ahead of their MFMAs
 typedef _Float16 fh8 __attribute__((ext_vector_type(8)));
 typedef _Float16 fh2 __attribute__((ext_vector_type(2)));
-#if ENC_FWD_F16
 typedef fh8 fop8;
 #define MFMA_FOP(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
+// term pairs of one product tile, smallest first: lo * hi, hi * lo, hi * hi
 #define SPLIT_MMA_FOP(A, B, C)       \
   do {                               \
     C = MFMA_FOP(A[1], B[0], C);     \
     C = MFMA_FOP(A[0], B[1], C);     \
     C = MFMA_FOP(A[0], B[0], C);     \
   } while (0)
-#else
-typedef bf16x8 fop8;
-#define MFMA_FOP(a, b, c) MFMA_BF16(a, b, c)
-#define SPLIT_MMA_FOP(A, B, C) SPLIT_MMA(A, B, C)
-#endif
-// 4 fp32 -> NPLF planes of 4 sixteen-bit terms
-__device__ __forceinline__ void split4_fop(const f32x4& v, float scale, u32x2v (&pl)[3]) {
-#if ENC_FWD_F16
+// 4 fp32 -> hi + lo planes of 4 fp16 terms of v * scale
+__device__ __forceinline__ void split4_fop(const f32x4& v, float scale, u32x2v (&pl)[NPLF]) {
   const f32x2v x01 = (f32x2v){v[0], v[1]} * scale, x23 = (f32x2v){v[2], v[3]} * scale;
   const fh2 h01 = __builtin_convertvector(x01, fh2), h23 = __builtin_convertvector(x23, fh2);
   const fh2 l01 = __builtin_convertvector(x01 - __builtin_convertvector(h01, f32x2v), fh2);
   const fh2 l23 = __builtin_convertvector(x23 - __builtin_convertvector(h23, f32x2v), fh2);
   pl[0] = (u32x2v){__builtin_bit_cast(unsigned int, h01), __builtin_bit_cast(unsigned int, h23)};
   pl[1] = (u32x2v){__builtin_bit_cast(unsigned int, l01), __builtin_bit_cast(unsigned int, l23)};
-  pl[2] = pl[1];
-#else
-  (void)scale;
-  split4(v, pl);
-#endif
 }
-// 8 uint8 (two dwords) -> 8 sixteen-bit floats (exact in either format)
+// 8 uint8 (two dwords) -> 8 fp16 (exact) with 4 byte permutes + 4 packed adds per 8-deep fragment instead of 8
+// v_cvt_f32_ubyte + 4 v_cvt_pkrtz: the halfword 0x6400 | b IS 1024 + b (ulp 1 in [1024, 2048)), and subtracting 1024 is
+// exact.  (Feeding the byte as an fp16 SUBNORMAL, b * 2^-24, needs the permutes alone, but the MFMA aligns its 32
+// products by their exponent FIELDS: a subnormal's leading zeros are lost bits of the adder -- 5e-4 relative error on 0 / 1
+// bytes, tools/exp/mfma_denorm_probe.py, profiles/r03_mfma_subnormal_probe.log.  Rejected.)
 __device__ __forceinline__ fop8 u8x8_to_fop(uint32_t w0, uint32_t w1) {
-#if ENC_FWD_F16 && ENC_FWD_MAGIC
   u32x4v r;        // halfword j = 0x6400 | byte j (selector 4 = byte 0 of the constant) = fp16(1024 + b)
   r[0] = __builtin_amdgcn_perm(0x64646464u, w0, 0x04010400u);
   r[1] = __builtin_amdgcn_perm(0x64646464u, w0, 0x04030402u);
@@ -338,23 +152,12 @@ __device__ __forceinline__ fop8 u8x8_to_fop(uint32_t w0, uint32_t w1) {
   r[3] = __builtin_amdgcn_perm(0x64646464u, w1, 0x04030402u);
   const fh8 k1024 = {1024, 1024, 1024, 1024, 1024, 1024, 1024, 1024};
   return __builtin_bit_cast(fop8, r) - k1024;
-#elif ENC_FWD_F16
-  float f[8];
-  f[0] = (float)(w0 & 0xffu); f[1] = (float)((w0 >> 8) & 0xffu); f[2] = (float)((w0 >> 16) & 0xffu); f[3] = (float)(w0 >> 24);
-  f[4] = (float)(w1 & 0xffu); f[5] = (float)((w1 >> 8) & 0xffu); f[6] = (float)((w1 >> 16) & 0xffu); f[7] = (float)(w1 >> 24);
-  u32x4v r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) r[e] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_pkrtz(f[2 * e], f[2 * e + 1]));   // exact: integers
-  return __builtin_bit_cast(fop8, r);
-#else
-  return u8x8_to_bf16(w0, w1);
-#endif
 }
 
 constexpr int FWD_FR = FR_DMA * 1024;            // 21504: uint8 frame + DMA overshoot
-constexpr int FWD_X = (1 + ENC_FWD_FR2) * FWD_FR;   // two frame buffers: the DMA runs two frames ahead
+constexpr int FWD_X = FWD_FR;
 constexpr int FWD_P = FWD_X + NPLF * XPL;
-constexpr int FWD_LDS = FWD_P + 2 * 6 * 1024;    // 80896 (fp16x2, two frame buffers)
+constexpr int FWD_LDS = FWD_P + 2 * 6 * 1024;    // 59392
 static_assert(2 * FWD_LDS <= 160 * 1024, "two workgroups must fit one CU's LDS");
 
 // conv1 for TWO (or one) 16-position tiles, transposed: acc[r] = channel 4q + r at position 16 t + i
@@ -391,26 +194,12 @@ __device__ __forceinline__ void conv1_tiles(const uint8_t* fr, unsigned char* xp
     for (int r = 0; r < 4; ++r) v[r] = fmaxf(scale * acc[r] + bias[r], 0.f);
     if (c1_out) *reinterpret_cast<f32x4*>(c1_out + pos * C1_CH + 4 * q) = v;
     c1_max = fmaxf(fmaxf(c1_max, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
-    u32x2v pl[3];
+    u32x2v pl[NPLF];
     split4_fop(v, c1_scale, pl);
 #pragma unroll
     for (int u = 0; u < NPLF; ++u) *reinterpret_cast<u32x2v*>(xp + u * XPL + xrow(pos) * XROW + 8 * q) = pl[u];
   }
 }
-
-#ifdef ENC_FWD_STAMPS   // tools/exp/fwd_ab.py only: where a wave's cycles go (workgroup 3, s_memtime ticks summed over its frames)
-__device__ unsigned long long g_fstamp[4][8];
-#define FSTAMP(k)                                                  \
-  do {                                                             \
-    if (blockIdx.x == 3 && lane == 0) {                            \
-      const unsigned long long t_ = __builtin_amdgcn_s_memtime();  \
-      g_fstamp[gw][k] += t_ - t_prev_;                             \
-      t_prev_ = t_;                                                \
-    }                                                              \
-  } while (0)
-#else
-#define FSTAMP(k)
-#endif
 
 // ---- the weights' share of the forward prologue: scales and operand fragments.  Every workgroup of every launch used to
 // redo it (two reductions over W1 / W2, 80 strided loads and their splits per thread: ~6 of the ~18 us a launch costs before
@@ -452,7 +241,8 @@ __device__ __forceinline__ EncFwdScales enc_fwd_scales(const float* __restrict__
   return sc;
 }
 
-// conv1: A[row = channel i][k = 32kc + 8q + j], NPLF terms
+// conv1: A[row = channel i][k = 32kc + 8q + j], NPLF terms.  w1 keeps a third, unused slot per kc: with [6][NPLF] the
+// compiler schedules two of conv2's fragment reads differently (same results, but not the measured machine code).
 __device__ __forceinline__ void enc_fwd_w1_frags(const float* __restrict__ W1, float S_W1, int q, int i, u32x4v (&w1)[6][3]) {
 #pragma unroll
   for (int kc = 0; kc < 6; ++kc) {
@@ -462,7 +252,7 @@ __device__ __forceinline__ void enc_fwd_w1_frags(const float* __restrict__ W1, f
       lo4[e] = W1[(32 * kc + 8 * q + e) * 16 + i];
       hi4[e] = W1[(32 * kc + 8 * q + 4 + e) * 16 + i];
     }
-    u32x2v lo[3], hi[3];
+    u32x2v lo[NPLF], hi[NPLF];
     split4_fop(lo4, S_W1, lo);
     split4_fop(hi4, S_W1, hi);
 #pragma unroll
@@ -482,7 +272,7 @@ __device__ __forceinline__ void enc_fwd_w2_frags(const float* __restrict__ W2, f
       lo4[j] = W2[(k0 + j) * 32 + 16 * nt + i];
       hi4[j] = W2[(k0 + 4 + j) * 32 + 16 * nt + i];
     }
-    u32x2v lo[3], hi[3];
+    u32x2v lo[NPLF], hi[NPLF];
     split4_fop(lo4, S_W2, lo);
     split4_fop(hi4, S_W2, hi);
 #pragma unroll
@@ -535,34 +325,28 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
   const unsigned lds_fr = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char*)smem;
   const int nt = gw & 1, kh = gw >> 1;         // conv2: this wave's n-tile and K half
 
-  // fp16x2: power-of-two scales of W1, W2 and of the c1 planes (from the bound above) -- read from the prepared block
+  // power-of-two scales of W1, W2 and of the c1 planes (from the bound above) -- read from the prepared block
   // (unreal_encoder_prepare: once per weight update) or reduced here, once per workgroup
-  float S_W1 = 1.f, S_W2 = 1.f, S_C1 = 1.f;
-  if (ENC_FWD_F16) {
-    if (prep) {
-      const u32x4 h = prep[0];
-      S_W1 = __uint_as_float(h[0]); S_W2 = __uint_as_float(h[1]); S_C1 = __uint_as_float(h[2]);
-    } else {
-      const EncFwdScales sc = enc_fwd_scales(W1, b1, W2, scale, reinterpret_cast<float*>(smem));
-      S_W1 = sc.S_W1; S_W2 = sc.S_W2; S_C1 = sc.S_C1;
-    }
+  float S_W1, S_W2, S_C1;
+  if (prep) {
+    const u32x4 h = prep[0];
+    S_W1 = __uint_as_float(h[0]); S_W2 = __uint_as_float(h[1]); S_C1 = __uint_as_float(h[2]);
+  } else {
+    const EncFwdScales sc = enc_fwd_scales(W1, b1, W2, scale, reinterpret_cast<float*>(smem));
+    S_W1 = sc.S_W1; S_W2 = sc.S_W2; S_C1 = sc.S_C1;
   }
   // conv1: un-scales W1 and applies the byte scale in one factor
   const float scale1 = scale * pow2_inv(S_W1);
   const float inv_c2 = pow2_inv(S_C1) * pow2_inv(S_W2);    // conv2: exact (both powers of two; |exponents| <= 100 each
                                                            // cannot meet here: c1's bound and W2's maximum are O(1))
   u32x4v w1[6][3];                             // conv1: A[row = channel i][k = 32kc + 8q + j], NPLF terms
-  if (ENC_FWD_F16) {
-    if (prep) {
+  if (prep) {
 #pragma unroll
-      for (int kc = 0; kc < 6; ++kc)
+    for (int kc = 0; kc < 6; ++kc)
 #pragma unroll
-        for (int t = 0; t < NPLF; ++t) w1[kc][t] = prep[ENC_PREP_W1 + (kc * NPLF + t) * 64 + lane];
-    } else {
-      enc_fwd_w1_frags(W1, S_W1, q, i, w1);
-    }
+      for (int t = 0; t < NPLF; ++t) w1[kc][t] = prep[ENC_PREP_W1 + (kc * NPLF + t) * 64 + lane];
   } else {
-    load_w1_bf16x3(W1, q, i, w1);
+    enc_fwd_w1_frags(W1, S_W1, q, i, w1);
   }
   int koff[6];                                 // byte offset of patch element k = 32kc + 8q inside the frame
 #pragma unroll
@@ -570,7 +354,7 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
   const f32x4 bias1 = *reinterpret_cast<const f32x4*>(b1 + 4 * q);
   // conv2: B[k = 32kc + 8q + j][col = n = 16nt + i] = W2[(tap = 2kc + (q>>1)) * 16 + 8(q&1) + j][n], kc = 4kh + c
   fop8 w2[4][NPLF];
-  if (ENC_FWD_F16 && prep) {
+  if (prep) {
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -597,69 +381,59 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
     c2tab[e2] = pk;
   }
 
-  // uint8 frame (pool index fidx) -> FR buffer `buf` (lane-linear 1 KiB pieces; wave gw issues pieces gw, gw + 4, ...)
-  auto dma_frame = [&](int fidx, int buf) {
+  // uint8 frame (pool index fidx) -> FR (lane-linear 1 KiB pieces; wave gw issues pieces gw, gw + 4, ...)
+  auto dma_frame = [&](int fidx) {
     const uint8_t* src = frames + (size_t)fidx * FRAME_BYTES;
     for (int kk = gw; kk < FR_DMA; kk += 4) {
       const int chunk = min(64 * kk + lane, FR_CHUNKS - 1);
-      glds16(src + 16 * chunk, __builtin_amdgcn_readfirstlane(lds_fr + buf * FWD_FR + 1024 * kk));
+      glds16(src + 16 * chunk, __builtin_amdgcn_readfirstlane(lds_fr + 1024 * kk));
     }
   };
   const int stride = gridDim.x;
-  dma_frame(frame_idx[blockIdx.x], 0);         // the launch guarantees gridDim.x <= N
-  if (ENC_FWD_FR2 && blockIdx.x + stride < N) dma_frame(frame_idx[blockIdx.x + stride], 1);
-  // index of the frame whose DMA is issued behind the next [F1]: two frames ahead (FR2) / one
-  int fidx_next = blockIdx.x + (1 + ENC_FWD_FR2) * stride < N ? frame_idx[blockIdx.x + (1 + ENC_FWD_FR2) * stride] : 0;
+  dma_frame(frame_idx[blockIdx.x]);            // the launch guarantees gridDim.x <= N
+  // index of the frame whose DMA is issued behind the next [F1]
+  int fidx_next = blockIdx.x + stride < N ? frame_idx[blockIdx.x + stride] : 0;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   WG_BARRIER();
 
-  // Two barriers per frame.  [F1] conv1 done: X complete, the frame buffer conv1 read is dead -> the DMA of the frame TWO
-  // ahead starts into it (FR2: two frame buffers; with one buffer the next frame's DMA had only conv2 -- 3,600 ticks --
-  // to land and every wave waited ~1,400 ticks for it).  [F2] conv2 done: P complete, X dead; every wave has first
-  // waited until at most its own pieces of the newest DMA are outstanding (loads return in order: the pieces of the
-  // frame conv1 reads next were issued a whole frame earlier).  Then every wave finishes its three output tiles and
-  // goes on to conv1 of the next frame; P and X are rewritten only behind the next [F1] / [F2].
-#ifdef ENC_FWD_STAMPS
-  unsigned long long t_prev_ = __builtin_amdgcn_s_memtime();
-#endif
-  int buf = 0;
+  // Two barriers per frame.  [F1] conv1 done: X complete, the frame buffer conv1 read is dead -> the DMA of the next
+  // frame starts into it.  [F2] conv2 done: P complete, X dead; every wave has first waited for its pieces of that DMA.
+  // Then every wave finishes its three output tiles and goes on to conv1 of the next frame; P and X are rewritten only
+  // behind the next [F1] / [F2].  (A second frame buffer, the DMA two frames ahead, measured neutral: the wait before
+  // [F2] is not the DMA -- vmcnt also counts the 25.6 KB of conv1 activations this wave has stored, and at 4.2 TB/s of
+  // HBM traffic those drain slowly; profiles/r03_encoder_fwd_ab.log.)
   for (int n = blockIdx.x; n < N; n += stride) {
     int zero;                                  // opaque 0, new every frame: keeps conv1's address sets out of the registers
     asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
-    FSTAMP(0);
     {
       float* c1n = c1_out ? c1_out + (size_t)n * (C1_POS * C1_CH) : nullptr;
-      const uint8_t* frn = fr + buf * FWD_FR;
       // 25 tiles over 4 waves = 7 + 6 + 6 + 6
       for (int tt = (gw + 2) & 3; tt < 25; tt += 8) {
-        if (tt + 4 < 25) conv1_tiles<true>(frn, xp, c1n, w1, koff, bias1, scale1, tt, tt + 4, i + zero, q, c1_max, S_C1);
-        else conv1_tiles<false>(frn, xp, c1n, w1, koff, bias1, scale1, tt, tt, i + zero, q, c1_max, S_C1);
+        if (tt + 4 < 25) conv1_tiles<true>(fr, xp, c1n, w1, koff, bias1, scale1, tt, tt + 4, i + zero, q, c1_max, S_C1);
+        else conv1_tiles<false>(fr, xp, c1n, w1, koff, bias1, scale1, tt, tt, i + zero, q, c1_max, S_C1);
       }
     }
-    FSTAMP(1);
     WG_BARRIER();     // [F1] c1 planes complete; this frame's buffer is dead
-    FSTAMP(2);
-    const bool dma_now = n + (1 + ENC_FWD_FR2) * stride < N;
-    if (dma_now) dma_frame(fidx_next, ENC_FWD_FR2 ? buf : 0);
-    fidx_next = n + (2 + ENC_FWD_FR2) * stride < N ? frame_idx[n + (2 + ENC_FWD_FR2) * stride] : 0;
+    if (n + stride < N) dma_frame(fidx_next);
+    fidx_next = n + 2 * stride < N ? frame_idx[n + 2 * stride] : 0;
     // conv2: this wave's n-tile and K half (4 chunks) of all 6 position tiles -- 24 steps s = 4u + c (u: tile in this
-    // wave's order, own tiles first; c: K chunk), fragments ENC_FWD_PF steps ahead
+    // wave's order, own tiles first; c: K chunk), fragments FWD_PF steps ahead
     f32x4 acc[3];
     {
-      fop8 af[ENC_FWD_PF + 1][NPLF];
+      fop8 af[FWD_PF + 1][NPLF];
       auto frag = [&](int st, fop8 (&dst)[NPLF]) {
         const unsigned off = (st & 1) ? (c2tab[st >> 1] >> 16) : (c2tab[st >> 1] & 0xffffu);
 #pragma unroll
         for (int t = 0; t < NPLF; ++t) dst[t] = *reinterpret_cast<const fop8*>(xp + off + t * XPL);
       };
 #pragma unroll
-      for (int st = 0; st < ENC_FWD_PF; ++st) frag(st, af[st]);
+      for (int st = 0; st < FWD_PF; ++st) frag(st, af[st]);
       f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int st = 0; st < 24; ++st) {
         const int u = st >> 2, c = st & 3;
-        if (st + ENC_FWD_PF < 24) frag(st + ENC_FWD_PF, af[(st + ENC_FWD_PF) % (ENC_FWD_PF + 1)]);
-        SPLIT_MMA_FOP(af[st % (ENC_FWD_PF + 1)], w2[c], a);
+        if (st + FWD_PF < 24) frag(st + FWD_PF, af[(st + FWD_PF) % (FWD_PF + 1)]);
+        SPLIT_MMA_FOP(af[st % (FWD_PF + 1)], w2[c], a);
         // program order inside the step: { MFMA, VALU, LDS read } x 3 -- the fragment requests of step st + PF go out in
         // the shadow of this step's MFMAs -- and nothing crosses the step boundary (left alone, the scheduler sinks every
         // read to just before its MFMA to save registers: read, lgkmcnt(0), MFMA, ...)
@@ -672,25 +446,15 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_barrier(0);
         if (c == 3) {
-          if (ENC_FWD_F16) a *= inv_c2;            // back to c1 * W2 units before the two K halves meet
+          a *= inv_c2;                             // back to c1 * W2 units before the two K halves meet
           if (u < 3) acc[u] = a;                   // own tile 3kh + u
           else *reinterpret_cast<f32x4*>(pp + ((nt * 6 + (u - 3 * kh)) * 64 + lane) * 16) = a;   // partner's tile u - 3kh
           a = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
       }
     }
-    FSTAMP(3);
-    // the frame conv1 reads next has landed: everything but this wave's pieces of the DMA just issued (6 for wave 0, 5 for
-    // the others; vector loads return in order, and no other vector load is in flight) must have returned
-    if (ENC_FWD_FR2 && dma_now) {
-      if (gw == 0) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    FSTAMP(4);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the frame conv1 reads next has landed
     WG_BARRIER();     // [F2]
-    FSTAMP(5);
     {
       // this wave's three tiles mt = 3kh + u: lower + upper K half (the sum of two floats does not depend on which wave
       // held which), bias, ReLU; tiles 0..4 are whole, tile 5 holds position 80 alone (q = 0, r = 0)
@@ -732,8 +496,6 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
         }
       }
     }
-    FSTAMP(6);
-    buf ^= ENC_FWD_FR2;
   }
   // one commit per workgroup and slot (the frame buffer is dead: no DMA was issued behind the last frame's [F1], and the
   // waves still in their epilogue only read P).  The 2,048 waves of a launch end within microseconds of each other: each
@@ -751,10 +513,6 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
   }
 }
 
-#ifdef UNREAL_EXP_KERNELS     // tools/exp/encoder_ablate.hip only: experiment kernels that need this file's helpers
-#include UNREAL_EXP_KERNELS
-#endif
-
 #include "encoder_bwd_roles.h"     // round 3: the role-specialised backward kernel (uses the helpers above)
 
 }  // namespace
@@ -765,7 +523,7 @@ int unreal_encoder_fwd(int N, const uint8_t* frames, const int* frame_idx, float
                        const float* b1, const float* W2, const float* b2, float* c1_out, float* f2_out,
                        uint16_t* relu_bits, float* f2_absmax, float* c1_absmax, const void* prepared, void* stream) {
   if (N <= 0 || !frames || !frame_idx || !W1 || !b1 || !W2 || !b2 || !f2_out) return UNREAL_EINVAL;
-  if ((((uintptr_t)prepared) & 15) || (prepared && !ENC_FWD_F16)) return UNREAL_EINVAL;
+  if (((uintptr_t)prepared) & 15) return UNREAL_EINVAL;
   const u32x4* prep = static_cast<const u32x4*>(prepared);
   int blocks = min(N, 512);             // one frame per workgroup at a time, two workgroups per CU
   if (relu_bits)
@@ -779,7 +537,7 @@ int unreal_encoder_fwd(int N, const uint8_t* frames, const int* frame_idx, float
 
 int unreal_encoder_prepare(const float* W1, const float* b1, const float* W2, float frame_scale, void* prepared,
                            long prepared_bytes, void* stream) {
-  if (!W1 || !b1 || !W2 || !prepared || (((uintptr_t)prepared) & 15) || !ENC_FWD_F16) return UNREAL_EINVAL;
+  if (!W1 || !b1 || !W2 || !prepared || (((uintptr_t)prepared) & 15)) return UNREAL_EINVAL;
   if (prepared_bytes < (long)ENC_PREP_VECS * 16) return UNREAL_EINVAL;
   hipLaunchKernelGGL(encoder_prepare_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, W1, b1, W2, frame_scale,
                      static_cast<u32x4*>(prepared));
@@ -791,26 +549,11 @@ int unreal_encoder_bwd(int N, const uint8_t* frames, const int* frame_idx, float
                        float* db1, float* dW2, float* db2, void* stream) {
   if (N <= 0 || !frames || !frame_idx || !W2 || !c1_saved || !d2 || !dW1 || !db1 || !dW2 || !db2)
     return UNREAL_EINVAL;
-  if (ENC_BWD_F16 && (!c1_absmax || !d2_absmax)) return UNREAL_EINVAL;
+  if (!c1_absmax || !d2_absmax) return UNREAL_EINVAL;
   int blocks = min(N, 256);             // one 512-thread workgroup per CU (4 consumer + 4 producer waves), a frame at a time
-  hipLaunchKernelGGL((encoder_bwd_roles_kernel<7, true>), dim3(blocks), dim3(512), 0, (hipStream_t)stream, N, frames,
+  hipLaunchKernelGGL(encoder_bwd_roles_kernel, dim3(blocks), dim3(512), 0, (hipStream_t)stream, N, frames,
                      frame_idx, frame_scale, W2, c1_saved, d2, dW1, db1, dW2, db2, c1_absmax, d2_absmax);
   return unreal_launch_status();
 }
-
-#ifdef ENC_FWD_STAMPS   // tools/exp only
-int exp_read_fstamps(unsigned long long* host32, int reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(host32, HIP_SYMBOL(g_fstamp), sizeof(unsigned long long) * 32);
-  if (reset) {
-    unsigned long long z[32] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fstamp), z, sizeof(z));
-  }
-  return 0;
-}
-#endif
-#ifdef UNREAL_EXP_ENTRIES     // tools/exp/encoder_ablate.hip only
-#include UNREAL_EXP_ENTRIES
-#endif
 
 }  // extern "C"

@@ -1,11 +1,11 @@
-// Included by encoder.hip inside its anonymous namespace (uses split4, tr_pair, kdeal, xrow, WG_BARRIER, SPLIT_MMA ...).
+// Included by encoder.hip inside its anonymous namespace (uses kdeal, xrow, WG_BARRIER and the layout constants).
 // ------------------------------------------------------------------------------------------------
 // Conv encoder backward, round 3: ROLE-SPECIALISED waves + TABLE-DRIVEN addressing.
 //
 // What round 2's stamps and this round's instruction counts say: the kernel is bound by a wave's own in-order
 // instruction stream, not by the matrix pipe and not by LDS latency.  A wave64 VALU instruction costs the issuing wave
 // 4 cycles, a 16x16x32 MFMA holds its issue for 8 of its 16; round 2 spent ~1,200 VALU per wave and frame -- staging
-// (fp32 -> three bf16 planes, uint8 -> bf16), div / mod / swizzle address arithmetic re-derived for every frame (it
+// (fp32 -> 16-bit planes, uint8 -> 16-bit), div / mod / swizzle address arithmetic re-derived for every frame (it
 // had to be: hoisted, the address sets spilled), the dgrad epilogue -- beside 438 MFMAs, so each phase ran at 2.2-4.6x
 // its matrix-pipe time whatever the wave layout (software-pipelining the LDS reads changed nothing).
 //
@@ -13,42 +13,24 @@
 // LDS address they use comes from per-lane TABLES built once per kernel (two 16-bit offsets per register, ~50
 // registers -- they fit because consumers no longer hold a frame of prefetched operands), so a frame costs them
 // ~440 VALU instead of ~1,100.  Waves 4-7 ("producers", one per SIMD beside a consumer) fetch frame n+1 from HBM into
-// registers, split c1 / d2 into the bf16x3 planes of the OTHER X / Z buffer, expand the uint8 frame to the bf16
+// registers, split c1 / d2 into the fp16 hi / lo planes of the OTHER X / Z buffer, expand the uint8 frame to the fp16
 // image, and take half the row tiles of the conv1 wgrad (phase 3), whose operands both waves then read.
-// LDS (162,144 B):  X[2] c1 / d1 planes, 402 rows per plane (row 400 = zeros: K padding of phase 3; row 401 = dump), double-buffered
+// LDS (122,208 B):  X[2] c1 / d1 planes, 402 rows per plane (row 400 = zeros: K padding of phase 3; row 401 = dump), double-buffered
 //       (frame n is read until the end of its phase 3 while n+1 is staged) | Z[2] d2 planes with their zero halo
-//       (zeroed ONCE: nothing overwrites them any more) | I the bf16 frame image (single: built for frame n between
+//       (zeroed ONCE: nothing overwrites them any more) | I the fp16 frame image (single: built for frame n between
 //       barriers A(n) and B(n), read by phase 3 of frame n only).
 // Three workgroup barriers per frame (round 2: six), executed by every wave whatever its role:
 //   A(n)  X(n), Z(n) staged; phase 3 of frame n-1 finished            -> phase 1        | producers: image, d2 planes of n+1
 //   S1(n) phase 1 finished reading the c1 planes                       -> phase 2 (d1 overwrites c1) | producers: c1 planes of n+1, loads
 //   B(n)  d1 planes and the image of frame n complete                  -> phase 3 on all waves
 // ------------------------------------------------------------------------------------------------
-#ifdef UNREAL_ABLATE     // diagnostic build only (tools/exp/roles_ab.py --stamps): where a wave's cycles go, per role
-__device__ unsigned long long g_rstamp[8][16];
-#define RSTAMP(k)                                                                  \
-  do {                                                                             \
-    if (STAMPS && blockIdx.x == 3 && lane == 0) {                                  \
-      unsigned long long t_ = __builtin_amdgcn_s_memtime();                        \
-      g_rstamp[wv][k] += t_ - t_prev_;                                             \
-      t_prev_ = t_;                                                                \
-    }                                                                              \
-  } while (0)
-#else
-#define RSTAMP(k)
-#endif
-
-// Operand format of the planes (and of the frame image and the W2 fragments):
-//   ENC_BWD_F16 0  three bf16 terms per fp32 value (round 2), 6 / 6 / 3 term-pair MFMAs per tile of phases 1 / 2 / 3
-//   ENC_BWD_F16 1  fp16 hi + lo of x * 2^k, k one power of two per TENSOR (csrc/gemm_split.hip's scheme): c1 and d2 from
-//                  their absmax slots, W2 and d1 from maxima / bounds computed here; 3 / 3 / 2 term pairs.
-#ifndef ENC_BWD_F16
-#define ENC_BWD_F16 1
-#endif
-constexpr int NPLB = ENC_BWD_F16 ? 2 : 3;          // planes per operand
+// Operand format of the planes (and of the frame image and the W2 fragments): fp16 hi + lo of x * 2^k, k one power of two
+// per TENSOR (csrc/gemm_split.hip's scheme): c1 and d2 from their absmax slots, W2 and d1 from maxima / bounds computed
+// here; 3 / 3 / 2 term pairs per tile of phases 1 / 2 / 3.
+constexpr int NPLB = 2;                            // planes per operand
+constexpr int NT3 = 3;                             // row tiles of phase (3) per wave
 typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
-#if ENC_BWD_F16
 typedef f16x8v op8;
 #define MFMA_OP(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
 // term pairs of one product tile, smallest first: lo * hi, hi * lo, hi * hi
@@ -58,20 +40,17 @@ typedef f16x8v op8;
     C = MFMA_OP(A[0], B[1], C);     \
     C = MFMA_OP(A[0], B[0], C);     \
   } while (0)
-#else
-typedef bf16x8 op8;
-#define MFMA_OP(a, b, c) MFMA_BF16(a, b, c)
-#define SPLIT_MMA_OP(A, B, C) SPLIT_MMA(A, B, C)
-#endif
 constexpr int XPLR = (C1_POS + 2) * XROW;          // 12864: plane stride; row 400 = zeros (K padding), row 401 = dump (padding lanes' stores)
 constexpr int R_XSZ = NPLB * XPLR;                 // one X buffer
 constexpr int ZB = NPLB * ZPL;                     // one Z buffer
 constexpr int R_Z = 2 * R_XSZ;
 constexpr int R_I = R_Z + 2 * ZB;
-constexpr int R_LDS = R_I + 2 * FRAME_BYTES;       // 162,144 (bf16x3) / 122,208 (fp16x2)
+constexpr int R_LDS = R_I + 2 * FRAME_BYTES;       // 122,208
 static_assert(R_LDS <= 160 * 1024, "one workgroup per CU must fit the LDS");
 static_assert(R_XSZ < 65536 && ZB < 65536 && 2 * FRAME_BYTES < 65536, "table offsets are 16-bit, region-relative");
 
+// two transposed 4-row blocks -> the 8 consecutive-k values of one 16x16x32 operand lane.  Lane 4*qq + pp of a
+// 16-lane group passes the address of block row qq (+ 8*pp bytes); it receives column (lane & 15) of the 4 rows.
 __device__ __forceinline__ op8 tr_pair_op(const unsigned char* a0, const unsigned char* a1) {
   typedef s16x4v __attribute__((address_space(3))) * lds_p;
   const s16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a0));
@@ -80,20 +59,14 @@ __device__ __forceinline__ op8 tr_pair_op(const unsigned char* a0, const unsigne
   return __builtin_bit_cast(op8, v);
 }
 
-// 4 fp32 -> NPLB planes of 4 sixteen-bit terms (bf16x3: exact; fp16x2: hi + lo of v * scale, 22 significant bits)
-__device__ __forceinline__ void split4_op(const f32x4& v, float scale, u32x2v (&pl)[3]) {
-#if ENC_BWD_F16
+// 4 fp32 -> hi + lo planes of 4 fp16 terms of v * scale (22 significant bits)
+__device__ __forceinline__ void split4_op(const f32x4& v, float scale, u32x2v (&pl)[NPLB]) {
   const f32x2v x01 = (f32x2v){v[0], v[1]} * scale, x23 = (f32x2v){v[2], v[3]} * scale;
   const f16x2v h01 = __builtin_convertvector(x01, f16x2v), h23 = __builtin_convertvector(x23, f16x2v);
   const f16x2v l01 = __builtin_convertvector(x01 - __builtin_convertvector(h01, f32x2v), f16x2v);
   const f16x2v l23 = __builtin_convertvector(x23 - __builtin_convertvector(h23, f32x2v), f16x2v);
   pl[0] = (u32x2v){__builtin_bit_cast(unsigned int, h01), __builtin_bit_cast(unsigned int, h23)};
   pl[1] = (u32x2v){__builtin_bit_cast(unsigned int, l01), __builtin_bit_cast(unsigned int, l23)};
-  pl[2] = pl[1];
-#else
-  (void)scale;
-  split4(v, pl);
-#endif
 }
 
 // X layout of this kernel: position p -> row xrow(p) (as in round 2: 8 consecutive rows AND 8 rows two apart fall into 8
@@ -134,7 +107,7 @@ struct P2Tab {
 };
 struct P3Tab {
   uint32_t b[7];        // [kc]  lo / hi: d1 rows of slots s0.. / s0 + 8..  (X-relative; row 400 = zero for K padding)
-  uint32_t a[7];        // [kc]  lo / hi: patch origins of the same slots in the bf16 image (I-relative)
+  uint32_t a[7];        // [kc]  lo / hi: patch origins of the same slots in the fp16 image (I-relative)
 };
 
 __device__ __forceinline__ void p1_tab_build(P1Tab& T, int ky, int q, int qq, int pp) {
@@ -225,21 +198,20 @@ __device__ __forceinline__ void bwd_phase1_t(const unsigned char* xp, const unsi
     SPLIT_MMA_OP(af[s & 1], bf[0], aw2[kx][0]);
     SPLIT_MMA_OP(af[s & 1], bf[1], aw2[kx][1]);
     ILV6(1, 1)
-    if (NPLB == 3) { ILV6(1, 1) }
     __builtin_amdgcn_sched_barrier(0);
     if (kx == 3 && ks < 2) load_bf(ks + 1);
   }
 }
 
-// (2) conv2 dgrad for the table's output parity, position tiles [T0, T1): d1 planes written over the c1 planes in
+// (2) conv2 dgrad for the table's output parity, all 7 position tiles: d1 planes written over the c1 planes in
 // place.  Steps = (tile, tap); one fragment set per tap (4 sets), the set of the step three ahead is requested before a
-// step's MFMAs.  The epilogue of tile t (ReLU mask from the c1 hi terms, split into the three planes, stores, bias
+// step's MFMAs.  The epilogue of tile t (ReLU mask from the c1 hi terms, split into the two planes, stores, bias
 // sums) is issued under the MFMAs of tile t + 1.
-template <int T0, int T1>
 __device__ __forceinline__ void bwd_phase2_t(unsigned char* xp, const unsigned char* zp, P2Tab& T, const op8 (&wa)[4][NPLB],
                                              float (&adb1)[4], float acc_scale, float d1_scale) {
-  // acc_scale: un-scales the product (1 / (scale of W2 * scale of d2), exact; 1 in the bf16x3 mode); d1_scale: the scale
-  // the d1 planes are stored with
+  // acc_scale: un-scales the product (1 / (scale of W2 * scale of d2), exact); d1_scale: the scale the d1 planes are
+  // stored with
+  constexpr int NT2 = 7;
   op8 f[4][NPLB];
   auto load_tap = [&](int t, int dd) {
     if (dd == 0 || dd == 2) PIN(T.tap[dd >> 1]);
@@ -261,7 +233,7 @@ __device__ __forceinline__ void bwd_phase2_t(unsigned char* xp, const unsigned c
   // BRANCH-FREE (an exec-masked block would sit behind the tap's MFMAs instead of between them): padding lanes store to
   // the dump row and add 0 to the bias sums
   auto epi_store = [&](int t, unsigned char* dst, const f32x4& g) {
-    u32x2v pl[3];
+    u32x2v pl[NPLB];
     split4_op(g, d1_scale, pl);
 #pragma unroll
     for (int u = 0; u < NPLB; ++u) *reinterpret_cast<u32x2v*>(dst + u * XPLR) = pl[u];
@@ -269,33 +241,31 @@ __device__ __forceinline__ void bwd_phase2_t(unsigned char* xp, const unsigned c
 #pragma unroll
     for (int e = 0; e < 4; ++e) adb1[e] = fmaf(w, g[e], adb1[e]);
   };
-  load_tap(T0, 0);
-  load_tap(T0, 1);
-  load_tap(T0, 2);
+  load_tap(0, 0);
+  load_tap(0, 1);
+  load_tap(0, 2);
   f32x4 prev = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int t = T0; t < T1; ++t) {
-    const int tn = t + 1 < T1 ? t + 1 : t;                   // (the last tile re-requests its own fragments: unused)
+  for (int t = 0; t < NT2; ++t) {
+    const int tn = t + 1 < NT2 ? t + 1 : t;                  // (the last tile re-requests its own fragments: unused)
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     unsigned char* dst = xp;
     f32x4 g = {0.f, 0.f, 0.f, 0.f};
-#define LT(a, b) load_tap(a, b)
-#define EPI_ON true
-    LT(t, 3);
+    load_tap(t, 3);
     SPLIT_MMA_OP(wa[0], f[0], acc);
-    if (EPI_ON && t > T0) epi_mask(t - 1, prev, dst, g);
+    if (t > 0) epi_mask(t - 1, prev, dst, g);
     ILV6(3, 1)
     __builtin_amdgcn_sched_barrier(0);
-    LT(tn, 0);
+    load_tap(tn, 0);
     SPLIT_MMA_OP(wa[1], f[1], acc);
-    if (EPI_ON && t > T0) epi_store(t - 1, dst, g);
+    if (t > 0) epi_store(t - 1, dst, g);
     ILV6(6, 1)
     __builtin_amdgcn_sched_barrier(0);
-    LT(tn, 1);
+    load_tap(tn, 1);
     SPLIT_MMA_OP(wa[2], f[2], acc);
     ILV6(1, 1)
     __builtin_amdgcn_sched_barrier(0);
-    LT(tn, 2);
+    load_tap(tn, 2);
     SPLIT_MMA_OP(wa[3], f[3], acc);
     ILV6(1, 1)
     __builtin_amdgcn_sched_barrier(0);
@@ -303,13 +273,12 @@ __device__ __forceinline__ void bwd_phase2_t(unsigned char* xp, const unsigned c
   }
   unsigned char* dst;
   f32x4 g;
-  epi_mask(T1 - 1, prev, dst, g);
-  epi_store(T1 - 1, dst, g);
+  epi_mask(NT2 - 1, prev, dst, g);
+  epi_store(NT2 - 1, dst, g);
 }
 
 // (3) conv1 wgrad: NT3 row tiles (toff) over the table's 200 positions as 7 steps of 32 slots; the fragments of step
 // kc + 1 are requested before the MFMAs of step kc
-template <int NT3>
 __device__ __forceinline__ void bwd_phase3_t(const unsigned char* xp, const unsigned char* ip, P3Tab& T, const int (&toff)[NT3],
                                              f32x4 (&aw1)[NT3]) {
   op8 bpl[2][NPLB], av[2][NT3];
@@ -331,12 +300,11 @@ __device__ __forceinline__ void bwd_phase3_t(const unsigned char* xp, const unsi
     if (kc + 1 < 7) load_step(kc + 1);
 #pragma unroll
     for (int u = 0; u < NT3; ++u) {
-      if (NPLB == 3) aw1[u] = MFMA_OP(av[kc & 1][u], bpl[kc & 1][NPLB - 1], aw1[u]);
       aw1[u] = MFMA_OP(av[kc & 1][u], bpl[kc & 1][1], aw1[u]);
       aw1[u] = MFMA_OP(av[kc & 1][u], bpl[kc & 1][0], aw1[u]);
     }
 #pragma unroll
-    for (int u = 0; u < NT3; ++u) { if (NPLB == 3) { ILV3(1, 2) } else { ILV1(2, 3) ILV1(2, 3) } }
+    for (int u = 0; u < NT3; ++u) { ILV1(2, 3) ILV1(2, 3) }
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -355,12 +323,11 @@ __device__ __forceinline__ void stage_c1_planes_r(unsigned char* xp, int tid, f3
 #pragma unroll
   for (int c = 0; c < C1_V; ++c) {
     const int id0 = tid + 256 * c, id = id0 < C1_POS * 4 ? id0 : tid;
-    u32x2v pl[3];
+    u32x2v pl[NPLB];
     split4_op(pc1[c], scale, pl);
-#if ENC_BWD_F16      // c1 = relu(...) >= 0: the dgrad epilogue's ReLU mask reads "hi != 0" (common.h: keep_positive_visible)
+    // c1 = relu(...) >= 0: the dgrad epilogue's ReLU mask reads "hi != 0" (common.h: keep_positive_visible)
     pl[0][0] = keep_positive_visible(pl[0][0], pc1[c][0], pc1[c][1]);
     pl[0][1] = keep_positive_visible(pl[0][1], pc1[c][2], pc1[c][3]);
-#endif
 #pragma unroll
     for (int t = 0; t < NPLB; ++t) *reinterpret_cast<u32x2v*>(xp + t * XPLR + xoff(id >> 2, id & 3)) = pl[t];
     pc1[c] = reinterpret_cast<const f32x4*>(next)[id];
@@ -374,7 +341,7 @@ __device__ __forceinline__ void stage_d2_planes_r(unsigned char* zp, int tid, f3
 #pragma unroll
   for (int c = 0; c < D2_V; ++c) {
     const int id0 = tid + 256 * c, id = id0 < C2_POS * 8 ? id0 : tid;
-    u32x2v pl[3];
+    u32x2v pl[NPLB];
     split4_op(pd2[c], scale, pl);
     const int pos = id >> 3, r = (pos / 9 + 1) * 10 + pos % 9 + 1;
 #pragma unroll
@@ -387,7 +354,7 @@ __device__ __forceinline__ void stage_d2_planes_r(unsigned char* zp, int tid, f3
   }
 }
 
-// uint8 frame (16-byte pieces in registers) -> bf16 image [84][252]: a byte is exact in bf16
+// uint8 frame (16-byte pieces in registers) -> fp16 image [84][252]: a byte is exact in fp16
 __device__ __forceinline__ void build_image_r(unsigned char* ip, int tid, u32x4 (&raw)[FR_V], const uint8_t* next) {
 #pragma unroll
   for (int k = 0; k < FR_V; ++k) {
@@ -396,18 +363,12 @@ __device__ __forceinline__ void build_image_r(unsigned char* ip, int tid, u32x4 
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
       const uint32_t w = raw[k][d];
-#if ENC_BWD_F16      // a byte is exact in fp16 too: halfword 0x6400 | b = fp16(1024 + b), minus 1024 (exact) -- 2 byte permutes + 2
-                     // packed adds per 4 pixels instead of 4 v_cvt_f32_ubyte + 2 v_cvt_pkrtz (as in encoder_fwd)
+      // halfword 0x6400 | b = fp16(1024 + b), minus 1024 (exact) -- 2 byte permutes + 2 packed adds per 4 pixels instead of
+      // 4 v_cvt_f32_ubyte + 2 v_cvt_pkrtz (as in encoder_fwd)
       typedef _Float16 fh2i __attribute__((ext_vector_type(2)));
       const fh2i k1024 = {1024, 1024};
       o[d >> 1][2 * (d & 1)] = __builtin_bit_cast(unsigned int, __builtin_bit_cast(fh2i, __builtin_amdgcn_perm(0x64646464u, w, 0x04010400u)) - k1024);
       o[d >> 1][2 * (d & 1) + 1] = __builtin_bit_cast(unsigned int, __builtin_bit_cast(fh2i, __builtin_amdgcn_perm(0x64646464u, w, 0x04030402u)) - k1024);
-#else
-      const float f0 = (float)(w & 0xffu), f1 = (float)((w >> 8) & 0xffu), f2 = (float)((w >> 16) & 0xffu),
-                  f3 = (float)(w >> 24);
-      o[d >> 1][2 * (d & 1)] = __builtin_amdgcn_perm(__float_as_uint(f1), __float_as_uint(f0), 0x07060302u);
-      o[d >> 1][2 * (d & 1) + 1] = __builtin_amdgcn_perm(__float_as_uint(f3), __float_as_uint(f2), 0x07060302u);
-#endif
     }
     *reinterpret_cast<u32x4*>(ip + 32 * c) = o[0];
     *reinterpret_cast<u32x4*>(ip + 32 * c + 16) = o[1];
@@ -416,9 +377,6 @@ __device__ __forceinline__ void build_image_r(unsigned char* ip, int tid, u32x4 
   }
 }
 
-// P2C: position tiles of phase (2) the consumers take (7 = all; the producers take [P2C, 7) of the same parity).
-// P3ALL: the producers take half the row tiles of phase (3).
-template <int P2C, bool P3ALL, bool STAMPS = false>
 __global__ __launch_bounds__(512, 2) void encoder_bwd_roles_kernel(int N, const uint8_t* __restrict__ frames,
                                                                    const int* __restrict__ frame_idx, float scale,
                                                                    const float* __restrict__ W2,
@@ -436,17 +394,15 @@ __global__ __launch_bounds__(512, 2) void encoder_bwd_roles_kernel(int N, const 
   const int i = lane & 15, q = lane >> 4;
   const int qq = i >> 2, pp = i & 3;
   unsigned char* const ip = smem + R_I;
-  constexpr int NT3 = P3ALL ? 3 : 6;           // row tiles of phase (3) per wave
-  constexpr bool P2SPLIT = P2C < 7;
-  // phase (3): 12 row tiles x 2 position halves = 8 x (3 tiles, half) or 4 x (6 tiles, half)
-  const int tset = P3ALL ? (wv & 3) : (gw & 1), khalf = P3ALL ? (wv >> 2) : (gw >> 1);
+  // phase (3): 12 row tiles x 2 position halves = 8 waves x (NT3 tiles, half)
+  const int tset = wv & 3, khalf = wv >> 2;
 
-  // fp16x2: the tensors' power-of-two scales.  c1 and d2 come with absmax slots (the forward kernel / the fc dgrad
+  // the tensors' power-of-two scales.  c1 and d2 come with absmax slots (the forward kernel / the fc dgrad
   // commit them); W2's maximum and the bound of d1 are computed here, once per kernel: |d1[c]| <= max |d2| * sum over
   // (tap, n) of |W2[tap][c][n]| -- typically ~20x the largest d1 that occurs (signs cancel), which costs the d1 planes
   // four of their 17 binades of full-precision range and nothing in absolute terms.
-  float S_C1 = 1.f, S_D2 = 1.f, S_W2 = 1.f, S_D1 = 1.f;
-  if (ENC_BWD_F16) {
+  float S_C1, S_D2, S_W2, S_D1;
+  {
     float* red = reinterpret_cast<float*>(smem);            // [16] channel L1 norms, [16] max |W2| (LDS is free here)
     if (tid < 17) red[tid] = 0.f;
     __syncthreads();
@@ -505,15 +461,15 @@ __global__ __launch_bounds__(512, 2) void encoder_bwd_roles_kernel(int N, const 
   const int stride = gridDim.x;
   const int trip = (N - (int)blockIdx.x + stride - 1) / stride;       // the launch guarantees gridDim.x <= N
 
-  // W2 fragments of phase (2), once per kernel: wave gw (and its producer partner) owns output parity (gw>>1, gw&1)
+  // W2 fragments of phase (2), once per kernel: consumer wave gw owns output parity (gw>>1, gw&1)
   op8 wa[4][NPLB];
   P2Tab T2;
-  if (consumer || P2SPLIT) {
+  if (consumer) {
 #pragma unroll
     for (int dd = 0; dd < 4; ++dd) {
       const int ky = (gw >> 1) + 2 * (dd >> 1), kx = (gw & 1) + 2 * (dd & 1);
       const f32x4* wsrc = reinterpret_cast<const f32x4*>(W2 + ((ky * 4 + kx) * 16 + i) * 32 + 8 * q);
-      u32x2v lo[3], hi[3];
+      u32x2v lo[NPLB], hi[NPLB];
       split4_op(wsrc[0], S_W2, lo);
       split4_op(wsrc[1], S_W2, hi);
 #pragma unroll
@@ -525,30 +481,20 @@ __global__ __launch_bounds__(512, 2) void encoder_bwd_roles_kernel(int N, const 
     p2_tab_build(T2, gw, i, q);
   }
   P3Tab T3;
-  if (consumer || P3ALL) p3_tab_build(T3, khalf, q, qq, pp);
+  p3_tab_build(T3, khalf, q, qq, pp);
 
-#ifdef UNREAL_ABLATE
-  unsigned long long t_prev_ = __builtin_amdgcn_s_memtime();
-#endif
   if (consumer) {
     P1Tab T1;
     p1_tab_build(T1, gw, q, qq, pp);
     for (int k = 0; k < trip; ++k) {
       unsigned char* xp = smem + (k & 1) * R_XSZ;
       const unsigned char* zp = smem + R_Z + (k & 1) * ZB;
-      RSTAMP(0);
       WG_BARRIER();     // A(n)
-      RSTAMP(1);        // wait at A
       bwd_phase1_t(xp, zp, T1, aw2);
-      RSTAMP(2);        // phase 1
       WG_BARRIER();     // S1(n)
-      RSTAMP(3);        // wait at S1
-      bwd_phase2_t<0, P2C>(xp, zp, T2, wa, adb1, INV_W2 * INV_D2, S_D1);
-      RSTAMP(4);        // phase 2
+      bwd_phase2_t(xp, zp, T2, wa, adb1, INV_W2 * INV_D2, S_D1);
       WG_BARRIER();     // B(n)
-      RSTAMP(5);        // wait at B
-      bwd_phase3_t<NT3>(xp, ip, T3, toff, aw1);
-      RSTAMP(6);        // phase 3
+      bwd_phase3_t(xp, ip, T3, toff, aw1);
     }
   } else {
     // producers: registers U (uint8 frame), C (c1), D (d2) of the frames ahead.  At barrier A(n): U = frame n,
@@ -579,24 +525,14 @@ __global__ __launch_bounds__(512, 2) void encoder_bwd_roles_kernel(int N, const 
       const unsigned char* zp = smem + R_Z + (k & 1) * ZB;
       unsigned char* xn = smem + ((k + 1) & 1) * R_XSZ;        // (staged unconditionally: at the tail nobody reads them)
       unsigned char* zn = smem + R_Z + ((k + 1) & 1) * ZB;
-      RSTAMP(0);
       WG_BARRIER();     // A(n): phase 3 of frame n-1 finished -> the image buffer and X / Z of frame n-1 are free
-      RSTAMP(1);        // wait at A
       build_image_r(ip, t256, ur, frames + (size_t)fidx_next * FRAME_BYTES);
-      RSTAMP(7);        // image
       stage_d2_planes_r(zn, t256, pd2, adb2, d2_of(nnn_c), has_next ? 1.f : 0.f, S_D2);
-      RSTAMP(9);        // d2 planes
       WG_BARRIER();     // S1(n)
-      RSTAMP(3);        // wait at S1
       stage_c1_planes_r(xn, t256, pc1, c1_of(nnn_c), S_C1);
-      RSTAMP(8);        // c1 planes
-      if (P2SPLIT) bwd_phase2_t<P2C, 7>(xp, zp, T2, wa, adb1, INV_W2 * INV_D2, S_D1);
-      RSTAMP(4);        // phase 2 share
       fidx_next = frame_idx[min(nnn, N - 1)];
       WG_BARRIER();     // B(n)
-      RSTAMP(5);        // wait at B
-      if (P3ALL) bwd_phase3_t<NT3>(xp, ip, T3, toff, aw1);
-      RSTAMP(6);        // phase 3 share
+      bwd_phase3_t(xp, ip, T3, toff, aw1);
     }
   }
 
@@ -610,19 +546,17 @@ __global__ __launch_bounds__(512, 2) void encoder_bwd_roles_kernel(int N, const 
         for (int r = 0; r < 4; ++r)
           atomicAdd(dW2 + ((gw * 4 + kx) * 16 + 4 * q + r) * 32 + nt * 16 + i, (aw2[kx][nt][r] * INV_C1) * INV_D2);
   }
-  if (consumer || P3ALL) {
 #pragma unroll
-    for (int u = 0; u < NT3; ++u)
+  for (int u = 0; u < NT3; ++u)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) atomicAdd(dW1 + (16 * (NT3 * tset + u) + 4 * q + r) * 16 + i, scale * (aw1[u][r] * INV_D1));
-  }
+    for (int r = 0; r < 4; ++r) atomicAdd(dW1 + (16 * (NT3 * tset + u) + 4 * q + r) * 16 + i, scale * (aw1[u][r] * INV_D1));
   // bias gradients: ONE atomic per workgroup and channel (the 256 workgroups end together: 2,048 / 1,024 same-address
   // atomics per channel from per-wave flushes serialised into ~25 us per launch).  Partials meet in LDS -- the planes are
   // dead once every wave has left phase 3 of the last frame (first barrier).
   float v1[4], v2[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {        // db1: lanes with equal q hold channels 4q..4q+3 (positions differ with i)
-    float v = (consumer || P2SPLIT) ? adb1[e] : 0.f;
+    float v = consumer ? adb1[e] : 0.f;
     v += __shfl_xor(v, 1, 64);
     v += __shfl_xor(v, 2, 64);
     v += __shfl_xor(v, 4, 64);

@@ -61,14 +61,8 @@ __device__ __forceinline__ uint32_t render_byte(int idx, int ax, int ay) {
 // the step kernel VALU-bound at 1.6 TB/s) and streams it out for each of its actors; the agent block -- 12 rows of 36
 // contiguous bytes (0,1,0)x12, never on a wall cell -- is patched in afterwards as 9 dwords per row.
 constexpr int kActorsPerGroup = 8;
-#ifndef MAZE_APG_BIG
-#define MAZE_APG_BIG 8          // actors per workgroup of the step kernel at > 1024 actors (A/B: tools/exp/maze_apg_ab.py)
-#endif
-constexpr int kStepActorsBig = MAZE_APG_BIG;
-#ifndef MAZE_APG_TINY
-#define MAZE_APG_TINY 1         // actors per workgroup at <= 64 actors (a small update's rollout step: one actor per workgroup)
-#endif
-constexpr int kStepActorsTiny = MAZE_APG_TINY;
+constexpr int kStepActorsBig = 8;      // actors per workgroup of the step kernel at > 1024 actors
+constexpr int kStepActorsTiny = 1;     // actors per workgroup at <= 64 actors (a small update's rollout step: one actor per workgroup)
 
 __device__ __forceinline__ void build_wall_image(uint4* img) {
   for (int c = threadIdx.x; c < FRAME_BYTES / 16; c += blockDim.x) {

@@ -1,93 +1,56 @@
-// fp32-equivalent GEMMs on the 16-bit matrix cores of gfx950 ("split-operand").  Two operand formats:
-//   round 3 (all kernels): fp16 hi + lo with ONE power-of-two scale per tensor, 3 term pairs (see "fp16x2" below)
-//   round 2 (SPLIT_NT_MODE / SPLIT_TN_MODE 0, kept for A/B): 3 x bf16, 6 term pairs, described first:
+// fp32-equivalent GEMMs on the 16-bit matrix cores of gfx950 ("split-operand"):
 //
 //   C[M,N] = A[M,K] * W[N,K]^T (+ bias) (ReLU) (ReLU-mask) (accumulate)
 //
-// A is an fp32 activation matrix (k contiguous).  W is a WEIGHT matrix that the host keeps as a pre-split shadow:
-// three bf16 planes W = W1 + W2 + W3 (round-to-nearest at each level, residuals exact in fp32: 8+8+8 mantissa
-// bits), rows zero-padded to a multiple of 32 k (unreal_split_bf16x3, refreshed after every optimiser step).  A's
-// tile is split the same way when it is staged into LDS.  Each 32x32x16 product tile is accumulated in fp32 from
-// the six term pairs whose weight is >= 2^-16:
-//   a1b1, a1b2, a2b1, a1b3, a2b2, a3b1          (v_mfma_f32_32x32x16_bf16, exact bf16 x bf16 products)
-// The dropped pairs (a2b3, a3b2, a3b3) are below 2^-25 |ab| with random sign, i.e. under the rounding error of the
-// fp32 product they replace, so the result carries fp32-grade error (parity tests use the SAME tolerance as the
-// fp32-MFMA kernel of gemm.hip, and compare the two kernels' errors on the same data).
+// A is an fp32 activation matrix (k contiguous).  W is a WEIGHT matrix that the host keeps as a pre-split shadow: two
+// fp16 planes (hi, lo; see "fp16x2" below), rows zero-padded to a multiple of 32 k (unreal_split_f16x2, refreshed after
+// every optimiser step).  A's tile is split the same way when it is staged into LDS.  The result carries fp32-grade
+// error (parity tests use the SAME tolerance as the fp32-MFMA kernel of gemm.hip, and compare the two kernels' errors
+// on the same data).
 // Used for the forward and dgrad GEMMs of /root/reference/model/model.py:314,334,423 + BasicLSTMCell (model.py:110);
-// wgrad (both operands activations, k-major) stays on the fp32 MFMA path of gemm.hip.
+// the wgrad kernel below (both operands activations, k-major) uses the same core.
 //
-// Layout: 128x128x32 (or 64x64x32) block tile, 4 waves as 2x2.  LDS image per operand: [plane(3)][row][k(32) bf16]
+// Layout: 128x128x32 (or 64x64x32) block tile, 4 waves as 2x2.  LDS image per operand: [plane(2)][row][k(32) fp16]
 // with 80-byte rows (ds_read_b128 fragment reads are conflict-free).  One LDS buffer; the next K tile travels in
 // registers and is split/stored between the two barriers while the second half of the current tile's MFMAs runs.
 // Blocks are numbered so that the column blocks sharing one A row panel run back-to-back on ONE XCD (its L2 then
 // serves the re-reads; with the default order they land on 8 different L2s and A is fetched from HBM 2..8 times).
 //
-// fp16x2 (NT kernels).  x * s = hi + lo, both fp16 (round to nearest; hi + lo carries 22 significant bits), s the power of
+// fp16x2.  x * s = hi + lo, both fp16 (round to nearest; hi + lo carries 22 significant bits), s the power of
 // two that puts the tensor's largest |x| into [2^14, 2^15).  The tensor maxima travel in "absmax slots" (common.h): the
 // weight's is reduced when its shadow is made, an activation's is committed by the kernel that PRODUCES it (encoder,
 // GEMM / LSTM / deconv epilogues: one atomic per workgroup) -- unreal_absmax_f32 is the stand-alone reduction for callers that
 // have none.  A product tile accumulates hh + hl + lh on v_mfma_f32_32x32x16_f16 (the dropped ll pair is < 2^-22 |ab|) and
-// is un-scaled exactly in the epilogue.  Gate (tools/exp/f16x2_gate.py, profiles/r03_f16x2_gate.log):
-// on the trainer's live operands at production shape the error against fp64 is BELOW the plain-fp32-MFMA kernel's
-// (rms and max) for fc forward, fc dgrad and the LSTM dgrad, at 1.3 - 1.7x the speed of the 6-pass kernel.  The wgrad
-// form first FAILED that gate at K = 81,920 (rms 4.6e-7 vs 2.3e-7; the 6-pass form it replaces: 1.5e-6): the MFMA's own
-// accumulation is biased over a 3,400-deep chain.  With the accumulators flushed into a second fp32 set every 8 K tiles
-// (SPLIT_TN_FLUSH) it passes (1.0e-7 / 2.9e-7 against 2.3e-7 / 6.6e-7) at 1.28x the speed of the shipped 6-pass kernel.
+// is un-scaled exactly in the epilogue.  Gate (profiles/r03_f16x2_gate.log; now
+// tests/test_fullsize_gpu.py): on the trainer's live operands at production shape the error against fp64 is BELOW the
+// plain-fp32-MFMA kernel's (rms and max) for fc forward, fc dgrad and the LSTM dgrad.  The wgrad form first FAILED that
+// gate at K = 81,920 (rms 4.6e-7 vs 2.3e-7): the MFMA's own accumulation is biased over a 3,400-deep chain.  With the
+// accumulators flushed into a second fp32 set every 8 K tiles (TN_FLUSH) it passes (1.0e-7 / 2.9e-7 against 2.3e-7 / 6.6e-7).
 #include "common.h"
 
 namespace {
 
 constexpr int BK = 32;
-constexpr int MODE_BF16X3 = 0, MODE_F16X2 = 1;
-#ifndef SPLIT_NT_MODE
-#define SPLIT_NT_MODE 1     // 0: the round-2 bf16x3 NT kernels (A/B: tools/exp/f16x2_gate.py)
-#endif
-#ifndef SPLIT_TN_MODE
-#define SPLIT_TN_MODE 1     // 0: the round-2 bf16x3 wgrad kernel
-#endif
-__host__ __device__ constexpr int npl(int mode) { return mode == MODE_F16X2 ? 2 : 3; }   // operand planes
+constexpr int NPL = 2;                       // operand planes: hi, lo
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-template <int MODE> struct Frag { typedef __bf16 type __attribute__((ext_vector_type(8))); };
-template <> struct Frag<MODE_F16X2> { typedef f16x8 type; };
-constexpr int ROW_B = 80;                    // bytes per LDS row: 32 bf16 + 16 pad
+constexpr int ROW_B = 80;                    // bytes per LDS row: 32 fp16 + 16 pad
 constexpr int FLAG_RELU = 1, FLAG_ACCUM = 2, FLAG_ATOMIC = 4, FLAG_RELU_MASK = 8, FLAG_RELU_BITS = 16;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef SPLIT_ABLATE
-#define SPLIT_ABLATE 0      // tools/exp/split_ablate.py: 1 no global loads in the loop, 2 no split/store, 4 no MFMA,
-                            // 8 every block reads the same 8 rows of A (cache hits)
-#endif
-
-#ifndef SPLIT_NT_DBUF
-#define SPLIT_NT_DBUF 0     // 1: two LDS operand images, one barrier per K tile (tools/exp/gemm_ab.py)
-#endif
-#ifndef SPLIT_NT_OCC3
-#define SPLIT_NT_OCC3 1     // three 128 x 128 workgroups per CU (168 VGPRs, epilogue staged in two 64-row halves so that a
-                            // workgroup needs 40,960 B of LDS instead of 67,648).  Round 4, tools/exp/gemm_ab.py: the K = 256
-                            // products (13,440 tiles of 8 K steps: prologue / epilogue-bound) 0.89-0.90x the time, the long-K
-                            // products unchanged, outputs bit-identical (profiles/r04_gemm_occ3_ab.log).  0: two per CU.
-#endif
-#ifndef SPLIT_ROW_DEAL
-#define SPLIT_ROW_DEAL 1    // 0: tile rows in lane order (tools/exp/ab_split_rows.py times both)
-#endif
 // Which tile row an 8-lane (A, ds_write_b64) or 4-lane (W, ds_write_b128) block stages.  A store instruction's lane
 // group covers two such blocks; with 80-byte LDS rows, rows r and r + 1 overlap in 4 of the 32 store banks (every store
 // 2-way conflicted: 13 % of the kernel's cycles were LDS conflict cycles, all from stores), rows r and r + 4 do not
 // (80 * 4 = 320 B = 16 banks past a multiple of 128 B).  So blocks 2m and 2m + 1 take rows (m, m + 4) of each 8 rows.
-__device__ __forceinline__ int row_deal(int j) {
-  return SPLIT_ROW_DEAL ? ((j & ~7) | ((j & 1) << 2) | ((j >> 1) & 3)) : j;
-}
+__device__ __forceinline__ int row_deal(int j) { return (j & ~7) | ((j & 1) << 2) | ((j >> 1) & 3); }
 
 struct SplitArgs {
   int M, N, K;
   const float* A; int lda;
-  const unsigned short* W; int ldw; long plane;     // bf16 planes: W + t*plane + n*ldw + k
+  const unsigned short* W; int ldw; long plane;     // fp16 planes: W + t*plane + n*ldw + k
   float* C; int ldc;
   const float* bias;
   const float* mask; int ldm;
@@ -116,7 +79,7 @@ template <int ROWS, bool VEC>
 __device__ __forceinline__ f32x4 a_piece_load(const float* __restrict__ P, int ld, int rows_total, int K, int r0, int k0, int p,
                                               int tid) {
   const int id = tid + 256 * p;
-  const int r = (SPLIT_ABLATE & 8) ? (id / (BK / 4)) & 7 : min(r0 + row_deal(id / (BK / 4)), rows_total - 1);
+  const int r = min(r0 + row_deal(id / (BK / 4)), rows_total - 1);
   const int k = k0 + (id % (BK / 4)) * 4;
   const float* row = P + (size_t)r * ld;
   if (VEC) return *reinterpret_cast<const f32x4*>(row + min(k, ld - 4));
@@ -126,61 +89,30 @@ __device__ __forceinline__ f32x4 a_piece_load(const float* __restrict__ P, int l
   return v;
 }
 
-// 4 fp32 values -> three bf16x4 terms (8 bytes each): round to nearest, residual exact in fp32, twice.
-// PACKED selects how the residuals are subtracted: as 2-vectors (v_pk_add_f32) or with scalar v_sub_f32.  Same values
-// either way; A/B on one device: the NT kernels (one operand split) are 1-5 % faster with the scalar form, the TN
-// kernel (both operands split, twice the VALU) 5 % faster with the packed one.
-template <bool PACKED, int MODE = MODE_BF16X3>
-__device__ __forceinline__ void split4_terms(float x0, float x1, float x2, float x3, u32x2 (&pl)[3]) {
-  if (MODE == MODE_F16X2) {   // x (already scaled) = hi + lo, both fp16, round to nearest; pl[2] unused
-    const f16x2 h01 = __builtin_convertvector((f32x2){x0, x1}, f16x2), h23 = __builtin_convertvector((f32x2){x2, x3}, f16x2);
-    const f32x2 r01 = (f32x2){x0, x1} - __builtin_convertvector(h01, f32x2), r23 = (f32x2){x2, x3} - __builtin_convertvector(h23, f32x2);
-    const f16x2 l01 = __builtin_convertvector(r01, f16x2), l23 = __builtin_convertvector(r23, f16x2);
-    pl[0] = (u32x2){__builtin_bit_cast(unsigned int, h01), __builtin_bit_cast(unsigned int, h23)};
-    pl[1] = (u32x2){__builtin_bit_cast(unsigned int, l01), __builtin_bit_cast(unsigned int, l23)};
-    pl[2] = pl[1];
-    return;
-  }
-  if (PACKED) {
-    f32x2 x01 = {x0, x1}, x23 = {x2, x3};
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      const bf16x2 h01 = __builtin_convertvector(x01, bf16x2), h23 = __builtin_convertvector(x23, bf16x2);
-      pl[t] = (u32x2){__builtin_bit_cast(unsigned int, h01), __builtin_bit_cast(unsigned int, h23)};
-      if (t < 2) {
-        x01 = x01 - __builtin_convertvector(h01, f32x2);
-        x23 = x23 - __builtin_convertvector(h23, f32x2);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      const bf16x2 h01 = __builtin_convertvector((f32x2){x0, x1}, bf16x2), h23 = __builtin_convertvector((f32x2){x2, x3}, bf16x2);
-      const unsigned int w01 = __builtin_bit_cast(unsigned int, h01), w23 = __builtin_bit_cast(unsigned int, h23);
-      pl[t] = (u32x2){w01, w23};
-      if (t < 2) {
-        x0 -= __uint_as_float(w01 << 16); x1 -= __uint_as_float(w01 & 0xffff0000u);
-        x2 -= __uint_as_float(w23 << 16); x3 -= __uint_as_float(w23 & 0xffff0000u);
-      }
-    }
-  }
+// 4 fp32 values (already scaled) -> hi + lo, both fp16x4 (8 bytes each), round to nearest
+__device__ __forceinline__ void split4_terms(float x0, float x1, float x2, float x3, u32x2 (&pl)[NPL]) {
+  const f16x2 h01 = __builtin_convertvector((f32x2){x0, x1}, f16x2), h23 = __builtin_convertvector((f32x2){x2, x3}, f16x2);
+  const f32x2 r01 = (f32x2){x0, x1} - __builtin_convertvector(h01, f32x2), r23 = (f32x2){x2, x3} - __builtin_convertvector(h23, f32x2);
+  const f16x2 l01 = __builtin_convertvector(r01, f16x2), l23 = __builtin_convertvector(r23, f16x2);
+  pl[0] = (u32x2){__builtin_bit_cast(unsigned int, h01), __builtin_bit_cast(unsigned int, h23)};
+  pl[1] = (u32x2){__builtin_bit_cast(unsigned int, l01), __builtin_bit_cast(unsigned int, l23)};
 }
 
-// split 4 consecutive-k fp32 values into three bf16 planes and store 8 bytes per plane; klim = K - k0 of that tile
-template <int ROWS, int MODE, bool RAGGED = true>
+// scale and split 4 consecutive-k fp32 values into the two planes and store 8 bytes per plane; klim = K - k0 of that tile
+template <int ROWS>
 __device__ __forceinline__ void a_piece_store(unsigned char* S, f32x4 v, int klim, int p, int tid, float scale) {
   const int id = tid + 256 * p;
   const int r = row_deal(id / (BK / 4)), k = (id % (BK / 4)) * 4;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = (!RAGGED || k + e < klim) ? (MODE == MODE_F16X2 ? v[e] * scale : v[e]) : 0.f;
-  u32x2 pl[3];
-  split4_terms<false, MODE>(v[0], v[1], v[2], v[3], pl);
+  for (int e = 0; e < 4; ++e) v[e] = k + e < klim ? v[e] * scale : 0.f;
+  u32x2 pl[NPL];
+  split4_terms(v[0], v[1], v[2], v[3], pl);
 #pragma unroll
-  for (int t = 0; t < npl(MODE); ++t)
+  for (int t = 0; t < NPL; ++t)
     *reinterpret_cast<u32x2*>(S + (t * ROWS + r) * ROW_B + k * 2) = pl[t];
 }
 
-// weight tile piece: 3 planes x ROWS rows x 64 B, 16 B per lane (planes are zero-padded in k, rows clamped)
+// weight tile piece: 2 planes x ROWS rows x 64 B, 16 B per lane (planes are zero-padded in k, rows clamped)
 template <int ROWS>
 __device__ __forceinline__ u32x4 w_piece_load(const unsigned short* __restrict__ W, int ldw, long plane, int rows_total,
                                               int r0, int k0, int p, int tid) {
@@ -198,47 +130,28 @@ __device__ __forceinline__ void w_piece_store(unsigned char* S, u32x4 v, int p, 
 }
 
 // SWZ: the 16-byte k chunk c of row r sits at chunk c ^ ((r >> 4) & 3) (transposing stores of the TN kernel)
-template <int BM, int BN, int MODE, bool SWZ = false>
+template <int BM, int BN, bool SWZ = false>
 __device__ __forceinline__ void read_frags(const unsigned char* As, const unsigned char* Bs, int wm, int wn, int li, int kh,
-                                           int ks, typename Frag<MODE>::type (&af)[BM / 64][npl(MODE)],
-                                           typename Frag<MODE>::type (&bf)[BN / 64][npl(MODE)]) {
-  typedef typename Frag<MODE>::type frag8;
+                                           int ks, f16x8 (&af)[BM / 64][NPL], f16x8 (&bf)[BN / 64][NPL]) {
   const int c = 2 * ks + kh;
 #pragma unroll
   for (int i = 0; i < BM / 64; ++i)
 #pragma unroll
-    for (int t = 0; t < npl(MODE); ++t) {
+    for (int t = 0; t < NPL; ++t) {
       const int r = wm * (BM / 2) + i * 32 + li;
-      af[i][t] = *reinterpret_cast<const frag8*>(As + (t * BM + r) * ROW_B + (SWZ ? (c ^ ((r >> 4) & 3)) : c) * 16);
+      af[i][t] = *reinterpret_cast<const f16x8*>(As + (t * BM + r) * ROW_B + (SWZ ? (c ^ ((r >> 4) & 3)) : c) * 16);
     }
 #pragma unroll
   for (int j = 0; j < BN / 64; ++j)
 #pragma unroll
-    for (int t = 0; t < npl(MODE); ++t) {
+    for (int t = 0; t < NPL; ++t) {
       const int r = wn * (BN / 2) + j * 32 + li;
-      bf[j][t] = *reinterpret_cast<const frag8*>(Bs + (t * BN + r) * ROW_B + (SWZ ? (c ^ ((r >> 4) & 3)) : c) * 16);
+      bf[j][t] = *reinterpret_cast<const f16x8*>(Bs + (t * BN + r) * ROW_B + (SWZ ? (c ^ ((r >> 4) & 3)) : c) * 16);
     }
 }
 
 template <int TM, int TN>
-__device__ __forceinline__ void mma_frags(const bf16x8 (&af)[TM][3], const bf16x8 (&bf)[TN][3], f32x16 (&acc)[TM][TN]) {
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      f32x16 c = acc[i][j];
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], bf[j][0], c, 0, 0, 0);   // smallest terms first
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][2], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][1], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][0], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][1], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][0], c, 0, 0, 0);
-      acc[i][j] = c;
-    }
-}
-
-template <int TM, int TN>
-__device__ __forceinline__ void mma_frags(const f16x8 (&af)[TM][2], const f16x8 (&bf)[TN][2], f32x16 (&acc)[TM][TN]) {
+__device__ __forceinline__ void mma_frags(const f16x8 (&af)[TM][NPL], const f16x8 (&bf)[TN][NPL], f32x16 (&acc)[TM][TN]) {
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -250,33 +163,6 @@ __device__ __forceinline__ void mma_frags(const f16x8 (&af)[TM][2], const f16x8 
       acc[i][j] = c;
     }
 }
-
-// DEEP: activation tiles travel two K tiles ahead instead of one.  Measured on one device, same process: +20 % on the
-// 64x64 kernel's long-K shapes (4096 x 256 x 2592: 76 -> 62 us), -3 % on the 128x128 kernel (16 more live registers).
-//
-// KW (64x64 tiles of the 4096-row rollout / BPTT steps): KW groups of 4 waves share ONE output tile and deal its K tiles
-// round-robin (group g takes tiles g, g + KW, ...), each with its own LDS image; their partial tiles are summed in a
-// fixed order in the epilogue.  A 4096 x 256 product has only 256 tiles of 64 x 64 -- one 4-wave workgroup per CU, one
-// wave per SIMD, nothing to hide an LDS read or a barrier behind; with KW = 4 the same tile keeps 4 waves per SIMD busy
-// without fetching any operand byte twice (smaller tiles would) and without a zero-fill + atomics pass (split-K over
-// workgroups would).
-//
-// DUAL (the LSTM step of a rollout): the A operand is the row-wise concatenation [A | A2] -- k < K1pad comes from A
-// (K1 valid columns, zero beyond), the rest from A2 -- multiplied by ONE weight shadow laid out the same way, so the
-// input half and the recurrent half of the gates are one product (BasicLSTMCell's own [x, h] @ kernel, model.py:110).
-#ifdef SPLIT_STAMPS      // diagnostic build only (tools/exp/lstm_step_stamps.py): where one workgroup's time goes
-__device__ unsigned long long g_split_stamps[8];
-#define SSTAMP(k)                                                                  \
-  do {                                                                             \
-    if (blockIdx.x == 9 && threadIdx.x == 0) {                                     \
-      const unsigned long long t_ = __builtin_amdgcn_s_memtime();                  \
-      g_split_stamps[k] += t_ - t_prev_;                                           \
-      t_prev_ = t_;                                                                \
-    }                                                                              \
-  } while (0)
-#else
-#define SSTAMP(k)
-#endif
 
 template <bool DUAL>
 struct ASrc { const float* P; int ld, K, k0; };
@@ -294,36 +180,42 @@ __device__ __forceinline__ ASrc<DUAL> a_src(const SplitArgs& p, int kg) {
   return s;
 }
 
-// RAG false (K a multiple of 32, one wave group, one A source: the big products of the trainer): no k of a tile lies past
-// K, the per-element selects of the A split go
-template <int BM, int BN, bool VEC, bool DEEP = (BM == 64), int EPI = 0, int KW = 1, bool DUAL = false, bool RAG = true>
-__global__ __launch_bounds__(256 * KW, KW == 1 ? ((BM == 64 && BN == 128) ? 4 : (SPLIT_NT_OCC3 && BM == 128 && EPI == 0) ? 3 : 2) : 1) void gemm_split_nt_kernel(SplitArgs p) {
-  constexpr int MODE = SPLIT_NT_MODE, NPL = npl(MODE);
-  typedef typename Frag<MODE>::type frag8;
+// DEEP (the 64 x 64 kernels): activation tiles travel two K tiles ahead instead of one.  Measured on one device, same
+// process: +20 % on the 64x64 kernel's long-K shapes (4096 x 256 x 2592: 76 -> 62 us), -3 % on the 128x128 kernel (16
+// more live registers).
+//
+// KW (64x64 tiles of the 4096-row rollout / BPTT steps): KW groups of 4 waves share ONE output tile and deal its K tiles
+// round-robin (group g takes tiles g, g + KW, ...), each with its own LDS image; their partial tiles are summed in a
+// fixed order in the epilogue.  A 4096 x 256 product has only 256 tiles of 64 x 64 -- one 4-wave workgroup per CU, one
+// wave per SIMD, nothing to hide an LDS read or a barrier behind; with KW = 4 the same tile keeps 4 waves per SIMD busy
+// without fetching any operand byte twice (smaller tiles would) and without a zero-fill + atomics pass (split-K over
+// workgroups would).
+//
+// DUAL (the LSTM step of a rollout): the A operand is the row-wise concatenation [A | A2] -- k < K1pad comes from A
+// (K1 valid columns, zero beyond), the rest from A2 -- multiplied by ONE weight shadow laid out the same way, so the
+// input half and the recurrent half of the gates are one product (BasicLSTMCell's own [x, h] @ kernel, model.py:110).
+//
+// 128 x 128 with one wave group and the plain epilogue: THREE workgroups per CU (168 VGPRs; the C tile leaves in two 64-row
+// halves so that a workgroup needs 40,960 B of LDS instead of 67,648).  Round 4: the K = 256 products (13,440 tiles of 8 K
+// steps: prologue / epilogue-bound) 0.89-0.90x the time of two per CU, the long-K products unchanged, outputs
+// bit-identical (profiles/r04_gemm_occ3_ab.log).
+template <int BM, int BN, bool VEC, int EPI = 0, int KW = 1, bool DUAL = false>
+__global__ __launch_bounds__(256 * KW, KW == 1 ? ((BM == 128 && EPI == 0) ? 3 : 2) : 1) void gemm_split_nt_kernel(SplitArgs p) {
+  constexpr bool DEEP = BM == 64;
   constexpr int TM = BM / 64, TN = BN / 64;
   constexpr int PA = BM * BK / 1024, PW = NPL * BN / 64;
   constexpr int A_BYTES = NPL * BM * ROW_B, B_BYTES = NPL * BN * ROW_B;
-  // fp16x2: the tensors' power-of-two scales (exact), read once; everything below is scale-free in the bf16x3 mode
-  float SA = 1.f, INV_A = 1.f, INV_W = 1.f;
-  if (MODE == MODE_F16X2) {
-    SA = pow2_scale(fmaxf(p.a_absmax ? *p.a_absmax : 0.f, p.a_floor));
-    INV_A = pow2_inv(SA);
-    INV_W = pow2_inv(pow2_scale(*p.w_absmax));
-  }
-  constexpr bool HALF = SPLIT_NT_OCC3 && BM == 128 && EPI == 0 && KW == 1;      // epilogue staged in two 64-row halves
+  // the tensors' power-of-two scales (exact), read once
+  const float SA = pow2_scale(fmaxf(p.a_absmax ? *p.a_absmax : 0.f, p.a_floor));
+  const float INV_A = pow2_inv(SA);
+  const float INV_W = pow2_inv(pow2_scale(*p.w_absmax));
+  constexpr bool HALF = BM == 128 && EPI == 0 && KW == 1;      // epilogue staged in two 64-row halves
   constexpr int C_BYTES = (HALF ? BM / 2 : BM) * (BN + 4) * 4;
-  // DBUF: two operand images -- tile it + 1 is split / stored into the other one while tile it is multiplied, so a K tile
-  // costs ONE workgroup barrier (stores visible) instead of two (all reads done; stores visible).  128 x 128: 2 x 40,960 B
-  // per workgroup, two workgroups per CU use the 160 KB exactly.
-  constexpr int NBUF = SPLIT_NT_DBUF ? 2 : 1;
   constexpr int OP_BYTES = A_BYTES + B_BYTES;
   constexpr int RED_BYTES = 64;                  // the epilogues' per-wave maxima (absmax commits) live behind the C tile
-  constexpr int SMEM = (NBUF * OP_BYTES) > (C_BYTES + RED_BYTES) ? (NBUF * OP_BYTES) : (C_BYTES + RED_BYTES);
+  constexpr int SMEM = OP_BYTES > (C_BYTES + RED_BYTES) ? OP_BYTES : (C_BYTES + RED_BYTES);
   static_assert(4 * KW * 4 <= RED_BYTES, "one float per wave");
   __shared__ __attribute__((aligned(16))) unsigned char smem_all[KW * SMEM];
-#ifdef SPLIT_STAMPS
-  unsigned long long t_prev_ = __builtin_amdgcn_s_memtime();
-#endif
   const int tid = KW == 1 ? (int)threadIdx.x : (int)(threadIdx.x & 255);
   const int grp = KW == 1 ? 0 : (int)(threadIdx.x >> 8);
   unsigned char* smem = smem_all + grp * SMEM;
@@ -370,7 +262,7 @@ __global__ __launch_bounds__(256 * KW, KW == 1 ? ((BM == 64 && BN == 128) ? 4 : 
 #pragma unroll
     for (int q = 0; q < PW; ++q) rw[q] = w_piece_load<BN>(p.W, p.ldw, p.plane, p.N, n0, k0, q, tid);
 #pragma unroll
-    for (int q = 0; q < PA; ++q) a_piece_store<BM, MODE, RAG>(As, ra[0][q], KLIM(0, s0), q, tid, SA);
+    for (int q = 0; q < PA; ++q) a_piece_store<BM>(As, ra[0][q], KLIM(0, s0), q, tid, SA);
 #pragma unroll
     for (int q = 0; q < PW; ++q) w_piece_store<BN>(Bs, rw[q], q, tid);
     const int k1 = KG_AT(1), k2 = KG_AT(2);
@@ -385,7 +277,6 @@ __global__ __launch_bounds__(256 * KW, KW == 1 ? ((BM == 64 && BN == 128) ? 4 : 
     for (int q = 0; q < PW; ++q) rw[q] = w_piece_load<BN>(p.W, p.ldw, p.plane, p.N, n0, k1, q, tid);
   }
   __syncthreads();
-  SSTAMP(0);       // prologue: first tile fetched, split, stored; next tiles requested
 
   // One K tile.  Tile it+1 leaves register set S (split, LDS store) and tile it+3 is fetched into it, piece by piece,
   // next to the second-half MFMAs: loads spread between MFMAs keep the CU's vector-memory queue short (8 waves
@@ -396,66 +287,26 @@ __global__ __launch_bounds__(256 * KW, KW == 1 ? ((BM == 64 && BN == 128) ? 4 : 
   // interleaves it (explicit sched_group_barrier pipelines measured 5-10 % slower than its own schedule).
 #define SPLIT_NT_TILE(S, IT)                                                                                        \
   {                                                                                                                 \
-    frag8 af[TM][NPL], bf[TN][NPL];                                                                                  \
-    if (!(SPLIT_ABLATE & 4)) {                                                                                      \
-      read_frags<BM, BN, MODE>(As, Bs, wm, wn, li, kh, 0, af, bf);                                                  \
-      mma_frags<TM, TN>(af, bf, acc);                                                                               \
-      read_frags<BM, BN, MODE>(As, Bs, wm, wn, li, kh, 1, af, bf);   /* second half: read before, multiplied after */ \
-    }                                                                                                               \
+    f16x8 af[TM][NPL], bf[TN][NPL];                                                                                 \
+    read_frags<BM, BN>(As, Bs, wm, wn, li, kh, 0, af, bf);                                                          \
+    mma_frags<TM, TN>(af, bf, acc);                                                                                 \
+    read_frags<BM, BN>(As, Bs, wm, wn, li, kh, 1, af, bf);   /* second half: read before, multiplied after */       \
     __syncthreads();                                   /* every wave has read tile IT */                            \
     const int kcur = KG_AT((IT) + 1), kw = KG_AT((IT) + 2), ka = KG_AT((IT) + (DEEP ? 3 : 2));                      \
     const ASrc<DUAL> scur = a_src<DUAL>(p, kcur), snext = a_src<DUAL>(p, ka);                                       \
     const int klim = KLIM((IT) + 1, scur);                                                                          \
     _Pragma("unroll") for (int q = 0; q < PA; ++q) {                                                                \
-      if (!(SPLIT_ABLATE & 2) || (IT) == 0) a_piece_store<BM, MODE, RAG>(As, ra[S][q], klim, q, tid, SA);                \
-      if (!(SPLIT_ABLATE & 1)) ra[S][q] = A_LOAD(snext, q);                                                         \
-    }                                                                                                               \
-    _Pragma("unroll") for (int q = 0; q < PW; ++q) {                                                                \
-      if (!(SPLIT_ABLATE & 2) || (IT) == 0) w_piece_store<BN>(Bs, rw[q], q, tid);                                   \
-      if (!(SPLIT_ABLATE & 1)) rw[q] = w_piece_load<BN>(p.W, p.ldw, p.plane, p.N, n0, kw, q, tid);                  \
-    }                                                                                                               \
-    if (!(SPLIT_ABLATE & 4)) mma_frags<TM, TN>(af, bf, acc);                                                        \
-    __syncthreads();                                   /* tile IT + 1 is visible */                                 \
-  }
-  // DBUF form of one K tile: fragments of tile IT come from image IT & 1; tile IT + 1 goes into the other image at any
-  // point of the step (everybody left that image before the previous step's barrier), so the split VALU, the LDS stores
-  // and the next global loads spread over all 24 MFMAs; the one barrier sits before the second half's MFMAs, which then
-  // run while the slower waves arrive.
-#define SPLIT_NT_TILE_DB(S, IT)                                                                                     \
-  {                                                                                                                 \
-    frag8 af[TM][NPL], bf[TN][NPL];                                                                                  \
-    const unsigned char* Ac = As + ((IT) & 1) * OP_BYTES;                                                           \
-    const unsigned char* Bc = Bs + ((IT) & 1) * OP_BYTES;                                                           \
-    unsigned char* An = As + (((IT) + 1) & 1) * OP_BYTES;                                                           \
-    unsigned char* Bn = Bs + (((IT) + 1) & 1) * OP_BYTES;                                                           \
-    read_frags<BM, BN, MODE>(Ac, Bc, wm, wn, li, kh, 0, af, bf);                                                    \
-    const int kcur = KG_AT((IT) + 1), kw = KG_AT((IT) + 2), ka = KG_AT((IT) + (DEEP ? 3 : 2));                      \
-    const ASrc<DUAL> scur = a_src<DUAL>(p, kcur), snext = a_src<DUAL>(p, ka);                                       \
-    const int klim = KLIM((IT) + 1, scur);                                                                          \
-    _Pragma("unroll") for (int q = 0; q < PA; ++q) {                                                                \
-      a_piece_store<BM, MODE, RAG>(An, ra[S][q], klim, q, tid, SA);                                                      \
+      a_piece_store<BM>(As, ra[S][q], klim, q, tid, SA);                                                            \
       ra[S][q] = A_LOAD(snext, q);                                                                                  \
     }                                                                                                               \
     _Pragma("unroll") for (int q = 0; q < PW; ++q) {                                                                \
-      w_piece_store<BN>(Bn, rw[q], q, tid);                                                                         \
+      w_piece_store<BN>(Bs, rw[q], q, tid);                                                                         \
       rw[q] = w_piece_load<BN>(p.W, p.ldw, p.plane, p.N, n0, kw, q, tid);                                           \
     }                                                                                                               \
     mma_frags<TM, TN>(af, bf, acc);                                                                                 \
-    read_frags<BM, BN, MODE>(Ac, Bc, wm, wn, li, kh, 1, af, bf);                                                    \
-    __syncthreads();                                   /* tile IT + 1 is visible; everybody has read tile IT */      \
-    mma_frags<TM, TN>(af, bf, acc);                                                                                 \
+    __syncthreads();                                   /* tile IT + 1 is visible */                                 \
   }
-  if (SPLIT_NT_DBUF) {
-    if (DEEP) {
-      for (int it = 0; it < nit; it += 2) {
-        SPLIT_NT_TILE_DB(0, it)
-        if (it + 1 < nit) SPLIT_NT_TILE_DB(1, it + 1)
-      }
-    } else {
-      for (int it = 0; it < nit; ++it) SPLIT_NT_TILE_DB(0, it)
-    }
-    __syncthreads();     // the epilogue parks its tile over the operand images: every wave must have read the last one
-  } else if (DEEP) {
+  if (DEEP) {
     for (int it = 0; it < nit; it += 2) {
       SPLIT_NT_TILE(0, it)
       if (it + 1 < nit) SPLIT_NT_TILE(1, it + 1)
@@ -464,8 +315,6 @@ __global__ __launch_bounds__(256 * KW, KW == 1 ? ((BM == 64 && BN == 128) ? 4 : 
     for (int it = 0; it < nit; ++it) SPLIT_NT_TILE(0, it)
   }
 #undef SPLIT_NT_TILE
-#undef SPLIT_NT_TILE_DB
-  SSTAMP(1);       // K loop
 #undef A_LOAD
 #undef KLIM
 #undef KG_AT
@@ -483,7 +332,7 @@ __global__ __launch_bounds__(256 * KW, KW == 1 ? ((BM == 64 && BN == 128) ? 4 : 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int row = m0 + wm * (BM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-          const float v = MODE == MODE_F16X2 ? (acc[i][j][r] * INV_A) * INV_W : acc[i][j][r];
+          const float v = (acc[i][j][r] * INV_A) * INV_W;
           if (row < p.M) atomicAdd(p.C + (size_t)row * p.ldc + col, v + bv);
         }
       }
@@ -514,7 +363,7 @@ __global__ __launch_bounds__(256 * KW, KW == 1 ? ((BM == 64 && BN == 128) ? 4 : 
 #pragma unroll
             for (int r = 0; r < 16; ++r)
               Cs[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh) * CLD + wn * (BN / 2) + j * 32 + li] =
-                  MODE == MODE_F16X2 ? (acc[i][j][r] * INV_A) * INV_W : acc[i][j][r];
+                  (acc[i][j][r] * INV_A) * INV_W;
       }
       __syncthreads();
       for (int id = threadIdx.x; id < (BM / 2) * CV; id += 256) {
@@ -574,14 +423,13 @@ __global__ __launch_bounds__(256 * KW, KW == 1 ? ((BM == 64 && BN == 128) ? 4 : 
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         Cs[(wm * (BM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh) * CLD + wn * (BN / 2) + j * 32 + li] =
-            MODE == MODE_F16X2 ? (acc[i][j][r] * INV_A) * INV_W : acc[i][j][r];
+            (acc[i][j][r] * INV_A) * INV_W;
   __syncthreads();
-  SSTAMP(2);       // partial tiles parked in LDS
   const float* C0 = reinterpret_cast<const float*>(smem_all);
   constexpr int GSTRIDE = SMEM / 4;                   // floats between the partial tiles of consecutive groups
   if (EPI == 1) {
     // BasicLSTMCell gate math fused into the recurrent GEMM (model/model.py:110, TF BasicLSTMCell: gates i,j,f,o,
-    // forget_bias 1).  The weight shadow is gate-interleaved (unreal_split_bf16x3 row_perm = 1): this block's 64
+    // forget_bias 1).  The weight shadow is gate-interleaved (unreal_split_f16x2 row_perm = 1): this block's 64
     // columns are hidden units u0..u0+15 of the four gates, so the tile holds everything one unit needs.
     // FLAG_ACCUM: C holds the input-half pre-activations on entry (added after the product, as the chain does).
     const int u0 = bx * (BN / 4);
@@ -627,7 +475,6 @@ __global__ __launch_bounds__(256 * KW, KW == 1 ? ((BM == 64 && BN == 128) ? 4 : 
       p.c_out[(size_t)row * 256 + u] = c;
       p.h_out[(size_t)row * p.ld_h + u] = tanhf(c) * go;
     }
-    SSTAMP(3);     // gate math + stores issued
     return;
   }
   if (EPI == 2) {
@@ -753,7 +600,7 @@ __global__ __launch_bounds__(256 * KW, KW == 1 ? ((BM == 64 && BN == 128) ? 4 : 
 //
 // Same MFMA core; the difference is the staging.  A thread owns a 4(k) x 4(m) patch of the 32(k) x 128(m) tile: four
 // 16-byte loads (one per k row, 512 B contiguous per row across 32 lanes), a register transpose, and per m a split of
-// the 4 k values into 3 bf16 planes stored as 8 bytes at [plane][m][k] -- the same LDS image the NT kernel reads.
+// the 4 k values into the 2 fp16 planes stored as 8 bytes at [plane][m][k] -- the same LDS image the NT kernel reads.
 // The stores of 32 lanes go to rows 4 apart (320 B = 16 banks), so the 16-byte chunk index is XOR-swizzled with row
 // bits 4-5: 2-way instead of 8-way bank conflicts; the fragment reads apply the same swizzle and stay conflict-free.
 struct SplitTnArgs {
@@ -763,7 +610,7 @@ struct SplitTnArgs {
   float* C; int ldc;
   float* colsum;                       // nullable: colsum[n] += sum_k B[k][n] (the bias gradient that goes with dW)
   int ntx, nty, splitk, ktiles_per_split;
-  const float* a_absmax; const float* b_absmax;     // fp16x2: absmax slots of A and B
+  const float* a_absmax; const float* b_absmax;     // absmax slots of A and B
 };
 
 // Thread -> (m4: which 4 columns of the 128, k4: which 4 k rows of the 32) of the TN tile it stages.  Lane order
@@ -772,16 +619,13 @@ struct SplitTnArgs {
 // conflict cycles).  Dealing tid bit 0 to k4 and bits 1-5 to m4 bits 0, 2, 3, 1, 4 makes a store group cover both 8-byte
 // halves, both row parities and four different swizzled chunks: 16 distinct slots.  A wave still reads two whole
 // 512-byte rows per load instruction.
-#ifndef SPLIT_TN_DEAL
-#define SPLIT_TN_DEAL 1
-#endif
 __device__ __forceinline__ int tn_m4() {
   const int t = threadIdx.x;
-  return SPLIT_TN_DEAL ? (((t >> 1) & 1) | (((t >> 4) & 1) << 1) | (((t >> 2) & 3) << 2) | (((t >> 5) & 1) << 4)) : (t & 31);
+  return ((t >> 1) & 1) | (((t >> 4) & 1) << 1) | (((t >> 2) & 3) << 2) | (((t >> 5) & 1) << 4);
 }
 __device__ __forceinline__ int tn_k4() {
   const int t = threadIdx.x;
-  return SPLIT_TN_DEAL ? ((t & 1) | ((t >> 6) << 1)) : (t >> 5);
+  return (t & 1) | ((t >> 6) << 1);
 }
 
 __device__ __forceinline__ void tn_piece_load(const float* __restrict__ P, int ld, int K, int c0, int k0, f32x4 (&reg)[4]) {
@@ -795,7 +639,7 @@ __device__ __forceinline__ void tn_piece_load(const float* __restrict__ P, int l
 }
 
 // RAGGED false (K a multiple of 32: every production wgrad): no k row of a tile lies past K, the 32 selects per tile go
-template <int ROWS, int MODE, bool RAGGED = true>
+template <int ROWS, bool RAGGED>
 __device__ __forceinline__ void tn_piece_store(unsigned char* S, const f32x4 (&reg)[4], int klim, float scale) {
   const int m4 = tn_m4(), k4 = tn_k4();
   bool ok[4];
@@ -804,19 +648,18 @@ __device__ __forceinline__ void tn_piece_store(unsigned char* S, const f32x4 (&r
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int r = 4 * m4 + j;
-    u32x2 pl[3];
-    const float sc = MODE == MODE_F16X2 ? scale : 1.f;
-    split4_terms<true, MODE>(ok[0] ? reg[0][j] * sc : 0.f, ok[1] ? reg[1][j] * sc : 0.f, ok[2] ? reg[2][j] * sc : 0.f,
-                             ok[3] ? reg[3][j] * sc : 0.f, pl);
+    u32x2 pl[NPL];
+    split4_terms(ok[0] ? reg[0][j] * scale : 0.f, ok[1] ? reg[1][j] * scale : 0.f, ok[2] ? reg[2][j] * scale : 0.f,
+                 ok[3] ? reg[3][j] * scale : 0.f, pl);
     const int off = (((k4 >> 1) ^ ((r >> 4) & 3)) * 2 + (k4 & 1)) * 8;       // swizzled 16-B chunk, 8-B half
 #pragma unroll
-    for (int t = 0; t < npl(MODE); ++t)
+    for (int t = 0; t < NPL; ++t)
       *reinterpret_cast<u32x2*>(S + (t * ROWS + r) * ROW_B + off) = pl[t];
   }
 }
 
 // column sums of the B tile a thread holds (rows past K masked), weighted by w (0 or 1)
-template <bool RAGGED = true>
+template <bool RAGGED>
 __device__ __forceinline__ void tn_colsum_acc(const f32x4 (&reg)[4], int klim, float w, float (&cs)[4]) {
   const int k4 = tn_k4();
 #pragma unroll
@@ -830,19 +673,11 @@ __device__ __forceinline__ void tn_colsum_acc(const f32x4 (&reg)[4], int klim, f
 template <bool RAGGED>
 __global__ __launch_bounds__(256, 2) void gemm_split_tn_kernel(SplitTnArgs p) {
   constexpr int BM = 128, BN = 128, TM = 2, TN = 2;
-  constexpr int MODE = SPLIT_TN_MODE, NPL = npl(MODE);
-  typedef typename Frag<MODE>::type frag8;
   constexpr int A_BYTES = NPL * BM * ROW_B, B_BYTES = NPL * BN * ROW_B;
-#ifndef SPLIT_TN_DBUF
-#define SPLIT_TN_DBUF 0     // 1: two LDS operand images, one barrier per K tile (as SPLIT_NT_DBUF)
-#endif
-  constexpr int OP_BYTES = A_BYTES + B_BYTES, NBUF = SPLIT_TN_DBUF ? 2 : 1;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[NBUF * OP_BYTES > 8 * BN * 4 ? NBUF * OP_BYTES : 8 * BN * 4];
-  float SA = 1.f, SB = 1.f, INV_A = 1.f, INV_B = 1.f;
-  if (MODE == MODE_F16X2) {
-    SA = pow2_scale(*p.a_absmax); SB = pow2_scale(*p.b_absmax);
-    INV_A = pow2_inv(SA); INV_B = pow2_inv(SB);
-  }
+  constexpr int OP_BYTES = A_BYTES + B_BYTES;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[OP_BYTES > 8 * BN * 4 ? OP_BYTES : 8 * BN * 4];
+  const float SA = pow2_scale(*p.a_absmax), SB = pow2_scale(*p.b_absmax);
+  const float INV_A = pow2_inv(SA), INV_B = pow2_inv(SB);
   unsigned char* As = smem;
   unsigned char* Bs = smem + A_BYTES;
 
@@ -870,22 +705,18 @@ __global__ __launch_bounds__(256, 2) void gemm_split_tn_kernel(SplitTnArgs p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-#ifndef SPLIT_TN_FLUSH
-#define SPLIT_TN_FLUSH 8      // K tiles between two flushes of the MFMA accumulators (0: never)
-#endif
+  constexpr int TN_FLUSH = 8;      // K tiles between two flushes of the MFMA accumulators
   // Long-K accuracy: the MFMA adds its 16 products into the running accumulator with a rounding that is biased (measured:
-  // at K = 81,920 the error of a 3,400-long chain grows linearly with the chain, fp16x2 4.6e-7 and bf16x3 1.5e-6 rms against
-  // 2.3e-7 for the fp32 MFMA's round-to-nearest chain).  So every SPLIT_TN_FLUSH tiles the accumulators are added into a
-  // second fp32 set with ordinary VALU adds (round to nearest) and restarted from zero: the MFMA chains stay short.
+  // at K = 81,920 the error of a 3,400-long chain grows linearly with the chain, 4.6e-7 rms against 2.3e-7 for the fp32
+  // MFMA's round-to-nearest chain).  So every TN_FLUSH tiles the accumulators are added into a second fp32 set with
+  // ordinary VALU adds (round to nearest) and restarted from zero: the MFMA chains stay short.
   f32x16 tot[TM][TN];
-  if (SPLIT_TN_FLUSH > 0) {
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+  for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j)
+    for (int j = 0; j < TN; ++j)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.f;
-  }
+      for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.f;
   f32x4 ra[4], rb[4];
   // bias gradient: the row of tiles by == 0 also sums the columns of every B tile it stages (multiplying by 0
   // elsewhere keeps the K loop one basic block)
@@ -893,8 +724,8 @@ __global__ __launch_bounds__(256, 2) void gemm_split_tn_kernel(SplitTnArgs p) {
   float cs[4] = {0.f, 0.f, 0.f, 0.f};
   tn_piece_load(p.A, p.lda, p.K, m0, kt0 * BK, ra);
   tn_piece_load(p.B, p.ldb, p.K, n0, kt0 * BK, rb);
-  tn_piece_store<BM, MODE, RAGGED>(As, ra, p.K - kt0 * BK, SA);
-  tn_piece_store<BN, MODE, RAGGED>(Bs, rb, p.K - kt0 * BK, SB);
+  tn_piece_store<BM, RAGGED>(As, ra, p.K - kt0 * BK, SA);
+  tn_piece_store<BN, RAGGED>(Bs, rb, p.K - kt0 * BK, SB);
   tn_colsum_acc<RAGGED>(rb, p.K - kt0 * BK, csw, cs);
   {
     const int k1 = (kt0 + min(1, nkt - 1)) * BK;
@@ -903,50 +734,21 @@ __global__ __launch_bounds__(256, 2) void gemm_split_tn_kernel(SplitTnArgs p) {
   }
   __syncthreads();
 
-  if (SPLIT_TN_DBUF) {
-    for (int it = 0; it < nkt; ++it) {
-      frag8 af[TM][NPL], bf[TN][NPL];
-      const unsigned char* Ac = As + (it & 1) * OP_BYTES;
-      const unsigned char* Bc = Bs + (it & 1) * OP_BYTES;
-      unsigned char* An = As + ((it + 1) & 1) * OP_BYTES;
-      unsigned char* Bn = Bs + ((it + 1) & 1) * OP_BYTES;
-      read_frags<BM, BN, MODE, true>(Ac, Bc, wm, wn, li, kh, 0, af, bf);
-      const int kcur = (kt0 + min(it + 1, nkt - 1)) * BK, knext = (kt0 + min(it + 2, nkt - 1)) * BK;
-      tn_piece_store<BM, MODE, RAGGED>(An, ra, p.K - kcur, SA);
-      tn_piece_load(p.A, p.lda, p.K, m0, knext, ra);
-      tn_piece_store<BN, MODE, RAGGED>(Bn, rb, p.K - kcur, SB);
-      tn_colsum_acc<RAGGED>(rb, p.K - kcur, (it + 1 < nkt) ? csw : 0.f, cs);
-      tn_piece_load(p.B, p.ldb, p.K, n0, knext, rb);
-      mma_frags<TM, TN>(af, bf, acc);
-      read_frags<BM, BN, MODE, true>(Ac, Bc, wm, wn, li, kh, 1, af, bf);
-      __syncthreads();                                 // tile it + 1 is visible; everybody has read tile it
-      mma_frags<TM, TN>(af, bf, acc);
-      if (SPLIT_TN_FLUSH > 0 && (it + 1) % SPLIT_TN_FLUSH == 0) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.f; }
-      }
-    }
-    __syncthreads();                                   // the colsum reduction below reuses the operand images
-  } else
   for (int it = 0; it < nkt; ++it) {
-    frag8 af[TM][NPL], bf[TN][NPL];
-    read_frags<BM, BN, MODE, true>(As, Bs, wm, wn, li, kh, 0, af, bf);
+    f16x8 af[TM][NPL], bf[TN][NPL];
+    read_frags<BM, BN, true>(As, Bs, wm, wn, li, kh, 0, af, bf);
     mma_frags<TM, TN>(af, bf, acc);
-    read_frags<BM, BN, MODE, true>(As, Bs, wm, wn, li, kh, 1, af, bf);
+    read_frags<BM, BN, true>(As, Bs, wm, wn, li, kh, 1, af, bf);
     __syncthreads();                                   // every wave has read tile `it`
     // unconditional like the NT kernel: one basic block, the compiler interleaves split VALU, loads and MFMAs
     const int kcur = (kt0 + min(it + 1, nkt - 1)) * BK, knext = (kt0 + min(it + 2, nkt - 1)) * BK;
-    tn_piece_store<BM, MODE, RAGGED>(As, ra, p.K - kcur, SA);
+    tn_piece_store<BM, RAGGED>(As, ra, p.K - kcur, SA);
     tn_piece_load(p.A, p.lda, p.K, m0, knext, ra);
-    tn_piece_store<BN, MODE, RAGGED>(Bs, rb, p.K - kcur, SB);
+    tn_piece_store<BN, RAGGED>(Bs, rb, p.K - kcur, SB);
     tn_colsum_acc<RAGGED>(rb, p.K - kcur, (it + 1 < nkt) ? csw : 0.f, cs);      // the last pass re-stages a tile already counted
     tn_piece_load(p.B, p.ldb, p.K, n0, knext, rb);
     mma_frags<TM, TN>(af, bf, acc);
-    if (SPLIT_TN_FLUSH > 0 && (it + 1) % SPLIT_TN_FLUSH == 0) {
+    if ((it + 1) % TN_FLUSH == 0) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -956,14 +758,12 @@ __global__ __launch_bounds__(256, 2) void gemm_split_tn_kernel(SplitTnArgs p) {
     }
     __syncthreads();                                   // tile `it + 1` is visible
   }
-  if (SPLIT_TN_FLUSH > 0) {
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+  for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j)
+    for (int j = 0; j < TN; ++j)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] += tot[i][j][r];
-  }
+      for (int r = 0; r < 16; ++r) acc[i][j][r] += tot[i][j][r];
 
   if (csw != 0.f) {      // block-uniform; the K loop ended with a barrier, so the operand LDS is free
     float* red = reinterpret_cast<float*>(smem);
@@ -988,39 +788,14 @@ __global__ __launch_bounds__(256, 2) void gemm_split_tn_kernel(SplitTnArgs p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm * (BM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        if (row < p.M) atomicAdd(p.C + (size_t)row * p.ldc + col, MODE == MODE_F16X2 ? (acc[i][j][r] * INV_A) * INV_B : acc[i][j][r]);
+        if (row < p.M) atomicAdd(p.C + (size_t)row * p.ldc + col, (acc[i][j][r] * INV_A) * INV_B);
       }
     }
 }
 
-// weights -> bf16x3 planes: dst[t][r][c] = term_t(src[r][c]) (transpose = 0) or dst[t][c][r] (transpose = 1);
-// 32x32 tiles through LDS so both sides stay coalesced.  Padding columns of dst are left as the caller zeroed them.
-__global__ __launch_bounds__(256) void split_planes_kernel(int rows, int cols, const float* __restrict__ src, int ld_src,
-                                                           int transpose, unsigned short* __restrict__ dst, int ld_dst,
-                                                           long plane, int row_perm) {
-  __shared__ float t[32][33];
-  const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int y = ty; y < 32; y += 8)
-    if (r0 + y < rows && c0 + tx < cols) t[y][tx] = src[(size_t)(r0 + y) * ld_src + c0 + tx];
-  __syncthreads();
-  for (int y = ty; y < 32; y += 8) {
-    int orow = transpose ? c0 + y : r0 + y;
-    const int ocol = transpose ? r0 + tx : c0 + tx;
-    if (row_perm == 1) orow = ((orow & 255) >> 4) * 64 + (orow >> 8) * 16 + (orow & 15);   // LSTM gate interleave
-    const bool ok = transpose ? (c0 + y < cols && r0 + tx < rows) : (r0 + y < rows && c0 + tx < cols);
-    if (!ok) continue;
-    float x = transpose ? t[tx][y] : t[y][tx];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const __bf16 h = (__bf16)x;
-      dst[k * plane + (size_t)orow * ld_dst + ocol] = __builtin_bit_cast(unsigned short, h);
-      x -= (float)h;
-    }
-  }
-}
-
-// weights -> fp16x2 planes (hi, lo of src * 2^k, k from the weight's absmax slot): same tiling / layouts as above
+// weights -> fp16x2 planes (hi, lo of src * 2^k, k from the weight's absmax slot): dst[t][r][c] (transpose = 0) or
+// dst[t][c][r] (transpose = 1); 32x32 tiles through LDS so both sides stay coalesced.  Padding columns of dst are left as
+// the caller zeroed them.
 __global__ __launch_bounds__(256) void split_planes_f16x2_kernel(int rows, int cols, const float* __restrict__ src, int ld_src,
                                                                  int transpose, unsigned short* __restrict__ dst, int ld_dst,
                                                                  long plane, int row_perm, const float* __restrict__ w_absmax) {
@@ -1200,7 +975,7 @@ static int split_nt_launch(int M, int N, int K, const float* A, int lda, const f
                            long plane_stride, const float* w_absmax, float* C, int ldc, float* c_absmax, const float* bias,
                            const void* mask, int ldm, int flags, int splitk, long slab_stride, int* splitk_eff, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || !A || !W3 || !C) return UNREAL_EINVAL;
-  if (SPLIT_NT_MODE == MODE_F16X2 && (!a_absmax || !w_absmax)) return UNREAL_EINVAL;
+  if (!a_absmax || !w_absmax) return UNREAL_EINVAL;
   const int kpad = (K + BK - 1) / BK * BK;
   if (lda < K || ldw < kpad || (ldw & 7) || (plane_stride & 7) || plane_stride < (long)N * ldw || ldc < N ||
       (((uintptr_t)W3) & 15))
@@ -1233,58 +1008,15 @@ static int split_nt_launch(int M, int N, int K, const float* A, int lda, const f
     if (splitk_eff) *splitk_eff = a.splitk;
   }
   const long blocks128 = (long)((M + 127) / 128) * ((N + 127) / 128) * a.splitk;
-  // Experiment knobs of round 4 (tools/exp/gemm_ab.py, profiles/r04_ab_summary.md; all default 0, none of their kernels is
-  // instantiated in the product build): SPLIT_NT_N256 = 64 x 256 tiles for the N = 256 products (0.89x), SPLIT_NT_K256 =
-  // 64 x 128 tiles at four workgroups per CU for the short-K products (0.89x), SPLIT_NT_NORAG = the 128 x 128 kernel without
-  // its "k < K" selects when K % 32 == 0 (0.87-0.95x: fewer instructions, worse schedule); SPLIT_FORCE_RAGGED = the masked
-  // instantiations everywhere (A/B of the wgrad kernel's non-ragged form, which is kept: +1 %).
-#ifndef SPLIT_NT_K256
-#define SPLIT_NT_K256 0
-#endif
-#ifndef SPLIT_NT_N256
-#define SPLIT_NT_N256 0
-#endif
-#ifndef SPLIT_FORCE_RAGGED
-#define SPLIT_FORCE_RAGGED 0
-#endif
-#ifndef SPLIT_NT_NORAG
-#define SPLIT_NT_NORAG 0
-#endif
-#ifndef SPLIT_NT_DEEP128      // A tiles of the 128 x 128 kernel two K tiles ahead (round 3: 0.97-1.02x)
-#define SPLIT_NT_DEEP128 0
-#endif
-  bool launched = false;
-#if SPLIT_NT_N256
-  if (!launched && blocks128 >= 384 && N > 128 && N <= 256 && a.vecA) {
-    a.nbx = 1; a.nby = (M + 63) / 64;
-    const int grid = a.splitk * a.nbx * ((a.nby + 7) / 8 * 8);
-    hipLaunchKernelGGL((gemm_split_nt_kernel<64, 256, true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    launched = true;
-  }
-#endif
-#if SPLIT_NT_K256
-  if (!launched && blocks128 >= 384 && a.ktiles_per_split <= 8 && a.vecA) {
-    a.nbx = (N + 127) / 128; a.nby = (M + 63) / 64;
-    const int grid = a.splitk * a.nbx * ((a.nby + 7) / 8 * 8);
-    hipLaunchKernelGGL((gemm_split_nt_kernel<64, 128, true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    launched = true;
-  }
-#endif
-  if (launched) {
-  } else if (blocks128 >= 384) {
+  if (blocks128 >= 384) {
     a.nbx = (N + 127) / 128; a.nby = (M + 127) / 128;
     const int grid = a.splitk * a.nbx * ((a.nby + 7) / 8 * 8);
-#if SPLIT_NT_NORAG
-    if (!SPLIT_FORCE_RAGGED && a.vecA && K % BK == 0)
-      hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, true, SPLIT_NT_DEEP128 != 0, 0, 1, false, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    else
-#endif
     if (a.vecA) {
       UNREAL_LAUNCHED("split_nt 128x128 vec");
-      hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, true, SPLIT_NT_DEEP128 != 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+      hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
     } else {
       UNREAL_LAUNCHED("split_nt 128x128 novec");
-      hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, false, SPLIT_NT_DEEP128 != 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+      hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
     }
   } else {
     a.nbx = (N + 63) / 64; a.nby = (M + 63) / 64;
@@ -1292,7 +1024,7 @@ static int split_nt_launch(int M, int N, int K, const float* A, int lda, const f
     // few tiles (the N = 256 products of a 4096-row step): KW wave groups share each tile's K range
     const long tiles = (long)a.nbx * a.nby * a.splitk;
     const int kw = (tiles <= 256 && a.ktiles_per_split >= 8) ? 4 : (tiles <= 512 && a.ktiles_per_split >= 4) ? 2 : 1;
-#define LAUNCH64(VEC_, KW_) hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, VEC_, true, 0, KW_>), dim3(grid), \
+#define LAUNCH64(VEC_, KW_) hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, VEC_, 0, KW_>), dim3(grid), \
                                                dim3(256 * KW_), 0, (hipStream_t)stream, a)
     if (a.vecA) {
       if (kw == 4) { UNREAL_LAUNCHED("split_nt 64x64 vec kw4"); LAUNCH64(true, 4); }
@@ -1350,7 +1082,7 @@ int unreal_lstm_step_fwd(int rows, const float* x, int ldx, int Kx, const float*
                          const uint16_t* W3, int ldw, long plane_stride, const float* w_absmax, float* gates, const float* bias,
                          const float* c_prev, float* c_out, float* h_out, int ld_h, void* stream) {
   if (rows <= 0 || !h_prev || !W3 || !gates || !bias || !c_prev || !c_out || !h_out) return UNREAL_EINVAL;
-  if (SPLIT_NT_MODE == MODE_F16X2 && (!w_absmax || (x && !x_absmax))) return UNREAL_EINVAL;
+  if (!w_absmax || (x && !x_absmax)) return UNREAL_EINVAL;
   const int kxpad = x ? (Kx + BK - 1) / BK * BK : 0;
   if (x && (Kx <= 0 || ldx < Kx)) return UNREAL_EINVAL;
   if (ld_hprev < 256 || ld_h < 256 || ldw < kxpad + 256 || (ldw & 7) || (plane_stride & 7) ||
@@ -1374,35 +1106,28 @@ int unreal_lstm_step_fwd(int rows, const float* x, int ldx, int Kx, const float*
     a.vecA = vec_h;
     if (a.vecA) {
       UNREAL_LAUNCHED("lstm_step hoisted vec");
-      hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+      hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
     } else {
       UNREAL_LAUNCHED("lstm_step hoisted novec");
-      hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, false, true, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+      hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, false, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
     }
   } else {                               // [x | h_prev] @ the whole kernel in one product
     a.A = x; a.lda = ldx; a.K1 = Kx; a.K1pad = kxpad; a.A2 = h_prev; a.lda2 = ld_hprev;
     a.flags = 0;
     a.vecA = vec_h && ((ldx & 3) == 0) && ldx >= 4 && ((((uintptr_t)x) & 15) == 0);
-#ifdef LSTM_FORCE_64
-    if (false) {
-#else
     if (a.vecA && rows >= 2048) {
-#endif
       // a full step (4096 rows): 128 x 128 tiles halve the operand bytes per flop (the 64 x 64 step moves 350 MB from
       // L2 for 13.7 GMAC); two wave groups share each tile's K range so that the 256 tiles still put 8 waves on a CU
       a.nbx = 8; a.nby = (rows + 127) / 128;
       const int grid128 = a.nbx * ((a.nby + 7) / 8 * 8);
-#ifndef LSTM_BIG_KW
-#define LSTM_BIG_KW 1
-#endif
       // more than one tile per CU (the 8192-row steps of the batched replay branches): plain 128 x 128 workgroups, two
       // resident per CU, so one's gate epilogue runs beside the other's K loop
-      if (LSTM_BIG_KW == 1 && (long)a.nbx * a.nby > 256) {
+      if ((long)a.nbx * a.nby > 256) {
         UNREAL_LAUNCHED("lstm_step 128x128 kw1");
-        hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, true, false, 1, 1, true>), dim3(grid128), dim3(256), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, true, 1, 1, true>), dim3(grid128), dim3(256), 0, (hipStream_t)stream, a);
       } else {
         UNREAL_LAUNCHED("lstm_step 128x128 kw2");
-        hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, true, false, 1, 2, true>), dim3(grid128), dim3(512), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, true, 1, 2, true>), dim3(grid128), dim3(512), 0, (hipStream_t)stream, a);
       }
     } else if (a.vecA) {
       // small steps (grouped updates: 512 / 64 rows per launch): 16 x rows/64 tiles of 64 x 64 leave most CUs without a
@@ -1411,14 +1136,14 @@ int unreal_lstm_step_fwd(int rows, const float* x, int ldx, int Kx, const float*
       const long tiles = (long)a.nbx * a.nby;
       if (tiles <= 256) {
         UNREAL_LAUNCHED("lstm_step 64x64 vec kw4");
-        hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 1, 4, true>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, 1, 4, true>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, a);
       } else {
         UNREAL_LAUNCHED("lstm_step 64x64 vec kw2");
-        hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 1, 2, true>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, 1, 2, true>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
       }
     } else {
       UNREAL_LAUNCHED("lstm_step 64x64 novec");
-      hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, false, true, 1, 1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+      hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, false, 1, 1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
     }
   }
   return unreal_launch_status();
@@ -1429,7 +1154,7 @@ int unreal_lstm_bptt_step(int rows, const float* d_gates, const float* a_absmax,
                           const float* c_prev, const float* c_new, float* dpre, float* dpre_absmax0, float* dpre_absmax1,
                           void* stream) {
   if (rows <= 0 || !d_gates || !Wh3 || !dh_above || !dc_io || !gates_act || !c_prev || !c_new || !dpre) return UNREAL_EINVAL;
-  if (SPLIT_NT_MODE == MODE_F16X2 && (!a_absmax || !w_absmax)) return UNREAL_EINVAL;
+  if (!a_absmax || !w_absmax) return UNREAL_EINVAL;
   if (ldw < 1024 || (ldw & 7) || (plane_stride & 7) || plane_stride < 256L * ldw || (((uintptr_t)Wh3) & 15) ||
       (((uintptr_t)d_gates) & 15))
     return UNREAL_EINVAL;
@@ -1445,20 +1170,16 @@ int unreal_lstm_bptt_step(int rows, const float* d_gates, const float* a_absmax,
   a.nbx = 4; a.nby = (rows + 63) / 64;
   const int grid = a.nbx * ((a.nby + 7) / 8 * 8);
   const long tiles = (long)a.nbx * a.nby;
-#ifdef BPTT_FORCE_KW
-  const int kw = BPTT_FORCE_KW;
-#else
   const int kw = tiles <= 256 ? 4 : tiles <= 512 ? 2 : 1;
-#endif
   if (kw == 4) {
     UNREAL_LAUNCHED("bptt kw4");
-    hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 2, 4>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, 2, 4>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, a);
   } else if (kw == 2) {
     UNREAL_LAUNCHED("bptt kw2");
-    hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 2, 2>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, 2, 2>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
   } else {
     UNREAL_LAUNCHED("bptt kw1");
-    hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, true, 2, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((gemm_split_nt_kernel<64, 64, true, 2, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   }
   return unreal_launch_status();
 }
@@ -1470,7 +1191,7 @@ int unreal_gemm_f32_split_tn(int M, int N, int K, const float* A, int lda, const
   SplitTnArgs a;
   a.M = M; a.N = N; a.K = K; a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc; a.colsum = colsum;
   a.a_absmax = a_absmax; a.b_absmax = b_absmax;
-  if (SPLIT_TN_MODE == MODE_F16X2 && (!a.a_absmax || !a.b_absmax)) return UNREAL_EINVAL;
+  if (!a.a_absmax || !a.b_absmax) return UNREAL_EINVAL;
   a.ntx = (N + 127) / 128; a.nty = (M + 127) / 128;
   const int nk = (K + BK - 1) / BK;
   if (splitk < 1) splitk = 1;
@@ -1479,7 +1200,7 @@ int unreal_gemm_f32_split_tn(int M, int N, int K, const float* A, int lda, const
   a.splitk = (nk + a.ktiles_per_split - 1) / a.ktiles_per_split;
   const long grid = (long)a.ntx * a.nty * ((a.splitk + 7) / 8 * 8);
   if (grid > 0x7fffffffL) return UNREAL_EINVAL;
-  if (!SPLIT_FORCE_RAGGED && K % BK == 0) {
+  if (K % BK == 0) {
     UNREAL_LAUNCHED("split_tn even");
     hipLaunchKernelGGL(gemm_split_tn_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
   } else {
@@ -1488,29 +1209,5 @@ int unreal_gemm_f32_split_tn(int M, int N, int K, const float* A, int lda, const
   }
   return unreal_launch_status();
 }
-
-int unreal_split_bf16x3(int rows, int cols, const float* src, int ld_src, int transpose, int row_perm, uint16_t* dst,
-                        int ld_dst, long plane_stride, void* stream) {
-  if (rows <= 0 || cols <= 0 || !src || !dst || ld_src < cols) return UNREAL_EINVAL;
-  const int orows = transpose ? cols : rows, ocols = transpose ? rows : cols;
-  if (ld_dst < ocols || plane_stride < (long)orows * ld_dst) return UNREAL_EINVAL;
-  if (row_perm != 0 && (row_perm != 1 || orows != 1024)) return UNREAL_EINVAL;
-  dim3 grid((cols + 31) / 32, (rows + 31) / 32);
-  hipLaunchKernelGGL(split_planes_kernel, grid, dim3(256), 0, (hipStream_t)stream, rows, cols, src, ld_src, transpose,
-                     dst, ld_dst, plane_stride, row_perm);
-  return unreal_launch_status();
-}
-
-#ifdef SPLIT_STAMPS
-int exp_split_read_stamps(unsigned long long* host8, int reset) {
-  hipDeviceSynchronize();
-  hipMemcpyFromSymbol(host8, HIP_SYMBOL(g_split_stamps), sizeof(unsigned long long) * 8);
-  if (reset) {
-    unsigned long long z[8] = {0};
-    hipMemcpyToSymbol(HIP_SYMBOL(g_split_stamps), z, sizeof(z));
-  }
-  return 0;
-}
-#endif
 
 }  // extern "C"

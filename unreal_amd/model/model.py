@@ -250,9 +250,9 @@ class UnrealModel(object):
                              % (self.frame_scale, scale))
         self.frame_scale = scale
 
-    # -- bf16x3 weight shadows (W operand of ops.gemm_split_nt) ---------------------------------------
+    # -- fp16x2 weight shadows (W operand of ops.gemm_split_nt) ---------------------------------------
     def refresh_shadows(self, only_if_stale=False):
-        """Re-split the dense-layer weights into the bf16x3 planes the split-operand GEMM multiplies by (forward:
+        """Re-split the dense-layer weights into the fp16x2 planes the split-operand GEMM multiplies by (forward:
         transposed, dgrad: natural layout).  Cheap (a few MB); called at the start of every Trainer.process /
         Evaluate.process / batch-1 runner, i.e. after any optimiser step, load or restore.  `only_if_stale`: skip
         when no load / sync / optimiser step was announced (mark_params_changed) since the last split -- the replay

@@ -586,14 +586,6 @@ def split_f16x2(rows, cols, src, ld_src, transpose, dst, ld_dst, plane, wmax, ro
           plane, ptr(wmax))
 
 
-def split_bf16x3(rows, cols, src, ld_src, transpose, dst, ld_dst, plane, row_perm=0):
-    _chk(src, "f32", (rows - 1) * ld_src + cols, "src")
-    orows, ocols = (cols, rows) if transpose else (rows, cols)
-    _chk(dst, "i16", 2 * plane + (orows - 1) * ld_dst + ocols, "dst")
-    _call("unreal_split_bf16x3", rows, cols, ptr(src), ld_src, int(bool(transpose)), int(row_perm), ptr(dst), ld_dst,
-          plane)
-
-
 class LstmKernelShadow:
     """Gate-interleaved fp16x2 shadow of the WHOLE BasicLSTMCell kernel [K_x + 256, 1024] as unreal_lstm_step_fwd(x=...)
     multiplies it: planes[t][1024][pad32(K_x) + 256] -- input rows, zero padding to a K tile, recurrent rows; one scale
