@@ -65,6 +65,41 @@ int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, cons
                                     int idx_base_actor, void* stream);
 int unreal_maze_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
                       const int* count, uint8_t* frames, void* stream);
+/* configured mazes (environment/maze_environment.py MazeConfig): the four maze entries above with a configuration block
+ * `cfg` (int32 words: N, layouts, flags, max_episode_steps, seed; per layout the wall bits, S / G cells and free-cell list)
+ * and the per-actor state of a configured maze: goal[2B] (x, y), layout[B], ep_steps[B], episode[B] (-1 before the first
+ * reset).  N in {7, 12, 14, 21} must be the block's grid size (word 0): the block lives in device memory, so the entry
+ * cannot read it, and a kernel whose N differs from the block's writes nothing at all (no frame, no state) rather than
+ * index a frame with the wrong cell size -- the call still returns 0.  Reset draws are Philox4x32-10 with key = the block's seed and
+ * counter = (actor_base + b, episode, 0x4D415A45, 0).  cfg = NULL: the reference's map (N must be 7; the arrays are not
+ * used), exactly what the entries above do. */
+int unreal_maze_step_cfg(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
+                         float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                         int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc,
+                         float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
+                         int* score_valid, int reset_on_terminal, int track_score, int N, const int* cfg,
+                         int actor_base, int* goal, int* layout, int* ep_steps, int* episode, void* stream);
+int unreal_maze_rollout_step_cfg(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                 int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                 int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                 int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                 int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
+                                 float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A, int idx_base_actor, int N,
+                                 const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps, int* episode,
+                                 void* stream);
+int unreal_maze_policy_rollout_step_cfg(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                        const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                        int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
+                                        uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                        int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                        int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                        int* active, int* active_log_t, int* n_steps, int* terminal_end,
+                                        int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0,
+                                        int A, int idx_base_actor, int N, const int* cfg, int actor_base, int* goal,
+                                        int* layout, int* ep_steps, int* episode, void* stream);
+int unreal_maze_reset_cfg(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
+                          const int* count, uint8_t* frames, int N, const int* cfg, int actor_base, int* goal, int* layout,
+                          int* ep_steps, int* episode, void* stream);
 /* host-fed environments (environment/lab_environment.py:78-119 contract): `staged` holds one uint8
  * frame per actor (post-reset observation where terminals[b] != 0) */
 int unreal_hostfed_step(int B, int H1, const uint8_t* staged, const int* actions, const float* rewards,

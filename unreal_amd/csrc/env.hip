@@ -17,6 +17,39 @@
 
 namespace {
 
+// ---- Philox4x32-10 counter RNG: key = seed, counter = (index, stream) ------------------------
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+  uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
+  uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+  uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
+  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+}
+
+__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t index, uint64_t stream, uint32_t (&out)[4]) {
+  uint32_t c[4] = {(uint32_t)index, (uint32_t)(index >> 32), (uint32_t)stream, (uint32_t)(stream >> 32)};
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(c, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
+}
+
+// ---- maze configuration block (int32 words, built by the host: environment/environment.py register_maze_config) ------
+// header:  [0] N  [1] L layouts  [2] flags  [3] max_episode_steps (0: none)  [4..5] seed (lo, hi)  [6] record words  [7] 0
+// record l at kCfgHdr + l * rec:  [0..13] wall bits of cell y*N+x as 7 uint64 (lo, hi)  [14] S cell (-1: none)
+//   [15] G cell (-1: none)  [16] n_free  [17] index of G in the free list (-1: none)  [18 ..] free cells, ascending
+// The reference's map (maze_environment.py:18-25) is this same block, built at compile time (kDefaultMaze); a null
+// config means it.
+constexpr int kCfgHdr = 8, kRecHdr = 18;
+constexpr int kMazeRandomStart = 1, kMazeRandomGoal = 2, kMazeShowGoal = 4;
+// counter word 2 of a reset draw: far above any stream id PhiloxDraws hands out (2, 3, ...), so a configured maze's
+// reset draws take nothing from a run's action and replay streams
+constexpr uint32_t kMazeResetStream = 0x4D415A45u;
+
 constexpr const char* kMap =
     "--+---G"
     "--+-+++"
@@ -26,52 +59,74 @@ constexpr const char* kMap =
     "--+----"
     "-----++";
 
-constexpr uint64_t wall_mask() {
-  uint64_t m = 0;
-  for (int i = 0; i < 49; ++i)
-    if (kMap[i] == '+') m |= (1ull << i);
+struct DefaultMaze { int v[kCfgHdr + kRecHdr + 49]; };
+constexpr DefaultMaze make_default_maze() {
+  DefaultMaze m{};
+  m.v[0] = 7; m.v[1] = 1; m.v[6] = kRecHdr + 49;
+  int* r = m.v + kCfgHdr;
+  uint64_t walls = 0;
+  int nf = 0;
+  r[14] = r[15] = r[17] = -1;
+  for (int i = 0; i < 49; ++i) {
+    if (kMap[i] == '+') { walls |= 1ull << i; continue; }
+    if (kMap[i] == 'S') r[14] = i;
+    if (kMap[i] == 'G') { r[15] = i; r[17] = nf; }
+    r[kRecHdr + nf++] = i;
+  }
+  r[0] = (int)(uint32_t)walls; r[1] = (int)(uint32_t)(walls >> 32);
+  r[16] = nf;
   return m;
 }
-constexpr int find_cell(char c) {
-  for (int i = 0; i < 49; ++i)
-    if (kMap[i] == c) return i;
-  return -1;
-}
-constexpr uint64_t kWalls = wall_mask();
-constexpr int kStartX = find_cell('S') % 7, kStartY = find_cell('S') / 7;
-constexpr int kGoalX = find_cell('G') % 7, kGoalY = find_cell('G') / 7;
-static_assert(kStartX == 0 && kStartY == 2 && kGoalX == 6 && kGoalY == 0, "maze constants");
+// read at compile time: the null-config path loads nothing of the block
+constexpr DefaultMaze kDefaultMaze = make_default_maze();
+constexpr const int* kDefaultRec = kDefaultMaze.v + kCfgHdr;
+constexpr uint64_t kDefaultWalls = (uint64_t)(uint32_t)kDefaultRec[0] | ((uint64_t)(uint32_t)kDefaultRec[1] << 32);
+constexpr int kDefaultStart = kDefaultRec[14], kDefaultGoal = kDefaultRec[15];
+static_assert(kDefaultStart == 2 * 7 + 0 && kDefaultGoal == 6, "maze constants");
 
-__device__ __forceinline__ bool is_wall(int x, int y) { return (kWalls >> (y * 7 + x)) & 1ull; }
+// The wall bits of the layout a workgroup renders: at N = 7 (49 bits) in a uniform register; above, up to 441 bits in
+// LDS (a dynamically indexed register array is placed in scratch).  load() is called by every thread of the workgroup.
+template <int N>
+struct Walls {
+  static constexpr int NW = (N * N + 63) / 64;
+  uint64_t w0;
+  uint64_t* lds;         // NW > 1: the workgroup's copy, NW words
+  __device__ __forceinline__ void load(const int* rec) {     // rec null: the reference map
+    if constexpr (NW == 1) {
+      w0 = rec ? (uint64_t)(uint32_t)rec[0] | ((uint64_t)(uint32_t)rec[1] << 32) : kDefaultWalls;
+    } else {
+      if (threadIdx.x < NW)
+        lds[threadIdx.x] = (uint64_t)(uint32_t)rec[2 * threadIdx.x] | ((uint64_t)(uint32_t)rec[2 * threadIdx.x + 1] << 32);
+      __syncthreads();
+    }
+  }
+  __device__ __forceinline__ uint32_t bit(int cell) const {
+    if constexpr (NW == 1) return (uint32_t)(w0 >> cell) & 1u;
+    else return (uint32_t)(lds[cell >> 6] >> (cell & 63)) & 1u;
+  }
+};
 
-// one byte of the rendered frame: ch0 = wall block, ch1 = agent block, ch2 = 0
-__device__ __forceinline__ uint32_t render_byte(int idx, int ax, int ay) {
-  int row = idx / FRAME_ROW_BYTES;
-  int c3 = idx - row * FRAME_ROW_BYTES;
-  int col = c3 / 3;
-  int ch = c3 - col * 3;
-  int cy = row / 12, cx = col / 12;
-  uint32_t wall = (uint32_t)((kWalls >> (cy * 7 + cx)) & 1ull);
-  uint32_t agent = (cx == ax && cy == ay) ? 1u : 0u;
-  return ch == 0 ? wall : (ch == 1 ? agent : 0u);
-}
-
-// The frame is the constant wall image plus the 12x12 agent block (channel 1).  A workgroup builds the wall image
-// ONCE in LDS (the per-byte index arithmetic below is ~250 VALU per 16 bytes: rendering every frame from scratch made
-// the step kernel VALU-bound at 1.6 TB/s) and streams it out for each of its actors; the agent block -- 12 rows of 36
-// contiguous bytes (0,1,0)x12, never on a wall cell -- is patched in afterwards as 9 dwords per row.
+// The frame is the layout's wall image (ch 0) plus the c x c agent block (ch 1) and, with show_goal, the goal block (ch 2),
+// c = 84 / N.  A workgroup builds the wall image ONCE per layout in LDS (the per-byte index arithmetic below is ~250 VALU
+// per 16 bytes: rendering every frame from scratch made the step kernel VALU-bound at 1.6 TB/s) and streams it out for
+// each of its actors; the agent and goal blocks are patched in afterwards.
 constexpr int kActorsPerGroup = 8;
 constexpr int kStepActorsBig = 8;      // actors per workgroup of the step kernel at > 1024 actors
 constexpr int kStepActorsTiny = 1;     // actors per workgroup at <= 64 actors (a small update's rollout step: one actor per workgroup)
 
-__device__ __forceinline__ void build_wall_image(uint4* img) {
+template <int N>
+__device__ __forceinline__ void build_wall_image(uint4* img, const Walls<N>& walls) {
+  constexpr int C = FRAME_W / N;
   for (int c = threadIdx.x; c < FRAME_BYTES / 16; c += blockDim.x) {
     uint32_t w[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      int base = c * 16 + k * 4;
-      w[k] = render_byte(base, -1, -1) | (render_byte(base + 1, -1, -1) << 8) | (render_byte(base + 2, -1, -1) << 16) |
-             (render_byte(base + 3, -1, -1) << 24);
+      // a dword never spans two frame rows (252 = 4 * 63); its channel-0 bytes are e0 and, when e0 = 0, byte 3
+      const int q = c * 4 + k, row = q / (FRAME_ROW_BYTES / 4), cb = 4 * q - row * FRAME_ROW_BYTES;
+      const int wrow = (row / C) * N, m = cb % 3, e0 = m == 0 ? 0 : 3 - m;
+      uint32_t v = walls.bit(wrow + (cb + e0) / 3 / C) << (8 * e0);
+      if (e0 == 0) v |= walls.bit(wrow + (cb + 3) / 3 / C) << 24;
+      w[k] = v;
     }
     img[c] = make_uint4(w[0], w[1], w[2], w[3]);
   }
@@ -82,23 +137,74 @@ __device__ __forceinline__ void render_walls(uint8_t* dst, const uint4* img) {
   uint4* d4 = reinterpret_cast<uint4*>(dst);
   for (int c = threadIdx.x; c < FRAME_BYTES / 16; c += blockDim.x) d4[c] = img[c];
 }
-__device__ __forceinline__ void render_agent(uint8_t* dst, int ax, int ay) {
-  if (threadIdx.x < 12 * 9) {
-    const int r = threadIdx.x / 9, w = threadIdx.x % 9;            // dword w of the 36-byte run: bytes 4w..4w+3
-    // (0,1,0) repeated; byte 4w is channel w mod 3.  Selects, not a table: the compiler put `pat[3]` into constant memory, and
-    // the global load it then needed in here came with s_waitcnt vmcnt(0) -- which also waits for the wave's wall stores
-    // of this frame: a memory round trip per actor, and the next actor's barrier made the whole workgroup wait for it
-    const int ph = w % 3;
-    const uint32_t pat = ph == 0 ? 0x00000100u : (ph == 1 ? 0x01000001u : 0x00010000u);
-    reinterpret_cast<uint32_t*>(dst + (12 * ay + r) * FRAME_ROW_BYTES + 36 * ax)[w] = pat;
+
+// The dwords of the agent block's rows (and of the goal block's, when shown): each is the wall image's dword with the
+// agent's ch-1 bytes and the goal's ch-2 bytes set.  A block row is 3c bytes at byte 3c*cx of its frame row; at c = 7 and
+// c = 6 it does not start on a dword, so its first and last dwords hold bytes of the neighbouring cells, which come out
+// of the same formula.  A dword both blocks share is written by two threads with the same value.
+template <int N>
+__device__ __forceinline__ void render_blocks(uint8_t* dst, const uint4* img, int ax, int ay, int gx, int gy, bool show_goal) {
+  constexpr int C = FRAME_W / N, RUN = 3 * C;
+  constexpr int DW = RUN % 4 == 0 ? RUN / 4 : RUN / 4 + 2;      // dwords that can cover a run
+  const uint32_t* img32 = reinterpret_cast<const uint32_t*>(img);
+  const int n = (show_goal ? 2 : 1) * C * DW;
+  for (int t = threadIdx.x; t < n; t += blockDim.x) {
+    const int blk = t / (C * DW), r = (t / DW) % C, w = t % DW;
+    const int cx = blk ? gx : ax, cy = blk ? gy : ay;
+    const int d = (RUN * cx) / 4 + w;                              // dword within the frame row (252 B = 63 dwords)
+    if (4 * d > RUN * cx + RUN - 1) continue;
+    const int row = C * cy + r;                                   // (a row of cell row cy: the other block's too when they share it)
+    uint32_t v;
+    if constexpr (RUN % 4 == 0) {
+      // c = 12, 4: the dword lies inside its cell, which is no wall; byte 4w of the run is channel w mod 3 (selects, not a
+      // table: a table went to constant memory, and its load waited for the wave's wall stores of this frame)
+      const int ph = w % 3;
+      const uint32_t ch1 = ph == 0 ? 0x00000100u : (ph == 1 ? 0x01000001u : 0x00010000u);
+      const uint32_t ch2 = ph == 0 ? 0x00010000u : (ph == 1 ? 0x00000100u : 0x01000001u);
+      v = ((cx == ax && cy == ay) ? ch1 : 0u) | ((show_goal && cx == gx && cy == gy) ? ch2 : 0u);
+    } else {
+      v = img32[row * (FRAME_ROW_BYTES / 4) + d];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int pos = 4 * d + e, col = pos / 3, ch = pos - 3 * col, ccol = col / C;
+        const bool on = (ch == 1 && ccol == ax && cy == ay) || (show_goal && ch == 2 && ccol == gx && cy == gy);
+        if (on) v |= 1u << (8 * e);
+      }
+    }
+    reinterpret_cast<uint32_t*>(dst + row * FRAME_ROW_BYTES)[d] = v;
   }
 }
 
-// pixels of the 12x12 agent block at cell (cx,cy) inside pixel-change cell (i,j):
+// pixels of the c x c agent block at cell (cx,cy) inside pixel-change cell (i,j):
 // rows 4i+2..4i+5, cols 4j+2..4j+5 of the full frame (the [2:-2] crop, then 4x4 blocks)
+template <int N>
 __device__ __forceinline__ int overlap1(int cell, int k) {
-  int lo = max(12 * cell, 4 * k + 2), hi = min(12 * cell + 11, 4 * k + 5);
+  constexpr int C = FRAME_W / N;
+  int lo = max(C * cell, 4 * k + 2), hi = min(C * cell + C - 1, 4 * k + 5);
   return max(0, hi - lo + 1);
+}
+
+// Goal and start cells of global actor g's episode `ep` (a pure function of seed, g, ep): the goal from G or uniform over
+// the free cells, drawn first; the start from S or uniform over the free cells other than the goal.
+__device__ __forceinline__ void maze_reset_cells(const int* cfg, const int* rec, int g, int ep, int& goal, int& start) {
+  const int flags = cfg[2];
+  uint32_t u[4] = {0, 0, 0, 0};
+  if (flags & (kMazeRandomStart | kMazeRandomGoal)) {
+    const uint64_t seed = (uint64_t)(uint32_t)cfg[4] | ((uint64_t)(uint32_t)cfg[5] << 32);
+    philox4x32_10(seed, (uint64_t)(uint32_t)g | ((uint64_t)(uint32_t)ep << 32), kMazeResetStream, u);
+  }
+  const int nf = rec[16];
+  int gi = rec[17];
+  goal = rec[15];
+  if (flags & kMazeRandomGoal) {
+    gi = (int)(u[0] % (uint32_t)nf);
+    goal = rec[kRecHdr + gi];
+  }
+  start = rec[14];
+  if (flags & kMazeRandomStart) {
+    const int j = (int)(u[1] % (uint32_t)max(nf - 1, 1));        // (nf >= 2: MazeConfig checks it)
+    start = rec[kRecHdr + (j < gi ? j : j + 1)];
+  }
 }
 
 struct StepArgs {
@@ -138,13 +244,29 @@ struct StepArgs {
   const float* Wp; const float* bp; const float* Wv; const float* bv;
   const double* pol_u;
   float* pi_out; float* v_out; int* act_out;
+  // configured maze (the *_cfg entries; cfg null: the reference's map, and the four arrays below are null too)
+  const int* cfg;
+  int actor_base;        // global index of actor 0 of this launch (reset draws are keyed by it)
+  int* goal;             // [2B] goal cell (x, y) of the running episode
+  int* layout;           // [B] layout id
+  int* ep_steps;         // [B] steps taken in the running episode
+  int* episode;          // [B] episode index (-1 before the first reset)
 };
+
+__device__ __forceinline__ const int* maze_rec(const int* cfg, int lay) { return cfg + kCfgHdr + lay * cfg[6]; }
+__device__ __forceinline__ int maze_layout(const int* cfg, const int* layout, int b) {
+  return layout ? min(max(layout[b], 0), cfg[1] - 1) : 0;
+}
 
 // APG actors per workgroup: 8 when the batch fills the chip (the wall image is built once per workgroup: ~2.5 us of VALU),
 // 2 for small batches (grouped updates: 512 actors per launch), where 8 actors in a row per workgroup were 20 of the
 // launch's 23 us and most CUs had no workgroup at all, 1 at <= 64 actors (an 8-actor update: 8 workgroups instead of 4)
-template <int APG>
+template <int N, int APG>
 __global__ __launch_bounds__(256) void maze_step_kernel(StepArgs p) {
+  const int* cfg = p.cfg;                      // null: the reference map (kDefaultMaze)
+  // (uniform) the block's grid size must be the one this kernel was built for: with another N the cell arithmetic would
+  // address outside the frame, so nothing is written (documented with the *_cfg entries in unreal_hip.h)
+  if ((cfg ? cfg[0] : 7) != N) return;
   __shared__ uint4 wall_img[FRAME_BYTES / 16];
   // the workgroup's actors' scalar state, fetched by one thread per actor while the wall image is built: read inside the
   // per-actor loop, each actor would start with two dependent global round trips (state, then the previous slot's terminal
@@ -152,6 +274,8 @@ __global__ __launch_bounds__(256) void maze_step_kernel(StepArgs p) {
   __shared__ int s_flag[APG], s_x[APG], s_y[APG], s_a[APG],
       s_cnt[APG], s_la[APG], s_prev[APG], s_ns[APG];
   __shared__ float s_lr[APG], s_ep[APG];
+  // configured maze: layout, goal cell, episode steps, and the goal / start cells of the next episode (drawn here too)
+  __shared__ int s_lay[APG], s_goal[APG], s_st[APG], s_epi[APG], s_rgoal[APG], s_rstart[APG];
   if (p.pol_x) {       // (workgroup-uniform) policy of this workgroup's actors: wave w takes actors w, w + 4, ...
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int k = wave; k < APG; k += 4) {
@@ -176,11 +300,27 @@ __global__ __launch_bounds__(256) void maze_step_kernel(StepArgs p) {
       s_ns[k] = p.active_rw ? p.n_steps[b] : 0;      // (read here: a load inside the actor loop stalls thread 0's wave -- and,
                                                      // through the loop's barrier, the workgroup -- for a memory round trip per actor)
       s_prev[k] = cnt > 0 ? p.r_terminal[(size_t)b * p.H1 + (cnt - 1) % p.H1] : 0;
+      int lay = 0, goal = kDefaultGoal, st = 0, epi = 0, rg = kDefaultGoal, rs = kDefaultStart;
+      if (cfg) {
+        lay = maze_layout(cfg, p.layout, b);
+        goal = p.goal[2 * b + 1] * N + p.goal[2 * b];
+        st = p.ep_steps[b];
+        epi = p.episode[b];
+        maze_reset_cells(cfg, maze_rec(cfg, lay), p.actor_base + b, epi + 1, rg, rs);
+      }
+      s_lay[k] = lay; s_goal[k] = goal; s_st[k] = st; s_epi[k] = epi; s_rgoal[k] = rg; s_rstart[k] = rs;
     }
   }
-  build_wall_image(wall_img);
+  int built = cfg ? maze_layout(cfg, p.layout, blockIdx.x * APG) : 0;     // the first actor's layout: read by every thread
+  __shared__ uint64_t s_walls[Walls<N>::NW];
+  Walls<N> walls;
+  walls.lds = s_walls;
+  walls.load(cfg ? maze_rec(cfg, built) : nullptr);
+  build_wall_image<N>(wall_img, walls);
   __syncthreads();
   const int H1 = p.H1;
+  const int max_steps = cfg ? cfg[3] : 0;
+  const bool show_goal = cfg && (cfg[2] & kMazeShowGoal);
   for (int k = 0; k < APG; ++k) {
     const int b = blockIdx.x * APG + k;
     if (b >= p.B) break;
@@ -199,6 +339,13 @@ __global__ __launch_bounds__(256) void maze_step_kernel(StepArgs p) {
       }
       continue;
     }
+    if (s_lay[k] != built) {           // (uniform) a layout boundary inside the workgroup: rebuild the wall image
+      built = s_lay[k];
+      __syncthreads();                 // every thread is done reading the previous image
+      walls.load(maze_rec(cfg, built));       // (a layout other than the first: cfg is not null)
+      build_wall_image<N>(wall_img, walls);
+      __syncthreads();
+    }
     const int x = s_x[k], y = s_y[k];
     const int a = s_a[k];
     const int cnt = s_cnt[k];
@@ -207,18 +354,21 @@ __global__ __launch_bounds__(256) void maze_step_kernel(StepArgs p) {
     const int slot = cnt % H1;
     const int prev_term = s_prev[k];
     float ep = s_ep[k];
+    const int gc = s_goal[k], gx = gc % N, gy = gc / N;
 
-    // _move (maze_environment.py:76-91)
+    // _move (maze_environment.py:76-91), bound N - 1
     int dx = (a == 3) - (a == 2), dy = (a == 1) - (a == 0);
     int nx = x + dx, ny = y + dy;
-    bool clamped = nx < 0 || nx > 6 || ny < 0 || ny > 6;
-    nx = min(max(nx, 0), 6);
-    ny = min(max(ny, 0), 6);
-    bool hit_wall = is_wall(nx, ny);
+    bool clamped = nx < 0 || nx > N - 1 || ny < 0 || ny > N - 1;
+    nx = min(max(nx, 0), N - 1);
+    ny = min(max(ny, 0), N - 1);
+    bool hit_wall = walls.bit(ny * N + nx);
     if (hit_wall) { nx = x; ny = y; }
     const bool hit = clamped || hit_wall;
-    const bool terminal = (nx == kGoalX && ny == kGoalY);
-    const float reward = terminal ? 1.f : (hit ? -1.f : 0.f);
+    const bool at_goal = (nx == gx && ny == gy);
+    const int steps = s_st[k] + 1;
+    const bool terminal = at_goal || (max_steps > 0 && steps >= max_steps);   // goal, or the episode's time-out
+    const float reward = at_goal ? 1.f : (hit ? -1.f : 0.f);
 
     const size_t base = (size_t)b * H1 + slot;
     // pixel change between render(nx,ny) and render(x,y): only the two agent blocks differ (ch 1)
@@ -226,19 +376,20 @@ __global__ __launch_bounds__(256) void maze_step_kernel(StepArgs p) {
     for (int c = threadIdx.x; c < PC_CELLS; c += blockDim.x) {
       int i = c / 20, j = c - i * 20;
       int s = 0;
-      if (moved) s = overlap1(y, i) * overlap1(x, j) + overlap1(ny, i) * overlap1(nx, j);
+      if (moved) s = overlap1<N>(y, i) * overlap1<N>(x, j) + overlap1<N>(ny, i) * overlap1<N>(nx, j);
       p.r_pc[base * PC_CELLS + c] = (float)s / 48.0f;
     }
 
     const bool discard = terminal && cnt > 0 && prev_term;  // experience.py:64-67
     const int ncnt = discard ? cnt : cnt + 1;
     const bool reset = terminal && p.reset_on_terminal;
-    const int rx = reset ? kStartX : nx, ry = reset ? kStartY : ny;
+    const int rc = s_rstart[k], ngc = reset ? s_rgoal[k] : gc;
+    const int rx = reset ? rc % N : nx, ry = reset ? rc / N : ny;
     const int nslot = ncnt % H1;
     uint8_t* dst = p.frames + ((size_t)b * H1 + nslot) * FRAME_BYTES;
     render_walls(dst, wall_img);
-    __syncthreads();  // every thread has read the actor's state; wall stores precede the agent patch
-    render_agent(dst, rx, ry);
+    __syncthreads();  // every thread has read the actor's state; wall stores precede the block patch
+    render_blocks<N>(dst, wall_img, rx, ry, ngc % N, ngc / N, show_goal);
 
     if (threadIdx.x == 0) {
       p.r_reward[base] = reward;
@@ -251,6 +402,12 @@ __global__ __launch_bounds__(256) void maze_step_kernel(StepArgs p) {
       p.count[b] = ncnt;
       p.last_action[b] = reset ? 0 : a;
       p.last_reward[b] = reset ? 0.f : reward;
+      if (p.cfg) {
+        p.goal[2 * b] = ngc % N;
+        p.goal[2 * b + 1] = ngc / N;
+        p.ep_steps[b] = reset ? 0 : steps;
+        p.episode[b] = s_epi[k] + (reset ? 1 : 0);
+      }
       if (p.out_reward) p.out_reward[b] = reward;
       if (p.out_terminal) p.out_terminal[b] = terminal ? 1 : 0;
       if (p.track_score) {
@@ -280,26 +437,76 @@ __global__ __launch_bounds__(256) void maze_step_kernel(StepArgs p) {
   }
 }
 
-__global__ __launch_bounds__(256) void maze_reset_kernel(int B, int H1, const int* mask, int* pos,
-                                                         int* last_action, float* last_reward,
-                                                         const int* count, uint8_t* frames) {
+struct ResetArgs {
+  int B, H1;
+  const int* mask;
+  int* pos;
+  int* last_action;
+  float* last_reward;
+  const int* count;
+  uint8_t* frames;
+  const int* cfg;        // as in StepArgs
+  int actor_base;
+  int* goal;
+  int* layout;
+  int* ep_steps;
+  int* episode;
+};
+
+template <int N>
+__global__ __launch_bounds__(256) void maze_reset_kernel(ResetArgs p) {
+  const int* cfg = p.cfg;
+  if ((cfg ? cfg[0] : 7) != N) return;
   __shared__ uint4 wall_img[FRAME_BYTES / 16];
-  build_wall_image(wall_img);
+  __shared__ int s_lay[kActorsPerGroup], s_epi[kActorsPerGroup], s_rgoal[kActorsPerGroup], s_rstart[kActorsPerGroup];
+  if (threadIdx.x < kActorsPerGroup) {
+    const int k = threadIdx.x, b = blockIdx.x * kActorsPerGroup + k;
+    if (b < p.B) {
+      int lay = 0, epi = 0, rg = kDefaultGoal, rs = kDefaultStart;
+      if (cfg) {
+        lay = maze_layout(cfg, p.layout, b);
+        epi = p.episode[b];
+        maze_reset_cells(cfg, maze_rec(cfg, lay), p.actor_base + b, epi + 1, rg, rs);
+      }
+      s_lay[k] = lay; s_epi[k] = epi; s_rgoal[k] = rg; s_rstart[k] = rs;
+    }
+  }
+  int built = cfg ? maze_layout(cfg, p.layout, blockIdx.x * kActorsPerGroup) : 0;
+  __shared__ uint64_t s_walls[Walls<N>::NW];
+  Walls<N> walls;
+  walls.lds = s_walls;
+  walls.load(cfg ? maze_rec(cfg, built) : nullptr);
+  build_wall_image<N>(wall_img, walls);
   __syncthreads();
+  const bool show_goal = cfg && (cfg[2] & kMazeShowGoal);
   for (int k = 0; k < kActorsPerGroup; ++k) {
     const int b = blockIdx.x * kActorsPerGroup + k;
-    if (b >= B) break;
-    if (mask && !mask[b]) continue;
-    const int slot = count[b] % H1;
-    uint8_t* dst = frames + ((size_t)b * H1 + slot) * FRAME_BYTES;
+    if (b >= p.B) break;
+    if (p.mask && !p.mask[b]) continue;
+    if (s_lay[k] != built) {
+      built = s_lay[k];
+      __syncthreads();
+      walls.load(maze_rec(cfg, built));       // (a layout other than the first: cfg is not null)
+      build_wall_image<N>(wall_img, walls);
+      __syncthreads();
+    }
+    const int sc = s_rstart[k], gc = s_rgoal[k];
+    const int slot = p.count[b] % p.H1;
+    uint8_t* dst = p.frames + ((size_t)b * p.H1 + slot) * FRAME_BYTES;
     render_walls(dst, wall_img);
     __syncthreads();
-    render_agent(dst, kStartX, kStartY);
+    render_blocks<N>(dst, wall_img, sc % N, sc / N, gc % N, gc / N, show_goal);
     if (threadIdx.x == 0) {
-      pos[2 * b] = kStartX;
-      pos[2 * b + 1] = kStartY;
-      last_action[b] = 0;
-      last_reward[b] = 0.f;
+      p.pos[2 * b] = sc % N;
+      p.pos[2 * b + 1] = sc / N;
+      p.last_action[b] = 0;
+      p.last_reward[b] = 0.f;
+      if (p.cfg) {
+        p.goal[2 * b] = gc % N;
+        p.goal[2 * b + 1] = gc / N;
+        p.ep_steps[b] = 0;
+        p.episode[b] = s_epi[k] + 1;
+      }
     }
   }
 }
@@ -505,27 +712,6 @@ __global__ __launch_bounds__(256) void hostfed_reset_hw_kernel(int H1, long fram
   }
 }
 
-// ---- Philox4x32-10 counter RNG: key = seed, counter = (index, stream) ------------------------
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-  uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-  uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-  uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
-__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t index, uint64_t stream, uint32_t (&out)[4]) {
-  uint32_t c[4] = {(uint32_t)index, (uint32_t)(index >> 32), (uint32_t)stream, (uint32_t)(stream >> 32)};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
-}
-
 // Element i of a rank's draw is element (i / row_len) * row_stride + col0 + i % row_len of the GLOBAL draw: with
 // row_len = this rank's actors, row_stride = all actors and col0 = the rank's first actor, a job sharded over W ranks
 // draws exactly what one process holding every actor would (row_len = row_stride = n, col0 = 0: a plain stream).
@@ -552,26 +738,93 @@ __global__ void philox_randint_kernel(uint64_t seed, uint64_t stream, int n, int
   out[i] = (int)(((uint64_t)r[0] * (uint64_t)high) >> 32);
 }
 
+template <int N>
+void launch_maze_step(const StepArgs& p, hipStream_t s) {
+  if (p.B <= 64) hipLaunchKernelGGL((maze_step_kernel<N, kStepActorsTiny>), dim3((p.B + kStepActorsTiny - 1) / kStepActorsTiny), dim3(256), 0, s, p);
+  else if (p.B <= 1024) hipLaunchKernelGGL((maze_step_kernel<N, 2>), dim3((p.B + 1) / 2), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((maze_step_kernel<N, kStepActorsBig>), dim3((p.B + kStepActorsBig - 1) / kStepActorsBig), dim3(256), 0, s, p);
+}
+
+// grid sizes whose cells tile the 84-px frame: 12, 7, 6 and 4 px
+bool maze_n_ok(int N) { return N == 7 || N == 12 || N == 14 || N == 21; }
+
+// the configured-maze arguments of a *_cfg entry: with a config block every per-actor array is required; without one the
+// reference's 7 x 7 map is stepped and the arrays are not used
+bool maze_cfg_ok(int N, const int* cfg, int actor_base, const int* goal, const int* layout, const int* ep_steps,
+                        const int* episode) {
+  if (!cfg) return N == 7;
+  return maze_n_ok(N) && actor_base >= 0 && goal && layout && ep_steps && episode;
+}
+
+int maze_step_launch(int N, StepArgs& p, const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps,
+                            int* episode, void* stream) {
+  p.cfg = cfg;
+  p.actor_base = actor_base;
+  p.goal = cfg ? goal : nullptr;
+  p.layout = cfg ? layout : nullptr;
+  p.ep_steps = cfg ? ep_steps : nullptr;
+  p.episode = cfg ? episode : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  switch (N) {
+    case 7: launch_maze_step<7>(p, s); break;
+    case 12: launch_maze_step<12>(p, s); break;
+    case 14: launch_maze_step<14>(p, s); break;
+    default: launch_maze_step<21>(p, s); break;
+  }
+  return unreal_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
+
+int unreal_maze_step_cfg(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
+                         float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                         int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc,
+                         float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
+                         int* score_valid, int reset_on_terminal, int track_score, int N, const int* cfg,
+                         int actor_base, int* goal, int* layout, int* ep_steps, int* episode, void* stream) {
+  if (B <= 0 || H1 < 2 || !actions || !pos || !count || !frames) return UNREAL_EINVAL;
+  if (track_score && (!episode_reward || !score_out || !score_valid)) return UNREAL_EINVAL;
+  if (!maze_cfg_ok(N, cfg, actor_base, goal, layout, ep_steps, episode)) return UNREAL_EINVAL;
+  StepArgs p{B, H1, actions, active, pos, last_action, last_reward, count, frames, r_reward, r_action,
+             r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward,
+             score_out, score_valid, reset_on_terminal, track_score};
+  UNREAL_LAUNCHED(B <= 64 ? "maze_step tiny" : B <= 1024 ? "maze_step apg2" : "maze_step big");
+  return maze_step_launch(N, p, cfg, actor_base, goal, layout, ep_steps, episode, stream);
+}
 
 int unreal_maze_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
                      float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
                      int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc,
                      float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
                      int* score_valid, int reset_on_terminal, int track_score, void* stream) {
-  if (B <= 0 || H1 < 2 || !actions || !pos || !count || !frames) return UNREAL_EINVAL;
-  if (track_score && (!episode_reward || !score_out || !score_valid)) return UNREAL_EINVAL;
-  StepArgs p{B, H1, actions, active, pos, last_action, last_reward, count, frames, r_reward, r_action,
+  return unreal_maze_step_cfg(B, H1, actions, active, pos, last_action, last_reward, count, frames, r_reward, r_action,
+                              r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward,
+                              score_out, score_valid, reset_on_terminal, track_score, 7, nullptr, 0, nullptr, nullptr,
+                              nullptr, nullptr, stream);
+}
+
+int unreal_maze_rollout_step_cfg(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                 int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                 int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                 int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                 int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                 float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor, int N,
+                                 const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps, int* episode,
+                                 void* stream) {
+  if (B <= 0 || H1 < 2 || !actions || !pos || !count || !frames || !last_action || !last_reward) return UNREAL_EINVAL;
+  if (!episode_reward || !score_out || !score_valid || !active || !active_log_t || !n_steps || !terminal_end)
+    return UNREAL_EINVAL;
+  if (next_lar && (A <= 0 || lar_col0 < 0 || lar_ld < lar_col0 + A + 1)) return UNREAL_EINVAL;
+  if (idx_base_actor < 0) return UNREAL_EINVAL;
+  if (!maze_cfg_ok(N, cfg, actor_base, goal, layout, ep_steps, episode)) return UNREAL_EINVAL;
+  StepArgs p{B, H1, actions, nullptr, pos, last_action, last_reward, count, frames, r_reward, r_action,
              r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward,
-             score_out, score_valid, reset_on_terminal, track_score, nullptr, nullptr, nullptr, nullptr, nullptr,
-             nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  UNREAL_LAUNCHED(B <= 64 ? "maze_step tiny" : B <= 1024 ? "maze_step apg2" : "maze_step big");
-  if (B <= 64) hipLaunchKernelGGL(maze_step_kernel<kStepActorsTiny>, dim3((B + kStepActorsTiny - 1) / kStepActorsTiny), dim3(256), 0, (hipStream_t)stream, p);
-  else if (B <= 1024) hipLaunchKernelGGL(maze_step_kernel<2>, dim3((B + 1) / 2), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(maze_step_kernel<kStepActorsBig>, dim3((B + kStepActorsBig - 1) / kStepActorsBig), dim3(256), 0, (hipStream_t)stream, p);
-  return unreal_launch_status();
+             score_out, score_valid, 1, 1, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
+             lar_col0, A, idx_base_actor};
+  UNREAL_LAUNCHED(B <= 64 ? "maze_rollout_step tiny" : B <= 1024 ? "maze_rollout_step apg2" : "maze_rollout_step big");
+  return maze_step_launch(N, p, cfg, actor_base, goal, layout, ep_steps, episode, stream);
 }
 
 int unreal_maze_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward, int* count,
@@ -580,20 +833,37 @@ int unreal_maze_rollout_step(int B, int H1, const int* actions, int* pos, int* l
                              float* episode_reward, float* score_out, int* score_valid, int* active,
                              int* active_log_t, int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
                              int lar_ld, int lar_col0, int A, int idx_base_actor, void* stream) {
-  if (B <= 0 || H1 < 2 || !actions || !pos || !count || !frames || !last_action || !last_reward) return UNREAL_EINVAL;
+  return unreal_maze_rollout_step_cfg(B, H1, actions, pos, last_action, last_reward, count, frames, r_reward, r_action,
+                                      r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal,
+                                      episode_reward, score_out, score_valid, active, active_log_t, n_steps,
+                                      terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, 7, nullptr,
+                                      0, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+int unreal_maze_policy_rollout_step_cfg(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                        const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                        int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
+                                        uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                        int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                        int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                        int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                        float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor, int N,
+                                        const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps,
+                                        int* episode, void* stream) {
+  if (B <= 0 || H1 < 2 || !pos || !count || !frames || !last_action || !last_reward) return UNREAL_EINVAL;
+  if (!X || ldx < LSTM_N || !Wp || !bp || !Wv || !bv || !u || !pi_out || !v_out || !actions_out) return UNREAL_EINVAL;
+  if (A != 4) return UNREAL_EINVAL;                  // the maze has four actions (maze_environment.py:98-112)
   if (!episode_reward || !score_out || !score_valid || !active || !active_log_t || !n_steps || !terminal_end)
     return UNREAL_EINVAL;
-  if (next_lar && (A <= 0 || lar_col0 < 0 || lar_ld < lar_col0 + A + 1)) return UNREAL_EINVAL;
+  if (next_lar && (lar_col0 < 0 || lar_ld < lar_col0 + A + 1)) return UNREAL_EINVAL;
   if (idx_base_actor < 0) return UNREAL_EINVAL;
-  StepArgs p{B, H1, actions, nullptr, pos, last_action, last_reward, count, frames, r_reward, r_action,
+  if (!maze_cfg_ok(N, cfg, actor_base, goal, layout, ep_steps, episode)) return UNREAL_EINVAL;
+  StepArgs p{B, H1, nullptr, nullptr, pos, last_action, last_reward, count, frames, r_reward, r_action,
              r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward,
              score_out, score_valid, 1, 1, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
-             lar_col0, A, idx_base_actor, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  UNREAL_LAUNCHED(B <= 64 ? "maze_rollout_step tiny" : B <= 1024 ? "maze_rollout_step apg2" : "maze_rollout_step big");
-  if (B <= 64) hipLaunchKernelGGL(maze_step_kernel<kStepActorsTiny>, dim3((B + kStepActorsTiny - 1) / kStepActorsTiny), dim3(256), 0, (hipStream_t)stream, p);
-  else if (B <= 1024) hipLaunchKernelGGL(maze_step_kernel<2>, dim3((B + 1) / 2), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(maze_step_kernel<kStepActorsBig>, dim3((B + kStepActorsBig - 1) / kStepActorsBig), dim3(256), 0, (hipStream_t)stream, p);
-  return unreal_launch_status();
+             lar_col0, A, idx_base_actor, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
+  UNREAL_LAUNCHED(B <= 64 ? "maze_policy_step tiny" : B <= 1024 ? "maze_policy_step apg2" : "maze_policy_step big");
+  return maze_step_launch(N, p, cfg, actor_base, goal, layout, ep_steps, episode, stream);
 }
 
 int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp, const float* Wv,
@@ -604,30 +874,36 @@ int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, cons
                                     int* score_valid, int* active, int* active_log_t, int* n_steps, int* terminal_end,
                                     int* next_idx, float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
                                     void* stream) {
-  if (B <= 0 || H1 < 2 || !pos || !count || !frames || !last_action || !last_reward) return UNREAL_EINVAL;
-  if (!X || ldx < LSTM_N || !Wp || !bp || !Wv || !bv || !u || !pi_out || !v_out || !actions_out) return UNREAL_EINVAL;
-  if (A != 4) return UNREAL_EINVAL;                  // the maze has four actions (maze_environment.py:98-112)
-  if (!episode_reward || !score_out || !score_valid || !active || !active_log_t || !n_steps || !terminal_end)
-    return UNREAL_EINVAL;
-  if (next_lar && (lar_col0 < 0 || lar_ld < lar_col0 + A + 1)) return UNREAL_EINVAL;
-  if (idx_base_actor < 0) return UNREAL_EINVAL;
-  StepArgs p{B, H1, nullptr, nullptr, pos, last_action, last_reward, count, frames, r_reward, r_action,
-             r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward,
-             score_out, score_valid, 1, 1, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
-             lar_col0, A, idx_base_actor, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
-  UNREAL_LAUNCHED(B <= 64 ? "maze_policy_step tiny" : B <= 1024 ? "maze_policy_step apg2" : "maze_policy_step big");
-  if (B <= 64) hipLaunchKernelGGL(maze_step_kernel<kStepActorsTiny>, dim3((B + kStepActorsTiny - 1) / kStepActorsTiny), dim3(256), 0, (hipStream_t)stream, p);
-  else if (B <= 1024) hipLaunchKernelGGL(maze_step_kernel<2>, dim3((B + 1) / 2), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(maze_step_kernel<kStepActorsBig>, dim3((B + kStepActorsBig - 1) / kStepActorsBig), dim3(256), 0, (hipStream_t)stream, p);
+  return unreal_maze_policy_rollout_step_cfg(B, H1, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions_out, pos, last_action,
+                                             last_reward, count, frames, r_reward, r_action, r_terminal, r_last_action,
+                                             r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out,
+                                             score_valid, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
+                                             lar_ld, lar_col0, A, idx_base_actor, 7, nullptr, 0, nullptr, nullptr, nullptr,
+                                             nullptr, stream);
+}
+
+int unreal_maze_reset_cfg(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
+                          const int* count, uint8_t* frames, int N, const int* cfg, int actor_base, int* goal, int* layout,
+                          int* ep_steps, int* episode, void* stream) {
+  if (B <= 0 || H1 < 2 || !pos || !count || !frames) return UNREAL_EINVAL;
+  if (!maze_cfg_ok(N, cfg, actor_base, goal, layout, ep_steps, episode)) return UNREAL_EINVAL;
+  ResetArgs p{B, H1, mask, pos, last_action, last_reward, count, frames, cfg, actor_base, cfg ? goal : nullptr,
+              cfg ? layout : nullptr, cfg ? ep_steps : nullptr, cfg ? episode : nullptr};
+  const dim3 grid((B + kActorsPerGroup - 1) / kActorsPerGroup);
+  hipStream_t s = (hipStream_t)stream;
+  switch (N) {
+    case 7: hipLaunchKernelGGL(maze_reset_kernel<7>, grid, dim3(256), 0, s, p); break;
+    case 12: hipLaunchKernelGGL(maze_reset_kernel<12>, grid, dim3(256), 0, s, p); break;
+    case 14: hipLaunchKernelGGL(maze_reset_kernel<14>, grid, dim3(256), 0, s, p); break;
+    default: hipLaunchKernelGGL(maze_reset_kernel<21>, grid, dim3(256), 0, s, p); break;
+  }
   return unreal_launch_status();
 }
 
 int unreal_maze_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
                       const int* count, uint8_t* frames, void* stream) {
-  if (B <= 0 || H1 < 2 || !pos || !count || !frames) return UNREAL_EINVAL;
-  hipLaunchKernelGGL(maze_reset_kernel, dim3((B + kActorsPerGroup - 1) / kActorsPerGroup), dim3(256), 0, (hipStream_t)stream, B, H1, mask, pos,
-                     last_action, last_reward, count, frames);
-  return unreal_launch_status();
+  return unreal_maze_reset_cfg(B, H1, mask, pos, last_action, last_reward, count, frames, 7, nullptr, 0, nullptr, nullptr,
+                               nullptr, nullptr, stream);
 }
 
 int unreal_hostfed_step(int B, int H1, const uint8_t* staged, const int* actions, const float* rewards,

@@ -13,6 +13,8 @@ class Environment(object):
     INDOOR_CONFIG = {}
     # stands in for gym.make(env_name).action_space.n (gym_environment.py:55-60): env_name -> action count
     GYM_CONFIG = {}
+    # env_name -> maze_environment.MazeConfig: user mazes on the device (an unregistered name is the reference's map)
+    MAZE_CONFIG = {}
 
     @staticmethod
     def register_indoor_config(env_name, objective_size, height=84, width=84):
@@ -30,10 +32,21 @@ class Environment(object):
         Environment.GYM_CONFIG[env_name] = a
 
     @staticmethod
+    def register_maze_config(env_name, layouts, random_start=False, random_goal=False, show_goal=False,
+                             max_episode_steps=0):
+        """Mazes of `env_name`: `layouts` = N x N maps (strings, or lists of row strings; + wall, - free, S start, G goal),
+        N in {7, 12, 14, 21}, up to 1024 of them; global actor g runs layout g * L // (all actors).  random_start /
+        random_goal: drawn at every reset, uniformly over the free cells (the start never on the goal); show_goal: the
+        goal block in channel 2; max_episode_steps > 0: an episode that has not reached the goal ends (terminal) at
+        that step.  Raises ValueError on a malformed config."""
+        from .maze_environment import MazeConfig
+        Environment.MAZE_CONFIG[env_name] = MazeConfig(layouts, random_start, random_goal, show_goal, max_episode_steps)
+
+    @staticmethod
     def create_environment(env_type, env_name, termination_time=50.0, env_args=None, thread_index=0):
         if env_type == 'maze':
             from . import maze_environment
-            return maze_environment.MazeEnvironment()
+            return maze_environment.MazeEnvironment(config=Environment.MAZE_CONFIG.get(env_name))
         raise NotImplementedError("env_type %r needs an external simulator that is out of scope (SURVEY 8f)" % env_type)
 
     @staticmethod

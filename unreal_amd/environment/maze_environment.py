@@ -3,21 +3,154 @@
 `BatchedMazeEnvironment` steps B mazes with one kernel launch and writes frames straight into the
 replay ring; `MazeEnvironment` is the reference's batch-1 object surface over the same kernels
 (`process(action) -> (image, reward, terminal, pixel_change)`, `reset`, `last_state` dict with 'image',
-`last_action`, `last_reward`), with the adapter semantics of SURVEY H1 (`flag` ignored)."""
+`last_action`, `last_reward`), with the adapter semantics of SURVEY H1 (`flag` ignored).
+
+`MazeConfig` describes user mazes (Environment.register_maze_config): N x N layouts in the reference map's alphabet, optional
+random start / goal cells drawn at every reset, an optional goal block in channel 2 and an optional episode step limit."""
+from collections import deque
+
 import numpy as np
 import torch
 
 from .. import ops
 from . import environment
 
+REFERENCE_MAP = ("--+---G"
+                 "--+-+++"
+                 "S-+---+"
+                 "--+++--"
+                 "--+-+--"
+                 "--+----"
+                 "-----++")       # maze_environment.py:18-25
+
+
+class MazeConfig(object):
+    """Validated layouts and options of a configured maze, and the int32 configuration block the kernels read
+    (unreal_maze_*_cfg in include/unreal_hip.h).  Raises ValueError on a malformed configuration."""
+    SIZES = (7, 12, 14, 21)          # the grid sizes whose cells tile the 84-px frame: 12, 7, 6, 4 px
+    MAX_LAYOUTS = 1024
+    RANDOM_START, RANDOM_GOAL, SHOW_GOAL = 1, 2, 4
+    HEADER, RECORD_HEADER = 8, 18
+
+    def __init__(self, layouts, random_start=False, random_goal=False, show_goal=False, max_episode_steps=0):
+        if isinstance(layouts, str) or not len(layouts):
+            raise ValueError("layouts: a non-empty list of layouts (strings, or lists of row strings)")
+        if len(layouts) > self.MAX_LAYOUTS:
+            raise ValueError("%d layouts: at most %d per config" % (len(layouts), self.MAX_LAYOUTS))
+        self.random_start, self.random_goal, self.show_goal = bool(random_start), bool(random_goal), bool(show_goal)
+        if int(max_episode_steps) != max_episode_steps or not 0 <= max_episode_steps <= 2 ** 31 - 1:
+            raise ValueError("max_episode_steps %r: an integer in [0, 2**31 - 1] (0: no limit; the kernels count steps "
+                             "in int32)" % (max_episode_steps,))
+        self.max_episode_steps = int(max_episode_steps)
+        self.layouts = [self._parse(i, lay) for i, lay in enumerate(layouts)]
+        sizes = set(int(round(len(m) ** 0.5)) for m in self.layouts)
+        if len(sizes) != 1:
+            raise ValueError("layouts of one config must share their size; got %s" % sorted(sizes))
+        self.N = sizes.pop()
+        self.L = len(self.layouts)
+        self.walls, self.start, self.goal, self.free = [], [], [], []
+        for i, m in enumerate(self.layouts):
+            self._check(i, m)
+
+    def _parse(self, i, lay):
+        if isinstance(lay, str):
+            m = "".join(lay.split())
+        else:
+            rows = [str(r) for r in lay]
+            if len(set(len(r) for r in rows)) != 1 or len(rows) != len(rows[0]):
+                raise ValueError("layout %d: %d rows of lengths %s, not N x N" % (i, len(rows), [len(r) for r in rows]))
+            m = "".join(rows)
+        n = int(round(len(m) ** 0.5))
+        if n * n != len(m) or n not in self.SIZES:
+            raise ValueError("layout %d: %d cells; supported are N x N with N in %s" % (i, len(m), self.SIZES))
+        bad = set(m) - set("+-SG")
+        if bad:
+            raise ValueError("layout %d: unknown characters %s (use + wall, - free, S start, G goal)" % (i, sorted(bad)))
+        return m
+
+    def _check(self, i, m):
+        N = int(round(len(m) ** 0.5))
+        n_s, n_g = m.count("S"), m.count("G")
+        if not self.random_start and n_s != 1:
+            raise ValueError("layout %d: %d 'S' cells; exactly one is needed without random_start" % (i, n_s))
+        if not self.random_goal and n_g != 1:
+            raise ValueError("layout %d: %d 'G' cells; exactly one is needed without random_goal" % (i, n_g))
+        free = [c for c in range(N * N) if m[c] != "+"]
+        if self.random_start and len(free) < 2:
+            raise ValueError("layout %d: %d free cells; random_start needs at least 2" % (i, len(free)))
+        if not free:
+            raise ValueError("layout %d has no free cell" % i)
+        seen, todo = {free[0]}, deque([free[0]])        # 4-connectivity of the free cells (BFS)
+        while todo:
+            c = todo.popleft()
+            x, y = c % N, c // N
+            for nx, ny in ((x + 1, y), (x - 1, y), (x, y + 1), (x, y - 1)):
+                d = ny * N + nx
+                if 0 <= nx < N and 0 <= ny < N and m[d] != "+" and d not in seen:
+                    seen.add(d)
+                    todo.append(d)
+        if len(seen) != len(free):
+            raise ValueError("layout %d: the free cells are not 4-connected (%d of %d reachable)" % (i, len(seen), len(free)))
+        self.walls.append(np.array([ch == "+" for ch in m], dtype=bool))
+        self.start.append(m.index("S") if n_s == 1 else -1)
+        self.goal.append(m.index("G") if n_g == 1 else -1)
+        self.free.append(np.array(free, dtype=np.int32))
+
+    @property
+    def flags(self):
+        return (self.RANDOM_START * self.random_start) | (self.RANDOM_GOAL * self.random_goal) | \
+            (self.SHOW_GOAL * self.show_goal)
+
+    def block(self, seed):
+        """-> int32 numpy array: header [N, L, flags, max_episode_steps, seed lo, seed hi, record words, 0], then per
+        layout [wall bits of cell y*N+x as 7 x (lo, hi) uint32, S cell, G cell, n_free, index of G in the free list,
+        free cells ascending] (-1: none)."""
+        N, rec = self.N, self.RECORD_HEADER + self.N * self.N
+        seed = int(seed) & (2 ** 64 - 1)
+        out = np.zeros(self.HEADER + self.L * rec, dtype=np.int64)
+        out[:8] = [N, self.L, self.flags, self.max_episode_steps, seed & 0xFFFFFFFF, seed >> 32, rec, 0]
+        for l in range(self.L):
+            r = out[self.HEADER + l * rec:self.HEADER + (l + 1) * rec]
+            bits = np.zeros(448, dtype=np.int64)
+            bits[:N * N] = self.walls[l]
+            words = (bits.reshape(14, 32) << np.arange(32)).sum(1)
+            r[:14] = words
+            free, g = self.free[l], self.goal[l]
+            r[14], r[15], r[16] = self.start[l], g, len(free)
+            r[17] = int(np.searchsorted(free, g)) if g >= 0 else -1
+            r[self.RECORD_HEADER:self.RECORD_HEADER + len(free)] = free
+        return (out & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+    def layout_ids(self, actor_base, batch, actors_total):
+        """Layout of global actors [actor_base, actor_base + batch): g * L // actors_total (contiguous blocks)."""
+        g = np.arange(actor_base, actor_base + batch, dtype=np.int64)
+        return (g * self.L // int(actors_total)).astype(np.int32)
+
+    @staticmethod
+    def reference():
+        """The reference's map as a configuration (renders and steps exactly like the unconfigured maze)."""
+        return MazeConfig([REFERENCE_MAP])
+
 
 class BatchedMazeEnvironment(object):
     ACTION_SIZE = 4
     frame_scale = 1.0          # ring bytes are the pixel values themselves (0 / 1)
 
-    def __init__(self, batch, history_size, device="cuda:0"):
+    def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0):
+        """`config`: a MazeConfig (None: the reference's map).  `actor_base` / `actors_total`: global index of actor 0 and
+        the number of actors over every rank (layouts are assigned and reset draws keyed by the global index);
+        `seed`: key of the reset draws."""
         self.B = batch
-        self.ring = ops.Ring(batch, history_size, torch.device(device))
+        self.config = config
+        self.ring = ops.Ring(batch, history_size, torch.device(device), maze_state=config is not None)
+        self.maze = None
+        if config is not None:
+            total = batch if actors_total is None else int(actors_total)
+            if actor_base < 0 or actor_base + batch > total:
+                raise ValueError("actors [%d, %d) outside the %d actors of the job" % (actor_base, actor_base + batch, total))
+            block = torch.from_numpy(config.block(seed)).to(self.ring.count.device)
+            self.ring.layout.copy_(torch.from_numpy(config.layout_ids(actor_base, batch, total)))
+            self.maze = (config.N, block, int(actor_base))
         self.reset()
 
     def view(self, b0, b1):
@@ -26,6 +159,8 @@ class BatchedMazeEnvironment(object):
         v = object.__new__(BatchedMazeEnvironment)
         v.B, v.ring = b1 - b0, ops.ring_view(self.ring, b0, b1)
         v.base_actor = b0
+        v.config = self.config
+        v.maze = None if self.maze is None else (self.maze[0], self.maze[1], self.maze[2] + b0)
         return v
 
     @staticmethod
@@ -33,18 +168,18 @@ class BatchedMazeEnvironment(object):
         return 4
 
     def reset(self, mask=None):
-        ops.maze_reset(self.ring, mask)
+        ops.maze_reset(self.ring, mask, maze=self.maze)
 
     def process(self, actions, active=None, out_reward=None, out_terminal=None, reset_on_terminal=True,
                 track_score=False):
-        ops.maze_step(self.ring, actions, active, out_reward, out_terminal, reset_on_terminal, track_score)
+        ops.maze_step(self.ring, actions, active, out_reward, out_terminal, reset_on_terminal, track_score, maze=self.maze)
 
     def rollout_step(self, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
                      index_parent=False, **nxt):
         """process() + the rollout loop's bookkeeping (+ the next step's frame indices / LSTM-input columns) fused.
         `index_parent` (views only): the prepared frame indices address the ring this view was cut from."""
         ops.maze_rollout_step(self.ring, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
-                              base_actor=getattr(self, "base_actor", 0) if index_parent else 0, **nxt)
+                              base_actor=getattr(self, "base_actor", 0) if index_parent else 0, maze=self.maze, **nxt)
 
     def policy_rollout_step(self, net, feat, ld, u, pi_out, v_out, actions, out_reward, out_terminal, active, active_log_t,
                             n_steps, terminal_end, index_parent=False, **nxt):
@@ -53,7 +188,7 @@ class BatchedMazeEnvironment(object):
         ops.maze_policy_rollout_step(self.ring, feat, ld, p["W_base_fc_p"], p["b_base_fc_p"], p["W_base_fc_v"],
                                      p["b_base_fc_v"], u, pi_out, v_out, actions, out_reward, out_terminal, active,
                                      active_log_t, n_steps, terminal_end,
-                                     base_actor=getattr(self, "base_actor", 0) if index_parent else 0, **nxt)
+                                     base_actor=getattr(self, "base_actor", 0) if index_parent else 0, maze=self.maze, **nxt)
 
     def stop(self):
         pass
@@ -64,9 +199,9 @@ class MazeEnvironment(environment.Environment):
     def get_action_size():
         return 4
 
-    def __init__(self, device="cuda:0"):
+    def __init__(self, device="cuda:0", config=None, seed=0):
         environment.Environment.__init__(self)
-        self._env = BatchedMazeEnvironment(1, 2, device)
+        self._env = BatchedMazeEnvironment(1, 2, device, config=config, seed=seed)
         self._a = torch.zeros(1, dtype=torch.int32, device=device)
         self._r = torch.zeros(1, dtype=torch.float32, device=device)
         self._t = torch.zeros(1, dtype=torch.int32, device=device)

@@ -4,7 +4,10 @@ reference evaluates one MINOS episode at a time with batch-1 session calls; here
 lock-step on the device with the same kernels the trainer uses (policy sampled like `choose_action`, or
 greedy).  With `simulator=` the actors are host-fed indoor (MINOS-contract) simulators instead, at the network's
 image_shape (main.py:196), rewards divided by termination_time.  The maze has no step limit (maze_environment.py:114-118), so `max_episode_steps` bounds an episode;
-such episodes count as failures ("success := terminal")."""
+such episodes count as failures ("success := terminal").  With `maze=` (a name given to
+Environment.register_maze_config) the actors run that configured maze: success is reaching the goal (terminal with reward
++1), and a time-out is the environment's own (its max_episode_steps); `max_episode_steps` here bounds episodes only when
+the config sets no limit."""
 import torch
 
 from . import ops
@@ -15,13 +18,19 @@ from .train.trainer import PhiloxDraws
 
 class Evaluate(object):
     def __init__(self, network, batch_size=64, device="cuda:0", seed=0xE7A1, greedy=False, draws=None, simulator=None,
-                 termination_time=50.0):
+                 termination_time=50.0, maze=None):
         self.net, self.B, self.greedy = network, int(batch_size), greedy
         self.device = torch.device(device)
         self.draws = draws if draws is not None else PhiloxDraws(seed)
         B, A = self.B, network._action_size
+        self.maze_config = None
         if simulator is None:
-            self.env = BatchedMazeEnvironment(B, 2, self.device)
+            if maze is not None:
+                from .environment.environment import Environment
+                if maze not in Environment.MAZE_CONFIG:
+                    raise KeyError("maze %r: call Environment.register_maze_config(name, layouts, ...) first" % maze)
+                self.maze_config = Environment.MAZE_CONFIG[maze]
+            self.env = BatchedMazeEnvironment(B, 2, self.device, config=self.maze_config, seed=seed)
         else:
             from .environment.hostfed_environment import HostFedEnvironment
             if tuple(getattr(simulator, "image_shape", (84, 84))) != tuple(network.image_shape):
@@ -52,6 +61,9 @@ class Evaluate(object):
             ws.h0.zero_()
         steps = [0] * B
         done, returns, lengths, successes, timeouts = 0, [], [], 0, 0
+        cfg = self.maze_config
+        env_limit = cfg is not None and cfg.max_episode_steps > 0       # episodes end in the environment
+        configured = cfg is not None
         counted = [False] * B
         if one_episode_per_actor:
             n_episodes = B
@@ -72,6 +84,7 @@ class Evaluate(object):
                 ops.copy_(ws.h0, ws.h[:B * 256])
                 ops.reset_state(B, self.terminals, ws.c0, ws.h0)
             term = self.terminals.cpu().numpy()
+            rew = self.rewards.cpu().numpy()
             score = ring.score_out.cpu().numpy()
             force = torch.zeros(B, dtype=torch.int32)
             ep_r = None
@@ -80,9 +93,13 @@ class Evaluate(object):
                 skip = one_episode_per_actor and counted[b]
                 if term[b]:
                     if not skip:
-                        returns.append(float(score[b])); lengths.append(steps[b]); successes += 1; done += 1
+                        returns.append(float(score[b])); lengths.append(steps[b]); done += 1
+                        if not configured or rew[b] == 1.0:
+                            successes += 1
+                        else:
+                            timeouts += 1              # the configured maze's own time-out
                     steps[b] = 0; counted[b] = True
-                elif steps[b] >= max_episode_steps:
+                elif not env_limit and steps[b] >= max_episode_steps:
                     if ep_r is None:
                         ep_r = ring.episode_reward.cpu()
                     if not skip:

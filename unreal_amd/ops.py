@@ -97,7 +97,7 @@ def kernel_timer_stop():
 class Ring(object):
     """Device replay ring + per-actor environment state (layout: include/unreal_hip.h)."""
 
-    def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE):
+    def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False):
         self.B, self.H, self.H1 = B, H, H + 1
         self.objective_size = objective_size
         self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
@@ -121,6 +121,12 @@ class Ring(object):
         self.episode_reward = z(B)
         self.score_out = z(B)
         self.score_valid = z(B, dt=torch.int32)
+        # configured mazes only (environment/maze_environment.MazeConfig): goal cell (x, y), layout id, steps of the
+        # running episode, episode index (-1 before the first reset)
+        self.goal = z(B * 2, dt=torch.int32) if maze_state else None
+        self.layout = z(B, dt=torch.int32) if maze_state else None
+        self.ep_steps = z(B, dt=torch.int32) if maze_state else None
+        self.episode = torch.full((B,), -1, dtype=torch.int32, device=device) if maze_state else None
 
         self._cur = z(B, dt=torch.int32)
 
@@ -148,31 +154,49 @@ def ring_view(ring, b0, b1):
     v.pos = ring.pos[2 * b0:2 * b1]
     for name in ("last_action", "last_reward", "count", "episode_reward", "score_out", "score_valid", "_cur"):
         setattr(v, name, getattr(ring, name)[b0:b1])
+    v.goal = ring.goal[2 * b0:2 * b1] if ring.goal is not None else None
+    for name in ("layout", "ep_steps", "episode"):
+        t = getattr(ring, name)
+        setattr(v, name, t[b0:b1] if t is not None else None)
     return v
 
 
-def maze_reset(ring, mask=None):
+def _maze_args(ring, maze):
+    """The trailing arguments of a *_cfg maze entry: `maze` = (N, int32 config block on the device, global index of the
+    ring's actor 0), or None for the reference's map."""
+    if maze is None:
+        return ()
+    N, block, actor_base = maze
+    _chk(block, "i32", 8, "maze config")
+    for name, n in (("goal", 2 * ring.B), ("layout", ring.B), ("ep_steps", ring.B), ("episode", ring.B)):
+        _chk(getattr(ring, name), "i32", n, "ring." + name)
+    return (int(N), ptr(block), int(actor_base), ptr(ring.goal), ptr(ring.layout), ptr(ring.ep_steps), ptr(ring.episode))
+
+
+def maze_reset(ring, mask=None, maze=None):
+    """`maze` (every maze wrapper): (N, config block, global actor index of ring actor 0) of a configured maze -> the
+    *_cfg entry; None -> the reference's map."""
     _chk(mask, "i32", ring.B, "mask", optional=True)
-    _call("unreal_maze_reset", ring.B, ring.H1, ptr(mask), ptr(ring.pos), ptr(ring.last_action),
-          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames))
+    _call("unreal_maze_reset" + ("_cfg" if maze else ""), ring.B, ring.H1, ptr(mask), ptr(ring.pos), ptr(ring.last_action),
+          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), *_maze_args(ring, maze))
 
 
 def maze_step(ring, actions, active=None, out_reward=None, out_terminal=None, reset_on_terminal=True,
-              track_score=False):
+              track_score=False, maze=None):
     B = ring.B
     _chk(actions, "i32", B, "actions")
     _chk(active, "i32", B, "active", optional=True)
     _chk(out_reward, "f32", B, "out_reward", optional=True)
     _chk(out_terminal, "i32", B, "out_terminal", optional=True)
-    _call("unreal_maze_step", B, ring.H1, ptr(actions), ptr(active), ptr(ring.pos), ptr(ring.last_action),
+    _call("unreal_maze_step" + ("_cfg" if maze else ""), B, ring.H1, ptr(actions), ptr(active), ptr(ring.pos), ptr(ring.last_action),
           ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward), ptr(ring.r_action),
           ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc),
           ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out),
-          ptr(ring.score_valid), int(reset_on_terminal), int(track_score))
+          ptr(ring.score_valid), int(reset_on_terminal), int(track_score), *_maze_args(ring, maze))
 
 
 def maze_rollout_step(ring, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
-                      next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=0, base_actor=0):
+                      next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=0, base_actor=0, maze=None):
     """maze_step + rollout_advance (+ cur_idx and lar_fill for the NEXT step's rows) in one launch.  `base_actor`: index
     of this (view's) first actor in the ring the next_idx values are meant for (see Ring.cur_idx)."""
     B = ring.B
@@ -181,16 +205,17 @@ def maze_rollout_step(ring, actions, out_reward, out_terminal, active, active_lo
         _chk(t, "i32", B)
     _chk(next_idx, "i32", B, "next_idx", optional=True)
     _chk(next_lar, "f32", (B - 1) * lar_ld + lar_col0 + A + 1 if next_lar is not None else None, "next_lar", optional=True)
-    _call("unreal_maze_rollout_step", B, ring.H1, ptr(actions), ptr(ring.pos), ptr(ring.last_action), ptr(ring.last_reward),
+    _call("unreal_maze_rollout_step" + ("_cfg" if maze else ""), B, ring.H1, ptr(actions), ptr(ring.pos), ptr(ring.last_action), ptr(ring.last_reward),
           ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward), ptr(ring.r_action), ptr(ring.r_terminal),
           ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc), ptr(out_reward), ptr(out_terminal),
           ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid), ptr(active), ptr(active_log_t),
-          ptr(n_steps), ptr(terminal_end), ptr(next_idx), ptr(next_lar), int(lar_ld), int(lar_col0), int(A), int(base_actor))
+          ptr(n_steps), ptr(terminal_end), ptr(next_idx), ptr(next_lar), int(lar_ld), int(lar_col0), int(A), int(base_actor),
+          *_maze_args(ring, maze))
 
 
 def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions, out_reward, out_terminal, active,
                              active_log_t, n_steps, terminal_end, next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=4,
-                             base_actor=0):
+                             base_actor=0, maze=None):
     """policy_step + maze_rollout_step in one launch: the workgroup that steps an actor computes its pi / V / action first
     (bit-identical to the two launches)."""
     B = ring.B
@@ -203,12 +228,12 @@ def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, act
         _chk(t, "i32", B)
     _chk(next_idx, "i32", B, "next_idx", optional=True)
     _chk(next_lar, "f32", (B - 1) * lar_ld + lar_col0 + A + 1 if next_lar is not None else None, "next_lar", optional=True)
-    _call("unreal_maze_policy_rollout_step", B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(u),
+    _call("unreal_maze_policy_rollout_step" + ("_cfg" if maze else ""), B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(u),
           ptr(pi_out), ptr(v_out), ptr(actions), ptr(ring.pos), ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count),
           ptr(ring.frames), ptr(ring.r_reward), ptr(ring.r_action), ptr(ring.r_terminal), ptr(ring.r_last_action),
           ptr(ring.r_last_reward), ptr(ring.r_pc), ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward),
           ptr(ring.score_out), ptr(ring.score_valid), ptr(active), ptr(active_log_t), ptr(n_steps), ptr(terminal_end),
-          ptr(next_idx), ptr(next_lar), int(lar_ld), int(lar_col0), int(A), int(base_actor))
+          ptr(next_idx), ptr(next_lar), int(lar_ld), int(lar_col0), int(A), int(base_actor), *_maze_args(ring, maze))
 
 
 def pixel_change_u8(frames, idx_new, idx_old, denom, out):

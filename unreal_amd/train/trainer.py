@@ -128,6 +128,7 @@ class Trainer(object):
         self.initial_learning_rate = initial_learning_rate
         self._own_draws = draws is None
         self.draws = draws if draws is not None else PhiloxDraws(seed, self.rank, self.B, self.world_size)
+        self.seed = int(seed)                        # also the key of a configured maze's reset draws
         self.local_t = 0
         self.episode_reward = 0
         self.prev_local_t = -1
@@ -144,7 +145,12 @@ class Trainer(object):
         B, A, dev = self.B, self.action_size, self.device
         T, Ta = self.n_step_TD, self.local_t_max
         if self.env_type == "maze":
-            self.environment = BatchedMazeEnvironment(B, self.experience_history_size, dev)
+            # a registered maze config (Environment.register_maze_config): layouts and reset draws follow the GLOBAL actor
+            # index, so a job over W ranks runs what one process with all W * B actors would
+            self.environment = BatchedMazeEnvironment(B, self.experience_history_size, dev,
+                                                      config=Environment.MAZE_CONFIG.get(self.env_name),
+                                                      actor_base=self.rank * B, actors_total=self.world_size * B,
+                                                      seed=self.seed)
         else:
             from ..environment.hostfed_environment import HostFedEnvironment
             indoor = self.env_type == "indoor"
