@@ -100,6 +100,38 @@ int unreal_maze_policy_rollout_step_cfg(int B, int H1, const float* X, int ldx, 
 int unreal_maze_reset_cfg(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
                           const int* count, uint8_t* frames, int N, const int* cfg, int actor_base, int* goal, int* layout,
                           int* ep_steps, int* episode, void* stream);
+/* first-person views of configured mazes (MazeConfig(view="first_person"); maze_fp.hip): the *_cfg entries
+ * with a per-actor heading[B] (0: +x, 1: +y, 2: -x, 3: -y) after pos.  Actions: 0 turn left, 1 turn right, 2 step forward,
+ * 3 step back.  Frames are the raycast 84 x 84 RGB view (bytes 0..255, read at scale 1/255); r_pc is the pixel change of
+ * the two frames over 48 * 255, as unreal_pixel_change_u8.  `cfg` is required (word 7: start heading + 1, 0 = drawn from
+ * Philox word 2 of the reset draw); a block whose N differs from the entry's makes the kernel write nothing. */
+int unreal_maze_fp_reset(int B, int H1, const int* mask, int* pos, int* heading, int* last_action, float* last_reward,
+                         const int* count, uint8_t* frames, int N, const int* cfg, int actor_base, int* goal, int* layout,
+                         int* ep_steps, int* episode, void* stream);
+int unreal_maze_fp_step(int B, int H1, const int* actions, const int* active, int* pos, int* heading, int* last_action,
+                        float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                        int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                        float* episode_reward, float* score_out, int* score_valid, int reset_on_terminal,
+                        int track_score, int N, const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps,
+                        int* episode, void* stream);
+int unreal_maze_fp_rollout_step(int B, int H1, const int* actions, int* pos, int* heading, int* last_action,
+                                float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                                int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                int* out_terminal, float* episode_reward, float* score_out, int* score_valid, int* active,
+                                int* active_log_t, int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
+                                float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A, int idx_base_actor, int N,
+                                const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps, int* episode,
+                                void* stream);
+int unreal_maze_fp_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                       const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                       int* actions_out, int* pos, int* heading, int* last_action, float* last_reward,
+                                       int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                       int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                       int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                       int* active, int* active_log_t, int* n_steps, int* terminal_end,
+                                       int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0,
+                                       int A, int idx_base_actor, int N, const int* cfg, int actor_base, int* goal,
+                                       int* layout, int* ep_steps, int* episode, void* stream);
 /* host-fed environments (environment/lab_environment.py:78-119 contract): `staged` holds one uint8
  * frame per actor (post-reset observation where terminals[b] != 0) */
 int unreal_hostfed_step(int B, int H1, const uint8_t* staged, const int* actions, const float* rewards,

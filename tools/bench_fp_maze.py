@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""First-person vs top-down device mazes, in one process:
+
+  * the step kernel's time per launch (HIP events around each launch, random actions) for the top-down and the
+    first-person view of the same configured mazes, at B = 512 and B = 4096, N = 7 and N = 21;
+  * Trainer.process() ms for full UNREAL at B = 4096 in both views (replay history --history, filled untimed).
+
+  python tools/bench_fp_maze.py [--launches 200] [--steps 10] [--warmup 3] [--history 100]
+
+Prints one JSON line per measurement."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+DEV = "cuda:0"
+
+
+def layouts(N, L=8, seed=0):
+    from maze_model import random_layout
+    rs = np.random.RandomState(seed + N)
+    return [random_layout(N, rs, marks="") for _ in range(L)]
+
+
+def kernel_ms(env, B, launches):
+    """Mean HIP-event time of one step launch (the entry point env.process calls)."""
+    from unreal_amd import ops
+    rs = np.random.RandomState(0)
+    acts = [torch.from_numpy(rs.randint(0, 4, B).astype(np.int32)).to(DEV) for _ in range(8)]
+    r = torch.zeros(B, dtype=torch.float32, device=DEV)
+    t = torch.zeros(B, dtype=torch.int32, device=DEV)
+    for k in range(10):
+        env.process(acts[k % 8], None, r, t, track_score=True)
+    name = "unreal_maze_fp_step" if env.frame_scale != 1.0 else "unreal_maze_step_cfg"
+    ops.kernel_timer_start(name)
+    for k in range(launches):
+        env.process(acts[k % 8], None, r, t, track_score=True)
+    res = ops.kernel_timer_stop()
+    assert res["launches"] == launches, res
+    return res["ms"] / launches
+
+
+def trainer_ms(env_name, B, history, steps, warmup):
+    from unreal_amd.environment.environment import Environment
+    from unreal_amd.model.model import UnrealModel
+    from unreal_amd.options import get_options
+    from unreal_amd.train.rmsprop_applier import RMSPropApplier
+    from unreal_amd.train.trainer import Trainer, log_uniform
+    flags = get_options("training", preset="lab", argv=["--env_type", "maze", "--env_name", env_name])
+    Environment.action_size = -1
+    A = Environment.get_action_size("maze", env_name)
+    net = UnrealModel(A, 0, -1, flags.use_lstm, flags.use_pixel_change, flags.use_value_replay,
+                      flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta, DEV, seed=1)
+    lr0 = log_uniform(flags.initial_alpha_low, flags.initial_alpha_high, flags.initial_alpha_log_rate)
+    applier = RMSPropApplier(None, decay=flags.rmsp_alpha, momentum=0.0, epsilon=flags.rmsp_epsilon,
+                             clip_norm=flags.grad_norm_clip, device=DEV)
+    tr = Trainer(0, net, lr0, None, applier, "maze", env_name, flags.use_lstm, flags.use_pixel_change,
+                 flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
+                 flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, history, flags.max_time_step, DEV,
+                 batch_size=B, seed=0xA3C)
+    tr.prepare()
+    while not tr._full:
+        tr.process(None, 0)
+    for _ in range(warmup):
+        tr.process(None, 0)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    for _ in range(steps):
+        tr.process(None, 0)
+    e1.record()
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) * 1e3 / steps
+    out = e0.elapsed_time(e1) / steps, wall
+    del tr, net, applier
+    torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--launches", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--history", type=int, default=100)
+    ap.add_argument("--skip-trainer", action="store_true")
+    args = ap.parse_args()
+    from unreal_amd.environment.environment import Environment
+    from unreal_amd.environment.maze_environment import MazeConfig, batched_maze_environment
+    kw = dict(random_start=True, random_goal=True, show_goal=True, max_episode_steps=200)
+    for N in (7, 21):
+        lays = layouts(N)
+        for view in ("top_down", "first_person"):
+            cfg = MazeConfig(lays, view=view, **kw)
+            for B in (512, 4096):
+                env = batched_maze_environment(B, 3, DEV, config=cfg, seed=1)
+                ms = kernel_ms(env, B, args.launches)
+                print(json.dumps(dict(what="step_kernel", view=view, N=N, B=B, us_per_launch=round(ms * 1e3, 2),
+                                      GBps=round(B * 21168 * (2 if view == "first_person" else 1) / ms / 1e6, 1))),
+                      flush=True)
+                del env
+    if args.skip_trainer:
+        return
+    lays = layouts(7)
+    for view in ("top_down", "first_person"):
+        name = "bench_fp_" + view
+        Environment.register_maze_config(name, lays, view=view, **kw)
+        ms, wall = trainer_ms(name, 4096, args.history, args.steps, args.warmup)
+        print(json.dumps(dict(what="trainer_process", view=view, N=7, B=4096, history=args.history,
+                              ms_per_call=round(ms, 3), wall_ms_per_call=round(wall, 3))), flush=True)
+
+
+if __name__ == "__main__":
+    main()

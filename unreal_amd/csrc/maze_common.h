@@ -1,0 +1,73 @@
+// Pieces shared by the top-down maze kernels (env.hip) and the first-person ones (maze_fp.hip): the Philox4x32-10 counter
+// RNG, the configuration block's layout and accessors, and the reset draw of goal and start cells.
+#pragma once
+#include "common.h"
+
+namespace {
+
+// ---- Philox4x32-10 counter RNG: key = seed, counter = (index, stream) ------------------------
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+  uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
+  uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+  uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
+  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+}
+
+__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t index, uint64_t stream, uint32_t (&out)[4]) {
+  uint32_t c[4] = {(uint32_t)index, (uint32_t)(index >> 32), (uint32_t)stream, (uint32_t)(stream >> 32)};
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(c, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
+}
+
+// ---- maze configuration block (int32 words, built by the host: environment/environment.py register_maze_config) ------
+// header:  [0] N  [1] L layouts  [2] flags  [3] max_episode_steps (0: none)  [4..5] seed (lo, hi)  [6] record words  [7] 0
+// record l at kCfgHdr + l * rec:  [0..13] wall bits of cell y*N+x as 7 uint64 (lo, hi)  [14] S cell (-1: none)
+//   [15] G cell (-1: none)  [16] n_free  [17] index of G in the free list (-1: none)  [18 ..] free cells, ascending
+// The reference's map (maze_environment.py:18-25) is this same block, built at compile time (kDefaultMaze in env.hip); a
+// null config means it.
+constexpr int kCfgHdr = 8, kRecHdr = 18;
+constexpr int kMazeRandomStart = 1, kMazeRandomGoal = 2, kMazeShowGoal = 4;
+// counter word 2 of a reset draw: far above any stream id PhiloxDraws hands out (2, 3, ...), so a configured maze's
+// reset draws take nothing from a run's action and replay streams
+constexpr uint32_t kMazeResetStream = 0x4D415A45u;
+
+// The Philox words of global actor g's reset into episode `ep`: word 0 draws the goal, word 1 the start, word 2 the
+// first-person heading.
+__device__ __forceinline__ void maze_reset_draw(const int* cfg, int g, int ep, uint32_t (&u)[4]) {
+  const uint64_t seed = (uint64_t)(uint32_t)cfg[4] | ((uint64_t)(uint32_t)cfg[5] << 32);
+  philox4x32_10(seed, (uint64_t)(uint32_t)g | ((uint64_t)(uint32_t)ep << 32), kMazeResetStream, u);
+}
+
+// Goal and start cells of global actor g's episode `ep` (a pure function of seed, g, ep): the goal from G or uniform over
+// the free cells, drawn first; the start from S or uniform over the free cells other than the goal.
+__device__ __forceinline__ void maze_reset_cells(const int* cfg, const int* rec, int g, int ep, int& goal, int& start) {
+  const int flags = cfg[2];
+  uint32_t u[4] = {0, 0, 0, 0};
+  if (flags & (kMazeRandomStart | kMazeRandomGoal)) maze_reset_draw(cfg, g, ep, u);
+  const int nf = rec[16];
+  int gi = rec[17];
+  goal = rec[15];
+  if (flags & kMazeRandomGoal) {
+    gi = (int)(u[0] % (uint32_t)nf);
+    goal = rec[kRecHdr + gi];
+  }
+  start = rec[14];
+  if (flags & kMazeRandomStart) {
+    const int j = (int)(u[1] % (uint32_t)max(nf - 1, 1));        // (nf >= 2: MazeConfig checks it)
+    start = rec[kRecHdr + (j < gi ? j : j + 1)];
+  }
+}
+
+__device__ __forceinline__ const int* maze_rec(const int* cfg, int lay) { return cfg + kCfgHdr + lay * cfg[6]; }
+__device__ __forceinline__ int maze_layout(const int* cfg, const int* layout, int b) {
+  return layout ? min(max(layout[b], 0), cfg[1] - 1) : 0;
+}
+
+}  // namespace

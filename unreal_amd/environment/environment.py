@@ -33,14 +33,17 @@ class Environment(object):
 
     @staticmethod
     def register_maze_config(env_name, layouts, random_start=False, random_goal=False, show_goal=False,
-                             max_episode_steps=0):
+                             max_episode_steps=0, view="top_down", start_heading=None):
         """Mazes of `env_name`: `layouts` = N x N maps (strings, or lists of row strings; + wall, - free, S start, G goal),
         N in {7, 12, 14, 21}, up to 1024 of them; global actor g runs layout g * L // (all actors).  random_start /
         random_goal: drawn at every reset, uniformly over the free cells (the start never on the goal); show_goal: the
         goal block in channel 2; max_episode_steps > 0: an episode that has not reached the goal ends (terminal) at
-        that step.  Raises ValueError on a malformed config."""
+        that step.  view="first_person": a raycast 84 x 84 camera in the agent's cell (actions turn left / right, step
+        forward / back), start_heading None (drawn at every reset) or 0..3.  Raises ValueError on a malformed
+        config."""
         from .maze_environment import MazeConfig
-        Environment.MAZE_CONFIG[env_name] = MazeConfig(layouts, random_start, random_goal, show_goal, max_episode_steps)
+        Environment.MAZE_CONFIG[env_name] = MazeConfig(layouts, random_start, random_goal, show_goal, max_episode_steps,
+                                                       view, start_heading)
 
     @staticmethod
     def create_environment(env_type, env_name, termination_time=50.0, env_args=None, thread_index=0):

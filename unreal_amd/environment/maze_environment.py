@@ -6,7 +6,9 @@ replay ring; `MazeEnvironment` is the reference's batch-1 object surface over th
 `last_action`, `last_reward`), with the adapter semantics of SURVEY H1 (`flag` ignored).
 
 `MazeConfig` describes user mazes (Environment.register_maze_config): N x N layouts in the reference map's alphabet, optional
-random start / goal cells drawn at every reset, an optional goal block in channel 2 and an optional episode step limit."""
+random start / goal cells drawn at every reset, an optional goal block in channel 2 and an optional episode step limit.
+With view="first_person" the same mazes are seen through a raycast camera (`FirstPersonMazeEnvironment`, maze_fp.hip);
+`batched_maze_environment` picks the class from the config."""
 from collections import deque
 
 import numpy as np
@@ -31,8 +33,10 @@ class MazeConfig(object):
     MAX_LAYOUTS = 1024
     RANDOM_START, RANDOM_GOAL, SHOW_GOAL = 1, 2, 4
     HEADER, RECORD_HEADER = 8, 18
+    VIEWS = ("top_down", "first_person")
 
-    def __init__(self, layouts, random_start=False, random_goal=False, show_goal=False, max_episode_steps=0):
+    def __init__(self, layouts, random_start=False, random_goal=False, show_goal=False, max_episode_steps=0,
+                 view="top_down", start_heading=None):
         if isinstance(layouts, str) or not len(layouts):
             raise ValueError("layouts: a non-empty list of layouts (strings, or lists of row strings)")
         if len(layouts) > self.MAX_LAYOUTS:
@@ -42,6 +46,16 @@ class MazeConfig(object):
             raise ValueError("max_episode_steps %r: an integer in [0, 2**31 - 1] (0: no limit; the kernels count steps "
                              "in int32)" % (max_episode_steps,))
         self.max_episode_steps = int(max_episode_steps)
+        if view not in self.VIEWS:
+            raise ValueError("view %r: one of %s" % (view, self.VIEWS))
+        if start_heading is not None:
+            if view != "first_person":
+                raise ValueError("start_heading is a first-person setting; view is %r" % (view,))
+            if isinstance(start_heading, bool) or int(start_heading) != start_heading or not 0 <= start_heading <= 3:
+                raise ValueError("start_heading %r: None (drawn at every reset) or 0..3 (0: +x, 1: +y, 2: -x, 3: -y)"
+                                 % (start_heading,))
+            start_heading = int(start_heading)
+        self.view, self.start_heading = view, start_heading
         self.layouts = [self._parse(i, lay) for i, lay in enumerate(layouts)]
         sizes = set(int(round(len(m) ** 0.5)) for m in self.layouts)
         if len(sizes) != 1:
@@ -102,13 +116,15 @@ class MazeConfig(object):
             (self.SHOW_GOAL * self.show_goal)
 
     def block(self, seed):
-        """-> int32 numpy array: header [N, L, flags, max_episode_steps, seed lo, seed hi, record words, 0], then per
+        """-> int32 numpy array: header [N, L, flags, max_episode_steps, seed lo, seed hi, record words, start heading + 1
+        (first person with a fixed heading; else 0)], then per
         layout [wall bits of cell y*N+x as 7 x (lo, hi) uint32, S cell, G cell, n_free, index of G in the free list,
         free cells ascending] (-1: none)."""
         N, rec = self.N, self.RECORD_HEADER + self.N * self.N
         seed = int(seed) & (2 ** 64 - 1)
         out = np.zeros(self.HEADER + self.L * rec, dtype=np.int64)
-        out[:8] = [N, self.L, self.flags, self.max_episode_steps, seed & 0xFFFFFFFF, seed >> 32, rec, 0]
+        heading = 0 if self.start_heading is None else self.start_heading + 1
+        out[:8] = [N, self.L, self.flags, self.max_episode_steps, seed & 0xFFFFFFFF, seed >> 32, rec, heading]
         for l in range(self.L):
             r = out[self.HEADER + l * rec:self.HEADER + (l + 1) * rec]
             bits = np.zeros(448, dtype=np.int64)
@@ -194,6 +210,51 @@ class BatchedMazeEnvironment(object):
         pass
 
 
+class FirstPersonMazeEnvironment(BatchedMazeEnvironment):
+    """B first-person views of a configured maze (MazeConfig(view="first_person")), stepped by the maze_fp.hip kernels:
+    actions 0 turn left, 1 turn right, 2 step forward, 3 step back; frames are raycast RGB bytes 0..255."""
+    frame_scale = 1.0 / 255.0          # ring bytes 0..255, read like Lab's obs / 255
+
+    def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0):
+        if config is None or config.view != "first_person":
+            raise ValueError("FirstPersonMazeEnvironment needs a MazeConfig with view='first_person'")
+        BatchedMazeEnvironment.__init__(self, batch, history_size, device, config, actor_base, actors_total, seed)
+
+    def view(self, b0, b1):
+        v = BatchedMazeEnvironment.view(self, b0, b1)
+        v.__class__ = FirstPersonMazeEnvironment
+        return v
+
+    def reset(self, mask=None):
+        ops.maze_fp_reset(self.ring, mask, maze=self.maze)
+
+    def process(self, actions, active=None, out_reward=None, out_terminal=None, reset_on_terminal=True,
+                track_score=False):
+        ops.maze_fp_step(self.ring, actions, active, out_reward, out_terminal, reset_on_terminal, track_score,
+                         maze=self.maze)
+
+    def rollout_step(self, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
+                     index_parent=False, **nxt):
+        ops.maze_fp_rollout_step(self.ring, actions, out_reward, out_terminal, active, active_log_t, n_steps,
+                                 terminal_end, base_actor=getattr(self, "base_actor", 0) if index_parent else 0,
+                                 maze=self.maze, **nxt)
+
+    def policy_rollout_step(self, net, feat, ld, u, pi_out, v_out, actions, out_reward, out_terminal, active, active_log_t,
+                            n_steps, terminal_end, index_parent=False, **nxt):
+        p = net.p
+        ops.maze_fp_policy_rollout_step(self.ring, feat, ld, p["W_base_fc_p"], p["b_base_fc_p"], p["W_base_fc_v"],
+                                        p["b_base_fc_v"], u, pi_out, v_out, actions, out_reward, out_terminal, active,
+                                        active_log_t, n_steps, terminal_end,
+                                        base_actor=getattr(self, "base_actor", 0) if index_parent else 0,
+                                        maze=self.maze, **nxt)
+
+
+def batched_maze_environment(batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0):
+    """The batched maze environment of `config` (None: the reference's map): first-person or top-down, by config.view."""
+    cls = FirstPersonMazeEnvironment if config is not None and config.view == "first_person" else BatchedMazeEnvironment
+    return cls(batch, history_size, device, config=config, actor_base=actor_base, actors_total=actors_total, seed=seed)
+
+
 class MazeEnvironment(environment.Environment):
     @staticmethod
     def get_action_size():
@@ -201,7 +262,7 @@ class MazeEnvironment(environment.Environment):
 
     def __init__(self, device="cuda:0", config=None, seed=0):
         environment.Environment.__init__(self)
-        self._env = BatchedMazeEnvironment(1, 2, device, config=config, seed=seed)
+        self._env = batched_maze_environment(1, 2, device, config=config, seed=seed)
         self._a = torch.zeros(1, dtype=torch.int32, device=device)
         self._r = torch.zeros(1, dtype=torch.float32, device=device)
         self._t = torch.zeros(1, dtype=torch.int32, device=device)
@@ -211,7 +272,9 @@ class MazeEnvironment(environment.Environment):
         ring = self._env.ring
         slot = int(ring.count.cpu()[0]) % ring.H1
         fr = ring.frames[slot * ops.FRAME_BYTES:(slot + 1) * ops.FRAME_BYTES]
-        return fr.cpu().numpy().reshape(84, 84, 3).astype(np.float64)
+        img = fr.cpu().numpy().reshape(84, 84, 3).astype(np.float64)
+        # the pixel values (top-down 0 / 1; first person bytes / 255)
+        return img if self._env.frame_scale == 1.0 else img / round(1.0 / self._env.frame_scale)
 
     def reset(self):
         self._env.reset()

@@ -11,7 +11,7 @@ the config sets no limit."""
 import torch
 
 from . import ops
-from .environment.maze_environment import BatchedMazeEnvironment
+from .environment.maze_environment import batched_maze_environment
 from .model.model import PathWS
 from .train.trainer import PhiloxDraws
 
@@ -30,7 +30,7 @@ class Evaluate(object):
                 if maze not in Environment.MAZE_CONFIG:
                     raise KeyError("maze %r: call Environment.register_maze_config(name, layouts, ...) first" % maze)
                 self.maze_config = Environment.MAZE_CONFIG[maze]
-            self.env = BatchedMazeEnvironment(B, 2, self.device, config=self.maze_config, seed=seed)
+            self.env = batched_maze_environment(B, 2, self.device, config=self.maze_config, seed=seed)
         else:
             from .environment.hostfed_environment import HostFedEnvironment
             if tuple(getattr(simulator, "image_shape", (84, 84))) != tuple(network.image_shape):

@@ -127,6 +127,8 @@ class Ring(object):
         self.layout = z(B, dt=torch.int32) if maze_state else None
         self.ep_steps = z(B, dt=torch.int32) if maze_state else None
         self.episode = torch.full((B,), -1, dtype=torch.int32, device=device) if maze_state else None
+        # first-person views (MazeConfig(view="first_person")): heading 0: +x, 1: +y, 2: -x, 3: -y
+        self.heading = z(B, dt=torch.int32) if maze_state else None
 
         self._cur = z(B, dt=torch.int32)
 
@@ -155,7 +157,7 @@ def ring_view(ring, b0, b1):
     for name in ("last_action", "last_reward", "count", "episode_reward", "score_out", "score_valid", "_cur"):
         setattr(v, name, getattr(ring, name)[b0:b1])
     v.goal = ring.goal[2 * b0:2 * b1] if ring.goal is not None else None
-    for name in ("layout", "ep_steps", "episode"):
+    for name in ("layout", "ep_steps", "episode", "heading"):
         t = getattr(ring, name)
         setattr(v, name, t[b0:b1] if t is not None else None)
     return v
@@ -234,6 +236,78 @@ def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, act
           ptr(ring.r_last_reward), ptr(ring.r_pc), ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward),
           ptr(ring.score_out), ptr(ring.score_valid), ptr(active), ptr(active_log_t), ptr(n_steps), ptr(terminal_end),
           ptr(next_idx), ptr(next_lar), int(lar_ld), int(lar_col0), int(A), int(base_actor), *_maze_args(ring, maze))
+
+
+def _fp_args(ring, maze):
+    """The trailing arguments of a unreal_maze_fp_* entry (`maze` as for the *_cfg entries; a block is required)."""
+    if maze is None:
+        raise ValueError("a first-person maze needs its configuration block")
+    return _maze_args(ring, maze)
+
+
+def maze_fp_reset(ring, mask=None, maze=None):
+    """First-person view of a configured maze (maze_fp.hip): reset every actor (where mask != 0)."""
+    _chk(mask, "i32", ring.B, "mask", optional=True)
+    _chk(ring.heading, "i32", ring.B, "ring.heading")
+    _call("unreal_maze_fp_reset", ring.B, ring.H1, ptr(mask), ptr(ring.pos), ptr(ring.heading), ptr(ring.last_action),
+          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), *_fp_args(ring, maze))
+
+
+def maze_fp_step(ring, actions, active=None, out_reward=None, out_terminal=None, reset_on_terminal=True,
+                 track_score=False, maze=None):
+    B = ring.B
+    _chk(actions, "i32", B, "actions")
+    _chk(active, "i32", B, "active", optional=True)
+    _chk(out_reward, "f32", B, "out_reward", optional=True)
+    _chk(out_terminal, "i32", B, "out_terminal", optional=True)
+    _chk(ring.heading, "i32", B, "ring.heading")
+    _call("unreal_maze_fp_step", B, ring.H1, ptr(actions), ptr(active), ptr(ring.pos), ptr(ring.heading),
+          ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward),
+          ptr(ring.r_action), ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc),
+          ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid),
+          int(reset_on_terminal), int(track_score), *_fp_args(ring, maze))
+
+
+def maze_fp_rollout_step(ring, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
+                         next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=0, base_actor=0, maze=None):
+    """maze_fp_step + rollout_advance (+ the next step's frame indices / LSTM-input columns), as maze_rollout_step."""
+    B = ring.B
+    _chk(actions, "i32", B, "actions"); _chk(out_reward, "f32", B, "out_reward"); _chk(out_terminal, "i32", B, "out_terminal")
+    for t in (active, active_log_t, n_steps, terminal_end):
+        _chk(t, "i32", B)
+    _chk(next_idx, "i32", B, "next_idx", optional=True)
+    _chk(next_lar, "f32", (B - 1) * lar_ld + lar_col0 + A + 1 if next_lar is not None else None, "next_lar", optional=True)
+    _chk(ring.heading, "i32", B, "ring.heading")
+    _call("unreal_maze_fp_rollout_step", B, ring.H1, ptr(actions), ptr(ring.pos), ptr(ring.heading), ptr(ring.last_action),
+          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward), ptr(ring.r_action),
+          ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc), ptr(out_reward),
+          ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid), ptr(active),
+          ptr(active_log_t), ptr(n_steps), ptr(terminal_end), ptr(next_idx), ptr(next_lar), int(lar_ld), int(lar_col0),
+          int(A), int(base_actor), *_fp_args(ring, maze))
+
+
+def maze_fp_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions, out_reward, out_terminal,
+                                active, active_log_t, n_steps, terminal_end, next_idx=None, next_lar=None, lar_ld=0,
+                                lar_col0=0, A=4, base_actor=0, maze=None):
+    """policy_step + maze_fp_rollout_step in one launch (bit-identical to the two launches)."""
+    B = ring.B
+    if A != 4:
+        raise ValueError("the maze has 4 actions")
+    _chk(X, "f32", (B - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A); _chk(bp, "f32", A); _chk(Wv, "f32", 256)
+    _chk(bv, "f32", 1); _chk(u, "f64", B, "u"); _chk(pi_out, "f32", B * A); _chk(v_out, "f32", B)
+    _chk(actions, "i32", B, "actions"); _chk(out_reward, "f32", B, "out_reward"); _chk(out_terminal, "i32", B, "out_terminal")
+    for t in (active, active_log_t, n_steps, terminal_end):
+        _chk(t, "i32", B)
+    _chk(next_idx, "i32", B, "next_idx", optional=True)
+    _chk(next_lar, "f32", (B - 1) * lar_ld + lar_col0 + A + 1 if next_lar is not None else None, "next_lar", optional=True)
+    _chk(ring.heading, "i32", B, "ring.heading")
+    _call("unreal_maze_fp_policy_rollout_step", B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(u),
+          ptr(pi_out), ptr(v_out), ptr(actions), ptr(ring.pos), ptr(ring.heading), ptr(ring.last_action),
+          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward), ptr(ring.r_action),
+          ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc), ptr(out_reward),
+          ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid), ptr(active),
+          ptr(active_log_t), ptr(n_steps), ptr(terminal_end), ptr(next_idx), ptr(next_lar), int(lar_ld), int(lar_col0),
+          int(A), int(base_actor), *_fp_args(ring, maze))
 
 
 def pixel_change_u8(frames, idx_new, idx_old, denom, out):

@@ -30,7 +30,7 @@ import torch
 
 from .. import ops
 from ..environment.environment import Environment
-from ..environment.maze_environment import BatchedMazeEnvironment
+from ..environment.maze_environment import batched_maze_environment
 from ..model.model import UnrealModel, PathWS, GradWS
 from .experience import Experience
 
@@ -147,10 +147,10 @@ class Trainer(object):
         if self.env_type == "maze":
             # a registered maze config (Environment.register_maze_config): layouts and reset draws follow the GLOBAL actor
             # index, so a job over W ranks runs what one process with all W * B actors would
-            self.environment = BatchedMazeEnvironment(B, self.experience_history_size, dev,
-                                                      config=Environment.MAZE_CONFIG.get(self.env_name),
-                                                      actor_base=self.rank * B, actors_total=self.world_size * B,
-                                                      seed=self.seed)
+            self.environment = batched_maze_environment(B, self.experience_history_size, dev,
+                                                        config=Environment.MAZE_CONFIG.get(self.env_name),
+                                                        actor_base=self.rank * B, actors_total=self.world_size * B,
+                                                        seed=self.seed)
         else:
             from ..environment.hostfed_environment import HostFedEnvironment
             indoor = self.env_type == "indoor"
