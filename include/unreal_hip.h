@@ -33,12 +33,37 @@ extern "C" {
 #define UNREAL_GEMM_RELU_BITS 16   /* split_nt only: mask = uint16 bit words (unreal_encoder_fwd relu_bits), ldm in words */
 
 /* ---- environment (environment/maze_environment.py:50-55,98-128; environment/environment.py:88-102;
- *      train/experience.py:63-93 add_frame; train/trainer.py:194-205,264-296 reset rules) ---------- */
-int unreal_maze_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
-                     float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
-                     int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc,
-                     float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
-                     int* score_valid, int reset_on_terminal, int track_score, void* stream);
+ *      train/experience.py:63-93 add_frame; train/trainer.py:194-205,264-296 reset rules) ----------
+ * The maze (csrc/maze.hip).  Every maze entry ends in the same maze tail (view, N, cfg, actor_base, goal, layout,
+ * ep_steps, episode, heading), in one of three forms:
+ *   view 0, cfg NULL   the reference's 7 x 7 map, top-down (N must be 7; goal .. heading are not used)
+ *   view 0, cfg block  a configured maze, top-down (environment/maze_environment.py MazeConfig)
+ *   view 1, cfg block  a configured maze in first person (MazeConfig(view="first_person")); cfg NULL is EINVAL
+ * `cfg` is the configuration block (int32 words: N, layouts, flags, max_episode_steps, seed, start heading + 1; per
+ * layout the wall bits, S / G cells and free-cell list); with a block, goal[2B] (x, y), layout[B], ep_steps[B] and
+ * episode[B] (-1 before the first reset) are the per-actor state of the configured maze and are required, and so is
+ * heading[B] (0: +x, 1: +y, 2: -x, 3: -y) in first person.  N in {7, 12, 14, 21} must be the block's grid size (word 0):
+ * the block lives in device memory, so the entry cannot read it, and a kernel whose N differs from the block's writes
+ * nothing at all (no frame, no state) rather than index a frame with the wrong cell size -- the call still returns 0.
+ * Reset draws are Philox4x32-10 with key = the block's seed and counter = (actor_base + b, episode, 0x4D415A45, 0); word 2
+ * draws the first-person start heading when the block's word 7 is 0.
+ * First person: actions 0 turn left, 1 turn right, 2 step forward, 3 step back; frames are the raycast 84 x 84 RGB view
+ * (bytes 0..255, read at scale 1/255) and r_pc is the pixel change of the two frames over 48 * 255, as
+ * unreal_pixel_change_u8.  `frames` must be 16-byte aligned; every pointer an entry writes through is required. */
+#define UNREAL_MAZE_TOP_DOWN 0
+#define UNREAL_MAZE_FIRST_PERSON 1
+/* env.reset() of every actor where mask[b] != 0 (mask nullable) */
+int unreal_maze_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward, const int* count,
+                      uint8_t* frames, int view, int N, const int* cfg, int actor_base, int* goal, int* layout,
+                      int* ep_steps, int* episode, int* heading, void* stream);
+/* environment.process + experience.add_frame of every actor where active[b] != 0 (active, out_reward, out_terminal
+ * nullable; episode_reward / score_out / score_valid required with track_score) */
+int unreal_maze_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action, float* last_reward,
+                     int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal, int* r_last_action,
+                     float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                     float* score_out, int* score_valid, int reset_on_terminal, int track_score, int view, int N,
+                     const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps, int* episode, int* heading,
+                     void* stream);
 /* the same step with the rollout loop's bookkeeping (train/trainer.py:236-296) in the same launch: `active` is read
  * AND updated (an actor leaves the rollout at its terminal, the reference's `break`), active_log_t / n_steps /
  * terminal_end as unreal_rollout_advance writes them, next_idx = ring index of every actor's next observation
@@ -47,91 +72,26 @@ int unreal_maze_step(int B, int H1, const int* actions, const int* active, int* 
 int unreal_maze_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward, int* count,
                              uint8_t* frames, float* r_reward, int* r_action, int* r_terminal, int* r_last_action,
                              float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
-                             float* episode_reward, float* score_out, int* score_valid, int* active,
-                             int* active_log_t, int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
-                             float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A,
+                             float* episode_reward, float* score_out, int* score_valid, int* active, int* active_log_t,
+                             int* n_steps, int* terminal_end, int* next_idx /*nullable*/, float* next_lar /*nullable*/,
+                             int lar_ld, int lar_col0, int A,
                              int idx_base_actor /* next_idx[b] = (idx_base_actor + b) * H1 + slot: a half-batch whose
-                                                   rows index the whole ring */, void* stream);
+                                                   rows index the whole ring */,
+                             int view, int N, const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps,
+                             int* episode, int* heading, void* stream);
 /* unreal_policy_step + unreal_maze_rollout_step in ONE launch (trainer.py:236-296: run_base_policy_and_value, choose_action,
  * environment.process of one rollout step): the workgroup that steps an actor first computes its pi / V from the feature row
  * X[b] (K = 256) and draws its action from u[b] -- bit-identical to the two-launch path.  A must be 4 (the maze). */
-int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp, const float* Wv,
-                                    const float* bv, const double* u, float* pi_out, float* v_out, int* actions_out, int* pos,
-                                    int* last_action, float* last_reward, int* count, uint8_t* frames, float* r_reward,
-                                    int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc,
-                                    float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
-                                    int* score_valid, int* active, int* active_log_t, int* n_steps, int* terminal_end,
-                                    int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A,
-                                    int idx_base_actor, void* stream);
-int unreal_maze_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
-                      const int* count, uint8_t* frames, void* stream);
-/* configured mazes (environment/maze_environment.py MazeConfig): the four maze entries above with a configuration block
- * `cfg` (int32 words: N, layouts, flags, max_episode_steps, seed; per layout the wall bits, S / G cells and free-cell list)
- * and the per-actor state of a configured maze: goal[2B] (x, y), layout[B], ep_steps[B], episode[B] (-1 before the first
- * reset).  N in {7, 12, 14, 21} must be the block's grid size (word 0): the block lives in device memory, so the entry
- * cannot read it, and a kernel whose N differs from the block's writes nothing at all (no frame, no state) rather than
- * index a frame with the wrong cell size -- the call still returns 0.  Reset draws are Philox4x32-10 with key = the block's seed and
- * counter = (actor_base + b, episode, 0x4D415A45, 0).  cfg = NULL: the reference's map (N must be 7; the arrays are not
- * used), exactly what the entries above do. */
-int unreal_maze_step_cfg(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
-                         float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
-                         int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc,
-                         float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
-                         int* score_valid, int reset_on_terminal, int track_score, int N, const int* cfg,
-                         int actor_base, int* goal, int* layout, int* ep_steps, int* episode, void* stream);
-int unreal_maze_rollout_step_cfg(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
-                                 int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
-                                 int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                                 int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
-                                 int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
-                                 float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A, int idx_base_actor, int N,
-                                 const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps, int* episode,
-                                 void* stream);
-int unreal_maze_policy_rollout_step_cfg(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
-                                        const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
-                                        int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
-                                        uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
-                                        int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                                        int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
-                                        int* active, int* active_log_t, int* n_steps, int* terminal_end,
-                                        int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0,
-                                        int A, int idx_base_actor, int N, const int* cfg, int actor_base, int* goal,
-                                        int* layout, int* ep_steps, int* episode, void* stream);
-int unreal_maze_reset_cfg(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
-                          const int* count, uint8_t* frames, int N, const int* cfg, int actor_base, int* goal, int* layout,
-                          int* ep_steps, int* episode, void* stream);
-/* first-person views of configured mazes (MazeConfig(view="first_person"); maze_fp.hip): the *_cfg entries
- * with a per-actor heading[B] (0: +x, 1: +y, 2: -x, 3: -y) after pos.  Actions: 0 turn left, 1 turn right, 2 step forward,
- * 3 step back.  Frames are the raycast 84 x 84 RGB view (bytes 0..255, read at scale 1/255); r_pc is the pixel change of
- * the two frames over 48 * 255, as unreal_pixel_change_u8.  `cfg` is required (word 7: start heading + 1, 0 = drawn from
- * Philox word 2 of the reset draw); a block whose N differs from the entry's makes the kernel write nothing. */
-int unreal_maze_fp_reset(int B, int H1, const int* mask, int* pos, int* heading, int* last_action, float* last_reward,
-                         const int* count, uint8_t* frames, int N, const int* cfg, int actor_base, int* goal, int* layout,
-                         int* ep_steps, int* episode, void* stream);
-int unreal_maze_fp_step(int B, int H1, const int* actions, const int* active, int* pos, int* heading, int* last_action,
-                        float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
-                        int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
-                        float* episode_reward, float* score_out, int* score_valid, int reset_on_terminal,
-                        int track_score, int N, const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps,
-                        int* episode, void* stream);
-int unreal_maze_fp_rollout_step(int B, int H1, const int* actions, int* pos, int* heading, int* last_action,
-                                float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
-                                int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                                int* out_terminal, float* episode_reward, float* score_out, int* score_valid, int* active,
-                                int* active_log_t, int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
-                                float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A, int idx_base_actor, int N,
-                                const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps, int* episode,
-                                void* stream);
-int unreal_maze_fp_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
-                                       const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
-                                       int* actions_out, int* pos, int* heading, int* last_action, float* last_reward,
-                                       int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
-                                       int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                                       int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
-                                       int* active, int* active_log_t, int* n_steps, int* terminal_end,
-                                       int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0,
-                                       int A, int idx_base_actor, int N, const int* cfg, int actor_base, int* goal,
-                                       int* layout, int* ep_steps, int* episode, void* stream);
+int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                    const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                    int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
+                                    uint8_t* frames, float* r_reward, int* r_action, int* r_terminal, int* r_last_action,
+                                    float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                                    float* episode_reward, float* score_out, int* score_valid, int* active,
+                                    int* active_log_t, int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
+                                    float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                                    int view, int N, const int* cfg, int actor_base, int* goal, int* layout,
+                                    int* ep_steps, int* episode, int* heading, void* stream);
 /* host-fed environments (environment/lab_environment.py:78-119 contract): `staged` holds one uint8
  * frame per actor (post-reset observation where terminals[b] != 0) */
 int unreal_hostfed_step(int B, int H1, const uint8_t* staged, const int* actions, const float* rewards,

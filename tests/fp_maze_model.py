@@ -1,6 +1,6 @@
 """Host model of the first-person maze view (numpy, integer arithmetic).  TEST INFRASTRUCTURE ONLY.
 
-Restates DESIGN §7e independently of maze_fp.hip.  The state is a cell (x, y) and a heading h (0: +x, 1: +y, 2: -x,
+Restates DESIGN §7e independently of maze.hip.  The state is a cell (x, y) and a heading h (0: +x, 1: +y, 2: -x,
 3: -y); actions 0 / 1 turn left / right, 2 / 3 step forward / back (a step into a wall or off the map stays: reward -1);
 the goal is terminal with +1 and max_episode_steps works as in tests/maze_model.py.  Resets draw goal and start exactly as
 the top-down maze (maze_model.reset_cells) and, with start_heading None, the heading as word 2 of the same draw, mod 4.

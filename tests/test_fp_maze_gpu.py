@@ -1,5 +1,5 @@
-"""First-person views of configured mazes on the device (maze_fp.hip, unreal_maze_fp_*) against the host model of
-tests/fp_maze_model.py, the two-launch paths, OracleTrainer and the top-down maze."""
+"""First-person views of configured mazes on the device (maze.hip, the unreal_maze_* entries with view 1) against the
+host model of tests/fp_maze_model.py, the two-launch paths, OracleTrainer and the top-down maze."""
 import numpy as np
 import pytest
 import torch

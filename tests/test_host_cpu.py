@@ -36,13 +36,21 @@ def test_library_exports_every_declared_symbol(built):
     assert exported == set(protos), exported ^ set(protos)
 
 
-def test_invalid_arguments_are_rejected_without_launch(built):
+def test_invalid_arguments_and_maze_tails_are_rejected_without_launch(built):
     from unreal_amd import _lib
     L = _lib.lib()
     with pytest.raises(_lib.UnrealLibError):
         L.call("unreal_gemm_f32", 0, 0, 0, 4, 4, None, 4, None, 4, None, 4, None, None, 0, 0, 1, None)
     with pytest.raises(_lib.UnrealLibError):
-        L.call("unreal_maze_step", 0, 3, *([None] * 18), 1, 0, None)
+        L.call("unreal_maze_step", 0, 3, *([None] * 18), 1, 0, 0, 7, None, 0, *([None] * 5), None)
+    # a well-formed step except for its maze tail (view, N, cfg, actor_base, goal, layout, ep_steps, episode, heading):
+    # refused on the host, so these fake device pointers never reach a kernel
+    dev = 1 << 20
+    step = [4, 3, dev, None] + [dev] * 11 + [None, None] + [dev] * 3 + [1, 1]
+    for tail in ([1, 7, None, 0] + [dev] * 5,           # first person needs a configuration block
+                 [2, 7, dev, 0] + [dev] * 5,            # no such view
+                 [0, 12, None, 0] + [None] * 5):        # the reference's map is 7 x 7
+        assert L._fn["unreal_maze_step"](*step, *tail, None) == -22, tail
     with pytest.raises(_lib.UnrealLibError):
         L.call("unreal_rmsprop_step", None, None, None, None, 10, 0.1, 0.9, 0.0, 0.1, 40.0, None, None)
 

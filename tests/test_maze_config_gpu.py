@@ -1,5 +1,5 @@
-"""Configured mazes on the device (Environment.register_maze_config, unreal_maze_*_cfg) against the reference map's
-null-config path and the host model of tests/maze_model.py."""
+"""Configured mazes on the device (Environment.register_maze_config: a config block in the unreal_maze_* entries) against
+the reference map's null-config path and the host model of tests/maze_model.py."""
 import numpy as np
 import pytest
 import torch
@@ -42,8 +42,8 @@ def _current_frames(ring):
 
 @pytest.mark.parametrize("B", [3, 64, 512, 4096])
 def test_reference_map_through_the_cfg_path_is_the_default(B):
-    """The reference's map registered as a config (the *_cfg entries, a config block in device memory) steps and renders
-    bit for bit like the null-config kernels, at every actors-per-workgroup tier."""
+    """The reference's map registered as a config (a config block in device memory) steps and renders bit for bit like
+    the null-config kernels, at every actors-per-workgroup tier."""
     from unreal_amd import ops
     from unreal_amd.environment.maze_environment import MazeConfig
     H = 3
@@ -169,8 +169,8 @@ def test_configured_maze_matches_the_host_model(N, B, steps, random, marks):
 
 @pytest.mark.parametrize("B", [64, 1025])
 def test_fused_policy_step_on_a_configured_maze_is_the_two_launch_path(B):
-    """unreal_maze_policy_rollout_step_cfg == unreal_policy_step + unreal_maze_rollout_step_cfg, bit for bit, with time-outs
-    and goals ending episodes on the way."""
+    """unreal_maze_policy_rollout_step == unreal_policy_step + unreal_maze_rollout_step on a configured maze, bit for
+    bit, with time-outs and goals ending episodes on the way."""
     from unreal_amd import ops
     H, A, xld = 4, 4, 264
     rs = np.random.RandomState(B)

@@ -39,8 +39,7 @@ def kernel_ms(env, B, launches):
     t = torch.zeros(B, dtype=torch.int32, device=DEV)
     for k in range(10):
         env.process(acts[k % 8], None, r, t, track_score=True)
-    name = "unreal_maze_fp_step" if env.frame_scale != 1.0 else "unreal_maze_step_cfg"
-    ops.kernel_timer_start(name)
+    ops.kernel_timer_start("unreal_maze_step")
     for k in range(launches):
         env.process(acts[k % 8], None, r, t, track_score=True)
     res = ops.kernel_timer_stop()

@@ -13,6 +13,7 @@
 // step IS the terminal observation, so that step's pixel change is taken against it; the ring slot after it receives
 // the post-reset observation the trainer's env.reset() obtains.  Rewards are stored raw (this fork's train/experience.py).
 #include "common.h"
+#include "ring_step.h"
 
 namespace {
 
@@ -85,55 +86,30 @@ __global__ __launch_bounds__(256) void gym_step_kernel(GymStepArgs p) {
   const int cnt = p.count[b];
   const int la = p.last_action[b];
   const float lr = p.last_reward[b];
-  const int slot = cnt % H1;
   const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
-  float ep = p.track_score ? p.episode_reward[b] : 0.f;
+  const float ep = p.track_score ? p.episode_reward[b] : 0.f;
   __syncthreads();
-  const size_t base = (size_t)b * H1 + slot;
+  const RingStep s = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
   const uint8_t* fnew = p.staged + (size_t)b * FRAME_BYTES;
-  const uint8_t* fold = p.frames + base * FRAME_BYTES;
+  const uint8_t* fold = p.frames + s.base * FRAME_BYTES;
   for (int c = threadIdx.x; c < PC_CELLS; c += blockDim.x) {     // terminal steps included (gym_environment.py:86)
     const int i = c / 20, j = c - i * 20;
-    int s = 0;
+    int sum = 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int off = (4 * i + 2 + r) * FRAME_ROW_BYTES + (4 * j + 2) * 3;
 #pragma unroll
-      for (int k = 0; k < 12; ++k) s += abs((int)fnew[off + k] - (int)fold[off + k]);
+      for (int k = 0; k < 12; ++k) sum += abs((int)fnew[off + k] - (int)fold[off + k]);
     }
-    p.r_pc[base * PC_CELLS + c] = (float)s / p.pc_denom;
+    p.r_pc[s.base * PC_CELLS + c] = (float)sum / p.pc_denom;
   }
-  const bool discard = terminal && cnt > 0 && prev_term;     // successive terminals (experience.py:63-93)
-  const int ncnt = discard ? cnt : cnt + 1;
-  const bool reset = terminal && p.reset_on_terminal;
-  const int nslot = ncnt % H1;
   __syncthreads();   // pixel change has read the old frame before a discard could overwrite the same slot
   {
-    const uint4* s4 = reinterpret_cast<const uint4*>(reset ? p.reset_staged + (size_t)b * FRAME_BYTES : fnew);
-    uint4* d4 = reinterpret_cast<uint4*>(p.frames + ((size_t)b * H1 + nslot) * FRAME_BYTES);
+    const uint4* s4 = reinterpret_cast<const uint4*>(s.reset ? p.reset_staged + (size_t)b * FRAME_BYTES : fnew);
+    uint4* d4 = reinterpret_cast<uint4*>(p.frames + ((size_t)b * H1 + s.nslot) * FRAME_BYTES);
     for (int c = threadIdx.x; c < FRAME_BYTES / 16; c += blockDim.x) d4[c] = s4[c];
   }
-  if (threadIdx.x == 0) {
-    p.r_reward[base] = reward;
-    p.r_action[base] = a;
-    p.r_terminal[base] = terminal ? 1 : 0;
-    p.r_last_action[base] = la;
-    p.r_last_reward[base] = lr;
-    p.count[b] = ncnt;
-    p.last_action[b] = reset ? 0 : a;
-    p.last_reward[b] = reset ? 0.f : reward;
-    if (p.out_reward) p.out_reward[b] = reward;
-    if (p.out_terminal) p.out_terminal[b] = terminal ? 1 : 0;
-    if (p.track_score) {
-      ep += reward;
-      if (terminal) {
-        p.score_out[b] = ep;
-        p.score_valid[b] = 1;
-        ep = 0.f;
-      }
-      p.episode_reward[b] = ep;
-    }
-  }
+  if (threadIdx.x == 0) ring_commit(p, b, s, a, reward, reward, la, lr, ep);     // rewards stored raw
 }
 
 }  // namespace

@@ -1,0 +1,783 @@
+// The batched maze environment on the device, top-down and first person, for gfx950: the step and reset kernels of both
+// views and the four unreal_maze_* entries (include/unreal_hip.h).
+//
+// Reference behaviour restated (never copied) from the reference's
+//   environment/maze_environment.py:18-128  (map, _move, _get_current_image, process)
+//   environment/environment.py:88-102       (_calc_pixel_change)
+//   train/experience.py:63-93               (add_frame: ring_step.h)
+//   train/trainer.py:194-205,264-296        (who resets what, and when)
+//
+// Top-down: one workgroup (256 threads) serves 1, 2 or 8 actors; 21,168 B of frame are written per actor with 16 B/lane
+// coalesced stores, so the kernel is a pure HBM-write stream.
+//
+// First person: the same layouts, reset draws and step limit, seen by a camera at the centre of the agent's cell that
+// looks along one of four headings.  Every quantity below is a ratio of small integers compared exactly, so
+// tests/fp_maze_model.py reproduces every byte (DESIGN §7e states the semantics).
+//
+//   state:    cell (x, y) and heading h in {0: +x, 1: +y, 2: -x, 3: -y}; forward d = dir[h], right r = dir[(h + 1) % 4]
+//   actions:  0 turn left, 1 turn right, 2 step forward, 3 step back; a step into a wall or off the map stays (reward -1)
+//   camera:   column i casts W d + q_i r, q_i = 2i + 1 - W (odd; W = 84 even).  Forward cell boundary k is crossed at
+//             t = (2k+1)/2, side boundary m at t = (2m+1) W / (2|q_i|); (2k+1)|q_i| != (2m+1) W (odd vs even), so the DDA
+//             has no ties.  The first wall / off-map cell gives t = tn / td; row y is wall iff |2y+1-H| tn < H td.  Other
+//             rows: ceiling above the horizon, floor below; floor row y (p = 2y+1-H > 0) lies floor((2H+p) / 2p) cells
+//             ahead and floor((2Hq+pW) / 2pW) cells to the side of the eye.
+//   palette:  ceiling 0; floor (40,40,40), the goal tile (40,40,255) with show_goal; interior walls 255 (x-faces) / 160
+//             (y-faces) in channel 0, the map border the same shades in channel 1.
+//
+// One workgroup (256 threads) per actor.  The step renders s_{t+1} into LDS (lanes 0..83: one column's DDA each, over
+// the layout's wall bits in LDS; then every thread fills whole frame-row dwords), streams it to the ring slot with 16 B
+// per lane, turns the LDS image into |new - old| bytes against the stored frame (read at kernel entry, so its latency
+// hides under the render) and sums the 20 x 20 pixel-change cells from there.
+#include "common.h"
+#include "maze_common.h"
+#include "policy_row.h"
+#include "ring_step.h"
+
+namespace {
+
+constexpr int kTopDown = 0, kFirstPerson = 1;      // UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON
+
+// The reference's map as a configuration block (layout: maze_common.h).
+constexpr const char* kMap =
+    "--+---G"
+    "--+-+++"
+    "S-+---+"
+    "--+++--"
+    "--+-+--"
+    "--+----"
+    "-----++";
+
+struct DefaultMaze { int v[kCfgHdr + kRecHdr + 49]; };
+constexpr DefaultMaze make_default_maze() {
+  DefaultMaze m{};
+  m.v[0] = 7; m.v[1] = 1; m.v[6] = kRecHdr + 49;
+  int* r = m.v + kCfgHdr;
+  uint64_t walls = 0;
+  int nf = 0;
+  r[14] = r[15] = r[17] = -1;
+  for (int i = 0; i < 49; ++i) {
+    if (kMap[i] == '+') { walls |= 1ull << i; continue; }
+    if (kMap[i] == 'S') r[14] = i;
+    if (kMap[i] == 'G') { r[15] = i; r[17] = nf; }
+    r[kRecHdr + nf++] = i;
+  }
+  r[0] = (int)(uint32_t)walls; r[1] = (int)(uint32_t)(walls >> 32);
+  r[16] = nf;
+  return m;
+}
+// read at compile time: the null-config path loads nothing of the block
+constexpr DefaultMaze kDefaultMaze = make_default_maze();
+constexpr const int* kDefaultRec = kDefaultMaze.v + kCfgHdr;
+constexpr uint64_t kDefaultWalls = (uint64_t)(uint32_t)kDefaultRec[0] | ((uint64_t)(uint32_t)kDefaultRec[1] << 32);
+constexpr int kDefaultStart = kDefaultRec[14], kDefaultGoal = kDefaultRec[15];
+static_assert(kDefaultStart == 2 * 7 + 0 && kDefaultGoal == 6, "maze constants");
+
+// The wall bits of the layout a workgroup renders: at N = 7 (49 bits) in a uniform register; above, up to 441 bits in
+// LDS (a dynamically indexed register array is placed in scratch).  load() is called by every thread of the workgroup.
+template <int N>
+struct Walls {
+  static constexpr int NW = (N * N + 63) / 64;
+  uint64_t w0;
+  uint64_t* lds;         // NW > 1: the workgroup's copy, NW words
+  __device__ __forceinline__ void load(const int* rec) {     // rec null: the reference map
+    if constexpr (NW == 1) {
+      w0 = rec ? (uint64_t)(uint32_t)rec[0] | ((uint64_t)(uint32_t)rec[1] << 32) : kDefaultWalls;
+    } else {
+      if (threadIdx.x < NW)
+        lds[threadIdx.x] = (uint64_t)(uint32_t)rec[2 * threadIdx.x] | ((uint64_t)(uint32_t)rec[2 * threadIdx.x + 1] << 32);
+      __syncthreads();
+    }
+  }
+  __device__ __forceinline__ uint32_t bit(int cell) const {
+    if constexpr (NW == 1) return (uint32_t)(w0 >> cell) & 1u;
+    else return (uint32_t)(lds[cell >> 6] >> (cell & 63)) & 1u;
+  }
+};
+
+// The frame is the layout's wall image (ch 0) plus the c x c agent block (ch 1) and, with show_goal, the goal block (ch 2),
+// c = 84 / N.  A workgroup builds the wall image ONCE per layout in LDS (the per-byte index arithmetic below is ~250 VALU
+// per 16 bytes: rendering every frame from scratch made the step kernel VALU-bound at 1.6 TB/s) and streams it out for
+// each of its actors; the agent and goal blocks are patched in afterwards.
+constexpr int kActorsPerGroup = 8;
+constexpr int kStepActorsBig = 8;      // actors per workgroup of the step kernel at > 1024 actors
+constexpr int kStepActorsTiny = 1;     // actors per workgroup at <= 64 actors (a small update's rollout step: one actor per workgroup)
+
+template <int N>
+__device__ __forceinline__ void build_wall_image(uint4* img, const Walls<N>& walls) {
+  constexpr int C = FRAME_W / N;
+  for (int c = threadIdx.x; c < FRAME_BYTES / 16; c += blockDim.x) {
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      // a dword never spans two frame rows (252 = 4 * 63); its channel-0 bytes are e0 and, when e0 = 0, byte 3
+      const int q = c * 4 + k, row = q / (FRAME_ROW_BYTES / 4), cb = 4 * q - row * FRAME_ROW_BYTES;
+      const int wrow = (row / C) * N, m = cb % 3, e0 = m == 0 ? 0 : 3 - m;
+      uint32_t v = walls.bit(wrow + (cb + e0) / 3 / C) << (8 * e0);
+      if (e0 == 0) v |= walls.bit(wrow + (cb + 3) / 3 / C) << 24;
+      w[k] = v;
+    }
+    img[c] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
+// caller: __syncthreads() between the two (same workgroup, same addresses: the barrier orders the stores)
+__device__ __forceinline__ void render_walls(uint8_t* dst, const uint4* img) {
+  uint4* d4 = reinterpret_cast<uint4*>(dst);
+  for (int c = threadIdx.x; c < FRAME_BYTES / 16; c += blockDim.x) d4[c] = img[c];
+}
+
+// The dwords of the agent block's rows (and of the goal block's, when shown): each is the wall image's dword with the
+// agent's ch-1 bytes and the goal's ch-2 bytes set.  A block row is 3c bytes at byte 3c*cx of its frame row; at c = 7 and
+// c = 6 it does not start on a dword, so its first and last dwords hold bytes of the neighbouring cells, which come out
+// of the same formula.  A dword both blocks share is written by two threads with the same value.
+template <int N>
+__device__ __forceinline__ void render_blocks(uint8_t* dst, const uint4* img, int ax, int ay, int gx, int gy, bool show_goal) {
+  constexpr int C = FRAME_W / N, RUN = 3 * C;
+  constexpr int DW = RUN % 4 == 0 ? RUN / 4 : RUN / 4 + 2;      // dwords that can cover a run
+  const uint32_t* img32 = reinterpret_cast<const uint32_t*>(img);
+  const int n = (show_goal ? 2 : 1) * C * DW;
+  for (int t = threadIdx.x; t < n; t += blockDim.x) {
+    const int blk = t / (C * DW), r = (t / DW) % C, w = t % DW;
+    const int cx = blk ? gx : ax, cy = blk ? gy : ay;
+    const int d = (RUN * cx) / 4 + w;                              // dword within the frame row (252 B = 63 dwords)
+    if (4 * d > RUN * cx + RUN - 1) continue;
+    const int row = C * cy + r;                                   // (a row of cell row cy: the other block's too when they share it)
+    uint32_t v;
+    if constexpr (RUN % 4 == 0) {
+      // c = 12, 4: the dword lies inside its cell, which is no wall; byte 4w of the run is channel w mod 3 (selects, not a
+      // table: a table went to constant memory, and its load waited for the wave's wall stores of this frame)
+      const int ph = w % 3;
+      const uint32_t ch1 = ph == 0 ? 0x00000100u : (ph == 1 ? 0x01000001u : 0x00010000u);
+      const uint32_t ch2 = ph == 0 ? 0x00010000u : (ph == 1 ? 0x00000100u : 0x01000001u);
+      v = ((cx == ax && cy == ay) ? ch1 : 0u) | ((show_goal && cx == gx && cy == gy) ? ch2 : 0u);
+    } else {
+      v = img32[row * (FRAME_ROW_BYTES / 4) + d];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int pos = 4 * d + e, col = pos / 3, ch = pos - 3 * col, ccol = col / C;
+        const bool on = (ch == 1 && ccol == ax && cy == ay) || (show_goal && ch == 2 && ccol == gx && cy == gy);
+        if (on) v |= 1u << (8 * e);
+      }
+    }
+    reinterpret_cast<uint32_t*>(dst + row * FRAME_ROW_BYTES)[d] = v;
+  }
+}
+
+// pixels of the c x c agent block at cell (cx,cy) inside pixel-change cell (i,j):
+// rows 4i+2..4i+5, cols 4j+2..4j+5 of the full frame (the [2:-2] crop, then 4x4 blocks)
+template <int N>
+__device__ __forceinline__ int overlap1(int cell, int k) {
+  constexpr int C = FRAME_W / N;
+  int lo = max(C * cell, 4 * k + 2), hi = min(C * cell + C - 1, 4 * k + 5);
+  return max(0, hi - lo + 1);
+}
+
+// The arguments of every maze kernel, both views, step and reset.
+struct MazeArgs {
+  int B, H1;
+  const int* actions;
+  const int* active;
+  int* pos;
+  int* last_action;
+  float* last_reward;
+  int* count;
+  uint8_t* frames;
+  float* r_reward;
+  int* r_action;
+  int* r_terminal;
+  int* r_last_action;
+  float* r_last_reward;
+  float* r_pc;
+  float* out_reward;
+  int* out_terminal;
+  float* episode_reward;
+  float* score_out;
+  int* score_valid;
+  int reset_on_terminal;
+  int track_score;
+  // rollout bookkeeping fused into the step (unreal_maze_rollout_step; all null / 0 for the plain step):
+  int* active_rw;        // in: actor still inside its rollout; out: cleared at its terminal (trainer.py:279-296 `break`)
+  int* active_log_t;     // active flag of this step (row mask of the losses)
+  int* n_steps;          // += 1 per step taken
+  int* terminal_end;     // set at the terminal
+  int* next_idx;         // nullable: ring index of the NEXT observation ((idx_base + b) * H1 + slot), also for idle actors
+  float* next_lar;       // nullable: [B][lar_ld] rows of the next step's LSTM input: one-hot last action | last reward
+  int lar_ld, lar_col0, A;
+  int idx_base;          // index of this launch's first actor in the ring next_idx is meant for (a half-batch of a ring)
+  // fused policy step (unreal_maze_policy_rollout_step; pol_x null: the actions are given): the actors' feature rows ->
+  // pi, V and the drawn action, computed by the workgroup that then steps those actors (one launch less per rollout step)
+  const float* pol_x; int pol_ldx;
+  const float* Wp; const float* bp; const float* Wv; const float* bv;
+  const double* pol_u;
+  float* pi_out; float* v_out; int* act_out;
+  // the maze tail: configuration block (null: the reference's map, top-down only, and the arrays below unused)
+  const int* cfg;
+  int actor_base;        // global index of actor 0 of this launch (reset draws are keyed by it)
+  int* goal;             // [2B] goal cell (x, y) of the running episode
+  int* layout;           // [B] layout id
+  int* ep_steps;         // [B] steps taken in the running episode
+  int* episode;          // [B] episode index (-1 before the first reset)
+  int* heading;          // [B] first person: heading of the camera
+  const int* mask;       // reset only (nullable): the actors to reset
+};
+
+// APG actors per workgroup: 8 when the batch fills the chip (the wall image is built once per workgroup: ~2.5 us of VALU),
+// 2 for small batches (grouped updates: 512 actors per launch), where 8 actors in a row per workgroup were 20 of the
+// launch's 23 us and most CUs had no workgroup at all, 1 at <= 64 actors (an 8-actor update: 8 workgroups instead of 4)
+template <int N, int APG>
+__global__ __launch_bounds__(256) void maze_step_kernel(MazeArgs p) {
+  const int* cfg = p.cfg;                      // null: the reference map (kDefaultMaze)
+  // (uniform) the block's grid size must be the one this kernel was built for: with another N the cell arithmetic would
+  // address outside the frame, so nothing is written (documented with the maze entries in unreal_hip.h)
+  if ((cfg ? cfg[0] : 7) != N) return;
+  __shared__ uint4 wall_img[FRAME_BYTES / 16];
+  // the workgroup's actors' scalar state, fetched by one thread per actor while the wall image is built: read inside the
+  // per-actor loop, each actor would start with two dependent global round trips (state, then the previous slot's terminal
+  // flag) that nothing overlaps -- 8 actors x ~2 us of a 38 us launch
+  __shared__ int s_flag[APG], s_x[APG], s_y[APG], s_a[APG],
+      s_cnt[APG], s_la[APG], s_prev[APG], s_ns[APG];
+  __shared__ float s_lr[APG], s_ep[APG];
+  // configured maze: layout, goal cell, episode steps, and the goal / start cells of the next episode (drawn here too)
+  __shared__ int s_lay[APG], s_goal[APG], s_st[APG], s_epi[APG], s_rgoal[APG], s_rstart[APG];
+  if (p.pol_x) {       // (workgroup-uniform) policy of this workgroup's actors: wave w takes actors w, w + 4, ...
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int k = wave; k < APG; k += 4) {
+      const int b = blockIdx.x * APG + k;
+      if (b >= p.B) break;
+      const int act = policy_row<4>(p.pol_x + (size_t)b * p.pol_ldx, p.Wp, p.bp, p.Wv, p.bv, p.pol_u + b,
+                                    p.pi_out + (size_t)b * 4, p.v_out + b, lane);
+      if (lane == 0) { s_a[k] = act; p.act_out[b] = act; }
+    }
+  }
+  if (threadIdx.x < APG) {
+    const int k = threadIdx.x, b = blockIdx.x * APG + k;
+    if (b < p.B) {
+      const int cnt = p.count[b];
+      s_flag[k] = p.active_rw ? p.active_rw[b] : (p.active ? p.active[b] : 1);
+      s_x[k] = p.pos[2 * b]; s_y[k] = p.pos[2 * b + 1];
+      if (!p.pol_x) s_a[k] = p.actions[b];
+      s_cnt[k] = cnt;
+      s_la[k] = p.last_action[b];
+      s_lr[k] = p.last_reward[b];
+      s_ep[k] = p.track_score ? p.episode_reward[b] : 0.f;
+      s_ns[k] = p.active_rw ? p.n_steps[b] : 0;      // (read here: a load inside the actor loop stalls thread 0's wave -- and,
+                                                     // through the loop's barrier, the workgroup -- for a memory round trip per actor)
+      s_prev[k] = cnt > 0 ? p.r_terminal[(size_t)b * p.H1 + (cnt - 1) % p.H1] : 0;
+      int lay = 0, goal = kDefaultGoal, st = 0, epi = 0, rg = kDefaultGoal, rs = kDefaultStart;
+      if (cfg) {
+        lay = maze_layout(cfg, p.layout, b);
+        goal = p.goal[2 * b + 1] * N + p.goal[2 * b];
+        st = p.ep_steps[b];
+        epi = p.episode[b];
+        maze_reset_cells(cfg, maze_rec(cfg, lay), p.actor_base + b, epi + 1, rg, rs);
+      }
+      s_lay[k] = lay; s_goal[k] = goal; s_st[k] = st; s_epi[k] = epi; s_rgoal[k] = rg; s_rstart[k] = rs;
+    }
+  }
+  int built = cfg ? maze_layout(cfg, p.layout, blockIdx.x * APG) : 0;     // the first actor's layout: read by every thread
+  __shared__ uint64_t s_walls[Walls<N>::NW];
+  Walls<N> walls;
+  walls.lds = s_walls;
+  walls.load(cfg ? maze_rec(cfg, built) : nullptr);
+  build_wall_image<N>(wall_img, walls);
+  __syncthreads();
+  const int H1 = p.H1;
+  const int max_steps = cfg ? cfg[3] : 0;
+  const bool show_goal = cfg && (cfg[2] & kMazeShowGoal);
+  for (int k = 0; k < APG; ++k) {
+    const int b = blockIdx.x * APG + k;
+    if (b >= p.B) break;
+    if (!s_flag[k]) {
+      if (threadIdx.x == 0) rollout_idle(p, b, s_cnt[k] % H1, s_la[k], s_lr[k]);
+      continue;
+    }
+    if (s_lay[k] != built) {           // (uniform) a layout boundary inside the workgroup: rebuild the wall image
+      built = s_lay[k];
+      __syncthreads();                 // every thread is done reading the previous image
+      walls.load(maze_rec(cfg, built));       // (a layout other than the first: cfg is not null)
+      build_wall_image<N>(wall_img, walls);
+      __syncthreads();
+    }
+    const int x = s_x[k], y = s_y[k];
+    const int a = s_a[k];
+    const int gc = s_goal[k], gx = gc % N, gy = gc / N;
+
+    // _move (maze_environment.py:76-91), bound N - 1
+    int dx = (a == 3) - (a == 2), dy = (a == 1) - (a == 0);
+    int nx = x + dx, ny = y + dy;
+    bool clamped = nx < 0 || nx > N - 1 || ny < 0 || ny > N - 1;
+    nx = min(max(nx, 0), N - 1);
+    ny = min(max(ny, 0), N - 1);
+    bool hit_wall = walls.bit(ny * N + nx);
+    if (hit_wall) { nx = x; ny = y; }
+    const bool hit = clamped || hit_wall;
+    const bool at_goal = (nx == gx && ny == gy);
+    const int steps = s_st[k] + 1;
+    const bool terminal = at_goal || (max_steps > 0 && steps >= max_steps);   // goal, or the episode's time-out
+    const float reward = at_goal ? 1.f : (hit ? -1.f : 0.f);
+    const RingStep s = ring_step(b, H1, s_cnt[k], s_prev[k], terminal, p.reset_on_terminal);
+
+    // pixel change between render(nx,ny) and render(x,y): only the two agent blocks differ (ch 1)
+    const bool moved = (nx != x) || (ny != y);
+    for (int c = threadIdx.x; c < PC_CELLS; c += blockDim.x) {
+      int i = c / 20, j = c - i * 20;
+      int sum = 0;
+      if (moved) sum = overlap1<N>(y, i) * overlap1<N>(x, j) + overlap1<N>(ny, i) * overlap1<N>(nx, j);
+      p.r_pc[s.base * PC_CELLS + c] = (float)sum / 48.0f;
+    }
+
+    const int rc = s_rstart[k], ngc = s.reset ? s_rgoal[k] : gc;
+    const int rx = s.reset ? rc % N : nx, ry = s.reset ? rc / N : ny;
+    uint8_t* dst = p.frames + ((size_t)b * H1 + s.nslot) * FRAME_BYTES;
+    render_walls(dst, wall_img);
+    __syncthreads();  // every thread has read the actor's state; wall stores precede the block patch
+    render_blocks<N>(dst, wall_img, rx, ry, ngc % N, ngc / N, show_goal);
+
+    if (threadIdx.x == 0) {
+      ring_commit(p, b, s, a, reward, reward, s_la[k], s_lr[k], s_ep[k]);
+      p.pos[2 * b] = rx;
+      p.pos[2 * b + 1] = ry;
+      if (cfg) {
+        p.goal[2 * b] = ngc % N;
+        p.goal[2 * b + 1] = ngc / N;
+        p.ep_steps[b] = s.reset ? 0 : steps;
+        p.episode[b] = s_epi[k] + (s.reset ? 1 : 0);
+      }
+      rollout_commit(p, b, s, s_ns[k], a, reward);
+    }
+  }
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void maze_reset_kernel(MazeArgs p) {
+  const int* cfg = p.cfg;
+  if ((cfg ? cfg[0] : 7) != N) return;
+  __shared__ uint4 wall_img[FRAME_BYTES / 16];
+  __shared__ int s_lay[kActorsPerGroup], s_epi[kActorsPerGroup], s_rgoal[kActorsPerGroup], s_rstart[kActorsPerGroup];
+  if (threadIdx.x < kActorsPerGroup) {
+    const int k = threadIdx.x, b = blockIdx.x * kActorsPerGroup + k;
+    if (b < p.B) {
+      int lay = 0, epi = 0, rg = kDefaultGoal, rs = kDefaultStart;
+      if (cfg) {
+        lay = maze_layout(cfg, p.layout, b);
+        epi = p.episode[b];
+        maze_reset_cells(cfg, maze_rec(cfg, lay), p.actor_base + b, epi + 1, rg, rs);
+      }
+      s_lay[k] = lay; s_epi[k] = epi; s_rgoal[k] = rg; s_rstart[k] = rs;
+    }
+  }
+  int built = cfg ? maze_layout(cfg, p.layout, blockIdx.x * kActorsPerGroup) : 0;
+  __shared__ uint64_t s_walls[Walls<N>::NW];
+  Walls<N> walls;
+  walls.lds = s_walls;
+  walls.load(cfg ? maze_rec(cfg, built) : nullptr);
+  build_wall_image<N>(wall_img, walls);
+  __syncthreads();
+  const bool show_goal = cfg && (cfg[2] & kMazeShowGoal);
+  for (int k = 0; k < kActorsPerGroup; ++k) {
+    const int b = blockIdx.x * kActorsPerGroup + k;
+    if (b >= p.B) break;
+    if (p.mask && !p.mask[b]) continue;
+    if (s_lay[k] != built) {
+      built = s_lay[k];
+      __syncthreads();
+      walls.load(maze_rec(cfg, built));       // (a layout other than the first: cfg is not null)
+      build_wall_image<N>(wall_img, walls);
+      __syncthreads();
+    }
+    const int sc = s_rstart[k], gc = s_rgoal[k];
+    const int slot = p.count[b] % p.H1;
+    uint8_t* dst = p.frames + ((size_t)b * p.H1 + slot) * FRAME_BYTES;
+    render_walls(dst, wall_img);
+    __syncthreads();
+    render_blocks<N>(dst, wall_img, sc % N, sc / N, gc % N, gc / N, show_goal);
+    if (threadIdx.x == 0) {
+      p.pos[2 * b] = sc % N;
+      p.pos[2 * b + 1] = sc / N;
+      p.last_action[b] = 0;
+      p.last_reward[b] = 0.f;
+      if (cfg) {
+        p.goal[2 * b] = gc % N;
+        p.goal[2 * b + 1] = gc / N;
+        p.ep_steps[b] = 0;
+        p.episode[b] = s_epi[k] + 1;
+      }
+    }
+  }
+}
+
+// ---- first person --------------------------------------------------------------------------------------------------
+constexpr int kChunks = FRAME_BYTES / 16;                 // 1323 uint4 per frame
+constexpr int kChunksPerThread = (kChunks + 255) / 256;   // 6
+constexpr int kRowDw = FRAME_ROW_BYTES / 4;               // 63 dwords per frame row
+constexpr float kPcDenom = 48.f * 255.f;                  // 4 x 4 x 3 bytes at 1/255 (unreal_pixel_change_u8's denom)
+// colours as little-endian (ch0, ch1, ch2) bytes
+constexpr uint32_t kFloor = 0x282828u, kGoalFloor = 0xFF2828u, kWallX = 255u, kWallY = 160u;
+static_assert(FRAME_H % 2 == 0 && FRAME_W % 2 == 0, "q_i and 2y+1-H are odd: the camera has no ties");
+
+template <int N>
+struct FpLds {
+  static constexpr int NW = (N * N + 63) / 64;
+  uint4 img[kChunks];
+  int tn[FRAME_W], td[FRAME_W];
+  uint32_t col[FRAME_W];
+  uint64_t walls[NW];
+  int act;
+};
+
+template <int N>
+__device__ __forceinline__ void fp_load_walls(FpLds<N>& s, const int* rec) {
+  if (threadIdx.x < FpLds<N>::NW)
+    s.walls[threadIdx.x] = (uint64_t)(uint32_t)rec[2 * threadIdx.x] | ((uint64_t)(uint32_t)rec[2 * threadIdx.x + 1] << 32);
+}
+
+// Renders the view from cell (ex, ey) along heading h into s.img.  Call with the whole workgroup after the wall bits are
+// in LDS (and every thread is done reading s.img); returns after a barrier.
+template <int N>
+__device__ __forceinline__ void fp_render(FpLds<N>& s, int ex, int ey, int h, int gx, int gy, bool show_goal) {
+  const int dx = (h == 0) - (h == 2), dy = (h == 1) - (h == 3);
+  const int rx = -dy, ry = dx;
+  if (threadIdx.x < FRAME_W) {           // one column's DDA per lane: at most 2N cells before the ray leaves the map
+    const int i = threadIdx.x, q = 2 * i + 1 - FRAME_W, aq = abs(q), sg = q > 0 ? 1 : -1;
+    int f = 0, sd = 0, k = 0, m = 0, tn = 1, td = 2;
+    bool xface = false, border = true;
+    for (int it = 0; it < 2 * N + 2; ++it) {
+      if ((2 * k + 1) * aq < (2 * m + 1) * FRAME_W) {
+        ++f; tn = 2 * k + 1; td = 2; ++k; xface = dx != 0;
+      } else {
+        sd += sg; tn = (2 * m + 1) * FRAME_W; td = 2 * aq; ++m; xface = rx != 0;
+      }
+      const int cx = ex + f * dx + sd * rx, cy = ey + f * dy + sd * ry;
+      if (cx < 0 || cx >= N || cy < 0 || cy >= N) { border = true; break; }
+      const int c = cy * N + cx;
+      if ((s.walls[c >> 6] >> (c & 63)) & 1) { border = false; break; }
+    }
+    const uint32_t shade = xface ? kWallX : kWallY;
+    s.tn[i] = tn; s.td[i] = td; s.col[i] = border ? shade << 8 : shade;
+  }
+  __syncthreads();
+  // dword w of a frame row holds bytes 4w..4w+3: channel c0 = 4w % 3 onwards of pixel P0 = 4w / 3, then pixel P0 + 1
+  const int w = threadIdx.x & 63;
+  if (w < kRowDw) {
+    const int P0 = (4 * w) / 3, c0 = 4 * w - 3 * P0, P1 = P0 + 1;
+    const int tn0 = s.tn[P0], td0 = s.td[P0], tn1 = s.tn[P1], td1 = s.td[P1];
+    const uint32_t wc0 = s.col[P0], wc1 = s.col[P1];
+    const int q0 = 2 * P0 + 1 - FRAME_W, q1 = 2 * P1 + 1 - FRAME_W;
+    const int gf = (gx - ex) * dx + (gy - ey) * dy, gs = (gx - ex) * rx + (gy - ey) * ry;   // goal: ahead, to the right
+    uint32_t* img32 = reinterpret_cast<uint32_t*>(s.img);
+    for (int y = threadIdx.x >> 6; y < FRAME_H; y += blockDim.x >> 6) {
+      const int p = 2 * y + 1 - FRAME_H, ap = abs(p);
+      // floor((2H + p) / 2p) == gf, as products (p > 0)
+      const bool grow = show_goal && p > 0 && 2 * p * gf <= 2 * FRAME_H + p && 2 * FRAME_H + p < 2 * p * (gf + 1);
+      const int den = 2 * p * FRAME_W;
+      auto pixel = [&](int tn, int td, uint32_t wc, int q) -> uint32_t {
+        if (ap * tn < FRAME_H * td) return wc;
+        if (p < 0) return 0u;
+        const int v = 2 * FRAME_H * q + p * FRAME_W;            // floor(v / den) == gs
+        return (grow && den * gs <= v && v < den * (gs + 1)) ? kGoalFloor : kFloor;
+      };
+      const uint32_t a = pixel(tn0, td0, wc0, q0), b = pixel(tn1, td1, wc1, q1);
+      img32[y * kRowDw + w] = (a >> (8 * c0)) | (b << (8 * (3 - c0)));
+    }
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ uint32_t absdiff_u8x4(uint32_t a, uint32_t b) {
+  uint32_t r = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int d = (int)((a >> (8 * e)) & 255u) - (int)((b >> (8 * e)) & 255u);
+    r |= (uint32_t)abs(d) << (8 * e);
+  }
+  return r;
+}
+
+__device__ __forceinline__ uint4 absdiff_u8x16(uint4 a, uint4 b) {
+  return make_uint4(absdiff_u8x4(a.x, b.x), absdiff_u8x4(a.y, b.y), absdiff_u8x4(a.z, b.z), absdiff_u8x4(a.w, b.w));
+}
+
+__device__ __forceinline__ int bytesum(uint32_t x) {
+  return (int)(x & 255u) + (int)((x >> 8) & 255u) + (int)((x >> 16) & 255u) + (int)(x >> 24);
+}
+
+__device__ __forceinline__ void fp_store(uint8_t* dst, const uint4* img) {
+  uint4* d4 = reinterpret_cast<uint4*>(dst);
+  for (int c = threadIdx.x; c < kChunks; c += blockDim.x) d4[c] = img[c];
+}
+
+// Heading of a reset: header word 7 holds start_heading + 1, or 0 for one drawn from Philox word 2.
+__device__ __forceinline__ int fp_reset_heading(const int* cfg, int g, int ep) {
+  if (cfg[7]) return (cfg[7] - 1) & 3;
+  uint32_t u[4];
+  maze_reset_draw(cfg, g, ep, u);
+  return (int)(u[2] & 3u);
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void maze_fp_step_kernel(MazeArgs p) {
+  const int* cfg = p.cfg;
+  if (cfg[0] != N) return;               // (uniform) a block of another grid size: nothing is written
+  __shared__ FpLds<N> s;
+  const int b = blockIdx.x;
+  const int H1 = p.H1;
+  const int lay = maze_layout(cfg, p.layout, b);
+  const int* rec = maze_rec(cfg, lay);
+  fp_load_walls<N>(s, rec);
+  if (p.pol_x && threadIdx.x < 64) {     // the policy of this actor on wave 0 (for idle actors too, as unreal_policy_step)
+    const int act = policy_row<4>(p.pol_x + (size_t)b * p.pol_ldx, p.Wp, p.bp, p.Wv, p.bv, p.pol_u + b,
+                                  p.pi_out + (size_t)b * 4, p.v_out + b, threadIdx.x);
+    if (threadIdx.x == 0) { s.act = act; p.act_out[b] = act; }
+  }
+  const int cnt = p.count[b];
+  const int slot = cnt % H1;
+  const size_t base = (size_t)b * H1 + slot;
+  const int act_flag = p.active_rw ? p.active_rw[b] : (p.active ? p.active[b] : 1);
+  const int la = p.last_action[b];
+  const float lr = p.last_reward[b];
+  if (!act_flag) {
+    if (threadIdx.x == 0) rollout_idle(p, b, slot, la, lr);
+    return;
+  }
+  // the stored observation s_t, read now: its latency hides under the render
+  uint4 old[kChunksPerThread];
+  {
+    const uint4* src = reinterpret_cast<const uint4*>(p.frames + base * FRAME_BYTES);
+#pragma unroll
+    for (int k = 0; k < kChunksPerThread; ++k) {
+      const int c = threadIdx.x + 256 * k;
+      old[k] = c < kChunks ? src[c] : make_uint4(0, 0, 0, 0);
+    }
+  }
+  const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
+  const int x = p.pos[2 * b], y = p.pos[2 * b + 1], h = p.heading[b] & 3;
+  const int gx = p.goal[2 * b], gy = p.goal[2 * b + 1];
+  const int steps = p.ep_steps[b] + 1;
+  const int epi = p.episode[b];
+  const int ns = p.active_rw ? p.n_steps[b] : 0;
+  const float ep = p.track_score ? p.episode_reward[b] : 0.f;
+  __syncthreads();                       // wall bits and the drawn action are in LDS
+  const int a = p.pol_x ? s.act : p.actions[b];
+
+  // the move: turns keep the cell; a step into a wall or off the map keeps it and is a hit
+  int nx = x, ny = y, nh = h;
+  bool hit = false;
+  if (a == 0) nh = (h + 3) & 3;
+  else if (a == 1) nh = (h + 1) & 3;
+  else if (a == 2 || a == 3) {
+    const int sgn = a == 2 ? 1 : -1;
+    const int tx = x + sgn * ((h == 0) - (h == 2)), ty = y + sgn * ((h == 1) - (h == 3));
+    hit = tx < 0 || tx >= N || ty < 0 || ty >= N || ((s.walls[(ty * N + tx) >> 6] >> ((ty * N + tx) & 63)) & 1);
+    if (!hit) { nx = tx; ny = ty; }
+  }
+  const bool at_goal = nx == gx && ny == gy;
+  const int max_steps = cfg[3];
+  const bool terminal = at_goal || (max_steps > 0 && steps >= max_steps);
+  const float reward = at_goal ? 1.f : (hit ? -1.f : 0.f);
+  const RingStep ring = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
+  const bool reset = ring.reset;
+  const bool show_goal = cfg[2] & kMazeShowGoal;
+  uint8_t* dst = p.frames + ((size_t)b * H1 + ring.nslot) * FRAME_BYTES;
+
+  // s_{t+1}: stored unless the episode restarts; then its bytes become |s_{t+1} - s_t| in place
+  fp_render<N>(s, nx, ny, nh, gx, gy, show_goal);
+#pragma unroll
+  for (int k = 0; k < kChunksPerThread; ++k) {
+    const int c = threadIdx.x + 256 * k;
+    if (c < kChunks) {
+      const uint4 v = s.img[c];
+      if (!reset) reinterpret_cast<uint4*>(dst)[c] = v;     // (a discard's slot is the old one: read above)
+      s.img[c] = absdiff_u8x16(v, old[k]);
+    }
+  }
+  __syncthreads();
+  // pixel change: cell (i, j) sums rows 4i+2..4i+5, bytes 12j+6..12j+17 of the difference (the [2:-2] crop, 4 x 4 blocks)
+  {
+    const uint32_t* d32 = reinterpret_cast<const uint32_t*>(s.img);
+    for (int c = threadIdx.x; c < PC_CELLS; c += blockDim.x) {
+      const int i = c / 20, j = c - 20 * i;
+      int sum = 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t* q = d32 + (4 * i + 2 + r) * kRowDw + 3 * j + 1;
+        sum += bytesum(q[0] >> 16) + bytesum(q[1]) + bytesum(q[2]) + bytesum(q[3] & 0xFFFFu);
+      }
+      p.r_pc[base * PC_CELLS + c] = (float)sum / kPcDenom;
+    }
+  }
+  int rx = nx, ry = ny, rh = nh, rgx = gx, rgy = gy;
+  if (reset) {                           // (uniform) the next episode's first observation goes into the slot instead
+    int rg, rs;
+    maze_reset_cells(cfg, rec, p.actor_base + b, epi + 1, rg, rs);
+    rx = rs % N; ry = rs / N; rgx = rg % N; rgy = rg / N;
+    rh = fp_reset_heading(cfg, p.actor_base + b, epi + 1);
+    fp_render<N>(s, rx, ry, rh, rgx, rgy, show_goal);     // (its first barrier: every thread is done with the difference)
+    fp_store(dst, s.img);
+  }
+
+  if (threadIdx.x == 0) {
+    ring_commit(p, b, ring, a, reward, reward, la, lr, ep);
+    p.pos[2 * b] = rx;
+    p.pos[2 * b + 1] = ry;
+    p.heading[b] = rh;
+    p.goal[2 * b] = rgx;
+    p.goal[2 * b + 1] = rgy;
+    p.ep_steps[b] = reset ? 0 : steps;
+    p.episode[b] = epi + (reset ? 1 : 0);
+    rollout_commit(p, b, ring, ns, a, reward);
+  }
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void maze_fp_reset_kernel(MazeArgs p) {
+  const int* cfg = p.cfg;
+  if (cfg[0] != N) return;
+  const int b = blockIdx.x;
+  if (p.mask && !p.mask[b]) return;
+  __shared__ FpLds<N> s;
+  const int* rec = maze_rec(cfg, maze_layout(cfg, p.layout, b));
+  fp_load_walls<N>(s, rec);
+  const int g = p.actor_base + b, epi = p.episode[b];
+  int gc, sc;
+  maze_reset_cells(cfg, rec, g, epi + 1, gc, sc);
+  const int h = fp_reset_heading(cfg, g, epi + 1);
+  const int slot = p.count[b] % p.H1;
+  __syncthreads();
+  fp_render<N>(s, sc % N, sc / N, h, gc % N, gc / N, cfg[2] & kMazeShowGoal);
+  fp_store(p.frames + ((size_t)b * p.H1 + slot) * FRAME_BYTES, s.img);
+  if (threadIdx.x == 0) {
+    p.pos[2 * b] = sc % N;
+    p.pos[2 * b + 1] = sc / N;
+    p.heading[b] = h;
+    p.goal[2 * b] = gc % N;
+    p.goal[2 * b + 1] = gc / N;
+    p.ep_steps[b] = 0;
+    p.episode[b] = epi + 1;
+    p.last_action[b] = 0;
+    p.last_reward[b] = 0.f;
+  }
+}
+
+
+// ---- host side: one check and one launcher for the four entries -------------------------------------------------------
+enum MazeEntry { kReset, kStep, kRollout, kPolicy };
+
+// The union of what the kernels of the entry write through or read: every pointer non-null, frames 16-byte aligned (both
+// views store 16 B per lane), and the maze tail one of the three forms documented in unreal_hip.h.
+bool maze_args_ok(MazeEntry e, const MazeArgs& p, int view, int N) {
+  if (p.B <= 0 || p.H1 < 2 || !p.pos || !p.last_action || !p.last_reward || !p.count || !p.frames) return false;
+  if ((uintptr_t)p.frames & 15) return false;
+  if (view != kTopDown && view != kFirstPerson) return false;
+  if (!p.cfg) {
+    if (view != kTopDown || N != 7) return false;          // the reference's map
+  } else if (!(N == 7 || N == 12 || N == 14 || N == 21) || p.actor_base < 0 || !p.goal || !p.layout || !p.ep_steps ||
+             !p.episode) {
+    return false;                                           // grid sizes whose cells tile the 84-px frame: 12, 7, 6, 4 px
+  }
+  if (view == kFirstPerson && !p.heading) return false;
+  if (e == kReset) return true;
+  if (!p.r_reward || !p.r_action || !p.r_terminal || !p.r_last_action || !p.r_last_reward || !p.r_pc) return false;
+  if (p.track_score && (!p.episode_reward || !p.score_out || !p.score_valid)) return false;
+  if (e != kPolicy && !p.actions) return false;
+  if (e == kStep) return true;
+  if (!p.active_rw || !p.active_log_t || !p.n_steps || !p.terminal_end || p.idx_base < 0) return false;
+  if (p.next_lar && (p.A <= 0 || p.lar_col0 < 0 || p.lar_ld < p.lar_col0 + p.A + 1)) return false;
+  if (e == kRollout) return true;
+  return p.pol_x && p.pol_ldx >= LSTM_N && p.Wp && p.bp && p.Wv && p.bv && p.pol_u && p.pi_out && p.v_out && p.act_out &&
+         p.A == 4;                                          // the maze has four actions (maze_environment.py:98-112)
+}
+
+template <int N>
+void maze_launch_n(bool reset, int view, const MazeArgs& p, hipStream_t s) {
+  if (view == kFirstPerson) {
+    if (reset) hipLaunchKernelGGL(maze_fp_reset_kernel<N>, dim3(p.B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(maze_fp_step_kernel<N>, dim3(p.B), dim3(256), 0, s, p);
+  } else if (reset) {
+    hipLaunchKernelGGL(maze_reset_kernel<N>, dim3((p.B + kActorsPerGroup - 1) / kActorsPerGroup), dim3(256), 0, s, p);
+  } else if (p.B <= 64) {
+    hipLaunchKernelGGL((maze_step_kernel<N, kStepActorsTiny>), dim3((p.B + kStepActorsTiny - 1) / kStepActorsTiny), dim3(256), 0, s, p);
+  } else if (p.B <= 1024) {
+    hipLaunchKernelGGL((maze_step_kernel<N, 2>), dim3((p.B + 1) / 2), dim3(256), 0, s, p);
+  } else {
+    hipLaunchKernelGGL((maze_step_kernel<N, kStepActorsBig>), dim3((p.B + kStepActorsBig - 1) / kStepActorsBig), dim3(256), 0, s, p);
+  }
+}
+
+// fills in the maze tail, checks, records the top-down step's tier (the first-person kernels have one launch shape and
+// record no label) and launches
+int maze_launch(MazeEntry e, MazeArgs& p, int view, int N, const int* cfg, int actor_base, int* goal, int* layout,
+                int* ep_steps, int* episode, int* heading, void* stream) {
+  p.cfg = cfg; p.actor_base = actor_base; p.goal = goal; p.layout = layout; p.ep_steps = ep_steps; p.episode = episode;
+  p.heading = heading;
+  if (!maze_args_ok(e, p, view, N)) return UNREAL_EINVAL;
+  const int B = p.B;
+  if (view == kTopDown && e == kStep) UNREAL_LAUNCHED(B <= 64 ? "maze_step tiny" : B <= 1024 ? "maze_step apg2" : "maze_step big");
+  if (view == kTopDown && e == kRollout)
+    UNREAL_LAUNCHED(B <= 64 ? "maze_rollout_step tiny" : B <= 1024 ? "maze_rollout_step apg2" : "maze_rollout_step big");
+  if (view == kTopDown && e == kPolicy)
+    UNREAL_LAUNCHED(B <= 64 ? "maze_policy_step tiny" : B <= 1024 ? "maze_policy_step apg2" : "maze_policy_step big");
+  hipStream_t s = (hipStream_t)stream;
+  switch (N) {
+    case 7: maze_launch_n<7>(e == kReset, view, p, s); break;
+    case 12: maze_launch_n<12>(e == kReset, view, p, s); break;
+    case 14: maze_launch_n<14>(e == kReset, view, p, s); break;
+    default: maze_launch_n<21>(e == kReset, view, p, s); break;
+  }
+  return unreal_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int unreal_maze_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward, const int* count,
+                      uint8_t* frames, int view, int N, const int* cfg, int actor_base, int* goal, int* layout,
+                      int* ep_steps, int* episode, int* heading, void* stream) {
+  MazeArgs p{B, H1, nullptr, nullptr, pos, last_action, last_reward, const_cast<int*>(count), frames};
+  p.mask = mask;
+  return maze_launch(kReset, p, view, N, cfg, actor_base, goal, layout, ep_steps, episode, heading, stream);
+}
+
+int unreal_maze_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action, float* last_reward,
+                     int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal, int* r_last_action,
+                     float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                     float* score_out, int* score_valid, int reset_on_terminal, int track_score, int view, int N,
+                     const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps, int* episode, int* heading,
+                     void* stream) {
+  MazeArgs p{B, H1, actions, active, pos, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+             r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid,
+             reset_on_terminal, track_score};
+  return maze_launch(kStep, p, view, N, cfg, actor_base, goal, layout, ep_steps, episode, heading, stream);
+}
+
+int unreal_maze_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward, int* count,
+                             uint8_t* frames, float* r_reward, int* r_action, int* r_terminal, int* r_last_action,
+                             float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                             float* episode_reward, float* score_out, int* score_valid, int* active, int* active_log_t,
+                             int* n_steps, int* terminal_end, int* next_idx, float* next_lar, int lar_ld, int lar_col0,
+                             int A, int idx_base_actor, int view, int N, const int* cfg, int actor_base, int* goal,
+                             int* layout, int* ep_steps, int* episode, int* heading, void* stream) {
+  MazeArgs p{B, H1, actions, nullptr, pos, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+             r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+             active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
+  return maze_launch(kRollout, p, view, N, cfg, actor_base, goal, layout, ep_steps, episode, heading, stream);
+}
+
+int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                    const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                    int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
+                                    uint8_t* frames, float* r_reward, int* r_action, int* r_terminal, int* r_last_action,
+                                    float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                                    float* episode_reward, float* score_out, int* score_valid, int* active,
+                                    int* active_log_t, int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
+                                    int lar_ld, int lar_col0, int A, int idx_base_actor, int view, int N, const int* cfg,
+                                    int actor_base, int* goal, int* layout, int* ep_steps, int* episode, int* heading,
+                                    void* stream) {
+  MazeArgs p{B, H1, nullptr, nullptr, pos, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+             r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+             active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
+             Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
+  return maze_launch(kPolicy, p, view, N, cfg, actor_base, goal, layout, ep_steps, episode, heading, stream);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
-// Pieces shared by the top-down maze kernels (env.hip) and the first-person ones (maze_fp.hip): the Philox4x32-10 counter
-// RNG, the configuration block's layout and accessors, and the reset draw of goal and start cells.
+// Pieces shared by the maze kernels (maze.hip) and env.hip's Philox draws: the Philox4x32-10 counter RNG, the
+// configuration block's layout and accessors, and the reset draw of goal and start cells.
 #pragma once
 #include "common.h"
 
@@ -30,7 +30,7 @@ __device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t index, uin
 // header:  [0] N  [1] L layouts  [2] flags  [3] max_episode_steps (0: none)  [4..5] seed (lo, hi)  [6] record words  [7] 0
 // record l at kCfgHdr + l * rec:  [0..13] wall bits of cell y*N+x as 7 uint64 (lo, hi)  [14] S cell (-1: none)
 //   [15] G cell (-1: none)  [16] n_free  [17] index of G in the free list (-1: none)  [18 ..] free cells, ascending
-// The reference's map (maze_environment.py:18-25) is this same block, built at compile time (kDefaultMaze in env.hip); a
+// The reference's map (maze_environment.py:18-25) is this same block, built at compile time (kDefaultMaze in maze.hip); a
 // null config means it.
 constexpr int kCfgHdr = 8, kRecHdr = 18;
 constexpr int kMazeRandomStart = 1, kMazeRandomGoal = 2, kMazeShowGoal = 4;

@@ -1,6 +1,6 @@
 // One rollout step of the policy for ONE feature row, on one wave: pi = softmax(x Wp + bp), v = x Wv + bv, action ~ pi by
 // inverse CDF in fp64 (numpy RandomState.choice: searchsorted(cumsum(pi) / sum, u, 'right')) or arg max when u == null.
-// Shared by unreal_policy_step (heads.hip) and the fused environment step unreal_maze_policy_rollout_step (env.hip): the
+// Shared by unreal_policy_step (heads.hip) and the fused environment step unreal_maze_policy_rollout_step (maze.hip): the
 // SAME instructions in the same order, so the two paths agree bit for bit (model/model.py:358-377, trainer.py:147-148).
 #pragma once
 #include "common.h"

@@ -6,7 +6,7 @@
 //   /root/reference/train/trainer.py:298-324 (n-step returns), 354-372 (pc returns), 394-406 (vr returns),
 //   427-435 (reward class), experience.py:35-46 (concat_action_and_reward)
 //
-// Ring convention (see env.hip): absolute frame index i of actor b lives in slot i % H1 with
+// Ring convention (see ring_step.h): absolute frame index i of actor b lives in slot i % H1 with
 // H1 = H + 1; the deque of the reference is the absolute range [max(0,count-H), count).
 #include "common.h"
 

@@ -7,7 +7,7 @@ replay ring; `MazeEnvironment` is the reference's batch-1 object surface over th
 
 `MazeConfig` describes user mazes (Environment.register_maze_config): N x N layouts in the reference map's alphabet, optional
 random start / goal cells drawn at every reset, an optional goal block in channel 2 and an optional episode step limit.
-With view="first_person" the same mazes are seen through a raycast camera (`FirstPersonMazeEnvironment`, maze_fp.hip);
+With view="first_person" the same mazes are seen through a raycast camera (`FirstPersonMazeEnvironment`, maze.hip);
 `batched_maze_environment` picks the class from the config."""
 from collections import deque
 
@@ -27,8 +27,8 @@ REFERENCE_MAP = ("--+---G"
 
 
 class MazeConfig(object):
-    """Validated layouts and options of a configured maze, and the int32 configuration block the kernels read
-    (unreal_maze_*_cfg in include/unreal_hip.h).  Raises ValueError on a malformed configuration."""
+    """Validated layouts and options of a configured maze, and the int32 configuration block the kernels read (the maze
+    tail of the unreal_maze_* entries in include/unreal_hip.h).  Raises ValueError on a malformed configuration."""
     SIZES = (7, 12, 14, 21)          # the grid sizes whose cells tile the 84-px frame: 12, 7, 6, 4 px
     MAX_LAYOUTS = 1024
     RANDOM_START, RANDOM_GOAL, SHOW_GOAL = 1, 2, 4
@@ -166,7 +166,8 @@ class BatchedMazeEnvironment(object):
                 raise ValueError("actors [%d, %d) outside the %d actors of the job" % (actor_base, actor_base + batch, total))
             block = torch.from_numpy(config.block(seed)).to(self.ring.count.device)
             self.ring.layout.copy_(torch.from_numpy(config.layout_ids(actor_base, batch, total)))
-            self.maze = (config.N, block, int(actor_base))
+            view = ops.MAZE_FIRST_PERSON if config.view == "first_person" else ops.MAZE_TOP_DOWN
+            self.maze = (view, config.N, block, int(actor_base))
         self.reset()
 
     def view(self, b0, b1):
@@ -176,7 +177,7 @@ class BatchedMazeEnvironment(object):
         v.B, v.ring = b1 - b0, ops.ring_view(self.ring, b0, b1)
         v.base_actor = b0
         v.config = self.config
-        v.maze = None if self.maze is None else (self.maze[0], self.maze[1], self.maze[2] + b0)
+        v.maze = None if self.maze is None else self.maze[:3] + (self.maze[3] + b0,)
         return v
 
     @staticmethod
@@ -211,7 +212,7 @@ class BatchedMazeEnvironment(object):
 
 
 class FirstPersonMazeEnvironment(BatchedMazeEnvironment):
-    """B first-person views of a configured maze (MazeConfig(view="first_person")), stepped by the maze_fp.hip kernels:
+    """B first-person views of a configured maze (MazeConfig(view="first_person")), stepped by the maze.hip kernels:
     actions 0 turn left, 1 turn right, 2 step forward, 3 step back; frames are raycast RGB bytes 0..255."""
     frame_scale = 1.0 / 255.0          # ring bytes 0..255, read like Lab's obs / 255
 
@@ -224,29 +225,6 @@ class FirstPersonMazeEnvironment(BatchedMazeEnvironment):
         v = BatchedMazeEnvironment.view(self, b0, b1)
         v.__class__ = FirstPersonMazeEnvironment
         return v
-
-    def reset(self, mask=None):
-        ops.maze_fp_reset(self.ring, mask, maze=self.maze)
-
-    def process(self, actions, active=None, out_reward=None, out_terminal=None, reset_on_terminal=True,
-                track_score=False):
-        ops.maze_fp_step(self.ring, actions, active, out_reward, out_terminal, reset_on_terminal, track_score,
-                         maze=self.maze)
-
-    def rollout_step(self, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
-                     index_parent=False, **nxt):
-        ops.maze_fp_rollout_step(self.ring, actions, out_reward, out_terminal, active, active_log_t, n_steps,
-                                 terminal_end, base_actor=getattr(self, "base_actor", 0) if index_parent else 0,
-                                 maze=self.maze, **nxt)
-
-    def policy_rollout_step(self, net, feat, ld, u, pi_out, v_out, actions, out_reward, out_terminal, active, active_log_t,
-                            n_steps, terminal_end, index_parent=False, **nxt):
-        p = net.p
-        ops.maze_fp_policy_rollout_step(self.ring, feat, ld, p["W_base_fc_p"], p["b_base_fc_p"], p["W_base_fc_v"],
-                                        p["b_base_fc_v"], u, pi_out, v_out, actions, out_reward, out_terminal, active,
-                                        active_log_t, n_steps, terminal_end,
-                                        base_actor=getattr(self, "base_actor", 0) if index_parent else 0,
-                                        maze=self.maze, **nxt)
 
 
 def batched_maze_environment(batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0):

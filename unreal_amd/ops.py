@@ -163,24 +163,38 @@ def ring_view(ring, b0, b1):
     return v
 
 
+MAZE_TOP_DOWN, MAZE_FIRST_PERSON = 0, 1       # the `view` of a maze (UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON)
+
+
 def _maze_args(ring, maze):
-    """The trailing arguments of a *_cfg maze entry: `maze` = (N, int32 config block on the device, global index of the
-    ring's actor 0), or None for the reference's map."""
+    """The maze tail of every maze entry.  `maze` (every maze wrapper) = (view, N, int32 config block on the device, global
+    index of the ring's actor 0) of a configured maze, or None for the reference's map, top-down."""
     if maze is None:
-        return ()
-    N, block, actor_base = maze
+        return (MAZE_TOP_DOWN, 7, None, 0, None, None, None, None, None)
+    view, N, block, actor_base = maze
     _chk(block, "i32", 8, "maze config")
-    for name, n in (("goal", 2 * ring.B), ("layout", ring.B), ("ep_steps", ring.B), ("episode", ring.B)):
+    arrays = (("goal", 2 * ring.B), ("layout", ring.B), ("ep_steps", ring.B), ("episode", ring.B))
+    if view == MAZE_FIRST_PERSON:
+        arrays += (("heading", ring.B),)
+    for name, n in arrays:
         _chk(getattr(ring, name), "i32", n, "ring." + name)
-    return (int(N), ptr(block), int(actor_base), ptr(ring.goal), ptr(ring.layout), ptr(ring.ep_steps), ptr(ring.episode))
+    return (int(view), int(N), ptr(block), int(actor_base), ptr(ring.goal), ptr(ring.layout), ptr(ring.ep_steps),
+            ptr(ring.episode), ptr(ring.heading))
+
+
+def _ring_args(ring, out_reward, out_terminal):
+    """pos .. score_valid of the step entries: the ring and the per-actor state they commit to."""
+    return (ptr(ring.pos), ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames),
+            ptr(ring.r_reward), ptr(ring.r_action), ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward),
+            ptr(ring.r_pc), ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out),
+            ptr(ring.score_valid))
 
 
 def maze_reset(ring, mask=None, maze=None):
-    """`maze` (every maze wrapper): (N, config block, global actor index of ring actor 0) of a configured maze -> the
-    *_cfg entry; None -> the reference's map."""
+    """Reset every actor (where mask != 0)."""
     _chk(mask, "i32", ring.B, "mask", optional=True)
-    _call("unreal_maze_reset" + ("_cfg" if maze else ""), ring.B, ring.H1, ptr(mask), ptr(ring.pos), ptr(ring.last_action),
-          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), *_maze_args(ring, maze))
+    _call("unreal_maze_reset", ring.B, ring.H1, ptr(mask), ptr(ring.pos), ptr(ring.last_action), ptr(ring.last_reward),
+          ptr(ring.count), ptr(ring.frames), *_maze_args(ring, maze))
 
 
 def maze_step(ring, actions, active=None, out_reward=None, out_terminal=None, reset_on_terminal=True,
@@ -190,29 +204,31 @@ def maze_step(ring, actions, active=None, out_reward=None, out_terminal=None, re
     _chk(active, "i32", B, "active", optional=True)
     _chk(out_reward, "f32", B, "out_reward", optional=True)
     _chk(out_terminal, "i32", B, "out_terminal", optional=True)
-    _call("unreal_maze_step" + ("_cfg" if maze else ""), B, ring.H1, ptr(actions), ptr(active), ptr(ring.pos), ptr(ring.last_action),
-          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward), ptr(ring.r_action),
-          ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc),
-          ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out),
-          ptr(ring.score_valid), int(reset_on_terminal), int(track_score), *_maze_args(ring, maze))
+    _call("unreal_maze_step", B, ring.H1, ptr(actions), ptr(active), *_ring_args(ring, out_reward, out_terminal),
+          int(reset_on_terminal), int(track_score), *_maze_args(ring, maze))
+
+
+def _rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
+                  lar_col0, A, base_actor):
+    B = ring.B
+    _chk(out_reward, "f32", B, "out_reward"); _chk(out_terminal, "i32", B, "out_terminal")
+    for t in (active, active_log_t, n_steps, terminal_end):
+        _chk(t, "i32", B)
+    _chk(next_idx, "i32", B, "next_idx", optional=True)
+    _chk(next_lar, "f32", (B - 1) * lar_ld + lar_col0 + A + 1 if next_lar is not None else None, "next_lar", optional=True)
+    return _ring_args(ring, out_reward, out_terminal) + (
+        ptr(active), ptr(active_log_t), ptr(n_steps), ptr(terminal_end), ptr(next_idx), ptr(next_lar), int(lar_ld),
+        int(lar_col0), int(A), int(base_actor))
 
 
 def maze_rollout_step(ring, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
                       next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=0, base_actor=0, maze=None):
     """maze_step + rollout_advance (+ cur_idx and lar_fill for the NEXT step's rows) in one launch.  `base_actor`: index
     of this (view's) first actor in the ring the next_idx values are meant for (see Ring.cur_idx)."""
-    B = ring.B
-    _chk(actions, "i32", B, "actions"); _chk(out_reward, "f32", B, "out_reward"); _chk(out_terminal, "i32", B, "out_terminal")
-    for t in (active, active_log_t, n_steps, terminal_end):
-        _chk(t, "i32", B)
-    _chk(next_idx, "i32", B, "next_idx", optional=True)
-    _chk(next_lar, "f32", (B - 1) * lar_ld + lar_col0 + A + 1 if next_lar is not None else None, "next_lar", optional=True)
-    _call("unreal_maze_rollout_step" + ("_cfg" if maze else ""), B, ring.H1, ptr(actions), ptr(ring.pos), ptr(ring.last_action), ptr(ring.last_reward),
-          ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward), ptr(ring.r_action), ptr(ring.r_terminal),
-          ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc), ptr(out_reward), ptr(out_terminal),
-          ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid), ptr(active), ptr(active_log_t),
-          ptr(n_steps), ptr(terminal_end), ptr(next_idx), ptr(next_lar), int(lar_ld), int(lar_col0), int(A), int(base_actor),
-          *_maze_args(ring, maze))
+    _chk(actions, "i32", ring.B, "actions")
+    _call("unreal_maze_rollout_step", ring.B, ring.H1, ptr(actions),
+          *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
+                         lar_ld, lar_col0, A, base_actor), *_maze_args(ring, maze))
 
 
 def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions, out_reward, out_terminal, active,
@@ -225,89 +241,11 @@ def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, act
         raise ValueError("the maze has 4 actions")
     _chk(X, "f32", (B - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A); _chk(bp, "f32", A); _chk(Wv, "f32", 256)
     _chk(bv, "f32", 1); _chk(u, "f64", B, "u"); _chk(pi_out, "f32", B * A); _chk(v_out, "f32", B)
-    _chk(actions, "i32", B, "actions"); _chk(out_reward, "f32", B, "out_reward"); _chk(out_terminal, "i32", B, "out_terminal")
-    for t in (active, active_log_t, n_steps, terminal_end):
-        _chk(t, "i32", B)
-    _chk(next_idx, "i32", B, "next_idx", optional=True)
-    _chk(next_lar, "f32", (B - 1) * lar_ld + lar_col0 + A + 1 if next_lar is not None else None, "next_lar", optional=True)
-    _call("unreal_maze_policy_rollout_step" + ("_cfg" if maze else ""), B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(u),
-          ptr(pi_out), ptr(v_out), ptr(actions), ptr(ring.pos), ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count),
-          ptr(ring.frames), ptr(ring.r_reward), ptr(ring.r_action), ptr(ring.r_terminal), ptr(ring.r_last_action),
-          ptr(ring.r_last_reward), ptr(ring.r_pc), ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward),
-          ptr(ring.score_out), ptr(ring.score_valid), ptr(active), ptr(active_log_t), ptr(n_steps), ptr(terminal_end),
-          ptr(next_idx), ptr(next_lar), int(lar_ld), int(lar_col0), int(A), int(base_actor), *_maze_args(ring, maze))
-
-
-def _fp_args(ring, maze):
-    """The trailing arguments of a unreal_maze_fp_* entry (`maze` as for the *_cfg entries; a block is required)."""
-    if maze is None:
-        raise ValueError("a first-person maze needs its configuration block")
-    return _maze_args(ring, maze)
-
-
-def maze_fp_reset(ring, mask=None, maze=None):
-    """First-person view of a configured maze (maze_fp.hip): reset every actor (where mask != 0)."""
-    _chk(mask, "i32", ring.B, "mask", optional=True)
-    _chk(ring.heading, "i32", ring.B, "ring.heading")
-    _call("unreal_maze_fp_reset", ring.B, ring.H1, ptr(mask), ptr(ring.pos), ptr(ring.heading), ptr(ring.last_action),
-          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), *_fp_args(ring, maze))
-
-
-def maze_fp_step(ring, actions, active=None, out_reward=None, out_terminal=None, reset_on_terminal=True,
-                 track_score=False, maze=None):
-    B = ring.B
     _chk(actions, "i32", B, "actions")
-    _chk(active, "i32", B, "active", optional=True)
-    _chk(out_reward, "f32", B, "out_reward", optional=True)
-    _chk(out_terminal, "i32", B, "out_terminal", optional=True)
-    _chk(ring.heading, "i32", B, "ring.heading")
-    _call("unreal_maze_fp_step", B, ring.H1, ptr(actions), ptr(active), ptr(ring.pos), ptr(ring.heading),
-          ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward),
-          ptr(ring.r_action), ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc),
-          ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid),
-          int(reset_on_terminal), int(track_score), *_fp_args(ring, maze))
-
-
-def maze_fp_rollout_step(ring, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
-                         next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=0, base_actor=0, maze=None):
-    """maze_fp_step + rollout_advance (+ the next step's frame indices / LSTM-input columns), as maze_rollout_step."""
-    B = ring.B
-    _chk(actions, "i32", B, "actions"); _chk(out_reward, "f32", B, "out_reward"); _chk(out_terminal, "i32", B, "out_terminal")
-    for t in (active, active_log_t, n_steps, terminal_end):
-        _chk(t, "i32", B)
-    _chk(next_idx, "i32", B, "next_idx", optional=True)
-    _chk(next_lar, "f32", (B - 1) * lar_ld + lar_col0 + A + 1 if next_lar is not None else None, "next_lar", optional=True)
-    _chk(ring.heading, "i32", B, "ring.heading")
-    _call("unreal_maze_fp_rollout_step", B, ring.H1, ptr(actions), ptr(ring.pos), ptr(ring.heading), ptr(ring.last_action),
-          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward), ptr(ring.r_action),
-          ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc), ptr(out_reward),
-          ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid), ptr(active),
-          ptr(active_log_t), ptr(n_steps), ptr(terminal_end), ptr(next_idx), ptr(next_lar), int(lar_ld), int(lar_col0),
-          int(A), int(base_actor), *_fp_args(ring, maze))
-
-
-def maze_fp_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions, out_reward, out_terminal,
-                                active, active_log_t, n_steps, terminal_end, next_idx=None, next_lar=None, lar_ld=0,
-                                lar_col0=0, A=4, base_actor=0, maze=None):
-    """policy_step + maze_fp_rollout_step in one launch (bit-identical to the two launches)."""
-    B = ring.B
-    if A != 4:
-        raise ValueError("the maze has 4 actions")
-    _chk(X, "f32", (B - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A); _chk(bp, "f32", A); _chk(Wv, "f32", 256)
-    _chk(bv, "f32", 1); _chk(u, "f64", B, "u"); _chk(pi_out, "f32", B * A); _chk(v_out, "f32", B)
-    _chk(actions, "i32", B, "actions"); _chk(out_reward, "f32", B, "out_reward"); _chk(out_terminal, "i32", B, "out_terminal")
-    for t in (active, active_log_t, n_steps, terminal_end):
-        _chk(t, "i32", B)
-    _chk(next_idx, "i32", B, "next_idx", optional=True)
-    _chk(next_lar, "f32", (B - 1) * lar_ld + lar_col0 + A + 1 if next_lar is not None else None, "next_lar", optional=True)
-    _chk(ring.heading, "i32", B, "ring.heading")
-    _call("unreal_maze_fp_policy_rollout_step", B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(u),
-          ptr(pi_out), ptr(v_out), ptr(actions), ptr(ring.pos), ptr(ring.heading), ptr(ring.last_action),
-          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward), ptr(ring.r_action),
-          ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc), ptr(out_reward),
-          ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid), ptr(active),
-          ptr(active_log_t), ptr(n_steps), ptr(terminal_end), ptr(next_idx), ptr(next_lar), int(lar_ld), int(lar_col0),
-          int(A), int(base_actor), *_fp_args(ring, maze))
+    _call("unreal_maze_policy_rollout_step", B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(u),
+          ptr(pi_out), ptr(v_out), ptr(actions),
+          *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
+                         lar_ld, lar_col0, A, base_actor), *_maze_args(ring, maze))
 
 
 def pixel_change_u8(frames, idx_new, idx_old, denom, out):
