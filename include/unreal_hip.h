@@ -49,7 +49,16 @@ extern "C" {
  * draws the first-person start heading when the block's word 7 is 0.
  * First person: actions 0 turn left, 1 turn right, 2 step forward, 3 step back; frames are the raycast 84 x 84 RGB view
  * (bytes 0..255, read at scale 1/255) and r_pc is the pixel change of the two frames over 48 * 255, as
- * unreal_pixel_change_u8.  `frames` must be 16-byte aligned; every pointer an entry writes through is required. */
+ * unreal_pixel_change_u8.  `frames` must be 16-byte aligned; every pointer an entry writes through is required.
+ * Navigation (first person, flag 8 in the block's word 2): after the last layout record the block holds
+ * [goal reward, apple reward, hit reward, mode (1: goal_respawn, 2: Lab's six actions), 0, 0, 0, 0] and per layout 65
+ * words [n apples <= 64, apple cells ascending, 0 ...].  `heading` then addresses B records of UNREAL_MAZE_NAV_RECORD
+ * int32: (heading, apple bits lo, apple bits hi, goals_total, apples_total, 0, 0, 0); apple bit k (the k-th apple cell of
+ * the layout) set = collected in the running episode; goals_total / apples_total count from the actor's first reset and
+ * no reset zeroes them.  Lab's actions: 0 / 1 look left / right, 2 / 3 strafe left / right (-r / +r), 4 / 5 forward /
+ * back.  With goal_respawn a goal is not terminal: the actor moves to S or a free cell other than the goal drawn with
+ * counter = (actor_base + b, episode, 0x4D415A52, goals_total), word 1, heading word 2 (or the block's fixed one). */
+#define UNREAL_MAZE_NAV_RECORD 8
 #define UNREAL_MAZE_TOP_DOWN 0
 #define UNREAL_MAZE_FIRST_PERSON 1
 /* env.reset() of every actor where mask[b] != 0 (mask nullable) */
@@ -81,7 +90,9 @@ int unreal_maze_rollout_step(int B, int H1, const int* actions, int* pos, int* l
                              int* episode, int* heading, void* stream);
 /* unreal_policy_step + unreal_maze_rollout_step in ONE launch (trainer.py:236-296: run_base_policy_and_value, choose_action,
  * environment.process of one rollout step): the workgroup that steps an actor first computes its pi / V from the feature row
- * X[b] (K = 256) and draws its action from u[b] -- bit-identical to the two-launch path.  A must be 4 (the maze). */
+ * X[b] (K = 256) and draws its action from u[b] -- bit-identical to the two-launch path.  A must be 4 (the maze), or 6 on a
+ * first-person navigation block with Lab's actions; a first-person launch whose A is not its block's action count
+ * writes nothing (as a block of another N). */
 int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
                                     const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
                                     int* actions_out, int* pos, int* last_action, float* last_reward, int* count,

@@ -3,7 +3,9 @@
 
   * the step kernel's time per launch (HIP events around each launch, random actions) for the top-down and the
     first-person view of the same configured mazes, at B = 512 and B = 4096, N = 7 and N = 21;
-  * Trainer.process() ms for full UNREAL at B = 4096 in both views (replay history --history, filled untimed).
+  * Trainer.process() ms for full UNREAL at B = 4096 in both views (replay history --history, filled untimed);
+  * navigation rows: the step of a navigation block (apples, rewards (10, 1, 0), goal_respawn, Lab's six
+    actions) next to the plain first-person step of the same layouts, and Trainer.process() at A = 6.
 
   python tools/bench_fp_maze.py [--launches 200] [--steps 10] [--warmup 3] [--history 100]
 
@@ -24,17 +26,20 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 DEV = "cuda:0"
 
 
-def layouts(N, L=8, seed=0):
+def layouts(N, L=8, seed=0, apples=0):
     from maze_model import random_layout
     rs = np.random.RandomState(seed + N)
-    return [random_layout(N, rs, marks="") for _ in range(L)]
+    return [random_layout(N, rs, marks="A" * apples) for _ in range(L)]
 
 
-def kernel_ms(env, B, launches):
+NAV_APPLES = {7: 8, 21: 64}
+
+
+def kernel_ms(env, B, launches, A=4):
     """Mean HIP-event time of one step launch (the entry point env.process calls)."""
     from unreal_amd import ops
     rs = np.random.RandomState(0)
-    acts = [torch.from_numpy(rs.randint(0, 4, B).astype(np.int32)).to(DEV) for _ in range(8)]
+    acts = [torch.from_numpy(rs.randint(0, A, B).astype(np.int32)).to(DEV) for _ in range(8)]
     r = torch.zeros(B, dtype=torch.float32, device=DEV)
     t = torch.zeros(B, dtype=torch.int32, device=DEV)
     for k in range(10):
@@ -92,10 +97,33 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--history", type=int, default=100)
     ap.add_argument("--skip-trainer", action="store_true")
+    ap.add_argument("--nav-only", action="store_true", help="only the navigation rows and their plain references")
     args = ap.parse_args()
     from unreal_amd.environment.environment import Environment
     from unreal_amd.environment.maze_environment import MazeConfig, batched_maze_environment
     kw = dict(random_start=True, random_goal=True, show_goal=True, max_episode_steps=200)
+    nav_kw = dict(goal_reward=10, apple_reward=1, hit_reward=0, goal_respawn=True, action_set="lab")
+    for N in (7, 21):       # navigation vs plain first person: same layouts (apples only in the nav block), same process
+        for B in (512, 4096):
+            res = {}
+            for what in ("plain", "nav"):
+                lays = layouts(N, apples=NAV_APPLES[N] if what == "nav" else 0)
+                cfg = MazeConfig(lays, view="first_person", **dict(kw, **(nav_kw if what == "nav" else {})))
+                env = batched_maze_environment(B, 3, DEV, config=cfg, seed=1)
+                res[what] = kernel_ms(env, B, args.launches, A=cfg.action_size) * 1e3
+                del env
+            print(json.dumps(dict(what="nav_step_kernel", N=N, B=B, plain_us=round(res["plain"], 2),
+                                  nav_us=round(res["nav"], 2), ratio=round(res["nav"] / res["plain"], 3))), flush=True)
+    if args.nav_only:
+        if not args.skip_trainer:
+            name = "bench_nav"
+            Environment.register_maze_config(name, layouts(7, apples=NAV_APPLES[7]), view="first_person",
+                                             **dict(kw, **nav_kw))
+            ms, wall = trainer_ms(name, 4096, args.history, args.steps, args.warmup)
+            print(json.dumps(dict(what="trainer_process", view="first_person_nav", A=6, N=7, B=4096,
+                                  history=args.history, ms_per_call=round(ms, 3), wall_ms_per_call=round(wall, 3))),
+                  flush=True)
+        return
     for N in (7, 21):
         lays = layouts(N)
         for view in ("top_down", "first_person"):

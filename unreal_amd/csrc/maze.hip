@@ -24,6 +24,9 @@
 //   palette:  ceiling 0; floor (40,40,40), the goal tile (40,40,255) with show_goal; interior walls 255 (x-faces) / 160
 //             (y-faces) in channel 0, the map border the same shades in channel 1.
 //
+// Navigation blocks (flag kMazeNav) add apples drawn on the floor, the block's rewards, respawn at the goal and
+// Lab's six actions, in the same kernels behind one uniform branch (fp_step / fp_reset<N, NAV>).
+//
 // One workgroup (256 threads) per actor.  The step renders s_{t+1} into LDS (lanes 0..83: one column's DDA each, over
 // the layout's wall bits in LDS; then every thread fills whole frame-row dwords), streams it to the ring slot with 16 B
 // per lane, turns the LDS image into |new - old| bytes against the stored frame (read at kernel entry, so its latency
@@ -412,17 +415,20 @@ constexpr int kChunksPerThread = (kChunks + 255) / 256;   // 6
 constexpr int kRowDw = FRAME_ROW_BYTES / 4;               // 63 dwords per frame row
 constexpr float kPcDenom = 48.f * 255.f;                  // 4 x 4 x 3 bytes at 1/255 (unreal_pixel_change_u8's denom)
 // colours as little-endian (ch0, ch1, ch2) bytes
-constexpr uint32_t kFloor = 0x282828u, kGoalFloor = 0xFF2828u, kWallX = 255u, kWallY = 160u;
+constexpr uint32_t kFloor = 0x282828u, kGoalFloor = 0xFF2828u, kAppleFloor = 0x28FF28u, kWallX = 255u, kWallY = 160u;
 static_assert(FRAME_H % 2 == 0 && FRAME_W % 2 == 0, "q_i and 2y+1-H are odd: the camera has no ties");
 
 template <int N>
 struct FpLds {
   static constexpr int NW = (N * N + 63) / 64;
+  static constexpr int NA = (N * N + 31) / 32;   // navigation: words of the active-apple cell bitmap
   uint4 img[kChunks];
   int tn[FRAME_W], td[FRAME_W];
   uint32_t col[FRAME_W];
   uint64_t walls[NW];
+  uint32_t apples[NA];
   int act;
+  int collect;                                  // navigation: bit index of the apple the step collects (-1: none)
 };
 
 template <int N>
@@ -431,9 +437,16 @@ __device__ __forceinline__ void fp_load_walls(FpLds<N>& s, const int* rec) {
     s.walls[threadIdx.x] = (uint64_t)(uint32_t)rec[2 * threadIdx.x] | ((uint64_t)(uint32_t)rec[2 * threadIdx.x + 1] << 32);
 }
 
-// Renders the view from cell (ex, ey) along heading h into s.img.  Call with the whole workgroup after the wall bits are
-// in LDS (and every thread is done reading s.img); returns after a barrier.
+// Navigation: sets the bit of every active apple (not collected, not on the goal cell) of one apple record in the
+// bitmap, which must be zero and separated from this by a barrier.  Thread k < n handles apple k (its cell `cell`).
 template <int N>
+__device__ __forceinline__ void fp_mark_apple(FpLds<N>& s, int k, int n, int cell, uint64_t collected, int goal) {
+  if (k < n && !((collected >> k) & 1) && cell != goal) atomicOr(&s.apples[cell >> 5], 1u << (cell & 31));
+}
+
+// Renders the view from cell (ex, ey) along heading h into s.img.  Call with the whole workgroup after the wall bits (and
+// with NAV, the apple bitmap's marks) are issued to LDS and every thread is done reading s.img; returns after a barrier.
+template <int N, bool NAV>
 __device__ __forceinline__ void fp_render(FpLds<N>& s, int ex, int ey, int h, int gx, int gy, bool show_goal) {
   const int dx = (h == 0) - (h == 2), dy = (h == 1) - (h == 3);
   const int rx = -dy, ry = dx;
@@ -470,11 +483,28 @@ __device__ __forceinline__ void fp_render(FpLds<N>& s, int ex, int ey, int h, in
       // floor((2H + p) / 2p) == gf, as products (p > 0)
       const bool grow = show_goal && p > 0 && 2 * p * gf <= 2 * FRAME_H + p && 2 * FRAME_H + p < 2 * p * (gf + 1);
       const int den = 2 * p * FRAME_W;
+      // navigation: the row's floor cells lie `ahead` cells forward; a pixel's side offset floor(v / den) comes from one
+      // float product: v / den is >= 1 / den from every integer, far above the product's error
+      int ahead = 0;
+      float inv = 0.f;
+      if constexpr (NAV) {
+        ahead = p > 0 ? (2 * FRAME_H + p) / (2 * p) : 0;
+        inv = p > 0 ? 1.f / (float)den : 0.f;
+      }
       auto pixel = [&](int tn, int td, uint32_t wc, int q) -> uint32_t {
         if (ap * tn < FRAME_H * td) return wc;
         if (p < 0) return 0u;
         const int v = 2 * FRAME_H * q + p * FRAME_W;            // floor(v / den) == gs
-        return (grow && den * gs <= v && v < den * (gs + 1)) ? kGoalFloor : kFloor;
+        if (grow && den * gs <= v && v < den * (gs + 1)) return kGoalFloor;
+        if constexpr (NAV) {
+          const int side = (int)floorf((float)v * inv);
+          const int cx = ex + ahead * dx + side * rx, cy = ey + ahead * dy + side * ry;
+          if ((unsigned)cx < (unsigned)N && (unsigned)cy < (unsigned)N) {
+            const int c = cy * N + cx;
+            if ((s.apples[c >> 5] >> (c & 31)) & 1u) return kAppleFloor;
+          }
+        }
+        return kFloor;
       };
       const uint32_t a = pixel(tn0, td0, wc0, q0), b = pixel(tn1, td1, wc1, q1);
       img32[y * kRowDw + w] = (a >> (8 * c0)) | (b << (8 * (3 - c0)));
@@ -514,19 +544,49 @@ __device__ __forceinline__ int fp_reset_heading(const int* cfg, int g, int ep) {
   return (int)(u[2] & 3u);
 }
 
-template <int N>
-__global__ __launch_bounds__(256) void maze_fp_step_kernel(MazeArgs p) {
+// Navigation respawn after global actor g's goal number `goals` (counted) in episode `ep`: Philox key = seed, counter =
+// (g, ep, kMazeRespawnStream, goals); the start from S or word 1 over the free cells other than the goal (the free list
+// is ascending and holds the goal), the heading start_heading or word 2 mod 4.
+__device__ __forceinline__ void nav_respawn(const int* cfg, const int* rec, int g, int ep, int goals, int goal, int& start,
+                                            int& heading) {
+  const uint64_t seed = (uint64_t)(uint32_t)cfg[4] | ((uint64_t)(uint32_t)cfg[5] << 32);
+  uint32_t u[4];
+  philox4x32_10(seed, (uint64_t)(uint32_t)g | ((uint64_t)(uint32_t)ep << 32),
+                (uint64_t)kMazeRespawnStream | ((uint64_t)(uint32_t)goals << 32), u);
+  start = rec[14];
+  if (cfg[2] & kMazeRandomStart) {
+    const int j = (int)(u[1] % (uint32_t)max(rec[16] - 1, 1));
+    start = rec[kRecHdr + j];
+    if (start >= goal) start = rec[kRecHdr + j + 1];
+  }
+  heading = cfg[7] ? (cfg[7] - 1) & 3 : (int)(u[2] & 3u);
+}
+
+// The first-person step of one actor per workgroup.  NAV: a navigation block (kMazeNav): the per-actor
+// record behind `heading`, the block's rewards and action set, apples, and respawn at the goal.
+template <int N, bool NAV>
+__device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
   const int* cfg = p.cfg;
-  if (cfg[0] != N) return;               // (uniform) a block of another grid size: nothing is written
-  __shared__ FpLds<N> s;
   const int b = blockIdx.x;
   const int H1 = p.H1;
   const int lay = maze_layout(cfg, p.layout, b);
   const int* rec = maze_rec(cfg, lay);
+  const int* ext = NAV ? maze_nav_ext(cfg) : nullptr;
+  const int* arec = NAV ? ext + kNavHdr + lay * kNavRec : nullptr;
+  const int mode = NAV ? ext[3] : 0;
   fp_load_walls<N>(s, rec);
+  if (NAV) {
+    if (threadIdx.x < FpLds<N>::NA) s.apples[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) s.collect = -1;
+  }
   if (p.pol_x && threadIdx.x < 64) {     // the policy of this actor on wave 0 (for idle actors too, as unreal_policy_step)
-    const int act = policy_row<4>(p.pol_x + (size_t)b * p.pol_ldx, p.Wp, p.bp, p.Wv, p.bv, p.pol_u + b,
-                                  p.pi_out + (size_t)b * 4, p.v_out + b, threadIdx.x);
+    int act;
+    if (NAV && (mode & kNavLabActions))
+      act = policy_row<6>(p.pol_x + (size_t)b * p.pol_ldx, p.Wp, p.bp, p.Wv, p.bv, p.pol_u + b, p.pi_out + (size_t)b * 6,
+                          p.v_out + b, threadIdx.x);
+    else
+      act = policy_row<4>(p.pol_x + (size_t)b * p.pol_ldx, p.Wp, p.bp, p.Wv, p.bv, p.pol_u + b, p.pi_out + (size_t)b * 4,
+                          p.v_out + b, threadIdx.x);
     if (threadIdx.x == 0) { s.act = act; p.act_out[b] = act; }
   }
   const int cnt = p.count[b];
@@ -549,38 +609,75 @@ __global__ __launch_bounds__(256) void maze_fp_step_kernel(MazeArgs p) {
       old[k] = c < kChunks ? src[c] : make_uint4(0, 0, 0, 0);
     }
   }
+  int* hrec = p.heading + (NAV ? kNavActorWords * b : b);
   const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
-  const int x = p.pos[2 * b], y = p.pos[2 * b + 1], h = p.heading[b] & 3;
+  const int x = p.pos[2 * b], y = p.pos[2 * b + 1], h = hrec[0] & 3;
   const int gx = p.goal[2 * b], gy = p.goal[2 * b + 1];
   const int steps = p.ep_steps[b] + 1;
   const int epi = p.episode[b];
   const int ns = p.active_rw ? p.n_steps[b] : 0;
   const float ep = p.track_score ? p.episode_reward[b] : 0.f;
-  __syncthreads();                       // wall bits and the drawn action are in LDS
+  uint64_t bits = 0;
+  int goals = 0, apples = 0, n_apples = 0, my_apple = -1;
+  if (NAV) {
+    bits = (uint64_t)(uint32_t)hrec[1] | ((uint64_t)(uint32_t)hrec[2] << 32);
+    goals = hrec[3];
+    apples = hrec[4];
+    n_apples = min(arec[0], kMaxApples);
+    if (threadIdx.x < n_apples) my_apple = arec[1 + threadIdx.x];
+  }
+  __syncthreads();                       // wall bits, the drawn action (and the zeroed apple bitmap) are in LDS
   const int a = p.pol_x ? s.act : p.actions[b];
 
-  // the move: turns keep the cell; a step into a wall or off the map keeps it and is a hit
+  // the move: turns keep the cell; a move into a wall or off the map keeps it and is a hit.  Turn set: 2 / 3 step
+  // forward / back; lab set: 2 / 3 strafe left / right (-r / +r), 4 / 5 step forward / back
   int nx = x, ny = y, nh = h;
-  bool hit = false;
+  bool hit = false, moved = false;
   if (a == 0) nh = (h + 3) & 3;
   else if (a == 1) nh = (h + 1) & 3;
-  else if (a == 2 || a == 3) {
-    const int sgn = a == 2 ? 1 : -1;
-    const int tx = x + sgn * ((h == 0) - (h == 2)), ty = y + sgn * ((h == 1) - (h == 3));
-    hit = tx < 0 || tx >= N || ty < 0 || ty >= N || ((s.walls[(ty * N + tx) >> 6] >> ((ty * N + tx) & 63)) & 1);
-    if (!hit) { nx = tx; ny = ty; }
+  else {
+    const int dx = (h == 0) - (h == 2), dy = (h == 1) - (h == 3);
+    int mx = 0, my = 0;
+    if (NAV && (mode & kNavLabActions)) {
+      if (a == 2) { mx = dy; my = -dx; }
+      else if (a == 3) { mx = -dy; my = dx; }
+      else if (a == 4) { mx = dx; my = dy; }
+      else if (a == 5) { mx = -dx; my = -dy; }
+    } else if (a == 2 || a == 3) {
+      const int sgn = a == 2 ? 1 : -1;
+      mx = sgn * dx; my = sgn * dy;
+    }
+    if (mx | my) {
+      const int tx = x + mx, ty = y + my;
+      hit = tx < 0 || tx >= N || ty < 0 || ty >= N || ((s.walls[(ty * N + tx) >> 6] >> ((ty * N + tx) & 63)) & 1);
+      if (!hit) { nx = tx; ny = ty; moved = true; }
+    }
   }
   const bool at_goal = nx == gx && ny == gy;
   const int max_steps = cfg[3];
-  const bool terminal = at_goal || (max_steps > 0 && steps >= max_steps);
-  const float reward = at_goal ? 1.f : (hit ? -1.f : 0.f);
+  const bool timeout = max_steps > 0 && steps >= max_steps;
+  const bool terminal = (NAV && (mode & kNavRespawn)) ? timeout : (at_goal || timeout);
   const RingStep ring = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
   const bool reset = ring.reset;
   const bool show_goal = cfg[2] & kMazeShowGoal;
   uint8_t* dst = p.frames + ((size_t)b * H1 + ring.nslot) * FRAME_BYTES;
 
+  int ex = nx, ey = ny, eh = nh;          // the eye of s_{t+1}: the respawn start when a goal respawns
+  if (NAV) {
+    goals += at_goal ? 1 : 0;
+    if (at_goal && !terminal && (mode & kNavRespawn)) {
+      int st;
+      nav_respawn(cfg, rec, p.actor_base + b, epi, goals, gy * N + gx, st, eh);
+      ex = st % N; ey = st / N;
+    }
+    // the active apples of the running episode; the apple of the cell moved into (never the goal's) is collected
+    fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, bits, gy * N + gx);
+    if (moved && my_apple == ny * N + nx && my_apple != gy * N + gx && !((bits >> threadIdx.x) & 1))
+      s.collect = threadIdx.x;
+  }
+
   // s_{t+1}: stored unless the episode restarts; then its bytes become |s_{t+1} - s_t| in place
-  fp_render<N>(s, nx, ny, nh, gx, gy, show_goal);
+  fp_render<N, NAV>(s, ex, ey, eh, gx, gy, show_goal);
 #pragma unroll
   for (int k = 0; k < kChunksPerThread; ++k) {
     const int c = threadIdx.x + 256 * k;
@@ -589,6 +686,13 @@ __global__ __launch_bounds__(256) void maze_fp_step_kernel(MazeArgs p) {
       if (!reset) reinterpret_cast<uint4*>(dst)[c] = v;     // (a discard's slot is the old one: read above)
       s.img[c] = absdiff_u8x16(v, old[k]);
     }
+  }
+  float reward = at_goal ? 1.f : (hit ? -1.f : 0.f);
+  if (NAV) {
+    const int col = s.collect;           // (written before the render's barriers)
+    reward = at_goal ? (float)ext[0] : col >= 0 ? (float)ext[1] : hit ? (float)ext[2] : 0.f;
+    if (col >= 0) { bits |= 1ull << col; ++apples; }
+    if (reset && threadIdx.x < FpLds<N>::NA) s.apples[threadIdx.x] = 0u;   // (read by nobody until the reset render)
   }
   __syncthreads();
   // pixel change: cell (i, j) sums rows 4i+2..4i+5, bytes 12j+6..12j+17 of the difference (the [2:-2] crop, 4 x 4 blocks)
@@ -605,13 +709,17 @@ __global__ __launch_bounds__(256) void maze_fp_step_kernel(MazeArgs p) {
       p.r_pc[base * PC_CELLS + c] = (float)sum / kPcDenom;
     }
   }
-  int rx = nx, ry = ny, rh = nh, rgx = gx, rgy = gy;
+  int rx = ex, ry = ey, rh = eh, rgx = gx, rgy = gy;
   if (reset) {                           // (uniform) the next episode's first observation goes into the slot instead
     int rg, rs;
     maze_reset_cells(cfg, rec, p.actor_base + b, epi + 1, rg, rs);
     rx = rs % N; ry = rs / N; rgx = rg % N; rgy = rg / N;
     rh = fp_reset_heading(cfg, p.actor_base + b, epi + 1);
-    fp_render<N>(s, rx, ry, rh, rgx, rgy, show_goal);     // (its first barrier: every thread is done with the difference)
+    if (NAV) {                           // every apple is back
+      bits = 0;
+      fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, 0, rg);
+    }
+    fp_render<N, NAV>(s, rx, ry, rh, rgx, rgy, show_goal);     // (its first barrier: every thread is done with the difference)
     fp_store(dst, s.img);
   }
 
@@ -619,12 +727,68 @@ __global__ __launch_bounds__(256) void maze_fp_step_kernel(MazeArgs p) {
     ring_commit(p, b, ring, a, reward, reward, la, lr, ep);
     p.pos[2 * b] = rx;
     p.pos[2 * b + 1] = ry;
-    p.heading[b] = rh;
+    hrec[0] = rh;
+    if (NAV) {
+      hrec[1] = (int)(uint32_t)bits;
+      hrec[2] = (int)(uint32_t)(bits >> 32);
+      hrec[3] = goals;
+      hrec[4] = apples;
+    }
     p.goal[2 * b] = rgx;
     p.goal[2 * b + 1] = rgy;
     p.ep_steps[b] = reset ? 0 : steps;
     p.episode[b] = epi + (reset ? 1 : 0);
     rollout_commit(p, b, ring, ns, a, reward);
+  }
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void maze_fp_step_kernel(MazeArgs p) {
+  const int* cfg = p.cfg;
+  if (cfg[0] != N) return;               // (uniform) a block of another grid size: nothing is written
+  __shared__ FpLds<N> s;
+  const bool nav = cfg[2] & kMazeNav;
+  // (uniform) a fused policy step whose A is not the block's action count: nothing is written either
+  if (p.pol_x && p.A != (nav && (maze_nav_ext(cfg)[3] & kNavLabActions) ? 6 : 4)) return;
+  if (nav) fp_step<N, true>(p, s);
+  else fp_step<N, false>(p, s);
+}
+
+template <int N, bool NAV>
+__device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
+  const int* cfg = p.cfg;
+  const int b = blockIdx.x;
+  const int lay = maze_layout(cfg, p.layout, b);
+  const int* rec = maze_rec(cfg, lay);
+  fp_load_walls<N>(s, rec);
+  const int g = p.actor_base + b, epi = p.episode[b];
+  int gc, sc;
+  maze_reset_cells(cfg, rec, g, epi + 1, gc, sc);
+  const int h = fp_reset_heading(cfg, g, epi + 1);
+  const int slot = p.count[b] % p.H1;
+  int n_apples = 0, my_apple = -1;
+  if (NAV) {
+    const int* arec = maze_nav_ext(cfg) + kNavHdr + lay * kNavRec;
+    n_apples = min(arec[0], kMaxApples);
+    if (threadIdx.x < n_apples) my_apple = arec[1 + threadIdx.x];
+    if (threadIdx.x < FpLds<N>::NA) s.apples[threadIdx.x] = 0u;
+  }
+  __syncthreads();
+  if (NAV) fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, 0, gc);
+  fp_render<N, NAV>(s, sc % N, sc / N, h, gc % N, gc / N, cfg[2] & kMazeShowGoal);
+  fp_store(p.frames + ((size_t)b * p.H1 + slot) * FRAME_BYTES, s.img);
+  if (threadIdx.x == 0) {
+    p.pos[2 * b] = sc % N;
+    p.pos[2 * b + 1] = sc / N;
+    int* hrec = p.heading + (NAV ? kNavActorWords * b : b);
+    hrec[0] = h;
+    if (NAV) { hrec[1] = 0; hrec[2] = 0; }          // every apple is back; goals_total / apples_total run on
+    p.goal[2 * b] = gc % N;
+    p.goal[2 * b + 1] = gc / N;
+    p.ep_steps[b] = 0;
+    p.episode[b] = epi + 1;
+    p.last_action[b] = 0;
+    p.last_reward[b] = 0.f;
   }
 }
 
@@ -635,27 +799,8 @@ __global__ __launch_bounds__(256) void maze_fp_reset_kernel(MazeArgs p) {
   const int b = blockIdx.x;
   if (p.mask && !p.mask[b]) return;
   __shared__ FpLds<N> s;
-  const int* rec = maze_rec(cfg, maze_layout(cfg, p.layout, b));
-  fp_load_walls<N>(s, rec);
-  const int g = p.actor_base + b, epi = p.episode[b];
-  int gc, sc;
-  maze_reset_cells(cfg, rec, g, epi + 1, gc, sc);
-  const int h = fp_reset_heading(cfg, g, epi + 1);
-  const int slot = p.count[b] % p.H1;
-  __syncthreads();
-  fp_render<N>(s, sc % N, sc / N, h, gc % N, gc / N, cfg[2] & kMazeShowGoal);
-  fp_store(p.frames + ((size_t)b * p.H1 + slot) * FRAME_BYTES, s.img);
-  if (threadIdx.x == 0) {
-    p.pos[2 * b] = sc % N;
-    p.pos[2 * b + 1] = sc / N;
-    p.heading[b] = h;
-    p.goal[2 * b] = gc % N;
-    p.goal[2 * b + 1] = gc / N;
-    p.ep_steps[b] = 0;
-    p.episode[b] = epi + 1;
-    p.last_action[b] = 0;
-    p.last_reward[b] = 0.f;
-  }
+  if (cfg[2] & kMazeNav) fp_reset<N, true>(p, s);
+  else fp_reset<N, false>(p, s);
 }
 
 
@@ -683,8 +828,9 @@ bool maze_args_ok(MazeEntry e, const MazeArgs& p, int view, int N) {
   if (!p.active_rw || !p.active_log_t || !p.n_steps || !p.terminal_end || p.idx_base < 0) return false;
   if (p.next_lar && (p.A <= 0 || p.lar_col0 < 0 || p.lar_ld < p.lar_col0 + p.A + 1)) return false;
   if (e == kRollout) return true;
+  // the maze has four actions (maze_environment.py:98-112); a first-person navigation block with Lab's action set six
   return p.pol_x && p.pol_ldx >= LSTM_N && p.Wp && p.bp && p.Wv && p.bv && p.pol_u && p.pi_out && p.v_out && p.act_out &&
-         p.A == 4;                                          // the maze has four actions (maze_environment.py:98-112)
+         (p.A == 4 || (p.A == 6 && view == kFirstPerson));
 }
 
 template <int N>

@@ -33,10 +33,23 @@ __device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t index, uin
 // The reference's map (maze_environment.py:18-25) is this same block, built at compile time (kDefaultMaze in maze.hip); a
 // null config means it.
 constexpr int kCfgHdr = 8, kRecHdr = 18;
-constexpr int kMazeRandomStart = 1, kMazeRandomGoal = 2, kMazeShowGoal = 4;
+constexpr int kMazeRandomStart = 1, kMazeRandomGoal = 2, kMazeShowGoal = 4, kMazeNav = 8;
 // counter word 2 of a reset draw: far above any stream id PhiloxDraws hands out (2, 3, ...), so a configured maze's
 // reset draws take nothing from a run's action and replay streams
 constexpr uint32_t kMazeResetStream = 0x4D415A45u;
+// counter word 2 of a navigation maze's respawn draw (word 3: the actor's goals_total, this goal counted); as far from
+// the PhiloxDraws streams as kMazeResetStream
+constexpr uint32_t kMazeRespawnStream = 0x4D415A52u;
+
+// ---- navigation extension (flag kMazeNav, first person only), after the last layout record ------------------------------
+// ext = cfg + kCfgHdr + L * rec:  [0] goal reward  [1] apple reward  [2] hit reward  [3] mode bits (kNavRespawn,
+//   kNavLabActions)  [4..7] 0;  apple record of layout l at ext + kNavHdr + l * kNavRec: [0] n apples (<= 64)  [1 .. n]
+//   apple cells, ascending (apple bit k of an actor is the k-th of them)
+constexpr int kNavHdr = 8, kNavRec = 65, kMaxApples = 64;
+constexpr int kNavRespawn = 1, kNavLabActions = 2;
+// the per-actor record of a navigation maze (the tail's `heading` pointer): heading, apple bits lo, hi, goals_total,
+// apples_total, 0, 0, 0
+constexpr int kNavActorWords = 8;
 
 // The Philox words of global actor g's reset into episode `ep`: word 0 draws the goal, word 1 the start, word 2 the
 // first-person heading.
@@ -66,6 +79,7 @@ __device__ __forceinline__ void maze_reset_cells(const int* cfg, const int* rec,
 }
 
 __device__ __forceinline__ const int* maze_rec(const int* cfg, int lay) { return cfg + kCfgHdr + lay * cfg[6]; }
+__device__ __forceinline__ const int* maze_nav_ext(const int* cfg) { return cfg + kCfgHdr + cfg[1] * cfg[6]; }
 __device__ __forceinline__ int maze_layout(const int* cfg, const int* layout, int b) {
   return layout ? min(max(layout[b], 0), cfg[1] - 1) : 0;
 }

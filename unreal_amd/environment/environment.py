@@ -33,17 +33,22 @@ class Environment(object):
 
     @staticmethod
     def register_maze_config(env_name, layouts, random_start=False, random_goal=False, show_goal=False,
-                             max_episode_steps=0, view="top_down", start_heading=None):
+                             max_episode_steps=0, view="top_down", start_heading=None, goal_reward=1, apple_reward=1,
+                             hit_reward=-1, goal_respawn=False, action_set="turn"):
         """Mazes of `env_name`: `layouts` = N x N maps (strings, or lists of row strings; + wall, - free, S start, G goal),
         N in {7, 12, 14, 21}, up to 1024 of them; global actor g runs layout g * L // (all actors).  random_start /
         random_goal: drawn at every reset, uniformly over the free cells (the start never on the goal); show_goal: the
         goal block in channel 2; max_episode_steps > 0: an episode that has not reached the goal ends (terminal) at
         that step.  view="first_person": a raycast 84 x 84 camera in the agent's cell (actions turn left / right, step
-        forward / back), start_heading None (drawn at every reset) or 0..3.  Raises ValueError on a malformed
-        config."""
+        forward / back), start_heading None (drawn at every reset) or 0..3.  First person only:
+        'A' layout cells hold apples (at most 64 per layout); goal_reward / apple_reward / hit_reward are integers in
+        [-100, 100]; goal_respawn=True (needs max_episode_steps > 0) moves the agent to a start cell at the goal instead
+        of ending the episode; action_set="lab" selects Lab's six actions (look left / right, strafe left / right,
+        forward, back).  Raises ValueError on a malformed config."""
         from .maze_environment import MazeConfig
         Environment.MAZE_CONFIG[env_name] = MazeConfig(layouts, random_start, random_goal, show_goal, max_episode_steps,
-                                                       view, start_heading)
+                                                       view, start_heading, goal_reward, apple_reward, hit_reward,
+                                                       goal_respawn, action_set)
 
     @staticmethod
     def create_environment(env_type, env_name, termination_time=50.0, env_args=None, thread_index=0):
@@ -54,6 +59,9 @@ class Environment(object):
 
     @staticmethod
     def get_action_size(env_type, env_name):
+        conf = Environment.MAZE_CONFIG.get(env_name) if env_type == 'maze' else None
+        if conf is not None and conf.action_set == "lab":
+            return 6                             # a navigation maze with Lab's actions: the class cache is not involved
         if Environment.action_size >= 0:
             return Environment.action_size
         if env_type == 'maze':

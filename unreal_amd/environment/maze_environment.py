@@ -8,7 +8,8 @@ replay ring; `MazeEnvironment` is the reference's batch-1 object surface over th
 `MazeConfig` describes user mazes (Environment.register_maze_config): N x N layouts in the reference map's alphabet, optional
 random start / goal cells drawn at every reset, an optional goal block in channel 2 and an optional episode step limit.
 With view="first_person" the same mazes are seen through a raycast camera (`FirstPersonMazeEnvironment`, maze.hip);
-`batched_maze_environment` picks the class from the config."""
+`batched_maze_environment` picks the class from the config.  First-person configs may be navigation mazes:
+apples ('A' cells), configurable rewards, respawn at the goal and Lab's six actions."""
 from collections import deque
 
 import numpy as np
@@ -31,12 +32,19 @@ class MazeConfig(object):
     tail of the unreal_maze_* entries in include/unreal_hip.h).  Raises ValueError on a malformed configuration."""
     SIZES = (7, 12, 14, 21)          # the grid sizes whose cells tile the 84-px frame: 12, 7, 6, 4 px
     MAX_LAYOUTS = 1024
-    RANDOM_START, RANDOM_GOAL, SHOW_GOAL = 1, 2, 4
+    RANDOM_START, RANDOM_GOAL, SHOW_GOAL, NAV = 1, 2, 4, 8
     HEADER, RECORD_HEADER = 8, 18
     VIEWS = ("top_down", "first_person")
+    # navigation extension after the layout records (maze_common.h): header [goal, apple, hit reward, mode, 0 x 4], then
+    # per layout [n apples, apple cells ascending, padding to 64]
+    NAV_HEADER, NAV_RECORD, MAX_APPLES = 8, 65, 64
+    NAV_RESPAWN, NAV_LAB_ACTIONS = 1, 2
+    ACTION_SETS = ("turn", "lab")
+    MAX_REWARD = 100
 
     def __init__(self, layouts, random_start=False, random_goal=False, show_goal=False, max_episode_steps=0,
-                 view="top_down", start_heading=None):
+                 view="top_down", start_heading=None, goal_reward=1, apple_reward=1, hit_reward=-1,
+                 goal_respawn=False, action_set="turn"):
         if isinstance(layouts, str) or not len(layouts):
             raise ValueError("layouts: a non-empty list of layouts (strings, or lists of row strings)")
         if len(layouts) > self.MAX_LAYOUTS:
@@ -56,15 +64,35 @@ class MazeConfig(object):
                                  % (start_heading,))
             start_heading = int(start_heading)
         self.view, self.start_heading = view, start_heading
+        rewards = dict(goal_reward=goal_reward, apple_reward=apple_reward, hit_reward=hit_reward)
+        for k, v in rewards.items():
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or \
+                    not -self.MAX_REWARD <= v <= self.MAX_REWARD:
+                raise ValueError("%s %r: an integer in [-%d, %d]" % (k, v, self.MAX_REWARD, self.MAX_REWARD))
+        self.goal_reward, self.apple_reward, self.hit_reward = int(goal_reward), int(apple_reward), int(hit_reward)
+        if action_set not in self.ACTION_SETS:
+            raise ValueError("action_set %r: one of %s" % (action_set, self.ACTION_SETS))
+        self.goal_respawn, self.action_set = bool(goal_respawn), action_set
+        nav_options = (self.goal_reward, self.apple_reward, self.hit_reward, self.goal_respawn, action_set) != \
+            (1, 1, -1, False, "turn")
+        if nav_options and view != "first_person":
+            raise ValueError("goal_reward, apple_reward, hit_reward, goal_respawn and action_set are first-person "
+                             "settings; view is %r" % (view,))
+        if self.goal_respawn and self.max_episode_steps == 0:
+            raise ValueError("goal_respawn needs max_episode_steps > 0 (the time-out ends every episode)")
+        if self.goal_respawn and self.random_goal and not self.random_start:
+            raise ValueError("goal_respawn with random_goal needs random_start (a respawn at S could be on the goal)")
         self.layouts = [self._parse(i, lay) for i, lay in enumerate(layouts)]
         sizes = set(int(round(len(m) ** 0.5)) for m in self.layouts)
         if len(sizes) != 1:
             raise ValueError("layouts of one config must share their size; got %s" % sorted(sizes))
         self.N = sizes.pop()
         self.L = len(self.layouts)
-        self.walls, self.start, self.goal, self.free = [], [], [], []
+        self.walls, self.start, self.goal, self.free, self.apples = [], [], [], [], []
         for i, m in enumerate(self.layouts):
             self._check(i, m)
+        # a navigation maze: any of the options above, or an apple in a layout (the default block stays word for word)
+        self.nav = nav_options or any(len(a) for a in self.apples)
 
     def _parse(self, i, lay):
         if isinstance(lay, str):
@@ -77,9 +105,14 @@ class MazeConfig(object):
         n = int(round(len(m) ** 0.5))
         if n * n != len(m) or n not in self.SIZES:
             raise ValueError("layout %d: %d cells; supported are N x N with N in %s" % (i, len(m), self.SIZES))
-        bad = set(m) - set("+-SG")
+        bad = set(m) - set("+-SGA")
         if bad:
-            raise ValueError("layout %d: unknown characters %s (use + wall, - free, S start, G goal)" % (i, sorted(bad)))
+            raise ValueError("layout %d: unknown characters %s (use + wall, - free, S start, G goal, A apple)"
+                             % (i, sorted(bad)))
+        if "A" in m and self.view != "first_person":
+            raise ValueError("layout %d: apples ('A') are a first-person setting; view is %r" % (i, self.view))
+        if m.count("A") > self.MAX_APPLES:
+            raise ValueError("layout %d: %d apples; at most %d per layout" % (i, m.count("A"), self.MAX_APPLES))
         return m
 
     def _check(self, i, m):
@@ -109,17 +142,29 @@ class MazeConfig(object):
         self.start.append(m.index("S") if n_s == 1 else -1)
         self.goal.append(m.index("G") if n_g == 1 else -1)
         self.free.append(np.array(free, dtype=np.int32))
+        self.apples.append(np.array([c for c in range(N * N) if m[c] == "A"], dtype=np.int32))
 
     @property
     def flags(self):
         return (self.RANDOM_START * self.random_start) | (self.RANDOM_GOAL * self.random_goal) | \
-            (self.SHOW_GOAL * self.show_goal)
+            (self.SHOW_GOAL * self.show_goal) | (self.NAV * self.nav)
+
+    @property
+    def action_size(self):
+        return 6 if self.action_set == "lab" else 4
+
+    @property
+    def reward_bound(self):
+        """max |reward| of a step (1 for every config without navigation rewards)."""
+        return max(abs(self.goal_reward), abs(self.apple_reward), abs(self.hit_reward))
 
     def block(self, seed):
         """-> int32 numpy array: header [N, L, flags, max_episode_steps, seed lo, seed hi, record words, start heading + 1
         (first person with a fixed heading; else 0)], then per
         layout [wall bits of cell y*N+x as 7 x (lo, hi) uint32, S cell, G cell, n_free, index of G in the free list,
-        free cells ascending] (-1: none)."""
+        free cells ascending] (-1: none); a navigation maze (flag NAV) appends [goal reward, apple reward, hit reward, mode
+        (1: goal_respawn, 2: Lab's actions), 0, 0, 0, 0] and per layout [n apples, apple cells ascending, 0 padding to
+        65 words]."""
         N, rec = self.N, self.RECORD_HEADER + self.N * self.N
         seed = int(seed) & (2 ** 64 - 1)
         out = np.zeros(self.HEADER + self.L * rec, dtype=np.int64)
@@ -135,6 +180,15 @@ class MazeConfig(object):
             r[14], r[15], r[16] = self.start[l], g, len(free)
             r[17] = int(np.searchsorted(free, g)) if g >= 0 else -1
             r[self.RECORD_HEADER:self.RECORD_HEADER + len(free)] = free
+        if self.nav:
+            ext = np.zeros(self.NAV_HEADER + self.L * self.NAV_RECORD, dtype=np.int64)
+            mode = self.NAV_RESPAWN * self.goal_respawn | self.NAV_LAB_ACTIONS * (self.action_set == "lab")
+            ext[:4] = [self.goal_reward, self.apple_reward, self.hit_reward, mode]
+            for l, a in enumerate(self.apples):
+                r = ext[self.NAV_HEADER + l * self.NAV_RECORD:]
+                r[0] = len(a)
+                r[1:1 + len(a)] = a
+            out = np.concatenate([out, ext])
         return (out & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
 
     def layout_ids(self, actor_base, batch, actors_total):
@@ -158,7 +212,8 @@ class BatchedMazeEnvironment(object):
         `seed`: key of the reset draws."""
         self.B = batch
         self.config = config
-        self.ring = ops.Ring(batch, history_size, torch.device(device), maze_state=config is not None)
+        self.ring = ops.Ring(batch, history_size, torch.device(device), maze_state=config is not None,
+                             nav=config is not None and config.nav)
         self.maze = None
         if config is not None:
             total = batch if actors_total is None else int(actors_total)
@@ -202,6 +257,8 @@ class BatchedMazeEnvironment(object):
                             n_steps, terminal_end, index_parent=False, **nxt):
         """The policy head + action draw of `net` on the feature rows `feat` and rollout_step() in one launch."""
         p = net.p
+        if self.config is not None:
+            nxt["A"] = self.config.action_size
         ops.maze_policy_rollout_step(self.ring, feat, ld, p["W_base_fc_p"], p["b_base_fc_p"], p["W_base_fc_v"],
                                      p["b_base_fc_v"], u, pi_out, v_out, actions, out_reward, out_terminal, active,
                                      active_log_t, n_steps, terminal_end,
@@ -213,7 +270,8 @@ class BatchedMazeEnvironment(object):
 
 class FirstPersonMazeEnvironment(BatchedMazeEnvironment):
     """B first-person views of a configured maze (MazeConfig(view="first_person")), stepped by the maze.hip kernels:
-    actions 0 turn left, 1 turn right, 2 step forward, 3 step back; frames are raycast RGB bytes 0..255."""
+    actions 0 turn left, 1 turn right, 2 step forward, 3 step back; frames are raycast RGB bytes 0..255.
+    With action_set="lab": 0 / 1 look left / right, 2 / 3 strafe left / right, 4 / 5 step forward / back."""
     frame_scale = 1.0 / 255.0          # ring bytes 0..255, read like Lab's obs / 255
 
     def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0):

@@ -7,7 +7,8 @@ image_shape (main.py:196), rewards divided by termination_time.  The maze has no
 such episodes count as failures ("success := terminal").  With `maze=` (a name given to
 Environment.register_maze_config) the actors run that configured maze: success is reaching the goal (terminal with reward
 +1), and a time-out is the environment's own (its max_episode_steps); `max_episode_steps` here bounds episodes only when
-the config sets no limit."""
+the config sets no limit.  On a navigation maze success is an episode with at least one goal, read from the
+per-actor goals_total / apples_total counters; with goal_respawn an episode ends only at its time-out."""
 import torch
 
 from . import ops
@@ -31,6 +32,8 @@ class Evaluate(object):
                     raise KeyError("maze %r: call Environment.register_maze_config(name, layouts, ...) first" % maze)
                 self.maze_config = Environment.MAZE_CONFIG[maze]
             self.env = batched_maze_environment(B, 2, self.device, config=self.maze_config, seed=seed)
+            if self.maze_config is not None and self.maze_config.reward_bound > 1:
+                network.lar_bounded = False    # raw navigation rewards in the LSTM input (Trainer.prepare)
         else:
             from .environment.hostfed_environment import HostFedEnvironment
             if tuple(getattr(simulator, "image_shape", (84, 84))) != tuple(network.image_shape):
@@ -48,7 +51,8 @@ class Evaluate(object):
         self.rewards, self.terminals = z(B, torch.float32), z(B, torch.int32)
 
     def process(self, n_episodes, max_episode_steps=2000, one_episode_per_actor=False):
-        """-> dict(episodes, success_rate, mean_return, return_std, mean_length, timeouts).
+        """-> dict(episodes, success_rate, mean_return, return_std, mean_length, timeouts, goals_per_episode,
+        apples_per_episode).
         `one_episode_per_actor`: count only the FIRST episode of each of the B lock-step actors and stop when all B have
         finished or timed out (n_episodes is ignored).  Stopping at the first n finished episodes instead over-represents
         short episodes whenever actors restart while others are still in their first one."""
@@ -64,7 +68,12 @@ class Evaluate(object):
         cfg = self.maze_config
         env_limit = cfg is not None and cfg.max_episode_steps > 0       # episodes end in the environment
         configured = cfg is not None
+        nav = cfg is not None and cfg.nav
         counted = [False] * B
+        goals, apples = [], []                 # per counted episode
+        if nav:                                # goals_total / apples_total (never zeroed by a reset): per-episode differences
+            tot = ring.nav.view(B, ops.NAV_RECORD)[:, 3:5]
+            ep0 = tot.cpu().numpy().copy()
         if one_episode_per_actor:
             n_episodes = B
         while done < n_episodes:
@@ -86,15 +95,23 @@ class Evaluate(object):
             term = self.terminals.cpu().numpy()
             rew = self.rewards.cpu().numpy()
             score = ring.score_out.cpu().numpy()
+            now = tot.cpu().numpy() if nav else None
             force = torch.zeros(B, dtype=torch.int32)
             ep_r = None
             for b in range(B):
                 steps[b] += 1
                 skip = one_episode_per_actor and counted[b]
+                ended = bool(term[b]) or (not env_limit and steps[b] >= max_episode_steps)
+                if ended and not skip:
+                    n_goals = int(now[b, 0] - ep0[b, 0]) if nav else int(bool(term[b]) and rew[b] == 1.0)
+                    goals.append(n_goals)
+                    apples.append(int(now[b, 1] - ep0[b, 1]) if nav else 0)
+                if ended and nav:
+                    ep0[b] = now[b]
                 if term[b]:
                     if not skip:
                         returns.append(float(score[b])); lengths.append(steps[b]); done += 1
-                        if not configured or rew[b] == 1.0:
+                        if not configured or (goals[-1] > 0 if nav else rew[b] == 1.0):
                             successes += 1
                         else:
                             timeouts += 1              # the configured maze's own time-out
@@ -116,4 +133,5 @@ class Evaluate(object):
         mean = sum(returns) / n
         return dict(episodes=n, success_rate=successes / float(n), mean_return=mean,
                     return_std=(sum((r - mean) ** 2 for r in returns) / n) ** 0.5,
-                    mean_length=sum(lengths) / float(n), timeouts=timeouts)
+                    mean_length=sum(lengths) / float(n), timeouts=timeouts, goals_per_episode=sum(goals) / float(n),
+                    apples_per_episode=sum(apples) / float(n))

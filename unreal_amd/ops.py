@@ -97,7 +97,7 @@ def kernel_timer_stop():
 class Ring(object):
     """Device replay ring + per-actor environment state (layout: include/unreal_hip.h)."""
 
-    def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False):
+    def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False, nav=False):
         self.B, self.H, self.H1 = B, H, H + 1
         self.objective_size = objective_size
         self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
@@ -129,6 +129,11 @@ class Ring(object):
         self.episode = torch.full((B,), -1, dtype=torch.int32, device=device) if maze_state else None
         # first-person views (MazeConfig(view="first_person")): heading 0: +x, 1: +y, 2: -x, 3: -y
         self.heading = z(B, dt=torch.int32) if maze_state else None
+        # navigation mazes (MazeConfig.nav): [B, 8] records (heading, apple bits lo, hi, goals_total, apples_total, 0, 0, 0)
+        # handed to the kernels in place of `heading`, which is then a [B] view of their word 0
+        self.nav = z(B * NAV_RECORD, dt=torch.int32) if maze_state and nav else None
+        if self.nav is not None:
+            self.heading = self.nav.view(B, NAV_RECORD)[:, 0]
 
         self._cur = z(B, dt=torch.int32)
 
@@ -160,10 +165,13 @@ def ring_view(ring, b0, b1):
     for name in ("layout", "ep_steps", "episode", "heading"):
         t = getattr(ring, name)
         setattr(v, name, t[b0:b1] if t is not None else None)
+    nav = getattr(ring, "nav", None)
+    v.nav = nav[b0 * NAV_RECORD:b1 * NAV_RECORD] if nav is not None else None
     return v
 
 
 MAZE_TOP_DOWN, MAZE_FIRST_PERSON = 0, 1       # the `view` of a maze (UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON)
+NAV_RECORD = 8                                # int32 words of a navigation maze's per-actor record (UNREAL_MAZE_NAV_RECORD)
 
 
 def _maze_args(ring, maze):
@@ -173,13 +181,15 @@ def _maze_args(ring, maze):
         return (MAZE_TOP_DOWN, 7, None, 0, None, None, None, None, None)
     view, N, block, actor_base = maze
     _chk(block, "i32", 8, "maze config")
+    nav = getattr(ring, "nav", None)
     arrays = (("goal", 2 * ring.B), ("layout", ring.B), ("ep_steps", ring.B), ("episode", ring.B))
     if view == MAZE_FIRST_PERSON:
-        arrays += (("heading", ring.B),)
+        arrays += (("nav", NAV_RECORD * ring.B),) if nav is not None else (("heading", ring.B),)
     for name, n in arrays:
         _chk(getattr(ring, name), "i32", n, "ring." + name)
+    heading = nav if nav is not None and view == MAZE_FIRST_PERSON else ring.heading
     return (int(view), int(N), ptr(block), int(actor_base), ptr(ring.goal), ptr(ring.layout), ptr(ring.ep_steps),
-            ptr(ring.episode), ptr(ring.heading))
+            ptr(ring.episode), ptr(heading))
 
 
 def _ring_args(ring, out_reward, out_terminal):
@@ -235,10 +245,11 @@ def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, act
                              active_log_t, n_steps, terminal_end, next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=4,
                              base_actor=0, maze=None):
     """policy_step + maze_rollout_step in one launch: the workgroup that steps an actor computes its pi / V / action first
-    (bit-identical to the two launches)."""
+    (bit-identical to the two launches).  A = 6: a first-person navigation maze with Lab's action set."""
     B = ring.B
-    if A != 4:
-        raise ValueError("the maze has 4 actions")
+    nav = maze is not None and maze[0] == MAZE_FIRST_PERSON and getattr(ring, "nav", None) is not None
+    if A != 4 and not (A == 6 and nav):
+        raise ValueError("the maze has 4 actions (6: a first-person navigation maze with action_set='lab'); A = %r" % (A,))
     _chk(X, "f32", (B - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A); _chk(bp, "f32", A); _chk(Wv, "f32", 256)
     _chk(bv, "f32", 1); _chk(u, "f64", B, "u"); _chk(pi_out, "f32", B * A); _chk(v_out, "f32", B)
     _chk(actions, "i32", B, "actions")

@@ -181,7 +181,9 @@ class Trainer(object):
         self.local_network.bind_frame_scale(self.environment.frame_scale)
         # [last action | last reward] columns of the LSTM input: within 1 for the maze (rewards -1 / 0 / +1); host-fed
         # actors feed raw rewards and measurement vectors, whose maximum is reduced per pass (model.encode_rows)
-        self.local_network.lar_bounded = self.env_type == "maze"
+        # (navigation mazes with a reward beyond 1 feed it raw too: experience.py, unclipped)
+        conf = Environment.MAZE_CONFIG.get(self.env_name) if self.env_type == "maze" else None
+        self.local_network.lar_bounded = self.env_type == "maze" and (conf is None or conf.reward_bound <= 1)
         self.experience = Experience(self.experience_history_size, ring=self.full_ring)
         B = self.Bg                                  # everything below is sized for ONE group
         lstm = self.use_lstm
