@@ -103,42 +103,39 @@ int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, cons
                                     float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A, int idx_base_actor,
                                     int view, int N, const int* cfg, int actor_base, int* goal, int* layout,
                                     int* ep_steps, int* episode, int* heading, void* stream);
-/* host-fed environments (environment/lab_environment.py:78-119 contract): `staged` holds one uint8
- * frame per actor (post-reset observation where terminals[b] != 0) */
-int unreal_hostfed_step(int B, int H1, const uint8_t* staged, const int* actions, const float* rewards,
-                        const int* terminals, const int* active, int* last_action, float* last_reward, int* count,
-                        uint8_t* frames, float* r_reward, int* r_action, int* r_terminal, int* r_last_action,
-                        float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
-                        float* episode_reward, float* score_out, int* score_valid, int reset_on_terminal,
-                        int track_score, int clip_reward, float pc_denom, void* stream);
-int unreal_hostfed_reset(int B, int H1, const int* mask, const uint8_t* staged, int* last_action, float* last_reward,
-                         const int* count, uint8_t* frames, void* stream);
-/* indoor environments at any frame size H x W, 20 <= H, W <= 480 (environment/indoor_environment.py:63-139 with the
- * MINOS config's height / width, main.py:196): unreal_hostfed_step / _reset with `frame_stride` bytes per frame in
- * `staged` and in the ring (a multiple of 16, >= H * W * 3).  Rewards (divided by termination_time on the host,
- * indoor_environment.py:111), the replay fields and the terminal rules are those of unreal_hostfed_step; the objective
- * goes through unreal_objective_put as there.  No pixel change is computed and the ring's r_pc is not an argument: pixel
- * control is 84 x 84 only (model/model.py:416-430,554). */
-int unreal_hostfed_step_hw(int B, int H1, int H, int W, long frame_stride, const uint8_t* staged, const int* actions,
-                           const float* rewards, const int* terminals, const int* active, int* last_action,
-                           float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
-                           int* r_terminal, int* r_last_action, float* r_last_reward, float* out_reward,
-                           int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
-                           int reset_on_terminal, int track_score, int clip_reward, void* stream);
-int unreal_hostfed_reset_hw(int B, int H1, int H, int W, long frame_stride, const int* mask, const uint8_t* staged,
-                            int* last_action, float* last_reward, const int* count, uint8_t* frames, void* stream);
-/* gym / Atari environments (environment/gym_environment.py:18-96).  unreal_frame_resize: src [n][Hs][Ws][3] raw uint8
- * frames -> dst [n][84][84][3], cv2 INTER_LINEAR's half-pixel rule in fp32 rounded to nearest-even (csrc/gym.hip); rows
- * with mask[i] == 0 are skipped (mask nullable).  unreal_gym_step: unreal_hostfed_step with the gym terminal rule -- the
- * pixel change of a terminal step is taken against its terminal observation (`staged`), the next slot receives
- * `reset_staged` (the post-reset observation) where terminal and reset_on_terminal; rewards are stored raw. */
+/* host-fed environments (environment/hostfed_environment.py): environment.process + experience.add_frame of
+ * every actor where active[b] != 0, for simulators on the host.  `staged` holds one uint8 frame per actor, frame_stride
+ * bytes apart as in the ring (a multiple of 16 within [1200, 691200]: 20 x 20 x 3 .. 480 x 480 x 3 rounded up to 16).
+ * r_pc nullable: the pixel change over pc_denom (> 0) against the stored frame, 84 x 84 only (frame_stride 21168).
+ * flags: UNREAL_HOSTFED_CLIP_REWARD stores np.clip(reward, -1, 1) as the slot's reward and last reward (the environment's
+ * own last_reward stays raw); UNREAL_HOSTFED_TERMINAL_OBS is the gym terminal rule: `staged` holds the terminal
+ * observation of a terminal step and its pixel change is taken against it, and the next slot receives reset_staged (the
+ * post-reset observation; required where reset_on_terminal, NULL without the flag) where terminal and reset_on_terminal.
+ * Without it a terminal step's pixel change is 0 and `staged` holds the post-reset observation.  The three contracts:
+ *   Lab     (lab_environment.py:78-119)     frame_stride 21168, r_pc, UNREAL_HOSTFED_CLIP_REWARD
+ *   indoor  (indoor_environment.py:63-139)  any frame_stride (the MINOS config's height x width, main.py:196), r_pc at
+ *                                           84 x 84 only (pixel control, model/model.py:416-430,554), no flags; rewards
+ *                                           are divided by termination_time on the host (:111) and the objective goes
+ *                                           through unreal_objective_put
+ *   gym     (gym_environment.py:18-96)      frame_stride 21168 (after unreal_frame_resize), r_pc,
+ *                                           UNREAL_HOSTFED_TERMINAL_OBS, reset_staged; rewards stored raw
+ * active, out_reward, out_terminal nullable; episode_reward / score_out / score_valid required with track_score; staged,
+ * reset_staged and frames 16-byte aligned. */
+#define UNREAL_HOSTFED_CLIP_REWARD 1
+#define UNREAL_HOSTFED_TERMINAL_OBS 2
+int unreal_hostfed_step(int B, int H1, int frame_stride, const uint8_t* staged, const uint8_t* reset_staged,
+                        const int* actions, const float* rewards, const int* terminals, const int* active,
+                        int* last_action, float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                        int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                        int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                        int reset_on_terminal, int track_score, int flags, float pc_denom, void* stream);
+/* env.reset() of every actor where mask[b] != 0 (mask nullable): the staged post-reset observation becomes the current one */
+int unreal_hostfed_reset(int B, int H1, int frame_stride, const int* mask, const uint8_t* staged, int* last_action,
+                         float* last_reward, const int* count, uint8_t* frames, void* stream);
+/* gym / Atari raw frames (environment/gym_environment.py:18-23): src [n][Hs][Ws][3] uint8 -> dst [n][84][84][3], cv2
+ * INTER_LINEAR's half-pixel rule in fp32 rounded to nearest-even (csrc/gym.hip); rows with mask[i] == 0 are skipped (mask
+ * nullable). */
 int unreal_frame_resize(int n, int Hs, int Ws, const uint8_t* src, const int* mask, uint8_t* dst, void* stream);
-int unreal_gym_step(int B, int H1, const uint8_t* staged, const uint8_t* reset_staged, const int* actions,
-                    const float* rewards, const int* terminals, const int* active, int* last_action, float* last_reward,
-                    int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal, int* r_last_action,
-                    float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
-                    float* score_out, int* score_valid, int reset_on_terminal, int track_score, float pc_denom,
-                    void* stream);
 /* generic _calc_pixel_change on stored uint8 frames: out[n][400] = sum_{4x4x3}|new-old| / denom */
 int unreal_pixel_change_u8(int N, const uint8_t* frames, const int* idx_new, const int* idx_old,
                            float denom, float* out, void* stream);

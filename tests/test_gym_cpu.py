@@ -142,13 +142,20 @@ def test_frame_resize_argument_checks():
     assert L.call("unreal_frame_resize", 1, 210, 160, src, None, buf(offset=4), None) == EINVAL     # misaligned dst
 
 
-def test_gym_step_argument_checks():
+def test_hostfed_step_argument_checks():
+    """unreal_hostfed_step refuses on the host what any of the three contracts (Lab, indoor, gym) refused."""
     L, buf = _lib(), _Buf()
     p = [buf() for _ in range(20)]
+    CLIP, TERMINAL_OBS = 1, 2
+    r = dict(last_action=p[5], last_reward=p[6], r_reward=p[9], r_action=p[10], r_terminal=p[11], r_last_action=p[12],
+             r_last_reward=p[13])
 
-    def call(B=2, H1=4, staged=p[0], reset=p[1], reset_on_terminal=1, track=0, denom=48.0 * 255.0):
-        return L.call("unreal_gym_step", B, H1, staged, reset, p[2], p[3], p[4], None, p[5], p[6], p[7], p[8], p[9], p[10],
-                      p[11], p[12], p[13], p[14], None, None, None, None, None, reset_on_terminal, track, denom, None)
+    def call(B=2, H1=4, stride=21168, staged=p[0], reset=p[1], frames=p[8], r_pc=p[14], reset_on_terminal=1, track=0,
+             flags=TERMINAL_OBS, denom=48.0 * 255.0, **kw):
+        q = dict(r, **kw)
+        return L.call("unreal_hostfed_step", B, H1, stride, staged, reset, p[2], p[3], p[4], None, q["last_action"],
+                      q["last_reward"], p[7], frames, q["r_reward"], q["r_action"], q["r_terminal"], q["r_last_action"],
+                      q["r_last_reward"], r_pc, None, None, None, None, None, reset_on_terminal, track, flags, denom, None)
 
     assert call(B=0) == EINVAL
     assert call(H1=1) == EINVAL
@@ -158,6 +165,18 @@ def test_gym_step_argument_checks():
     assert call(denom=0.0) == EINVAL
     assert call(staged=buf(offset=8)) == EINVAL          # misaligned
     assert call(reset=buf(offset=4)) == EINVAL
+    assert call(frames=buf(offset=4)) == EINVAL
+    # the Lab and indoor checks, now the same entry's
+    assert call(stride=21168 + 8) == EINVAL              # not a multiple of 16
+    assert call(stride=1200 - 16, r_pc=None) == EINVAL   # below 20 x 20 x 3
+    assert call(stride=691200 + 16, r_pc=None) == EINVAL  # above 480 x 480 x 3
+    assert call(stride=1200) == EINVAL                   # pixel change at 84 x 84 only
+    assert call(flags=CLIP) == EINVAL                    # reset_staged without the gym terminal rule
+    assert call(flags=0, reset=None, denom=0.0) == EINVAL
+    assert call(flags=4) == EINVAL                       # no such flag
+    for name in r:                                       # every pointer the step writes through
+        assert call(**{name: None}) == EINVAL, name
+        assert call(flags=CLIP, reset=None, **{name: None}) == EINVAL, name
 
 
 @pytest.mark.parametrize("A", [0, 19])

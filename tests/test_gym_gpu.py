@@ -89,7 +89,7 @@ def test_frame_resize_matches_formula(ops, shape, n):
     np.testing.assert_array_equal(g2[mask == 1], got[mask == 1])
 
 
-def test_gym_step_terminal_pixel_change_and_reset(ops):
+def test_gym_terminal_obs_pixel_change_and_reset(ops):
     """A terminal step's pixel change is taken against the terminal observation (gym_environment.py:86), not 0 as for Lab;
     the next slot gets the post-reset observation, last action / reward are reset, the reward is stored raw."""
     from oracle.maze import calc_pixel_change
@@ -103,7 +103,8 @@ def test_gym_step_terminal_pixel_change_and_reset(ops):
     actions = np.array([7, 17, 2], np.int32)
     rewards = np.array([3.0, -1.0, 12.0], np.float32)
     terminals = np.array([1, 0, 1], np.int32)
-    ops.gym_step(ring, dev(f1.reshape(-1)), dev(fr.reshape(-1)), dev(actions), dev(rewards), dev(terminals))
+    ops.hostfed_step(ring, dev(f1.reshape(-1)), dev(actions), dev(rewards), dev(terminals), clip_reward=False,
+                     reset_staged=dev(fr.reshape(-1)), terminal_obs=True)
     H1 = H + 1
     pc = ring.r_pc.cpu().numpy().reshape(B, H1, 20, 20)
     frames = ring.frames.cpu().numpy().reshape(B, H1, 84, 84, 3)

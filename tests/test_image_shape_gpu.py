@@ -181,10 +181,10 @@ def _mirror_step(st, H1, staged, actions, rewards, terminals, active, reset_on_t
 
 
 @pytest.mark.parametrize("shape", [(100, 90), (120, 160), (20, 20)])
-def test_hostfed_step_hw_matches_numpy_mirror(ops, shape):
-    """unreal_hostfed_step_hw / _reset_hw write the ring (frames at ring.frame_stride), rewards as given (the indoor
-    wrapper divides by termination_time on the host), the replay fields, the terminal / discard rules and the per-actor
-    state exactly as a numpy mirror; the stride padding and r_pc are never written."""
+def test_hostfed_step_at_frame_size_matches_numpy_mirror(ops, shape):
+    """unreal_hostfed_step / _reset at another frame size (no pixel change) write the ring (frames at ring.frame_stride),
+    rewards as given (the indoor wrapper divides by termination_time on the host), the replay fields, the terminal /
+    discard rules and the per-actor state exactly as a numpy mirror; the stride padding and r_pc are never written."""
     H, W = shape
     B, Hist = 5, 3
     H1 = Hist + 1
@@ -208,7 +208,7 @@ def test_hostfed_step_hw_matches_numpy_mirror(ops, shape):
 
     fr0 = rs.randint(0, 256, size=(B, fb)).astype(np.uint8)
     s0 = staged_of(fr0)
-    ops.hostfed_reset_hw(ring, torch.from_numpy(s0.reshape(-1)).to(DEV))
+    ops.hostfed_reset(ring, torch.from_numpy(s0.reshape(-1)).to(DEV))
     for b in range(B):
         st["frames"][b, 0] = s0[b]
     for step in range(9):
@@ -218,15 +218,15 @@ def test_hostfed_step_hw_matches_numpy_mirror(ops, shape):
         r = (rs.randint(-8, 9, size=B) / 8.0).astype(np.float32)
         t = (rs.random_sample(B) < 0.3).astype(np.int32)
         act = (rs.random_sample(B) < 0.8).astype(np.int32) if step % 3 == 2 else None
-        ops.hostfed_step_hw(ring, torch.from_numpy(s.reshape(-1)).to(DEV), torch.from_numpy(a).to(DEV),
-                            torch.from_numpy(r).to(DEV), torch.from_numpy(t).to(DEV),
-                            None if act is None else torch.from_numpy(act).to(DEV))
+        ops.hostfed_step(ring, torch.from_numpy(s.reshape(-1)).to(DEV), torch.from_numpy(a).to(DEV),
+                         torch.from_numpy(r).to(DEV), torch.from_numpy(t).to(DEV),
+                         None if act is None else torch.from_numpy(act).to(DEV), clip_reward=False)
         _mirror_step(st, H1, s, a, r, t, act)
         if step == 5:                                # a masked reset of two actors
             m = np.array([1, 0, 0, 1, 0], np.int32)
             fr = rs.randint(0, 256, size=(B, fb)).astype(np.uint8)
             s = staged_of(fr)
-            ops.hostfed_reset_hw(ring, torch.from_numpy(s.reshape(-1)).to(DEV), torch.from_numpy(m).to(DEV))
+            ops.hostfed_reset(ring, torch.from_numpy(s.reshape(-1)).to(DEV), torch.from_numpy(m).to(DEV))
             for b in np.nonzero(m)[0]:
                 st["frames"][b, st["count"][b] % H1] = s[b]
                 st["last_action"][b], st["last_reward"][b] = 0, 0.0
@@ -240,9 +240,10 @@ def test_hostfed_step_hw_matches_numpy_mirror(ops, shape):
     assert st["r_terminal"].any() and (st["count"] > H1).any()
 
 
-def test_ring_of_84_frames_is_unchanged(ops):
-    """The default ring keeps FRAME_BYTES per frame, and at 84 x 84 the _hw ingest writes exactly what
-    unreal_hostfed_step writes (pixel change aside)."""
+def test_ring_of_84_frames_is_unchanged_without_pixel_change(ops):
+    """The default ring keeps FRAME_BYTES per frame, and at 84 x 84 the ingest without pixel change (r_pc NULL, the
+    indoor contract at other sizes) writes exactly what the one with it writes (pixel change aside)."""
+    from unreal_amd._lib import lib, ptr, stream
     B, Hist = 4, 3
     H1 = Hist + 1
     assert ops.frame_stride(84, 84) == ops.FRAME_BYTES
@@ -253,17 +254,26 @@ def test_ring_of_84_frames_is_unchanged(ops):
         ring.frames.zero_()
     s0 = torch.from_numpy(rs.randint(0, 256, size=B * ops.FRAME_BYTES).astype(np.uint8)).to(DEV)
     ops.hostfed_reset(rings[0], s0)
-    ops.hostfed_reset_hw(rings[1], s0)
+    ops.hostfed_reset(rings[1], s0)
+    rings[1].r_pc.fill_(SENT)
+
+    def step_without_pc(ring, s, a, r, t):         # ops.hostfed_step passes r_pc at 84 x 84: the entry, r_pc NULL
+        lib().call("unreal_hostfed_step", B, H1, ring.frame_stride, ptr(s), None, ptr(a), ptr(r), ptr(t), None,
+                   ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward),
+                   ptr(ring.r_action), ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward), None, None,
+                   None, ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid), 1, 0, 0, 48.0 * 255.0,
+                   stream())
     for step in range(7):
         s = torch.from_numpy(rs.randint(0, 256, size=B * ops.FRAME_BYTES).astype(np.uint8)).to(DEV)
         a = torch.from_numpy(rs.randint(0, 3, size=B).astype(np.int32)).to(DEV)
         r = torch.from_numpy((rs.randint(-8, 9, size=B) / 4.0).astype(np.float32)).to(DEV)
         t = torch.from_numpy((rs.random_sample(B) < 0.3).astype(np.int32)).to(DEV)
         ops.hostfed_step(rings[0], s, a, r, t, clip_reward=False)
-        ops.hostfed_step_hw(rings[1], s, a, r, t, clip_reward=False)
+        step_without_pc(rings[1], s, a, r, t)
     for k in ("frames", "count", "last_action", "last_reward", "r_reward", "r_action", "r_terminal", "r_last_action",
               "r_last_reward"):
         assert torch.equal(getattr(rings[0], k), getattr(rings[1], k)), k
+    assert (rings[1].r_pc.cpu().numpy() == SENT).all()
 
 
 # ---- end to end --------------------------------------------------------------------------------------------------

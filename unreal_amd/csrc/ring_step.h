@@ -1,6 +1,5 @@
 // The replay ring's add_frame (the reference's train/experience.py:63-93) and the rollout loop's per-actor bookkeeping
-// (train/trainer.py:236-296), shared by every environment step kernel: the maze's (maze.hip), the host-fed ones (env.hip)
-// and gym's (gym.hip).
+// (train/trainer.py:236-296), shared by every environment step kernel: the maze's (maze.hip) and the host-fed one (env.hip).
 //
 // Layout: every actor owns H1 = history_size + 1 physical ring slots.  The observation the policy is about to act on
 // already lives in slot (count % H1) -- a step writes s_{t+1} straight into the slot that the NEXT add_frame will commit,

@@ -4,7 +4,8 @@
 does what the reference's worker process does per command (gym_environment.py:25-50): an action is repeated 4 times, the
 rewards summed, the repeat stops at a terminal.  It hands RAW uint8 frames [n, Hs, Ws, 3] to the host-fed environment,
 which stages them as they are; the resize to 84 x 84 (preprocess_frame, :18-23) runs on the device (ops.frame_resize) and
-the ring commit follows the gym terminal rule (ops.gym_step).  Rewards are not clipped (this fork's train/experience.py).
+the ring commit follows the gym terminal rule (ops.hostfed_step, terminal_obs).  Rewards are not clipped (this fork's
+train/experience.py).
 
 gym and cv2 are not in the image: `SyntheticAtariEnv` is a deterministic stand-in with the Atari frame shape."""
 import numpy as np

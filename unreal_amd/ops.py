@@ -16,7 +16,7 @@ GEMM_RELU, GEMM_ACCUM, GEMM_ATOMIC, GEMM_RELU_MASK, GEMM_RELU_BITS = 1, 2, 4, 8,
 RELU_WORDS = 162                      # uint16 words of ReLU bits per frame (2592 / 16)
 
 FRAME_SHAPE = (84, 84)                # maze, Lab, gym and the default indoor frame
-FRAME_HW_MIN, FRAME_HW_MAX = 20, 480  # frame sizes of the indoor contract (encoder_hw_fwd / hostfed_step_hw)
+FRAME_HW_MIN, FRAME_HW_MAX = 20, 480  # frame sizes of the indoor contract (encoder_hw_fwd / hostfed_step)
 
 
 def frame_dims(H, W):
@@ -301,49 +301,37 @@ def replay_sample_rp(ring, coin, u, rp_idx, rp_class, mode=0):
           ptr(ring.r_reward), ptr(rp_idx), ptr(rp_class), int(mode))
 
 
+HOSTFED_CLIP_REWARD, HOSTFED_TERMINAL_OBS = 1, 2   # unreal_hostfed_step flags (UNREAL_HOSTFED_*)
+
+
 def hostfed_step(ring, staged, actions, rewards, terminals, active=None, out_reward=None, out_terminal=None,
-                 reset_on_terminal=True, track_score=False, clip_reward=True, pc_denom=48.0 * 255.0):
+                 reset_on_terminal=True, track_score=False, clip_reward=True, pc_denom=48.0 * 255.0, reset_staged=None,
+                 terminal_obs=False):
+    """One step of host-fed actors (include/unreal_hip.h: Lab, indoor and gym): `staged` holds one frame per actor,
+    ring.frame_stride bytes apart.  The pixel change goes to ring.r_pc at 84 x 84 only.  terminal_obs: gym's terminal rule,
+    with `reset_staged` the post-reset observations the next slot gets where terminal (required with reset_on_terminal)."""
     B = ring.B
-    _chk(staged, "u8", B * FRAME_BYTES, "staged"); _chk(actions, "i32", B); _chk(rewards, "f32", B)
-    _chk(terminals, "i32", B); _chk(active, "i32", B, optional=True)
-    _chk(out_reward, "f32", B, optional=True); _chk(out_terminal, "i32", B, optional=True)
-    _call("unreal_hostfed_step", B, ring.H1, ptr(staged), ptr(actions), ptr(rewards), ptr(terminals), ptr(active),
-          ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward),
-          ptr(ring.r_action), ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc),
-          ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid),
-          int(reset_on_terminal), int(track_score), int(clip_reward), float(pc_denom))
+    frame_dims(*ring.frame_shape)
+    pc = ring.frame_shape == FRAME_SHAPE
+    _chk(staged, "u8", B * ring.frame_stride, "staged")
+    _chk(reset_staged, "u8", B * ring.frame_stride, "reset_staged", optional=not (terminal_obs and reset_on_terminal))
+    _chk(actions, "i32", B, "actions"); _chk(rewards, "f32", B, "rewards"); _chk(terminals, "i32", B, "terminals")
+    _chk(active, "i32", B, "active", optional=True)
+    _chk(out_reward, "f32", B, "out_reward", optional=True); _chk(out_terminal, "i32", B, "out_terminal", optional=True)
+    flags = (HOSTFED_CLIP_REWARD if clip_reward else 0) | (HOSTFED_TERMINAL_OBS if terminal_obs else 0)
+    _call("unreal_hostfed_step", B, ring.H1, ring.frame_stride, ptr(staged), ptr(reset_staged), ptr(actions),
+          ptr(rewards), ptr(terminals), ptr(active), ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count),
+          ptr(ring.frames), ptr(ring.r_reward), ptr(ring.r_action), ptr(ring.r_terminal), ptr(ring.r_last_action),
+          ptr(ring.r_last_reward), ptr(ring.r_pc) if pc else None, ptr(out_reward), ptr(out_terminal),
+          ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid), int(reset_on_terminal), int(track_score),
+          flags, float(pc_denom))
 
 
 def hostfed_reset(ring, staged, mask=None):
-    _chk(staged, "u8", ring.B * FRAME_BYTES, "staged"); _chk(mask, "i32", ring.B, optional=True)
-    _call("unreal_hostfed_reset", ring.B, ring.H1, ptr(mask), ptr(staged), ptr(ring.last_action),
-          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames))
-
-
-def hostfed_step_hw(ring, staged, actions, rewards, terminals, active=None, out_reward=None, out_terminal=None,
-                    reset_on_terminal=True, track_score=False, clip_reward=False):
-    """hostfed_step for a ring of ring.frame_shape frames (the indoor contract at any size): `staged` holds one frame per
-    actor, ring.frame_stride bytes apart; no pixel change (ring.r_pc is not written)."""
-    B = ring.B
-    H, W = ring.frame_shape
-    frame_dims(H, W)
-    _chk(staged, "u8", B * ring.frame_stride, "staged"); _chk(actions, "i32", B, "actions")
-    _chk(rewards, "f32", B, "rewards"); _chk(terminals, "i32", B, "terminals")
-    _chk(active, "i32", B, "active", optional=True)
-    _chk(out_reward, "f32", B, "out_reward", optional=True); _chk(out_terminal, "i32", B, "out_terminal", optional=True)
-    _call("unreal_hostfed_step_hw", B, ring.H1, H, W, ring.frame_stride, ptr(staged), ptr(actions), ptr(rewards),
-          ptr(terminals), ptr(active), ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames),
-          ptr(ring.r_reward), ptr(ring.r_action), ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward),
-          ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid),
-          int(reset_on_terminal), int(track_score), int(clip_reward))
-
-
-def hostfed_reset_hw(ring, staged, mask=None):
-    H, W = ring.frame_shape
-    frame_dims(H, W)
+    frame_dims(*ring.frame_shape)
     _chk(staged, "u8", ring.B * ring.frame_stride, "staged"); _chk(mask, "i32", ring.B, "mask", optional=True)
-    _call("unreal_hostfed_reset_hw", ring.B, ring.H1, H, W, ring.frame_stride, ptr(mask), ptr(staged),
-          ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames))
+    _call("unreal_hostfed_reset", ring.B, ring.H1, ring.frame_stride, ptr(mask), ptr(staged), ptr(ring.last_action),
+          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames))
 
 
 def frame_resize(n, Hs, Ws, src, dst, mask=None):
@@ -353,21 +341,6 @@ def frame_resize(n, Hs, Ws, src, dst, mask=None):
         raise ValueError("frame_resize: n=%d Hs=%d Ws=%d" % (n, Hs, Ws))
     _chk(src, "u8", n * Hs * Ws * 3, "src"); _chk(dst, "u8", n * FRAME_BYTES, "dst"); _chk(mask, "i32", n, optional=True)
     _call("unreal_frame_resize", n, Hs, Ws, ptr(src), ptr(mask), ptr(dst))
-
-
-def gym_step(ring, staged, reset_staged, actions, rewards, terminals, active=None, out_reward=None, out_terminal=None,
-             reset_on_terminal=True, track_score=False, pc_denom=48.0 * 255.0):
-    """hostfed_step with the gym terminal rule: `staged` holds the observation after the step (the terminal one where
-    terminal), `reset_staged` the post-reset observation the next slot gets where terminal; rewards are stored raw."""
-    B = ring.B
-    _chk(staged, "u8", B * FRAME_BYTES, "staged"); _chk(reset_staged, "u8", B * FRAME_BYTES, "reset_staged")
-    _chk(actions, "i32", B); _chk(rewards, "f32", B); _chk(terminals, "i32", B); _chk(active, "i32", B, optional=True)
-    _chk(out_reward, "f32", B, optional=True); _chk(out_terminal, "i32", B, optional=True)
-    _call("unreal_gym_step", B, ring.H1, ptr(staged), ptr(reset_staged), ptr(actions), ptr(rewards), ptr(terminals),
-          ptr(active), ptr(ring.last_action), ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), ptr(ring.r_reward),
-          ptr(ring.r_action), ptr(ring.r_terminal), ptr(ring.r_last_action), ptr(ring.r_last_reward), ptr(ring.r_pc),
-          ptr(out_reward), ptr(out_terminal), ptr(ring.episode_reward), ptr(ring.score_out), ptr(ring.score_valid),
-          int(reset_on_terminal), int(track_score), float(pc_denom))
 
 
 def base_returns(B, T, rewards, values, n_steps, boot_v, terminal_end, gamma, R_out, adv_out):
