@@ -35,10 +35,12 @@ extern "C" {
 /* ---- environment (environment/maze_environment.py:50-55,98-128; environment/environment.py:88-102;
  *      train/experience.py:63-93 add_frame; train/trainer.py:194-205,264-296 reset rules) ----------
  * The maze (csrc/maze.hip).  Every maze entry ends in the same maze tail (view, N, cfg, actor_base, goal, layout,
- * ep_steps, episode, heading), in one of three forms:
+ * ep_steps, episode, heading), in one of four forms:
  *   view 0, cfg NULL   the reference's 7 x 7 map, top-down (N must be 7; goal .. heading are not used)
  *   view 0, cfg block  a configured maze, top-down (environment/maze_environment.py MazeConfig)
  *   view 1, cfg block  a configured maze in first person (MazeConfig(view="first_person")); cfg NULL is EINVAL
+ *   view 2, cfg block  a generated maze in first person (MazeConfig(generate=N)); cfg or heading NULL is EINVAL,
+ *                      and so is a layout array: a generated block has no layout records, layout must be NULL
  * `cfg` is the configuration block (int32 words: N, layouts, flags, max_episode_steps, seed, start heading + 1; per
  * layout the wall bits, S / G cells and free-cell list); with a block, goal[2B] (x, y), layout[B], ep_steps[B] and
  * episode[B] (-1 before the first reset) are the per-actor state of the configured maze and are required, and so is
@@ -57,10 +59,25 @@ extern "C" {
  * the layout) set = collected in the running episode; goals_total / apples_total count from the actor's first reset and
  * no reset zeroes them.  Lab's actions: 0 / 1 look left / right, 2 / 3 strafe left / right (-r / +r), 4 / 5 forward /
  * back.  With goal_respawn a goal is not terminal: the actor moves to S or a free cell other than the goal drawn with
- * counter = (actor_base + b, episode, 0x4D415A52, goals_total), word 1, heading word 2 (or the block's fixed one). */
+ * counter = (actor_base + b, episode, 0x4D415A52, goals_total), word 1, heading word 2 (or the block's fixed one).
+ * Generated (first person, flag 16 in the block's word 2, view 2): the block has 0 layouts and no records;
+ * word 6 is still 18 + N * N, and after the header come [goal reward, apple reward, hit reward, mode, gen_loops,
+ * gen_apples, 0, 0] (the rewards and mode are read only with flag 8).  `heading` addresses B records of
+ * UNREAL_MAZE_GEN_RECORD(N) int32: the 8 navigation words above, then the actor's own layout record (wall bits, S = G =
+ * -1, n_free, -1, free cells ascending; 18 + N * N words) and apple record (65 words).  Every reset, the reset entry's
+ * and a step's terminal reset alike, first rewrites the two records for the new episode: rooms at the even cells, R =
+ * (N + 1) / 2 per side; edge e between neighbouring rooms (horizontal first, row-major: e = j (R - 1) + i, cell (2i + 1,
+ * 2j); then vertical: e = R (R - 1) + j R + i, cell (2i, 2j + 1)) has the key (w << 8) | e with w = word e & 3 of the
+ * draw with counter (actor_base + b, episode, 0x4D415A47, e >> 2); open are the minimum spanning tree of the room grid
+ * under these keys and the gen_loops lightest other edges; apples lie in the gen_apples rooms r = j R + i with the
+ * smallest keys (w << 8) | r from counter (actor_base + b, episode, 0x4D415A41, r >> 2).  Goal, start and heading are
+ * then drawn over that record as for any block.  A view-1 launch on a generated block, a view-2 launch on any other
+ * block and a top-down launch on a generated block write nothing, as a launch with the wrong N. */
 #define UNREAL_MAZE_NAV_RECORD 8
+#define UNREAL_MAZE_GEN_RECORD(N) (8 + 18 + (N) * (N) + 65)
 #define UNREAL_MAZE_TOP_DOWN 0
 #define UNREAL_MAZE_FIRST_PERSON 1
+#define UNREAL_MAZE_FIRST_PERSON_GENERATED 2
 /* env.reset() of every actor where mask[b] != 0 (mask nullable) */
 int unreal_maze_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward, const int* count,
                       uint8_t* frames, int view, int N, const int* cfg, int actor_base, int* goal, int* layout,

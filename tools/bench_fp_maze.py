@@ -5,9 +5,13 @@
     first-person view of the same configured mazes, at B = 512 and B = 4096, N = 7 and N = 21;
   * Trainer.process() ms for full UNREAL at B = 4096 in both views (replay history --history, filled untimed);
   * navigation rows: the step of a navigation block (apples, rewards (10, 1, 0), goal_respawn, Lab's six
-    actions) next to the plain first-person step of the same layouts, and Trainer.process() at A = 6.
+    actions) next to the plain first-person step of the same layouts, and Trainer.process() at A = 6;
+  * generated mazes (--gen-only): the step of a generated block next to the static first-person step of the
+    same N and B, (a) at a 200-step limit, where resets are rare, and (b) at max_episode_steps=1, where every launch
+    resets every actor and the generated block also regenerates its layout: (b) minus its static counterpart is the cost
+    of generation per reset.  Then Trainer.process() on a generated config at B = 4096.
 
-  python tools/bench_fp_maze.py [--launches 200] [--steps 10] [--warmup 3] [--history 100]
+  python tools/bench_fp_maze.py [--launches 200] [--steps 10] [--warmup 3] [--history 100] [--nav-only | --gen-only]
 
 Prints one JSON line per measurement."""
 import argparse
@@ -98,11 +102,36 @@ def main():
     ap.add_argument("--history", type=int, default=100)
     ap.add_argument("--skip-trainer", action="store_true")
     ap.add_argument("--nav-only", action="store_true", help="only the navigation rows and their plain references")
+    ap.add_argument("--gen-only", action="store_true", help="only the generated-maze rows and their static references")
     args = ap.parse_args()
     from unreal_amd.environment.environment import Environment
     from unreal_amd.environment.maze_environment import MazeConfig, batched_maze_environment
     kw = dict(random_start=True, random_goal=True, show_goal=True, max_episode_steps=200)
     nav_kw = dict(goal_reward=10, apple_reward=1, hit_reward=0, goal_respawn=True, action_set="lab")
+    if args.gen_only:
+        for N in (7, 21):       # generated vs static first person, same N, B and step limit, same process
+            for B in (512, 4096):
+                for limit in (200, 1):
+                    res = {}
+                    for what in ("static", "generated"):
+                        okw = dict(kw, max_episode_steps=limit)
+                        cfg = MazeConfig(layouts(N), view="first_person", **okw) if what == "static" else \
+                            MazeConfig(None, view="first_person", generate=N, **okw)
+                        env = batched_maze_environment(B, 3, DEV, config=cfg, seed=1)
+                        res[what] = kernel_ms(env, B, args.launches) * 1e3
+                        del env
+                    print(json.dumps(dict(what="gen_step_kernel", N=N, B=B, max_episode_steps=limit,
+                                          static_us=round(res["static"], 2), generated_us=round(res["generated"], 2),
+                                          diff_us=round(res["generated"] - res["static"], 2),
+                                          ratio=round(res["generated"] / res["static"], 3))), flush=True)
+        if not args.skip_trainer:
+            for name, N in (("bench_gen7", 7), ("bench_gen21", 21)):
+                Environment.register_maze_config(name, None, view="first_person", generate=N, **kw)
+                ms, wall = trainer_ms(name, 4096, args.history, args.steps, args.warmup)
+                print(json.dumps(dict(what="trainer_process", view="first_person_generated", N=N, B=4096,
+                                      history=args.history, ms_per_call=round(ms, 3), wall_ms_per_call=round(wall, 3))),
+                      flush=True)
+        return
     for N in (7, 21):       # navigation vs plain first person: same layouts (apples only in the nav block), same process
         for B in (512, 4096):
             res = {}

@@ -25,7 +25,11 @@
 //             (y-faces) in channel 0, the map border the same shades in channel 1.
 //
 // Navigation blocks (flag kMazeNav) add apples drawn on the floor, the block's rewards, respawn at the goal and
-// Lab's six actions, in the same kernels behind one uniform branch (fp_step / fp_reset<N, NAV>).
+// Lab's six actions, in the same kernels behind one uniform branch (fp_step / fp_reset<N, NAV, GEN>).
+//
+// Generated blocks (flag kMazeGen) have no layout records: every reset writes the actor's own layout and apple
+// records (gen_maze) behind `heading`, and the same step and reset bodies read them from there.  They run in kernels of
+// their own (view kFirstPersonGen), so the kernels of the static blocks carry none of the generator.
 //
 // One workgroup (256 threads) per actor.  The step renders s_{t+1} into LDS (lanes 0..83: one column's DDA each, over
 // the layout's wall bits in LDS; then every thread fills whole frame-row dwords), streams it to the ring slot with 16 B
@@ -38,7 +42,8 @@
 
 namespace {
 
-constexpr int kTopDown = 0, kFirstPerson = 1;      // UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON
+// UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON / UNREAL_MAZE_FIRST_PERSON_GENERATED
+constexpr int kTopDown = 0, kFirstPerson = 1, kFirstPersonGen = 2;
 
 // The reference's map as a configuration block (layout: maze_common.h).
 constexpr const char* kMap =
@@ -220,7 +225,7 @@ struct MazeArgs {
   int* layout;           // [B] layout id
   int* ep_steps;         // [B] steps taken in the running episode
   int* episode;          // [B] episode index (-1 before the first reset)
-  int* heading;          // [B] first person: heading of the camera
+  int* heading;          // [B] first person: heading of the camera; navigation / generated blocks: the per-actor records
   const int* mask;       // reset only (nullable): the actors to reset
 };
 
@@ -232,7 +237,8 @@ __global__ __launch_bounds__(256) void maze_step_kernel(MazeArgs p) {
   const int* cfg = p.cfg;                      // null: the reference map (kDefaultMaze)
   // (uniform) the block's grid size must be the one this kernel was built for: with another N the cell arithmetic would
   // address outside the frame, so nothing is written (documented with the maze entries in unreal_hip.h)
-  if ((cfg ? cfg[0] : 7) != N) return;
+  // (a generated block, which has no layout record and is first person only, counts as another size)
+  if ((cfg ? cfg[0] | (cfg[2] & kMazeGen) << 8 : 7) != N) return;
   __shared__ uint4 wall_img[FRAME_BYTES / 16];
   // the workgroup's actors' scalar state, fetched by one thread per actor while the wall image is built: read inside the
   // per-actor loop, each actor would start with two dependent global round trips (state, then the previous slot's terminal
@@ -354,7 +360,8 @@ __global__ __launch_bounds__(256) void maze_step_kernel(MazeArgs p) {
 template <int N>
 __global__ __launch_bounds__(256) void maze_reset_kernel(MazeArgs p) {
   const int* cfg = p.cfg;
-  if ((cfg ? cfg[0] : 7) != N) return;
+  // (a generated block, which has no layout record and is first person only, counts as another size)
+  if ((cfg ? cfg[0] | (cfg[2] & kMazeGen) << 8 : 7) != N) return;
   __shared__ uint4 wall_img[FRAME_BYTES / 16];
   __shared__ int s_lay[kActorsPerGroup], s_epi[kActorsPerGroup], s_rgoal[kActorsPerGroup], s_rstart[kActorsPerGroup];
   if (threadIdx.x < kActorsPerGroup) {
@@ -562,17 +569,167 @@ __device__ __forceinline__ void nav_respawn(const int* cfg, const int* rec, int 
   heading = cfg[7] ? (cfg[7] - 1) & 3 : (int)(u[2] & 3u);
 }
 
+// ---- generated mazes (flag kMazeGen) ------------------------------------------------------------------------
+// The layout of global actor g's episode `ep` is a pure function of (seed, g, ep, N, loops, apples): rooms at the even
+// cells, R = (N + 1) / 2 per side; edge e between neighbouring rooms (horizontal first, row-major, then vertical) has the
+// key (w << 8) | e, w = word e & 3 of Philox(key = seed, counter = (g, ep, kMazeGenStream, e >> 2)); the open edges are
+// the minimum spanning tree of the room grid under these keys plus the `loops` lightest other edges.  Apples: the
+// `apples` rooms with the smallest keys (w << 8) | r from counter (g, ep, kMazeAppleStream, r >> 2).
+template <int N>
+struct GenLds {                        // the generator's scratch: aliases FpLds<N>::img, which is rendered afterwards
+  static constexpr int R = (N + 1) / 2, E = 2 * R * (R - 1), RR = R * R;
+  uint64_t key[E];                     // edge keys
+  uint64_t akey[RR];                   // room (apple) keys
+  uint32_t sorted[E];                  // rank -> room a | room b << 7 | the edge's cell << 14
+  uint32_t walls[14];                  // wall bits of cell y * N + x
+  int wave_free[8];                    // free cells per wave and pass
+  int wave_apples;                     // apples among wave 0's rooms
+};
+static_assert(GenLds<21>::E <= 256 && GenLds<21>::RR <= 128 && sizeof(GenLds<21>) <= sizeof(uint4) * kChunks, "generator scratch");
+
+__device__ __forceinline__ uint32_t gen_weight(uint64_t seed, int g, int ep, uint32_t stream, int i) {
+  uint32_t u[4];
+  philox4x32_10(seed, (uint64_t)(uint32_t)g | ((uint64_t)(uint32_t)ep << 32),
+                (uint64_t)stream | ((uint64_t)(uint32_t)(i >> 2) << 32), u);
+  const int k = i & 3;                 // (selects: a dynamically indexed register array is placed in scratch)
+  return k == 0 ? u[0] : k == 1 ? u[1] : k == 2 ? u[2] : u[3];
+}
+
+// Fills `rec` (the layout and apple records of one actor, in global memory) and s.walls for episode `ep` of global actor
+// g.  Call with the whole workgroup; s.img is overwritten.  Begins and ends with a barrier: on return the record, the wall
+// bits in LDS and nothing else of `s` have changed, and every thread may read them.
+template <int N>
+__device__ __forceinline__ void gen_maze(FpLds<N>& s, const int* cfg, int g, int ep, int* rec) {
+  using G = GenLds<N>;
+  constexpr int R = G::R, E = G::E, RR = G::RR, NN = N * N, EH = R * (R - 1);
+  G& t = *reinterpret_cast<G*>(s.img);
+  const int* ext = maze_nav_ext(cfg);
+  const int loops = min(max(ext[4], 0), E - (RR - 1)), n_apples = min(max(ext[5], 0), min(kMaxApples, RR));
+  const uint64_t seed = (uint64_t)(uint32_t)cfg[4] | ((uint64_t)(uint32_t)cfg[5] << 32);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __syncthreads();                     // every thread is done with s.img
+  uint64_t key = 0, akey = 0;
+  uint32_t packed = 0;
+  int room_cell = 0;
+  if (tid < E) {
+    key = ((uint64_t)gen_weight(seed, g, ep, kMazeGenStream, tid) << 8) | (uint32_t)tid;
+    const bool horiz = tid < EH;
+    const int a = horiz ? (tid / (R - 1)) * R + tid % (R - 1) : tid - EH;      // rooms a and b = a + 1 / a + R
+    const int b = horiz ? a + 1 : a + R;
+    const int cell = 2 * (a / R) * N + 2 * (a % R) + (horiz ? 1 : N);
+    packed = (uint32_t)a | ((uint32_t)b << 7) | ((uint32_t)cell << 14);
+    t.key[tid] = key;
+  }
+  if (tid < RR) {
+    room_cell = 2 * (tid / R) * N + 2 * (tid % R);
+    if (n_apples > 0) {
+      akey = ((uint64_t)gen_weight(seed, g, ep, kMazeAppleStream, tid) << 8) | (uint32_t)tid;
+      t.akey[tid] = akey;
+    }
+  }
+  if (tid < 14) {                      // every cell a wall
+    const int n = min(max(NN - 32 * tid, 0), 32);
+    t.walls[tid] = n == 32 ? ~0u : (1u << n) - 1u;
+  }
+  __syncthreads();
+  if (tid < E) {                       // sort by counting: the keys are distinct
+    int rank = 0;
+    for (int j = 0; j < E; ++j) rank += t.key[j] < key ? 1 : 0;
+    t.sorted[rank] = packed;
+  }
+  bool apple = false;
+  if (tid < RR) {
+    atomicAnd(&t.walls[room_cell >> 5], ~(1u << (room_cell & 31)));
+    if (n_apples > 0) {
+      int rank = 0;
+      for (int j = 0; j < RR; ++j) rank += t.akey[j] < akey ? 1 : 0;
+      apple = rank < n_apples;
+    }
+  }
+  const unsigned long long aballot = __ballot(apple);
+  const int apple_idx = __popcll(aballot & ((1ull << lane) - 1ull));       // + wave 0's count for wave 1's rooms
+  if (tid == 0) t.wave_apples = __popcll(aballot);
+  __syncthreads();
+  // Kruskal on wave 0: the component labels of rooms `lane` and `lane + 64` live in two registers, an edge's labels are
+  // read with v_readlane (the edge is uniform), a union relabels with two selects.  Edges rejected by the tree are opened
+  // while `loops` lasts; the loop ends when the tree is complete and the loops are spent.  The loop body is scalar but for
+  // the five v_readlane and the two relabelling selects; the wall bits are cleared after it, one edge per lane.
+  if (tid < 64) {
+    uint32_t se[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) se[q] = 64 * q + lane < E ? t.sorted[64 * q + lane] : 0u;
+    int c0 = lane, c1 = lane + 64, ntree = 0, extra = 0;
+    bool done = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (64 * q >= E) break;
+      unsigned long long opened = 0;     // (uniform) bit kk: edge 64 q + kk of the sorted list opens
+      for (int kk = 0; kk < min(64, E - 64 * q) && !done; ++kk) {
+        const uint32_t pk = (uint32_t)__builtin_amdgcn_readlane((int)se[q], kk);
+        const int a = pk & 127, b = (pk >> 7) & 127;
+        const int la0 = __builtin_amdgcn_readlane(c0, a & 63), la1 = __builtin_amdgcn_readlane(c1, a & 63);
+        const int lb0 = __builtin_amdgcn_readlane(c0, b & 63), lb1 = __builtin_amdgcn_readlane(c1, b & 63);
+        const int la = a < 64 ? la0 : la1, lb = b < 64 ? lb0 : lb1;
+        const bool join = la != lb, loop = !join && extra < loops;
+        const int from = join ? lb : -1;               // (no label is -1: selects, not a branch)
+        c0 = c0 == from ? la : c0;
+        c1 = c1 == from ? la : c1;
+        ntree += join ? 1 : 0;
+        extra += loop ? 1 : 0;
+        opened |= (unsigned long long)(join || loop) << kk;
+        done = ntree >= RR - 1 && extra >= loops;
+      }
+      if ((opened >> lane) & 1ull) {     // every lane opens its own edge's cell
+        const uint32_t cell = se[q] >> 14;
+        atomicAnd(&t.walls[cell >> 5], ~(1u << (cell & 31)));
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < FpLds<N>::NW) s.walls[tid] = (uint64_t)t.walls[2 * tid] | ((uint64_t)t.walls[2 * tid + 1] << 32);
+  if (tid < kRecHdr) rec[tid] = tid < 14 ? (int)t.walls[tid] : -1;           // (word 16, n_free, is written below)
+  int* arec = rec + kRecHdr + NN;
+  if (tid == 0) arec[0] = n_apples;
+  if (apple) arec[1 + (wave ? t.wave_apples : 0) + apple_idx] = room_cell;     // ascending: room order is cell order
+  // the free list, ascending: a ballot / popcount prefix sum over two passes of 256 cells
+  bool fr[2];
+  int pre[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int c = tid + 256 * q;
+    fr[q] = c < NN && !((t.walls[c >> 5] >> (c & 31)) & 1u);
+    const unsigned long long bal = __ballot(fr[q]);
+    pre[q] = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) t.wave_free[4 * q + wave] = __popcll(bal);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    int off = 0;
+    for (int w = 0; w < 4 * q + wave; ++w) off += t.wave_free[w];
+    if (fr[q]) rec[kRecHdr + off + pre[q]] = tid + 256 * q;
+  }
+  if (tid == 0) {
+    int nf = 0;
+    for (int w = 0; w < 8; ++w) nf += t.wave_free[w];
+    rec[16] = nf;
+  }
+  __syncthreads();                     // the record and s.walls are written; s.img is free again
+}
+
 // The first-person step of one actor per workgroup.  NAV: a navigation block (kMazeNav): the per-actor
-// record behind `heading`, the block's rewards and action set, apples, and respawn at the goal.
-template <int N, bool NAV>
+// record behind `heading`, the block's rewards and action set, apples, and respawn at the goal.  GEN: a generated block
+// (kMazeGen): the layout and apple records are the actor's own, rewritten before the reset draw.
+template <int N, bool NAV, bool GEN>
 __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
   const int* cfg = p.cfg;
   const int b = blockIdx.x;
   const int H1 = p.H1;
-  const int lay = maze_layout(cfg, p.layout, b);
-  const int* rec = maze_rec(cfg, lay);
+  int* const actor = GEN ? p.heading + (size_t)gen_actor_words(N) * b : nullptr;
+  const int lay = GEN ? 0 : maze_layout(cfg, p.layout, b);
+  const int* rec = GEN ? actor + kNavActorWords : maze_rec(cfg, lay);
   const int* ext = NAV ? maze_nav_ext(cfg) : nullptr;
-  const int* arec = NAV ? ext + kNavHdr + lay * kNavRec : nullptr;
+  const int* arec = NAV ? (GEN ? rec + kRecHdr + N * N : ext + kNavHdr + lay * kNavRec) : nullptr;
   const int mode = NAV ? ext[3] : 0;
   fp_load_walls<N>(s, rec);
   if (NAV) {
@@ -609,7 +766,7 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
       old[k] = c < kChunks ? src[c] : make_uint4(0, 0, 0, 0);
     }
   }
-  int* hrec = p.heading + (NAV ? kNavActorWords * b : b);
+  int* hrec = GEN ? actor : p.heading + (NAV ? kNavActorWords * b : b);
   const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
   const int x = p.pos[2 * b], y = p.pos[2 * b + 1], h = hrec[0] & 3;
   const int gx = p.goal[2 * b], gy = p.goal[2 * b + 1];
@@ -712,6 +869,13 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
   int rx = ex, ry = ey, rh = eh, rgx = gx, rgy = gy;
   if (reset) {                           // (uniform) the next episode's first observation goes into the slot instead
     int rg, rs;
+    if constexpr (GEN) {                 // the next episode's maze, before its reset draw and its first view
+      gen_maze<N>(s, cfg, p.actor_base + b, epi + 1, actor + kNavActorWords);
+      if (NAV) {
+        n_apples = min(arec[0], kMaxApples);
+        my_apple = threadIdx.x < n_apples ? arec[1 + threadIdx.x] : -1;
+      }
+    }
     maze_reset_cells(cfg, rec, p.actor_base + b, epi + 1, rg, rs);
     rx = rs % N; ry = rs / N; rgx = rg % N; rgy = rg / N;
     rh = fp_reset_heading(cfg, p.actor_base + b, epi + 1);
@@ -719,7 +883,8 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
       bits = 0;
       fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, 0, rg);
     }
-    fp_render<N, NAV>(s, rx, ry, rh, rgx, rgy, show_goal);     // (its first barrier: every thread is done with the difference)
+    // (static blocks: the render's first barrier separates the difference's readers from its writers)
+    fp_render<N, NAV>(s, rx, ry, rh, rgx, rgy, show_goal);
     fp_store(dst, s.img);
   }
 
@@ -742,33 +907,44 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
   }
 }
 
-template <int N>
-__global__ __launch_bounds__(256) void maze_fp_step_kernel(MazeArgs p) {
+template <int N, bool GEN>
+__device__ __forceinline__ void fp_step_entry(const MazeArgs& p) {
   const int* cfg = p.cfg;
-  if (cfg[0] != N) return;               // (uniform) a block of another grid size: nothing is written
+  // (uniform) a block of another grid size, or a generated block in a static kernel (and the reverse): nothing is written
+  if (cfg[0] != N || (bool)(cfg[2] & kMazeGen) != GEN) return;
   __shared__ FpLds<N> s;
   const bool nav = cfg[2] & kMazeNav;
   // (uniform) a fused policy step whose A is not the block's action count: nothing is written either
   if (p.pol_x && p.A != (nav && (maze_nav_ext(cfg)[3] & kNavLabActions) ? 6 : 4)) return;
-  if (nav) fp_step<N, true>(p, s);
-  else fp_step<N, false>(p, s);
+  if (nav) fp_step<N, true, GEN>(p, s);
+  else fp_step<N, false, GEN>(p, s);
 }
 
-template <int N, bool NAV>
+template <int N>
+__global__ __launch_bounds__(256) void maze_fp_step_kernel(MazeArgs p) { fp_step_entry<N, false>(p); }
+
+// the step of a generated block (view kFirstPersonGen): a kernel of its own, so the generator's registers are not the
+// static step's
+template <int N>
+__global__ __launch_bounds__(256) void maze_fp_gen_step_kernel(MazeArgs p) { fp_step_entry<N, true>(p); }
+
+template <int N, bool NAV, bool GEN>
 __device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
   const int* cfg = p.cfg;
   const int b = blockIdx.x;
-  const int lay = maze_layout(cfg, p.layout, b);
-  const int* rec = maze_rec(cfg, lay);
-  fp_load_walls<N>(s, rec);
+  int* const actor = GEN ? p.heading + (size_t)gen_actor_words(N) * b : nullptr;
+  const int lay = GEN ? 0 : maze_layout(cfg, p.layout, b);
+  const int* rec = GEN ? actor + kNavActorWords : maze_rec(cfg, lay);
+  if constexpr (!GEN) fp_load_walls<N>(s, rec);
   const int g = p.actor_base + b, epi = p.episode[b];
+  if constexpr (GEN) gen_maze<N>(s, cfg, g, epi + 1, actor + kNavActorWords);
   int gc, sc;
   maze_reset_cells(cfg, rec, g, epi + 1, gc, sc);
   const int h = fp_reset_heading(cfg, g, epi + 1);
   const int slot = p.count[b] % p.H1;
   int n_apples = 0, my_apple = -1;
   if (NAV) {
-    const int* arec = maze_nav_ext(cfg) + kNavHdr + lay * kNavRec;
+    const int* arec = GEN ? rec + kRecHdr + N * N : maze_nav_ext(cfg) + kNavHdr + lay * kNavRec;
     n_apples = min(arec[0], kMaxApples);
     if (threadIdx.x < n_apples) my_apple = arec[1 + threadIdx.x];
     if (threadIdx.x < FpLds<N>::NA) s.apples[threadIdx.x] = 0u;
@@ -780,7 +956,7 @@ __device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
   if (threadIdx.x == 0) {
     p.pos[2 * b] = sc % N;
     p.pos[2 * b + 1] = sc / N;
-    int* hrec = p.heading + (NAV ? kNavActorWords * b : b);
+    int* hrec = GEN ? actor : p.heading + (NAV ? kNavActorWords * b : b);
     hrec[0] = h;
     if (NAV) { hrec[1] = 0; hrec[2] = 0; }          // every apple is back; goals_total / apples_total run on
     p.goal[2 * b] = gc % N;
@@ -795,12 +971,23 @@ __device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
 template <int N>
 __global__ __launch_bounds__(256) void maze_fp_reset_kernel(MazeArgs p) {
   const int* cfg = p.cfg;
-  if (cfg[0] != N) return;
+  if ((cfg[0] | (cfg[2] & kMazeGen) << 8) != N) return;               // as in fp_step_entry
   const int b = blockIdx.x;
   if (p.mask && !p.mask[b]) return;
   __shared__ FpLds<N> s;
-  if (cfg[2] & kMazeNav) fp_reset<N, true>(p, s);
-  else fp_reset<N, false>(p, s);
+  if (cfg[2] & kMazeNav) fp_reset<N, true, false>(p, s);
+  else fp_reset<N, false, false>(p, s);
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void maze_fp_gen_reset_kernel(MazeArgs p) {
+  const int* cfg = p.cfg;
+  if ((cfg[0] | (cfg[2] & kMazeGen) << 8) != (N | kMazeGen << 8)) return;
+  const int b = blockIdx.x;
+  if (p.mask && !p.mask[b]) return;
+  __shared__ FpLds<N> s;
+  if (cfg[2] & kMazeNav) fp_reset<N, true, true>(p, s);
+  else fp_reset<N, false, true>(p, s);
 }
 
 
@@ -808,18 +995,21 @@ __global__ __launch_bounds__(256) void maze_fp_reset_kernel(MazeArgs p) {
 enum MazeEntry { kReset, kStep, kRollout, kPolicy };
 
 // The union of what the kernels of the entry write through or read: every pointer non-null, frames 16-byte aligned (both
-// views store 16 B per lane), and the maze tail one of the three forms documented in unreal_hip.h.
+// views store 16 B per lane), and the maze tail one of the four forms documented in unreal_hip.h.
 bool maze_args_ok(MazeEntry e, const MazeArgs& p, int view, int N) {
   if (p.B <= 0 || p.H1 < 2 || !p.pos || !p.last_action || !p.last_reward || !p.count || !p.frames) return false;
   if ((uintptr_t)p.frames & 15) return false;
-  if (view != kTopDown && view != kFirstPerson) return false;
+  if (view != kTopDown && view != kFirstPerson && view != kFirstPersonGen) return false;
   if (!p.cfg) {
     if (view != kTopDown || N != 7) return false;          // the reference's map
-  } else if (!(N == 7 || N == 12 || N == 14 || N == 21) || p.actor_base < 0 || !p.goal || !p.layout || !p.ep_steps ||
-             !p.episode) {
+  } else if (!(N == 7 || N == 12 || N == 14 || N == 21) || p.actor_base < 0 || !p.goal || !p.ep_steps || !p.episode) {
     return false;                                           // grid sizes whose cells tile the 84-px frame: 12, 7, 6, 4 px
+  } else if ((view == kFirstPersonGen) != !p.layout) {
+    // layout ids are required with layout records; a generated block has none (its kernels never read the array), and
+    // a tail that hands one over was built for another view: refused
+    return false;
   }
-  if (view == kFirstPerson && !p.heading) return false;
+  if (view != kTopDown && !p.heading) return false;       // heading[B], or the per-actor records of a navigation / generated block
   if (e == kReset) return true;
   if (!p.r_reward || !p.r_action || !p.r_terminal || !p.r_last_action || !p.r_last_reward || !p.r_pc) return false;
   if (p.track_score && (!p.episode_reward || !p.score_out || !p.score_valid)) return false;
@@ -830,12 +1020,15 @@ bool maze_args_ok(MazeEntry e, const MazeArgs& p, int view, int N) {
   if (e == kRollout) return true;
   // the maze has four actions (maze_environment.py:98-112); a first-person navigation block with Lab's action set six
   return p.pol_x && p.pol_ldx >= LSTM_N && p.Wp && p.bp && p.Wv && p.bv && p.pol_u && p.pi_out && p.v_out && p.act_out &&
-         (p.A == 4 || (p.A == 6 && view == kFirstPerson));
+         (p.A == 4 || (p.A == 6 && view != kTopDown));
 }
 
 template <int N>
 void maze_launch_n(bool reset, int view, const MazeArgs& p, hipStream_t s) {
-  if (view == kFirstPerson) {
+  if (view == kFirstPersonGen) {
+    if (reset) hipLaunchKernelGGL(maze_fp_gen_reset_kernel<N>, dim3(p.B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(maze_fp_gen_step_kernel<N>, dim3(p.B), dim3(256), 0, s, p);
+  } else if (view == kFirstPerson) {
     if (reset) hipLaunchKernelGGL(maze_fp_reset_kernel<N>, dim3(p.B), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(maze_fp_step_kernel<N>, dim3(p.B), dim3(256), 0, s, p);
   } else if (reset) {

@@ -33,7 +33,7 @@ __device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t index, uin
 // The reference's map (maze_environment.py:18-25) is this same block, built at compile time (kDefaultMaze in maze.hip); a
 // null config means it.
 constexpr int kCfgHdr = 8, kRecHdr = 18;
-constexpr int kMazeRandomStart = 1, kMazeRandomGoal = 2, kMazeShowGoal = 4, kMazeNav = 8;
+constexpr int kMazeRandomStart = 1, kMazeRandomGoal = 2, kMazeShowGoal = 4, kMazeNav = 8, kMazeGen = 16;
 // counter word 2 of a reset draw: far above any stream id PhiloxDraws hands out (2, 3, ...), so a configured maze's
 // reset draws take nothing from a run's action and replay streams
 constexpr uint32_t kMazeResetStream = 0x4D415A45u;
@@ -50,6 +50,14 @@ constexpr int kNavRespawn = 1, kNavLabActions = 2;
 // the per-actor record of a navigation maze (the tail's `heading` pointer): heading, apple bits lo, hi, goals_total,
 // apples_total, 0, 0, 0
 constexpr int kNavActorWords = 8;
+
+// ---- generated mazes (flag kMazeGen, first person only): a new layout per actor and episode ------------------
+// The block has L = 0 layout records; word 6 is still the record size kRecHdr + N * N.  ext = cfg + kCfgHdr is the
+// navigation header above (rewards and mode; read only with kMazeNav) with [4] gen_loops  [5] gen_apples.  The tail's
+// `heading` pointer addresses B per-actor records of gen_actor_words(N) words: the navigation actor record (kNavActorWords),
+// then the actor's layout record in the format above (S = G = -1), then its apple record (kNavRec words).
+constexpr uint32_t kMazeGenStream = 0x4D415A47u, kMazeAppleStream = 0x4D415A41u;
+constexpr int gen_actor_words(int N) { return kNavActorWords + kRecHdr + N * N + kNavRec; }
 
 // The Philox words of global actor g's reset into episode `ep`: word 0 draws the goal, word 1 the start, word 2 the
 // first-person heading.

@@ -32,9 +32,10 @@ class Environment(object):
         Environment.GYM_CONFIG[env_name] = a
 
     @staticmethod
-    def register_maze_config(env_name, layouts, random_start=False, random_goal=False, show_goal=False,
+    def register_maze_config(env_name, layouts=None, random_start=False, random_goal=False, show_goal=False,
                              max_episode_steps=0, view="top_down", start_heading=None, goal_reward=1, apple_reward=1,
-                             hit_reward=-1, goal_respawn=False, action_set="turn"):
+                             hit_reward=-1, goal_respawn=False, action_set="turn", generate=None, gen_loops=0,
+                             gen_apples=0):
         """Mazes of `env_name`: `layouts` = N x N maps (strings, or lists of row strings; + wall, - free, S start, G goal),
         N in {7, 12, 14, 21}, up to 1024 of them; global actor g runs layout g * L // (all actors).  random_start /
         random_goal: drawn at every reset, uniformly over the free cells (the start never on the goal); show_goal: the
@@ -44,11 +45,15 @@ class Environment(object):
         'A' layout cells hold apples (at most 64 per layout); goal_reward / apple_reward / hit_reward are integers in
         [-100, 100]; goal_respawn=True (needs max_episode_steps > 0) moves the agent to a start cell at the goal instead
         of ending the episode; action_set="lab" selects Lab's six actions (look left / right, strafe left / right,
-        forward, back).  Raises ValueError on a malformed config."""
+        forward, back).  generate=N (first person, layouts=None, random_start and random_goal): no layouts
+        are given; every reset of an actor writes a new N x N maze on the device, a spanning tree of the rooms at the
+        even cells plus gen_loops extra openings, with gen_apples apples in drawn rooms -- a pure function of (seed,
+        global actor, episode), so training on one seed and evaluating on another tests generalisation over layouts.
+        Raises ValueError on a malformed config."""
         from .maze_environment import MazeConfig
         Environment.MAZE_CONFIG[env_name] = MazeConfig(layouts, random_start, random_goal, show_goal, max_episode_steps,
                                                        view, start_heading, goal_reward, apple_reward, hit_reward,
-                                                       goal_respawn, action_set)
+                                                       goal_respawn, action_set, generate, gen_loops, gen_apples)
 
     @staticmethod
     def create_environment(env_type, env_name, termination_time=50.0, env_args=None, thread_index=0):

@@ -9,7 +9,9 @@ replay ring; `MazeEnvironment` is the reference's batch-1 object surface over th
 random start / goal cells drawn at every reset, an optional goal block in channel 2 and an optional episode step limit.
 With view="first_person" the same mazes are seen through a raycast camera (`FirstPersonMazeEnvironment`, maze.hip);
 `batched_maze_environment` picks the class from the config.  First-person configs may be navigation mazes:
-apples ('A' cells), configurable rewards, respawn at the goal and Lab's six actions."""
+apples ('A' cells), configurable rewards, respawn at the goal and Lab's six actions.  With generate=N a first-person
+config has no layouts: every reset writes a new maze for the actor on the device (DESIGN §7g);
+`MazeConfig.generated_layout` computes the same maze on the host."""
 from collections import deque
 
 import numpy as np
@@ -32,7 +34,8 @@ class MazeConfig(object):
     tail of the unreal_maze_* entries in include/unreal_hip.h).  Raises ValueError on a malformed configuration."""
     SIZES = (7, 12, 14, 21)          # the grid sizes whose cells tile the 84-px frame: 12, 7, 6, 4 px
     MAX_LAYOUTS = 1024
-    RANDOM_START, RANDOM_GOAL, SHOW_GOAL, NAV = 1, 2, 4, 8
+    RANDOM_START, RANDOM_GOAL, SHOW_GOAL, NAV, GENERATED = 1, 2, 4, 8, 16
+    GEN_STREAM, APPLE_STREAM = 0x4D415A47, 0x4D415A41      # Philox counter word 2 of a generated maze's edge / apple draws
     HEADER, RECORD_HEADER = 8, 18
     VIEWS = ("top_down", "first_person")
     # navigation extension after the layout records (maze_common.h): header [goal, apple, hit reward, mode, 0 x 4], then
@@ -42,10 +45,17 @@ class MazeConfig(object):
     ACTION_SETS = ("turn", "lab")
     MAX_REWARD = 100
 
-    def __init__(self, layouts, random_start=False, random_goal=False, show_goal=False, max_episode_steps=0,
+    def __init__(self, layouts=None, random_start=False, random_goal=False, show_goal=False, max_episode_steps=0,
                  view="top_down", start_heading=None, goal_reward=1, apple_reward=1, hit_reward=-1,
-                 goal_respawn=False, action_set="turn"):
-        if isinstance(layouts, str) or not len(layouts):
+                 goal_respawn=False, action_set="turn", generate=None, gen_loops=0, gen_apples=0):
+        self.generate, self.gen_loops, self.gen_apples = None, 0, 0
+        if generate is not None:
+            self._check_generate(layouts, random_start, random_goal, view, generate, gen_loops, gen_apples)
+            layouts = []
+        elif isinstance(gen_loops, (bool, np.bool_)) or isinstance(gen_apples, (bool, np.bool_)) or gen_loops != 0 or \
+                gen_apples != 0:
+            raise ValueError("gen_loops and gen_apples are settings of a generated maze; generate is None")
+        elif layouts is None or isinstance(layouts, str) or not len(layouts):
             raise ValueError("layouts: a non-empty list of layouts (strings, or lists of row strings)")
         if len(layouts) > self.MAX_LAYOUTS:
             raise ValueError("%d layouts: at most %d per config" % (len(layouts), self.MAX_LAYOUTS))
@@ -83,7 +93,7 @@ class MazeConfig(object):
         if self.goal_respawn and self.random_goal and not self.random_start:
             raise ValueError("goal_respawn with random_goal needs random_start (a respawn at S could be on the goal)")
         self.layouts = [self._parse(i, lay) for i, lay in enumerate(layouts)]
-        sizes = set(int(round(len(m) ** 0.5)) for m in self.layouts)
+        sizes = set(int(round(len(m) ** 0.5)) for m in self.layouts) if self.generate is None else {self.generate}
         if len(sizes) != 1:
             raise ValueError("layouts of one config must share their size; got %s" % sorted(sizes))
         self.N = sizes.pop()
@@ -92,7 +102,73 @@ class MazeConfig(object):
         for i, m in enumerate(self.layouts):
             self._check(i, m)
         # a navigation maze: any of the options above, or an apple in a layout (the default block stays word for word)
-        self.nav = nav_options or any(len(a) for a in self.apples)
+        # (a generated maze with apples is one too)
+        self.nav = nav_options or any(len(a) for a in self.apples) or self.gen_apples > 0
+
+    @staticmethod
+    def gen_rooms(N):
+        """(R, E): rooms per side of a generated N x N maze (the even cells) and edges between neighbouring rooms."""
+        R = (N + 1) // 2
+        return R, 2 * R * (R - 1)
+
+    def _check_generate(self, layouts, random_start, random_goal, view, generate, gen_loops, gen_apples):
+        integer = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
+        if layouts is not None:
+            raise ValueError("generate: a generated maze has no layouts (layouts must be None)")
+        if not integer(generate) or generate not in self.SIZES:
+            raise ValueError("generate %r: None, or a grid size N in %s" % (generate, self.SIZES))
+        if view != "first_person":
+            raise ValueError("generate is a first-person setting; view is %r" % (view,))
+        if not (random_start and random_goal):
+            raise ValueError("generate needs random_start and random_goal (a generated layout has no 'S' or 'G' cell)")
+        R, E = self.gen_rooms(int(generate))
+        if not integer(gen_loops) or not 0 <= gen_loops <= E - (R * R - 1):
+            raise ValueError("gen_loops %r: an integer in [0, %d] (the edges of the %d x %d room grid outside its "
+                             "spanning tree)" % (gen_loops, E - (R * R - 1), R, R))
+        if not integer(gen_apples) or not 0 <= gen_apples <= min(self.MAX_APPLES, R * R):
+            raise ValueError("gen_apples %r: an integer in [0, %d] (at most one per room, %d per layout)"
+                             % (gen_apples, min(self.MAX_APPLES, R * R), self.MAX_APPLES))
+        self.generate, self.gen_loops, self.gen_apples = int(generate), int(gen_loops), int(gen_apples)
+
+    def generated_layout(self, seed, g, episode):
+        """The layout of global actor g's episode `episode` under the key `seed`, as a string in the layout alphabet
+        ('+' wall, '-' free, 'A' apple): what the device writes at that reset (DESIGN §7g).  Rooms are the even cells;
+        edge e between neighbouring rooms (horizontal first, row-major, then vertical) has the key (w << 8) | e, w = word
+        e & 3 of Philox4x32-10(key = seed, counter = (g, episode, GEN_STREAM, e >> 2)); open are the minimum spanning
+        tree of the room grid under these keys and the gen_loops lightest other edges.  Apples lie in the gen_apples
+        rooms with the smallest keys (w << 8) | r drawn with APPLE_STREAM."""
+        if self.generate is None:
+            raise ValueError("generated_layout: the config is not a generated maze (generate is None)")
+        N = self.N
+        R, E = self.gen_rooms(N)
+        eh = R * (R - 1)
+        e = np.arange(E)
+        a = np.where(e < eh, (e // (R - 1)) * R + e % (R - 1), e - eh)      # rooms a, b of every edge
+        b = np.where(e < eh, a + 1, a + R)
+        room_cell = lambda r: 2 * (r // R) * N + 2 * (r % R)
+        edge_cell = room_cell(a) + np.where(e < eh, 1, N)
+        key = (_philox_words(seed, g, episode, self.GEN_STREAM, E).astype(np.uint64) << np.uint64(8)) | e.astype(np.uint64)
+        # Prim from room 0: with distinct keys every algorithm finds the same tree
+        in_tree = np.zeros(R * R, dtype=bool)
+        in_tree[0] = True
+        tree = np.zeros(E, dtype=bool)
+        for _ in range(R * R - 1):
+            cut = np.flatnonzero(in_tree[a] != in_tree[b])
+            pick = cut[np.argmin(key[cut])]
+            tree[pick] = True
+            in_tree[a[pick]] = in_tree[b[pick]] = True
+        rest = np.flatnonzero(~tree)
+        extra = rest[np.argsort(key[rest])[:self.gen_loops]]
+        cells = np.full(N * N, "+")
+        cells[room_cell(np.arange(R * R))] = "-"
+        cells[edge_cell[tree]] = "-"
+        cells[edge_cell[extra]] = "-"
+        if self.gen_apples:
+            r = np.arange(R * R)
+            akey = (_philox_words(seed, g, episode, self.APPLE_STREAM, R * R).astype(np.uint64) << np.uint64(8)) | \
+                r.astype(np.uint64)
+            cells[room_cell(np.argsort(akey)[:self.gen_apples])] = "A"
+        return "".join(cells)
 
     def _parse(self, i, lay):
         if isinstance(lay, str):
@@ -147,7 +223,7 @@ class MazeConfig(object):
     @property
     def flags(self):
         return (self.RANDOM_START * self.random_start) | (self.RANDOM_GOAL * self.random_goal) | \
-            (self.SHOW_GOAL * self.show_goal) | (self.NAV * self.nav)
+            (self.SHOW_GOAL * self.show_goal) | (self.NAV * self.nav) | (self.GENERATED * (self.generate is not None))
 
     @property
     def action_size(self):
@@ -164,7 +240,9 @@ class MazeConfig(object):
         layout [wall bits of cell y*N+x as 7 x (lo, hi) uint32, S cell, G cell, n_free, index of G in the free list,
         free cells ascending] (-1: none); a navigation maze (flag NAV) appends [goal reward, apple reward, hit reward, mode
         (1: goal_respawn, 2: Lab's actions), 0, 0, 0, 0] and per layout [n apples, apple cells ascending, 0 padding to
-        65 words]."""
+        65 words].  A generated maze (flag GENERATED) has L = 0 and no records: after the header come the 8 words
+        [goal reward, apple reward, hit reward, mode, gen_loops, gen_apples, 0, 0]; the layout and apple records are
+        per actor, written on the device at every reset."""
         N, rec = self.N, self.RECORD_HEADER + self.N * self.N
         seed = int(seed) & (2 ** 64 - 1)
         out = np.zeros(self.HEADER + self.L * rec, dtype=np.int64)
@@ -180,10 +258,10 @@ class MazeConfig(object):
             r[14], r[15], r[16] = self.start[l], g, len(free)
             r[17] = int(np.searchsorted(free, g)) if g >= 0 else -1
             r[self.RECORD_HEADER:self.RECORD_HEADER + len(free)] = free
-        if self.nav:
+        if self.nav or self.generate is not None:
             ext = np.zeros(self.NAV_HEADER + self.L * self.NAV_RECORD, dtype=np.int64)
             mode = self.NAV_RESPAWN * self.goal_respawn | self.NAV_LAB_ACTIONS * (self.action_set == "lab")
-            ext[:4] = [self.goal_reward, self.apple_reward, self.hit_reward, mode]
+            ext[:6] = [self.goal_reward, self.apple_reward, self.hit_reward, mode, self.gen_loops, self.gen_apples]
             for l, a in enumerate(self.apples):
                 r = ext[self.NAV_HEADER + l * self.NAV_RECORD:]
                 r[0] = len(a)
@@ -196,10 +274,33 @@ class MazeConfig(object):
         g = np.arange(actor_base, actor_base + batch, dtype=np.int64)
         return (g * self.L // int(actors_total)).astype(np.int32)
 
+    def layout_config(self, layout_string):
+        """A config with this one's options and the single static layout `layout_string` (host-side views of a generated
+        maze: its walls, free cells and apples as a MazeConfig)."""
+        return MazeConfig([layout_string], self.random_start, self.random_goal, self.show_goal, self.max_episode_steps,
+                          self.view, self.start_heading, self.goal_reward, self.apple_reward, self.hit_reward,
+                          self.goal_respawn, self.action_set)
+
     @staticmethod
     def reference():
         """The reference's map as a configuration (renders and steps exactly like the unconfigured maze)."""
         return MazeConfig([REFERENCE_MAP])
+
+
+def _philox_words(seed, g, episode, stream, n):
+    """Words 0 .. n-1 of Philox4x32-10 (Salmon et al., SC'11) with key = seed and counters (g, episode, stream, i >> 2):
+    word i is output word i & 3 of counter i >> 2 -> uint32 [n]."""
+    m32 = np.uint64(0xFFFFFFFF)
+    seed = int(seed) & (2 ** 64 - 1)
+    blocks = np.arange((n + 3) // 4, dtype=np.uint64)
+    c = [np.full_like(blocks, int(g) & 0xFFFFFFFF), np.full_like(blocks, int(episode) & 0xFFFFFFFF),
+         np.full_like(blocks, stream), blocks]
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]        # < 2^64: exact in uint64
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & m32]
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return np.stack(c, 1).reshape(-1)[:n].astype(np.uint32)
 
 
 class BatchedMazeEnvironment(object):
@@ -213,7 +314,8 @@ class BatchedMazeEnvironment(object):
         self.B = batch
         self.config = config
         self.ring = ops.Ring(batch, history_size, torch.device(device), maze_state=config is not None,
-                             nav=config is not None and config.nav)
+                             nav=config is not None and config.nav,
+                             gen=(config.generate or 0) if config is not None else 0)
         self.maze = None
         if config is not None:
             total = batch if actors_total is None else int(actors_total)
@@ -222,6 +324,8 @@ class BatchedMazeEnvironment(object):
             block = torch.from_numpy(config.block(seed)).to(self.ring.count.device)
             self.ring.layout.copy_(torch.from_numpy(config.layout_ids(actor_base, batch, total)))
             view = ops.MAZE_FIRST_PERSON if config.view == "first_person" else ops.MAZE_TOP_DOWN
+            if config.generate is not None:
+                view = ops.MAZE_FIRST_PERSON_GENERATED
             self.maze = (view, config.N, block, int(actor_base))
         self.reset()
 
@@ -263,6 +367,19 @@ class BatchedMazeEnvironment(object):
                                      p["b_base_fc_v"], u, pi_out, v_out, actions, out_reward, out_terminal, active,
                                      active_log_t, n_steps, terminal_end,
                                      base_actor=getattr(self, "base_actor", 0) if index_parent else 0, maze=self.maze, **nxt)
+
+    def current_layouts(self):
+        """The layouts the actors of a generated maze are in -> (walls, apples): bool [B, N, N] (True: wall; [b, y, x])
+        and a list of B int arrays of apple cells y * N + x, ascending (collected ones included)."""
+        if self.config is None or self.config.generate is None:
+            raise ValueError("current_layouts: the config is not a generated maze")
+        N = self.config.N
+        rec = self.ring.gen.view(self.B, -1).cpu().numpy()[:, ops.NAV_RECORD:]
+        words = rec[:, :14].astype(np.int64) & 0xFFFFFFFF
+        bits = (words[:, :, None] >> np.arange(32)) & 1
+        walls = bits.reshape(self.B, 448)[:, :N * N].astype(bool).reshape(self.B, N, N)
+        arec = rec[:, ops.MAZE_RECORD_HEADER + N * N:]
+        return walls, [arec[b, 1:1 + arec[b, 0]].copy() for b in range(self.B)]
 
     def stop(self):
         pass

@@ -72,7 +72,7 @@ class Evaluate(object):
         counted = [False] * B
         goals, apples = [], []                 # per counted episode
         if nav:                                # goals_total / apples_total (never zeroed by a reset): per-episode differences
-            tot = ring.nav.view(B, ops.NAV_RECORD)[:, 3:5]
+            tot = ring.actor_records[:, 3:5]
             ep0 = tot.cpu().numpy().copy()
         if one_episode_per_actor:
             n_episodes = B

@@ -97,7 +97,7 @@ def kernel_timer_stop():
 class Ring(object):
     """Device replay ring + per-actor environment state (layout: include/unreal_hip.h)."""
 
-    def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False, nav=False):
+    def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False, nav=False, gen=0):
         self.B, self.H, self.H1 = B, H, H + 1
         self.objective_size = objective_size
         self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
@@ -134,8 +134,24 @@ class Ring(object):
         self.nav = z(B * NAV_RECORD, dt=torch.int32) if maze_state and nav else None
         if self.nav is not None:
             self.heading = self.nav.view(B, NAV_RECORD)[:, 0]
+        # generated mazes (MazeConfig.generate = N = `gen`): [B, gen_record_words(N)] records (the 8 words above, then the
+        # actor's own layout record and apple record, rewritten by every reset), handed to the kernels in place of `heading`
+        self.gen_n = int(gen) if maze_state else 0
+        self.gen = z(B * gen_record_words(self.gen_n), dt=torch.int32) if self.gen_n else None
+        if self.gen is not None:
+            self.nav = None
+            self.heading = self.gen.view(B, -1)[:, 0]
 
         self._cur = z(B, dt=torch.int32)
+
+    @property
+    def actor_records(self):
+        """[B, words] view of the per-actor records of a navigation or generated maze (words 3, 4: goals_total,
+        apples_total), or None."""
+        gen, nav = getattr(self, "gen", None), getattr(self, "nav", None)
+        if gen is not None:
+            return gen.view(self.B, -1)
+        return nav.view(self.B, NAV_RECORD) if nav is not None else None
 
     def cur_idx(self, out=None, base_actor=0):
         """Frame index of every actor's current observation (slot count % H1).  `base_actor` = index of this (view's)
@@ -167,11 +183,21 @@ def ring_view(ring, b0, b1):
         setattr(v, name, t[b0:b1] if t is not None else None)
     nav = getattr(ring, "nav", None)
     v.nav = nav[b0 * NAV_RECORD:b1 * NAV_RECORD] if nav is not None else None
+    v.gen_n, gen = getattr(ring, "gen_n", 0), getattr(ring, "gen", None)
+    v.gen = gen[b0 * gen_record_words(v.gen_n):b1 * gen_record_words(v.gen_n)] if gen is not None else None
     return v
 
 
 MAZE_TOP_DOWN, MAZE_FIRST_PERSON = 0, 1       # the `view` of a maze (UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON)
+MAZE_FIRST_PERSON_GENERATED = 2               # first person, a generated block (UNREAL_MAZE_FIRST_PERSON_GENERATED)
 NAV_RECORD = 8                                # int32 words of a navigation maze's per-actor record (UNREAL_MAZE_NAV_RECORD)
+MAZE_RECORD_HEADER, NAV_APPLE_RECORD = 18, 65  # words of a layout record before its free list; of an apple record
+
+
+def gen_record_words(N):
+    """int32 words of a generated maze's per-actor record (UNREAL_MAZE_GEN_RECORD(N)): the navigation record, the layout
+    record (18 + N * N) and the apple record (65)."""
+    return NAV_RECORD + MAZE_RECORD_HEADER + N * N + NAV_APPLE_RECORD if N else 0
 
 
 def _maze_args(ring, maze):
@@ -183,12 +209,21 @@ def _maze_args(ring, maze):
     _chk(block, "i32", 8, "maze config")
     nav = getattr(ring, "nav", None)
     arrays = (("goal", 2 * ring.B), ("layout", ring.B), ("ep_steps", ring.B), ("episode", ring.B))
+    if view == MAZE_FIRST_PERSON_GENERATED:
+        arrays = tuple(a for a in arrays if a[0] != "layout")
     if view == MAZE_FIRST_PERSON:
         arrays += (("nav", NAV_RECORD * ring.B),) if nav is not None else (("heading", ring.B),)
+    if view == MAZE_FIRST_PERSON_GENERATED:
+        if getattr(ring, "gen_n", 0) != N:
+            raise ValueError("a generated maze needs a ring with per-actor records of its size (Ring(gen=%d))" % N)
+        arrays += (("gen", gen_record_words(N) * ring.B),)
     for name, n in arrays:
         _chk(getattr(ring, name), "i32", n, "ring." + name)
     heading = nav if nav is not None and view == MAZE_FIRST_PERSON else ring.heading
-    return (int(view), int(N), ptr(block), int(actor_base), ptr(ring.goal), ptr(ring.layout), ptr(ring.ep_steps),
+    if view == MAZE_FIRST_PERSON_GENERATED:
+        heading = ring.gen
+    layout = None if view == MAZE_FIRST_PERSON_GENERATED else ring.layout      # (a generated block has no layout records)
+    return (int(view), int(N), ptr(block), int(actor_base), ptr(ring.goal), ptr(layout), ptr(ring.ep_steps),
             ptr(ring.episode), ptr(heading))
 
 
@@ -247,7 +282,8 @@ def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, act
     """policy_step + maze_rollout_step in one launch: the workgroup that steps an actor computes its pi / V / action first
     (bit-identical to the two launches).  A = 6: a first-person navigation maze with Lab's action set."""
     B = ring.B
-    nav = maze is not None and maze[0] == MAZE_FIRST_PERSON and getattr(ring, "nav", None) is not None
+    nav = maze is not None and ((maze[0] == MAZE_FIRST_PERSON and getattr(ring, "nav", None) is not None) or
+                                maze[0] == MAZE_FIRST_PERSON_GENERATED)
     if A != 4 and not (A == 6 and nav):
         raise ValueError("the maze has 4 actions (6: a first-person navigation maze with action_set='lab'); A = %r" % (A,))
     _chk(X, "f32", (B - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A); _chk(bp, "f32", A); _chk(Wv, "f32", 256)
