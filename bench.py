@@ -20,8 +20,12 @@ either, trainer.py:446-448) and W warm-up calls are untimed.
 --dump-outputs DIR writes, after the timed calls, what the last timed call handed its caller (see dump_outputs) as
 DIR/<name>.npy: the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
-Extra objects on the JSON line: `roofline` for the dominant kernel (HIP-event timed inside the timed
-region) and `cpu_baseline` (the oracle's threaded restatement of the reference loop on host cores).
+A plain run does only what the headline figure needs: set up, fill the replay, warm up, time the K calls, dump if
+asked, print the JSON line.  That line also carries `roofline` for the dominant kernel: its launches are bracketed with
+HIP events inside the timed region, as they always were, so it costs no run of its own.
+
+--full adds what takes runs of its own: `cpu_baseline`, the oracle's threaded restatement of the reference loop on host
+cores (about half a minute: its replay fill plus --cpu-seconds of timed legs; --gpus 1 only).
 """
 import argparse
 import json
@@ -190,7 +194,7 @@ def dump_outputs(out_dir, tr, net, losses, stats):
         json.dump(manifest, f, indent=1)
 
 
-def main():
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)       # 100 x 33 ms: a timed region long enough for a 5-s utilisation
@@ -199,14 +203,21 @@ def main():
     ap.add_argument("--history", type=int, default=2000, help="experience_history_size per actor")
     ap.add_argument("--groups", type=int, default=1, help="sequential updates per process() call (actors are dealt into "
                     "this many groups; 1 = one update from all actors, the headline configuration)")
-    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="total timed CPU-baseline budget: half of it for the "
-                    "parallel_size leg, a quarter each for the 1-thread and the nproc-thread legs")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own beside the headline "
+                    "figure: the CPU baseline (`cpu_baseline` on the JSON line, --gpus 1 only)")
+    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="--full: total timed CPU-baseline budget: half of it "
+                    "for the parallel_size leg, a quarter each for the 1-thread and the nproc-thread legs")
     ap.add_argument("--cpu-threads", type=int, default=8, help="parallel_size of the reference (options.py:37)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline (a plain run has none)")
     ap.add_argument("--timed-kernel", default="unreal_encoder_bwd")
     ap.add_argument("--progress", action="store_true", help="phase markers on stderr (diagnosing a run under a profiler)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed calls, write what the last one "
                     "computed as DIR/<name>.npy (rank 0; at most 64 MB in all)")
+    return ap
+
+
+def main():
+    ap = make_parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be >= 1")
@@ -379,7 +390,7 @@ def main():
                "whole_path_frac_fp32_mfma": value * 69.67e6 / (FP32_MFMA_PEAK_TFLOPS * 1e12 * world),
                "whole_path_frac_hbm_u8": value * 114396.0 / (HBM_PEAK_GBS * 1e9 * world)}),
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         hist_cpu = args.history          # the workload's own replay history (its fill is untimed, like the GPU's)
         nproc = host_cpus()
         legs = [(1, args.cpu_seconds / 4.0), (args.cpu_threads, args.cpu_seconds / 2.0)]
