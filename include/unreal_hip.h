@@ -72,9 +72,24 @@ extern "C" {
  * under these keys and the gen_loops lightest other edges; apples lie in the gen_apples rooms r = j R + i with the
  * smallest keys (w << 8) | r from counter (actor_base + b, episode, 0x4D415A41, r >> 2).  Goal, start and heading are
  * then drawn over that record as for any block.  A view-1 launch on a generated block, a view-2 launch on any other
- * block and a top-down launch on a generated block write nothing, as a launch with the wrong N. */
+ * block and a top-down launch on a generated block write nothing, as a launch with the wrong N.
+ * Styled walls (first person, flag 32 in the block's word 2): after everything above the block holds the
+ * style section: [S styles (1..7), gen_landmark_density (0..256), 0 x 6], then 8 style words r | g << 8 | b << 16 |
+ * pattern << 24 (word k - 1: style k; unused slots and the eighth 0), then, for a static block, per layout
+ * UNREAL_MAZE_STYLE_WORDS(N) words of 4-bit style ids: cell c = y * N + x is nibble c & 7 of word c >> 3 (0: a free cell,
+ * or a wall that looks as without the flag).  A ray whose first blocked cell is an interior wall of style k >= 1 leaves
+ * that style's (r, g, b) in channels 0..2, each channel halved where bit u of the pattern is set (u in 0..7: the eighth
+ * of the cell's face that was hit, in world coordinates) and then scaled by 5 / 8 on a face crossed along y.  A generated
+ * styled block (flags 16 | 32) has no id words in the block: `heading` then addresses B records of
+ * UNREAL_MAZE_GEN_STYLED_RECORD(N) int32, the generated record followed by the actor's id words, which every reset
+ * draws once the walls are known: wall cell c with w = word c & 3 of the draw with counter (actor_base + b, episode,
+ * 0x4D415A53, c >> 2) is a landmark iff (w >> 24) < gen_landmark_density, of style 1 + (w & 0xFFFFFF) % S.  The entries
+ * and the view values are the same; the flag selects the styled path, and a launch with the wrong N still writes
+ * nothing. */
 #define UNREAL_MAZE_NAV_RECORD 8
 #define UNREAL_MAZE_GEN_RECORD(N) (8 + 18 + (N) * (N) + 65)
+#define UNREAL_MAZE_STYLE_WORDS(N) (((N) * (N) + 7) / 8)
+#define UNREAL_MAZE_GEN_STYLED_RECORD(N) (UNREAL_MAZE_GEN_RECORD(N) + UNREAL_MAZE_STYLE_WORDS(N))
 #define UNREAL_MAZE_TOP_DOWN 0
 #define UNREAL_MAZE_FIRST_PERSON 1
 #define UNREAL_MAZE_FIRST_PERSON_GENERATED 2

@@ -9,9 +9,13 @@
   * generated mazes (--gen-only): the step of a generated block next to the static first-person step of the
     same N and B, (a) at a 200-step limit, where resets are rare, and (b) at max_episode_steps=1, where every launch
     resets every actor and the generated block also regenerates its layout: (b) minus its static counterpart is the cost
-    of generation per reset.  Then Trainer.process() on a generated config at B = 4096.
+    of generation per reset.  Then Trainer.process() on a generated config at B = 4096;
+  * styled walls (--style-only): the step of a styled block next to the unstyled step of the same N, B and
+    step limit, static (the same layouts, three wall cells in four carrying a digit 1..7) and generated (landmark
+    density 64).
 
-  python tools/bench_fp_maze.py [--launches 200] [--steps 10] [--warmup 3] [--history 100] [--nav-only | --gen-only]
+  python tools/bench_fp_maze.py [--launches 200] [--steps 10] [--warmup 3] [--history 100]
+                                [--nav-only | --gen-only | --style-only]
 
 Prints one JSON line per measurement."""
 import argparse
@@ -37,6 +41,19 @@ def layouts(N, L=8, seed=0, apples=0):
 
 
 NAV_APPLES = {7: 8, 21: 64}
+# seven styles: plain, striped and half-dark patterns
+STYLES = [(200, 100, 50, 0xAA), (0, 255, 0, 0x00), (255, 255, 255, 0xFF), (10, 20, 250, 0x0F), (90, 90, 90, 0x81),
+          (255, 0, 255, 0x3C), (120, 60, 200, 0x55)]
+
+
+def styled_layouts(N, L=8, seed=0):
+    """layouts(N, L, seed) with three wall cells in four drawn in a style 1..7."""
+    rs = np.random.RandomState(seed + 1000 + N)
+    out = []
+    for lay in layouts(N, L, seed):
+        k = rs.randint(0, 28, len(lay))
+        out.append("".join(str(1 + d % 7) if ch == "+" and d < 21 else ch for ch, d in zip(lay, k)))
+    return out
 
 
 def kernel_ms(env, B, launches, A=4):
@@ -103,11 +120,33 @@ def main():
     ap.add_argument("--skip-trainer", action="store_true")
     ap.add_argument("--nav-only", action="store_true", help="only the navigation rows and their plain references")
     ap.add_argument("--gen-only", action="store_true", help="only the generated-maze rows and their static references")
+    ap.add_argument("--style-only", action="store_true", help="only the styled rows and their unstyled references")
     args = ap.parse_args()
     from unreal_amd.environment.environment import Environment
     from unreal_amd.environment.maze_environment import MazeConfig, batched_maze_environment
     kw = dict(random_start=True, random_goal=True, show_goal=True, max_episode_steps=200)
     nav_kw = dict(goal_reward=10, apple_reward=1, hit_reward=0, goal_respawn=True, action_set="lab")
+    if args.style_only:
+        for N in (7, 21):       # styled vs unstyled first person, same N, B and step limit, same process
+            for B in (512, 4096):
+                for kind in ("static", "generated"):
+                    res = {}
+                    for what in ("unstyled", "styled"):
+                        skw = dict(wall_styles=STYLES) if what == "styled" else {}
+                        if kind == "static":
+                            lays = styled_layouts(N) if what == "styled" else layouts(N)
+                            cfg = MazeConfig(lays, view="first_person", **dict(kw, **skw))
+                        else:
+                            if what == "styled":
+                                skw["gen_landmark_density"] = 64
+                            cfg = MazeConfig(None, view="first_person", generate=N, **dict(kw, **skw))
+                        env = batched_maze_environment(B, 3, DEV, config=cfg, seed=1)
+                        res[what] = kernel_ms(env, B, args.launches) * 1e3
+                        del env
+                    print(json.dumps(dict(what="style_step_kernel", kind=kind, N=N, B=B,
+                                          unstyled_us=round(res["unstyled"], 2), styled_us=round(res["styled"], 2),
+                                          ratio=round(res["styled"] / res["unstyled"], 3))), flush=True)
+        return
     if args.gen_only:
         for N in (7, 21):       # generated vs static first person, same N, B and step limit, same process
             for B in (512, 4096):

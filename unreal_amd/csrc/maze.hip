@@ -31,6 +31,10 @@
 // records (gen_maze) behind `heading`, and the same step and reset bodies read them from there.  They run in kernels of
 // their own (view kFirstPersonGen), so the kernels of the static blocks carry none of the generator.
 //
+// Styled blocks (flag kMazeStyled) give interior wall cells a style: a colour and a stripe pattern along the
+// face, fixed to the world.  The colour is chosen per column by the DDA lane (fp_render) behind one uniform branch; the
+// style ids of a static block lie in the block, those of a generated block at the end of the actor's record (gen_maze).
+//
 // One workgroup (256 threads) per actor.  The step renders s_{t+1} into LDS (lanes 0..83: one column's DDA each, over
 // the layout's wall bits in LDS; then every thread fills whole frame-row dwords), streams it to the ring slot with 16 B
 // per lane, turns the LDS image into |new - old| bytes against the stored frame (read at kernel entry, so its latency
@@ -429,6 +433,7 @@ template <int N>
 struct FpLds {
   static constexpr int NW = (N * N + 63) / 64;
   static constexpr int NA = (N * N + 31) / 32;   // navigation: words of the active-apple cell bitmap
+  static constexpr int NS = maze_style_words(N); // styled: words of 4-bit style ids
   uint4 img[kChunks];
   int tn[FRAME_W], td[FRAME_W];
   uint32_t col[FRAME_W];
@@ -436,12 +441,23 @@ struct FpLds {
   uint32_t apples[NA];
   int act;
   int collect;                                  // navigation: bit index of the apple the step collects (-1: none)
+  uint32_t styles[NS];                          // styled: style id of cell c in nibble c & 7 of word c >> 3
+  uint32_t style_col[kStyleSlots];              // styled: r | g << 8 | b << 16 | pattern << 24 of style k at k - 1
 };
 
 template <int N>
 __device__ __forceinline__ void fp_load_walls(FpLds<N>& s, const int* rec) {
   if (threadIdx.x < FpLds<N>::NW)
     s.walls[threadIdx.x] = (uint64_t)(uint32_t)rec[2 * threadIdx.x] | ((uint64_t)(uint32_t)rec[2 * threadIdx.x + 1] << 32);
+}
+
+// Styled blocks: the 8 style words of the section `sext` and, unless `ids` is null (a generated block's reset, which
+// draws them), the layout's or the actor's nibble words.  Waves 1 and 2, so that wave 0's wall loads do not wait.
+template <int N>
+__device__ __forceinline__ void fp_load_styles(FpLds<N>& s, const int* sext, const int* ids) {
+  const int t = threadIdx.x - 64;
+  if (t >= 0 && t < kStyleSlots) s.style_col[t] = (uint32_t)sext[kStyleHdr + t];
+  if (ids && t >= 64 && t < 64 + FpLds<N>::NS) s.styles[t - 64] = (uint32_t)ids[t - 64];
 }
 
 // Navigation: sets the bit of every active apple (not collected, not on the goal cell) of one apple record in the
@@ -452,9 +468,16 @@ __device__ __forceinline__ void fp_mark_apple(FpLds<N>& s, int k, int n, int cel
 }
 
 // Renders the view from cell (ex, ey) along heading h into s.img.  Call with the whole workgroup after the wall bits (and
-// with NAV, the apple bitmap's marks) are issued to LDS and every thread is done reading s.img; returns after a barrier.
+// with NAV, the apple bitmap's marks; with `styled`, the style ids and words) are issued to LDS and every thread is done
+// reading s.img; returns after a barrier.
+//
+// Styled blocks: a ray whose first blocked cell is an interior wall of style k >= 1 leaves that style's
+// colour instead of the shade.  u in 0..7 is the texel of the hit along the face, floor(8 frac(c)) for the hit point's
+// world coordinate c along the face: at forward crossing k, frac(c) = frac((sigma q (2k+1) + W) / 2W) with sigma = rx + ry;
+// at side crossing m, frac((sigma (2m+1) W + |q|) / 2|q|) with sigma = dx + dy.  A channel is halved where bit u of the
+// style's pattern is set, then scaled by 5/8 on a face crossed along y.
 template <int N, bool NAV>
-__device__ __forceinline__ void fp_render(FpLds<N>& s, int ex, int ey, int h, int gx, int gy, bool show_goal) {
+__device__ __forceinline__ void fp_render(FpLds<N>& s, int ex, int ey, int h, int gx, int gy, bool show_goal, bool styled) {
   const int dx = (h == 0) - (h == 2), dy = (h == 1) - (h == 3);
   const int rx = -dy, ry = dx;
   if (threadIdx.x < FRAME_W) {           // one column's DDA per lane: at most 2N cells before the ray leaves the map
@@ -473,7 +496,30 @@ __device__ __forceinline__ void fp_render(FpLds<N>& s, int ex, int ey, int h, in
       if ((s.walls[c >> 6] >> (c & 63)) & 1) { border = false; break; }
     }
     const uint32_t shade = xface ? kWallX : kWallY;
-    s.tn[i] = tn; s.td[i] = td; s.col[i] = border ? shade << 8 : shade;
+    uint32_t col = border ? shade << 8 : shade;
+    if (styled && !border) {             // (the flag is uniform)
+      const int c = (ey + f * dy + sd * ry) * N + ex + f * dx + sd * rx;
+      const uint32_t st = (s.styles[c >> 3] >> (4 * (c & 7))) & 15u;
+      if (st) {
+        const bool fwd = xface == (dx != 0);             // k or m was incremented after the crossing that hit
+        const int n = fwd ? (rx + ry) * q * (2 * k - 1) + FRAME_W : (dx + dy) * (2 * m - 1) * FRAME_W + aq;
+        const int den = fwd ? 2 * FRAME_W : 2 * aq;
+        int rem = n % den;
+        rem += rem < 0 ? den : 0;
+        const int u = (rem * 8) / den;
+        const uint32_t sw = s.style_col[st - 1];
+        const bool dark = (sw >> (24 + u)) & 1u;
+        col = 0;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          uint32_t v = (sw >> (8 * ch)) & 255u;
+          v = dark ? v >> 1 : v;
+          v = xface ? v : (5u * v) >> 3;
+          col |= v << (8 * ch);
+        }
+      }
+    }
+    s.tn[i] = tn; s.td[i] = td; s.col[i] = col;
   }
   __syncthreads();
   // dword w of a frame row holds bytes 4w..4w+3: channel c0 = 4w % 3 onwards of pixel P0 = 4w / 3, then pixel P0 + 1
@@ -597,9 +643,10 @@ __device__ __forceinline__ uint32_t gen_weight(uint64_t seed, int g, int ep, uin
 
 // Fills `rec` (the layout and apple records of one actor, in global memory) and s.walls for episode `ep` of global actor
 // g.  Call with the whole workgroup; s.img is overwritten.  Begins and ends with a barrier: on return the record, the wall
-// bits in LDS and nothing else of `s` have changed, and every thread may read them.
+// bits in LDS and nothing else of `s` have changed, and every thread may read them.  `ids` (a styled block; else null):
+// the actor's nibble words, drawn once the walls are final and written there and to s.styles.
 template <int N>
-__device__ __forceinline__ void gen_maze(FpLds<N>& s, const int* cfg, int g, int ep, int* rec) {
+__device__ __forceinline__ void gen_maze(FpLds<N>& s, const int* cfg, int g, int ep, int* rec, int* ids) {
   using G = GenLds<N>;
   constexpr int R = G::R, E = G::E, RR = G::RR, NN = N * N, EH = R * (R - 1);
   G& t = *reinterpret_cast<G*>(s.img);
@@ -687,6 +734,26 @@ __device__ __forceinline__ void gen_maze(FpLds<N>& s, const int* cfg, int g, int
   }
   __syncthreads();
   if (tid < FpLds<N>::NW) s.walls[tid] = (uint64_t)t.walls[2 * tid] | ((uint64_t)t.walls[2 * tid + 1] << 32);
+  if (ids && tid >= 64 && tid < 64 + FpLds<N>::NS) {     // (uniform pointer) landmarks: 8 cells, two draws per thread
+    const int j = tid - 64;
+    const int* sext = maze_style_ext(cfg);
+    const uint32_t S = (uint32_t)min(max(sext[0], 1), kStyleSlots - 1), density = (uint32_t)sext[1];
+    uint32_t word = 0;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      uint32_t u[4];
+      philox4x32_10(seed, (uint64_t)(uint32_t)g | ((uint64_t)(uint32_t)ep << 32),
+                    (uint64_t)kMazeStyleStream | ((uint64_t)(uint32_t)(2 * j + half) << 32), u);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = 8 * j + 4 * half + e;
+        const bool wall = c < NN && ((t.walls[c >> 5] >> (c & 31)) & 1u);
+        if (wall && (u[e] >> 24) < density) word |= (1u + (u[e] & 0xFFFFFFu) % S) << (4 * (4 * half + e));
+      }
+    }
+    s.styles[j] = word;
+    ids[j] = (int)word;
+  }
   if (tid < kRecHdr) rec[tid] = tid < 14 ? (int)t.walls[tid] : -1;           // (word 16, n_free, is written below)
   int* arec = rec + kRecHdr + NN;
   if (tid == 0) arec[0] = n_apples;
@@ -725,13 +792,18 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
   const int* cfg = p.cfg;
   const int b = blockIdx.x;
   const int H1 = p.H1;
-  int* const actor = GEN ? p.heading + (size_t)gen_actor_words(N) * b : nullptr;
+  const bool styled = cfg[2] & kMazeStyled;       // (uniform) a styled block: its generated records carry the style ids
+  int* const actor = GEN ? p.heading + (size_t)(gen_actor_words(N) + (styled ? maze_style_words(N) : 0)) * b : nullptr;
   const int lay = GEN ? 0 : maze_layout(cfg, p.layout, b);
   const int* rec = GEN ? actor + kNavActorWords : maze_rec(cfg, lay);
   const int* ext = NAV ? maze_nav_ext(cfg) : nullptr;
   const int* arec = NAV ? (GEN ? rec + kRecHdr + N * N : ext + kNavHdr + lay * kNavRec) : nullptr;
   const int mode = NAV ? ext[3] : 0;
   fp_load_walls<N>(s, rec);
+  if (styled) {
+    const int* sext = maze_style_ext(cfg);
+    fp_load_styles<N>(s, sext, GEN ? actor + gen_actor_words(N) : sext + kStyleHdr + kStyleSlots + lay * maze_style_words(N));
+  }
   if (NAV) {
     if (threadIdx.x < FpLds<N>::NA) s.apples[threadIdx.x] = 0u;
     if (threadIdx.x == 0) s.collect = -1;
@@ -834,7 +906,7 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
   }
 
   // s_{t+1}: stored unless the episode restarts; then its bytes become |s_{t+1} - s_t| in place
-  fp_render<N, NAV>(s, ex, ey, eh, gx, gy, show_goal);
+  fp_render<N, NAV>(s, ex, ey, eh, gx, gy, show_goal, styled);
 #pragma unroll
   for (int k = 0; k < kChunksPerThread; ++k) {
     const int c = threadIdx.x + 256 * k;
@@ -870,7 +942,7 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
   if (reset) {                           // (uniform) the next episode's first observation goes into the slot instead
     int rg, rs;
     if constexpr (GEN) {                 // the next episode's maze, before its reset draw and its first view
-      gen_maze<N>(s, cfg, p.actor_base + b, epi + 1, actor + kNavActorWords);
+      gen_maze<N>(s, cfg, p.actor_base + b, epi + 1, actor + kNavActorWords, styled ? actor + gen_actor_words(N) : nullptr);
       if (NAV) {
         n_apples = min(arec[0], kMaxApples);
         my_apple = threadIdx.x < n_apples ? arec[1 + threadIdx.x] : -1;
@@ -884,7 +956,7 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
       fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, 0, rg);
     }
     // (static blocks: the render's first barrier separates the difference's readers from its writers)
-    fp_render<N, NAV>(s, rx, ry, rh, rgx, rgy, show_goal);
+    fp_render<N, NAV>(s, rx, ry, rh, rgx, rgy, show_goal, styled);
     fp_store(dst, s.img);
   }
 
@@ -932,12 +1004,17 @@ template <int N, bool NAV, bool GEN>
 __device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
   const int* cfg = p.cfg;
   const int b = blockIdx.x;
-  int* const actor = GEN ? p.heading + (size_t)gen_actor_words(N) * b : nullptr;
+  const bool styled = cfg[2] & kMazeStyled;
+  int* const actor = GEN ? p.heading + (size_t)(gen_actor_words(N) + (styled ? maze_style_words(N) : 0)) * b : nullptr;
   const int lay = GEN ? 0 : maze_layout(cfg, p.layout, b);
   const int* rec = GEN ? actor + kNavActorWords : maze_rec(cfg, lay);
   if constexpr (!GEN) fp_load_walls<N>(s, rec);
+  if (styled) {
+    const int* sext = maze_style_ext(cfg);
+    fp_load_styles<N>(s, sext, GEN ? nullptr : sext + kStyleHdr + kStyleSlots + lay * maze_style_words(N));
+  }
   const int g = p.actor_base + b, epi = p.episode[b];
-  if constexpr (GEN) gen_maze<N>(s, cfg, g, epi + 1, actor + kNavActorWords);
+  if constexpr (GEN) gen_maze<N>(s, cfg, g, epi + 1, actor + kNavActorWords, styled ? actor + gen_actor_words(N) : nullptr);
   int gc, sc;
   maze_reset_cells(cfg, rec, g, epi + 1, gc, sc);
   const int h = fp_reset_heading(cfg, g, epi + 1);
@@ -951,7 +1028,7 @@ __device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
   }
   __syncthreads();
   if (NAV) fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, 0, gc);
-  fp_render<N, NAV>(s, sc % N, sc / N, h, gc % N, gc / N, cfg[2] & kMazeShowGoal);
+  fp_render<N, NAV>(s, sc % N, sc / N, h, gc % N, gc / N, cfg[2] & kMazeShowGoal, styled);
   fp_store(p.frames + ((size_t)b * p.H1 + slot) * FRAME_BYTES, s.img);
   if (threadIdx.x == 0) {
     p.pos[2 * b] = sc % N;

@@ -59,6 +59,19 @@ constexpr int kNavActorWords = 8;
 constexpr uint32_t kMazeGenStream = 0x4D415A47u, kMazeAppleStream = 0x4D415A41u;
 constexpr int gen_actor_words(int N) { return kNavActorWords + kRecHdr + N * N + kNavRec; }
 
+// ---- styled walls (flag kMazeStyled, first person only): wall cells with a colour and a stripe pattern ------
+// The style section is appended after everything above (maze_style_ext): [0] S styles (1..7)  [1] gen_landmark_density
+// [2..7] 0;  then 8 style words r | g << 8 | b << 16 | pattern << 24 (word k - 1: style k; unused slots and the eighth 0);
+// then, for a static block, per layout maze_style_words(N) words of 4-bit style ids: cell c is nibble c & 7 of word
+// c >> 3 (0: today's wall, or a free cell).  A generated styled block has no such words: they sit at the end of the
+// per-actor record, which then has gen_actor_words(N) + maze_style_words(N) words, and every reset draws them after the
+// walls: cell c gets w = word c & 3 of Philox(key = seed, counter = (g, ep, kMazeStyleStream, c >> 2)); a wall cell with
+// (w >> 24) < density is a landmark of style 1 + (w & 0xFFFFFF) % S.
+constexpr int kMazeStyled = 32;
+constexpr int kStyleHdr = 8, kStyleSlots = 8;
+constexpr uint32_t kMazeStyleStream = 0x4D415A53u;
+constexpr int maze_style_words(int N) { return (N * N + 7) / 8; }
+
 // The Philox words of global actor g's reset into episode `ep`: word 0 draws the goal, word 1 the start, word 2 the
 // first-person heading.
 __device__ __forceinline__ void maze_reset_draw(const int* cfg, int g, int ep, uint32_t (&u)[4]) {
@@ -88,6 +101,11 @@ __device__ __forceinline__ void maze_reset_cells(const int* cfg, const int* rec,
 
 __device__ __forceinline__ const int* maze_rec(const int* cfg, int lay) { return cfg + kCfgHdr + lay * cfg[6]; }
 __device__ __forceinline__ const int* maze_nav_ext(const int* cfg) { return cfg + kCfgHdr + cfg[1] * cfg[6]; }
+// the style section of a styled block: after the layout records and, when the block has one, the navigation extension
+__device__ __forceinline__ const int* maze_style_ext(const int* cfg) {
+  const int* ext = maze_nav_ext(cfg);
+  return (cfg[2] & (kMazeNav | kMazeGen)) ? ext + kNavHdr + cfg[1] * kNavRec : ext;
+}
 __device__ __forceinline__ int maze_layout(const int* cfg, const int* layout, int b) {
   return layout ? min(max(layout[b], 0), cfg[1] - 1) : 0;
 }

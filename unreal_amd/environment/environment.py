@@ -35,7 +35,7 @@ class Environment(object):
     def register_maze_config(env_name, layouts=None, random_start=False, random_goal=False, show_goal=False,
                              max_episode_steps=0, view="top_down", start_heading=None, goal_reward=1, apple_reward=1,
                              hit_reward=-1, goal_respawn=False, action_set="turn", generate=None, gen_loops=0,
-                             gen_apples=0):
+                             gen_apples=0, wall_styles=None, gen_landmark_density=0):
         """Mazes of `env_name`: `layouts` = N x N maps (strings, or lists of row strings; + wall, - free, S start, G goal),
         N in {7, 12, 14, 21}, up to 1024 of them; global actor g runs layout g * L // (all actors).  random_start /
         random_goal: drawn at every reset, uniformly over the free cells (the start never on the goal); show_goal: the
@@ -49,11 +49,16 @@ class Environment(object):
         are given; every reset of an actor writes a new N x N maze on the device, a spanning tree of the rooms at the
         even cells plus gen_loops extra openings, with gen_apples apples in drawn rooms -- a pure function of (seed,
         global actor, episode), so training on one seed and evaluating on another tests generalisation over layouts.
+        wall_styles (first person): 1 to 7 styles (r, g, b, pattern), integers in 0..255; layout digits 1..7
+        are wall cells drawn in style k: its colour, halved in the eighths of a cell's face whose bit of `pattern` is set
+        (stripes fixed to the world, the same from every cell and heading); gen_landmark_density in 0..256 (with generate
+        and wall_styles): every wall cell of a generated maze is such a landmark with probability density / 256.
         Raises ValueError on a malformed config."""
         from .maze_environment import MazeConfig
         Environment.MAZE_CONFIG[env_name] = MazeConfig(layouts, random_start, random_goal, show_goal, max_episode_steps,
                                                        view, start_heading, goal_reward, apple_reward, hit_reward,
-                                                       goal_respawn, action_set, generate, gen_loops, gen_apples)
+                                                       goal_respawn, action_set, generate, gen_loops, gen_apples,
+                                                       wall_styles, gen_landmark_density)
 
     @staticmethod
     def create_environment(env_type, env_name, termination_time=50.0, env_args=None, thread_index=0):

@@ -11,7 +11,9 @@ With view="first_person" the same mazes are seen through a raycast camera (`Firs
 `batched_maze_environment` picks the class from the config.  First-person configs may be navigation mazes:
 apples ('A' cells), configurable rewards, respawn at the goal and Lab's six actions.  With generate=N a first-person
 config has no layouts: every reset writes a new maze for the actor on the device (DESIGN §7g);
-`MazeConfig.generated_layout` computes the same maze on the host."""
+`MazeConfig.generated_layout` computes the same maze on the host.  With wall_styles, first-person wall cells written as
+digits 1..7 (or drawn as landmarks of a generated maze, gen_landmark_density) show a colour and a stripe pattern of
+their own."""
 from collections import deque
 
 import numpy as np
@@ -34,8 +36,12 @@ class MazeConfig(object):
     tail of the unreal_maze_* entries in include/unreal_hip.h).  Raises ValueError on a malformed configuration."""
     SIZES = (7, 12, 14, 21)          # the grid sizes whose cells tile the 84-px frame: 12, 7, 6, 4 px
     MAX_LAYOUTS = 1024
-    RANDOM_START, RANDOM_GOAL, SHOW_GOAL, NAV, GENERATED = 1, 2, 4, 8, 16
+    RANDOM_START, RANDOM_GOAL, SHOW_GOAL, NAV, GENERATED, STYLED = 1, 2, 4, 8, 16, 32
     GEN_STREAM, APPLE_STREAM = 0x4D415A47, 0x4D415A41      # Philox counter word 2 of a generated maze's edge / apple draws
+    STYLE_STREAM = 0x4D415A53                              # ... and of its landmark draws
+    # style section after everything else (maze_common.h): header [S, gen_landmark_density, 0 x 6], 8 style words
+    # r | g << 8 | b << 16 | pattern << 24, then per static layout (N * N + 7) // 8 words of 4-bit style ids
+    STYLE_HEADER, STYLE_SLOTS, MAX_STYLES, WALL_CHARS = 8, 8, 7, "+1234567"
     HEADER, RECORD_HEADER = 8, 18
     VIEWS = ("top_down", "first_person")
     # navigation extension after the layout records (maze_common.h): header [goal, apple, hit reward, mode, 0 x 4], then
@@ -47,8 +53,10 @@ class MazeConfig(object):
 
     def __init__(self, layouts=None, random_start=False, random_goal=False, show_goal=False, max_episode_steps=0,
                  view="top_down", start_heading=None, goal_reward=1, apple_reward=1, hit_reward=-1,
-                 goal_respawn=False, action_set="turn", generate=None, gen_loops=0, gen_apples=0):
+                 goal_respawn=False, action_set="turn", generate=None, gen_loops=0, gen_apples=0, wall_styles=None,
+                 gen_landmark_density=0):
         self.generate, self.gen_loops, self.gen_apples = None, 0, 0
+        self._check_styles(wall_styles, gen_landmark_density, view, generate)
         if generate is not None:
             self._check_generate(layouts, random_start, random_goal, view, generate, gen_loops, gen_apples)
             layouts = []
@@ -98,12 +106,43 @@ class MazeConfig(object):
             raise ValueError("layouts of one config must share their size; got %s" % sorted(sizes))
         self.N = sizes.pop()
         self.L = len(self.layouts)
-        self.walls, self.start, self.goal, self.free, self.apples = [], [], [], [], []
+        self.walls, self.start, self.goal, self.free, self.apples, self.styles = [], [], [], [], [], []
         for i, m in enumerate(self.layouts):
             self._check(i, m)
         # a navigation maze: any of the options above, or an apple in a layout (the default block stays word for word)
         # (a generated maze with apples is one too)
         self.nav = nav_options or any(len(a) for a in self.apples) or self.gen_apples > 0
+
+    def _check_styles(self, wall_styles, density, view, generate):
+        integer = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
+        self.wall_styles, self.gen_landmark_density = None, 0
+        if wall_styles is not None:
+            if view != "first_person":
+                raise ValueError("wall_styles is a first-person setting; view is %r" % (view,))
+            seq = (list, tuple, np.ndarray)
+            if not isinstance(wall_styles, seq) or not 1 <= len(wall_styles) <= self.MAX_STYLES:
+                raise ValueError("wall_styles: a list of 1 to %d styles (r, g, b, pattern)" % self.MAX_STYLES)
+            styles = []
+            for k, st in enumerate(wall_styles):
+                if not isinstance(st, seq) or len(st) != 4 or not all(integer(v) and 0 <= v <= 255 for v in st):
+                    raise ValueError("wall_styles[%d] %r: (r, g, b, pattern), four integers in 0..255" % (k, st))
+                styles.append(tuple(int(v) for v in st))
+            self.wall_styles = styles
+        if not integer(density) or not 0 <= density <= 256:
+            raise ValueError("gen_landmark_density %r: an integer in [0, 256]" % (density,))
+        if density and (generate is None or wall_styles is None):
+            raise ValueError("gen_landmark_density needs generate and wall_styles (static layouts take their styles "
+                             "from the digits 1..7)")
+        self.gen_landmark_density = int(density)
+
+    @property
+    def styled(self):
+        return self.wall_styles is not None
+
+    @staticmethod
+    def style_words(N):
+        """int32 words of one layout's 4-bit style ids (UNREAL_MAZE_STYLE_WORDS(N))."""
+        return (N * N + 7) // 8
 
     @staticmethod
     def gen_rooms(N):
@@ -136,7 +175,9 @@ class MazeConfig(object):
         edge e between neighbouring rooms (horizontal first, row-major, then vertical) has the key (w << 8) | e, w = word
         e & 3 of Philox4x32-10(key = seed, counter = (g, episode, GEN_STREAM, e >> 2)); open are the minimum spanning
         tree of the room grid under these keys and the gen_loops lightest other edges.  Apples lie in the gen_apples
-        rooms with the smallest keys (w << 8) | r drawn with APPLE_STREAM."""
+        rooms with the smallest keys (w << 8) | r drawn with APPLE_STREAM.  A styled config writes the
+        landmarks as digits: wall cell c with w = word c & 3 of the draw with counter (g, episode, STYLE_STREAM, c >> 2) is
+        one iff (w >> 24) < gen_landmark_density, of style 1 + (w & 0xFFFFFF) % len(wall_styles)."""
         if self.generate is None:
             raise ValueError("generated_layout: the config is not a generated maze (generate is None)")
         N = self.N
@@ -168,6 +209,11 @@ class MazeConfig(object):
             akey = (_philox_words(seed, g, episode, self.APPLE_STREAM, R * R).astype(np.uint64) << np.uint64(8)) | \
                 r.astype(np.uint64)
             cells[room_cell(np.argsort(akey)[:self.gen_apples])] = "A"
+        if self.styled and self.gen_landmark_density:
+            w = _philox_words(seed, g, episode, self.STYLE_STREAM, N * N).astype(np.int64)
+            mark = (cells == "+") & ((w >> 24) < self.gen_landmark_density)
+            style = 1 + (w & 0xFFFFFF) % len(self.wall_styles)
+            cells[mark] = style[mark].astype(str)
         return "".join(cells)
 
     def _parse(self, i, lay):
@@ -181,10 +227,14 @@ class MazeConfig(object):
         n = int(round(len(m) ** 0.5))
         if n * n != len(m) or n not in self.SIZES:
             raise ValueError("layout %d: %d cells; supported are N x N with N in %s" % (i, len(m), self.SIZES))
-        bad = set(m) - set("+-SGA")
+        bad = set(m) - set("+-SGA1234567")
         if bad:
-            raise ValueError("layout %d: unknown characters %s (use + wall, - free, S start, G goal, A apple)"
-                             % (i, sorted(bad)))
+            raise ValueError("layout %d: unknown characters %s (use + wall, - free, S start, G goal, A apple, 1..7 "
+                             "styled wall)" % (i, sorted(bad)))
+        digits = [int(ch) for ch in set(m) if ch.isdigit()]
+        if digits and max(digits) > len(self.wall_styles or ()):
+            raise ValueError("layout %d: wall digit %d, but wall_styles holds %d styles"
+                             % (i, max(digits), len(self.wall_styles or ())))
         if "A" in m and self.view != "first_person":
             raise ValueError("layout %d: apples ('A') are a first-person setting; view is %r" % (i, self.view))
         if m.count("A") > self.MAX_APPLES:
@@ -198,7 +248,8 @@ class MazeConfig(object):
             raise ValueError("layout %d: %d 'S' cells; exactly one is needed without random_start" % (i, n_s))
         if not self.random_goal and n_g != 1:
             raise ValueError("layout %d: %d 'G' cells; exactly one is needed without random_goal" % (i, n_g))
-        free = [c for c in range(N * N) if m[c] != "+"]
+        wall = self.WALL_CHARS
+        free = [c for c in range(N * N) if m[c] not in wall]
         if self.random_start and len(free) < 2:
             raise ValueError("layout %d: %d free cells; random_start needs at least 2" % (i, len(free)))
         if not free:
@@ -209,12 +260,13 @@ class MazeConfig(object):
             x, y = c % N, c // N
             for nx, ny in ((x + 1, y), (x - 1, y), (x, y + 1), (x, y - 1)):
                 d = ny * N + nx
-                if 0 <= nx < N and 0 <= ny < N and m[d] != "+" and d not in seen:
+                if 0 <= nx < N and 0 <= ny < N and m[d] not in wall and d not in seen:
                     seen.add(d)
                     todo.append(d)
         if len(seen) != len(free):
             raise ValueError("layout %d: the free cells are not 4-connected (%d of %d reachable)" % (i, len(seen), len(free)))
-        self.walls.append(np.array([ch == "+" for ch in m], dtype=bool))
+        self.walls.append(np.array([ch in wall for ch in m], dtype=bool))
+        self.styles.append(np.array([int(ch) if ch.isdigit() else 0 for ch in m], dtype=np.uint8))
         self.start.append(m.index("S") if n_s == 1 else -1)
         self.goal.append(m.index("G") if n_g == 1 else -1)
         self.free.append(np.array(free, dtype=np.int32))
@@ -223,7 +275,8 @@ class MazeConfig(object):
     @property
     def flags(self):
         return (self.RANDOM_START * self.random_start) | (self.RANDOM_GOAL * self.random_goal) | \
-            (self.SHOW_GOAL * self.show_goal) | (self.NAV * self.nav) | (self.GENERATED * (self.generate is not None))
+            (self.SHOW_GOAL * self.show_goal) | (self.NAV * self.nav) | (self.GENERATED * (self.generate is not None)) | \
+            (self.STYLED * self.styled)
 
     @property
     def action_size(self):
@@ -242,7 +295,9 @@ class MazeConfig(object):
         (1: goal_respawn, 2: Lab's actions), 0, 0, 0, 0] and per layout [n apples, apple cells ascending, 0 padding to
         65 words].  A generated maze (flag GENERATED) has L = 0 and no records: after the header come the 8 words
         [goal reward, apple reward, hit reward, mode, gen_loops, gen_apples, 0, 0]; the layout and apple records are
-        per actor, written on the device at every reset."""
+        per actor, written on the device at every reset.  A styled maze (flag STYLED) appends, after all of
+        this, [S, gen_landmark_density, 0 x 6], the 8 style words r | g << 8 | b << 16 | pattern << 24 (unused: 0) and,
+        per static layout, (N * N + 7) // 8 words of 4-bit style ids (cell c: nibble c & 7 of word c >> 3)."""
         N, rec = self.N, self.RECORD_HEADER + self.N * self.N
         seed = int(seed) & (2 ** 64 - 1)
         out = np.zeros(self.HEADER + self.L * rec, dtype=np.int64)
@@ -267,6 +322,17 @@ class MazeConfig(object):
                 r[0] = len(a)
                 r[1:1 + len(a)] = a
             out = np.concatenate([out, ext])
+        if self.styled:
+            sw = self.style_words(N)
+            sec = np.zeros(self.STYLE_HEADER + self.STYLE_SLOTS + self.L * sw, dtype=np.int64)
+            sec[0], sec[1] = len(self.wall_styles), self.gen_landmark_density
+            for k, (r, g, b, pat) in enumerate(self.wall_styles):
+                sec[self.STYLE_HEADER + k] = r | g << 8 | b << 16 | pat << 24
+            for l, ids in enumerate(self.styles):
+                nib = np.zeros(8 * sw, dtype=np.int64)
+                nib[:N * N] = ids
+                sec[self.STYLE_HEADER + self.STYLE_SLOTS + l * sw:][:sw] = (nib.reshape(sw, 8) << (4 * np.arange(8))).sum(1)
+            out = np.concatenate([out, sec])
         return (out & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
 
     def layout_ids(self, actor_base, batch, actors_total):
@@ -279,7 +345,7 @@ class MazeConfig(object):
         maze: its walls, free cells and apples as a MazeConfig)."""
         return MazeConfig([layout_string], self.random_start, self.random_goal, self.show_goal, self.max_episode_steps,
                           self.view, self.start_heading, self.goal_reward, self.apple_reward, self.hit_reward,
-                          self.goal_respawn, self.action_set)
+                          self.goal_respawn, self.action_set, wall_styles=self.wall_styles)
 
     @staticmethod
     def reference():
@@ -315,7 +381,8 @@ class BatchedMazeEnvironment(object):
         self.config = config
         self.ring = ops.Ring(batch, history_size, torch.device(device), maze_state=config is not None,
                              nav=config is not None and config.nav,
-                             gen=(config.generate or 0) if config is not None else 0)
+                             gen=(config.generate or 0) if config is not None else 0,
+                             gen_styled=config is not None and config.styled)
         self.maze = None
         if config is not None:
             total = batch if actors_total is None else int(actors_total)
@@ -326,7 +393,7 @@ class BatchedMazeEnvironment(object):
             view = ops.MAZE_FIRST_PERSON if config.view == "first_person" else ops.MAZE_TOP_DOWN
             if config.generate is not None:
                 view = ops.MAZE_FIRST_PERSON_GENERATED
-            self.maze = (view, config.N, block, int(actor_base))
+            self.maze = (view, config.N, block, int(actor_base)) + ((True,) if config.styled else ())
         self.reset()
 
     def view(self, b0, b1):
@@ -336,7 +403,7 @@ class BatchedMazeEnvironment(object):
         v.B, v.ring = b1 - b0, ops.ring_view(self.ring, b0, b1)
         v.base_actor = b0
         v.config = self.config
-        v.maze = None if self.maze is None else self.maze[:3] + (self.maze[3] + b0,)
+        v.maze = None if self.maze is None else self.maze[:3] + (self.maze[3] + b0,) + self.maze[4:]
         return v
 
     @staticmethod
@@ -374,12 +441,25 @@ class BatchedMazeEnvironment(object):
         if self.config is None or self.config.generate is None:
             raise ValueError("current_layouts: the config is not a generated maze")
         N = self.config.N
-        rec = self.ring.gen.view(self.B, -1).cpu().numpy()[:, ops.NAV_RECORD:]
+        rec = self.ring.gen.view(self.B, -1).cpu().numpy()[:, ops.NAV_RECORD:ops.gen_record_words(N)]
         words = rec[:, :14].astype(np.int64) & 0xFFFFFFFF
         bits = (words[:, :, None] >> np.arange(32)) & 1
         walls = bits.reshape(self.B, 448)[:, :N * N].astype(bool).reshape(self.B, N, N)
         arec = rec[:, ops.MAZE_RECORD_HEADER + N * N:]
         return walls, [arec[b, 1:1 + arec[b, 0]].copy() for b in range(self.B)]
+
+    def current_styles(self):
+        """The style ids of the mazes the actors are in -> uint8 [B, N, N] ([b, y, x]; 0: a free cell or a plain
+        wall, k: a wall of wall_styles[k - 1]), of a static or a generated styled config."""
+        if self.config is None or not self.config.styled:
+            raise ValueError("current_styles: the config has no wall_styles")
+        N = self.config.N
+        if self.config.generate is None:
+            ids = np.stack(self.config.styles)[self.ring.layout.cpu().numpy()]
+            return ids.reshape(self.B, N, N)
+        words = self.ring.gen.view(self.B, -1).cpu().numpy()[:, ops.gen_record_words(N):].astype(np.int64) & 0xFFFFFFFF
+        nib = (words[:, :, None] >> (4 * np.arange(8))) & 15
+        return nib.reshape(self.B, -1)[:, :N * N].astype(np.uint8).reshape(self.B, N, N)
 
     def stop(self):
         pass

@@ -97,7 +97,8 @@ def kernel_timer_stop():
 class Ring(object):
     """Device replay ring + per-actor environment state (layout: include/unreal_hip.h)."""
 
-    def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False, nav=False, gen=0):
+    def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False, nav=False, gen=0,
+                 gen_styled=False):
         self.B, self.H, self.H1 = B, H, H + 1
         self.objective_size = objective_size
         self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
@@ -136,8 +137,10 @@ class Ring(object):
             self.heading = self.nav.view(B, NAV_RECORD)[:, 0]
         # generated mazes (MazeConfig.generate = N = `gen`): [B, gen_record_words(N)] records (the 8 words above, then the
         # actor's own layout record and apple record, rewritten by every reset), handed to the kernels in place of `heading`
+        # (`gen_styled`: a styled config, DESIGN §7h: the record also ends in the actor's style_words(N) nibble words)
         self.gen_n = int(gen) if maze_state else 0
-        self.gen = z(B * gen_record_words(self.gen_n), dt=torch.int32) if self.gen_n else None
+        self.gen_words = gen_record_words(self.gen_n, bool(gen_styled))
+        self.gen = z(B * self.gen_words, dt=torch.int32) if self.gen_n else None
         if self.gen is not None:
             self.nav = None
             self.heading = self.gen.view(B, -1)[:, 0]
@@ -184,7 +187,8 @@ def ring_view(ring, b0, b1):
     nav = getattr(ring, "nav", None)
     v.nav = nav[b0 * NAV_RECORD:b1 * NAV_RECORD] if nav is not None else None
     v.gen_n, gen = getattr(ring, "gen_n", 0), getattr(ring, "gen", None)
-    v.gen = gen[b0 * gen_record_words(v.gen_n):b1 * gen_record_words(v.gen_n)] if gen is not None else None
+    v.gen_words = getattr(ring, "gen_words", gen_record_words(v.gen_n))
+    v.gen = gen[b0 * v.gen_words:b1 * v.gen_words] if gen is not None else None
     return v
 
 
@@ -194,18 +198,26 @@ NAV_RECORD = 8                                # int32 words of a navigation maze
 MAZE_RECORD_HEADER, NAV_APPLE_RECORD = 18, 65  # words of a layout record before its free list; of an apple record
 
 
-def gen_record_words(N):
+def style_words(N):
+    """int32 words of one maze's 4-bit style ids (UNREAL_MAZE_STYLE_WORDS(N))."""
+    return (N * N + 7) // 8
+
+
+def gen_record_words(N, styled=False):
     """int32 words of a generated maze's per-actor record (UNREAL_MAZE_GEN_RECORD(N)): the navigation record, the layout
-    record (18 + N * N) and the apple record (65)."""
-    return NAV_RECORD + MAZE_RECORD_HEADER + N * N + NAV_APPLE_RECORD if N else 0
+    record (18 + N * N) and the apple record (65); `styled`: of a styled block's (UNREAL_MAZE_GEN_STYLED_RECORD(N)), which
+    ends in the style ids."""
+    return NAV_RECORD + MAZE_RECORD_HEADER + N * N + NAV_APPLE_RECORD + (style_words(N) if styled else 0) if N else 0
 
 
 def _maze_args(ring, maze):
     """The maze tail of every maze entry.  `maze` (every maze wrapper) = (view, N, int32 config block on the device, global
-    index of the ring's actor 0) of a configured maze, or None for the reference's map, top-down."""
+    index of the ring's actor 0[, True for a styled block]) of a configured maze, or None for the reference's map,
+    top-down."""
     if maze is None:
         return (MAZE_TOP_DOWN, 7, None, 0, None, None, None, None, None)
-    view, N, block, actor_base = maze
+    view, N, block, actor_base = maze[:4]
+    styled = len(maze) > 4 and bool(maze[4])
     _chk(block, "i32", 8, "maze config")
     nav = getattr(ring, "nav", None)
     arrays = (("goal", 2 * ring.B), ("layout", ring.B), ("ep_steps", ring.B), ("episode", ring.B))
@@ -214,9 +226,10 @@ def _maze_args(ring, maze):
     if view == MAZE_FIRST_PERSON:
         arrays += (("nav", NAV_RECORD * ring.B),) if nav is not None else (("heading", ring.B),)
     if view == MAZE_FIRST_PERSON_GENERATED:
-        if getattr(ring, "gen_n", 0) != N:
-            raise ValueError("a generated maze needs a ring with per-actor records of its size (Ring(gen=%d))" % N)
-        arrays += (("gen", gen_record_words(N) * ring.B),)
+        if getattr(ring, "gen_n", 0) != N or getattr(ring, "gen_words", gen_record_words(N)) != gen_record_words(N, styled):
+            raise ValueError("a generated maze needs a ring with per-actor records of its size (Ring(gen=%d, gen_styled=%s))"
+                             % (N, styled))
+        arrays += (("gen", gen_record_words(N, styled) * ring.B),)
     for name, n in arrays:
         _chk(getattr(ring, name), "i32", n, "ring." + name)
     heading = nav if nav is not None and view == MAZE_FIRST_PERSON else ring.heading
