@@ -85,7 +85,20 @@ extern "C" {
  * draws once the walls are known: wall cell c with w = word c & 3 of the draw with counter (actor_base + b, episode,
  * 0x4D415A53, c >> 2) is a landmark iff (w >> 24) < gen_landmark_density, of style 1 + (w & 0xFFFFFF) % S.  The entries
  * and the view values are the same; the flag selects the styled path, and a launch with the wrong N still writes
- * nothing. */
+ * nothing.
+ * Goal sense (first person, flag 64 in the block's word 2, always with flag 8; views 3 and 4): words 5, 6, 7
+ * of the 8 navigation words hold gf, gs and d of the actor's current state: gf = (gx - x) dx + (gy - y) dy and gs =
+ * (gx - x) rx + (gy - y) ry, the goal's offset along the heading's forward axis d and right axis r, and d the path distance
+ * of the actor's cell: the length of the shortest 4-connected path over free cells to the episode's goal.  Every record
+ * ends in the actor's distance field, UNREAL_MAZE_DIST_WORDS(N) int32: cell c = y * N + x is the 16-bit half c & 1 of word
+ * c >> 1; wall cells, and the unused half of the last word where N * N is odd, hold 0xFFFF.  `heading` addresses B records
+ * of UNREAL_MAZE_SENSE_RECORD(N) int32 (a static block, view 3) or of UNREAL_MAZE_GEN_RECORD(N) / ..._GEN_STYLED_RECORD(N)
+ * + UNREAL_MAZE_DIST_WORDS(N) (a generated block, view 4).  The field is computed by a breadth-first search at every
+ * reset, the reset entry's and a step's terminal reset alike, after the goal is drawn (generated: after the layout is
+ * written); a respawn at the goal keeps it.  Word 6 of the navigation header is progress_reward p: a step's reward is the
+ * first-that-applies reward plus p * (d of the cell before the action - d of the cell the move ends in, before any respawn
+ * or reset).  A launch of view 3 / 4 on a block without the flag, or of view 1 / 2 on a block with it, writes nothing.
+ * unreal_maze_objective turns words 5..7 into the ring's objective vectors. */
 #define UNREAL_MAZE_NAV_RECORD 8
 #define UNREAL_MAZE_GEN_RECORD(N) (8 + 18 + (N) * (N) + 65)
 #define UNREAL_MAZE_STYLE_WORDS(N) (((N) * (N) + 7) / 8)
@@ -93,6 +106,10 @@ extern "C" {
 #define UNREAL_MAZE_TOP_DOWN 0
 #define UNREAL_MAZE_FIRST_PERSON 1
 #define UNREAL_MAZE_FIRST_PERSON_GENERATED 2
+#define UNREAL_MAZE_DIST_WORDS(N) (((N) * (N) + 1) / 2)
+#define UNREAL_MAZE_SENSE_RECORD(N) (8 + UNREAL_MAZE_DIST_WORDS(N))
+#define UNREAL_MAZE_FIRST_PERSON_SENSE 3
+#define UNREAL_MAZE_FIRST_PERSON_GENERATED_SENSE 4
 /* env.reset() of every actor where mask[b] != 0 (mask nullable) */
 int unreal_maze_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward, const int* count,
                       uint8_t* frames, int view, int N, const int* cfg, int actor_base, int* goal, int* layout,
@@ -135,6 +152,14 @@ int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, cons
                                     float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A, int idx_base_actor,
                                     int view, int N, const int* cfg, int actor_base, int* goal, int* layout,
                                     int* ep_steps, int* episode, int* heading, void* stream);
+/* The objective vectors of a goal-sense maze, from the per-actor records the maze entries keep behind
+ * `heading` (record_words int32 each, >= 8): for every actor b, {w5 / 32, w6 / 32, w7 / 512} of record b go to
+ * r_objective[(b * H1 + count[b] % H1) * 3 ..), the slot of the actor's current observation, and, with next_lar, to
+ * next_lar[b * lar_ld + lar_col0 .. + 3), the objective columns of the next step's LSTM-input row.  Nothing else is
+ * written; a second call writes the same values.  -EINVAL without a launch: B <= 0, H1 <= 0, record_words < 8, a null
+ * count / records / r_objective, or next_lar with lar_col0 < 0 or lar_ld < lar_col0 + 3. */
+int unreal_maze_objective(int B, int H1, const int* count, const int* records, int record_words, float* r_objective,
+                          float* next_lar /*nullable*/, int lar_ld, int lar_col0, void* stream);
 /* host-fed environments (environment/hostfed_environment.py): environment.process + experience.add_frame of
  * every actor where active[b] != 0, for simulators on the host.  `staged` holds one uint8 frame per actor, frame_stride
  * bytes apart as in the ring (a multiple of 16 within [1200, 691200]: 20 x 20 x 3 .. 480 x 480 x 3 rounded up to 16).

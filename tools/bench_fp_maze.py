@@ -12,10 +12,13 @@
     of generation per reset.  Then Trainer.process() on a generated config at B = 4096;
   * styled walls (--style-only): the step of a styled block next to the unstyled step of the same N, B and
     step limit, static (the same layouts, three wall cells in four carrying a digit 1..7) and generated (landmark
-    density 64).
+    density 64);
+  * goal sense (--sense-only): the step of a goal_sense block next to the step of the same navigation block
+    without the option, static and generated; the objective launch on its own; a full-batch reset() of a generated
+    N = 21 maze with and without the option (the difference is the breadth-first search); Trainer.process() on both.
 
   python tools/bench_fp_maze.py [--launches 200] [--steps 10] [--warmup 3] [--history 100]
-                                [--nav-only | --gen-only | --style-only]
+                                [--nav-only | --gen-only | --style-only | --sense-only]
 
 Prints one JSON line per measurement."""
 import argparse
@@ -56,8 +59,8 @@ def styled_layouts(N, L=8, seed=0):
     return out
 
 
-def kernel_ms(env, B, launches, A=4):
-    """Mean HIP-event time of one step launch (the entry point env.process calls)."""
+def kernel_ms(env, B, launches, A=4, entry="unreal_maze_step"):
+    """Mean HIP-event time of one step launch (the entry point env.process calls), or of the launches of `entry`."""
     from unreal_amd import ops
     rs = np.random.RandomState(0)
     acts = [torch.from_numpy(rs.randint(0, A, B).astype(np.int32)).to(DEV) for _ in range(8)]
@@ -65,9 +68,22 @@ def kernel_ms(env, B, launches, A=4):
     t = torch.zeros(B, dtype=torch.int32, device=DEV)
     for k in range(10):
         env.process(acts[k % 8], None, r, t, track_score=True)
-    ops.kernel_timer_start("unreal_maze_step")
+    ops.kernel_timer_start(entry)
     for k in range(launches):
         env.process(acts[k % 8], None, r, t, track_score=True)
+    res = ops.kernel_timer_stop()
+    assert res["launches"] == launches, res
+    return res["ms"] / launches
+
+
+def reset_ms(env, launches):
+    """Mean HIP-event time of the reset launch of a full-batch env.reset()."""
+    from unreal_amd import ops
+    for _ in range(10):
+        env.reset()
+    ops.kernel_timer_start("unreal_maze_reset")
+    for _ in range(launches):
+        env.reset()
     res = ops.kernel_timer_stop()
     assert res["launches"] == launches, res
     return res["ms"] / launches
@@ -82,7 +98,7 @@ def trainer_ms(env_name, B, history, steps, warmup):
     flags = get_options("training", preset="lab", argv=["--env_type", "maze", "--env_name", env_name])
     Environment.action_size = -1
     A = Environment.get_action_size("maze", env_name)
-    net = UnrealModel(A, 0, -1, flags.use_lstm, flags.use_pixel_change, flags.use_value_replay,
+    net = UnrealModel(A, Environment.get_objective_size("maze", env_name), -1, flags.use_lstm, flags.use_pixel_change, flags.use_value_replay,
                       flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta, DEV, seed=1)
     lr0 = log_uniform(flags.initial_alpha_low, flags.initial_alpha_high, flags.initial_alpha_log_rate)
     applier = RMSPropApplier(None, decay=flags.rmsp_alpha, momentum=0.0, epsilon=flags.rmsp_epsilon,
@@ -121,11 +137,53 @@ def main():
     ap.add_argument("--nav-only", action="store_true", help="only the navigation rows and their plain references")
     ap.add_argument("--gen-only", action="store_true", help="only the generated-maze rows and their static references")
     ap.add_argument("--style-only", action="store_true", help="only the styled rows and their unstyled references")
+    ap.add_argument("--sense-only", action="store_true", help="only the goal-sense rows and their references")
     args = ap.parse_args()
     from unreal_amd.environment.environment import Environment
     from unreal_amd.environment.maze_environment import MazeConfig, batched_maze_environment
     kw = dict(random_start=True, random_goal=True, show_goal=True, max_episode_steps=200)
     nav_kw = dict(goal_reward=10, apple_reward=1, hit_reward=0, goal_respawn=True, action_set="lab")
+    if args.sense_only:
+        for N in (7, 21):       # goal sense vs the same navigation block without it: same layouts, same process
+            for B in (512, 4096):
+                for kind in ("static", "generated"):
+                    res = {}
+                    for what in ("plain", "sense"):
+                        okw = dict(kw, **nav_kw)
+                        if what == "sense":
+                            okw.update(goal_sense=True, progress_reward=1)
+                        cfg = MazeConfig(layouts(N, apples=NAV_APPLES[N]), view="first_person", **okw) \
+                            if kind == "static" else MazeConfig(None, view="first_person", generate=N, **okw)
+                        env = batched_maze_environment(B, 3, DEV, config=cfg, seed=1)
+                        res[what] = kernel_ms(env, B, args.launches, A=6) * 1e3
+                        if what == "sense":
+                            res["objective"] = kernel_ms(env, B, args.launches, A=6, entry="unreal_maze_objective") * 1e3
+                        del env
+                    print(json.dumps(dict(what="sense_step_kernel", kind=kind, N=N, B=B, plain_us=round(res["plain"], 2),
+                                          sense_us=round(res["sense"], 2), ratio=round(res["sense"] / res["plain"], 3),
+                                          objective_launch_us=round(res["objective"], 2))), flush=True)
+        for B in (512, 4096):   # the search: a full-batch reset of a generated N = 21 maze
+            res = {}
+            for what in ("plain", "sense"):
+                cfg = MazeConfig(None, view="first_person", generate=21, **dict(kw, goal_sense=what == "sense"))
+                env = batched_maze_environment(B, 3, DEV, config=cfg, seed=1)
+                res[what] = reset_ms(env, args.launches) * 1e3
+                del env
+            print(json.dumps(dict(what="sense_reset_kernel", kind="generated", N=21, B=B, plain_us=round(res["plain"], 2),
+                                  sense_us=round(res["sense"], 2), bfs_us=round(res["sense"] - res["plain"], 2))),
+                  flush=True)
+        if not args.skip_trainer:
+            for what in ("plain", "sense"):
+                name = "bench_sense_" + what
+                okw = dict(kw, **nav_kw)
+                if what == "sense":
+                    okw.update(goal_sense=True, progress_reward=1)
+                Environment.register_maze_config(name, layouts(7, apples=NAV_APPLES[7]), view="first_person", **okw)
+                ms, wall = trainer_ms(name, 4096, args.history, args.steps, args.warmup)
+                print(json.dumps(dict(what="trainer_process", view="first_person_nav", goal_sense=what == "sense", A=6,
+                                      N=7, B=4096, history=args.history, ms_per_call=round(ms, 3),
+                                      wall_ms_per_call=round(wall, 3))), flush=True)
+        return
     if args.style_only:
         for N in (7, 21):       # styled vs unstyled first person, same N, B and step limit, same process
             for B in (512, 4096):

@@ -35,6 +35,13 @@
 // face, fixed to the world.  The colour is chosen per column by the DDA lane (fp_render) behind one uniform branch; the
 // style ids of a static block lie in the block, those of a generated block at the end of the actor's record (gen_maze).
 //
+// Goal-sense blocks (flag kMazeSense) keep the goal's offset in the actor's frame and the path distance of its
+// cell in words 5..7 of the actor record, and the episode's distance field at the record's end: every reset runs a
+// breadth-first search of the actor's maze from the goal (maze_bfs), a step reads two entries of the field and adds
+// progress_reward * (d before - d after) to its reward.  They run in kernels of their own (views kFirstPersonSense /
+// kFirstPersonGenSense), so the kernels of every other block are what they were.  unreal_maze_objective turns the three
+// record words into the ring's objective vector.
+//
 // One workgroup (256 threads) per actor.  The step renders s_{t+1} into LDS (lanes 0..83: one column's DDA each, over
 // the layout's wall bits in LDS; then every thread fills whole frame-row dwords), streams it to the ring slot with 16 B
 // per lane, turns the LDS image into |new - old| bytes against the stored frame (read at kernel entry, so its latency
@@ -47,7 +54,8 @@
 namespace {
 
 // UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON / UNREAL_MAZE_FIRST_PERSON_GENERATED
-constexpr int kTopDown = 0, kFirstPerson = 1, kFirstPersonGen = 2;
+// UNREAL_MAZE_FIRST_PERSON_SENSE / UNREAL_MAZE_FIRST_PERSON_GENERATED_SENSE
+constexpr int kTopDown = 0, kFirstPerson = 1, kFirstPersonGen = 2, kFirstPersonSense = 3, kFirstPersonGenSense = 4;
 
 // The reference's map as a configuration block (layout: maze_common.h).
 constexpr const char* kMap =
@@ -784,16 +792,85 @@ __device__ __forceinline__ void gen_maze(FpLds<N>& s, const int* cfg, int g, int
   __syncthreads();                     // the record and s.walls are written; s.img is free again
 }
 
+// ---- goal sense (flag kMazeSense) -----------------------------------------------------------------------------
+template <int N>
+struct DistLds {                       // the search's scratch: aliases FpLds<N>::img, which is rendered afterwards
+  uint16_t d[2 * maze_dist_words(N)];  // path distance of cell y * N + x (kMazeNoPath: a wall, or not reached yet)
+  int changed[3];                      // pass i sets [i % 3] and clears [(i + 1) % 3]: one barrier per pass
+};
+static_assert(sizeof(DistLds<21>) <= sizeof(uint4) * kChunks, "search scratch");
+
+// Breadth-first search from cell `goal` over the free cells of s.walls: every thread relaxes its (at most two) cells in
+// place against their four neighbours, pass after pass, until a pass changes no cell.  An entry only ever falls, and never
+// below the cell's distance, so a value read while a neighbour's thread replaces it is still an upper bound; a pass without
+// a change is a fixed point, which is the distance field.  Passes: the largest distance + 1 at the most (a 21 x 21
+// serpentine: 241).  Writes the field to `field` (maze_dist_words(N) words, global memory) and returns the entry of cell
+// `at`.  Call with the whole workgroup once s.walls is issued; s.img is overwritten.  Begins with a barrier and ends after
+// one: the caller may render straight away, since the render's first barrier precedes its first store to s.img.
+template <int N>
+__device__ __forceinline__ int maze_bfs(FpLds<N>& s, int goal, int at, int* field) {
+  constexpr int NN = N * N, DW = maze_dist_words(N);
+  DistLds<N>& t = *reinterpret_cast<DistLds<N>*>(s.img);
+  const int tid = threadIdx.x;
+  __syncthreads();                     // the wall bits are in LDS; every thread is done with s.img
+  int cell[2], nb[2][4];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int c = tid + 256 * q;
+    const bool fr = c < NN && !((s.walls[c >> 6] >> (c & 63)) & 1);
+    const int x = c % N, y = c / N;
+    cell[q] = fr ? c : -1;
+    nb[q][0] = x > 0 ? c - 1 : c;      // (off the map: the cell itself, which never lowers it)
+    nb[q][1] = x < N - 1 ? c + 1 : c;
+    nb[q][2] = y > 0 ? c - N : c;
+    nb[q][3] = y < N - 1 ? c + N : c;
+  }
+  for (int i = tid; i < 2 * DW; i += 256) t.d[i] = i == goal ? 0 : (uint16_t)kMazeNoPath;
+  if (tid < 3) t.changed[tid] = 0;
+  __syncthreads();
+  for (int f = 0;; f = f == 2 ? 0 : f + 1) {
+    if (tid == 0) t.changed[f == 2 ? 0 : f + 1] = 0;
+    bool ch = false;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      if (cell[q] < 0) continue;
+      const int cur = t.d[cell[q]];
+      const int m = min(min((int)t.d[nb[q][0]], (int)t.d[nb[q][1]]), min((int)t.d[nb[q][2]], (int)t.d[nb[q][3]]));
+      if (m + 1 < cur) { t.d[cell[q]] = (uint16_t)(m + 1); ch = true; }     // (m = kMazeNoPath: m + 1 > cur)
+    }
+    if (ch) t.changed[f] = 1;
+    __syncthreads();
+    if (!t.changed[f]) break;          // (uniform: nobody writes this flag before the pass after the next)
+  }
+  if (tid < DW) field[tid] = (int)((uint32_t)t.d[2 * tid] | ((uint32_t)t.d[2 * tid + 1] << 16));
+  return t.d[at];
+}
+
+// entry of cell c of a distance field in global memory
+__device__ __forceinline__ int maze_dist(const int* field, int c) {
+  return (int)(((uint32_t)field[c >> 1] >> (16 * (c & 1))) & 0xFFFFu);
+}
+
+// words of one actor's record behind `heading` (the distance field, when there is one, is its tail)
+template <int N, bool GEN, bool SENSE>
+__device__ __forceinline__ int fp_record_words(bool styled) {
+  const int base = GEN ? gen_actor_words(N) + (styled ? maze_style_words(N) : 0) : kNavActorWords;
+  return base + (SENSE ? maze_dist_words(N) : 0);
+}
+
 // The first-person step of one actor per workgroup.  NAV: a navigation block (kMazeNav): the per-actor
 // record behind `heading`, the block's rewards and action set, apples, and respawn at the goal.  GEN: a generated block
-// (kMazeGen): the layout and apple records are the actor's own, rewritten before the reset draw.
-template <int N, bool NAV, bool GEN>
+// (kMazeGen): the layout and apple records are the actor's own, rewritten before the reset draw.  SENSE (with
+// NAV): a goal-sense block (kMazeSense): the record ends in the distance field, words 5..7 are kept.
+template <int N, bool NAV, bool GEN, bool SENSE = false>
 __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
+  static_assert(NAV || !SENSE, "a goal-sense block is a navigation block");
   const int* cfg = p.cfg;
   const int b = blockIdx.x;
   const int H1 = p.H1;
   const bool styled = cfg[2] & kMazeStyled;       // (uniform) a styled block: its generated records carry the style ids
-  int* const actor = GEN ? p.heading + (size_t)(gen_actor_words(N) + (styled ? maze_style_words(N) : 0)) * b : nullptr;
+  const int rw = fp_record_words<N, GEN, SENSE>(styled);
+  int* const actor = GEN ? p.heading + (size_t)rw * b : nullptr;
   const int lay = GEN ? 0 : maze_layout(cfg, p.layout, b);
   const int* rec = GEN ? actor + kNavActorWords : maze_rec(cfg, lay);
   const int* ext = NAV ? maze_nav_ext(cfg) : nullptr;
@@ -838,7 +915,8 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
       old[k] = c < kChunks ? src[c] : make_uint4(0, 0, 0, 0);
     }
   }
-  int* hrec = GEN ? actor : p.heading + (NAV ? kNavActorWords * b : b);
+  int* hrec = GEN ? actor : p.heading + (NAV ? (size_t)rw * b : b);
+  int* const field = SENSE ? hrec + rw - maze_dist_words(N) : nullptr;
   const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
   const int x = p.pos[2 * b], y = p.pos[2 * b + 1], h = hrec[0] & 3;
   const int gx = p.goal[2 * b], gy = p.goal[2 * b + 1];
@@ -882,6 +960,12 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
       if (!hit) { nx = tx; ny = ty; moved = true; }
     }
   }
+  // goal sense: the path distances of the cell before the action and of the cell the move ends in
+  int d_before = 0, d_after = 0, d_now = 0;          // d_now: of the state the step leaves (after a respawn or reset)
+  if constexpr (SENSE) {
+    d_before = maze_dist(field, y * N + x);
+    d_now = d_after = moved ? maze_dist(field, ny * N + nx) : d_before;
+  }
   const bool at_goal = nx == gx && ny == gy;
   const int max_steps = cfg[3];
   const bool timeout = max_steps > 0 && steps >= max_steps;
@@ -898,6 +982,7 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
       int st;
       nav_respawn(cfg, rec, p.actor_base + b, epi, goals, gy * N + gx, st, eh);
       ex = st % N; ey = st / N;
+      if constexpr (SENSE) d_now = maze_dist(field, st);     // (the goal stays: the field does too)
     }
     // the active apples of the running episode; the apple of the cell moved into (never the goal's) is collected
     fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, bits, gy * N + gx);
@@ -920,6 +1005,7 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
   if (NAV) {
     const int col = s.collect;           // (written before the render's barriers)
     reward = at_goal ? (float)ext[0] : col >= 0 ? (float)ext[1] : hit ? (float)ext[2] : 0.f;
+    if constexpr (SENSE) reward += (float)(ext[kNavProgressWord] * (d_before - d_after));
     if (col >= 0) { bits |= 1ull << col; ++apples; }
     if (reset && threadIdx.x < FpLds<N>::NA) s.apples[threadIdx.x] = 0u;   // (read by nobody until the reset render)
   }
@@ -951,6 +1037,7 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
     maze_reset_cells(cfg, rec, p.actor_base + b, epi + 1, rg, rs);
     rx = rs % N; ry = rs / N; rgx = rg % N; rgy = rg / N;
     rh = fp_reset_heading(cfg, p.actor_base + b, epi + 1);
+    if constexpr (SENSE) d_now = maze_bfs<N>(s, rg, rs, field);      // the new episode's field (its barrier: as the render's)
     if (NAV) {                           // every apple is back
       bits = 0;
       fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, 0, rg);
@@ -971,6 +1058,12 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
       hrec[3] = goals;
       hrec[4] = apples;
     }
+    if constexpr (SENSE) {               // the state the slot now shows: goal ahead, goal to the right, path distance
+      const int fx = (rh == 0) - (rh == 2), fy = (rh == 1) - (rh == 3);
+      hrec[5] = (rgx - rx) * fx + (rgy - ry) * fy;
+      hrec[6] = (rgx - rx) * -fy + (rgy - ry) * fx;
+      hrec[7] = d_now;
+    }
     p.goal[2 * b] = rgx;
     p.goal[2 * b + 1] = rgy;
     p.ep_steps[b] = reset ? 0 : steps;
@@ -979,17 +1072,22 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
   }
 }
 
-template <int N, bool GEN>
+template <int N, bool GEN, bool SENSE = false>
 __device__ __forceinline__ void fp_step_entry(const MazeArgs& p) {
   const int* cfg = p.cfg;
   // (uniform) a block of another grid size, or a generated block in a static kernel (and the reverse): nothing is written
-  if (cfg[0] != N || (bool)(cfg[2] & kMazeGen) != GEN) return;
+  // (nor for a goal-sense block in another kernel than its own, whose records have another size)
+  if (cfg[0] != N || (bool)(cfg[2] & kMazeGen) != GEN || (bool)(cfg[2] & kMazeSense) != SENSE) return;
   __shared__ FpLds<N> s;
   const bool nav = cfg[2] & kMazeNav;
   // (uniform) a fused policy step whose A is not the block's action count: nothing is written either
   if (p.pol_x && p.A != (nav && (maze_nav_ext(cfg)[3] & kNavLabActions) ? 6 : 4)) return;
-  if (nav) fp_step<N, true, GEN>(p, s);
-  else fp_step<N, false, GEN>(p, s);
+  if constexpr (SENSE) {
+    if (nav) fp_step<N, true, GEN, true>(p, s);      // (a goal-sense block without the navigation header: malformed)
+  } else {
+    if (nav) fp_step<N, true, GEN>(p, s);
+    else fp_step<N, false, GEN>(p, s);
+  }
 }
 
 template <int N>
@@ -1000,12 +1098,17 @@ __global__ __launch_bounds__(256) void maze_fp_step_kernel(MazeArgs p) { fp_step
 template <int N>
 __global__ __launch_bounds__(256) void maze_fp_gen_step_kernel(MazeArgs p) { fp_step_entry<N, true>(p); }
 
-template <int N, bool NAV, bool GEN>
+// the steps of goal-sense blocks (views kFirstPersonSense / kFirstPersonGenSense): kernels of their own again
+template <int N, bool GEN>
+__global__ __launch_bounds__(256) void maze_fp_sense_step_kernel(MazeArgs p) { fp_step_entry<N, GEN, true>(p); }
+
+template <int N, bool NAV, bool GEN, bool SENSE = false>
 __device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
   const int* cfg = p.cfg;
   const int b = blockIdx.x;
   const bool styled = cfg[2] & kMazeStyled;
-  int* const actor = GEN ? p.heading + (size_t)(gen_actor_words(N) + (styled ? maze_style_words(N) : 0)) * b : nullptr;
+  const int rw = fp_record_words<N, GEN, SENSE>(styled);
+  int* const actor = GEN ? p.heading + (size_t)rw * b : nullptr;
   const int lay = GEN ? 0 : maze_layout(cfg, p.layout, b);
   const int* rec = GEN ? actor + kNavActorWords : maze_rec(cfg, lay);
   if constexpr (!GEN) fp_load_walls<N>(s, rec);
@@ -1019,6 +1122,9 @@ __device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
   maze_reset_cells(cfg, rec, g, epi + 1, gc, sc);
   const int h = fp_reset_heading(cfg, g, epi + 1);
   const int slot = p.count[b] % p.H1;
+  int* const hrec = GEN ? actor : p.heading + (NAV ? (size_t)rw * b : b);
+  int d_start = 0;
+  if constexpr (SENSE) d_start = maze_bfs<N>(s, gc, sc, hrec + rw - maze_dist_words(N));
   int n_apples = 0, my_apple = -1;
   if (NAV) {
     const int* arec = GEN ? rec + kRecHdr + N * N : maze_nav_ext(cfg) + kNavHdr + lay * kNavRec;
@@ -1033,9 +1139,14 @@ __device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
   if (threadIdx.x == 0) {
     p.pos[2 * b] = sc % N;
     p.pos[2 * b + 1] = sc / N;
-    int* hrec = GEN ? actor : p.heading + (NAV ? kNavActorWords * b : b);
     hrec[0] = h;
     if (NAV) { hrec[1] = 0; hrec[2] = 0; }          // every apple is back; goals_total / apples_total run on
+    if constexpr (SENSE) {
+      const int fx = (h == 0) - (h == 2), fy = (h == 1) - (h == 3), ox = gc % N - sc % N, oy = gc / N - sc / N;
+      hrec[5] = ox * fx + oy * fy;
+      hrec[6] = ox * -fy + oy * fx;
+      hrec[7] = d_start;
+    }
     p.goal[2 * b] = gc % N;
     p.goal[2 * b + 1] = gc / N;
     p.ep_steps[b] = 0;
@@ -1048,7 +1159,7 @@ __device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
 template <int N>
 __global__ __launch_bounds__(256) void maze_fp_reset_kernel(MazeArgs p) {
   const int* cfg = p.cfg;
-  if ((cfg[0] | (cfg[2] & kMazeGen) << 8) != N) return;               // as in fp_step_entry
+  if ((cfg[0] | (cfg[2] & (kMazeGen | kMazeSense)) << 8) != N) return;               // as in fp_step_entry
   const int b = blockIdx.x;
   if (p.mask && !p.mask[b]) return;
   __shared__ FpLds<N> s;
@@ -1059,12 +1170,40 @@ __global__ __launch_bounds__(256) void maze_fp_reset_kernel(MazeArgs p) {
 template <int N>
 __global__ __launch_bounds__(256) void maze_fp_gen_reset_kernel(MazeArgs p) {
   const int* cfg = p.cfg;
-  if ((cfg[0] | (cfg[2] & kMazeGen) << 8) != (N | kMazeGen << 8)) return;
+  if ((cfg[0] | (cfg[2] & (kMazeGen | kMazeSense)) << 8) != (N | kMazeGen << 8)) return;
   const int b = blockIdx.x;
   if (p.mask && !p.mask[b]) return;
   __shared__ FpLds<N> s;
   if (cfg[2] & kMazeNav) fp_reset<N, true, true>(p, s);
   else fp_reset<N, false, true>(p, s);
+}
+
+template <int N, bool GEN>
+__global__ __launch_bounds__(256) void maze_fp_sense_reset_kernel(MazeArgs p) {
+  const int* cfg = p.cfg;
+  constexpr int kKind = kMazeGen | kMazeSense | kMazeNav;             // as in fp_step_entry: this N, this kind of block
+  if ((cfg[0] | (cfg[2] & kKind) << 8) != (N | ((GEN ? kMazeGen : 0) | kMazeSense | kMazeNav) << 8)) return;
+  const int b = blockIdx.x;
+  if (p.mask && !p.mask[b]) return;
+  __shared__ FpLds<N> s;
+  fp_reset<N, true, GEN, true>(p, s);
+}
+
+// unreal_maze_objective: one thread per actor
+__global__ __launch_bounds__(256) void maze_objective_kernel(int B, int H1, const int* count, const int* records,
+                                                             int record_words, float* r_objective, float* next_lar,
+                                                             int lar_ld, int lar_col0) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const int* rec = records + (size_t)b * record_words;
+  const float o0 = (float)rec[5] * (1.f / 32.f), o1 = (float)rec[6] * (1.f / 32.f), o2 = (float)rec[7] * (1.f / 512.f);
+  const int slot = count[b] % H1;
+  float* dst = r_objective + ((size_t)b * H1 + slot) * 3;
+  dst[0] = o0; dst[1] = o1; dst[2] = o2;
+  if (next_lar) {
+    float* row = next_lar + (size_t)b * lar_ld + lar_col0;
+    row[0] = o0; row[1] = o1; row[2] = o2;
+  }
 }
 
 
@@ -1076,12 +1215,13 @@ enum MazeEntry { kReset, kStep, kRollout, kPolicy };
 bool maze_args_ok(MazeEntry e, const MazeArgs& p, int view, int N) {
   if (p.B <= 0 || p.H1 < 2 || !p.pos || !p.last_action || !p.last_reward || !p.count || !p.frames) return false;
   if ((uintptr_t)p.frames & 15) return false;
-  if (view != kTopDown && view != kFirstPerson && view != kFirstPersonGen) return false;
+  if (view < kTopDown || view > kFirstPersonGenSense) return false;
+  const bool gen = view == kFirstPersonGen || view == kFirstPersonGenSense;
   if (!p.cfg) {
     if (view != kTopDown || N != 7) return false;          // the reference's map
   } else if (!(N == 7 || N == 12 || N == 14 || N == 21) || p.actor_base < 0 || !p.goal || !p.ep_steps || !p.episode) {
     return false;                                           // grid sizes whose cells tile the 84-px frame: 12, 7, 6, 4 px
-  } else if ((view == kFirstPersonGen) != !p.layout) {
+  } else if (gen != !p.layout) {
     // layout ids are required with layout records; a generated block has none (its kernels never read the array), and
     // a tail that hands one over was built for another view: refused
     return false;
@@ -1102,7 +1242,13 @@ bool maze_args_ok(MazeEntry e, const MazeArgs& p, int view, int N) {
 
 template <int N>
 void maze_launch_n(bool reset, int view, const MazeArgs& p, hipStream_t s) {
-  if (view == kFirstPersonGen) {
+  if (view == kFirstPersonSense) {
+    if (reset) hipLaunchKernelGGL((maze_fp_sense_reset_kernel<N, false>), dim3(p.B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((maze_fp_sense_step_kernel<N, false>), dim3(p.B), dim3(256), 0, s, p);
+  } else if (view == kFirstPersonGenSense) {
+    if (reset) hipLaunchKernelGGL((maze_fp_sense_reset_kernel<N, true>), dim3(p.B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((maze_fp_sense_step_kernel<N, true>), dim3(p.B), dim3(256), 0, s, p);
+  } else if (view == kFirstPersonGen) {
     if (reset) hipLaunchKernelGGL(maze_fp_gen_reset_kernel<N>, dim3(p.B), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(maze_fp_gen_step_kernel<N>, dim3(p.B), dim3(256), 0, s, p);
   } else if (view == kFirstPerson) {
@@ -1194,6 +1340,15 @@ int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, cons
              active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
              Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
   return maze_launch(kPolicy, p, view, N, cfg, actor_base, goal, layout, ep_steps, episode, heading, stream);
+}
+
+int unreal_maze_objective(int B, int H1, const int* count, const int* records, int record_words, float* r_objective,
+                          float* next_lar, int lar_ld, int lar_col0, void* stream) {
+  if (B <= 0 || H1 <= 0 || record_words < kNavActorWords || !count || !records || !r_objective) return UNREAL_EINVAL;
+  if (next_lar && (lar_col0 < 0 || lar_ld < lar_col0 + 3)) return UNREAL_EINVAL;
+  hipLaunchKernelGGL(maze_objective_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, B, H1, count, records,
+                     record_words, r_objective, next_lar, lar_ld, lar_col0);
+  return unreal_launch_status();
 }
 
 }  // extern "C"

@@ -43,7 +43,7 @@ constexpr uint32_t kMazeRespawnStream = 0x4D415A52u;
 
 // ---- navigation extension (flag kMazeNav, first person only), after the last layout record ------------------------------
 // ext = cfg + kCfgHdr + L * rec:  [0] goal reward  [1] apple reward  [2] hit reward  [3] mode bits (kNavRespawn,
-//   kNavLabActions)  [4..7] 0;  apple record of layout l at ext + kNavHdr + l * kNavRec: [0] n apples (<= 64)  [1 .. n]
+//   kNavLabActions)  [4..5] 0  [6] progress reward (kMazeSense)  [7] 0;  apple record of layout l at ext + kNavHdr + l * kNavRec: [0] n apples (<= 64)  [1 .. n]
 //   apple cells, ascending (apple bit k of an actor is the k-th of them)
 constexpr int kNavHdr = 8, kNavRec = 65, kMaxApples = 64;
 constexpr int kNavRespawn = 1, kNavLabActions = 2;
@@ -71,6 +71,20 @@ constexpr int kMazeStyled = 32;
 constexpr int kStyleHdr = 8, kStyleSlots = 8;
 constexpr uint32_t kMazeStyleStream = 0x4D415A53u;
 constexpr int maze_style_words(int N) { return (N * N + 7) / 8; }
+
+// ---- goal sense (flag kMazeSense, first person navigation blocks only): goal offset and path distance ------
+// Words 5, 6, 7 of the navigation actor record hold gf, gs (the goal's offset along the forward and right axes of the
+// actor's heading) and d, the path distance of its cell: the length of the shortest 4-connected path over free cells to
+// the episode's goal.  Every per-actor record ends in the actor's distance field, maze_dist_words(N) words written by
+// every reset (after the goal is drawn; a generated block: after its layout and style ids): cell c is the 16-bit half
+// c & 1 of word c >> 1, kMazeNoPath in wall cells and in the unused half of the last word (N * N is odd at 7 and 21).
+// A static block's records are then kNavActorWords + maze_dist_words(N) words; a generated block's grow by the same.
+// Word 6 of the navigation header is progress_reward p: a step's reward is the block's first-that-applies reward plus
+// p * (d before the action - d of the cell the move ends in, before any respawn or reset).
+constexpr int kMazeSense = 64;
+constexpr int kNavProgressWord = 6;
+constexpr uint32_t kMazeNoPath = 0xFFFFu;
+constexpr int maze_dist_words(int N) { return (N * N + 1) / 2; }
 
 // The Philox words of global actor g's reset into episode `ep`: word 0 draws the goal, word 1 the start, word 2 the
 // first-person heading.

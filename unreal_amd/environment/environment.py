@@ -35,7 +35,7 @@ class Environment(object):
     def register_maze_config(env_name, layouts=None, random_start=False, random_goal=False, show_goal=False,
                              max_episode_steps=0, view="top_down", start_heading=None, goal_reward=1, apple_reward=1,
                              hit_reward=-1, goal_respawn=False, action_set="turn", generate=None, gen_loops=0,
-                             gen_apples=0, wall_styles=None, gen_landmark_density=0):
+                             gen_apples=0, wall_styles=None, gen_landmark_density=0, goal_sense=False, progress_reward=0):
         """Mazes of `env_name`: `layouts` = N x N maps (strings, or lists of row strings; + wall, - free, S start, G goal),
         N in {7, 12, 14, 21}, up to 1024 of them; global actor g runs layout g * L // (all actors).  random_start /
         random_goal: drawn at every reset, uniformly over the free cells (the start never on the goal); show_goal: the
@@ -53,12 +53,17 @@ class Environment(object):
         are wall cells drawn in style k: its colour, halved in the eighths of a cell's face whose bit of `pattern` is set
         (stripes fixed to the world, the same from every cell and heading); gen_landmark_density in 0..256 (with generate
         and wall_styles): every wall cell of a generated maze is such a landmark with probability density / 256.
+        goal_sense=True (first person): every state carries an 'objective' vector [gf / 32, gs / 32, d / 512]:
+        the goal's offset ahead of and to the right of the agent, in cells, and the length d of the shortest path to it;
+        get_objective_size('maze', env_name) is then 3 and the network needs objective_size=3.  progress_reward (an
+        integer in [-100, 100]; needs goal_sense) adds progress_reward * (d before the move - d after it) to every step's
+        reward.
         Raises ValueError on a malformed config."""
         from .maze_environment import MazeConfig
         Environment.MAZE_CONFIG[env_name] = MazeConfig(layouts, random_start, random_goal, show_goal, max_episode_steps,
                                                        view, start_heading, goal_reward, apple_reward, hit_reward,
                                                        goal_respawn, action_set, generate, gen_loops, gen_apples,
-                                                       wall_styles, gen_landmark_density)
+                                                       wall_styles, gen_landmark_density, goal_sense, progress_reward)
 
     @staticmethod
     def create_environment(env_type, env_name, termination_time=50.0, env_args=None, thread_index=0):
@@ -93,6 +98,9 @@ class Environment(object):
     def get_objective_size(env_type, env_name):
         if env_type == 'indoor':               # environment.py:68-72 -> indoor_environment.py:26-29
             return Environment.INDOOR_CONFIG.get(env_name, {}).get('objective_size', 0)
+        conf = Environment.MAZE_CONFIG.get(env_name) if env_type == 'maze' else None
+        if conf is not None and conf.goal_sense:       # a goal-sense maze: goal offset and path distance
+            return conf.OBJECTIVE_SIZE
         return 0
 
     @staticmethod

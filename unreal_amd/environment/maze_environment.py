@@ -13,7 +13,9 @@ apples ('A' cells), configurable rewards, respawn at the goal and Lab's six acti
 config has no layouts: every reset writes a new maze for the actor on the device (DESIGN §7g);
 `MazeConfig.generated_layout` computes the same maze on the host.  With wall_styles, first-person wall cells written as
 digits 1..7 (or drawn as landmarks of a generated maze, gen_landmark_density) show a colour and a stripe pattern of
-their own."""
+their own.  With goal_sense a first-person config hands the agent a measurement vector, the goal's offset
+in its own frame and the shortest-path distance to it, as the state's 'objective', and progress_reward pays for getting
+closer."""
 from collections import deque
 
 import numpy as np
@@ -36,7 +38,9 @@ class MazeConfig(object):
     tail of the unreal_maze_* entries in include/unreal_hip.h).  Raises ValueError on a malformed configuration."""
     SIZES = (7, 12, 14, 21)          # the grid sizes whose cells tile the 84-px frame: 12, 7, 6, 4 px
     MAX_LAYOUTS = 1024
-    RANDOM_START, RANDOM_GOAL, SHOW_GOAL, NAV, GENERATED, STYLED = 1, 2, 4, 8, 16, 32
+    RANDOM_START, RANDOM_GOAL, SHOW_GOAL, NAV, GENERATED, STYLED, GOAL_SENSE = 1, 2, 4, 8, 16, 32, 64
+    # goal sense (DESIGN §7i): objective = [gf / 32, gs / 32, d / 512]; progress_reward is word 6 of the navigation header
+    OBJECTIVE_SIZE, OFFSET_SCALE, DISTANCE_SCALE, PROGRESS_WORD, NO_PATH = 3, 32, 512, 6, 0xFFFF
     GEN_STREAM, APPLE_STREAM = 0x4D415A47, 0x4D415A41      # Philox counter word 2 of a generated maze's edge / apple draws
     STYLE_STREAM = 0x4D415A53                              # ... and of its landmark draws
     # style section after everything else (maze_common.h): header [S, gen_landmark_density, 0 x 6], 8 style words
@@ -54,7 +58,7 @@ class MazeConfig(object):
     def __init__(self, layouts=None, random_start=False, random_goal=False, show_goal=False, max_episode_steps=0,
                  view="top_down", start_heading=None, goal_reward=1, apple_reward=1, hit_reward=-1,
                  goal_respawn=False, action_set="turn", generate=None, gen_loops=0, gen_apples=0, wall_styles=None,
-                 gen_landmark_density=0):
+                 gen_landmark_density=0, goal_sense=False, progress_reward=0):
         self.generate, self.gen_loops, self.gen_apples = None, 0, 0
         self._check_styles(wall_styles, gen_landmark_density, view, generate)
         if generate is not None:
@@ -82,12 +86,18 @@ class MazeConfig(object):
                                  % (start_heading,))
             start_heading = int(start_heading)
         self.view, self.start_heading = view, start_heading
-        rewards = dict(goal_reward=goal_reward, apple_reward=apple_reward, hit_reward=hit_reward)
+        rewards = dict(goal_reward=goal_reward, apple_reward=apple_reward, hit_reward=hit_reward,
+                       progress_reward=progress_reward)
         for k, v in rewards.items():
             if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or \
                     not -self.MAX_REWARD <= v <= self.MAX_REWARD:
                 raise ValueError("%s %r: an integer in [-%d, %d]" % (k, v, self.MAX_REWARD, self.MAX_REWARD))
         self.goal_reward, self.apple_reward, self.hit_reward = int(goal_reward), int(apple_reward), int(hit_reward)
+        self.goal_sense, self.progress_reward = bool(goal_sense), int(progress_reward)
+        if self.goal_sense and view != "first_person":
+            raise ValueError("goal_sense is a first-person setting; view is %r" % (view,))
+        if self.progress_reward and not self.goal_sense:
+            raise ValueError("progress_reward %d needs goal_sense (the path distance it pays for)" % self.progress_reward)
         if action_set not in self.ACTION_SETS:
             raise ValueError("action_set %r: one of %s" % (action_set, self.ACTION_SETS))
         self.goal_respawn, self.action_set = bool(goal_respawn), action_set
@@ -111,7 +121,8 @@ class MazeConfig(object):
             self._check(i, m)
         # a navigation maze: any of the options above, or an apple in a layout (the default block stays word for word)
         # (a generated maze with apples is one too)
-        self.nav = nav_options or any(len(a) for a in self.apples) or self.gen_apples > 0
+        # (and so is a goal-sense maze: its block carries the rewards header, its actors keep records)
+        self.nav = nav_options or any(len(a) for a in self.apples) or self.gen_apples > 0 or self.goal_sense
 
     def _check_styles(self, wall_styles, density, view, generate):
         integer = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
@@ -276,7 +287,7 @@ class MazeConfig(object):
     def flags(self):
         return (self.RANDOM_START * self.random_start) | (self.RANDOM_GOAL * self.random_goal) | \
             (self.SHOW_GOAL * self.show_goal) | (self.NAV * self.nav) | (self.GENERATED * (self.generate is not None)) | \
-            (self.STYLED * self.styled)
+            (self.STYLED * self.styled) | (self.GOAL_SENSE * self.goal_sense)
 
     @property
     def action_size(self):
@@ -284,8 +295,46 @@ class MazeConfig(object):
 
     @property
     def reward_bound(self):
-        """max |reward| of a step (1 for every config without navigation rewards)."""
-        return max(abs(self.goal_reward), abs(self.apple_reward), abs(self.hit_reward))
+        """max |reward| over the kinds of step (1 for every config without navigation rewards): a goal step pays
+        goal_reward + p (it always gets one cell closer), an apple step apple_reward +- p, a hit hit_reward, any other
+        move +- p, with p = progress_reward."""
+        p = self.progress_reward
+        return max(abs(self.goal_reward + p), abs(self.apple_reward) + abs(p), abs(self.hit_reward), abs(p))
+
+    @staticmethod
+    def dist_words(N):
+        """int32 words of one actor's distance field, 16 bits per cell (UNREAL_MAZE_DIST_WORDS(N))."""
+        return (N * N + 1) // 2
+
+    @property
+    def record_words(self):
+        """int32 words of the per-actor record the kernels keep for this config (0: none, a plain heading array)."""
+        dist = self.dist_words(self.N) if self.goal_sense else 0
+        if self.generate is not None:
+            return ops.gen_record_words(self.N, self.styled) + dist
+        return ops.NAV_RECORD + dist if self.nav else 0
+
+    def distance_field(self, layout, goal):
+        """Path distances to cell `goal` (y * N + x) over `layout`, a layout string or an index into this config's
+        layouts -> uint16 [N, N] ([y, x]): the length of the shortest 4-connected path over free cells, NO_PATH in walls:
+        what the device writes at a reset."""
+        N = self.N
+        if isinstance(layout, str):
+            wall = np.array([ch in self.WALL_CHARS for ch in "".join(layout.split())], dtype=bool)
+        else:
+            wall = self.walls[layout]
+        d = np.full(N * N, self.NO_PATH, dtype=np.uint16)
+        d[goal] = 0
+        todo = deque([int(goal)])
+        while todo:
+            c = todo.popleft()
+            x, y = c % N, c // N
+            for nx, ny in ((x + 1, y), (x - 1, y), (x, y + 1), (x, y - 1)):
+                n = ny * N + nx
+                if 0 <= nx < N and 0 <= ny < N and not wall[n] and d[n] == self.NO_PATH and n != goal:
+                    d[n] = d[c] + 1
+                    todo.append(n)
+        return d.reshape(N, N)
 
     def block(self, seed):
         """-> int32 numpy array: header [N, L, flags, max_episode_steps, seed lo, seed hi, record words, start heading + 1
@@ -293,7 +342,8 @@ class MazeConfig(object):
         layout [wall bits of cell y*N+x as 7 x (lo, hi) uint32, S cell, G cell, n_free, index of G in the free list,
         free cells ascending] (-1: none); a navigation maze (flag NAV) appends [goal reward, apple reward, hit reward, mode
         (1: goal_respawn, 2: Lab's actions), 0, 0, 0, 0] and per layout [n apples, apple cells ascending, 0 padding to
-        65 words].  A generated maze (flag GENERATED) has L = 0 and no records: after the header come the 8 words
+        65 words]; a goal-sense maze (flag GOAL_SENSE) is a navigation maze whose header word 6 is
+        progress_reward.  A generated maze (flag GENERATED) has L = 0 and no records: after the header come the 8 words
         [goal reward, apple reward, hit reward, mode, gen_loops, gen_apples, 0, 0]; the layout and apple records are
         per actor, written on the device at every reset.  A styled maze (flag STYLED) appends, after all of
         this, [S, gen_landmark_density, 0 x 6], the 8 style words r | g << 8 | b << 16 | pattern << 24 (unused: 0) and,
@@ -317,6 +367,7 @@ class MazeConfig(object):
             ext = np.zeros(self.NAV_HEADER + self.L * self.NAV_RECORD, dtype=np.int64)
             mode = self.NAV_RESPAWN * self.goal_respawn | self.NAV_LAB_ACTIONS * (self.action_set == "lab")
             ext[:6] = [self.goal_reward, self.apple_reward, self.hit_reward, mode, self.gen_loops, self.gen_apples]
+            ext[self.PROGRESS_WORD] = self.progress_reward
             for l, a in enumerate(self.apples):
                 r = ext[self.NAV_HEADER + l * self.NAV_RECORD:]
                 r[0] = len(a)
@@ -345,7 +396,8 @@ class MazeConfig(object):
         maze: its walls, free cells and apples as a MazeConfig)."""
         return MazeConfig([layout_string], self.random_start, self.random_goal, self.show_goal, self.max_episode_steps,
                           self.view, self.start_heading, self.goal_reward, self.apple_reward, self.hit_reward,
-                          self.goal_respawn, self.action_set, wall_styles=self.wall_styles)
+                          self.goal_respawn, self.action_set, wall_styles=self.wall_styles, goal_sense=self.goal_sense,
+                          progress_reward=self.progress_reward)
 
     @staticmethod
     def reference():
@@ -379,10 +431,12 @@ class BatchedMazeEnvironment(object):
         `seed`: key of the reset draws."""
         self.B = batch
         self.config = config
+        sense = config is not None and config.goal_sense
         self.ring = ops.Ring(batch, history_size, torch.device(device), maze_state=config is not None,
                              nav=config is not None and config.nav,
                              gen=(config.generate or 0) if config is not None else 0,
-                             gen_styled=config is not None and config.styled)
+                             gen_styled=config is not None and config.styled,
+                             objective_size=config.OBJECTIVE_SIZE if sense else 0, sense=config.N if sense else 0)
         self.maze = None
         if config is not None:
             total = batch if actors_total is None else int(actors_total)
@@ -393,6 +447,8 @@ class BatchedMazeEnvironment(object):
             view = ops.MAZE_FIRST_PERSON if config.view == "first_person" else ops.MAZE_TOP_DOWN
             if config.generate is not None:
                 view = ops.MAZE_FIRST_PERSON_GENERATED
+            if config.goal_sense:                  # kernels of their own
+                view = ops.MAZE_FIRST_PERSON_SENSE if config.generate is None else ops.MAZE_FIRST_PERSON_GENERATED_SENSE
             self.maze = (view, config.N, block, int(actor_base)) + ((True,) if config.styled else ())
         self.reset()
 
@@ -410,12 +466,28 @@ class BatchedMazeEnvironment(object):
     def get_action_size():
         return 4
 
+    @property
+    def objective_size(self):
+        return self.ring.objective_size
+
+    def _objective(self, nxt=None):
+        """Goal-sense configs: the objective of every actor's current state into its ring slot, after every kernel that
+        changes the state (and into the next step's LSTM-input rows, next to the columns the step has written)."""
+        if not self.ring.objective_size:
+            return
+        if nxt and nxt.get("next_lar") is not None:
+            ops.maze_objective(self.ring, nxt["next_lar"], nxt["lar_ld"], nxt["lar_col0"] + nxt["A"] + 1)
+        else:
+            ops.maze_objective(self.ring)
+
     def reset(self, mask=None):
         ops.maze_reset(self.ring, mask, maze=self.maze)
+        self._objective()
 
     def process(self, actions, active=None, out_reward=None, out_terminal=None, reset_on_terminal=True,
                 track_score=False):
         ops.maze_step(self.ring, actions, active, out_reward, out_terminal, reset_on_terminal, track_score, maze=self.maze)
+        self._objective()
 
     def rollout_step(self, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
                      index_parent=False, **nxt):
@@ -423,6 +495,7 @@ class BatchedMazeEnvironment(object):
         `index_parent` (views only): the prepared frame indices address the ring this view was cut from."""
         ops.maze_rollout_step(self.ring, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
                               base_actor=getattr(self, "base_actor", 0) if index_parent else 0, maze=self.maze, **nxt)
+        self._objective(nxt)
 
     def policy_rollout_step(self, net, feat, ld, u, pi_out, v_out, actions, out_reward, out_terminal, active, active_log_t,
                             n_steps, terminal_end, index_parent=False, **nxt):
@@ -434,6 +507,17 @@ class BatchedMazeEnvironment(object):
                                      p["b_base_fc_v"], u, pi_out, v_out, actions, out_reward, out_terminal, active,
                                      active_log_t, n_steps, terminal_end,
                                      base_actor=getattr(self, "base_actor", 0) if index_parent else 0, maze=self.maze, **nxt)
+        self._objective(nxt)
+
+    def current_distances(self):
+        """The distance fields of the running episodes of a goal-sense config -> uint16 [B, N, N] ([b, y, x]): path
+        distance of every cell to the actor's goal, MazeConfig.NO_PATH in walls."""
+        if self.config is None or not self.config.goal_sense:
+            raise ValueError("current_distances: the config has no goal_sense")
+        N = self.config.N
+        words = self.ring.actor_records.cpu().numpy()[:, self.ring.record_words - ops.dist_words(N):]
+        halves = np.ascontiguousarray(words).view(np.uint16)              # little-endian: half c & 1 of word c >> 1
+        return halves[:, :N * N].reshape(self.B, N, N).copy()
 
     def current_layouts(self):
         """The layouts the actors of a generated maze are in -> (walls, apples): bool [B, N, N] (True: wall; [b, y, x])
@@ -441,7 +525,7 @@ class BatchedMazeEnvironment(object):
         if self.config is None or self.config.generate is None:
             raise ValueError("current_layouts: the config is not a generated maze")
         N = self.config.N
-        rec = self.ring.gen.view(self.B, -1).cpu().numpy()[:, ops.NAV_RECORD:ops.gen_record_words(N)]
+        rec = self.ring.actor_records.cpu().numpy()[:, ops.NAV_RECORD:ops.gen_record_words(N)]
         words = rec[:, :14].astype(np.int64) & 0xFFFFFFFF
         bits = (words[:, :, None] >> np.arange(32)) & 1
         walls = bits.reshape(self.B, 448)[:, :N * N].astype(bool).reshape(self.B, N, N)
@@ -457,7 +541,8 @@ class BatchedMazeEnvironment(object):
         if self.config.generate is None:
             ids = np.stack(self.config.styles)[self.ring.layout.cpu().numpy()]
             return ids.reshape(self.B, N, N)
-        words = self.ring.gen.view(self.B, -1).cpu().numpy()[:, ops.gen_record_words(N):].astype(np.int64) & 0xFFFFFFFF
+        words = self.ring.actor_records.cpu().numpy()[:, ops.gen_record_words(N):ops.gen_record_words(N, True)]
+        words = words.astype(np.int64) & 0xFFFFFFFF
         nib = (words[:, :, None] >> (4 * np.arange(8))) & 15
         return nib.reshape(self.B, -1)[:, :N * N].astype(np.uint8).reshape(self.B, N, N)
 
@@ -509,9 +594,19 @@ class MazeEnvironment(environment.Environment):
         # the pixel values (top-down 0 / 1; first person bytes / 255)
         return img if self._env.frame_scale == 1.0 else img / round(1.0 / self._env.frame_scale)
 
+    def _state(self, image):
+        """The state dict: 'image' and, for a goal-sense config, 'objective' (float64 [3]: goal ahead / 32, goal to the
+        right / 32, path distance / 512) as indoor_environment.py:70-73 hands its measurements over."""
+        state = {'image': image}
+        ring = self._env.ring
+        if ring.objective_size:
+            slot = int(ring.count.cpu()[0]) % ring.H1
+            state['objective'] = ring.r_objective[3 * slot:3 * slot + 3].cpu().numpy().astype(np.float64)
+        return state
+
     def reset(self):
         self._env.reset()
-        self.last_state = {'image': self._image()}
+        self.last_state = self._state(self._image())
         self.last_action = 0
         self.last_reward = 0
 
@@ -524,7 +619,7 @@ class MazeEnvironment(environment.Environment):
         reward = int(self._r.cpu()[0])
         terminal = bool(self._t.cpu()[0])
         pc = ring.r_pc[slot * ops.PC_CELLS:(slot + 1) * ops.PC_CELLS].cpu().numpy().reshape(20, 20)
-        self.last_state = {'image': image}
+        self.last_state = self._state(image)
         self.last_action = int(action)
         self.last_reward = reward
         self._last_full_state = {"success": terminal}

@@ -8,7 +8,10 @@ such episodes count as failures ("success := terminal").  With `maze=
 Environment.register_maze_config) the actors run that configured maze: success is reaching the goal (terminal with reward
 +1), and a time-out is the environment's own (its max_episode_steps); `max_episode_steps` here bounds episodes only when
 the config sets no limit.  On a navigation maze success is an episode with at least one goal, read from the
-per-actor goals_total / apples_total counters; with goal_respawn an episode ends only at its time-out."""
+per-actor goals_total / apples_total counters; with goal_respawn an episode ends only at its time-out.  On a goal-sense
+maze without goal_respawn the result also holds `start_distance`, the mean path distance d0 from start to
+goal of the counted episodes, and `spl`, the mean of success * d0 / max(d0, episode length in steps): every action is a
+step, turns and looks included, so an agent on the shortest path scores d0 / (d0 + its turns)."""
 import torch
 
 from . import ops
@@ -32,6 +35,9 @@ class Evaluate(object):
                     raise KeyError("maze %r: call Environment.register_maze_config(name, layouts, ...) first" % maze)
                 self.maze_config = Environment.MAZE_CONFIG[maze]
             self.env = batched_maze_environment(B, 2, self.device, config=self.maze_config, seed=seed)
+            if self.env.ring.objective_size != network._objective_size:
+                raise ValueError("the network's objective_size %d differs from the maze's %d"
+                                 % (network._objective_size, self.env.ring.objective_size))
             if self.maze_config is not None and self.maze_config.reward_bound > 1:
                 network.lar_bounded = False    # raw navigation rewards in the LSTM input (Trainer.prepare)
         else:
@@ -52,7 +58,7 @@ class Evaluate(object):
 
     def process(self, n_episodes, max_episode_steps=2000, one_episode_per_actor=False):
         """-> dict(episodes, success_rate, mean_return, return_std, mean_length, timeouts, goals_per_episode,
-        apples_per_episode).
+        apples_per_episode[, start_distance, spl]).
         `one_episode_per_actor`: count only the FIRST episode of each of the B lock-step actors and stop when all B have
         finished or timed out (n_episodes is ignored).  Stopping at the first n finished episodes instead over-represents
         short episodes whenever actors restart while others are still in their first one."""
@@ -74,6 +80,11 @@ class Evaluate(object):
         if nav:                                # goals_total / apples_total (never zeroed by a reset): per-episode differences
             tot = ring.actor_records[:, 3:5]
             ep0 = tot.cpu().numpy().copy()
+        # goal sense: path efficiency.  d0 = word 7 of the actor's record after the reset that started the episode
+        sense = cfg is not None and cfg.goal_sense and not cfg.goal_respawn
+        start_d, spl = [], []
+        if sense:
+            d0 = ring.actor_records[:, 7].cpu().numpy().copy()
         if one_episode_per_actor:
             n_episodes = B
         while done < n_episodes:
@@ -96,6 +107,7 @@ class Evaluate(object):
             rew = self.rewards.cpu().numpy()
             score = ring.score_out.cpu().numpy()
             now = tot.cpu().numpy() if nav else None
+            d_now = ring.actor_records[:, 7].cpu().numpy() if sense else None
             force = torch.zeros(B, dtype=torch.int32)
             ep_r = None
             for b in range(B):
@@ -111,10 +123,16 @@ class Evaluate(object):
                 if term[b]:
                     if not skip:
                         returns.append(float(score[b])); lengths.append(steps[b]); done += 1
-                        if not configured or (goals[-1] > 0 if nav else rew[b] == 1.0):
+                        success = not configured or (goals[-1] > 0 if nav else rew[b] == 1.0)
+                        if success:
                             successes += 1
                         else:
                             timeouts += 1              # the configured maze's own time-out
+                        if sense:
+                            start_d.append(int(d0[b]))
+                            spl.append(d0[b] / float(max(d0[b], steps[b])) if success else 0.0)
+                    if sense:
+                        d0[b] = d_now[b]               # the step's own reset has started the next episode
                     steps[b] = 0; counted[b] = True
                 elif not env_limit and steps[b] >= max_episode_steps:
                     if ep_r is None:
@@ -122,16 +140,24 @@ class Evaluate(object):
                     if not skip:
                         timeouts += 1; done += 1
                         returns.append(float(ep_r[b])); lengths.append(max_episode_steps)
+                        if sense:
+                            start_d.append(int(d0[b])); spl.append(0.0)
                     steps[b] = 0; force[b] = 1; counted[b] = True
             if int(force.sum()):                   # abandon timed-out episodes
                 m = force.to(self.device)
                 self.env.reset(m)
                 ring.episode_reward.mul_((1 - m).to(torch.float32))
+                if sense:
+                    forced = force.numpy().astype(bool)                    # (running episodes keep theirs)
+                    d0[forced] = ring.actor_records[:, 7].cpu().numpy()[forced]
                 if net._use_lstm:
                     ops.reset_state(B, m, ws.c0, ws.h0)
         n = len(returns)
         mean = sum(returns) / n
-        return dict(episodes=n, success_rate=successes / float(n), mean_return=mean,
-                    return_std=(sum((r - mean) ** 2 for r in returns) / n) ** 0.5,
-                    mean_length=sum(lengths) / float(n), timeouts=timeouts, goals_per_episode=sum(goals) / float(n),
-                    apples_per_episode=sum(apples) / float(n))
+        res = dict(episodes=n, success_rate=successes / float(n), mean_return=mean,
+                   return_std=(sum((r - mean) ** 2 for r in returns) / n) ** 0.5,
+                   mean_length=sum(lengths) / float(n), timeouts=timeouts, goals_per_episode=sum(goals) / float(n),
+                   apples_per_episode=sum(apples) / float(n))
+        if sense:
+            res.update(start_distance=sum(start_d) / float(n), spl=sum(spl) / float(n))
+        return res

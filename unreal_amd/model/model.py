@@ -436,11 +436,13 @@ class UnrealModel(object):
         return ws.s_f2, ws.s_x, ws.s_c1
 
     def encode_rows(self, ring, ws, row0, nrows, lar_from_ring=True, save_c1=True, clip_lar=False,
-                    objective_slot_offset=0, actor_ring=None, lar_prefilled=False, lstm_x=True, slots=None):
+                    objective_slot_offset=0, actor_ring=None, lar_prefilled=False, lstm_x=True, slots=None,
+                    objective_prefilled=False):
         """conv encoder -> fc (+ last_action_reward[_objective] columns and the input half of the LSTM gates) for
         rows [row0, row0+nrows) of a path workspace.  `objective_slot_offset` = -1 reproduces trainer.py:300, where the
         bootstrap value is fed the objective of the previous frame's state.  `lstm_x` False: a single time step follows
-        whose lstm_step(fused_x=True) multiplies [x | h] by the whole kernel, so the input half is not hoisted."""
+        whose lstm_step(fused_x=True) multiplies [x | h] by the whole kernel, so the input half is not hoisted.
+        `objective_prefilled`: the environment step has written the objective columns too (a goal-sense maze)."""
         p = self.p
         idx = ws.frame_idx[row0:row0 + nrows]
         F = self.F
@@ -491,7 +493,7 @@ class UnrealModel(object):
         else:
             ar = ring if actor_ring is None else actor_ring     # per-actor state of a sub-range of the ring's actors
             ops.lar_fill(nrows, A, ar.last_action, ar.last_reward, None, xcat, self.xld, clip=clip_lar)
-        if self._objective_size:
+        if self._objective_size and not objective_prefilled:
             ops.objective_fill(ring, nrows, idx, xcat, self.xld, 256 + A + 1, slot_offset=objective_slot_offset)
         # [one-hot last action | last reward | objective]: the one-hot and a clipped reward stay within the kernel's own
         # floor of 1 (|h| < 1); raw rewards / measurement vectors (host-fed actors) are reduced into the slot

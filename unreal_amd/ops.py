@@ -98,7 +98,7 @@ class Ring(object):
     """Device replay ring + per-actor environment state (layout: include/unreal_hip.h)."""
 
     def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False, nav=False, gen=0,
-                 gen_styled=False):
+                 gen_styled=False, sense=0):
         self.B, self.H, self.H1 = B, H, H + 1
         self.objective_size = objective_size
         self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
@@ -132,14 +132,18 @@ class Ring(object):
         self.heading = z(B, dt=torch.int32) if maze_state else None
         # navigation mazes (MazeConfig.nav): [B, 8] records (heading, apple bits lo, hi, goals_total, apples_total, 0, 0, 0)
         # handed to the kernels in place of `heading`, which is then a [B] view of their word 0
-        self.nav = z(B * NAV_RECORD, dt=torch.int32) if maze_state and nav else None
+        # (`sense` = N: a goal-sense maze, DESIGN §7i: words 5..7 are gf, gs, d and every record, a generated maze's too,
+        # ends in the actor's distance field of dist_words(N) words)
+        self.sense_n = int(sense) if maze_state else 0
+        self.nav_words = NAV_RECORD + dist_words(self.sense_n)
+        self.nav = z(B * self.nav_words, dt=torch.int32) if maze_state and (nav or self.sense_n) else None
         if self.nav is not None:
-            self.heading = self.nav.view(B, NAV_RECORD)[:, 0]
+            self.heading = self.nav.view(B, self.nav_words)[:, 0]
         # generated mazes (MazeConfig.generate = N = `gen`): [B, gen_record_words(N)] records (the 8 words above, then the
         # actor's own layout record and apple record, rewritten by every reset), handed to the kernels in place of `heading`
         # (`gen_styled`: a styled config, DESIGN §7h: the record also ends in the actor's style_words(N) nibble words)
         self.gen_n = int(gen) if maze_state else 0
-        self.gen_words = gen_record_words(self.gen_n, bool(gen_styled))
+        self.gen_words = gen_record_words(self.gen_n, bool(gen_styled)) + (dist_words(self.sense_n) if self.gen_n else 0)
         self.gen = z(B * self.gen_words, dt=torch.int32) if self.gen_n else None
         if self.gen is not None:
             self.nav = None
@@ -154,7 +158,14 @@ class Ring(object):
         gen, nav = getattr(self, "gen", None), getattr(self, "nav", None)
         if gen is not None:
             return gen.view(self.B, -1)
-        return nav.view(self.B, NAV_RECORD) if nav is not None else None
+        return nav.view(self.B, -1) if nav is not None else None
+
+    @property
+    def record_words(self):
+        """int32 words of one actor's record (0: the maze keeps none)."""
+        if getattr(self, "gen", None) is not None:
+            return self.gen_words
+        return getattr(self, "nav_words", NAV_RECORD) if getattr(self, "nav", None) is not None else 0
 
     def cur_idx(self, out=None, base_actor=0):
         """Frame index of every actor's current observation (slot count % H1).  `base_actor` = index of this (view's)
@@ -185,7 +196,8 @@ def ring_view(ring, b0, b1):
         t = getattr(ring, name)
         setattr(v, name, t[b0:b1] if t is not None else None)
     nav = getattr(ring, "nav", None)
-    v.nav = nav[b0 * NAV_RECORD:b1 * NAV_RECORD] if nav is not None else None
+    v.sense_n, v.nav_words = getattr(ring, "sense_n", 0), getattr(ring, "nav_words", NAV_RECORD)
+    v.nav = nav[b0 * v.nav_words:b1 * v.nav_words] if nav is not None else None
     v.gen_n, gen = getattr(ring, "gen_n", 0), getattr(ring, "gen", None)
     v.gen_words = getattr(ring, "gen_words", gen_record_words(v.gen_n))
     v.gen = gen[b0 * v.gen_words:b1 * v.gen_words] if gen is not None else None
@@ -194,6 +206,8 @@ def ring_view(ring, b0, b1):
 
 MAZE_TOP_DOWN, MAZE_FIRST_PERSON = 0, 1       # the `view` of a maze (UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON)
 MAZE_FIRST_PERSON_GENERATED = 2               # first person, a generated block (UNREAL_MAZE_FIRST_PERSON_GENERATED)
+# goal-sense blocks: UNREAL_MAZE_FIRST_PERSON_SENSE / UNREAL_MAZE_FIRST_PERSON_GENERATED_SENSE
+MAZE_FIRST_PERSON_SENSE, MAZE_FIRST_PERSON_GENERATED_SENSE = 3, 4
 NAV_RECORD = 8                                # int32 words of a navigation maze's per-actor record (UNREAL_MAZE_NAV_RECORD)
 MAZE_RECORD_HEADER, NAV_APPLE_RECORD = 18, 65  # words of a layout record before its free list; of an apple record
 
@@ -201,6 +215,16 @@ MAZE_RECORD_HEADER, NAV_APPLE_RECORD = 18, 65  # words of a layout record before
 def style_words(N):
     """int32 words of one maze's 4-bit style ids (UNREAL_MAZE_STYLE_WORDS(N))."""
     return (N * N + 7) // 8
+
+
+def dist_words(N):
+    """int32 words of one actor's distance field, 16 bits per cell (UNREAL_MAZE_DIST_WORDS(N)); 0 for N = 0."""
+    return (N * N + 1) // 2 if N else 0
+
+
+def sense_record_words(N):
+    """int32 words of a static goal-sense maze's per-actor record (UNREAL_MAZE_SENSE_RECORD(N))."""
+    return NAV_RECORD + dist_words(N)
 
 
 def gen_record_words(N, styled=False):
@@ -220,22 +244,33 @@ def _maze_args(ring, maze):
     styled = len(maze) > 4 and bool(maze[4])
     _chk(block, "i32", 8, "maze config")
     nav = getattr(ring, "nav", None)
+    # a goal-sense block (views 3, 4) is a first-person / generated block whose records end in the distance field: the
+    # record widths are the ring's (Ring(sense=N)), checked against the block's here
+    sense = view in (MAZE_FIRST_PERSON_SENSE, MAZE_FIRST_PERSON_GENERATED_SENSE)
+    generated = view in (MAZE_FIRST_PERSON_GENERATED, MAZE_FIRST_PERSON_GENERATED_SENSE)
+    static_fp = view in (MAZE_FIRST_PERSON, MAZE_FIRST_PERSON_SENSE)
+    if getattr(ring, "sense_n", 0) != (N if sense else 0):
+        raise ValueError("a goal-sense maze needs a ring with distance fields of its size (Ring(sense=%d)), any other "
+                         "maze a ring without" % N)
     arrays = (("goal", 2 * ring.B), ("layout", ring.B), ("ep_steps", ring.B), ("episode", ring.B))
-    if view == MAZE_FIRST_PERSON_GENERATED:
+    if generated:
         arrays = tuple(a for a in arrays if a[0] != "layout")
-    if view == MAZE_FIRST_PERSON:
-        arrays += (("nav", NAV_RECORD * ring.B),) if nav is not None else (("heading", ring.B),)
-    if view == MAZE_FIRST_PERSON_GENERATED:
-        if getattr(ring, "gen_n", 0) != N or getattr(ring, "gen_words", gen_record_words(N)) != gen_record_words(N, styled):
+    if static_fp:
+        if sense and nav is None:
+            raise ValueError("a goal-sense maze keeps per-actor records (Ring(nav=True, sense=%d))" % N)
+        arrays += (("nav", getattr(ring, "nav_words", NAV_RECORD) * ring.B),) if nav is not None else (("heading", ring.B),)
+    if generated:
+        want = gen_record_words(N, styled) + (dist_words(N) if sense else 0)
+        if getattr(ring, "gen_n", 0) != N or getattr(ring, "gen_words", gen_record_words(N)) != want:
             raise ValueError("a generated maze needs a ring with per-actor records of its size (Ring(gen=%d, gen_styled=%s))"
                              % (N, styled))
-        arrays += (("gen", gen_record_words(N, styled) * ring.B),)
+        arrays += (("gen", ring.gen_words * ring.B),)
     for name, n in arrays:
         _chk(getattr(ring, name), "i32", n, "ring." + name)
-    heading = nav if nav is not None and view == MAZE_FIRST_PERSON else ring.heading
-    if view == MAZE_FIRST_PERSON_GENERATED:
+    heading = nav if nav is not None and static_fp else ring.heading
+    if generated:
         heading = ring.gen
-    layout = None if view == MAZE_FIRST_PERSON_GENERATED else ring.layout      # (a generated block has no layout records)
+    layout = None if generated else ring.layout      # (a generated block has no layout records)
     return (int(view), int(N), ptr(block), int(actor_base), ptr(ring.goal), ptr(layout), ptr(ring.ep_steps),
             ptr(ring.episode), ptr(heading))
 
@@ -295,8 +330,9 @@ def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, act
     """policy_step + maze_rollout_step in one launch: the workgroup that steps an actor computes its pi / V / action first
     (bit-identical to the two launches).  A = 6: a first-person navigation maze with Lab's action set."""
     B = ring.B
-    nav = maze is not None and ((maze[0] == MAZE_FIRST_PERSON and getattr(ring, "nav", None) is not None) or
-                                maze[0] == MAZE_FIRST_PERSON_GENERATED)
+    nav = maze is not None and ((maze[0] in (MAZE_FIRST_PERSON, MAZE_FIRST_PERSON_SENSE) and
+                                 getattr(ring, "nav", None) is not None) or
+                                maze[0] in (MAZE_FIRST_PERSON_GENERATED, MAZE_FIRST_PERSON_GENERATED_SENSE))
     if A != 4 and not (A == 6 and nav):
         raise ValueError("the maze has 4 actions (6: a first-person navigation maze with action_set='lab'); A = %r" % (A,))
     _chk(X, "f32", (B - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A); _chk(bp, "f32", A); _chk(Wv, "f32", 256)
@@ -306,6 +342,24 @@ def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, act
           ptr(pi_out), ptr(v_out), ptr(actions),
           *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
                          lar_ld, lar_col0, A, base_actor), *_maze_args(ring, maze))
+
+
+def maze_objective(ring, next_lar=None, lar_ld=0, lar_col0=0):
+    """The objective vectors of a goal-sense maze: {gf / 32, gs / 32, d / 512} of every actor's record ->
+    the current slot of ring.r_objective and, with `next_lar`, columns [lar_col0, lar_col0 + 3) of its rows (stride
+    lar_ld): the objective columns of the next step's LSTM input."""
+    rec, words = ring.actor_records, ring.record_words
+    if rec is None or not getattr(ring, "sense_n", 0) or ring.objective_size != 3:
+        raise ValueError("maze_objective needs the ring of a goal-sense maze (Ring(objective_size=3, sense=N))")
+    B = ring.B
+    _chk(rec, "i32", B * words, "ring records"); _chk(ring.r_objective, "f32", B * ring.H1 * 3, "ring.r_objective")
+    _chk(ring.count, "i32", B, "ring.count")
+    if next_lar is not None:
+        if lar_col0 < 0 or lar_ld < lar_col0 + 3:
+            raise ValueError("next_lar: lar_ld %d < lar_col0 %d + 3" % (lar_ld, lar_col0))
+        _chk(next_lar, "f32", (B - 1) * lar_ld + lar_col0 + 3, "next_lar")
+    _call("unreal_maze_objective", B, ring.H1, ptr(ring.count), ptr(rec), int(words), ptr(ring.r_objective),
+          ptr(next_lar), int(lar_ld), int(lar_col0))
 
 
 def pixel_change_u8(frames, idx_new, idx_old, denom, out):

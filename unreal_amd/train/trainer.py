@@ -103,6 +103,11 @@ class Trainer(object):
         self.max_global_time_step = max_global_time_step
         self.action_size = Environment.get_action_size(env_type, env_name)
         self.objective_size = Environment.get_objective_size(env_type, env_name)
+        # a goal-sense maze feeds its measurement vector to the LSTM: the network must have its columns
+        net_obj = getattr(global_network, "_objective_size", 0)
+        if env_type == "maze" and net_obj != self.objective_size:
+            raise ValueError("the network's objective_size %d differs from the environment's %d (Environment."
+                             "get_objective_size(%r, %r))" % (net_obj, self.objective_size, env_type, env_name))
         # frame size: the network's image_shape must be the environment's (main.py:196 builds both from the MINOS config)
         self.image_shape = tuple(int(x) for x in Environment.get_image_shape(env_type, env_name))
         net_shape = tuple(getattr(global_network, "image_shape", (84, 84)))
@@ -294,8 +299,10 @@ class Trainer(object):
         B, A, net = self.Bg, self.action_size, self.local_network
         if not prefilled:
             self.ring.cur_idx(out=ws.frame_idx[t * B:(t + 1) * B])
+        # (a goal-sense maze's step has also written the objective columns: no objective_fill launch at t > 0)
         net.encode_rows(self.ring, ws, t * B, B, lar_from_ring=False, save_c1=ws.c1 is not None,
-                        lar_prefilled=prefilled and self.use_lstm, lstm_x=False)
+                        lar_prefilled=prefilled and self.use_lstm, lstm_x=False,
+                        objective_prefilled=prefilled and self.use_lstm and self.env_type == "maze")
         if self.use_lstm:
             net.lstm_step(ws, t, B, fused_x=True)
         feat, ld = net.features(ws, t * B)
@@ -405,6 +412,8 @@ class Trainer(object):
         n_parts = self.rollout_parts_default
         self._split = None
         if self.env_type != "maze" or n_parts < 2 or self.Bg % n_parts or self.Bg < self.ROLLOUT_SPLIT_MIN_ACTORS:
+            return
+        if self.objective_size:                # goal-sense mazes take the lock-step loop
             return
         Bp = self.Bg // n_parts
         streams = [torch.cuda.Stream(device=self.device) for _ in range(n_parts)]
