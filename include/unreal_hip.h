@@ -98,7 +98,20 @@ extern "C" {
  * written); a respawn at the goal keeps it.  Word 6 of the navigation header is progress_reward p: a step's reward is the
  * first-that-applies reward plus p * (d of the cell before the action - d of the cell the move ends in, before any respawn
  * or reset).  A launch of view 3 / 4 on a block without the flag, or of view 1 / 2 on a block with it, writes nothing.
- * unreal_maze_objective turns words 5..7 into the ring's objective vectors. */
+ * unreal_maze_objective turns words 5..7 into the ring's objective vectors.
+ * Foraging (first person, flag 128 in the block's word 2, always with flag 8 and never with flag 64; views 5 and 6;
+ * DESIGN §7j): up to three more kinds of pickup next to the apple, and episodes without a goal.  The block ends, after
+ * everything above, in 16 words: [0] K kinds (0..3)  [1] mode (bit 0: no goal)  [4..6] the rewards of kinds 1..3  [8..10]
+ * r | g << 8 | b << 16 | ends_episode << 24 of kinds 1..3  [12..14] gen_pickups (rooms of a generated maze that hold kind
+ * 1..3, ranked after the gen_apples rooms by the same keys); every other word 0.  Entry k of an apple record, the block's
+ * or a generated actor's, is cell | kind << 16, ascending by cell (kind 0: the apple, with the navigation header's apple
+ * reward and floor colour (40, 255, 40)); bit k of the actor's collected mask is entry k.  A move into the cell of an
+ * active pickup pays its kind's reward (after the goal's, before a hit's) and, for a kind with ends_episode, ends the
+ * episode, also under goal respawn; the floor of an active pickup's cell has its kind's colour.  Words 4..7 of the 8
+ * navigation words are the running totals of kinds 0..3, never zeroed.  Without a goal, goal[] holds (-1, -1), a layout
+ * record's G is -1, and the start is S or free cell number (word 1 of the reset draw) % n_free.  The record widths are
+ * those of views 1 and 2.  A launch of view 5 / 6 on a block without the flag, or of any other view on a block with it,
+ * writes nothing. */
 #define UNREAL_MAZE_NAV_RECORD 8
 #define UNREAL_MAZE_GEN_RECORD(N) (8 + 18 + (N) * (N) + 65)
 #define UNREAL_MAZE_STYLE_WORDS(N) (((N) * (N) + 7) / 8)
@@ -110,6 +123,8 @@ extern "C" {
 #define UNREAL_MAZE_SENSE_RECORD(N) (8 + UNREAL_MAZE_DIST_WORDS(N))
 #define UNREAL_MAZE_FIRST_PERSON_SENSE 3
 #define UNREAL_MAZE_FIRST_PERSON_GENERATED_SENSE 4
+#define UNREAL_MAZE_FIRST_PERSON_FORAGE 5
+#define UNREAL_MAZE_FIRST_PERSON_GENERATED_FORAGE 6
 /* env.reset() of every actor where mask[b] != 0 (mask nullable) */
 int unreal_maze_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward, const int* count,
                       uint8_t* frames, int view, int N, const int* cfg, int actor_base, int* goal, int* layout,

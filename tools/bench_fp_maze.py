@@ -15,10 +15,13 @@
     density 64);
   * goal sense (--sense-only): the step of a goal_sense block next to the step of the same navigation block
     without the option, static and generated; the objective launch on its own; a full-batch reset() of a generated
-    N = 21 maze with and without the option (the difference is the breadth-first search); Trainer.process() on both.
+    N = 21 maze with and without the option (the difference is the breadth-first search); Trainer.process() on both;
+  * foraging (--forage-only): the step of a forage block (three more kinds of pickup, one of them ending the
+    episode) next to the step of the navigation block with the same pickup cells, all apples, static and generated; the
+    two blocks are timed in turn, twice per row, and the whole table is printed --repeat times; Trainer.process() on both.
 
   python tools/bench_fp_maze.py [--launches 200] [--steps 10] [--warmup 3] [--history 100]
-                                [--nav-only | --gen-only | --style-only | --sense-only]
+                                [--nav-only | --gen-only | --style-only | --sense-only | --forage-only [--repeat 2]]
 
 Prints one JSON line per measurement."""
 import argparse
@@ -138,11 +141,64 @@ def main():
     ap.add_argument("--gen-only", action="store_true", help="only the generated-maze rows and their static references")
     ap.add_argument("--style-only", action="store_true", help="only the styled rows and their unstyled references")
     ap.add_argument("--sense-only", action="store_true", help="only the goal-sense rows and their references")
+    ap.add_argument("--forage-only", action="store_true", help="only the forage rows and their navigation references")
+    ap.add_argument("--repeat", type=int, default=2, help="--forage-only: how often the whole table is measured")
     args = ap.parse_args()
     from unreal_amd.environment.environment import Environment
     from unreal_amd.environment.maze_environment import MazeConfig, batched_maze_environment
     kw = dict(random_start=True, random_goal=True, show_goal=True, max_episode_steps=200)
     nav_kw = dict(goal_reward=10, apple_reward=1, hit_reward=0, goal_respawn=True, action_set="lab")
+    if args.forage_only:
+        # lemons at -1, a +5, and a melon at +20 that ends the episode: every fourth pickup cell of the navigation block each
+        kinds = [(-1, (255, 255, 0), False), (5, (0, 255, 255), False), (20, (255, 0, 255), True)]
+        okw = dict(kw, **nav_kw)
+
+        def forage_layout(lay):
+            k, out = 0, []
+            for ch in lay:
+                out.append("ABCD"[k % 4] if ch == "A" else ch)
+                k += ch == "A"
+            return "".join(out)
+        for run in range(args.repeat):
+            for N in (7, 21):   # forage vs the navigation block of the same cells, all 'A': same process, in turn
+                for B in (512, 4096):
+                    for kind in ("static", "generated"):
+                        n = NAV_APPLES[N]
+                        if kind == "static":
+                            lays = layouts(N, apples=n)
+                            cfgs = dict(nav=MazeConfig(lays, view="first_person", **okw),
+                                        forage=MazeConfig([forage_layout(l) for l in lays], view="first_person",
+                                                          pickups=kinds, **okw))
+                        else:
+                            cfgs = dict(nav=MazeConfig(None, view="first_person", generate=N, gen_apples=n, **okw),
+                                        forage=MazeConfig(None, view="first_person", generate=N, gen_apples=n // 4,
+                                                          pickups=kinds, gen_pickups=(n // 4,) * 3, **okw))
+                        envs = dict((k, batched_maze_environment(B, 3, DEV, config=c, seed=1)) for k, c in cfgs.items())
+                        us = dict(nav=[], forage=[])
+                        for _ in range(2):
+                            for what in ("nav", "forage"):
+                                us[what].append(kernel_ms(envs[what], B, args.launches, A=6) * 1e3)
+                        del envs
+                        nav_us, forage_us = sum(us["nav"]) / 2, sum(us["forage"]) / 2
+                        print(json.dumps(dict(what="forage_step_kernel", run=run, kind=kind, N=N, B=B,
+                                              nav_us=round(nav_us, 2), forage_us=round(forage_us, 2),
+                                              ratio=round(forage_us / nav_us, 3),
+                                              passes=dict((k, [round(v, 2) for v in vs]) for k, vs in us.items()))),
+                              flush=True)
+        if not args.skip_trainer:
+            lays = layouts(7, apples=NAV_APPLES[7])
+            for what in ("nav", "forage"):
+                name = "bench_forage_" + what
+                if what == "nav":
+                    Environment.register_maze_config(name, lays, view="first_person", **okw)
+                else:
+                    Environment.register_maze_config(name, [forage_layout(l) for l in lays], view="first_person",
+                                                     pickups=kinds, **okw)
+                ms, wall = trainer_ms(name, 4096, args.history, args.steps, args.warmup)
+                print(json.dumps(dict(what="trainer_process", view="first_person_nav", forage=what == "forage", A=6,
+                                      N=7, B=4096, history=args.history, ms_per_call=round(ms, 3),
+                                      wall_ms_per_call=round(wall, 3))), flush=True)
+        return
     if args.sense_only:
         for N in (7, 21):       # goal sense vs the same navigation block without it: same layouts, same process
             for B in (512, 4096):

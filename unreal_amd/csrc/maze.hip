@@ -42,6 +42,11 @@
 // kFirstPersonGenSense), so the kernels of every other block are what they were.  unreal_maze_objective turns the three
 // record words into the ring's objective vector.
 //
+// Forage blocks (flag kMazeForage) have up to three more kinds of pickup next to the apple, each with a reward,
+// a floor colour and an ends-the-episode bit, and may have no goal at all.  An apple entry carries its kind, words 5..7 of
+// the actor record count the kinds, and the step resolves what it collects before it decides the terminal.  They run in
+// kernels of their own (views kFirstPersonForage / kFirstPersonGenForage); every other kernel is what it was.
+//
 // One workgroup (256 threads) per actor.  The step renders s_{t+1} into LDS (lanes 0..83: one column's DDA each, over
 // the layout's wall bits in LDS; then every thread fills whole frame-row dwords), streams it to the ring slot with 16 B
 // per lane, turns the LDS image into |new - old| bytes against the stored frame (read at kernel entry, so its latency
@@ -55,7 +60,9 @@ namespace {
 
 // UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON / UNREAL_MAZE_FIRST_PERSON_GENERATED
 // UNREAL_MAZE_FIRST_PERSON_SENSE / UNREAL_MAZE_FIRST_PERSON_GENERATED_SENSE
+// UNREAL_MAZE_FIRST_PERSON_FORAGE / UNREAL_MAZE_FIRST_PERSON_GENERATED_FORAGE
 constexpr int kTopDown = 0, kFirstPerson = 1, kFirstPersonGen = 2, kFirstPersonSense = 3, kFirstPersonGenSense = 4;
+constexpr int kFirstPersonForage = 5, kFirstPersonGenForage = 6;
 
 // The reference's map as a configuration block (layout: maze_common.h).
 constexpr const char* kMap =
@@ -249,8 +256,8 @@ __global__ __launch_bounds__(256) void maze_step_kernel(MazeArgs p) {
   const int* cfg = p.cfg;                      // null: the reference map (kDefaultMaze)
   // (uniform) the block's grid size must be the one this kernel was built for: with another N the cell arithmetic would
   // address outside the frame, so nothing is written (documented with the maze entries in unreal_hip.h)
-  // (a generated block, which has no layout record and is first person only, counts as another size)
-  if ((cfg ? cfg[0] | (cfg[2] & kMazeGen) << 8 : 7) != N) return;
+  // (a generated block, which has no layout record and is first person only, counts as another size; so does a forage block)
+  if ((cfg ? cfg[0] | (cfg[2] & (kMazeGen | kMazeForage)) << 8 : 7) != N) return;
   __shared__ uint4 wall_img[FRAME_BYTES / 16];
   // the workgroup's actors' scalar state, fetched by one thread per actor while the wall image is built: read inside the
   // per-actor loop, each actor would start with two dependent global round trips (state, then the previous slot's terminal
@@ -373,7 +380,7 @@ template <int N>
 __global__ __launch_bounds__(256) void maze_reset_kernel(MazeArgs p) {
   const int* cfg = p.cfg;
   // (a generated block, which has no layout record and is first person only, counts as another size)
-  if ((cfg ? cfg[0] | (cfg[2] & kMazeGen) << 8 : 7) != N) return;
+  if ((cfg ? cfg[0] | (cfg[2] & (kMazeGen | kMazeForage)) << 8 : 7) != N) return;
   __shared__ uint4 wall_img[FRAME_BYTES / 16];
   __shared__ int s_lay[kActorsPerGroup], s_epi[kActorsPerGroup], s_rgoal[kActorsPerGroup], s_rstart[kActorsPerGroup];
   if (threadIdx.x < kActorsPerGroup) {
@@ -453,6 +460,15 @@ struct FpLds {
   uint32_t style_col[kStyleSlots];              // styled: r | g << 8 | b << 16 | pattern << 24 of style k at k - 1
 };
 
+// Forage blocks: the kind of every marked cell as two more bit planes next to FpLds<N>::apples, the kinds'
+// floor colours, and what the step collects.  LDS of the forage kernels only.
+template <int N>
+struct ForageLds {
+  uint32_t kind0[FpLds<N>::NA], kind1[FpLds<N>::NA];   // bits 0 and 1 of the kind of the pickup in cell c
+  uint32_t colour[4];                                  // floor colour of kind k (0: kAppleFloor)
+  int collect;                                         // entry index | kind << 8 of the pickup the step collects (-1: none)
+};
+
 template <int N>
 __device__ __forceinline__ void fp_load_walls(FpLds<N>& s, const int* rec) {
   if (threadIdx.x < FpLds<N>::NW)
@@ -475,6 +491,23 @@ __device__ __forceinline__ void fp_mark_apple(FpLds<N>& s, int k, int n, int cel
   if (k < n && !((collected >> k) & 1) && cell != goal) atomicOr(&s.apples[cell >> 5], 1u << (cell & 31));
 }
 
+// Forage: fp_mark_apple for entry k of kind `kind`; the kind planes must be zero as the bitmap is.
+template <int N>
+__device__ __forceinline__ void fp_mark_pickup(FpLds<N>& s, ForageLds<N>& fs, int k, int n, int cell, int kind,
+                                               uint64_t collected, int goal) {
+  if (k < n && !((collected >> k) & 1) && cell != goal) {
+    atomicOr(&s.apples[cell >> 5], 1u << (cell & 31));
+    if (kind & 1) atomicOr(&fs.kind0[cell >> 5], 1u << (cell & 31));
+    if (kind & 2) atomicOr(&fs.kind1[cell >> 5], 1u << (cell & 31));
+  }
+}
+
+// Forage: zeroes the bitmap and the kind planes (a barrier must follow before anything is marked).
+template <int N>
+__device__ __forceinline__ void fp_clear_pickups(FpLds<N>& s, ForageLds<N>& fs) {
+  if (threadIdx.x < FpLds<N>::NA) { s.apples[threadIdx.x] = 0u; fs.kind0[threadIdx.x] = 0u; fs.kind1[threadIdx.x] = 0u; }
+}
+
 // Renders the view from cell (ex, ey) along heading h into s.img.  Call with the whole workgroup after the wall bits (and
 // with NAV, the apple bitmap's marks; with `styled`, the style ids and words) are issued to LDS and every thread is done
 // reading s.img; returns after a barrier.
@@ -484,8 +517,10 @@ __device__ __forceinline__ void fp_mark_apple(FpLds<N>& s, int k, int n, int cel
 // world coordinate c along the face: at forward crossing k, frac(c) = frac((sigma q (2k+1) + W) / 2W) with sigma = rx + ry;
 // at side crossing m, frac((sigma (2m+1) W + |q|) / 2|q|) with sigma = dx + dy.  A channel is halved where bit u of the
 // style's pattern is set, then scaled by 5/8 on a face crossed along y.
-template <int N, bool NAV>
-__device__ __forceinline__ void fp_render(FpLds<N>& s, int ex, int ey, int h, int gx, int gy, bool show_goal, bool styled) {
+// `fs` (FORAGE; else null): the floor of a marked cell takes its kind's colour.
+template <int N, bool NAV, bool FORAGE = false>
+__device__ __forceinline__ void fp_render(FpLds<N>& s, int ex, int ey, int h, int gx, int gy, bool show_goal, bool styled,
+                                          const ForageLds<N>* fs = nullptr) {
   const int dx = (h == 0) - (h == 2), dy = (h == 1) - (h == 3);
   const int rx = -dy, ry = dx;
   if (threadIdx.x < FRAME_W) {           // one column's DDA per lane: at most 2N cells before the ray leaves the map
@@ -562,7 +597,14 @@ __device__ __forceinline__ void fp_render(FpLds<N>& s, int ex, int ey, int h, in
           const int cx = ex + ahead * dx + side * rx, cy = ey + ahead * dy + side * ry;
           if ((unsigned)cx < (unsigned)N && (unsigned)cy < (unsigned)N) {
             const int c = cy * N + cx;
-            if ((s.apples[c >> 5] >> (c & 31)) & 1u) return kAppleFloor;
+            if ((s.apples[c >> 5] >> (c & 31)) & 1u) {
+              if constexpr (FORAGE) {
+                const uint32_t kind = ((fs->kind0[c >> 5] >> (c & 31)) & 1u) | (((fs->kind1[c >> 5] >> (c & 31)) & 1u) << 1);
+                return fs->colour[kind];
+              } else {
+                return kAppleFloor;
+              }
+            }
           }
         }
         return kFloor;
@@ -653,13 +695,24 @@ __device__ __forceinline__ uint32_t gen_weight(uint64_t seed, int g, int ep, uin
 // g.  Call with the whole workgroup; s.img is overwritten.  Begins and ends with a barrier: on return the record, the wall
 // bits in LDS and nothing else of `s` have changed, and every thread may read them.  `ids` (a styled block; else null):
 // the actor's nibble words, drawn once the walls are final and written there and to s.styles.
+// rank past the rooms of forage kind k + 1, which begin at rank `from` (at most one pickup per room, kMaxApples in all)
 template <int N>
+__device__ __forceinline__ int gen_pickup_end(const int* cfg, int from, int k) {
+  return min(from + max(maze_forage_ext(cfg)[kForageGen + k], 0), min(kMaxApples, GenLds<N>::RR));
+}
+
+// FORAGE: the rooms ranked after the `apples` first hold kind 1, 2, 3 pickups (the forage section's
+// gen_pickups), and an apple entry is cell | kind << 16.
+template <int N, bool FORAGE = false>
 __device__ __forceinline__ void gen_maze(FpLds<N>& s, const int* cfg, int g, int ep, int* rec, int* ids) {
   using G = GenLds<N>;
   constexpr int R = G::R, E = G::E, RR = G::RR, NN = N * N, EH = R * (R - 1);
   G& t = *reinterpret_cast<G*>(s.img);
   const int* ext = maze_nav_ext(cfg);
-  const int loops = min(max(ext[4], 0), E - (RR - 1)), n_apples = min(max(ext[5], 0), min(kMaxApples, RR));
+  // FORAGE: ranks below n_kind0 / end1 / end2 / n_apples are pickups of kind 0 / 1 / 2 / 3
+  const int loops = min(max(ext[4], 0), E - (RR - 1)), n_kind0 = min(max(ext[5], 0), min(kMaxApples, RR));
+  const int end1 = FORAGE ? gen_pickup_end<N>(cfg, n_kind0, 0) : n_kind0, end2 = FORAGE ? gen_pickup_end<N>(cfg, end1, 1) : n_kind0;
+  const int n_apples = FORAGE ? gen_pickup_end<N>(cfg, end2, 2) : n_kind0;
   const uint64_t seed = (uint64_t)(uint32_t)cfg[4] | ((uint64_t)(uint32_t)cfg[5] << 32);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   __syncthreads();                     // every thread is done with s.img
@@ -693,12 +746,14 @@ __device__ __forceinline__ void gen_maze(FpLds<N>& s, const int* cfg, int g, int
     t.sorted[rank] = packed;
   }
   bool apple = false;
+  [[maybe_unused]] int kind = 0;
   if (tid < RR) {
     atomicAnd(&t.walls[room_cell >> 5], ~(1u << (room_cell & 31)));
     if (n_apples > 0) {
       int rank = 0;
       for (int j = 0; j < RR; ++j) rank += t.akey[j] < akey ? 1 : 0;
       apple = rank < n_apples;
+      if constexpr (FORAGE) kind = (rank >= n_kind0 ? 1 : 0) + (rank >= end1 ? 1 : 0) + (rank >= end2 ? 1 : 0);
     }
   }
   const unsigned long long aballot = __ballot(apple);
@@ -765,7 +820,11 @@ __device__ __forceinline__ void gen_maze(FpLds<N>& s, const int* cfg, int g, int
   if (tid < kRecHdr) rec[tid] = tid < 14 ? (int)t.walls[tid] : -1;           // (word 16, n_free, is written below)
   int* arec = rec + kRecHdr + NN;
   if (tid == 0) arec[0] = n_apples;
-  if (apple) arec[1 + (wave ? t.wave_apples : 0) + apple_idx] = room_cell;     // ascending: room order is cell order
+  if constexpr (FORAGE) {
+    if (apple) arec[1 + (wave ? t.wave_apples : 0) + apple_idx] = room_cell | kind << 16;
+  } else {
+    if (apple) arec[1 + (wave ? t.wave_apples : 0) + apple_idx] = room_cell;     // ascending: room order is cell order
+  }
   // the free list, ascending: a ballot / popcount prefix sum over two passes of 256 cells
   bool fr[2];
   int pre[2];
@@ -862,9 +921,12 @@ __device__ __forceinline__ int fp_record_words(bool styled) {
 // record behind `heading`, the block's rewards and action set, apples, and respawn at the goal.  GEN: a generated block
 // (kMazeGen): the layout and apple records are the actor's own, rewritten before the reset draw.  SENSE (with
 // NAV): a goal-sense block (kMazeSense): the record ends in the distance field, words 5..7 are kept.
-template <int N, bool NAV, bool GEN, bool SENSE = false>
-__device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
+// FORAGE (with NAV, never SENSE): a forage block (kMazeForage): pickup kinds in `fs`, words 5..7 count them;
+// the collection is resolved before the terminal, which an ending kind sets; without a goal the goal cell is (-1, -1).
+template <int N, bool NAV, bool GEN, bool SENSE = false, bool FORAGE = false>
+__device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s, ForageLds<N>* fs = nullptr) {
   static_assert(NAV || !SENSE, "a goal-sense block is a navigation block");
+  static_assert(!FORAGE || (NAV && !SENSE), "a forage block is a navigation block without goal sense");
   const int* cfg = p.cfg;
   const int b = blockIdx.x;
   const int H1 = p.H1;
@@ -876,12 +938,19 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
   const int* ext = NAV ? maze_nav_ext(cfg) : nullptr;
   const int* arec = NAV ? (GEN ? rec + kRecHdr + N * N : ext + kNavHdr + lay * kNavRec) : nullptr;
   const int mode = NAV ? ext[3] : 0;
+  const int* fsec = FORAGE ? maze_forage_ext(cfg) : nullptr;
+  const bool no_goal = FORAGE && (fsec[1] & kForageNoGoal);
   fp_load_walls<N>(s, rec);
   if (styled) {
     const int* sext = maze_style_ext(cfg);
     fp_load_styles<N>(s, sext, GEN ? actor + gen_actor_words(N) : sext + kStyleHdr + kStyleSlots + lay * maze_style_words(N));
   }
-  if (NAV) {
+  if constexpr (FORAGE) {
+    fp_clear_pickups<N>(s, *fs);
+    if (threadIdx.x == 0) fs->collect = -1;
+    const int t = threadIdx.x - 192;      // wave 3: the kinds' colours
+    if (t >= 0 && t < 4) fs->colour[t] = t == 0 ? kAppleFloor : (uint32_t)fsec[kForageColour + t - 1] & 0xFFFFFFu;
+  } else if (NAV) {
     if (threadIdx.x < FpLds<N>::NA) s.apples[threadIdx.x] = 0u;
     if (threadIdx.x == 0) s.collect = -1;
   }
@@ -926,12 +995,17 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
   const float ep = p.track_score ? p.episode_reward[b] : 0.f;
   uint64_t bits = 0;
   int goals = 0, apples = 0, n_apples = 0, my_apple = -1;
+  int my_kind = 0, kind1 = 0, kind2 = 0, kind3 = 0;      // FORAGE: the kind of this thread's entry; the totals of kinds 1..3
   if (NAV) {
     bits = (uint64_t)(uint32_t)hrec[1] | ((uint64_t)(uint32_t)hrec[2] << 32);
     goals = hrec[3];
     apples = hrec[4];
     n_apples = min(arec[0], kMaxApples);
     if (threadIdx.x < n_apples) my_apple = arec[1 + threadIdx.x];
+    if constexpr (FORAGE) {
+      kind1 = hrec[5]; kind2 = hrec[6]; kind3 = hrec[7];
+      if (threadIdx.x < n_apples) { my_kind = (my_apple >> 16) & 3; my_apple &= 0xFFFF; }
+    }
   }
   __syncthreads();                       // wall bits, the drawn action (and the zeroed apple bitmap) are in LDS
   const int a = p.pol_x ? s.act : p.actions[b];
@@ -966,10 +1040,22 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
     d_before = maze_dist(field, y * N + x);
     d_now = d_after = moved ? maze_dist(field, ny * N + nx) : d_before;
   }
-  const bool at_goal = nx == gx && ny == gy;
+  const bool at_goal = nx == gx && ny == gy;           // (no goal: (-1, -1), no cell)
   const int max_steps = cfg[3];
   const bool timeout = max_steps > 0 && steps >= max_steps;
-  const bool terminal = (NAV && (mode & kNavRespawn)) ? timeout : (at_goal || timeout);
+  // forage: what the move collects, known to every thread before the terminal is (an ending kind ends the episode)
+  int fcol = -1, fkind = 0;
+  bool ends = false;
+  if constexpr (FORAGE) {
+    if (moved && my_apple == ny * N + nx && my_apple != gy * N + gx && !((bits >> threadIdx.x) & 1))
+      fs->collect = threadIdx.x | my_kind << 8;
+    __syncthreads();
+    fcol = fs->collect;
+    fkind = fcol >= 0 ? (fcol >> 8) & 3 : 0;
+    ends = fkind > 0 && (((uint32_t)fsec[kForageColour + max(fkind, 1) - 1] >> 24) & 1u);
+  }
+  const bool goal_or_timeout = (NAV && (mode & kNavRespawn)) ? timeout : (at_goal || timeout);
+  const bool terminal = FORAGE ? (goal_or_timeout || ends) : goal_or_timeout;
   const RingStep ring = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
   const bool reset = ring.reset;
   const bool show_goal = cfg[2] & kMazeShowGoal;
@@ -985,13 +1071,18 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
       if constexpr (SENSE) d_now = maze_dist(field, st);     // (the goal stays: the field does too)
     }
     // the active apples of the running episode; the apple of the cell moved into (never the goal's) is collected
-    fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, bits, gy * N + gx);
-    if (moved && my_apple == ny * N + nx && my_apple != gy * N + gx && !((bits >> threadIdx.x) & 1))
-      s.collect = threadIdx.x;
+    if constexpr (FORAGE) {
+      if (fcol >= 0) bits |= 1ull << (fcol & 63);         // s_{t+1} is rendered with the pickup just collected gone
+      fp_mark_pickup<N>(s, *fs, threadIdx.x, n_apples, my_apple, my_kind, bits, gy * N + gx);
+    } else {
+      fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, bits, gy * N + gx);
+      if (moved && my_apple == ny * N + nx && my_apple != gy * N + gx && !((bits >> threadIdx.x) & 1))
+        s.collect = threadIdx.x;
+    }
   }
 
   // s_{t+1}: stored unless the episode restarts; then its bytes become |s_{t+1} - s_t| in place
-  fp_render<N, NAV>(s, ex, ey, eh, gx, gy, show_goal, styled);
+  fp_render<N, NAV, FORAGE>(s, ex, ey, eh, gx, gy, show_goal, styled, fs);
 #pragma unroll
   for (int k = 0; k < kChunksPerThread; ++k) {
     const int c = threadIdx.x + 256 * k;
@@ -1002,7 +1093,14 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
     }
   }
   float reward = at_goal ? 1.f : (hit ? -1.f : 0.f);
-  if (NAV) {
+  if constexpr (FORAGE) {
+    const int pay = fkind == 0 ? ext[1] : fsec[kForageReward + fkind - 1];
+    reward = at_goal ? (float)ext[0] : fcol >= 0 ? (float)pay : hit ? (float)ext[2] : 0.f;
+    if (fcol >= 0) {                     // (its bit is set above)
+      apples += fkind == 0; kind1 += fkind == 1; kind2 += fkind == 2; kind3 += fkind == 3;
+    }
+    if (reset) fp_clear_pickups<N>(s, *fs);        // (read by nobody until the reset render)
+  } else if (NAV) {
     const int col = s.collect;           // (written before the render's barriers)
     reward = at_goal ? (float)ext[0] : col >= 0 ? (float)ext[1] : hit ? (float)ext[2] : 0.f;
     if constexpr (SENSE) reward += (float)(ext[kNavProgressWord] * (d_before - d_after));
@@ -1028,22 +1126,32 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
   if (reset) {                           // (uniform) the next episode's first observation goes into the slot instead
     int rg, rs;
     if constexpr (GEN) {                 // the next episode's maze, before its reset draw and its first view
-      gen_maze<N>(s, cfg, p.actor_base + b, epi + 1, actor + kNavActorWords, styled ? actor + gen_actor_words(N) : nullptr);
+      gen_maze<N, FORAGE>(s, cfg, p.actor_base + b, epi + 1, actor + kNavActorWords,
+                          styled ? actor + gen_actor_words(N) : nullptr);
       if (NAV) {
         n_apples = min(arec[0], kMaxApples);
         my_apple = threadIdx.x < n_apples ? arec[1 + threadIdx.x] : -1;
+        if constexpr (FORAGE) {
+          my_kind = threadIdx.x < n_apples ? (my_apple >> 16) & 3 : 0;
+          my_apple = threadIdx.x < n_apples ? my_apple & 0xFFFF : -1;
+        }
       }
     }
-    maze_reset_cells(cfg, rec, p.actor_base + b, epi + 1, rg, rs);
+    if constexpr (FORAGE) maze_forage_reset_cells(cfg, rec, no_goal, p.actor_base + b, epi + 1, rg, rs);
+    else maze_reset_cells(cfg, rec, p.actor_base + b, epi + 1, rg, rs);
     rx = rs % N; ry = rs / N; rgx = rg % N; rgy = rg / N;
+    if (FORAGE && no_goal) rgx = rgy = -1;
     rh = fp_reset_heading(cfg, p.actor_base + b, epi + 1);
     if constexpr (SENSE) d_now = maze_bfs<N>(s, rg, rs, field);      // the new episode's field (its barrier: as the render's)
-    if (NAV) {                           // every apple is back
+    if constexpr (FORAGE) {              // every pickup is back
+      bits = 0;
+      fp_mark_pickup<N>(s, *fs, threadIdx.x, n_apples, my_apple, my_kind, 0, rg);
+    } else if (NAV) {                    // every apple is back
       bits = 0;
       fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, 0, rg);
     }
     // (static blocks: the render's first barrier separates the difference's readers from its writers)
-    fp_render<N, NAV>(s, rx, ry, rh, rgx, rgy, show_goal, styled);
+    fp_render<N, NAV, FORAGE>(s, rx, ry, rh, rgx, rgy, show_goal, styled, fs);
     fp_store(dst, s.img);
   }
 
@@ -1058,6 +1166,7 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s) {
       hrec[3] = goals;
       hrec[4] = apples;
     }
+    if constexpr (FORAGE) { hrec[5] = kind1; hrec[6] = kind2; hrec[7] = kind3; }
     if constexpr (SENSE) {               // the state the slot now shows: goal ahead, goal to the right, path distance
       const int fx = (rh == 0) - (rh == 2), fy = (rh == 1) - (rh == 3);
       hrec[5] = (rgx - rx) * fx + (rgy - ry) * fy;
@@ -1077,7 +1186,9 @@ __device__ __forceinline__ void fp_step_entry(const MazeArgs& p) {
   const int* cfg = p.cfg;
   // (uniform) a block of another grid size, or a generated block in a static kernel (and the reverse): nothing is written
   // (nor for a goal-sense block in another kernel than its own, whose records have another size)
-  if (cfg[0] != N || (bool)(cfg[2] & kMazeGen) != GEN || (bool)(cfg[2] & kMazeSense) != SENSE) return;
+  // (nor for a forage block, which has kernels of its own too)
+  if (cfg[0] != N || (bool)(cfg[2] & kMazeGen) != GEN || (cfg[2] & (kMazeSense | kMazeForage)) != (SENSE ? kMazeSense : 0))
+    return;
   __shared__ FpLds<N> s;
   const bool nav = cfg[2] & kMazeNav;
   // (uniform) a fused policy step whose A is not the block's action count: nothing is written either
@@ -1102,8 +1213,27 @@ __global__ __launch_bounds__(256) void maze_fp_gen_step_kernel(MazeArgs p) { fp_
 template <int N, bool GEN>
 __global__ __launch_bounds__(256) void maze_fp_sense_step_kernel(MazeArgs p) { fp_step_entry<N, GEN, true>(p); }
 
-template <int N, bool NAV, bool GEN, bool SENSE = false>
-__device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
+// this N, this kind of block: a forage block is a navigation block, generated or not, and never a goal-sense block
+template <int N, bool GEN>
+__device__ __forceinline__ bool fp_forage_block(const int* cfg) {
+  constexpr int kKind = kMazeGen | kMazeSense | kMazeNav | kMazeForage;
+  return cfg[0] == N && (cfg[2] & kKind) == ((GEN ? kMazeGen : 0) | kMazeNav | kMazeForage);
+}
+
+// the steps of forage blocks (views kFirstPersonForage / kFirstPersonGenForage)
+template <int N, bool GEN>
+__global__ __launch_bounds__(256) void maze_fp_forage_step_kernel(MazeArgs p) {
+  const int* cfg = p.cfg;
+  if (!fp_forage_block<N, GEN>(cfg)) return;           // (uniform) as in fp_step_entry: nothing is written
+  if (p.pol_x && p.A != ((maze_nav_ext(cfg)[3] & kNavLabActions) ? 6 : 4)) return;
+  __shared__ FpLds<N> s;
+  __shared__ ForageLds<N> fs;
+  fp_step<N, true, GEN, false, true>(p, s, &fs);
+}
+
+template <int N, bool NAV, bool GEN, bool SENSE = false, bool FORAGE = false>
+__device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s, ForageLds<N>* fs = nullptr) {
+  static_assert(!FORAGE || (NAV && !SENSE), "a forage block is a navigation block without goal sense");
   const int* cfg = p.cfg;
   const int b = blockIdx.x;
   const bool styled = cfg[2] & kMazeStyled;
@@ -1117,24 +1247,37 @@ __device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
     fp_load_styles<N>(s, sext, GEN ? nullptr : sext + kStyleHdr + kStyleSlots + lay * maze_style_words(N));
   }
   const int g = p.actor_base + b, epi = p.episode[b];
-  if constexpr (GEN) gen_maze<N>(s, cfg, g, epi + 1, actor + kNavActorWords, styled ? actor + gen_actor_words(N) : nullptr);
+  if constexpr (GEN)
+    gen_maze<N, FORAGE>(s, cfg, g, epi + 1, actor + kNavActorWords, styled ? actor + gen_actor_words(N) : nullptr);
   int gc, sc;
-  maze_reset_cells(cfg, rec, g, epi + 1, gc, sc);
+  const int* fsec = FORAGE ? maze_forage_ext(cfg) : nullptr;
+  const bool no_goal = FORAGE && (fsec[1] & kForageNoGoal);
+  if constexpr (FORAGE) maze_forage_reset_cells(cfg, rec, no_goal, g, epi + 1, gc, sc);
+  else maze_reset_cells(cfg, rec, g, epi + 1, gc, sc);
+  const int gx = no_goal ? -1 : gc % N, gy = no_goal ? -1 : gc / N;
   const int h = fp_reset_heading(cfg, g, epi + 1);
   const int slot = p.count[b] % p.H1;
   int* const hrec = GEN ? actor : p.heading + (NAV ? (size_t)rw * b : b);
   int d_start = 0;
   if constexpr (SENSE) d_start = maze_bfs<N>(s, gc, sc, hrec + rw - maze_dist_words(N));
-  int n_apples = 0, my_apple = -1;
+  int n_apples = 0, my_apple = -1, my_kind = 0;
   if (NAV) {
     const int* arec = GEN ? rec + kRecHdr + N * N : maze_nav_ext(cfg) + kNavHdr + lay * kNavRec;
     n_apples = min(arec[0], kMaxApples);
     if (threadIdx.x < n_apples) my_apple = arec[1 + threadIdx.x];
-    if (threadIdx.x < FpLds<N>::NA) s.apples[threadIdx.x] = 0u;
+    if constexpr (FORAGE) {
+      if (threadIdx.x < n_apples) { my_kind = (my_apple >> 16) & 3; my_apple &= 0xFFFF; }
+      fp_clear_pickups<N>(s, *fs);
+      const int t = threadIdx.x - 192;
+      if (t >= 0 && t < 4) fs->colour[t] = t == 0 ? kAppleFloor : (uint32_t)fsec[kForageColour + t - 1] & 0xFFFFFFu;
+    } else {
+      if (threadIdx.x < FpLds<N>::NA) s.apples[threadIdx.x] = 0u;
+    }
   }
   __syncthreads();
-  if (NAV) fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, 0, gc);
-  fp_render<N, NAV>(s, sc % N, sc / N, h, gc % N, gc / N, cfg[2] & kMazeShowGoal, styled);
+  if constexpr (FORAGE) fp_mark_pickup<N>(s, *fs, threadIdx.x, n_apples, my_apple, my_kind, 0, gc);
+  else if (NAV) fp_mark_apple<N>(s, threadIdx.x, n_apples, my_apple, 0, gc);
+  fp_render<N, NAV, FORAGE>(s, sc % N, sc / N, h, gx, gy, cfg[2] & kMazeShowGoal, styled, fs);
   fp_store(p.frames + ((size_t)b * p.H1 + slot) * FRAME_BYTES, s.img);
   if (threadIdx.x == 0) {
     p.pos[2 * b] = sc % N;
@@ -1147,8 +1290,8 @@ __device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
       hrec[6] = ox * -fy + oy * fx;
       hrec[7] = d_start;
     }
-    p.goal[2 * b] = gc % N;
-    p.goal[2 * b + 1] = gc / N;
+    p.goal[2 * b] = gx;
+    p.goal[2 * b + 1] = gy;
     p.ep_steps[b] = 0;
     p.episode[b] = epi + 1;
     p.last_action[b] = 0;
@@ -1159,7 +1302,7 @@ __device__ __forceinline__ void fp_reset(const MazeArgs& p, FpLds<N>& s) {
 template <int N>
 __global__ __launch_bounds__(256) void maze_fp_reset_kernel(MazeArgs p) {
   const int* cfg = p.cfg;
-  if ((cfg[0] | (cfg[2] & (kMazeGen | kMazeSense)) << 8) != N) return;               // as in fp_step_entry
+  if ((cfg[0] | (cfg[2] & (kMazeGen | kMazeSense | kMazeForage)) << 8) != N) return;               // as in fp_step_entry
   const int b = blockIdx.x;
   if (p.mask && !p.mask[b]) return;
   __shared__ FpLds<N> s;
@@ -1170,7 +1313,7 @@ __global__ __launch_bounds__(256) void maze_fp_reset_kernel(MazeArgs p) {
 template <int N>
 __global__ __launch_bounds__(256) void maze_fp_gen_reset_kernel(MazeArgs p) {
   const int* cfg = p.cfg;
-  if ((cfg[0] | (cfg[2] & (kMazeGen | kMazeSense)) << 8) != (N | kMazeGen << 8)) return;
+  if ((cfg[0] | (cfg[2] & (kMazeGen | kMazeSense | kMazeForage)) << 8) != (N | kMazeGen << 8)) return;
   const int b = blockIdx.x;
   if (p.mask && !p.mask[b]) return;
   __shared__ FpLds<N> s;
@@ -1181,12 +1324,22 @@ __global__ __launch_bounds__(256) void maze_fp_gen_reset_kernel(MazeArgs p) {
 template <int N, bool GEN>
 __global__ __launch_bounds__(256) void maze_fp_sense_reset_kernel(MazeArgs p) {
   const int* cfg = p.cfg;
-  constexpr int kKind = kMazeGen | kMazeSense | kMazeNav;             // as in fp_step_entry: this N, this kind of block
+  constexpr int kKind = kMazeGen | kMazeSense | kMazeNav | kMazeForage;             // as in fp_step_entry: this N, this kind of block
   if ((cfg[0] | (cfg[2] & kKind) << 8) != (N | ((GEN ? kMazeGen : 0) | kMazeSense | kMazeNav) << 8)) return;
   const int b = blockIdx.x;
   if (p.mask && !p.mask[b]) return;
   __shared__ FpLds<N> s;
   fp_reset<N, true, GEN, true>(p, s);
+}
+
+template <int N, bool GEN>
+__global__ __launch_bounds__(256) void maze_fp_forage_reset_kernel(MazeArgs p) {
+  if (!fp_forage_block<N, GEN>(p.cfg)) return;
+  const int b = blockIdx.x;
+  if (p.mask && !p.mask[b]) return;
+  __shared__ FpLds<N> s;
+  __shared__ ForageLds<N> fs;
+  fp_reset<N, true, GEN, false, true>(p, s, &fs);
 }
 
 // unreal_maze_objective: one thread per actor
@@ -1215,8 +1368,8 @@ enum MazeEntry { kReset, kStep, kRollout, kPolicy };
 bool maze_args_ok(MazeEntry e, const MazeArgs& p, int view, int N) {
   if (p.B <= 0 || p.H1 < 2 || !p.pos || !p.last_action || !p.last_reward || !p.count || !p.frames) return false;
   if ((uintptr_t)p.frames & 15) return false;
-  if (view < kTopDown || view > kFirstPersonGenSense) return false;
-  const bool gen = view == kFirstPersonGen || view == kFirstPersonGenSense;
+  if (view < kTopDown || view > kFirstPersonGenForage) return false;
+  const bool gen = view == kFirstPersonGen || view == kFirstPersonGenSense || view == kFirstPersonGenForage;
   if (!p.cfg) {
     if (view != kTopDown || N != 7) return false;          // the reference's map
   } else if (!(N == 7 || N == 12 || N == 14 || N == 21) || p.actor_base < 0 || !p.goal || !p.ep_steps || !p.episode) {
@@ -1242,7 +1395,13 @@ bool maze_args_ok(MazeEntry e, const MazeArgs& p, int view, int N) {
 
 template <int N>
 void maze_launch_n(bool reset, int view, const MazeArgs& p, hipStream_t s) {
-  if (view == kFirstPersonSense) {
+  if (view == kFirstPersonForage) {
+    if (reset) hipLaunchKernelGGL((maze_fp_forage_reset_kernel<N, false>), dim3(p.B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((maze_fp_forage_step_kernel<N, false>), dim3(p.B), dim3(256), 0, s, p);
+  } else if (view == kFirstPersonGenForage) {
+    if (reset) hipLaunchKernelGGL((maze_fp_forage_reset_kernel<N, true>), dim3(p.B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((maze_fp_forage_step_kernel<N, true>), dim3(p.B), dim3(256), 0, s, p);
+  } else if (view == kFirstPersonSense) {
     if (reset) hipLaunchKernelGGL((maze_fp_sense_reset_kernel<N, false>), dim3(p.B), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((maze_fp_sense_step_kernel<N, false>), dim3(p.B), dim3(256), 0, s, p);
   } else if (view == kFirstPersonGenSense) {

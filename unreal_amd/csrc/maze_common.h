@@ -124,4 +124,34 @@ __device__ __forceinline__ int maze_layout(const int* cfg, const int* layout, in
   return layout ? min(max(layout[b], 0), cfg[1] - 1) : 0;
 }
 
+// ---- foraging (flag kMazeForage, first person navigation blocks only): pickup kinds, goal-less episodes ----
+// Entry k of an apple record (the block's, or a generated actor's) is cell | kind << 16, ascending by cell; kind 0 is
+// the apple ('A': the header's apple reward, kAppleFloor, never terminal), kinds 1..K are the section's ('B', 'C', 'D').
+// Bit k of an actor's collected mask is entry k.  Words 4..7 of the navigation actor record are the running totals of
+// kinds 0..3 (never zeroed); such a block is never a goal-sense block.  The forage section is appended after everything
+// above (maze_forage_ext): [0] K kinds (0..3)  [1] mode (kForageNoGoal)  [4..6] the kinds' rewards
+// [8..10] r | g << 8 | b << 16 | ends_episode << 24  [12..14] gen_pickups (generated blocks: rooms of kind 1..3, ranked
+// after the gen_apples rooms by the same keys); every other word 0.
+// A kForageNoGoal block has no goal: goal[] holds (-1, -1), the start is S or free cell word 1 % n_free of the reset draw.
+constexpr int kMazeForage = 128;
+constexpr int kForageWords = 16, kForageNoGoal = 1, kForageKinds = 3;
+constexpr int kForageReward = 4, kForageColour = 8, kForageGen = 12;
+__device__ __forceinline__ const int* maze_forage_ext(const int* cfg) {
+  const int* sext = maze_style_ext(cfg);
+  return (cfg[2] & kMazeStyled) ? sext + kStyleHdr + kStyleSlots + cfg[1] * maze_style_words(cfg[0]) : sext;
+}
+
+// maze_reset_cells of a forage block: as above with a goal; without one, goal = -1 and word 0 is unused.
+__device__ __forceinline__ void maze_forage_reset_cells(const int* cfg, const int* rec, bool no_goal, int g, int ep,
+                                                        int& goal, int& start) {
+  if (!no_goal) { maze_reset_cells(cfg, rec, g, ep, goal, start); return; }
+  goal = -1;
+  start = rec[14];
+  if (cfg[2] & kMazeRandomStart) {
+    uint32_t u[4];
+    maze_reset_draw(cfg, g, ep, u);
+    start = rec[kRecHdr + (int)(u[1] % (uint32_t)max(rec[16], 1))];
+  }
+}
+
 }  // namespace

@@ -35,7 +35,8 @@ class Environment(object):
     def register_maze_config(env_name, layouts=None, random_start=False, random_goal=False, show_goal=False,
                              max_episode_steps=0, view="top_down", start_heading=None, goal_reward=1, apple_reward=1,
                              hit_reward=-1, goal_respawn=False, action_set="turn", generate=None, gen_loops=0,
-                             gen_apples=0, wall_styles=None, gen_landmark_density=0, goal_sense=False, progress_reward=0):
+                             gen_apples=0, wall_styles=None, gen_landmark_density=0, goal_sense=False, progress_reward=0,
+                             pickups=None, gen_pickups=None, no_goal=False):
         """Mazes of `env_name`: `layouts` = N x N maps (strings, or lists of row strings; + wall, - free, S start, G goal),
         N in {7, 12, 14, 21}, up to 1024 of them; global actor g runs layout g * L // (all actors).  random_start /
         random_goal: drawn at every reset, uniformly over the free cells (the start never on the goal); show_goal: the
@@ -58,12 +59,20 @@ class Environment(object):
         get_objective_size('maze', env_name) is then 3 and the network needs objective_size=3.  progress_reward (an
         integer in [-100, 100]; needs goal_sense) adds progress_reward * (d before the move - d after it) to every step's
         reward.
+        pickups (first person): 1 to 3 kinds (reward, (r, g, b), ends_episode) next to the apple: layout cells
+        'B', 'C', 'D' hold a pickup of kind 1, 2, 3, drawn on the floor in its colour, paying its reward (an integer in
+        [-100, 100]) once per episode and, with ends_episode=True, ending the episode; at most 64 pickups of all kinds
+        per layout; not with goal_sense.  gen_pickups (with generate and pickups): how many rooms of a generated maze hold
+        each kind.  no_goal=True (first person; needs max_episode_steps > 0): the layouts have no 'G', nothing is drawn as
+        a goal, and an episode ends at its time-out or at an ending pickup: with lemons at -1 the seek-avoid arena, with
+        one large ending pickup stairway-to-melon.
         Raises ValueError on a malformed config."""
         from .maze_environment import MazeConfig
         Environment.MAZE_CONFIG[env_name] = MazeConfig(layouts, random_start, random_goal, show_goal, max_episode_steps,
                                                        view, start_heading, goal_reward, apple_reward, hit_reward,
                                                        goal_respawn, action_set, generate, gen_loops, gen_apples,
-                                                       wall_styles, gen_landmark_density, goal_sense, progress_reward)
+                                                       wall_styles, gen_landmark_density, goal_sense, progress_reward,
+                                                       pickups, gen_pickups, no_goal)
 
     @staticmethod
     def create_environment(env_type, env_name, termination_time=50.0, env_args=None, thread_index=0):

@@ -15,7 +15,9 @@ config has no layouts: every reset writes a new maze for the actor on the device
 digits 1..7 (or drawn as landmarks of a generated maze, gen_landmark_density) show a colour and a stripe pattern of
 their own.  With goal_sense a first-person config hands the agent a measurement vector, the goal's offset
 in its own frame and the shortest-path distance to it, as the state's 'objective', and progress_reward pays for getting
-closer."""
+closer.  With pickups a first-person config has up to three more kinds of pickup next to the apple ('B', 'C',
+'D' cells), each with its own reward, floor colour and ends-the-episode bit, and with no_goal its episodes have no goal
+cell at all: the foraging levels."""
 from collections import deque
 
 import numpy as np
@@ -39,6 +41,11 @@ class MazeConfig(object):
     SIZES = (7, 12, 14, 21)          # the grid sizes whose cells tile the 84-px frame: 12, 7, 6, 4 px
     MAX_LAYOUTS = 1024
     RANDOM_START, RANDOM_GOAL, SHOW_GOAL, NAV, GENERATED, STYLED, GOAL_SENSE = 1, 2, 4, 8, 16, 32, 64
+    # foraging: a 16-word section after everything else (maze_common.h): [K, mode (1: no goal), 0, 0, the
+    # kinds' rewards x 3, 0, r | g << 8 | b << 16 | ends << 24 x 3, 0, gen_pickups x 3, 0]; an apple entry is then
+    # cell | kind << 16 (kind 0: 'A')
+    FORAGE, FORAGE_WORDS, FORAGE_NO_GOAL, MAX_KINDS, PICKUP_CHARS = 128, 16, 1, 3, "ABCD"
+    FORAGE_REWARD, FORAGE_COLOUR, FORAGE_GEN = 4, 8, 12
     # goal sense: objective = [gf / 32, gs / 32, d / 512]; progress_reward is word 6 of the navigation header
     OBJECTIVE_SIZE, OFFSET_SCALE, DISTANCE_SCALE, PROGRESS_WORD, NO_PATH = 3, 32, 512, 6, 0xFFFF
     GEN_STREAM, APPLE_STREAM = 0x4D415A47, 0x4D415A41      # Philox counter word 2 of a generated maze's edge / apple draws
@@ -58,9 +65,12 @@ class MazeConfig(object):
     def __init__(self, layouts=None, random_start=False, random_goal=False, show_goal=False, max_episode_steps=0,
                  view="top_down", start_heading=None, goal_reward=1, apple_reward=1, hit_reward=-1,
                  goal_respawn=False, action_set="turn", generate=None, gen_loops=0, gen_apples=0, wall_styles=None,
-                 gen_landmark_density=0, goal_sense=False, progress_reward=0):
+                 gen_landmark_density=0, goal_sense=False, progress_reward=0, pickups=None, gen_pickups=None,
+                 no_goal=False):
         self.generate, self.gen_loops, self.gen_apples = None, 0, 0
         self._check_styles(wall_styles, gen_landmark_density, view, generate)
+        self._check_forage(pickups, gen_pickups, no_goal, view, generate, random_goal, show_goal, goal_respawn,
+                           goal_sense, goal_reward, max_episode_steps)
         if generate is not None:
             self._check_generate(layouts, random_start, random_goal, view, generate, gen_loops, gen_apples)
             layouts = []
@@ -76,6 +86,9 @@ class MazeConfig(object):
             raise ValueError("max_episode_steps %r: an integer in [0, 2**31 - 1] (0: no limit; the kernels count steps "
                              "in int32)" % (max_episode_steps,))
         self.max_episode_steps = int(max_episode_steps)
+        if self.no_goal and self.max_episode_steps == 0:
+            raise ValueError("no_goal needs max_episode_steps > 0 (without an ending kind only the time-out ends an "
+                             "episode)")
         if view not in self.VIEWS:
             raise ValueError("view %r: one of %s" % (view, self.VIEWS))
         if start_heading is not None:
@@ -117,12 +130,14 @@ class MazeConfig(object):
         self.N = sizes.pop()
         self.L = len(self.layouts)
         self.walls, self.start, self.goal, self.free, self.apples, self.styles = [], [], [], [], [], []
+        self.pickup_cells, self.pickup_kinds = [], []
         for i, m in enumerate(self.layouts):
             self._check(i, m)
         # a navigation maze: any of the options above, or an apple in a layout (the default block stays word for word)
         # (a generated maze with apples is one too)
         # (and so is a goal-sense maze: its block carries the rewards header, its actors keep records)
-        self.nav = nav_options or any(len(a) for a in self.apples) or self.gen_apples > 0 or self.goal_sense
+        # (and a forage maze)
+        self.nav = nav_options or any(len(a) for a in self.apples) or self.gen_apples > 0 or self.goal_sense or self.forage
 
     def _check_styles(self, wall_styles, density, view, generate):
         integer = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
@@ -150,6 +165,61 @@ class MazeConfig(object):
     def styled(self):
         return self.wall_styles is not None
 
+    def _check_forage(self, pickups, gen_pickups, no_goal, view, generate, random_goal, show_goal, goal_respawn,
+                      goal_sense, goal_reward, max_episode_steps):
+        integer = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
+        seq = (list, tuple, np.ndarray)
+        self.pickups, self.gen_pickups, self.no_goal = None, None, False
+        if not isinstance(no_goal, (bool, np.bool_)):
+            raise ValueError("no_goal %r: a bool" % (no_goal,))
+        for name, used in (("pickups", pickups is not None), ("gen_pickups", gen_pickups is not None),
+                           ("no_goal", bool(no_goal))):
+            if used and view != "first_person":
+                raise ValueError("%s is a first-person setting; view is %r" % (name, view))
+        if pickups is not None:
+            if goal_sense:
+                raise ValueError("pickups with goal_sense: words 5..7 of the actor record cannot count the kinds and hold "
+                                 "the goal's offset and distance")
+            if not isinstance(pickups, seq) or not 1 <= len(pickups) <= self.MAX_KINDS:
+                raise ValueError("pickups: None, or a list of 1 to %d kinds (reward, (r, g, b), ends_episode)"
+                                 % self.MAX_KINDS)
+            kinds = []
+            for k, kind in enumerate(pickups):
+                if not isinstance(kind, seq) or len(kind) != 3:
+                    raise ValueError("pickups[%d] %r: (reward, (r, g, b), ends_episode)" % (k, kind))
+                reward, colour, ends = kind
+                if not integer(reward) or not -self.MAX_REWARD <= reward <= self.MAX_REWARD:
+                    raise ValueError("pickups[%d]: reward %r: an integer in [-%d, %d]"
+                                     % (k, reward, self.MAX_REWARD, self.MAX_REWARD))
+                if not isinstance(colour, seq) or len(colour) != 3 or not all(integer(v) and 0 <= v <= 255 for v in colour):
+                    raise ValueError("pickups[%d]: colour %r: (r, g, b), three integers in 0..255" % (k, colour))
+                if not isinstance(ends, (bool, np.bool_)):
+                    raise ValueError("pickups[%d]: ends_episode %r: a bool" % (k, ends))
+                kinds.append((int(reward), tuple(int(v) for v in colour), bool(ends)))
+            self.pickups = kinds
+        if gen_pickups is not None:
+            if generate is None or self.pickups is None:
+                raise ValueError("gen_pickups needs generate and pickups (static layouts place their pickups as 'B', 'C', "
+                                 "'D' cells)")
+            if not isinstance(gen_pickups, seq) or len(gen_pickups) != len(self.pickups) or \
+                    not all(integer(v) and v >= 0 for v in gen_pickups):
+                raise ValueError("gen_pickups %r: %d integers >= 0, one per kind of pickups"
+                                 % (gen_pickups, len(self.pickups)))
+            self.gen_pickups = tuple(int(v) for v in gen_pickups)
+        if no_goal:
+            if random_goal:
+                raise ValueError("no_goal: random_goal must be False (there is no goal to draw)")
+            if show_goal or goal_respawn or goal_sense:
+                raise ValueError("no_goal: show_goal, goal_respawn and goal_sense need a goal")
+            if isinstance(goal_reward, (bool, np.bool_)) or goal_reward != 1:
+                raise ValueError("no_goal: goal_reward %r is never paid (leave it at its default)" % (goal_reward,))
+            self.no_goal = True
+
+    @property
+    def forage(self):
+        """A forage config: pickups or no_goal is used."""
+        return self.pickups is not None or self.no_goal
+
     @staticmethod
     def style_words(N):
         """int32 words of one layout's 4-bit style ids (UNREAL_MAZE_STYLE_WORDS(N))."""
@@ -169,7 +239,9 @@ class MazeConfig(object):
             raise ValueError("generate %r: None, or a grid size N in %s" % (generate, self.SIZES))
         if view != "first_person":
             raise ValueError("generate is a first-person setting; view is %r" % (view,))
-        if not (random_start and random_goal):
+        if self.no_goal and not random_start:
+            raise ValueError("generate with no_goal needs random_start (a generated layout has no 'S' cell)")
+        if not self.no_goal and not (random_start and random_goal):
             raise ValueError("generate needs random_start and random_goal (a generated layout has no 'S' or 'G' cell)")
         R, E = self.gen_rooms(int(generate))
         if not integer(gen_loops) or not 0 <= gen_loops <= E - (R * R - 1):
@@ -178,11 +250,15 @@ class MazeConfig(object):
         if not integer(gen_apples) or not 0 <= gen_apples <= min(self.MAX_APPLES, R * R):
             raise ValueError("gen_apples %r: an integer in [0, %d] (at most one per room, %d per layout)"
                              % (gen_apples, min(self.MAX_APPLES, R * R), self.MAX_APPLES))
+        if self.gen_pickups is not None and gen_apples + sum(self.gen_pickups) > min(self.MAX_APPLES, R * R):
+            raise ValueError("gen_apples %d + gen_pickups %r: at most %d pickups (one per room, %d per layout)"
+                             % (gen_apples, self.gen_pickups, min(self.MAX_APPLES, R * R), self.MAX_APPLES))
         self.generate, self.gen_loops, self.gen_apples = int(generate), int(gen_loops), int(gen_apples)
 
     def generated_layout(self, seed, g, episode):
         """The layout of global actor g's episode `episode` under the key `seed`, as a string in the layout alphabet
-        ('+' wall, '-' free, 'A' apple): what the device writes at that reset (DESIGN §7g).  Rooms are the even cells;
+        ('+' wall, '-' free, 'A' apple, 'B' / 'C' / 'D' a pickup of kind 1 / 2 / 3: the rooms ranked after the apples'
+        by the same keys, gen_pickups[0] of 'B', then 'C', then 'D'; DESIGN §7j): what the device writes at that reset (DESIGN §7g).  Rooms are the even cells;
         edge e between neighbouring rooms (horizontal first, row-major, then vertical) has the key (w << 8) | e, w = word
         e & 3 of Philox4x32-10(key = seed, counter = (g, episode, GEN_STREAM, e >> 2)); open are the minimum spanning
         tree of the room grid under these keys and the gen_loops lightest other edges.  Apples lie in the gen_apples
@@ -215,11 +291,15 @@ class MazeConfig(object):
         cells[room_cell(np.arange(R * R))] = "-"
         cells[edge_cell[tree]] = "-"
         cells[edge_cell[extra]] = "-"
-        if self.gen_apples:
+        counts = (self.gen_apples,) + (self.gen_pickups or ())
+        if sum(counts):
             r = np.arange(R * R)
             akey = (_philox_words(seed, g, episode, self.APPLE_STREAM, R * R).astype(np.uint64) << np.uint64(8)) | \
                 r.astype(np.uint64)
-            cells[room_cell(np.argsort(akey)[:self.gen_apples])] = "A"
+            ranked, first = np.argsort(akey), 0
+            for kind, n in enumerate(counts):
+                cells[room_cell(ranked[first:first + n])] = self.PICKUP_CHARS[kind]
+                first += n
         if self.styled and self.gen_landmark_density:
             w = _philox_words(seed, g, episode, self.STYLE_STREAM, N * N).astype(np.int64)
             mark = (cells == "+") & ((w >> 24) < self.gen_landmark_density)
@@ -238,10 +318,13 @@ class MazeConfig(object):
         n = int(round(len(m) ** 0.5))
         if n * n != len(m) or n not in self.SIZES:
             raise ValueError("layout %d: %d cells; supported are N x N with N in %s" % (i, len(m), self.SIZES))
-        bad = set(m) - set("+-SGA1234567")
+        bad = set(m) - set("+-SGA1234567" + self.PICKUP_CHARS[1:1 + len(self.pickups or ())])
+        if bad & set(self.PICKUP_CHARS) and self.pickups is not None:
+            raise ValueError("layout %d: pickup %s, but pickups holds %d kinds ('B' is kind 1)"
+                             % (i, sorted(bad & set(self.PICKUP_CHARS)), len(self.pickups)))
         if bad:
             raise ValueError("layout %d: unknown characters %s (use + wall, - free, S start, G goal, A apple, 1..7 "
-                             "styled wall)" % (i, sorted(bad)))
+                             "styled wall; B, C, D a pickup of pickups)" % (i, sorted(bad)))
         digits = [int(ch) for ch in set(m) if ch.isdigit()]
         if digits and max(digits) > len(self.wall_styles or ()):
             raise ValueError("layout %d: wall digit %d, but wall_styles holds %d styles"
@@ -250,6 +333,10 @@ class MazeConfig(object):
             raise ValueError("layout %d: apples ('A') are a first-person setting; view is %r" % (i, self.view))
         if m.count("A") > self.MAX_APPLES:
             raise ValueError("layout %d: %d apples; at most %d per layout" % (i, m.count("A"), self.MAX_APPLES))
+        n_pick = sum(m.count(ch) for ch in self.PICKUP_CHARS)
+        if n_pick > self.MAX_APPLES:
+            raise ValueError("layout %d: %d pickups of all kinds; at most %d per layout (an actor has %d collected bits)"
+                             % (i, n_pick, self.MAX_APPLES, self.MAX_APPLES))
         return m
 
     def _check(self, i, m):
@@ -257,7 +344,10 @@ class MazeConfig(object):
         n_s, n_g = m.count("S"), m.count("G")
         if not self.random_start and n_s != 1:
             raise ValueError("layout %d: %d 'S' cells; exactly one is needed without random_start" % (i, n_s))
-        if not self.random_goal and n_g != 1:
+        if self.no_goal:
+            if n_g:
+                raise ValueError("layout %d: %d 'G' cells; a no_goal config has none" % (i, n_g))
+        elif not self.random_goal and n_g != 1:
             raise ValueError("layout %d: %d 'G' cells; exactly one is needed without random_goal" % (i, n_g))
         wall = self.WALL_CHARS
         free = [c for c in range(N * N) if m[c] not in wall]
@@ -282,12 +372,16 @@ class MazeConfig(object):
         self.goal.append(m.index("G") if n_g == 1 else -1)
         self.free.append(np.array(free, dtype=np.int32))
         self.apples.append(np.array([c for c in range(N * N) if m[c] == "A"], dtype=np.int32))
+        if self.forage:       # every pickup, ascending by cell, and its kind ('A': 0); self.apples keeps the 'A' cells
+            cells = [c for c in range(N * N) if m[c] in self.PICKUP_CHARS]
+            self.pickup_cells.append(np.array(cells, dtype=np.int32))
+            self.pickup_kinds.append(np.array([self.PICKUP_CHARS.index(m[c]) for c in cells], dtype=np.int32))
 
     @property
     def flags(self):
         return (self.RANDOM_START * self.random_start) | (self.RANDOM_GOAL * self.random_goal) | \
             (self.SHOW_GOAL * self.show_goal) | (self.NAV * self.nav) | (self.GENERATED * (self.generate is not None)) | \
-            (self.STYLED * self.styled) | (self.GOAL_SENSE * self.goal_sense)
+            (self.STYLED * self.styled) | (self.GOAL_SENSE * self.goal_sense) | (self.FORAGE * self.forage)
 
     @property
     def action_size(self):
@@ -297,9 +391,12 @@ class MazeConfig(object):
     def reward_bound(self):
         """max |reward| over the kinds of step (1 for every config without navigation rewards): a goal step pays
         goal_reward + p (it always gets one cell closer), an apple step apple_reward +- p, a hit hit_reward, any other
-        move +- p, with p = progress_reward."""
+        move +- p, with p = progress_reward.  A forage config: a pickup of kind k pays its own reward, and
+        without a goal goal_reward is never paid."""
         p = self.progress_reward
-        return max(abs(self.goal_reward + p), abs(self.apple_reward) + abs(p), abs(self.hit_reward), abs(p))
+        kinds = [abs(r) for r, _, _ in self.pickups or ()]
+        goal = [] if self.no_goal else [abs(self.goal_reward + p)]
+        return max(goal + kinds + [abs(self.apple_reward) + abs(p), abs(self.hit_reward), abs(p)])
 
     @staticmethod
     def dist_words(N):
@@ -347,7 +444,11 @@ class MazeConfig(object):
         [goal reward, apple reward, hit reward, mode, gen_loops, gen_apples, 0, 0]; the layout and apple records are
         per actor, written on the device at every reset.  A styled maze (flag STYLED) appends, after all of
         this, [S, gen_landmark_density, 0 x 6], the 8 style words r | g << 8 | b << 16 | pattern << 24 (unused: 0) and,
-        per static layout, (N * N + 7) // 8 words of 4-bit style ids (cell c: nibble c & 7 of word c >> 3)."""
+        per static layout, (N * N + 7) // 8 words of 4-bit style ids (cell c: nibble c & 7 of word c >> 3).  A forage
+        maze (flag FORAGE, always with NAV) appends, after all of this, the 16 words [K, mode (1: no goal), 0,
+        0, rewards of kinds 1..3, 0, r | g << 8 | b << 16 | ends << 24 of kinds 1..3, 0, gen_pickups, 0]; its apple
+        records hold every pickup, ascending by cell, as cell | kind << 16 ('A': kind 0), and a layout record of a
+        no_goal maze has G = -1."""
         N, rec = self.N, self.RECORD_HEADER + self.N * self.N
         seed = int(seed) & (2 ** 64 - 1)
         out = np.zeros(self.HEADER + self.L * rec, dtype=np.int64)
@@ -370,6 +471,8 @@ class MazeConfig(object):
             ext[self.PROGRESS_WORD] = self.progress_reward
             for l, a in enumerate(self.apples):
                 r = ext[self.NAV_HEADER + l * self.NAV_RECORD:]
+                if self.forage:
+                    a = self.pickup_cells[l] | self.pickup_kinds[l] << 16
                 r[0] = len(a)
                 r[1:1 + len(a)] = a
             out = np.concatenate([out, ext])
@@ -384,6 +487,15 @@ class MazeConfig(object):
                 nib[:N * N] = ids
                 sec[self.STYLE_HEADER + self.STYLE_SLOTS + l * sw:][:sw] = (nib.reshape(sw, 8) << (4 * np.arange(8))).sum(1)
             out = np.concatenate([out, sec])
+        if self.forage:
+            sec = np.zeros(self.FORAGE_WORDS, dtype=np.int64)
+            sec[0], sec[1] = len(self.pickups or ()), self.FORAGE_NO_GOAL * self.no_goal
+            for k, (reward, (r, g, b), ends) in enumerate(self.pickups or ()):
+                sec[self.FORAGE_REWARD + k] = reward
+                sec[self.FORAGE_COLOUR + k] = r | g << 8 | b << 16 | int(ends) << 24
+            for k, n in enumerate(self.gen_pickups or ()):
+                sec[self.FORAGE_GEN + k] = n
+            out = np.concatenate([out, sec])
         return (out & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
 
     def layout_ids(self, actor_base, batch, actors_total):
@@ -397,7 +509,7 @@ class MazeConfig(object):
         return MazeConfig([layout_string], self.random_start, self.random_goal, self.show_goal, self.max_episode_steps,
                           self.view, self.start_heading, self.goal_reward, self.apple_reward, self.hit_reward,
                           self.goal_respawn, self.action_set, wall_styles=self.wall_styles, goal_sense=self.goal_sense,
-                          progress_reward=self.progress_reward)
+                          progress_reward=self.progress_reward, pickups=self.pickups, no_goal=self.no_goal)
 
     @staticmethod
     def reference():
@@ -449,6 +561,8 @@ class BatchedMazeEnvironment(object):
                 view = ops.MAZE_FIRST_PERSON_GENERATED
             if config.goal_sense:                  # kernels of their own
                 view = ops.MAZE_FIRST_PERSON_SENSE if config.generate is None else ops.MAZE_FIRST_PERSON_GENERATED_SENSE
+            if config.forage:                      # and so have forage blocks
+                view = ops.MAZE_FIRST_PERSON_FORAGE if config.generate is None else ops.MAZE_FIRST_PERSON_GENERATED_FORAGE
             self.maze = (view, config.N, block, int(actor_base)) + ((True,) if config.styled else ())
         self.reset()
 
@@ -521,7 +635,9 @@ class BatchedMazeEnvironment(object):
 
     def current_layouts(self):
         """The layouts the actors of a generated maze are in -> (walls, apples): bool [B, N, N] (True: wall; [b, y, x])
-        and a list of B int arrays of apple cells y * N + x, ascending (collected ones included)."""
+        and a list of B int arrays of apple cells y * N + x, ascending (collected ones included).  A forage config
+        (DESIGN §7j): a third item, a list of B layout strings with the letters 'A' .. 'D' of every pickup, and the
+        second lists the cells of every kind."""
         if self.config is None or self.config.generate is None:
             raise ValueError("current_layouts: the config is not a generated maze")
         N = self.config.N
@@ -530,6 +646,14 @@ class BatchedMazeEnvironment(object):
         bits = (words[:, :, None] >> np.arange(32)) & 1
         walls = bits.reshape(self.B, 448)[:, :N * N].astype(bool).reshape(self.B, N, N)
         arec = rec[:, ops.MAZE_RECORD_HEADER + N * N:]
+        if self.config.forage:
+            entries = [arec[b, 1:1 + arec[b, 0]] for b in range(self.B)]
+            letters = []
+            for b, e in enumerate(entries):
+                cells = np.where(walls[b].reshape(-1), "+", "-")
+                cells[e & 0xFFFF] = np.array(list(MazeConfig.PICKUP_CHARS))[(e >> 16) & 3]
+                letters.append("".join(cells))
+            return walls, [e & 0xFFFF for e in entries], letters
         return walls, [arec[b, 1:1 + arec[b, 0]].copy() for b in range(self.B)]
 
     def current_styles(self):

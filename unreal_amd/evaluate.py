@@ -11,7 +11,9 @@ the config sets no limit.  On a navigation maze success is an epis
 per-actor goals_total / apples_total counters; with goal_respawn an episode ends only at its time-out.  On a goal-sense
 maze without goal_respawn the result also holds `start_distance`, the mean path distance d0 from start to
 goal of the counted episodes, and `spl`, the mean of success * d0 / max(d0, episode length in steps): every action is a
-step, turns and looks included, so an agent on the shortest path scores d0 / (d0 + its turns)."""
+step, turns and looks included, so an agent on the shortest path scores d0 / (d0 + its turns).  On a forage maze
+ the result also holds `pickups_per_episode`, the mean number of collected pickups of kinds A, B, C, D, and on a
+no_goal maze success is an episode whose final step collected an ends_episode kind with a reward > 0."""
 import torch
 
 from . import ops
@@ -58,7 +60,10 @@ class Evaluate(object):
 
     def process(self, n_episodes, max_episode_steps=2000, one_episode_per_actor=False):
         """-> dict(episodes, success_rate, mean_return, return_std, mean_length, timeouts, goals_per_episode,
-        apples_per_episode[, start_distance, spl]).
+        apples_per_episode[, start_distance, spl][, pickups_per_episode]).
+        On a forage maze `pickups_per_episode` holds the mean number of collected pickups of kinds A, B, C, D
+        per counted episode (differences of record words 4..7); on a no_goal maze success is an episode whose final step
+        collected an ends_episode kind with a reward > 0, read from those totals before and after that step.
         `one_episode_per_actor`: count only the FIRST episode of each of the B lock-step actors and stop when all B have
         finished or timed out (n_episodes is ignored).  Stopping at the first n finished episodes instead over-represents
         short episodes whenever actors restart while others are still in their first one."""
@@ -78,8 +83,12 @@ class Evaluate(object):
         counted = [False] * B
         goals, apples = [], []                 # per counted episode
         if nav:                                # goals_total / apples_total (never zeroed by a reset): per-episode differences
-            tot = ring.actor_records[:, 3:5]
+            forage = cfg.forage
+            tot = ring.actor_records[:, 3:8] if forage else ring.actor_records[:, 3:5]
             ep0 = tot.cpu().numpy().copy()
+            before = ep0.copy()                # forage: the totals before the step
+            kinds = []                         # per counted episode: collected A, B, C, D
+            winning = [k for k, (r, _, ends) in enumerate(cfg.pickups or (), 1) if ends and r > 0]
         # goal sense: path efficiency.  d0 = word 7 of the actor's record after the reset that started the episode
         sense = cfg is not None and cfg.goal_sense and not cfg.goal_respawn
         start_d, spl = [], []
@@ -118,12 +127,16 @@ class Evaluate(object):
                     n_goals = int(now[b, 0] - ep0[b, 0]) if nav else int(bool(term[b]) and rew[b] == 1.0)
                     goals.append(n_goals)
                     apples.append(int(now[b, 1] - ep0[b, 1]) if nav else 0)
+                    if nav and forage:
+                        kinds.append([int(v) for v in now[b, 1:5] - ep0[b, 1:5]])
                 if ended and nav:
                     ep0[b] = now[b]
                 if term[b]:
                     if not skip:
                         returns.append(float(score[b])); lengths.append(steps[b]); done += 1
                         success = not configured or (goals[-1] > 0 if nav else rew[b] == 1.0)
+                        if nav and cfg.no_goal:        # the final step collected a winning kind
+                            success = any(now[b, 1 + k] > before[b, 1 + k] for k in winning)
                         if success:
                             successes += 1
                         else:
@@ -143,6 +156,8 @@ class Evaluate(object):
                         if sense:
                             start_d.append(int(d0[b])); spl.append(0.0)
                     steps[b] = 0; force[b] = 1; counted[b] = True
+            if nav and forage:
+                before = now.copy()
             if int(force.sum()):                   # abandon timed-out episodes
                 m = force.to(self.device)
                 self.env.reset(m)
@@ -160,4 +175,6 @@ class Evaluate(object):
                    apples_per_episode=sum(apples) / float(n))
         if sense:
             res.update(start_distance=sum(start_d) / float(n), spl=sum(spl) / float(n))
+        if nav and forage:
+            res.update(pickups_per_episode=[sum(k[i] for k in kinds) / float(n) for i in range(4)])
         return res

@@ -208,6 +208,9 @@ MAZE_TOP_DOWN, MAZE_FIRST_PERSON = 0, 1       # the `view` of a maze (UNREAL_MAZ
 MAZE_FIRST_PERSON_GENERATED = 2               # first person, a generated block (UNREAL_MAZE_FIRST_PERSON_GENERATED)
 # goal-sense blocks: UNREAL_MAZE_FIRST_PERSON_SENSE / UNREAL_MAZE_FIRST_PERSON_GENERATED_SENSE
 MAZE_FIRST_PERSON_SENSE, MAZE_FIRST_PERSON_GENERATED_SENSE = 3, 4
+# forage blocks: UNREAL_MAZE_FIRST_PERSON_FORAGE / UNREAL_MAZE_FIRST_PERSON_GENERATED_FORAGE; their records
+# are the navigation / generated records (words 4..7: the running totals of pickup kinds 0..3)
+MAZE_FIRST_PERSON_FORAGE, MAZE_FIRST_PERSON_GENERATED_FORAGE = 5, 6
 NAV_RECORD = 8                                # int32 words of a navigation maze's per-actor record (UNREAL_MAZE_NAV_RECORD)
 MAZE_RECORD_HEADER, NAV_APPLE_RECORD = 18, 65  # words of a layout record before its free list; of an apple record
 
@@ -247,8 +250,8 @@ def _maze_args(ring, maze):
     # a goal-sense block (views 3, 4) is a first-person / generated block whose records end in the distance field: the
     # record widths are the ring's (Ring(sense=N)), checked against the block's here
     sense = view in (MAZE_FIRST_PERSON_SENSE, MAZE_FIRST_PERSON_GENERATED_SENSE)
-    generated = view in (MAZE_FIRST_PERSON_GENERATED, MAZE_FIRST_PERSON_GENERATED_SENSE)
-    static_fp = view in (MAZE_FIRST_PERSON, MAZE_FIRST_PERSON_SENSE)
+    generated = view in (MAZE_FIRST_PERSON_GENERATED, MAZE_FIRST_PERSON_GENERATED_SENSE, MAZE_FIRST_PERSON_GENERATED_FORAGE)
+    static_fp = view in (MAZE_FIRST_PERSON, MAZE_FIRST_PERSON_SENSE, MAZE_FIRST_PERSON_FORAGE)
     if getattr(ring, "sense_n", 0) != (N if sense else 0):
         raise ValueError("a goal-sense maze needs a ring with distance fields of its size (Ring(sense=%d)), any other "
                          "maze a ring without" % N)
@@ -258,6 +261,8 @@ def _maze_args(ring, maze):
     if static_fp:
         if sense and nav is None:
             raise ValueError("a goal-sense maze keeps per-actor records (Ring(nav=True, sense=%d))" % N)
+        if view == MAZE_FIRST_PERSON_FORAGE and nav is None:
+            raise ValueError("a forage maze keeps per-actor records (Ring(nav=True))")
         arrays += (("nav", getattr(ring, "nav_words", NAV_RECORD) * ring.B),) if nav is not None else (("heading", ring.B),)
     if generated:
         want = gen_record_words(N, styled) + (dist_words(N) if sense else 0)
@@ -330,9 +335,10 @@ def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, act
     """policy_step + maze_rollout_step in one launch: the workgroup that steps an actor computes its pi / V / action first
     (bit-identical to the two launches).  A = 6: a first-person navigation maze with Lab's action set."""
     B = ring.B
-    nav = maze is not None and ((maze[0] in (MAZE_FIRST_PERSON, MAZE_FIRST_PERSON_SENSE) and
+    nav = maze is not None and ((maze[0] in (MAZE_FIRST_PERSON, MAZE_FIRST_PERSON_SENSE, MAZE_FIRST_PERSON_FORAGE) and
                                  getattr(ring, "nav", None) is not None) or
-                                maze[0] in (MAZE_FIRST_PERSON_GENERATED, MAZE_FIRST_PERSON_GENERATED_SENSE))
+                                maze[0] in (MAZE_FIRST_PERSON_GENERATED, MAZE_FIRST_PERSON_GENERATED_SENSE,
+                                            MAZE_FIRST_PERSON_GENERATED_FORAGE))
     if A != 4 and not (A == 6 and nav):
         raise ValueError("the maze has 4 actions (6: a first-person navigation maze with action_set='lab'); A = %r" % (A,))
     _chk(X, "f32", (B - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A); _chk(bp, "f32", A); _chk(Wv, "f32", 256)
