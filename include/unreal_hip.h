@@ -175,6 +175,68 @@ int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, cons
  * count / records / r_objective, or next_lar with lar_col0 < 0 or lar_ld < lar_col0 + 3. */
 int unreal_maze_objective(int B, int H1, const int* count, const int* records, int record_words, float* r_objective,
                           float* next_lar /*nullable*/, int lar_ld, int lar_col0, void* stream);
+/* Device arcade (csrc/arcade.hip): games stepped and rendered on the device, one actor per workgroup.  The
+ * four entries take the ring and rollout arguments of the maze entries above (`pos` is accepted and never touched;
+ * nullable) and commit through the same helpers; the maze tail is replaced by (cfg, actor_base, ep_steps[B], episode[B],
+ * records[B][UNREAL_ARCADE_RECORD]).  There is one launch shape and no launch label.
+ *
+ * cfg: UNREAL_ARCADE_CFG_WORDS int32 words.  [0] game id (UNREAL_ARCADE_BREAKOUT; a kernel that reads another id writes
+ * nothing)  [1] 0  [2] rows 1..6  [3] max_episode_steps >= 1  [4..5] seed (lo, hi)  [6] paddle_width (even, 4..24)
+ * [7] paddle_speed 1..8  [8] ball_speed 1..4  [9] lives 1..5  [10] serve_wait 0..255 (0: only fire serves)
+ * [11] life_reward -100..0  [12..17] row rewards 0..100, top row first  [18..23] 0.
+ * record: [0..6] px, bx, by, vx, vy, wait (>= 0: the ball waits to be served, -1: in flight), lives  [7..8] live bricks
+ * (bit 10 r + c, lo, hi)  [9] serve_index  [10] bricks total  [11] lives-lost total  [12] walls-cleared total (the totals
+ * are never zeroed)  [13..15] 0.
+ *
+ * Breakout, actions 0 noop, 1 fire, 2 right, 3 left (ALE's minimal set: A = 4).  Frame 84 x 84 x 3 bytes (frame scale
+ * 1 / 255), back to front: black; border (142, 142, 142) on rows 0..5 and columns 0..1, 82..83; life k < lives the block
+ * x 4+4k..5+4k, y 2..3 in (236, 236, 236); brick (r, c) x 2+8c..9+8c, y 18+3r..20+3r in its row's colour; paddle y 78..79,
+ * x px..px+w-1 in (200, 72, 72); the ball, 2 x 2 at (bx, by) in (236, 236, 236), only in flight.  One step:
+ *  1. steps += 1; action 2 / 3 moves the paddle by paddle_speed, clamped to [2, 82 - w].
+ *  2. A waiting ball is served on fire, or when serve_wait > 0 and wait >= serve_wait: u = Philox4x32-10(key = seed,
+ *     counter = (actor_base + b, episode, 0x41524B53, serve_index)); bx = 2 + 2 (u[0] % 39), by = 40, vx = u[1] & 1 ? +1
+ *     : -1, vy = +1, wait = -1, serve_index += 1.  Otherwise wait += 1.  The ball does not move in such a step.
+ *  3. A ball in flight makes ball_speed micro-steps, each an x move and then a y move, ending early after the micro-step
+ *     in which a life is lost or the last brick goes.  x: tx = bx + vx; outside [2, 80]: vx = -vx; else if the 2 x 2 box at
+ *     (tx, by) overlaps live bricks: the one with the lowest bit is cleared and pays its row's reward, vx = -vx; else
+ *     bx = tx.  y: ty = by + vy; ty < 6: vy = +1; else a brick as in x (vy = -vy); else if vy > 0, ty + 1 == 78 and
+ *     [bx, bx+1] meets the paddle: vy = -1 and, with d = bx + 1 - (px + w / 2), vx = -2 if 4 d < -w, -1 if d < 0, +1 if
+ *     4 d < w, else +2; else if ty + 1 > 83: lives -= 1, the reward gets life_reward, wait = 0; else by = ty.
+ *  4. terminal: lives <= 0, no live brick, or steps >= max_episode_steps.  With reset_on_terminal the next episode starts
+ *     (episode += 1, full wall, all lives, px = 42 - w / 2, ball waiting, wait = serve_index = steps = 0) and its first
+ *     frame goes into the next slot.  The pixel change is that of the two frames before the reset, over 48 * 255.
+ * -EINVAL without a launch: B <= 0, H1 < 2, a null or misaligned pointer the entry uses (cfg included), actor_base < 0,
+ * and in the rollout entries A != 4 or a next_lar row too short for A + 1 columns. */
+#define UNREAL_ARCADE_BREAKOUT 1
+#define UNREAL_ARCADE_CFG_WORDS 24
+#define UNREAL_ARCADE_RECORD 16
+#define UNREAL_ARCADE_SERVE_STREAM 0x41524B53
+int unreal_arcade_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward, const int* count,
+                        uint8_t* frames, const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
+                        void* stream);
+int unreal_arcade_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
+                       float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                       int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                       float* episode_reward, float* score_out, int* score_valid, int reset_on_terminal, int track_score,
+                       const int* cfg, int actor_base, int* ep_steps, int* episode, int* records, void* stream);
+int unreal_arcade_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                               int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                               int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                               int* out_terminal, float* episode_reward, float* score_out, int* score_valid, int* active,
+                               int* active_log_t, int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
+                               float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                               const int* cfg, int actor_base, int* ep_steps, int* episode, int* records, void* stream);
+/* unreal_policy_step + unreal_arcade_rollout_step in one launch, bit-identical to the two (policy_row<4>) */
+int unreal_arcade_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                      const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                      int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
+                                      uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                      int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                      int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                      int* active, int* active_log_t, int* n_steps, int* terminal_end,
+                                      int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0,
+                                      int A, int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
+                                      int* episode, int* records, void* stream);
 /* host-fed environments (environment/hostfed_environment.py): environment.process + experience.add_frame of
  * every actor where active[b] != 0, for simulators on the host.  `staged` holds one uint8 frame per actor, frame_stride
  * bytes apart as in the ring (a multiple of 16 within [1200, 691200]: 20 x 20 x 3 .. 480 x 480 x 3 rounded up to 16).

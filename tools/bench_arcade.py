@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""The device arcade next to the device mazes, in one process:
+
+  * time per launch (HIP events around each launch, random actions) of the arcade step and of the arcade step with the
+    policy fused into it, next to the static first-person maze step (N = 7) and the top-down maze step, at B = 512 and
+    B = 4096.  The kernels are timed in turn and the whole table is printed --repeat times;
+  * Trainer.process() ms for full UNREAL at B = 4096 (replay history --history, filled untimed) on the arcade and on the
+    first-person maze.
+
+  python tools/bench_arcade.py [--launches 200] [--steps 10] [--warmup 3] [--history 100] [--repeat 2] [--skip-trainer]
+
+Prints one JSON line per measurement."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from bench_fp_maze import DEV, kernel_ms, layouts, trainer_ms as maze_trainer_ms    # noqa: E402
+
+
+def fused_ms(env, B, launches):
+    """Mean HIP-event time of one policy-fused arcade step (random feature rows and weights, all actors active)."""
+    from unreal_amd import ops
+    rs = np.random.RandomState(0)
+    dev = lambda a, dt: torch.from_numpy(np.asarray(a)).to(DEV, dt)
+    net = type("Net", (), {"p": dict(W_base_fc_p=dev(rs.uniform(-.3, .3, 1024), torch.float32),
+                                     b_base_fc_p=dev(rs.uniform(-.1, .1, 4), torch.float32),
+                                     W_base_fc_v=dev(rs.uniform(-.3, .3, 256), torch.float32),
+                                     b_base_fc_v=dev(rs.uniform(-.1, .1, 1), torch.float32))})
+    X = dev(rs.uniform(-1, 1, B * 256), torch.float32)
+    us = [dev(rs.uniform(0, 1, B), torch.float64) for _ in range(8)]
+    z = lambda dt, n=B: torch.zeros(n, dtype=dt, device=DEV)
+    pi, v, a, r, t = z(torch.float32, 4 * B), z(torch.float32), z(torch.int32), z(torch.float32), z(torch.int32)
+    active, log, n, te = torch.ones(B, dtype=torch.int32, device=DEV), z(torch.int32), z(torch.int32), z(torch.int32)
+
+    def step(k):
+        active.fill_(1)
+        env.policy_rollout_step(net, X, 256, us[k % 8], pi, v, a, r, t, active, log, n, te)
+    for k in range(10):
+        step(k)
+    ops.kernel_timer_start("unreal_arcade_policy_rollout_step")
+    for k in range(launches):
+        step(k)
+    res = ops.kernel_timer_stop()
+    assert res["launches"] == launches, res
+    return res["ms"] / launches
+
+
+def arcade_trainer_ms(env_name, B, history, steps, warmup):
+    import time
+    from unreal_amd.model.model import UnrealModel
+    from unreal_amd.options import get_options
+    from unreal_amd.train.rmsprop_applier import RMSPropApplier
+    from unreal_amd.train.trainer import Trainer, log_uniform
+    flags = get_options("training", preset="lab", argv=[])
+    net = UnrealModel(4, 0, -1, flags.use_lstm, flags.use_pixel_change, flags.use_value_replay,
+                      flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta, DEV, seed=1)
+    lr0 = log_uniform(flags.initial_alpha_low, flags.initial_alpha_high, flags.initial_alpha_log_rate)
+    applier = RMSPropApplier(None, decay=flags.rmsp_alpha, momentum=0.0, epsilon=flags.rmsp_epsilon,
+                             clip_norm=flags.grad_norm_clip, device=DEV)
+    tr = Trainer(0, net, lr0, None, applier, "arcade", env_name, flags.use_lstm, flags.use_pixel_change,
+                 flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
+                 flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, history, flags.max_time_step, DEV,
+                 batch_size=B, seed=0xA3C)
+    tr.prepare()
+    while not tr._full:
+        tr.process(None, 0)
+    for _ in range(warmup):
+        tr.process(None, 0)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    for _ in range(steps):
+        tr.process(None, 0)
+    e1.record()
+    torch.cuda.synchronize()
+    out = e0.elapsed_time(e1) / steps, (time.perf_counter() - t0) * 1e3 / steps
+    del tr, net, applier
+    torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--launches", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--history", type=int, default=100)
+    ap.add_argument("--repeat", type=int, default=2)
+    ap.add_argument("--skip-trainer", action="store_true")
+    args = ap.parse_args()
+    from unreal_amd.environment.environment import Environment
+    from unreal_amd.environment.arcade_environment import BatchedArcadeEnvironment
+    from unreal_amd.environment.maze_environment import batched_maze_environment
+    Environment.register_arcade_config("bench_breakout")
+    kw = dict(random_start=True, random_goal=True, max_episode_steps=200)
+    Environment.register_maze_config("bench_fp7", layouts(7), view="first_person", **kw)
+    Environment.register_maze_config("bench_td7", layouts(7), **kw)
+    for rep in range(args.repeat):
+        for B in (512, 4096):
+            envs = dict(arcade=BatchedArcadeEnvironment(B, 3, DEV, config=Environment.ARCADE_CONFIG["bench_breakout"]),
+                        first_person=batched_maze_environment(B, 3, DEV, config=Environment.MAZE_CONFIG["bench_fp7"]),
+                        top_down=batched_maze_environment(B, 3, DEV, config=Environment.MAZE_CONFIG["bench_td7"]))
+            row = dict(bench="arcade_step", B=B, repeat=rep)
+            for k in range(2):                                  # the kernels in turn, twice
+                row["arcade_us_%d" % k] = round(1e3 * kernel_ms(envs["arcade"], B, args.launches, entry="unreal_arcade_step"), 2)
+                row["arcade_fused_us_%d" % k] = round(1e3 * fused_ms(envs["arcade"], B, args.launches), 2)
+                row["first_person_us_%d" % k] = round(1e3 * kernel_ms(envs["first_person"], B, args.launches), 2)
+                row["top_down_us_%d" % k] = round(1e3 * kernel_ms(envs["top_down"], B, args.launches), 2)
+            print(json.dumps(row), flush=True)
+            del envs
+            torch.cuda.empty_cache()
+    if not args.skip_trainer:
+        for rep in range(args.repeat):
+            for name, fn in (("bench_breakout", arcade_trainer_ms), ("bench_fp7", maze_trainer_ms)):
+                dev_ms, wall_ms = fn(name, 4096, args.history, args.steps, args.warmup)
+                print(json.dumps(dict(bench="trainer_process", env=name, B=4096, history=args.history, repeat=rep,
+                                      device_ms=round(dev_ms, 2), wall_ms=round(wall_ms, 2),
+                                      env_steps_per_s=round(4096 * 20 / wall_ms * 1e3))), flush=True)
+
+
+if __name__ == "__main__":
+    main()

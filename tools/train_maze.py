@@ -2,9 +2,11 @@
 """Train the maze agent with the batched Trainer and log episode returns (GPU box).
 
 usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] [--steps 2e7] [--log-every 10]
-                                  [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl]
+                                  [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout]
 `--groups G`: G sequential updates per process() call (update density x G, see Trainer).  One JSON line per
-`--log-every` calls: global_t, episodes finished since the last line, their mean return, losses, entropy, steps/s."""
+`--log-every` calls: global_t, episodes finished since the last line, their mean return, losses, entropy, steps/s.
+`--arcade GAME`: train on the device arcade with that game's default config instead; a line then also holds
+bricks_per_episode and lives_lost_per_episode (differences of the records' totals over the episodes of the line)."""
 import argparse
 import json
 import os
@@ -26,9 +28,35 @@ ap.add_argument("--lr-scale", type=float, default=1.0)
 ap.add_argument("--max-time-step", type=float, default=0)
 ap.add_argument("--entropy-beta", type=float, default=None, help="override options_lab's 0.001 (a stated deviation)")
 ap.add_argument("--out", default="")
+ap.add_argument("--arcade", default="", help="a device arcade game (breakout) instead of the maze")
 args = ap.parse_args()
 device = torch.device("cuda", 0)
-flags, net, tr = build_trainer(args, 0, 1, device)
+
+
+def build_arcade_trainer(args, device):
+    """bench.build_trainer for env_type 'arcade' (one rank)."""
+    from unreal_amd.environment.environment import Environment
+    from unreal_amd.model.model import UnrealModel
+    from unreal_amd.options import get_options
+    from unreal_amd.train.rmsprop_applier import RMSPropApplier
+    from unreal_amd.train.trainer import Trainer, log_uniform
+    Environment.register_arcade_config(args.arcade, game=args.arcade)
+    flags = get_options("training", preset="lab", argv=["--env_type", "arcade", "--env_name", args.arcade])
+    net = UnrealModel(Environment.get_action_size("arcade", args.arcade), 0, -1, flags.use_lstm, flags.use_pixel_change,
+                      flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
+                      device, seed=1)
+    lr0 = log_uniform(flags.initial_alpha_low, flags.initial_alpha_high, flags.initial_alpha_log_rate)
+    applier = RMSPropApplier(None, decay=flags.rmsp_alpha, momentum=0.0, epsilon=flags.rmsp_epsilon,
+                             clip_norm=flags.grad_norm_clip, device=device)
+    tr = Trainer(0, net, lr0, None, applier, "arcade", args.arcade, flags.use_lstm, flags.use_pixel_change,
+                 flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
+                 flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
+                 batch_size=args.actors, seed=0xA3C, groups=args.groups)
+    tr.prepare()
+    return flags, net, tr
+
+
+flags, net, tr = build_arcade_trainer(args, device) if args.arcade else build_trainer(args, 0, 1, device)
 tr.initial_learning_rate *= args.lr_scale
 if args.entropy_beta is not None:
     tr.entropy_beta = args.entropy_beta
@@ -52,6 +80,7 @@ print(json.dumps(head), flush=True)
 if out:
     out.write(json.dumps(head) + "\n")
 global_t, t0, k = 0, time.time(), 0
+totals = tr.full_ring.actor_records[:, 10:12].sum(0).cpu() if args.arcade else None      # bricks, lives lost
 while global_t < args.steps:
     tr.process(None, global_t + k % args.log_every * args.actors * flags.n_step_TD, sync_stats=False)
     k += 1
@@ -64,10 +93,17 @@ while global_t < args.steps:
         n_live = float(live.sum().clamp(min=1))
         bump = float(((rw < 0).float() * live).sum()) / n_live
         goal = float(((rw > 0).float() * live).sum()) / n_live
+        extra = {}
+        if args.arcade:
+            now = tr.full_ring.actor_records[:, 10:12].sum(0).cpu()
+            d = (now - totals).tolist()
+            totals = now
+            extra = {"bricks_per_episode": round(d[0] / episodes, 3) if episodes else None,
+                     "lives_lost_per_episode": round(d[1] / episodes, 3) if episodes else None}
         line = json.dumps({"global_t": global_t, "episodes": episodes, "bump_rate": round(bump, 5), "goal_rate": round(goal, 6),
                            "mean_return": (score_sum / episodes) if episodes else None,
                            "total_loss": round(l["total_loss"], 4), "entropy": round(l["entropy"], 4),
-                           "grad_norm": round(l["grad_norm"], 3), "steps_per_s": round(global_t / (time.time() - t0))})
+                           "grad_norm": round(l["grad_norm"], 3), "steps_per_s": round(global_t / (time.time() - t0)), **extra})
         print(line, flush=True)
         if out:
             out.write(line + "\n")

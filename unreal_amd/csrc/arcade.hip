@@ -1,0 +1,500 @@
+// Device arcade: games stepped AND rendered on the GPU, behind the ring and rollout arguments of the maze
+// entries.  One game so far: Breakout with ALE's minimal action set (0 noop, 1 fire, 2 right, 3 left), integer-only and a
+// pure function of (config block, seed, global actor, episode, actions).  The rules, the 24-word config block and the
+// 16-word per-actor record are documented with the entries in include/unreal_hip.h; tests/arcade_model.py is the host
+// model every kernel here is compared with bit for bit.
+//
+// One actor per 256-thread workgroup.  The game logic is computed by every thread from the record (uniform: scalar
+// registers).  The stored frame of s_t is always the render of the pre-step record, so the step renders the new record
+// and, in the rows where the two can differ, the old one, in registers, 16 bytes per lane at a time: the new chunk goes
+// straight to the slot the next add_frame commits, the byte-wise difference goes to LDS for the pixel-change block sums.
+// No frame is read back from HBM.
+#include "maze_common.h"
+#include "policy_row.h"
+#include "ring_step.h"
+
+namespace {
+
+constexpr int kArcadeBreakout = 1;                  // word 0 of the block
+constexpr int kArcadeRecord = 16;                   // int32 words per actor (the block has 24)
+constexpr int kMaxRows = 6, kCols = 10, kMaxBallSpeed = 4;
+constexpr int kBrickX0 = 2, kBrickW = 8, kBrickY0 = 18, kBrickH = 3;
+constexpr int kPaddleY = 78, kFieldL = 2, kFieldR = 81, kFieldTop = 6, kServeY = 40;
+// counter word 2 of a serve draw (word 3: the serve index); as far from the PhiloxDraws streams as the maze's constants
+constexpr uint32_t kArcadeServeStream = 0x41524B53u;
+constexpr uint32_t kBorder = 142u * 0x010101u, kWhite = 236u * 0x010101u, kPaddle = 200u | 72u << 8 | 72u << 16;
+
+constexpr int kChunks = FRAME_BYTES / 16;                 // 1323 uint4 per frame
+constexpr int kChunksPerThread = (kChunks + 255) / 256;   // 6
+constexpr int kRowDw = FRAME_ROW_BYTES / 4;               // 63 dwords per frame row
+constexpr float kPcDenom = 48.f * 255.f;                  // 4 x 4 x 3 bytes at 1/255
+
+// private copies of maze.hip's pure helpers (maze.hip is not touched: its kernels keep their register numbers)
+__device__ __forceinline__ uint32_t absdiff_u8x4(uint32_t a, uint32_t b) {
+  uint32_t r = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int d = (int)((a >> (8 * e)) & 255u) - (int)((b >> (8 * e)) & 255u);
+    r |= (uint32_t)abs(d) << (8 * e);
+  }
+  return r;
+}
+
+__device__ __forceinline__ int bytesum(uint32_t x) {
+  return (int)(x & 255u) + (int)((x >> 8) & 255u) + (int)((x >> 16) & 255u) + (int)(x >> 24);
+}
+
+// The arguments of every arcade kernel: the ring / rollout / policy fields the helpers of ring_step.h name, then the tail.
+struct ArcadeArgs {
+  int B, H1;
+  const int* actions;
+  const int* active;
+  int* last_action;
+  float* last_reward;
+  int* count;
+  uint8_t* frames;
+  float* r_reward;
+  int* r_action;
+  int* r_terminal;
+  int* r_last_action;
+  float* r_last_reward;
+  float* r_pc;
+  float* out_reward;
+  int* out_terminal;
+  float* episode_reward;
+  float* score_out;
+  int* score_valid;
+  int reset_on_terminal;
+  int track_score;
+  int* active_rw;
+  int* active_log_t;
+  int* n_steps;
+  int* terminal_end;
+  int* next_idx;
+  float* next_lar;
+  int lar_ld, lar_col0, A;
+  int idx_base;
+  const float* pol_x; int pol_ldx;
+  const float* Wp; const float* bp; const float* Wv; const float* bv;
+  const double* pol_u;
+  float* pi_out; float* v_out; int* act_out;
+  // the arcade tail
+  const int* cfg;        // the 24-word block
+  int actor_base;        // global index of actor 0 of this launch (serve draws are keyed by it)
+  int* ep_steps;         // [B] steps taken in the running episode
+  int* episode;          // [B] episode index (-1 before the first reset)
+  int* records;          // [B][16] per-actor records
+  const int* mask;       // reset only (nullable): the actors to reset
+};
+
+// the block's settings, clamped to what the loops and the colour table below are built for (ArcadeConfig checks them)
+struct Rules {
+  int rows, max_steps, w, paddle_speed, ball_speed, lives, serve_wait, life_reward;
+  uint64_t seed;
+  const int* row_reward;
+};
+
+__device__ __forceinline__ Rules load_rules(const int* cfg) {
+  Rules r;
+  r.rows = min(max(cfg[2], 1), kMaxRows);
+  r.max_steps = cfg[3];
+  r.seed = (uint64_t)(uint32_t)cfg[4] | ((uint64_t)(uint32_t)cfg[5] << 32);
+  r.w = cfg[6];
+  r.paddle_speed = cfg[7];
+  r.ball_speed = min(cfg[8], kMaxBallSpeed);
+  r.lives = cfg[9];
+  r.serve_wait = cfg[10];
+  r.life_reward = cfg[11];
+  r.row_reward = cfg + 12;
+  return r;
+}
+
+struct Game {
+  int px, bx, by, vx, vy, wait, lives;
+  uint64_t bricks;        // bit 10 r + c: brick (r, c) is live
+  int serve;              // serves of the running episode
+  int n_bricks, n_lost, n_cleared;     // running totals, never zeroed
+};
+
+__device__ __forceinline__ Game load_game(const int* rec) {
+  Game g;
+  g.px = rec[0]; g.bx = rec[1]; g.by = rec[2]; g.vx = rec[3]; g.vy = rec[4]; g.wait = rec[5]; g.lives = rec[6];
+  g.bricks = (uint64_t)(uint32_t)rec[7] | ((uint64_t)(uint32_t)rec[8] << 32);
+  g.serve = rec[9]; g.n_bricks = rec[10]; g.n_lost = rec[11]; g.n_cleared = rec[12];
+  return g;
+}
+
+__device__ __forceinline__ void store_game(int* rec, const Game& g) {
+  rec[0] = g.px; rec[1] = g.bx; rec[2] = g.by; rec[3] = g.vx; rec[4] = g.vy; rec[5] = g.wait; rec[6] = g.lives;
+  rec[7] = (int)(uint32_t)g.bricks; rec[8] = (int)(uint32_t)(g.bricks >> 32);
+  rec[9] = g.serve; rec[10] = g.n_bricks; rec[11] = g.n_lost; rec[12] = g.n_cleared;
+  rec[13] = 0; rec[14] = 0; rec[15] = 0;
+}
+
+// the first state of an episode: full wall, all lives, paddle in the middle, the ball waiting; the totals run on
+__device__ __forceinline__ Game reset_game(const Rules& r, const Game& old) {
+  Game g = old;
+  g.px = 42 - r.w / 2; g.bx = 0; g.by = 0; g.vx = 0; g.vy = 0; g.wait = 0; g.lives = r.lives;
+  g.bricks = (1ull << (kCols * r.rows)) - 1;
+  g.serve = 0;
+  return g;
+}
+
+// the live brick with the lowest bit that the 2 x 2 box at (x, y) overlaps, or -1
+__device__ __forceinline__ int brick_hit(uint64_t bricks, int rows, int x, int y) {
+  int best = -1;
+#pragma unroll
+  for (int dy = 1; dy >= 0; --dy)
+#pragma unroll
+    for (int dx = 1; dx >= 0; --dx) {
+      const int xx = x + dx, yy = y + dy;
+      if (xx < kBrickX0 || xx > kFieldR || yy < kBrickY0 || yy >= kBrickY0 + kBrickH * rows) continue;
+      const int bit = kCols * ((yy - kBrickY0) / kBrickH) + (xx - kBrickX0) / kBrickW;
+      if ((bricks >> bit) & 1ull) best = bit;           // (visited from the highest bit down: the lowest stays)
+    }
+  return best;
+}
+
+// clears brick `bit`; -> its row's reward
+__device__ __forceinline__ int take_brick(Game& g, const Rules& r, int bit) {
+  g.bricks &= ~(1ull << bit);
+  g.n_bricks += 1;
+  if (g.bricks == 0) g.n_cleared += 1;
+  return r.row_reward[min(bit / kCols, kMaxRows - 1)];
+}
+
+// One step of global actor `actor` in episode `ep` (rules 1..3 of the header); -> the step's reward.
+__device__ __forceinline__ int step_game(Game& g, const Rules& r, int a, int actor, int ep) {
+  int reward = 0;
+  if (a == 2) g.px = min(g.px + r.paddle_speed, 82 - r.w);
+  if (a == 3) g.px = max(g.px - r.paddle_speed, kFieldL);
+  if (g.wait >= 0) {
+    if (a == 1 || (r.serve_wait > 0 && g.wait >= r.serve_wait)) {
+      uint32_t u[4];
+      philox4x32_10(r.seed, (uint64_t)(uint32_t)actor | ((uint64_t)(uint32_t)ep << 32),
+                    (uint64_t)kArcadeServeStream | ((uint64_t)(uint32_t)g.serve << 32), u);
+      g.bx = kFieldL + 2 * (int)(u[0] % 39u);
+      g.by = kServeY;
+      g.vx = (u[1] & 1u) ? 1 : -1;
+      g.vy = 1;
+      g.wait = -1;
+      g.serve += 1;
+    } else {
+      g.wait += 1;
+    }
+    return reward;
+  }
+  for (int m = 0; m < r.ball_speed; ++m) {
+    // x move
+    const int tx = g.bx + g.vx;
+    if (tx < kFieldL || tx + 1 > kFieldR) {
+      g.vx = -g.vx;
+    } else {
+      const int bit = brick_hit(g.bricks, r.rows, tx, g.by);
+      if (bit >= 0) { reward += take_brick(g, r, bit); g.vx = -g.vx; }
+      else g.bx = tx;
+    }
+    // y move
+    const int ty = g.by + g.vy;
+    bool lost = false;
+    if (ty < kFieldTop) {
+      g.vy = 1;
+    } else {
+      const int bit = brick_hit(g.bricks, r.rows, g.bx, ty);
+      if (bit >= 0) {
+        reward += take_brick(g, r, bit);
+        g.vy = -g.vy;
+      } else if (g.vy > 0 && ty + 1 == kPaddleY && g.bx + 1 >= g.px && g.bx <= g.px + r.w - 1) {
+        const int d = (g.bx + 1) - (g.px + r.w / 2);
+        g.vy = -1;
+        g.vx = 4 * d < -r.w ? -2 : d < 0 ? -1 : 4 * d < r.w ? 1 : 2;
+      } else if (ty + 1 > 83) {
+        g.lives -= 1;
+        g.n_lost += 1;
+        reward += r.life_reward;
+        g.wait = 0;
+        lost = true;
+      } else {
+        g.by = ty;
+      }
+    }
+    if (lost || g.bricks == 0) break;
+  }
+  return reward;
+}
+
+__device__ __forceinline__ bool game_over(const Game& g, const Rules& r, int steps) {
+  return g.lives <= 0 || g.bricks == 0 || steps >= r.max_steps;
+}
+
+__device__ __forceinline__ uint32_t row_colour(int r) {
+  return r == 0 ? (200u | 72u << 8 | 72u << 16) : r == 1 ? (198u | 108u << 8 | 58u << 16)
+       : r == 2 ? (180u | 122u << 8 | 48u << 16) : r == 3 ? (162u | 162u << 8 | 42u << 16)
+       : r == 4 ? (72u | 160u << 8 | 72u << 16) : (66u | 72u << 8 | 200u << 16);
+}
+
+// What row y of the state's frame can hold, from the tests on y alone: a dword lies in one row, so they are made once per
+// dword and a pixel costs only its tests on x.
+struct Row {
+  bool ball, paddle, brick, life, top;
+  int shift;              // bit of the row's first brick
+  uint32_t colour;        // of the row's bricks
+};
+
+__device__ __forceinline__ Row frame_row(const Game& g, const Rules& r, int y) {
+  Row row;
+  row.ball = g.wait < 0 && (unsigned)(y - g.by) < 2u;
+  row.paddle = (unsigned)(y - kPaddleY) < 2u;
+  row.brick = y >= kBrickY0 && y < kBrickY0 + kBrickH * r.rows;
+  const int br = row.brick ? (y - kBrickY0) / kBrickH : 0;
+  row.shift = kCols * br;
+  row.colour = row_colour(br);
+  row.life = (unsigned)(y - 2) < 2u;
+  row.top = y < kFieldTop;
+  return row;
+}
+
+// pixel x of that row as r | g << 8 | b << 16: front to back ball, paddle, bricks, lives, border
+__device__ __forceinline__ uint32_t pixel(const Game& g, const Rules& r, const Row& row, int x) {
+  if (row.ball && (unsigned)(x - g.bx) < 2u) return kWhite;
+  if (row.paddle && x >= g.px && x < g.px + r.w) return kPaddle;
+  if (row.brick && x >= kBrickX0 && x <= kFieldR && ((g.bricks >> (row.shift + (x - kBrickX0) / kBrickW)) & 1ull))
+    return row.colour;
+  if (row.life && x >= 4 && x < 4 + 4 * g.lives && ((x - 4) & 3) < 2) return kWhite;
+  if (row.top || x < kFieldL || x > kFieldR) return kBorder;
+  return 0u;
+}
+
+// dword `dw` of the frame: bytes 4 w .. 4 w + 3 of row y lie in pixels x0 and x0 + 1 (from channel c0 of the first)
+__device__ __forceinline__ uint32_t frame_dword(const Game& g, const Rules& r, int dw) {
+  const int y = dw / kRowDw, w = dw - kRowDw * y;
+  const int x0 = (4 * w) / 3, c0 = 4 * w - 3 * x0;
+  const Row row = frame_row(g, r, y);
+  const uint32_t a = pixel(g, r, row, x0), b = pixel(g, r, row, x0 + 1);
+  return (a >> (8 * c0)) | (b << (8 * (3 - c0)));
+}
+
+// The rows in which the frames of two states of one actor can differ: the ball's rows in either, the paddle's if it
+// moved, the brick rows if a brick went, the lives' if one was lost.  Nothing else of a record is drawn.
+struct Dirty {
+  int ball0, ball1;       // first ball row of either state (-8: not drawn)
+  bool paddle, bricks, lives;
+  int brick_end;
+};
+
+__device__ __forceinline__ Dirty frame_dirty(const Game& a, const Game& b, const Rules& r) {
+  return {a.wait < 0 ? a.by : -8, b.wait < 0 ? b.by : -8, a.px != b.px, a.bricks != b.bricks, a.lives != b.lives,
+          kBrickY0 + kBrickH * r.rows};
+}
+
+__device__ __forceinline__ bool row_differs(const Dirty& d, int y) {
+  return (unsigned)(y - d.ball0) < 2u || (unsigned)(y - d.ball1) < 2u || (d.paddle && (unsigned)(y - kPaddleY) < 2u) ||
+         (d.bricks && y >= kBrickY0 && y < d.brick_end) || (d.lives && (unsigned)(y - 2) < 2u);
+}
+
+// |new - old| of dword `dw`, given the new state's dword: the old state is rendered only in rows that can differ
+__device__ __forceinline__ uint32_t diff_dword(const Game& old, const Rules& r, const Dirty& d, int dw, uint32_t v) {
+  return row_differs(d, dw / kRowDw) ? absdiff_u8x4(v, frame_dword(old, r, dw)) : 0u;
+}
+
+__device__ __forceinline__ uint4 frame_chunk(const Game& g, const Rules& r, int c) {
+  return make_uint4(frame_dword(g, r, 4 * c), frame_dword(g, r, 4 * c + 1), frame_dword(g, r, 4 * c + 2),
+                    frame_dword(g, r, 4 * c + 3));
+}
+
+__device__ __forceinline__ void store_frame(uint8_t* dst, const Game& g, const Rules& r) {
+  uint4* d4 = reinterpret_cast<uint4*>(dst);
+  for (int c = threadIdx.x; c < kChunks; c += 256) d4[c] = frame_chunk(g, r, c);
+}
+
+__global__ __launch_bounds__(256) void arcade_step_kernel(ArcadeArgs p) {
+  const int* cfg = p.cfg;
+  if (cfg[0] != kArcadeBreakout) return;        // (uniform) a block of another game: nothing is written
+  __shared__ uint4 diff[kChunks];               // |s_{t+1} - s_t|, byte-wise
+  __shared__ int s_act;
+  const int b = blockIdx.x;
+  const int H1 = p.H1;
+  if (p.pol_x && threadIdx.x < 64) {            // the policy of this actor on wave 0 (for idle actors too, as unreal_policy_step)
+    const int act = policy_row<4>(p.pol_x + (size_t)b * p.pol_ldx, p.Wp, p.bp, p.Wv, p.bv, p.pol_u + b,
+                                  p.pi_out + (size_t)b * 4, p.v_out + b, threadIdx.x);
+    if (threadIdx.x == 0) { s_act = act; p.act_out[b] = act; }
+  }
+  const int cnt = p.count[b];
+  const int slot = cnt % H1;
+  const int act_flag = p.active_rw ? p.active_rw[b] : (p.active ? p.active[b] : 1);
+  const int la = p.last_action[b];
+  const float lr = p.last_reward[b];
+  if (!act_flag) {
+    if (threadIdx.x == 0) rollout_idle(p, b, slot, la, lr);
+    return;
+  }
+  const Rules rules = load_rules(cfg);
+  int* rec = p.records + (size_t)kArcadeRecord * b;
+  const Game old = load_game(rec);
+  const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
+  const int steps = p.ep_steps[b] + 1;
+  const int epi = p.episode[b];
+  const int ns = p.active_rw ? p.n_steps[b] : 0;
+  const float ep = p.track_score ? p.episode_reward[b] : 0.f;
+  __syncthreads();                              // the drawn action is in LDS; every thread has read the record
+  const int a = p.pol_x ? s_act : p.actions[b];
+
+  Game g = old;
+  const float reward = (float)step_game(g, rules, a, p.actor_base + b, epi);
+  const bool terminal = game_over(g, rules, steps);
+  const RingStep ring = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
+  uint8_t* dst = p.frames + ((size_t)b * H1 + ring.nslot) * FRAME_BYTES;
+
+  // s_{t+1} and, in the rows where it can differ, s_t, 16 bytes per lane: the new chunk is stored unless the episode
+  // restarts, the difference goes to LDS
+  const Dirty dirty = frame_dirty(old, g, rules);
+#pragma unroll 1
+  for (int k = 0; k < kChunksPerThread; ++k) {
+    const int c = threadIdx.x + 256 * k;
+    if (c < kChunks) {
+      const uint4 v = frame_chunk(g, rules, c);
+      if (!ring.reset) reinterpret_cast<uint4*>(dst)[c] = v;
+      diff[c] = make_uint4(diff_dword(old, rules, dirty, 4 * c, v.x), diff_dword(old, rules, dirty, 4 * c + 1, v.y),
+                           diff_dword(old, rules, dirty, 4 * c + 2, v.z), diff_dword(old, rules, dirty, 4 * c + 3, v.w));
+    }
+  }
+  __syncthreads();
+  // pixel change: cell (i, j) sums rows 4i+2..4i+5, bytes 12j+6..12j+17 of the difference (the [2:-2] crop, 4 x 4 blocks)
+  {
+    const uint32_t* d32 = reinterpret_cast<const uint32_t*>(diff);
+    for (int c = threadIdx.x; c < PC_CELLS; c += 256) {
+      const int i = c / 20, j = c - 20 * i;
+      int sum = 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t* q = d32 + (4 * i + 2 + r) * kRowDw + 3 * j + 1;
+        sum += bytesum(q[0] >> 16) + bytesum(q[1]) + bytesum(q[2]) + bytesum(q[3] & 0xFFFFu);
+      }
+      p.r_pc[ring.base * PC_CELLS + c] = (float)sum / kPcDenom;
+    }
+  }
+  if (ring.reset) {                             // (uniform) the next episode's first observation goes into the slot instead
+    g = reset_game(rules, g);
+    store_frame(dst, g, rules);
+  }
+  if (threadIdx.x == 0) {
+    ring_commit(p, b, ring, a, reward, reward, la, lr, ep);
+    store_game(rec, g);
+    p.ep_steps[b] = ring.reset ? 0 : steps;
+    p.episode[b] = epi + (ring.reset ? 1 : 0);
+    rollout_commit(p, b, ring, ns, a, reward);
+  }
+}
+
+__global__ __launch_bounds__(256) void arcade_reset_kernel(ArcadeArgs p) {
+  const int* cfg = p.cfg;
+  if (cfg[0] != kArcadeBreakout) return;        // (uniform) as in the step
+  const int b = blockIdx.x;
+  if (p.mask && !p.mask[b]) return;
+  const Rules rules = load_rules(cfg);
+  int* rec = p.records + (size_t)kArcadeRecord * b;
+  const Game old = load_game(rec);
+  const int epi = p.episode[b];
+  __syncthreads();                              // every thread has read the record
+  const Game g = reset_game(rules, old);
+  store_frame(p.frames + ((size_t)b * p.H1 + p.count[b] % p.H1) * FRAME_BYTES, g, rules);
+  if (threadIdx.x == 0) {
+    store_game(rec, g);
+    p.ep_steps[b] = 0;
+    p.episode[b] = epi + 1;
+    p.last_action[b] = 0;
+    p.last_reward[b] = 0.f;
+  }
+}
+
+// ---- host side: one check and one launcher for the four entries -------------------------------------------------------
+enum ArcadeEntry { kReset, kStep, kRollout, kPolicy };
+
+// Every pointer the kernels of the entry write through or read is non-null, frames are 16-byte aligned (16 B per lane),
+// and the game has four actions.  (The block lives in device memory: its words are checked by the kernels.)
+bool arcade_args_ok(ArcadeEntry e, const ArcadeArgs& p) {
+  if (p.B <= 0 || p.H1 < 2 || !p.last_action || !p.last_reward || !p.count || !p.frames) return false;
+  if ((uintptr_t)p.frames & 15) return false;
+  if (!p.cfg || ((uintptr_t)p.cfg & 3) || p.actor_base < 0 || !p.ep_steps || !p.episode || !p.records) return false;
+  if (e == kReset) return true;
+  if (!p.r_reward || !p.r_action || !p.r_terminal || !p.r_last_action || !p.r_last_reward || !p.r_pc) return false;
+  if (p.track_score && (!p.episode_reward || !p.score_out || !p.score_valid)) return false;
+  if (e != kPolicy && !p.actions) return false;
+  if (e == kStep) return true;
+  if (!p.active_rw || !p.active_log_t || !p.n_steps || !p.terminal_end || p.idx_base < 0) return false;
+  if (p.A != 4) return false;                   // Breakout's minimal action set
+  if (p.next_lar && (p.lar_col0 < 0 || p.lar_ld < p.lar_col0 + p.A + 1)) return false;
+  if (e == kRollout) return true;
+  return p.pol_x && p.pol_ldx >= LSTM_N && p.Wp && p.bp && p.Wv && p.bv && p.pol_u && p.pi_out && p.v_out && p.act_out;
+}
+
+// fills in the tail, checks and launches (one launch shape: no label is recorded)
+int arcade_launch(ArcadeEntry e, ArcadeArgs& p, const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
+                  void* stream) {
+  p.cfg = cfg; p.actor_base = actor_base; p.ep_steps = ep_steps; p.episode = episode; p.records = records;
+  if (!arcade_args_ok(e, p)) return UNREAL_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (e == kReset) hipLaunchKernelGGL(arcade_reset_kernel, dim3(p.B), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(arcade_step_kernel, dim3(p.B), dim3(256), 0, s, p);
+  return unreal_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+// `pos` is the maze's argument of that name: the arcade keeps its state in `records` and never touches it (nullable).
+
+int unreal_arcade_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward, const int* count,
+                        uint8_t* frames, const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
+                        void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, const_cast<int*>(count), frames};
+  p.mask = mask;
+  return arcade_launch(kReset, p, cfg, actor_base, ep_steps, episode, records, stream);
+}
+
+int unreal_arcade_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
+                       float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                       int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                       float* episode_reward, float* score_out, int* score_valid, int reset_on_terminal, int track_score,
+                       const int* cfg, int actor_base, int* ep_steps, int* episode, int* records, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid,
+               reset_on_terminal, track_score};
+  return arcade_launch(kStep, p, cfg, actor_base, ep_steps, episode, records, stream);
+}
+
+int unreal_arcade_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                               int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                               int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                               int* out_terminal, float* episode_reward, float* score_out, int* score_valid, int* active,
+                               int* active_log_t, int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
+                               int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg, int actor_base,
+                               int* ep_steps, int* episode, int* records, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
+  return arcade_launch(kRollout, p, cfg, actor_base, ep_steps, episode, records, stream);
+}
+
+int unreal_arcade_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                      const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                      int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
+                                      uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                      int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                      int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                      int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                      float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                      int actor_base, int* ep_steps, int* episode, int* records, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
+               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
+  return arcade_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, stream);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 """Environment factory with the reference's surface (/root/reference/environment/environment.py:11-102).
 
-Only the maze is a device environment; lab / indoor actors are HOST-FED (hostfed_environment.py) by simulator objects
+The maze and the arcade (arcade_environment.py: Breakout) are device environments; lab / indoor actors are HOST-FED (hostfed_environment.py) by simulator objects
 the caller supplies, because deepmind_lab / minos / gym are not in the image.  Gym actors are host-fed through
 gym_environment.GymBatchSimulator (any object with gym's reset / step API)."""
 
@@ -15,6 +15,8 @@ class Environment(object):
     GYM_CONFIG = {}
     # env_name -> maze_environment.MazeConfig: user mazes on the device (an unregistered name is the reference's map)
     MAZE_CONFIG = {}
+    # env_name -> arcade_environment.ArcadeConfig: arcade games stepped and rendered on the device
+    ARCADE_CONFIG = {}
 
     @staticmethod
     def register_indoor_config(env_name, objective_size, height=84, width=84):
@@ -75,10 +77,33 @@ class Environment(object):
                                                        pickups, gen_pickups, no_goal)
 
     @staticmethod
+    def register_arcade_config(env_name, game="breakout", rows=6, row_rewards=None, paddle_width=12, paddle_speed=3,
+                               ball_speed=2, lives=3, serve_wait=8, life_reward=0, max_episode_steps=5000):
+        """Arcade game of `env_name` on the device (env_type 'arcade').  game="breakout": ALE Breakout's
+        minimal action set (0 noop, 1 fire, 2 right, 3 left) on an 84 x 84 RGB frame.  rows in 1..6 rows of 10 bricks;
+        row_rewards: one integer in 0..100 per row from the top (None: all 1); paddle_width even in 4..24 px;
+        paddle_speed in 1..8 px per step; ball_speed in 1..4 micro-steps per step; lives in 1..5; serve_wait in 0..255:
+        a waiting ball serves itself after that many steps (0: only fire serves); life_reward in -100..0 is paid with
+        every lost life; max_episode_steps in 1..2^31 - 1 ends an episode (a looping ball would never).  An episode
+        also ends with the last life or the last brick (success).  Raises ValueError outside these ranges."""
+        from .arcade_environment import ArcadeConfig
+        Environment.ARCADE_CONFIG[env_name] = ArcadeConfig(game, rows, row_rewards, paddle_width, paddle_speed, ball_speed,
+                                                           lives, serve_wait, life_reward, max_episode_steps)
+
+    @staticmethod
+    def arcade_config(env_name):
+        if env_name not in Environment.ARCADE_CONFIG:
+            raise KeyError("arcade env %r: call Environment.register_arcade_config(name, ...) first" % env_name)
+        return Environment.ARCADE_CONFIG[env_name]
+
+    @staticmethod
     def create_environment(env_type, env_name, termination_time=50.0, env_args=None, thread_index=0):
         if env_type == 'maze':
             from . import maze_environment
             return maze_environment.MazeEnvironment(config=Environment.MAZE_CONFIG.get(env_name))
+        if env_type == 'arcade':
+            from . import arcade_environment
+            return arcade_environment.ArcadeEnvironment(config=Environment.arcade_config(env_name))
         raise NotImplementedError("env_type %r needs an external simulator that is out of scope (SURVEY 8f)" % env_type)
 
     @staticmethod
@@ -86,6 +111,8 @@ class Environment(object):
         conf = Environment.MAZE_CONFIG.get(env_name) if env_type == 'maze' else None
         if conf is not None and conf.action_set == "lab":
             return 6                             # a navigation maze with Lab's actions: the class cache is not involved
+        if env_type == 'arcade':                 # nor here: the game's own action count
+            return Environment.arcade_config(env_name).action_size
         if Environment.action_size >= 0:
             return Environment.action_size
         if env_type == 'maze':

@@ -13,7 +13,10 @@ maze without goal_respawn the result also holds `start_distance`, 
 goal of the counted episodes, and `spl`, the mean of success * d0 / max(d0, episode length in steps): every action is a
 step, turns and looks included, so an agent on the shortest path scores d0 / (d0 + its turns).  On a forage maze
  the result also holds `pickups_per_episode`, the mean number of collected pickups of kinds A, B, C, D, and on a
-no_goal maze success is an episode whose final step collected an ends_episode kind with a reward > 0."""
+no_goal maze success is an episode whose final step collected an ends_episode kind with a reward > 0.  With `arcade=` (a
+name given to Environment.register_arcade_config) the actors play that game: success is a cleared wall, every
+other ending (last life, the config's max_episode_steps) counts under `timeouts`, and the result holds
+`bricks_per_episode` and `lives_lost_per_episode` from differences of the records' running totals."""
 import torch
 
 from . import ops
@@ -24,13 +27,20 @@ from .train.trainer import PhiloxDraws
 
 class Evaluate(object):
     def __init__(self, network, batch_size=64, device="cuda:0", seed=0xE7A1, greedy=False, draws=None, simulator=None,
-                 termination_time=50.0, maze=None):
+                 termination_time=50.0, maze=None, arcade=None):
         self.net, self.B, self.greedy = network, int(batch_size), greedy
         self.device = torch.device(device)
         self.draws = draws if draws is not None else PhiloxDraws(seed)
         B, A = self.B, network._action_size
         self.maze_config = None
-        if simulator is None:
+        self.arcade_config = None
+        if simulator is None and arcade is not None:
+            from .environment.environment import Environment
+            from .environment.arcade_environment import BatchedArcadeEnvironment
+            self.arcade_config = Environment.arcade_config(arcade)
+            self.env = BatchedArcadeEnvironment(B, 2, self.device, config=self.arcade_config, seed=seed)
+            network.lar_bounded = False        # a step can pay more than 1 (Trainer.prepare)
+        elif simulator is None:
             if maze is not None:
                 from .environment.environment import Environment
                 if maze not in Environment.MAZE_CONFIG:
@@ -58,6 +68,56 @@ class Evaluate(object):
         self.u, self.actions = z(B, torch.float64), z(B, torch.int32)
         self.rewards, self.terminals = z(B, torch.float32), z(B, torch.int32)
 
+    def _step(self):
+        """One lock-step policy + environment step of the B actors (reset on terminal, scores tracked)."""
+        B, net, ws, ring = self.B, self.net, self.ws, self.env.ring
+        net.begin_pass()
+        ring.cur_idx(out=ws.frame_idx[:B])
+        net.encode_rows(ring, ws, 0, B, lar_from_ring=False, save_c1=False, lstm_x=False)
+        if net._use_lstm:
+            net.lstm_step(ws, 0, B, fused_x=True)
+        feat, ld = net.features(ws, 0)
+        if not self.greedy:
+            self.draws.uniform(self.u)
+        net.policy_step(B, feat, ld, None if self.greedy else self.u, self.pi, self.v, self.actions)
+        self.env.process(self.actions, None, self.rewards, self.terminals, reset_on_terminal=True,
+                         track_score=True)
+        if net._use_lstm:                      # carry the state; zero it where the episode ended
+            ops.copy_(ws.c0, ws.c[:B * 256])
+            ops.copy_(ws.h0, ws.h[:B * 256])
+            ops.reset_state(B, self.terminals, ws.c0, ws.h0)
+
+    def _process_arcade(self, n_episodes, one_episode_per_actor):
+        """The arcade's statistics: every episode ends in the environment (lives, wall, max_episode_steps)."""
+        B, ring = self.B, self.env.ring
+        tot = ring.actor_records[:, 10:13]     # bricks, lives lost, walls cleared: never zeroed
+        ep0 = tot.cpu().numpy().copy()
+        steps, counted = [0] * B, [False] * B
+        returns, lengths, bricks, lost, successes = [], [], [], [], 0
+        if one_episode_per_actor:
+            n_episodes = B
+        while len(returns) < n_episodes:
+            self._step()
+            term = self.terminals.cpu().numpy()
+            score = ring.score_out.cpu().numpy()
+            now = tot.cpu().numpy()
+            for b in range(B):
+                steps[b] += 1
+                if not term[b]:
+                    continue
+                if not (one_episode_per_actor and counted[b]):
+                    returns.append(float(score[b])); lengths.append(steps[b])
+                    bricks.append(int(now[b, 0] - ep0[b, 0])); lost.append(int(now[b, 1] - ep0[b, 1]))
+                    successes += int(now[b, 2] - ep0[b, 2] > 0)
+                ep0[b] = now[b]
+                steps[b] = 0; counted[b] = True
+        n = len(returns)
+        mean = sum(returns) / n
+        return dict(episodes=n, success_rate=successes / float(n), mean_return=mean,
+                    return_std=(sum((r - mean) ** 2 for r in returns) / n) ** 0.5, mean_length=sum(lengths) / float(n),
+                    timeouts=n - successes, bricks_per_episode=sum(bricks) / float(n),
+                    lives_lost_per_episode=sum(lost) / float(n))
+
     def process(self, n_episodes, max_episode_steps=2000, one_episode_per_actor=False):
         """-> dict(episodes, success_rate, mean_return, return_std, mean_length, timeouts, goals_per_episode,
         apples_per_episode[, start_distance, spl][, pickups_per_episode]).
@@ -74,6 +134,8 @@ class Evaluate(object):
         if net._use_lstm:
             ws.c0.zero_()
             ws.h0.zero_()
+        if self.arcade_config is not None:
+            return self._process_arcade(n_episodes, one_episode_per_actor)
         steps = [0] * B
         done, returns, lengths, successes, timeouts = 0, [], [], 0, 0
         cfg = self.maze_config
@@ -97,21 +159,7 @@ class Evaluate(object):
         if one_episode_per_actor:
             n_episodes = B
         while done < n_episodes:
-            net.begin_pass()
-            ring.cur_idx(out=ws.frame_idx[:B])
-            net.encode_rows(ring, ws, 0, B, lar_from_ring=False, save_c1=False, lstm_x=False)
-            if net._use_lstm:
-                net.lstm_step(ws, 0, B, fused_x=True)
-            feat, ld = net.features(ws, 0)
-            if not self.greedy:
-                self.draws.uniform(self.u)
-            net.policy_step(B, feat, ld, None if self.greedy else self.u, self.pi, self.v, self.actions)
-            self.env.process(self.actions, None, self.rewards, self.terminals, reset_on_terminal=True,
-                             track_score=True)
-            if net._use_lstm:                      # carry the state; zero it where the episode ended
-                ops.copy_(ws.c0, ws.c[:B * 256])
-                ops.copy_(ws.h0, ws.h[:B * 256])
-                ops.reset_state(B, self.terminals, ws.c0, ws.h0)
+            self._step()
             term = self.terminals.cpu().numpy()
             rew = self.rewards.cpu().numpy()
             score = ring.score_out.cpu().numpy()

@@ -98,7 +98,7 @@ class Ring(object):
     """Device replay ring + per-actor environment state (layout: include/unreal_hip.h)."""
 
     def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False, nav=False, gen=0,
-                 gen_styled=False, sense=0):
+                 gen_styled=False, sense=0, arcade=False):
         self.B, self.H, self.H1 = B, H, H + 1
         self.objective_size = objective_size
         self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
@@ -149,6 +149,13 @@ class Ring(object):
             self.nav = None
             self.heading = self.gen.view(B, -1)[:, 0]
 
+        # device arcade (environment/arcade_environment.ArcadeConfig): steps of the running episode, episode
+        # index (-1 before the first reset) and the [B, ARCADE_RECORD] game records
+        self.arcade = z(B * ARCADE_RECORD, dt=torch.int32) if arcade else None
+        if arcade:
+            self.ep_steps = z(B, dt=torch.int32)
+            self.episode = torch.full((B,), -1, dtype=torch.int32, device=device)
+
         self._cur = z(B, dt=torch.int32)
 
     @property
@@ -156,6 +163,8 @@ class Ring(object):
         """[B, words] view of the per-actor records of a navigation or generated maze (words 3, 4: goals_total,
         apples_total), or None."""
         gen, nav = getattr(self, "gen", None), getattr(self, "nav", None)
+        if getattr(self, "arcade", None) is not None:        # a device arcade's game records (words 10..12: the totals)
+            return self.arcade.view(self.B, ARCADE_RECORD)
         if gen is not None:
             return gen.view(self.B, -1)
         return nav.view(self.B, -1) if nav is not None else None
@@ -163,6 +172,8 @@ class Ring(object):
     @property
     def record_words(self):
         """int32 words of one actor's record (0: the maze keeps none)."""
+        if getattr(self, "arcade", None) is not None:
+            return ARCADE_RECORD
         if getattr(self, "gen", None) is not None:
             return self.gen_words
         return getattr(self, "nav_words", NAV_RECORD) if getattr(self, "nav", None) is not None else 0
@@ -201,9 +212,13 @@ def ring_view(ring, b0, b1):
     v.gen_n, gen = getattr(ring, "gen_n", 0), getattr(ring, "gen", None)
     v.gen_words = getattr(ring, "gen_words", gen_record_words(v.gen_n))
     v.gen = gen[b0 * v.gen_words:b1 * v.gen_words] if gen is not None else None
+    arcade = getattr(ring, "arcade", None)
+    v.arcade = arcade[b0 * ARCADE_RECORD:b1 * ARCADE_RECORD] if arcade is not None else None
     return v
 
 
+ARCADE_BREAKOUT, ARCADE_CFG_WORDS, ARCADE_RECORD = 1, 24, 16   # UNREAL_ARCADE_BREAKOUT / _CFG_WORDS / _RECORD
+ARCADE_SERVE_STREAM = 0x41524B53             # counter word 2 of a serve draw (UNREAL_ARCADE_SERVE_STREAM)
 MAZE_TOP_DOWN, MAZE_FIRST_PERSON = 0, 1       # the `view` of a maze (UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON)
 MAZE_FIRST_PERSON_GENERATED = 2               # first person, a generated block (UNREAL_MAZE_FIRST_PERSON_GENERATED)
 # goal-sense blocks: UNREAL_MAZE_FIRST_PERSON_SENSE / UNREAL_MAZE_FIRST_PERSON_GENERATED_SENSE
@@ -348,6 +363,69 @@ def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, act
           ptr(pi_out), ptr(v_out), ptr(actions),
           *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
                          lar_ld, lar_col0, A, base_actor), *_maze_args(ring, maze))
+
+
+# ---- device arcade (csrc/arcade.hip) -----------------------------------------------------------------------
+def _arcade_args(ring, arcade):
+    """The tail of every arcade entry.  `arcade` = (int32 config block on the device, global index of the ring's actor 0)."""
+    block, actor_base = arcade
+    _chk(block, "i32", ARCADE_CFG_WORDS, "arcade config")
+    if getattr(ring, "arcade", None) is None:
+        raise ValueError("an arcade environment needs a ring with game records (Ring(arcade=True))")
+    for name, n in (("ep_steps", ring.B), ("episode", ring.B), ("arcade", ARCADE_RECORD * ring.B)):
+        _chk(getattr(ring, name), "i32", n, "ring." + name)
+    if actor_base < 0:
+        raise ValueError("actor_base %d < 0" % actor_base)
+    return (ptr(block), int(actor_base), ptr(ring.ep_steps), ptr(ring.episode), ptr(ring.arcade))
+
+
+def arcade_reset(ring, mask=None, arcade=None):
+    """Start a new episode of every actor (where mask != 0)."""
+    _chk(mask, "i32", ring.B, "mask", optional=True)
+    _call("unreal_arcade_reset", ring.B, ring.H1, ptr(mask), ptr(ring.pos), ptr(ring.last_action), ptr(ring.last_reward),
+          ptr(ring.count), ptr(ring.frames), *_arcade_args(ring, arcade))
+
+
+def arcade_step(ring, actions, active=None, out_reward=None, out_terminal=None, reset_on_terminal=True,
+                track_score=False, arcade=None):
+    B = ring.B
+    _chk(actions, "i32", B, "actions")
+    _chk(active, "i32", B, "active", optional=True)
+    _chk(out_reward, "f32", B, "out_reward", optional=True)
+    _chk(out_terminal, "i32", B, "out_terminal", optional=True)
+    _call("unreal_arcade_step", B, ring.H1, ptr(actions), ptr(active), *_ring_args(ring, out_reward, out_terminal),
+          int(reset_on_terminal), int(track_score), *_arcade_args(ring, arcade))
+
+
+def _arcade_actions(A):
+    if A != 4:
+        raise ValueError("the arcade has 4 actions; A = %r" % (A,))
+
+
+def arcade_rollout_step(ring, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
+                        next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=4, base_actor=0, arcade=None):
+    """arcade_step + rollout_advance (+ cur_idx and lar_fill for the NEXT step's rows) in one launch, as
+    maze_rollout_step."""
+    _arcade_actions(A)
+    _chk(actions, "i32", ring.B, "actions")
+    _call("unreal_arcade_rollout_step", ring.B, ring.H1, ptr(actions),
+          *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
+                         lar_ld, lar_col0, A, base_actor), *_arcade_args(ring, arcade))
+
+
+def arcade_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions, out_reward, out_terminal, active,
+                               active_log_t, n_steps, terminal_end, next_idx=None, next_lar=None, lar_ld=0, lar_col0=0,
+                               A=4, base_actor=0, arcade=None):
+    """policy_step + arcade_rollout_step in one launch (bit-identical to the two launches)."""
+    B = ring.B
+    _arcade_actions(A)
+    _chk(X, "f32", (B - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A); _chk(bp, "f32", A); _chk(Wv, "f32", 256)
+    _chk(bv, "f32", 1); _chk(u, "f64", B, "u"); _chk(pi_out, "f32", B * A); _chk(v_out, "f32", B)
+    _chk(actions, "i32", B, "actions")
+    _call("unreal_arcade_policy_rollout_step", B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(u),
+          ptr(pi_out), ptr(v_out), ptr(actions),
+          *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
+                         lar_ld, lar_col0, A, base_actor), *_arcade_args(ring, arcade))
 
 
 def maze_objective(ring, next_lar=None, lar_ld=0, lar_col0=0):

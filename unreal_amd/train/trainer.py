@@ -76,9 +76,11 @@ class Trainer(object):
                  image_shape=(84, 84), is_training=True, n_classes=0, random_state=None, termination_time=50.0,
                  segnet_lambda=1.0, dropout=0.0, batch_size=1, world_size=1, rank=0, seed=0xA3C, draws=None,
                  grad_sync=None, simulator=None, groups=1, overlap_host=None):
-        if env_type != "maze" and simulator is None:
-            raise NotImplementedError("env_type=%r needs a host simulator object (simulator=...); only 'maze' runs "
-                                      "entirely on the device" % env_type)
+        # device environments: stepped and rendered by kernels (no simulator, sub-ranges of actors, fused rollout step)
+        self.device_env = env_type in ("maze", "arcade")
+        if not self.device_env and simulator is None:
+            raise NotImplementedError("env_type=%r needs a host simulator object (simulator=...); only 'maze' and "
+                                      "'arcade' run entirely on the device" % env_type)
         self.simulator = simulator
         # host-fed actors: alternate two half-batches between the host (simulators, staging) and the device.  None = on
         # from 2048 actors: measured with a cost-free simulator the halves win 1.22x at 4096 actors (654 k vs 537 k
@@ -119,8 +121,9 @@ class Trainer(object):
         self.groups = int(groups)                    # sequential updates per process() call
         if self.groups < 1 or self.B % self.groups:
             raise ValueError("groups=%d must divide batch_size=%d" % (self.groups, self.B))
-        if self.groups > 1 and env_type != "maze":
-            raise NotImplementedError("groups > 1 needs an environment that steps a sub-range of its actors (maze)")
+        if self.groups > 1 and not self.device_env:
+            raise NotImplementedError("groups > 1 needs an environment that steps a sub-range of its actors (maze, "
+                                      "arcade)")
         self.Bg = self.B // self.groups              # actors per group = batch of every kernel launch
         self.world_size, self.rank = int(world_size), int(rank)
         self.grad_scale = 1.0 / float(self.Bg * self.world_size)
@@ -156,6 +159,12 @@ class Trainer(object):
                                                         config=Environment.MAZE_CONFIG.get(self.env_name),
                                                         actor_base=self.rank * B, actors_total=self.world_size * B,
                                                         seed=self.seed)
+        elif self.env_type == "arcade":
+            from ..environment.arcade_environment import BatchedArcadeEnvironment
+            self.environment = BatchedArcadeEnvironment(B, self.experience_history_size, dev,
+                                                        config=Environment.arcade_config(self.env_name),
+                                                        actor_base=self.rank * B, actors_total=self.world_size * B,
+                                                        seed=self.seed)
         else:
             from ..environment.hostfed_environment import HostFedEnvironment
             indoor = self.env_type == "indoor"
@@ -176,7 +185,7 @@ class Trainer(object):
                                                   raw_frame_shape=self.simulator.frame_shape if gym else None,
                                                   frame_shape=self.image_shape if indoor else None)
         self.overlap_host = False
-        if self.env_type != "maze":
+        if not self.device_env:
             want = self._overlap_request if self._overlap_request is not None else (B % 2 == 0 and B >= 2048)
             if want:
                 self.environment.enable_parts(2)
@@ -186,7 +195,8 @@ class Trainer(object):
         self.local_network.bind_frame_scale(self.environment.frame_scale)
         # [last action | last reward] columns of the LSTM input: within 1 for the maze (rewards -1 / 0 / +1); host-fed
         # actors feed raw rewards and measurement vectors, whose maximum is reduced per pass (model.encode_rows)
-        # (navigation mazes with a reward beyond 1 feed it raw too: experience.py, unclipped)
+        # (navigation mazes with a reward beyond 1 feed it raw too: experience.py, unclipped; so does the arcade, where a
+        # step can pay more than 1)
         conf = Environment.MAZE_CONFIG.get(self.env_name) if self.env_type == "maze" else None
         self.local_network.lar_bounded = self.env_type == "maze" and (conf is None or conf.reward_bound <= 1)
         self.experience = Experience(self.experience_history_size, ring=self.full_ring)
@@ -302,7 +312,7 @@ class Trainer(object):
         # (a goal-sense maze's step has also written the objective columns: no objective_fill launch at t > 0)
         net.encode_rows(self.ring, ws, t * B, B, lar_from_ring=False, save_c1=ws.c1 is not None,
                         lar_prefilled=prefilled and self.use_lstm, lstm_x=False,
-                        objective_prefilled=prefilled and self.use_lstm and self.env_type == "maze")
+                        objective_prefilled=prefilled and self.use_lstm and self.device_env)
         if self.use_lstm:
             net.lstm_step(ws, t, B, fused_x=True)
         feat, ld = net.features(ws, t * B)
@@ -411,7 +421,7 @@ class Trainer(object):
         """Per group: the halves' environment views, streams and running absmax slot pairs (built once)."""
         n_parts = self.rollout_parts_default
         self._split = None
-        if self.env_type != "maze" or n_parts < 2 or self.Bg % n_parts or self.Bg < self.ROLLOUT_SPLIT_MIN_ACTORS:
+        if not self.device_env or n_parts < 2 or self.Bg % n_parts or self.Bg < self.ROLLOUT_SPLIT_MIN_ACTORS:
             return
         if self.objective_size:                # goal-sense mazes take the lock-step loop (DESIGN §7i)
             return
@@ -478,7 +488,7 @@ class Trainer(object):
         split = getattr(self, "_split", None) is not None
         if split:
             self._rollout_steps_split()
-        fused = self.env_type == "maze"      # the maze step kernel also does the loop bookkeeping and prepares step t+1
+        fused = self.device_env              # the maze / arcade step kernel also does the loop bookkeeping and prepares step t+1
         fuse_policy = fused and self.fuse_policy_env     # policy head + draw inside the environment step's launch
         for t in range(0 if not (self.overlap_host or split) else T, T):
             s = slice(t * B, (t + 1) * B)
