@@ -180,8 +180,9 @@ int unreal_maze_objective(int B, int H1, const int* count, const int* records, i
  * nullable) and commit through the same helpers; the maze tail is replaced by (cfg, actor_base, ep_steps[B], episode[B],
  * records[B][UNREAL_ARCADE_RECORD]).  There is one launch shape and no launch label.
  *
- * cfg: UNREAL_ARCADE_CFG_WORDS int32 words.  [0] game id (UNREAL_ARCADE_BREAKOUT; a kernel that reads another id writes
- * nothing)  [1] 0  [2] rows 1..6  [3] max_episode_steps >= 1  [4..5] seed (lo, hi)  [6] paddle_width (even, 4..24)
+ * cfg: UNREAL_ARCADE_CFG_WORDS int32 words; word 0 is the game id, which the kernels read from the block (uniform):
+ * UNREAL_ARCADE_BREAKOUT or UNREAL_ARCADE_DUEL (below); a kernel that reads another id (2 included) writes nothing.
+ * Breakout's block: [0] UNREAL_ARCADE_BREAKOUT  [1] 0  [2] rows 1..6  [3] max_episode_steps >= 1  [4..5] seed (lo, hi)  [6] paddle_width (even, 4..24)
  * [7] paddle_speed 1..8  [8] ball_speed 1..4  [9] lives 1..5  [10] serve_wait 0..255 (0: only fire serves)
  * [11] life_reward -100..0  [12..17] row rewards 0..100, top row first  [18..23] 0.
  * record: [0..6] px, bx, by, vx, vy, wait (>= 0: the ball waits to be served, -1: in flight), lives  [7..8] live bricks
@@ -205,9 +206,38 @@ int unreal_maze_objective(int B, int H1, const int* count, const int* records, i
  *  4. terminal: lives <= 0, no live brick, or steps >= max_episode_steps.  With reset_on_terminal the next episode starts
  *     (episode += 1, full wall, all lives, px = 42 - w / 2, ball waiting, wait = serve_index = steps = 0) and its first
  *     frame goes into the next slot.  The pixel change is that of the two frames before the reset, over 48 * 255.
+ *
+ * The duel (UNREAL_ARCADE_DUEL): Breakout's field, ball, serve draw and four actions, with an opponent's paddle
+ * in place of the wall.  cfg: [0] UNREAL_ARCADE_DUEL  [1] 0  [2] points 1..9  [3] max_episode_steps >= 1  [4..5] seed
+ * (lo, hi)  [6] paddle_width (even, 4..24)  [7] paddle_speed 1..8  [8] ball_speed 1..4  [9] opponent_width (even, 4..24)
+ * [10] serve_wait 0..255  [11] lose_reward -100..0  [12] win_reward 0..100  [13] opponent_speed 0..8 (0: it stands)
+ * [14..23] 0.
+ * record: [0..5] px, bx, by, vx, vy, wait  [6] ox  [7] mine  [8] theirs (the two scores)  [9] serve_index  [10] points-won
+ * total  [11] points-lost total  [12] matches-won total (the totals are never zeroed)  [13..15] 0.
+ * Frame, back to front: black; Breakout's border; score blocks on rows 2..3: the agent's k-th point (k = 0..) x 4+4k..5+4k
+ * in (236, 236, 236), the opponent's k-th x 78-4k..79-4k in (66, 72, 200), nine of each at the most; the agent's paddle
+ * y 78..79, x px..px+paddle_width-1 in (200, 72, 72); the opponent's y 8..9, x ox..ox+opponent_width-1 in (66, 72, 200);
+ * the ball as in Breakout, only in flight.  One step:
+ *  1. steps += 1; the agent's paddle as in Breakout.
+ *  2. The opponent's paddle, from the ball of the state before this step: target = bx + 1 if the ball is in flight and
+ *     vy < 0, else 42; d = target - (ox + opponent_width / 2); ox += clamp(d, -opponent_speed, +opponent_speed), then
+ *     clamped to [2, 82 - opponent_width].  It moves in every step, also while the ball waits.
+ *  3. A waiting ball is served as in Breakout (same key and counter words, bx, by = 40, vx), and vy = u[2] & 1 ? +1 : -1.
+ *  4. A ball in flight makes ball_speed micro-steps, each an x move and then a y move; a point ends them.  x: tx = bx + vx;
+ *     outside [2, 80]: vx = -vx; else bx = tx.  y: ty = by + vy, tested in this order: (a) vy > 0, ty + 1 == 78 and
+ *     [bx, bx+1] meets the agent's paddle: vy = -1 and Breakout's vx from d = bx + 1 - (px + paddle_width / 2); (b) vy < 0,
+ *     ty == 9 and [bx, bx+1] meets the opponent's: vy = +1, vx by the same rule from ox and opponent_width; (c) ty + 1 > 83:
+ *     theirs += 1, the reward gets lose_reward, wait = 0; (d) ty < 6: mine += 1, the reward gets win_reward, wait = 0;
+ *     (e) else by = ty.  A point leaves bx, by, vx, vy as they are.
+ *  5. terminal: mine >= points, theirs >= points, or steps >= max_episode_steps.  Matches-won counts the step in which
+ *     mine reaches points, once.  With reset_on_terminal the next episode starts (episode += 1, px = 42 - paddle_width / 2,
+ *     ox = 42 - opponent_width / 2, bx = by = vx = vy = wait = mine = theirs = serve_index = steps = 0).  Without it the
+ *     game goes on: the scores run past points and terminal stays set.
+ *
  * -EINVAL without a launch: B <= 0, H1 < 2, a null or misaligned pointer the entry uses (cfg included), actor_base < 0,
  * and in the rollout entries A != 4 or a next_lar row too short for A + 1 columns. */
 #define UNREAL_ARCADE_BREAKOUT 1
+#define UNREAL_ARCADE_DUEL 3
 #define UNREAL_ARCADE_CFG_WORDS 24
 #define UNREAL_ARCADE_RECORD 16
 #define UNREAL_ARCADE_SERVE_STREAM 0x41524B53

@@ -8,8 +8,10 @@
     first-person maze.
 
   python tools/bench_arcade.py [--launches 200] [--steps 10] [--warmup 3] [--history 100] [--repeat 2] [--skip-trainer]
+                               [--game breakout]
 
-Prints one JSON line per measurement."""
+`--game duel` measures the two-paddle duel on its default config instead of Breakout; its lines then also hold
+the game's name.  Prints one JSON line per measurement."""
 import argparse
 import json
 import os
@@ -96,20 +98,23 @@ def main():
     ap.add_argument("--history", type=int, default=100)
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--skip-trainer", action="store_true")
+    ap.add_argument("--game", default="breakout", choices=("breakout", "duel"))
     args = ap.parse_args()
     from unreal_amd.environment.environment import Environment
     from unreal_amd.environment.arcade_environment import BatchedArcadeEnvironment
     from unreal_amd.environment.maze_environment import batched_maze_environment
-    Environment.register_arcade_config("bench_breakout")
+    arcade = "bench_" + args.game
+    Environment.register_arcade_config(arcade, game=args.game)
+    tag = {} if args.game == "breakout" else {"game": args.game}
     kw = dict(random_start=True, random_goal=True, max_episode_steps=200)
     Environment.register_maze_config("bench_fp7", layouts(7), view="first_person", **kw)
     Environment.register_maze_config("bench_td7", layouts(7), **kw)
     for rep in range(args.repeat):
         for B in (512, 4096):
-            envs = dict(arcade=BatchedArcadeEnvironment(B, 3, DEV, config=Environment.ARCADE_CONFIG["bench_breakout"]),
+            envs = dict(arcade=BatchedArcadeEnvironment(B, 3, DEV, config=Environment.ARCADE_CONFIG[arcade]),
                         first_person=batched_maze_environment(B, 3, DEV, config=Environment.MAZE_CONFIG["bench_fp7"]),
                         top_down=batched_maze_environment(B, 3, DEV, config=Environment.MAZE_CONFIG["bench_td7"]))
-            row = dict(bench="arcade_step", B=B, repeat=rep)
+            row = dict(bench="arcade_step", B=B, repeat=rep, **tag)
             for k in range(2):                                  # the kernels in turn, twice
                 row["arcade_us_%d" % k] = round(1e3 * kernel_ms(envs["arcade"], B, args.launches, entry="unreal_arcade_step"), 2)
                 row["arcade_fused_us_%d" % k] = round(1e3 * fused_ms(envs["arcade"], B, args.launches), 2)
@@ -120,7 +125,7 @@ def main():
             torch.cuda.empty_cache()
     if not args.skip_trainer:
         for rep in range(args.repeat):
-            for name, fn in (("bench_breakout", arcade_trainer_ms), ("bench_fp7", maze_trainer_ms)):
+            for name, fn in ((arcade, arcade_trainer_ms), ("bench_fp7", maze_trainer_ms)):
                 dev_ms, wall_ms = fn(name, 4096, args.history, args.steps, args.warmup)
                 print(json.dumps(dict(bench="trainer_process", env=name, B=4096, history=args.history, repeat=rep,
                                       device_ms=round(dev_ms, 2), wall_ms=round(wall_ms, 2),

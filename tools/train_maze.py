@@ -2,11 +2,14 @@
 """Train the maze agent with the batched Trainer and log episode returns (GPU box).
 
 usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] [--steps 2e7] [--log-every 10]
-                                  [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout]
+                                  [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout|duel]
+                                  [--opponent-speed N]
 `--groups G`: G sequential updates per process() call (update density x G, see Trainer).  One JSON line per
 `--log-every` calls: global_t, episodes finished since the last line, their mean return, losses, entropy, steps/s.
 `--arcade GAME`: train on the device arcade with that game's default config instead; a line then also holds
-bricks_per_episode and lives_lost_per_episode (differences of the records' totals over the episodes of the line)."""
+bricks_per_episode and lives_lost_per_episode (differences of the records' totals over the episodes of the line); on the
+duel these are points_won_per_episode, points_lost_per_episode and matches_won_per_episode, and
+`--opponent-speed` overrides the opponent's 2 px per step."""
 import argparse
 import json
 import os
@@ -28,7 +31,8 @@ ap.add_argument("--lr-scale", type=float, default=1.0)
 ap.add_argument("--max-time-step", type=float, default=0)
 ap.add_argument("--entropy-beta", type=float, default=None, help="override options_lab's 0.001 (a stated deviation)")
 ap.add_argument("--out", default="")
-ap.add_argument("--arcade", default="", help="a device arcade game (breakout) instead of the maze")
+ap.add_argument("--arcade", default="", help="a device arcade game (breakout, duel) instead of the maze")
+ap.add_argument("--opponent-speed", type=int, default=None, help="the duel's opponent_speed (default: the game's)")
 args = ap.parse_args()
 device = torch.device("cuda", 0)
 
@@ -40,7 +44,7 @@ def build_arcade_trainer(args, device):
     from unreal_amd.options import get_options
     from unreal_amd.train.rmsprop_applier import RMSPropApplier
     from unreal_amd.train.trainer import Trainer, log_uniform
-    Environment.register_arcade_config(args.arcade, game=args.arcade)
+    Environment.register_arcade_config(args.arcade, game=args.arcade, opponent_speed=args.opponent_speed)
     flags = get_options("training", preset="lab", argv=["--env_type", "arcade", "--env_name", args.arcade])
     net = UnrealModel(Environment.get_action_size("arcade", args.arcade), 0, -1, flags.use_lstm, flags.use_pixel_change,
                       flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
@@ -80,7 +84,10 @@ print(json.dumps(head), flush=True)
 if out:
     out.write(json.dumps(head) + "\n")
 global_t, t0, k = 0, time.time(), 0
-totals = tr.full_ring.actor_records[:, 10:12].sum(0).cpu() if args.arcade else None      # bricks, lives lost
+# the totals of the game's records (words 10 ..), never zeroed: per-line differences over the line's episodes
+TOTALS = {"breakout": ("bricks_per_episode", "lives_lost_per_episode"),
+          "duel": ("points_won_per_episode", "points_lost_per_episode", "matches_won_per_episode")}.get(args.arcade, ())
+totals = tr.full_ring.actor_records[:, 10:10 + len(TOTALS)].sum(0).cpu() if args.arcade else None
 while global_t < args.steps:
     tr.process(None, global_t + k % args.log_every * args.actors * flags.n_step_TD, sync_stats=False)
     k += 1
@@ -95,11 +102,10 @@ while global_t < args.steps:
         goal = float(((rw > 0).float() * live).sum()) / n_live
         extra = {}
         if args.arcade:
-            now = tr.full_ring.actor_records[:, 10:12].sum(0).cpu()
+            now = tr.full_ring.actor_records[:, 10:10 + len(TOTALS)].sum(0).cpu()
             d = (now - totals).tolist()
             totals = now
-            extra = {"bricks_per_episode": round(d[0] / episodes, 3) if episodes else None,
-                     "lives_lost_per_episode": round(d[1] / episodes, 3) if episodes else None}
+            extra = {key: round(v / episodes, 3) if episodes else None for key, v in zip(TOTALS, d)}
         line = json.dumps({"global_t": global_t, "episodes": episodes, "bump_rate": round(bump, 5), "goal_rate": round(goal, 6),
                            "mean_return": (score_sum / episodes) if episodes else None,
                            "total_loss": round(l["total_loss"], 4), "entropy": round(l["entropy"], 4),

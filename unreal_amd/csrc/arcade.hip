@@ -1,8 +1,10 @@
-// Device arcade: games stepped AND rendered on the GPU, behind the ring and rollout arguments of the maze
-// entries.  One game so far: Breakout with ALE's minimal action set (0 noop, 1 fire, 2 right, 3 left), integer-only and a
-// pure function of (config block, seed, global actor, episode, actions).  The rules, the 24-word config block and the
-// 16-word per-actor record are documented with the entries in include/unreal_hip.h; tests/arcade_model.py is the host
-// model every kernel here is compared with bit for bit.
+// Device arcade: games stepped AND rendered on the GPU, behind the ring and rollout arguments of the
+// maze entries.  Two games, both with ALE's minimal action set (0 noop, 1 fire, 2 right, 3 left), integer-only and a pure
+// function of (config block, seed, global actor, episode, actions): Breakout (game id 1) and the two-paddle duel (id 3),
+// which keeps Breakout's geometry, ball and serve and puts an opponent's paddle where the wall was.  The rules, the 24-word
+// config blocks and the 16-word per-actor records are documented with the entries in include/unreal_hip.h;
+// tests/arcade_model.py and tests/duel_model.py are the host models every kernel here is compared with bit for bit.
+// The kernels read the game id from the block (uniform) and run that game's instance of one body.
 //
 // One actor per 256-thread workgroup.  The game logic is computed by every thread from the record (uniform: scalar
 // registers).  The stored frame of s_t is always the render of the pre-step record, so the step renders the new record
@@ -15,7 +17,7 @@
 
 namespace {
 
-constexpr int kArcadeBreakout = 1;                  // word 0 of the block
+constexpr int kArcadeBreakout = 1, kArcadeDuel = 3; // word 0 of the block
 constexpr int kArcadeRecord = 16;                   // int32 words per actor (the block has 24)
 constexpr int kMaxRows = 6, kCols = 10, kMaxBallSpeed = 4;
 constexpr int kBrickX0 = 2, kBrickW = 8, kBrickY0 = 18, kBrickH = 3;
@@ -23,6 +25,9 @@ constexpr int kPaddleY = 78, kFieldL = 2, kFieldR = 81, kFieldTop = 6, kServeY =
 // counter word 2 of a serve draw (word 3: the serve index); as far from the PhiloxDraws streams as the maze's constants
 constexpr uint32_t kArcadeServeStream = 0x41524B53u;
 constexpr uint32_t kBorder = 142u * 0x010101u, kWhite = 236u * 0x010101u, kPaddle = 200u | 72u << 8 | 72u << 16;
+// the duel: the opponent's paddle (and its score blocks) and the score row's capacity per side
+constexpr int kOppY = 8, kMaxScore = 9;
+constexpr uint32_t kOpponent = 66u | 72u << 8 | 200u << 16;
 
 constexpr int kChunks = FRAME_BYTES / 16;                 // 1323 uint4 per frame
 constexpr int kChunksPerThread = (kChunks + 255) / 256;   // 6
@@ -265,11 +270,181 @@ __device__ __forceinline__ uint32_t pixel(const Game& g, const Rules& r, const R
   return 0u;
 }
 
+// ---- the duel (game id 3): the block's settings, clamped like Breakout's (the score blocks drawn are clamped in the render)
+struct DuelRules {
+  int points, max_steps, w, paddle_speed, ball_speed, ow, serve_wait, lose_reward, win_reward, opp_speed;
+  uint64_t seed;
+};
+
+__device__ __forceinline__ DuelRules load_duel_rules(const int* cfg) {
+  DuelRules r;
+  r.points = cfg[2];
+  r.max_steps = cfg[3];
+  r.seed = (uint64_t)(uint32_t)cfg[4] | ((uint64_t)(uint32_t)cfg[5] << 32);
+  r.w = cfg[6];
+  r.paddle_speed = cfg[7];
+  r.ball_speed = min(cfg[8], kMaxBallSpeed);
+  r.ow = cfg[9];
+  r.serve_wait = cfg[10];
+  r.lose_reward = cfg[11];
+  r.win_reward = cfg[12];
+  r.opp_speed = cfg[13];
+  return r;
+}
+
+struct DuelGame {
+  int px, bx, by, vx, vy, wait, ox, mine, theirs;
+  int serve;              // serves of the running episode
+  int n_won, n_lost, n_matches;        // running totals, never zeroed
+};
+
+__device__ __forceinline__ DuelGame load_duel_game(const int* rec) {
+  DuelGame g;
+  g.px = rec[0]; g.bx = rec[1]; g.by = rec[2]; g.vx = rec[3]; g.vy = rec[4]; g.wait = rec[5]; g.ox = rec[6];
+  g.mine = rec[7]; g.theirs = rec[8]; g.serve = rec[9]; g.n_won = rec[10]; g.n_lost = rec[11]; g.n_matches = rec[12];
+  return g;
+}
+
+__device__ __forceinline__ void store_game(int* rec, const DuelGame& g) {
+  rec[0] = g.px; rec[1] = g.bx; rec[2] = g.by; rec[3] = g.vx; rec[4] = g.vy; rec[5] = g.wait; rec[6] = g.ox;
+  rec[7] = g.mine; rec[8] = g.theirs; rec[9] = g.serve; rec[10] = g.n_won; rec[11] = g.n_lost; rec[12] = g.n_matches;
+  rec[13] = 0; rec[14] = 0; rec[15] = 0;
+}
+
+// the first state of a match: both paddles in the middle, no points, the ball waiting; the totals run on
+__device__ __forceinline__ DuelGame reset_game(const DuelRules& r, const DuelGame& old) {
+  DuelGame g = old;
+  g.px = 42 - r.w / 2; g.ox = 42 - r.ow / 2; g.bx = 0; g.by = 0; g.vx = 0; g.vy = 0; g.wait = 0;
+  g.mine = 0; g.theirs = 0; g.serve = 0;
+  return g;
+}
+
+// the return off a paddle of width w at x: the four segments of d = ball middle - paddle middle
+__device__ __forceinline__ int return_vx(int bx, int x, int w) {
+  const int d = (bx + 1) - (x + w / 2);
+  return 4 * d < -w ? -2 : d < 0 ? -1 : 4 * d < w ? 1 : 2;
+}
+
+// One step of global actor `actor` in episode `ep` (the duel's rules 1..4 of the header); -> the step's reward.
+__device__ __forceinline__ int step_game(DuelGame& g, const DuelRules& r, int a, int actor, int ep) {
+  int reward = 0;
+  if (a == 2) g.px = min(g.px + r.paddle_speed, 82 - r.w);
+  if (a == 3) g.px = max(g.px - r.paddle_speed, kFieldL);
+  {                                               // the opponent follows the ball of the state before this step
+    const int target = (g.wait < 0 && g.vy < 0) ? g.bx + 1 : 42;
+    const int d = target - (g.ox + r.ow / 2);
+    g.ox = min(max(g.ox + min(max(d, -r.opp_speed), r.opp_speed), kFieldL), 82 - r.ow);
+  }
+  if (g.wait >= 0) {
+    if (a == 1 || (r.serve_wait > 0 && g.wait >= r.serve_wait)) {
+      uint32_t u[4];
+      philox4x32_10(r.seed, (uint64_t)(uint32_t)actor | ((uint64_t)(uint32_t)ep << 32),
+                    (uint64_t)kArcadeServeStream | ((uint64_t)(uint32_t)g.serve << 32), u);
+      g.bx = kFieldL + 2 * (int)(u[0] % 39u);
+      g.by = kServeY;
+      g.vx = (u[1] & 1u) ? 1 : -1;
+      g.vy = (u[2] & 1u) ? 1 : -1;
+      g.wait = -1;
+      g.serve += 1;
+    } else {
+      g.wait += 1;
+    }
+    return reward;
+  }
+  for (int m = 0; m < r.ball_speed; ++m) {
+    // x move
+    const int tx = g.bx + g.vx;
+    if (tx < kFieldL || tx + 1 > kFieldR) g.vx = -g.vx;
+    else g.bx = tx;
+    // y move
+    const int ty = g.by + g.vy;
+    if (g.vy > 0 && ty + 1 == kPaddleY && g.bx + 1 >= g.px && g.bx <= g.px + r.w - 1) {
+      g.vy = -1;
+      g.vx = return_vx(g.bx, g.px, r.w);
+    } else if (g.vy < 0 && ty == kOppY + 1 && g.bx + 1 >= g.ox && g.bx <= g.ox + r.ow - 1) {
+      g.vy = 1;
+      g.vx = return_vx(g.bx, g.ox, r.ow);
+    } else if (ty + 1 > 83) {
+      g.theirs += 1;
+      g.n_lost += 1;
+      reward += r.lose_reward;
+      g.wait = 0;
+      break;
+    } else if (ty < kFieldTop) {
+      g.mine += 1;
+      g.n_won += 1;
+      if (g.mine == r.points) g.n_matches += 1;
+      reward += r.win_reward;
+      g.wait = 0;
+      break;
+    } else {
+      g.by = ty;
+    }
+  }
+  return reward;
+}
+
+__device__ __forceinline__ bool game_over(const DuelGame& g, const DuelRules& r, int steps) {
+  return g.mine >= r.points || g.theirs >= r.points || steps >= r.max_steps;
+}
+
+struct DuelRow {
+  bool ball, paddle, opp, score, top;
+};
+
+__device__ __forceinline__ DuelRow frame_row(const DuelGame& g, const DuelRules&, int y) {
+  DuelRow row;
+  row.ball = g.wait < 0 && (unsigned)(y - g.by) < 2u;
+  row.paddle = (unsigned)(y - kPaddleY) < 2u;
+  row.opp = (unsigned)(y - kOppY) < 2u;
+  row.score = (unsigned)(y - 2) < 2u;
+  row.top = y < kFieldTop;
+  return row;
+}
+
+// pixel x of that row: front to back ball, paddles, score blocks (mine from x = 4 rightwards, theirs from x = 78
+// leftwards, nine a side at the most), border
+__device__ __forceinline__ uint32_t pixel(const DuelGame& g, const DuelRules& r, const DuelRow& row, int x) {
+  if (row.ball && (unsigned)(x - g.bx) < 2u) return kWhite;
+  if (row.paddle && x >= g.px && x < g.px + r.w) return kPaddle;
+  if (row.opp && x >= g.ox && x < g.ox + r.ow) return kOpponent;
+  if (row.score) {
+    if (x >= 4 && x < 4 + 4 * min(max(g.mine, 0), kMaxScore) && ((x - 4) & 3) < 2) return kWhite;
+    if (x <= 79 && x > 79 - 4 * min(max(g.theirs, 0), kMaxScore) && ((79 - x) & 3) < 2) return kOpponent;
+  }
+  if (row.top || x < kFieldL || x > kFieldR) return kBorder;
+  return 0u;
+}
+
+// The rows in which the frames of two states can differ: the ball's rows in either, a paddle's if it moved, the score
+// row if a point was made.
+struct DuelDirty {
+  int ball0, ball1;       // first ball row of either state (-8: not drawn)
+  bool paddle, opp, score;
+};
+
+__device__ __forceinline__ DuelDirty frame_dirty(const DuelGame& a, const DuelGame& b, const DuelRules&) {
+  return {a.wait < 0 ? a.by : -8, b.wait < 0 ? b.by : -8, a.px != b.px, a.ox != b.ox,
+          a.mine != b.mine || a.theirs != b.theirs};
+}
+
+__device__ __forceinline__ bool row_differs(const DuelDirty& d, int y) {
+  return (unsigned)(y - d.ball0) < 2u || (unsigned)(y - d.ball1) < 2u || (d.paddle && (unsigned)(y - kPaddleY) < 2u) ||
+         (d.opp && (unsigned)(y - kOppY) < 2u) || (d.score && (unsigned)(y - 2) < 2u);
+}
+
+// what the one body below asks of a game by type
+__device__ __forceinline__ void load(const int* cfg, const int* rec, Rules& r, Game& g) { r = load_rules(cfg); g = load_game(rec); }
+__device__ __forceinline__ void load(const int* cfg, const int* rec, DuelRules& r, DuelGame& g) {
+  r = load_duel_rules(cfg); g = load_duel_game(rec);
+}
+
 // dword `dw` of the frame: bytes 4 w .. 4 w + 3 of row y lie in pixels x0 and x0 + 1 (from channel c0 of the first)
-__device__ __forceinline__ uint32_t frame_dword(const Game& g, const Rules& r, int dw) {
+template <class G, class R>
+__device__ __forceinline__ uint32_t frame_dword(const G& g, const R& r, int dw) {
   const int y = dw / kRowDw, w = dw - kRowDw * y;
   const int x0 = (4 * w) / 3, c0 = 4 * w - 3 * x0;
-  const Row row = frame_row(g, r, y);
+  const auto row = frame_row(g, r, y);
   const uint32_t a = pixel(g, r, row, x0), b = pixel(g, r, row, x0 + 1);
   return (a >> (8 * c0)) | (b << (8 * (3 - c0)));
 }
@@ -293,31 +468,33 @@ __device__ __forceinline__ bool row_differs(const Dirty& d, int y) {
 }
 
 // |new - old| of dword `dw`, given the new state's dword: the old state is rendered only in rows that can differ
-__device__ __forceinline__ uint32_t diff_dword(const Game& old, const Rules& r, const Dirty& d, int dw, uint32_t v) {
+template <class G, class R, class D>
+__device__ __forceinline__ uint32_t diff_dword(const G& old, const R& r, const D& d, int dw, uint32_t v) {
   return row_differs(d, dw / kRowDw) ? absdiff_u8x4(v, frame_dword(old, r, dw)) : 0u;
 }
 
-__device__ __forceinline__ uint4 frame_chunk(const Game& g, const Rules& r, int c) {
+template <class G, class R>
+__device__ __forceinline__ uint4 frame_chunk(const G& g, const R& r, int c) {
   return make_uint4(frame_dword(g, r, 4 * c), frame_dword(g, r, 4 * c + 1), frame_dword(g, r, 4 * c + 2),
                     frame_dword(g, r, 4 * c + 3));
 }
 
-__device__ __forceinline__ void store_frame(uint8_t* dst, const Game& g, const Rules& r) {
+template <class G, class R>
+__device__ __forceinline__ void store_frame(uint8_t* dst, const G& g, const R& r) {
   uint4* d4 = reinterpret_cast<uint4*>(dst);
   for (int c = threadIdx.x; c < kChunks; c += 256) d4[c] = frame_chunk(g, r, c);
 }
 
-__global__ __launch_bounds__(256) void arcade_step_kernel(ArcadeArgs p) {
+// One step of actor blockIdx.x of game (G, R).  `diff` (|s_{t+1} - s_t|, byte-wise) and `s_act` are the kernel's LDS.
+template <class G, class R>
+__device__ __forceinline__ void step_actor(const ArcadeArgs& p, uint4* diff, int* s_act) {
   const int* cfg = p.cfg;
-  if (cfg[0] != kArcadeBreakout) return;        // (uniform) a block of another game: nothing is written
-  __shared__ uint4 diff[kChunks];               // |s_{t+1} - s_t|, byte-wise
-  __shared__ int s_act;
   const int b = blockIdx.x;
   const int H1 = p.H1;
   if (p.pol_x && threadIdx.x < 64) {            // the policy of this actor on wave 0 (for idle actors too, as unreal_policy_step)
     const int act = policy_row<4>(p.pol_x + (size_t)b * p.pol_ldx, p.Wp, p.bp, p.Wv, p.bv, p.pol_u + b,
                                   p.pi_out + (size_t)b * 4, p.v_out + b, threadIdx.x);
-    if (threadIdx.x == 0) { s_act = act; p.act_out[b] = act; }
+    if (threadIdx.x == 0) { *s_act = act; p.act_out[b] = act; }
   }
   const int cnt = p.count[b];
   const int slot = cnt % H1;
@@ -328,18 +505,19 @@ __global__ __launch_bounds__(256) void arcade_step_kernel(ArcadeArgs p) {
     if (threadIdx.x == 0) rollout_idle(p, b, slot, la, lr);
     return;
   }
-  const Rules rules = load_rules(cfg);
   int* rec = p.records + (size_t)kArcadeRecord * b;
-  const Game old = load_game(rec);
+  R rules;
+  G old;
+  load(cfg, rec, rules, old);
   const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
   const int steps = p.ep_steps[b] + 1;
   const int epi = p.episode[b];
   const int ns = p.active_rw ? p.n_steps[b] : 0;
   const float ep = p.track_score ? p.episode_reward[b] : 0.f;
   __syncthreads();                              // the drawn action is in LDS; every thread has read the record
-  const int a = p.pol_x ? s_act : p.actions[b];
+  const int a = p.pol_x ? *s_act : p.actions[b];
 
-  Game g = old;
+  G g = old;
   const float reward = (float)step_game(g, rules, a, p.actor_base + b, epi);
   const bool terminal = game_over(g, rules, steps);
   const RingStep ring = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
@@ -347,7 +525,7 @@ __global__ __launch_bounds__(256) void arcade_step_kernel(ArcadeArgs p) {
 
   // s_{t+1} and, in the rows where it can differ, s_t, 16 bytes per lane: the new chunk is stored unless the episode
   // restarts, the difference goes to LDS
-  const Dirty dirty = frame_dirty(old, g, rules);
+  const auto dirty = frame_dirty(old, g, rules);
 #pragma unroll 1
   for (int k = 0; k < kChunksPerThread; ++k) {
     const int c = threadIdx.x + 256 * k;
@@ -386,17 +564,25 @@ __global__ __launch_bounds__(256) void arcade_step_kernel(ArcadeArgs p) {
   }
 }
 
-__global__ __launch_bounds__(256) void arcade_reset_kernel(ArcadeArgs p) {
-  const int* cfg = p.cfg;
-  if (cfg[0] != kArcadeBreakout) return;        // (uniform) as in the step
+__global__ __launch_bounds__(256) void arcade_step_kernel(ArcadeArgs p) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act;
+  const int game = p.cfg[0];                    // (uniform) a block of another game: nothing is written
+  if (game == kArcadeBreakout) step_actor<Game, Rules>(p, diff, &s_act);
+  else if (game == kArcadeDuel) step_actor<DuelGame, DuelRules>(p, diff, &s_act);
+}
+
+template <class G, class R>
+__device__ __forceinline__ void reset_actor(const ArcadeArgs& p) {
   const int b = blockIdx.x;
   if (p.mask && !p.mask[b]) return;
-  const Rules rules = load_rules(cfg);
   int* rec = p.records + (size_t)kArcadeRecord * b;
-  const Game old = load_game(rec);
+  R rules;
+  G old;
+  load(p.cfg, rec, rules, old);
   const int epi = p.episode[b];
   __syncthreads();                              // every thread has read the record
-  const Game g = reset_game(rules, old);
+  const G g = reset_game(rules, old);
   store_frame(p.frames + ((size_t)b * p.H1 + p.count[b] % p.H1) * FRAME_BYTES, g, rules);
   if (threadIdx.x == 0) {
     store_game(rec, g);
@@ -405,6 +591,12 @@ __global__ __launch_bounds__(256) void arcade_reset_kernel(ArcadeArgs p) {
     p.last_action[b] = 0;
     p.last_reward[b] = 0.f;
   }
+}
+
+__global__ __launch_bounds__(256) void arcade_reset_kernel(ArcadeArgs p) {
+  const int game = p.cfg[0];                    // (uniform) as in the step
+  if (game == kArcadeBreakout) reset_actor<Game, Rules>(p);
+  else if (game == kArcadeDuel) reset_actor<DuelGame, DuelRules>(p);
 }
 
 // ---- host side: one check and one launcher for the four entries -------------------------------------------------------
@@ -422,7 +614,7 @@ bool arcade_args_ok(ArcadeEntry e, const ArcadeArgs& p) {
   if (e != kPolicy && !p.actions) return false;
   if (e == kStep) return true;
   if (!p.active_rw || !p.active_log_t || !p.n_steps || !p.terminal_end || p.idx_base < 0) return false;
-  if (p.A != 4) return false;                   // Breakout's minimal action set
+  if (p.A != 4) return false;                   // the games' minimal action set
   if (p.next_lar && (p.lar_col0 < 0 || p.lar_ld < p.lar_col0 + p.A + 1)) return false;
   if (e == kRollout) return true;
   return p.pol_x && p.pol_ldx >= LSTM_N && p.Wp && p.bp && p.Wv && p.bv && p.pol_u && p.pi_out && p.v_out && p.act_out;

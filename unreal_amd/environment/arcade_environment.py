@@ -1,13 +1,17 @@
-"""Device arcade (csrc/arcade.hip): games stepped and rendered on the GPU.  One game, Breakout with ALE's
-minimal action set (0 noop, 1 fire, 2 right, 3 left): integer-only and a pure function of (config, seed, global actor,
-episode, actions).  The rules are written out with the entries in include/unreal_hip.h."""
+"""Device arcade (csrc/arcade.hip): games stepped and rendered on the GPU.  Two games with ALE's minimal
+action set (0 noop, 1 fire, 2 right, 3 left): Breakout, and the two-paddle duel that keeps Breakout's geometry, ball and
+serve and puts an opponent's paddle where the wall was.  Both are integer-only and a pure function of (config, seed, global
+actor, episode, actions).  The rules are written out with the entries in include/unreal_hip.h."""
 import numpy as np
 import torch
 
 from . import environment
 from .. import ops
 
-GAMES = {"breakout": ops.ARCADE_BREAKOUT}
+GAMES = {"breakout": ops.ARCADE_BREAKOUT, "duel": ops.ARCADE_DUEL}
+# the settings only one game has, with that game's defaults (None given to ArcadeConfig: the default)
+GAME_SETTINGS = {"breakout": dict(rows=6, row_rewards=None, lives=3, life_reward=0),
+                 "duel": dict(points=5, opponent_width=12, opponent_speed=2, win_reward=1, lose_reward=-1)}
 
 
 def _int(name, v, lo, hi):
@@ -18,30 +22,57 @@ def _int(name, v, lo, hi):
     return int(v)
 
 
+def _even(name, v, lo, hi):
+    v = _int(name, v, lo, hi)
+    if v % 2:
+        raise ValueError("%s = %d must be even" % (name, v))
+    return v
+
+
 class ArcadeConfig(object):
-    """Settings of one arcade game (Environment.register_arcade_config).  Raises ValueError outside the documented ranges."""
+    """Settings of one arcade game (Environment.register_arcade_config).  Raises ValueError outside the documented ranges,
+    and for a setting of the other game (rows, row_rewards, lives, life_reward are Breakout's; points, opponent_width,
+    opponent_speed, win_reward, lose_reward the duel's; None: the game's default)."""
     ACTION_SIZE = 4
     MAX_ROWS, COLUMNS = 6, 10
+    MAX_POINTS = 9                      # the score row holds nine blocks a side
 
-    def __init__(self, game="breakout", rows=6, row_rewards=None, paddle_width=12, paddle_speed=3, ball_speed=2, lives=3,
-                 serve_wait=8, life_reward=0, max_episode_steps=5000):
+    def __init__(self, game="breakout", rows=None, row_rewards=None, paddle_width=12, paddle_speed=3, ball_speed=2,
+                 lives=None, serve_wait=8, life_reward=None, max_episode_steps=5000, points=None, opponent_width=None,
+                 opponent_speed=None, win_reward=None, lose_reward=None):
         if game not in GAMES:
             raise ValueError("arcade game %r: known games are %s" % (game, sorted(GAMES)))
         self.game = game
-        self.rows = _int("rows", rows, 1, self.MAX_ROWS)
-        if row_rewards is None:
-            row_rewards = (1,) * self.rows
-        if isinstance(row_rewards, (str, bytes)) or not hasattr(row_rewards, "__len__") or len(row_rewards) != self.rows:
-            raise ValueError("row_rewards must hold rows = %d integers, not %r" % (self.rows, row_rewards))
-        self.row_rewards = tuple(_int("row_rewards[%d]" % i, r, 0, 100) for i, r in enumerate(row_rewards))
-        self.paddle_width = _int("paddle_width", paddle_width, 4, 24)
-        if self.paddle_width % 2:
-            raise ValueError("paddle_width = %d must be even" % self.paddle_width)
+        own = dict(rows=rows, row_rewards=row_rewards, lives=lives, life_reward=life_reward, points=points,
+                   opponent_width=opponent_width, opponent_speed=opponent_speed, win_reward=win_reward,
+                   lose_reward=lose_reward)
+        for other, names in GAME_SETTINGS.items():
+            for name in names:
+                if other != game and own[name] is not None:
+                    raise ValueError("%s is a setting of game %r, not of %r" % (name, other, game))
+        own = {k: (own[k] if own[k] is not None else v) for k, v in GAME_SETTINGS[game].items()}
+        if game == "breakout":
+            self.rows = _int("rows", own["rows"], 1, self.MAX_ROWS)
+            row_rewards = own["row_rewards"]
+            if row_rewards is None:
+                row_rewards = (1,) * self.rows
+            if isinstance(row_rewards, (str, bytes)) or not hasattr(row_rewards, "__len__") or len(row_rewards) != self.rows:
+                raise ValueError("row_rewards must hold rows = %d integers, not %r" % (self.rows, row_rewards))
+            self.row_rewards = tuple(_int("row_rewards[%d]" % i, r, 0, 100) for i, r in enumerate(row_rewards))
+        else:
+            self.points = _int("points", own["points"], 1, self.MAX_POINTS)
+            self.opponent_width = _even("opponent_width", own["opponent_width"], 4, 24)
+            self.opponent_speed = _int("opponent_speed", own["opponent_speed"], 0, 8)
+            self.win_reward = _int("win_reward", own["win_reward"], 0, 100)
+            self.lose_reward = _int("lose_reward", own["lose_reward"], -100, 0)
+        self.paddle_width = _even("paddle_width", paddle_width, 4, 24)
         self.paddle_speed = _int("paddle_speed", paddle_speed, 1, 8)
         self.ball_speed = _int("ball_speed", ball_speed, 1, 4)
-        self.lives = _int("lives", lives, 1, 5)
+        if game == "breakout":
+            self.lives = _int("lives", own["lives"], 1, 5)
         self.serve_wait = _int("serve_wait", serve_wait, 0, 255)
-        self.life_reward = _int("life_reward", life_reward, -100, 0)
+        if game == "breakout":
+            self.life_reward = _int("life_reward", own["life_reward"], -100, 0)
         # mandatory: a ball that loops between the walls never ends an episode on its own
         self.max_episode_steps = _int("max_episode_steps", max_episode_steps, 1, 2 ** 31 - 1)
 
@@ -50,14 +81,20 @@ class ArcadeConfig(object):
         return self.ACTION_SIZE
 
     def block(self, seed):
-        """The int32 block of the kernels (UNREAL_ARCADE_CFG_WORDS words; layout: include/unreal_hip.h)."""
+        """The int32 block of the kernels (UNREAL_ARCADE_CFG_WORDS words; both games' layouts: include/unreal_hip.h)."""
         seed = int(seed) & (2 ** 64 - 1)
         w = np.zeros(ops.ARCADE_CFG_WORDS, dtype=np.int64)
         w[0] = GAMES[self.game]
-        w[2], w[3] = self.rows, self.max_episode_steps
+        w[3] = self.max_episode_steps
         w[4], w[5] = seed & 0xFFFFFFFF, seed >> 32
-        w[6:12] = (self.paddle_width, self.paddle_speed, self.ball_speed, self.lives, self.serve_wait, self.life_reward)
-        w[12:12 + self.rows] = self.row_rewards
+        w[6:9] = (self.paddle_width, self.paddle_speed, self.ball_speed)
+        w[10] = self.serve_wait
+        if self.game == "breakout":
+            w[2], w[9], w[11] = self.rows, self.lives, self.life_reward
+            w[12:12 + self.rows] = self.row_rewards
+        else:
+            w[2], w[9], w[11] = self.points, self.opponent_width, self.lose_reward
+            w[12], w[13] = self.win_reward, self.opponent_speed
         return (w & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
 
 
@@ -120,8 +157,9 @@ class BatchedArcadeEnvironment(object):
                                        arcade=self.arcade, **nxt)
 
     def current_records(self):
-        """The game records -> int32 [B, 16]: px, bx, by, vx, vy, wait, lives, bricks lo, hi, serve_index, then the
-        running totals of bricks, lives lost and walls cleared."""
+        """The game records -> int32 [B, 16].  Breakout: px, bx, by, vx, vy, wait, lives, bricks lo, hi, serve_index, then
+        the running totals of bricks, lives lost and walls cleared.  Duel: px, bx, by, vx, vy, wait, ox, mine, theirs,
+        serve_index, then the running totals of points won, points lost and matches won.  Words 13..15 are 0."""
         return self.ring.actor_records.cpu().numpy().copy()
 
     def stop(self):
@@ -169,5 +207,9 @@ class ArcadeEnvironment(environment.Environment):
         self.last_action = int(action)
         self.last_reward = reward
         rec = self._env.current_records()[0]
-        self._last_full_state = {"success": terminal and not (rec[7] | rec[8])}
+        if self._env.config.game == "duel":            # the match is won
+            success = terminal and int(rec[7]) >= self._env.config.points
+        else:                                          # the wall is cleared
+            success = terminal and not (rec[7] | rec[8])
+        self._last_full_state = {"success": bool(success)}
         return image, reward, terminal, pc

@@ -1,6 +1,6 @@
 """Environment factory with the reference's surface (/root/reference/environment/environment.py:11-102).
 
-The maze and the arcade (arcade_environment.py: Breakout) are device environments; lab / indoor actors are HOST-FED (hostfed_environment.py) by simulator objects
+The maze and the arcade (arcade_environment.py: Breakout and the two-paddle duel) are device environments; lab / indoor actors are HOST-FED (hostfed_environment.py) by simulator objects
 the caller supplies, because deepmind_lab / minos / gym are not in the image.  Gym actors are host-fed through
 gym_environment.GymBatchSimulator (any object with gym's reset / step API)."""
 
@@ -77,18 +77,26 @@ class Environment(object):
                                                        pickups, gen_pickups, no_goal)
 
     @staticmethod
-    def register_arcade_config(env_name, game="breakout", rows=6, row_rewards=None, paddle_width=12, paddle_speed=3,
-                               ball_speed=2, lives=3, serve_wait=8, life_reward=0, max_episode_steps=5000):
-        """Arcade game of `env_name` on the device (env_type 'arcade').  game="breakout": ALE Breakout's
-        minimal action set (0 noop, 1 fire, 2 right, 3 left) on an 84 x 84 RGB frame.  rows in 1..6 rows of 10 bricks;
-        row_rewards: one integer in 0..100 per row from the top (None: all 1); paddle_width even in 4..24 px;
-        paddle_speed in 1..8 px per step; ball_speed in 1..4 micro-steps per step; lives in 1..5; serve_wait in 0..255:
-        a waiting ball serves itself after that many steps (0: only fire serves); life_reward in -100..0 is paid with
-        every lost life; max_episode_steps in 1..2^31 - 1 ends an episode (a looping ball would never).  An episode
-        also ends with the last life or the last brick (success).  Raises ValueError outside these ranges."""
+    def register_arcade_config(env_name, game="breakout", rows=None, row_rewards=None, paddle_width=12, paddle_speed=3,
+                               ball_speed=2, lives=None, serve_wait=8, life_reward=None, max_episode_steps=5000,
+                               points=None, opponent_width=None, opponent_speed=None, win_reward=None, lose_reward=None):
+        """Arcade game of `env_name` on the device (env_type 'arcade'), with ALE's minimal action set
+        (0 noop, 1 fire, 2 right, 3 left) on an 84 x 84 RGB frame.  Both games: paddle_width even in 4..24 px;
+        paddle_speed in 1..8 px per step; ball_speed in 1..4 micro-steps per step; serve_wait in 0..255: a waiting ball
+        serves itself after that many steps (0: only fire serves); max_episode_steps in 1..2^31 - 1 ends an episode (a
+        looping ball would never).
+        game="breakout": rows in 1..6 rows of 10 bricks (None: 6); row_rewards: one integer in 0..100 per row from the
+        top (None: all 1); lives in 1..5 (None: 3); life_reward in -100..0 is paid with every lost life (None: 0).  An
+        episode also ends with the last life or the last brick (success).
+        game="duel": an opponent's paddle at the top follows the ball; a ball past it pays win_reward in 0..100 (None: 1),
+        a ball past the agent's pays lose_reward in -100..0 (None: -1); the first side with `points` in 1..9 (None: 5)
+        wins the match, which ends the episode (success: the agent's); opponent_width even in 4..24 (None: 12);
+        opponent_speed in 0..8 px per step (None: 2; 0: it stands).
+        Raises ValueError outside these ranges and for a setting of the other game."""
         from .arcade_environment import ArcadeConfig
         Environment.ARCADE_CONFIG[env_name] = ArcadeConfig(game, rows, row_rewards, paddle_width, paddle_speed, ball_speed,
-                                                           lives, serve_wait, life_reward, max_episode_steps)
+                                                           lives, serve_wait, life_reward, max_episode_steps, points,
+                                                           opponent_width, opponent_speed, win_reward, lose_reward)
 
     @staticmethod
     def arcade_config(env_name):

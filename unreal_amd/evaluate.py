@@ -16,7 +16,9 @@ step, turns and looks included, so an agent on the shortest path scores d0 / (d0
 no_goal maze success is an episode whose final step collected an ends_episode kind with a reward > 0.  With `arcade=` (a
 name given to Environment.register_arcade_config) the actors play that game: success is a cleared wall, every
 other ending (last life, the config's max_episode_steps) counts under `timeouts`, and the result holds
-`bricks_per_episode` and `lives_lost_per_episode` from differences of the records' running totals."""
+`bricks_per_episode` and `lives_lost_per_episode` from differences of the records' running totals.  On the duel
+ success is a match won, `timeouts` counts the episodes that ended at the step limit, `losses` those the opponent
+won, and the differences of the totals are `points_won_per_episode` and `points_lost_per_episode`."""
 import torch
 
 from . import ops
@@ -88,12 +90,14 @@ class Evaluate(object):
             ops.reset_state(B, self.terminals, ws.c0, ws.h0)
 
     def _process_arcade(self, n_episodes, one_episode_per_actor):
-        """The arcade's statistics: every episode ends in the environment (lives, wall, max_episode_steps)."""
+        """The arcade's statistics: every episode ends in the environment (lives, wall or points, max_episode_steps)."""
         B, ring = self.B, self.env.ring
-        tot = ring.actor_records[:, 10:13]     # bricks, lives lost, walls cleared: never zeroed
+        duel = self.arcade_config.game == "duel"
+        # Breakout: bricks, lives lost, walls cleared; duel: points won, points lost, matches won.  Never zeroed.
+        tot = ring.actor_records[:, 10:13]
         ep0 = tot.cpu().numpy().copy()
         steps, counted = [0] * B, [False] * B
-        returns, lengths, bricks, lost, successes = [], [], [], [], 0
+        returns, lengths, bricks, lost, successes, losses = [], [], [], [], 0, 0
         if one_episode_per_actor:
             n_episodes = B
         while len(returns) < n_episodes:
@@ -108,15 +112,23 @@ class Evaluate(object):
                 if not (one_episode_per_actor and counted[b]):
                     returns.append(float(score[b])); lengths.append(steps[b])
                     bricks.append(int(now[b, 0] - ep0[b, 0])); lost.append(int(now[b, 1] - ep0[b, 1]))
-                    successes += int(now[b, 2] - ep0[b, 2] > 0)
+                    won = now[b, 2] - ep0[b, 2] > 0
+                    successes += int(won)
+                    # an episode starts at 0 : 0, so the opponent's score is the episode's points lost
+                    losses += int(duel and not won and lost[-1] >= self.arcade_config.points)
                 ep0[b] = now[b]
                 steps[b] = 0; counted[b] = True
         n = len(returns)
         mean = sum(returns) / n
-        return dict(episodes=n, success_rate=successes / float(n), mean_return=mean,
-                    return_std=(sum((r - mean) ** 2 for r in returns) / n) ** 0.5, mean_length=sum(lengths) / float(n),
-                    timeouts=n - successes, bricks_per_episode=sum(bricks) / float(n),
-                    lives_lost_per_episode=sum(lost) / float(n))
+        res = dict(episodes=n, success_rate=successes / float(n), mean_return=mean,
+                   return_std=(sum((r - mean) ** 2 for r in returns) / n) ** 0.5, mean_length=sum(lengths) / float(n))
+        if duel:
+            res.update(timeouts=n - successes - losses, losses=losses, points_won_per_episode=sum(bricks) / float(n),
+                       points_lost_per_episode=sum(lost) / float(n))
+        else:
+            res.update(timeouts=n - successes, bricks_per_episode=sum(bricks) / float(n),
+                       lives_lost_per_episode=sum(lost) / float(n))
+        return res
 
     def process(self, n_episodes, max_episode_steps=2000, one_episode_per_actor=False):
         """-> dict(episodes, success_rate, mean_return, return_std, mean_length, timeouts, goals_per_episode,
