@@ -175,16 +175,17 @@ int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, cons
  * count / records / r_objective, or next_lar with lar_col0 < 0 or lar_ld < lar_col0 + 3. */
 int unreal_maze_objective(int B, int H1, const int* count, const int* records, int record_words, float* r_objective,
                           float* next_lar /*nullable*/, int lar_ld, int lar_col0, void* stream);
-/* Device arcade (csrc/arcade.hip, DESIGN §7k): games stepped and rendered on the device, one actor per workgroup.  The
+/* Device arcade (csrc/arcade.hip, DESIGN §7k, §7l, §7m): games stepped and rendered on the device, one actor per workgroup.  The
  * four entries take the ring and rollout arguments of the maze entries above (`pos` is accepted and never touched;
  * nullable) and commit through the same helpers; the maze tail is replaced by (cfg, actor_base, ep_steps[B], episode[B],
  * records[B][UNREAL_ARCADE_RECORD]).  There is one launch shape and no launch label.
  *
  * cfg: UNREAL_ARCADE_CFG_WORDS int32 words; word 0 is the game id, which the kernels read from the block (uniform):
  * UNREAL_ARCADE_BREAKOUT or UNREAL_ARCADE_DUEL (below); a kernel that reads another id (2 included) writes nothing.
- * Breakout's block: [0] UNREAL_ARCADE_BREAKOUT  [1] 0  [2] rows 1..6  [3] max_episode_steps >= 1  [4..5] seed (lo, hi)  [6] paddle_width (even, 4..24)
+ * Breakout's block: [0] UNREAL_ARCADE_BREAKOUT  [1] action_repeat - 1, 0..7 (the kernel clamps it; see "An agent step"
+ * below)  [2] rows 1..6  [3] max_episode_steps >= 1  [4..5] seed (lo, hi)  [6] paddle_width (even, 4..24)
  * [7] paddle_speed 1..8  [8] ball_speed 1..4  [9] lives 1..5  [10] serve_wait 0..255 (0: only fire serves)
- * [11] life_reward -100..0  [12..17] row rewards 0..100, top row first  [18..23] 0.
+ * [11] life_reward -100..0  [12..17] row rewards 0..100, top row first  [18] return_reward 0..100  [19..23] 0.
  * record: [0..6] px, bx, by, vx, vy, wait (>= 0: the ball waits to be served, -1: in flight), lives  [7..8] live bricks
  * (bit 10 r + c, lo, hi)  [9] serve_index  [10] bricks total  [11] lives-lost total  [12] walls-cleared total (the totals
  * are never zeroed)  [13..15] 0.
@@ -192,7 +193,8 @@ int unreal_maze_objective(int B, int H1, const int* count, const int* records, i
  * Breakout, actions 0 noop, 1 fire, 2 right, 3 left (ALE's minimal set: A = 4).  Frame 84 x 84 x 3 bytes (frame scale
  * 1 / 255), back to front: black; border (142, 142, 142) on rows 0..5 and columns 0..1, 82..83; life k < lives the block
  * x 4+4k..5+4k, y 2..3 in (236, 236, 236); brick (r, c) x 2+8c..9+8c, y 18+3r..20+3r in its row's colour; paddle y 78..79,
- * x px..px+w-1 in (200, 72, 72); the ball, 2 x 2 at (bx, by) in (236, 236, 236), only in flight.  One step:
+ * x px..px+w-1 in (200, 72, 72); the ball, 2 x 2 at (bx, by) in (236, 236, 236), only in flight.  One tick (with
+ * action_repeat = 1 an agent step is one tick; steps += 1 and rule 4 belong to the agent step, see below):
  *  1. steps += 1; action 2 / 3 moves the paddle by paddle_speed, clamped to [2, 82 - w].
  *  2. A waiting ball is served on fire, or when serve_wait > 0 and wait >= serve_wait: u = Philox4x32-10(key = seed,
  *     counter = (actor_base + b, episode, 0x41524B53, serve_index)); bx = 2 + 2 (u[0] % 39), by = 40, vx = u[1] & 1 ? +1
@@ -202,22 +204,44 @@ int unreal_maze_objective(int B, int H1, const int* count, const int* records, i
  *     (tx, by) overlaps live bricks: the one with the lowest bit is cleared and pays its row's reward, vx = -vx; else
  *     bx = tx.  y: ty = by + vy; ty < 6: vy = +1; else a brick as in x (vy = -vy); else if vy > 0, ty + 1 == 78 and
  *     [bx, bx+1] meets the paddle: vy = -1 and, with d = bx + 1 - (px + w / 2), vx = -2 if 4 d < -w, -1 if d < 0, +1 if
- *     4 d < w, else +2; else if ty + 1 > 83: lives -= 1, the reward gets life_reward, wait = 0; else by = ty.
+ *     4 d < w, else +2, and the reward gets return_reward; else if ty + 1 > 83: lives -= 1, the reward gets life_reward,
+ *     wait = 0; else by = ty.
  *  4. terminal: lives <= 0, no live brick, or steps >= max_episode_steps.  With reset_on_terminal the next episode starts
  *     (episode += 1, full wall, all lives, px = 42 - w / 2, ball waiting, wait = serve_index = steps = 0) and its first
  *     frame goes into the next slot.  The pixel change is that of the two frames before the reset, over 48 * 255.
  *
+ * An agent step (both games).  With word 1 = k - 1 one call of a step entry is one agent step of up to k
+ * ticks:
+ *  a. A tick is rules 1..3 above (the duel: its rules 1..4) without `steps += 1`, every tick with the step's action: the
+ *     paddle moves in every tick, so does the duel's opponent (from the ball of the state before that tick); a repeated
+ *     fire serves while the ball waits and is a noop in flight; `wait` advances once per tick; a ball served in one tick
+ *     flies in the next, and a lost life or point can be followed by waiting ticks and the next serve, all in one step.
+ *  b. The ticks stop after a tick that ends the game by the state's own conditions (Breakout: lives <= 0 or no live
+ *     brick; duel: mine >= points or theirs >= points).  Without reset_on_terminal the state stays ended, so every later
+ *     step runs exactly one tick.
+ *  c. steps, max_episode_steps, ep_steps and the ring count agent steps, not ticks, and the step limit never shortens a
+ *     step's ticks.  terminal is rule 4 (the duel: 5) on the record after the last tick run and the agent step count;
+ *     the endings keep their order.
+ *  d. The step's reward is the sum over its ticks, raw and unclipped into last_reward and the ring.
+ *  e. Word 18, return_reward, is added in the tick in which the AGENT's paddle returns the ball (Breakout: the
+ *     ty + 1 == 78 branch; duel: branch (a)); the opponent's returns pay nothing.  A tick holds at most one such return.
+ *  f. The frame stored is the render of the record after the last tick, and the pixel change is between that frame and
+ *     the frame before the step: the states between ticks are never drawn.  The kernel finds the rows that can differ
+ *     from the two end records alone, which stays exact for any k because it compares only fields that are drawn.
+ *  g. Serve draws keep their key and counter (seed, global actor, episode, serve_index): no other random stream.
+ * At word 1 = 0 and word 18 = 0 every entry computes what it computed before these words had a meaning.
+ *
  * The duel (UNREAL_ARCADE_DUEL): Breakout's field, ball, serve draw and four actions, with an opponent's paddle
- * in place of the wall.  cfg: [0] UNREAL_ARCADE_DUEL  [1] 0  [2] points 1..9  [3] max_episode_steps >= 1  [4..5] seed
- * (lo, hi)  [6] paddle_width (even, 4..24)  [7] paddle_speed 1..8  [8] ball_speed 1..4  [9] opponent_width (even, 4..24)
+ * in place of the wall.  cfg: [0] UNREAL_ARCADE_DUEL  [1] action_repeat - 1, 0..7  [2] points 1..9
+ * [3] max_episode_steps >= 1  [4..5] seed (lo, hi)  [6] paddle_width (even, 4..24)  [7] paddle_speed 1..8  [8] ball_speed 1..4  [9] opponent_width (even, 4..24)
  * [10] serve_wait 0..255  [11] lose_reward -100..0  [12] win_reward 0..100  [13] opponent_speed 0..8 (0: it stands)
- * [14..23] 0.
+ * [14..17] 0  [18] return_reward 0..100  [19..23] 0.
  * record: [0..5] px, bx, by, vx, vy, wait  [6] ox  [7] mine  [8] theirs (the two scores)  [9] serve_index  [10] points-won
  * total  [11] points-lost total  [12] matches-won total (the totals are never zeroed)  [13..15] 0.
  * Frame, back to front: black; Breakout's border; score blocks on rows 2..3: the agent's k-th point (k = 0..) x 4+4k..5+4k
  * in (236, 236, 236), the opponent's k-th x 78-4k..79-4k in (66, 72, 200), nine of each at the most; the agent's paddle
  * y 78..79, x px..px+paddle_width-1 in (200, 72, 72); the opponent's y 8..9, x ox..ox+opponent_width-1 in (66, 72, 200);
- * the ball as in Breakout, only in flight.  One step:
+ * the ball as in Breakout, only in flight.  One tick (an agent step is up to action_repeat ticks: "An agent step" above):
  *  1. steps += 1; the agent's paddle as in Breakout.
  *  2. The opponent's paddle, from the ball of the state before this step: target = bx + 1 if the ball is in flight and
  *     vy < 0, else 42; d = target - (ox + opponent_width / 2); ox += clamp(d, -opponent_speed, +opponent_speed), then
@@ -225,7 +249,8 @@ int unreal_maze_objective(int B, int H1, const int* count, const int* records, i
  *  3. A waiting ball is served as in Breakout (same key and counter words, bx, by = 40, vx), and vy = u[2] & 1 ? +1 : -1.
  *  4. A ball in flight makes ball_speed micro-steps, each an x move and then a y move; a point ends them.  x: tx = bx + vx;
  *     outside [2, 80]: vx = -vx; else bx = tx.  y: ty = by + vy, tested in this order: (a) vy > 0, ty + 1 == 78 and
- *     [bx, bx+1] meets the agent's paddle: vy = -1 and Breakout's vx from d = bx + 1 - (px + paddle_width / 2); (b) vy < 0,
+ *     [bx, bx+1] meets the agent's paddle: vy = -1, Breakout's vx from d = bx + 1 - (px + paddle_width / 2) and the
+ *     reward gets return_reward; (b) vy < 0,
  *     ty == 9 and [bx, bx+1] meets the opponent's: vy = +1, vx by the same rule from ox and opponent_width; (c) ty + 1 > 83:
  *     theirs += 1, the reward gets lose_reward, wait = 0; (d) ty < 6: mine += 1, the reward gets win_reward, wait = 0;
  *     (e) else by = ty.  A point leaves bx, by, vx, vy as they are.

@@ -1,0 +1,110 @@
+// Stand-alone host program around the device arcade's own game, tick-loop and render functions.
+// tools/check_arcade_host.py cuts those functions unchanged out of unreal_amd/csrc/arcade.hip (and the Philox draw out of
+// maze_common.h) into arcade_functions.inc, builds this file with AddressSanitizer and UBSan, and compares what it writes
+// with tests/repeat_model.py.  Nothing here runs on a GPU: the qualifiers of the device code are defined away.
+//
+//   arcade_host_check IN OUT
+// IN:  int32 words: cfg[24], B, S, F, actor_base, then S x B actions, then S x B active flags.
+// OUT: per agent step, for the first F actors the 21168 frame bytes of the record after the last tick (before a reset; an
+//      idle actor's current frame), then int32 words: B x (record[16], reward, terminal, ep_steps, episode) after the
+//      step's commit (after the reset at a terminal; -7 for the reward and terminal of an idle actor).
+// Exit status 1 when a difference dword of the kernel's dirty-row path is not the byte-wise difference of the two frames.
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#define __device__
+#define __forceinline__ inline
+#define FRAME_BYTES 21168
+#define FRAME_ROW_BYTES 252
+#define PC_CELLS 400
+#define LSTM_N 256
+using std::max;
+using std::min;
+struct uint4 { uint32_t x, y, z, w; };
+static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return {x, y, z, w}; }
+static inline uint32_t __umulhi(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
+
+namespace {
+#include "arcade_functions.inc"
+
+template <class G, class R>
+int run(const std::vector<int32_t>& in, FILE* out) {
+  const int32_t* cfg = in.data();
+  const int B = in[24], S = in[25], F = in[26], base = in[27];
+  const int32_t* acts = in.data() + 28;
+  const int32_t* active = acts + (size_t)S * B;
+  std::vector<int32_t> rec((size_t)B * kArcadeRecord, 0), steps(B, 0), episode(B, 0), line((size_t)B * 20);
+  std::vector<uint32_t> now(FRAME_BYTES / 4);
+  R rules;
+  int bad = 0;
+  for (int b = 0; b < B; ++b) {                   // the constructor's reset: episode 0
+    G g;
+    load(cfg, &rec[(size_t)b * kArcadeRecord], rules, g);
+    store_game(&rec[(size_t)b * kArcadeRecord], reset_game(rules, g));
+  }
+  for (int s = 0; s < S; ++s) {
+    for (int b = 0; b < B; ++b) {
+      int32_t* r = &rec[(size_t)b * kArcadeRecord];
+      G old;
+      load(cfg, r, rules, old);
+      G g = old;
+      int32_t reward = -7, terminal = -7;
+      if (active[(size_t)s * B + b]) {
+        reward = step_ticks(g, rules, acts[(size_t)s * B + b], base + b, episode[b]);
+        steps[b] += 1;
+        terminal = game_over(g, rules, steps[b]);
+      }
+      if (b < F) {                                // the step's render: the new frame, and the difference the kernel's way
+        const auto dirty = frame_dirty(old, g, rules);
+        for (int c = 0; c < kChunks; ++c) {
+          const uint4 v = frame_chunk(g, rules, c), o = frame_chunk(old, rules, c);
+          const uint32_t vs[4] = {v.x, v.y, v.z, v.w}, os[4] = {o.x, o.y, o.z, o.w};
+          for (int e = 0; e < 4; ++e) {
+            now[4 * c + e] = vs[e];
+            if (diff_dword(old, rules, dirty, 4 * c + e, vs[e]) != absdiff_u8x4(vs[e], os[e])) {
+              if (!bad) fprintf(stderr, "step %d actor %d dword %d: the dirty rows miss a difference\n", s, b, 4 * c + e);
+              bad = 1;
+            }
+          }
+        }
+        fwrite(now.data(), 1, FRAME_BYTES, out);
+      }
+      if (terminal == 1) {
+        g = reset_game(rules, g);
+        steps[b] = 0;
+        episode[b] += 1;
+      }
+      store_game(r, g);
+      int32_t* l = &line[(size_t)b * 20];
+      std::copy(r, r + kArcadeRecord, l);
+      l[16] = reward; l[17] = terminal; l[18] = steps[b]; l[19] = episode[b];
+    }
+    fwrite(line.data(), 4, line.size(), out);
+  }
+  return bad;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc != 3) return 2;
+  FILE* f = fopen(argv[1], "rb");
+  if (!f) return 2;
+  std::vector<int32_t> in;
+  int32_t w;
+  while (fread(&w, 4, 1, f) == 1) in.push_back(w);
+  fclose(f);
+  if (in.size() < 28 || in[24] <= 0 || in[25] <= 0 || in[26] < 0 || in[26] > in[24] ||
+      in.size() != 28 + 2 * (size_t)in[24] * in[25])
+    return 2;
+  FILE* out = fopen(argv[2], "wb");
+  if (!out) return 2;
+  int bad = 2;
+  if (in[0] == kArcadeBreakout) bad = run<Game, Rules>(in, out);
+  else if (in[0] == kArcadeDuel) bad = run<DuelGame, DuelRules>(in, out);
+  fclose(out);
+  return bad;
+}

@@ -8,10 +8,12 @@
     first-person maze.
 
   python tools/bench_arcade.py [--launches 200] [--steps 10] [--warmup 3] [--history 100] [--repeat 2] [--skip-trainer]
-                               [--game breakout]
+                               [--game breakout] [--action-repeat 1]
 
 `--game duel` measures the two-paddle duel on its default config instead of Breakout; its lines then also hold
-the game's name.  Prints one JSON line per measurement."""
+the game's name.  `--action-repeat K` measures the game at K ticks per agent step; its lines then also hold
+action_repeat and, for the arcade kernels, µs per game tick: the launch's time over K (a step runs fewer ticks only where
+one ends the game, about once in a hundred steps on the default configs).  Prints one JSON line per measurement."""
 import argparse
 import json
 import os
@@ -99,13 +101,17 @@ def main():
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--skip-trainer", action="store_true")
     ap.add_argument("--game", default="breakout", choices=("breakout", "duel"))
+    ap.add_argument("--action-repeat", type=int, default=None, help="game ticks per agent step, 1..8 (DESIGN §7m)")
     args = ap.parse_args()
     from unreal_amd.environment.environment import Environment
     from unreal_amd.environment.arcade_environment import BatchedArcadeEnvironment
     from unreal_amd.environment.maze_environment import batched_maze_environment
     arcade = "bench_" + args.game
-    Environment.register_arcade_config(arcade, game=args.game)
+    repeat = args.action_repeat
+    Environment.register_arcade_config(arcade, game=args.game, action_repeat=1 if repeat is None else repeat)
     tag = {} if args.game == "breakout" else {"game": args.game}
+    if repeat is not None:
+        tag["action_repeat"] = repeat
     kw = dict(random_start=True, random_goal=True, max_episode_steps=200)
     Environment.register_maze_config("bench_fp7", layouts(7), view="first_person", **kw)
     Environment.register_maze_config("bench_td7", layouts(7), **kw)
@@ -120,6 +126,9 @@ def main():
                 row["arcade_fused_us_%d" % k] = round(1e3 * fused_ms(envs["arcade"], B, args.launches), 2)
                 row["first_person_us_%d" % k] = round(1e3 * kernel_ms(envs["first_person"], B, args.launches), 2)
                 row["top_down_us_%d" % k] = round(1e3 * kernel_ms(envs["top_down"], B, args.launches), 2)
+            if repeat is not None:
+                for key in [n for n in row if n.startswith("arcade_")]:
+                    row[key.replace("_us_", "_tick_us_")] = round(row[key] / repeat, 2)
             print(json.dumps(row), flush=True)
             del envs
             torch.cuda.empty_cache()
@@ -129,7 +138,9 @@ def main():
                 dev_ms, wall_ms = fn(name, 4096, args.history, args.steps, args.warmup)
                 print(json.dumps(dict(bench="trainer_process", env=name, B=4096, history=args.history, repeat=rep,
                                       device_ms=round(dev_ms, 2), wall_ms=round(wall_ms, 2),
-                                      env_steps_per_s=round(4096 * 20 / wall_ms * 1e3))), flush=True)
+                                      env_steps_per_s=round(4096 * 20 / wall_ms * 1e3),
+                                      **({"action_repeat": repeat} if repeat is not None and name == arcade else {}))),
+                      flush=True)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""The device arcade's own game functions, tick loop and render on the CPU, under AddressSanitizer and UBSan, against the
+host models of tests/repeat_model.py.  No GPU is used and nothing loaded into Python is sanitized.
+
+The functions are cut unchanged out of unreal_amd/csrc/arcade.hip (everything from its constants to `frame_chunk`:
+`load_rules`, `step_game`, `game_ended`, `game_over`, `reset_game`, `store_game`, `step_ticks`, `frame_dirty`, `diff_dword`, ...,
+of both games) and the Philox draw out of maze_common.h, and compiled with tools/arcade_host_main.cpp into a stand-alone
+program.  Over every trace of tests/repeat_model.py (six random ones of 200 actors x 300 agent steps, two scripted ones) it
+is compared on every record, reward, terminal, ep_steps and episode, on every frame byte of the traces' watched actors, and
+inside the program every difference dword of the dirty-row path against the full byte-wise difference of the two frames.
+
+  python tools/check_arcade_host.py [--cxx clang++] [--keep DIR]"""
+import argparse
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+CSRC = os.path.join(ROOT, "unreal_amd", "csrc")
+
+
+def cut(path, first, last):
+    """The lines of `path` from the one that starts with `first` up to, not including, the one that starts with `last`."""
+    lines = open(path).read().split("\n")
+    i = [n for n, l in enumerate(lines) if l.startswith(first)]
+    j = [n for n, l in enumerate(lines) if l.startswith(last)]
+    assert len(i) == 1 and len(j) == 1 and i[0] < j[0], (path, first, last)
+    return "\n".join(lines[i[0]:j[0]]) + "\n"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cxx", default=os.environ.get("CXX") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++")
+    ap.add_argument("--keep", default="", help="work in this directory and keep it")
+    args = ap.parse_args()
+    import repeat_model as RM
+    work = args.keep or tempfile.mkdtemp(prefix="arcade_host_")
+    os.makedirs(work, exist_ok=True)
+    src = open(os.path.join(CSRC, "arcade.hip")).read()
+    begin = src.index("constexpr int kArcadeBreakout")
+    end = src.index("template <class G, class R>\n__device__ __forceinline__ void store_frame")
+    with open(os.path.join(work, "arcade_functions.inc"), "w") as f:
+        f.write(cut(os.path.join(CSRC, "maze_common.h"), "// ---- Philox4x32-10", "// ---- maze configuration block"))
+        f.write(src[begin:end])
+    exe = os.path.join(work, "arcade_host_check")
+    subprocess.check_call([args.cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", work, os.path.join(ROOT, "tools", "arcade_host_main.cpp"), "-o", exe])
+    total = 0
+    for k in range(len(RM.TRACE_SETTINGS) + len(RM.SCRIPTED_SETTINGS)):
+        conf, tr = RM.trace_config(k), RM.run_trace(k)
+        S, B = tr["acts"].shape
+        F = tr["pc"].shape[1]
+        head = np.concatenate([conf.block(RM.TRACE_SEED), np.array([B, S, F, 0], np.int32)])
+        fin, fout = os.path.join(work, "trace%d.in" % k), os.path.join(work, "trace%d.out" % k)
+        np.concatenate([head, tr["acts"].reshape(-1), tr["active"].reshape(-1)]).astype(np.int32).tofile(fin)
+        subprocess.check_call([exe, fin, fout])            # a sanitizer report or a wrong difference dword ends it here
+        raw = np.fromfile(fout, dtype=np.uint8).reshape(S, F * 21168 + B * 80)
+        frames = raw[:, :F * 21168].reshape(S, F, 21168)
+        words = np.ascontiguousarray(raw[:, F * 21168:]).view(np.int32).reshape(S, B, 20)
+        np.testing.assert_array_equal(words[:, :, :16], tr["records"], err_msg="records of trace %d" % k)
+        np.testing.assert_array_equal(words[:, :, 16], np.where(tr["active"] != 0, tr["reward"], -7).astype(np.int32))
+        np.testing.assert_array_equal(words[:, :, 17], tr["terminal"], err_msg="terminals of trace %d" % k)
+        np.testing.assert_array_equal(words[:, :, 18], tr["ep_steps"], err_msg="ep_steps of trace %d" % k)
+        np.testing.assert_array_equal(words[:, :, 19], tr["episode"], err_msg="episodes of trace %d" % k)
+        for s in range(S):
+            for b in range(F):
+                rec = tr["pre_reset"][s, b] if tr["active"][s, b] else tr["records"][s, b]
+                np.testing.assert_array_equal(frames[s, b], RM.frame_of(conf, rec).reshape(-1),
+                                              err_msg="frame of trace %d step %d actor %d" % (k, s, b))
+        total += int(tr["active"].sum())
+        print("trace %d (%s, action_repeat %d, return_reward %d): %d agent steps, %d frames agree"
+              % (k, conf.game, conf.action_repeat, conf.return_reward, int(tr["active"].sum()), S * F), flush=True)
+    print("arcade host check ok: %d agent steps; the sanitizers reported nothing" % total)
+    if not args.keep:
+        shutil.rmtree(work)
+
+
+if __name__ == "__main__":
+    main()

@@ -3,13 +3,16 @@
 
 usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] [--steps 2e7] [--log-every 10]
                                   [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout|duel]
-                                  [--opponent-speed N]
+                                  [--opponent-speed N] [--action-repeat K] [--return-reward R] [--seed S]
 `--groups G`: G sequential updates per process() call (update density x G, see Trainer).  One JSON line per
 `--log-every` calls: global_t, episodes finished since the last line, their mean return, losses, entropy, steps/s.
 `--arcade GAME`: train on the device arcade with that game's default config instead; a line then also holds
 bricks_per_episode and lives_lost_per_episode (differences of the records' totals over the episodes of the line); on the
 duel these are points_won_per_episode, points_lost_per_episode and matches_won_per_episode, and
-`--opponent-speed` overrides the opponent's 2 px per step."""
+`--opponent-speed` overrides the opponent's 2 px per step.  `--action-repeat K` (1..8) and `--return-reward R` (0..100) are
+the arcade config's settings of those names: K game ticks per agent step, R paid for every ball the agent's
+paddle returns; steps, steps_per_s and episode lengths stay agent steps.  `--seed S` (arcade only) replaces the run's two
+seeds, the network's initial weights (1) and the trainer's draws and serve key (0xA3C), by S."""
 import argparse
 import json
 import os
@@ -33,7 +36,13 @@ ap.add_argument("--entropy-beta", type=float, default=None, help="override optio
 ap.add_argument("--out", default="")
 ap.add_argument("--arcade", default="", help="a device arcade game (breakout, duel) instead of the maze")
 ap.add_argument("--opponent-speed", type=int, default=None, help="the duel's opponent_speed (default: the game's)")
+ap.add_argument("--action-repeat", type=int, default=1, help="arcade: game ticks per agent step, 1..8")
+ap.add_argument("--return-reward", type=int, default=0, help="arcade: reward for a ball the agent's paddle returns, 0..100")
+ap.add_argument("--seed", type=int, default=None, help="arcade: seed of the weights and of the trainer (default: 1 and 0xA3C)")
 args = ap.parse_args()
+if not args.arcade and (args.action_repeat != 1 or args.return_reward != 0 or args.seed is not None or
+                        args.opponent_speed is not None):
+    ap.error("--action-repeat, --return-reward, --seed and --opponent-speed are settings of --arcade GAME")
 device = torch.device("cuda", 0)
 
 
@@ -44,18 +53,19 @@ def build_arcade_trainer(args, device):
     from unreal_amd.options import get_options
     from unreal_amd.train.rmsprop_applier import RMSPropApplier
     from unreal_amd.train.trainer import Trainer, log_uniform
-    Environment.register_arcade_config(args.arcade, game=args.arcade, opponent_speed=args.opponent_speed)
+    Environment.register_arcade_config(args.arcade, game=args.arcade, opponent_speed=args.opponent_speed,
+                                       action_repeat=args.action_repeat, return_reward=args.return_reward)
     flags = get_options("training", preset="lab", argv=["--env_type", "arcade", "--env_name", args.arcade])
     net = UnrealModel(Environment.get_action_size("arcade", args.arcade), 0, -1, flags.use_lstm, flags.use_pixel_change,
                       flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
-                      device, seed=1)
+                      device, seed=1 if args.seed is None else args.seed)
     lr0 = log_uniform(flags.initial_alpha_low, flags.initial_alpha_high, flags.initial_alpha_log_rate)
     applier = RMSPropApplier(None, decay=flags.rmsp_alpha, momentum=0.0, epsilon=flags.rmsp_epsilon,
                              clip_norm=flags.grad_norm_clip, device=device)
     tr = Trainer(0, net, lr0, None, applier, "arcade", args.arcade, flags.use_lstm, flags.use_pixel_change,
                  flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
                  flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
-                 batch_size=args.actors, seed=0xA3C, groups=args.groups)
+                 batch_size=args.actors, seed=0xA3C if args.seed is None else args.seed, groups=args.groups)
     tr.prepare()
     return flags, net, tr
 

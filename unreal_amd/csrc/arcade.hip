@@ -20,6 +20,7 @@ namespace {
 constexpr int kArcadeBreakout = 1, kArcadeDuel = 3; // word 0 of the block
 constexpr int kArcadeRecord = 16;                   // int32 words per actor (the block has 24)
 constexpr int kMaxRows = 6, kCols = 10, kMaxBallSpeed = 4;
+constexpr int kMaxRepeat = 8;                       // ticks of one agent step at the most (word 1 of the block + 1)
 constexpr int kBrickX0 = 2, kBrickW = 8, kBrickY0 = 18, kBrickH = 3;
 constexpr int kPaddleY = 78, kFieldL = 2, kFieldR = 81, kFieldTop = 6, kServeY = 40;
 // counter word 2 of a serve draw (word 3: the serve index); as far from the PhiloxDraws streams as the maze's constants
@@ -95,12 +96,16 @@ struct ArcadeArgs {
 // the block's settings, clamped to what the loops and the colour table below are built for (ArcadeConfig checks them)
 struct Rules {
   int rows, max_steps, w, paddle_speed, ball_speed, lives, serve_wait, life_reward;
+  int repeat;             // ticks of one agent step beyond the first, 0..7 (word 1)
+  int return_reward;      // paid in the tick in which the paddle returns the ball (word 18)
   uint64_t seed;
   const int* row_reward;
 };
 
 __device__ __forceinline__ Rules load_rules(const int* cfg) {
   Rules r;
+  r.repeat = min(max(cfg[1], 0), kMaxRepeat - 1);
+  r.return_reward = cfg[18];
   r.rows = min(max(cfg[2], 1), kMaxRows);
   r.max_steps = cfg[3];
   r.seed = (uint64_t)(uint32_t)cfg[4] | ((uint64_t)(uint32_t)cfg[5] << 32);
@@ -168,7 +173,7 @@ __device__ __forceinline__ int take_brick(Game& g, const Rules& r, int bit) {
   return r.row_reward[min(bit / kCols, kMaxRows - 1)];
 }
 
-// One step of global actor `actor` in episode `ep` (rules 1..3 of the header); -> the step's reward.
+// One tick of global actor `actor` in episode `ep` (rules 1..3 of the header); -> the tick's reward.
 __device__ __forceinline__ int step_game(Game& g, const Rules& r, int a, int actor, int ep) {
   int reward = 0;
   if (a == 2) g.px = min(g.px + r.paddle_speed, 82 - r.w);
@@ -213,6 +218,7 @@ __device__ __forceinline__ int step_game(Game& g, const Rules& r, int a, int act
         const int d = (g.bx + 1) - (g.px + r.w / 2);
         g.vy = -1;
         g.vx = 4 * d < -r.w ? -2 : d < 0 ? -1 : 4 * d < r.w ? 1 : 2;
+        reward += r.return_reward;
       } else if (ty + 1 > 83) {
         g.lives -= 1;
         g.n_lost += 1;
@@ -228,8 +234,11 @@ __device__ __forceinline__ int step_game(Game& g, const Rules& r, int a, int act
   return reward;
 }
 
+// the game is over by the state's own conditions: no tick of an agent step follows (the step limit is no such condition)
+__device__ __forceinline__ bool game_ended(const Game& g, const Rules&) { return g.lives <= 0 || g.bricks == 0; }
+
 __device__ __forceinline__ bool game_over(const Game& g, const Rules& r, int steps) {
-  return g.lives <= 0 || g.bricks == 0 || steps >= r.max_steps;
+  return game_ended(g, r) || steps >= r.max_steps;
 }
 
 __device__ __forceinline__ uint32_t row_colour(int r) {
@@ -273,11 +282,14 @@ __device__ __forceinline__ uint32_t pixel(const Game& g, const Rules& r, const R
 // ---- the duel (game id 3): the block's settings, clamped like Breakout's (the score blocks drawn are clamped in the render)
 struct DuelRules {
   int points, max_steps, w, paddle_speed, ball_speed, ow, serve_wait, lose_reward, win_reward, opp_speed;
+  int repeat, return_reward;          // as in Rules (words 1 and 18)
   uint64_t seed;
 };
 
 __device__ __forceinline__ DuelRules load_duel_rules(const int* cfg) {
   DuelRules r;
+  r.repeat = min(max(cfg[1], 0), kMaxRepeat - 1);
+  r.return_reward = cfg[18];
   r.points = cfg[2];
   r.max_steps = cfg[3];
   r.seed = (uint64_t)(uint32_t)cfg[4] | ((uint64_t)(uint32_t)cfg[5] << 32);
@@ -325,7 +337,7 @@ __device__ __forceinline__ int return_vx(int bx, int x, int w) {
   return 4 * d < -w ? -2 : d < 0 ? -1 : 4 * d < w ? 1 : 2;
 }
 
-// One step of global actor `actor` in episode `ep` (the duel's rules 1..4 of the header); -> the step's reward.
+// One tick of global actor `actor` in episode `ep` (the duel's rules 1..4 of the header); -> the tick's reward.
 __device__ __forceinline__ int step_game(DuelGame& g, const DuelRules& r, int a, int actor, int ep) {
   int reward = 0;
   if (a == 2) g.px = min(g.px + r.paddle_speed, 82 - r.w);
@@ -361,6 +373,7 @@ __device__ __forceinline__ int step_game(DuelGame& g, const DuelRules& r, int a,
     if (g.vy > 0 && ty + 1 == kPaddleY && g.bx + 1 >= g.px && g.bx <= g.px + r.w - 1) {
       g.vy = -1;
       g.vx = return_vx(g.bx, g.px, r.w);
+      reward += r.return_reward;
     } else if (g.vy < 0 && ty == kOppY + 1 && g.bx + 1 >= g.ox && g.bx <= g.ox + r.ow - 1) {
       g.vy = 1;
       g.vx = return_vx(g.bx, g.ox, r.ow);
@@ -384,8 +397,12 @@ __device__ __forceinline__ int step_game(DuelGame& g, const DuelRules& r, int a,
   return reward;
 }
 
+__device__ __forceinline__ bool game_ended(const DuelGame& g, const DuelRules& r) {
+  return g.mine >= r.points || g.theirs >= r.points;
+}
+
 __device__ __forceinline__ bool game_over(const DuelGame& g, const DuelRules& r, int steps) {
-  return g.mine >= r.points || g.theirs >= r.points || steps >= r.max_steps;
+  return game_ended(g, r) || steps >= r.max_steps;
 }
 
 struct DuelRow {
@@ -417,7 +434,7 @@ __device__ __forceinline__ uint32_t pixel(const DuelGame& g, const DuelRules& r,
 }
 
 // The rows in which the frames of two states can differ: the ball's rows in either, a paddle's if it moved, the score
-// row if a point was made.
+// row if a point was made.  Only drawn fields of the two records are compared, so any number of ticks may lie between them.
 struct DuelDirty {
   int ball0, ball1;       // first ball row of either state (-8: not drawn)
   bool paddle, opp, score;
@@ -439,6 +456,20 @@ __device__ __forceinline__ void load(const int* cfg, const int* rec, DuelRules& 
   r = load_duel_rules(cfg); g = load_duel_game(rec);
 }
 
+// One agent step of global actor `actor` in episode `ep` ("An agent step" in the header): up to repeat + 1 ticks with the
+// same action, none after the tick that ends the game; -> the sum of the ticks' rewards.  The loop stays a loop: eight
+// inlined copies of a tick would not fit the step kernel's registers.
+template <class G, class R>
+__device__ __forceinline__ int step_ticks(G& g, const R& r, int a, int actor, int ep) {
+  int reward = 0;
+#pragma unroll 1
+  for (int tick = 0;; ++tick) {
+    reward += step_game(g, r, a, actor, ep);
+    if (tick >= r.repeat || game_ended(g, r)) break;
+  }
+  return reward;
+}
+
 // dword `dw` of the frame: bytes 4 w .. 4 w + 3 of row y lie in pixels x0 and x0 + 1 (from channel c0 of the first)
 template <class G, class R>
 __device__ __forceinline__ uint32_t frame_dword(const G& g, const R& r, int dw) {
@@ -450,7 +481,8 @@ __device__ __forceinline__ uint32_t frame_dword(const G& g, const R& r, int dw) 
 }
 
 // The rows in which the frames of two states of one actor can differ: the ball's rows in either, the paddle's if it
-// moved, the brick rows if a brick went, the lives' if one was lost.  Nothing else of a record is drawn.
+// moved, the brick rows if a brick went, the lives' if one was lost.  Nothing else of a record is drawn, so this holds for
+// any two records, whatever number of ticks lies between them.
 struct Dirty {
   int ball0, ball1;       // first ball row of either state (-8: not drawn)
   bool paddle, bricks, lives;
@@ -485,7 +517,7 @@ __device__ __forceinline__ void store_frame(uint8_t* dst, const G& g, const R& r
   for (int c = threadIdx.x; c < kChunks; c += 256) d4[c] = frame_chunk(g, r, c);
 }
 
-// One step of actor blockIdx.x of game (G, R).  `diff` (|s_{t+1} - s_t|, byte-wise) and `s_act` are the kernel's LDS.
+// One agent step of actor blockIdx.x of game (G, R).  `diff` (|s_{t+1} - s_t|, byte-wise) and `s_act` are the kernel's LDS.
 template <class G, class R>
 __device__ __forceinline__ void step_actor(const ArcadeArgs& p, uint4* diff, int* s_act) {
   const int* cfg = p.cfg;
@@ -517,8 +549,9 @@ __device__ __forceinline__ void step_actor(const ArcadeArgs& p, uint4* diff, int
   __syncthreads();                              // the drawn action is in LDS; every thread has read the record
   const int a = p.pol_x ? *s_act : p.actions[b];
 
+  // only the record after the agent step's last tick is drawn, so everything below sees two records, as with one tick
   G g = old;
-  const float reward = (float)step_game(g, rules, a, p.actor_base + b, epi);
+  const float reward = (float)step_ticks(g, rules, a, p.actor_base + b, epi);
   const bool terminal = game_over(g, rules, steps);
   const RingStep ring = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
   uint8_t* dst = p.frames + ((size_t)b * H1 + ring.nslot) * FRAME_BYTES;

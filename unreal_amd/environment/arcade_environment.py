@@ -1,7 +1,8 @@
-"""Device arcade (csrc/arcade.hip, DESIGN §7k, §7l): games stepped and rendered on the GPU.  Two games with ALE's minimal
+"""Device arcade (csrc/arcade.hip, DESIGN §7k, §7l, §7m): games stepped and rendered on the GPU.  Two games with ALE's minimal
 action set (0 noop, 1 fire, 2 right, 3 left): Breakout, and the two-paddle duel that keeps Breakout's geometry, ball and
 serve and puts an opponent's paddle where the wall was.  Both are integer-only and a pure function of (config, seed, global
-actor, episode, actions).  The rules are written out with the entries in include/unreal_hip.h."""
+actor, episode, actions).  An agent step is `action_repeat` game ticks with one action (§7m).  The rules are written out
+with the entries in include/unreal_hip.h."""
 import numpy as np
 import torch
 
@@ -32,14 +33,16 @@ def _even(name, v, lo, hi):
 class ArcadeConfig(object):
     """Settings of one arcade game (Environment.register_arcade_config).  Raises ValueError outside the documented ranges,
     and for a setting of the other game (rows, row_rewards, lives, life_reward are Breakout's; points, opponent_width,
-    opponent_speed, win_reward, lose_reward the duel's; None: the game's default)."""
+    opponent_speed, win_reward, lose_reward the duel's; None: the game's default).  Both games: action_repeat in 1..8 game
+    ticks per agent step, return_reward in 0..100 paid when the agent's paddle returns the ball."""
     ACTION_SIZE = 4
+    MAX_ACTION_REPEAT = 8
     MAX_ROWS, COLUMNS = 6, 10
     MAX_POINTS = 9                      # the score row holds nine blocks a side
 
     def __init__(self, game="breakout", rows=None, row_rewards=None, paddle_width=12, paddle_speed=3, ball_speed=2,
                  lives=None, serve_wait=8, life_reward=None, max_episode_steps=5000, points=None, opponent_width=None,
-                 opponent_speed=None, win_reward=None, lose_reward=None):
+                 opponent_speed=None, win_reward=None, lose_reward=None, action_repeat=1, return_reward=0):
         if game not in GAMES:
             raise ValueError("arcade game %r: known games are %s" % (game, sorted(GAMES)))
         self.game = game
@@ -75,6 +78,8 @@ class ArcadeConfig(object):
             self.life_reward = _int("life_reward", own["life_reward"], -100, 0)
         # mandatory: a ball that loops between the walls never ends an episode on its own
         self.max_episode_steps = _int("max_episode_steps", max_episode_steps, 1, 2 ** 31 - 1)
+        self.action_repeat = _int("action_repeat", action_repeat, 1, self.MAX_ACTION_REPEAT)
+        self.return_reward = _int("return_reward", return_reward, 0, 100)
 
     @property
     def action_size(self):
@@ -85,6 +90,7 @@ class ArcadeConfig(object):
         seed = int(seed) & (2 ** 64 - 1)
         w = np.zeros(ops.ARCADE_CFG_WORDS, dtype=np.int64)
         w[0] = GAMES[self.game]
+        w[1], w[18] = self.action_repeat - 1, self.return_reward
         w[3] = self.max_episode_steps
         w[4], w[5] = seed & 0xFFFFFFFF, seed >> 32
         w[6:9] = (self.paddle_width, self.paddle_speed, self.ball_speed)

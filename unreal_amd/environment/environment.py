@@ -79,12 +79,15 @@ class Environment(object):
     @staticmethod
     def register_arcade_config(env_name, game="breakout", rows=None, row_rewards=None, paddle_width=12, paddle_speed=3,
                                ball_speed=2, lives=None, serve_wait=8, life_reward=None, max_episode_steps=5000,
-                               points=None, opponent_width=None, opponent_speed=None, win_reward=None, lose_reward=None):
+                               points=None, opponent_width=None, opponent_speed=None, win_reward=None, lose_reward=None,
+                               action_repeat=1, return_reward=0):
         """Arcade game of `env_name` on the device (env_type 'arcade'), with ALE's minimal action set
         (0 noop, 1 fire, 2 right, 3 left) on an 84 x 84 RGB frame.  Both games: paddle_width even in 4..24 px;
         paddle_speed in 1..8 px per step; ball_speed in 1..4 micro-steps per step; serve_wait in 0..255: a waiting ball
         serves itself after that many steps (0: only fire serves); max_episode_steps in 1..2^31 - 1 ends an episode (a
-        looping ball would never).
+        looping ball would never), counted in agent steps; action_repeat in 1..8: an agent step is that many game
+        ticks with the same action, fewer where a tick ends the game, and pays their rewards' sum (DESIGN §7m);
+        return_reward in 0..100 is paid in the tick in which the agent's paddle returns the ball.
         game="breakout": rows in 1..6 rows of 10 bricks (None: 6); row_rewards: one integer in 0..100 per row from the
         top (None: all 1); lives in 1..5 (None: 3); life_reward in -100..0 is paid with every lost life (None: 0).  An
         episode also ends with the last life or the last brick (success).
@@ -96,7 +99,8 @@ class Environment(object):
         from .arcade_environment import ArcadeConfig
         Environment.ARCADE_CONFIG[env_name] = ArcadeConfig(game, rows, row_rewards, paddle_width, paddle_speed, ball_speed,
                                                            lives, serve_wait, life_reward, max_episode_steps, points,
-                                                           opponent_width, opponent_speed, win_reward, lose_reward)
+                                                           opponent_width, opponent_speed, win_reward, lose_reward,
+                                                           action_repeat, return_reward)
 
     @staticmethod
     def arcade_config(env_name):

@@ -18,7 +18,9 @@ name given to Environment.register_arcade_config) the actors play t
 other ending (last life, the config's max_episode_steps) counts under `timeouts`, and the result holds
 `bricks_per_episode` and `lives_lost_per_episode` from differences of the records' running totals.  On the duel
  success is a match won, `timeouts` counts the episodes that ended at the step limit, `losses` those the opponent
-won, and the differences of the totals are `points_won_per_episode` and `points_lost_per_episode`."""
+won, and the differences of the totals are `points_won_per_episode` and `points_lost_per_episode`.  On both games
+`mean_length` counts agent steps: with the config's `action_repeat = k` an episode of that length ran up to k
+game ticks per step."""
 import torch
 
 from . import ops
