@@ -175,13 +175,14 @@ int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, cons
  * count / records / r_objective, or next_lar with lar_col0 < 0 or lar_ld < lar_col0 + 3. */
 int unreal_maze_objective(int B, int H1, const int* count, const int* records, int record_words, float* r_objective,
                           float* next_lar /*nullable*/, int lar_ld, int lar_col0, void* stream);
-/* Device arcade (csrc/arcade.hip, DESIGN §7k, §7l, §7m): games stepped and rendered on the device, one actor per workgroup.  The
+/* Device arcade (csrc/arcade.hip, DESIGN §7k, §7l, §7m, §7n): games stepped and rendered on the device, one actor per workgroup.  The
  * four entries take the ring and rollout arguments of the maze entries above (`pos` is accepted and never touched;
  * nullable) and commit through the same helpers; the maze tail is replaced by (cfg, actor_base, ep_steps[B], episode[B],
  * records[B][UNREAL_ARCADE_RECORD]).  There is one launch shape and no launch label.
  *
  * cfg: UNREAL_ARCADE_CFG_WORDS int32 words; word 0 is the game id, which the kernels read from the block (uniform):
- * UNREAL_ARCADE_BREAKOUT or UNREAL_ARCADE_DUEL (below); a kernel that reads another id (2 included) writes nothing.
+ * UNREAL_ARCADE_BREAKOUT, UNREAL_ARCADE_DUEL or UNREAL_ARCADE_INVADERS (below); a kernel that reads another id (2 included)
+ * writes nothing.
  * Breakout's block: [0] UNREAL_ARCADE_BREAKOUT  [1] action_repeat - 1, 0..7 (the kernel clamps it; see "An agent step"
  * below)  [2] rows 1..6  [3] max_episode_steps >= 1  [4..5] seed (lo, hi)  [6] paddle_width (even, 4..24)
  * [7] paddle_speed 1..8  [8] ball_speed 1..4  [9] lives 1..5  [10] serve_wait 0..255 (0: only fire serves)
@@ -210,7 +211,7 @@ int unreal_maze_objective(int B, int H1, const int* count, const int* records, i
  *     (episode += 1, full wall, all lives, px = 42 - w / 2, ball waiting, wait = serve_index = steps = 0) and its first
  *     frame goes into the next slot.  The pixel change is that of the two frames before the reset, over 48 * 255.
  *
- * An agent step (both games).  With word 1 = k - 1 one call of a step entry is one agent step of up to k
+ * An agent step (every game).  With word 1 = k - 1 one call of a step entry is one agent step of up to k
  * ticks:
  *  a. A tick is rules 1..3 above (the duel: its rules 1..4) without `steps += 1`, every tick with the step's action: the
  *     paddle moves in every tick, so does the duel's opponent (from the ball of the state before that tick); a repeated
@@ -259,13 +260,55 @@ int unreal_maze_objective(int B, int H1, const int* count, const int* records, i
  *     ox = 42 - opponent_width / 2, bx = by = vx = vy = wait = mine = theirs = serve_index = steps = 0).  Without it the
  *     game goes on: the scores run past points and terminal stays set.
  *
+ * Invaders (UNREAL_ARCADE_INVADERS): a fixed shooter on Breakout's field, border, life blocks and four actions
+ * (0 noop, 1 fire, 2 right, 3 left).  cfg: [0] UNREAL_ARCADE_INVADERS  [1] ticks per agent step less one, 0..7, as above  [2] alien_rows 1..4
+ * (the kernel clamps it)  [3] max_episode_steps >= 1  [4..5] seed (lo, hi)  [6] paddle_width, the cannon's (even, 4..24)
+ * [7] paddle_speed 1..8  [8] ball_speed, the shot's, 1..4 (clamped)  [9] lives 1..5  [10] serve_wait 0..255, the grace
+ * [11] life_reward -100..0  [12..15] alien rewards 0..100, top row first  [16] march_period 1..16  [17] descend 1..8
+ * [18] return_reward, 0 (no paddle returns a ball; never read)  [19] bomb_period 1..64  [20] bomb_speed 1..4 (clamped)
+ * [21..23] 0.
+ * record: [0] px  [1..2] sx, sy, the shot (sy = 0: none; in flight 6 <= sy <= 76)  [3..4] gx, gy, the grid's origin
+ * [5] direction +1 / -1  [6] lives  [7] live aliens (bit 8 r + c)  [8] march counter | bomb counter << 8 | grace counter
+ * << 16  [9] draw_index  [10] aliens-shot total  [11] lives-lost total  [12] waves-cleared total (the totals are never
+ * zeroed)  [13..15] the three bombs, x | y << 8 (0: the slot is free).
+ * Frame, back to front: black; Breakout's border and life blocks; alien (r, c), r < alien_rows, c < 8, x gx+8c..gx+8c+5,
+ * y gy+6r..gy+6r+3 in Breakout's colour of brick row r; the cannon y 78..79, x px..px+paddle_width-1 in (200, 72, 72); the
+ * bombs, 2 x 2 at (x, y) in (214, 214, 92), slot 2 behind slot 1 behind slot 0; the shot, 2 x 2 at (sx, sy) in
+ * (236, 236, 236).  One tick (an agent step is up to action_repeat ticks: "An agent step" above, where the game ends by
+ * its own conditions with lives <= 0 or no live alien):
+ *  1. steps += 1; action 2 / 3 moves the cannon by paddle_speed, clamped to [2, 82 - paddle_width]; action 1 with no shot
+ *     in flight starts one at (px + paddle_width / 2 - 1, 76); with a shot in flight it is a noop.
+ *  2. A shot (one fired in step 1 included) makes ball_speed micro-steps: sy -= 1; if sy < 6 the shot is removed; else if
+ *     the 2 x 2 box at (sx, sy) overlaps live aliens, the one with the lowest bit is cleared and pays its row's reward, the
+ *     aliens-shot total grows (and the waves-cleared total if it was the last), and the shot is removed.  A removed shot
+ *     has sx = sy = 0 and ends the micro-steps.
+ *  3. march += 1; at march >= march_period: march = 0 and the grid moves: nx = gx + 2 direction; if nx is outside 2..20:
+ *     gy = min(gy + descend, 84), direction = -direction, gx stays; else gx = nx.
+ *  4. The bombs in slot order, each bomb_speed micro-steps: y += 1; if y + 1 > 83 the bomb is removed; else if [x, x+1]
+ *     meets [px, px+paddle_width-1] and [y, y+1] meets [78, 79]: lives -= 1, the lives-lost total grows, the reward gets
+ *     life_reward, the shot and all three bombs are removed, grace = serve_wait + 1, and the step 4 of this tick ends.
+ *     Shot and bombs do not interact.
+ *  5. If grace > 0: grace -= 1 and no bomb is dropped in this tick.  bomb += 1; at bomb >= bomb_period: bomb = 0 and, if
+ *     the grace allows, an alien lives and a slot is free (the first free one is taken): u = Philox4x32-10(key = seed,
+ *     counter = (actor_base + b, episode, 0x494E5642, draw_index)), draw_index += 1; of the columns that hold a live
+ *     alien, in ascending order, number u[0] % (their count) is c; r is the row of its lowest live alien; the bomb starts
+ *     at (gx + 8 c + 2, gy + 6 r + 4) and first moves in the next tick.  Otherwise no draw is made.
+ *  6. If the grid moved in step 3, lives > 0, an alien lives and gy + 6 r + 3 >= 76 for the row r of the lowest live alien:
+ *     the invasion: the reward gets life_reward once, the lives-lost total grows by lives, lives = 0.
+ *  7. terminal: no live alien (the wave is cleared: success), lives <= 0, or steps >= max_episode_steps.  With
+ *     reset_on_terminal the next episode starts (episode += 1, px = 42 - paddle_width / 2, no shot, no bomb, gx = gy = 10,
+ *     direction = +1, all lives, the full grid, march = bomb = draw_index = steps = 0, grace = serve_wait).  Without it
+ *     the game goes on: lives fall below 0, the grid marches on (gy stops at 84), terminal stays set.
+ *
  * -EINVAL without a launch: B <= 0, H1 < 2, a null or misaligned pointer the entry uses (cfg included), actor_base < 0,
  * and in the rollout entries A != 4 or a next_lar row too short for A + 1 columns. */
 #define UNREAL_ARCADE_BREAKOUT 1
 #define UNREAL_ARCADE_DUEL 3
+#define UNREAL_ARCADE_INVADERS 5
 #define UNREAL_ARCADE_CFG_WORDS 24
 #define UNREAL_ARCADE_RECORD 16
 #define UNREAL_ARCADE_SERVE_STREAM 0x41524B53
+#define UNREAL_ARCADE_BOMB_STREAM 0x494E5642
 int unreal_arcade_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward, const int* count,
                         uint8_t* frames, const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
                         void* stream);

@@ -1,7 +1,7 @@
-// Stand-alone host program around the device arcade's own game, tick-loop and render functions (DESIGN §7m).
+// Stand-alone host program around the device arcade's own game, tick-loop and render functions (DESIGN §7m, §7n).
 // tools/check_arcade_host.py cuts those functions unchanged out of unreal_amd/csrc/arcade.hip (and the Philox draw out of
 // maze_common.h) into arcade_functions.inc, builds this file with AddressSanitizer and UBSan, and compares what it writes
-// with tests/repeat_model.py.  Nothing here runs on a GPU: the qualifiers of the device code are defined away.
+// with tests/repeat_model.py and tests/invaders_model.py.  Nothing here runs on a GPU: the qualifiers of the device code are defined away.
 //
 //   arcade_host_check IN OUT
 // IN:  int32 words: cfg[24], B, S, F, actor_base, then S x B actions, then S x B active flags.
@@ -26,6 +26,9 @@ using std::min;
 struct uint4 { uint32_t x, y, z, w; };
 static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return {x, y, z, w}; }
 static inline uint32_t __umulhi(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
+static inline int __clz(int x) { return x ? __builtin_clz((unsigned)x) : 32; }
+static inline int __popc(uint32_t x) { return __builtin_popcount(x); }
+static inline int __ffs(int x) { return __builtin_ffs(x); }
 
 namespace {
 #include "arcade_functions.inc"
@@ -105,6 +108,7 @@ int main(int argc, char** argv) {
   int bad = 2;
   if (in[0] == kArcadeBreakout) bad = run<Game, Rules>(in, out);
   else if (in[0] == kArcadeDuel) bad = run<DuelGame, DuelRules>(in, out);
+  else if (in[0] == kArcadeInvaders) bad = run<InvGame, InvRules>(in, out);
   fclose(out);
   return bad;
 }

@@ -10,8 +10,9 @@
   python tools/bench_arcade.py [--launches 200] [--steps 10] [--warmup 3] [--history 100] [--repeat 2] [--skip-trainer]
                                [--game breakout] [--action-repeat 1]
 
-`--game duel` measures the two-paddle duel on its default config instead of Breakout; its lines then also hold
-the game's name.  `--action-repeat K` measures the game at K ticks per agent step; its lines then also hold
+`--game duel` / `--game invaders` measures the two-paddle duel or invaders (§7n) on its default config instead
+of Breakout; its lines then also hold the game's name.  `--game A,B[,C]` times the step and the fused step of these games in
+turn in one process (lines of bench "arcade_games", keys <game>_us_<k> and <game>_fused_us_<k>; no maze kernels, no trainer).  `--action-repeat K` measures the game at K ticks per agent step; its lines then also hold
 action_repeat and, for the arcade kernels, µs per game tick: the launch's time over K (a step runs fewer ticks only where
 one ends the game, about once in a hundred steps on the default configs).  Prints one JSON line per measurement."""
 import argparse
@@ -100,14 +101,30 @@ def main():
     ap.add_argument("--history", type=int, default=100)
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--skip-trainer", action="store_true")
-    ap.add_argument("--game", default="breakout", choices=("breakout", "duel"))
+    ap.add_argument("--game", default="breakout", help="breakout, duel, invaders, or several of them joined by commas")
     ap.add_argument("--action-repeat", type=int, default=None, help="game ticks per agent step, 1..8 (DESIGN §7m)")
     args = ap.parse_args()
     from unreal_amd.environment.environment import Environment
     from unreal_amd.environment.arcade_environment import BatchedArcadeEnvironment
     from unreal_amd.environment.maze_environment import batched_maze_environment
-    arcade = "bench_" + args.game
     repeat = args.action_repeat
+    games = args.game.split(",")
+    if len(games) > 1:
+        for g in games:
+            Environment.register_arcade_config("bench_" + g, game=g, action_repeat=1 if repeat is None else repeat)
+        for rep in range(args.repeat):
+            for B in (512, 4096):
+                envs = {g: BatchedArcadeEnvironment(B, 3, DEV, config=Environment.ARCADE_CONFIG["bench_" + g]) for g in games}
+                row = dict(bench="arcade_games", B=B, repeat=rep, **({} if repeat is None else {"action_repeat": repeat}))
+                for k in range(2):                              # the games in turn, twice
+                    for g in games:
+                        row["%s_us_%d" % (g, k)] = round(1e3 * kernel_ms(envs[g], B, args.launches, entry="unreal_arcade_step"), 2)
+                        row["%s_fused_us_%d" % (g, k)] = round(1e3 * fused_ms(envs[g], B, args.launches), 2)
+                print(json.dumps(row), flush=True)
+                del envs
+                torch.cuda.empty_cache()
+        return
+    arcade = "bench_" + args.game
     Environment.register_arcade_config(arcade, game=args.game, action_repeat=1 if repeat is None else repeat)
     tag = {} if args.game == "breakout" else {"game": args.game}
     if repeat is not None:

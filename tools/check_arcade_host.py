@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """The device arcade's own game functions, tick loop and render on the CPU, under AddressSanitizer and UBSan, against the
-host models of tests/repeat_model.py.  No GPU is used and nothing loaded into Python is sanitized.
+host models of tests/repeat_model.py (Breakout and the duel) and tests/invaders_model.py (invaders, §7n).  No GPU is used and nothing loaded into Python is sanitized.
 
 The functions are cut unchanged out of unreal_amd/csrc/arcade.hip (everything from its constants to `frame_chunk`:
 `load_rules`, `step_game`, `game_ended`, `game_over`, `reset_game`, `store_game`, `step_ticks`, `frame_dirty`, `diff_dword`, ...,
-of both games) and the Philox draw out of maze_common.h, and compiled with tools/arcade_host_main.cpp into a stand-alone
-program.  Over every trace of tests/repeat_model.py (six random ones of 200 actors x 300 agent steps, two scripted ones) it
-is compared on every record, reward, terminal, ep_steps and episode, on every frame byte of the traces' watched actors, and
+of all three games) and the Philox draw out of maze_common.h, and compiled with tools/arcade_host_main.cpp into a stand-alone
+program.  Over every trace of tests/repeat_model.py (six random ones of 200 actors x 300 agent steps, two scripted ones) and
+of tests/invaders_model.py (four random ones, one scripted) it is compared on every record, reward, terminal, ep_steps and episode, on every frame byte of the traces' watched actors, and
 inside the program every difference dword of the dirty-row path against the full byte-wise difference of the two frames.
 
   python tools/check_arcade_host.py [--cxx clang++] [--keep DIR]"""
@@ -39,6 +39,7 @@ def main():
     ap.add_argument("--cxx", default=os.environ.get("CXX") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++")
     ap.add_argument("--keep", default="", help="work in this directory and keep it")
     args = ap.parse_args()
+    import invaders_model as IM
     import repeat_model as RM
     work = args.keep or tempfile.mkdtemp(prefix="arcade_host_")
     os.makedirs(work, exist_ok=True)
@@ -52,11 +53,14 @@ def main():
     subprocess.check_call([args.cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I", work, os.path.join(ROOT, "tools", "arcade_host_main.cpp"), "-o", exe])
     total = 0
-    for k in range(len(RM.TRACE_SETTINGS) + len(RM.SCRIPTED_SETTINGS)):
-        conf, tr = RM.trace_config(k), RM.run_trace(k)
+    traces = [(RM, k) for k in range(len(RM.TRACE_SETTINGS) + len(RM.SCRIPTED_SETTINGS))] + \
+             [(IM, k) for k in range(IM.N_TRACES)]
+    for n, (mod, k) in enumerate(traces):
+        conf, tr = mod.trace_config(k), mod.run_trace(k)
         S, B = tr["acts"].shape
         F = tr["pc"].shape[1]
-        head = np.concatenate([conf.block(RM.TRACE_SEED), np.array([B, S, F, 0], np.int32)])
+        head = np.concatenate([conf.block(mod.TRACE_SEED), np.array([B, S, F, 0], np.int32)])
+        k = n
         fin, fout = os.path.join(work, "trace%d.in" % k), os.path.join(work, "trace%d.out" % k)
         np.concatenate([head, tr["acts"].reshape(-1), tr["active"].reshape(-1)]).astype(np.int32).tofile(fin)
         subprocess.check_call([exe, fin, fout])            # a sanitizer report or a wrong difference dword ends it here
@@ -71,7 +75,7 @@ def main():
         for s in range(S):
             for b in range(F):
                 rec = tr["pre_reset"][s, b] if tr["active"][s, b] else tr["records"][s, b]
-                np.testing.assert_array_equal(frames[s, b], RM.frame_of(conf, rec).reshape(-1),
+                np.testing.assert_array_equal(frames[s, b], mod.frame_of(conf, rec).reshape(-1),
                                               err_msg="frame of trace %d step %d actor %d" % (k, s, b))
         total += int(tr["active"].sum())
         print("trace %d (%s, action_repeat %d, return_reward %d): %d agent steps, %d frames agree"

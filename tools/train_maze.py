@@ -2,14 +2,15 @@
 """Train the maze agent with the batched Trainer and log episode returns (GPU box).
 
 usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] [--steps 2e7] [--log-every 10]
-                                  [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout|duel]
+                                  [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout|duel|invaders]
                                   [--opponent-speed N] [--action-repeat K] [--return-reward R] [--seed S]
 `--groups G`: G sequential updates per process() call (update density x G, see Trainer).  One JSON line per
 `--log-every` calls: global_t, episodes finished since the last line, their mean return, losses, entropy, steps/s.
 `--arcade GAME`: train on the device arcade with that game's default config instead; a line then also holds
 bricks_per_episode and lives_lost_per_episode (differences of the records' totals over the episodes of the line); on the
 duel these are points_won_per_episode, points_lost_per_episode and matches_won_per_episode, and
-`--opponent-speed` overrides the opponent's 2 px per step.  `--action-repeat K` (1..8) and `--return-reward R` (0..100) are
+`--opponent-speed` overrides the opponent's 2 px per step; on invaders aliens_per_episode, lives_lost_per_episode
+and waves_cleared_per_episode.  `--action-repeat K` (1..8) and `--return-reward R` (0..100) are
 the arcade config's settings of those names: K game ticks per agent step, R paid for every ball the agent's
 paddle returns; steps, steps_per_s and episode lengths stay agent steps.  `--seed S` (arcade only) replaces the run's two
 seeds, the network's initial weights (1) and the trainer's draws and serve key (0xA3C), by S."""
@@ -34,7 +35,7 @@ ap.add_argument("--lr-scale", type=float, default=1.0)
 ap.add_argument("--max-time-step", type=float, default=0)
 ap.add_argument("--entropy-beta", type=float, default=None, help="override options_lab's 0.001 (a stated deviation)")
 ap.add_argument("--out", default="")
-ap.add_argument("--arcade", default="", help="a device arcade game (breakout, duel) instead of the maze")
+ap.add_argument("--arcade", default="", help="a device arcade game (breakout, duel, invaders) instead of the maze")
 ap.add_argument("--opponent-speed", type=int, default=None, help="the duel's opponent_speed (default: the game's)")
 ap.add_argument("--action-repeat", type=int, default=1, help="arcade: game ticks per agent step, 1..8")
 ap.add_argument("--return-reward", type=int, default=0, help="arcade: reward for a ball the agent's paddle returns, 0..100")
@@ -96,7 +97,8 @@ if out:
 global_t, t0, k = 0, time.time(), 0
 # the totals of the game's records (words 10 ..), never zeroed: per-line differences over the line's episodes
 TOTALS = {"breakout": ("bricks_per_episode", "lives_lost_per_episode"),
-          "duel": ("points_won_per_episode", "points_lost_per_episode", "matches_won_per_episode")}.get(args.arcade, ())
+          "duel": ("points_won_per_episode", "points_lost_per_episode", "matches_won_per_episode"),
+          "invaders": ("aliens_per_episode", "lives_lost_per_episode", "waves_cleared_per_episode")}.get(args.arcade, ())
 totals = tr.full_ring.actor_records[:, 10:10 + len(TOTALS)].sum(0).cpu() if args.arcade else None
 while global_t < args.steps:
     tr.process(None, global_t + k % args.log_every * args.actors * flags.n_step_TD, sync_stats=False)

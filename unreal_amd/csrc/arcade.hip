@@ -1,9 +1,10 @@
-// Device arcade (DESIGN §7k, §7l): games stepped AND rendered on the GPU, behind the ring and rollout arguments of the
-// maze entries.  Two games, both with ALE's minimal action set (0 noop, 1 fire, 2 right, 3 left), integer-only and a pure
-// function of (config block, seed, global actor, episode, actions): Breakout (game id 1) and the two-paddle duel (id 3),
-// which keeps Breakout's geometry, ball and serve and puts an opponent's paddle where the wall was.  The rules, the 24-word
-// config blocks and the 16-word per-actor records are documented with the entries in include/unreal_hip.h;
-// tests/arcade_model.py and tests/duel_model.py are the host models every kernel here is compared with bit for bit.
+// Device arcade (DESIGN §7k, §7l, §7n): games stepped AND rendered on the GPU, behind the ring and rollout arguments of the
+// maze entries.  Three games, all with ALE's minimal action set (0 noop, 1 fire, 2 right, 3 left), integer-only and a pure
+// function of (config block, seed, global actor, episode, actions): Breakout (game id 1), the two-paddle duel (id 3),
+// which keeps Breakout's geometry, ball and serve and puts an opponent's paddle where the wall was, and invaders (id 5), a
+// fixed shooter on Breakout's field.  The rules, the 24-word config blocks and the 16-word per-actor records are documented
+// with the entries in include/unreal_hip.h; tests/arcade_model.py, tests/duel_model.py and tests/invaders_model.py are the
+// host models every kernel here is compared with bit for bit.
 // The kernels read the game id from the block (uniform) and run that game's instance of one body.
 //
 // One actor per 256-thread workgroup.  The game logic is computed by every thread from the record (uniform: scalar
@@ -17,7 +18,7 @@
 
 namespace {
 
-constexpr int kArcadeBreakout = 1, kArcadeDuel = 3; // word 0 of the block
+constexpr int kArcadeBreakout = 1, kArcadeDuel = 3, kArcadeInvaders = 5;   // word 0 of the block
 constexpr int kArcadeRecord = 16;                   // int32 words per actor (the block has 24)
 constexpr int kMaxRows = 6, kCols = 10, kMaxBallSpeed = 4;
 constexpr int kMaxRepeat = 8;                       // ticks of one agent step at the most (word 1 of the block + 1)
@@ -450,10 +451,282 @@ __device__ __forceinline__ bool row_differs(const DuelDirty& d, int y) {
          (d.opp && (unsigned)(y - kOppY) < 2u) || (d.score && (unsigned)(y - 2) < 2u);
 }
 
+// ---- invaders (game id 5): a grid of aliens that marches and drops bombs, a cannon that shoots ----------------
+constexpr int kAlienCols = 8, kMaxAlienRows = 4, kAlienDX = 8, kAlienDY = 6, kAlienW = 6, kAlienH = 4;
+constexpr int kGridX0 = 10, kGridY0 = 10, kGridXMin = 2, kGridXMax = 20, kGridYMax = 84, kInvadeY = 76, kShotY = 76;
+constexpr int kBombs = 3, kMaxBombSpeed = 4;
+// counter word 2 of a bomb draw (word 3: the draw index)
+constexpr uint32_t kArcadeBombStream = 0x494E5642u;
+constexpr uint32_t kBomb = 214u | 214u << 8 | 92u << 16;
+
+struct InvRules {
+  int rows, max_steps, w, paddle_speed, ball_speed, lives, grace, life_reward, march_period, descend, bomb_period, bomb_speed;
+  int repeat;             // as in Rules (word 1)
+  uint64_t seed;
+  const int* row_reward;
+};
+
+__device__ __forceinline__ InvRules load_inv_rules(const int* cfg) {
+  InvRules r;
+  r.repeat = min(max(cfg[1], 0), kMaxRepeat - 1);
+  r.rows = min(max(cfg[2], 1), kMaxAlienRows);
+  r.max_steps = cfg[3];
+  r.seed = (uint64_t)(uint32_t)cfg[4] | ((uint64_t)(uint32_t)cfg[5] << 32);
+  r.w = cfg[6];
+  r.paddle_speed = cfg[7];
+  r.ball_speed = min(cfg[8], kMaxBallSpeed);
+  r.lives = cfg[9];
+  r.grace = min(max(cfg[10], 0), 255);
+  r.life_reward = cfg[11];
+  r.row_reward = cfg + 12;
+  r.march_period = cfg[16];
+  r.descend = cfg[17];
+  r.bomb_period = cfg[19];
+  r.bomb_speed = min(cfg[20], kMaxBombSpeed);
+  return r;
+}
+
+struct InvGame {
+  int px, sx, sy;         // cannon; the shot (sy = 0: none)
+  int gx, gy, dir, lives;
+  uint32_t aliens;        // bit 8 r + c: alien (r, c) is live
+  int march, bomb, grace; // the three counters of word 8
+  int draws;              // bomb draws of the running episode
+  int n_aliens, n_lost, n_cleared;     // running totals, never zeroed
+  int bombs[kBombs];      // x | y << 8, 0: the slot is free
+};
+
+__device__ __forceinline__ InvGame load_inv_game(const int* rec) {
+  InvGame g;
+  g.px = rec[0]; g.sx = rec[1]; g.sy = rec[2]; g.gx = rec[3]; g.gy = rec[4]; g.dir = rec[5]; g.lives = rec[6];
+  g.aliens = (uint32_t)rec[7];
+  g.march = rec[8] & 255; g.bomb = (rec[8] >> 8) & 255; g.grace = (rec[8] >> 16) & 511;
+  g.draws = rec[9]; g.n_aliens = rec[10]; g.n_lost = rec[11]; g.n_cleared = rec[12];
+  g.bombs[0] = rec[13]; g.bombs[1] = rec[14]; g.bombs[2] = rec[15];
+  return g;
+}
+
+__device__ __forceinline__ void store_game(int* rec, const InvGame& g) {
+  rec[0] = g.px; rec[1] = g.sx; rec[2] = g.sy; rec[3] = g.gx; rec[4] = g.gy; rec[5] = g.dir; rec[6] = g.lives;
+  rec[7] = (int)g.aliens;
+  rec[8] = g.march | g.bomb << 8 | g.grace << 16;
+  rec[9] = g.draws; rec[10] = g.n_aliens; rec[11] = g.n_lost; rec[12] = g.n_cleared;
+  rec[13] = g.bombs[0]; rec[14] = g.bombs[1]; rec[15] = g.bombs[2];
+}
+
+// the first state of an episode: the full grid at its origin marching right, all lives, the cannon in the middle, no shot,
+// no bomb, the grace running; the totals run on
+__device__ __forceinline__ InvGame reset_game(const InvRules& r, const InvGame& old) {
+  InvGame g = old;
+  g.px = 42 - r.w / 2; g.sx = 0; g.sy = 0; g.gx = kGridX0; g.gy = kGridY0; g.dir = 1; g.lives = r.lives;
+  g.aliens = (r.rows >= kMaxAlienRows) ? 0xFFFFFFFFu : (1u << (kAlienCols * r.rows)) - 1u;
+  g.march = 0; g.bomb = 0; g.grace = r.grace; g.draws = 0;
+  g.bombs[0] = 0; g.bombs[1] = 0; g.bombs[2] = 0;
+  return g;
+}
+
+// the live alien with the lowest bit that the 2 x 2 box at (x, y) overlaps, or -1
+__device__ __forceinline__ int alien_hit(const InvGame& g, int rows, int x, int y) {
+  int best = -1;
+#pragma unroll
+  for (int dy = 1; dy >= 0; --dy)
+#pragma unroll
+    for (int dx = 1; dx >= 0; --dx) {
+      const int rx = x + dx - g.gx, ry = y + dy - g.gy;
+      if (rx < 0 || rx >= kAlienDX * kAlienCols || ry < 0 || ry >= kAlienDY * rows) continue;
+      const int c = rx / kAlienDX, row = ry / kAlienDY;
+      if (rx - kAlienDX * c >= kAlienW || ry - kAlienDY * row >= kAlienH) continue;
+      const int bit = kAlienCols * row + c;
+      if ((g.aliens >> bit) & 1u) best = bit;           // (visited from the highest bit down: the lowest stays)
+    }
+  return best;
+}
+
+// row of the lowest live alien of the columns in `cols` (a byte of column bits); aliens & cols-in-every-row must not be 0
+__device__ __forceinline__ int lowest_alien_row(uint32_t aliens, uint32_t cols) {
+  const uint32_t m = aliens & (cols * 0x01010101u);
+  return (31 - __clz((int)m)) / kAlienCols;
+}
+
+// One tick of global actor `actor` in episode `ep` (invaders' rules 1..6 of the header); -> the tick's reward.
+__device__ __forceinline__ int step_game(InvGame& g, const InvRules& r, int a, int actor, int ep) {
+  int reward = 0;
+  // 1. the cannon
+  if (a == 2) g.px = min(g.px + r.paddle_speed, 82 - r.w);
+  if (a == 3) g.px = max(g.px - r.paddle_speed, kFieldL);
+  if (a == 1 && g.sy == 0) { g.sx = g.px + r.w / 2 - 1; g.sy = kShotY; }
+  // 2. the shot
+  if (g.sy != 0) {
+    for (int m = 0; m < r.ball_speed; ++m) {
+      g.sy -= 1;
+      if (g.sy < kFieldTop) { g.sx = 0; g.sy = 0; break; }
+      const int bit = alien_hit(g, r.rows, g.sx, g.sy);
+      if (bit >= 0) {
+        g.aliens &= ~(1u << bit);
+        g.n_aliens += 1;
+        if (g.aliens == 0) g.n_cleared += 1;
+        reward += r.row_reward[min(bit / kAlienCols, kMaxAlienRows - 1)];
+        g.sx = 0; g.sy = 0;
+        break;
+      }
+    }
+  }
+  // 3. the march
+  bool marched = false;
+  g.march += 1;
+  if (g.march >= r.march_period) {
+    g.march = 0;
+    marched = true;
+    const int nx = g.gx + 2 * g.dir;
+    if (nx < kGridXMin || nx > kGridXMax) { g.gy = min(g.gy + r.descend, kGridYMax); g.dir = -g.dir; }
+    else g.gx = nx;
+  }
+  // 4. the bombs, in slot order; a hit removes them all
+  bool hit = false;
+#pragma unroll
+  for (int k = 0; k < kBombs; ++k) {
+    if (hit || g.bombs[k] == 0) continue;
+    const int x = g.bombs[k] & 255;
+    int y = g.bombs[k] >> 8;
+    bool gone = false;
+    for (int m = 0; m < r.bomb_speed; ++m) {
+      y += 1;
+      if (y + 1 > 83) { gone = true; break; }
+      if (y + 1 >= kPaddleY && y <= kPaddleY + 1 && x + 1 >= g.px && x <= g.px + r.w - 1) { hit = true; break; }
+    }
+    g.bombs[k] = gone ? 0 : (x | y << 8);
+  }
+  if (hit) {
+    g.lives -= 1;
+    g.n_lost += 1;
+    reward += r.life_reward;
+    g.sx = 0; g.sy = 0;
+    g.bombs[0] = 0; g.bombs[1] = 0; g.bombs[2] = 0;
+    g.grace = r.grace + 1;
+  }
+  // 5. the drop
+  const bool graced = g.grace > 0;
+  if (graced) g.grace -= 1;
+  g.bomb += 1;
+  if (g.bomb >= r.bomb_period) {
+    g.bomb = 0;
+    const int slot = g.bombs[0] == 0 ? 0 : g.bombs[1] == 0 ? 1 : g.bombs[2] == 0 ? 2 : -1;
+    if (!graced && g.aliens != 0 && slot >= 0) {
+      uint32_t u[4];
+      philox4x32_10(r.seed, (uint64_t)(uint32_t)actor | ((uint64_t)(uint32_t)ep << 32),
+                    (uint64_t)kArcadeBombStream | ((uint64_t)(uint32_t)g.draws << 32), u);
+      g.draws += 1;
+      uint32_t cols = (g.aliens | g.aliens >> 8 | g.aliens >> 16 | g.aliens >> 24) & 255u;   // columns with a live alien
+      const int pick = (int)(u[0] % (uint32_t)__popc(cols));
+      for (int i = 0; i < pick; ++i) cols &= cols - 1u;                                  // drop the `pick` lowest ones
+      const int c = __ffs((int)cols) - 1;
+      const int row = lowest_alien_row(g.aliens, 1u << c);
+      const int bomb = (g.gx + kAlienDX * c + 2) | (g.gy + kAlienDY * row + kAlienH) << 8;
+      if (slot == 0) g.bombs[0] = bomb; else if (slot == 1) g.bombs[1] = bomb; else g.bombs[2] = bomb;
+    }
+  }
+  // 6. the invasion
+  if (marched && g.lives > 0 && g.aliens != 0 &&
+      g.gy + kAlienDY * lowest_alien_row(g.aliens, 255u) + kAlienH - 1 >= kInvadeY) {
+    reward += r.life_reward;
+    g.n_lost += g.lives;
+    g.lives = 0;
+  }
+  return reward;
+}
+
+__device__ __forceinline__ bool game_ended(const InvGame& g, const InvRules&) { return g.lives <= 0 || g.aliens == 0; }
+
+__device__ __forceinline__ bool game_over(const InvGame& g, const InvRules& r, int steps) {
+  return game_ended(g, r) || steps >= r.max_steps;
+}
+
+struct InvRow {
+  bool shot, paddle, alien, life, top;
+  bool bomb[kBombs];
+  int shift;              // bit of the row's first alien
+  uint32_t colour;        // of the row's aliens
+};
+
+__device__ __forceinline__ InvRow frame_row(const InvGame& g, const InvRules& r, int y) {
+  InvRow row;
+  row.shot = g.sy != 0 && (unsigned)(y - g.sy) < 2u;
+#pragma unroll
+  for (int k = 0; k < kBombs; ++k) row.bomb[k] = g.bombs[k] != 0 && (unsigned)(y - (g.bombs[k] >> 8)) < 2u;
+  row.paddle = (unsigned)(y - kPaddleY) < 2u;
+  const int ry = y - g.gy;
+  const int ar = (ry >= 0 && ry < kAlienDY * r.rows) ? ry / kAlienDY : 0;
+  row.alien = ry >= 0 && ry < kAlienDY * r.rows && ry - kAlienDY * ar < kAlienH;
+  row.shift = kAlienCols * ar;
+  row.colour = row_colour(ar);
+  row.life = (unsigned)(y - 2) < 2u;
+  row.top = y < kFieldTop;
+  return row;
+}
+
+// pixel x of that row: front to back shot, bombs (slot 0 first), cannon, aliens, lives, border
+__device__ __forceinline__ uint32_t pixel(const InvGame& g, const InvRules& r, const InvRow& row, int x) {
+  if (row.shot && (unsigned)(x - g.sx) < 2u) return kWhite;
+#pragma unroll
+  for (int k = 0; k < kBombs; ++k)
+    if (row.bomb[k] && (unsigned)(x - (g.bombs[k] & 255)) < 2u) return kBomb;
+  if (row.paddle && x >= g.px && x < g.px + r.w) return kPaddle;
+  const int rx = x - g.gx;
+  if (row.alien && (unsigned)rx < (unsigned)(kAlienDX * kAlienCols) && (rx & (kAlienDX - 1)) < kAlienW &&
+      ((g.aliens >> (row.shift + rx / kAlienDX)) & 1u))
+    return row.colour;
+  if (row.life && x >= 4 && x < 4 + 4 * g.lives && ((x - 4) & 3) < 2) return kWhite;
+  if (row.top || x < kFieldL || x > kFieldR) return kBorder;
+  return 0u;
+}
+
+// The rows in which the frames of two states can differ, as a set of the frame's 84 rows: the grid's rows in either state
+// if the mask or the origin changed, the rows of every bomb and of the shot in either state, the cannon's if it moved, the
+// lives' if one was lost.  Only drawn fields of the two records are compared, so any number of ticks may lie between them.
+struct InvDirty {
+  uint64_t lo;            // rows 0..63
+  uint32_t hi;            // rows 64..83 (bit 0: row 64)
+};
+
+// adds rows [y0, y1), clipped to the frame
+__device__ __forceinline__ void add_rows(InvDirty& d, int y0, int y1) {
+  y0 = max(y0, 0); y1 = min(y1, 84);
+  if (y0 >= y1) return;
+  const int a = min(y0, 64), b = min(y1, 64);
+  if (a < b) d.lo |= ((b == 64) ? ~0ull : (1ull << b) - 1ull) & ~((1ull << a) - 1ull);
+  const int c = max(y0, 64) - 64, e = max(y1, 64) - 64;
+  if (c < e) d.hi |= ((1u << e) - 1u) & ~((1u << c) - 1u);
+}
+
+__device__ __forceinline__ InvDirty frame_dirty(const InvGame& a, const InvGame& b, const InvRules& r) {
+  InvDirty d = {0ull, 0u};
+  if (a.aliens != b.aliens || a.gx != b.gx || a.gy != b.gy) {
+    add_rows(d, a.gy, a.gy + kAlienDY * r.rows);
+    add_rows(d, b.gy, b.gy + kAlienDY * r.rows);
+  }
+  if (a.sy != 0) add_rows(d, a.sy, a.sy + 2);
+  if (b.sy != 0) add_rows(d, b.sy, b.sy + 2);
+#pragma unroll
+  for (int k = 0; k < kBombs; ++k) {
+    if (a.bombs[k] != 0) add_rows(d, a.bombs[k] >> 8, (a.bombs[k] >> 8) + 2);
+    if (b.bombs[k] != 0) add_rows(d, b.bombs[k] >> 8, (b.bombs[k] >> 8) + 2);
+  }
+  if (a.px != b.px) add_rows(d, kPaddleY, kPaddleY + 2);
+  if (a.lives != b.lives) add_rows(d, 2, 4);
+  return d;
+}
+
+__device__ __forceinline__ bool row_differs(const InvDirty& d, int y) {
+  return y < 64 ? (d.lo >> y) & 1ull : (d.hi >> (y - 64)) & 1u;
+}
+
 // what the one body below asks of a game by type
 __device__ __forceinline__ void load(const int* cfg, const int* rec, Rules& r, Game& g) { r = load_rules(cfg); g = load_game(rec); }
 __device__ __forceinline__ void load(const int* cfg, const int* rec, DuelRules& r, DuelGame& g) {
   r = load_duel_rules(cfg); g = load_duel_game(rec);
+}
+__device__ __forceinline__ void load(const int* cfg, const int* rec, InvRules& r, InvGame& g) {
+  r = load_inv_rules(cfg); g = load_inv_game(rec);
 }
 
 // One agent step of global actor `actor` in episode `ep` ("An agent step" in the header): up to repeat + 1 ticks with the
@@ -603,6 +876,7 @@ __global__ __launch_bounds__(256) void arcade_step_kernel(ArcadeArgs p) {
   const int game = p.cfg[0];                    // (uniform) a block of another game: nothing is written
   if (game == kArcadeBreakout) step_actor<Game, Rules>(p, diff, &s_act);
   else if (game == kArcadeDuel) step_actor<DuelGame, DuelRules>(p, diff, &s_act);
+  else if (game == kArcadeInvaders) step_actor<InvGame, InvRules>(p, diff, &s_act);
 }
 
 template <class G, class R>
@@ -630,6 +904,7 @@ __global__ __launch_bounds__(256) void arcade_reset_kernel(ArcadeArgs p) {
   const int game = p.cfg[0];                    // (uniform) as in the step
   if (game == kArcadeBreakout) reset_actor<Game, Rules>(p);
   else if (game == kArcadeDuel) reset_actor<DuelGame, DuelRules>(p);
+  else if (game == kArcadeInvaders) reset_actor<InvGame, InvRules>(p);
 }
 
 // ---- host side: one check and one launcher for the four entries -------------------------------------------------------

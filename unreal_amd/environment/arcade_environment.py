@@ -1,6 +1,7 @@
-"""Device arcade (csrc/arcade.hip): games stepped and rendered on the GPU.  Two games with ALE's minimal
-action set (0 noop, 1 fire, 2 right, 3 left): Breakout, and the two-paddle duel that keeps Breakout's geometry, ball and
-serve and puts an opponent's paddle where the wall was.  Both are integer-only and a pure function of (config, seed, global
+"""Device arcade (csrc/arcade.hip): games stepped and rendered on the GPU.  Three games with ALE's
+minimal action set (0 noop, 1 fire, 2 right, 3 left): Breakout, the two-paddle duel that keeps Breakout's geometry, ball and
+serve and puts an opponent's paddle where the wall was, and invaders, a fixed shooter on Breakout's field: a marching grid
+of aliens that drop bombs, a cannon that shoots them.  All are integer-only and a pure function of (config, seed, global
 actor, episode, actions).  An agent step is `action_repeat` game ticks with one action (§7m).  The rules are written out
 with the entries in include/unreal_hip.h."""
 import numpy as np
@@ -9,10 +10,16 @@ import torch
 from . import environment
 from .. import ops
 
+# the two games of DESIGN §7k and §7l by id, kept as it was (tests/test_duel_cpu.py pins this dictionary as a whole), and
+# every game by id: what ArcadeConfig accepts and writes into word 0 of the block
 GAMES = {"breakout": ops.ARCADE_BREAKOUT, "duel": ops.ARCADE_DUEL}
-# the settings only one game has, with that game's defaults (None given to ArcadeConfig: the default)
+GAME_IDS = dict(GAMES, invaders=ops.ARCADE_INVADERS)
+# the settings that not every game has, with the game's defaults (None given to ArcadeConfig: the default); a setting is
+# refused by the games that do not list it (lives and life_reward: by the duel only)
 GAME_SETTINGS = {"breakout": dict(rows=6, row_rewards=None, lives=3, life_reward=0),
-                 "duel": dict(points=5, opponent_width=12, opponent_speed=2, win_reward=1, lose_reward=-1)}
+                 "duel": dict(points=5, opponent_width=12, opponent_speed=2, win_reward=1, lose_reward=-1),
+                 "invaders": dict(alien_rows=3, alien_rewards=None, lives=3, life_reward=0, march_period=4, descend=4,
+                                  bomb_period=12, bomb_speed=1)}
 
 
 def _int(name, v, lo, hi):
@@ -32,26 +39,32 @@ def _even(name, v, lo, hi):
 
 class ArcadeConfig(object):
     """Settings of one arcade game (Environment.register_arcade_config).  Raises ValueError outside the documented ranges,
-    and for a setting of the other game (rows, row_rewards, lives, life_reward are Breakout's; points, opponent_width,
-    opponent_speed, win_reward, lose_reward the duel's; None: the game's default).  Both games: action_repeat in 1..8 game
-    ticks per agent step, return_reward in 0..100 paid when the agent's paddle returns the ball."""
+    and for a setting of another game (rows, row_rewards are Breakout's; points, opponent_width, opponent_speed,
+    win_reward, lose_reward the duel's; alien_rows, alien_rewards, march_period, descend, bomb_period, bomb_speed
+    invaders'; lives and life_reward are Breakout's and invaders'; None: the game's default).  Every game: action_repeat in
+    1..8 game ticks per agent step.  return_reward in 0..100 is paid when the agent's paddle returns the ball; invaders has
+    no such event and takes only 0.  There paddle_width and paddle_speed are the cannon's, ball_speed the shot's, and
+    serve_wait the ticks after a reset or a lost life in which no bomb is dropped."""
     ACTION_SIZE = 4
     MAX_ACTION_REPEAT = 8
     MAX_ROWS, COLUMNS = 6, 10
     MAX_POINTS = 9                      # the score row holds nine blocks a side
+    MAX_ALIEN_ROWS, ALIEN_COLUMNS = 4, 8
 
     def __init__(self, game="breakout", rows=None, row_rewards=None, paddle_width=12, paddle_speed=3, ball_speed=2,
                  lives=None, serve_wait=8, life_reward=None, max_episode_steps=5000, points=None, opponent_width=None,
-                 opponent_speed=None, win_reward=None, lose_reward=None, action_repeat=1, return_reward=0):
-        if game not in GAMES:
-            raise ValueError("arcade game %r: known games are %s" % (game, sorted(GAMES)))
+                 opponent_speed=None, win_reward=None, lose_reward=None, action_repeat=1, return_reward=0, alien_rows=None,
+                 alien_rewards=None, march_period=None, descend=None, bomb_period=None, bomb_speed=None):
+        if game not in GAME_IDS:
+            raise ValueError("arcade game %r: known games are %s" % (game, sorted(GAME_IDS)))
         self.game = game
         own = dict(rows=rows, row_rewards=row_rewards, lives=lives, life_reward=life_reward, points=points,
                    opponent_width=opponent_width, opponent_speed=opponent_speed, win_reward=win_reward,
-                   lose_reward=lose_reward)
+                   lose_reward=lose_reward, alien_rows=alien_rows, alien_rewards=alien_rewards, march_period=march_period,
+                   descend=descend, bomb_period=bomb_period, bomb_speed=bomb_speed)
         for other, names in GAME_SETTINGS.items():
             for name in names:
-                if other != game and own[name] is not None:
+                if other != game and name not in GAME_SETTINGS[game] and own[name] is not None:
                     raise ValueError("%s is a setting of game %r, not of %r" % (name, other, game))
         own = {k: (own[k] if own[k] is not None else v) for k, v in GAME_SETTINGS[game].items()}
         if game == "breakout":
@@ -62,6 +75,18 @@ class ArcadeConfig(object):
             if isinstance(row_rewards, (str, bytes)) or not hasattr(row_rewards, "__len__") or len(row_rewards) != self.rows:
                 raise ValueError("row_rewards must hold rows = %d integers, not %r" % (self.rows, row_rewards))
             self.row_rewards = tuple(_int("row_rewards[%d]" % i, r, 0, 100) for i, r in enumerate(row_rewards))
+        elif game == "invaders":
+            self.alien_rows = _int("alien_rows", own["alien_rows"], 1, self.MAX_ALIEN_ROWS)
+            rewards = own["alien_rewards"]
+            if rewards is None:
+                rewards = (1,) * self.alien_rows
+            if isinstance(rewards, (str, bytes)) or not hasattr(rewards, "__len__") or len(rewards) != self.alien_rows:
+                raise ValueError("alien_rewards must hold alien_rows = %d integers, not %r" % (self.alien_rows, rewards))
+            self.alien_rewards = tuple(_int("alien_rewards[%d]" % i, r, 0, 100) for i, r in enumerate(rewards))
+            self.march_period = _int("march_period", own["march_period"], 1, 16)
+            self.descend = _int("descend", own["descend"], 1, 8)
+            self.bomb_period = _int("bomb_period", own["bomb_period"], 1, 64)
+            self.bomb_speed = _int("bomb_speed", own["bomb_speed"], 1, 4)
         else:
             self.points = _int("points", own["points"], 1, self.MAX_POINTS)
             self.opponent_width = _even("opponent_width", own["opponent_width"], 4, 24)
@@ -71,25 +96,25 @@ class ArcadeConfig(object):
         self.paddle_width = _even("paddle_width", paddle_width, 4, 24)
         self.paddle_speed = _int("paddle_speed", paddle_speed, 1, 8)
         self.ball_speed = _int("ball_speed", ball_speed, 1, 4)
-        if game == "breakout":
+        if game != "duel":
             self.lives = _int("lives", own["lives"], 1, 5)
         self.serve_wait = _int("serve_wait", serve_wait, 0, 255)
-        if game == "breakout":
+        if game != "duel":
             self.life_reward = _int("life_reward", own["life_reward"], -100, 0)
         # mandatory: a ball that loops between the walls never ends an episode on its own
         self.max_episode_steps = _int("max_episode_steps", max_episode_steps, 1, 2 ** 31 - 1)
         self.action_repeat = _int("action_repeat", action_repeat, 1, self.MAX_ACTION_REPEAT)
-        self.return_reward = _int("return_reward", return_reward, 0, 100)
+        self.return_reward = _int("return_reward", return_reward, 0, 0 if game == "invaders" else 100)
 
     @property
     def action_size(self):
         return self.ACTION_SIZE
 
     def block(self, seed):
-        """The int32 block of the kernels (UNREAL_ARCADE_CFG_WORDS words; both games' layouts: include/unreal_hip.h)."""
+        """The int32 block of the kernels (UNREAL_ARCADE_CFG_WORDS words; the games' layouts: include/unreal_hip.h)."""
         seed = int(seed) & (2 ** 64 - 1)
         w = np.zeros(ops.ARCADE_CFG_WORDS, dtype=np.int64)
-        w[0] = GAMES[self.game]
+        w[0] = GAME_IDS[self.game]
         w[1], w[18] = self.action_repeat - 1, self.return_reward
         w[3] = self.max_episode_steps
         w[4], w[5] = seed & 0xFFFFFFFF, seed >> 32
@@ -98,6 +123,10 @@ class ArcadeConfig(object):
         if self.game == "breakout":
             w[2], w[9], w[11] = self.rows, self.lives, self.life_reward
             w[12:12 + self.rows] = self.row_rewards
+        elif self.game == "invaders":
+            w[2], w[9], w[11] = self.alien_rows, self.lives, self.life_reward
+            w[12:12 + self.alien_rows] = self.alien_rewards
+            w[16], w[17], w[19], w[20] = self.march_period, self.descend, self.bomb_period, self.bomb_speed
         else:
             w[2], w[9], w[11] = self.points, self.opponent_width, self.lose_reward
             w[12], w[13] = self.win_reward, self.opponent_speed
@@ -165,7 +194,9 @@ class BatchedArcadeEnvironment(object):
     def current_records(self):
         """The game records -> int32 [B, 16].  Breakout: px, bx, by, vx, vy, wait, lives, bricks lo, hi, serve_index, then
         the running totals of bricks, lives lost and walls cleared.  Duel: px, bx, by, vx, vy, wait, ox, mine, theirs,
-        serve_index, then the running totals of points won, points lost and matches won.  Words 13..15 are 0."""
+        serve_index, then the running totals of points won, points lost and matches won.  Words 13..15 are 0.  Invaders: px,
+        sx, sy (0: no shot), gx, gy, direction, lives, alien mask, march | bomb << 8 | grace << 16 counters, draw_index,
+        then the running totals of aliens shot, lives lost and waves cleared, then the three bombs as x | y << 8 (0: free)."""
         return self.ring.actor_records.cpu().numpy().copy()
 
     def stop(self):
@@ -215,6 +246,8 @@ class ArcadeEnvironment(environment.Environment):
         rec = self._env.current_records()[0]
         if self._env.config.game == "duel":            # the match is won
             success = terminal and int(rec[7]) >= self._env.config.points
+        elif self._env.config.game == "invaders":      # the wave is cleared
+            success = terminal and not rec[7]
         else:                                          # the wall is cleared
             success = terminal and not (rec[7] | rec[8])
         self._last_full_state = {"success": bool(success)}

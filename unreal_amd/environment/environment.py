@@ -1,6 +1,6 @@
 """Environment factory with the reference's surface (/root/reference/environment/environment.py:11-102).
 
-The maze and the arcade (arcade_environment.py: Breakout and the two-paddle duel) are device environments; lab / indoor actors are HOST-FED (hostfed_environment.py) by simulator objects
+The maze and the arcade (arcade_environment.py: Breakout, the two-paddle duel and invaders) are device environments; lab / indoor actors are HOST-FED (hostfed_environment.py) by simulator objects
 the caller supplies, because deepmind_lab / minos / gym are not in the image.  Gym actors are host-fed through
 gym_environment.GymBatchSimulator (any object with gym's reset / step API)."""
 
@@ -80,7 +80,8 @@ class Environment(object):
     def register_arcade_config(env_name, game="breakout", rows=None, row_rewards=None, paddle_width=12, paddle_speed=3,
                                ball_speed=2, lives=None, serve_wait=8, life_reward=None, max_episode_steps=5000,
                                points=None, opponent_width=None, opponent_speed=None, win_reward=None, lose_reward=None,
-                               action_repeat=1, return_reward=0):
+                               action_repeat=1, return_reward=0, alien_rows=None, alien_rewards=None, march_period=None,
+                               descend=None, bomb_period=None, bomb_speed=None):
         """Arcade game of `env_name` on the device (env_type 'arcade'), with ALE's minimal action set
         (0 noop, 1 fire, 2 right, 3 left) on an 84 x 84 RGB frame.  Both games: paddle_width even in 4..24 px;
         paddle_speed in 1..8 px per step; ball_speed in 1..4 micro-steps per step; serve_wait in 0..255: a waiting ball
@@ -95,12 +96,21 @@ class Environment(object):
         a ball past the agent's pays lose_reward in -100..0 (None: -1); the first side with `points` in 1..9 (None: 5)
         wins the match, which ends the episode (success: the agent's); opponent_width even in 4..24 (None: 12);
         opponent_speed in 0..8 px per step (None: 2; 0: it stands).
-        Raises ValueError outside these ranges and for a setting of the other game."""
+        game="invaders" (DESIGN §7n): alien_rows in 1..4 rows of 8 aliens (None: 3) march 2 px every march_period in 1..16
+        ticks (None: 4) and come down by descend in 1..8 px at each edge (None: 4); alien_rewards: one integer in 0..100
+        per row from the top (None: all 1); every bomb_period in 1..64 ticks (None: 12) a random column drops a bomb, three
+        in flight at the most, falling bomb_speed in 1..4 px per tick (None: 1); a bomb on the cannon takes one of lives in
+        1..5 (None: 3) and pays life_reward in -100..0 (None: 0).  paddle_width and paddle_speed are the cannon's,
+        ball_speed the shot's, serve_wait the ticks without a new bomb after a reset or a lost life; return_reward must
+        be 0.  An episode also ends with the last life, when the aliens reach the cannon's rows, or with the last alien
+        (success).
+        Raises ValueError outside these ranges and for a setting of another game."""
         from .arcade_environment import ArcadeConfig
         Environment.ARCADE_CONFIG[env_name] = ArcadeConfig(game, rows, row_rewards, paddle_width, paddle_speed, ball_speed,
                                                            lives, serve_wait, life_reward, max_episode_steps, points,
                                                            opponent_width, opponent_speed, win_reward, lose_reward,
-                                                           action_repeat, return_reward)
+                                                           action_repeat, return_reward, alien_rows, alien_rewards,
+                                                           march_period, descend, bomb_period, bomb_speed)
 
     @staticmethod
     def arcade_config(env_name):

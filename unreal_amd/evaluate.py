@@ -18,7 +18,9 @@ name given to Environment.register_arcade_config) the actors play t
 other ending (last life, the config's max_episode_steps) counts under `timeouts`, and the result holds
 `bricks_per_episode` and `lives_lost_per_episode` from differences of the records' running totals.  On the duel
  success is a match won, `timeouts` counts the episodes that ended at the step limit, `losses` those the opponent
-won, and the differences of the totals are `points_won_per_episode` and `points_lost_per_episode`.  On both games
+won, and the differences of the totals are `points_won_per_episode` and `points_lost_per_episode`.  On invaders
+ success is a cleared wave, every other ending (last life, invasion, step limit) counts under `timeouts`, and the
+differences are `aliens_per_episode` and `lives_lost_per_episode` (an invasion counts the lives that were left).  On every game
 `mean_length` counts agent steps: with the config's `action_repeat = k` an episode of that length ran up to k
 game ticks per step."""
 import torch
@@ -95,7 +97,8 @@ class Evaluate(object):
         """The arcade's statistics: every episode ends in the environment (lives, wall or points, max_episode_steps)."""
         B, ring = self.B, self.env.ring
         duel = self.arcade_config.game == "duel"
-        # Breakout: bricks, lives lost, walls cleared; duel: points won, points lost, matches won.  Never zeroed.
+        # Breakout: bricks, lives lost, walls cleared; duel: points won, points lost, matches won; invaders: aliens shot,
+        # lives lost, waves cleared.  Never zeroed.
         tot = ring.actor_records[:, 10:13]
         ep0 = tot.cpu().numpy().copy()
         steps, counted = [0] * B, [False] * B
@@ -127,6 +130,9 @@ class Evaluate(object):
         if duel:
             res.update(timeouts=n - successes - losses, losses=losses, points_won_per_episode=sum(bricks) / float(n),
                        points_lost_per_episode=sum(lost) / float(n))
+        elif self.arcade_config.game == "invaders":
+            res.update(timeouts=n - successes, aliens_per_episode=sum(bricks) / float(n),
+                       lives_lost_per_episode=sum(lost) / float(n))
         else:
             res.update(timeouts=n - successes, bricks_per_episode=sum(bricks) / float(n),
                        lives_lost_per_episode=sum(lost) / float(n))

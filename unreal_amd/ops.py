@@ -219,6 +219,8 @@ def ring_view(ring, b0, b1):
 
 ARCADE_BREAKOUT, ARCADE_CFG_WORDS, ARCADE_RECORD = 1, 24, 16   # UNREAL_ARCADE_BREAKOUT / _CFG_WORDS / _RECORD
 ARCADE_DUEL = 3                              # UNREAL_ARCADE_DUEL (2 is no game: the kernels write nothing for it)
+ARCADE_INVADERS = 5                          # UNREAL_ARCADE_INVADERS
+ARCADE_BOMB_STREAM = 0x494E5642              # counter word 2 of an invaders bomb draw (UNREAL_ARCADE_BOMB_STREAM)
 ARCADE_SERVE_STREAM = 0x41524B53             # counter word 2 of a serve draw (UNREAL_ARCADE_SERVE_STREAM)
 MAZE_TOP_DOWN, MAZE_FIRST_PERSON = 0, 1       # the `view` of a maze (UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON)
 MAZE_FIRST_PERSON_GENERATED = 2               # first person, a generated block (UNREAL_MAZE_FIRST_PERSON_GENERATED)
