@@ -30,23 +30,43 @@ def xrow(p, mode):
     return mode(p)
 
 
-FRB, XROW, XPL, FWD_X = 252, 32, 12800, 21504
+FRB, XROW, XPL, FWD_X = 252, 32, 12800, 42336      # the frame is an fp16 image: 504 bytes per row, 42,336 in all
+G_R2B64 = G_W64                                     # ds_read2_b64: two accesses, each in 16-lane contiguous groups, 32 banks
 
 
-def conv1_reads(koff_fn=None, pix_base=None):
+def conv1_reads(form="read2_b64"):
+    """conv1 B fragments: 16 consecutive bytes of the image at 2 (252 row + 12 ox + k0 mod 24), as one ds_read2_b64 (what
+    the compiler emits) or as two ds_read_b64 (32-lane groups over 64 banks)."""
     ideal = real = 0
     for tt in range(25):
         for kc in range(6):
-            for dw in range(2):
+            for half in range(2):
                 addrs = []
                 for lane in range(64):
                     i, q = lane & 15, lane >> 4
                     pos = tt * 16 + i
                     k = 32 * kc + 8 * q
-                    a = (4 * (pos // 20)) * FRB + 12 * (pos % 20) + (k // 24) * FRB + k % 24 + 4 * dw
-                    addrs.append(a)
-                real += cycles(addrs, G_B32, 4, 32)
-                ideal += 2
+                    addrs.append(2 * ((4 * (pos // 20) + k // 24) * FRB + 12 * (pos % 20) + k % 24) + 8 * half)
+                if form == "read2_b64":
+                    real += cycles(addrs, G_R2B64, 8, 32)
+                    ideal += 4
+                else:
+                    real += cycles(addrs, G_B32, 8, 64)
+                    ideal += 2
+    return ideal, real
+
+
+def image_writes():
+    """the frame's expansion: thread's piece c (16 uint8) -> 32 bytes at 32 c, two ds_write_b128 (groups of 8 contiguous lanes,
+    32 banks); light waves take pieces (3 r + w) 64 + lane, the wave with 7 conv1 tiles 1152 + 64 r + lane"""
+    G_W128 = [list(range(8 * k, 8 * k + 8)) for k in range(8)]
+    ideal = real = 0
+    rounds = [(3 * r + w) * 64 for w in range(3) for r in range(6)] + [1152 + 64 * r for r in range(3)]
+    for base in rounds:
+        for half in range(2):
+            addrs = [32 * (base + lane) + 16 * half if base + lane < 1323 else None for lane in range(64)]
+            real += cycles(addrs, G_W128, 16, 32)
+            ideal += 8
     return ideal, real
 
 
@@ -83,7 +103,9 @@ def conv2_reads(mode="cur"):
 
 
 if __name__ == "__main__":
-    for name, (i, r) in (("conv1 pixel reads (ds_read2_b32)", conv1_reads()), ("c1 plane writes (ds_write_b64)", plane_writes()),
+    for name, (i, r) in (("conv1 fragment reads (ds_read2_b64)", conv1_reads()),
+                         ("  ... as two ds_read_b64", conv1_reads("read_b64")),
+                         ("image expansion (ds_write_b128)", image_writes()), ("c1 plane writes (ds_write_b64)", plane_writes()),
                          ("conv2 fragment reads (ds_read_b128)", conv2_reads())):
         print("%-40s ideal %5d  with conflicts %5d LDS cycles per frame" % (name, i, r))
 

@@ -9,9 +9,10 @@
 //   W1[(ky*8+kx)*3+cin][16], W2[(ky*4+kx)*16+cin][32]; outputs NHWC (flatten = model.py:331).
 //
 // The forward processes ONE frame per 256-thread workgroup at a time and runs TWO workgroups per CU, so that one
-// workgroup's staging / epilogue VALU overlaps the other's MFMAs; the uint8 frame reaches LDS by LDS-DMA
-// (global_load_lds, 1 KiB per wave instruction) issued a frame ahead; the frame is read from HBM exactly once and
-// conv1's output never leaves the CU on the inference path.  The backward is encoder_bwd_roles.h.
+// workgroup's staging / epilogue VALU overlaps the other's MFMAs; the uint8 frame is fetched into registers a frame
+// ahead and expanded ONCE into an fp16 image in LDS, from which conv1's MFMA operands are read with no conversion (the
+// 8x8 stride-4 patches overlap: converting at the read converted every pixel 3.6 times); the frame is read from HBM
+// exactly once and conv1's output never leaves the CU on the inference path.  The backward is encoder_bwd_roles.h.
 // MFMA operand convention (16x16x32): lane l = (i = l&15, q = l>>4) supplies A[row i][k = 8q + j] and
 // B[k = 8q + j][col i], j = 0..7; C/D: lane holds rows 4q..4q+3 of column i.
 #include "common.h"
@@ -55,10 +56,9 @@ constexpr int ZROWS = 111;                       // 11 x 10 halo grid + row 110 
 constexpr int ZPL = ZROWS * ZROW;                // 7104
 constexpr int Z_HALO = 30;                       // zero rows: 0..9 (y = -1), 10,20..90 (x = -1), 100..110 (y = 9)
 constexpr int FR_CHUNKS = FRAME_BYTES / 16;      // 1323 16-byte pieces of a frame
-constexpr int FR_DMA = (FR_CHUNKS + 63) / 64;    // 21 wave-wide LDS-DMA instructions (1 KiB each; the last one overshoots)
 
-// workgroup barrier that does NOT drain the vector-memory counter (an LDS-DMA stays in flight across it): LDS
-// writes / reads of this wave are retired first, the compiler may not move memory accesses across it
+// workgroup barrier that does NOT drain the vector-memory counter (global loads and stores stay in flight across it):
+// LDS writes / reads of this wave are retired first, the compiler may not move memory accesses across it
 #define WG_BARRIER()                                      \
   do {                                                    \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    \
@@ -77,20 +77,6 @@ constexpr int FR_DMA = (FR_CHUNKS + 63) / 64;    // 21 wave-wide LDS-DMA instruc
 __device__ __forceinline__ int xrow(int p) { return p ^ ((p >> 3) & 1); }
 __device__ __forceinline__ int kdeal(int q, int qq) { return 16 * (q >> 1) + 4 * (q & 1) + qq; }
 
-// One wave-wide LDS-DMA: 64 x 16 bytes, lane l's source -> LDS byte address lds_dst + 16 l (M0 = wave-uniform base).
-// Issued from inline asm ON PURPOSE: hipcc orders every later LDS read of the same __shared__ array behind a DMA it
-// can see (s_waitcnt vmcnt(0) at the first ds_read behind it), which would expose the HBM latency the DMA is there
-// to hide.  The kernel waits for it itself (s_waitcnt vmcnt(0) + barrier before the frame is read); no compiler-counted
-// vector load is in flight while a DMA is (the prefetch loads are issued after that wait and consumed before the next
-// DMA), so the compiler's own vmcnt bookkeeping stays exact.
-__device__ __forceinline__ void glds16(const uint8_t* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds_dst)
-               : "memory");
-}
-
 // ------------------------------------------------------------------------------------------------
 // Forward: conv1 8x8 s4 + ReLU -> conv2 4x4 s2 + ReLU, fused per frame, BOTH on v_mfma_f32_16x16x32_f16 with
 // fp32-grade error.  Operands are fp16 hi + lo with one power-of-two scale per tensor, like gemm_split.hip: conv1 takes
@@ -100,12 +86,22 @@ __device__ __forceinline__ void glds16(const uint8_t* gsrc, unsigned lds_dst) {
 // |c1[c]| <= 255 * frame_scale * sum_k |W1[k][c]| + |b1[c]| -- loose (by the 255 for the maze's 0 / 1 bytes), which
 // shortens the range over which hi + lo carry 22 bits but keeps the absolute error under 2^-32 of the largest c1.
 //
-// One frame per 256-thread workgroup at a time, two workgroups per CU (59 KB of LDS each):
-//   FR  the uint8 frame, by LDS-DMA (issued for frame n+1 as soon as conv1 of frame n has read FR; lands under conv2)
+// One frame per 256-thread workgroup at a time, two workgroups per CU (80,224 B of LDS each):
+//   IMG the frame as fp16 [84 rows][252], plain values of the bytes (the MFMAs see the operands u8x8_to_fop would give
+//       them).  There is ONE image, so it cannot be the target of a load in flight: frame n+1 waits in registers (up to
+//       six 16-byte pieces per thread, requested a whole frame earlier) and is expanded behind barrier [F1] of frame n,
+//       when conv1 has read the image; then frame n+2 is requested.  Nothing in the loop waits for vmcnt(0): the waits
+//       in front of the expansion are counted ones that leave this wave's latest stores (the 25.6 KB of saved conv1
+//       activation per frame, which drain slowly at > 4 TB/s) in flight -- which is why SAVE is a template parameter
+//       (the stores must be unconditional to be counted) and why the prologue's loads are consumed before the loop.
 //   X   c1 planes [2][400 pos][16 ch] fp16 (row p stored at p ^ ((p>>3)&1), as in the backward)
 //   P   partial conv2 tiles of the waves that own the upper half of K
 // conv1 is evaluated TRANSPOSED (D[channel][position] = W1^T x patches): a lane then holds 4 consecutive channels of
-// one position, i.e. one 16-byte store of the saved fp32 activation and one 8-byte store per plane.
+// one position, i.e. one 16-byte store of the saved fp32 activation and one 8-byte store per plane.  A conv1 B fragment
+// is 16 consecutive bytes of the image at 2 (252 row + 12 ox + k0 mod 24) -- a multiple of 8, not of 16: two 8-byte reads
+// (one ds_read2_b64: its 16-lane groups of one q read 24-byte-strided granules, conflict-free over 32 banks).  Fragment
+// addresses are table + table (ftab: the patch corner of each of the wave's tiles, koff: the K chunk), built once per
+// kernel; reads run C1_PF steps ahead of their MFMAs across tile pairs, pinned with sched_barrier like conv2's.
 // conv2: M = 81 positions (6 tiles), N = 32, K = 256 = 8 chunks of (2 taps x 16 channels).  No LDS is left for
 // W2, so its fragments live in registers and the work is cut so that a wave needs few of them: wave gw owns n-tile
 // gw & 1 and K half gw >> 1 (4 chunks: 32 registers of W2 fragments) for all 6 position tiles; the two halves of K
@@ -154,51 +150,34 @@ __device__ __forceinline__ fop8 u8x8_to_fop(uint32_t w0, uint32_t w1) {
   return __builtin_bit_cast(fop8, r) - k1024;
 }
 
-constexpr int FWD_FR = FR_DMA * 1024;            // 21504: uint8 frame + DMA overshoot
-constexpr int FWD_X = FWD_FR;
+constexpr int IMG_ROW = 2 * FRAME_ROW_BYTES;     // 504: bytes per frame row of the fp16 image
+constexpr int FWD_IMG = 2 * FRAME_BYTES;         // 42336: the frame as fp16, halfword e = byte e of the uint8 frame
+constexpr int FWD_X = FWD_IMG;
 constexpr int FWD_P = FWD_X + NPLF * XPL;
-constexpr int FWD_LDS = FWD_P + 2 * 6 * 1024;    // 59392
+constexpr int FWD_LDS = FWD_P + 2 * 6 * 1024;    // 80224
+constexpr int C1_PF = 2;                         // conv1: fragment reads this many steps ahead of their MFMAs
 static_assert(2 * FWD_LDS <= 160 * 1024, "two workgroups must fit one CU's LDS");
 
-// conv1 for TWO (or one) 16-position tiles, transposed: acc[r] = channel 4q + r at position 16 t + i
-template <bool TWO>
-__device__ __forceinline__ void conv1_tiles(const uint8_t* fr, unsigned char* xp, float* __restrict__ c1_out,
-                                            const u32x4v (&w1)[6][3], const int (&koff)[6], const f32x4& bias, float scale,
-                                            int ta, int tb, int i, int q, float& c1_max, float c1_scale) {
-  const int pa = ta * 16 + i, pb = tb * 16 + i;
-  const uint8_t* fa = fr + (4 * (pa / 20)) * FRAME_ROW_BYTES + 12 * (pa % 20);
-  const uint8_t* fb = fr + (4 * (pb / 20)) * FRAME_ROW_BYTES + 12 * (pb % 20);
-  f32x4 acca = {0.f, 0.f, 0.f, 0.f}, accb = {0.f, 0.f, 0.f, 0.f};
+// conv1 B fragment: 8 consecutive fp16 pixels of the image, 8-byte aligned (the offset is a multiple of 8, not of 16)
+__device__ __forceinline__ fop8 img_frag(const unsigned char* img, unsigned off) {
+  const u32x2v lo = *reinterpret_cast<const u32x2v*>(img + off), hi = *reinterpret_cast<const u32x2v*>(img + off + 8);
+  return __builtin_bit_cast(fop8, (u32x4v){lo[0], lo[1], hi[0], hi[1]});
+}
+
+// conv1 tile epilogue: acc[r] = channel 4q + r of one position -> scale, bias, ReLU; the saved fp32 activation (c1_dst: this
+// lane's 4 floats, SAVE only) and the lane's 8 bytes of both c1 planes (xdst: plane 0)
+template <bool SAVE>
+__device__ __forceinline__ void conv1_finish(const f32x4& acc, const f32x4& bias, float scale, float* __restrict__ c1_dst,
+                                             unsigned char* xdst, float& c1_max, float c1_scale) {
+  f32x4 v;
 #pragma unroll
-  for (int kc = 0; kc < 6; ++kc) {
-    const uint32_t* pa32 = reinterpret_cast<const uint32_t*>(fa + koff[kc]);
-    const fop8 xa = u8x8_to_fop(pa32[0], pa32[1]);
-    fop8 xb;
-    if (TWO) {
-      const uint32_t* pb32 = reinterpret_cast<const uint32_t*>(fb + koff[kc]);
-      xb = u8x8_to_fop(pb32[0], pb32[1]);
-    }
+  for (int r = 0; r < 4; ++r) v[r] = fmaxf(scale * acc[r] + bias[r], 0.f);
+  if (SAVE) *reinterpret_cast<f32x4*>(c1_dst) = v;
+  c1_max = fmaxf(fmaxf(c1_max, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
+  u32x2v pl[NPLF];
+  split4_fop(v, c1_scale, pl);
 #pragma unroll
-    for (int t = NPLF - 1; t >= 0; --t) {            // smallest weight term first
-      const fop8 w = __builtin_bit_cast(fop8, w1[kc][t]);
-      acca = MFMA_FOP(w, xa, acca);
-      if (TWO) accb = MFMA_FOP(w, xb, accb);
-    }
-  }
-#pragma unroll
-  for (int h = 0; h < (TWO ? 2 : 1); ++h) {
-    const f32x4& acc = h ? accb : acca;
-    const int pos = h ? pb : pa;
-    f32x4 v;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = fmaxf(scale * acc[r] + bias[r], 0.f);
-    if (c1_out) *reinterpret_cast<f32x4*>(c1_out + pos * C1_CH + 4 * q) = v;
-    c1_max = fmaxf(fmaxf(c1_max, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
-    u32x2v pl[NPLF];
-    split4_fop(v, c1_scale, pl);
-#pragma unroll
-    for (int u = 0; u < NPLF; ++u) *reinterpret_cast<u32x2v*>(xp + u * XPL + xrow(pos) * XROW + 8 * q) = pl[u];
-  }
+  for (int u = 0; u < NPLF; ++u) *reinterpret_cast<u32x2v*>(xdst + u * XPL) = pl[u];
 }
 
 // ---- the weights' share of the forward prologue: scales and operand fragments.  Every workgroup of every launch used to
@@ -241,9 +220,8 @@ __device__ __forceinline__ EncFwdScales enc_fwd_scales(const float* __restrict__
   return sc;
 }
 
-// conv1: A[row = channel i][k = 32kc + 8q + j], NPLF terms.  w1 keeps a third, unused slot per kc: with [6][NPLF] the
-// compiler schedules two of conv2's fragment reads differently (same results, but not the measured machine code).
-__device__ __forceinline__ void enc_fwd_w1_frags(const float* __restrict__ W1, float S_W1, int q, int i, u32x4v (&w1)[6][3]) {
+// conv1: A[row = channel i][k = 32kc + 8q + j], NPLF terms
+__device__ __forceinline__ void enc_fwd_w1_frags(const float* __restrict__ W1, float S_W1, int q, int i, u32x4v (&w1)[6][NPLF]) {
 #pragma unroll
   for (int kc = 0; kc < 6; ++kc) {
     f32x4 lo4, hi4;
@@ -291,7 +269,7 @@ __global__ __launch_bounds__(256) void encoder_prepare_kernel(const float* __res
   const int i = lane & 15, q = lane >> 4, nt = gw & 1, kh = gw >> 1;
   const EncFwdScales sc = enc_fwd_scales(W1, b1, W2, scale, red);
   if (tid == 0) prep[0] = (u32x4){__float_as_uint(sc.S_W1), __float_as_uint(sc.S_W2), __float_as_uint(sc.S_C1), __float_as_uint(scale)};
-  u32x4v w1[6][3];
+  u32x4v w1[6][NPLF];
   enc_fwd_w1_frags(W1, sc.S_W1, q, i, w1);
   if (gw == 0) {
 #pragma unroll
@@ -307,7 +285,7 @@ __global__ __launch_bounds__(256) void encoder_prepare_kernel(const float* __res
     for (int t = 0; t < NPLF; ++t) prep[ENC_PREP_W2 + (c * NPLF + t) * 256 + tid] = __builtin_bit_cast(u32x4, w2[c][t]);
 }
 
-template <bool BITS>
+template <bool BITS, bool SAVE>
 __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_t* __restrict__ frames,
                                                              const int* __restrict__ frame_idx, float scale,
                                                              const float* __restrict__ W1, const float* __restrict__ b1,
@@ -319,11 +297,12 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
   float f2_max = 0.f, c1_max = 0.f;            // max of the outputs this lane has stored (they are >= 0)
   const int tid = threadIdx.x, lane = tid & 63, gw = tid >> 6;
   const int i = lane & 15, q = lane >> 4;
-  uint8_t* fr = smem;
+  unsigned char* img = smem;
   unsigned char* xp = smem + FWD_X;
   unsigned char* pp = smem + FWD_P;
-  const unsigned lds_fr = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char*)smem;
   const int nt = gw & 1, kh = gw >> 1;         // conv2: this wave's n-tile and K half
+  // a block prepared for another frame scale carries the wrong S_C1: treat it as absent
+  if (prep && prep[0][3] != __float_as_uint(scale)) prep = nullptr;
 
   // power-of-two scales of W1, W2 and of the c1 planes (from the bound above) -- read from the prepared block
   // (unreal_encoder_prepare: once per weight update) or reduced here, once per workgroup
@@ -339,7 +318,7 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
   const float scale1 = scale * pow2_inv(S_W1);
   const float inv_c2 = pow2_inv(S_C1) * pow2_inv(S_W2);    // conv2: exact (both powers of two; |exponents| <= 100 each
                                                            // cannot meet here: c1's bound and W2's maximum are O(1))
-  u32x4v w1[6][3];                             // conv1: A[row = channel i][k = 32kc + 8q + j], NPLF terms
+  u32x4v w1[6][NPLF];                             // conv1: A[row = channel i][k = 32kc + 8q + j], NPLF terms
   if (prep) {
 #pragma unroll
     for (int kc = 0; kc < 6; ++kc)
@@ -348,10 +327,29 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
   } else {
     enc_fwd_w1_frags(W1, S_W1, q, i, w1);
   }
-  int koff[6];                                 // byte offset of patch element k = 32kc + 8q inside the frame
+  // conv1 fragment addresses, once per kernel.  Wave gw owns the tiles t = tt0 + 4j (j = 0..5, and j = 6 = tile 24 for the
+  // wave with tt0 = 0); lane (i, q) of tile t supplies position 16t + i and patch elements k = 32kc + 8q .. + 7:
+  //   koff[kc]  image byte offset of patch element k (row k / 24 of the patch, 24 bytes of a frame row per patch row)
+  //   ftab      image byte offset of the patch's corner, two tiles per register (j = 2p low, 2p + 1 high)
+  // The c1 store and plane offsets are linear in t (xrow only flips bit 0 of the row by bit 3 of i): one base each.
+  const int tt0 = (gw + 2) & 3;
+  unsigned koff[6];
 #pragma unroll
-  for (int kc = 0; kc < 6; ++kc) koff[kc] = ((32 * kc + 8 * q) / 24) * FRAME_ROW_BYTES + (32 * kc + 8 * q) % 24;
-  const f32x4 bias1 = *reinterpret_cast<const f32x4*>(b1 + 4 * q);
+  for (int kc = 0; kc < 6; ++kc) koff[kc] = ((32 * kc + 8 * q) / 24) * IMG_ROW + 2 * ((32 * kc + 8 * q) % 24);
+  unsigned ftab[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    unsigned pk = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int pos = min(16 * (tt0 + 4 * (2 * p + h)) + i, C1_POS - 1);
+      pk |= (unsigned)((4 * (pos / 20)) * IMG_ROW + 24 * (pos % 20)) << (16 * h);
+    }
+    ftab[p] = pk;
+  }
+  const int c1_lane = (16 * tt0 + i) * C1_CH + 4 * q;                       // floats; tile j: + 64 j positions
+  unsigned char* x_lane = xp + xrow(16 * tt0 + i) * XROW + 8 * q;           // plane 0; tile j: + 64 j rows
+  f32x4 bias1 = *reinterpret_cast<const f32x4*>(b1 + 4 * q);
   // conv2: B[k = 32kc + 8q + j][col = n = 16nt + i] = W2[(tap = 2kc + (q>>1)) * 16 + 8(q&1) + j][n], kc = 4kh + c
   fop8 w2[4][NPLF];
   if (prep) {
@@ -362,7 +360,7 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
   } else {
     enc_fwd_w2_frags(W2, S_W2, q, i, nt, kh, w2);
   }
-  const float bias2 = b2[16 * nt + i];
+  float bias2 = b2[16 * nt + i];
   // conv2 fragment of (position tile mt, K chunk c): byte offset inside a c1 plane of row (2oy + dy)*20 + 2ox + dx, channel
   // half q & 1, for this lane's position 16mt + i and tap 2(4kh + c) + (q >> 1) = (dy, dx); two offsets per register
   unsigned c2tab[12];
@@ -381,41 +379,102 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
     c2tab[e2] = pk;
   }
 
-  // uint8 frame (pool index fidx) -> FR (lane-linear 1 KiB pieces; wave gw issues pieces gw, gw + 4, ...)
-  auto dma_frame = [&](int fidx) {
-    const uint8_t* src = frames + (size_t)fidx * FRAME_BYTES;
-    for (int kk = gw; kk < FR_DMA; kk += 4) {
-      const int chunk = min(64 * kk + lane, FR_CHUNKS - 1);
-      glds16(src + 16 * chunk, __builtin_amdgcn_readfirstlane(lds_fr + 1024 * kk));
-    }
+  // The frame travels through registers: every thread fetches up to FR_V 16-byte pieces one frame ahead, and behind [F1]
+  // (the image conv1 has just read is dead) expands them to fp16 into the image and requests the frame after.  Light
+  // waves (6 conv1 tiles) take 6 pieces per lane, the wave with 7 tiles the remaining 171 pieces (3 rounds).
+  const int lw = gw - (gw > 2);                // rank among the light waves 0, 1, 3 (unused on wave 2)
+  const int pc0 = (tt0 == 0 ? 18 * 64 : lw * 64) + lane, pcs = tt0 == 0 ? 64 : 3 * 64;
+  u32x4 pf[FR_V];
+  auto load_frame = [&](int fidx) {
+    const u32x4* src = reinterpret_cast<const u32x4*>(frames + (size_t)fidx * FRAME_BYTES);
+    // every lane loads in every round (index clamped; only the stores are predicated): six loads in straight-line code keep
+    // the compiler's vmcnt waits in front of stage_frame counted ones
+#pragma unroll
+    for (int r = 0; r < FR_V; ++r) pf[r] = src[min(pc0 + r * pcs, FR_CHUNKS - 1)];
   };
+  auto stage_frame = [&]() {
+#pragma unroll
+    for (int r = 0; r < FR_V; ++r)
+      if (pc0 + r * pcs < FR_CHUNKS) {
+        fop8* dst = reinterpret_cast<fop8*>(img + 32 * (pc0 + r * pcs));
+        dst[0] = u8x8_to_fop(pf[r][0], pf[r][1]);
+        dst[1] = u8x8_to_fop(pf[r][2], pf[r][3]);
+      }
+  };
+  // the prologue's loads are consumed HERE: a register still pending at the loop's entry would make the compiler wait for
+  // vmcnt(0) at its first use inside the loop, every frame, behind the frame loads and the c1 stores
+#pragma unroll
+  for (int kc = 0; kc < 6; ++kc)
+#pragma unroll
+    for (int t = 0; t < NPLF; ++t) asm volatile("" : "+v"(w1[kc][t]));
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int t = 0; t < NPLF; ++t) asm volatile("" : "+v"(w2[c][t]));
+  asm volatile("" : "+v"(bias1), "+v"(bias2));
   const int stride = gridDim.x;
-  dma_frame(frame_idx[blockIdx.x]);            // the launch guarantees gridDim.x <= N
-  // index of the frame whose DMA is issued behind the next [F1]
-  int fidx_next = blockIdx.x + stride < N ? frame_idx[blockIdx.x + stride] : 0;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  load_frame(frame_idx[blockIdx.x]);           // the launch guarantees gridDim.x <= N
+  // pool index of the frame requested behind the next [F1]
+  int fidx_next = blockIdx.x + 2 * stride < N ? frame_idx[blockIdx.x + 2 * stride] : 0;
+  stage_frame();
+  if (blockIdx.x + stride < N) load_frame(frame_idx[blockIdx.x + stride]);
   WG_BARRIER();
 
-  // Two barriers per frame.  [F1] conv1 done: X complete, the frame buffer conv1 read is dead -> the DMA of the next
-  // frame starts into it.  [F2] conv2 done: P complete, X dead; every wave has first waited for its pieces of that DMA.
-  // Then every wave finishes its three output tiles and goes on to conv1 of the next frame; P and X are rewritten only
-  // behind the next [F1] / [F2].  (A second frame buffer, the DMA two frames ahead, measured neutral: the wait before
-  // [F2] is not the DMA -- vmcnt also counts the 25.6 KB of conv1 activations this wave has stored, and at 4.2 TB/s of
-  // HBM traffic those drain slowly; profiles/r03_encoder_fwd_ab.log.)
+  // Two barriers per frame.  [F1] conv1 done: X complete, the image conv1 read is dead -> the next frame is expanded
+  // into it from the registers and the frame after that is requested.  [F2] conv2 done: P complete, X dead, the next image
+  // complete.  Then every wave finishes its three output tiles and goes on to conv1 of the next frame; P and X are
+  // rewritten only behind the next [F1] / [F2].  The loop holds ordinary loads and stores only and no vmcnt wait of its
+  // own: a frame's pieces are used a whole frame after their request, and nothing waits for the c1 stores to drain.
   for (int n = blockIdx.x; n < N; n += stride) {
-    int zero;                                  // opaque 0, new every frame: keeps conv1's address sets out of the registers
-    asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
     {
-      float* c1n = c1_out ? c1_out + (size_t)n * (C1_POS * C1_CH) : nullptr;
-      // 25 tiles over 4 waves = 7 + 6 + 6 + 6
-      for (int tt = (gw + 2) & 3; tt < 25; tt += 8) {
-        if (tt + 4 < 25) conv1_tiles<true>(fr, xp, c1n, w1, koff, bias1, scale1, tt, tt + 4, i + zero, q, c1_max, S_C1);
-        else conv1_tiles<false>(fr, xp, c1n, w1, koff, bias1, scale1, tt, tt, i + zero, q, c1_max, S_C1);
+      float* c1n = SAVE ? c1_out + (size_t)n * (C1_POS * C1_CH) + c1_lane : nullptr;
+      // 25 tiles over 4 waves = 7 + 6 + 6 + 6: three tile pairs as 18 steps s = 6p + kc (fragments C1_PF steps ahead, the
+      // next pair's first reads under this pair's last MFMAs), then tile 24 on the wave that owns it.  Per tile: kc
+      // ascending, the low weight term before the high one.
+      fop8 xf[C1_PF + 1][2];
+      auto frag = [&](int st, fop8 (&dst)[2]) {
+        const unsigned ko = koff[st % 6];
+        dst[0] = img_frag(img, (ftab[st / 6] & 0xffffu) + ko);
+        dst[1] = img_frag(img, (ftab[st / 6] >> 16) + ko);
+      };
+#pragma unroll
+      for (int st = 0; st < C1_PF; ++st) frag(st, xf[st]);
+      f32x4 acca = {0.f, 0.f, 0.f, 0.f}, accb = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int st = 0; st < 18; ++st) {
+        const int p = st / 6, kc = st % 6;
+        if (st + C1_PF < 18) frag(st + C1_PF, xf[(st + C1_PF) % (C1_PF + 1)]);
+#pragma unroll
+        for (int t = NPLF - 1; t >= 0; --t) {            // smallest weight term first
+          const fop8 w = __builtin_bit_cast(fop8, w1[kc][t]);
+          acca = MFMA_FOP(w, xf[st % (C1_PF + 1)][0], acca);
+          accb = MFMA_FOP(w, xf[st % (C1_PF + 1)][1], accb);
+        }
+        // nothing crosses the step boundary: left alone, the scheduler sinks every read to just before its MFMA
+        __builtin_amdgcn_sched_barrier(0);
+        if (kc == 5) {
+          conv1_finish<SAVE>(acca, bias1, scale1, c1n + (2 * p) * 64 * C1_CH, x_lane + (2 * p) * 64 * XROW, c1_max, S_C1);
+          conv1_finish<SAVE>(accb, bias1, scale1, c1n + (2 * p + 1) * 64 * C1_CH, x_lane + (2 * p + 1) * 64 * XROW, c1_max, S_C1);
+          acca = (f32x4){0.f, 0.f, 0.f, 0.f};
+          accb = (f32x4){0.f, 0.f, 0.f, 0.f};
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      if (tt0 == 0) {                                    // tile 24
+        fop8 xs[6];
+#pragma unroll
+        for (int kc = 0; kc < 6; ++kc) xs[kc] = img_frag(img, (ftab[3] & 0xffffu) + koff[kc]);
+#pragma unroll
+        for (int kc = 0; kc < 6; ++kc)
+#pragma unroll
+          for (int t = NPLF - 1; t >= 0; --t) acca = MFMA_FOP(__builtin_bit_cast(fop8, w1[kc][t]), xs[kc], acca);
+        conv1_finish<SAVE>(acca, bias1, scale1, c1n + 6 * 64 * C1_CH, x_lane + 6 * 64 * XROW, c1_max, S_C1);
       }
     }
-    WG_BARRIER();     // [F1] c1 planes complete; this frame's buffer is dead
-    if (n + stride < N) dma_frame(fidx_next);
-    fidx_next = n + 2 * stride < N ? frame_idx[n + 2 * stride] : 0;
+    WG_BARRIER();     // [F1] c1 planes complete; this frame's image is dead
+    if (n + stride < N) stage_frame();
+    if (n + 2 * stride < N) load_frame(fidx_next);
+    fidx_next = n + 3 * stride < N ? frame_idx[n + 3 * stride] : 0;
     // conv2: this wave's n-tile and K half (4 chunks) of all 6 position tiles -- 24 steps s = 4u + c (u: tile in this
     // wave's order, own tiles first; c: K chunk), fragments FWD_PF steps ahead
     f32x4 acc[3];
@@ -453,7 +512,6 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
         }
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the frame conv1 reads next has landed
     WG_BARRIER();     // [F2]
     {
       // this wave's three tiles mt = 3kh + u: lower + upper K half (the sum of two floats does not depend on which wave
@@ -497,7 +555,7 @@ __global__ __launch_bounds__(256, 2) void encoder_fwd_kernel(int N, const uint8_
       }
     }
   }
-  // one commit per workgroup and slot (the frame buffer is dead: no DMA was issued behind the last frame's [F1], and the
+  // one commit per workgroup and slot (the image is dead: nothing was staged behind the last frame's [F1], and the
   // waves still in their epilogue only read P).  The 2,048 waves of a launch end within microseconds of each other: each
   // would find the slots at their old values and issue its own serialised atomics
   {
@@ -526,12 +584,10 @@ int unreal_encoder_fwd(int N, const uint8_t* frames, const int* frame_idx, float
   if (((uintptr_t)prepared) & 15) return UNREAL_EINVAL;
   const u32x4* prep = static_cast<const u32x4*>(prepared);
   int blocks = min(N, 512);             // one frame per workgroup at a time, two workgroups per CU
-  if (relu_bits)
-    hipLaunchKernelGGL(encoder_fwd_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, N, frames, frame_idx,
-                       frame_scale, W1, b1, W2, b2, c1_out, f2_out, relu_bits, f2_absmax, c1_absmax, prep);
-  else
-    hipLaunchKernelGGL(encoder_fwd_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, N, frames, frame_idx,
-                       frame_scale, W1, b1, W2, b2, c1_out, f2_out, relu_bits, f2_absmax, c1_absmax, prep);
+  auto kernel = relu_bits ? (c1_out ? encoder_fwd_kernel<true, true> : encoder_fwd_kernel<true, false>)
+                          : (c1_out ? encoder_fwd_kernel<false, true> : encoder_fwd_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, N, frames, frame_idx, frame_scale, W1, b1, W2,
+                     b2, c1_out, f2_out, relu_bits, f2_absmax, c1_absmax, prep);
   return unreal_launch_status();
 }
 

@@ -284,15 +284,21 @@ class UnrealModel(object):
             self._shadow, self._shadow_set = sh, ss
         self._shadow_set.refresh()
         if self.prepare_encoder and not self.hw:
-            # the conv weights' share of encoder_fwd's prologue (scales + MFMA operand fragments), once per update instead
-            # of once per workgroup of each of the ~24 encoder launches that follow
-            p = self.p
-            self._enc_prep = ops.encoder_prepare(p["W_base_conv1"], p["b_base_conv1"], p["W_base_conv2"], self.frame_scale,
-                                                 self._enc_prep)
+            self._prepare_encoder()
+
+    def _prepare_encoder(self):
+        """The conv weights' share of encoder_fwd's prologue (scales + MFMA operand fragments), once per update instead of
+        once per workgroup of each of the ~24 encoder launches that follow.  The block holds the c1 planes' scale, which
+        depends on the frame scale: it is valid for the current weights AND self.frame_scale."""
+        p = self.p
+        self._enc_prep = ops.encoder_prepare(p["W_base_conv1"], p["b_base_conv1"], p["W_base_conv2"], self.frame_scale,
+                                             self._enc_prep)
+        self._enc_prep_scale = self.frame_scale
 
     # False: every encoder_fwd workgroup derives scales and fragments itself (identical results; A/B: r04_ab_summary.md 3f)
     prepare_encoder = True
     _enc_prep = None
+    _enc_prep_scale = None        # the frame scale self._enc_prep was made for
 
     @property
     def enc_prepared(self):
@@ -301,6 +307,8 @@ class UnrealModel(object):
             return None
         if self._enc_prep is None or self._shadow_stale:
             self.refresh_shadows()
+        if self._enc_prep_scale != self.frame_scale:      # bind_frame_scale, or a batch-1 runner's 1/255, since it was made
+            self._prepare_encoder()
         return self._enc_prep
 
     @property
