@@ -167,6 +167,33 @@ int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, cons
                                     float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A, int idx_base_actor,
                                     int view, int N, const int* cfg, int actor_base, int* goal, int* layout,
                                     int* ep_steps, int* episode, int* heading, void* stream);
+/* Time-limit bootstrapping: the two rollout entries above with a final-observation store, for the
+ * first-person views without goal sense (views 1, 2, 5, 6; any other view: -EINVAL).  A step is a TRUNCATION when the
+ * episode ends in it only because of the step limit: steps >= max_episode_steps, no ending pickup, and no goal reached
+ * unless goals respawn (then a goal in that step is no end).  A truncation writes s_{t+1}, the observation the limit cut
+ * off, to final_obs[b] (one 21168-byte frame per actor of the launch) before the next episode's first view goes to the ring
+ * slot, and commits 2 instead of 1 to r_terminal[slot], out_terminal[b] and terminal_end[b]; every consumer of these words
+ * tests them for non-zero.  A true end writes 1 and leaves final_obs[b] alone.  Everything else is written as by the
+ * entries above.  -EINVAL also for a null final_obs or one not 16-byte aligned. */
+int unreal_maze_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                                float* episode_reward, float* score_out, int* score_valid, int* active, int* active_log_t,
+                                int* n_steps, int* terminal_end, int* next_idx /*nullable*/, float* next_lar /*nullable*/,
+                                int lar_ld, int lar_col0, int A, int idx_base_actor, int view, int N, const int* cfg,
+                                int actor_base, int* goal, int* layout, int* ep_steps, int* episode, int* heading,
+                                uint8_t* final_obs, void* stream);
+int unreal_maze_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                       const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                       int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
+                                       uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                       int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                       int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                       int* active, int* active_log_t, int* n_steps, int* terminal_end,
+                                       int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0,
+                                       int A, int idx_base_actor, int view, int N, const int* cfg, int actor_base,
+                                       int* goal, int* layout, int* ep_steps, int* episode, int* heading,
+                                       uint8_t* final_obs, void* stream);
 /* The objective vectors of a goal-sense maze, from the per-actor records the maze entries keep behind
  * `heading` (record_words int32 each, >= 8): for every actor b, {w5 / 32, w6 / 32, w7 / 512} of record b go to
  * r_objective[(b * H1 + count[b] % H1) * 3 ..), the slot of the actor's current observation, and, with next_lar, to
@@ -335,6 +362,29 @@ int unreal_arcade_policy_rollout_step(int B, int H1, const float* X, int ldx, co
                                       int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0,
                                       int A, int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
                                       int* episode, int* records, void* stream);
+/* Time-limit bootstrapping: the two rollout entries above with a final-observation store, as
+ * unreal_maze_rollout_step_tl.  A step is a truncation when, after its last tick, steps >= max_episode_steps and the game
+ * itself has not ended (Breakout: a life left and a brick left; duel: neither side at `points`; invaders: a life left and
+ * an alien left); a step that ends the game and reaches the limit is a true end.  -EINVAL also for a null final_obs or
+ * one not 16-byte aligned. */
+int unreal_arcade_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                  int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                  int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                  int* out_terminal, float* episode_reward, float* score_out, int* score_valid, int* active,
+                                  int* active_log_t, int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
+                                  float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                                  const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
+                                  uint8_t* final_obs, void* stream);
+int unreal_arcade_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                         const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                         int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
+                                         uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                         int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                         int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                         int* active, int* active_log_t, int* n_steps, int* terminal_end,
+                                         int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0,
+                                         int A, int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
+                                         int* episode, int* records, uint8_t* final_obs, void* stream);
 /* host-fed environments (environment/hostfed_environment.py): environment.process + experience.add_frame of
  * every actor where active[b] != 0, for simulators on the host.  `staged` holds one uint8 frame per actor, frame_stride
  * bytes apart as in the ring (a multiple of 16 within [1200, 691200]: 20 x 20 x 3 .. 480 x 480 x 3 rounded up to 16).
@@ -394,6 +444,28 @@ int unreal_replay_sample_rp(int B, int H, int H1, const int* coin, const double*
 int unreal_base_returns(int B, int T, const float* rewards, const float* values, const int* n_steps,
                         const float* boot_v, const int* terminal_end, double gamma, float* R_out, float* adv_out,
                         void* stream);
+/* GAE(lambda) with time-limit bootstrapping, one fp64 backward scan per actor:
+ *   next_v = terminal_end[b] == 1 ? 0 : boot_v[b]   (1: a true end; 2: cut off at the step limit, boot_v = V(final
+ *   observation); 0: still running, boot_v = V(s_T)); for t = n_steps[b] - 1 .. 0: delta = r_t + gamma next_v - v_t,
+ *   gae = delta + gamma lambda gae, adv_t = gae, R_t = gae + v_t, next_v = v_t; rows t >= n_steps[b] are 0.
+ * lambda = 1 is the n-step return of unreal_base_returns, which stays the default path's.  -EINVAL: B or T <= 0, a null
+ * pointer, lambda outside [0, 1]. */
+int unreal_base_returns_tl(int B, int T, const float* rewards, const float* values, const int* n_steps,
+                           const float* boot_v, const int* terminal_end, double gamma, double lambda, float* R_out,
+                           float* adv_out, void* stream);
+/* The bootstrap pass's inputs with time-limit bootstrapping, per actor b of a group whose first actor is idx_base_actor
+ * of the ring.  terminal_end[b] == 2 (and 1 <= n = n_steps[b] <= T): frame_idx[b] = final_base + idx_base_actor + b (the
+ * actor's final-observation slot: final_base = actors of the whole ring * H1), c0 / h0 [b] = rows (n - 1) B + b of ws_c /
+ * ws_h (the recurrent state after the last step taken), xcat[b][col0 .. col0 + A] = one-hot actions[(n - 1) B + b] |
+ * rewards[(n - 1) B + b] (unclipped).  Any other actor: frame_idx[b] = (idx_base_actor + b) H1 + count[b] % H1, carried_c /
+ * carried_h [b], one-hot last_action[b] | last_reward[b].  c0 null: no state is written (feed-forward); xcat null: no
+ * columns.  -EINVAL: a size <= 0, H1 < 2, a negative base, a null pointer the call uses, A >= 256, ld < col0 + A + 1. */
+int unreal_boot_gather(int B, int T, int H1, int idx_base_actor, int final_base, int A, const int* count,
+                       const int* terminal_end, const int* n_steps, const int* last_action, const float* last_reward,
+                       const int* actions, const float* rewards, const float* carried_c /*nullable*/,
+                       const float* carried_h /*nullable*/, const float* ws_c /*nullable*/, const float* ws_h /*nullable*/,
+                       int* frame_idx, float* c0 /*nullable*/, float* h0 /*nullable*/, float* xcat /*nullable*/, int ld,
+                       int col0, void* stream);
 int unreal_vr_returns(int B, int L, const int* seq_idx, const int* seq_len, const float* r_reward,
                       const int* r_terminal, const float* boot_v, double gamma, float* R_out, void* stream);
 int unreal_pc_returns(int B, int L, const int* seq_idx, const int* seq_len, const float* r_pc,

@@ -4,6 +4,7 @@
 usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] [--steps 2e7] [--log-every 10]
                                   [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout|duel|invaders]
                                   [--opponent-speed N] [--action-repeat K] [--return-reward R] [--seed S]
+                                  [--max-episode-steps N] [--bootstrap-timeouts] [--gae-lambda L]
 `--groups G`: G sequential updates per process() call (update density x G, see Trainer).  One JSON line per
 `--log-every` calls: global_t, episodes finished since the last line, their mean return, losses, entropy, steps/s.
 `--arcade GAME`: train on the device arcade with that game's default config instead; a line then also holds
@@ -13,7 +14,9 @@ duel these are points_won_per_episode, points_lost_per_episode and
 and waves_cleared_per_episode.  `--action-repeat K` (1..8) and `--return-reward R` (0..100) are
 the arcade config's settings of those names: K game ticks per agent step, R paid for every ball the agent's
 paddle returns; steps, steps_per_s and episode lengths stay agent steps.  `--seed S` (arcade only) replaces the run's two
-seeds, the network's initial weights (1) and the trainer's draws and serve key (0xA3C), by S."""
+seeds, the network's initial weights (1) and the trainer's draws and serve key (0xA3C), by S.
+`--max-episode-steps N` (arcade only) is the config's step limit.  `--bootstrap-timeouts` (arcade only) and `--gae-lambda L`
+are the Trainer's rollout options of DESIGN §7o."""
 import argparse
 import json
 import os
@@ -40,10 +43,16 @@ ap.add_argument("--opponent-speed", type=int, default=None, help="the duel's opp
 ap.add_argument("--action-repeat", type=int, default=1, help="arcade: game ticks per agent step, 1..8")
 ap.add_argument("--return-reward", type=int, default=0, help="arcade: reward for a ball the agent's paddle returns, 0..100")
 ap.add_argument("--seed", type=int, default=None, help="arcade: seed of the weights and of the trainer (default: 1 and 0xA3C)")
+ap.add_argument("--max-episode-steps", type=int, default=None, help="arcade: the step limit (default: the game's 5000)")
+ap.add_argument("--bootstrap-timeouts", action="store_true",
+                help="arcade: an episode cut off at the step limit bootstraps from V(final observation) (DESIGN 7o)")
+ap.add_argument("--gae-lambda", type=float, default=None, help="GAE(lambda) instead of the n-step return, 0..1 (DESIGN 7o)")
 args = ap.parse_args()
 if not args.arcade and (args.action_repeat != 1 or args.return_reward != 0 or args.seed is not None or
-                        args.opponent_speed is not None):
-    ap.error("--action-repeat, --return-reward, --seed and --opponent-speed are settings of --arcade GAME")
+                        args.opponent_speed is not None or args.max_episode_steps is not None or
+                        args.bootstrap_timeouts):
+    ap.error("--action-repeat, --return-reward, --seed, --opponent-speed, --max-episode-steps and --bootstrap-timeouts "
+             "are settings of --arcade GAME")
 device = torch.device("cuda", 0)
 
 
@@ -54,8 +63,9 @@ def build_arcade_trainer(args, device):
     from unreal_amd.options import get_options
     from unreal_amd.train.rmsprop_applier import RMSPropApplier
     from unreal_amd.train.trainer import Trainer, log_uniform
+    limit = {} if args.max_episode_steps is None else dict(max_episode_steps=args.max_episode_steps)
     Environment.register_arcade_config(args.arcade, game=args.arcade, opponent_speed=args.opponent_speed,
-                                       action_repeat=args.action_repeat, return_reward=args.return_reward)
+                                       action_repeat=args.action_repeat, return_reward=args.return_reward, **limit)
     flags = get_options("training", preset="lab", argv=["--env_type", "arcade", "--env_name", args.arcade])
     net = UnrealModel(Environment.get_action_size("arcade", args.arcade), 0, -1, flags.use_lstm, flags.use_pixel_change,
                       flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
@@ -66,12 +76,15 @@ def build_arcade_trainer(args, device):
     tr = Trainer(0, net, lr0, None, applier, "arcade", args.arcade, flags.use_lstm, flags.use_pixel_change,
                  flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
                  flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
-                 batch_size=args.actors, seed=0xA3C if args.seed is None else args.seed, groups=args.groups)
+                 batch_size=args.actors, seed=0xA3C if args.seed is None else args.seed, groups=args.groups,
+                 bootstrap_timeouts=args.bootstrap_timeouts, gae_lambda=args.gae_lambda)
     tr.prepare()
     return flags, net, tr
 
 
 flags, net, tr = build_arcade_trainer(args, device) if args.arcade else build_trainer(args, 0, 1, device)
+if not args.arcade:                        # (the reference's maze: the returns kernel is chosen per rollout, nothing is allocated)
+    tr.gae_lambda = tr.check_rollout_options(flags.env_type, flags.env_name, False, args.gae_lambda)[1]
 tr.initial_learning_rate *= args.lr_scale
 if args.entropy_beta is not None:
     tr.entropy_beta = args.entropy_beta

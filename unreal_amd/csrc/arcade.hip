@@ -91,7 +91,10 @@ struct ArcadeArgs {
   int* ep_steps;         // [B] steps taken in the running episode
   int* episode;          // [B] episode index (-1 before the first reset)
   int* records;          // [B][16] per-actor records
-  const int* mask;       // reset only (nullable): the actors to reset
+  union {                // (one word: the step kernels of the entries without a store keep the arguments they had)
+    const int* mask;     // reset only (nullable): the actors to reset
+    uint8_t* final_obs;  // the _tl entries only: [B] frames, the final observation of an episode cut off at the step limit
+  };
 };
 
 // the block's settings, clamped to what the loops and the colour table below are built for (ArcadeConfig checks them)
@@ -791,7 +794,10 @@ __device__ __forceinline__ void store_frame(uint8_t* dst, const G& g, const R& r
 }
 
 // One agent step of actor blockIdx.x of game (G, R).  `diff` (|s_{t+1} - s_t|, byte-wise) and `s_act` are the kernel's LDS.
-template <class G, class R>
+// TL (the _tl entries): an episode that ends in this step only because of the step limit keeps its final
+// observation in final_obs[b] and is flagged 2 instead of 1.  An instance of its own: the step kernel sits on a register
+// tier's edge (§7n), so the plain instance's code stays what it is.
+template <class G, class R, bool TL = false>
 __device__ __forceinline__ void step_actor(const ArcadeArgs& p, uint4* diff, int* s_act) {
   const int* cfg = p.cfg;
   const int b = blockIdx.x;
@@ -828,6 +834,8 @@ __device__ __forceinline__ void step_actor(const ArcadeArgs& p, uint4* diff, int
   const bool terminal = game_over(g, rules, steps);
   const RingStep ring = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
   uint8_t* dst = p.frames + ((size_t)b * H1 + ring.nslot) * FRAME_BYTES;
+  const bool cut = TL && ring.reset && !game_ended(g, rules);      // (uniform) ended by the step limit alone
+  uint8_t* fin = TL ? p.final_obs + (size_t)b * FRAME_BYTES : nullptr;
 
   // s_{t+1} and, in the rows where it can differ, s_t, 16 bytes per lane: the new chunk is stored unless the episode
   // restarts, the difference goes to LDS
@@ -838,6 +846,9 @@ __device__ __forceinline__ void step_actor(const ArcadeArgs& p, uint4* diff, int
     if (c < kChunks) {
       const uint4 v = frame_chunk(g, rules, c);
       if (!ring.reset) reinterpret_cast<uint4*>(dst)[c] = v;
+      if constexpr (TL) {
+        if (cut) reinterpret_cast<uint4*>(fin)[c] = v;
+      }
       diff[c] = make_uint4(diff_dword(old, rules, dirty, 4 * c, v.x), diff_dword(old, rules, dirty, 4 * c + 1, v.y),
                            diff_dword(old, rules, dirty, 4 * c + 2, v.z), diff_dword(old, rules, dirty, 4 * c + 3, v.w));
     }
@@ -867,6 +878,13 @@ __device__ __forceinline__ void step_actor(const ArcadeArgs& p, uint4* diff, int
     p.ep_steps[b] = ring.reset ? 0 : steps;
     p.episode[b] = epi + (ring.reset ? 1 : 0);
     rollout_commit(p, b, ring, ns, a, reward);
+    if constexpr (TL) {
+      if (cut) {                                  // the three words the commits above have set to 1
+        p.r_terminal[ring.base] = 2;
+        if (p.out_terminal) p.out_terminal[b] = 2;
+        p.terminal_end[b] = 2;
+      }
+    }
   }
 }
 
@@ -877,6 +895,16 @@ __global__ __launch_bounds__(256) void arcade_step_kernel(ArcadeArgs p) {
   if (game == kArcadeBreakout) step_actor<Game, Rules>(p, diff, &s_act);
   else if (game == kArcadeDuel) step_actor<DuelGame, DuelRules>(p, diff, &s_act);
   else if (game == kArcadeInvaders) step_actor<InvGame, InvRules>(p, diff, &s_act);
+}
+
+// the rollout step of the _tl entries
+__global__ __launch_bounds__(256) void arcade_step_tl_kernel(ArcadeArgs p) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act;
+  const int game = p.cfg[0];                    // (uniform) as above
+  if (game == kArcadeBreakout) step_actor<Game, Rules, true>(p, diff, &s_act);
+  else if (game == kArcadeDuel) step_actor<DuelGame, DuelRules, true>(p, diff, &s_act);
+  else if (game == kArcadeInvaders) step_actor<InvGame, InvRules, true>(p, diff, &s_act);
 }
 
 template <class G, class R>
@@ -929,12 +957,16 @@ bool arcade_args_ok(ArcadeEntry e, const ArcadeArgs& p) {
 }
 
 // fills in the tail, checks and launches (one launch shape: no label is recorded)
+// `final_obs` (the _tl entries, which are rollout entries): [B] frames, 16-byte aligned; selects the kernel that keeps them
 int arcade_launch(ArcadeEntry e, ArcadeArgs& p, const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
-                  void* stream) {
+                  void* stream, bool tl = false, uint8_t* final_obs = nullptr) {
   p.cfg = cfg; p.actor_base = actor_base; p.ep_steps = ep_steps; p.episode = episode; p.records = records;
+  if (tl) p.final_obs = final_obs;
   if (!arcade_args_ok(e, p)) return UNREAL_EINVAL;
+  if (tl && (!final_obs || ((uintptr_t)final_obs & 15) || (e != kRollout && e != kPolicy))) return UNREAL_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   if (e == kReset) hipLaunchKernelGGL(arcade_reset_kernel, dim3(p.B), dim3(256), 0, s, p);
+  else if (tl) hipLaunchKernelGGL(arcade_step_tl_kernel, dim3(p.B), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(arcade_step_kernel, dim3(p.B), dim3(256), 0, s, p);
   return unreal_launch_status();
 }
@@ -995,6 +1027,40 @@ int unreal_arcade_policy_rollout_step(int B, int H1, const float* X, int ldx, co
                active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
                Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
   return arcade_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, stream);
+}
+
+// The two rollout entries with time-limit bootstrapping: `final_obs` [B] frames.
+
+int unreal_arcade_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                  int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                  int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                  int* out_terminal, float* episode_reward, float* score_out, int* score_valid, int* active,
+                                  int* active_log_t, int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
+                                  int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg, int actor_base,
+                                  int* ep_steps, int* episode, int* records, uint8_t* final_obs, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
+  return arcade_launch(kRollout, p, cfg, actor_base, ep_steps, episode, records, stream, true, final_obs);
+}
+
+int unreal_arcade_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                         const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                         int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
+                                         uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                         int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                         int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                         int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                         float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                                         const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
+                                         uint8_t* final_obs, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
+               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
+  return arcade_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, stream, true, final_obs);
 }
 
 }  // extern "C"

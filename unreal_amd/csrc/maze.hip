@@ -245,7 +245,10 @@ struct MazeArgs {
   int* ep_steps;         // [B] steps taken in the running episode
   int* episode;          // [B] episode index (-1 before the first reset)
   int* heading;          // [B] first person: heading of the camera; navigation / generated blocks: the per-actor records
-  const int* mask;       // reset only (nullable): the actors to reset
+  union {                // (one word: the step kernels of the entries without a store keep the arguments they had)
+    const int* mask;     // reset only (nullable): the actors to reset
+    uint8_t* final_obs;  // the _tl entries only: [B] frames, the final observation of an episode cut off at the step limit
+  };
 };
 
 // APG actors per workgroup: 8 when the batch fills the chip (the wall image is built once per workgroup: ~2.5 us of VALU),
@@ -923,10 +926,14 @@ __device__ __forceinline__ int fp_record_words(bool styled) {
 // NAV): a goal-sense block (kMazeSense): the record ends in the distance field, words 5..7 are kept.
 // FORAGE (with NAV, never SENSE): a forage block (kMazeForage): pickup kinds in `fs`, words 5..7 count them;
 // the collection is resolved before the terminal, which an ending kind sets; without a goal the goal cell is (-1, -1).
-template <int N, bool NAV, bool GEN, bool SENSE = false, bool FORAGE = false>
+// TL (the _tl entries, never SENSE): an episode that ends in this step only because of the step limit keeps
+// its final observation in final_obs[b] and is flagged 2 instead of 1; instances of their own, so the plain ones keep
+// their code.
+template <int N, bool NAV, bool GEN, bool SENSE = false, bool FORAGE = false, bool TL = false>
 __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s, ForageLds<N>* fs = nullptr) {
   static_assert(NAV || !SENSE, "a goal-sense block is a navigation block");
   static_assert(!FORAGE || (NAV && !SENSE), "a forage block is a navigation block without goal sense");
+  static_assert(!TL || !SENSE, "the final state's objective vector is not kept");
   const int* cfg = p.cfg;
   const int b = blockIdx.x;
   const int H1 = p.H1;
@@ -1060,6 +1067,9 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s, ForageLd
   const bool reset = ring.reset;
   const bool show_goal = cfg[2] & kMazeShowGoal;
   uint8_t* dst = p.frames + ((size_t)b * H1 + ring.nslot) * FRAME_BYTES;
+  // (uniform) ended by the step limit alone: no ending pickup, and no goal unless goals respawn
+  const bool cut = TL && reset && !(FORAGE && ends) && !(at_goal && !(NAV && (mode & kNavRespawn)));
+  uint8_t* fin = TL ? p.final_obs + (size_t)b * FRAME_BYTES : nullptr;
 
   int ex = nx, ey = ny, eh = nh;          // the eye of s_{t+1}: the respawn start when a goal respawns
   if (NAV) {
@@ -1089,6 +1099,9 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s, ForageLd
     if (c < kChunks) {
       const uint4 v = s.img[c];
       if (!reset) reinterpret_cast<uint4*>(dst)[c] = v;     // (a discard's slot is the old one: read above)
+      if constexpr (TL) {
+        if (cut) reinterpret_cast<uint4*>(fin)[c] = v;
+      }
       s.img[c] = absdiff_u8x16(v, old[k]);
     }
   }
@@ -1178,10 +1191,17 @@ __device__ __forceinline__ void fp_step(const MazeArgs& p, FpLds<N>& s, ForageLd
     p.ep_steps[b] = reset ? 0 : steps;
     p.episode[b] = epi + (reset ? 1 : 0);
     rollout_commit(p, b, ring, ns, a, reward);
+    if constexpr (TL) {
+      if (cut) {                           // the three words the commits above have set to 1
+        p.r_terminal[base] = 2;
+        if (p.out_terminal) p.out_terminal[b] = 2;
+        p.terminal_end[b] = 2;
+      }
+    }
   }
 }
 
-template <int N, bool GEN, bool SENSE = false>
+template <int N, bool GEN, bool SENSE = false, bool TL = false>
 __device__ __forceinline__ void fp_step_entry(const MazeArgs& p) {
   const int* cfg = p.cfg;
   // (uniform) a block of another grid size, or a generated block in a static kernel (and the reverse): nothing is written
@@ -1196,8 +1216,8 @@ __device__ __forceinline__ void fp_step_entry(const MazeArgs& p) {
   if constexpr (SENSE) {
     if (nav) fp_step<N, true, GEN, true>(p, s);      // (a goal-sense block without the navigation header: malformed)
   } else {
-    if (nav) fp_step<N, true, GEN>(p, s);
-    else fp_step<N, false, GEN>(p, s);
+    if (nav) fp_step<N, true, GEN, false, false, TL>(p, s);
+    else fp_step<N, false, GEN, false, false, TL>(p, s);
   }
 }
 
@@ -1208,6 +1228,10 @@ __global__ __launch_bounds__(256) void maze_fp_step_kernel(MazeArgs p) { fp_step
 // static step's
 template <int N>
 __global__ __launch_bounds__(256) void maze_fp_gen_step_kernel(MazeArgs p) { fp_step_entry<N, true>(p); }
+
+// the rollout steps of the _tl entries, static and generated
+template <int N, bool GEN>
+__global__ __launch_bounds__(256) void maze_fp_step_tl_kernel(MazeArgs p) { fp_step_entry<N, GEN, false, true>(p); }
 
 // the steps of goal-sense blocks (views kFirstPersonSense / kFirstPersonGenSense): kernels of their own again
 template <int N, bool GEN>
@@ -1229,6 +1253,16 @@ __global__ __launch_bounds__(256) void maze_fp_forage_step_kernel(MazeArgs p) {
   __shared__ FpLds<N> s;
   __shared__ ForageLds<N> fs;
   fp_step<N, true, GEN, false, true>(p, s, &fs);
+}
+
+template <int N, bool GEN>
+__global__ __launch_bounds__(256) void maze_fp_forage_step_tl_kernel(MazeArgs p) {
+  const int* cfg = p.cfg;
+  if (!fp_forage_block<N, GEN>(cfg)) return;           // (uniform) as above
+  if (p.pol_x && p.A != ((maze_nav_ext(cfg)[3] & kNavLabActions) ? 6 : 4)) return;
+  __shared__ FpLds<N> s;
+  __shared__ ForageLds<N> fs;
+  fp_step<N, true, GEN, false, true, true>(p, s, &fs);
 }
 
 template <int N, bool NAV, bool GEN, bool SENSE = false, bool FORAGE = false>
@@ -1393,6 +1427,15 @@ bool maze_args_ok(MazeEntry e, const MazeArgs& p, int view, int N) {
          (p.A == 4 || (p.A == 6 && view != kTopDown));
 }
 
+// the step kernels of the _tl entries: first-person views without goal sense (maze_launch refuses the others)
+template <int N>
+void maze_launch_tl_n(int view, const MazeArgs& p, hipStream_t s) {
+  if (view == kFirstPersonForage) hipLaunchKernelGGL((maze_fp_forage_step_tl_kernel<N, false>), dim3(p.B), dim3(256), 0, s, p);
+  else if (view == kFirstPersonGenForage) hipLaunchKernelGGL((maze_fp_forage_step_tl_kernel<N, true>), dim3(p.B), dim3(256), 0, s, p);
+  else if (view == kFirstPersonGen) hipLaunchKernelGGL((maze_fp_step_tl_kernel<N, true>), dim3(p.B), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((maze_fp_step_tl_kernel<N, false>), dim3(p.B), dim3(256), 0, s, p);
+}
+
 template <int N>
 void maze_launch_n(bool reset, int view, const MazeArgs& p, hipStream_t s) {
   if (view == kFirstPersonForage) {
@@ -1426,11 +1469,27 @@ void maze_launch_n(bool reset, int view, const MazeArgs& p, hipStream_t s) {
 
 // fills in the maze tail, checks, records the top-down step's tier (the first-person kernels have one launch shape and
 // record no label) and launches
+// `final_obs` (the _tl entries, which are rollout entries of first-person views without goal sense): [B] frames, 16-byte
+// aligned; selects the kernels that keep them
 int maze_launch(MazeEntry e, MazeArgs& p, int view, int N, const int* cfg, int actor_base, int* goal, int* layout,
-                int* ep_steps, int* episode, int* heading, void* stream) {
+                int* ep_steps, int* episode, int* heading, void* stream, bool tl = false, uint8_t* final_obs = nullptr) {
   p.cfg = cfg; p.actor_base = actor_base; p.goal = goal; p.layout = layout; p.ep_steps = ep_steps; p.episode = episode;
   p.heading = heading;
+  if (tl) p.final_obs = final_obs;
   if (!maze_args_ok(e, p, view, N)) return UNREAL_EINVAL;
+  if (tl) {
+    if (!final_obs || ((uintptr_t)final_obs & 15) || (e != kRollout && e != kPolicy)) return UNREAL_EINVAL;
+    if (view != kFirstPerson && view != kFirstPersonGen && view != kFirstPersonForage && view != kFirstPersonGenForage)
+      return UNREAL_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    switch (N) {
+      case 7: maze_launch_tl_n<7>(view, p, s); break;
+      case 12: maze_launch_tl_n<12>(view, p, s); break;
+      case 14: maze_launch_tl_n<14>(view, p, s); break;
+      default: maze_launch_tl_n<21>(view, p, s); break;
+    }
+    return unreal_launch_status();
+  }
   const int B = p.B;
   if (view == kTopDown && e == kStep) UNREAL_LAUNCHED(B <= 64 ? "maze_step tiny" : B <= 1024 ? "maze_step apg2" : "maze_step big");
   if (view == kTopDown && e == kRollout)
@@ -1499,6 +1558,41 @@ int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, cons
              active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
              Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
   return maze_launch(kPolicy, p, view, N, cfg, actor_base, goal, layout, ep_steps, episode, heading, stream);
+}
+
+// The two rollout entries with time-limit bootstrapping: `final_obs` [B] frames; first-person views without
+// goal sense only.
+
+int unreal_maze_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                                float* episode_reward, float* score_out, int* score_valid, int* active, int* active_log_t,
+                                int* n_steps, int* terminal_end, int* next_idx, float* next_lar, int lar_ld, int lar_col0,
+                                int A, int idx_base_actor, int view, int N, const int* cfg, int actor_base, int* goal,
+                                int* layout, int* ep_steps, int* episode, int* heading, uint8_t* final_obs, void* stream) {
+  MazeArgs p{B, H1, actions, nullptr, pos, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+             r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+             active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
+  return maze_launch(kRollout, p, view, N, cfg, actor_base, goal, layout, ep_steps, episode, heading, stream, true,
+                     final_obs);
+}
+
+int unreal_maze_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                       const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                       int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
+                                       uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                       int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                       int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                       int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                       float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor, int view, int N,
+                                       const int* cfg, int actor_base, int* goal, int* layout, int* ep_steps, int* episode,
+                                       int* heading, uint8_t* final_obs, void* stream) {
+  MazeArgs p{B, H1, nullptr, nullptr, pos, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+             r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+             active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
+             Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
+  return maze_launch(kPolicy, p, view, N, cfg, actor_base, goal, layout, ep_steps, episode, heading, stream, true,
+                     final_obs);
 }
 
 int unreal_maze_objective(int B, int H1, const int* count, const int* records, int record_words, float* r_objective,

@@ -102,6 +102,60 @@ __global__ void base_returns_kernel(int B, int T, const float* rewards, const fl
   }
 }
 
+// Time-limit bootstrapping and GAE(lambda): terminal_end 1 = the episode truly ended (nothing follows),
+// 2 = it was cut off at the step limit (boot_v is V(final observation)), 0 = still running (boot_v is V(s_T)).
+// gae = delta + gamma lambda gae, R = gae + v; lambda = 1 is the n-step return.
+// No fused multiply-adds: R = gae + v cancels (a return of 0 is +-v), so a product rounded once more than the plain scan's
+// shows as a return of 1e-17 where that scan gives 0.  Every operation below is the scan's, in its order.
+__global__ void base_returns_tl_kernel(int B, int T, const float* rewards, const float* values, const int* n_steps,
+                                       const float* boot_v, const int* terminal_end, double gamma, double lambda,
+                                       float* R_out, float* adv_out) {
+#pragma clang fp contract(off)
+  int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int n = n_steps[b];
+  double next_v = terminal_end[b] == 1 ? 0.0 : (double)boot_v[b];
+  double gae = 0.0;
+  for (int t = T - 1; t >= 0; --t) {
+    size_t i = (size_t)t * B + b;
+    if (t >= n) { R_out[i] = 0.f; adv_out[i] = 0.f; continue; }
+    const double v = (double)values[i];
+    const double delta = (double)rewards[i] + gamma * next_v - v;
+    gae = delta + gamma * lambda * gae;
+    adv_out[i] = (float)gae;
+    R_out[i] = (float)(gae + v);
+    next_v = v;
+  }
+}
+
+// The bootstrap pass's inputs, one 256-thread workgroup per actor.  An actor cut off at the step limit (terminal_end 2)
+// is fed its final observation (ring index final_base + idx_base + b), the recurrent state after its last step (row
+// (n_steps - 1) B + b of the [T B] rows of ws_c / ws_h) and that step's action and unclipped reward; every other actor
+// what the pass is fed without this kernel: its current observation, the carried state, the ring's last action and reward.
+__global__ __launch_bounds__(256) void boot_gather_kernel(int B, int T, int H1, int idx_base, int final_base, int A,
+                                                          const int* count, const int* terminal_end, const int* n_steps,
+                                                          const int* last_action, const float* last_reward,
+                                                          const int* actions, const float* rewards, const float* carried_c,
+                                                          const float* carried_h, const float* ws_c, const float* ws_h,
+                                                          int* frame_idx, float* c0, float* h0, float* xcat, int ld,
+                                                          int col0) {
+  const int b = blockIdx.x, j = threadIdx.x;
+  const int n = min(n_steps[b], T);                  // (a count outside 1..T reads no row)
+  const bool cut = terminal_end[b] == 2 && n >= 1;
+  const size_t row = cut ? (size_t)(n - 1) * B + b : 0;
+  if (c0) {
+    static_assert(LSTM_N == 256, "one thread per state column");
+    c0[(size_t)b * LSTM_N + j] = cut ? ws_c[row * LSTM_N + j] : carried_c[(size_t)b * LSTM_N + j];
+    h0[(size_t)b * LSTM_N + j] = cut ? ws_h[row * LSTM_N + j] : carried_h[(size_t)b * LSTM_N + j];
+  }
+  if (xcat && j <= A) {
+    const int la = cut ? actions[row] : last_action[b];
+    const float lr = cut ? rewards[row] : last_reward[b];
+    xcat[(size_t)b * ld + col0 + j] = j < A ? (j == la ? 1.f : 0.f) : lr;
+  }
+  if (j == 0) frame_idx[b] = cut ? final_base + idx_base + b : (idx_base + b) * H1 + count[b] % H1;
+}
+
 __global__ void vr_returns_kernel(int B, int L, const int* seq_idx, const int* seq_len, const float* r_reward,
                                   const int* r_terminal, const float* boot_v, double gamma, float* R_out) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -265,6 +319,33 @@ int unreal_base_returns(int B, int T, const float* rewards, const float* values,
   if (B <= 0 || T <= 0) return UNREAL_EINVAL;
   hipLaunchKernelGGL(base_returns_kernel, GRID1(B), B, T, rewards, values, n_steps, boot_v, terminal_end, gamma,
                      R_out, adv_out);
+  return unreal_launch_status();
+}
+
+int unreal_base_returns_tl(int B, int T, const float* rewards, const float* values, const int* n_steps,
+                           const float* boot_v, const int* terminal_end, double gamma, double lambda, float* R_out,
+                           float* adv_out, void* stream) {
+  if (B <= 0 || T <= 0 || !rewards || !values || !n_steps || !boot_v || !terminal_end || !R_out || !adv_out)
+    return UNREAL_EINVAL;
+  if (!(lambda >= 0.0 && lambda <= 1.0)) return UNREAL_EINVAL;
+  hipLaunchKernelGGL(base_returns_tl_kernel, GRID1(B), B, T, rewards, values, n_steps, boot_v, terminal_end, gamma, lambda,
+                     R_out, adv_out);
+  return unreal_launch_status();
+}
+
+int unreal_boot_gather(int B, int T, int H1, int idx_base_actor, int final_base, int A, const int* count, const int* terminal_end,
+                       const int* n_steps, const int* last_action, const float* last_reward, const int* actions,
+                       const float* rewards, const float* carried_c, const float* carried_h, const float* ws_c,
+                       const float* ws_h, int* frame_idx, float* c0, float* h0, float* xcat, int ld, int col0,
+                       void* stream) {
+  if (B <= 0 || T <= 0 || H1 < 2 || idx_base_actor < 0 || final_base < 0 || !count || !terminal_end || !n_steps || !frame_idx)
+    return UNREAL_EINVAL;
+  if (c0 && (!h0 || !carried_c || !carried_h || !ws_c || !ws_h)) return UNREAL_EINVAL;
+  if (xcat && (A <= 0 || A >= 256 || col0 < 0 || ld < col0 + A + 1 || !last_action || !last_reward || !actions || !rewards))
+    return UNREAL_EINVAL;
+  hipLaunchKernelGGL(boot_gather_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, B, T, H1, idx_base_actor, final_base, A,
+                     count, terminal_end, n_steps, last_action, last_reward, actions, rewards, carried_c, carried_h, ws_c,
+                     ws_h, frame_idx, c0, h0, xcat, ld, col0);
   return unreal_launch_status();
 }
 

@@ -139,9 +139,12 @@ class BatchedArcadeEnvironment(object):
     frame_scale = 1.0 / 255.0          # ring bytes 0..255
     objective_size = 0
 
-    def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0):
+    def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
+                 final_obs=False):
         """`actor_base` / `actors_total`: global index of actor 0 and the number of actors over every rank (the serve
-        draws are keyed by the global index); `seed`: their key."""
+        draws are keyed by the global index); `seed`: their key.  `final_obs`: time-limit bootstrapping: the
+        rollout steps keep the final observation of an episode that ends by max_episode_steps alone in ring.final_obs
+        and flag it 2 instead of 1."""
         if not isinstance(config, ArcadeConfig):
             raise ValueError("BatchedArcadeEnvironment needs an ArcadeConfig")
         self.B = batch
@@ -149,7 +152,7 @@ class BatchedArcadeEnvironment(object):
         total = batch if actors_total is None else int(actors_total)
         if actor_base < 0 or actor_base + batch > total:
             raise ValueError("actors [%d, %d) outside the %d actors of the job" % (actor_base, actor_base + batch, total))
-        self.ring = ops.Ring(batch, history_size, torch.device(device), arcade=True)
+        self.ring = ops.Ring(batch, history_size, torch.device(device), arcade=True, final_obs=bool(final_obs))
         block = torch.from_numpy(config.block(seed)).to(self.ring.count.device)
         self.arcade = (block, int(actor_base))
         self.reset()
@@ -180,7 +183,7 @@ class BatchedArcadeEnvironment(object):
                      index_parent=False, **nxt):
         ops.arcade_rollout_step(self.ring, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
                                 base_actor=getattr(self, "base_actor", 0) if index_parent else 0, arcade=self.arcade,
-                                **nxt)
+                                final_obs=self.ring.final_obs, **nxt)
 
     def policy_rollout_step(self, net, feat, ld, u, pi_out, v_out, actions, out_reward, out_terminal, active, active_log_t,
                             n_steps, terminal_end, index_parent=False, **nxt):
@@ -189,7 +192,7 @@ class BatchedArcadeEnvironment(object):
                                        p["b_base_fc_v"], u, pi_out, v_out, actions, out_reward, out_terminal, active,
                                        active_log_t, n_steps, terminal_end,
                                        base_actor=getattr(self, "base_actor", 0) if index_parent else 0,
-                                       arcade=self.arcade, **nxt)
+                                       arcade=self.arcade, final_obs=self.ring.final_obs, **nxt)
 
     def current_records(self):
         """The game records -> int32 [B, 16].  Breakout: px, bx, by, vx, vy, wait, lives, bricks lo, hi, serve_index, then

@@ -533,22 +533,40 @@ def _philox_words(seed, g, episode, stream, n):
     return np.stack(c, 1).reshape(-1)[:n].astype(np.uint32)
 
 
+def check_final_obs(config):
+    """Time-limit bootstrapping covers first-person mazes without goal_sense: raises ValueError for the rest."""
+    if config is None or config.view != "first_person":
+        raise ValueError("time-limit bootstrapping is out of scope for top-down mazes: it needs a MazeConfig with "
+                         "view='first_person'")
+    if config.goal_sense:
+        raise ValueError("time-limit bootstrapping is out of scope for goal_sense mazes: the final state's objective "
+                         "vector is not kept")
+    if not config.max_episode_steps > 0:
+        raise ValueError("time-limit bootstrapping needs a step limit (max_episode_steps > 0)")
+
+
 class BatchedMazeEnvironment(object):
     ACTION_SIZE = 4
     frame_scale = 1.0          # ring bytes are the pixel values themselves (0 / 1)
 
-    def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0):
+    def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
+                 final_obs=False):
         """`config`: a MazeConfig (None: the reference's map).  `actor_base` / `actors_total`: global index of actor 0 and
         the number of actors over every rank (layouts are assigned and reset draws keyed by the global index);
-        `seed`: key of the reset draws."""
+        `seed`: key of the reset draws.  `final_obs`: time-limit bootstrapping, first-person configs without
+        goal_sense only: the rollout steps keep the final observation of an episode that ends by max_episode_steps alone
+        in ring.final_obs and flag it 2 instead of 1."""
         self.B = batch
         self.config = config
+        if final_obs:
+            check_final_obs(config)
         sense = config is not None and config.goal_sense
         self.ring = ops.Ring(batch, history_size, torch.device(device), maze_state=config is not None,
                              nav=config is not None and config.nav,
                              gen=(config.generate or 0) if config is not None else 0,
                              gen_styled=config is not None and config.styled,
-                             objective_size=config.OBJECTIVE_SIZE if sense else 0, sense=config.N if sense else 0)
+                             objective_size=config.OBJECTIVE_SIZE if sense else 0, sense=config.N if sense else 0,
+                             final_obs=bool(final_obs))
         self.maze = None
         if config is not None:
             total = batch if actors_total is None else int(actors_total)
@@ -608,7 +626,8 @@ class BatchedMazeEnvironment(object):
         """process() + the rollout loop's bookkeeping (+ the next step's frame indices / LSTM-input columns) fused.
         `index_parent` (views only): the prepared frame indices address the ring this view was cut from."""
         ops.maze_rollout_step(self.ring, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
-                              base_actor=getattr(self, "base_actor", 0) if index_parent else 0, maze=self.maze, **nxt)
+                              base_actor=getattr(self, "base_actor", 0) if index_parent else 0, maze=self.maze,
+                              final_obs=self.ring.final_obs, **nxt)
         self._objective(nxt)
 
     def policy_rollout_step(self, net, feat, ld, u, pi_out, v_out, actions, out_reward, out_terminal, active, active_log_t,
@@ -620,7 +639,8 @@ class BatchedMazeEnvironment(object):
         ops.maze_policy_rollout_step(self.ring, feat, ld, p["W_base_fc_p"], p["b_base_fc_p"], p["W_base_fc_v"],
                                      p["b_base_fc_v"], u, pi_out, v_out, actions, out_reward, out_terminal, active,
                                      active_log_t, n_steps, terminal_end,
-                                     base_actor=getattr(self, "base_actor", 0) if index_parent else 0, maze=self.maze, **nxt)
+                                     base_actor=getattr(self, "base_actor", 0) if index_parent else 0, maze=self.maze,
+                                     final_obs=self.ring.final_obs, **nxt)
         self._objective(nxt)
 
     def current_distances(self):
@@ -680,10 +700,11 @@ class FirstPersonMazeEnvironment(BatchedMazeEnvironment):
     With action_set="lab": 0 / 1 look left / right, 2 / 3 strafe left / right, 4 / 5 step forward / back."""
     frame_scale = 1.0 / 255.0          # ring bytes 0..255, read like Lab's obs / 255
 
-    def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0):
+    def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
+                 final_obs=False):
         if config is None or config.view != "first_person":
             raise ValueError("FirstPersonMazeEnvironment needs a MazeConfig with view='first_person'")
-        BatchedMazeEnvironment.__init__(self, batch, history_size, device, config, actor_base, actors_total, seed)
+        BatchedMazeEnvironment.__init__(self, batch, history_size, device, config, actor_base, actors_total, seed, final_obs)
 
     def view(self, b0, b1):
         v = BatchedMazeEnvironment.view(self, b0, b1)
@@ -691,10 +712,12 @@ class FirstPersonMazeEnvironment(BatchedMazeEnvironment):
         return v
 
 
-def batched_maze_environment(batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0):
+def batched_maze_environment(batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
+                             final_obs=False):
     """The batched maze environment of `config` (None: the reference's map): first-person or top-down, by config.view."""
     cls = FirstPersonMazeEnvironment if config is not None and config.view == "first_person" else BatchedMazeEnvironment
-    return cls(batch, history_size, device, config=config, actor_base=actor_base, actors_total=actors_total, seed=seed)
+    return cls(batch, history_size, device, config=config, actor_base=actor_base, actors_total=actors_total, seed=seed,
+               final_obs=final_obs)
 
 
 class MazeEnvironment(environment.Environment):

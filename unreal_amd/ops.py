@@ -98,7 +98,7 @@ class Ring(object):
     """Device replay ring + per-actor environment state (layout: include/unreal_hip.h)."""
 
     def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False, nav=False, gen=0,
-                 gen_styled=False, sense=0, arcade=False):
+                 gen_styled=False, sense=0, arcade=False, final_obs=False):
         self.B, self.H, self.H1 = B, H, H + 1
         self.objective_size = objective_size
         self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
@@ -107,7 +107,11 @@ class Ring(object):
         self.frame_stride = frame_stride(*self.frame_shape)
         n = B * self.H1
         z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=device)
-        self.frames = torch.empty(n * self.frame_stride, dtype=torch.uint8, device=device)
+        # `final_obs` (time-limit bootstrapping): B more frames behind the ring's, slot final_base + b keeps the
+        # final observation of actor b's last episode that the step limit cut off; the encoder reads it by that index
+        self.final_base = n
+        self.frames = torch.empty((n + (B if final_obs else 0)) * self.frame_stride, dtype=torch.uint8, device=device)
+        self.final_obs = self.frames[n * self.frame_stride:] if final_obs else None
         self.r_reward = z(n)
         self.r_action = z(n, dt=torch.int32)
         self.r_terminal = z(n, dt=torch.int32)
@@ -214,6 +218,10 @@ def ring_view(ring, b0, b1):
     v.gen = gen[b0 * v.gen_words:b1 * v.gen_words] if gen is not None else None
     arcade = getattr(ring, "arcade", None)
     v.arcade = arcade[b0 * ARCADE_RECORD:b1 * ARCADE_RECORD] if arcade is not None else None
+    # the view's actors' final-observation slots; their indices are the parent's: final_base + (b0 + b)
+    fin = getattr(ring, "final_obs", None)
+    v.final_base = getattr(ring, "final_base", ring.B * H1)
+    v.final_obs = fin[b0 * fs:b1 * fs] if fin is not None else None
     return v
 
 
@@ -337,22 +345,49 @@ def _rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps,
         int(lar_col0), int(A), int(base_actor))
 
 
+def _final_obs_args(ring, final_obs):
+    """The trailing argument of the _tl entries: `final_obs` None -> () and the plain entry; else the [B] frames of the
+    final-observation store (time-limit bootstrapping)."""
+    if final_obs is None:
+        return "", ()
+    if ring.frame_stride != FRAME_BYTES:
+        raise ValueError("the final-observation store holds 84 x 84 frames")
+    _chk(final_obs, "u8", ring.B * FRAME_BYTES, "final_obs")
+    if final_obs.data_ptr() % 16:
+        raise ValueError("final_obs must be 16-byte aligned")
+    return "_tl", (ptr(final_obs),)
+
+
+def _maze_final_obs(maze, final_obs):
+    if final_obs is not None and (maze is None or maze[0] not in (MAZE_FIRST_PERSON, MAZE_FIRST_PERSON_GENERATED,
+                                                                  MAZE_FIRST_PERSON_FORAGE,
+                                                                  MAZE_FIRST_PERSON_GENERATED_FORAGE)):
+        raise ValueError("a final-observation store needs a first-person maze without goal_sense (top-down and goal-sense "
+                         "mazes are out of scope of time-limit bootstrapping)")
+
+
 def maze_rollout_step(ring, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
-                      next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=0, base_actor=0, maze=None):
+                      next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=0, base_actor=0, maze=None, final_obs=None):
     """maze_step + rollout_advance (+ cur_idx and lar_fill for the NEXT step's rows) in one launch.  `base_actor`: index
-    of this (view's) first actor in the ring the next_idx values are meant for (see Ring.cur_idx)."""
+    of this (view's) first actor in the ring the next_idx values are meant for (see Ring.cur_idx).  `final_obs`: the
+    unreal_maze_rollout_step_tl form, which keeps the final observation of a timed-out episode there and flags it 2."""
     _chk(actions, "i32", ring.B, "actions")
-    _call("unreal_maze_rollout_step", ring.B, ring.H1, ptr(actions),
+    _maze_final_obs(maze, final_obs)
+    tl, fin = _final_obs_args(ring, final_obs)
+    _call("unreal_maze_rollout_step" + tl, ring.B, ring.H1, ptr(actions),
           *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
-                         lar_ld, lar_col0, A, base_actor), *_maze_args(ring, maze))
+                         lar_ld, lar_col0, A, base_actor), *_maze_args(ring, maze), *fin)
 
 
 def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions, out_reward, out_terminal, active,
                              active_log_t, n_steps, terminal_end, next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=4,
-                             base_actor=0, maze=None):
+                             base_actor=0, maze=None, final_obs=None):
     """policy_step + maze_rollout_step in one launch: the workgroup that steps an actor computes its pi / V / action first
-    (bit-identical to the two launches).  A = 6: a first-person navigation maze with Lab's action set."""
+    (bit-identical to the two launches).  A = 6: a first-person navigation maze with Lab's action set.  `final_obs`: the
+    _tl form, as maze_rollout_step."""
     B = ring.B
+    _maze_final_obs(maze, final_obs)
+    tl, fin = _final_obs_args(ring, final_obs)
     nav = maze is not None and ((maze[0] in (MAZE_FIRST_PERSON, MAZE_FIRST_PERSON_SENSE, MAZE_FIRST_PERSON_FORAGE) and
                                  getattr(ring, "nav", None) is not None) or
                                 maze[0] in (MAZE_FIRST_PERSON_GENERATED, MAZE_FIRST_PERSON_GENERATED_SENSE,
@@ -362,10 +397,10 @@ def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, act
     _chk(X, "f32", (B - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A); _chk(bp, "f32", A); _chk(Wv, "f32", 256)
     _chk(bv, "f32", 1); _chk(u, "f64", B, "u"); _chk(pi_out, "f32", B * A); _chk(v_out, "f32", B)
     _chk(actions, "i32", B, "actions")
-    _call("unreal_maze_policy_rollout_step", B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(u),
+    _call("unreal_maze_policy_rollout_step" + tl, B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(u),
           ptr(pi_out), ptr(v_out), ptr(actions),
           *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
-                         lar_ld, lar_col0, A, base_actor), *_maze_args(ring, maze))
+                         lar_ld, lar_col0, A, base_actor), *_maze_args(ring, maze), *fin)
 
 
 # ---- device arcade (csrc/arcade.hip) -----------------------------------------------------------------------
@@ -406,29 +441,32 @@ def _arcade_actions(A):
 
 
 def arcade_rollout_step(ring, actions, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end,
-                        next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=4, base_actor=0, arcade=None):
+                        next_idx=None, next_lar=None, lar_ld=0, lar_col0=0, A=4, base_actor=0, arcade=None,
+                        final_obs=None):
     """arcade_step + rollout_advance (+ cur_idx and lar_fill for the NEXT step's rows) in one launch, as
-    maze_rollout_step."""
+    maze_rollout_step (`final_obs`: the _tl form)."""
     _arcade_actions(A)
     _chk(actions, "i32", ring.B, "actions")
-    _call("unreal_arcade_rollout_step", ring.B, ring.H1, ptr(actions),
+    tl, fin = _final_obs_args(ring, final_obs)
+    _call("unreal_arcade_rollout_step" + tl, ring.B, ring.H1, ptr(actions),
           *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
-                         lar_ld, lar_col0, A, base_actor), *_arcade_args(ring, arcade))
+                         lar_ld, lar_col0, A, base_actor), *_arcade_args(ring, arcade), *fin)
 
 
 def arcade_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions, out_reward, out_terminal, active,
                                active_log_t, n_steps, terminal_end, next_idx=None, next_lar=None, lar_ld=0, lar_col0=0,
-                               A=4, base_actor=0, arcade=None):
-    """policy_step + arcade_rollout_step in one launch (bit-identical to the two launches)."""
+                               A=4, base_actor=0, arcade=None, final_obs=None):
+    """policy_step + arcade_rollout_step in one launch (bit-identical to the two launches; `final_obs`: the _tl form)."""
     B = ring.B
     _arcade_actions(A)
+    tl, fin = _final_obs_args(ring, final_obs)
     _chk(X, "f32", (B - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A); _chk(bp, "f32", A); _chk(Wv, "f32", 256)
     _chk(bv, "f32", 1); _chk(u, "f64", B, "u"); _chk(pi_out, "f32", B * A); _chk(v_out, "f32", B)
     _chk(actions, "i32", B, "actions")
-    _call("unreal_arcade_policy_rollout_step", B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(u),
+    _call("unreal_arcade_policy_rollout_step" + tl, B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(u),
           ptr(pi_out), ptr(v_out), ptr(actions),
           *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
-                         lar_ld, lar_col0, A, base_actor), *_arcade_args(ring, arcade))
+                         lar_ld, lar_col0, A, base_actor), *_arcade_args(ring, arcade), *fin)
 
 
 def maze_objective(ring, next_lar=None, lar_ld=0, lar_col0=0):
@@ -539,6 +577,45 @@ def base_returns(B, T, rewards, values, n_steps, boot_v, terminal_end, gamma, R_
     _chk(n_steps, "i32", B); _chk(boot_v, "f32", B); _chk(terminal_end, "i32", B)
     _call("unreal_base_returns", B, T, ptr(rewards), ptr(values), ptr(n_steps), ptr(boot_v),
           ptr(terminal_end), float(gamma), ptr(R_out), ptr(adv_out))
+
+
+def base_returns_tl(B, T, rewards, values, n_steps, boot_v, terminal_end, gamma, lam, R_out, adv_out):
+    """GAE(lam) returns and advantages; terminal_end 1: no bootstrap, 0 / 2: from boot_v.  lam = 1: n-step."""
+    if not 0.0 <= float(lam) <= 1.0:
+        raise ValueError("lambda = %r outside [0, 1]" % (lam,))
+    for t in (rewards, values, R_out, adv_out):
+        _chk(t, "f32", B * T)
+    _chk(n_steps, "i32", B); _chk(boot_v, "f32", B); _chk(terminal_end, "i32", B)
+    _call("unreal_base_returns_tl", B, T, ptr(rewards), ptr(values), ptr(n_steps), ptr(boot_v),
+          ptr(terminal_end), float(gamma), float(lam), ptr(R_out), ptr(adv_out))
+
+
+def boot_gather(ring, T, A, terminal_end, n_steps, actions, rewards, frame_idx, base_actor=0, carried_c=None,
+                carried_h=None, ws_c=None, ws_h=None, c0=None, h0=None, xcat=None, ld=0, col0=256):
+    """The bootstrap pass's inputs with time-limit bootstrapping.  `ring`: the B actors of the pass (a view:
+    its first actor is `base_actor` of the ring the frame indices are meant for, whose final-observation slots start at
+    ring.final_base).  Actors with terminal_end 2 get their final-observation slot, rows (n_steps - 1) B + b of ws_c / ws_h
+    and of actions / rewards; the others their current slot, carried_c / carried_h and the ring's last action / reward.
+    c0 None: no state (feed-forward); xcat None: no [one-hot last action | last reward] columns."""
+    B = ring.B
+    if T <= 0:
+        raise ValueError("T = %r" % (T,))
+    if getattr(ring, "final_obs", None) is None:
+        raise ValueError("boot_gather needs a ring with a final-observation store (Ring(final_obs=True))")
+    _chk(terminal_end, "i32", B, "terminal_end"); _chk(n_steps, "i32", B, "n_steps"); _chk(frame_idx, "i32", B, "frame_idx")
+    _chk(actions, "i32", T * B, "actions"); _chk(rewards, "f32", T * B, "rewards")
+    if c0 is not None:
+        for t, n, name in ((carried_c, B, "carried_c"), (carried_h, B, "carried_h"), (ws_c, T * B, "ws_c"),
+                           (ws_h, T * B, "ws_h"), (c0, B, "c0"), (h0, B, "h0")):
+            _chk(t, "f32", n * 256, name)
+    if xcat is not None:
+        if not 0 < A < 256 or col0 < 0 or ld < col0 + A + 1:
+            raise ValueError("xcat: A %d, ld %d, col0 %d" % (A, ld, col0))
+        _chk(xcat, "f32", (B - 1) * ld + col0 + A + 1, "xcat")
+    _call("unreal_boot_gather", B, int(T), ring.H1, int(base_actor), int(ring.final_base), int(A), ptr(ring.count),
+          ptr(terminal_end), ptr(n_steps), ptr(ring.last_action), ptr(ring.last_reward), ptr(actions), ptr(rewards),
+          ptr(carried_c), ptr(carried_h), ptr(ws_c), ptr(ws_h), ptr(frame_idx), ptr(c0), ptr(h0), ptr(xcat), int(ld),
+          int(col0))
 
 
 def vr_returns(ring, L, seq_idx, seq_len, boot_v, gamma, R_out):

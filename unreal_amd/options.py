@@ -51,6 +51,9 @@ def get_options(option_type="training", preset="lab", argv=()):
         a("--max_time_step", type=int, default=int(13.2 * 10 ** 6))
         a("--save_interval_step", type=int, default=100 * 1000)
         a("--grad_norm_clip", type=float, default=40.0)
+        # not in the reference, both off by default: Trainer(bootstrap_timeouts=..., gae_lambda=...)
+        a("--bootstrap_timeouts", type=_bool, default=False)
+        a("--gae_lambda", type=float, default=None)
     if option_type == "display":
         a("--frame_save_dir", default="/tmp/unreal_frames")
         a("--recording", type=_bool, default=False)

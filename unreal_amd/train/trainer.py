@@ -69,13 +69,35 @@ class PhiloxDraws(object):
 
 
 class Trainer(object):
+    @staticmethod
+    def check_rollout_options(env_type, env_name, bootstrap_timeouts, gae_lambda):
+        """-> (bootstrap_timeouts, gae_lambda) as the trainer keeps them; ValueError for what is out of scope: gae_lambda
+        outside [0, 1]; bootstrap_timeouts on anything but the device arcade and first-person device mazes without
+        goal_sense (top-down and goal-sense mazes keep no final observation, host-fed environments own their resets)."""
+        if gae_lambda is not None:
+            if isinstance(gae_lambda, bool) or not isinstance(gae_lambda, (int, float)) or not 0.0 <= gae_lambda <= 1.0:
+                raise ValueError("gae_lambda = %r: a number in [0, 1], or None for the n-step return" % (gae_lambda,))
+            gae_lambda = float(gae_lambda)
+        if bootstrap_timeouts:
+            if env_type == "maze":
+                from ..environment.maze_environment import check_final_obs
+                check_final_obs(Environment.MAZE_CONFIG.get(env_name))
+            elif env_type != "arcade":
+                raise ValueError("bootstrap_timeouts is out of scope for host-fed environments (env_type=%r): it needs "
+                                 "env_type 'arcade' or a first-person 'maze' config without goal_sense" % (env_type,))
+        return bool(bootstrap_timeouts), gae_lambda
+
     def __init__(self, thread_index, global_network, initial_learning_rate, learning_rate_input, grad_applier,
                  env_type, env_name, use_lstm, use_pixel_change, use_value_replay, use_reward_prediction,
                  pixel_change_lambda, entropy_beta, local_t_max, n_step_TD, gamma, gamma_pc,
                  experience_history_size, max_global_time_step, device, segnet_param_dict=None,
                  image_shape=(84, 84), is_training=True, n_classes=0, random_state=None, termination_time=50.0,
                  segnet_lambda=1.0, dropout=0.0, batch_size=1, world_size=1, rank=0, seed=0xA3C, draws=None,
-                 grad_sync=None, simulator=None, groups=1, overlap_host=None):
+                 grad_sync=None, simulator=None, groups=1, overlap_host=None, bootstrap_timeouts=False, gae_lambda=None):
+        # rollout options (DESIGN §7o), both off by default: an episode cut off at max_episode_steps bootstraps from
+        # V(final observation) instead of 0; GAE(lambda) replaces the n-step return
+        self.bootstrap_timeouts, self.gae_lambda = self.check_rollout_options(env_type, env_name, bootstrap_timeouts,
+                                                                              gae_lambda)
         # device environments: stepped and rendered by kernels (no simulator, sub-ranges of actors, fused rollout step)
         self.device_env = env_type in ("maze", "arcade")
         if not self.device_env and simulator is None:
@@ -158,13 +180,13 @@ class Trainer(object):
             self.environment = batched_maze_environment(B, self.experience_history_size, dev,
                                                         config=Environment.MAZE_CONFIG.get(self.env_name),
                                                         actor_base=self.rank * B, actors_total=self.world_size * B,
-                                                        seed=self.seed)
+                                                        seed=self.seed, final_obs=self.bootstrap_timeouts)
         elif self.env_type == "arcade":
             from ..environment.arcade_environment import BatchedArcadeEnvironment
             self.environment = BatchedArcadeEnvironment(B, self.experience_history_size, dev,
                                                         config=Environment.arcade_config(self.env_name),
                                                         actor_base=self.rank * B, actors_total=self.world_size * B,
-                                                        seed=self.seed)
+                                                        seed=self.seed, final_obs=self.bootstrap_timeouts)
         else:
             from ..environment.hostfed_environment import HostFedEnvironment
             indoor = self.env_type == "indoor"
@@ -425,6 +447,8 @@ class Trainer(object):
             return
         if self.objective_size:                # goal-sense mazes take the lock-step loop
             return
+        if self.bootstrap_timeouts:            # so does time-limit bootstrapping
+            return
         Bp = self.Bg // n_parts
         streams = [torch.cuda.Stream(device=self.device) for _ in range(n_parts)]
         self._split = []
@@ -521,15 +545,31 @@ class Trainer(object):
         if self.use_lstm:
             ops.copy_(bw.c0, self.lstm_c)
             ops.copy_(bw.h0, self.lstm_h)
-        self.ring.cur_idx(out=bw.frame_idx[:B])
-        feat, ld = net.trunk_forward(self.ring, bw, 1, B, lar_from_ring=False, save_c1=False,
-                                     clip_lar=self.rp_mode == 1,   # frame.get_action_reward(): stored (clipped) reward
-                                     objective_slot_offset=-1)     # ... and the objective of frame.state (:300)
+        if self.bootstrap_timeouts:
+            # an actor cut off at the step limit (terminal_end 2) is valued at its final observation, with the state and
+            # the action / reward of its last step; the others as below.  The final-observation slots are the whole
+            # ring's, so the pass reads the frames by indices into it
+            lstm = self.use_lstm
+            ops.boot_gather(self.ring, T, A, self.terminal_end, self.n_steps, self.actions, self.rewards, bw.frame_idx[:B],
+                            base_actor=self._group_views[self.group][3],
+                            carried_c=self.lstm_c if lstm else None, carried_h=self.lstm_h if lstm else None,
+                            ws_c=ws.c if lstm else None, ws_h=ws.h if lstm else None, c0=bw.c0 if lstm else None,
+                            h0=bw.h0 if lstm else None, xcat=bw.xcat if lstm else None, ld=bw.xld, col0=256)
+            feat, ld = net.trunk_forward(self.full_ring, bw, 1, B, lar_from_ring=False, save_c1=False, lar_prefilled=True)
+        else:
+            self.ring.cur_idx(out=bw.frame_idx[:B])
+            feat, ld = net.trunk_forward(self.ring, bw, 1, B, lar_from_ring=False, save_c1=False,
+                                         clip_lar=self.rp_mode == 1,   # frame.get_action_reward(): stored (clipped) reward
+                                         objective_slot_offset=-1)     # ... and the objective of frame.state (:300)
         net.value_forward(B, feat, ld, self.boot_v)
         if self.use_lstm:                      # episode ended -> reset_state() (trainer.py:293)
             ops.reset_state(B, self.terminal_end, self.lstm_c, self.lstm_h)
-        ops.base_returns(B, T, self.rewards, self.v, self.n_steps, self.boot_v, self.terminal_end, self.gamma,
-                         self.R, self.adv)
+        if self.bootstrap_timeouts or self.gae_lambda is not None:
+            ops.base_returns_tl(B, T, self.rewards, self.v, self.n_steps, self.boot_v, self.terminal_end, self.gamma,
+                                1.0 if self.gae_lambda is None else self.gae_lambda, self.R, self.adv)
+        else:
+            ops.base_returns(B, T, self.rewards, self.v, self.n_steps, self.boot_v, self.terminal_end, self.gamma,
+                             self.R, self.adv)
 
     def _train_base(self):
         B, T, A, ws, net, g, p = self.Bg, self.n_step_TD, self.action_size, self.base_ws, self.local_network, \
