@@ -202,6 +202,24 @@ int unreal_maze_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, c
  * count / records / r_objective, or next_lar with lar_col0 < 0 or lar_ld < lar_col0 + 3. */
 int unreal_maze_objective(int B, int H1, const int* count, const int* records, int record_words, float* r_objective,
                           float* next_lar /*nullable*/, int lar_ld, int lar_col0, void* stream);
+/* Depth labels of first-person mazes (csrc/depth.hip): the depth class of UNREAL_DEPTH_POSITIONS columns of
+ * every actor's current view, computed from its cell, heading and walls in integers.  Position j is frame column
+ * i = 7 j + 3 (q = 2 i + 1 - 84, odd); its ray is the camera's (above): t = tn / td at the first wall cell or map border,
+ * a border like any wall.  The class, 0 .. UNREAL_DEPTH_CLASSES - 1, is the number of edges e in {1, 2, 3, 4, 6, 8, 12}
+ * with tn >= e td, so a ray that ends exactly on an edge is in the upper class.  Pickups, the goal and wall styles do not
+ * change it.  The 12 bytes go to r_depth[(b * H1 + count[b] % H1) * 12 ..), the slot of the actor's current observation
+ * (the slot unreal_maze_objective writes); nothing else is written and a second call writes the same bytes.
+ * pos[2B], cfg and layout are the maze tail's; `heading` is the tail's heading argument: heading[B] with record_words 0,
+ * or the B per-actor records of record_words int32 (word 0: the heading).  layout NULL: a generated block, whose wall
+ * bits are read from the actor's record (record_words >= UNREAL_MAZE_GEN_RECORD(N)).  Every first-person view is served
+ * (plain, generated, goal sense, forage; styled or not).  A launch whose N is not the block's, or with a layout array on
+ * a generated block (or none on a static one), writes nothing.  -EINVAL without a launch: B <= 0, H1 <= 0, N not in
+ * {7, 12, 14, 21}, a null count / pos / heading / cfg / r_depth, record_words < 0 or in 1..7, or layout NULL with a
+ * record shorter than the generated record. */
+#define UNREAL_DEPTH_POSITIONS 12
+#define UNREAL_DEPTH_CLASSES 8
+int unreal_maze_depth_labels(int B, int H1, int N, const int* count, const int* pos, const int* heading, int record_words,
+                             const int* cfg, const int* layout /*nullable*/, uint8_t* r_depth, void* stream);
 /* Device arcade (csrc/arcade.hip): games stepped and rendered on the device, one actor per workgroup.  The
  * four entries take the ring and rollout arguments of the maze entries above (`pos` is accepted and never touched;
  * nullable) and commit through the same helpers; the maze tail is replaced by (cfg, actor_base, ep_steps[B], episode[B],
@@ -645,6 +663,16 @@ int unreal_vr_loss_grad(int rows, const float* v, const float* R, const int* mas
                         float* loss, void* stream);
 int unreal_rp_loss_grad(int rows, const float* logits, const int* cls, float grad_scale, float* prob, float* dlogits,
                         float* loss, void* stream);
+/* Depth-prediction loss (csrc/depth.hip): logits [rows][ld] hold UNREAL_DEPTH_POSITIONS groups of
+ * UNREAL_DEPTH_CLASSES in their first 96 columns; the label of row r, position j is r_depth[frame_idx[r] * 12 + j] (the
+ * frame index the encoder read for the row; unreal_maze_depth_labels wrote the byte).  Per active row and position a
+ * max-subtracted log-softmax: loss += scale * sum -log p[label]; dlogits [rows][96] = scale * (p - onehot) on active
+ * rows and 0 on the others (dlogits NULL: forward only, nothing but loss and hits is written); hits[0] += positions whose
+ * arg max (the lowest index on ties) is the label, hits[1] += positions counted.  scale = depth_lambda * grad_scale.
+ * -EINVAL without a launch: rows <= 0, ld < 96, a null logits / r_depth / frame_idx / active / loss / hits. */
+int unreal_depth_loss_grad(int rows, const float* logits, int ld, const uint8_t* r_depth, const int* frame_idx,
+                           const int* active, float scale, float* dlogits /*nullable*/, float* loss, int* hits,
+                           void* stream);
 int unreal_colsum(int rows, int cols, const float* X, int ld, float* out, void* stream);
 int unreal_relu_mask(int rows, int cols, float* d, int ldd, const float* src, int lds, void* stream);
 

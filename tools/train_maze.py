@@ -5,6 +5,7 @@ usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] 
                                   [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout|duel|invaders]
                                   [--opponent-speed N] [--action-repeat K] [--return-reward R] [--seed S]
                                   [--max-episode-steps N] [--bootstrap-timeouts] [--gae-lambda L]
+                                  [--gen-maze N] [--depth-prediction] [--depth-lambda X]
 `--groups G`: G sequential updates per process() call (update density x G, see Trainer).  One JSON line per
 `--log-every` calls: global_t, episodes finished since the last line, their mean return, losses, entropy, steps/s.
 `--arcade GAME`: train on the device arcade with that game's default config instead; a line then also holds
@@ -16,7 +17,11 @@ the arcade config's settings of those names: K game ticks per agen
 paddle returns; steps, steps_per_s and episode lengths stay agent steps.  `--seed S` (arcade only) replaces the run's two
 seeds, the network's initial weights (1) and the trainer's draws and serve key (0xA3C), by S.
 `--max-episode-steps N` (arcade only) is the config's step limit.  `--bootstrap-timeouts` (arcade only) and `--gae-lambda L`
-are the Trainer's rollout options of DESIGN §7o."""
+are the Trainer's rollout options of DESIGN §7o.
+`--gen-maze N` trains on a generated first-person navigation maze of size N (a new layout per episode, 4 apples,
+300-step episodes) instead of the reference's map; `--depth-prediction [--depth-lambda X]` (needs --gen-maze) adds the
+depth-prediction head of DESIGN §7p, and a line then also holds depth_loss, depth_accuracy and depth_majority_rate (the
+share of the most common class among the replay's labels: what a constant prediction would score)."""
 import argparse
 import json
 import os
@@ -47,7 +52,14 @@ ap.add_argument("--max-episode-steps", type=int, default=None, help="arcade: the
 ap.add_argument("--bootstrap-timeouts", action="store_true",
                 help="arcade: an episode cut off at the step limit bootstraps from V(final observation) (DESIGN 7o)")
 ap.add_argument("--gae-lambda", type=float, default=None, help="GAE(lambda) instead of the n-step return, 0..1 (DESIGN 7o)")
+ap.add_argument("--gen-maze", type=int, default=0, help="a generated first-person maze of this size (7, 12, 14, 21)")
+ap.add_argument("--depth-prediction", action="store_true", help="the depth-prediction head (DESIGN 7p); needs --gen-maze")
+ap.add_argument("--depth-lambda", type=float, default=1.0, help="weight of the depth loss")
 args = ap.parse_args()
+if args.depth_prediction and not args.gen_maze:
+    ap.error("--depth-prediction needs a first-person maze: --gen-maze N")
+if args.gen_maze and args.arcade:
+    ap.error("--gen-maze and --arcade are two environments")
 if not args.arcade and (args.action_repeat != 1 or args.return_reward != 0 or args.seed is not None or
                         args.opponent_speed is not None or args.max_episode_steps is not None or
                         args.bootstrap_timeouts):
@@ -82,8 +94,40 @@ def build_arcade_trainer(args, device):
     return flags, net, tr
 
 
-flags, net, tr = build_arcade_trainer(args, device) if args.arcade else build_trainer(args, 0, 1, device)
-if not args.arcade:                        # (the reference's maze: the returns kernel is chosen per rollout, nothing is allocated)
+def build_gen_maze_trainer(args, device):
+    """bench.build_trainer for a generated first-person navigation maze (one rank), with or without the depth head."""
+    from unreal_amd.environment.environment import Environment
+    from unreal_amd.model.model import UnrealModel
+    from unreal_amd.options import get_options
+    from unreal_amd.train.rmsprop_applier import RMSPropApplier
+    from unreal_amd.train.trainer import Trainer, log_uniform
+    name = "gen_maze_%d" % args.gen_maze
+    Environment.register_maze_config(name, view="first_person", generate=args.gen_maze, random_start=True,
+                                     random_goal=True, max_episode_steps=300, gen_loops=2, gen_apples=4, goal_reward=10)
+    flags = get_options("training", preset="lab", argv=["--env_type", "maze", "--env_name", name, "--use_depth_prediction",
+                                                        str(args.depth_prediction), "--depth_lambda", str(args.depth_lambda)])
+    net = UnrealModel(Environment.get_action_size("maze", name), 0, -1, flags.use_lstm, flags.use_pixel_change,
+                      flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
+                      device, seed=1, use_depth_prediction=flags.use_depth_prediction)
+    lr0 = log_uniform(flags.initial_alpha_low, flags.initial_alpha_high, flags.initial_alpha_log_rate)
+    applier = RMSPropApplier(None, decay=flags.rmsp_alpha, momentum=0.0, epsilon=flags.rmsp_epsilon,
+                             clip_norm=flags.grad_norm_clip, device=device)
+    tr = Trainer(0, net, lr0, None, applier, "maze", name, flags.use_lstm, flags.use_pixel_change,
+                 flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
+                 flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
+                 batch_size=args.actors, seed=0xA3C, groups=args.groups, gae_lambda=args.gae_lambda,
+                 use_depth_prediction=flags.use_depth_prediction, depth_lambda=flags.depth_lambda)
+    tr.prepare()
+    return flags, net, tr
+
+
+if args.arcade:
+    flags, net, tr = build_arcade_trainer(args, device)
+elif args.gen_maze:
+    flags, net, tr = build_gen_maze_trainer(args, device)
+else:
+    flags, net, tr = build_trainer(args, 0, 1, device)
+if not args.arcade and not args.gen_maze:                        # (the reference's maze: the returns kernel is chosen per rollout, nothing is allocated)
     tr.gae_lambda = tr.check_rollout_options(flags.env_type, flags.env_name, False, args.gae_lambda)[1]
 tr.initial_learning_rate *= args.lr_scale
 if args.entropy_beta is not None:
@@ -131,6 +175,11 @@ while global_t < args.steps:
             d = (now - totals).tolist()
             totals = now
             extra = {key: round(v / episodes, 3) if episodes else None for key, v in zip(TOTALS, d)}
+        if args.depth_prediction:
+            # the yardstick of depth_accuracy: the share of the most common class among the labels the replay holds
+            hist = torch.bincount(tr.full_ring.r_depth.long(), minlength=8).float()
+            extra.update(depth_loss=round(l["depth_loss"], 4), depth_accuracy=round(l["depth_accuracy"], 4),
+                         depth_majority_rate=round(float(hist.max() / hist.sum()), 4))
         line = json.dumps({"global_t": global_t, "episodes": episodes, "bump_rate": round(bump, 5), "goal_rate": round(goal, 6),
                            "mean_return": (score_sum / episodes) if episodes else None,
                            "total_loss": round(l["total_loss"], 4), "entropy": round(l["entropy"], 4),

@@ -140,11 +140,14 @@ class BatchedArcadeEnvironment(object):
     objective_size = 0
 
     def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
-                 final_obs=False):
+                 final_obs=False, depth_labels=False):
         """`actor_base` / `actors_total`: global index of actor 0 and the number of actors over every rank (the serve
         draws are keyed by the global index); `seed`: their key.  `final_obs`: time-limit bootstrapping: the
         rollout steps keep the final observation of an episode that ends by max_episode_steps alone in ring.final_obs
-        and flag it 2 instead of 1."""
+        and flag it 2 instead of 1.  `depth_labels`: refused (first-person mazes only)."""
+        if depth_labels:
+            raise ValueError("depth_labels is out of scope for the arcade: a game has no wall distances (it needs a "
+                             "first-person device maze)")
         if not isinstance(config, ArcadeConfig):
             raise ValueError("BatchedArcadeEnvironment needs an ArcadeConfig")
         self.B = batch

@@ -55,7 +55,11 @@ def _stage(h, frames, dst):
 
 class HostFedEnvironment(object):
     def __init__(self, simulator, batch, history_size, device="cuda:0", action_size=6, clip_reward=True,
-                 frame_max=255.0, objective_size=0, reward_divisor=1.0, raw_frame_shape=None, frame_shape=None):
+                 frame_max=255.0, objective_size=0, reward_divisor=1.0, raw_frame_shape=None, frame_shape=None,
+                 depth_labels=False):
+        if depth_labels:          # the labels come from a device maze's own walls
+            raise ValueError("depth_labels is out of scope for host-fed environments: the device does not know their "
+                             "geometry (it needs a first-person device maze)")
         self.B, self.sim = batch, simulator
         self.action_size = action_size
         self.clip_reward = clip_reward

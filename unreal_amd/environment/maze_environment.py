@@ -545,13 +545,23 @@ def check_final_obs(config):
         raise ValueError("time-limit bootstrapping needs a step limit (max_episode_steps > 0)")
 
 
+def check_depth_labels(config):
+    """Depth labels exist for first-person mazes: raises ValueError for the reference's map and every
+    top-down config."""
+    if config is None or config.view != "first_person":
+        raise ValueError("depth labels are out of scope for top-down mazes: they need a MazeConfig with "
+                         "view='first_person'")
+
+
 class BatchedMazeEnvironment(object):
     ACTION_SIZE = 4
     frame_scale = 1.0          # ring bytes are the pixel values themselves (0 / 1)
 
     def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
-                 final_obs=False):
-        """`config`: a MazeConfig (None: the reference's map).  `actor_base` / `actors_total`: global index of actor 0 and
+                 final_obs=False, depth_labels=False):
+        """`depth_labels`: depth prediction, first-person configs only: every kernel that changes an actor's
+        state is followed by the launch that writes the 12 depth classes of its view into ring.r_depth.
+        `config`: a MazeConfig (None: the reference's map).  `actor_base` / `actors_total`: global index of actor 0 and
         the number of actors over every rank (layouts are assigned and reset draws keyed by the global index);
         `seed`: key of the reset draws.  `final_obs`: time-limit bootstrapping, first-person configs without
         goal_sense only: the rollout steps keep the final observation of an episode that ends by max_episode_steps alone
@@ -560,13 +570,16 @@ class BatchedMazeEnvironment(object):
         self.config = config
         if final_obs:
             check_final_obs(config)
+        if depth_labels:
+            check_depth_labels(config)
+        self.depth_labels = bool(depth_labels)
         sense = config is not None and config.goal_sense
         self.ring = ops.Ring(batch, history_size, torch.device(device), maze_state=config is not None,
                              nav=config is not None and config.nav,
                              gen=(config.generate or 0) if config is not None else 0,
                              gen_styled=config is not None and config.styled,
                              objective_size=config.OBJECTIVE_SIZE if sense else 0, sense=config.N if sense else 0,
-                             final_obs=bool(final_obs))
+                             final_obs=bool(final_obs), depth=self.depth_labels)
         self.maze = None
         if config is not None:
             total = batch if actors_total is None else int(actors_total)
@@ -591,6 +604,7 @@ class BatchedMazeEnvironment(object):
         v.B, v.ring = b1 - b0, ops.ring_view(self.ring, b0, b1)
         v.base_actor = b0
         v.config = self.config
+        v.depth_labels = getattr(self, "depth_labels", False)
         v.maze = None if self.maze is None else self.maze[:3] + (self.maze[3] + b0,) + self.maze[4:]
         return v
 
@@ -604,7 +618,10 @@ class BatchedMazeEnvironment(object):
 
     def _objective(self, nxt=None):
         """Goal-sense configs: the objective of every actor's current state into its ring slot, after every kernel that
-        changes the state (and into the next step's LSTM-input rows, next to the columns the step has written)."""
+        changes the state (and into the next step's LSTM-input rows, next to the columns the step has written).  With
+        depth_labels, at the same points: the depth classes of every actor's current view into its slot."""
+        if getattr(self, "depth_labels", False):
+            ops.maze_depth_labels(self.ring, self.maze)
         if not self.ring.objective_size:
             return
         if nxt and nxt.get("next_lar") is not None:
@@ -701,10 +718,11 @@ class FirstPersonMazeEnvironment(BatchedMazeEnvironment):
     frame_scale = 1.0 / 255.0          # ring bytes 0..255, read like Lab's obs / 255
 
     def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
-                 final_obs=False):
+                 final_obs=False, depth_labels=False):
         if config is None or config.view != "first_person":
             raise ValueError("FirstPersonMazeEnvironment needs a MazeConfig with view='first_person'")
-        BatchedMazeEnvironment.__init__(self, batch, history_size, device, config, actor_base, actors_total, seed, final_obs)
+        BatchedMazeEnvironment.__init__(self, batch, history_size, device, config, actor_base, actors_total, seed, final_obs,
+                                        depth_labels)
 
     def view(self, b0, b1):
         v = BatchedMazeEnvironment.view(self, b0, b1)
@@ -713,11 +731,11 @@ class FirstPersonMazeEnvironment(BatchedMazeEnvironment):
 
 
 def batched_maze_environment(batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
-                             final_obs=False):
+                             final_obs=False, depth_labels=False):
     """The batched maze environment of `config` (None: the reference's map): first-person or top-down, by config.view."""
     cls = FirstPersonMazeEnvironment if config is not None and config.view == "first_person" else BatchedMazeEnvironment
     return cls(batch, history_size, device, config=config, actor_base=actor_base, actors_total=actors_total, seed=seed,
-               final_obs=final_obs)
+               final_obs=final_obs, depth_labels=depth_labels)
 
 
 class MazeEnvironment(environment.Environment):

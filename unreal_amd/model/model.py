@@ -21,6 +21,8 @@ from .. import ops
 
 ALIGN = 64
 XLD = 264          # row stride of the [fc(256) | last_action_reward | pad] LSTM input buffer (no objective vector)
+# depth-prediction head: feat (256) -> 128, ReLU -> 12 positions x 8 classes
+DEPTH_HIDDEN, DEPTH_OUT = 128, ops.DEPTH_POSITIONS * ops.DEPTH_CLASSES
 
 
 def xcat_ld(action_size, objective_size=0):
@@ -46,8 +48,9 @@ def conv_out_dim(image_shape=(84, 84)):
 
 
 def param_spec(action_size, objective_size=0, use_lstm=True, use_pixel_change=True,
-               use_value_replay=True, use_reward_prediction=True, image_shape=(84, 84)):
-    """(name, shape, fan_in) in the reference's variable-creation order (model.py:106-136)."""
+               use_value_replay=True, use_reward_prediction=True, image_shape=(84, 84), use_depth_prediction=False):
+    """(name, shape, fan_in) in the reference's variable-creation order (model.py:106-136).  The depth-prediction head
+    (not in the reference) comes last, so every other layout is what it is without it."""
     A = action_size
     F = conv_out_dim(image_shape)
     lstm_in = 256 + A + 1 + objective_size
@@ -64,6 +67,9 @@ def param_spec(action_size, objective_size=0, use_lstm=True, use_pixel_change=Tr
                  ("W_pc_deconv_a", (4, 4, A, 32), 512), ("b_pc_deconv_a", (A,), 512)]
     if use_reward_prediction:
         spec += [("W_rp_fc1", (3 * F, 3), 3 * F), ("b_rp_fc1", (3,), 3 * F)]
+    if use_depth_prediction:
+        spec += [("W_dp_fc1", (256, DEPTH_HIDDEN), 256), ("b_dp_fc1", (DEPTH_HIDDEN,), 256),
+                 ("W_dp_fc2", (DEPTH_HIDDEN, DEPTH_OUT), DEPTH_HIDDEN), ("b_dp_fc2", (DEPTH_OUT,), DEPTH_HIDDEN)]
     return spec
 
 
@@ -182,7 +188,8 @@ class UnrealModel(object):
     def __init__(self, action_size, objective_size, thread_index, use_lstm, use_pixel_change,
                  use_value_replay, use_reward_prediction, pixel_change_lambda, entropy_beta, device,
                  segnet_param_dict=None, image_shape=(84, 84), is_training=True, n_classes=0,
-                 segnet_lambda=1.0, dropout=0.0, for_display=False, frame_scale=None, seed=0):
+                 segnet_lambda=1.0, dropout=0.0, for_display=False, frame_scale=None, seed=0,
+                 use_depth_prediction=False):
         if objective_size < 0:
             raise ValueError("objective_size must be >= 0")
         if segnet_param_dict is not None and segnet_param_dict.get("segnet_mode", 0) not in (0, None):
@@ -218,8 +225,13 @@ class UnrealModel(object):
         # "whatever the environment stores": Trainer.prepare() / Evaluate set it from environment.frame_scale.
         self._frame_scale_given = frame_scale is not None
         self.frame_scale = 1.0 if frame_scale is None else float(frame_scale)
+        # depth prediction: a head on the base features that classifies the wall distance of 12 frame columns
+        self._use_depth_prediction = bool(use_depth_prediction)
+        if self._use_depth_prediction and self.hw:
+            raise ValueError("image_shape %r: depth prediction is a task of first-person device mazes, whose frames are "
+                             "84x84" % (self.image_shape,))
         self.spec = param_spec(action_size, objective_size, use_lstm, use_pixel_change, use_value_replay,
-                               use_reward_prediction, self.image_shape)
+                               use_reward_prediction, self.image_shape, self._use_depth_prediction)
         self.params = FlatParams(self.spec, self._device)
         self.grads = FlatParams(self.spec, self._device)
         self.p = self.params.views
@@ -230,6 +242,7 @@ class UnrealModel(object):
         # loss attributes of the reference (populated by Trainer after every update)
         self.total_loss = self.base_loss = self.policy_loss = self.value_loss = None
         self.entropy = self.pc_loss = self.vr_loss = self.rp_loss = None
+        self.depth_loss = None
         self._b1 = None
         self._c1_tmp, self._enc_work = {}, {}      # per-stream conv scratch of the runtime-size encoder (encoder_forward / _backward)
         self._shadow = None
@@ -661,6 +674,32 @@ class UnrealModel(object):
         ops.gemm_split_nt(rows, 2592, 256, feat, ld, self.shadow["pc_fc1_fwd"], hp, 2592, bias=p["b_pc_fc1"],
                           flags=ops.GEMM_RELU, a_max=a_max, c_max=hp_max)
 
+    # -- depth-prediction head ---------------------------------------------------------------
+    # feat -> relu(W_dp_fc1) -> W_dp_fc2: 12 groups of 8 logits.  All six products run on the exact-fp32 MFMA GEMM
+    # (unreal_gemm_f32): K is 256 / 128 / 96 forward and backward, short enough that the fp16x2 split has nothing to win,
+    # and the entry masks, accumulates and handles N = 96 (a 64-wide tile and a half-empty one) by itself.
+    def depth_head_forward(self, rows, feat, ld, hidden, logits):
+        """hidden [rows, 128] = relu(feat @ W_dp_fc1 + b), logits [rows, 96] = hidden @ W_dp_fc2 + b."""
+        p = self.p
+        ops.gemm(False, False, rows, DEPTH_HIDDEN, 256, feat, ld, p["W_dp_fc1"], DEPTH_HIDDEN, hidden, DEPTH_HIDDEN,
+                 bias=p["b_dp_fc1"], flags=ops.GEMM_RELU)
+        ops.gemm(False, False, rows, DEPTH_OUT, DEPTH_HIDDEN, hidden, DEPTH_HIDDEN, p["W_dp_fc2"], DEPTH_OUT, logits,
+                 DEPTH_OUT, bias=p["b_dp_fc2"])
+
+    def depth_head_backward(self, rows, feat, ld, hidden, dlogits, d_hidden, d_feat, ldd):
+        """Gradient of depth_head_forward: dW / db are added into self.g, dX is ADDED into d_feat [rows, ldd]."""
+        p, g = self.p, self.g
+        H, O = DEPTH_HIDDEN, DEPTH_OUT
+        ops.gemm(False, True, rows, H, O, dlogits, O, p["W_dp_fc2"], O, d_hidden, H, mask=hidden, ldm=H,
+                 flags=ops.GEMM_RELU_MASK)
+        ops.gemm(True, False, H, O, rows, hidden, H, dlogits, O, g["W_dp_fc2"], O, flags=ops.GEMM_ATOMIC,
+                 splitk=_splitk(H, O, rows))
+        ops.colsum(rows, O, dlogits, O, g["b_dp_fc2"])
+        ops.gemm(False, True, rows, 256, H, d_hidden, H, p["W_dp_fc1"], H, d_feat, ldd, flags=ops.GEMM_ACCUM)
+        ops.gemm(True, False, 256, H, rows, feat, ld, d_hidden, H, g["W_dp_fc1"], H, flags=ops.GEMM_ATOMIC,
+                 splitk=_splitk(256, H, rows))
+        ops.colsum(rows, H, d_hidden, H, g["b_dp_fc1"])
+
     # -- reference batch-1 runners (model.py:630-728) ---------------------------------------------------
     def _b1_ws(self):
         if self._b1 is None:
@@ -743,6 +782,21 @@ class UnrealModel(object):
         ws, feat, ld = self._run_trunk1(s_t, last_action_reward, self._zero_state())
         self.value_forward(1, feat, ld, b1["v"])
         return float(b1["v"].cpu()[0])
+
+    def run_depth(self, sess, s_t, last_action_reward):
+        """-> int array [12]: the predicted depth class (0..7) of the 12 frame columns 7 j + 3.  The head
+        reads the base features, so the trunk starts from the carried base LSTM state, which is not advanced
+        (as run_base_value)."""
+        if not self._use_depth_prediction:
+            raise ValueError("run_depth: the network has no depth-prediction head (UnrealModel(use_depth_prediction=True))")
+        b1 = self._b1_ws()
+        if "dp_h" not in b1:
+            b1["dp_h"] = torch.zeros(DEPTH_HIDDEN, device=self._device)
+            b1["dp_z"] = torch.zeros(DEPTH_OUT, device=self._device)
+        ws, feat, ld = self._run_trunk1(s_t, last_action_reward, self.base_lstm_state_out)
+        self.depth_head_forward(1, feat, ld, b1["dp_h"], b1["dp_z"])
+        z = b1["dp_z"].cpu().numpy().reshape(ops.DEPTH_POSITIONS, ops.DEPTH_CLASSES)
+        return np.argmax(z, axis=1)          # (the lowest index on ties, as the loss kernel counts hits)
 
     def run_rp_c(self, sess, state_history):
         b1 = self._b1_ws()

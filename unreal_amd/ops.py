@@ -98,7 +98,7 @@ class Ring(object):
     """Device replay ring + per-actor environment state (layout: include/unreal_hip.h)."""
 
     def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False, nav=False, gen=0,
-                 gen_styled=False, sense=0, arcade=False, final_obs=False):
+                 gen_styled=False, sense=0, arcade=False, final_obs=False, depth=False):
         self.B, self.H, self.H1 = B, H, H + 1
         self.objective_size = objective_size
         self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
@@ -119,6 +119,11 @@ class Ring(object):
         self.r_last_reward = z(n)
         self.r_pc = torch.empty(n * PC_CELLS, dtype=torch.float32, device=device)
         self.r_objective = z(n * objective_size) if objective_size else None
+        # depth prediction, first-person mazes only: the 12 depth classes of every slot's view
+        # (unreal_maze_depth_labels), allocated only when asked
+        if depth and not maze_state:
+            raise ValueError("depth labels are kept for first-person device mazes only (Ring(maze_state=True, depth=True))")
+        self.r_depth = z(n * DEPTH_POSITIONS, dt=torch.uint8) if depth else None
         self.pos = z(B * 2, dt=torch.int32)
         self.last_action = z(B, dt=torch.int32)
         self.last_reward = z(B)
@@ -203,6 +208,8 @@ def ring_view(ring, b0, b1):
     v.r_pc = ring.r_pc[b0 * H1 * PC_CELLS:b1 * H1 * PC_CELLS]
     obj = ring.objective_size
     v.r_objective = ring.r_objective[b0 * H1 * obj:b1 * H1 * obj] if obj else None
+    dep = getattr(ring, "r_depth", None)
+    v.r_depth = dep[b0 * H1 * DEPTH_POSITIONS:b1 * H1 * DEPTH_POSITIONS] if dep is not None else None
     v.pos = ring.pos[2 * b0:2 * b1]
     for name in ("last_action", "last_reward", "count", "episode_reward", "score_out", "score_valid", "_cur"):
         setattr(v, name, getattr(ring, name)[b0:b1])
@@ -239,6 +246,8 @@ MAZE_FIRST_PERSON_SENSE, MAZE_FIRST_PERSON_GENERATED_SENSE = 3, 4
 MAZE_FIRST_PERSON_FORAGE, MAZE_FIRST_PERSON_GENERATED_FORAGE = 5, 6
 NAV_RECORD = 8                                # int32 words of a navigation maze's per-actor record (UNREAL_MAZE_NAV_RECORD)
 MAZE_RECORD_HEADER, NAV_APPLE_RECORD = 18, 65  # words of a layout record before its free list; of an apple record
+DEPTH_POSITIONS, DEPTH_CLASSES = 12, 8        # UNREAL_DEPTH_POSITIONS / UNREAL_DEPTH_CLASSES
+DEPTH_EDGES = (1, 2, 3, 4, 6, 8, 12)          # class = number of edges e with t >= e
 
 
 def style_words(N):
@@ -485,6 +494,42 @@ def maze_objective(ring, next_lar=None, lar_ld=0, lar_col0=0):
         _chk(next_lar, "f32", (B - 1) * lar_ld + lar_col0 + 3, "next_lar")
     _call("unreal_maze_objective", B, ring.H1, ptr(ring.count), ptr(rec), int(words), ptr(ring.r_objective),
           ptr(next_lar), int(lar_ld), int(lar_col0))
+
+
+def check_depth_maze(maze):
+    """Depth labels exist for first-person device mazes only: raises ValueError for the reference's map and
+    every top-down maze.  `maze` as in _maze_args."""
+    if maze is None or maze[0] == MAZE_TOP_DOWN:
+        raise ValueError("depth labels need a first-person device maze (MazeConfig(view='first_person')); top-down mazes, "
+                         "the arcade and host-fed environments are out of scope")
+
+
+def maze_depth_labels(ring, maze):
+    """The depth classes of every actor's current view -> the current slot of ring.r_depth, 12 bytes per
+    slot.  `maze` as in _maze_args; every first-person view is served."""
+    check_depth_maze(maze)
+    if getattr(ring, "r_depth", None) is None:
+        raise ValueError("maze_depth_labels needs a ring with depth labels (Ring(depth=True))")
+    B = ring.B
+    view, N, cfg, _, _, layout, _, _, heading = _maze_args(ring, maze)
+    _chk(ring.r_depth, "u8", B * ring.H1 * DEPTH_POSITIONS, "ring.r_depth")
+    _chk(ring.count, "i32", B, "ring.count"); _chk(ring.pos, "i32", 2 * B, "ring.pos")
+    _call("unreal_maze_depth_labels", B, ring.H1, N, ptr(ring.count), ptr(ring.pos), heading, int(ring.record_words), cfg,
+          layout, ptr(ring.r_depth))
+
+
+def depth_loss_grad(rows, logits, ld, r_depth, frame_idx, active, scale, dlogits, loss, hits):
+    """Softmax cross-entropy of 12 groups of 8 logits against the ring's depth labels: the label of row r,
+    position j is r_depth[frame_idx[r] * 12 + j].  loss += scale * sum over active rows; dlogits [rows, 96] = scale *
+    (p - onehot) on active rows, 0 elsewhere (None: forward only); hits (int32 [2]) += (arg max == label, counted)."""
+    n = DEPTH_POSITIONS * DEPTH_CLASSES
+    if rows <= 0 or ld < n:
+        raise ValueError("depth_loss_grad: rows=%d ld=%d" % (rows, ld))
+    _chk(logits, "f32", (rows - 1) * ld + n, "logits"); _chk(r_depth, "u8", DEPTH_POSITIONS, "r_depth")
+    _chk(frame_idx, "i32", rows, "frame_idx"); _chk(active, "i32", rows, "active")
+    _chk(dlogits, "f32", rows * n, "dlogits", optional=True); _chk(loss, "f32", 1, "loss"); _chk(hits, "i32", 2, "hits")
+    _call("unreal_depth_loss_grad", rows, ptr(logits), int(ld), ptr(r_depth), ptr(frame_idx), ptr(active), float(scale),
+          ptr(dlogits), ptr(loss), ptr(hits))
 
 
 def pixel_change_u8(frames, idx_new, idx_old, denom, out):

@@ -24,6 +24,9 @@ def get_options(option_type="training", preset="lab", argv=()):
     a("--use_pixel_change", type=_bool, default=True if lab else False)
     a("--use_value_replay", type=_bool, default=True)
     a("--use_reward_prediction", type=_bool, default=True)
+    # not in the reference, off by default: UnrealModel / Trainer(use_depth_prediction=..., depth_lambda=...)
+    a("--use_depth_prediction", type=_bool, default=False)
+    a("--depth_lambda", type=float, default=1.0)
     a("--segnet_pretrain", type=_bool, default=False)
     a("--checkpoint_dir", default="lab_ckpt" if lab else "ckpt"); a("--checkpoint", default="")
     a("--segnet", type=int, default=0 if lab else 2)

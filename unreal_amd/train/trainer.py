@@ -87,17 +87,43 @@ class Trainer(object):
                                  "env_type 'arcade' or a first-person 'maze' config without goal_sense" % (env_type,))
         return bool(bootstrap_timeouts), gae_lambda
 
+    @staticmethod
+    def check_depth_prediction(env_type, env_name, use_depth_prediction, depth_lambda=1.0):
+        """-> (use_depth_prediction, depth_lambda) as the trainer keeps them; ValueError for what is out of scope (DESIGN
+        §7p): the labels are the wall distances of a first-person device maze, so top-down mazes, the arcade and host-fed
+        environments have none; depth_lambda must be a finite number >= 0."""
+        if not use_depth_prediction:
+            return False, float(depth_lambda)
+        if isinstance(depth_lambda, bool) or not isinstance(depth_lambda, (int, float)) or not 0.0 <= depth_lambda < float("inf"):
+            raise ValueError("depth_lambda = %r: a finite number >= 0" % (depth_lambda,))
+        if env_type == "maze":
+            from ..environment.maze_environment import check_depth_labels
+            check_depth_labels(Environment.MAZE_CONFIG.get(env_name))
+        elif env_type == "arcade":
+            raise ValueError("use_depth_prediction is out of scope for the arcade: it needs a first-person 'maze' config")
+        else:
+            raise ValueError("use_depth_prediction is out of scope for host-fed environments (env_type=%r): it needs a "
+                             "first-person 'maze' config" % (env_type,))
+        return True, float(depth_lambda)
+
     def __init__(self, thread_index, global_network, initial_learning_rate, learning_rate_input, grad_applier,
                  env_type, env_name, use_lstm, use_pixel_change, use_value_replay, use_reward_prediction,
                  pixel_change_lambda, entropy_beta, local_t_max, n_step_TD, gamma, gamma_pc,
                  experience_history_size, max_global_time_step, device, segnet_param_dict=None,
                  image_shape=(84, 84), is_training=True, n_classes=0, random_state=None, termination_time=50.0,
                  segnet_lambda=1.0, dropout=0.0, batch_size=1, world_size=1, rank=0, seed=0xA3C, draws=None,
-                 grad_sync=None, simulator=None, groups=1, overlap_host=None, bootstrap_timeouts=False, gae_lambda=None):
+                 grad_sync=None, simulator=None, groups=1, overlap_host=None, bootstrap_timeouts=False, gae_lambda=None,
+                 use_depth_prediction=False, depth_lambda=1.0):
         # rollout options (DESIGN §7o), both off by default: an episode cut off at max_episode_steps bootstraps from
         # V(final observation) instead of 0; GAE(lambda) replaces the n-step return
         self.bootstrap_timeouts, self.gae_lambda = self.check_rollout_options(env_type, env_name, bootstrap_timeouts,
                                                                               gae_lambda)
+        # depth prediction (DESIGN §7p), off by default: one more head on the base features, trained on the rollout rows
+        self.use_depth_prediction, self.depth_lambda = self.check_depth_prediction(env_type, env_name,
+                                                                                   use_depth_prediction, depth_lambda)
+        if self.use_depth_prediction != bool(getattr(global_network, "_use_depth_prediction", False)):
+            raise ValueError("Trainer(use_depth_prediction=%r) but the network was built with use_depth_prediction=%r"
+                             % (self.use_depth_prediction, getattr(global_network, "_use_depth_prediction", False)))
         # device environments: stepped and rendered by kernels (no simulator, sub-ranges of actors, fused rollout step)
         self.device_env = env_type in ("maze", "arcade")
         if not self.device_env and simulator is None:
@@ -180,7 +206,8 @@ class Trainer(object):
             self.environment = batched_maze_environment(B, self.experience_history_size, dev,
                                                         config=Environment.MAZE_CONFIG.get(self.env_name),
                                                         actor_base=self.rank * B, actors_total=self.world_size * B,
-                                                        seed=self.seed, final_obs=self.bootstrap_timeouts)
+                                                        seed=self.seed, final_obs=self.bootstrap_timeouts,
+                                                        depth_labels=self.use_depth_prediction)
         elif self.env_type == "arcade":
             from ..environment.arcade_environment import BatchedArcadeEnvironment
             self.environment = BatchedArcadeEnvironment(B, self.experience_history_size, dev,
@@ -255,7 +282,12 @@ class Trainer(object):
         self.boot_v, self.R, self.adv = f(B), f(T * B), f(T * B)
         self.dlogits, self.dv = f(max(T, Ta) * B * A), f(max(T, Ta) * B)
         self.u_act = d(T * B)
-        self.losses = f(8)            # policy, value, entropy, pc, vr, rp
+        self.losses = f(8)            # policy, value, entropy, pc, vr, rp, depth
+        if self.use_depth_prediction:
+            from ..model.model import DEPTH_HIDDEN, DEPTH_OUT
+            self.dp_hidden, self.dp_d_hidden = f(T * B * DEPTH_HIDDEN), f(T * B * DEPTH_HIDDEN)
+            self.dp_logits, self.dp_dlogits = f(T * B * DEPTH_OUT), f(T * B * DEPTH_OUT)
+            self.dp_hits = i(2)       # positions predicted right, positions counted: summed over a call's groups
         self.stats = d(3)
         if aux:
             L = Ta + 1
@@ -583,7 +615,19 @@ class Trainer(object):
                              g["W_base_fc_p"], g["b_base_fc_p"])
         ops.linear_small_bwd(rows, 256, 1, feat, ld, self.dv, 1, p["W_base_fc_v"], d_feat, 256, True,
                              g["W_base_fc_v"], g["b_base_fc_v"])
+        if self.use_depth_prediction:
+            self._train_depth(rows, feat, ld, d_feat)
         net.trunk_backward(self.ring, ws, self.gws, T, B, d_feat, h0_nonzero=True)
+
+    def _train_depth(self, rows, feat, ld, d_feat):
+        """[Depth prediction] on the rollout's rows: head forward, cross-entropy against the ring's labels of
+        the frames the encoder read, head backward; the head's share of d(loss)/d(feat) is added into d_feat."""
+        from ..model.model import DEPTH_OUT
+        net, ws = self.local_network, self.base_ws
+        net.depth_head_forward(rows, feat, ld, self.dp_hidden, self.dp_logits)
+        ops.depth_loss_grad(rows, self.dp_logits, DEPTH_OUT, self.ring.r_depth, ws.frame_idx, self.active_log,
+                            self.depth_lambda * self.grad_scale, self.dp_dlogits, self.losses[6:7], self.dp_hits)
+        net.depth_head_backward(rows, feat, ld, self.dp_hidden, self.dp_dlogits, self.dp_d_hidden, d_feat, 256)
 
     def _sample_sequence(self):
         """experience.sample_sequence(local_t_max+1) for every actor + the bootstrap frame's features."""
@@ -759,6 +803,8 @@ class Trainer(object):
         self._rollout()
         net.grads.flat.zero_()
         self.losses.zero_()
+        if self.use_depth_prediction and self.group == 0:
+            self.dp_hits.zero_()
         self._train_base()
         if self.batch_aux:
             self._train_aux_batched()
@@ -837,10 +883,16 @@ class Trainer(object):
         net.base_loss = net.policy_loss + net.value_loss
         net.pc_loss, net.vr_loss, net.rp_loss = float(l[3]), float(l[4]), float(l[5])
         net.total_loss = net.base_loss + net.pc_loss + net.vr_loss + net.rp_loss
+        if self.use_depth_prediction:
+            net.depth_loss = float(l[6])
+            net.total_loss += net.depth_loss
         self.last_losses = dict(total_loss=net.total_loss, base_loss=net.base_loss, policy_loss=net.policy_loss,
                                 value_loss=net.value_loss, entropy=net.entropy, pc_loss=net.pc_loss,
                                 vr_loss=net.vr_loss, rp_loss=net.rp_loss,
                                 grad_norm=float(self.last_grad_norm.cpu()[0]))
+        if self.use_depth_prediction:
+            hits = self.dp_hits.cpu().numpy()
+            self.last_losses.update(depth_loss=net.depth_loss, depth_accuracy=float(hits[0]) / max(int(hits[1]), 1))
         return self.last_losses
 
     def _print_log(self, global_t):
