@@ -673,6 +673,23 @@ int unreal_rp_loss_grad(int rows, const float* logits, const int* cls, float gra
 int unreal_depth_loss_grad(int rows, const float* logits, int ld, const uint8_t* r_depth, const int* frame_idx,
                            const int* active, float scale, float* dlogits /*nullable*/, float* loss, int* hits,
                            void* stream);
+/* Sample reuse (csrc/ppo.hip): heads forward + clipped-surrogate (PPO) loss and gradient of `rows` re-evaluated
+ * rollout rows in ONE launch, one wave per row.  pi_out [rows][A] = softmax(X Wp + bp) and v_out [rows] = X Wv + bv are
+ * bit-identical to unreal_policy_step(u = NULL) (K = 256 features, ldx >= 256, A in 2..18).  With the probability clip
+ * to [1e-20, 1] and its pass-through indicator `un` of unreal_base_loss_grad: pc' = clip(pi_out[a]), p_old =
+ * clip(pi_old[row * ld_old + a]), rho = pc' / p_old, rc = clip(rho, 1 - clip_eps, 1 + clip_eps); per active row
+ * policy loss = -min(rho adv, rc adv) - entropy_beta H(pi_out), whose unclipped term is the active one when rho adv <=
+ * rc adv (a tie counts as unclipped: d/dpc' = -adv un / p_old, otherwise 0); value loss 0.25 (R - v_out)^2, dv = -0.5 (R -
+ * v_out).  dlogits [rows][A] and dv [rows] are scaled by grad_scale and 0 on inactive rows (dlogits NULL: forward only,
+ * neither is written).  losses[0..2] += grad_scale * (policy, value, entropy); stats_i[0] += active rows whose policy term
+ * was clipped, stats_i[1] += active rows; stats_f[0] += sum (rho - 1 - ln rho), stats_f[1] += sum |rho - 1|.
+ * -EINVAL without a launch: rows <= 0, a null required pointer (dv when dlogits is given), A outside 2..18, ldx < 256,
+ * ld_old < A, clip_eps outside (0, 1). */
+int unreal_ppo_heads_loss_grad(int rows, int A, const float* X, int ldx, const float* Wp, const float* bp, const float* Wv,
+                               const float* bv, const float* pi_old, int ld_old, const int* action, const float* adv,
+                               const float* R, const int* active, float clip_eps, float entropy_beta, float grad_scale,
+                               float* pi_out, float* v_out, float* dlogits /*nullable*/, float* dv, float* losses /*[3]*/,
+                               int* stats_i /*[2]*/, float* stats_f /*[2]*/, void* stream);
 int unreal_colsum(int rows, int cols, const float* X, int ld, float* out, void* stream);
 int unreal_relu_mask(int rows, int cols, float* d, int ldd, const float* src, int lds, void* stream);
 

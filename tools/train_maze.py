@@ -6,6 +6,7 @@ usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] 
                                   [--opponent-speed N] [--action-repeat K] [--return-reward R] [--seed S]
                                   [--max-episode-steps N] [--bootstrap-timeouts] [--gae-lambda L]
                                   [--gen-maze N] [--depth-prediction] [--depth-lambda X]
+                                  [--reuse-epochs E] [--ppo-clip X]
 `--groups G`: G sequential updates per process() call (update density x G, see Trainer).  One JSON line per
 `--log-every` calls: global_t, episodes finished since the last line, their mean return, losses, entropy, steps/s.
 `--arcade GAME`: train on the device arcade with that game's default config instead; a line then also holds
@@ -21,7 +22,9 @@ are the Trainer's rollout options of DESIGN §7o.
 `--gen-maze N` trains on a generated first-person navigation maze of size N (a new layout per episode, 4 apples,
 300-step episodes) instead of the reference's map; `--depth-prediction [--depth-lambda X]` (needs --gen-maze) adds the
 depth-prediction head of DESIGN §7p, and a line then also holds depth_loss, depth_accuracy and depth_majority_rate (the
-share of the most common class among the replay's labels: what a constant prediction would score)."""
+share of the most common class among the replay's labels: what a constant prediction would score).
+`--reuse-epochs E [--ppo-clip X]` are the Trainer's sample-reuse options of DESIGN §7q (every environment of this tool): E
+updates per rollout; a line then also holds clip_fraction and approx_kl, and its steps stay environment steps."""
 import argparse
 import json
 import os
@@ -55,6 +58,8 @@ ap.add_argument("--gae-lambda", type=float, default=None, help="GAE(lambda) inst
 ap.add_argument("--gen-maze", type=int, default=0, help="a generated first-person maze of this size (7, 12, 14, 21)")
 ap.add_argument("--depth-prediction", action="store_true", help="the depth-prediction head (DESIGN 7p); needs --gen-maze")
 ap.add_argument("--depth-lambda", type=float, default=1.0, help="weight of the depth loss")
+ap.add_argument("--reuse-epochs", type=int, default=1, help="updates per rollout, 1..16 (DESIGN 7q)")
+ap.add_argument("--ppo-clip", type=float, default=0.2, help="the clip range of the reuse updates' surrogate (DESIGN 7q)")
 args = ap.parse_args()
 if args.depth_prediction and not args.gen_maze:
     ap.error("--depth-prediction needs a first-person maze: --gen-maze N")
@@ -89,7 +94,8 @@ def build_arcade_trainer(args, device):
                  flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
                  flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
                  batch_size=args.actors, seed=0xA3C if args.seed is None else args.seed, groups=args.groups,
-                 bootstrap_timeouts=args.bootstrap_timeouts, gae_lambda=args.gae_lambda)
+                 bootstrap_timeouts=args.bootstrap_timeouts, gae_lambda=args.gae_lambda, reuse_epochs=args.reuse_epochs,
+                 ppo_clip=args.ppo_clip)
     tr.prepare()
     return flags, net, tr
 
@@ -116,7 +122,32 @@ def build_gen_maze_trainer(args, device):
                  flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
                  flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
                  batch_size=args.actors, seed=0xA3C, groups=args.groups, gae_lambda=args.gae_lambda,
-                 use_depth_prediction=flags.use_depth_prediction, depth_lambda=flags.depth_lambda)
+                 use_depth_prediction=flags.use_depth_prediction, depth_lambda=flags.depth_lambda,
+                 reuse_epochs=args.reuse_epochs, ppo_clip=args.ppo_clip)
+    tr.prepare()
+    return flags, net, tr
+
+
+def build_reuse_trainer(args, device):
+    """bench.build_trainer (one rank, the reference's maze) with the sample-reuse options."""
+    from unreal_amd.environment.environment import Environment
+    from unreal_amd.model.model import UnrealModel
+    from unreal_amd.options import get_options
+    from unreal_amd.train.rmsprop_applier import RMSPropApplier
+    from unreal_amd.train.trainer import Trainer, log_uniform
+    flags = get_options("training", preset="lab", argv=["--env_type", "maze", "--env_name", ""])
+    Environment.action_size = -1
+    net = UnrealModel(Environment.get_action_size("maze", ""), 0, -1, flags.use_lstm, flags.use_pixel_change,
+                      flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
+                      device, seed=1)
+    lr0 = log_uniform(flags.initial_alpha_low, flags.initial_alpha_high, flags.initial_alpha_log_rate)
+    applier = RMSPropApplier(None, decay=flags.rmsp_alpha, momentum=0.0, epsilon=flags.rmsp_epsilon,
+                             clip_norm=flags.grad_norm_clip, device=device)
+    tr = Trainer(0, net, lr0, None, applier, "maze", "", flags.use_lstm, flags.use_pixel_change, flags.use_value_replay,
+                 flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta, flags.local_t_max,
+                 flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
+                 batch_size=args.actors, seed=0xA3C, groups=args.groups, reuse_epochs=args.reuse_epochs,
+                 ppo_clip=args.ppo_clip)
     tr.prepare()
     return flags, net, tr
 
@@ -125,6 +156,8 @@ if args.arcade:
     flags, net, tr = build_arcade_trainer(args, device)
 elif args.gen_maze:
     flags, net, tr = build_gen_maze_trainer(args, device)
+elif args.reuse_epochs > 1:
+    flags, net, tr = build_reuse_trainer(args, device)
 else:
     flags, net, tr = build_trainer(args, 0, 1, device)
 if not args.arcade and not args.gen_maze:                        # (the reference's maze: the returns kernel is chosen per rollout, nothing is allocated)
@@ -146,7 +179,7 @@ while not tr._full:
 torch.cuda.synchronize()
 t_fill = time.time() - t_fill
 out = open(args.out, "w") if args.out else None
-head = {"actors": args.actors, "groups": args.groups, "entropy_beta": tr.entropy_beta, "history": args.history, "lr0": tr.initial_learning_rate,
+head = {"actors": args.actors, "groups": args.groups, "reuse_epochs": tr.reuse_epochs, "ppo_clip": tr.ppo_clip, "entropy_beta": tr.entropy_beta, "history": args.history, "lr0": tr.initial_learning_rate,
         "max_time_step": tr.max_global_time_step, "replay_fill_s": round(t_fill, 1)}
 print(json.dumps(head), flush=True)
 if out:
@@ -180,6 +213,8 @@ while global_t < args.steps:
             hist = torch.bincount(tr.full_ring.r_depth.long(), minlength=8).float()
             extra.update(depth_loss=round(l["depth_loss"], 4), depth_accuracy=round(l["depth_accuracy"], 4),
                          depth_majority_rate=round(float(hist.max() / hist.sum()), 4))
+        if tr.reuse_epochs > 1:
+            extra.update(clip_fraction=round(l["clip_fraction"], 4), approx_kl=round(l["approx_kl"], 6))
         line = json.dumps({"global_t": global_t, "episodes": episodes, "bump_rate": round(bump, 5), "goal_rate": round(goal, 6),
                            "mean_return": (score_sum / episodes) if episodes else None,
                            "total_loss": round(l["total_loss"], 4), "entropy": round(l["entropy"], 4),

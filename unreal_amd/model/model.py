@@ -561,12 +561,14 @@ class UnrealModel(object):
     fuse_bptt = True           # BPTT: recurrent dgrad + the earlier step's gate backward in one launch (lstm_bptt_step)
 
     def trunk_forward(self, ring, ws, T, B, lar_from_ring=True, save_c1=True, clip_lar=False,
-                      objective_slot_offset=0, lar_prefilled=False):
+                      objective_slot_offset=0, lar_prefilled=False, objective_prefilled=False):
         """conv encoder -> fc -> (LSTM over T steps from ws.c0/ws.h0); rows = T*B listed in ws.frame_idx.
-        `lar_prefilled`: the caller has written the [last action | last reward] columns of ws.xcat."""
+        `lar_prefilled`: the caller has written the [last action | last reward] columns of ws.xcat;
+        `objective_prefilled`: and the objective columns of a goal-sense maze (a reuse pass re-runs a rollout's rows)."""
         hoist = self.hoist_lstm_x and T > 1
         self.encode_rows(ring, ws, 0, T * B, lar_from_ring, save_c1, clip_lar, objective_slot_offset, lstm_x=hoist,
-                         lar_prefilled=lar_prefilled and self._use_lstm)
+                         lar_prefilled=lar_prefilled and self._use_lstm,
+                         objective_prefilled=objective_prefilled and self._use_lstm)
         if self._use_lstm:
             for t in range(T):
                 self.lstm_step(ws, t, B, fused_x=not hoist)

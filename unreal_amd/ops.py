@@ -1163,6 +1163,28 @@ def base_loss_grad(rows, A, pi, ld_pi, v, action, adv, R, active, beta, grad_sca
           float(beta), float(grad_scale), ptr(dlogits), ptr(dv), ptr(losses))
 
 
+def ppo_heads_loss_grad(rows, A, X, ldx, Wp, bp, Wv, bv, pi_old, ld_old, action, adv, R, active, clip_eps, beta, grad_scale,
+                        pi_out, v_out, dlogits, dv, losses, stats_i, stats_f):
+    """Sample reuse: heads forward + clipped-surrogate loss and gradient of `rows` re-evaluated rollout rows in
+    one launch.  pi_out / v_out as policy_step(u=None), bit for bit; dlogits / dv (None: forward only) as base_loss_grad's
+    with the PPO policy term against pi_old; losses[3] += policy, value, entropy; stats_i[2] += (clipped, counted) rows;
+    stats_f[2] += (sum rho - 1 - ln rho, sum |rho - 1|)."""
+    rows, A, ldx, ld_old = int(rows), int(A), int(ldx), int(ld_old)
+    if rows <= 0 or not 2 <= A <= 18 or ldx < 256 or ld_old < A:
+        raise ValueError("ppo_heads_loss_grad: rows=%d A=%d ldx=%d ld_old=%d" % (rows, A, ldx, ld_old))
+    if not 0.0 < float(clip_eps) < 1.0:
+        raise ValueError("ppo_heads_loss_grad: clip_eps = %r outside (0, 1)" % (clip_eps,))
+    _chk(X, "f32", (rows - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A, "Wp"); _chk(bp, "f32", A, "bp")
+    _chk(Wv, "f32", 256, "Wv"); _chk(bv, "f32", 1, "bv"); _chk(pi_old, "f32", (rows - 1) * ld_old + A, "pi_old")
+    _chk(action, "i32", rows, "action"); _chk(adv, "f32", rows, "adv"); _chk(R, "f32", rows, "R")
+    _chk(active, "i32", rows, "active"); _chk(pi_out, "f32", rows * A, "pi_out"); _chk(v_out, "f32", rows, "v_out")
+    _chk(dlogits, "f32", rows * A, "dlogits", optional=True); _chk(dv, "f32", rows, "dv", optional=dlogits is None)
+    _chk(losses, "f32", 3, "losses"); _chk(stats_i, "i32", 2, "stats_i"); _chk(stats_f, "f32", 2, "stats_f")
+    _call("unreal_ppo_heads_loss_grad", rows, A, ptr(X), ldx, ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(pi_old), ld_old,
+          ptr(action), ptr(adv), ptr(R), ptr(active), float(clip_eps), float(beta), float(grad_scale), ptr(pi_out),
+          ptr(v_out), ptr(dlogits), ptr(dv) if dlogits is not None else None, ptr(losses), ptr(stats_i), ptr(stats_f))
+
+
 def vr_loss_grad(rows, v, R, mask, grad_scale, dv, loss):
     _chk(v, "f32", rows); _chk(R, "f32", rows); _chk(mask, "i32", rows); _chk(dv, "f32", rows); _chk(loss, "f32", 1)
     _call("unreal_vr_loss_grad", rows, ptr(v), ptr(R), ptr(mask), float(grad_scale), ptr(dv), ptr(loss))

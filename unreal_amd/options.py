@@ -57,6 +57,9 @@ def get_options(option_type="training", preset="lab", argv=()):
         # not in the reference, both off by default: Trainer(bootstrap_timeouts=..., gae_lambda=...)
         a("--bootstrap_timeouts", type=_bool, default=False)
         a("--gae_lambda", type=float, default=None)
+        # not in the reference, off by default: Trainer(reuse_epochs=..., ppo_clip=...)
+        a("--reuse_epochs", type=int, default=1)
+        a("--ppo_clip", type=float, default=0.2)
     if option_type == "display":
         a("--frame_save_dir", default="/tmp/unreal_frames")
         a("--recording", type=_bool, default=False)

@@ -106,6 +106,23 @@ class Trainer(object):
                              "first-person 'maze' config" % (env_type,))
         return True, float(depth_lambda)
 
+    REUSE_EPOCHS_MAX = 16
+
+    @staticmethod
+    def check_reuse_options(env_type, reuse_epochs, ppo_clip):
+        """-> (reuse_epochs, ppo_clip) as the trainer keeps them; ValueError for what is out of scope:
+        reuse_epochs must be an int in 1..16 and ppo_clip a finite number with 0 < ppo_clip < 1; more than one update per
+        rollout needs a device environment ('maze', 'arcade'), as groups > 1 does."""
+        if isinstance(reuse_epochs, bool) or not isinstance(reuse_epochs, int) or \
+                not 1 <= reuse_epochs <= Trainer.REUSE_EPOCHS_MAX:
+            raise ValueError("reuse_epochs = %r: an int in 1..%d" % (reuse_epochs, Trainer.REUSE_EPOCHS_MAX))
+        if isinstance(ppo_clip, bool) or not isinstance(ppo_clip, (int, float)) or not 0.0 < ppo_clip < 1.0:
+            raise ValueError("ppo_clip = %r: a number with 0 < ppo_clip < 1" % (ppo_clip,))
+        if reuse_epochs > 1 and env_type not in ("maze", "arcade"):
+            raise ValueError("reuse_epochs > 1 is out of scope for host-fed environments (env_type=%r): it needs "
+                             "env_type 'maze' or 'arcade'" % (env_type,))
+        return int(reuse_epochs), float(ppo_clip)
+
     def __init__(self, thread_index, global_network, initial_learning_rate, learning_rate_input, grad_applier,
                  env_type, env_name, use_lstm, use_pixel_change, use_value_replay, use_reward_prediction,
                  pixel_change_lambda, entropy_beta, local_t_max, n_step_TD, gamma, gamma_pc,
@@ -113,7 +130,10 @@ class Trainer(object):
                  image_shape=(84, 84), is_training=True, n_classes=0, random_state=None, termination_time=50.0,
                  segnet_lambda=1.0, dropout=0.0, batch_size=1, world_size=1, rank=0, seed=0xA3C, draws=None,
                  grad_sync=None, simulator=None, groups=1, overlap_host=None, bootstrap_timeouts=False, gae_lambda=None,
-                 use_depth_prediction=False, depth_lambda=1.0):
+                 use_depth_prediction=False, depth_lambda=1.0, reuse_epochs=1, ppo_clip=0.2):
+        # sample reuse, off by default: reuse_epochs updates per rollout, the later ones clipped-surrogate
+        # (PPO) steps on the same rows against the rollout's policy
+        self.reuse_epochs, self.ppo_clip = self.check_reuse_options(env_type, reuse_epochs, ppo_clip)
         # rollout options, both off by default: an episode cut off at max_episode_steps bootstraps from
         # V(final observation) instead of 0; GAE(lambda) replaces the n-step return
         self.bootstrap_timeouts, self.gae_lambda = self.check_rollout_options(env_type, env_name, bootstrap_timeouts,
@@ -312,6 +332,10 @@ class Trainer(object):
             self.map_boot = torch.stack([b, b + B], dim=1).reshape(-1).contiguous().to(dev)          # [2b + s] = s*B + b
             self.aux_dv = f(Ta * B)
         self.loss_sum = f(8)          # losses summed over the groups of one process() call
+        if self.reuse_epochs > 1:     # sample reuse: the re-evaluated heads and a call's sums over its reuse updates
+            self.pi_new, self.v_new = f(T * B * A), f(T * B)
+            self.reuse_stats_i, self.reuse_stats_f = i(2), f(2)   # (clipped, counted) rows; (sum rho - 1 - ln rho, sum |rho - 1|)
+            self.reuse_loss_sum = f(8)
         self._fill_calls = 0
         self._full = False
         self._group_views = []
@@ -603,13 +627,21 @@ class Trainer(object):
             ops.base_returns(B, T, self.rewards, self.v, self.n_steps, self.boot_v, self.terminal_end, self.gamma,
                              self.R, self.adv)
 
-    def _train_base(self):
+    def _train_base(self, reuse=False):
+        """Loss and backward of the rollout's rows.  `reuse`: the rows have been re-evaluated with the current weights
+        (reuse_gradients): heads, clipped-surrogate loss against the rollout's policy self.pi and gradient in one launch."""
         B, T, A, ws, net, g, p = self.Bg, self.n_step_TD, self.action_size, self.base_ws, self.local_network, \
             self.local_network.g, self.local_network.p
         rows = T * B
-        ops.base_loss_grad(rows, A, self.pi, A, self.v, self.actions, self.adv, self.R, self.active_log,
-                           self.entropy_beta, self.grad_scale, self.dlogits, self.dv, self.losses[0:3])
         feat, ld = net.features(ws)
+        if reuse:
+            ops.ppo_heads_loss_grad(rows, A, feat, ld, p["W_base_fc_p"], p["b_base_fc_p"], p["W_base_fc_v"],
+                                    p["b_base_fc_v"], self.pi, A, self.actions, self.adv, self.R, self.active_log,
+                                    self.ppo_clip, self.entropy_beta, self.grad_scale, self.pi_new, self.v_new,
+                                    self.dlogits, self.dv, self.losses[0:3], self.reuse_stats_i, self.reuse_stats_f)
+        else:
+            ops.base_loss_grad(rows, A, self.pi, A, self.v, self.actions, self.adv, self.R, self.active_log,
+                               self.entropy_beta, self.grad_scale, self.dlogits, self.dv, self.losses[0:3])
         d_feat = self.gws.d_feat
         ops.linear_small_bwd(rows, 256, A, feat, ld, self.dlogits, A, p["W_base_fc_p"], d_feat, 256, False,
                              g["W_base_fc_p"], g["b_base_fc_p"])
@@ -806,6 +838,10 @@ class Trainer(object):
         if self.use_depth_prediction and self.group == 0:
             self.dp_hits.zero_()
         self._train_base()
+        self._train_aux()
+
+    def _train_aux(self):
+        """The auxiliary branches of one update, each with fresh draws, in the reference's order (pc, vr, rp)."""
         if self.batch_aux:
             self._train_aux_batched()
         else:
@@ -816,6 +852,38 @@ class Trainer(object):
         if self.use_reward_prediction:
             self._train_rp()
 
+    def reuse_gradients(self):
+        """One more update's gradient from the rollout compute_gradients() has just made, without an
+        environment step: the trunk re-run on the rollout's rows with the current weights -- frame indices, [last action |
+        last reward | objective] columns and start state as the rollout left them in base_ws --, the clipped-surrogate loss
+        against the behaviour policy self.pi with the rollout's advantages and returns, and the auxiliary branches with
+        fresh draws.  The carried LSTM state, boot_ws and self.pi / self.v are not touched."""
+        if self.reuse_epochs < 2:
+            raise ValueError("reuse_gradients needs Trainer(reuse_epochs > 1): its buffers are not allocated")
+        net = self.local_network
+        net.refresh_shadows()
+        net.begin_pass()                       # the absmax slots belong to a pass: base_ws takes fresh ones
+        net.trunk_forward(self.ring, self.base_ws, self.n_step_TD, self.Bg, lar_from_ring=False, save_c1=True,
+                          lar_prefilled=True, objective_prefilled=True)
+        net.grads.flat.zero_()
+        self.losses.zero_()
+        self._train_base(reuse=True)
+        self._train_aux()
+
+    def _apply_update(self, lr):
+        """Gradient exchange (multi-rank), global-norm clip + RMSProp on local_network.grads.flat."""
+        net = self.local_network
+        if self.grad_sync is not None:
+            if self.time_grad_sync:                  # HIP events on the launch stream around the exchange
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+            self.grad_sync(net.grads.flat)           # RCCL all-reduce (sum of per-rank means / world)
+            if self.time_grad_sync:
+                e1.record()
+                self._sync_events.append((e0, e1))
+        self.last_grad_norm = self.grad_applier.step(net.params.flat, net.grads.flat, lr)
+        net.mark_params_changed()
+
     def process(self, sess=None, global_t=0, summary_writer=None, summary_op_dict=None, score_input=None,
                 sr_input=None, eval_input=None, entropy_input=None, term_global_t=None, losses_input=None,
                 sync_stats=True):
@@ -825,32 +893,37 @@ class Trainer(object):
         if not self._full:
             self._fill_experience(sess)
             return 0, None
-        net = self.local_network
-        G = self.groups
-        if G > 1:
+        G, E = self.groups, self.reuse_epochs
+        if G > 1 or E > 1:
             self.loss_sum.zero_()
+        if E > 1:
+            self.reuse_loss_sum.zero_()
+            self.reuse_stats_i.zero_()
+            self.reuse_stats_f.zero_()
+        # (a group pass is ~300 launches per update: see the dispatch-queue bound below)
+        sync_every = max(1, self.GROUP_SYNC_EVERY // E)
         for g in range(G):                               # G complete actor-learner passes, one after the other
             self._select_group(g)
             # the reference reads global_t when a worker's process() starts (main.py:114-125)
             lr = self._anneal_learning_rate(global_t + g * self.Bg * self.n_step_TD * self.world_size)
             self.compute_gradients()
-            if self.grad_sync is not None:
-                if self.time_grad_sync:                  # HIP events on the launch stream around the exchange
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                self.grad_sync(net.grads.flat)           # RCCL all-reduce (sum of per-rank means / world)
-                if self.time_grad_sync:
-                    e1.record()
-                    self._sync_events.append((e0, e1))
-            self.last_grad_norm = self.grad_applier.step(net.params.flat, net.grads.flat, lr)
-            net.mark_params_changed()
+            self._apply_update(lr)
+            if E > 1:
+                # update 1's losses are the ones last_losses reports under its present keys; the reuse passes overwrite
+                # self.losses.  E - 1 more updates on the same rollout, at this group's learning rate
+                ops.axpy(1.0 / G, self.losses, self.loss_sum)
+                for _ in range(1, E):
+                    self.reuse_gradients()
+                    self._apply_update(lr)
+                    ops.axpy(1.0 / (G * (E - 1)), self.losses, self.reuse_loss_sum)
             ops.rollout_stats(self.Bg, self.n_steps, self.ring.score_valid, self.ring.score_out, self.stats)
             if G > 1:
-                ops.axpy(1.0 / G, self.losses, self.loss_sum)
+                if E == 1:
+                    ops.axpy(1.0 / G, self.losses, self.loss_sum)
                 # bound the un-synchronised dispatch queue like the replay fill does (a group pass is ~300 launches: at
                 # G = 64 one call would enqueue ~19 k dispatches before its only host sync; rocprofv3's counter thread
                 # did not survive ~24 k in the fill, profiles/r02_pmc_fault.log).  One sync per 16 groups: < 0.1 % of a call.
-                if (g + 1) % self.GROUP_SYNC_EVERY == 0 and g + 1 < G:
+                if (g + 1) % sync_every == 0 and g + 1 < G:
                     torch.cuda.current_stream().synchronize()
         if G > 1:
             self._select_group(0)
@@ -877,7 +950,8 @@ class Trainer(object):
         return steps, episodes, score_sum
 
     def _publish_losses(self):
-        l = (self.loss_sum if self.groups > 1 else self.losses).cpu().numpy()    # groups: mean over the call's updates
+        # groups: mean over the call's groups; with reuse_epochs > 1 of every group's update 1 (process())
+        l = (self.loss_sum if self.groups > 1 or self.reuse_epochs > 1 else self.losses).cpu().numpy()
         net = self.local_network
         net.policy_loss, net.value_loss, net.entropy = float(l[0]), float(l[1]), float(l[2])
         net.base_loss = net.policy_loss + net.value_loss
@@ -893,6 +967,12 @@ class Trainer(object):
         if self.use_depth_prediction:
             hits = self.dp_hits.cpu().numpy()
             self.last_losses.update(depth_loss=net.depth_loss, depth_accuracy=float(hits[0]) / max(int(hits[1]), 1))
+        if self.reuse_epochs > 1:         # means over the call's reuse updates; the two counts are exact
+            r = self.reuse_loss_sum.cpu().numpy()
+            si, sf = self.reuse_stats_i.cpu().numpy(), self.reuse_stats_f.cpu().numpy()
+            n = max(int(si[1]), 1)
+            self.last_losses.update(reuse_policy_loss=float(r[0]), reuse_value_loss=float(r[1]), reuse_entropy=float(r[2]),
+                                    clip_fraction=float(si[0]) / n, approx_kl=float(sf[0]) / n)
         return self.last_losses
 
     def _print_log(self, global_t):
