@@ -690,6 +690,38 @@ int unreal_ppo_heads_loss_grad(int rows, int A, const float* X, int ldx, const f
                                const float* R, const int* active, float clip_eps, float entropy_beta, float grad_scale,
                                float* pi_out, float* v_out, float* dlogits /*nullable*/, float* dv, float* losses /*[3]*/,
                                int* stats_i /*[2]*/, float* stats_f /*[2]*/, void* stream);
+/* Count-based exploration bonus on hashed frames (csrc/explore.hip).  The code of an H x W x 3 uint8 frame in
+ * the ring's byte order (y, x, channel), with cell dividing H and W, cell >= 2 and F = (H / cell) (W / cell) 3 <= 1323:
+ *   S_f = sum over the cell's cell^2 pixels of min(byte, vmax),  f = ((y / cell) (W / cell) + x / cell) 3 + c
+ *   level_f = S_f levels / (vmax cell^2 + 1)  (integer division),  h = sum_f level_f mult[f] mod 2^32
+ *   code = (h 0x9E3779B1 mod 2^32) >> (32 - bits)
+ * with levels in 2..64, vmax in 1..255, bits in 10..26: integers throughout, tests/explore_model.py is the host model.
+ * unreal_explore_multipliers: mult[f] = word 0 of Philox4x32-10(key = seed, counter = (f, 0x4558504C)) | 1, f < F.
+ * unreal_frame_codes: codes[r] of frame idx[r] of the pool `frames` (n_frames frames, frame_stride bytes apart: a multiple
+ *   of 16 that is >= H W 3; the pointer 16-byte aligned).  One workgroup per frame: every byte is loaded once, 16 B per
+ *   lane, and pooled in LDS; stride padding is loaded with the last chunk and not counted.  The optional rollout gate
+ *   (active_log [rows], n_steps [B], terminal_end [B]; all three null: every row): row r = t B + b is hashed iff
+ *   active_log[r] != 0 and not (terminal_end[b] != 0 and t == n_steps[b] - 1).  A gated-out row, and a row whose idx is
+ *   outside [0, n_frames), reads no frame and gets code -1.  Also -EINVAL: H or W > 480, cell W 3 > 57344 (LDS).
+ * unreal_count_add: table[codes[r]] += 1 (int32 atomics) for every code in [0, 2^bits); other rows are skipped.
+ * unreal_count_bonus, a later launch: bonus[r] = beta / sqrtf((float)table[codes[r]]) for every such row (0 for the
+ *   others); rewards_total[r] = rewards[r] + bonus[r]; r_bonus (nullable) [n_slots]: r_bonus[frame_idx[r]] = bonus[r] for
+ *   every row with active_log[r] != 0 and frame_idx[r] in [0, n_slots); stats_i[0] += rows with a bonus, stats_i[1] +=
+ *   those whose count is 1, stats_f[0] += sum of bonus.  beta must be finite and >= 0.
+ * unreal_vr_returns_bonus: unreal_vr_returns with the reward of a step = r_reward[i] + r_bonus[i], summed in fp64.
+ * Each returns -EINVAL without a launch for a size <= 0, a null required pointer or a parameter outside its range. */
+int unreal_explore_multipliers(int F, uint64_t seed, uint32_t* mult, void* stream);
+int unreal_frame_codes(int rows, const uint8_t* frames, long frame_stride, int n_frames, int H, int W, const int* idx,
+                       int B, const int* active_log /*nullable*/, const int* n_steps /*nullable*/,
+                       const int* terminal_end /*nullable*/, int cell, int levels, int vmax, int bits,
+                       const uint32_t* mult, int* codes, void* stream);
+int unreal_count_add(int rows, const int* codes, int* table, int bits, void* stream);
+int unreal_count_bonus(int rows, const int* codes, const int* table, int bits, float beta, const float* rewards,
+                       const int* active_log, const int* frame_idx, int n_slots, float* bonus, float* rewards_total,
+                       float* r_bonus /*nullable*/, int* stats_i /*[2]*/, float* stats_f /*[1]*/, void* stream);
+int unreal_vr_returns_bonus(int B, int L, const int* seq_idx, const int* seq_len, const float* r_reward,
+                            const float* r_bonus, const int* r_terminal, const float* boot_v, double gamma, float* R_out,
+                            void* stream);
 int unreal_colsum(int rows, int cols, const float* X, int ld, float* out, void* stream);
 int unreal_relu_mask(int rows, int cols, float* d, int ldd, const float* src, int lds, void* stream);
 

@@ -7,6 +7,7 @@ usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] 
                                   [--max-episode-steps N] [--bootstrap-timeouts] [--gae-lambda L]
                                   [--gen-maze N] [--depth-prediction] [--depth-lambda X]
                                   [--reuse-epochs E] [--ppo-clip X]
+                                  [--explore-beta X] [--explore-cell C] [--explore-levels K] [--explore-bits N]
 `--groups G`: G sequential updates per process() call (update density x G, see Trainer).  One JSON line per
 `--log-every` calls: global_t, episodes finished since the last line, their mean return, losses, entropy, steps/s.
 `--arcade GAME`: train on the device arcade with that game's default config instead; a line then also holds
@@ -24,7 +25,10 @@ are the Trainer's rollout options of DESIGN §7o.
 depth-prediction head of DESIGN §7p, and a line then also holds depth_loss, depth_accuracy and depth_majority_rate (the
 share of the most common class among the replay's labels: what a constant prediction would score).
 `--reuse-epochs E [--ppo-clip X]` are the Trainer's sample-reuse options of DESIGN §7q (every environment of this tool): E
-updates per rollout; a line then also holds clip_fraction and approx_kl, and its steps stay environment steps."""
+updates per rollout; a line then also holds clip_fraction and approx_kl, and its steps stay environment steps.
+`--explore-beta X [--explore-cell C] [--explore-levels K] [--explore-bits N]` are the Trainer's exploration-bonus options
+of DESIGN §7r (`--arcade` and `--gen-maze`): a line then also holds explore_bonus and explore_first of its last call.  A
+`--gen-maze` line always holds goals_per_episode and apples_per_episode (the actor records' totals over the line's episodes)."""
 import argparse
 import json
 import os
@@ -60,11 +64,19 @@ ap.add_argument("--depth-prediction", action="store_true", help="the depth-predi
 ap.add_argument("--depth-lambda", type=float, default=1.0, help="weight of the depth loss")
 ap.add_argument("--reuse-epochs", type=int, default=1, help="updates per rollout, 1..16 (DESIGN 7q)")
 ap.add_argument("--ppo-clip", type=float, default=0.2, help="the clip range of the reuse updates' surrogate (DESIGN 7q)")
+ap.add_argument("--explore-beta", type=float, default=0.0, help="exploration bonus beta / sqrt(count) (DESIGN 7r); 0: off")
+ap.add_argument("--explore-cell", type=int, default=7, help="pooling cell of the frame code: 4, 6, 7, 12, 14 or 21")
+ap.add_argument("--explore-levels", type=int, default=8, help="quantisation levels of the frame code, 2..64")
+ap.add_argument("--explore-bits", type=int, default=22, help="the count table has 2^bits entries, 10..26")
 args = ap.parse_args()
 if args.depth_prediction and not args.gen_maze:
     ap.error("--depth-prediction needs a first-person maze: --gen-maze N")
 if args.gen_maze and args.arcade:
     ap.error("--gen-maze and --arcade are two environments")
+if args.explore_beta > 0 and not (args.gen_maze or args.arcade):
+    ap.error("--explore-beta needs --gen-maze N or --arcade GAME")
+explore = dict(explore_beta=args.explore_beta, explore_cell=args.explore_cell, explore_levels=args.explore_levels,
+               explore_bits=args.explore_bits)
 if not args.arcade and (args.action_repeat != 1 or args.return_reward != 0 or args.seed is not None or
                         args.opponent_speed is not None or args.max_episode_steps is not None or
                         args.bootstrap_timeouts):
@@ -95,7 +107,7 @@ def build_arcade_trainer(args, device):
                  flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
                  batch_size=args.actors, seed=0xA3C if args.seed is None else args.seed, groups=args.groups,
                  bootstrap_timeouts=args.bootstrap_timeouts, gae_lambda=args.gae_lambda, reuse_epochs=args.reuse_epochs,
-                 ppo_clip=args.ppo_clip)
+                 ppo_clip=args.ppo_clip, **explore)
     tr.prepare()
     return flags, net, tr
 
@@ -123,7 +135,7 @@ def build_gen_maze_trainer(args, device):
                  flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
                  batch_size=args.actors, seed=0xA3C, groups=args.groups, gae_lambda=args.gae_lambda,
                  use_depth_prediction=flags.use_depth_prediction, depth_lambda=flags.depth_lambda,
-                 reuse_epochs=args.reuse_epochs, ppo_clip=args.ppo_clip)
+                 reuse_epochs=args.reuse_epochs, ppo_clip=args.ppo_clip, **explore)
     tr.prepare()
     return flags, net, tr
 
@@ -179,7 +191,7 @@ while not tr._full:
 torch.cuda.synchronize()
 t_fill = time.time() - t_fill
 out = open(args.out, "w") if args.out else None
-head = {"actors": args.actors, "groups": args.groups, "reuse_epochs": tr.reuse_epochs, "ppo_clip": tr.ppo_clip, "entropy_beta": tr.entropy_beta, "history": args.history, "lr0": tr.initial_learning_rate,
+head = {"actors": args.actors, "groups": args.groups, "reuse_epochs": tr.reuse_epochs, "ppo_clip": tr.ppo_clip, "explore_beta": tr.explore_beta, "entropy_beta": tr.entropy_beta, "history": args.history, "lr0": tr.initial_learning_rate,
         "max_time_step": tr.max_global_time_step, "replay_fill_s": round(t_fill, 1)}
 print(json.dumps(head), flush=True)
 if out:
@@ -190,6 +202,7 @@ TOTALS = {"breakout": ("bricks_per_episode", "lives_lost_per_episode"),
           "duel": ("points_won_per_episode", "points_lost_per_episode", "matches_won_per_episode"),
           "invaders": ("aliens_per_episode", "lives_lost_per_episode", "waves_cleared_per_episode")}.get(args.arcade, ())
 totals = tr.full_ring.actor_records[:, 10:10 + len(TOTALS)].sum(0).cpu() if args.arcade else None
+nav_totals = tr.full_ring.actor_records[:, 3:5].sum(0).cpu() if args.gen_maze else None      # goals_total, apples_total
 while global_t < args.steps:
     tr.process(None, global_t + k % args.log_every * args.actors * flags.n_step_TD, sync_stats=False)
     k += 1
@@ -213,6 +226,14 @@ while global_t < args.steps:
             hist = torch.bincount(tr.full_ring.r_depth.long(), minlength=8).float()
             extra.update(depth_loss=round(l["depth_loss"], 4), depth_accuracy=round(l["depth_accuracy"], 4),
                          depth_majority_rate=round(float(hist.max() / hist.sum()), 4))
+        if args.gen_maze:
+            now = tr.full_ring.actor_records[:, 3:5].sum(0).cpu()
+            d = (now - nav_totals).tolist()
+            nav_totals = now
+            extra.update(goals_per_episode=round(d[0] / episodes, 4) if episodes else None,
+                         apples_per_episode=round(d[1] / episodes, 4) if episodes else None)
+        if tr.explore_beta > 0:
+            extra.update(explore_bonus=round(l["explore_bonus"], 6), explore_first=round(l["explore_first"], 6))
         if tr.reuse_epochs > 1:
             extra.update(clip_fraction=round(l["clip_fraction"], 4), approx_kl=round(l["approx_kl"], 6))
         line = json.dumps({"global_t": global_t, "episodes": episodes, "bump_rate": round(bump, 5), "goal_rate": round(goal, 6),

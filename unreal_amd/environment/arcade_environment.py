@@ -140,8 +140,9 @@ class BatchedArcadeEnvironment(object):
     objective_size = 0
 
     def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
-                 final_obs=False, depth_labels=False):
-        """`actor_base` / `actors_total`: global index of actor 0 and the number of actors over every rank (the serve
+                 final_obs=False, depth_labels=False, bonus=False):
+        """`bonus`: exploration bonus: the ring keeps r_bonus beside r_reward.
+        `actor_base` / `actors_total`: global index of actor 0 and the number of actors over every rank (the serve
         draws are keyed by the global index); `seed`: their key.  `final_obs`: time-limit bootstrapping: the
         rollout steps keep the final observation of an episode that ends by max_episode_steps alone in ring.final_obs
         and flag it 2 instead of 1.  `depth_labels`: refused (first-person mazes only)."""
@@ -155,7 +156,8 @@ class BatchedArcadeEnvironment(object):
         total = batch if actors_total is None else int(actors_total)
         if actor_base < 0 or actor_base + batch > total:
             raise ValueError("actors [%d, %d) outside the %d actors of the job" % (actor_base, actor_base + batch, total))
-        self.ring = ops.Ring(batch, history_size, torch.device(device), arcade=True, final_obs=bool(final_obs))
+        self.ring = ops.Ring(batch, history_size, torch.device(device), arcade=True, final_obs=bool(final_obs),
+                             bonus=bool(bonus))
         block = torch.from_numpy(config.block(seed)).to(self.ring.count.device)
         self.arcade = (block, int(actor_base))
         self.reset()

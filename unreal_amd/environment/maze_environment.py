@@ -558,8 +558,9 @@ class BatchedMazeEnvironment(object):
     frame_scale = 1.0          # ring bytes are the pixel values themselves (0 / 1)
 
     def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
-                 final_obs=False, depth_labels=False):
-        """`depth_labels`: depth prediction, first-person configs only: every kernel that changes an actor's
+                 final_obs=False, depth_labels=False, bonus=False):
+        """`bonus`: exploration bonus: the ring keeps r_bonus beside r_reward.
+        `depth_labels`: depth prediction, first-person configs only: every kernel that changes an actor's
         state is followed by the launch that writes the 12 depth classes of its view into ring.r_depth.
         `config`: a MazeConfig (None: the reference's map).  `actor_base` / `actors_total`: global index of actor 0 and
         the number of actors over every rank (layouts are assigned and reset draws keyed by the global index);
@@ -579,7 +580,7 @@ class BatchedMazeEnvironment(object):
                              gen=(config.generate or 0) if config is not None else 0,
                              gen_styled=config is not None and config.styled,
                              objective_size=config.OBJECTIVE_SIZE if sense else 0, sense=config.N if sense else 0,
-                             final_obs=bool(final_obs), depth=self.depth_labels)
+                             final_obs=bool(final_obs), depth=self.depth_labels, bonus=bool(bonus))
         self.maze = None
         if config is not None:
             total = batch if actors_total is None else int(actors_total)
@@ -718,11 +719,11 @@ class FirstPersonMazeEnvironment(BatchedMazeEnvironment):
     frame_scale = 1.0 / 255.0          # ring bytes 0..255, read like Lab's obs / 255
 
     def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
-                 final_obs=False, depth_labels=False):
+                 final_obs=False, depth_labels=False, bonus=False):
         if config is None or config.view != "first_person":
             raise ValueError("FirstPersonMazeEnvironment needs a MazeConfig with view='first_person'")
         BatchedMazeEnvironment.__init__(self, batch, history_size, device, config, actor_base, actors_total, seed, final_obs,
-                                        depth_labels)
+                                        depth_labels, bonus)
 
     def view(self, b0, b1):
         v = BatchedMazeEnvironment.view(self, b0, b1)
@@ -731,11 +732,11 @@ class FirstPersonMazeEnvironment(BatchedMazeEnvironment):
 
 
 def batched_maze_environment(batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
-                             final_obs=False, depth_labels=False):
+                             final_obs=False, depth_labels=False, bonus=False):
     """The batched maze environment of `config` (None: the reference's map): first-person or top-down, by config.view."""
     cls = FirstPersonMazeEnvironment if config is not None and config.view == "first_person" else BatchedMazeEnvironment
     return cls(batch, history_size, device, config=config, actor_base=actor_base, actors_total=actors_total, seed=seed,
-               final_obs=final_obs, depth_labels=depth_labels)
+               final_obs=final_obs, depth_labels=depth_labels, bonus=bonus)
 
 
 class MazeEnvironment(environment.Environment):

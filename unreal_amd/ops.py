@@ -98,7 +98,7 @@ class Ring(object):
     """Device replay ring + per-actor environment state (layout: include/unreal_hip.h)."""
 
     def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False, nav=False, gen=0,
-                 gen_styled=False, sense=0, arcade=False, final_obs=False, depth=False):
+                 gen_styled=False, sense=0, arcade=False, final_obs=False, depth=False, bonus=False):
         self.B, self.H, self.H1 = B, H, H + 1
         self.objective_size = objective_size
         self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
@@ -124,6 +124,9 @@ class Ring(object):
         if depth and not maze_state:
             raise ValueError("depth labels are kept for first-person device mazes only (Ring(maze_state=True, depth=True))")
         self.r_depth = z(n * DEPTH_POSITIONS, dt=torch.uint8) if depth else None
+        # exploration bonus: the bonus of the step stored in every slot, beside r_reward (unreal_count_bonus),
+        # allocated only when asked
+        self.r_bonus = z(n) if bonus else None
         self.pos = z(B * 2, dt=torch.int32)
         self.last_action = z(B, dt=torch.int32)
         self.last_reward = z(B)
@@ -210,6 +213,8 @@ def ring_view(ring, b0, b1):
     v.r_objective = ring.r_objective[b0 * H1 * obj:b1 * H1 * obj] if obj else None
     dep = getattr(ring, "r_depth", None)
     v.r_depth = dep[b0 * H1 * DEPTH_POSITIONS:b1 * H1 * DEPTH_POSITIONS] if dep is not None else None
+    bon = getattr(ring, "r_bonus", None)
+    v.r_bonus = bon[b0 * H1:b1 * H1] if bon is not None else None
     v.pos = ring.pos[2 * b0:2 * b1]
     for name in ("last_action", "last_reward", "count", "episode_reward", "score_out", "score_valid", "_cur"):
         setattr(v, name, getattr(ring, name)[b0:b1])
@@ -663,11 +668,94 @@ def boot_gather(ring, T, A, terminal_end, n_steps, actions, rewards, frame_idx, 
           int(col0))
 
 
-def vr_returns(ring, L, seq_idx, seq_len, boot_v, gamma, R_out):
+def vr_returns(ring, L, seq_idx, seq_len, boot_v, gamma, R_out, bonus=False):
+    """`bonus`: a ring with r_bonus pays a replayed step r_reward + r_bonus; without one, or by default, r_reward."""
     B = ring.B
     _chk(seq_idx, "i32", L * B); _chk(seq_len, "i32", B); _chk(boot_v, "f32", B); _chk(R_out, "f32", (L - 1) * B)
+    r_bonus = getattr(ring, "r_bonus", None) if bonus else None
+    if r_bonus is not None:
+        _chk(r_bonus, "f32", ring.r_reward.numel(), "r_bonus")
+        _call("unreal_vr_returns_bonus", B, L, ptr(seq_idx), ptr(seq_len), ptr(ring.r_reward), ptr(r_bonus),
+              ptr(ring.r_terminal), ptr(boot_v), float(gamma), ptr(R_out))
+        return
     _call("unreal_vr_returns", B, L, ptr(seq_idx), ptr(seq_len), ptr(ring.r_reward), ptr(ring.r_terminal),
           ptr(boot_v), float(gamma), ptr(R_out))
+
+
+# ---- exploration bonus (csrc/explore.hip, DESIGN §7r) ------------------------------------------------------------------
+EXPLORE_STREAM = 0x4558504C                   # counter word 2 of the multiplier draws ("EXPL")
+EXPLORE_MAX_FEATURES = 1323                   # 21 x 21 x 3: an 84 x 84 frame at cell 4
+
+
+def explore_features(H, W, cell, levels=8, vmax=255, bits=22):
+    """F = (H / cell) (W / cell) 3 of the frame code; ValueError for parameters outside the kernels' ranges."""
+    H, W, cell, levels, vmax, bits = int(H), int(W), int(cell), int(levels), int(vmax), int(bits)
+    if H <= 0 or W <= 0 or cell < 2 or H % cell or W % cell:
+        raise ValueError("explore: cell = %d must be >= 2 and divide the %d x %d frame" % (cell, H, W))
+    F = (H // cell) * (W // cell) * 3
+    if F > EXPLORE_MAX_FEATURES:
+        raise ValueError("explore: %d features at cell %d, at most %d" % (F, cell, EXPLORE_MAX_FEATURES))
+    if not (2 <= levels <= 64 and 1 <= vmax <= 255 and 10 <= bits <= 26):
+        raise ValueError("explore: levels = %d (2..64), vmax = %d (1..255), bits = %d (10..26)" % (levels, vmax, bits))
+    return F
+
+
+def explore_multipliers(F, seed, mult):
+    """mult[f] = word 0 of Philox4x32-10(seed, f, EXPLORE_STREAM) | 1 (uint32 kept in an int32 tensor)."""
+    F = int(F)
+    if not 0 < F <= EXPLORE_MAX_FEATURES:
+        raise ValueError("explore_multipliers: F = %d" % F)
+    _chk(mult, "i32", F, "mult")
+    _call("unreal_explore_multipliers", F, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(mult))
+
+
+def frame_codes(rows, frames, frame_stride, n_frames, H, W, idx, cell, levels, vmax, bits, mult, codes, gate=None):
+    """codes[r] = the code of frame idx[r] of the pool (-1: idx outside [0, n_frames), or gated out).  `gate` = (B,
+    active_log [rows], n_steps [B], terminal_end [B]): row t B + b is hashed iff active_log is set and the step does not
+    end an episode.  A row that is not hashed reads no frame."""
+    rows, n_frames, frame_stride = int(rows), int(n_frames), int(frame_stride)
+    F = explore_features(H, W, cell, levels, vmax, bits)
+    if rows <= 0 or n_frames <= 0 or frame_stride < int(H) * int(W) * 3 or frame_stride % 16:
+        raise ValueError("frame_codes: rows=%d n_frames=%d frame_stride=%d" % (rows, n_frames, frame_stride))
+    _chk(frames, "u8", n_frames * frame_stride, "frames"); _chk(idx, "i32", rows, "idx")
+    _chk(mult, "i32", F, "mult"); _chk(codes, "i32", rows, "codes")
+    B, act, ns, te = 0, None, None, None
+    if gate is not None:
+        B, act, ns, te = gate
+        B = int(B)
+        if B <= 0:
+            raise ValueError("frame_codes: gate B = %d" % B)
+        _chk(act, "i32", rows, "active_log"); _chk(ns, "i32", B, "n_steps"); _chk(te, "i32", B, "terminal_end")
+    _call("unreal_frame_codes", rows, ptr(frames), frame_stride, n_frames, int(H), int(W), ptr(idx), B, ptr(act), ptr(ns),
+          ptr(te), int(cell), int(levels), int(vmax), int(bits), ptr(mult), ptr(codes))
+
+
+def count_add(rows, codes, table, bits):
+    """table[code] += 1 for every code in [0, 2^bits) of codes[:rows] (int32 atomics)."""
+    rows, bits = int(rows), int(bits)
+    if rows <= 0 or not 10 <= bits <= 26:
+        raise ValueError("count_add: rows=%d bits=%d" % (rows, bits))
+    _chk(codes, "i32", rows, "codes"); _chk(table, "i32", 1 << bits, "table")
+    _call("unreal_count_add", rows, ptr(codes), ptr(table), bits)
+
+
+def count_bonus(rows, codes, table, bits, beta, rewards, active_log, frame_idx, bonus, rewards_total, r_bonus, stats_i,
+                stats_f):
+    """bonus = beta / sqrt(table[code]) of every counted row (0 elsewhere), rewards_total = rewards + bonus, r_bonus (None:
+    no scatter) [frame_idx[r]] = bonus[r] on rows with active_log set; stats_i[2] += (rows with a bonus, those counted
+    once), stats_f[1] += sum of bonus."""
+    rows, bits, beta = int(rows), int(bits), float(beta)
+    if rows <= 0 or not 10 <= bits <= 26 or not 0.0 <= beta < float("inf"):
+        raise ValueError("count_bonus: rows=%d bits=%d beta=%r" % (rows, bits, beta))
+    _chk(codes, "i32", rows, "codes"); _chk(table, "i32", 1 << bits, "table"); _chk(rewards, "f32", rows, "rewards")
+    _chk(bonus, "f32", rows, "bonus"); _chk(rewards_total, "f32", rows, "rewards_total")
+    _chk(stats_i, "i32", 2, "stats_i"); _chk(stats_f, "f32", 1, "stats_f")
+    _chk(r_bonus, "f32", 1, "r_bonus", optional=True)
+    if r_bonus is not None:
+        _chk(active_log, "i32", rows, "active_log"); _chk(frame_idx, "i32", rows, "frame_idx")
+    _call("unreal_count_bonus", rows, ptr(codes), ptr(table), bits, beta, ptr(rewards), ptr(active_log), ptr(frame_idx),
+          0 if r_bonus is None else r_bonus.numel(), ptr(bonus), ptr(rewards_total), ptr(r_bonus), ptr(stats_i),
+          ptr(stats_f))
 
 
 def pc_returns(ring, L, seq_idx, seq_len, boot_qmax, gamma_pc, R_out):

@@ -60,6 +60,12 @@ def get_options(option_type="training", preset="lab", argv=()):
         # not in the reference, off by default: Trainer(reuse_epochs=..., ppo_clip=...)
         a("--reuse_epochs", type=int, default=1)
         a("--ppo_clip", type=float, default=0.2)
+        # not in the reference, off by default: Trainer(explore_beta=..., explore_cell=..., explore_levels=...,
+        # explore_bits=...)
+        a("--explore_beta", type=float, default=0.0)
+        a("--explore_cell", type=int, default=7)
+        a("--explore_levels", type=int, default=8)
+        a("--explore_bits", type=int, default=22)
     if option_type == "display":
         a("--frame_save_dir", default="/tmp/unreal_frames")
         a("--recording", type=_bool, default=False)

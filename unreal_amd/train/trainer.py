@@ -123,6 +123,29 @@ class Trainer(object):
                              "env_type 'maze' or 'arcade'" % (env_type,))
         return int(reuse_epochs), float(ppo_clip)
 
+    EXPLORE_CELLS = (4, 6, 7, 12, 14, 21)
+
+    @staticmethod
+    def check_explore_options(env_type, explore_beta, explore_cell=7, explore_levels=8, explore_bits=22):
+        """-> (explore_beta, explore_cell, explore_levels, explore_bits) as the trainer keeps them; ValueError for what is
+        out of scope: explore_beta must be a finite number >= 0, explore_cell one of 4, 6, 7, 12, 14, 21 (the
+        divisors of 84 with at most 1323 features), explore_levels an int in 2..64, explore_bits an int in 10..26; a bonus
+        (explore_beta > 0) needs a device environment ('maze', 'arcade'): the frames are hashed where the rollout left
+        them, in the device ring."""
+        b = explore_beta
+        if isinstance(b, bool) or not isinstance(b, (int, float)) or not 0.0 <= b < float("inf"):
+            raise ValueError("explore_beta = %r: a finite number >= 0" % (b,))
+        for name, v, ok in (("explore_cell", explore_cell, lambda v: v in Trainer.EXPLORE_CELLS),
+                            ("explore_levels", explore_levels, lambda v: 2 <= v <= 64),
+                            ("explore_bits", explore_bits, lambda v: 10 <= v <= 26)):
+            if isinstance(v, bool) or not isinstance(v, int) or not ok(v):
+                raise ValueError("%s = %r: explore_cell one of %r, explore_levels an int in 2..64, explore_bits an int in "
+                                 "10..26" % (name, v, Trainer.EXPLORE_CELLS))
+        if b > 0 and env_type not in ("maze", "arcade"):
+            raise ValueError("explore_beta > 0 is out of scope for host-fed environments (env_type=%r): it needs "
+                             "env_type 'maze' or 'arcade'" % (env_type,))
+        return float(b), int(explore_cell), int(explore_levels), int(explore_bits)
+
     def __init__(self, thread_index, global_network, initial_learning_rate, learning_rate_input, grad_applier,
                  env_type, env_name, use_lstm, use_pixel_change, use_value_replay, use_reward_prediction,
                  pixel_change_lambda, entropy_beta, local_t_max, n_step_TD, gamma, gamma_pc,
@@ -130,7 +153,12 @@ class Trainer(object):
                  image_shape=(84, 84), is_training=True, n_classes=0, random_state=None, termination_time=50.0,
                  segnet_lambda=1.0, dropout=0.0, batch_size=1, world_size=1, rank=0, seed=0xA3C, draws=None,
                  grad_sync=None, simulator=None, groups=1, overlap_host=None, bootstrap_timeouts=False, gae_lambda=None,
-                 use_depth_prediction=False, depth_lambda=1.0, reuse_epochs=1, ppo_clip=0.2):
+                 use_depth_prediction=False, depth_lambda=1.0, reuse_epochs=1, ppo_clip=0.2, explore_beta=0.0,
+                 explore_cell=7, explore_levels=8, explore_bits=22):
+        # exploration bonus, off by default: explore_beta / sqrt(count of the next frame's code) joins the
+        # reward of the base returns and of value replay
+        self.explore_beta, self.explore_cell, self.explore_levels, self.explore_bits = self.check_explore_options(
+            env_type, explore_beta, explore_cell, explore_levels, explore_bits)
         # sample reuse, off by default: reuse_epochs updates per rollout, the later ones clipped-surrogate
         # (PPO) steps on the same rows against the rollout's policy
         self.reuse_epochs, self.ppo_clip = self.check_reuse_options(env_type, reuse_epochs, ppo_clip)
@@ -227,13 +255,15 @@ class Trainer(object):
                                                         config=Environment.MAZE_CONFIG.get(self.env_name),
                                                         actor_base=self.rank * B, actors_total=self.world_size * B,
                                                         seed=self.seed, final_obs=self.bootstrap_timeouts,
-                                                        depth_labels=self.use_depth_prediction)
+                                                        depth_labels=self.use_depth_prediction,
+                                                        bonus=self.explore_beta > 0)
         elif self.env_type == "arcade":
             from ..environment.arcade_environment import BatchedArcadeEnvironment
             self.environment = BatchedArcadeEnvironment(B, self.experience_history_size, dev,
                                                         config=Environment.arcade_config(self.env_name),
                                                         actor_base=self.rank * B, actors_total=self.world_size * B,
-                                                        seed=self.seed, final_obs=self.bootstrap_timeouts)
+                                                        seed=self.seed, final_obs=self.bootstrap_timeouts,
+                                                        bonus=self.explore_beta > 0)
         else:
             from ..environment.hostfed_environment import HostFedEnvironment
             indoor = self.env_type == "indoor"
@@ -336,6 +366,8 @@ class Trainer(object):
             self.pi_new, self.v_new = f(T * B * A), f(T * B)
             self.reuse_stats_i, self.reuse_stats_f = i(2), f(2)   # (clipped, counted) rows; (sum rho - 1 - ln rho, sum |rho - 1|)
             self.reuse_loss_sum = f(8)
+        if self.explore_beta > 0:     # exploration bonus
+            self._prepare_explore(T * B, dev)
         self._fill_calls = 0
         self._full = False
         self._group_views = []
@@ -345,6 +377,52 @@ class Trainer(object):
             self._group_views.append((env, self.full_lstm_c[b0 * 256:b1 * 256], self.full_lstm_h[b0 * 256:b1 * 256], b0))
         self._select_group(0)
         self._rollout_split_setup()
+
+    def _prepare_explore(self, rows, dev):
+        """The exploration bonus's buffers: the hash's multipliers, ONE count table for this trainer (its
+        groups add to it in turn; per rank: not all-reduced, and not checkpointed, like the replay), and a group's rows."""
+        H, W = self.ring.frame_shape
+        scale = float(self.environment.frame_scale)
+        vmax = int(round(1.0 / scale)) if scale > 0 else 0
+        if not 1 <= vmax <= 255:
+            raise ValueError("explore_beta > 0: the environment's frame_scale %r gives a byte range of %d, outside 1..255"
+                             % (scale, vmax))
+        self.explore_vmax = vmax
+        F = ops.explore_features(H, W, self.explore_cell, self.explore_levels, vmax, self.explore_bits)
+        i = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+        f = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
+        self.explore_mult = i(F)
+        ops.explore_multipliers(F, self.seed, self.explore_mult)
+        self.explore_table = i(1 << self.explore_bits)
+        self.explore_codes, self.explore_next_idx = i(rows), i(rows)
+        self.explore_bonus, self.rewards_total = f(rows), f(rows)
+        self.explore_stats_i, self.explore_stats_f = i(2), f(1)   # (earning rows, those counted once); sum of bonus
+
+    def explore_counts(self):
+        """The count table of the exploration bonus: int32 [2^explore_bits] on the device."""
+        if self.explore_beta <= 0:
+            raise ValueError("explore_counts needs Trainer(explore_beta > 0): no table is kept")
+        if self.environment is None:
+            self.prepare()
+        return self.explore_table
+
+    def _explore_rewards(self):
+        """[Exploration bonus] of the rollout just made: the code of every earning row's NEXT observation --
+        row (t, b)'s is the frame row (t + 1, b) read, the last row's the actor's current slot --, the counts, then
+        rewards_total = rewards + explore_beta / sqrt(count) and the ring's r_bonus.  Three launches and a copy, no sync."""
+        B, T, ws, ring = self.Bg, self.n_step_TD, self.base_ws, self.ring
+        rows = T * B
+        H, W = ring.frame_shape
+        if T > 1:
+            ops.copy_(self.explore_next_idx[:rows - B], ws.frame_idx[B:rows])
+        ring.cur_idx(out=self.explore_next_idx[rows - B:rows])
+        ops.frame_codes(rows, ring.frames, ring.frame_stride, ring.B * ring.H1, H, W, self.explore_next_idx,
+                        self.explore_cell, self.explore_levels, self.explore_vmax, self.explore_bits, self.explore_mult,
+                        self.explore_codes, gate=(B, self.active_log, self.n_steps, self.terminal_end))
+        ops.count_add(rows, self.explore_codes, self.explore_table, self.explore_bits)
+        ops.count_bonus(rows, self.explore_codes, self.explore_table, self.explore_bits, self.explore_beta, self.rewards,
+                        self.active_log, ws.frame_idx, self.explore_bonus, self.rewards_total, ring.r_bonus,
+                        self.explore_stats_i, self.explore_stats_f)
 
     @property
     def aux_ws(self):
@@ -620,11 +698,15 @@ class Trainer(object):
         net.value_forward(B, feat, ld, self.boot_v)
         if self.use_lstm:                      # episode ended -> reset_state() (trainer.py:293)
             ops.reset_state(B, self.terminal_end, self.lstm_c, self.lstm_h)
+        rewards = self.rewards
+        if self.explore_beta > 0:              # the returns see rewards + bonus; self.rewards stays extrinsic
+            self._explore_rewards()
+            rewards = self.rewards_total
         if self.bootstrap_timeouts or self.gae_lambda is not None:
-            ops.base_returns_tl(B, T, self.rewards, self.v, self.n_steps, self.boot_v, self.terminal_end, self.gamma,
+            ops.base_returns_tl(B, T, rewards, self.v, self.n_steps, self.boot_v, self.terminal_end, self.gamma,
                                 1.0 if self.gae_lambda is None else self.gae_lambda, self.R, self.adv)
         else:
-            ops.base_returns(B, T, self.rewards, self.v, self.n_steps, self.boot_v, self.terminal_end, self.gamma,
+            ops.base_returns(B, T, rewards, self.v, self.n_steps, self.boot_v, self.terminal_end, self.gamma,
                              self.R, self.adv)
 
     def _train_base(self, reuse=False):
@@ -747,7 +829,7 @@ class Trainer(object):
         ws = self.aux_ws                              # (allocates the per-branch workspace on first use)
         feat, ld = self._sample_sequence()
         net.value_forward(B, feat, ld, self.aux_boot_v)
-        ops.vr_returns(self.ring, Ta + 1, self.seq_idx, self.seq_len, self.aux_boot_v, self.gamma, self.aux_R)
+        ops.vr_returns(self.ring, Ta + 1, self.seq_idx, self.seq_len, self.aux_boot_v, self.gamma, self.aux_R, bonus=True)
         feat, ld = self._aux_forward()
         net.value_forward(rows, feat, ld, self.aux_v)
         ops.vr_loss_grad(rows, self.aux_v, self.aux_R, self.seq_mask, self.grad_scale, self.dv, self.losses[4:5])
@@ -783,7 +865,8 @@ class Trainer(object):
                           p["b_pc_deconv_a"], qmax=self.boot_qmax, hp_max=s_bhp)
         ops.pc_returns(self.ring, L, self.seq_idx2[0], self.seq_len2[0], self.boot_qmax, self.gamma_pc, gws.pc_R)
         net.value_forward(B, feat[ld:], 2 * ld, self.aux_boot_v)
-        ops.vr_returns(self.ring, L, self.seq_idx2[1], self.seq_len2[1], self.aux_boot_v, self.gamma, self.aux_R)
+        ops.vr_returns(self.ring, L, self.seq_idx2[1], self.seq_len2[1], self.aux_boot_v, self.gamma, self.aux_R,
+                       bonus=True)
         # the 2B sequences through the trunk
         ws = self.aux2_ws
         ops.gather_i32(self.seq_idx_cat, self.map_seq, ws.frame_idx[:2 * rows])
@@ -900,6 +983,9 @@ class Trainer(object):
             self.reuse_loss_sum.zero_()
             self.reuse_stats_i.zero_()
             self.reuse_stats_f.zero_()
+        if self.explore_beta > 0:
+            self.explore_stats_i.zero_()
+            self.explore_stats_f.zero_()
         # (a group pass is ~300 launches per update: see the dispatch-queue bound below)
         sync_every = max(1, self.GROUP_SYNC_EVERY // E)
         for g in range(G):                               # G complete actor-learner passes, one after the other
@@ -973,6 +1059,10 @@ class Trainer(object):
             n = max(int(si[1]), 1)
             self.last_losses.update(reuse_policy_loss=float(r[0]), reuse_value_loss=float(r[1]), reuse_entropy=float(r[2]),
                                     clip_fraction=float(si[0]) / n, approx_kl=float(sf[0]) / n)
+        if self.explore_beta > 0:         # over the call's groups; the counts are exact
+            si, sf = self.explore_stats_i.cpu().numpy(), self.explore_stats_f.cpu().numpy()
+            n = max(int(si[0]), 1)
+            self.last_losses.update(explore_bonus=float(sf[0]) / n, explore_first=float(si[1]) / n)
         return self.last_losses
 
     def _print_log(self, global_t):
