@@ -751,6 +751,28 @@ int unreal_pc_deconv_train(int N, int A, const float* hp, const float* hp_absmax
 int unreal_grad_norm(const float* grad, long n, float* scratch /*256 floats*/, float* norm_out, void* stream);
 int unreal_rmsprop_step(float* var, float* ms, float* mom, const float* grad, long n, float lr, float decay,
                         float momentum, float eps, float clip_norm, const float* norm, void* stream);
+/* Global-norm clip + Adam / AdamW (decoupled decay) over a flat fp32 buffer (csrc/adam.hip), PyTorch's
+ * arithmetic in fp32:
+ *   g = grad scale, scale = clip_norm min(1 / norm[0], 1 / clip_norm) when clip_norm > 0 and norm[0] > 0, else 1 (the
+ *     scale of unreal_rmsprop_step; norm from unreal_grad_norm; clip_norm <= 0: no clipping, norm may be null)
+ *   var <- var (1 - lr weight_decay)                 (not executed when weight_decay == 0; the kernel subtracts
+ *     var lr weight_decay together with the step of the last line, so that var is rounded once per call)
+ *   m <- beta1 m + (1 - beta1) g,   v <- beta2 v + (1 - beta2) g g
+ *   var <- var - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ * bc1 = 1 - beta1^t and bc2 = 1 - beta2^t come from the host's step count: no counter on the device, no sync.
+ * -EINVAL without a launch: a null required pointer (norm only when clip_norm > 0), n <= 0, var / m / v / grad not 16-byte
+ * aligned, beta1 or beta2 outside [0, 1), eps <= 0, weight_decay < 0, bc1 or bc2 outside (0, 1], a non-finite scalar. */
+int unreal_adam_step(float* var, float* m, float* v, const float* grad, long n, float lr, float beta1, float beta2,
+                     float eps, float weight_decay, float bc1, float bc2, float clip_norm, const float* norm,
+                     void* stream);
+/* Masked normalisation of a rollout's advantages (csrc/adam.hip).  Over the n rows with active[row] != 0:
+ *   mean = sum adv / n,  var = sum (adv - mean)^2 / n  (population variance, two passes)
+ *   adv_out = (adv - mean) / (sqrt(var) + eps) on active rows, 0 on the others; with n < 2, adv_out = adv on active rows
+ *   stats[0] += mean, stats[1] += sqrt(var), stats[2] += 1  (both 0 when n = 0)
+ * fp64 sums in an order that depends on `rows` alone (one workgroup): the result repeats bit for bit.  -EINVAL without a
+ * launch: rows <= 0, a null pointer, eps <= 0 or non-finite, adv_out == adv. */
+int unreal_adv_normalize(int rows, const float* adv, const int* active, float eps, float* adv_out, float* stats /*[3]*/,
+                         void* stream);
 
 /* ---- device-to-device hand-over of 4-byte words (start_lstm_state = base_lstm_state_out, trainer.py:228-230; the
  * sampled index lists): an ordinary kernel, so the whole path can run under rocprofv3 --pmc ---------------------- */

@@ -175,6 +175,15 @@ def main():
         report("grad_norm + rmsprop", timeit(lambda: (ops.grad_norm(gr, sc, nm),
                                                       ops.rmsprop_step(v, ms, mom, gr, 1e-3, .99, 0., .1, 40., nm))),
                bytes_=n * 32.0)
+        am, av = torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
+        report("grad_norm + adam", timeit(lambda: (ops.grad_norm(gr, sc, nm),
+                                                   ops.adam_step(v, am, av, gr, 1e-3, .9, .999, 1e-8, 0., .1, .001, 40., nm))),
+               bytes_=n * 32.0)
+        rows = 20 * B
+        adv, on = rnd(rows), (torch.rand(rows, device=DEV) < 0.9).to(torch.int32)
+        adv_out, st = torch.zeros(rows, device=DEV), torch.zeros(3, device=DEV)
+        report("adv_normalize rows=%d (one workgroup)" % rows,
+               timeit(lambda: ops.adv_normalize(rows, adv, on, 1e-8, adv_out, st), reps=20), bytes_=rows * 28.0)
 
 
 if __name__ == "__main__":

@@ -8,6 +8,8 @@ usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] 
                                   [--gen-maze N] [--depth-prediction] [--depth-lambda X]
                                   [--reuse-epochs E] [--ppo-clip X]
                                   [--explore-beta X] [--explore-cell C] [--explore-levels K] [--explore-bits N]
+                                  [--optimizer rmsprop|adam] [--adam-beta1 X] [--adam-beta2 X] [--adam-epsilon X]
+                                  [--weight-decay X] [--normalize-advantages]
 `--groups G`: G sequential updates per process() call (update density x G, see Trainer).  One JSON line per
 `--log-every` calls: global_t, episodes finished since the last line, their mean return, losses, entropy, steps/s.
 `--arcade GAME`: train on the device arcade with that game's default config instead; a line then also holds
@@ -28,7 +30,10 @@ share of the most common class among the replay's labels: what a constant predic
 updates per rollout; a line then also holds clip_fraction and approx_kl, and its steps stay environment steps.
 `--explore-beta X [--explore-cell C] [--explore-levels K] [--explore-bits N]` are the Trainer's exploration-bonus options
 of DESIGN §7r (`--arcade` and `--gen-maze`): a line then also holds explore_bonus and explore_first of its last call.  A
-`--gen-maze` line always holds goals_per_episode and apples_per_episode (the actor records' totals over the line's episodes)."""
+`--gen-maze` line always holds goals_per_episode and apples_per_episode (the actor records' totals over the line's episodes).
+`--optimizer adam [--adam-beta1 X] [--adam-beta2 X] [--adam-epsilon X] [--weight-decay X]` steps with AdamApplier instead of
+RMSPropApplier and `--normalize-advantages` is the Trainer's option of that name (every environment of this
+tool); a line then also holds adv_mean and adv_std of its last call, and the head line the optimizer."""
 import argparse
 import json
 import os
@@ -68,6 +73,13 @@ ap.add_argument("--explore-beta", type=float, default=0.0, help="exploration bon
 ap.add_argument("--explore-cell", type=int, default=7, help="pooling cell of the frame code: 4, 6, 7, 12, 14 or 21")
 ap.add_argument("--explore-levels", type=int, default=8, help="quantisation levels of the frame code, 2..64")
 ap.add_argument("--explore-bits", type=int, default=22, help="the count table has 2^bits entries, 10..26")
+ap.add_argument("--optimizer", choices=("rmsprop", "adam"), default="rmsprop", help="the grad_applier (DESIGN 7s)")
+ap.add_argument("--adam-beta1", type=float, default=0.9)
+ap.add_argument("--adam-beta2", type=float, default=0.999)
+ap.add_argument("--adam-epsilon", type=float, default=1e-8)
+ap.add_argument("--weight-decay", type=float, default=0.0, help="AdamW's decoupled decay; 0: Adam")
+ap.add_argument("--normalize-advantages", action="store_true",
+                help="the policy loss reads per-rollout normalised advantages (DESIGN 7s)")
 args = ap.parse_args()
 if args.depth_prediction and not args.gen_maze:
     ap.error("--depth-prediction needs a first-person maze: --gen-maze N")
@@ -85,12 +97,22 @@ if not args.arcade and (args.action_repeat != 1 or args.return_reward != 0 or ar
 device = torch.device("cuda", 0)
 
 
+def build_applier(args, flags, device):
+    """The grad_applier --optimizer names, with the flags' clip norm."""
+    if args.optimizer == "adam":
+        from unreal_amd.train.adam_applier import AdamApplier
+        return AdamApplier(None, beta1=args.adam_beta1, beta2=args.adam_beta2, epsilon=args.adam_epsilon,
+                           weight_decay=args.weight_decay, clip_norm=flags.grad_norm_clip, device=device)
+    from unreal_amd.train.rmsprop_applier import RMSPropApplier
+    return RMSPropApplier(None, decay=flags.rmsp_alpha, momentum=0.0, epsilon=flags.rmsp_epsilon,
+                          clip_norm=flags.grad_norm_clip, device=device)
+
+
 def build_arcade_trainer(args, device):
     """bench.build_trainer for env_type 'arcade' (one rank)."""
     from unreal_amd.environment.environment import Environment
     from unreal_amd.model.model import UnrealModel
     from unreal_amd.options import get_options
-    from unreal_amd.train.rmsprop_applier import RMSPropApplier
     from unreal_amd.train.trainer import Trainer, log_uniform
     limit = {} if args.max_episode_steps is None else dict(max_episode_steps=args.max_episode_steps)
     Environment.register_arcade_config(args.arcade, game=args.arcade, opponent_speed=args.opponent_speed,
@@ -100,14 +122,13 @@ def build_arcade_trainer(args, device):
                       flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
                       device, seed=1 if args.seed is None else args.seed)
     lr0 = log_uniform(flags.initial_alpha_low, flags.initial_alpha_high, flags.initial_alpha_log_rate)
-    applier = RMSPropApplier(None, decay=flags.rmsp_alpha, momentum=0.0, epsilon=flags.rmsp_epsilon,
-                             clip_norm=flags.grad_norm_clip, device=device)
+    applier = build_applier(args, flags, device)
     tr = Trainer(0, net, lr0, None, applier, "arcade", args.arcade, flags.use_lstm, flags.use_pixel_change,
                  flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
                  flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
                  batch_size=args.actors, seed=0xA3C if args.seed is None else args.seed, groups=args.groups,
                  bootstrap_timeouts=args.bootstrap_timeouts, gae_lambda=args.gae_lambda, reuse_epochs=args.reuse_epochs,
-                 ppo_clip=args.ppo_clip, **explore)
+                 ppo_clip=args.ppo_clip, normalize_advantages=args.normalize_advantages, **explore)
     tr.prepare()
     return flags, net, tr
 
@@ -117,7 +138,6 @@ def build_gen_maze_trainer(args, device):
     from unreal_amd.environment.environment import Environment
     from unreal_amd.model.model import UnrealModel
     from unreal_amd.options import get_options
-    from unreal_amd.train.rmsprop_applier import RMSPropApplier
     from unreal_amd.train.trainer import Trainer, log_uniform
     name = "gen_maze_%d" % args.gen_maze
     Environment.register_maze_config(name, view="first_person", generate=args.gen_maze, random_start=True,
@@ -128,24 +148,23 @@ def build_gen_maze_trainer(args, device):
                       flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
                       device, seed=1, use_depth_prediction=flags.use_depth_prediction)
     lr0 = log_uniform(flags.initial_alpha_low, flags.initial_alpha_high, flags.initial_alpha_log_rate)
-    applier = RMSPropApplier(None, decay=flags.rmsp_alpha, momentum=0.0, epsilon=flags.rmsp_epsilon,
-                             clip_norm=flags.grad_norm_clip, device=device)
+    applier = build_applier(args, flags, device)
     tr = Trainer(0, net, lr0, None, applier, "maze", name, flags.use_lstm, flags.use_pixel_change,
                  flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
                  flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
                  batch_size=args.actors, seed=0xA3C, groups=args.groups, gae_lambda=args.gae_lambda,
                  use_depth_prediction=flags.use_depth_prediction, depth_lambda=flags.depth_lambda,
-                 reuse_epochs=args.reuse_epochs, ppo_clip=args.ppo_clip, **explore)
+                 reuse_epochs=args.reuse_epochs, ppo_clip=args.ppo_clip, normalize_advantages=args.normalize_advantages,
+                 **explore)
     tr.prepare()
     return flags, net, tr
 
 
 def build_reuse_trainer(args, device):
-    """bench.build_trainer (one rank, the reference's maze) with the sample-reuse options."""
+    """bench.build_trainer (one rank, the reference's maze) with the sample-reuse, optimizer and normalisation options."""
     from unreal_amd.environment.environment import Environment
     from unreal_amd.model.model import UnrealModel
     from unreal_amd.options import get_options
-    from unreal_amd.train.rmsprop_applier import RMSPropApplier
     from unreal_amd.train.trainer import Trainer, log_uniform
     flags = get_options("training", preset="lab", argv=["--env_type", "maze", "--env_name", ""])
     Environment.action_size = -1
@@ -153,13 +172,12 @@ def build_reuse_trainer(args, device):
                       flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
                       device, seed=1)
     lr0 = log_uniform(flags.initial_alpha_low, flags.initial_alpha_high, flags.initial_alpha_log_rate)
-    applier = RMSPropApplier(None, decay=flags.rmsp_alpha, momentum=0.0, epsilon=flags.rmsp_epsilon,
-                             clip_norm=flags.grad_norm_clip, device=device)
+    applier = build_applier(args, flags, device)
     tr = Trainer(0, net, lr0, None, applier, "maze", "", flags.use_lstm, flags.use_pixel_change, flags.use_value_replay,
                  flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta, flags.local_t_max,
                  flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
                  batch_size=args.actors, seed=0xA3C, groups=args.groups, reuse_epochs=args.reuse_epochs,
-                 ppo_clip=args.ppo_clip)
+                 ppo_clip=args.ppo_clip, normalize_advantages=args.normalize_advantages)
     tr.prepare()
     return flags, net, tr
 
@@ -168,7 +186,7 @@ if args.arcade:
     flags, net, tr = build_arcade_trainer(args, device)
 elif args.gen_maze:
     flags, net, tr = build_gen_maze_trainer(args, device)
-elif args.reuse_epochs > 1:
+elif args.reuse_epochs > 1 or args.optimizer != "rmsprop" or args.normalize_advantages:
     flags, net, tr = build_reuse_trainer(args, device)
 else:
     flags, net, tr = build_trainer(args, 0, 1, device)
@@ -191,7 +209,7 @@ while not tr._full:
 torch.cuda.synchronize()
 t_fill = time.time() - t_fill
 out = open(args.out, "w") if args.out else None
-head = {"actors": args.actors, "groups": args.groups, "reuse_epochs": tr.reuse_epochs, "ppo_clip": tr.ppo_clip, "explore_beta": tr.explore_beta, "entropy_beta": tr.entropy_beta, "history": args.history, "lr0": tr.initial_learning_rate,
+head = {"actors": args.actors, "groups": args.groups, "reuse_epochs": tr.reuse_epochs, "ppo_clip": tr.ppo_clip, "optimizer": tr.grad_applier.kind, "normalize_advantages": tr.normalize_advantages, "explore_beta": tr.explore_beta, "entropy_beta": tr.entropy_beta, "history": args.history, "lr0": tr.initial_learning_rate,
         "max_time_step": tr.max_global_time_step, "replay_fill_s": round(t_fill, 1)}
 print(json.dumps(head), flush=True)
 if out:
@@ -236,6 +254,8 @@ while global_t < args.steps:
             extra.update(explore_bonus=round(l["explore_bonus"], 6), explore_first=round(l["explore_first"], 6))
         if tr.reuse_epochs > 1:
             extra.update(clip_fraction=round(l["clip_fraction"], 4), approx_kl=round(l["approx_kl"], 6))
+        if tr.normalize_advantages:
+            extra.update(adv_mean=round(l["adv_mean"], 6), adv_std=round(l["adv_std"], 6))
         line = json.dumps({"global_t": global_t, "episodes": episodes, "bump_rate": round(bump, 5), "goal_rate": round(goal, 6),
                            "mean_return": (score_sum / episodes) if episodes else None,
                            "total_loss": round(l["total_loss"], 4), "entropy": round(l["entropy"], 4),

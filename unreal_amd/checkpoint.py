@@ -8,7 +8,11 @@ The payload is the flat fp32 parameter buffer (TF layouts, TF variable order -- 
 per-variable offset table, so it can be converted to / from a TF checkpoint of the reference by name.  The
 reference's Saver does NOT include the RMSProp slots (they are created after the saved-variable list is taken,
 SURVEY 5.4) and restarts them at rms = 1, momentum = 0; here they are saved too and `restore(..., restore_slots=
-False)` reproduces the reference's behaviour.  Replay, LSTM state and RNG are not saved (reference: neither)."""
+False)` reproduces the reference's behaviour.  Replay, LSTM state and RNG are not saved (reference: neither).
+
+`"optimizer"` names the applier that wrote the slots ("rmsprop"; a payload without the key is one); an AdamApplier's
+checkpoint ("adam") holds `adam_m`, `adam_v` and the step count `adam_t` instead of `rms` / `momentum`, and a
+restore across optimizers restarts the restoring applier's slots."""
 import glob
 import os
 import warnings
@@ -61,6 +65,8 @@ def save(checkpoint_dir, net, applier, global_t, wall_t, best_score=0.0, name=""
     os.makedirs(checkpoint_dir, exist_ok=True)
     with open(os.path.join(checkpoint_dir, "wall_t." + str(int(global_t))), "w") as f:
         f.write(str(float(wall_t)))
+    kind = getattr(applier, "kind", "rmsprop")           # AdamApplier: "adam" 
+    adam = applier is not None and kind == "adam"
     payload = {
         "format": "unreal_amd.flat.v1",
         "global_t": int(global_t),
@@ -69,9 +75,14 @@ def save(checkpoint_dir, net, applier, global_t, wall_t, best_score=0.0, name=""
         "spec": [(n, tuple(s)) for n, s, _ in net.spec],
         "offsets": {k: (o, n) for k, (o, n, _) in net.params.offsets.items()},
         "params": net.params.flat.detach().cpu(),
-        "rms": None if applier is None or applier.ms is None else applier.ms.detach().cpu(),
-        "momentum": None if applier is None or applier.mom is None else applier.mom.detach().cpu(),
+        "optimizer": kind,
+        "rms": None if applier is None or adam or applier.ms is None else applier.ms.detach().cpu(),
+        "momentum": None if applier is None or adam or applier.mom is None else applier.mom.detach().cpu(),
     }
+    if adam:                                             # Adam's moments and step count; rms / momentum stay None
+        payload["adam_m"] = None if applier.m is None else applier.m.detach().cpu()
+        payload["adam_v"] = None if applier.v is None else applier.v.detach().cpu()
+        payload["adam_t"] = int(applier.t)
     path = os.path.join(checkpoint_dir, checkpoint_name(best_score, global_t, name))
     torch.save(payload, path)
     ck = list_checkpoints(checkpoint_dir, name)
@@ -110,7 +121,20 @@ def restore(checkpoint_dir, net, applier=None, restore_slots=True, name=""):
     net.params.flat.copy_(payload["params"])
     if hasattr(net, "mark_params_changed"):      # derived weight planes must follow the restored parameters
         net.mark_params_changed()
-    if applier is not None:
+    if applier is not None and getattr(applier, "kind", "rmsprop") == "adam":
+        applier._create_slots(net.params.flat)
+        saved = payload.get("optimizer", "rmsprop")      # a payload without the key is an RMSProp checkpoint
+        if restore_slots and saved == "adam" and payload.get("adam_m") is not None:
+            applier.m.copy_(payload["adam_m"])
+            applier.v.copy_(payload["adam_v"])
+            applier.t = int(payload["adam_t"])
+        else:                                   # nothing of Adam's to restore: the moments and the step count restart
+            applier.m.zero_()
+            applier.v.zero_()
+            applier.t = 0
+            warnings.warn("%s: %s; Adam restarts with m = v = 0 and t = 0" % (
+                path, "restore_slots=False" if not restore_slots else "an '%s' checkpoint holds no Adam slots" % saved))
+    elif applier is not None:
         applier._create_slots(net.params.flat)
         if restore_slots and payload.get("rms") is not None:
             applier.ms.copy_(payload["rms"])

@@ -1365,3 +1365,28 @@ def rmsprop_step(var, ms, mom, grad, lr, decay, momentum, eps, clip_norm, norm):
     _chk(norm, "f32", 1, optional=True)
     _call("unreal_rmsprop_step", ptr(var), ptr(ms), ptr(mom), ptr(grad), n, float(lr), float(decay),
           float(momentum), float(eps), float(clip_norm), ptr(norm))
+
+
+def adam_step(var, m, v, grad, lr, beta1, beta2, eps, weight_decay, bc1, bc2, clip_norm, norm):
+    """Global-norm clip + Adam / AdamW on flat buffers: PyTorch's arithmetic in fp32, bc1 = 1 - beta1^t and
+    bc2 = 1 - beta2^t from the caller's step count; norm from grad_norm (None with clip_norm <= 0)."""
+    n = var.numel()
+    _chk(var, "f32", name="var"); _chk(m, "f32", n, "m"); _chk(v, "f32", n, "v"); _chk(grad, "f32", n, "grad")
+    _chk(norm, "f32", 1, "norm", optional=not clip_norm > 0)
+    _call("unreal_adam_step", ptr(var), ptr(m), ptr(v), ptr(grad), n, float(lr), float(beta1), float(beta2), float(eps),
+          float(weight_decay), float(bc1), float(bc2), float(clip_norm), ptr(norm))
+
+
+def adv_normalize(rows, adv, active, eps, adv_out, stats):
+    """Masked advantage normalisation: adv_out = (adv - mean) / (std + eps) over the rows with active != 0, 0 on
+    the others (adv itself with fewer than 2 active rows); stats[3] += mean, std, 1."""
+    rows = int(rows)
+    if rows <= 0:
+        raise ValueError("adv_normalize: rows=%d" % rows)
+    if not 0.0 < float(eps) < float("inf"):
+        raise ValueError("adv_normalize: eps = %r, a finite number > 0" % (eps,))
+    _chk(adv, "f32", rows, "adv"); _chk(active, "i32", rows, "active"); _chk(adv_out, "f32", rows, "adv_out")
+    _chk(stats, "f32", 3, "stats")
+    if adv_out.data_ptr() == adv.data_ptr():
+        raise ValueError("adv_normalize: adv_out must not alias adv")
+    _call("unreal_adv_normalize", rows, ptr(adv), ptr(active), float(eps), ptr(adv_out), ptr(stats))

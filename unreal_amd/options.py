@@ -66,6 +66,14 @@ def get_options(option_type="training", preset="lab", argv=()):
         a("--explore_cell", type=int, default=7)
         a("--explore_levels", type=int, default=8)
         a("--explore_bits", type=int, default=22)
+        # not in the reference, off by default: AdamApplier(beta1, beta2, epsilon, weight_decay) as the
+        # grad_applier instead of RMSPropApplier; Trainer(normalize_advantages=...)
+        a("--optimizer", choices=("rmsprop", "adam"), default="rmsprop")
+        a("--adam_beta1", type=float, default=0.9)
+        a("--adam_beta2", type=float, default=0.999)
+        a("--adam_epsilon", type=float, default=1e-8)
+        a("--weight_decay", type=float, default=0.0)
+        a("--normalize_advantages", type=_bool, default=False)
     if option_type == "display":
         a("--frame_save_dir", default="/tmp/unreal_frames")
         a("--recording", type=_bool, default=False)

@@ -9,6 +9,8 @@ from .. import ops
 
 
 class RMSPropApplier(object):
+    kind = "rmsprop"                    # what checkpoint.save records as "optimizer" (AdamApplier: "adam")
+
     def __init__(self, learning_rate=None, decay=0.9, momentum=0.0, epsilon=1e-10, clip_norm=40.0,
                  device="cuda:0", name="RMSPropApplier"):
         self._name = name

@@ -146,6 +146,18 @@ class Trainer(object):
                              "env_type 'maze' or 'arcade'" % (env_type,))
         return float(b), int(explore_cell), int(explore_levels), int(explore_bits)
 
+    @staticmethod
+    def check_optim_options(normalize_advantages, adv_norm_eps=1e-8):
+        """-> (normalize_advantages, adv_norm_eps) as the trainer keeps them; ValueError for what is out of scope (DESIGN
+        §7s): normalize_advantages must be a bool and adv_norm_eps a finite number > 0 (checked even when the option is
+        off).  Every environment type may normalise: the statistics are taken over the rollout's own rows."""
+        if not isinstance(normalize_advantages, bool):
+            raise ValueError("normalize_advantages = %r: a bool" % (normalize_advantages,))
+        e = adv_norm_eps
+        if isinstance(e, bool) or not isinstance(e, (int, float)) or not 0.0 < e < float("inf"):
+            raise ValueError("adv_norm_eps = %r: a finite number > 0" % (e,))
+        return normalize_advantages, float(e)
+
     def __init__(self, thread_index, global_network, initial_learning_rate, learning_rate_input, grad_applier,
                  env_type, env_name, use_lstm, use_pixel_change, use_value_replay, use_reward_prediction,
                  pixel_change_lambda, entropy_beta, local_t_max, n_step_TD, gamma, gamma_pc,
@@ -154,7 +166,10 @@ class Trainer(object):
                  segnet_lambda=1.0, dropout=0.0, batch_size=1, world_size=1, rank=0, seed=0xA3C, draws=None,
                  grad_sync=None, simulator=None, groups=1, overlap_host=None, bootstrap_timeouts=False, gae_lambda=None,
                  use_depth_prediction=False, depth_lambda=1.0, reuse_epochs=1, ppo_clip=0.2, explore_beta=0.0,
-                 explore_cell=7, explore_levels=8, explore_bits=22):
+                 explore_cell=7, explore_levels=8, explore_bits=22, normalize_advantages=False, adv_norm_eps=1e-8):
+        # advantage normalisation, off by default: the policy loss of every update of a rollout reads
+        # (adv - mean) / (std + eps) over the rollout's active rows; self.adv, self.R and the value loss stay raw
+        self.normalize_advantages, self.adv_norm_eps = self.check_optim_options(normalize_advantages, adv_norm_eps)
         # exploration bonus, off by default: explore_beta / sqrt(count of the next frame's code) joins the
         # reward of the base returns and of value replay
         self.explore_beta, self.explore_cell, self.explore_levels, self.explore_bits = self.check_explore_options(
@@ -368,6 +383,8 @@ class Trainer(object):
             self.reuse_loss_sum = f(8)
         if self.explore_beta > 0:     # exploration bonus
             self._prepare_explore(T * B, dev)
+        if self.normalize_advantages:  # advantage normalisation: a group's rows; (sum of means, of stds, groups)
+            self.adv_norm, self.adv_stats = f(T * B), f(3)
         self._fill_calls = 0
         self._full = False
         self._group_views = []
@@ -708,6 +725,8 @@ class Trainer(object):
         else:
             ops.base_returns(B, T, rewards, self.v, self.n_steps, self.boot_v, self.terminal_end, self.gamma,
                              self.R, self.adv)
+        if self.normalize_advantages:          # after GAE and the bonus have shaped self.adv, which stays raw
+            ops.adv_normalize(T * B, self.adv, self.active_log, self.adv_norm_eps, self.adv_norm, self.adv_stats)
 
     def _train_base(self, reuse=False):
         """Loss and backward of the rollout's rows.  `reuse`: the rows have been re-evaluated with the current weights
@@ -716,13 +735,14 @@ class Trainer(object):
             self.local_network.g, self.local_network.p
         rows = T * B
         feat, ld = net.features(ws)
+        adv = self.adv_norm if self.normalize_advantages else self.adv      # the policy loss's advantages
         if reuse:
             ops.ppo_heads_loss_grad(rows, A, feat, ld, p["W_base_fc_p"], p["b_base_fc_p"], p["W_base_fc_v"],
-                                    p["b_base_fc_v"], self.pi, A, self.actions, self.adv, self.R, self.active_log,
+                                    p["b_base_fc_v"], self.pi, A, self.actions, adv, self.R, self.active_log,
                                     self.ppo_clip, self.entropy_beta, self.grad_scale, self.pi_new, self.v_new,
                                     self.dlogits, self.dv, self.losses[0:3], self.reuse_stats_i, self.reuse_stats_f)
         else:
-            ops.base_loss_grad(rows, A, self.pi, A, self.v, self.actions, self.adv, self.R, self.active_log,
+            ops.base_loss_grad(rows, A, self.pi, A, self.v, self.actions, adv, self.R, self.active_log,
                                self.entropy_beta, self.grad_scale, self.dlogits, self.dv, self.losses[0:3])
         d_feat = self.gws.d_feat
         ops.linear_small_bwd(rows, 256, A, feat, ld, self.dlogits, A, p["W_base_fc_p"], d_feat, 256, False,
@@ -954,7 +974,8 @@ class Trainer(object):
         self._train_aux()
 
     def _apply_update(self, lr):
-        """Gradient exchange (multi-rank), global-norm clip + RMSProp on local_network.grads.flat."""
+        """Gradient exchange (multi-rank), global-norm clip + the grad_applier's step (RMSProp; Adam: DESIGN §7s) on
+        local_network.grads.flat."""
         net = self.local_network
         if self.grad_sync is not None:
             if self.time_grad_sync:                  # HIP events on the launch stream around the exchange
@@ -986,6 +1007,8 @@ class Trainer(object):
         if self.explore_beta > 0:
             self.explore_stats_i.zero_()
             self.explore_stats_f.zero_()
+        if self.normalize_advantages:
+            self.adv_stats.zero_()
         # (a group pass is ~300 launches per update: see the dispatch-queue bound below)
         sync_every = max(1, self.GROUP_SYNC_EVERY // E)
         for g in range(G):                               # G complete actor-learner passes, one after the other
@@ -1063,6 +1086,10 @@ class Trainer(object):
             si, sf = self.explore_stats_i.cpu().numpy(), self.explore_stats_f.cpu().numpy()
             n = max(int(si[0]), 1)
             self.last_losses.update(explore_bonus=float(sf[0]) / n, explore_first=float(si[1]) / n)
+        if self.normalize_advantages:     # means over the call's groups of each rollout's mean and std
+            st = self.adv_stats.cpu().numpy()
+            n = max(float(st[2]), 1.0)
+            self.last_losses.update(adv_mean=float(st[0]) / n, adv_std=float(st[1]) / n)
         return self.last_losses
 
     def _print_log(self, global_t):
