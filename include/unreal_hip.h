@@ -773,6 +773,21 @@ int unreal_adam_step(float* var, float* m, float* v, const float* grad, long n, 
  * launch: rows <= 0, a null pointer, eps <= 0 or non-finite, adv_out == adv. */
 int unreal_adv_normalize(int rows, const float* adv, const int* active, float eps, float* adv_out, float* stats /*[3]*/,
                          void* stream);
+/* Minibatched reuse epochs (csrc/minibatch.hip): the rows of the block of Bm actors that starts at actor j0 of
+ * a rollout over Bg actors, compacted in ONE launch.  Source row t Bg + j0 + j -> destination row t Bm + j (t < T, j < Bm)
+ * of frame_idx, actions, active (int32), adv, R (fp32) and pi (fp32, [rows][A]); with an LSTM also the `side` columns from
+ * column 256 of the rows of xcat (leading dimension ld on both sides: [one-hot last action | last reward | objective], side
+ * = A + 1 + objective_size; the destination's other columns are not written) and c0 / h0 [Bg][256] from actor j0 into
+ * c0_out / h0_out [Bm][256], 16 bytes per lane.  A bit-exact copy; nothing past row T Bm (actor Bm) is written.
+ * -EINVAL without a launch: T <= 0, Bm <= 0, j0 < 0, j0 + Bm > Bg, A outside 2..18, side < 0 or 256 + side > ld, a null
+ * required pointer, some but not all of xcat, xcat_out, c0, h0, c0_out, h0_out given (feed-forward: none), a c0 / h0
+ * pointer that is not 16-byte aligned. */
+int unreal_minibatch_gather(int T, int Bg, int Bm, int j0, int A, const int* frame_idx, const int* actions,
+                            const int* active, const float* adv, const float* R, const float* pi, int* frame_idx_out,
+                            int* actions_out, int* active_out, float* adv_out, float* R_out, float* pi_out, int side, int ld,
+                            const float* xcat /*nullable*/, float* xcat_out /*nullable*/, const float* c0 /*nullable*/,
+                            const float* h0 /*nullable*/, float* c0_out /*nullable*/, float* h0_out /*nullable*/,
+                            void* stream);
 
 /* ---- device-to-device hand-over of 4-byte words (start_lstm_state = base_lstm_state_out, trainer.py:228-230; the
  * sampled index lists): an ordinary kernel, so the whole path can run under rocprofv3 --pmc ---------------------- */

@@ -6,7 +6,7 @@ usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] 
                                   [--opponent-speed N] [--action-repeat K] [--return-reward R] [--seed S]
                                   [--max-episode-steps N] [--bootstrap-timeouts] [--gae-lambda L]
                                   [--gen-maze N] [--depth-prediction] [--depth-lambda X]
-                                  [--reuse-epochs E] [--ppo-clip X]
+                                  [--reuse-epochs E] [--ppo-clip X] [--reuse-minibatches M]
                                   [--explore-beta X] [--explore-cell C] [--explore-levels K] [--explore-bits N]
                                   [--optimizer rmsprop|adam] [--adam-beta1 X] [--adam-beta2 X] [--adam-epsilon X]
                                   [--weight-decay X] [--normalize-advantages]
@@ -28,6 +28,8 @@ depth-prediction head of DESIGN §7p, and a line then also holds depth_loss, dep
 share of the most common class among the replay's labels: what a constant prediction would score).
 `--reuse-epochs E [--ppo-clip X]` are the Trainer's sample-reuse options of DESIGN §7q (every environment of this tool): E
 updates per rollout; a line then also holds clip_fraction and approx_kl, and its steps stay environment steps.
+`--reuse-minibatches M` is the Trainer's option of DESIGN §7t: every rollout is consumed as E x M clipped-surrogate updates,
+each on one block of actors / groups / M actors; a line then also holds updates, the optimiser steps of its last call.
 `--explore-beta X [--explore-cell C] [--explore-levels K] [--explore-bits N]` are the Trainer's exploration-bonus options
 of DESIGN §7r (`--arcade` and `--gen-maze`): a line then also holds explore_bonus and explore_first of its last call.  A
 `--gen-maze` line always holds goals_per_episode and apples_per_episode (the actor records' totals over the line's episodes).
@@ -69,6 +71,7 @@ ap.add_argument("--depth-prediction", action="store_true", help="the depth-predi
 ap.add_argument("--depth-lambda", type=float, default=1.0, help="weight of the depth loss")
 ap.add_argument("--reuse-epochs", type=int, default=1, help="updates per rollout, 1..16 (DESIGN 7q)")
 ap.add_argument("--ppo-clip", type=float, default=0.2, help="the clip range of the reuse updates' surrogate (DESIGN 7q)")
+ap.add_argument("--reuse-minibatches", type=int, default=1, help="updates per reuse epoch, each on 1/M of a group's actors (DESIGN 7t)")
 ap.add_argument("--explore-beta", type=float, default=0.0, help="exploration bonus beta / sqrt(count) (DESIGN 7r); 0: off")
 ap.add_argument("--explore-cell", type=int, default=7, help="pooling cell of the frame code: 4, 6, 7, 12, 14 or 21")
 ap.add_argument("--explore-levels", type=int, default=8, help="quantisation levels of the frame code, 2..64")
@@ -128,7 +131,8 @@ def build_arcade_trainer(args, device):
                  flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
                  batch_size=args.actors, seed=0xA3C if args.seed is None else args.seed, groups=args.groups,
                  bootstrap_timeouts=args.bootstrap_timeouts, gae_lambda=args.gae_lambda, reuse_epochs=args.reuse_epochs,
-                 ppo_clip=args.ppo_clip, normalize_advantages=args.normalize_advantages, **explore)
+                 ppo_clip=args.ppo_clip, normalize_advantages=args.normalize_advantages,
+                 reuse_minibatches=args.reuse_minibatches, **explore)
     tr.prepare()
     return flags, net, tr
 
@@ -155,7 +159,7 @@ def build_gen_maze_trainer(args, device):
                  batch_size=args.actors, seed=0xA3C, groups=args.groups, gae_lambda=args.gae_lambda,
                  use_depth_prediction=flags.use_depth_prediction, depth_lambda=flags.depth_lambda,
                  reuse_epochs=args.reuse_epochs, ppo_clip=args.ppo_clip, normalize_advantages=args.normalize_advantages,
-                 **explore)
+                 reuse_minibatches=args.reuse_minibatches, **explore)
     tr.prepare()
     return flags, net, tr
 
@@ -177,7 +181,8 @@ def build_reuse_trainer(args, device):
                  flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta, flags.local_t_max,
                  flags.n_step_TD, flags.gamma, flags.gamma_pc, args.history, flags.max_time_step, device,
                  batch_size=args.actors, seed=0xA3C, groups=args.groups, reuse_epochs=args.reuse_epochs,
-                 ppo_clip=args.ppo_clip, normalize_advantages=args.normalize_advantages)
+                 ppo_clip=args.ppo_clip, normalize_advantages=args.normalize_advantages,
+                 reuse_minibatches=args.reuse_minibatches)
     tr.prepare()
     return flags, net, tr
 
@@ -186,7 +191,7 @@ if args.arcade:
     flags, net, tr = build_arcade_trainer(args, device)
 elif args.gen_maze:
     flags, net, tr = build_gen_maze_trainer(args, device)
-elif args.reuse_epochs > 1 or args.optimizer != "rmsprop" or args.normalize_advantages:
+elif args.reuse_epochs > 1 or args.reuse_minibatches > 1 or args.optimizer != "rmsprop" or args.normalize_advantages:
     flags, net, tr = build_reuse_trainer(args, device)
 else:
     flags, net, tr = build_trainer(args, 0, 1, device)
@@ -209,7 +214,7 @@ while not tr._full:
 torch.cuda.synchronize()
 t_fill = time.time() - t_fill
 out = open(args.out, "w") if args.out else None
-head = {"actors": args.actors, "groups": args.groups, "reuse_epochs": tr.reuse_epochs, "ppo_clip": tr.ppo_clip, "optimizer": tr.grad_applier.kind, "normalize_advantages": tr.normalize_advantages, "explore_beta": tr.explore_beta, "entropy_beta": tr.entropy_beta, "history": args.history, "lr0": tr.initial_learning_rate,
+head = {"actors": args.actors, "groups": args.groups, "reuse_epochs": tr.reuse_epochs, "reuse_minibatches": tr.reuse_minibatches, "ppo_clip": tr.ppo_clip, "optimizer": tr.grad_applier.kind, "normalize_advantages": tr.normalize_advantages, "explore_beta": tr.explore_beta, "entropy_beta": tr.entropy_beta, "history": args.history, "lr0": tr.initial_learning_rate,
         "max_time_step": tr.max_global_time_step, "replay_fill_s": round(t_fill, 1)}
 print(json.dumps(head), flush=True)
 if out:
@@ -252,8 +257,10 @@ while global_t < args.steps:
                          apples_per_episode=round(d[1] / episodes, 4) if episodes else None)
         if tr.explore_beta > 0:
             extra.update(explore_bonus=round(l["explore_bonus"], 6), explore_first=round(l["explore_first"], 6))
-        if tr.reuse_epochs > 1:
+        if tr.reuse_epochs > 1 or tr.reuse_minibatches > 1:
             extra.update(clip_fraction=round(l["clip_fraction"], 4), approx_kl=round(l["approx_kl"], 6))
+        if tr.reuse_minibatches > 1:
+            extra.update(updates=l["updates"])
         if tr.normalize_advantages:
             extra.update(adv_mean=round(l["adv_mean"], 6), adv_std=round(l["adv_std"], 6))
         line = json.dumps({"global_t": global_t, "episodes": episodes, "bump_rate": round(bump, 5), "goal_rate": round(goal, 6),

@@ -1390,3 +1390,36 @@ def adv_normalize(rows, adv, active, eps, adv_out, stats):
     if adv_out.data_ptr() == adv.data_ptr():
         raise ValueError("adv_normalize: adv_out must not alias adv")
     _call("unreal_adv_normalize", rows, ptr(adv), ptr(active), float(eps), ptr(adv_out), ptr(stats))
+
+
+def minibatch_gather(T, Bg, Bm, j0, A, frame_idx, actions, active, adv, R, pi, frame_idx_out, actions_out, active_out,
+                     adv_out, R_out, pi_out, side=0, ld=256, xcat=None, xcat_out=None, c0=None, h0=None, c0_out=None,
+                     h0_out=None):
+    """Minibatched reuse epochs: rows t * Bg + j0 + j of a rollout over Bg actors -> rows t * Bm + j (t < T,
+    j < Bm) of every per-row stream of a reuse pass, in one launch; bit for bit.  With an LSTM (all six of xcat .. h0_out)
+    also the `side` columns from column 256 of the xcat rows (leading dimension `ld` on both sides) and the start state of
+    the actors [j0, j0 + Bm); feed-forward: none of the six."""
+    T, Bg, Bm, j0, A, side, ld = int(T), int(Bg), int(Bm), int(j0), int(A), int(side), int(ld)
+    if T <= 0 or Bm <= 0 or j0 < 0 or j0 + Bm > Bg or not 2 <= A <= 18:
+        raise ValueError("minibatch_gather: T=%d Bg=%d Bm=%d j0=%d A=%d" % (T, Bg, Bm, j0, A))
+    if side < 0 or 256 + side > ld:
+        raise ValueError("minibatch_gather: side=%d does not fit in ld=%d" % (side, ld))
+    lstm = (xcat, xcat_out, c0, h0, c0_out, h0_out)
+    if any(t is not None for t in lstm) and any(t is None for t in lstm):
+        raise ValueError("minibatch_gather: xcat, xcat_out, c0, h0, c0_out, h0_out go together (all, or none without an LSTM)")
+    src, dst = T * Bg, T * Bm
+    for t, dt, n, name in ((frame_idx, "i32", src, "frame_idx"), (actions, "i32", src, "actions"),
+                           (active, "i32", src, "active"), (adv, "f32", src, "adv"), (R, "f32", src, "R"),
+                           (pi, "f32", src * A, "pi"), (frame_idx_out, "i32", dst, "frame_idx_out"),
+                           (actions_out, "i32", dst, "actions_out"), (active_out, "i32", dst, "active_out"),
+                           (adv_out, "f32", dst, "adv_out"), (R_out, "f32", dst, "R_out"), (pi_out, "f32", dst * A, "pi_out")):
+        _chk(t, dt, n, name)
+    if xcat is not None:
+        _chk(xcat, "f32", (src - 1) * ld + 256 + side, "xcat"); _chk(xcat_out, "f32", (dst - 1) * ld + 256 + side, "xcat_out")
+        _chk(c0, "f32", Bg * 256, "c0"); _chk(h0, "f32", Bg * 256, "h0")
+        _chk(c0_out, "f32", Bm * 256, "c0_out"); _chk(h0_out, "f32", Bm * 256, "h0_out")
+        if any(t.data_ptr() % 16 for t in (c0, h0, c0_out, h0_out)):
+            raise ValueError("minibatch_gather: c0 / h0 must be 16-byte aligned")
+    _call("unreal_minibatch_gather", T, Bg, Bm, j0, A, ptr(frame_idx), ptr(actions), ptr(active), ptr(adv), ptr(R), ptr(pi),
+          ptr(frame_idx_out), ptr(actions_out), ptr(active_out), ptr(adv_out), ptr(R_out), ptr(pi_out), side, ld, ptr(xcat),
+          ptr(xcat_out), ptr(c0), ptr(h0), ptr(c0_out), ptr(h0_out))

@@ -60,6 +60,8 @@ def get_options(option_type="training", preset="lab", argv=()):
         # not in the reference, off by default: Trainer(reuse_epochs=..., ppo_clip=...)
         a("--reuse_epochs", type=int, default=1)
         a("--ppo_clip", type=float, default=0.2)
+        # not in the reference, off by default: Trainer(reuse_minibatches=...)
+        a("--reuse_minibatches", type=int, default=1)
         # not in the reference, off by default: Trainer(explore_beta=..., explore_cell=..., explore_levels=...,
         # explore_bits=...)
         a("--explore_beta", type=float, default=0.0)

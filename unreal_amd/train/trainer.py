@@ -68,7 +68,23 @@ class PhiloxDraws(object):
         return out
 
 
-class Trainer(object):
+class PassState(object):
+    """What the loss branches of ONE update read and write, sized for `Bg` actors: the path and gradient workspaces, the
+    replay samples' buffers, the heads' outputs and gradients, the ring the replay branches sample (`ring`) and the ring the
+    base rows' frame indices point into (`base_ring`).  The Trainer is its own for a whole group; with reuse_minibatches > 1
+    a second one, sized for a block of the group's actors, also holds the block's compacted rollout rows."""
+
+    @property
+    def aux_ws(self):
+        """Workspace of the one-branch-at-a-time replay schedule (lazy: see Trainer.prepare())."""
+        if self._aux_ws is None and self._aux_ws_args is not None:
+            rows, B, dev, lstm, xld = self._aux_ws_args
+            self._aux_ws = PathWS(rows, B, dev, save_c1=True, lstm=lstm, xld=xld, **self.local_network.ws_kw)
+            self.gws.ensure_rows(rows, B, dev)
+        return self._aux_ws
+
+
+class Trainer(PassState):
     @staticmethod
     def check_rollout_options(env_type, env_name, bootstrap_timeouts, gae_lambda):
         """-> (bootstrap_timeouts, gae_lambda) as the trainer keeps them; ValueError for what is out of scope: gae_lambda
@@ -123,6 +139,28 @@ class Trainer(object):
                              "env_type 'maze' or 'arcade'" % (env_type,))
         return int(reuse_epochs), float(ppo_clip)
 
+    @staticmethod
+    def check_minibatch_options(env_type, batch_size, groups, reuse_minibatches):
+        """-> reuse_minibatches as the trainer keeps it; ValueError for what is out of scope: an int >= 1 that
+        divides the actors of a group, batch_size // groups; more than one needs a device environment ('maze', 'arcade'),
+        as reuse_epochs > 1 does."""
+        M = reuse_minibatches
+        if isinstance(M, bool) or not isinstance(M, int) or M < 1:
+            raise ValueError("reuse_minibatches = %r: an int >= 1" % (M,))
+        if M > 1:
+            if env_type not in ("maze", "arcade"):
+                raise ValueError("reuse_minibatches > 1 is out of scope for host-fed environments (env_type=%r): it needs "
+                                 "env_type 'maze' or 'arcade'" % (env_type,))
+            B, G = int(batch_size), int(groups)
+            if G < 1 or B % G or (B // G) % M:
+                raise ValueError("reuse_minibatches = %d must divide the %d // %d actors of a group" % (M, B, G))
+        return int(M)
+
+    @staticmethod
+    def minibatch_order(epoch, M):
+        """The blocks of a group's actors in the order epoch `epoch` (1-based) visits them: (i + epoch - 1) mod M."""
+        return [(i + epoch - 1) % M for i in range(M)]
+
     EXPLORE_CELLS = (4, 6, 7, 12, 14, 21)
 
     @staticmethod
@@ -166,7 +204,11 @@ class Trainer(object):
                  segnet_lambda=1.0, dropout=0.0, batch_size=1, world_size=1, rank=0, seed=0xA3C, draws=None,
                  grad_sync=None, simulator=None, groups=1, overlap_host=None, bootstrap_timeouts=False, gae_lambda=None,
                  use_depth_prediction=False, depth_lambda=1.0, reuse_epochs=1, ppo_clip=0.2, explore_beta=0.0,
-                 explore_cell=7, explore_levels=8, explore_bits=22, normalize_advantages=False, adv_norm_eps=1e-8):
+                 explore_cell=7, explore_levels=8, explore_bits=22, normalize_advantages=False, adv_norm_eps=1e-8,
+                 reuse_minibatches=1):
+        # minibatched reuse epochs, off by default: a rollout is consumed as reuse_epochs * reuse_minibatches
+        # clipped-surrogate updates, each on one block of the group's actors
+        self.reuse_minibatches = self.check_minibatch_options(env_type, batch_size, groups, reuse_minibatches)
         # advantage normalisation, off by default: the policy loss of every update of a rollout reads
         # (adv - mean) / (std + eps) over the rollout's active rows; self.adv, self.R and the value loss stay raw
         self.normalize_advantages, self.adv_norm_eps = self.check_optim_options(normalize_advantages, adv_norm_eps)
@@ -315,27 +357,9 @@ class Trainer(object):
         self.local_network.lar_bounded = self.env_type == "maze" and (conf is None or conf.reward_bound <= 1)
         self.experience = Experience(self.experience_history_size, ring=self.full_ring)
         B = self.Bg                                  # everything below is sized for ONE group
-        lstm = self.use_lstm
-        aux = self.use_pixel_change or self.use_value_replay
-        xld = self.local_network.xld
-        wkw = self.local_network.ws_kw                # conv activation sizes of the network's frame size
-        self.base_ws = PathWS(T * B, B, dev, save_c1=True, lstm=lstm, xld=xld, **wkw)
-        self.boot_ws = PathWS(B, B, dev, save_c1=False, lstm=lstm, xld=xld, **wkw)
-        self.rp_ws = PathWS(3 * B, B, dev, save_c1=True, lstm=False, xld=xld, **wkw) if self.use_reward_prediction else None
-        # pixel control and value replay as ONE batch of 2B replayed sequences (actor 2b = pc sample of b, 2b + 1 = vr
-        # sample): see _train_aux_batched.  Decided HERE, once (the class default is read at prepare() time only).
-        self.batch_aux = bool(self.batch_aux_default and self.use_pixel_change and self.use_value_replay)
-        # per-branch workspaces (_train_pc / _train_vr: one of the two tasks on, or batch_aux off) are allocated on first
-        # use: with the batched pass they would be ~5 GB of dead HBM per rank at 4096 actors
-        self._aux_ws = None
-        self._aux_ws_args = (Ta * B, B, dev, lstm, xld) if aux else None
-        per_branch = aux and not self.batch_aux
-        rows = max(T, Ta if per_branch else 0, 3 if self.use_reward_prediction else 0) * B
-        self.gws = GradWS(rows, B, dev, lstm=lstm, pc=self.use_pixel_change and per_branch, A=A, f2_dim=wkw["f2_dim"])
-        if self.batch_aux:
-            self.aux2_ws = PathWS(Ta * 2 * B, 2 * B, dev, save_c1=True, lstm=lstm, xld=xld, **wkw)
-            self.boot2_ws = PathWS(2 * B, 2 * B, dev, save_c1=False, lstm=lstm, xld=xld, **wkw)
-            self.gws2 = GradWS(Ta * 2 * B, 2 * B, dev, lstm=lstm, pc=True, A=A, pc_rows=Ta * B, f2_dim=wkw["f2_dim"])
+        M = self.reuse_minibatches
+        reuse = self.reuse_epochs > 1 or M > 1
+        self._alloc_pass(self, B, reuse)
         f = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
         i = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
         d = lambda n: torch.zeros(n, dtype=torch.float64, device=dev)
@@ -345,46 +369,33 @@ class Trainer(object):
         self.active_log, self.active = i(T * B), i(B)
         self.n_steps, self.terminal_end = i(B), i(B)
         self.boot_v, self.R, self.adv = f(B), f(T * B), f(T * B)
-        self.dlogits, self.dv = f(max(T, Ta) * B * A), f(max(T, Ta) * B)
         self.u_act = d(T * B)
         self.losses = f(8)            # policy, value, entropy, pc, vr, rp, depth
         if self.use_depth_prediction:
-            from ..model.model import DEPTH_HIDDEN, DEPTH_OUT
-            self.dp_hidden, self.dp_d_hidden = f(T * B * DEPTH_HIDDEN), f(T * B * DEPTH_HIDDEN)
-            self.dp_logits, self.dp_dlogits = f(T * B * DEPTH_OUT), f(T * B * DEPTH_OUT)
             self.dp_hits = i(2)       # positions predicted right, positions counted: summed over a call's groups
         self.stats = d(3)
-        if aux:
-            L = Ta + 1
-            self.seq_idx, self.seq_len, self.seq_start = i(L * B), i(B), i(B)
-            self.seq_mask, self.seq_act = i(Ta * B), i(Ta * B)
-            self.aux_v, self.aux_R, self.aux_boot_v = f(Ta * B), f(Ta * B), f(B)
-            if self.use_pixel_change:
-                self.boot_hp, self.boot_qmax = f(B * ops.F2_DIM), f(B * ops.PC_CELLS)
-        if self.use_reward_prediction:
-            self.rp_coin, self.rp_u, self.rp_class = i(B), d(B), i(B)
-            self.rp_logits, self.rp_dlogits = f(B * 3), f(B * 3)
-        if self.batch_aux:
-            L = Ta + 1
-            self.seq_idx_cat = i(2 * L * B)
-            self.seq_idx2 = [self.seq_idx_cat[:L * B], self.seq_idx_cat[L * B:]]
-            self.seq_len2, self.seq_start2 = [i(B), i(B)], [i(B), i(B)]
-            self.seq_mask2 = [i(Ta * B), i(Ta * B)]
-            self.last2 = i(2 * B)
-            r = torch.arange(Ta * B, dtype=torch.int32)
-            self.map_seq = torch.stack([r, r + L * B], dim=1).reshape(-1).contiguous().to(dev)      # [2r + s] = s*L*B + r
-            b = torch.arange(B, dtype=torch.int32)
-            self.map_boot = torch.stack([b, b + B], dim=1).reshape(-1).contiguous().to(dev)          # [2b + s] = s*B + b
-            self.aux_dv = f(Ta * B)
         self.loss_sum = f(8)          # losses summed over the groups of one process() call
-        if self.reuse_epochs > 1:     # sample reuse: the re-evaluated heads and a call's sums over its reuse updates
-            self.pi_new, self.v_new = f(T * B * A), f(T * B)
+        if reuse:                     # sample reuse: a call's sums over its reuse updates
             self.reuse_stats_i, self.reuse_stats_f = i(2), f(2)   # (clipped, counted) rows; (sum rho - 1 - ln rho, sum |rho - 1|)
             self.reuse_loss_sum = f(8)
         if self.explore_beta > 0:     # exploration bonus
             self._prepare_explore(T * B, dev)
         if self.normalize_advantages:  # advantage normalisation: a group's rows; (sum of means, of stds, groups)
             self.adv_norm, self.adv_stats = f(T * B), f(3)
+        self.mb = None
+        if M > 1:                     # minibatched reuse epochs: the twin of the state above for ONE block
+            Bm = B // M
+            mb = self.mb = PassState()
+            mb.local_network, mb.block = self.local_network, None
+            self._alloc_pass(mb, Bm, True)
+            # the block's rows of the rollout, compacted by unreal_minibatch_gather: behaviour policy, actions, the policy
+            # loss's advantages (normalised over the WHOLE rollout when normalisation is on), returns, active flags
+            mb.pi, mb.actions, mb.adv, mb.R, mb.active_log = f(T * Bm * A), i(T * Bm), f(T * Bm), f(T * Bm), i(T * Bm)
+            mb.adv_norm = mb.adv
+            mb.losses = self.losses
+            if self.use_depth_prediction:
+                mb.dp_hits = self.dp_hits
+            mb.reuse_stats_i, mb.reuse_stats_f = self.reuse_stats_i, self.reuse_stats_f
         self._fill_calls = 0
         self._full = False
         self._group_views = []
@@ -392,8 +403,76 @@ class Trainer(object):
             b0, b1 = g * self.Bg, (g + 1) * self.Bg
             env = self.full_environment if self.groups == 1 else self.full_environment.view(b0, b1)
             self._group_views.append((env, self.full_lstm_c[b0 * 256:b1 * 256], self.full_lstm_h[b0 * 256:b1 * 256], b0))
+        self._block_views = None
+        if self.reuse_minibatches > 1:
+            # per block of every group: the block's actors as a ring of their own (the replay branches sample it, indices
+            # relative to the view) and the first actor's column of this rank's draws
+            Bm = self.Bg // self.reuse_minibatches
+            self._block_views = [[(ops.ring_view(env.ring, m * Bm, (m + 1) * Bm), b0 + m * Bm)
+                                  for m in range(self.reuse_minibatches)] for env, _, _, b0 in self._group_views]
         self._select_group(0)
         self._rollout_split_setup()
+
+    def _alloc_pass(self, c, B, reuse):
+        """The workspaces and buffers of the loss branches of one update over B actors, as attributes of `c`: the trainer
+        itself for a group, or the minibatch twin for a block.  `reuse`: with the re-evaluated heads."""
+        A, dev = self.action_size, self.device
+        T, Ta = self.n_step_TD, self.local_t_max
+        c.Bg = B
+        c.grad_scale = 1.0 / float(B * self.world_size)
+        lstm = self.use_lstm
+        aux = self.use_pixel_change or self.use_value_replay
+        xld = self.local_network.xld
+        wkw = self.local_network.ws_kw                # conv activation sizes of the network's frame size
+        c.base_ws = PathWS(T * B, B, dev, save_c1=True, lstm=lstm, xld=xld, **wkw)
+        c.boot_ws = PathWS(B, B, dev, save_c1=False, lstm=lstm, xld=xld, **wkw)
+        c.rp_ws = PathWS(3 * B, B, dev, save_c1=True, lstm=False, xld=xld, **wkw) if self.use_reward_prediction else None
+        # pixel control and value replay as ONE batch of 2B replayed sequences (actor 2b = pc sample of b, 2b + 1 = vr
+        # sample): see _train_aux_batched.  Decided HERE, once (the class default is read at prepare() time only).
+        c.batch_aux = bool(self.batch_aux_default and self.use_pixel_change and self.use_value_replay)
+        # per-branch workspaces (_train_pc / _train_vr: one of the two tasks on, or batch_aux off) are allocated on first
+        # use: with the batched pass they would be ~5 GB of dead HBM per rank at 4096 actors
+        c._aux_ws = None
+        c._aux_ws_args = (Ta * B, B, dev, lstm, xld) if aux else None
+        per_branch = aux and not c.batch_aux
+        rows = max(T, Ta if per_branch else 0, 3 if self.use_reward_prediction else 0) * B
+        c.gws = GradWS(rows, B, dev, lstm=lstm, pc=self.use_pixel_change and per_branch, A=A, f2_dim=wkw["f2_dim"])
+        if c.batch_aux:
+            c.aux2_ws = PathWS(Ta * 2 * B, 2 * B, dev, save_c1=True, lstm=lstm, xld=xld, **wkw)
+            c.boot2_ws = PathWS(2 * B, 2 * B, dev, save_c1=False, lstm=lstm, xld=xld, **wkw)
+            c.gws2 = GradWS(Ta * 2 * B, 2 * B, dev, lstm=lstm, pc=True, A=A, pc_rows=Ta * B, f2_dim=wkw["f2_dim"])
+        f = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
+        i = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+        d = lambda n: torch.zeros(n, dtype=torch.float64, device=dev)
+        c.dlogits, c.dv = f(max(T, Ta) * B * A), f(max(T, Ta) * B)
+        if self.use_depth_prediction:
+            from ..model.model import DEPTH_HIDDEN, DEPTH_OUT
+            c.dp_hidden, c.dp_d_hidden = f(T * B * DEPTH_HIDDEN), f(T * B * DEPTH_HIDDEN)
+            c.dp_logits, c.dp_dlogits = f(T * B * DEPTH_OUT), f(T * B * DEPTH_OUT)
+        if aux:
+            L = Ta + 1
+            c.seq_idx, c.seq_len, c.seq_start = i(L * B), i(B), i(B)
+            c.seq_mask, c.seq_act = i(Ta * B), i(Ta * B)
+            c.aux_v, c.aux_R, c.aux_boot_v = f(Ta * B), f(Ta * B), f(B)
+            if self.use_pixel_change:
+                c.boot_hp, c.boot_qmax = f(B * ops.F2_DIM), f(B * ops.PC_CELLS)
+        if self.use_reward_prediction:
+            c.rp_coin, c.rp_u, c.rp_class = i(B), d(B), i(B)
+            c.rp_logits, c.rp_dlogits = f(B * 3), f(B * 3)
+        if c.batch_aux:
+            L = Ta + 1
+            c.seq_idx_cat = i(2 * L * B)
+            c.seq_idx2 = [c.seq_idx_cat[:L * B], c.seq_idx_cat[L * B:]]
+            c.seq_len2, c.seq_start2 = [i(B), i(B)], [i(B), i(B)]
+            c.seq_mask2 = [i(Ta * B), i(Ta * B)]
+            c.last2 = i(2 * B)
+            r = torch.arange(Ta * B, dtype=torch.int32)
+            c.map_seq = torch.stack([r, r + L * B], dim=1).reshape(-1).contiguous().to(dev)      # [2r + s] = s*L*B + r
+            b = torch.arange(B, dtype=torch.int32)
+            c.map_boot = torch.stack([b, b + B], dim=1).reshape(-1).contiguous().to(dev)          # [2b + s] = s*B + b
+            c.aux_dv = f(Ta * B)
+        if reuse:                     # sample reuse (DESIGN §7q): the re-evaluated heads
+            c.pi_new, c.v_new = f(T * B * A), f(T * B)
 
     def _prepare_explore(self, rows, dev):
         """The exploration bonus's buffers: the hash's multipliers, ONE count table for this trainer (its
@@ -441,22 +520,18 @@ class Trainer(object):
                         self.active_log, ws.frame_idx, self.explore_bonus, self.rewards_total, ring.r_bonus,
                         self.explore_stats_i, self.explore_stats_f)
 
-    @property
-    def aux_ws(self):
-        """Workspace of the one-branch-at-a-time replay schedule (lazy: see prepare())."""
-        if self._aux_ws is None and self._aux_ws_args is not None:
-            rows, B, dev, lstm, xld = self._aux_ws_args
-            self._aux_ws = PathWS(rows, B, dev, save_c1=True, lstm=lstm, xld=xld, **self.local_network.ws_kw)
-            self.gws.ensure_rows(rows, B, dev)
-        return self._aux_ws
-
     def _select_group(self, g):
         """Point the pipeline at the actors [g*Bg, (g+1)*Bg): environment / ring views, carried LSTM state, draws."""
         env, c, h, b0 = self._group_views[g]
         self.group = g
         self.environment, self.ring, self.lstm_c, self.lstm_h = env, env.ring, c, h
+        self.base_ring = env.ring                    # (PassState: a group's base rows and replay samples share its ring)
+        self._point_draws(self.Bg, b0)
+
+    def _point_draws(self, batch, b0):
+        """The trainer's own draws serve `batch` actors from actor b0 of this rank on."""
         if self._own_draws:
-            self.draws.batch = self.Bg
+            self.draws.batch = batch
             self.draws.col0 = self.rank * self.B + b0
 
     def stop(self):
@@ -728,205 +803,215 @@ class Trainer(object):
         if self.normalize_advantages:          # after GAE and the bonus have shaped self.adv, which stays raw
             ops.adv_normalize(T * B, self.adv, self.active_log, self.adv_norm_eps, self.adv_norm, self.adv_stats)
 
-    def _train_base(self, reuse=False):
+    def _train_base(self, reuse=False, c=None):
         """Loss and backward of the rollout's rows.  `reuse`: the rows have been re-evaluated with the current weights
-        (reuse_gradients): heads, clipped-surrogate loss against the rollout's policy self.pi and gradient in one launch."""
-        B, T, A, ws, net, g, p = self.Bg, self.n_step_TD, self.action_size, self.base_ws, self.local_network, \
+        (reuse_gradients): heads, clipped-surrogate loss against the rollout's policy c.pi and gradient in one launch.
+        `c`: the pass state holding the rows (the trainer's own by default; the minibatch twin: one block's rows)."""
+        c = self if c is None else c
+        B, T, A, ws, net, g, p = c.Bg, self.n_step_TD, self.action_size, c.base_ws, self.local_network, \
             self.local_network.g, self.local_network.p
         rows = T * B
         feat, ld = net.features(ws)
-        adv = self.adv_norm if self.normalize_advantages else self.adv      # the policy loss's advantages (DESIGN §7s)
+        adv = c.adv_norm if self.normalize_advantages else c.adv      # the policy loss's advantages (DESIGN §7s)
         if reuse:
             ops.ppo_heads_loss_grad(rows, A, feat, ld, p["W_base_fc_p"], p["b_base_fc_p"], p["W_base_fc_v"],
-                                    p["b_base_fc_v"], self.pi, A, self.actions, adv, self.R, self.active_log,
-                                    self.ppo_clip, self.entropy_beta, self.grad_scale, self.pi_new, self.v_new,
-                                    self.dlogits, self.dv, self.losses[0:3], self.reuse_stats_i, self.reuse_stats_f)
+                                    p["b_base_fc_v"], c.pi, A, c.actions, adv, c.R, c.active_log,
+                                    self.ppo_clip, self.entropy_beta, c.grad_scale, c.pi_new, c.v_new,
+                                    c.dlogits, c.dv, c.losses[0:3], c.reuse_stats_i, c.reuse_stats_f)
         else:
-            ops.base_loss_grad(rows, A, self.pi, A, self.v, self.actions, adv, self.R, self.active_log,
-                               self.entropy_beta, self.grad_scale, self.dlogits, self.dv, self.losses[0:3])
-        d_feat = self.gws.d_feat
-        ops.linear_small_bwd(rows, 256, A, feat, ld, self.dlogits, A, p["W_base_fc_p"], d_feat, 256, False,
+            ops.base_loss_grad(rows, A, c.pi, A, c.v, c.actions, adv, c.R, c.active_log,
+                               self.entropy_beta, c.grad_scale, c.dlogits, c.dv, c.losses[0:3])
+        d_feat = c.gws.d_feat
+        ops.linear_small_bwd(rows, 256, A, feat, ld, c.dlogits, A, p["W_base_fc_p"], d_feat, 256, False,
                              g["W_base_fc_p"], g["b_base_fc_p"])
-        ops.linear_small_bwd(rows, 256, 1, feat, ld, self.dv, 1, p["W_base_fc_v"], d_feat, 256, True,
+        ops.linear_small_bwd(rows, 256, 1, feat, ld, c.dv, 1, p["W_base_fc_v"], d_feat, 256, True,
                              g["W_base_fc_v"], g["b_base_fc_v"])
         if self.use_depth_prediction:
-            self._train_depth(rows, feat, ld, d_feat)
-        net.trunk_backward(self.ring, ws, self.gws, T, B, d_feat, h0_nonzero=True)
+            self._train_depth(rows, feat, ld, d_feat, c)
+        net.trunk_backward(c.base_ring, ws, c.gws, T, B, d_feat, h0_nonzero=True)
 
-    def _train_depth(self, rows, feat, ld, d_feat):
+    def _train_depth(self, rows, feat, ld, d_feat, c=None):
         """[Depth prediction] on the rollout's rows: head forward, cross-entropy against the ring's labels of
         the frames the encoder read, head backward; the head's share of d(loss)/d(feat) is added into d_feat."""
         from ..model.model import DEPTH_OUT
-        net, ws = self.local_network, self.base_ws
-        net.depth_head_forward(rows, feat, ld, self.dp_hidden, self.dp_logits)
-        ops.depth_loss_grad(rows, self.dp_logits, DEPTH_OUT, self.ring.r_depth, ws.frame_idx, self.active_log,
-                            self.depth_lambda * self.grad_scale, self.dp_dlogits, self.losses[6:7], self.dp_hits)
-        net.depth_head_backward(rows, feat, ld, self.dp_hidden, self.dp_dlogits, self.dp_d_hidden, d_feat, 256)
+        c = self if c is None else c
+        net, ws = self.local_network, c.base_ws
+        net.depth_head_forward(rows, feat, ld, c.dp_hidden, c.dp_logits)
+        ops.depth_loss_grad(rows, c.dp_logits, DEPTH_OUT, c.base_ring.r_depth, ws.frame_idx, c.active_log,
+                            self.depth_lambda * c.grad_scale, c.dp_dlogits, c.losses[6:7], c.dp_hits)
+        net.depth_head_backward(rows, feat, ld, c.dp_hidden, c.dp_dlogits, c.dp_d_hidden, d_feat, 256)
 
-    def _sample_sequence(self):
+    def _sample_sequence(self, c=None):
         """experience.sample_sequence(local_t_max+1) for every actor + the bootstrap frame's features."""
-        B, Ta, net = self.Bg, self.local_t_max, self.local_network
+        c = self if c is None else c
+        B, Ta, net = c.Bg, self.local_t_max, self.local_network
         L = Ta + 1
-        self.draws.randint(self.experience_history_size - L - 1, self.seq_start)
-        ops.replay_sample_seq(self.ring, L, self.seq_start, self.seq_idx, self.seq_len)
-        bw = self.boot_ws
-        ops.seq_last_idx(B, self.seq_idx, self.seq_len, bw.frame_idx[:B])
+        self.draws.randint(self.experience_history_size - L - 1, c.seq_start)
+        ops.replay_sample_seq(c.ring, L, c.seq_start, c.seq_idx, c.seq_len)
+        bw = c.boot_ws
+        ops.seq_last_idx(B, c.seq_idx, c.seq_len, bw.frame_idx[:B])
         if self.use_lstm:
             bw.c0.zero_()                      # aux networks always start from the zero state (model.py:395,461)
             bw.h0.zero_()
-        feat, ld = net.trunk_forward(self.ring, bw, 1, B, lar_from_ring=True, save_c1=False)
+        feat, ld = net.trunk_forward(c.ring, bw, 1, B, lar_from_ring=True, save_c1=False)
         return feat, ld
 
-    def _aux_forward(self):
-        B, Ta, net, ws = self.Bg, self.local_t_max, self.local_network, self.aux_ws
+    def _aux_forward(self, c=None):
+        c = self if c is None else c
+        B, Ta, net, ws = c.Bg, self.local_t_max, self.local_network, c.aux_ws
         rows = Ta * B
-        ops.copy_(ws.frame_idx[:rows], self.seq_idx[:rows])
+        ops.copy_(ws.frame_idx[:rows], c.seq_idx[:rows])
         if self.use_lstm:
             ws.c0.zero_()
             ws.h0.zero_()
-        ops.seq_mask(B, Ta, self.seq_len, self.seq_mask)
-        return net.trunk_forward(self.ring, ws, Ta, B, lar_from_ring=True, save_c1=True)
+        ops.seq_mask(B, Ta, c.seq_len, c.seq_mask)
+        return net.trunk_forward(c.ring, ws, Ta, B, lar_from_ring=True, save_c1=True)
 
     # Pixel-control head, training pass: loss + backward of the two deconvolutions in ONE launch (unreal_pc_deconv_train:
     # d_dec stays on chip, hp is staged once; 22 KB of HBM traffic per frame instead of 49).  False: the two-launch form.
     fuse_pc_deconv = True
     keep_d_dec = False       # True: the one-launch form also writes d_dec to gws.d_dec (the full-size tests read it)
 
-    def _pc_deconv_loss_backward(self, gws, rows, mask, d_hp, s_hp):
-        """gws.hp (relu(pc_fc1), max in slot s_hp), self.seq_act, gws.pc_R -> losses[3], d_hp, the deconv parameter
+    def _pc_deconv_loss_backward(self, gws, rows, mask, d_hp, s_hp, c=None):
+        """gws.hp (relu(pc_fc1), max in slot s_hp), c.seq_act, gws.pc_R -> losses[3], d_hp, the deconv parameter
         gradients; returns the slot holding max |d_hp| (model.py:411-443, 542-557 and their gradients)."""
+        c = self if c is None else c
         A, net = self.action_size, self.local_network
         p, g = net.p, net.g
         s_dhp = net.new_slot()             # max |d_hp|: committed by the deconv backward, read by the pc_fc1 dgrad
         if self.fuse_pc_deconv:
             ops.pc_deconv_train(rows, A, gws.hp, p["W_pc_deconv_v"], p["b_pc_deconv_v"], p["W_pc_deconv_a"], p["b_pc_deconv_a"],
-                                self.seq_act, gws.pc_R, mask, self.pixel_change_lambda, self.grad_scale, self.losses[3:4], d_hp,
+                                c.seq_act, gws.pc_R, mask, self.pixel_change_lambda, c.grad_scale, c.losses[3:4], d_hp,
                                 g["W_pc_deconv_v"], g["b_pc_deconv_v"], g["W_pc_deconv_a"], g["b_pc_deconv_a"], dhp_max=s_dhp,
                                 hp_max=s_hp, d_dec=gws.ensure_d_dec(rows, A) if self.keep_d_dec else None)
             return s_dhp
         s_dd = net.new_slot()              # bound of max |d_dec|: committed by the deconv forward
         d_dec = gws.ensure_d_dec(rows, A)
         ops.pc_deconv_fwd(rows, A, gws.hp, p["W_pc_deconv_v"], p["b_pc_deconv_v"], p["W_pc_deconv_a"],
-                          p["b_pc_deconv_a"], action=self.seq_act, target=gws.pc_R, mask=mask,
-                          lam=self.pixel_change_lambda, grad_scale=self.grad_scale, d_dec=d_dec,
-                          loss=self.losses[3:4], hp_max=s_hp, ddec_max=s_dd)
+                          p["b_pc_deconv_a"], action=c.seq_act, target=gws.pc_R, mask=mask,
+                          lam=self.pixel_change_lambda, grad_scale=c.grad_scale, d_dec=d_dec,
+                          loss=c.losses[3:4], hp_max=s_hp, ddec_max=s_dd)
         ops.pc_deconv_bwd(rows, A, gws.hp, d_dec, p["W_pc_deconv_v"], p["W_pc_deconv_a"], d_hp,
                           g["W_pc_deconv_v"], g["b_pc_deconv_v"], g["W_pc_deconv_a"], g["b_pc_deconv_a"], dhp_max=s_dhp,
                           hp_max=s_hp, ddec_max=s_dd)
         return s_dhp
 
-    def _train_pc(self):
+    def _train_pc(self, c=None):
         """[Pixel change] (trainer.py:339-380, model.py:411-443, 542-557)."""
-        B, Ta, A, net = self.Bg, self.local_t_max, self.action_size, self.local_network
-        p, g, gws = net.p, net.g, self.gws
+        c = self if c is None else c
+        B, Ta, A, net = c.Bg, self.local_t_max, self.action_size, self.local_network
+        p, g, gws = net.p, net.g, c.gws
         rows = Ta * B
-        ws = self.aux_ws                              # (allocates the per-branch workspace on first use)
+        ws = c.aux_ws                              # (allocates the per-branch workspace on first use)
         gws.ensure_pc(rows, A)
-        feat, ld = self._sample_sequence()
+        feat, ld = self._sample_sequence(c)
         s_bhp = net.new_slot()             # max of the bootstrap frames' hp: committed by the pc_fc1 GEMM
-        net.pc_head_forward(B, feat, ld, self.boot_hp, ws=self.boot_ws, hp_max=s_bhp)
-        ops.pc_deconv_fwd(B, A, self.boot_hp, p["W_pc_deconv_v"], p["b_pc_deconv_v"], p["W_pc_deconv_a"],
-                          p["b_pc_deconv_a"], qmax=self.boot_qmax, hp_max=s_bhp)
-        ops.pc_returns(self.ring, Ta + 1, self.seq_idx, self.seq_len, self.boot_qmax, self.gamma_pc, gws.pc_R)
-        feat, ld = self._aux_forward()
+        net.pc_head_forward(B, feat, ld, c.boot_hp, ws=c.boot_ws, hp_max=s_bhp)
+        ops.pc_deconv_fwd(B, A, c.boot_hp, p["W_pc_deconv_v"], p["b_pc_deconv_v"], p["W_pc_deconv_a"],
+                          p["b_pc_deconv_a"], qmax=c.boot_qmax, hp_max=s_bhp)
+        ops.pc_returns(c.ring, Ta + 1, c.seq_idx, c.seq_len, c.boot_qmax, self.gamma_pc, gws.pc_R)
+        feat, ld = self._aux_forward(c)
         s_hp = net.new_slot()              # max hp: committed by the pc_fc1 GEMM
-        net.pc_head_forward(rows, feat, ld, gws.hp, ws=self.aux_ws, hp_max=s_hp)
-        ops.gather_i32(self.ring.r_action, self.aux_ws.frame_idx[:rows], self.seq_act)
+        net.pc_head_forward(rows, feat, ld, gws.hp, ws=c.aux_ws, hp_max=s_hp)
+        ops.gather_i32(c.ring.r_action, c.aux_ws.frame_idx[:rows], c.seq_act)
         d_hp = gws.d_f2
-        s_dhp = self._pc_deconv_loss_backward(gws, rows, self.seq_mask, d_hp, s_hp)
+        s_dhp = self._pc_deconv_loss_backward(gws, rows, c.seq_mask, d_hp, s_hp, c)
         from ..model.model import _splitk
         ops.gemm_split_tn(256, 2592, rows, feat, ld, d_hp, 2592, g["W_pc_fc1"], 2592,
                               splitk=_splitk(256, 2592, rows), colsum=g["b_pc_fc1"],
-                              a_max=net._one if self.use_lstm else self.aux_ws.s_x, b_max=s_dhp)
+                              a_max=net._one if self.use_lstm else c.aux_ws.s_x, b_max=s_dhp)
         ops.gemm_split_nt(rows, 256, 2592, d_hp, 2592, net.shadow["pc_fc1_dgrad"], gws.d_feat, 256, a_max=s_dhp)
-        net.trunk_backward(self.ring, self.aux_ws, gws, Ta, B, gws.d_feat)
+        net.trunk_backward(c.ring, c.aux_ws, gws, Ta, B, gws.d_feat)
 
-    def _train_vr(self):
+    def _train_vr(self, c=None):
         """[Value replay] (trainer.py:383-412, model.py:446-470, 559-566)."""
-        B, Ta, net = self.Bg, self.local_t_max, self.local_network
-        p, g, gws = net.p, net.g, self.gws
+        c = self if c is None else c
+        B, Ta, net = c.Bg, self.local_t_max, self.local_network
+        p, g, gws = net.p, net.g, c.gws
         rows = Ta * B
-        ws = self.aux_ws                              # (allocates the per-branch workspace on first use)
-        feat, ld = self._sample_sequence()
-        net.value_forward(B, feat, ld, self.aux_boot_v)
-        ops.vr_returns(self.ring, Ta + 1, self.seq_idx, self.seq_len, self.aux_boot_v, self.gamma, self.aux_R, bonus=True)
-        feat, ld = self._aux_forward()
-        net.value_forward(rows, feat, ld, self.aux_v)
-        ops.vr_loss_grad(rows, self.aux_v, self.aux_R, self.seq_mask, self.grad_scale, self.dv, self.losses[4:5])
-        ops.linear_small_bwd(rows, 256, 1, feat, ld, self.dv, 1, p["W_base_fc_v"], gws.d_feat, 256, False,
+        ws = c.aux_ws                              # (allocates the per-branch workspace on first use)
+        feat, ld = self._sample_sequence(c)
+        net.value_forward(B, feat, ld, c.aux_boot_v)
+        ops.vr_returns(c.ring, Ta + 1, c.seq_idx, c.seq_len, c.aux_boot_v, self.gamma, c.aux_R, bonus=True)
+        feat, ld = self._aux_forward(c)
+        net.value_forward(rows, feat, ld, c.aux_v)
+        ops.vr_loss_grad(rows, c.aux_v, c.aux_R, c.seq_mask, c.grad_scale, c.dv, c.losses[4:5])
+        ops.linear_small_bwd(rows, 256, 1, feat, ld, c.dv, 1, p["W_base_fc_v"], gws.d_feat, 256, False,
                              g["W_base_fc_v"], g["b_base_fc_v"])
-        net.trunk_backward(self.ring, self.aux_ws, gws, Ta, B, gws.d_feat)
+        net.trunk_backward(c.ring, c.aux_ws, gws, Ta, B, gws.d_feat)
 
     batch_aux_default = True       # class default, read by prepare() only (A/B tools build a second Trainer with it off)
 
-    def _train_aux_batched(self):
+    def _train_aux_batched(self, c=None):
         """[Pixel change] + [Value replay] (trainer.py:339-412) as ONE trunk pass over 2B replayed sequences: sequence
         2b is actor b's pixel-control sample, 2b + 1 its value-replay sample, so a branch's rows are every other row of the
         workspace (leading dimension doubled) and every trunk kernel -- encoder, fc, the T recurrent steps, their
         backward -- runs once at twice the rows instead of twice.  Draws, sampling, targets, heads and losses are the
         per-branch ones, in the reference's order (pc, vr)."""
-        B, Ta, A, net = self.Bg, self.local_t_max, self.action_size, self.local_network
-        p, g, gws, sh = net.p, net.g, self.gws2, net.shadow
+        c = self if c is None else c
+        B, Ta, A, net = c.Bg, self.local_t_max, self.action_size, self.local_network
+        p, g, gws, sh = net.p, net.g, c.gws2, net.shadow
         L, rows = Ta + 1, Ta * B
         for s in (0, 1):                                         # experience.sample_sequence(local_t_max + 1), pc then vr
-            self.draws.randint(self.experience_history_size - L - 1, self.seq_start2[s])
-            ops.replay_sample_seq(self.ring, L, self.seq_start2[s], self.seq_idx2[s], self.seq_len2[s])
-            ops.seq_last_idx(B, self.seq_idx2[s], self.seq_len2[s], self.last2[s * B:(s + 1) * B])
-            ops.seq_mask(B, Ta, self.seq_len2[s], self.seq_mask2[s])
+            self.draws.randint(self.experience_history_size - L - 1, c.seq_start2[s])
+            ops.replay_sample_seq(c.ring, L, c.seq_start2[s], c.seq_idx2[s], c.seq_len2[s])
+            ops.seq_last_idx(B, c.seq_idx2[s], c.seq_len2[s], c.last2[s * B:(s + 1) * B])
+            ops.seq_mask(B, Ta, c.seq_len2[s], c.seq_mask2[s])
         # bootstrap frames of both samples (zero LSTM state, model.py:395,461)
-        bw = self.boot2_ws
-        ops.gather_i32(self.last2, self.map_boot, bw.frame_idx[:2 * B])
+        bw = c.boot2_ws
+        ops.gather_i32(c.last2, c.map_boot, bw.frame_idx[:2 * B])
         # (boot2_ws / aux2_ws belong to this pass alone and nothing ever writes their c0 / h0: they are the zero state they
         # were allocated as -- model.py:395,461 -- so the four fills per pass the per-branch schedule needs are not issued)
-        feat, ld = net.trunk_forward(self.ring, bw, 1, 2 * B, lar_from_ring=True, save_c1=False)
+        feat, ld = net.trunk_forward(c.ring, bw, 1, 2 * B, lar_from_ring=True, save_c1=False)
         s_bhp = net.new_slot()             # max of the bootstrap frames' hp: committed by the pc_fc1 GEMM
-        net.pc_head_forward(B, feat, 2 * ld, self.boot_hp, ws=self.boot2_ws, hp_max=s_bhp)
-        ops.pc_deconv_fwd(B, A, self.boot_hp, p["W_pc_deconv_v"], p["b_pc_deconv_v"], p["W_pc_deconv_a"],
-                          p["b_pc_deconv_a"], qmax=self.boot_qmax, hp_max=s_bhp)
-        ops.pc_returns(self.ring, L, self.seq_idx2[0], self.seq_len2[0], self.boot_qmax, self.gamma_pc, gws.pc_R)
-        net.value_forward(B, feat[ld:], 2 * ld, self.aux_boot_v)
-        ops.vr_returns(self.ring, L, self.seq_idx2[1], self.seq_len2[1], self.aux_boot_v, self.gamma, self.aux_R,
+        net.pc_head_forward(B, feat, 2 * ld, c.boot_hp, ws=c.boot2_ws, hp_max=s_bhp)
+        ops.pc_deconv_fwd(B, A, c.boot_hp, p["W_pc_deconv_v"], p["b_pc_deconv_v"], p["W_pc_deconv_a"],
+                          p["b_pc_deconv_a"], qmax=c.boot_qmax, hp_max=s_bhp)
+        ops.pc_returns(c.ring, L, c.seq_idx2[0], c.seq_len2[0], c.boot_qmax, self.gamma_pc, gws.pc_R)
+        net.value_forward(B, feat[ld:], 2 * ld, c.aux_boot_v)
+        ops.vr_returns(c.ring, L, c.seq_idx2[1], c.seq_len2[1], c.aux_boot_v, self.gamma, c.aux_R,
                        bonus=True)
         # the 2B sequences through the trunk
-        ws = self.aux2_ws
-        ops.gather_i32(self.seq_idx_cat, self.map_seq, ws.frame_idx[:2 * rows])
-        feat, ld = net.trunk_forward(self.ring, ws, Ta, 2 * B, lar_from_ring=True, save_c1=True)
+        ws = c.aux2_ws
+        ops.gather_i32(c.seq_idx_cat, c.map_seq, ws.frame_idx[:2 * rows])
+        feat, ld = net.trunk_forward(c.ring, ws, Ta, 2 * B, lar_from_ring=True, save_c1=True)
         d_feat = gws.d_feat
         # pixel-control head on the even rows
         s_hp = net.new_slot()              # max hp: committed by the pc_fc1 GEMM
-        net.pc_head_forward(rows, feat, 2 * ld, gws.hp, ws=self.aux2_ws, hp_max=s_hp)
-        ops.gather_i32(self.ring.r_action, self.seq_idx2[0][:rows], self.seq_act)
+        net.pc_head_forward(rows, feat, 2 * ld, gws.hp, ws=c.aux2_ws, hp_max=s_hp)
+        ops.gather_i32(c.ring.r_action, c.seq_idx2[0][:rows], c.seq_act)
         d_hp = gws.d_hp
-        s_dhp = self._pc_deconv_loss_backward(gws, rows, self.seq_mask2[0], d_hp, s_hp)
+        s_dhp = self._pc_deconv_loss_backward(gws, rows, c.seq_mask2[0], d_hp, s_hp, c)
         from ..model.model import _splitk
         ops.gemm_split_tn(256, 2592, rows, feat, 2 * ld, d_hp, 2592, g["W_pc_fc1"], 2592,
                           splitk=_splitk(256, 2592, rows), colsum=g["b_pc_fc1"],
-                          a_max=net._one if self.use_lstm else self.aux2_ws.s_x, b_max=s_dhp)
+                          a_max=net._one if self.use_lstm else c.aux2_ws.s_x, b_max=s_dhp)
         ops.gemm_split_nt(rows, 256, 2592, d_hp, 2592, sh["pc_fc1_dgrad"], d_feat, 2 * 256, a_max=s_dhp)
         # value head on the odd rows
-        net.value_forward(rows, feat[ld:], 2 * ld, self.aux_v)
-        ops.vr_loss_grad(rows, self.aux_v, self.aux_R, self.seq_mask2[1], self.grad_scale, self.aux_dv, self.losses[4:5])
-        ops.linear_small_bwd(rows, 256, 1, feat[ld:], 2 * ld, self.aux_dv, 1, p["W_base_fc_v"], d_feat[256:], 2 * 256, False,
+        net.value_forward(rows, feat[ld:], 2 * ld, c.aux_v)
+        ops.vr_loss_grad(rows, c.aux_v, c.aux_R, c.seq_mask2[1], c.grad_scale, c.aux_dv, c.losses[4:5])
+        ops.linear_small_bwd(rows, 256, 1, feat[ld:], 2 * ld, c.aux_dv, 1, p["W_base_fc_v"], d_feat[256:], 2 * 256, False,
                              g["W_base_fc_v"], g["b_base_fc_v"])
-        net.trunk_backward(self.ring, ws, gws, Ta, 2 * B, d_feat)
+        net.trunk_backward(c.ring, ws, gws, Ta, 2 * B, d_feat)
 
-    def _train_rp(self):
+    def _train_rp(self, c=None):
         """[Reward prediction] (trainer.py:415-436, model.py:473-488, 569-576)."""
-        B, net, ws = self.Bg, self.local_network, self.rp_ws
-        p, g, gws = net.p, net.g, self.gws
-        self.draws.randint(2, self.rp_coin)
-        self.draws.uniform(self.rp_u)
-        ops.replay_sample_rp(self.ring, self.rp_coin, self.rp_u, ws.frame_idx[:3 * B], self.rp_class, self.rp_mode)
+        c = self if c is None else c
+        B, net, ws = c.Bg, self.local_network, c.rp_ws
+        p, g, gws = net.p, net.g, c.gws
+        self.draws.randint(2, c.rp_coin)
+        self.draws.uniform(c.rp_u)
+        ops.replay_sample_rp(c.ring, c.rp_coin, c.rp_u, ws.frame_idx[:3 * B], c.rp_class, self.rp_mode)
         s_c1 = net.new_slot()              # max of the conv1 activation: the c1 scale of the conv backward below
         F = net.F                          # 2592 at 84 x 84; the rp fc is [3F, 3] (model.py:480-484)
-        net.encoder_forward(self.ring, ws.frame_idx[:3 * B], ws.f2, ws.c1, c1_max=s_c1, ws=ws)
-        ops.linear_small_fwd(B, 3 * F, 3, ws.f2, 3 * F, p["W_rp_fc1"], p["b_rp_fc1"], self.rp_logits, 3)
-        ops.rp_loss_grad(B, self.rp_logits, self.rp_class, self.grad_scale, None, self.rp_dlogits,
-                         self.losses[5:6])
-        ops.linear_small_bwd(B, 3 * F, 3, ws.f2, 3 * F, self.rp_dlogits, 3, p["W_rp_fc1"], gws.d_f2, 3 * F, False,
+        net.encoder_forward(c.ring, ws.frame_idx[:3 * B], ws.f2, ws.c1, c1_max=s_c1, ws=ws)
+        ops.linear_small_fwd(B, 3 * F, 3, ws.f2, 3 * F, p["W_rp_fc1"], p["b_rp_fc1"], c.rp_logits, 3)
+        ops.rp_loss_grad(B, c.rp_logits, c.rp_class, c.grad_scale, None, c.rp_dlogits,
+                         c.losses[5:6])
+        ops.linear_small_bwd(B, 3 * F, 3, ws.f2, 3 * F, c.rp_dlogits, 3, p["W_rp_fc1"], gws.d_f2, 3 * F, False,
                              g["W_rp_fc1"], g["b_rp_fc1"])
         ops.relu_mask(3 * B, F, gws.d_f2, F, ws.f2, F)
-        net.encoder_backward(self.ring, ws.frame_idx[:3 * B], ws.c1, gws.d_f2,
+        net.encoder_backward(c.ring, ws.frame_idx[:3 * B], ws.c1, gws.d_f2,
                              c1_max=s_c1)      # (d_f2's maximum: reduced by the wrapper, 127 MB at 4096 actors)
 
     # ---------------------------------------------------------------------------------------------------
@@ -936,24 +1021,62 @@ class Trainer(object):
         net.refresh_shadows()                  # fp16x2 weight planes follow the last optimiser step / load
         net.begin_pass()                       # absmax slots of this pass (fp16x2 GEMM scales)
         self._rollout()
-        net.grads.flat.zero_()
-        self.losses.zero_()
         if self.use_depth_prediction and self.group == 0:
             self.dp_hits.zero_()
+        if self.reuse_minibatches > 1:         # the rollout only: its updates are minibatch_gradients()' 
+            return
+        net.grads.flat.zero_()
+        self.losses.zero_()
         self._train_base()
         self._train_aux()
 
-    def _train_aux(self):
-        """The auxiliary branches of one update, each with fresh draws, in the reference's order (pc, vr, rp)."""
-        if self.batch_aux:
-            self._train_aux_batched()
+    def minibatch_gradients(self, m):
+        """The gradient of one minibatch update: §7q's reuse pass on block m of the selected group, the actors
+        [m Bm, (m + 1) Bm) of the rollout compute_gradients() has just made.  One launch compacts the block's rows into the
+        twin's buffers (self.mb); the trunk is re-run on them with the current weights from the block's start state, the
+        clipped-surrogate loss reads the rollout's policy, actions, returns and advantages (normalised over the whole
+        rollout when normalisation is on), and the auxiliary branches sample the block's own replay with fresh draws for Bm
+        actors.  grad_scale is 1 / (Bm world_size).  base_ws, boot_ws, self.pi / v / adv / R and the carried LSTM state are
+        only read."""
+        M = self.reuse_minibatches
+        if M < 2:
+            raise ValueError("minibatch_gradients needs Trainer(reuse_minibatches > 1): its buffers are not allocated")
+        if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m < M:
+            raise ValueError("minibatch_gradients: block %r outside 0..%d" % (m, M - 1))
+        net, mb, src = self.local_network, self.mb, self.base_ws
+        T, A, Bg, Bm = self.n_step_TD, self.action_size, self.Bg, self.mb.Bg
+        mb.ring, b0 = self._block_views[self.group][m]
+        mb.base_ring, mb.block = self.ring, m      # the gathered frame indices are relative to the group's ring
+        net.refresh_shadows()
+        net.begin_pass()
+        dst = mb.base_ws
+        lstm = dict(side=A + 1 + self.objective_size, xcat=src.xcat, xcat_out=dst.xcat, c0=src.c0, h0=src.h0,
+                    c0_out=dst.c0, h0_out=dst.h0) if self.use_lstm else {}
+        ops.minibatch_gather(T, Bg, Bm, m * Bm, A, src.frame_idx, self.actions, self.active_log,
+                             self.adv_norm if self.normalize_advantages else self.adv, self.R, self.pi, dst.frame_idx,
+                             mb.actions, mb.active_log, mb.adv, mb.R, mb.pi, ld=src.xld, **lstm)
+        net.trunk_forward(self.ring, dst, T, Bm, lar_from_ring=False, save_c1=True, lar_prefilled=True,
+                          objective_prefilled=True)
+        net.grads.flat.zero_()
+        self.losses.zero_()
+        self._train_base(reuse=True, c=mb)
+        self._point_draws(Bm, b0)                  # fresh draws for the block's Bm actors, at their own columns
+        self._train_aux(mb)
+        self._point_draws(Bg, self._group_views[self.group][3])
+
+    def _train_aux(self, c=None):
+        """The auxiliary branches of one update, each with fresh draws, in the reference's order (pc, vr, rp); `c`: the
+        pass state they run on (the trainer's own by default; the minibatch twin: the block's actors and replay)."""
+        c = self if c is None else c
+        if c.batch_aux:
+            self._train_aux_batched(c)
         else:
             if self.use_pixel_change:
-                self._train_pc()
+                self._train_pc(c)
             if self.use_value_replay:
-                self._train_vr()
+                self._train_vr(c)
         if self.use_reward_prediction:
-            self._train_rp()
+            self._train_rp(c)
 
     def reuse_gradients(self):
         """One more update's gradient from the rollout compute_gradients() has just made, without an
@@ -997,10 +1120,10 @@ class Trainer(object):
         if not self._full:
             self._fill_experience(sess)
             return 0, None
-        G, E = self.groups, self.reuse_epochs
-        if G > 1 or E > 1:
+        G, E, M = self.groups, self.reuse_epochs, self.reuse_minibatches
+        if G > 1 or E > 1 or M > 1:
             self.loss_sum.zero_()
-        if E > 1:
+        if E > 1 or M > 1:
             self.reuse_loss_sum.zero_()
             self.reuse_stats_i.zero_()
             self.reuse_stats_f.zero_()
@@ -1010,14 +1133,17 @@ class Trainer(object):
         if self.normalize_advantages:
             self.adv_stats.zero_()
         # (a group pass is ~300 launches per update: see the dispatch-queue bound below)
-        sync_every = max(1, self.GROUP_SYNC_EVERY // E)
+        sync_every = max(1, self.GROUP_SYNC_EVERY // (E if M == 1 else E * M))
         for g in range(G):                               # G complete actor-learner passes, one after the other
             self._select_group(g)
             # the reference reads global_t when a worker's process() starts (main.py:114-125)
             lr = self._anneal_learning_rate(global_t + g * self.Bg * self.n_step_TD * self.world_size)
             self.compute_gradients()
-            self._apply_update(lr)
-            if E > 1:
+            if M > 1:
+                self._minibatch_updates(lr, last=g + 1 == G)
+            else:
+                self._apply_update(lr)
+            if E > 1 and M == 1:
                 # update 1's losses are the ones last_losses reports under its present keys; the reuse passes overwrite
                 # self.losses.  E - 1 more updates on the same rollout, at this group's learning rate
                 ops.axpy(1.0 / G, self.losses, self.loss_sum)
@@ -1027,7 +1153,7 @@ class Trainer(object):
                     ops.axpy(1.0 / (G * (E - 1)), self.losses, self.reuse_loss_sum)
             ops.rollout_stats(self.Bg, self.n_steps, self.ring.score_valid, self.ring.score_out, self.stats)
             if G > 1:
-                if E == 1:
+                if E == 1 and M == 1:
                     ops.axpy(1.0 / G, self.losses, self.loss_sum)
                 # bound the un-synchronised dispatch queue like the replay fill does (a group pass is ~300 launches: at
                 # G = 64 one call would enqueue ~19 k dispatches before its only host sync; rocprofv3's counter thread
@@ -1041,6 +1167,22 @@ class Trainer(object):
         steps, episodes, score_sum = self.read_stats()
         self._publish_losses()
         return steps, (score_sum / episodes if episodes > 0 else None)
+
+    def _minibatch_updates(self, lr, last=False):
+        """The E * M updates of the selected group's rollout, all at the group's learning rate: epoch e visits
+        the blocks in minibatch_order(e, M).  Every update's losses join the call's mean.  The un-synchronised dispatch
+        queue keeps process()'s bound: a host sync after every GROUP_SYNC_EVERY updates (`last`: but not after the call's
+        final update, which the caller's read of the stats follows)."""
+        G, E, M = self.groups, self.reuse_epochs, self.reuse_minibatches
+        done = 0
+        for e in range(1, E + 1):
+            for m in self.minibatch_order(e, M):
+                self.minibatch_gradients(m)
+                self._apply_update(lr)
+                ops.axpy(1.0 / (G * E * M), self.losses, self.loss_sum)
+                done += 1
+                if done % self.GROUP_SYNC_EVERY == 0 and not (last and done == E * M):
+                    torch.cuda.current_stream().synchronize()
 
     def grad_sync_ms(self):
         """[ms] of every gradient exchange since the last call (time_grad_sync): from the point the launch stream reaches
@@ -1060,7 +1202,8 @@ class Trainer(object):
 
     def _publish_losses(self):
         # groups: mean over the call's groups; with reuse_epochs > 1 of every group's update 1 (process())
-        l = (self.loss_sum if self.groups > 1 or self.reuse_epochs > 1 else self.losses).cpu().numpy()
+        M = self.reuse_minibatches
+        l = (self.loss_sum if self.groups > 1 or self.reuse_epochs > 1 or M > 1 else self.losses).cpu().numpy()
         net = self.local_network
         net.policy_loss, net.value_loss, net.entropy = float(l[0]), float(l[1]), float(l[2])
         net.base_loss = net.policy_loss + net.value_loss
@@ -1076,12 +1219,15 @@ class Trainer(object):
         if self.use_depth_prediction:
             hits = self.dp_hits.cpu().numpy()
             self.last_losses.update(depth_loss=net.depth_loss, depth_accuracy=float(hits[0]) / max(int(hits[1]), 1))
-        if self.reuse_epochs > 1:         # means over the call's reuse updates; the two counts are exact
-            r = self.reuse_loss_sum.cpu().numpy()
+        if self.reuse_epochs > 1 or M > 1:  # means over the call's reuse updates; the two counts are exact
+            # (minibatches, DESIGN §7t: every update of the call is a reuse update, so the means above are theirs)
+            r = l if M > 1 else self.reuse_loss_sum.cpu().numpy()
             si, sf = self.reuse_stats_i.cpu().numpy(), self.reuse_stats_f.cpu().numpy()
             n = max(int(si[1]), 1)
             self.last_losses.update(reuse_policy_loss=float(r[0]), reuse_value_loss=float(r[1]), reuse_entropy=float(r[2]),
                                     clip_fraction=float(si[0]) / n, approx_kl=float(sf[0]) / n)
+            if M > 1:
+                self.last_losses["updates"] = self.groups * self.reuse_epochs * M
         if self.explore_beta > 0:         # over the call's groups; the counts are exact
             si, sf = self.explore_stats_i.cpu().numpy(), self.explore_stats_f.cpu().numpy()
             n = max(int(si[0]), 1)
