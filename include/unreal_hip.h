@@ -167,6 +167,32 @@ int unreal_maze_policy_rollout_step(int B, int H1, const float* X, int ldx, cons
                                     float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A, int idx_base_actor,
                                     int view, int N, const int* cfg, int actor_base, int* goal, int* layout,
                                     int* ep_steps, int* episode, int* heading, void* stream);
+/* The wall image of every layout of a top-down block (cfg NULL: of the reference's map, N = 7, n_templates = 1):
+ * templates[l * 21168 ..) = the frame of layout l with channel 0 = 1 in wall cells and everything else 0 -- the frame the
+ * maze kernels draw before the agent and goal blocks (maze_environment.py:57-74 _get_current_image without the two
+ * blocks).  Layouts do not change once a block is bound, so this runs once per block.  n_templates must be the block's
+ * layout count (word 1; another count writes nothing); templates 16-byte aligned.  (csrc/maze.hip) */
+int unreal_maze_wall_templates(int N, const int* cfg, int n_templates, uint8_t* templates, void* stream);
+/* unreal_maze_policy_rollout_step + unreal_encoder_fwd of the NEXT observations in ONE launch (csrc/rollout_fused.hip;
+ * trainer.py:236-296 environment.process, then model.py:281-289 on the next step's states): the workgroup that steps actors
+ * 8w .. 8w + 7 builds each 16-byte piece of their next frames in registers (the layout's template from
+ * unreal_maze_wall_templates + the agent and goal blocks), stores it to the ring slot and expands the same registers into
+ * the encoder's image, so the frame is never read back.  Row b of c1_out / f2_out / relu_bits is the encoding of actor b's
+ * next observation, the frame next_idx[b] names; an idle actor's comes from its ring slot.  Everything the two launches
+ * write is written, bit for bit.  Top-down only (view 0), A = 4, cfg NULL or a block; `prepared` (unreal_encoder_prepare
+ * for frame_scale), c1_out, relu_bits and templates are required; anything else is -EINVAL.  A block of another N or
+ * layout count than N / n_templates writes nothing.  `heading` is not used. */
+int unreal_maze_policy_rollout_step_encode(
+    int B, int H1, const float* X, int ldx, const float* Wp, const float* bp, const float* Wv, const float* bv,
+    const double* u, float* pi_out, float* v_out, int* actions_out, int* pos, int* last_action, float* last_reward,
+    int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+    float* r_pc, float* out_reward, int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+    int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
+    float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A, int idx_base_actor, int view, int N, const int* cfg,
+    int actor_base, int* goal, int* layout, int* ep_steps, int* episode, int* heading, const uint8_t* templates,
+    int n_templates, float frame_scale, const float* W1, const float* b1, const float* W2, const float* b2, float* c1_out,
+    float* f2_out, uint16_t* relu_bits, float* f2_absmax /*nullable*/, float* c1_absmax /*nullable*/, const void* prepared,
+    void* stream);
 /* Time-limit bootstrapping: the two rollout entries above with a final-observation store, for the
  * first-person views without goal sense (views 1, 2, 5, 6; any other view: -EINVAL).  A step is a TRUNCATION when the
  * episode ends in it only because of the step limit: steps >= max_episode_steps, no ending pickup, and no goal reached

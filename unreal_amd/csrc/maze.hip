@@ -55,6 +55,7 @@
 #include "maze_common.h"
 #include "policy_row.h"
 #include "ring_step.h"
+#include "maze_step.h"
 
 namespace {
 
@@ -63,63 +64,6 @@ namespace {
 // UNREAL_MAZE_FIRST_PERSON_FORAGE / UNREAL_MAZE_FIRST_PERSON_GENERATED_FORAGE
 constexpr int kTopDown = 0, kFirstPerson = 1, kFirstPersonGen = 2, kFirstPersonSense = 3, kFirstPersonGenSense = 4;
 constexpr int kFirstPersonForage = 5, kFirstPersonGenForage = 6;
-
-// The reference's map as a configuration block (layout: maze_common.h).
-constexpr const char* kMap =
-    "--+---G"
-    "--+-+++"
-    "S-+---+"
-    "--+++--"
-    "--+-+--"
-    "--+----"
-    "-----++";
-
-struct DefaultMaze { int v[kCfgHdr + kRecHdr + 49]; };
-constexpr DefaultMaze make_default_maze() {
-  DefaultMaze m{};
-  m.v[0] = 7; m.v[1] = 1; m.v[6] = kRecHdr + 49;
-  int* r = m.v + kCfgHdr;
-  uint64_t walls = 0;
-  int nf = 0;
-  r[14] = r[15] = r[17] = -1;
-  for (int i = 0; i < 49; ++i) {
-    if (kMap[i] == '+') { walls |= 1ull << i; continue; }
-    if (kMap[i] == 'S') r[14] = i;
-    if (kMap[i] == 'G') { r[15] = i; r[17] = nf; }
-    r[kRecHdr + nf++] = i;
-  }
-  r[0] = (int)(uint32_t)walls; r[1] = (int)(uint32_t)(walls >> 32);
-  r[16] = nf;
-  return m;
-}
-// read at compile time: the null-config path loads nothing of the block
-constexpr DefaultMaze kDefaultMaze = make_default_maze();
-constexpr const int* kDefaultRec = kDefaultMaze.v + kCfgHdr;
-constexpr uint64_t kDefaultWalls = (uint64_t)(uint32_t)kDefaultRec[0] | ((uint64_t)(uint32_t)kDefaultRec[1] << 32);
-constexpr int kDefaultStart = kDefaultRec[14], kDefaultGoal = kDefaultRec[15];
-static_assert(kDefaultStart == 2 * 7 + 0 && kDefaultGoal == 6, "maze constants");
-
-// The wall bits of the layout a workgroup renders: at N = 7 (49 bits) in a uniform register; above, up to 441 bits in
-// LDS (a dynamically indexed register array is placed in scratch).  load() is called by every thread of the workgroup.
-template <int N>
-struct Walls {
-  static constexpr int NW = (N * N + 63) / 64;
-  uint64_t w0;
-  uint64_t* lds;         // NW > 1: the workgroup's copy, NW words
-  __device__ __forceinline__ void load(const int* rec) {     // rec null: the reference map
-    if constexpr (NW == 1) {
-      w0 = rec ? (uint64_t)(uint32_t)rec[0] | ((uint64_t)(uint32_t)rec[1] << 32) : kDefaultWalls;
-    } else {
-      if (threadIdx.x < NW)
-        lds[threadIdx.x] = (uint64_t)(uint32_t)rec[2 * threadIdx.x] | ((uint64_t)(uint32_t)rec[2 * threadIdx.x + 1] << 32);
-      __syncthreads();
-    }
-  }
-  __device__ __forceinline__ uint32_t bit(int cell) const {
-    if constexpr (NW == 1) return (uint32_t)(w0 >> cell) & 1u;
-    else return (uint32_t)(lds[cell >> 6] >> (cell & 63)) & 1u;
-  }
-};
 
 // The frame is the layout's wall image (ch 0) plus the c x c agent block (ch 1) and, with show_goal, the goal block (ch 2),
 // c = 84 / N.  A workgroup builds the wall image ONCE per layout in LDS (the per-byte index arithmetic below is ~250 VALU
@@ -190,67 +134,6 @@ __device__ __forceinline__ void render_blocks(uint8_t* dst, const uint4* img, in
   }
 }
 
-// pixels of the c x c agent block at cell (cx,cy) inside pixel-change cell (i,j):
-// rows 4i+2..4i+5, cols 4j+2..4j+5 of the full frame (the [2:-2] crop, then 4x4 blocks)
-template <int N>
-__device__ __forceinline__ int overlap1(int cell, int k) {
-  constexpr int C = FRAME_W / N;
-  int lo = max(C * cell, 4 * k + 2), hi = min(C * cell + C - 1, 4 * k + 5);
-  return max(0, hi - lo + 1);
-}
-
-// The arguments of every maze kernel, both views, step and reset.
-struct MazeArgs {
-  int B, H1;
-  const int* actions;
-  const int* active;
-  int* pos;
-  int* last_action;
-  float* last_reward;
-  int* count;
-  uint8_t* frames;
-  float* r_reward;
-  int* r_action;
-  int* r_terminal;
-  int* r_last_action;
-  float* r_last_reward;
-  float* r_pc;
-  float* out_reward;
-  int* out_terminal;
-  float* episode_reward;
-  float* score_out;
-  int* score_valid;
-  int reset_on_terminal;
-  int track_score;
-  // rollout bookkeeping fused into the step (unreal_maze_rollout_step; all null / 0 for the plain step):
-  int* active_rw;        // in: actor still inside its rollout; out: cleared at its terminal (trainer.py:279-296 `break`)
-  int* active_log_t;     // active flag of this step (row mask of the losses)
-  int* n_steps;          // += 1 per step taken
-  int* terminal_end;     // set at the terminal
-  int* next_idx;         // nullable: ring index of the NEXT observation ((idx_base + b) * H1 + slot), also for idle actors
-  float* next_lar;       // nullable: [B][lar_ld] rows of the next step's LSTM input: one-hot last action | last reward
-  int lar_ld, lar_col0, A;
-  int idx_base;          // index of this launch's first actor in the ring next_idx is meant for (a half-batch of a ring)
-  // fused policy step (unreal_maze_policy_rollout_step; pol_x null: the actions are given): the actors' feature rows ->
-  // pi, V and the drawn action, computed by the workgroup that then steps those actors (one launch less per rollout step)
-  const float* pol_x; int pol_ldx;
-  const float* Wp; const float* bp; const float* Wv; const float* bv;
-  const double* pol_u;
-  float* pi_out; float* v_out; int* act_out;
-  // the maze tail: configuration block (null: the reference's map, top-down only, and the arrays below unused)
-  const int* cfg;
-  int actor_base;        // global index of actor 0 of this launch (reset draws are keyed by it)
-  int* goal;             // [2B] goal cell (x, y) of the running episode
-  int* layout;           // [B] layout id
-  int* ep_steps;         // [B] steps taken in the running episode
-  int* episode;          // [B] episode index (-1 before the first reset)
-  int* heading;          // [B] first person: heading of the camera; navigation / generated blocks: the per-actor records
-  union {                // (one word: the step kernels of the entries without a store keep the arguments they had)
-    const int* mask;     // reset only (nullable): the actors to reset
-    uint8_t* final_obs;  // the _tl entries only: [B] frames, the final observation of an episode cut off at the step limit
-  };
-};
-
 // APG actors per workgroup: 8 when the batch fills the chip (the wall image is built once per workgroup: ~2.5 us of VALU),
 // 2 for small batches (grouped updates: 512 actors per launch), where 8 actors in a row per workgroup were 20 of the
 // launch's 23 us and most CUs had no workgroup at all, 1 at <= 64 actors (an 8-actor update: 8 workgroups instead of 4)
@@ -260,16 +143,14 @@ __global__ __launch_bounds__(256) void maze_step_kernel(MazeArgs p) {
   // (uniform) the block's grid size must be the one this kernel was built for: with another N the cell arithmetic would
   // address outside the frame, so nothing is written (documented with the maze entries in unreal_hip.h)
   // (a generated block, which has no layout record and is first person only, counts as another size; so does a forage block)
-  if ((cfg ? cfg[0] | (cfg[2] & (kMazeGen | kMazeForage)) << 8 : 7) != N) return;
+  if (maze_block_size(cfg) != N) return;
   __shared__ uint4 wall_img[FRAME_BYTES / 16];
   // the workgroup's actors' scalar state, fetched by one thread per actor while the wall image is built: read inside the
   // per-actor loop, each actor would start with two dependent global round trips (state, then the previous slot's terminal
-  // flag) that nothing overlaps -- 8 actors x ~2 us of a 38 us launch
-  __shared__ int s_flag[APG], s_x[APG], s_y[APG], s_a[APG],
-      s_cnt[APG], s_la[APG], s_prev[APG], s_ns[APG];
-  __shared__ float s_lr[APG], s_ep[APG];
-  // configured maze: layout, goal cell, episode steps, and the goal / start cells of the next episode (drawn here too)
-  __shared__ int s_lay[APG], s_goal[APG], s_st[APG], s_epi[APG], s_rgoal[APG], s_rstart[APG];
+  // flag) that nothing overlaps -- 8 actors x ~2 us of a 38 us launch.  With a configured maze it holds the layout, goal
+  // cell, episode steps, and the goal / start cells of the next episode (drawn here too)
+  __shared__ MazeActor s_act[APG];
+  __shared__ int s_a[APG];
   if (p.pol_x) {       // (workgroup-uniform) policy of this workgroup's actors: wave w takes actors w, w + 4, ...
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int k = wave; k < APG; k += 4) {
@@ -283,26 +164,8 @@ __global__ __launch_bounds__(256) void maze_step_kernel(MazeArgs p) {
   if (threadIdx.x < APG) {
     const int k = threadIdx.x, b = blockIdx.x * APG + k;
     if (b < p.B) {
-      const int cnt = p.count[b];
-      s_flag[k] = p.active_rw ? p.active_rw[b] : (p.active ? p.active[b] : 1);
-      s_x[k] = p.pos[2 * b]; s_y[k] = p.pos[2 * b + 1];
       if (!p.pol_x) s_a[k] = p.actions[b];
-      s_cnt[k] = cnt;
-      s_la[k] = p.last_action[b];
-      s_lr[k] = p.last_reward[b];
-      s_ep[k] = p.track_score ? p.episode_reward[b] : 0.f;
-      s_ns[k] = p.active_rw ? p.n_steps[b] : 0;      // (read here: a load inside the actor loop stalls thread 0's wave -- and,
-                                                     // through the loop's barrier, the workgroup -- for a memory round trip per actor)
-      s_prev[k] = cnt > 0 ? p.r_terminal[(size_t)b * p.H1 + (cnt - 1) % p.H1] : 0;
-      int lay = 0, goal = kDefaultGoal, st = 0, epi = 0, rg = kDefaultGoal, rs = kDefaultStart;
-      if (cfg) {
-        lay = maze_layout(cfg, p.layout, b);
-        goal = p.goal[2 * b + 1] * N + p.goal[2 * b];
-        st = p.ep_steps[b];
-        epi = p.episode[b];
-        maze_reset_cells(cfg, maze_rec(cfg, lay), p.actor_base + b, epi + 1, rg, rs);
-      }
-      s_lay[k] = lay; s_goal[k] = goal; s_st[k] = st; s_epi[k] = epi; s_rgoal[k] = rg; s_rstart[k] = rs;
+      s_act[k] = maze_fetch_actor<N>(p, b);
     }
   }
   int built = cfg ? maze_layout(cfg, p.layout, blockIdx.x * APG) : 0;     // the first actor's layout: read by every thread
@@ -313,69 +176,35 @@ __global__ __launch_bounds__(256) void maze_step_kernel(MazeArgs p) {
   build_wall_image<N>(wall_img, walls);
   __syncthreads();
   const int H1 = p.H1;
-  const int max_steps = cfg ? cfg[3] : 0;
   const bool show_goal = cfg && (cfg[2] & kMazeShowGoal);
   for (int k = 0; k < APG; ++k) {
     const int b = blockIdx.x * APG + k;
     if (b >= p.B) break;
-    if (!s_flag[k]) {
-      if (threadIdx.x == 0) rollout_idle(p, b, s_cnt[k] % H1, s_la[k], s_lr[k]);
+    const MazeActor st = s_act[k];
+    if (!st.flag) {
+      if (threadIdx.x == 0) rollout_idle(p, b, st.cnt % H1, st.la, st.lr);
       continue;
     }
-    if (s_lay[k] != built) {           // (uniform) a layout boundary inside the workgroup: rebuild the wall image
-      built = s_lay[k];
+    if (st.lay != built) {             // (uniform) a layout boundary inside the workgroup: rebuild the wall image
+      built = st.lay;
       __syncthreads();                 // every thread is done reading the previous image
       walls.load(maze_rec(cfg, built));       // (a layout other than the first: cfg is not null)
       build_wall_image<N>(wall_img, walls);
       __syncthreads();
     }
-    const int x = s_x[k], y = s_y[k];
     const int a = s_a[k];
-    const int gc = s_goal[k], gx = gc % N, gy = gc / N;
+    const MazeMove m = maze_move<N>(p, b, st, a, walls);
 
-    // _move (maze_environment.py:76-91), bound N - 1
-    int dx = (a == 3) - (a == 2), dy = (a == 1) - (a == 0);
-    int nx = x + dx, ny = y + dy;
-    bool clamped = nx < 0 || nx > N - 1 || ny < 0 || ny > N - 1;
-    nx = min(max(nx, 0), N - 1);
-    ny = min(max(ny, 0), N - 1);
-    bool hit_wall = walls.bit(ny * N + nx);
-    if (hit_wall) { nx = x; ny = y; }
-    const bool hit = clamped || hit_wall;
-    const bool at_goal = (nx == gx && ny == gy);
-    const int steps = s_st[k] + 1;
-    const bool terminal = at_goal || (max_steps > 0 && steps >= max_steps);   // goal, or the episode's time-out
-    const float reward = at_goal ? 1.f : (hit ? -1.f : 0.f);
-    const RingStep s = ring_step(b, H1, s_cnt[k], s_prev[k], terminal, p.reset_on_terminal);
+    // pixel change between render(nx,ny) and render(x,y)
+    for (int c = threadIdx.x; c < PC_CELLS; c += blockDim.x)
+      p.r_pc[m.s.base * PC_CELLS + c] = maze_pc_cell<N>(c, st.x, st.y, m.nx, m.ny);
 
-    // pixel change between render(nx,ny) and render(x,y): only the two agent blocks differ (ch 1)
-    const bool moved = (nx != x) || (ny != y);
-    for (int c = threadIdx.x; c < PC_CELLS; c += blockDim.x) {
-      int i = c / 20, j = c - i * 20;
-      int sum = 0;
-      if (moved) sum = overlap1<N>(y, i) * overlap1<N>(x, j) + overlap1<N>(ny, i) * overlap1<N>(nx, j);
-      p.r_pc[s.base * PC_CELLS + c] = (float)sum / 48.0f;
-    }
-
-    const int rc = s_rstart[k], ngc = s.reset ? s_rgoal[k] : gc;
-    const int rx = s.reset ? rc % N : nx, ry = s.reset ? rc / N : ny;
-    uint8_t* dst = p.frames + ((size_t)b * H1 + s.nslot) * FRAME_BYTES;
+    uint8_t* dst = p.frames + ((size_t)b * H1 + m.s.nslot) * FRAME_BYTES;
     render_walls(dst, wall_img);
     __syncthreads();  // every thread has read the actor's state; wall stores precede the block patch
-    render_blocks<N>(dst, wall_img, rx, ry, ngc % N, ngc / N, show_goal);
+    render_blocks<N>(dst, wall_img, m.rx, m.ry, m.ngc % N, m.ngc / N, show_goal);
 
-    if (threadIdx.x == 0) {
-      ring_commit(p, b, s, a, reward, reward, s_la[k], s_lr[k], s_ep[k]);
-      p.pos[2 * b] = rx;
-      p.pos[2 * b + 1] = ry;
-      if (cfg) {
-        p.goal[2 * b] = ngc % N;
-        p.goal[2 * b + 1] = ngc / N;
-        p.ep_steps[b] = s.reset ? 0 : steps;
-        p.episode[b] = s_epi[k] + (s.reset ? 1 : 0);
-      }
-      rollout_commit(p, b, s, s_ns[k], a, reward);
-    }
+    if (threadIdx.x == 0) maze_commit<N>(p, b, st, a, m);
   }
 }
 
@@ -436,6 +265,20 @@ __global__ __launch_bounds__(256) void maze_reset_kernel(MazeArgs p) {
       }
     }
   }
+}
+
+// The wall image of every layout of a block (cfg null: of the reference's map), one uint8 frame per layout: what
+// build_wall_image gives the step kernel, kept in global memory for the launch that patches the agent and goal blocks into
+// its pieces in registers (rollout_fused.hip).  Layouts do not change once a block is bound: written once.  One workgroup
+// per layout.
+template <int N>
+__global__ __launch_bounds__(256) void maze_wall_templates_kernel(const int* cfg, int n_templates, uint4* out) {
+  if (maze_block_size(cfg) != N || (cfg ? cfg[1] : 1) != n_templates) return;      // (uniform)
+  __shared__ uint64_t s_walls[Walls<N>::NW];
+  Walls<N> walls;
+  walls.lds = s_walls;
+  walls.load(cfg ? maze_rec(cfg, blockIdx.x) : nullptr);
+  build_wall_image<N>(out + (size_t)blockIdx.x * (FRAME_BYTES / 16), walls);
 }
 
 // ---- first person --------------------------------------------------------------------------------------------------
@@ -1593,6 +1436,20 @@ int unreal_maze_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, c
              Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
   return maze_launch(kPolicy, p, view, N, cfg, actor_base, goal, layout, ep_steps, episode, heading, stream, true,
                      final_obs);
+}
+
+int unreal_maze_wall_templates(int N, const int* cfg, int n_templates, uint8_t* templates, void* stream) {
+  if (!templates || ((uintptr_t)templates & 15) || n_templates < 1) return UNREAL_EINVAL;
+  if (!cfg ? (N != 7 || n_templates != 1) : !(N == 7 || N == 12 || N == 14 || N == 21)) return UNREAL_EINVAL;
+  uint4* out = reinterpret_cast<uint4*>(templates);
+  hipStream_t s = (hipStream_t)stream;
+  switch (N) {
+    case 7: hipLaunchKernelGGL(maze_wall_templates_kernel<7>, dim3(n_templates), dim3(256), 0, s, cfg, n_templates, out); break;
+    case 12: hipLaunchKernelGGL(maze_wall_templates_kernel<12>, dim3(n_templates), dim3(256), 0, s, cfg, n_templates, out); break;
+    case 14: hipLaunchKernelGGL(maze_wall_templates_kernel<14>, dim3(n_templates), dim3(256), 0, s, cfg, n_templates, out); break;
+    default: hipLaunchKernelGGL(maze_wall_templates_kernel<21>, dim3(n_templates), dim3(256), 0, s, cfg, n_templates, out); break;
+  }
+  return unreal_launch_status();
 }
 
 int unreal_maze_objective(int B, int H1, const int* count, const int* records, int record_words, float* r_objective,

@@ -661,6 +661,32 @@ class BatchedMazeEnvironment(object):
                                      final_obs=self.ring.final_obs, **nxt)
         self._objective(nxt)
 
+    @property
+    def fused_encoder_ok(self):
+        """True where policy_rollout_step_encode serves this environment: a top-down maze (the reference's map or a
+        config), without a final-observation store or depth labels (first person only anyway)."""
+        top_down = self.maze is None or self.maze[0] == ops.MAZE_TOP_DOWN
+        return top_down and self.ring.final_obs is None and not getattr(self, "depth_labels", False) and \
+            not self.ring.objective_size
+
+    def policy_rollout_step_encode(self, net, feat, ld, u, pi_out, v_out, actions, out_reward, out_terminal, active,
+                                   active_log_t, n_steps, terminal_end, f2_out, c1_out, relu_bits, f2_max, c1_max,
+                                   index_parent=False, **nxt):
+        """policy_rollout_step() and `net`'s conv encoder of the observations it leaves, in one launch: row b of f2_out /
+        c1_out / relu_bits is what net.encoder_forward gives for next_idx[b] (bit for bit)."""
+        p = net.p
+        tmpl = getattr(self, "_wall_templates", None)
+        if tmpl is None:            # once per environment (a view builds its own): layouts never change
+            tmpl = self._wall_templates = ops.maze_wall_templates(self.maze, 1 if self.config is None else self.config.L,
+                                                                  self.ring.frames.device)
+        ops.maze_policy_rollout_step_encode(self.ring, feat, ld, p["W_base_fc_p"], p["b_base_fc_p"], p["W_base_fc_v"],
+                                            p["b_base_fc_v"], u, pi_out, v_out, actions, out_reward, out_terminal, active,
+                                            active_log_t, n_steps, terminal_end, tmpl, net.frame_scale,
+                                            p["W_base_conv1"], p["b_base_conv1"], p["W_base_conv2"], p["b_base_conv2"],
+                                            f2_out, c1_out, relu_bits, net.enc_prepared, f2_max=f2_max, c1_max=c1_max,
+                                            base_actor=getattr(self, "base_actor", 0) if index_parent else 0,
+                                            maze=self.maze, **nxt)
+
     def current_distances(self):
         """The distance fields of the running episodes of a goal-sense config -> uint16 [B, N, N] ([b, y, x]): path
         distance of every cell to the actor's goal, MazeConfig.NO_PATH in walls."""

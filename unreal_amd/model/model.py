@@ -458,12 +458,15 @@ class UnrealModel(object):
 
     def encode_rows(self, ring, ws, row0, nrows, lar_from_ring=True, save_c1=True, clip_lar=False,
                     objective_slot_offset=0, actor_ring=None, lar_prefilled=False, lstm_x=True, slots=None,
-                    objective_prefilled=False):
+                    objective_prefilled=False, encoded=False):
         """conv encoder -> fc (+ last_action_reward[_objective] columns and the input half of the LSTM gates) for
         rows [row0, row0+nrows) of a path workspace.  `objective_slot_offset` = -1 reproduces trainer.py:300, where the
         bootstrap value is fed the objective of the previous frame's state.  `lstm_x` False: a single time step follows
         whose lstm_step(fused_x=True) multiplies [x | h] by the whole kernel, so the input half is not hoisted.
-        `objective_prefilled`: the environment step has written the objective columns too (a goal-sense maze)."""
+        `objective_prefilled`: the environment step has written the objective columns too (a goal-sense maze).
+        `encoded`: the rows' f2, saved conv1 and ReLU bits are there already and the absmax slots cover them (the
+        environment step that produced the frames has encoded them: Trainer.fuse_env_encoder); the fc product, the
+        last_action_reward handling and the slots are used as ever."""
         p = self.p
         idx = ws.frame_idx[row0:row0 + nrows]
         F = self.F
@@ -482,8 +485,9 @@ class UnrealModel(object):
         self.ws_slots(ws)
         own = actor_ring is not None and slots is None
         s_f2, s_fc = slots if slots is not None else ((self.new_slot(), self.new_slot()) if own else (ws.s_f2, ws.s_x))
-        self.encoder_forward(ring, idx, f2, c1, relu_bits=bits, f2_max=s_f2, c1_max=ws.s_c1 if c1 is not None else None,
-                             ws=ws)
+        if not encoded:
+            self.encoder_forward(ring, idx, f2, c1, relu_bits=bits, f2_max=s_f2,
+                                 c1_max=ws.s_c1 if c1 is not None else None, ws=ws)
         sh = self.shadow
         nslab = ops.slab_count(nrows, 256, F) if self.fc_few_rows_slabs else 0
         if nslab:

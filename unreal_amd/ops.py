@@ -417,6 +417,54 @@ def maze_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, act
                          lar_ld, lar_col0, A, base_actor), *_maze_args(ring, maze), *fin)
 
 
+def maze_wall_templates(maze, n_layouts, device, out=None):
+    """The wall image of every layout of a top-down maze (`maze` as in the maze wrappers; None: the reference's map, one
+    layout) -> uint8 [n_layouts * FRAME_BYTES], what maze_policy_rollout_step_encode patches the agent and goal blocks
+    into.  Layouts do not change once a block is bound: call once per block."""
+    n_layouts = int(n_layouts)
+    if maze is not None and maze[0] != MAZE_TOP_DOWN:
+        raise ValueError("wall templates are the top-down view's")
+    if maze is None and n_layouts != 1:
+        raise ValueError("the reference's map is one layout")
+    if out is None:
+        out = torch.empty(n_layouts * FRAME_BYTES, dtype=torch.uint8, device=device)
+    _chk(out, "u8", n_layouts * FRAME_BYTES, "templates")
+    N, block = (7, None) if maze is None else (maze[1], maze[2])
+    _chk(block, "i32", 8, "maze config", optional=True)
+    _call("unreal_maze_wall_templates", int(N), ptr(block), n_layouts, ptr(out))
+    return out
+
+
+def maze_policy_rollout_step_encode(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions, out_reward, out_terminal,
+                                    active, active_log_t, n_steps, terminal_end, templates, scale, W1, b1, W2, b2, f2_out,
+                                    c1_out, relu_bits, prepared, f2_max=None, c1_max=None, next_idx=None, next_lar=None,
+                                    lar_ld=0, lar_col0=0, A=4, base_actor=0, maze=None):
+    """maze_policy_rollout_step + encoder_fwd(ring.frames, next_idx, ...) in one launch, bit for bit: row b of f2_out /
+    c1_out / relu_bits is the encoding of actor b's next observation.  Top-down mazes with 4 actions only; `templates` from
+    maze_wall_templates, `prepared` from encoder_prepare(W1, b1, W2, scale)."""
+    B = ring.B
+    if (maze is not None and maze[0] != MAZE_TOP_DOWN) or A != 4:
+        raise ValueError("the fused step + encoder serves top-down mazes with 4 actions")
+    if ring.frame_stride != FRAME_BYTES:
+        raise ValueError("the fused step + encoder serves 84 x 84 frames")
+    _chk(X, "f32", (B - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A); _chk(bp, "f32", A); _chk(Wv, "f32", 256)
+    _chk(bv, "f32", 1); _chk(u, "f64", B, "u"); _chk(pi_out, "f32", B * A); _chk(v_out, "f32", B)
+    _chk(actions, "i32", B, "actions")
+    _chk(templates, "u8", FRAME_BYTES, "templates")
+    if templates.numel() % FRAME_BYTES:
+        raise ValueError("templates: whole frames")
+    _chk(W1, "f32", 3072); _chk(b1, "f32", 16); _chk(W2, "f32", 8192); _chk(b2, "f32", 32)
+    _chk(f2_out, "f32", B * F2_DIM); _chk(c1_out, "f32", B * C1_DIM); _chk(relu_bits, "i16", B * RELU_WORDS, "relu_bits")
+    _chk(f2_max, "f32", 1, "f2_max", optional=True); _chk(c1_max, "f32", 1, "c1_max", optional=True)
+    _chk(prepared, "u8", ENC_PREPARED_BYTES, "prepared")
+    _call("unreal_maze_policy_rollout_step_encode", B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv),
+          ptr(u), ptr(pi_out), ptr(v_out), ptr(actions),
+          *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
+                         lar_ld, lar_col0, A, base_actor), *_maze_args(ring, maze),
+          ptr(templates), templates.numel() // FRAME_BYTES, float(scale), ptr(W1), ptr(b1), ptr(W2), ptr(b2), ptr(c1_out),
+          ptr(f2_out), ptr(relu_bits), ptr(f2_max), ptr(c1_max), ptr(prepared))
+
+
 # ---- device arcade (csrc/arcade.hip, DESIGN §7k) -----------------------------------------------------------------------
 def _arcade_args(ring, arcade):
     """The tail of every arcade entry.  `arcade` = (int32 config block on the device, global index of the ring's actor 0)."""

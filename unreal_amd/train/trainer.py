@@ -550,17 +550,18 @@ class Trainer(PassState):
         raise NotImplementedError("actions are drawn on the device; see ops.softmax_sample")
 
     # ---------------------------------------------------------------------------------------------------
-    def _policy_step(self, ws, t, u, actions_out, pi_out, v_out, prefilled=False, heads=True):
+    def _policy_step(self, ws, t, u, actions_out, pi_out, v_out, prefilled=False, heads=True, encoded=False):
         """Forward the current observations of all actors as time row-block t of `ws` and draw actions.  `prefilled`:
         the previous environment step has already written this block's frame indices and last_action_reward columns.
-        `heads` False: the caller's environment step computes pi / V / action itself (fused launch); -> (feat, ld)."""
+        `heads` False: the caller's environment step computes pi / V / action itself (fused launch); -> (feat, ld).
+        `encoded`: the previous environment step has also run the conv encoder on this block's frames (fuse_env_encoder)."""
         B, A, net = self.Bg, self.action_size, self.local_network
         if not prefilled:
             self.ring.cur_idx(out=ws.frame_idx[t * B:(t + 1) * B])
         # (a goal-sense maze's step has also written the objective columns: no objective_fill launch at t > 0)
         net.encode_rows(self.ring, ws, t * B, B, lar_from_ring=False, save_c1=ws.c1 is not None,
                         lar_prefilled=prefilled and self.use_lstm, lstm_x=False,
-                        objective_prefilled=prefilled and self.use_lstm and self.device_env)
+                        objective_prefilled=prefilled and self.use_lstm and self.device_env, encoded=encoded)
         if self.use_lstm:
             net.lstm_step(ws, t, B, fused_x=True)
         feat, ld = net.features(ws, t * B)
@@ -664,6 +665,13 @@ class Trainer(PassState):
     # Maze rollout: policy head + softmax + action draw inside the environment step's launch (unreal_maze_policy_rollout_step,
     # bit-identical to unreal_policy_step + unreal_maze_rollout_step; one ~5-7 us launch less per step)
     fuse_policy_env = True
+    # Top-down maze rollout at > 1024 actors (the step kernel's 8-actors-per-workgroup regime): the environment step of
+    # t < T - 1 also runs the conv encoder of step t + 1 on the frames it produces, from registers
+    # (unreal_maze_policy_rollout_step_encode, bit-identical to the step's launch + unreal_encoder_fwd: the frame is not
+    # read back, one launch less per step).  Step 0 and the bootstrap frame keep the stand-alone encoder.  False: the two
+    # launches.  Same-process A/B: tools/bench_rollout_fused.py, profiles/r06_ab_summary.md.
+    fuse_env_encoder = True
+    FUSE_ENV_ENCODER_MIN_ACTORS = 1025
 
     def _rollout_split_setup(self):
         """Per group: the halves' environment views, streams and running absmax slot pairs (built once)."""
@@ -740,16 +748,32 @@ class Trainer(PassState):
             self._rollout_steps_split()
         fused = self.device_env              # the maze / arcade step kernel also does the loop bookkeeping and prepares step t+1
         fuse_policy = fused and self.fuse_policy_env     # policy head + draw inside the environment step's launch
+        # ... and the conv encoder of the next step's frames (rows t + 1 of ws: f2, saved conv1, ReLU bits, absmax slots)
+        fuse_encoder = (fuse_policy and self.fuse_env_encoder and B >= self.FUSE_ENV_ENCODER_MIN_ACTORS and A == 4 and
+                        getattr(self.environment, "fused_encoder_ok", False) and not net.hw and
+                        net.enc_prepared is not None and ws.c1 is not None and ws.f2_bits is not None)
+        encoded = False
         for t in range(0 if not (self.overlap_host or split) else T, T):
             s = slice(t * B, (t + 1) * B)
             feat, ld = self._policy_step(ws, t, self.u_act[s], self.actions[s], self.pi[t * B * A:(t + 1) * B * A],
-                                         self.v[s], prefilled=fused and t > 0, heads=not fuse_policy)
+                                         self.v[s], prefilled=fused and t > 0, heads=not fuse_policy, encoded=encoded)
+            encoded = False
             if fused:
                 nxt = {}
                 if t + 1 < T:
                     nxt = dict(next_idx=ws.frame_idx[(t + 1) * B:(t + 2) * B])
                     if self.use_lstm:
                         nxt.update(next_lar=ws.xcat[(t + 1) * B * ws.xld:], lar_ld=ws.xld, lar_col0=256, A=A)
+                if fuse_encoder and t + 1 < T:
+                    r1 = (t + 1) * B
+                    s_f2, _, s_c1 = net.ws_slots(ws)
+                    self.environment.policy_rollout_step_encode(
+                        net, feat, ld, self.u_act[s], self.pi[t * B * A:(t + 1) * B * A], self.v[s], self.actions[s],
+                        self.rewards[s], self.terminals[s], self.active, self.active_log[s], self.n_steps,
+                        self.terminal_end, ws.f2[r1 * net.F:], ws.c1[r1 * net.c1_dim:], ws.f2_bits[r1 * ops.RELU_WORDS:],
+                        s_f2, s_c1, **nxt)
+                    encoded = True
+                    continue
                 if fuse_policy:
                     self.environment.policy_rollout_step(net, feat, ld, self.u_act[s], self.pi[t * B * A:(t + 1) * B * A],
                                                          self.v[s], self.actions[s], self.rewards[s], self.terminals[s],
