@@ -429,6 +429,73 @@ int unreal_arcade_policy_rollout_step_tl(int B, int H1, const float* X, int ldx,
                                          int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0,
                                          int A, int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
                                          int* episode, int* records, uint8_t* final_obs, void* stream);
+/* Game mixtures: the six arcade entries above with one config block per actor.  cfg points to n_blocks
+ * consecutive blocks of UNREAL_ARCADE_CFG_WORDS words (1 <= n_blocks <= UNREAL_ARCADE_MIX_MAX); global actor
+ * g = actor_base + b plays block g % n_blocks for the whole run, whatever view or rank launches it.  Everything of a step
+ * is the block's own: game, rules, action_repeat, return_reward, max_episode_steps and the time-limit cut of the _tl
+ * forms; every actor's record is in its game's layout; the serve and bomb draws stay keyed by (seed, g, episode), so actor
+ * g plays what actor g of a single-block environment of its block plays.  With n_blocks = 1 an entry computes what the
+ * plain entry computes.  The arguments are the plain entry's in the same order, with n_blocks after cfg and, in the step
+ * and rollout forms, done_return[B] and done_episodes[B] before stream (both or neither): when a step ends an episode
+ * and track_score is set (it always is in the rollout forms), done_return[b] += the score written to score_out[b] and
+ * done_episodes[b] += 1.  Per-actor accumulators without atomics; the caller zeroes them.  An actor whose block has an
+ * unknown game id writes nothing; the actors of the other blocks are not affected.
+ * -EINVAL without a launch: n_blocks outside 1..UNREAL_ARCADE_MIX_MAX, one of done_return / done_episodes without the
+ * other, and everything the plain entry refuses. */
+#define UNREAL_ARCADE_MIX_MAX 16
+int unreal_arcade_mix_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
+                            const int* count, uint8_t* frames, const int* cfg, int n_blocks, int actor_base,
+                            int* ep_steps, int* episode, int* records, void* stream);
+int unreal_arcade_mix_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
+                           float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                           int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                           int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                           int reset_on_terminal, int track_score, const int* cfg, int n_blocks, int actor_base,
+                           int* ep_steps, int* episode, int* records, float* done_return /*nullable*/,
+                           int* done_episodes /*nullable*/, void* stream);
+int unreal_arcade_mix_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                   int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                   int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                   int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                   int* active, int* active_log_t, int* n_steps, int* terminal_end,
+                                   int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0,
+                                   int A, int idx_base_actor, const int* cfg, int n_blocks, int actor_base,
+                                   int* ep_steps, int* episode, int* records, float* done_return /*nullable*/,
+                                   int* done_episodes /*nullable*/, void* stream);
+int unreal_arcade_mix_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                          const float* Wv, const float* bv, const double* u, float* pi_out,
+                                          float* v_out, int* actions_out, int* pos, int* last_action,
+                                          float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                          int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+                                          float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                                          float* score_out, int* score_valid, int* active, int* active_log_t,
+                                          int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
+                                          float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A,
+                                          int idx_base_actor, const int* cfg, int n_blocks, int actor_base,
+                                          int* ep_steps, int* episode, int* records, float* done_return /*nullable*/,
+                                          int* done_episodes /*nullable*/, void* stream);
+int unreal_arcade_mix_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                      int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                      int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                      int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                      int* active, int* active_log_t, int* n_steps, int* terminal_end,
+                                      int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld,
+                                      int lar_col0, int A, int idx_base_actor, const int* cfg, int n_blocks,
+                                      int actor_base, int* ep_steps, int* episode, int* records, uint8_t* final_obs,
+                                      float* done_return /*nullable*/, int* done_episodes /*nullable*/, void* stream);
+int unreal_arcade_mix_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                             const float* Wv, const float* bv, const double* u, float* pi_out,
+                                             float* v_out, int* actions_out, int* pos, int* last_action,
+                                             float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                             int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+                                             float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                                             float* score_out, int* score_valid, int* active, int* active_log_t,
+                                             int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
+                                             float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A,
+                                             int idx_base_actor, const int* cfg, int n_blocks, int actor_base,
+                                             int* ep_steps, int* episode, int* records, uint8_t* final_obs,
+                                             float* done_return /*nullable*/, int* done_episodes /*nullable*/,
+                                             void* stream);
 /* host-fed environments (environment/hostfed_environment.py): environment.process + experience.add_frame of
  * every actor where active[b] != 0, for simulators on the host.  `staged` holds one uint8 frame per actor, frame_stride
  * bytes apart as in the ring (a multiple of 16 within [1200, 691200]: 20 x 20 x 3 .. 480 x 480 x 3 rounded up to 16).

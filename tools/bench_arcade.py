@@ -8,13 +8,19 @@
     first-person maze.
 
   python tools/bench_arcade.py [--launches 200] [--steps 10] [--warmup 3] [--history 100] [--repeat 2] [--skip-trainer]
-                               [--game breakout] [--action-repeat 1]
+                               [--game breakout] [--action-repeat 1] [--mix breakout,duel,invaders]
 
 `--game duel` / `--game invaders` measures the two-paddle duel or invaders (§7n) on its default config instead
 of Breakout; its lines then also hold the game's name.  `--game A,B[,C]` times the step and the fused step of these games in
 turn in one process (lines of bench "arcade_games", keys <game>_us_<k> and <game>_fused_us_<k>; no maze kernels, no trainer).  `--action-repeat K` measures the game at K ticks per agent step; its lines then also hold
 action_repeat and, for the arcade kernels, µs per game tick: the launch's time over K (a step runs fewer ticks only where
-one ends the game, about once in a hundred steps on the default configs).  Prints one JSON line per measurement."""
+one ends the game, about once in a hundred steps on the default configs).  Prints one JSON line per measurement.
+`--mix A,B[,C...]` measures game mixtures instead, on the games' default configs: (a) per distinct game, the
+rollout entry of the mixture with that one task (unreal_arcade_mix_rollout_step, K = 1) against the plain entry on the same
+config, the two alternating --repeat times in one process, at 4096 and at 64 actors, with the mix entry without its
+statistics arrays and the two _tl forms beside them (lines of bench "arcade_mix_k1"); (b) the
+K-task mixture's rollout step against each of its tasks' single-game steps and their mean (bench "arcade_mix_step") and,
+unless --skip-trainer, Trainer.process() at 4096 actors on the mixture and on each task (bench "arcade_mix_process")."""
 import argparse
 import json
 import os
@@ -56,6 +62,76 @@ def fused_ms(env, B, launches):
     res = ops.kernel_timer_stop()
     assert res["launches"] == launches, res
     return res["ms"] / launches
+
+
+def rollout_ms(env, B, launches, entry):
+    """Mean HIP-event time of one rollout step through `entry` (random actions, all actors re-armed before every step)."""
+    from unreal_amd import ops
+    rs = np.random.RandomState(0)
+    acts = [torch.from_numpy(rs.randint(0, 4, B).astype(np.int32)).to(DEV) for _ in range(8)]
+    z = lambda dt: torch.zeros(B, dtype=dt, device=DEV)
+    r, t, active, log, n, te = z(torch.float32), z(torch.int32), z(torch.int32), z(torch.int32), z(torch.int32), z(torch.int32)
+
+    def step(k):
+        active.fill_(1)
+        env.rollout_step(acts[k % 8], r, t, active, log, n, te)
+    for k in range(10):
+        step(k)
+    ops.kernel_timer_start(entry)
+    for k in range(launches):
+        step(k)
+    res = ops.kernel_timer_stop()
+    assert res["launches"] == launches, res
+    return res["ms"] / launches
+
+
+def bench_mix(args):
+    from unreal_amd.environment.environment import Environment
+    from unreal_amd.environment.arcade_environment import ArcadeMix, BatchedArcadeEnvironment
+    games = args.mix.split(",")
+    plain, mixed = "unreal_arcade_rollout_step", "unreal_arcade_mix_rollout_step"
+    for g in sorted(set(games)):
+        Environment.register_arcade_config("bench_" + g, game=g)
+    conf = {g: Environment.ARCADE_CONFIG["bench_" + g] for g in set(games)}
+    Environment.register_arcade_mix("bench_mix", ["bench_" + g for g in games])
+    for B in (4096, 64):                                            # (a) one task through the mix entry against the plain entry
+        for g in sorted(conf):
+            # the plain entry, the mix entry, the mix entry without the statistics arrays, and the two _tl forms
+            envs = [BatchedArcadeEnvironment(B, 3, DEV, config=c, final_obs=tl)
+                    for c, tl in ((conf[g], False), (ArcadeMix([conf[g]]), False), (ArcadeMix([conf[g]]), False),
+                                  (conf[g], True), (ArcadeMix([conf[g]]), True))]
+            envs[2].ring.done_return = envs[2].ring.done_episodes = None
+            row = dict(bench="arcade_mix_k1", game=g, B=B)
+            for k in range(args.repeat):
+                for key, env, entry in (("plain", envs[0], plain), ("mix", envs[1], mixed), ("mix_nostats", envs[2], mixed),
+                                        ("plain_tl", envs[3], plain + "_tl"), ("mix_tl", envs[4], mixed + "_tl")):
+                    row["%s_us_%d" % (key, k)] = round(1e3 * rollout_ms(env, B, args.launches, entry), 2)
+            print(json.dumps(row), flush=True)
+            del envs
+            torch.cuda.empty_cache()
+    for B in (4096, 64):                                            # (b) the mixture against its tasks
+        envs = {g: BatchedArcadeEnvironment(B, 3, DEV, config=conf[g]) for g in sorted(conf)}
+        mix_env = BatchedArcadeEnvironment(B, 3, DEV, config=Environment.ARCADE_CONFIG["bench_mix"])
+        for k in range(args.repeat):
+            row = dict(bench="arcade_mix_step", tasks=games, B=B, repeat=k)
+            for g in envs:
+                row[g + "_us"] = round(1e3 * rollout_ms(envs[g], B, args.launches, plain), 2)
+            row["mix_us"] = round(1e3 * rollout_ms(mix_env, B, args.launches, mixed), 2)
+            row["tasks_mean_us"] = round(sum(row[g + "_us"] for g in games) / len(games), 2)
+            row["mix_over_mean"] = round(row["mix_us"] / row["tasks_mean_us"], 3)
+            row["mix_over_slowest"] = round(row["mix_us"] / max(row[g + "_us"] for g in games), 3)
+            print(json.dumps(row), flush=True)
+        del envs, mix_env
+        torch.cuda.empty_cache()
+    if not args.skip_trainer:
+        for k in range(args.repeat):
+            row = dict(bench="arcade_mix_process", tasks=games, B=4096, history=args.history, repeat=k)
+            for g in sorted(conf):
+                row[g + "_ms"] = round(arcade_trainer_ms("bench_" + g, 4096, args.history, args.steps, args.warmup)[1], 2)
+            row["mix_ms"] = round(arcade_trainer_ms("bench_mix", 4096, args.history, args.steps, args.warmup)[1], 2)
+            row["tasks_mean_ms"] = round(sum(row[g + "_ms"] for g in games) / len(games), 2)
+            row["mix_over_mean"] = round(row["mix_ms"] / row["tasks_mean_ms"], 3)
+            print(json.dumps(row), flush=True)
 
 
 def arcade_trainer_ms(env_name, B, history, steps, warmup):
@@ -103,7 +179,10 @@ def main():
     ap.add_argument("--skip-trainer", action="store_true")
     ap.add_argument("--game", default="breakout", help="breakout, duel, invaders, or several of them joined by commas")
     ap.add_argument("--action-repeat", type=int, default=None, help="game ticks per agent step, 1..8 (DESIGN §7m)")
+    ap.add_argument("--mix", default="", help="a game mixture (DESIGN §7u): a comma list of breakout, duel, invaders")
     args = ap.parse_args()
+    if args.mix:
+        return bench_mix(args)
     from unreal_amd.environment.environment import Environment
     from unreal_amd.environment.arcade_environment import BatchedArcadeEnvironment
     from unreal_amd.environment.maze_environment import batched_maze_environment

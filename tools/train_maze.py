@@ -3,6 +3,7 @@
 
 usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] [--steps 2e7] [--log-every 10]
                                   [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout|duel|invaders]
+                                  [--arcade-mix breakout,duel,invaders]
                                   [--opponent-speed N] [--action-repeat K] [--return-reward R] [--seed S]
                                   [--max-episode-steps N] [--bootstrap-timeouts] [--gae-lambda L]
                                   [--gen-maze N] [--depth-prediction] [--depth-lambda X]
@@ -35,7 +36,11 @@ of DESIGN §7r (`--arcade` and `--gen-maze`): a line then also holds explore_bon
 `--gen-maze` line always holds goals_per_episode and apples_per_episode (the actor records' totals over the line's episodes).
 `--optimizer adam [--adam-beta1 X] [--adam-beta2 X] [--adam-epsilon X] [--weight-decay X]` steps with AdamApplier instead of
 RMSPropApplier and `--normalize-advantages` is the Trainer's option of that name (every environment of this
-tool); a line then also holds adv_mean and adv_std of its last call, and the head line the optimizer."""
+tool); a line then also holds adv_mean and adv_std of its last call, and the head line the optimizer.
+`--arcade-mix LIST` trains one agent on a game mixture: LIST is a comma list of breakout, duel and invaders with
+their default configs, repeats allowed (a game listed twice gets twice the actors); actor g plays entry g mod len(LIST).  The
+arcade's options apply to every entry (--return-reward not to invaders, which has no such event); a line then also holds
+`tasks`, Trainer.task_scores() over the line's episodes: per entry its name, game, finished episodes and mean return."""
 import argparse
 import json
 import os
@@ -58,6 +63,7 @@ ap.add_argument("--max-time-step", type=float, default=0)
 ap.add_argument("--entropy-beta", type=float, default=None, help="override options_lab's 0.001 (a stated deviation)")
 ap.add_argument("--out", default="")
 ap.add_argument("--arcade", default="", help="a device arcade game (breakout, duel, invaders) instead of the maze")
+ap.add_argument("--arcade-mix", default="", help="a game mixture: a comma list of breakout, duel, invaders (DESIGN 7u)")
 ap.add_argument("--opponent-speed", type=int, default=None, help="the duel's opponent_speed (default: the game's)")
 ap.add_argument("--action-repeat", type=int, default=1, help="arcade: game ticks per agent step, 1..8")
 ap.add_argument("--return-reward", type=int, default=0, help="arcade: reward for a ball the agent's paddle returns, 0..100")
@@ -84,6 +90,14 @@ ap.add_argument("--weight-decay", type=float, default=0.0, help="AdamW's decoupl
 ap.add_argument("--normalize-advantages", action="store_true",
                 help="the policy loss reads per-rollout normalised advantages (DESIGN 7s)")
 args = ap.parse_args()
+MIX_GAMES = ("breakout", "duel", "invaders")
+mix = [g for g in args.arcade_mix.split(",")] if args.arcade_mix else []
+if mix and (args.arcade or args.gen_maze):
+    ap.error("--arcade-mix, --arcade and --gen-maze are three environments")
+if mix and (not 1 <= len(mix) <= 16 or any(g not in MIX_GAMES for g in mix)):
+    ap.error("--arcade-mix takes a comma list of 1..16 games out of %s, not %r" % (", ".join(MIX_GAMES), args.arcade_mix))
+if mix:
+    args.arcade = "mix:" + ",".join(mix)                  # the mixture's name; everything arcade below applies to it
 if args.depth_prediction and not args.gen_maze:
     ap.error("--depth-prediction needs a first-person maze: --gen-maze N")
 if args.gen_maze and args.arcade:
@@ -118,8 +132,12 @@ def build_arcade_trainer(args, device):
     from unreal_amd.options import get_options
     from unreal_amd.train.trainer import Trainer, log_uniform
     limit = {} if args.max_episode_steps is None else dict(max_episode_steps=args.max_episode_steps)
-    Environment.register_arcade_config(args.arcade, game=args.arcade, opponent_speed=args.opponent_speed,
-                                       action_repeat=args.action_repeat, return_reward=args.return_reward, **limit)
+    for game in sorted(set(mix)) or [args.arcade]:
+        Environment.register_arcade_config(game, game=game, opponent_speed=args.opponent_speed if game == "duel" or not mix
+                                           else None, action_repeat=args.action_repeat,
+                                           return_reward=0 if mix and game == "invaders" else args.return_reward, **limit)
+    if mix:
+        Environment.register_arcade_mix(args.arcade, mix)
     flags = get_options("training", preset="lab", argv=["--env_type", "arcade", "--env_name", args.arcade])
     net = UnrealModel(Environment.get_action_size("arcade", args.arcade), 0, -1, flags.use_lstm, flags.use_pixel_change,
                       flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
@@ -244,6 +262,9 @@ while global_t < args.steps:
             d = (now - totals).tolist()
             totals = now
             extra = {key: round(v / episodes, 3) if episodes else None for key, v in zip(TOTALS, d)}
+        if mix:
+            extra.update(tasks=[dict(t, mean_return=None if t["mean_return"] is None else round(t["mean_return"], 4))
+                                for t in tr.task_scores()])
         if args.depth_prediction:
             # the yardstick of depth_accuracy: the share of the most common class among the labels the replay holds
             hist = torch.bincount(tr.full_ring.r_depth.long(), minlength=8).float()

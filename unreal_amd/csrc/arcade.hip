@@ -5,7 +5,8 @@
 // fixed shooter on Breakout's field.  The rules, the 24-word config blocks and the 16-word per-actor records are documented
 // with the entries in include/unreal_hip.h; tests/arcade_model.py, tests/duel_model.py and tests/invaders_model.py are the
 // host models every kernel here is compared with bit for bit.
-// The kernels read the game id from the block (uniform) and run that game's instance of one body.
+// The kernels read the game id from the block (uniform) and run that game's instance of one body.  The _mix entries at the
+// end of the file give every actor its own block of up to 16, chosen by its global index, through the same body.
 //
 // One actor per 256-thread workgroup.  The game logic is computed by every thread from the record (uniform: scalar
 // registers).  The stored frame of s_t is always the render of the pre-step record, so the step renders the new record
@@ -935,6 +936,83 @@ __global__ __launch_bounds__(256) void arcade_reset_kernel(ArcadeArgs p) {
   else if (game == kArcadeInvaders) reset_actor<InvGame, InvRules>(p);
 }
 
+// ---- game mixtures: one config block per actor ------------------------------------------------------------
+// Global actor g plays block g % n_blocks of `n_blocks` consecutive blocks.  The kernels below are the three above with
+// the block chosen per workgroup (one actor per workgroup: the game branch stays uniform); the bodies are the same
+// instances of step_actor / reset_actor, called on a copy of the arguments whose cfg points at the actor's block.  The
+// arguments the kernels above are compiled from stay what they were: the mixture's words travel in a wrapper.
+constexpr int kArcadeCfgWords = 24, kMaxMixBlocks = 16;
+
+struct ArcadeMixArgs {
+  ArcadeArgs a;
+  int n_blocks;          // 1..16
+  float* done_return;    // [B] (nullable, with done_episodes): the sum of the scores of the actor's finished episodes
+  int* done_episodes;    // [B] their number
+};
+
+__device__ __forceinline__ ArcadeArgs mix_actor_args(const ArcadeMixArgs& m) {
+  ArcadeArgs p = m.a;
+  p.cfg += kArcadeCfgWords * ((p.actor_base + (int)blockIdx.x) % m.n_blocks);
+  return p;
+}
+
+// step_actor, then the per-task statistics where the step ended an episode: the score is the value ring_commit has just
+// written to score_out[b] (thread 0's own stores, read back by thread 0).  Per-actor sums: no atomics.
+// Whether it did is read from what the step left.  A rollout form (active_rw; the _tl kernel serves only those) always
+// restarts a finished episode, so active_log_t[b] = 1 (the actor stepped) and ep_steps[b] = 0 say so, and nothing has to
+// be kept over the step, whose body sits on a register tier's edge.  The plain step may run without a restart: there the
+// slot an active actor commits is taken before the step, and that slot's terminal flag is read after it.
+template <class G, class R, bool TL>
+__device__ __forceinline__ void mix_step_actor(const ArcadeMixArgs& m, const ArcadeArgs& p, uint4* diff, int* s_act) {
+  const int b = blockIdx.x;
+  int slot = -1;                                // the slot of an active actor's plain step (-1: no statistics, or idle)
+  if constexpr (!TL) {
+    if (m.done_return && p.track_score && !p.active_rw && (p.active ? p.active[b] : 1)) slot = p.count[b] % p.H1;
+  }
+  step_actor<G, R, TL>(p, diff, s_act);
+  if constexpr (TL) {                           // (a rollout form: it tracks the score and has active_rw)
+    if (m.done_return && threadIdx.x == 0 && p.active_log_t[b] && p.ep_steps[b] == 0) {
+      m.done_return[b] += p.score_out[b];
+      m.done_episodes[b] += 1;
+    }
+  } else if (m.done_return && p.track_score && threadIdx.x == 0) {
+    const bool ended = p.active_rw ? p.active_log_t[b] && p.ep_steps[b] == 0
+                                   : slot >= 0 && p.r_terminal[(size_t)b * p.H1 + slot] != 0;
+    if (ended) {
+      m.done_return[b] += p.score_out[b];
+      m.done_episodes[b] += 1;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void arcade_mix_step_kernel(ArcadeMixArgs m) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act;
+  const ArcadeArgs p = mix_actor_args(m);
+  const int game = p.cfg[0];                    // (uniform per workgroup) a block of another game: this actor writes nothing
+  if (game == kArcadeBreakout) mix_step_actor<Game, Rules, false>(m, p, diff, &s_act);
+  else if (game == kArcadeDuel) mix_step_actor<DuelGame, DuelRules, false>(m, p, diff, &s_act);
+  else if (game == kArcadeInvaders) mix_step_actor<InvGame, InvRules, false>(m, p, diff, &s_act);
+}
+
+__global__ __launch_bounds__(256) void arcade_mix_step_tl_kernel(ArcadeMixArgs m) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act;
+  const ArcadeArgs p = mix_actor_args(m);
+  const int game = p.cfg[0];                    // (uniform per workgroup) as above
+  if (game == kArcadeBreakout) mix_step_actor<Game, Rules, true>(m, p, diff, &s_act);
+  else if (game == kArcadeDuel) mix_step_actor<DuelGame, DuelRules, true>(m, p, diff, &s_act);
+  else if (game == kArcadeInvaders) mix_step_actor<InvGame, InvRules, true>(m, p, diff, &s_act);
+}
+
+__global__ __launch_bounds__(256) void arcade_mix_reset_kernel(ArcadeMixArgs m) {
+  const ArcadeArgs p = mix_actor_args(m);
+  const int game = p.cfg[0];                    // (uniform per workgroup) as in the step
+  if (game == kArcadeBreakout) reset_actor<Game, Rules>(p);
+  else if (game == kArcadeDuel) reset_actor<DuelGame, DuelRules>(p);
+  else if (game == kArcadeInvaders) reset_actor<InvGame, InvRules>(p);
+}
+
 // ---- host side: one check and one launcher for the four entries -------------------------------------------------------
 enum ArcadeEntry { kReset, kStep, kRollout, kPolicy };
 
@@ -968,6 +1046,23 @@ int arcade_launch(ArcadeEntry e, ArcadeArgs& p, const int* cfg, int actor_base, 
   if (e == kReset) hipLaunchKernelGGL(arcade_reset_kernel, dim3(p.B), dim3(256), 0, s, p);
   else if (tl) hipLaunchKernelGGL(arcade_step_tl_kernel, dim3(p.B), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(arcade_step_kernel, dim3(p.B), dim3(256), 0, s, p);
+  return unreal_launch_status();
+}
+
+// the mixture's launcher: arcade_launch's tail and checks, then n_blocks in 1..16 and both statistics arrays or neither
+int arcade_mix_launch(ArcadeEntry e, ArcadeArgs& p, const int* cfg, int n_blocks, int actor_base, int* ep_steps, int* episode,
+                      int* records, float* done_return, int* done_episodes, void* stream, bool tl = false,
+                      uint8_t* final_obs = nullptr) {
+  p.cfg = cfg; p.actor_base = actor_base; p.ep_steps = ep_steps; p.episode = episode; p.records = records;
+  if (tl) p.final_obs = final_obs;
+  if (!arcade_args_ok(e, p)) return UNREAL_EINVAL;
+  if (tl && (!final_obs || ((uintptr_t)final_obs & 15) || (e != kRollout && e != kPolicy))) return UNREAL_EINVAL;
+  if (n_blocks < 1 || n_blocks > kMaxMixBlocks || !done_return != !done_episodes) return UNREAL_EINVAL;
+  const ArcadeMixArgs m{p, n_blocks, done_return, done_episodes};
+  hipStream_t s = (hipStream_t)stream;
+  if (e == kReset) hipLaunchKernelGGL(arcade_mix_reset_kernel, dim3(p.B), dim3(256), 0, s, m);
+  else if (tl) hipLaunchKernelGGL(arcade_mix_step_tl_kernel, dim3(p.B), dim3(256), 0, s, m);
+  else hipLaunchKernelGGL(arcade_mix_step_kernel, dim3(p.B), dim3(256), 0, s, m);
   return unreal_launch_status();
 }
 
@@ -1061,6 +1156,106 @@ int unreal_arcade_policy_rollout_step_tl(int B, int H1, const float* X, int ldx,
                active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
                Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
   return arcade_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, stream, true, final_obs);
+}
+
+// Game mixtures: the six entries above over `n_blocks` consecutive blocks, actor g on block g % n_blocks;
+// done_return / done_episodes [B] (both or neither): the per-actor sums of finished episodes' scores and their number.
+
+int unreal_arcade_mix_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
+                            const int* count, uint8_t* frames, const int* cfg, int n_blocks, int actor_base,
+                            int* ep_steps, int* episode, int* records, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, const_cast<int*>(count), frames};
+  p.mask = mask;
+  return arcade_mix_launch(kReset, p, cfg, n_blocks, actor_base, ep_steps, episode, records, nullptr, nullptr, stream);
+}
+
+int unreal_arcade_mix_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
+                           float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                           int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                           int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                           int reset_on_terminal, int track_score, const int* cfg, int n_blocks, int actor_base,
+                           int* ep_steps, int* episode, int* records, float* done_return, int* done_episodes,
+                           void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid,
+               reset_on_terminal, track_score};
+  return arcade_mix_launch(kStep, p, cfg, n_blocks, actor_base, ep_steps, episode, records, done_return, done_episodes,
+                           stream);
+}
+
+int unreal_arcade_mix_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                   int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                   int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                   int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                   int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                   float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                   int n_blocks, int actor_base, int* ep_steps, int* episode, int* records,
+                                   float* done_return, int* done_episodes, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
+  return arcade_mix_launch(kRollout, p, cfg, n_blocks, actor_base, ep_steps, episode, records, done_return,
+                           done_episodes, stream);
+}
+
+int unreal_arcade_mix_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                          const float* Wv, const float* bv, const double* u, float* pi_out,
+                                          float* v_out, int* actions_out, int* pos, int* last_action,
+                                          float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                          int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+                                          float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                                          float* score_out, int* score_valid, int* active, int* active_log_t,
+                                          int* n_steps, int* terminal_end, int* next_idx, float* next_lar, int lar_ld,
+                                          int lar_col0, int A, int idx_base_actor, const int* cfg, int n_blocks,
+                                          int actor_base, int* ep_steps, int* episode, int* records, float* done_return,
+                                          int* done_episodes, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
+               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
+  return arcade_mix_launch(kPolicy, p, cfg, n_blocks, actor_base, ep_steps, episode, records, done_return,
+                           done_episodes, stream);
+}
+
+int unreal_arcade_mix_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                      int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                      int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                      int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                      int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                      float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                                      const int* cfg, int n_blocks, int actor_base, int* ep_steps, int* episode,
+                                      int* records, uint8_t* final_obs, float* done_return, int* done_episodes,
+                                      void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
+  return arcade_mix_launch(kRollout, p, cfg, n_blocks, actor_base, ep_steps, episode, records, done_return,
+                           done_episodes, stream, true, final_obs);
+}
+
+int unreal_arcade_mix_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                             const float* Wv, const float* bv, const double* u, float* pi_out,
+                                             float* v_out, int* actions_out, int* pos, int* last_action,
+                                             float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                             int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+                                             float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                                             float* score_out, int* score_valid, int* active, int* active_log_t,
+                                             int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
+                                             int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                             int n_blocks, int actor_base, int* ep_steps, int* episode, int* records,
+                                             uint8_t* final_obs, float* done_return, int* done_episodes, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
+               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
+  return arcade_mix_launch(kPolicy, p, cfg, n_blocks, actor_base, ep_steps, episode, records, done_return,
+                           done_episodes, stream, true, final_obs);
 }
 
 }  // extern "C"

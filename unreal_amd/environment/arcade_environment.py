@@ -133,8 +133,49 @@ class ArcadeConfig(object):
         return (w & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
 
 
+class ArcadeMix(object):
+    """A game mixture (Environment.register_arcade_mix): an ordered list of 1..16 ArcadeConfigs ("tasks"),
+    different games or one game with different settings.  Global actor g plays task g % K for the whole run, by the
+    task's own rules (action_repeat, return_reward and max_episode_steps included); listing a task more than once gives
+    it more actors.  Raises ValueError for an empty list, more than 16 tasks or an item that is no ArcadeConfig."""
+    ACTION_SIZE = 4
+    MAX_TASKS = ops.ARCADE_MIX_MAX
+    game = "mix"
+
+    def __init__(self, tasks, names=None):
+        tasks = list(tasks)
+        if not 1 <= len(tasks) <= self.MAX_TASKS:
+            raise ValueError("a game mixture holds 1..%d tasks, not %d" % (self.MAX_TASKS, len(tasks)))
+        for t in tasks:
+            if not isinstance(t, ArcadeConfig):
+                raise ValueError("a task of a game mixture must be an ArcadeConfig, not %r" % (t,))
+        names = ["%d:%s" % (k, t.game) for k, t in enumerate(tasks)] if names is None else [str(n) for n in names]
+        if len(names) != len(tasks):
+            raise ValueError("%d names for %d tasks" % (len(names), len(tasks)))
+        self.tasks = tuple(tasks)
+        self.task_names = tuple(names)
+
+    @property
+    def action_size(self):
+        return self.ACTION_SIZE
+
+    def __len__(self):
+        return len(self.tasks)
+
+    def task_of(self, global_actor):
+        """Index of the task global actor `global_actor` plays (an integer or an integer array)."""
+        if np.any(np.asarray(global_actor) < 0):
+            raise ValueError("global actor %r < 0" % (global_actor,))
+        return global_actor % len(self.tasks)
+
+    def block(self, seed):
+        """The K consecutive blocks of the _mix entries: every task's own block(seed)."""
+        return np.concatenate([t.block(seed) for t in self.tasks])
+
+
 class BatchedArcadeEnvironment(object):
-    """B actors of one arcade game on the device, with the interface of BatchedMazeEnvironment."""
+    """B actors of one arcade game, or of a game mixture (ArcadeMix), on the device, with the interface of
+    BatchedMazeEnvironment."""
     ACTION_SIZE = 4
     frame_scale = 1.0 / 255.0          # ring bytes 0..255
     objective_size = 0
@@ -149,17 +190,19 @@ class BatchedArcadeEnvironment(object):
         if depth_labels:
             raise ValueError("depth_labels is out of scope for the arcade: a game has no wall distances (it needs a "
                              "first-person device maze)")
-        if not isinstance(config, ArcadeConfig):
-            raise ValueError("BatchedArcadeEnvironment needs an ArcadeConfig")
+        if not isinstance(config, (ArcadeConfig, ArcadeMix)):
+            raise ValueError("BatchedArcadeEnvironment needs an ArcadeConfig or an ArcadeMix")
         self.B = batch
         self.config = config
         total = batch if actors_total is None else int(actors_total)
         if actor_base < 0 or actor_base + batch > total:
             raise ValueError("actors [%d, %d) outside the %d actors of the job" % (actor_base, actor_base + batch, total))
+        mix = isinstance(config, ArcadeMix)
         self.ring = ops.Ring(batch, history_size, torch.device(device), arcade=True, final_obs=bool(final_obs),
-                             bonus=bool(bonus))
+                             bonus=bool(bonus), arcade_stats=mix)
         block = torch.from_numpy(config.block(seed)).to(self.ring.count.device)
-        self.arcade = (block, int(actor_base))
+        # a mixture: (K blocks, actor_base, K), which selects the _mix entries (ops._arcade_args)
+        self.arcade = (block, int(actor_base)) + ((len(config),) if mix else ())
         self.reset()
 
     def view(self, b0, b1):
@@ -169,8 +212,14 @@ class BatchedArcadeEnvironment(object):
         v.B, v.ring = b1 - b0, ops.ring_view(self.ring, b0, b1)
         v.base_actor = b0
         v.config = self.config
-        v.arcade = (self.arcade[0], self.arcade[1] + b0)
+        v.arcade = (self.arcade[0], self.arcade[1] + b0) + self.arcade[2:]
         return v
+
+    def task_of_actor(self):
+        """Index of the task every actor of this environment (or view) plays -> int [B]; zeros for a single game."""
+        if not isinstance(self.config, ArcadeMix):
+            return np.zeros(self.B, dtype=np.int64)
+        return self.config.task_of(self.arcade[1] + np.arange(self.B, dtype=np.int64))
 
     @staticmethod
     def get_action_size():
@@ -219,8 +268,14 @@ class ArcadeEnvironment(environment.Environment):
     def get_action_size():
         return 4
 
-    def __init__(self, device="cuda:0", config=None, seed=0):
+    def __init__(self, device="cuda:0", config=None, seed=0, task=0):
+        """`task`: of a game mixture (ArcadeMix), the task this one actor plays (a single game takes only 0)."""
         environment.Environment.__init__(self)
+        n_tasks = len(config) if isinstance(config, ArcadeMix) else 1
+        if isinstance(task, bool) or not isinstance(task, (int, np.integer)) or not 0 <= task < n_tasks:
+            raise ValueError("task = %r outside the %d task(s) of the config" % (task, n_tasks))
+        if isinstance(config, ArcadeMix):
+            config = config.tasks[task]
         self._env = BatchedArcadeEnvironment(1, 2, device, config=config, seed=seed)
         self._a = torch.zeros(1, dtype=torch.int32, device=device)
         self._r = torch.zeros(1, dtype=torch.float32, device=device)

@@ -113,6 +113,31 @@ class Environment(object):
                                                            march_period, descend, bomb_period, bomb_speed)
 
     @staticmethod
+    def register_arcade_mix(env_name, tasks):
+        """Game mixture of `env_name` on the device (env_type 'arcade'): `tasks` is a list of 1..16 items, each
+        the name of a registered arcade config or a dict of register_arcade_config's keywords.  Global actor g plays task
+        g % len(tasks) for the whole run, by that task's own rules; list a task more than once to give it more actors.
+        Raises KeyError for a name that is not registered and ValueError for a registered mixture's name, any other item
+        or a task count outside 1..16."""
+        from .arcade_environment import ArcadeConfig, ArcadeMix
+        if isinstance(tasks, (str, bytes, dict)) or not hasattr(tasks, "__iter__"):
+            raise ValueError("tasks must be a list of config names or dicts, not %r" % (tasks,))
+        confs, names = [], []
+        for k, t in enumerate(tasks):
+            if isinstance(t, str):
+                conf = Environment.arcade_config(t)
+                if not isinstance(conf, ArcadeConfig):
+                    raise ValueError("task %r is a mixture itself: a mixture lists single games" % t)
+                confs.append(conf)
+                names.append(t)
+            elif isinstance(t, dict):
+                confs.append(ArcadeConfig(**t))
+                names.append("%d:%s" % (k, confs[-1].game))
+            else:
+                raise ValueError("task %d must be a registered config's name or a dict of settings, not %r" % (k, t))
+        Environment.ARCADE_CONFIG[env_name] = ArcadeMix(confs, names)
+
+    @staticmethod
     def arcade_config(env_name):
         if env_name not in Environment.ARCADE_CONFIG:
             raise KeyError("arcade env %r: call Environment.register_arcade_config(name, ...) first" % env_name)

@@ -22,7 +22,10 @@ won, and the differences of the totals are `points_won_per_episode` and `points_
  success is a cleared wave, every other ending (last life, invasion, step limit) counts under `timeouts`, and the
 differences are `aliens_per_episode` and `lives_lost_per_episode` (an invasion counts the lives that were left).  On every game
 `mean_length` counts agent steps: with the config's `action_repeat = k` an episode of that length ran up to k
-game ticks per step."""
+game ticks per step.  With `arcade=` the name of a game mixture (Environment.register_arcade_mix) actor b plays
+task b mod K; the result keeps the overall keys over all counted episodes (`timeouts`: the sum of the tasks') and adds
+`tasks`, one dict per task with the keys and meanings of a single-game evaluation of that task's game, over the episodes of
+that task's actors (the duel's `losses` by the task's own `points`)."""
 import torch
 
 from . import ops
@@ -93,19 +96,46 @@ class Evaluate(object):
             ops.copy_(ws.h0, ws.h[:B * 256])
             ops.reset_state(B, self.terminals, ws.c0, ws.h0)
 
+    @staticmethod
+    def _arcade_result(conf, eps):
+        """The statistics of one game's counted episodes `eps`: (return, length, first total's gain, second total's gain,
+        won), in the order they ended."""
+        n = len(eps)
+        returns = [e[0] for e in eps]
+        bricks, lost = [e[2] for e in eps], [e[3] for e in eps]
+        successes = sum(int(e[4]) for e in eps)
+        mean = sum(returns) / n
+        res = dict(episodes=n, success_rate=successes / float(n), mean_return=mean,
+                   return_std=(sum((r - mean) ** 2 for r in returns) / n) ** 0.5,
+                   mean_length=sum(e[1] for e in eps) / float(n))
+        if conf.game == "duel":
+            # an episode starts at 0 : 0, so the opponent's score is the episode's points lost
+            losses = sum(int(not e[4] and e[3] >= conf.points) for e in eps)
+            res.update(timeouts=n - successes - losses, losses=losses, points_won_per_episode=sum(bricks) / float(n),
+                       points_lost_per_episode=sum(lost) / float(n))
+        elif conf.game == "invaders":
+            res.update(timeouts=n - successes, aliens_per_episode=sum(bricks) / float(n),
+                       lives_lost_per_episode=sum(lost) / float(n))
+        else:
+            res.update(timeouts=n - successes, bricks_per_episode=sum(bricks) / float(n),
+                       lives_lost_per_episode=sum(lost) / float(n))
+        return res
+
     def _process_arcade(self, n_episodes, one_episode_per_actor):
-        """The arcade's statistics: every episode ends in the environment (lives, wall or points, max_episode_steps)."""
+        """The arcade's statistics: every episode ends in the environment (lives, wall or points, max_episode_steps).  A
+        game mixture: the overall keys over every counted episode, and `tasks`: per task, what a single-game
+        evaluation of its game returns, over the episodes of the task's actors."""
         B, ring = self.B, self.env.ring
-        duel = self.arcade_config.game == "duel"
         # Breakout: bricks, lives lost, walls cleared; duel: points won, points lost, matches won; invaders: aliens shot,
         # lives lost, waves cleared.  Never zeroed.
         tot = ring.actor_records[:, 10:13]
         ep0 = tot.cpu().numpy().copy()
         steps, counted = [0] * B, [False] * B
-        returns, lengths, bricks, lost, successes, losses = [], [], [], [], 0, 0
+        eps, task_of_ep = [], []
+        task = self.env.task_of_actor()
         if one_episode_per_actor:
             n_episodes = B
-        while len(returns) < n_episodes:
+        while len(eps) < n_episodes:
             self._step()
             term = self.terminals.cpu().numpy()
             score = ring.score_out.cpu().numpy()
@@ -115,28 +145,23 @@ class Evaluate(object):
                 if not term[b]:
                     continue
                 if not (one_episode_per_actor and counted[b]):
-                    returns.append(float(score[b])); lengths.append(steps[b])
-                    bricks.append(int(now[b, 0] - ep0[b, 0])); lost.append(int(now[b, 1] - ep0[b, 1]))
-                    won = now[b, 2] - ep0[b, 2] > 0
-                    successes += int(won)
-                    # an episode starts at 0 : 0, so the opponent's score is the episode's points lost
-                    losses += int(duel and not won and lost[-1] >= self.arcade_config.points)
+                    eps.append((float(score[b]), steps[b], int(now[b, 0] - ep0[b, 0]), int(now[b, 1] - ep0[b, 1]),
+                                bool(now[b, 2] - ep0[b, 2] > 0)))
+                    task_of_ep.append(int(task[b]))
                 ep0[b] = now[b]
                 steps[b] = 0; counted[b] = True
-        n = len(returns)
+        if self.arcade_config.game != "mix":
+            return self._arcade_result(self.arcade_config, eps)
+        tasks = []
+        for k, conf in enumerate(self.arcade_config.tasks):
+            own = [e for e, t in zip(eps, task_of_ep) if t == k]
+            tasks.append(self._arcade_result(conf, own) if own else dict(episodes=0))   # (no episode: nothing to average)
+        n = len(eps)
+        returns = [e[0] for e in eps]
         mean = sum(returns) / n
-        res = dict(episodes=n, success_rate=successes / float(n), mean_return=mean,
-                   return_std=(sum((r - mean) ** 2 for r in returns) / n) ** 0.5, mean_length=sum(lengths) / float(n))
-        if duel:
-            res.update(timeouts=n - successes - losses, losses=losses, points_won_per_episode=sum(bricks) / float(n),
-                       points_lost_per_episode=sum(lost) / float(n))
-        elif self.arcade_config.game == "invaders":
-            res.update(timeouts=n - successes, aliens_per_episode=sum(bricks) / float(n),
-                       lives_lost_per_episode=sum(lost) / float(n))
-        else:
-            res.update(timeouts=n - successes, bricks_per_episode=sum(bricks) / float(n),
-                       lives_lost_per_episode=sum(lost) / float(n))
-        return res
+        return dict(episodes=n, success_rate=sum(int(e[4]) for e in eps) / float(n), mean_return=mean,
+                    return_std=(sum((r - mean) ** 2 for r in returns) / n) ** 0.5,
+                    mean_length=sum(e[1] for e in eps) / float(n), timeouts=sum(t.get("timeouts", 0) for t in tasks), tasks=tasks)
 
     def process(self, n_episodes, max_episode_steps=2000, one_episode_per_actor=False):
         """-> dict(episodes, success_rate, mean_return, return_std, mean_length, timeouts, goals_per_episode,

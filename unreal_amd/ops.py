@@ -98,7 +98,7 @@ class Ring(object):
     """Device replay ring + per-actor environment state (layout: include/unreal_hip.h)."""
 
     def __init__(self, B, H, device, objective_size=0, frame_shape=FRAME_SHAPE, maze_state=False, nav=False, gen=0,
-                 gen_styled=False, sense=0, arcade=False, final_obs=False, depth=False, bonus=False):
+                 gen_styled=False, sense=0, arcade=False, final_obs=False, depth=False, bonus=False, arcade_stats=False):
         self.B, self.H, self.H1 = B, H, H + 1
         self.objective_size = objective_size
         self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
@@ -167,6 +167,12 @@ class Ring(object):
         if arcade:
             self.ep_steps = z(B, dt=torch.int32)
             self.episode = torch.full((B,), -1, dtype=torch.int32, device=device)
+        # game mixtures: per actor, the sum of its finished episodes' scores and their number, allocated only
+        # when asked (the _mix entries add to them where an episode ends)
+        if arcade_stats and not arcade:
+            raise ValueError("per-task statistics are the device arcade's (Ring(arcade=True, arcade_stats=True))")
+        self.done_return = z(B) if arcade_stats else None
+        self.done_episodes = z(B, dt=torch.int32) if arcade_stats else None
 
         self._cur = z(B, dt=torch.int32)
 
@@ -230,6 +236,9 @@ def ring_view(ring, b0, b1):
     v.gen = gen[b0 * v.gen_words:b1 * v.gen_words] if gen is not None else None
     arcade = getattr(ring, "arcade", None)
     v.arcade = arcade[b0 * ARCADE_RECORD:b1 * ARCADE_RECORD] if arcade is not None else None
+    for name in ("done_return", "done_episodes"):
+        t = getattr(ring, name, None)
+        setattr(v, name, t[b0:b1] if t is not None else None)
     # the view's actors' final-observation slots; their indices are the parent's: final_base + (b0 + b)
     fin = getattr(ring, "final_obs", None)
     v.final_base = getattr(ring, "final_base", ring.B * H1)
@@ -242,6 +251,7 @@ ARCADE_DUEL = 3                              # UNREAL_ARCADE_DUEL (2 is no game:
 ARCADE_INVADERS = 5                          # UNREAL_ARCADE_INVADERS
 ARCADE_BOMB_STREAM = 0x494E5642              # counter word 2 of an invaders bomb draw (UNREAL_ARCADE_BOMB_STREAM)
 ARCADE_SERVE_STREAM = 0x41524B53             # counter word 2 of a serve draw (UNREAL_ARCADE_SERVE_STREAM)
+ARCADE_MIX_MAX = 16                          # config blocks of a game mixture at the most (UNREAL_ARCADE_MIX_MAX)
 MAZE_TOP_DOWN, MAZE_FIRST_PERSON = 0, 1       # the `view` of a maze (UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON)
 MAZE_FIRST_PERSON_GENERATED = 2               # first person, a generated block (UNREAL_MAZE_FIRST_PERSON_GENERATED)
 # goal-sense blocks: UNREAL_MAZE_FIRST_PERSON_SENSE / UNREAL_MAZE_FIRST_PERSON_GENERATED_SENSE
@@ -466,24 +476,44 @@ def maze_policy_rollout_step_encode(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_o
 
 
 # ---- device arcade (csrc/arcade.hip) -----------------------------------------------------------------------
-def _arcade_args(ring, arcade):
-    """The tail of every arcade entry.  `arcade` = (int32 config block on the device, global index of the ring's actor 0)."""
-    block, actor_base = arcade
-    _chk(block, "i32", ARCADE_CFG_WORDS, "arcade config")
+def _arcade_args(ring, arcade, stats=True):
+    """-> ("" or "_mix", the tail of the arcade entry of that name, the arguments behind its `records` and final_obs).
+    `arcade` = (int32 config block on the device, global index of the ring's actor 0), which selects the plain entries, or
+    (K consecutive blocks, that index, K), a game mixture, which selects the _mix entries: global actor g
+    plays block g % K, and the step forms (`stats`) also take the ring's done_return / done_episodes (None without
+    Ring(arcade_stats=True))."""
+    K = None
+    if len(arcade) == 3:
+        block, actor_base, K = arcade
+        K = int(K)
+        if not 1 <= K <= ARCADE_MIX_MAX:
+            raise ValueError("a game mixture holds 1..%d config blocks, not %d" % (ARCADE_MIX_MAX, K))
+    else:
+        block, actor_base = arcade
+    _chk(block, "i32", ARCADE_CFG_WORDS * (K or 1), "arcade config")
     if getattr(ring, "arcade", None) is None:
         raise ValueError("an arcade environment needs a ring with game records (Ring(arcade=True))")
     for name, n in (("ep_steps", ring.B), ("episode", ring.B), ("arcade", ARCADE_RECORD * ring.B)):
         _chk(getattr(ring, name), "i32", n, "ring." + name)
     if actor_base < 0:
         raise ValueError("actor_base %d < 0" % actor_base)
-    return (ptr(block), int(actor_base), ptr(ring.ep_steps), ptr(ring.episode), ptr(ring.arcade))
+    tail = (int(actor_base), ptr(ring.ep_steps), ptr(ring.episode), ptr(ring.arcade))
+    if K is None:
+        return "", (ptr(block),) + tail, ()
+    done_return, done_episodes = getattr(ring, "done_return", None), getattr(ring, "done_episodes", None)
+    if (done_return is None) != (done_episodes is None):
+        raise ValueError("ring.done_return and ring.done_episodes go together")
+    _chk(done_return, "f32", ring.B, "ring.done_return", optional=True)
+    _chk(done_episodes, "i32", ring.B, "ring.done_episodes", optional=True)
+    return "_mix", (ptr(block), K) + tail, ((ptr(done_return), ptr(done_episodes)) if stats else ())
 
 
 def arcade_reset(ring, mask=None, arcade=None):
     """Start a new episode of every actor (where mask != 0)."""
     _chk(mask, "i32", ring.B, "mask", optional=True)
-    _call("unreal_arcade_reset", ring.B, ring.H1, ptr(mask), ptr(ring.pos), ptr(ring.last_action), ptr(ring.last_reward),
-          ptr(ring.count), ptr(ring.frames), *_arcade_args(ring, arcade))
+    mix, tail, _ = _arcade_args(ring, arcade, stats=False)
+    _call("unreal_arcade%s_reset" % mix, ring.B, ring.H1, ptr(mask), ptr(ring.pos), ptr(ring.last_action),
+          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), *tail)
 
 
 def arcade_step(ring, actions, active=None, out_reward=None, out_terminal=None, reset_on_terminal=True,
@@ -493,8 +523,9 @@ def arcade_step(ring, actions, active=None, out_reward=None, out_terminal=None, 
     _chk(active, "i32", B, "active", optional=True)
     _chk(out_reward, "f32", B, "out_reward", optional=True)
     _chk(out_terminal, "i32", B, "out_terminal", optional=True)
-    _call("unreal_arcade_step", B, ring.H1, ptr(actions), ptr(active), *_ring_args(ring, out_reward, out_terminal),
-          int(reset_on_terminal), int(track_score), *_arcade_args(ring, arcade))
+    mix, tail, done = _arcade_args(ring, arcade)
+    _call("unreal_arcade%s_step" % mix, B, ring.H1, ptr(actions), ptr(active), *_ring_args(ring, out_reward, out_terminal),
+          int(reset_on_terminal), int(track_score), *tail, *done)
 
 
 def _arcade_actions(A):
@@ -510,9 +541,10 @@ def arcade_rollout_step(ring, actions, out_reward, out_terminal, active, active_
     _arcade_actions(A)
     _chk(actions, "i32", ring.B, "actions")
     tl, fin = _final_obs_args(ring, final_obs)
-    _call("unreal_arcade_rollout_step" + tl, ring.B, ring.H1, ptr(actions),
+    mix, tail, done = _arcade_args(ring, arcade)
+    _call("unreal_arcade%s_rollout_step%s" % (mix, tl), ring.B, ring.H1, ptr(actions),
           *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
-                         lar_ld, lar_col0, A, base_actor), *_arcade_args(ring, arcade), *fin)
+                         lar_ld, lar_col0, A, base_actor), *tail, *fin, *done)
 
 
 def arcade_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions, out_reward, out_terminal, active,
@@ -525,10 +557,11 @@ def arcade_policy_rollout_step(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, a
     _chk(X, "f32", (B - 1) * ldx + 256, "X"); _chk(Wp, "f32", 256 * A); _chk(bp, "f32", A); _chk(Wv, "f32", 256)
     _chk(bv, "f32", 1); _chk(u, "f64", B, "u"); _chk(pi_out, "f32", B * A); _chk(v_out, "f32", B)
     _chk(actions, "i32", B, "actions")
-    _call("unreal_arcade_policy_rollout_step" + tl, B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv), ptr(bv), ptr(u),
-          ptr(pi_out), ptr(v_out), ptr(actions),
+    mix, tail, done = _arcade_args(ring, arcade)
+    _call("unreal_arcade%s_policy_rollout_step%s" % (mix, tl), B, ring.H1, ptr(X), int(ldx), ptr(Wp), ptr(bp), ptr(Wv),
+          ptr(bv), ptr(u), ptr(pi_out), ptr(v_out), ptr(actions),
           *_rollout_args(ring, out_reward, out_terminal, active, active_log_t, n_steps, terminal_end, next_idx, next_lar,
-                         lar_ld, lar_col0, A, base_actor), *_arcade_args(ring, arcade), *fin)
+                         lar_ld, lar_col0, A, base_actor), *tail, *fin, *done)
 
 
 def maze_objective(ring, next_lar=None, lar_ld=0, lar_col0=0):

@@ -541,6 +541,27 @@ class Trainer(PassState):
     def set_start_time(self, start_time):
         self.start_time = start_time
 
+    def task_scores(self, reset=True):
+        """Per-task scores of a game mixture (Environment.register_arcade_mix) since the last reset -> a list
+        of dict(name, game, episodes, mean_return), one per task, over the episodes this rank's actors finished
+        (mean_return None where a task finished none).  One device read of the ring's per-actor accumulators, summed by
+        the actors' tasks on the host; `reset` zeroes them.  ValueError for anything but a mixture."""
+        env = self.full_environment if self.environment is not None else None
+        ring = env.ring if env is not None else None
+        if ring is None or getattr(ring, "done_return", None) is None:
+            raise ValueError("task_scores needs a prepared trainer on a game mixture (Environment.register_arcade_mix)")
+        acc = torch.stack((ring.done_return.double(), ring.done_episodes.double())).cpu().numpy()
+        if reset:
+            ring.done_return.zero_()
+            ring.done_episodes.zero_()
+        task = env.task_of_actor()
+        out = []
+        for k, (name, conf) in enumerate(zip(env.config.task_names, env.config.tasks)):
+            n = int(acc[1, task == k].sum())
+            out.append(dict(name=name, game=conf.game, episodes=n,
+                            mean_return=float(acc[0, task == k].sum()) / n if n else None))
+        return out
+
     def _anneal_learning_rate(self, global_time_step):
         lr = self.initial_learning_rate * (self.max_global_time_step - global_time_step) / self.max_global_time_step
         return max(lr, 0.0)
