@@ -72,10 +72,40 @@ typedef _Float16 fh2p __attribute__((ext_vector_type(2)));
 typedef float f32x2p __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2p __attribute__((ext_vector_type(2)));
 
-constexpr int HPP_ROW = 80;                        // bytes per hp row in a plane: 32 ci + 16 B pad
-constexpr int HPP_PLANE = HP_ROWS * HPP_ROW;       // 6720
-constexpr int WDP_ROW = 80;                        // bytes per (tap, column) weight row: 32 ci + pad
-constexpr int WDP_PLANE = 4 * 32 * WDP_ROW;        // [dd(4)][n(32)] rows = 10240
+// LDS layouts of the packed path.  Bank rule (64 dword banks = one 256-byte window): a 16-byte fragment read is served in
+// four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 -- so a group holds all 16
+// values of i = lane & 15, the middle eight at the NEXT k chunk q = lane >> 4; 8-byte and transposed reads are served per
+// 32-lane half.  tests/test_pc_lds_layout_cpu.py restates every instruction of the frame loop under this rule.
+//   hp and weight planes: dense 64-byte rows (32 ci fp16), the two 32-byte halves of a row exchanged by a bit of the row
+//   index.  Rows i, i+4, i+8, i+12 of a group share a 64-byte quarter of the window; their chunks are q, q+1, q+1, q, so
+//   exchanging the halves of the rows with bit 3 set (weights: row = i) makes the four distinct.  The hp rows are gathered
+//   by position, not by i, and are also read transposed (4 consecutive rows per 16 lanes, rows 8 apart per half-wave):
+//   bit 2 ^ bit 3 serves both (transposed reads, the 8-byte plane stores and the 2-byte mask reads conflict-free; the
+//   gathered fragment reads keep the conflicts of the 10-to-9 column wrap and the padding row).
+//   d_dec planes: 16 bytes per output position, 25 positions per output row instead of 20: the dgrad fragment of lane
+//   (i, q) is position (2y + ky, 2x + q), and 2 * 25 = 2 (mod 16) turns that into chunk 2 (x + y) + q of the window.
+constexpr int HPP_ROW = 64;                        // bytes per hp row in a plane: 32 ci
+constexpr int HPP_PLANE = HP_ROWS * HPP_ROW;       // 5376
+constexpr int WDP_ROW = 64;                        // bytes per (tap, column) weight row: 32 ci
+constexpr int WDP_PLANE = 4 * 32 * WDP_ROW;        // [dd(4)][n(32)] rows = 8192
+// byte b (< 64) of row `row`: hp planes / weight planes
+__device__ __forceinline__ int hpp_off(int row, int b) { return row * HPP_ROW + (b ^ ((((row >> 2) ^ (row >> 3)) & 1) << 5)); }
+__device__ __forceinline__ int wrow_off(int row, int b) { return row * WDP_ROW + (b ^ (((row >> 3) & 1) << 5)); }
+
+#define LO16(x) ((x) & 0xffffu)
+#define HI16(x) ((x) >> 16)
+// keeps a loop-invariant table register from being unpacked outside the frame loop (which would double the tables)
+#define PIN(x) asm volatile("" : "+v"(x))
+// n x { 1 MFMA, NV VALU, ND LDS operations } in program order: the next step's fragment requests (and a finished tile's
+// epilogue) issue in the shadow of this step's MFMAs instead of in a block of their own
+template <int N, int NV, int ND> __device__ __forceinline__ void pc_interleave() {
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x002, NV, 0);
+    __builtin_amdgcn_sched_group_barrier(0x080, ND, 0);
+  }
+}
 
 // 4 fp32 -> hi / lo planes of 4 fp16 each: x * scale = hi + lo (round to nearest; 22 significant bits + lo's sign)
 __device__ __forceinline__ void split4p(const f32x4& v, float scale, u32x2p (&pl)[NPLP]) {
@@ -99,7 +129,7 @@ __device__ __forceinline__ void hp_store_planes(unsigned char* hpp, int gtid, co
       pl[0][0] = keep_positive_visible(pl[0][0], r[c][0], r[c][1]);
       pl[0][1] = keep_positive_visible(pl[0][1], r[c][2], r[c][3]);
 #pragma unroll
-      for (int t = 0; t < NPLP; ++t) *reinterpret_cast<u32x2p*>(hpp + t * HPP_PLANE + (id >> 3) * HPP_ROW + (id & 7) * 8) = pl[t];
+      for (int t = 0; t < NPLP; ++t) *reinterpret_cast<u32x2p*>(hpp + t * HPP_PLANE + hpp_off(id >> 3, (id & 7) * 8)) = pl[t];
     }
   }
 }
@@ -142,7 +172,7 @@ __device__ __forceinline__ void pc_fwd_weight_planes(const float* __restrict__ W
     u32x2p pl[NPLP];
     split4p(v, S_W, pl);
 #pragma unroll
-    for (int t = 0; t < NPLP; ++t) *reinterpret_cast<u32x2p*>(wdp + t * WDP_PLANE + (dd * 32 + n) * WDP_ROW + c4 * 8) = pl[t];
+    for (int t = 0; t < NPLP; ++t) *reinterpret_cast<u32x2p*>(wdp + t * WDP_PLANE + wrow_off(dd * 32 + n, c4 * 8)) = pl[t];
   }
 }
 
@@ -156,76 +186,124 @@ __device__ __forceinline__ void pc_zero_hp_pad_rows(unsigned char* hpp) {
 
 // LDS of the forward kernel for CO = 1 + A output channels: hp planes | dec | dout | weight planes.  dec holds the
 // pre-activations [400][DS] with an ODD row stride DS >= CO (a thread reads one position's CO floats: odd strides are
-// conflict-free), dout the frame's d_dec [400][CO] dense (it leaves in 16-byte pieces).  At CO <= 7 the workgroup needs
-// <= 53 KB: THREE workgroups per CU (round 2: 76 KB with three bf16 planes and stride-8 rows, two per CU, 55 % of the
-// wave cycles waiting).
+// conflict-free) and 32 dump words behind them, dout the frame's d_dec [400][CO] dense (it leaves in 16-byte pieces).
+// At COT <= 5 the workgroup needs 43 KB: THREE workgroups per CU; two at COT = 7 and 8 (as before the dense rows, when
+// three did not fit them).
+constexpr int DEC_DUMP = 32 * 4;                   // behind dec: one dump word per lane & 31 (the padding lanes' stores)
 template <int COT> struct FwdLds {
   static constexpr int DS = COT | 1;
-  static constexpr int DEC = NPLP * HPP_PLANE, DOUT = DEC + PC_CELLS * DS * 4, W = DOUT + PC_CELLS * COT * 4,
+  static constexpr int DEC = NPLP * HPP_PLANE, DOUT = DEC + PC_CELLS * DS * 4 + DEC_DUMP, W = DOUT + PC_CELLS * COT * 4,
                        BYTES = W + NPLP * WDP_PLANE;
-  static constexpr int WGS = 3 * BYTES <= 160 * 1024 ? 3 : 2;
+  static constexpr int WGS = COT <= 5 ? 3 : 2;
+  static_assert(WGS * (BYTES + 64) <= 160 * 1024, "the forward workgroups of one CU must fit its LDS");
 };
 
-// deconv of the wave's position tiles (tile ids mt0 and mt0 + 4 when < 7) for ALL parities and channels:
-// column n = par * CO + co (n < 4 * CO <= 32, two 16-wide column tiles); pre-activations + bias -> dec
-template <bool TWO_NT, int DS>
-__device__ __forceinline__ void deconv_packed(const unsigned char* hpp, const unsigned char* wdp, float* dec, int mt0, int i,
-                                              int q, int CO, const float (&bias)[2], float unscale) {
-  constexpr int NTL = TWO_NT ? 2 : 1;
-  const int ntiles = (mt0 + 4 < 7) ? 2 : 1;              // wave-uniform
-  f32x4 acc[2][NTL];
-  int a[2], b[2];
+// Per-lane LDS offsets of the forward deconvolution, built once per kernel: two 16-bit region-relative byte offsets per
+// register.  The frame loop adds an entry to a base and nothing else.
+struct PcFwdTab {
+  uint32_t a[4];            // [dd]  lo / hi: hp row of tap dd for this lane's position in tile mt0 / mt0 + 4 (hp-plane relative)
+  uint32_t w;               // this lane's place in a 16-row weight block (weight-plane relative)
+  uint32_t dst[2][2][2];    // [t][nt][r >> 1]  lo / hi: dec word of accumulator element r even / odd; columns >= 4 CO and
+                            // positions >= 100 point at the lane's dump word
+};
+
+template <int DS>
+__device__ __forceinline__ void pc_fwd_tab_build(PcFwdTab& T, int mt0, int lane, int CO) {
+  const int i = lane & 15, q = lane >> 4;
+  uint32_t o[4][2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-#pragma unroll
-    for (int nt = 0; nt < NTL; ++nt) acc[t][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int m = min((mt0 + 4 * t) * 16 + i, 99);
-    a[t] = m / 10;
-    b[t] = m % 10;
+    const int a = m / 10, b = m % 10;
+#pragma unroll
+    for (int dd = 0; dd < 4; ++dd) {
+      const int y = a - (dd >> 1), x = b - (dd & 1);
+      const int row = (y >= 0 && y < 9 && x >= 0 && x < 9) ? y * 9 + x : C2_POS;
+      o[dd][t] = hpp_off(row, 16 * q);
+    }
   }
 #pragma unroll
-  for (int dd = 0; dd < 4; ++dd) {
-    const int da = dd >> 1, db = dd & 1;
-    fh8p bw[NTL][NPLP];
+  for (int dd = 0; dd < 4; ++dd) T.a[dd] = o[dd][0] | (o[dd][1] << 16);
+  T.w = wrow_off(i, 16 * q);
+  const uint32_t dump = PC_CELLS * DS * 4 + (lane & 31) * 4;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      const int n = nt * 16 + i;
+      const int par = n / CO, co = n - par * CO;
+      uint32_t d[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = (mt0 + 4 * t) * 16 + 4 * q + r;
+        d[r] = (n < 4 * CO && m < 100) ? (uint32_t)(((2 * (m / 10) + (par >> 1)) * 20 + 2 * (m % 10) + (par & 1)) * DS + co) * 4 : dump;
+      }
+      T.dst[t][nt][0] = d[0] | (d[1] << 16);
+      T.dst[t][nt][1] = d[2] | (d[3] << 16);
+    }
+}
+
+// deconv of the wave's position tiles (tile ids mt0 and mt0 + 4 when < 7) for ALL parities and channels:
+// column n = par * CO + co (n < 4 * CO <= 32, two 16-wide column tiles); pre-activations + bias -> dec.
+// NTILES: 2 for the waves that own tiles mt0 and mt0 + 4, 1 for the wave whose second tile would be the 8th.  Steps = taps;
+// the fragments of tap dd + 1 are requested before the MFMAs of tap dd; the stores are branch-free (dump words).
+template <bool TWO_NT, int NTILES>
+__device__ __forceinline__ void deconv_packed(const unsigned char* hpp, const unsigned char* wdp, float* dec, PcFwdTab& T,
+                                              const float (&bias)[2], float unscale) {
+  constexpr int NTL = TWO_NT ? 2 : 1;
+  f32x4 acc[NTILES][NTL];
+#pragma unroll
+  for (int t = 0; t < NTILES; ++t)
+#pragma unroll
+    for (int nt = 0; nt < NTL; ++nt) acc[t][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  fh8p bw[2][NTL][NPLP], av[2][NTILES][NPLP];      // fragments of tap dd, by parity of dd
+  PIN(T.w);
+  auto load = [&](int dd) {
+    PIN(T.a[dd]);
 #pragma unroll
     for (int nt = 0; nt < NTL; ++nt)
 #pragma unroll
       for (int pl = 0; pl < NPLP; ++pl)
-        bw[nt][pl] = *reinterpret_cast<const fh8p*>(wdp + pl * WDP_PLANE + ((dd * 32 + nt * 16 + i)) * WDP_ROW + 16 * q);
+        bw[dd & 1][nt][pl] = *reinterpret_cast<const fh8p*>(wdp + pl * WDP_PLANE + (dd * 32 + nt * 16) * WDP_ROW + T.w);
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      if (t < ntiles) {
-        const int y = a[t] - da, x = b[t] - db;
-        const int row = (y >= 0 && y < 9 && x >= 0 && x < 9) ? y * 9 + x : C2_POS;
-        fh8p av[NPLP];
+    for (int t = 0; t < NTILES; ++t) {
+      const unsigned char* ap = hpp + (t ? HI16(T.a[dd]) : LO16(T.a[dd]));
 #pragma unroll
-        for (int pl = 0; pl < NPLP; ++pl)
-          av[pl] = *reinterpret_cast<const fh8p*>(hpp + pl * HPP_PLANE + row * HPP_ROW + 16 * q);
+      for (int pl = 0; pl < NPLP; ++pl) av[dd & 1][t][pl] = *reinterpret_cast<const fh8p*>(ap + pl * HPP_PLANE);
+    }
+  };
+  load(0);
 #pragma unroll
-        for (int nt = 0; nt < NTL; ++nt) PC_SPLIT_MMA(av, bw[nt], acc[t][nt]);
+  for (int dd = 0; dd < 4; ++dd) {
+    if (dd + 1 < 4) load(dd + 1);
+#pragma unroll
+    for (int t = 0; t < NTILES; ++t)
+#pragma unroll
+      for (int nt = 0; nt < NTL; ++nt) PC_SPLIT_MMA(av[dd & 1][t], bw[dd & 1][nt], acc[t][nt]);
+    pc_interleave<3 * NTILES * NTL, 1, 1>();
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int t = 0; t < NTILES; ++t)
+#pragma unroll
+    for (int nt = 0; nt < NTL; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (!(r & 1)) PIN(T.dst[t][nt][r >> 1]);
+        const uint32_t o = (r & 1) ? HI16(T.dst[t][nt][r >> 1]) : LO16(T.dst[t][nt][r >> 1]);
+        *reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(dec) + o) = acc[t][nt][r] * unscale + bias[nt];
       }
-    }
-  }
-#pragma unroll
-  for (int nt = 0; nt < NTL; ++nt) {
-    const int n = nt * 16 + i;
-    if (n < 4 * CO) {
-      const int par = n / CO, co = n - par * CO;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-        if (t < ntiles) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int m = (mt0 + 4 * t) * 16 + 4 * q + r;
-            if (m < 100)
-              dec[((2 * (m / 10) + (par >> 1)) * 20 + 2 * (m % 10) + (par & 1)) * DS + co] = acc[t][nt][r] * unscale + bias[nt];
-          }
-        }
-    }
-  }
 }
 
-// One frame per 256-thread workgroup at a time, THREE independent workgroups per CU at CO <= 7 (two at CO = 8): one's
+// the wave's share of one frame's deconvolution: waves 0..2 own two position tiles, wave 3 one
+template <bool TWO_NT>
+__device__ __forceinline__ void deconv_packed_wave(const unsigned char* hpp, const unsigned char* wdp, float* dec, PcFwdTab& T,
+                                                   int gw, const float (&bias)[2], float unscale) {
+  if (gw + 4 < 7) deconv_packed<TWO_NT, 2>(hpp, wdp, dec, T, bias, unscale);
+  else deconv_packed<TWO_NT, 1>(hpp, wdp, dec, T, bias, unscale);
+}
+
+// One frame per 256-thread workgroup at a time, THREE independent workgroups per CU at COT <= 5 (two at COT = 7, 8): one's
 // dueling / loss VALU phase and its global traffic overlap the others' MFMAs.  COT = 1 + A (8: any A <= 7).
 template <int COT>
 __global__ __launch_bounds__(256, FwdLds<COT>::WGS) void pc_deconv_fwd_kernel(PcFwdArgs p) {
@@ -234,13 +312,13 @@ __global__ __launch_bounds__(256, FwdLds<COT>::WGS) void pc_deconv_fwd_kernel(Pc
   __shared__ __attribute__((aligned(16))) unsigned char smem[L::BYTES];
   __shared__ float s_red;
   const int gtid = threadIdx.x;
-  const int lane = threadIdx.x & 63, gw = gtid >> 6;
-  const int i = lane & 15, q = lane >> 4;
+  const int lane = threadIdx.x & 63, gw = __builtin_amdgcn_readfirstlane(gtid >> 6);
+  const int i = lane & 15;
   unsigned char* hpp = smem;
   float* dec = reinterpret_cast<float*>(smem + L::DEC);
   float* dout = reinterpret_cast<float*>(smem + L::DOUT);      // staged d_dec of the frame: [400][CO] dense
   unsigned char* wdp = smem + L::W;
-  const int A = p.A, CO = 1 + p.A;
+  const int A = COT < 8 ? COT - 1 : p.A, CO = 1 + A;      // COT = 4, 5, 7: exactly 1 + A (the launcher's dispatch)
 
   // power-of-two scales (exact): hp from its producer's absmax slot, the weights' maximum reduced here
   const float S_W = pow2_scale(pc_weight_max(p.Wv, p.Wa, A, &s_red));
@@ -256,7 +334,11 @@ __global__ __launch_bounds__(256, FwdLds<COT>::WGS) void pc_deconv_fwd_kernel(Pc
     const int co = n % CO;
     bias[nt] = (n < 4 * CO) ? (co == 0 ? p.bv[0] : p.ba[co - 1]) : 0.f;
   }
-  const bool two_nt = 4 * CO > 16;
+  // the second 16-column tile: needed from 5 channels on; COT = 8 always computes it (at 1 + A <= 4 its columns are all
+  // padding and go to the dump words)
+  constexpr bool TWO_NT = 4 * COT > 16;
+  PcFwdTab T;
+  pc_fwd_tab_build<DS>(T, gw, lane, CO);
   float loss_acc = 0.f, dd_max = 0.f;
 
   const int stride = gridDim.x;
@@ -291,8 +373,7 @@ __global__ __launch_bounds__(256, FwdLds<COT>::WGS) void pc_deconv_fwd_kernel(Pc
       on = p.mask[n] != 0;
     }
     if (valid) {
-      if (two_nt) deconv_packed<true, DS>(hpp, wdp, dec, gw, i, q, CO, bias, unscale);
-      else deconv_packed<false, DS>(hpp, wdp, dec, gw, i, q, CO, bias, unscale);
+      deconv_packed_wave<TWO_NT>(hpp, wdp, dec, T, gw, bias, unscale);
     }
     __syncthreads();  // [S1] dec complete; hp free; dout drained
     if (valid) {
@@ -370,9 +451,12 @@ struct PcBwdArgs {
 typedef short s16x4p __attribute__((ext_vector_type(4)));
 typedef short s16x8p __attribute__((ext_vector_type(8)));
 constexpr int DDP_ROW = 16;                          // bytes per output position in a d_dec plane (8 co bf16)
-constexpr int DDP_PLANE = (PC_CELLS + 4) * DDP_ROW;  // + 4 zero rows (positions past the 81 of the last k step)
-constexpr int WBP_PLANE = 4 * 32 * WDP_ROW;          // [ky][ci(32)] rows of 32 (kx,co) bf16 + pad = 10240
-constexpr int BWD_GRP_BYTES = NPLP * HPP_PLANE + NPLP * DDP_PLANE + F2_DIM * 4;   // hp planes | d_dec planes | d_hp staging
+constexpr int DDP_PITCH = 25;                        // positions per output row (20 + 5 never touched: see the bank rule above)
+constexpr int DDP_ZERO = 20 * DDP_PITCH;             // 4 zero rows (positions past the 81 of the last k step), then a dump row
+constexpr int DDP_PLANE = (DDP_ZERO + 5) * DDP_ROW;  // 8080
+constexpr int WBP_PLANE = 4 * 32 * WDP_ROW;          // [ky][ci(32)] rows of 32 (kx,co) bf16 = 8192
+constexpr int DHS_BYTES = (C2_POS + 4) * 128;        // d_hp staging [81][32] fp32 + 4 dump rows (the last tile's padding positions)
+constexpr int BWD_GRP_BYTES = NPLP * HPP_PLANE + NPLP * DDP_PLANE + DHS_BYTES;   // hp planes | d_dec planes | d_hp staging
 
 __device__ __forceinline__ fh8p tr_pair_p(const unsigned char* a0, const unsigned char* a1) {
   typedef s16x4p __attribute__((address_space(3))) * lds_p;
@@ -404,100 +488,164 @@ __device__ __forceinline__ void pc_bwd_weight_planes(const float* __restrict__ W
     split1p(v, S_W, t);
 #pragma unroll
     for (int pl = 0; pl < NPLP; ++pl)
-      reinterpret_cast<unsigned short*>(wbp + pl * WBP_PLANE + (ky * 32 + ci) * WDP_ROW)[k] = t[pl];
+      *reinterpret_cast<unsigned short*>(wbp + pl * WBP_PLANE + wrow_off(ky * 32 + ci, 2 * k)) = t[pl];
+  }
+}
+
+// Per-lane LDS offsets of the backward phases, built once per kernel (two 16-bit region-relative byte offsets per register)
+struct PcBwdTab {
+  uint32_t st;          // staging: lo / hi: d_dec rows of output positions gtid / gtid + 256 (>= 400: the dump row)
+  uint32_t da[2];       // dgrad: d_dec fragment of tap row ky = 0 for tiles jj = 0 | 1, 2 (ky: + ky pitch rows, an immediate)
+  uint32_t dw;          // dgrad: this lane's place in the [ci] weight block of its channel half
+  uint32_t de[3];       // dgrad epilogue [jj]: lo: hp row of element r = 0 (ReLU mask; r: + r rows), hi: its d_hp staging word.
+                        // Tiles past position 80 read the zero rows and write the dump rows.
+  uint32_t wb[3][2];    // wgrad [ks][t]: lo / hi: transposed hp blocks of positions p0.. / p0 + 4.. (p >= 81: a zero row)
+  uint32_t wa[3];       // wgrad [ks]: lo / hi: d_dec block rows of the same positions for kxh = 0 (kxh: + 2 rows)
+};
+
+__device__ __forceinline__ int ddp_row(int pos) { return (pos / 20) * DDP_PITCH + pos % 20; }
+
+__device__ __forceinline__ void pc_bwd_tab_build(PcBwdTab& T, int gtid, int gw) {
+  const int lane = gtid & 63, i = lane & 15, q = lane >> 4, nt = gw & 1;
+  const int qq = i >> 2, pp = i & 3;             // transposed reads: lane (4qq + pp) of a 16-lane group addresses block row qq
+  {
+    const uint32_t s0 = ddp_row(gtid) * DDP_ROW;
+    const uint32_t s1 = (gtid + 256 < PC_CELLS ? ddp_row(gtid + 256) : DDP_ZERO + 4) * DDP_ROW;
+    T.st = s0 | (s1 << 16);
+  }
+  uint32_t ab[3];
+#pragma unroll
+  for (int jj = 0; jj < 3; ++jj) {
+    const int tile = (gw >> 1) + 2 * jj;
+    const int pos = min(tile * 16 + i, C2_POS - 1);
+    ab[jj] = ((2 * (pos / 9)) * DDP_PITCH + 2 * (pos % 9) + q) * DDP_ROW;      // k chunk q = kx
+    const int p0 = tile * 16 + 4 * q, ci = nt * 16 + i;                        // elements r = 0..3: positions p0 + r
+    const bool live = p0 < C2_POS;                                            // (p0 = 80: r >= 1 are zero rows / dump rows)
+    T.de[jj] = (uint32_t)hpp_off(live ? p0 : C2_POS - 1, 2 * ci) | ((uint32_t)((live ? p0 : C2_POS) * 128 + ci * 4) << 16);
+  }
+  T.da[0] = ab[0] | (ab[1] << 16);
+  T.da[1] = ab[2];
+  T.dw = wrow_off(nt * 16 + i, 16 * q);
+#pragma unroll
+  for (int ks = 0; ks < 3; ++ks) {
+    const int p0 = 32 * ks + 8 * q + qq, p1 = p0 + 4;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+      T.wb[ks][t] = (uint32_t)hpp_off(min(p0, C2_POS), 8 * pp + 32 * t) | ((uint32_t)hpp_off(min(p1, C2_POS), 8 * pp + 32 * t) << 16);
+    // d_dec block row of position p: output rows (2y+ky, 2x + 2kxh .. +1) x 8 co = 32 contiguous bytes
+    const int r0 = p0 < C2_POS ? (2 * (p0 / 9) + gw) * DDP_PITCH + 2 * (p0 % 9) : DDP_ZERO;
+    const int r1 = p1 < C2_POS ? (2 * (p1 / 9) + gw) * DDP_PITCH + 2 * (p1 % 9) : DDP_ZERO;
+    T.wa[ks] = (uint32_t)(r0 * DDP_ROW + 8 * pp) | ((uint32_t)(r1 * DDP_ROW + 8 * pp) << 16);
   }
 }
 
 // d_dec of a frame, a thread's two output positions (gtid, gtid + 256; 8 channel slots each, channels >= CO zero), split
-// into the planes and stored as ONE 16-byte row per plane; the bias gradient sums ride along
-__device__ __forceinline__ void pc_stage_dd(unsigned char* ddp, int gtid, const float (&dd)[2][8], float S_DD, float (&adbk)[8]) {
+// into the planes and stored as ONE 16-byte row per plane; the bias gradient sums ride along.  Branch-free: a thread
+// without a second position holds zeros for it (they add nothing) and stores them to the dump row.
+__device__ __forceinline__ void pc_stage_dd(unsigned char* ddp, PcBwdTab& T, const float (&dd)[2][8], float S_DD, float (&adbk)[8]) {
+  PIN(T.st);
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const int pos = gtid + 256 * h;
-    if (pos < PC_CELLS) {
-      u32x2p lo[NPLP], hi[NPLP];
-      split4p((f32x4){dd[h][0], dd[h][1], dd[h][2], dd[h][3]}, S_DD, lo);
-      split4p((f32x4){dd[h][4], dd[h][5], dd[h][6], dd[h][7]}, S_DD, hi);
+    unsigned char* row = ddp + (h ? HI16(T.st) : LO16(T.st));
+    u32x2p lo[NPLP], hi[NPLP];
+    split4p((f32x4){dd[h][0], dd[h][1], dd[h][2], dd[h][3]}, S_DD, lo);
+    split4p((f32x4){dd[h][4], dd[h][5], dd[h][6], dd[h][7]}, S_DD, hi);
 #pragma unroll
-      for (int pl = 0; pl < NPLP; ++pl) {
-        typedef unsigned int u32x4p __attribute__((ext_vector_type(4)));
-        *reinterpret_cast<u32x4p*>(ddp + pl * DDP_PLANE + pos * DDP_ROW) = (u32x4p){lo[pl][0], lo[pl][1], hi[pl][0], hi[pl][1]};
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) adbk[k] += dd[h][k];
+    for (int pl = 0; pl < NPLP; ++pl) {
+      typedef unsigned int u32x4p __attribute__((ext_vector_type(4)));
+      *reinterpret_cast<u32x4p*>(row + pl * DDP_PLANE) = (u32x4p){lo[pl][0], lo[pl][1], hi[pl][0], hi[pl][1]};
     }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) adbk[k] += dd[h][k];
   }
 }
 
 // dgrad of one frame: wave gw owns position tiles (gw>>1) + 2jj (jj = 0..2) and channel half nt = gw & 1;
-// d_hp (relu mask of pc_fc1 applied: hp > 0 <=> its hi term > 0) -> dhs [81][32]
+// d_hp (relu mask of pc_fc1 applied: hp > 0 <=> its hi term > 0) -> dhs [81][32].  Steps = (jj, ky) with the four weight
+// fragments held; the d_dec fragment of step s + 1 is requested before the MFMAs of step s, and the epilogue of tile jj
+// (branch-free) is issued under the MFMAs of tile jj + 1.
 __device__ __forceinline__ void pc_dgrad_frame(const unsigned char* hpp, const unsigned char* ddp, const unsigned char* wbp,
-                                               float* dhs, int gw, int i, int q, float un_dgrad) {
-  const int nt = gw & 1;
+                                               float* dhs, PcBwdTab& T, float un_dgrad) {
   f32x4 acc[3];
-  int abase[3];
+  fh8p bw[4][NPLP], av[2][NPLP];
+  PIN(T.dw);
+  PIN(T.da[0]);
+  PIN(T.da[1]);
+  auto load_av = [&](int s) {
+    const int jj = s >> 2, ky = s & 3;
+    const unsigned char* ap = ddp + (jj == 0 ? LO16(T.da[0]) : jj == 1 ? HI16(T.da[0]) : T.da[1]) + ky * DDP_PITCH * DDP_ROW;
 #pragma unroll
-  for (int jj = 0; jj < 3; ++jj) {
-    acc[jj] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int pos = min(((gw >> 1) + 2 * jj) * 16 + i, C2_POS - 1);
-    abase[jj] = ((2 * (pos / 9)) * 20 + 2 * (pos % 9) + q) * DDP_ROW;      // k chunk q = kx
-  }
-#pragma unroll
-  for (int ky = 0; ky < 4; ++ky) {
-    fh8p bw[NPLP];
-#pragma unroll
-    for (int pl = 0; pl < NPLP; ++pl)
-      bw[pl] = *reinterpret_cast<const fh8p*>(wbp + pl * WBP_PLANE + (ky * 32 + nt * 16 + i) * WDP_ROW + 16 * q);
-#pragma unroll
-    for (int jj = 0; jj < 3; ++jj) {
-      fh8p av[NPLP];
-#pragma unroll
-      for (int pl = 0; pl < NPLP; ++pl)
-        av[pl] = *reinterpret_cast<const fh8p*>(ddp + pl * DDP_PLANE + abase[jj] + ky * 20 * DDP_ROW);
-      PC_SPLIT_MMA(av, bw, acc[jj]);
-    }
-  }
-#pragma unroll
-  for (int jj = 0; jj < 3; ++jj)
+    for (int pl = 0; pl < NPLP; ++pl) av[s & 1][pl] = *reinterpret_cast<const fh8p*>(ap + pl * DDP_PLANE);
+  };
+  auto epilogue = [&](int jj) {
+    PIN(T.de[jj]);
+    const unsigned char* hrow = hpp + LO16(T.de[jj]);
+    unsigned char* drow = reinterpret_cast<unsigned char*>(dhs) + HI16(T.de[jj]);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int pos = ((gw >> 1) + 2 * jj) * 16 + 4 * q + r;
-      if (pos < C2_POS) {
-        const int ci = nt * 16 + i;
-        const unsigned short h0 = reinterpret_cast<const unsigned short*>(hpp + pos * HPP_ROW)[ci];
-        dhs[pos * 32 + ci] = (h0 != 0 && !(h0 & 0x8000)) ? acc[jj][r] * un_dgrad : 0.f;
-      }
+      const unsigned short h0 = *reinterpret_cast<const unsigned short*>(hrow + r * HPP_ROW);
+      *reinterpret_cast<float*>(drow + r * 128) = (h0 != 0 && !(h0 & 0x8000)) ? acc[jj][r] * un_dgrad : 0.f;
     }
+  };
+#pragma unroll
+  for (int ky = 0; ky < 4; ++ky)
+#pragma unroll
+    for (int pl = 0; pl < NPLP; ++pl)
+      bw[ky][pl] = *reinterpret_cast<const fh8p*>(wbp + pl * WBP_PLANE + ky * 32 * WDP_ROW + T.dw);
+  load_av(0);
+#pragma unroll
+  for (int s = 0; s < 12; ++s) {
+    const int jj = s >> 2, ky = s & 3;
+    if (ky == 0) acc[jj] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (s + 1 < 12) load_av(s + 1);
+    PC_SPLIT_MMA(av[s & 1], bw[ky], acc[jj]);
+    if (ky == 0 && jj > 0) {
+      epilogue(jj - 1);
+      pc_interleave<3, 6, 4>();
+    } else {
+      pc_interleave<3, 1, 1>();
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  epilogue(2);
 }
 
 // wgrad of one frame into aw: wave gw = ky; K = 81 positions in 3 steps of 32 (rows past 80 read zero rows);
-// dW tiles: kxh = 0..1 (kx = 2kxh + (row>>3), co = row&7), nt = 0..1
-__device__ __forceinline__ void pc_wgrad_frame(const unsigned char* hpp, const unsigned char* ddp, int gw, int i, int q,
-                                               f32x4 (&aw)[2][2]) {
-  const int qq = i >> 2, pp = i & 3;             // transposed reads: lane (4qq + pp) of a 16-lane group addresses block row qq
-#pragma unroll 1
-  for (int ks = 0; ks < 3; ++ks) {
-    const int p0 = 32 * ks + 8 * q + qq, p1 = p0 + 4;
-    const unsigned char* b0 = hpp + min(p0, C2_POS) * HPP_ROW + 8 * pp;
-    const unsigned char* b1 = hpp + min(p1, C2_POS) * HPP_ROW + 8 * pp;
-    fh8p bf[2][NPLP];
+// dW tiles: kxh = 0..1 (kx = 2kxh + (row>>3), co = row&7), nt = 0..1.  Steps = (ks, kxh): the d_dec fragments of step
+// s + 1 and the hp fragments of the next ks are requested before the MFMAs of step s.
+__device__ __forceinline__ void pc_wgrad_frame(const unsigned char* hpp, const unsigned char* ddp, PcBwdTab& T, f32x4 (&aw)[2][2]) {
+  fh8p bf[2][2][NPLP];             // [ks & 1][t]
+  fh8p af[2][NPLP];                // [s & 1]
+  auto load_bf = [&](int ks) {
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+    for (int t = 0; t < 2; ++t) {
+      PIN(T.wb[ks][t]);
+      const unsigned char* b0 = hpp + LO16(T.wb[ks][t]);
+      const unsigned char* b1 = hpp + HI16(T.wb[ks][t]);
 #pragma unroll
-      for (int pl = 0; pl < NPLP; ++pl) bf[t][pl] = tr_pair_p(b0 + pl * HPP_PLANE + 32 * t, b1 + pl * HPP_PLANE + 32 * t);
-    // d_dec block row of position p: output rows (2y+ky, 2x + 2kxh .. +1) x 8 co = 32 contiguous bytes
-    const int r0 = p0 < C2_POS ? (2 * (p0 / 9) + gw) * 20 + 2 * (p0 % 9) : PC_CELLS;
-    const int r1 = p1 < C2_POS ? (2 * (p1 / 9) + gw) * 20 + 2 * (p1 % 9) : PC_CELLS;
-#pragma unroll
-    for (int kxh = 0; kxh < 2; ++kxh) {
-      fh8p af[NPLP];
-#pragma unroll
-      for (int pl = 0; pl < NPLP; ++pl)
-        af[pl] = tr_pair_p(ddp + pl * DDP_PLANE + (r0 + 2 * kxh) * DDP_ROW + 8 * pp,
-                           ddp + pl * DDP_PLANE + (r1 + 2 * kxh) * DDP_ROW + 8 * pp);
-      PC_SPLIT_MMA(af, bf[0], aw[kxh][0]);
-      PC_SPLIT_MMA(af, bf[1], aw[kxh][1]);
+      for (int pl = 0; pl < NPLP; ++pl) bf[ks & 1][t][pl] = tr_pair_p(b0 + pl * HPP_PLANE, b1 + pl * HPP_PLANE);
     }
+  };
+  auto load_af = [&](int s) {
+    const int ks = s >> 1, kxh = s & 1;
+    if (kxh == 0) PIN(T.wa[ks]);
+    const unsigned char* a0 = ddp + LO16(T.wa[ks]) + 2 * kxh * DDP_ROW;
+    const unsigned char* a1 = ddp + HI16(T.wa[ks]) + 2 * kxh * DDP_ROW;
+#pragma unroll
+    for (int pl = 0; pl < NPLP; ++pl) af[s & 1][pl] = tr_pair_p(a0 + pl * DDP_PLANE, a1 + pl * DDP_PLANE);
+  };
+  load_bf(0);
+  load_af(0);
+#pragma unroll
+  for (int s = 0; s < 6; ++s) {
+    const int ks = s >> 1, kxh = s & 1;
+    if (s + 1 < 6) load_af(s + 1);
+    if (kxh == 0 && ks + 1 < 3) load_bf(ks + 1);
+    PC_SPLIT_MMA(af[s & 1], bf[ks & 1][0], aw[kxh][0]);
+    PC_SPLIT_MMA(af[s & 1], bf[ks & 1][1], aw[kxh][1]);
+    if (kxh == 0 && ks + 1 < 3) pc_interleave<6, 1, 2>();
+    else pc_interleave<6, 1, 1>();
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
@@ -548,7 +696,7 @@ __device__ __forceinline__ void pc_commit_grads(const f32x4 (&aw)[2][2], float u
   if (gw == 0) absmax_commit(dhp_absmax, fmaxf(fmaxf(wmx[0], wmx[1]), fmaxf(wmx[2], wmx[3])));
 }
 
-// one frame per 256-thread workgroup at a time, two independent workgroups per CU (57 KB of LDS each)
+// one frame per 256-thread workgroup at a time, two independent workgroups per CU (53 KB of LDS each)
 __global__ __launch_bounds__(256, 2) void pc_deconv_bwd_kernel(PcBwdArgs p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[BWD_GRP_BYTES + NPLP * WBP_PLANE];
   __shared__ float s_red[36];
@@ -570,6 +718,8 @@ __global__ __launch_bounds__(256, 2) void pc_deconv_bwd_kernel(PcBwdArgs p) {
 
   pc_bwd_weight_planes(p.Wv, p.Wa, A, wbp, S_W);
   pc_zero_hp_pad_rows(hpp);
+  PcBwdTab T;
+  pc_bwd_tab_build(T, gtid, gw);
   // d_dec planes: the co >= CO padding columns and the 4 extra rows stay zero (never rewritten)
   for (int e = gtid; e < NPLP * DDP_PLANE / 4; e += 256) reinterpret_cast<uint32_t*>(ddp)[e] = 0u;
 
@@ -594,9 +744,9 @@ __global__ __launch_bounds__(256, 2) void pc_deconv_bwd_kernel(PcBwdArgs p) {
     const float* src = p.d_dec + (size_t)frame * PC_CELLS * CO;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const int pos = min(gtid + 256 * h, PC_CELLS - 1);
+      const int pos = gtid + 256 * h;              // (no second position: zeros, as pc_stage_dd wants them)
 #pragma unroll
-      for (int co = 0; co < 8; ++co) pre_dd[h][co] = (co < CO) ? src[pos * CO + co] : 0.f;
+      for (int co = 0; co < 8; ++co) pre_dd[h][co] = (co < CO && pos < PC_CELLS) ? src[pos * CO + co] : 0.f;
     }
   };
 
@@ -607,7 +757,7 @@ __global__ __launch_bounds__(256, 2) void pc_deconv_bwd_kernel(PcBwdArgs p) {
       hp_load(p.hp + (size_t)n0 * F2_DIM, gtid, pre_hp);
       hp_store_planes(hpp, gtid, pre_hp, S_HP);
       load_dd(n0);
-      pc_stage_dd(ddp, gtid, pre_dd, S_DD, adbk);
+      pc_stage_dd(ddp, T, pre_dd, S_DD, adbk);
     }
   }
   for (int n = blockIdx.x; n < p.N; n += stride) {
@@ -618,13 +768,13 @@ __global__ __launch_bounds__(256, 2) void pc_deconv_bwd_kernel(PcBwdArgs p) {
       hp_load(p.hp + (size_t)nn * F2_DIM, gtid, pre_hp);
       load_dd(nn);
     }
-    pc_dgrad_frame(hpp, ddp, wbp, dhs, gw, i, q, un_dgrad);
-    pc_wgrad_frame(hpp, ddp, gw, i, q, aw);
+    pc_dgrad_frame(hpp, ddp, wbp, dhs, T, un_dgrad);
+    pc_wgrad_frame(hpp, ddp, T, aw);
     __syncthreads();  // [S1] all reads of the planes done; dhs of frame n complete
     dhp_max = pc_drain_dhp(dhs, p.d_hp + (size_t)n * F2_DIM, gtid, dhp_max);
     if (has_next) {
       hp_store_planes(hpp, gtid, pre_hp, S_HP);
-      pc_stage_dd(ddp, gtid, pre_dd, S_DD, adbk);
+      pc_stage_dd(ddp, T, pre_dd, S_DD, adbk);
     }
   }
   pc_commit_grads(aw, un_wgrad, adbk, dhp_max, A, p.dWv, p.dWa, p.dbv, p.dba, p.dhp_absmax, s_red, gw, lane, i, q);
@@ -650,19 +800,22 @@ struct PcTrainArgs {
 
 template <int COT> struct TrainLds {
   static constexpr int DS = COT | 1;
-  static constexpr int UNI = PC_CELLS * DS * 4 > F2_DIM * 4 ? PC_CELLS * DS * 4 : F2_DIM * 4;   // dec, later dhs
+  static constexpr int UNI = PC_CELLS * DS * 4 + DEC_DUMP > DHS_BYTES ? PC_CELLS * DS * 4 + DEC_DUMP : DHS_BYTES;   // dec, later dhs
   static constexpr int DDP = NPLP * HPP_PLANE, U = DDP + NPLP * DDP_PLANE, WF = U + UNI, WB = WF + NPLP * WDP_PLANE,
                        RED = WB + NPLP * WBP_PLANE, BYTES = RED + 192;
-  static constexpr int WGS = 2 * BYTES <= 160 * 1024 ? 2 : 1;
+  static constexpr int WGS = 2;
+  static_assert(2 * BYTES <= 160 * 1024, "two training workgroups must fit one CU's LDS");
 };
 
+// COT = 4, 5, 7: exactly 1 + A channels (the launcher's dispatch), so every channel bound is a constant; COT = 8: any
+// 1 + A <= 8 at run time.
 template <int COT>
 __global__ __launch_bounds__(256, TrainLds<COT>::WGS) void pc_deconv_train_kernel(PcTrainArgs p) {
   typedef TrainLds<COT> L;
   constexpr int DS = L::DS;
   __shared__ __attribute__((aligned(16))) unsigned char smem[L::BYTES];
   const int gtid = threadIdx.x;
-  const int lane = threadIdx.x & 63, gw = gtid >> 6;
+  const int lane = threadIdx.x & 63, gw = __builtin_amdgcn_readfirstlane(gtid >> 6);   // wave-uniform: lives in an SGPR
   const int i = lane & 15, q = lane >> 4;
   unsigned char* hpp = smem;
   unsigned char* ddp = smem + L::DDP;
@@ -670,7 +823,7 @@ __global__ __launch_bounds__(256, TrainLds<COT>::WGS) void pc_deconv_train_kerne
   unsigned char* wdp = smem + L::WF;
   unsigned char* wbp = smem + L::WB;
   float* red = reinterpret_cast<float*>(smem + L::RED);    // [0..35] weight max / final sums; [40..43] the frame's wave maxima
-  const int A = p.A, CO = 1 + p.A;
+  const int A = COT < 8 ? COT - 1 : p.A, CO = 1 + A;
 
   const float S_W = pow2_scale(pc_weight_max(p.Wv, p.Wa, A, red));
   const float S_HP = pow2_scale(*p.hp_absmax);
@@ -686,7 +839,13 @@ __global__ __launch_bounds__(256, TrainLds<COT>::WGS) void pc_deconv_train_kerne
     const int co = n % CO;
     bias[nt] = (n < 4 * CO) ? (co == 0 ? p.bv[0] : p.ba[co - 1]) : 0.f;
   }
-  const bool two_nt = 4 * CO > 16;
+  // the second 16-column tile: needed from 5 channels on; COT = 8 always computes it (at 1 + A <= 4 its columns are all
+  // padding and go to the dump words)
+  constexpr bool TWO_NT = 4 * COT > 16;
+  PcFwdTab TF;
+  pc_fwd_tab_build<DS>(TF, gw, lane, CO);
+  PcBwdTab TB;
+  pc_bwd_tab_build(TB, gtid, gw);
 
   f32x4 aw[2][2];
 #pragma unroll
@@ -713,8 +872,7 @@ __global__ __launch_bounds__(256, TrainLds<COT>::WGS) void pc_deconv_train_kerne
     const float tg[2] = {p.target[(size_t)n * PC_CELLS + gtid], p.target[(size_t)n * PC_CELLS + min(gtid + 256, PC_CELLS - 1)]};
     const int act = p.action[n];
     const bool on = p.mask[n] != 0;
-    if (two_nt) deconv_packed<true, DS>(hpp, wdp, uni, gw, i, q, CO, bias, un_fwd);
-    else deconv_packed<false, DS>(hpp, wdp, uni, gw, i, q, CO, bias, un_fwd);
+    deconv_packed_wave<TWO_NT>(hpp, wdp, uni, TF, gw, bias, un_fwd);
     __syncthreads();  // [S1] pre-activations complete
     // dueling combine, loss and d_dec of this thread's two output positions (pc_deconv_fwd_kernel's arithmetic)
     float dd[2][8];
@@ -759,16 +917,16 @@ __global__ __launch_bounds__(256, TrainLds<COT>::WGS) void pc_deconv_train_kerne
     __syncthreads();  // [S2] the frame's max |dq|
     const float S_DD = pow2_scale(fmaxf(fmaxf(red[40], red[41]), fmaxf(red[42], red[43])));
     const float inv_dd = pow2_inv(S_DD);
-    pc_stage_dd(ddp, gtid, dd, S_DD, adbk);
+    pc_stage_dd(ddp, TB, dd, S_DD, adbk);
     __syncthreads();  // [S3] d_dec planes staged; every read of dec done
-    pc_dgrad_frame(hpp, ddp, wbp, uni, gw, i, q, inv_dd * pow2_inv(S_W));
+    pc_dgrad_frame(hpp, ddp, wbp, uni, TB, inv_dd * pow2_inv(S_W));
     {
       f32x4 awf[2][2];
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b) awf[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      pc_wgrad_frame(hpp, ddp, gw, i, q, awf);
+      pc_wgrad_frame(hpp, ddp, TB, awf);
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
