@@ -496,6 +496,89 @@ int unreal_arcade_mix_policy_rollout_step_tl(int B, int H1, const float* X, int 
                                              int* ep_steps, int* episode, int* records, uint8_t* final_obs,
                                              float* done_return /*nullable*/, int* done_episodes /*nullable*/,
                                              void* stream);
+/* Self-play: the duel with both paddles driven by actors.  The six entries below take the arguments of the
+ * plain arcade entries in the same order.  A launch of B actors holds B / 2 games: global actors 2 i and 2 i + 1
+ * (global = actor_base + b) are seat 0 and seat 1 of game i.  cfg is ONE block of the duel (word 0 UNREAL_ARCADE_DUEL, the
+ * duel's layout above); the top paddle's width is paddle_width (word 9 equals word 6; the kernels use word 6) and
+ * opponent_speed (word 13) is ignored.
+ * The canonical game is the duel's with two changes.  (1) The top paddle is seat 1's: its action 2 moves ox right and
+ * 3 left by paddle_speed, clamped to [2, 82 - paddle_width]; the scripted follower (tick rule 2 of the duel) is not run.
+ * Order within a tick: seat 0's paddle, seat 1's paddle, then the serve or the ball.  (2) Either seat serves: a waiting
+ * ball is served when seat 0 or seat 1 plays 1, or by serve_wait as in the duel; the draw's key is the duel's with the
+ * global index of SEAT 0 (even) as the actor word, the pair's episode and its serve_index, so both seats draw the same ball.
+ * Rewards of a tick: a point for seat 0 (ty < 6) pays seat 0 win_reward and seat 1 lose_reward, a point for seat 1
+ * (ty + 1 > 83) the reverse; return_reward goes to the seat whose paddle returned the ball.  An agent step is up to
+ * action_repeat ticks with both actions held, none after the tick that ends the match; a seat's reward is the sum of its
+ * own tick rewards.  terminal, the step limit, ep_steps and episode are the duel's and the same for both seats.
+ * The mirror M of a record swaps px and ox, mine and theirs, words 10 and 11 (points won / lost totals) and words 12 and
+ * 13, and sets by = 86 - by, vy = -vy; bx, vx, wait and serve_index stay.  It is applied whatever the state, so
+ * M(M(g)) = g.  Word 12 is the seat's own matches-won total, word 13 (written by these entries only) the other seat's:
+ * it counts the tick in which theirs reaches points, once.  records[2 i] holds the canonical record g, records[2 i + 1]
+ * holds M(g), after every launch.  A seat's frame, pixel change and final observation are the duel's render of ITS OWN
+ * record with opponent_width = paddle_width: every seat sees itself at the bottom in (200, 72, 72), its own score on the
+ * left, and left / right mean the same on both seats.  The paddle rows 8..9 and 78..79 and the ball's rows are exact
+ * images under y -> 87 - y; the field's ends are not (the canonical by ranges over 6..82, the mirrored one over 4..80,
+ * so seat 1 may see the ball over the top border for a tick or two before a point): accepted.
+ * One workgroup per seat (grid B).  Workgroup b reads its own record (un-mirrored if seat 1), steps the canonical game
+ * with both seats' actions, takes its own reward, and renders, differences and stores its own view.  No workgroup reads a
+ * word another workgroup of the launch writes: of its partner b ^ 1 it reads actions[b ^ 1], active[b ^ 1] in the plain
+ * step, mask[b ^ 1] in the reset and the policy's inputs X and u.  In the plain step a pair steps only when both
+ * active flags are set (else both seats idle); a pair is reset when either mask is set; in the rollout forms a seat reads
+ * its own active flag, and THE CALLER keeps the two flags of a pair equal on entry (they stay equal: both seats see the
+ * same terminal).  The policy forms evaluate the policy rows of b and b ^ 1 and store pi, v and the action of row b only.
+ * The _tl forms keep each seat's own final observation and flag both seats 2.  reset applies the duel's reset to the
+ * canonical record (ox = 42 - paddle_width / 2), then the seat's view.
+ * -EINVAL without a launch: odd B, odd actor_base, and everything the plain entry refuses.  A block of another game
+ * writes nothing. */
+int unreal_arcade_selfplay_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
+                                 const int* count, uint8_t* frames, const int* cfg, int actor_base, int* ep_steps,
+                                 int* episode, int* records, void* stream);
+int unreal_arcade_selfplay_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
+                                float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                                int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                int reset_on_terminal, int track_score, const int* cfg, int actor_base, int* ep_steps,
+                                int* episode, int* records, void* stream);
+int unreal_arcade_selfplay_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                        int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                        int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                        int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                        int* active, int* active_log_t, int* n_steps, int* terminal_end,
+                                        int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0,
+                                        int A, int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
+                                        int* episode, int* records, void* stream);
+int unreal_arcade_selfplay_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                               const float* Wv, const float* bv, const double* u, float* pi_out,
+                                               float* v_out, int* actions_out, int* pos, int* last_action,
+                                               float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                               int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+                                               float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                                               float* score_out, int* score_valid, int* active, int* active_log_t,
+                                               int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
+                                               float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A,
+                                               int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
+                                               int* episode, int* records, void* stream);
+int unreal_arcade_selfplay_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action,
+                                           float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                                           int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc,
+                                           float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
+                                           int* score_valid, int* active, int* active_log_t, int* n_steps,
+                                           int* terminal_end, int* next_idx /*nullable*/, float* next_lar /*nullable*/,
+                                           int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                           int actor_base, int* ep_steps, int* episode, int* records, uint8_t* final_obs,
+                                           void* stream);
+int unreal_arcade_selfplay_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                                  const float* Wv, const float* bv, const double* u, float* pi_out,
+                                                  float* v_out, int* actions_out, int* pos, int* last_action,
+                                                  float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                                  int* r_action, int* r_terminal, int* r_last_action,
+                                                  float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                                                  float* episode_reward, float* score_out, int* score_valid, int* active,
+                                                  int* active_log_t, int* n_steps, int* terminal_end,
+                                                  int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld,
+                                                  int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                                  int actor_base, int* ep_steps, int* episode, int* records,
+                                                  uint8_t* final_obs, void* stream);
 /* host-fed environments (environment/hostfed_environment.py): environment.process + experience.add_frame of
  * every actor where active[b] != 0, for simulators on the host.  `staged` holds one uint8 frame per actor, frame_stride
  * bytes apart as in the ring (a multiple of 16 within [1200, 691200]: 20 x 20 x 3 .. 480 x 480 x 3 rounded up to 16).

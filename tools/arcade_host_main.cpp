@@ -2,8 +2,11 @@
 // tools/check_arcade_host.py cuts those functions unchanged out of unreal_amd/csrc/arcade.hip (and the Philox draw out of
 // maze_common.h) into arcade_functions.inc, builds this file with AddressSanitizer and UBSan, and compares what it writes
 // with tests/repeat_model.py and tests/invaders_model.py.  Nothing here runs on a GPU: the qualifiers of the device code are defined away.
+// With a third argument `selfplay` the block is the duel's and the actors are the seats of B / 2 self-play games:
+// every actor steps its pair's canonical game from its own record with the two-action tick loop and the mirror, as a
+// workgroup of the self-play kernels does, and is compared with tests/selfplay_model.py.
 //
-//   arcade_host_check IN OUT
+//   arcade_host_check IN OUT [selfplay]
 // IN:  int32 words: cfg[24], B, S, F, actor_base, then S x B actions, then S x B active flags.
 // OUT: per agent step, for the first F actors the 21168 frame bytes of the record after the last tick (before a reset; an
 //      idle actor's current frame), then int32 words: B x (record[16], reward, terminal, ep_steps, episode) after the
@@ -13,6 +16,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #define __device__
@@ -90,10 +94,85 @@ int run(const std::vector<int32_t>& in, FILE* out) {
   return bad;
 }
 
+// the seats of B / 2 self-play games: step_seat's game logic and render per actor (B and actor_base even)
+int run_selfplay(const std::vector<int32_t>& in, FILE* out) {
+  const int32_t* cfg = in.data();
+  const int B = in[24], S = in[25], F = in[26], base = in[27];
+  const int32_t* acts = in.data() + 28;
+  const int32_t* active = acts + (size_t)S * B;
+  std::vector<int32_t> rec((size_t)B * kArcadeRecord, 0), steps(B, 0), episode(B, 0), line((size_t)B * 20);
+  std::vector<uint32_t> now(FRAME_BYTES / 4);
+  const DuelRules rules = load_seat_rules(cfg);
+  int bad = 0;
+  for (int b = 0; b < B; ++b) {                   // the constructor's reset: episode 0
+    const int seat = (base + b) & 1;
+    int32_t* r = &rec[(size_t)b * kArcadeRecord];
+    const SeatGame stored = load_seat_game(r);
+    SeatGame canon = seat ? mirror(stored) : stored;
+    canon.g = reset_game(rules, canon.g);
+    store_seat_game(r, seat ? mirror(canon) : canon);
+  }
+  for (int s = 0; s < S; ++s) {
+    const int32_t* a = acts + (size_t)s * B;
+    const int32_t* on = active + (size_t)s * B;
+    for (int b = 0; b < B; ++b) {
+      const int seat = (base + b) & 1, pb = b ^ 1;
+      int32_t* r = &rec[(size_t)b * kArcadeRecord];
+      const SeatGame own_old = load_seat_game(r);
+      SeatGame canon = seat ? mirror(own_old) : own_old;
+      int32_t reward = -7, terminal = -7;
+      if (on[b] && on[pb]) {
+        const SeatRewards rw = step_ticks2(canon, rules, seat ? a[pb] : a[b], seat ? a[b] : a[pb], (base + b) & ~1, episode[b]);
+        reward = seat ? rw.r1 : rw.r0;
+        steps[b] += 1;
+        terminal = game_over(canon.g, rules, steps[b]);
+      }
+      SeatGame own = seat ? mirror(canon) : canon;
+      if (b < F) {                                // the seat's render of its own view, and the difference the kernel's way
+        const DuelGame& old = own_old.g;
+        const DuelGame& g = own.g;
+        const auto dirty = frame_dirty(old, g, rules);
+        for (int c = 0; c < kChunks; ++c) {
+          const uint4 v = frame_chunk(g, rules, c), o = frame_chunk(old, rules, c);
+          const uint32_t vs[4] = {v.x, v.y, v.z, v.w}, os[4] = {o.x, o.y, o.z, o.w};
+          for (int e = 0; e < 4; ++e) {
+            now[4 * c + e] = vs[e];
+            if (diff_dword(old, rules, dirty, 4 * c + e, vs[e]) != absdiff_u8x4(vs[e], os[e])) {
+              if (!bad) fprintf(stderr, "step %d seat %d dword %d: the dirty rows miss a difference\n", s, b, 4 * c + e);
+              bad = 1;
+            }
+          }
+        }
+        fwrite(now.data(), 1, FRAME_BYTES, out);
+      }
+      if (terminal == 1) {
+        canon.g = reset_game(rules, canon.g);
+        own = seat ? mirror(canon) : canon;
+        steps[b] = 0;
+        episode[b] += 1;
+      }
+      store_seat_game(r, own);
+      const SeatGame back = mirror(mirror(own));  // M is an involution
+      if (back.g.px != own.g.px || back.g.ox != own.g.ox || back.g.by != own.g.by || back.g.vy != own.g.vy ||
+          back.g.mine != own.g.mine || back.g.theirs != own.g.theirs || back.g.n_won != own.g.n_won ||
+          back.g.n_lost != own.g.n_lost || back.g.n_matches != own.g.n_matches || back.n_other != own.n_other) {
+        if (!bad) fprintf(stderr, "step %d seat %d: M(M(g)) != g\n", s, b);
+        bad = 1;
+      }
+      int32_t* l = &line[(size_t)b * 20];
+      std::copy(r, r + kArcadeRecord, l);
+      l[16] = reward; l[17] = terminal; l[18] = steps[b]; l[19] = episode[b];
+    }
+    fwrite(line.data(), 4, line.size(), out);
+  }
+  return bad;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc != 3) return 2;
+  const bool selfplay = argc == 4 && std::string(argv[3]) == "selfplay";
+  if (argc != 3 && !selfplay) return 2;
   FILE* f = fopen(argv[1], "rb");
   if (!f) return 2;
   std::vector<int32_t> in;
@@ -106,7 +185,8 @@ int main(int argc, char** argv) {
   FILE* out = fopen(argv[2], "wb");
   if (!out) return 2;
   int bad = 2;
-  if (in[0] == kArcadeBreakout) bad = run<Game, Rules>(in, out);
+  if (selfplay) bad = (in[0] == kArcadeDuel && in[24] % 2 == 0 && in[27] % 2 == 0) ? run_selfplay(in, out) : 2;
+  else if (in[0] == kArcadeBreakout) bad = run<Game, Rules>(in, out);
   else if (in[0] == kArcadeDuel) bad = run<DuelGame, DuelRules>(in, out);
   else if (in[0] == kArcadeInvaders) bad = run<InvGame, InvRules>(in, out);
   fclose(out);

@@ -8,7 +8,7 @@
     first-person maze.
 
   python tools/bench_arcade.py [--launches 200] [--steps 10] [--warmup 3] [--history 100] [--repeat 2] [--skip-trainer]
-                               [--game breakout] [--action-repeat 1] [--mix breakout,duel,invaders]
+                               [--game breakout] [--action-repeat 1] [--mix breakout,duel,invaders] [--selfplay]
 
 `--game duel` / `--game invaders` measures the two-paddle duel or invaders (§7n) on its default config instead
 of Breakout; its lines then also hold the game's name.  `--game A,B[,C]` times the step and the fused step of these games in
@@ -20,7 +20,11 @@ rollout entry of the mixture with that one task (unreal_arcade_mix_rollout_step,
 config, the two alternating --repeat times in one process, at 4096 and at 64 actors, with the mix entry without its
 statistics arrays and the two _tl forms beside them (lines of bench "arcade_mix_k1"); (b) the
 K-task mixture's rollout step against each of its tasks' single-game steps and their mean (bench "arcade_mix_step") and,
-unless --skip-trainer, Trainer.process() at 4096 actors on the mixture and on each task (bench "arcade_mix_process")."""
+unless --skip-trainer, Trainer.process() at 4096 actors on the mixture and on each task (bench "arcade_mix_process").
+`--selfplay` measures the self-play duel instead, on the default config: its rollout step, plain
+(unreal_arcade_selfplay_rollout_step) and with the policy fused into it, beside the duel's two in the same process, the four
+alternating --repeat times, at 4096 and at 64 actors (lines of bench "arcade_selfplay_step") and, unless --skip-trainer,
+Trainer.process() at 4096 actors on both (bench "arcade_selfplay_process")."""
 import argparse
 import json
 import os
@@ -36,7 +40,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from bench_fp_maze import DEV, kernel_ms, layouts, trainer_ms as maze_trainer_ms    # noqa: E402
 
 
-def fused_ms(env, B, launches):
+def fused_ms(env, B, launches, entry="unreal_arcade_policy_rollout_step"):
     """Mean HIP-event time of one policy-fused arcade step (random feature rows and weights, all actors active)."""
     from unreal_amd import ops
     rs = np.random.RandomState(0)
@@ -56,7 +60,7 @@ def fused_ms(env, B, launches):
         env.policy_rollout_step(net, X, 256, us[k % 8], pi, v, a, r, t, active, log, n, te)
     for k in range(10):
         step(k)
-    ops.kernel_timer_start("unreal_arcade_policy_rollout_step")
+    ops.kernel_timer_start(entry)
     for k in range(launches):
         step(k)
     res = ops.kernel_timer_stop()
@@ -134,6 +138,32 @@ def bench_mix(args):
             print(json.dumps(row), flush=True)
 
 
+def bench_selfplay(args):
+    from unreal_amd.environment.environment import Environment
+    from unreal_amd.environment.arcade_environment import BatchedArcadeEnvironment
+    Environment.register_arcade_selfplay("bench_selfplay")
+    Environment.register_arcade_config("bench_duel", game="duel")
+    plain, sp = "unreal_arcade%s_rollout_step", "unreal_arcade%s_policy_rollout_step"
+    for B in (4096, 64):
+        duel = BatchedArcadeEnvironment(B, 3, DEV, config=Environment.ARCADE_CONFIG["bench_duel"])
+        selfplay = BatchedArcadeEnvironment(B, 3, DEV, config=Environment.ARCADE_CONFIG["bench_selfplay"])
+        row = dict(bench="arcade_selfplay_step", B=B)
+        for k in range(args.repeat):
+            row["duel_us_%d" % k] = round(1e3 * rollout_ms(duel, B, args.launches, plain % ""), 2)
+            row["selfplay_us_%d" % k] = round(1e3 * rollout_ms(selfplay, B, args.launches, plain % "_selfplay"), 2)
+            row["duel_fused_us_%d" % k] = round(1e3 * fused_ms(duel, B, args.launches, sp % ""), 2)
+            row["selfplay_fused_us_%d" % k] = round(1e3 * fused_ms(selfplay, B, args.launches, sp % "_selfplay"), 2)
+        print(json.dumps(row), flush=True)
+        del duel, selfplay
+        torch.cuda.empty_cache()
+    if not args.skip_trainer:
+        for k in range(args.repeat):
+            row = dict(bench="arcade_selfplay_process", B=4096, history=args.history, repeat=k)
+            for name in ("bench_duel", "bench_selfplay"):
+                row[name[6:] + "_ms"] = round(arcade_trainer_ms(name, 4096, args.history, args.steps, args.warmup)[1], 2)
+            print(json.dumps(row), flush=True)
+
+
 def arcade_trainer_ms(env_name, B, history, steps, warmup):
     import time
     from unreal_amd.model.model import UnrealModel
@@ -180,7 +210,10 @@ def main():
     ap.add_argument("--game", default="breakout", help="breakout, duel, invaders, or several of them joined by commas")
     ap.add_argument("--action-repeat", type=int, default=None, help="game ticks per agent step, 1..8 (DESIGN §7m)")
     ap.add_argument("--mix", default="", help="a game mixture (DESIGN §7u): a comma list of breakout, duel, invaders")
+    ap.add_argument("--selfplay", action="store_true", help="the self-play duel beside the duel (DESIGN §7v)")
     args = ap.parse_args()
+    if args.selfplay:
+        return bench_selfplay(args)
     if args.mix:
         return bench_mix(args)
     from unreal_amd.environment.environment import Environment

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """The device arcade's own game functions, tick loop and render on the CPU, under AddressSanitizer and UBSan, against the
-host models of tests/repeat_model.py (Breakout and the duel) and tests/invaders_model.py (invaders, §7n).  No GPU is used and nothing loaded into Python is sanitized.
+host models of tests/repeat_model.py (Breakout and the duel), tests/invaders_model.py (invaders, §7n) and
+tests/selfplay_model.py (the self-play duel's two-action tick and mirror, §7v).  No GPU is used and nothing loaded into Python is sanitized.
 
 The functions are cut unchanged out of unreal_amd/csrc/arcade.hip (everything from its constants to `frame_chunk`:
 `load_rules`, `step_game`, `game_ended`, `game_over`, `reset_game`, `store_game`, `step_ticks`, `frame_dirty`, `diff_dword`, ...,
@@ -8,6 +9,9 @@ of all three games) and the Philox draw out of maze_common.h, and compiled with 
 program.  Over every trace of tests/repeat_model.py (six random ones of 200 actors x 300 agent steps, two scripted ones) and
 of tests/invaders_model.py (four random ones, one scripted) it is compared on every record, reward, terminal, ep_steps and episode, on every frame byte of the traces' watched actors, and
 inside the program every difference dword of the dirty-row path against the full byte-wise difference of the two frames.
+The self-play functions (`mirror`, `step_game2`, `step_ticks2`, from `struct SeatGame` to the seat body) are cut the same
+way; over the four traces of tests/selfplay_model.py (64 seats x 300 steps) every seat steps its pair's game from its own
+record as a workgroup does and is compared on the same words, and on the frames of the first three pairs.
 
   python tools/check_arcade_host.py [--cxx clang++] [--keep DIR]"""
 import argparse
@@ -34,6 +38,42 @@ def cut(path, first, last):
     return "\n".join(lines[i[0]:j[0]]) + "\n"
 
 
+def selfplay_traces(exe, work):
+    """The four traces of tests/selfplay_model.py through the program's `selfplay` mode -> agent steps compared."""
+    import selfplay_model as SM
+    from unreal_amd.environment.arcade_environment import ArcadeSelfPlay
+    total = n = 0
+    B, S, F = SM.TRACE_B, SM.TRACE_STEPS, 2 * SM.TRACE_PAIR_FRAMES
+    for k, kw in enumerate(SM.TRACE_SETTINGS):
+        conf = ArcadeSelfPlay(**kw)
+        acts, active = SM.trace_inputs(k)
+        head = np.concatenate([conf.block(SM.TRACE_SEED), np.array([B, S, F, 0], np.int32)])
+        fin, fout = os.path.join(work, "selfplay%d.in" % k), os.path.join(work, "selfplay%d.out" % k)
+        np.concatenate([head, acts.reshape(-1), active.reshape(-1)]).astype(np.int32).tofile(fin)
+        subprocess.check_call([exe, fin, fout, "selfplay"])  # a sanitizer report or a wrong difference dword ends it here
+        raw = np.fromfile(fout, dtype=np.uint8).reshape(S, F * 21168 + B * 80)
+        frames = raw[:, :F * 21168].reshape(S, F, 21168)
+        words = np.ascontiguousarray(raw[:, F * 21168:]).view(np.int32).reshape(S, B, 20)
+        seats = [SM.HostSeat(conf, b, SM.TRACE_SEED, frames=b < F) for b in range(B)]
+        for s in range(S):
+            out = SM.step_pairs(seats, acts[s], active[s])
+            for b, (r, t, pc, stepped) in enumerate(out):
+                if b < F:                                     # the frame before a reset; an idle seat's current frame
+                    np.testing.assert_array_equal(frames[s, b], seats[b].frame.reshape(-1),
+                                                  err_msg="frame of self-play trace %d step %d seat %d" % (k, s, b))
+                if stepped and t:
+                    seats[b].reset()
+                want = list(seats[b].record()) + [r if stepped else -7, int(t) if stepped else -7, seats[b].ep_steps,
+                                                  seats[b].episode]
+                np.testing.assert_array_equal(words[s, b], want, err_msg="self-play trace %d step %d seat %d" % (k, s, b))
+                total += int(stepped)
+        np.testing.assert_array_equal(words[:, 1::2, :16], SM.mirror(words[:, 0::2, :16]))
+        print("self-play trace %d (action_repeat %d, return_reward %d): %d agent steps, %d frames agree"
+              % (k, conf.action_repeat, conf.return_reward, total - n, S * F), flush=True)
+        n = total
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cxx", default=os.environ.get("CXX") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++")
@@ -49,6 +89,7 @@ def main():
     with open(os.path.join(work, "arcade_functions.inc"), "w") as f:
         f.write(cut(os.path.join(CSRC, "maze_common.h"), "// ---- Philox4x32-10", "// ---- maze configuration block"))
         f.write(src[begin:end])
+        f.write(src[src.index("// a seat's record:"):src.index("// One agent step of the seat of workgroup")])
     exe = os.path.join(work, "arcade_host_check")
     subprocess.check_call([args.cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I", work, os.path.join(ROOT, "tools", "arcade_host_main.cpp"), "-o", exe])
@@ -80,6 +121,7 @@ def main():
         total += int(tr["active"].sum())
         print("trace %d (%s, action_repeat %d, return_reward %d): %d agent steps, %d frames agree"
               % (k, conf.game, conf.action_repeat, conf.return_reward, int(tr["active"].sum()), S * F), flush=True)
+    total += selfplay_traces(exe, work)
     print("arcade host check ok: %d agent steps; the sanitizers reported nothing" % total)
     if not args.keep:
         shutil.rmtree(work)

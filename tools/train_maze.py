@@ -3,7 +3,7 @@
 
 usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] [--steps 2e7] [--log-every 10]
                                   [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout|duel|invaders]
-                                  [--arcade-mix breakout,duel,invaders]
+                                  [--arcade-mix breakout,duel,invaders] [--arcade-selfplay]
                                   [--opponent-speed N] [--action-repeat K] [--return-reward R] [--seed S]
                                   [--max-episode-steps N] [--bootstrap-timeouts] [--gae-lambda L]
                                   [--gen-maze N] [--depth-prediction] [--depth-lambda X]
@@ -40,7 +40,12 @@ tool); a line then also holds adv_mean and adv_std of its last call, and the hea
 `--arcade-mix LIST` trains one agent on a game mixture: LIST is a comma list of breakout, duel and invaders with
 their default configs, repeats allowed (a game listed twice gets twice the actors); actor g plays entry g mod len(LIST).  The
 arcade's options apply to every entry (--return-reward not to invaders, which has no such event); a line then also holds
-`tasks`, Trainer.task_scores() over the line's episodes: per entry its name, game, finished episodes and mean return."""
+`tasks`, Trainer.task_scores() over the line's episodes: per entry its name, game, finished episodes and mean return.
+`--arcade-selfplay` trains on the self-play duel with its default config (the arcade's options apply; --actors
+and --actors / --groups must be even): actors 2 i and 2 i + 1 play game i against each other.  Before the first update and at
+every logged line it runs Evaluate(net, arcade=name) on 64 actors, one episode each: seat 0 against the scripted opponent,
+the transfer metric of the run; the line then also holds `scripted`, that evaluation's success_rate, losses, timeouts,
+mean_return and mean_length."""
 import argparse
 import json
 import os
@@ -64,6 +69,7 @@ ap.add_argument("--entropy-beta", type=float, default=None, help="override optio
 ap.add_argument("--out", default="")
 ap.add_argument("--arcade", default="", help="a device arcade game (breakout, duel, invaders) instead of the maze")
 ap.add_argument("--arcade-mix", default="", help="a game mixture: a comma list of breakout, duel, invaders (DESIGN 7u)")
+ap.add_argument("--arcade-selfplay", action="store_true", help="the self-play duel (DESIGN 7v)")
 ap.add_argument("--opponent-speed", type=int, default=None, help="the duel's opponent_speed (default: the game's)")
 ap.add_argument("--action-repeat", type=int, default=1, help="arcade: game ticks per agent step, 1..8")
 ap.add_argument("--return-reward", type=int, default=0, help="arcade: reward for a ball the agent's paddle returns, 0..100")
@@ -98,6 +104,12 @@ if mix and (not 1 <= len(mix) <= 16 or any(g not in MIX_GAMES for g in mix)):
     ap.error("--arcade-mix takes a comma list of 1..16 games out of %s, not %r" % (", ".join(MIX_GAMES), args.arcade_mix))
 if mix:
     args.arcade = "mix:" + ",".join(mix)                  # the mixture's name; everything arcade below applies to it
+if args.arcade_selfplay:
+    if args.arcade or args.gen_maze:
+        ap.error("--arcade-selfplay, --arcade-mix, --arcade and --gen-maze are four environments")
+    if args.actors % 2 or args.groups < 1 or args.actors % args.groups or (args.actors // args.groups) % 2:
+        ap.error("--arcade-selfplay: actors come in pairs, --actors and --actors / --groups must be even")
+    args.arcade = "selfplay"                              # the registered name; everything arcade below applies to it
 if args.depth_prediction and not args.gen_maze:
     ap.error("--depth-prediction needs a first-person maze: --gen-maze N")
 if args.gen_maze and args.arcade:
@@ -132,7 +144,10 @@ def build_arcade_trainer(args, device):
     from unreal_amd.options import get_options
     from unreal_amd.train.trainer import Trainer, log_uniform
     limit = {} if args.max_episode_steps is None else dict(max_episode_steps=args.max_episode_steps)
-    for game in sorted(set(mix)) or [args.arcade]:
+    if args.arcade_selfplay:
+        Environment.register_arcade_selfplay(args.arcade, opponent_speed=args.opponent_speed,
+                                             action_repeat=args.action_repeat, return_reward=args.return_reward, **limit)
+    for game in [] if args.arcade_selfplay else sorted(set(mix)) or [args.arcade]:
         Environment.register_arcade_config(game, game=game, opponent_speed=args.opponent_speed if game == "duel" or not mix
                                            else None, action_repeat=args.action_repeat,
                                            return_reward=0 if mix and game == "invaders" else args.return_reward, **limit)
@@ -237,6 +252,20 @@ head = {"actors": args.actors, "groups": args.groups, "reuse_epochs": tr.reuse_e
 print(json.dumps(head), flush=True)
 if out:
     out.write(json.dumps(head) + "\n")
+scripted = None
+if args.arcade_selfplay:
+    from unreal_amd.evaluate import Evaluate
+    scripted_eval = Evaluate(net, batch_size=64, device=device, arcade=args.arcade)
+
+
+    def scripted():
+        """Seat 0 against the scripted opponent, one episode of each of 64 actors."""
+        res = scripted_eval.process(0, one_episode_per_actor=True)
+        return {key: round(res[key], 4) for key in ("success_rate", "losses", "timeouts", "mean_return", "mean_length")}
+    line = json.dumps({"global_t": 0, "scripted": scripted()})
+    print(line, flush=True)
+    if out:
+        out.write(line + "\n")
 global_t, t0, k = 0, time.time(), 0
 # the totals of the game's records (words 10 ..), never zeroed: per-line differences over the line's episodes
 TOTALS = {"breakout": ("bricks_per_episode", "lives_lost_per_episode"),
@@ -265,6 +294,8 @@ while global_t < args.steps:
         if mix:
             extra.update(tasks=[dict(t, mean_return=None if t["mean_return"] is None else round(t["mean_return"], 4))
                                 for t in tr.task_scores()])
+        if scripted is not None:
+            extra.update(scripted=scripted())
         if args.depth_prediction:
             # the yardstick of depth_accuracy: the share of the most common class among the labels the replay holds
             hist = torch.bincount(tr.full_ring.r_depth.long(), minlength=8).float()

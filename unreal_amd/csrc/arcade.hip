@@ -1259,3 +1259,376 @@ int unreal_arcade_mix_policy_rollout_step_tl(int B, int H1, const float* X, int 
 }
 
 }  // extern "C"
+
+// ---- self-play: both paddles of the duel driven by actors -------------------------------------------------
+// A launch of B actors holds B / 2 games: global actors 2 i and 2 i + 1 are seat 0 and seat 1 of game i.  The canonical
+// game is the duel with its top paddle moved by seat 1's action instead of the script, the width of the bottom one, and a
+// serve on either seat's fire, drawn with seat 0's global index.  Seat 0 stores the canonical record, seat 1 its mirror
+// image M (include/unreal_hip.h), so that the duel's render functions above, applied to a seat's own record, show every
+// seat itself at the bottom.  One workgroup per SEAT, as everywhere else: both workgroups of a pair step the same game
+// from their own copy of it with both actions and keep their own view, reward, frame and ring words.  No workgroup reads
+// a word another workgroup of the launch writes: of its partner it reads actions, the read-only active / mask flags and
+// the policy's input rows.  Everything above this line is what it was.
+namespace {
+
+// a seat's record: the duel's thirteen words and word 13, the other seat's matches won
+struct SeatGame {
+  DuelGame g;
+  int n_other;
+};
+
+__device__ __forceinline__ SeatGame load_seat_game(const int* rec) { return {load_duel_game(rec), rec[13]}; }
+
+__device__ __forceinline__ void store_seat_game(int* rec, const SeatGame& s) {
+  store_game(rec, s.g);
+  rec[13] = s.n_other;
+}
+
+// the mirror M: the game as the other seat sees it (applied whatever the state: M(M(s)) = s)
+__device__ __forceinline__ SeatGame mirror(const SeatGame& s) {
+  SeatGame m = s;
+  m.g.px = s.g.ox; m.g.ox = s.g.px;
+  m.g.by = 86 - s.g.by;
+  m.g.vy = -s.g.vy;
+  m.g.mine = s.g.theirs; m.g.theirs = s.g.mine;
+  m.g.n_won = s.g.n_lost; m.g.n_lost = s.g.n_won;
+  m.g.n_matches = s.n_other; m.n_other = s.g.n_matches;
+  return m;
+}
+
+// the duel's rules with the top paddle as wide as the bottom one (word 9 equals word 6; word 13 is not used)
+__device__ __forceinline__ DuelRules load_seat_rules(const int* cfg) {
+  DuelRules r = load_duel_rules(cfg);
+  r.ow = r.w;
+  r.opp_speed = 0;
+  return r;
+}
+
+struct SeatRewards {
+  int r0, r1;
+};
+
+// One tick of the canonical game of the pair whose seat 0 is global actor `actor0`: step_game(DuelGame&) with seat 1's
+// move where the script was; -> both seats' rewards of the tick.
+__device__ __forceinline__ SeatRewards step_game2(SeatGame& s, const DuelRules& r, int a0, int a1, int actor0, int ep) {
+  DuelGame& g = s.g;
+  SeatRewards rw = {0, 0};
+  if (a0 == 2) g.px = min(g.px + r.paddle_speed, 82 - r.w);
+  if (a0 == 3) g.px = max(g.px - r.paddle_speed, kFieldL);
+  if (a1 == 2) g.ox = min(g.ox + r.paddle_speed, 82 - r.w);
+  if (a1 == 3) g.ox = max(g.ox - r.paddle_speed, kFieldL);
+  if (g.wait >= 0) {
+    if (a0 == 1 || a1 == 1 || (r.serve_wait > 0 && g.wait >= r.serve_wait)) {
+      uint32_t u[4];
+      philox4x32_10(r.seed, (uint64_t)(uint32_t)actor0 | ((uint64_t)(uint32_t)ep << 32),
+                    (uint64_t)kArcadeServeStream | ((uint64_t)(uint32_t)g.serve << 32), u);
+      g.bx = kFieldL + 2 * (int)(u[0] % 39u);
+      g.by = kServeY;
+      g.vx = (u[1] & 1u) ? 1 : -1;
+      g.vy = (u[2] & 1u) ? 1 : -1;
+      g.wait = -1;
+      g.serve += 1;
+    } else {
+      g.wait += 1;
+    }
+    return rw;
+  }
+  for (int m = 0; m < r.ball_speed; ++m) {
+    // x move
+    const int tx = g.bx + g.vx;
+    if (tx < kFieldL || tx + 1 > kFieldR) g.vx = -g.vx;
+    else g.bx = tx;
+    // y move
+    const int ty = g.by + g.vy;
+    if (g.vy > 0 && ty + 1 == kPaddleY && g.bx + 1 >= g.px && g.bx <= g.px + r.w - 1) {
+      g.vy = -1;
+      g.vx = return_vx(g.bx, g.px, r.w);
+      rw.r0 += r.return_reward;
+    } else if (g.vy < 0 && ty == kOppY + 1 && g.bx + 1 >= g.ox && g.bx <= g.ox + r.w - 1) {
+      g.vy = 1;
+      g.vx = return_vx(g.bx, g.ox, r.w);
+      rw.r1 += r.return_reward;
+    } else if (ty + 1 > 83) {                      // a point for seat 1
+      g.theirs += 1;
+      g.n_lost += 1;
+      if (g.theirs == r.points) s.n_other += 1;
+      rw.r0 += r.lose_reward;
+      rw.r1 += r.win_reward;
+      g.wait = 0;
+      break;
+    } else if (ty < kFieldTop) {                   // a point for seat 0
+      g.mine += 1;
+      g.n_won += 1;
+      if (g.mine == r.points) g.n_matches += 1;
+      rw.r0 += r.win_reward;
+      rw.r1 += r.lose_reward;
+      g.wait = 0;
+      break;
+    } else {
+      g.by = ty;
+    }
+  }
+  return rw;
+}
+
+// step_ticks with both actions held: each seat gets the sum of its own tick rewards
+__device__ __forceinline__ SeatRewards step_ticks2(SeatGame& s, const DuelRules& r, int a0, int a1, int actor0, int ep) {
+  SeatRewards rw = {0, 0};
+#pragma unroll 1
+  for (int tick = 0;; ++tick) {
+    const SeatRewards t = step_game2(s, r, a0, a1, actor0, ep);
+    rw.r0 += t.r0; rw.r1 += t.r1;
+    if (tick >= r.repeat || game_ended(s.g, r)) break;
+  }
+  return rw;
+}
+
+// One agent step of the seat of workgroup blockIdx.x: step_actor with the canonical game between the seat's two views.
+// `s_act`: [2], the seat's own action and its partner's; `s_pol`: [5], the partner's pi and v, which nobody reads.
+template <bool TL>
+__device__ __forceinline__ void step_seat(const ArcadeArgs& p, uint4* diff, int* s_act, float* s_pol) {
+  const int b = blockIdx.x, pb = b ^ 1;         // (B and actor_base are even: the partner is in the launch)
+  const int seat = (p.actor_base + b) & 1;
+  const int H1 = p.H1;
+  if (p.pol_x && threadIdx.x < 128) {           // the policy of this seat on wave 0, of its partner on wave 1: the same
+    const int w = threadIdx.x >> 6;             // instructions on the same inputs as the partner's workgroup runs
+    const int row = w ? pb : b;
+    const int act = policy_row<4>(p.pol_x + (size_t)row * p.pol_ldx, p.Wp, p.bp, p.Wv, p.bv, p.pol_u + row,
+                                  w ? s_pol : p.pi_out + (size_t)b * 4, w ? s_pol + 4 : p.v_out + b, threadIdx.x & 63);
+    if ((threadIdx.x & 63) == 0) {
+      s_act[w] = act;
+      if (w == 0) p.act_out[b] = act;
+    }
+  }
+  const int cnt = p.count[b];
+  const int slot = cnt % H1;
+  // a plain step moves a pair only when both seats are active; a rollout form reads its own flag (the pair's are equal)
+  const int act_flag = p.active_rw ? p.active_rw[b] : (p.active ? (p.active[b] && p.active[pb]) : 1);
+  const int la = p.last_action[b];
+  const float lr = p.last_reward[b];
+  if (!act_flag) {
+    if (threadIdx.x == 0) rollout_idle(p, b, slot, la, lr);
+    return;
+  }
+  int* rec = p.records + (size_t)kArcadeRecord * b;
+  const DuelRules rules = load_seat_rules(p.cfg);
+  const SeatGame own_old = load_seat_game(rec);                     // the stored frame's state
+  const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
+  const int steps = p.ep_steps[b] + 1;
+  const int epi = p.episode[b];
+  const int ns = p.active_rw ? p.n_steps[b] : 0;
+  const float ep = p.track_score ? p.episode_reward[b] : 0.f;
+  __syncthreads();                              // the drawn actions are in LDS; every thread has read the record
+  const int a = p.pol_x ? s_act[0] : p.actions[b];
+  const int ap = p.pol_x ? s_act[1] : p.actions[pb];
+
+  SeatGame canon = seat ? mirror(own_old) : own_old;
+  const SeatRewards rw = step_ticks2(canon, rules, seat ? ap : a, seat ? a : ap, (p.actor_base + b) & ~1, epi);
+  const float reward = (float)(seat ? rw.r1 : rw.r0);
+  const bool terminal = game_over(canon.g, rules, steps);
+  SeatGame own = seat ? mirror(canon) : canon;
+  const DuelGame& old = own_old.g;
+  const DuelGame& g = own.g;
+  const RingStep ring = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
+  uint8_t* dst = p.frames + ((size_t)b * H1 + ring.nslot) * FRAME_BYTES;
+  const bool cut = TL && ring.reset && !game_ended(g, rules);      // (uniform) ended by the step limit alone
+  uint8_t* fin = TL ? p.final_obs + (size_t)b * FRAME_BYTES : nullptr;
+
+  const auto dirty = frame_dirty(old, g, rules);
+#pragma unroll 1
+  for (int k = 0; k < kChunksPerThread; ++k) {
+    const int c = threadIdx.x + 256 * k;
+    if (c < kChunks) {
+      const uint4 v = frame_chunk(g, rules, c);
+      if (!ring.reset) reinterpret_cast<uint4*>(dst)[c] = v;
+      if constexpr (TL) {
+        if (cut) reinterpret_cast<uint4*>(fin)[c] = v;
+      }
+      diff[c] = make_uint4(diff_dword(old, rules, dirty, 4 * c, v.x), diff_dword(old, rules, dirty, 4 * c + 1, v.y),
+                           diff_dword(old, rules, dirty, 4 * c + 2, v.z), diff_dword(old, rules, dirty, 4 * c + 3, v.w));
+    }
+  }
+  __syncthreads();
+  {                                             // pixel change, as in step_actor
+    const uint32_t* d32 = reinterpret_cast<const uint32_t*>(diff);
+    for (int c = threadIdx.x; c < PC_CELLS; c += 256) {
+      const int i = c / 20, j = c - 20 * i;
+      int sum = 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t* q = d32 + (4 * i + 2 + r) * kRowDw + 3 * j + 1;
+        sum += bytesum(q[0] >> 16) + bytesum(q[1]) + bytesum(q[2]) + bytesum(q[3] & 0xFFFFu);
+      }
+      p.r_pc[ring.base * PC_CELLS + c] = (float)sum / kPcDenom;
+    }
+  }
+  if (ring.reset) {                             // (uniform) the next match's first observation goes into the slot instead
+    canon.g = reset_game(rules, canon.g);
+    own = seat ? mirror(canon) : canon;
+    store_frame(dst, own.g, rules);
+  }
+  if (threadIdx.x == 0) {
+    ring_commit(p, b, ring, a, reward, reward, la, lr, ep);
+    store_seat_game(rec, own);
+    p.ep_steps[b] = ring.reset ? 0 : steps;
+    p.episode[b] = epi + (ring.reset ? 1 : 0);
+    rollout_commit(p, b, ring, ns, a, reward);
+    if constexpr (TL) {
+      if (cut) {                                  // the three words the commits above have set to 1
+        p.r_terminal[ring.base] = 2;
+        if (p.out_terminal) p.out_terminal[b] = 2;
+        p.terminal_end[b] = 2;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void arcade_selfplay_step_kernel(ArcadeArgs p) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act[2];
+  __shared__ float s_pol[5];
+  if (p.cfg[0] == kArcadeDuel) step_seat<false>(p, diff, s_act, s_pol);   // (uniform) another game's block: nothing is written
+}
+
+__global__ __launch_bounds__(256) void arcade_selfplay_step_tl_kernel(ArcadeArgs p) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act[2];
+  __shared__ float s_pol[5];
+  if (p.cfg[0] == kArcadeDuel) step_seat<true>(p, diff, s_act, s_pol);
+}
+
+// a pair is reset when either seat's mask is set: reset_game on the canonical record, then the seat's view
+__global__ __launch_bounds__(256) void arcade_selfplay_reset_kernel(ArcadeArgs p) {
+  if (p.cfg[0] != kArcadeDuel) return;          // (uniform) as in the step
+  const int b = blockIdx.x;
+  if (p.mask && !p.mask[b] && !p.mask[b ^ 1]) return;
+  const int seat = (p.actor_base + b) & 1;
+  int* rec = p.records + (size_t)kArcadeRecord * b;
+  const DuelRules rules = load_seat_rules(p.cfg);
+  const SeatGame stored = load_seat_game(rec);
+  const int epi = p.episode[b];
+  __syncthreads();                              // every thread has read the record
+  SeatGame canon = seat ? mirror(stored) : stored;
+  canon.g = reset_game(rules, canon.g);
+  const SeatGame own = seat ? mirror(canon) : canon;
+  store_frame(p.frames + ((size_t)b * p.H1 + p.count[b] % p.H1) * FRAME_BYTES, own.g, rules);
+  if (threadIdx.x == 0) {
+    store_seat_game(rec, own);
+    p.ep_steps[b] = 0;
+    p.episode[b] = epi + 1;
+    p.last_action[b] = 0;
+    p.last_reward[b] = 0.f;
+  }
+}
+
+// the self-play launcher: arcade_launch's tail and checks, and whole pairs only (even B, even actor_base)
+int arcade_selfplay_launch(ArcadeEntry e, ArcadeArgs& p, const int* cfg, int actor_base, int* ep_steps, int* episode,
+                           int* records, void* stream, bool tl = false, uint8_t* final_obs = nullptr) {
+  p.cfg = cfg; p.actor_base = actor_base; p.ep_steps = ep_steps; p.episode = episode; p.records = records;
+  if (tl) p.final_obs = final_obs;
+  if (!arcade_args_ok(e, p)) return UNREAL_EINVAL;
+  if (tl && (!final_obs || ((uintptr_t)final_obs & 15) || (e != kRollout && e != kPolicy))) return UNREAL_EINVAL;
+  if ((p.B & 1) || (actor_base & 1)) return UNREAL_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (e == kReset) hipLaunchKernelGGL(arcade_selfplay_reset_kernel, dim3(p.B), dim3(256), 0, s, p);
+  else if (tl) hipLaunchKernelGGL(arcade_selfplay_step_tl_kernel, dim3(p.B), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(arcade_selfplay_step_kernel, dim3(p.B), dim3(256), 0, s, p);
+  return unreal_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+// Self-play: the six arcade entries with the arguments of the plain ones, over B / 2 games of two seats.
+
+int unreal_arcade_selfplay_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
+                                 const int* count, uint8_t* frames, const int* cfg, int actor_base, int* ep_steps,
+                                 int* episode, int* records, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, const_cast<int*>(count), frames};
+  p.mask = mask;
+  return arcade_selfplay_launch(kReset, p, cfg, actor_base, ep_steps, episode, records, stream);
+}
+
+int unreal_arcade_selfplay_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
+                                float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                                int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                int reset_on_terminal, int track_score, const int* cfg, int actor_base, int* ep_steps,
+                                int* episode, int* records, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid,
+               reset_on_terminal, track_score};
+  return arcade_selfplay_launch(kStep, p, cfg, actor_base, ep_steps, episode, records, stream);
+}
+
+int unreal_arcade_selfplay_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                        int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                        int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                        int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                        int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                        float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                                        const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
+                                        void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
+  return arcade_selfplay_launch(kRollout, p, cfg, actor_base, ep_steps, episode, records, stream);
+}
+
+int unreal_arcade_selfplay_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                               const float* Wv, const float* bv, const double* u, float* pi_out,
+                                               float* v_out, int* actions_out, int* pos, int* last_action,
+                                               float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                               int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+                                               float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                                               float* score_out, int* score_valid, int* active, int* active_log_t,
+                                               int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
+                                               int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                               int actor_base, int* ep_steps, int* episode, int* records, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
+               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
+  return arcade_selfplay_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, stream);
+}
+
+int unreal_arcade_selfplay_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action,
+                                           float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                                           int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc,
+                                           float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
+                                           int* score_valid, int* active, int* active_log_t, int* n_steps,
+                                           int* terminal_end, int* next_idx, float* next_lar, int lar_ld, int lar_col0,
+                                           int A, int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
+                                           int* episode, int* records, uint8_t* final_obs, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
+  return arcade_selfplay_launch(kRollout, p, cfg, actor_base, ep_steps, episode, records, stream, true, final_obs);
+}
+
+int unreal_arcade_selfplay_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                                  const float* Wv, const float* bv, const double* u, float* pi_out,
+                                                  float* v_out, int* actions_out, int* pos, int* last_action,
+                                                  float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                                  int* r_action, int* r_terminal, int* r_last_action,
+                                                  float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                                                  float* episode_reward, float* score_out, int* score_valid, int* active,
+                                                  int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                                  float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                                                  const int* cfg, int actor_base, int* ep_steps, int* episode,
+                                                  int* records, uint8_t* final_obs, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
+               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
+  return arcade_selfplay_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, stream, true, final_obs);
+}
+
+}  // extern "C"

@@ -3,7 +3,8 @@ minimal action set (0 noop, 1 fire, 2 right, 3 left): Breakout, the two-paddle d
 serve and puts an opponent's paddle where the wall was, and invaders, a fixed shooter on Breakout's field: a marching grid
 of aliens that drop bombs, a cannon that shoots them.  All are integer-only and a pure function of (config, seed, global
 actor, episode, actions).  An agent step is `action_repeat` game ticks with one action (§7m).  The rules are written out
-with the entries in include/unreal_hip.h."""
+with the entries in include/unreal_hip.h.  ArcadeSelfPlay (§7v) is the duel with both paddles driven by actors: actors 2 i
+and 2 i + 1 are the two seats of game i."""
 import numpy as np
 import torch
 
@@ -147,6 +148,8 @@ class ArcadeMix(object):
         if not 1 <= len(tasks) <= self.MAX_TASKS:
             raise ValueError("a game mixture holds 1..%d tasks, not %d" % (self.MAX_TASKS, len(tasks)))
         for t in tasks:
+            if isinstance(t, ArcadeSelfPlay):
+                raise ValueError("self-play inside a game mixture is out of scope: its actors come in pairs (DESIGN §7v)")
             if not isinstance(t, ArcadeConfig):
                 raise ValueError("a task of a game mixture must be an ArcadeConfig, not %r" % (t,))
         names = ["%d:%s" % (k, t.game) for k, t in enumerate(tasks)] if names is None else [str(n) for n in names]
@@ -173,9 +176,41 @@ class ArcadeMix(object):
         return np.concatenate([t.block(seed) for t in self.tasks])
 
 
+class ArcadeSelfPlay(object):
+    """The duel with both paddles driven by actors (Environment.register_arcade_selfplay): global actors 2 i and
+    2 i + 1 are seat 0 and seat 1 of game i, the top paddle is seat 1's and as wide and as fast as the bottom one, either
+    seat's fire serves, and seat 1 sees the game mirrored, itself at the bottom.  Built from the duel's settings;
+    `opponent_width` is no keyword (the width is paddle_width).  `.scripted` is the duel against the scripted opponent
+    with the same settings, the only place `opponent_speed` is used: what the batch-1 surface and Evaluate without
+    `versus` play.  Raises ValueError as ArcadeConfig does."""
+    ACTION_SIZE = 4
+    game = "selfplay"
+
+    def __init__(self, points=None, paddle_width=12, paddle_speed=3, ball_speed=2, serve_wait=8, win_reward=None,
+                 lose_reward=None, max_episode_steps=5000, action_repeat=1, return_reward=0, opponent_speed=None):
+        paddle_width = _even("paddle_width", paddle_width, 4, 24)          # (checked here: it is the opponent's, too)
+        self.scripted = ArcadeConfig(game="duel", points=points, paddle_width=paddle_width, paddle_speed=paddle_speed,
+                                     ball_speed=ball_speed, serve_wait=serve_wait, win_reward=win_reward,
+                                     lose_reward=lose_reward, max_episode_steps=max_episode_steps,
+                                     action_repeat=action_repeat, return_reward=return_reward,
+                                     opponent_speed=opponent_speed, opponent_width=paddle_width)
+        for name in ("points", "paddle_width", "paddle_speed", "ball_speed", "serve_wait", "win_reward", "lose_reward",
+                     "max_episode_steps", "action_repeat", "return_reward", "opponent_speed"):
+            setattr(self, name, getattr(self.scripted, name))
+
+    @property
+    def action_size(self):
+        return self.ACTION_SIZE
+
+    def block(self, seed):
+        """The duel's block of `.scripted` (word 9 equals word 6; the _selfplay entries ignore word 13)."""
+        return self.scripted.block(seed)
+
+
 class BatchedArcadeEnvironment(object):
-    """B actors of one arcade game, or of a game mixture (ArcadeMix), on the device, with the interface of
-    BatchedMazeEnvironment."""
+    """B actors of one arcade game, of a game mixture (ArcadeMix) or of B / 2 self-play games (ArcadeSelfPlay: actors
+    2 i and 2 i + 1 are the seats of game i, so B, actor_base and a view's bounds are even), on the device, with the
+    interface of BatchedMazeEnvironment."""
     ACTION_SIZE = 4
     frame_scale = 1.0 / 255.0          # ring bytes 0..255
     objective_size = 0
@@ -190,8 +225,12 @@ class BatchedArcadeEnvironment(object):
         if depth_labels:
             raise ValueError("depth_labels is out of scope for the arcade: a game has no wall distances (it needs a "
                              "first-person device maze)")
-        if not isinstance(config, (ArcadeConfig, ArcadeMix)):
-            raise ValueError("BatchedArcadeEnvironment needs an ArcadeConfig or an ArcadeMix")
+        if not isinstance(config, (ArcadeConfig, ArcadeMix, ArcadeSelfPlay)):
+            raise ValueError("BatchedArcadeEnvironment needs an ArcadeConfig, an ArcadeMix or an ArcadeSelfPlay")
+        selfplay = isinstance(config, ArcadeSelfPlay)
+        if selfplay and (batch % 2 or actor_base % 2):
+            raise ValueError("self-play actors come in pairs: batch = %d and actor_base = %d must be even"
+                             % (batch, actor_base))
         self.B = batch
         self.config = config
         total = batch if actors_total is None else int(actors_total)
@@ -201,13 +240,16 @@ class BatchedArcadeEnvironment(object):
         self.ring = ops.Ring(batch, history_size, torch.device(device), arcade=True, final_obs=bool(final_obs),
                              bonus=bool(bonus), arcade_stats=mix)
         block = torch.from_numpy(config.block(seed)).to(self.ring.count.device)
-        # a mixture: (K blocks, actor_base, K), which selects the _mix entries (ops._arcade_args)
-        self.arcade = (block, int(actor_base)) + ((len(config),) if mix else ())
+        # a mixture: (K blocks, actor_base, K), which selects the _mix entries (ops._arcade_args); self-play: (block,
+        # actor_base, ops.ARCADE_SELFPLAY), which selects the _selfplay entries
+        self.arcade = (block, int(actor_base)) + ((len(config),) if mix else (ops.ARCADE_SELFPLAY,) if selfplay else ())
         self.reset()
 
     def view(self, b0, b1):
         """The environments [b0, b1) as a batched environment of their own (shares the ring memory), as
         BatchedMazeEnvironment.view."""
+        if isinstance(self.config, ArcadeSelfPlay) and (b0 % 2 or b1 % 2):
+            raise ValueError("a view of a self-play environment holds whole pairs: [%d, %d) has an odd bound" % (b0, b1))
         v = object.__new__(BatchedArcadeEnvironment)
         v.B, v.ring = b1 - b0, ops.ring_view(self.ring, b0, b1)
         v.base_actor = b0
@@ -253,7 +295,10 @@ class BatchedArcadeEnvironment(object):
         the running totals of bricks, lives lost and walls cleared.  Duel: px, bx, by, vx, vy, wait, ox, mine, theirs,
         serve_index, then the running totals of points won, points lost and matches won.  Words 13..15 are 0.  Invaders: px,
         sx, sy (0: no shot), gx, gy, direction, lives, alien mask, march | bomb << 8 | grace << 16 counters, draw_index,
-        then the running totals of aliens shot, lives lost and waves cleared, then the three bombs as x | y << 8 (0: free)."""
+        then the running totals of aliens shot, lives lost and waves cleared, then the three bombs as x | y << 8 (0: free).
+        Self-play: one duel record per SEAT; rows 2 i hold game i's canonical record (seat 0 at the bottom),
+        rows 2 i + 1 its mirror image, the game as seat 1 sees it (px and ox, mine and theirs, words 10 and 11, words 12
+        and 13 swapped, by = 86 - by, vy = -vy); word 13 is the other seat's matches won, words 14..15 are 0."""
         return self.ring.actor_records.cpu().numpy().copy()
 
     def stop(self):
@@ -276,6 +321,8 @@ class ArcadeEnvironment(environment.Environment):
             raise ValueError("task = %r outside the %d task(s) of the config" % (task, n_tasks))
         if isinstance(config, ArcadeMix):
             config = config.tasks[task]
+        if isinstance(config, ArcadeSelfPlay):         # one actor: seat 0 against the scripted opponent
+            config = config.scripted
         self._env = BatchedArcadeEnvironment(1, 2, device, config=config, seed=seed)
         self._a = torch.zeros(1, dtype=torch.int32, device=device)
         self._r = torch.zeros(1, dtype=torch.float32, device=device)

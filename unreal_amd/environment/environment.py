@@ -127,7 +127,7 @@ class Environment(object):
             if isinstance(t, str):
                 conf = Environment.arcade_config(t)
                 if not isinstance(conf, ArcadeConfig):
-                    raise ValueError("task %r is a mixture itself: a mixture lists single games" % t)
+                    raise ValueError("task %r is a mixture itself or a self-play game: a mixture lists single games" % t)
                 confs.append(conf)
                 names.append(t)
             elif isinstance(t, dict):
@@ -136,6 +136,19 @@ class Environment(object):
             else:
                 raise ValueError("task %d must be a registered config's name or a dict of settings, not %r" % (k, t))
         Environment.ARCADE_CONFIG[env_name] = ArcadeMix(confs, names)
+
+    @staticmethod
+    def register_arcade_selfplay(env_name, **settings):
+        """Self-play duel of `env_name` on the device (env_type 'arcade'): both paddles are actors, global
+        actors 2 i and 2 i + 1 the two seats of game i, so every actor count the trainer steps at once must be even.
+        `settings` are the duel's keywords of register_arcade_config without `game` and `opponent_width` (the top paddle
+        is as wide as the bottom one): points, paddle_width, paddle_speed, ball_speed, serve_wait, win_reward,
+        lose_reward, max_episode_steps, action_repeat, return_reward, and opponent_speed, which only the scripted opponent
+        of the batch-1 surface and of Evaluate without `versus` uses.  The name shares register_arcade_config's namespace:
+        registering a name again replaces what it named, as there.  Raises ValueError outside the duel's ranges and
+        TypeError for any other keyword."""
+        from .arcade_environment import ArcadeSelfPlay
+        Environment.ARCADE_CONFIG[env_name] = ArcadeSelfPlay(**settings)
 
     @staticmethod
     def arcade_config(env_name):

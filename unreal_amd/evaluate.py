@@ -25,7 +25,13 @@ differences are `aliens_per_episode` and `lives_lost_per_episode` (an invasion c
 game ticks per step.  With `arcade=` the name of a game mixture (Environment.register_arcade_mix) actor b plays
 task b mod K; the result keeps the overall keys over all counted episodes (`timeouts`: the sum of the tasks') and adds
 `tasks`, one dict per task with the keys and meanings of a single-game evaluation of that task's game, over the episodes of
-that task's actors (the duel's `losses` by the task's own `points`)."""
+that task's actors (the duel's `losses` by the task's own `points`).  With `arcade=` the name of a self-play game
+(Environment.register_arcade_selfplay) the network plays seat 0 against the scripted opponent: exactly the
+evaluation of the duel config `.scripted`, the transfer metric of a self-play run.  `versus=other_network` (a self-play name
+only) plays the two networks head to head on the self-play kernels instead: B / 2 games, in game i `network` sits in seat
+i mod 2 and `other_network` in the other; both networks are evaluated on every row with LSTM states of their own, and a
+fixed per-row mask picks each row's action.  The result holds the duel's keys from `network`'s side, one episode per game,
+and `versus=True`."""
 import torch
 
 from . import ops
@@ -36,8 +42,16 @@ from .train.trainer import PhiloxDraws
 
 class Evaluate(object):
     def __init__(self, network, batch_size=64, device="cuda:0", seed=0xE7A1, greedy=False, draws=None, simulator=None,
-                 termination_time=50.0, maze=None, arcade=None):
+                 termination_time=50.0, maze=None, arcade=None, versus=None):
         self.net, self.B, self.greedy = network, int(batch_size), greedy
+        self.versus = versus
+        if versus is not None:
+            from .environment.environment import Environment
+            if simulator is not None or arcade is None or \
+                    getattr(Environment.arcade_config(arcade), "game", None) != "selfplay":
+                raise ValueError("versus needs arcade= the name of a self-play game (Environment.register_arcade_selfplay)")
+            if self.B % 2:
+                raise ValueError("versus plays batch_size / 2 games: batch_size = %d must be even" % self.B)
         self.device = torch.device(device)
         self.draws = draws if draws is not None else PhiloxDraws(seed)
         B, A = self.B, network._action_size
@@ -47,6 +61,8 @@ class Evaluate(object):
             from .environment.environment import Environment
             from .environment.arcade_environment import BatchedArcadeEnvironment
             self.arcade_config = Environment.arcade_config(arcade)
+            if self.arcade_config.game == "selfplay" and versus is None:
+                self.arcade_config = self.arcade_config.scripted      # seat 0 against the scripted opponent
             self.env = BatchedArcadeEnvironment(B, 2, self.device, config=self.arcade_config, seed=seed)
             network.lar_bounded = False        # a step can pay more than 1 (Trainer.prepare)
         elif simulator is None:
@@ -76,6 +92,43 @@ class Evaluate(object):
         self.pi, self.v = z(B * A, torch.float32), z(B, torch.float32)
         self.u, self.actions = z(B, torch.float64), z(B, torch.int32)
         self.rewards, self.terminals = z(B, torch.float32), z(B, torch.int32)
+        if versus is not None:                 # the other network: its own workspace (LSTM state), outputs and actions
+            if versus._action_size != A:
+                raise ValueError("versus: the other network has %d actions, not %d" % (versus._action_size, A))
+            versus.lar_bounded = False
+            versus.bind_frame_scale(self.env.frame_scale)
+            self.ws2 = PathWS(B, B, self.device, save_c1=False, lstm=versus._use_lstm, xld=versus.xld, **versus.ws_kw)
+            self.pi2, self.v2, self.actions2 = z(B * A, torch.float32), z(B, torch.float32), z(B, torch.int32)
+            self.played = z(B, torch.int32)
+            b = torch.arange(B, device=self.device)
+            self.mine = (b % 2) == ((b // 2) % 2)              # rows in which `network` sits: seat i mod 2 of game i
+
+    def _policy(self, net, ws, pi, v, actions):
+        """`net`'s policy on all B rows of the environment's current observations -> actions."""
+        B, ring = self.B, self.env.ring
+        net.begin_pass()
+        ring.cur_idx(out=ws.frame_idx[:B])
+        net.encode_rows(ring, ws, 0, B, lar_from_ring=False, save_c1=False, lstm_x=False)
+        if net._use_lstm:
+            net.lstm_step(ws, 0, B, fused_x=True)
+        feat, ld = net.features(ws, 0)
+        net.policy_step(B, feat, ld, None if self.greedy else self.u, pi, v, actions)
+
+    def _step_versus(self):
+        """One lock-step step of the B / 2 games: both networks on all rows (one draw per row serves both), the row's own
+        network's action by the mask, the self-play step, then each network's LSTM state carried on its own."""
+        B = self.B
+        if not self.greedy:
+            self.draws.uniform(self.u)
+        self._policy(self.net, self.ws, self.pi, self.v, self.actions)
+        self._policy(self.versus, self.ws2, self.pi2, self.v2, self.actions2)
+        self.played.copy_(torch.where(self.mine, self.actions, self.actions2))
+        self.env.process(self.played, None, self.rewards, self.terminals, reset_on_terminal=True, track_score=True)
+        for net, ws in ((self.net, self.ws), (self.versus, self.ws2)):
+            if net._use_lstm:
+                ops.copy_(ws.c0, ws.c[:B * 256])
+                ops.copy_(ws.h0, ws.h[:B * 256])
+                ops.reset_state(B, self.terminals, ws.c0, ws.h0)
 
     def _step(self):
         """One lock-step policy + environment step of the B actors (reset on terminal, scores tracked)."""
@@ -119,6 +172,35 @@ class Evaluate(object):
         else:
             res.update(timeouts=n - successes, bricks_per_episode=sum(bricks) / float(n),
                        lives_lost_per_episode=sum(lost) / float(n))
+        return res
+
+    def _process_versus(self, n_episodes, one_episode_per_actor):
+        """Head to head: one episode per game, counted on `network`'s row of the pair, whose record holds its
+        own points won (word 10), points lost (11) and matches won (12)."""
+        B, ring = self.B, self.env.ring
+        rows = [b for b in range(B) if (b % 2) == ((b // 2) % 2)]
+        tot = ring.actor_records[:, 10:13]
+        ep0 = tot.cpu().numpy().copy()
+        steps, counted = [0] * B, [False] * B
+        eps = []
+        if one_episode_per_actor:
+            n_episodes = len(rows)
+        while len(eps) < n_episodes:
+            self._step_versus()
+            term = self.terminals.cpu().numpy()
+            score = ring.score_out.cpu().numpy()
+            now = tot.cpu().numpy()
+            for b in rows:
+                steps[b] += 1
+                if not term[b]:
+                    continue
+                if not (one_episode_per_actor and counted[b]):
+                    eps.append((float(score[b]), steps[b], int(now[b, 0] - ep0[b, 0]), int(now[b, 1] - ep0[b, 1]),
+                                bool(now[b, 2] - ep0[b, 2] > 0)))
+                ep0[b] = now[b]
+                steps[b] = 0; counted[b] = True
+        res = self._arcade_result(self.arcade_config.scripted, eps)
+        res["versus"] = True
         return res
 
     def _process_arcade(self, n_episodes, one_episode_per_actor):
@@ -179,6 +261,12 @@ class Evaluate(object):
         if net._use_lstm:
             ws.c0.zero_()
             ws.h0.zero_()
+        if self.versus is not None:
+            self.versus.refresh_shadows()
+            if self.versus._use_lstm:
+                self.ws2.c0.zero_()
+                self.ws2.h0.zero_()
+            return self._process_versus(n_episodes, one_episode_per_actor)
         if self.arcade_config is not None:
             return self._process_arcade(n_episodes, one_episode_per_actor)
         steps = [0] * B

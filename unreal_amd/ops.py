@@ -252,6 +252,7 @@ ARCADE_INVADERS = 5                          # UNREAL_ARCADE_INVADERS
 ARCADE_BOMB_STREAM = 0x494E5642              # counter word 2 of an invaders bomb draw (UNREAL_ARCADE_BOMB_STREAM)
 ARCADE_SERVE_STREAM = 0x41524B53             # counter word 2 of a serve draw (UNREAL_ARCADE_SERVE_STREAM)
 ARCADE_MIX_MAX = 16                          # config blocks of a game mixture at the most (UNREAL_ARCADE_MIX_MAX)
+ARCADE_SELFPLAY = "selfplay"                 # third element of the arcade tuple that selects the _selfplay entries (§7v)
 MAZE_TOP_DOWN, MAZE_FIRST_PERSON = 0, 1       # the `view` of a maze (UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON)
 MAZE_FIRST_PERSON_GENERATED = 2               # first person, a generated block (UNREAL_MAZE_FIRST_PERSON_GENERATED)
 # goal-sense blocks: UNREAL_MAZE_FIRST_PERSON_SENSE / UNREAL_MAZE_FIRST_PERSON_GENERATED_SENSE
@@ -477,13 +478,21 @@ def maze_policy_rollout_step_encode(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_o
 
 # ---- device arcade (csrc/arcade.hip) -----------------------------------------------------------------------
 def _arcade_args(ring, arcade, stats=True):
-    """-> ("" or "_mix", the tail of the arcade entry of that name, the arguments behind its `records` and final_obs).
+    """-> ("", "_mix" or "_selfplay", the tail of the arcade entry of that name, the arguments behind its `records` and
+    final_obs).
     `arcade` = (int32 config block on the device, global index of the ring's actor 0), which selects the plain entries, or
     (K consecutive blocks, that index, K), a game mixture, which selects the _mix entries: global actor g
     plays block g % K, and the step forms (`stats`) also take the ring's done_return / done_episodes (None without
-    Ring(arcade_stats=True))."""
+    Ring(arcade_stats=True)); or (the duel's block, that index, ARCADE_SELFPLAY), self-play, which selects
+    the _selfplay entries: global actors 2 i and 2 i + 1 are the two seats of game i (the entries refuse an odd actor count
+    or index)."""
     K = None
-    if len(arcade) == 3:
+    selfplay = len(arcade) == 3 and isinstance(arcade[2], str)
+    if selfplay:
+        block, actor_base, tag = arcade
+        if tag != ARCADE_SELFPLAY:
+            raise ValueError("arcade tuple: unknown entry family %r" % (tag,))
+    elif len(arcade) == 3:
         block, actor_base, K = arcade
         K = int(K)
         if not 1 <= K <= ARCADE_MIX_MAX:
@@ -499,7 +508,7 @@ def _arcade_args(ring, arcade, stats=True):
         raise ValueError("actor_base %d < 0" % actor_base)
     tail = (int(actor_base), ptr(ring.ep_steps), ptr(ring.episode), ptr(ring.arcade))
     if K is None:
-        return "", (ptr(block),) + tail, ()
+        return "_selfplay" if selfplay else "", (ptr(block),) + tail, ()
     done_return, done_episodes = getattr(ring, "done_return", None), getattr(ring, "done_episodes", None)
     if (done_return is None) != (done_episodes is None):
         raise ValueError("ring.done_return and ring.done_episodes go together")

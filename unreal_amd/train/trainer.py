@@ -157,6 +157,20 @@ class Trainer(PassState):
         return int(M)
 
     @staticmethod
+    def check_selfplay_options(env_type, env_name, batch_size, groups):
+        """-> whether (env_type, env_name) is a self-play game (Environment.register_arcade_selfplay).  Its
+        actors 2 i and 2 i + 1 are the seats of one game, so everything stepped at once holds whole pairs: ValueError
+        unless this rank's batch_size and a group's batch_size // groups are even.  (The split rollout cuts a group with
+        the environment's view(), which refuses an odd bound.)"""
+        if env_type != "arcade" or getattr(Environment.arcade_config(env_name), "game", None) != "selfplay":
+            return False
+        B, G = int(batch_size), int(groups)
+        if B % 2 or (G >= 1 and B % G == 0 and (B // G) % 2):
+            raise ValueError("self-play actors come in pairs: batch_size = %d per rank and batch_size // groups = %d // %d "
+                             "must be even" % (B, B, G))
+        return True
+
+    @staticmethod
     def minibatch_order(epoch, M):
         """The blocks of a group's actors in the order epoch `epoch` (1-based) visits them: (i + epoch - 1) mod M."""
         return [(i + epoch - 1) % M for i in range(M)]
@@ -278,6 +292,7 @@ class Trainer(PassState):
             raise NotImplementedError("groups > 1 needs an environment that steps a sub-range of its actors (maze, "
                                       "arcade)")
         self.Bg = self.B // self.groups              # actors per group = batch of every kernel launch
+        self.selfplay = self.check_selfplay_options(env_type, env_name, self.B, self.groups)
         self.world_size, self.rank = int(world_size), int(rank)
         self.grad_scale = 1.0 / float(self.Bg * self.world_size)
         self.grad_sync = grad_sync
