@@ -579,6 +579,83 @@ int unreal_arcade_selfplay_policy_rollout_step_tl(int B, int H1, const float* X,
                                                   int lar_col0, int A, int idx_base_actor, const int* cfg,
                                                   int actor_base, int* ep_steps, int* episode, int* records,
                                                   uint8_t* final_obs, void* stream);
+/* Versus: self-play with ONE learner per game; the other paddle is an input.  The six entries below take the
+ * arguments of the plain arcade entries in the same order, then four pointers: opp_actions [B] (read by the step forms
+ * only; unused by reset), opp_frames [B x 84 * 84 * 3 bytes, 16-byte aligned], opp_last_action [B] and opp_last_reward [B].
+ * A launch of B actors holds B games; B and actor_base may be odd.  Game b IS game actor_base + b of a self-play
+ * environment (above): the canonical game, its rules, tick order, either-seat serve, both actions held over an agent
+ * step, rewards, terminal and step limit are the self-play entries', and the serve draws are keyed by
+ * 2 (actor_base + b), seat 0's global index there.  The actor is seat 0: its action is actions[b] (or the policy's draw
+ * in the fused forms), seat 1's is opp_actions[b].  records[b] holds the canonical record, and the record, frame, pixel
+ * change, ring slot, ep_steps, episode, rollout bookkeeping, next-step prefill, and in the _tl forms the final observation
+ * and flag 2, are bit for bit what seat 0 of the self-play entries writes.
+ * The opponent's side, written after the learner's: opp_frames[b] is the duel's render of M(canonical record) with
+ * opponent_width = paddle_width, the frame seat 1 would see; where the step resets it is the next match's first
+ * observation.  No pixel change, ring slot or final observation is kept for it.  opp_last_action[b] is the action it
+ * played, opp_last_reward[b] its reward of the step; both are 0 where the step resets, as last_action[b] and
+ * last_reward[b] are: the values seat 1 of the self-play entries keeps.  An idle actor (active / active_rw clear) leaves
+ * all three untouched.
+ * reset writes the mirrored first frame and zeroes the two words, where mask says so (mask nullable: every game).
+ * One workgroup of 256 threads per game (grid B) computes the game once and forms both views; no workgroup reads a word
+ * another workgroup of the launch writes.
+ * -EINVAL without a launch: everything the plain entry refuses, a null or misaligned opp_frames, a null opp_last_action
+ * or opp_last_reward, a null opp_actions in the step forms, and an actor_base + B beyond 2^30.  A block of another game
+ * writes nothing. */
+int unreal_arcade_versus_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
+                                 const int* count, uint8_t* frames, const int* cfg, int actor_base, int* ep_steps,
+                                 int* episode, int* records, const int* opp_actions, uint8_t* opp_frames,
+                                 int* opp_last_action, float* opp_last_reward, void* stream);
+int unreal_arcade_versus_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
+                                float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                                int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                int reset_on_terminal, int track_score, const int* cfg, int actor_base, int* ep_steps,
+                                int* episode, int* records, const int* opp_actions, uint8_t* opp_frames,
+                                int* opp_last_action, float* opp_last_reward, void* stream);
+int unreal_arcade_versus_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                        int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                        int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                        int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                        int* active, int* active_log_t, int* n_steps, int* terminal_end,
+                                        int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld, int lar_col0,
+                                        int A, int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
+                                        int* episode, int* records, const int* opp_actions, uint8_t* opp_frames,
+                                        int* opp_last_action, float* opp_last_reward, void* stream);
+int unreal_arcade_versus_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                               const float* Wv, const float* bv, const double* u, float* pi_out,
+                                               float* v_out, int* actions_out, int* pos, int* last_action,
+                                               float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                               int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+                                               float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                                               float* score_out, int* score_valid, int* active, int* active_log_t,
+                                               int* n_steps, int* terminal_end, int* next_idx /*nullable*/,
+                                               float* next_lar /*nullable*/, int lar_ld, int lar_col0, int A,
+                                               int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
+                                               int* episode, int* records, const int* opp_actions, uint8_t* opp_frames,
+                                               int* opp_last_action, float* opp_last_reward, void* stream);
+int unreal_arcade_versus_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action,
+                                           float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                                           int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc,
+                                           float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
+                                           int* score_valid, int* active, int* active_log_t, int* n_steps,
+                                           int* terminal_end, int* next_idx /*nullable*/, float* next_lar /*nullable*/,
+                                           int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                           int actor_base, int* ep_steps, int* episode, int* records, uint8_t* final_obs,
+                                           const int* opp_actions, uint8_t* opp_frames, int* opp_last_action,
+                                           float* opp_last_reward, void* stream);
+int unreal_arcade_versus_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                                  const float* Wv, const float* bv, const double* u, float* pi_out,
+                                                  float* v_out, int* actions_out, int* pos, int* last_action,
+                                                  float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                                  int* r_action, int* r_terminal, int* r_last_action,
+                                                  float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                                                  float* episode_reward, float* score_out, int* score_valid, int* active,
+                                                  int* active_log_t, int* n_steps, int* terminal_end,
+                                                  int* next_idx /*nullable*/, float* next_lar /*nullable*/, int lar_ld,
+                                                  int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                                  int actor_base, int* ep_steps, int* episode, int* records,
+                                                  uint8_t* final_obs, const int* opp_actions, uint8_t* opp_frames,
+                                                  int* opp_last_action, float* opp_last_reward, void* stream);
 /* host-fed environments (environment/hostfed_environment.py): environment.process + experience.add_frame of
  * every actor where active[b] != 0, for simulators on the host.  `staged` holds one uint8 frame per actor, frame_stride
  * bytes apart as in the ring (a multiple of 16 within [1200, 691200]: 20 x 20 x 3 .. 480 x 480 x 3 rounded up to 16).

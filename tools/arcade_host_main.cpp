@@ -5,8 +5,13 @@
 // With a third argument `selfplay` the block is the duel's and the actors are the seats of B / 2 self-play games:
 // every actor steps its pair's canonical game from its own record with the two-action tick loop and the mirror, as a
 // workgroup of the self-play kernels does, and is compared with tests/selfplay_model.py.
+// With `versus` the same input is read as B / 2 games of ONE learner each: a game is stepped once with the
+// learner's action (the even column) and the opponent's (the odd one) when both flags are set, as the one workgroup of
+// the versus kernels does, and both views are formed from the one canonical record.  OUT per agent step: for the first F
+// games the learner's frame (before a reset) and the opponent's frame (what opp_frames holds: after a reset), then per game
+// int32 x (record[16], reward, terminal, ep_steps, episode, opp_last_action, opp_last_reward).
 //
-//   arcade_host_check IN OUT [selfplay]
+//   arcade_host_check IN OUT [selfplay | versus]
 // IN:  int32 words: cfg[24], B, S, F, actor_base, then S x B actions, then S x B active flags.
 // OUT: per agent step, for the first F actors the 21168 frame bytes of the record after the last tick (before a reset; an
 //      idle actor's current frame), then int32 words: B x (record[16], reward, terminal, ep_steps, episode) after the
@@ -168,10 +173,88 @@ int run_selfplay(const std::vector<int32_t>& in, FILE* out) {
   return bad;
 }
 
+// B / 2 games of one learner each: step_versus's game logic and its two renders per game (game i is keyed by 2 (base / 2 + i))
+int run_versus(const std::vector<int32_t>& in, FILE* out) {
+  const int32_t* cfg = in.data();
+  const int B = in[24], S = in[25], F = in[26], base = in[27], G = B / 2;
+  const int32_t* acts = in.data() + 28;
+  const int32_t* active = acts + (size_t)S * B;
+  std::vector<int32_t> rec((size_t)G * kArcadeRecord, 0), steps(G, 0), episode(G, 0), line((size_t)G * 22);
+  std::vector<int32_t> opp_la(G, 0), opp_lr(G, 0);
+  std::vector<uint32_t> now(FRAME_BYTES / 4);
+  const DuelRules rules = load_seat_rules(cfg);
+  int bad = 0;
+  for (int i = 0; i < G; ++i) {                   // the constructor's reset: episode 0
+    int32_t* r = &rec[(size_t)i * kArcadeRecord];
+    SeatGame canon = load_seat_game(r);
+    canon.g = reset_game(rules, canon.g);
+    store_seat_game(r, canon);
+  }
+  for (int s = 0; s < S; ++s) {
+    const int32_t* a = acts + (size_t)s * B;
+    const int32_t* on = active + (size_t)s * B;
+    for (int i = 0; i < G; ++i) {
+      int32_t* r = &rec[(size_t)i * kArcadeRecord];
+      const SeatGame own_old = load_seat_game(r);
+      SeatGame canon = own_old;
+      int32_t reward = -7, terminal = -7;
+      const bool stepped = on[2 * i] && on[2 * i + 1];
+      SeatRewards rw = {0, 0};
+      if (stepped) {
+        rw = step_ticks2(canon, rules, a[2 * i], a[2 * i + 1], 2 * (base / 2 + i), episode[i]);
+        reward = rw.r0;
+        steps[i] += 1;
+        terminal = game_over(canon.g, rules, steps[i]);
+      }
+      if (i < F) {                                // the learner's render, and the difference the kernel's way
+        const DuelGame& old = own_old.g;
+        const DuelGame& g = canon.g;
+        const auto dirty = frame_dirty(old, g, rules);
+        for (int c = 0; c < kChunks; ++c) {
+          const uint4 v = frame_chunk(g, rules, c), o = frame_chunk(old, rules, c);
+          const uint32_t vs[4] = {v.x, v.y, v.z, v.w}, os[4] = {o.x, o.y, o.z, o.w};
+          for (int e = 0; e < 4; ++e) {
+            now[4 * c + e] = vs[e];
+            if (diff_dword(old, rules, dirty, 4 * c + e, vs[e]) != absdiff_u8x4(vs[e], os[e])) {
+              if (!bad) fprintf(stderr, "step %d game %d dword %d: the dirty rows miss a difference\n", s, i, 4 * c + e);
+              bad = 1;
+            }
+          }
+        }
+        fwrite(now.data(), 1, FRAME_BYTES, out);
+      }
+      if (terminal == 1) {
+        canon.g = reset_game(rules, canon.g);
+        steps[i] = 0;
+        episode[i] += 1;
+      }
+      if (stepped) {
+        opp_la[i] = terminal == 1 ? 0 : a[2 * i + 1];
+        opp_lr[i] = terminal == 1 ? 0 : rw.r1;
+      }
+      store_seat_game(r, canon);
+      if (i < F) {                                // the opponent's render, after the learner's: M of the stored record
+        const SeatGame opp = mirror(canon);
+        for (int c = 0; c < kChunks; ++c) {
+          const uint4 v = frame_chunk(opp.g, rules, c);
+          now[4 * c] = v.x; now[4 * c + 1] = v.y; now[4 * c + 2] = v.z; now[4 * c + 3] = v.w;
+        }
+        fwrite(now.data(), 1, FRAME_BYTES, out);
+      }
+      int32_t* l = &line[(size_t)i * 22];
+      std::copy(r, r + kArcadeRecord, l);
+      l[16] = reward; l[17] = terminal; l[18] = steps[i]; l[19] = episode[i]; l[20] = opp_la[i]; l[21] = opp_lr[i];
+    }
+    fwrite(line.data(), 4, line.size(), out);
+  }
+  return bad;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-  const bool selfplay = argc == 4 && std::string(argv[3]) == "selfplay";
+  const bool versus = argc == 4 && std::string(argv[3]) == "versus";
+  const bool selfplay = (argc == 4 && std::string(argv[3]) == "selfplay") || versus;
   if (argc != 3 && !selfplay) return 2;
   FILE* f = fopen(argv[1], "rb");
   if (!f) return 2;
@@ -185,7 +268,9 @@ int main(int argc, char** argv) {
   FILE* out = fopen(argv[2], "wb");
   if (!out) return 2;
   int bad = 2;
-  if (selfplay) bad = (in[0] == kArcadeDuel && in[24] % 2 == 0 && in[27] % 2 == 0) ? run_selfplay(in, out) : 2;
+  if (selfplay && !(in[0] == kArcadeDuel && in[24] % 2 == 0 && in[27] % 2 == 0)) bad = 2;
+  else if (versus) bad = in[26] <= in[24] / 2 ? run_versus(in, out) : 2;
+  else if (selfplay) bad = run_selfplay(in, out);
   else if (in[0] == kArcadeBreakout) bad = run<Game, Rules>(in, out);
   else if (in[0] == kArcadeDuel) bad = run<DuelGame, DuelRules>(in, out);
   else if (in[0] == kArcadeInvaders) bad = run<InvGame, InvRules>(in, out);

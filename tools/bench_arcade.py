@@ -9,6 +9,7 @@
 
   python tools/bench_arcade.py [--launches 200] [--steps 10] [--warmup 3] [--history 100] [--repeat 2] [--skip-trainer]
                                [--game breakout] [--action-repeat 1] [--mix breakout,duel,invaders] [--selfplay]
+                               [--versus]
 
 `--game duel` / `--game invaders` measures the two-paddle duel or invaders (§7n) on its default config instead
 of Breakout; its lines then also hold the game's name.  `--game A,B[,C]` times the step and the fused step of these games in
@@ -24,7 +25,12 @@ unless --skip-trainer, Trainer.process() at 4096 actors on the mixture and on ea
 `--selfplay` measures the self-play duel instead, on the default config: its rollout step, plain
 (unreal_arcade_selfplay_rollout_step) and with the policy fused into it, beside the duel's two in the same process, the four
 alternating --repeat times, at 4096 and at 64 actors (lines of bench "arcade_selfplay_step") and, unless --skip-trainer,
-Trainer.process() at 4096 actors on both (bench "arcade_selfplay_process")."""
+Trainer.process() at 4096 actors on both (bench "arcade_selfplay_process").
+`--versus` measures the versus step instead: unreal_arcade_versus_rollout_step, plain and fused, beside the
+self-play and the duel steps, alternating --repeat times in one process at B = 4096 and 64 launched actors (a versus
+launch of B actors steps B games, a self-play launch B / 2: the lines also hold µs per game), bench "arcade_versus_step";
+and, unless --skip-trainer, Trainer.process() at 4096 actors on the self-play game with opponent_pool K = 0 (mirror
+self-play), 1 and 4, the fill untimed (bench "arcade_versus_process", with the cost per slot)."""
 import argparse
 import json
 import os
@@ -164,7 +170,41 @@ def bench_selfplay(args):
             print(json.dumps(row), flush=True)
 
 
-def arcade_trainer_ms(env_name, B, history, steps, warmup):
+def bench_versus(args):
+    from unreal_amd.environment.environment import Environment
+    from unreal_amd.environment.arcade_environment import BatchedArcadeEnvironment
+    Environment.register_arcade_selfplay("bench_selfplay")
+    Environment.register_arcade_config("bench_duel", game="duel")
+    plain, fused = "unreal_arcade%s_rollout_step", "unreal_arcade%s_policy_rollout_step"
+    for B in (4096, 64):
+        conf = Environment.ARCADE_CONFIG["bench_selfplay"]
+        envs = (("duel", "", BatchedArcadeEnvironment(B, 3, DEV, config=Environment.ARCADE_CONFIG["bench_duel"])),
+                ("selfplay", "_selfplay", BatchedArcadeEnvironment(B, 3, DEV, config=conf)),
+                ("versus", "_versus", BatchedArcadeEnvironment(B, 3, DEV, config=conf, versus=True)))
+        envs[2][2].opponent.actions.copy_(torch.from_numpy(np.random.RandomState(1).randint(0, 4, B).astype(np.int32)))
+        row = dict(bench="arcade_versus_step", B=B)
+        for k in range(args.repeat):
+            for key, family, env in envs:
+                row["%s_us_%d" % (key, k)] = round(1e3 * rollout_ms(env, B, args.launches, plain % family), 2)
+                row["%s_fused_us_%d" % (key, k)] = round(1e3 * fused_ms(env, B, args.launches, fused % family), 2)
+        mean = lambda key: sum(row["%s_us_%d" % (key, k)] for k in range(args.repeat)) / args.repeat
+        row["versus_over_selfplay"] = round(mean("versus") / mean("selfplay"), 3)                  # per launch of B workgroups
+        row["versus_ns_per_game"] = round(1e3 * mean("versus") / B, 2)
+        row["selfplay_ns_per_game"] = round(1e3 * mean("selfplay") / (B // 2), 2)
+        print(json.dumps(row), flush=True)
+        del envs
+        torch.cuda.empty_cache()
+    if not args.skip_trainer:
+        for k in range(args.repeat):
+            row = dict(bench="arcade_versus_process", B=4096, history=args.history, repeat=k)
+            for K in (0, 1, 4):
+                row["pool%d_ms" % K] = round(arcade_trainer_ms("bench_selfplay", 4096, args.history, args.steps, args.warmup,
+                                                               opponent_pool=K)[1], 2)
+            row["ms_per_slot"] = round((row["pool4_ms"] - row["pool1_ms"]) / 3.0, 2)
+            print(json.dumps(row), flush=True)
+
+
+def arcade_trainer_ms(env_name, B, history, steps, warmup, **options):
     import time
     from unreal_amd.model.model import UnrealModel
     from unreal_amd.options import get_options
@@ -179,7 +219,7 @@ def arcade_trainer_ms(env_name, B, history, steps, warmup):
     tr = Trainer(0, net, lr0, None, applier, "arcade", env_name, flags.use_lstm, flags.use_pixel_change,
                  flags.use_value_replay, flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta,
                  flags.local_t_max, flags.n_step_TD, flags.gamma, flags.gamma_pc, history, flags.max_time_step, DEV,
-                 batch_size=B, seed=0xA3C)
+                 batch_size=B, seed=0xA3C, **options)
     tr.prepare()
     while not tr._full:
         tr.process(None, 0)
@@ -211,7 +251,10 @@ def main():
     ap.add_argument("--action-repeat", type=int, default=None, help="game ticks per agent step, 1..8 (DESIGN §7m)")
     ap.add_argument("--mix", default="", help="a game mixture (DESIGN §7u): a comma list of breakout, duel, invaders")
     ap.add_argument("--selfplay", action="store_true", help="the self-play duel beside the duel (DESIGN §7v)")
+    ap.add_argument("--versus", action="store_true", help="the versus step beside self-play and the duel (DESIGN §7w)")
     args = ap.parse_args()
+    if args.versus:
+        return bench_versus(args)
     if args.selfplay:
         return bench_selfplay(args)
     if args.mix:

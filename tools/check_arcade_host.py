@@ -12,6 +12,9 @@ inside the program every difference dword of the dirty-row path against the full
 The self-play functions (`mirror`, `step_game2`, `step_ticks2`, from `struct SeatGame` to the seat body) are cut the same
 way; over the four traces of tests/selfplay_model.py (64 seats x 300 steps) every seat steps its pair's game from its own
 record as a workgroup does and is compared on the same words, and on the frames of the first three pairs.
+The program's `versus` mode runs the one-workgroup two-view step over the same four traces as 32 games of one
+learner each (even columns the learner's actions, odd ones the opponent's): records, rewards, terminals, ep_steps, episode
+and the opponent's last action and reward of every game against HostSeat 2 i and 2 i + 1, both frames of the first three.
 
   python tools/check_arcade_host.py [--cxx clang++] [--keep DIR]"""
 import argparse
@@ -74,6 +77,48 @@ def selfplay_traces(exe, work):
     return total
 
 
+def versus_traces(exe, work):
+    """The four traces of tests/selfplay_model.py through the program's `versus` mode -> agent steps compared."""
+    import selfplay_model as SM
+    from unreal_amd.environment.arcade_environment import ArcadeSelfPlay
+    total = 0
+    B, S, F = SM.TRACE_B, SM.TRACE_STEPS, SM.TRACE_PAIR_FRAMES
+    G = B // 2
+    for k, kw in enumerate(SM.TRACE_SETTINGS):
+        conf = ArcadeSelfPlay(**kw)
+        acts, active = SM.trace_inputs(k)
+        head = np.concatenate([conf.block(SM.TRACE_SEED), np.array([B, S, F, 0], np.int32)])
+        fin, fout = os.path.join(work, "versus%d.in" % k), os.path.join(work, "versus%d.out" % k)
+        np.concatenate([head, acts.reshape(-1), active.reshape(-1)]).astype(np.int32).tofile(fin)
+        subprocess.check_call([exe, fin, fout, "versus"])    # a sanitizer report or a wrong difference dword ends it here
+        raw = np.fromfile(fout, dtype=np.uint8).reshape(S, 2 * F * 21168 + G * 88)
+        frames = raw[:, :2 * F * 21168].reshape(S, F, 2, 21168)
+        words = np.ascontiguousarray(raw[:, 2 * F * 21168:]).view(np.int32).reshape(S, G, 22)
+        seats = [SM.HostSeat(conf, b, SM.TRACE_SEED, frames=b < 2 * F) for b in range(B)]
+        n = 0
+        for s in range(S):
+            out = SM.step_pairs(seats, acts[s], active[s])
+            for i in range(G):
+                r, t, pc, stepped = out[2 * i]
+                if i < F:                                     # the learner's frame before a reset
+                    np.testing.assert_array_equal(frames[s, i, 0], seats[2 * i].frame.reshape(-1),
+                                                  err_msg="learner frame of versus trace %d step %d game %d" % (k, s, i))
+                if stepped and t:
+                    seats[2 * i].reset(); seats[2 * i + 1].reset()
+                if i < F:                                     # the opponent's frame after it
+                    np.testing.assert_array_equal(frames[s, i, 1], seats[2 * i + 1].frame.reshape(-1),
+                                                  err_msg="opponent frame of versus trace %d step %d game %d" % (k, s, i))
+                want = list(seats[2 * i].record()) + [r if stepped else -7, int(t) if stepped else -7, seats[2 * i].ep_steps,
+                                                      seats[2 * i].episode, seats[2 * i + 1].last_action,
+                                                      seats[2 * i + 1].last_reward]
+                np.testing.assert_array_equal(words[s, i], want, err_msg="versus trace %d step %d game %d" % (k, s, i))
+                n += int(stepped)
+        print("versus trace %d (action_repeat %d, return_reward %d): %d agent steps of %d games, %d frames agree"
+              % (k, conf.action_repeat, conf.return_reward, n, G, 2 * S * F), flush=True)
+        total += n
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cxx", default=os.environ.get("CXX") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++")
@@ -122,6 +167,7 @@ def main():
         print("trace %d (%s, action_repeat %d, return_reward %d): %d agent steps, %d frames agree"
               % (k, conf.game, conf.action_repeat, conf.return_reward, int(tr["active"].sum()), S * F), flush=True)
     total += selfplay_traces(exe, work)
+    total += versus_traces(exe, work)
     print("arcade host check ok: %d agent steps; the sanitizers reported nothing" % total)
     if not args.keep:
         shutil.rmtree(work)

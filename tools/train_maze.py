@@ -4,6 +4,7 @@
 usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] [--steps 2e7] [--log-every 10]
                                   [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout|duel|invaders]
                                   [--arcade-mix breakout,duel,invaders] [--arcade-selfplay]
+                                  [--opponent-pool K] [--snapshot-every N]
                                   [--opponent-speed N] [--action-repeat K] [--return-reward R] [--seed S]
                                   [--max-episode-steps N] [--bootstrap-timeouts] [--gae-lambda L]
                                   [--gen-maze N] [--depth-prediction] [--depth-lambda X]
@@ -45,7 +46,11 @@ arcade's options apply to every entry (--return-reward not to invaders, which ha
 and --actors / --groups must be even): actors 2 i and 2 i + 1 play game i against each other.  Before the first update and at
 every logged line it runs Evaluate(net, arcade=name) on 64 actors, one episode each: seat 0 against the scripted opponent,
 the transfer metric of the run; the line then also holds `scripted`, that evaluation's success_rate, losses, timeouts,
-mean_return and mean_length."""
+mean_return, mean_length and points_won_per_episode, and `versus_initial`, Evaluate(net, arcade=name, versus=<a copy of
+the initial weights the tool keeps>) over 32 games head to head: the usual progress measure of a self-play run.
+`--opponent-pool K [--snapshot-every N]` (with --arcade-selfplay) seats K frozen copies of the agent at the
+other paddle, Trainer(opponent_pool=K, opponent_snapshot_every=N): every actor is a learner (odd counts are fine) and a line
+then also holds `opponents`, Trainer.opponent_scores() over the line's matches with every slot's age in updates."""
 import argparse
 import json
 import os
@@ -70,6 +75,8 @@ ap.add_argument("--out", default="")
 ap.add_argument("--arcade", default="", help="a device arcade game (breakout, duel, invaders) instead of the maze")
 ap.add_argument("--arcade-mix", default="", help="a game mixture: a comma list of breakout, duel, invaders (DESIGN 7u)")
 ap.add_argument("--arcade-selfplay", action="store_true", help="the self-play duel (DESIGN 7v)")
+ap.add_argument("--opponent-pool", type=int, default=0, help="with --arcade-selfplay: K frozen copies of the agent play the other paddle (DESIGN 7w)")
+ap.add_argument("--snapshot-every", type=int, default=100, help="optimiser updates between two snapshots into the pool")
 ap.add_argument("--opponent-speed", type=int, default=None, help="the duel's opponent_speed (default: the game's)")
 ap.add_argument("--action-repeat", type=int, default=1, help="arcade: game ticks per agent step, 1..8")
 ap.add_argument("--return-reward", type=int, default=0, help="arcade: reward for a ball the agent's paddle returns, 0..100")
@@ -107,9 +114,12 @@ if mix:
 if args.arcade_selfplay:
     if args.arcade or args.gen_maze:
         ap.error("--arcade-selfplay, --arcade-mix, --arcade and --gen-maze are four environments")
-    if args.actors % 2 or args.groups < 1 or args.actors % args.groups or (args.actors // args.groups) % 2:
+    if not args.opponent_pool and (args.actors % 2 or args.groups < 1 or args.actors % args.groups or
+                                   (args.actors // args.groups) % 2):
         ap.error("--arcade-selfplay: actors come in pairs, --actors and --actors / --groups must be even")
     args.arcade = "selfplay"                              # the registered name; everything arcade below applies to it
+if args.opponent_pool and not args.arcade_selfplay:
+    ap.error("--opponent-pool needs --arcade-selfplay")
 if args.depth_prediction and not args.gen_maze:
     ap.error("--depth-prediction needs a first-person maze: --gen-maze N")
 if args.gen_maze and args.arcade:
@@ -165,7 +175,8 @@ def build_arcade_trainer(args, device):
                  batch_size=args.actors, seed=0xA3C if args.seed is None else args.seed, groups=args.groups,
                  bootstrap_timeouts=args.bootstrap_timeouts, gae_lambda=args.gae_lambda, reuse_epochs=args.reuse_epochs,
                  ppo_clip=args.ppo_clip, normalize_advantages=args.normalize_advantages,
-                 reuse_minibatches=args.reuse_minibatches, **explore)
+                 reuse_minibatches=args.reuse_minibatches, opponent_pool=args.opponent_pool,
+                 opponent_snapshot_every=args.snapshot_every, **explore)
     tr.prepare()
     return flags, net, tr
 
@@ -255,14 +266,28 @@ if out:
 scripted = None
 if args.arcade_selfplay:
     from unreal_amd.evaluate import Evaluate
+    from unreal_amd.model.model import UnrealModel
     scripted_eval = Evaluate(net, batch_size=64, device=device, arcade=args.arcade)
+    # a copy of the initial weights, kept for the whole run: the head-to-head opponent of every logged line
+    initial = UnrealModel(4, 0, -1, flags.use_lstm, flags.use_pixel_change, flags.use_value_replay,
+                          flags.use_reward_prediction, flags.pixel_change_lambda, flags.entropy_beta, device)
+    initial.sync_from(net)
+    versus_eval = Evaluate(net, batch_size=64, device=device, arcade=args.arcade, versus=initial)
 
 
     def scripted():
         """Seat 0 against the scripted opponent, one episode of each of 64 actors."""
         res = scripted_eval.process(0, one_episode_per_actor=True)
-        return {key: round(res[key], 4) for key in ("success_rate", "losses", "timeouts", "mean_return", "mean_length")}
-    line = json.dumps({"global_t": 0, "scripted": scripted()})
+        return {key: round(res[key], 4) for key in ("success_rate", "losses", "timeouts", "mean_return", "mean_length",
+                                                    "points_won_per_episode")}
+
+
+    def versus_initial():
+        """Head to head against the initial weights, one match of each of 32 games."""
+        res = versus_eval.process(0, one_episode_per_actor=True)
+        return {key: round(res[key], 4) for key in ("success_rate", "losses", "timeouts", "points_won_per_episode",
+                                                    "points_lost_per_episode")}
+    line = json.dumps({"global_t": 0, "scripted": scripted(), "versus_initial": versus_initial()})
     print(line, flush=True)
     if out:
         out.write(line + "\n")
@@ -295,7 +320,9 @@ while global_t < args.steps:
             extra.update(tasks=[dict(t, mean_return=None if t["mean_return"] is None else round(t["mean_return"], 4))
                                 for t in tr.task_scores()])
         if scripted is not None:
-            extra.update(scripted=scripted())
+            extra.update(scripted=scripted(), versus_initial=versus_initial())
+        if args.opponent_pool:
+            extra.update(opponents=[dict(o, age=a) for o, a in zip(tr.opponent_scores(), tr.opponent_ages())])
         if args.depth_prediction:
             # the yardstick of depth_accuracy: the share of the most common class among the labels the replay holds
             hist = torch.bincount(tr.full_ring.r_depth.long(), minlength=8).float()

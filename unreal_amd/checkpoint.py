@@ -61,7 +61,8 @@ def next_save_steps(global_t, save_interval_step):
     return (global_t + save_interval_step) // save_interval_step * save_interval_step
 
 
-def save(checkpoint_dir, net, applier, global_t, wall_t, best_score=0.0, name=""):
+def save(checkpoint_dir, net, applier, global_t, wall_t, best_score=0.0, name="", opponents=None):
+    """`opponents`: Trainer.opponent_state() of a trainer with an opponent pool, kept under "opponents"."""
     os.makedirs(checkpoint_dir, exist_ok=True)
     with open(os.path.join(checkpoint_dir, "wall_t." + str(int(global_t))), "w") as f:
         f.write(str(float(wall_t)))
@@ -83,6 +84,10 @@ def save(checkpoint_dir, net, applier, global_t, wall_t, best_score=0.0, name=""
         payload["adam_m"] = None if applier.m is None else applier.m.detach().cpu()
         payload["adam_v"] = None if applier.v is None else applier.v.detach().cpu()
         payload["adam_t"] = int(applier.t)
+    if opponents is not None:
+        payload["opponents"] = dict(params=[t.detach().cpu() for t in opponents["params"]],
+                                    updates=int(opponents["updates"]), snapshots=int(opponents["snapshots"]),
+                                    taken=[int(t) for t in opponents.get("taken", [])] or None)
     path = os.path.join(checkpoint_dir, checkpoint_name(best_score, global_t, name))
     torch.save(payload, path)
     ck = list_checkpoints(checkpoint_dir, name)
@@ -110,8 +115,10 @@ def _check_spec(path, saved, net, saved_shape=None):
                      % (path, shape, "; ".join(diff) if diff else "", names))
 
 
-def restore(checkpoint_dir, net, applier=None, restore_slots=True, name=""):
-    """-> (global_t, wall_t, best_score) of the newest checkpoint, or None if there is none."""
+def restore(checkpoint_dir, net, applier=None, restore_slots=True, name="", opponents=None):
+    """-> (global_t, wall_t, best_score) of the newest checkpoint, or None if there is none.  `opponents`: a prepared
+    Trainer with an opponent pool, whose load_opponent_state() receives the file's "opponents"; a file
+    without the key refills the pool from the restored weights, with a warning."""
     ck = list_checkpoints(checkpoint_dir, name)
     if not ck:
         return None
@@ -142,6 +149,11 @@ def restore(checkpoint_dir, net, applier=None, restore_slots=True, name=""):
         else:                                   # the reference's behaviour: slots restart at 1 / 0
             applier.ms.fill_(1.0)
             applier.mom.zero_()
+    if opponents is not None:
+        d = payload.get("opponents")
+        if d is not None and d.get("taken") is None:
+            d = {k: v for k, v in d.items() if k != "taken"}
+        opponents.load_opponent_state(d)
     wall = os.path.join(checkpoint_dir, "wall_t." + str(global_t))
     wall_t = float(open(wall).read()) if os.path.exists(wall) else 0.0
     assert payload["global_t"] == global_t

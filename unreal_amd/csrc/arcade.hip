@@ -1632,3 +1632,286 @@ int unreal_arcade_selfplay_policy_rollout_step_tl(int B, int H1, const float* X,
 }
 
 }  // extern "C"
+
+// ---- versus: one learner per game, the other paddle an input ----------------------------------------------
+// A launch of B actors holds B games: game b is game actor_base + b of a self-play environment (§7v), its serve draws
+// keyed by 2 (actor_base + b), seat 0's global index there.  The actor is seat 0 and everything it keeps is what seat 0
+// of the self-play entries keeps.  Seat 1 is no actor: its action is opp_actions[b], and of its side only the frame it
+// would see, its last action and its last reward are kept, in three arrays of their own.  One workgroup per game computes
+// the game once and forms both views, the opponent's after the learner's, so that the two render loops' values are not
+// live together.  No workgroup reads a word another workgroup writes.  Everything above this line is what it was.
+namespace {
+
+struct ArcadeVersusArgs {
+  ArcadeArgs a;
+  const int* opp_actions;   // [B] seat 1's action of this step
+  uint8_t* opp_frames;      // [B] frames, 16-byte aligned: seat 1's current observation
+  int* opp_last_action;     // [B]
+  float* opp_last_reward;   // [B]
+};
+
+// step_seat with seat = 0 and the partner's action from opp_actions, then the opponent's three words
+template <bool TL>
+__device__ __forceinline__ void step_versus(const ArcadeVersusArgs& m, uint4* diff, int* s_act) {
+  const ArcadeArgs& p = m.a;
+  const int b = blockIdx.x;
+  const int H1 = p.H1;
+  if (p.pol_x && threadIdx.x < 64) {            // the learner's policy on wave 0, as step_actor
+    const int act = policy_row<4>(p.pol_x + (size_t)b * p.pol_ldx, p.Wp, p.bp, p.Wv, p.bv, p.pol_u + b,
+                                  p.pi_out + (size_t)b * 4, p.v_out + b, threadIdx.x);
+    if (threadIdx.x == 0) { *s_act = act; p.act_out[b] = act; }
+  }
+  const int cnt = p.count[b];
+  const int slot = cnt % H1;
+  const int act_flag = p.active_rw ? p.active_rw[b] : (p.active ? p.active[b] : 1);
+  const int la = p.last_action[b];
+  const float lr = p.last_reward[b];
+  if (!act_flag) {                              // (uniform) idle: the opponent's words stay, too
+    if (threadIdx.x == 0) rollout_idle(p, b, slot, la, lr);
+    return;
+  }
+  int* rec = p.records + (size_t)kArcadeRecord * b;
+  const DuelRules rules = load_seat_rules(p.cfg);
+  const SeatGame own_old = load_seat_game(rec);                     // the stored frame's state (canonical)
+  const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
+  const int steps = p.ep_steps[b] + 1;
+  const int epi = p.episode[b];
+  const int ns = p.active_rw ? p.n_steps[b] : 0;
+  const float ep = p.track_score ? p.episode_reward[b] : 0.f;
+  __syncthreads();                              // the drawn action is in LDS; every thread has read the record
+  const int a = p.pol_x ? *s_act : p.actions[b];
+  const int ap = m.opp_actions[b];
+
+  SeatGame canon = own_old;
+  const SeatRewards rw = step_ticks2(canon, rules, a, ap, 2 * (p.actor_base + b), epi);
+  const float reward = (float)rw.r0;
+  const bool terminal = game_over(canon.g, rules, steps);
+  const DuelGame& old = own_old.g;
+  const DuelGame& g = canon.g;
+  const RingStep ring = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
+  uint8_t* dst = p.frames + ((size_t)b * H1 + ring.nslot) * FRAME_BYTES;
+  const bool cut = TL && ring.reset && !game_ended(g, rules);      // (uniform) ended by the step limit alone
+  uint8_t* fin = TL ? p.final_obs + (size_t)b * FRAME_BYTES : nullptr;
+
+  const auto dirty = frame_dirty(old, g, rules);
+#pragma unroll 1
+  for (int k = 0; k < kChunksPerThread; ++k) {
+    const int c = threadIdx.x + 256 * k;
+    if (c < kChunks) {
+      const uint4 v = frame_chunk(g, rules, c);
+      if (!ring.reset) reinterpret_cast<uint4*>(dst)[c] = v;
+      if constexpr (TL) {
+        if (cut) reinterpret_cast<uint4*>(fin)[c] = v;
+      }
+      diff[c] = make_uint4(diff_dword(old, rules, dirty, 4 * c, v.x), diff_dword(old, rules, dirty, 4 * c + 1, v.y),
+                           diff_dword(old, rules, dirty, 4 * c + 2, v.z), diff_dword(old, rules, dirty, 4 * c + 3, v.w));
+    }
+  }
+  __syncthreads();
+  {                                             // pixel change, as in step_actor
+    const uint32_t* d32 = reinterpret_cast<const uint32_t*>(diff);
+    for (int c = threadIdx.x; c < PC_CELLS; c += 256) {
+      const int i = c / 20, j = c - 20 * i;
+      int sum = 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t* q = d32 + (4 * i + 2 + r) * kRowDw + 3 * j + 1;
+        sum += bytesum(q[0] >> 16) + bytesum(q[1]) + bytesum(q[2]) + bytesum(q[3] & 0xFFFFu);
+      }
+      p.r_pc[ring.base * PC_CELLS + c] = (float)sum / kPcDenom;
+    }
+  }
+  if (ring.reset) {                             // (uniform) the next match's first observation goes into the slot instead
+    canon.g = reset_game(rules, canon.g);
+    store_frame(dst, canon.g, rules);
+  }
+  if (threadIdx.x == 0) {
+    ring_commit(p, b, ring, a, reward, reward, la, lr, ep);
+    store_seat_game(rec, canon);
+    p.ep_steps[b] = ring.reset ? 0 : steps;
+    p.episode[b] = epi + (ring.reset ? 1 : 0);
+    rollout_commit(p, b, ring, ns, a, reward);
+    if constexpr (TL) {
+      if (cut) {                                  // the three words the commits above have set to 1
+        p.r_terminal[ring.base] = 2;
+        if (p.out_terminal) p.out_terminal[b] = 2;
+        p.terminal_end[b] = 2;
+      }
+    }
+    m.opp_last_action[b] = ring.reset ? 0 : ap;     // (zeroed with the learner's where the step resets: what seat 1 keeps)
+    m.opp_last_reward[b] = ring.reset ? 0.f : (float)rw.r1;
+  }
+  // the opponent's view, after the learner's: what seat 1 sees now (the next match's first frame where the step reset)
+  const SeatGame opp = mirror(canon);
+  store_frame(m.opp_frames + (size_t)b * FRAME_BYTES, opp.g, rules);
+}
+
+__global__ __launch_bounds__(256) void arcade_versus_step_kernel(ArcadeVersusArgs m) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act;
+  if (m.a.cfg[0] == kArcadeDuel) step_versus<false>(m, diff, &s_act);   // (uniform) another game's block: nothing is written
+}
+
+__global__ __launch_bounds__(256) void arcade_versus_step_tl_kernel(ArcadeVersusArgs m) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act;
+  if (m.a.cfg[0] == kArcadeDuel) step_versus<true>(m, diff, &s_act);
+}
+
+// reset_game on the canonical record, the learner's frame, then the opponent's mirrored one and its two zeroed words
+__global__ __launch_bounds__(256) void arcade_versus_reset_kernel(ArcadeVersusArgs m) {
+  const ArcadeArgs& p = m.a;
+  if (p.cfg[0] != kArcadeDuel) return;          // (uniform) as in the step
+  const int b = blockIdx.x;
+  if (p.mask && !p.mask[b]) return;
+  int* rec = p.records + (size_t)kArcadeRecord * b;
+  const DuelRules rules = load_seat_rules(p.cfg);
+  SeatGame canon = load_seat_game(rec);
+  const int epi = p.episode[b];
+  __syncthreads();                              // every thread has read the record
+  canon.g = reset_game(rules, canon.g);
+  store_frame(p.frames + ((size_t)b * p.H1 + p.count[b] % p.H1) * FRAME_BYTES, canon.g, rules);
+  if (threadIdx.x == 0) {
+    store_seat_game(rec, canon);
+    p.ep_steps[b] = 0;
+    p.episode[b] = epi + 1;
+    p.last_action[b] = 0;
+    p.last_reward[b] = 0.f;
+    m.opp_last_action[b] = 0;
+    m.opp_last_reward[b] = 0.f;
+  }
+  const SeatGame opp = mirror(canon);
+  store_frame(m.opp_frames + (size_t)b * FRAME_BYTES, opp.g, rules);
+}
+
+// the versus launcher: arcade_launch's tail and checks, and the opponent's four arrays (any B, any actor_base)
+int arcade_versus_launch(ArcadeEntry e, ArcadeArgs& p, const int* cfg, int actor_base, int* ep_steps, int* episode,
+                         int* records, const int* opp_actions, uint8_t* opp_frames, int* opp_last_action,
+                         float* opp_last_reward, void* stream, bool tl = false, uint8_t* final_obs = nullptr) {
+  p.cfg = cfg; p.actor_base = actor_base; p.ep_steps = ep_steps; p.episode = episode; p.records = records;
+  if (tl) p.final_obs = final_obs;
+  if (!arcade_args_ok(e, p)) return UNREAL_EINVAL;
+  if (tl && (!final_obs || ((uintptr_t)final_obs & 15) || (e != kRollout && e != kPolicy))) return UNREAL_EINVAL;
+  if (!opp_frames || ((uintptr_t)opp_frames & 15) || !opp_last_action || !opp_last_reward) return UNREAL_EINVAL;
+  if (e != kReset && !opp_actions) return UNREAL_EINVAL;
+  if ((long long)actor_base + p.B > (1ll << 30)) return UNREAL_EINVAL;   // 2 (actor_base + b) is an int
+  const ArcadeVersusArgs m{p, opp_actions, opp_frames, opp_last_action, opp_last_reward};
+  hipStream_t s = (hipStream_t)stream;
+  if (e == kReset) hipLaunchKernelGGL(arcade_versus_reset_kernel, dim3(p.B), dim3(256), 0, s, m);
+  else if (tl) hipLaunchKernelGGL(arcade_versus_step_tl_kernel, dim3(p.B), dim3(256), 0, s, m);
+  else hipLaunchKernelGGL(arcade_versus_step_kernel, dim3(p.B), dim3(256), 0, s, m);
+  return unreal_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+// Versus: the six arcade entries with the arguments of the plain ones and the opponent's four arrays
+// behind them.
+
+int unreal_arcade_versus_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
+                               const int* count, uint8_t* frames, const int* cfg, int actor_base, int* ep_steps,
+                                 int* episode, int* records, const int* opp_actions, uint8_t* opp_frames,
+                                 int* opp_last_action, float* opp_last_reward, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, const_cast<int*>(count), frames};
+  p.mask = mask;
+  return arcade_versus_launch(kReset, p, cfg, actor_base, ep_steps, episode, records, opp_actions, opp_frames,
+                              opp_last_action, opp_last_reward, stream);
+}
+
+int unreal_arcade_versus_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
+                                float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                                int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                int reset_on_terminal, int track_score, const int* cfg, int actor_base, int* ep_steps,
+                                int* episode, int* records, const int* opp_actions, uint8_t* opp_frames,
+                                int* opp_last_action, float* opp_last_reward, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid,
+               reset_on_terminal, track_score};
+  return arcade_versus_launch(kStep, p, cfg, actor_base, ep_steps, episode, records, opp_actions, opp_frames,
+                              opp_last_action, opp_last_reward, stream);
+}
+
+int unreal_arcade_versus_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                        int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                        int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                        int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                        int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                        float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                                        const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
+                                        const int* opp_actions, uint8_t* opp_frames, int* opp_last_action,
+                                        float* opp_last_reward, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
+  return arcade_versus_launch(kRollout, p, cfg, actor_base, ep_steps, episode, records, opp_actions, opp_frames,
+                              opp_last_action, opp_last_reward, stream);
+}
+
+int unreal_arcade_versus_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                               const float* Wv, const float* bv, const double* u, float* pi_out,
+                                               float* v_out, int* actions_out, int* pos, int* last_action,
+                                               float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                               int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+                                               float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                                               float* score_out, int* score_valid, int* active, int* active_log_t,
+                                               int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
+                                               int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                               int actor_base, int* ep_steps, int* episode, int* records,
+                                               const int* opp_actions, uint8_t* opp_frames, int* opp_last_action,
+                                               float* opp_last_reward, void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
+               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
+  return arcade_versus_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, opp_actions, opp_frames,
+                              opp_last_action, opp_last_reward, stream);
+}
+
+int unreal_arcade_versus_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action,
+                                           float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                                           int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc,
+                                           float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
+                                           int* score_valid, int* active, int* active_log_t, int* n_steps,
+                                           int* terminal_end, int* next_idx, float* next_lar, int lar_ld, int lar_col0,
+                                           int A, int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
+                                           int* episode, int* records, uint8_t* final_obs, const int* opp_actions,
+                                           uint8_t* opp_frames, int* opp_last_action, float* opp_last_reward,
+                                           void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
+  return arcade_versus_launch(kRollout, p, cfg, actor_base, ep_steps, episode, records, opp_actions, opp_frames,
+                              opp_last_action, opp_last_reward, stream, true, final_obs);
+}
+
+int unreal_arcade_versus_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                                  const float* Wv, const float* bv, const double* u, float* pi_out,
+                                                  float* v_out, int* actions_out, int* pos, int* last_action,
+                                                  float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                                  int* r_action, int* r_terminal, int* r_last_action,
+                                                  float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                                                  float* episode_reward, float* score_out, int* score_valid, int* active,
+                                                  int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                                  float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                                                  const int* cfg, int actor_base, int* ep_steps, int* episode,
+                                                  int* records, uint8_t* final_obs, const int* opp_actions,
+                                                  uint8_t* opp_frames, int* opp_last_action, float* opp_last_reward,
+                                                  void* stream) {
+  (void)pos;
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
+               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
+  return arcade_versus_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, opp_actions, opp_frames,
+                              opp_last_action, opp_last_reward, stream, true, final_obs);
+}
+
+}  // extern "C"

@@ -207,16 +207,40 @@ class ArcadeSelfPlay(object):
         return self.scripted.block(seed)
 
 
+class ArcadeOpponent(object):
+    """The other paddle of the B games of a versus environment: `actions` (int32 [B], the input of every step),
+    and what the step keeps of seat 1's side: `frames` (uint8, one frame per game: the observation seat 1 would see),
+    `last_action` (int32 [B]) and `last_reward` (float32 [B]).  Shaped enough like a ring for
+    UnrealModel.encode_rows(..., lar_from_ring=False) to read it with frame index b."""
+
+    def __init__(self, B, device):
+        self.B = B
+        self.frame_shape, self.frame_stride = ops.FRAME_SHAPE, ops.FRAME_BYTES
+        self.actions = torch.zeros(B, dtype=torch.int32, device=device)
+        self.frames = torch.zeros(B * ops.FRAME_BYTES, dtype=torch.uint8, device=device)
+        self.last_action = torch.zeros(B, dtype=torch.int32, device=device)
+        self.last_reward = torch.zeros(B, dtype=torch.float32, device=device)
+
+    def view(self, b0, b1):
+        v = object.__new__(ArcadeOpponent)
+        v.B, v.frame_shape, v.frame_stride = b1 - b0, self.frame_shape, self.frame_stride
+        v.actions, v.last_action, v.last_reward = self.actions[b0:b1], self.last_action[b0:b1], self.last_reward[b0:b1]
+        v.frames = self.frames[b0 * ops.FRAME_BYTES:b1 * ops.FRAME_BYTES]
+        return v
+
+
 class BatchedArcadeEnvironment(object):
     """B actors of one arcade game, of a game mixture (ArcadeMix) or of B / 2 self-play games (ArcadeSelfPlay: actors
     2 i and 2 i + 1 are the seats of game i, so B, actor_base and a view's bounds are even), on the device, with the
-    interface of BatchedMazeEnvironment."""
+    interface of BatchedMazeEnvironment.  `versus=True` (an ArcadeSelfPlay only): B games with one actor
+    each, seat 0 of game actor_base + b of the self-play environment; the other paddle plays `.opponent.actions`, and
+    B, actor_base and a view's bounds may be odd."""
     ACTION_SIZE = 4
     frame_scale = 1.0 / 255.0          # ring bytes 0..255
     objective_size = 0
 
     def __init__(self, batch, history_size, device="cuda:0", config=None, actor_base=0, actors_total=None, seed=0,
-                 final_obs=False, depth_labels=False, bonus=False):
+                 final_obs=False, depth_labels=False, bonus=False, versus=False):
         """`bonus`: exploration bonus: the ring keeps r_bonus beside r_reward.
         `actor_base` / `actors_total`: global index of actor 0 and the number of actors over every rank (the serve
         draws are keyed by the global index); `seed`: their key.  `final_obs`: time-limit bootstrapping: the
@@ -228,7 +252,9 @@ class BatchedArcadeEnvironment(object):
         if not isinstance(config, (ArcadeConfig, ArcadeMix, ArcadeSelfPlay)):
             raise ValueError("BatchedArcadeEnvironment needs an ArcadeConfig, an ArcadeMix or an ArcadeSelfPlay")
         selfplay = isinstance(config, ArcadeSelfPlay)
-        if selfplay and (batch % 2 or actor_base % 2):
+        if versus and not selfplay:
+            raise ValueError("versus=True needs an ArcadeSelfPlay config: the other paddle is a self-play game's seat 1")
+        if selfplay and not versus and (batch % 2 or actor_base % 2):
             raise ValueError("self-play actors come in pairs: batch = %d and actor_base = %d must be even"
                              % (batch, actor_base))
         self.B = batch
@@ -242,19 +268,24 @@ class BatchedArcadeEnvironment(object):
         block = torch.from_numpy(config.block(seed)).to(self.ring.count.device)
         # a mixture: (K blocks, actor_base, K), which selects the _mix entries (ops._arcade_args); self-play: (block,
         # actor_base, ops.ARCADE_SELFPLAY), which selects the _selfplay entries
-        self.arcade = (block, int(actor_base)) + ((len(config),) if mix else (ops.ARCADE_SELFPLAY,) if selfplay else ())
+        # versus: (block, actor_base, ops.ARCADE_VERSUS, the opponent's buffers), which selects the _versus entries
+        self.opponent = ArcadeOpponent(batch, self.ring.count.device) if versus else None
+        self.arcade = (block, int(actor_base)) + ((len(config),) if mix else (ops.ARCADE_VERSUS, self.opponent) if versus
+                                                  else (ops.ARCADE_SELFPLAY,) if selfplay else ())
         self.reset()
 
     def view(self, b0, b1):
         """The environments [b0, b1) as a batched environment of their own (shares the ring memory), as
         BatchedMazeEnvironment.view."""
-        if isinstance(self.config, ArcadeSelfPlay) and (b0 % 2 or b1 % 2):
+        versus = getattr(self, "opponent", None) is not None
+        if isinstance(self.config, ArcadeSelfPlay) and not versus and (b0 % 2 or b1 % 2):
             raise ValueError("a view of a self-play environment holds whole pairs: [%d, %d) has an odd bound" % (b0, b1))
         v = object.__new__(BatchedArcadeEnvironment)
         v.B, v.ring = b1 - b0, ops.ring_view(self.ring, b0, b1)
         v.base_actor = b0
         v.config = self.config
-        v.arcade = (self.arcade[0], self.arcade[1] + b0) + self.arcade[2:]
+        v.opponent = self.opponent.view(b0, b1) if versus else None
+        v.arcade = (self.arcade[0], self.arcade[1] + b0) + ((ops.ARCADE_VERSUS, v.opponent) if versus else self.arcade[2:])
         return v
 
     def task_of_actor(self):
@@ -298,7 +329,8 @@ class BatchedArcadeEnvironment(object):
         then the running totals of aliens shot, lives lost and waves cleared, then the three bombs as x | y << 8 (0: free).
         Self-play: one duel record per SEAT; rows 2 i hold game i's canonical record (seat 0 at the bottom),
         rows 2 i + 1 its mirror image, the game as seat 1 sees it (px and ox, mine and theirs, words 10 and 11, words 12
-        and 13 swapped, by = 86 - by, vy = -vy); word 13 is the other seat's matches won, words 14..15 are 0."""
+        and 13 swapped, by = 86 - by, vy = -vy); word 13 is the other seat's matches won, words 14..15 are 0.  Versus (DESIGN
+        §7w): row b holds game b's canonical record."""
         return self.ring.actor_records.cpu().numpy().copy()
 
     def stop(self):

@@ -253,6 +253,7 @@ ARCADE_BOMB_STREAM = 0x494E5642              # counter word 2 of an invaders bom
 ARCADE_SERVE_STREAM = 0x41524B53             # counter word 2 of a serve draw (UNREAL_ARCADE_SERVE_STREAM)
 ARCADE_MIX_MAX = 16                          # config blocks of a game mixture at the most (UNREAL_ARCADE_MIX_MAX)
 ARCADE_SELFPLAY = "selfplay"                 # third element of the arcade tuple that selects the _selfplay entries (§7v)
+ARCADE_VERSUS = "versus"                     # ... the _versus entries (§7w); a fourth element holds the opponent's buffers
 MAZE_TOP_DOWN, MAZE_FIRST_PERSON = 0, 1       # the `view` of a maze (UNREAL_MAZE_TOP_DOWN / UNREAL_MAZE_FIRST_PERSON)
 MAZE_FIRST_PERSON_GENERATED = 2               # first person, a generated block (UNREAL_MAZE_FIRST_PERSON_GENERATED)
 # goal-sense blocks: UNREAL_MAZE_FIRST_PERSON_SENSE / UNREAL_MAZE_FIRST_PERSON_GENERATED_SENSE
@@ -478,17 +479,31 @@ def maze_policy_rollout_step_encode(ring, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_o
 
 # ---- device arcade (csrc/arcade.hip) -----------------------------------------------------------------------
 def _arcade_args(ring, arcade, stats=True):
-    """-> ("", "_mix" or "_selfplay", the tail of the arcade entry of that name, the arguments behind its `records` and
+    """-> ("", "_mix", "_selfplay" or "_versus", the tail of the arcade entry of that name, the arguments behind its `records` and
     final_obs).
     `arcade` = (int32 config block on the device, global index of the ring's actor 0), which selects the plain entries, or
     (K consecutive blocks, that index, K), a game mixture, which selects the _mix entries: global actor g
     plays block g % K, and the step forms (`stats`) also take the ring's done_return / done_episodes (None without
     Ring(arcade_stats=True)); or (the duel's block, that index, ARCADE_SELFPLAY), self-play, which selects
     the _selfplay entries: global actors 2 i and 2 i + 1 are the two seats of game i (the entries refuse an odd actor count
-    or index)."""
+    or index); or (the duel's block, that index, ARCADE_VERSUS, opponent), one learner per game, which
+    selects the _versus entries: `opponent` holds actions, last_action (int32 [B]), last_reward (float32 [B]) and frames
+    (uint8 [B * FRAME_BYTES]), whose pointers follow every other argument, in reset too."""
     K = None
     selfplay = len(arcade) == 3 and isinstance(arcade[2], str)
-    if selfplay:
+    if len(arcade) == 4:
+        block, actor_base, tag, opp = arcade
+        if tag != ARCADE_VERSUS:
+            raise ValueError("arcade tuple: unknown entry family %r" % (tag,))
+        _chk(block, "i32", ARCADE_CFG_WORDS, "arcade config")
+        _chk(opp.actions, "i32", ring.B, "opponent.actions")
+        _chk(opp.frames, "u8", ring.B * FRAME_BYTES, "opponent.frames")
+        _chk(opp.last_action, "i32", ring.B, "opponent.last_action")
+        _chk(opp.last_reward, "f32", ring.B, "opponent.last_reward")
+        if opp.frames.data_ptr() % 16:
+            raise ValueError("opponent.frames must be 16-byte aligned")
+        versus = (ptr(opp.actions), ptr(opp.frames), ptr(opp.last_action), ptr(opp.last_reward))
+    elif selfplay:
         block, actor_base, tag = arcade
         if tag != ARCADE_SELFPLAY:
             raise ValueError("arcade tuple: unknown entry family %r" % (tag,))
@@ -507,6 +522,8 @@ def _arcade_args(ring, arcade, stats=True):
     if actor_base < 0:
         raise ValueError("actor_base %d < 0" % actor_base)
     tail = (int(actor_base), ptr(ring.ep_steps), ptr(ring.episode), ptr(ring.arcade))
+    if len(arcade) == 4:
+        return "_versus", (ptr(block),) + tail, versus
     if K is None:
         return "_selfplay" if selfplay else "", (ptr(block),) + tail, ()
     done_return, done_episodes = getattr(ring, "done_return", None), getattr(ring, "done_episodes", None)
@@ -520,9 +537,9 @@ def _arcade_args(ring, arcade, stats=True):
 def arcade_reset(ring, mask=None, arcade=None):
     """Start a new episode of every actor (where mask != 0)."""
     _chk(mask, "i32", ring.B, "mask", optional=True)
-    mix, tail, _ = _arcade_args(ring, arcade, stats=False)
+    mix, tail, opp = _arcade_args(ring, arcade, stats=False)       # (what follows the tail: the _versus entries' alone)
     _call("unreal_arcade%s_reset" % mix, ring.B, ring.H1, ptr(mask), ptr(ring.pos), ptr(ring.last_action),
-          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), *tail)
+          ptr(ring.last_reward), ptr(ring.count), ptr(ring.frames), *tail, *opp)
 
 
 def arcade_step(ring, actions, active=None, out_reward=None, out_terminal=None, reset_on_terminal=True,

@@ -76,6 +76,9 @@ def get_options(option_type="training", preset="lab", argv=()):
         a("--adam_epsilon", type=float, default=1e-8)
         a("--weight_decay", type=float, default=0.0)
         a("--normalize_advantages", type=_bool, default=False)
+        # not in the reference, off by default: Trainer(opponent_pool=..., opponent_snapshot_every=...)
+        a("--opponent_pool", type=int, default=0)
+        a("--opponent_snapshot_every", type=int, default=100)
     if option_type == "display":
         a("--frame_save_dir", default="/tmp/unreal_frames")
         a("--recording", type=_bool, default=False)

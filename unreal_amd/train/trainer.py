@@ -170,6 +170,48 @@ class Trainer(PassState):
                              "must be even" % (B, B, G))
         return True
 
+    MAX_OPPONENTS = 16
+
+    @staticmethod
+    def check_opponent_options(env_type, env_name, batch_size, groups, opponent_pool, opponent_snapshot_every=100):
+        """-> (opponent_pool K, opponent_snapshot_every N) as the trainer keeps them.  K = 0: no pool (N is
+        still checked).  ValueError for what is out of scope: K no int in 0..16, N no int >= 1; K > 0 on anything but
+        env_type 'arcade' with a self-play name (Environment.register_arcade_selfplay; host-fed environments own their
+        opponents), or a K that does not divide the batch_size // groups actors of a group."""
+        K, N = opponent_pool, opponent_snapshot_every
+        if isinstance(K, bool) or not isinstance(K, int) or not 0 <= K <= Trainer.MAX_OPPONENTS:
+            raise ValueError("opponent_pool = %r: an int in 0..%d" % (K, Trainer.MAX_OPPONENTS))
+        if isinstance(N, bool) or not isinstance(N, int) or N < 1:
+            raise ValueError("opponent_snapshot_every = %r: an int >= 1 (optimiser updates)" % (N,))
+        if K == 0:
+            return 0, N
+        if env_type != "arcade" or getattr(Environment.arcade_config(env_name), "game", None) != "selfplay":
+            raise ValueError("opponent_pool = %d needs env_type='arcade' with a self-play game (Environment."
+                             "register_arcade_selfplay), not %r / %r" % (K, env_type, env_name))
+        B, G = int(batch_size), int(groups)
+        if G < 1 or B % G or (B // G) % K:
+            raise ValueError("opponent_pool = %d must divide the %d // %d actors of a group" % (K, B, G))
+        return K, N
+
+    @staticmethod
+    def opponent_slots(Bg, K):
+        """The pool slot every row of a group plays against -> a list of Bg ints: rows [k Bg / K, (k + 1) Bg / K) play
+        slot k.  A function of the index alone, as the mixtures' tasks are.  ValueError unless K in 1..16 divides Bg."""
+        if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= Trainer.MAX_OPPONENTS or Bg < 1 or Bg % K:
+            raise ValueError("opponent_pool = %r must be in 1..%d and divide the %d actors of a group"
+                             % (K, Trainer.MAX_OPPONENTS, Bg))
+        return [b // (Bg // K) for b in range(Bg)]
+
+    @staticmethod
+    def opponent_snapshot(K, N, updates, snapshots):
+        """The pool's rule at the end of a process() call -> (slot the current weights go into, or None; the new number
+        of snapshots).  With u = `updates` applied so far and s = `snapshots` taken: if u // N > s, slot 1 + (s mod (K - 1))
+        is overwritten and s becomes u // N (a call that crosses several multiples of N takes one snapshot).  Slot 0 is
+        the present self and K = 1 never snapshots."""
+        if K < 2 or updates // N <= snapshots:
+            return None, snapshots
+        return 1 + snapshots % (K - 1), updates // N
+
     @staticmethod
     def minibatch_order(epoch, M):
         """The blocks of a group's actors in the order epoch `epoch` (1-based) visits them: (i + epoch - 1) mod M."""
@@ -219,7 +261,11 @@ class Trainer(PassState):
                  grad_sync=None, simulator=None, groups=1, overlap_host=None, bootstrap_timeouts=False, gae_lambda=None,
                  use_depth_prediction=False, depth_lambda=1.0, reuse_epochs=1, ppo_clip=0.2, explore_beta=0.0,
                  explore_cell=7, explore_levels=8, explore_bits=22, normalize_advantages=False, adv_norm_eps=1e-8,
-                 reuse_minibatches=1):
+                 reuse_minibatches=1, opponent_pool=0, opponent_snapshot_every=100):
+        # opponent pool, off by default: every game has one learner, the other paddle is played by one of
+        # opponent_pool frozen copies of the network, refreshed every opponent_snapshot_every updates
+        self.opponent_pool, self.opponent_snapshot_every = self.check_opponent_options(
+            env_type, env_name, batch_size, groups, opponent_pool, opponent_snapshot_every)
         # minibatched reuse epochs, off by default: a rollout is consumed as reuse_epochs * reuse_minibatches
         # clipped-surrogate updates, each on one block of the group's actors
         self.reuse_minibatches = self.check_minibatch_options(env_type, batch_size, groups, reuse_minibatches)
@@ -292,7 +338,10 @@ class Trainer(PassState):
             raise NotImplementedError("groups > 1 needs an environment that steps a sub-range of its actors (maze, "
                                       "arcade)")
         self.Bg = self.B // self.groups              # actors per group = batch of every kernel launch
-        self.selfplay = self.check_selfplay_options(env_type, env_name, self.B, self.groups)
+        # (with a pool every actor is a learner: the pairs' even-count rule does not apply)
+        self.selfplay = True if self.opponent_pool else self.check_selfplay_options(env_type, env_name, self.B,
+                                                                                    self.groups)
+        self.updates = 0                             # optimiser updates applied so far (the pool's clock)
         self.world_size, self.rank = int(world_size), int(rank)
         self.grad_scale = 1.0 / float(self.Bg * self.world_size)
         self.grad_sync = grad_sync
@@ -335,7 +384,7 @@ class Trainer(PassState):
                                                         config=Environment.arcade_config(self.env_name),
                                                         actor_base=self.rank * B, actors_total=self.world_size * B,
                                                         seed=self.seed, final_obs=self.bootstrap_timeouts,
-                                                        bonus=self.explore_beta > 0)
+                                                        bonus=self.explore_beta > 0, versus=self.opponent_pool > 0)
         else:
             from ..environment.hostfed_environment import HostFedEnvironment
             indoor = self.env_type == "indoor"
@@ -425,8 +474,155 @@ class Trainer(PassState):
             Bm = self.Bg // self.reuse_minibatches
             self._block_views = [[(ops.ring_view(env.ring, m * Bm, (m + 1) * Bm), b0 + m * Bm)
                                   for m in range(self.reuse_minibatches)] for env, _, _, b0 in self._group_views]
+        if self.opponent_pool:
+            self._prepare_opponents()
         self._select_group(0)
         self._rollout_split_setup()
+
+    # ---- opponent pool ---------------------------------------------------------------------
+    def _prepare_opponents(self):
+        """K frozen copies of the network, a workspace per slot for Bg / K rows, LSTM state for all B opponents, the
+        opponents' own draws and the buffers of a group's rollout."""
+        from ..model.model import UnrealModel
+        K, B, Bg, A, dev, net = self.opponent_pool, self.B, self.Bg, self.action_size, self.device, self.local_network
+        T, Bk = self.n_step_TD, self.Bg // self.opponent_pool
+        self.opponents = []
+        for k in range(K):
+            o = UnrealModel(A, net._objective_size, -1 - k, net._use_lstm, net._use_pixel_change, net._use_value_replay,
+                            net._use_reward_prediction, net._pixel_change_lambda, net._entropy_beta, dev,
+                            image_shape=net.image_shape, use_depth_prediction=net._use_depth_prediction)
+            o.lar_bounded = False                    # a step can pay more than 1 (as Evaluate binds `versus`)
+            o.bind_frame_scale(self.full_environment.frame_scale)
+            o.sync_from(net)
+            self.opponents.append(o)
+        self.opponent_snapshots = 0                  # snapshots taken so far
+        self._opp_taken = [0] * K                    # the update count every slot's weights are from
+        self._opp_ws = [PathWS(Bk, Bk, dev, save_c1=False, lstm=self.use_lstm, xld=net.xld, **net.ws_kw) for _ in range(K)]
+        for ws in self._opp_ws:                      # opponent.frames of a block is read with frame index b
+            ws.frame_idx[:Bk].copy_(torch.arange(Bk, dtype=torch.int32))
+        f = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
+        self.full_opp_c, self.full_opp_h = f(B * 256), f(B * 256)
+        self.opp_pi, self.opp_v = f(Bg * A), f(Bg)
+        self.opp_u = torch.zeros(T * Bg, dtype=torch.float64, device=dev)
+        self.opponent_actions = torch.zeros(T * Bg, dtype=torch.int32, device=dev)
+        # a stream of the opponents' own, keyed like the learner's by rank and batch: the learner's draws are what they
+        # are without a pool
+        self.opp_draws = PhiloxDraws(self.seed ^ 0x4F505053, self.rank, self.B, self.world_size)
+        # per group and slot: the block's opponent buffers and LSTM state
+        self._opp_views = []
+        for env, _, _, b0 in self._group_views:
+            blocks = []
+            for k in range(K):
+                r0, g0 = k * Bk, b0 + k * Bk
+                blocks.append((env.opponent.view(r0, r0 + Bk), self.full_opp_c[g0 * 256:(g0 + Bk) * 256],
+                               self.full_opp_h[g0 * 256:(g0 + Bk) * 256]))
+            self._opp_views.append(blocks)
+        # the learners' match totals (record words 12, 13) at the last opponent_scores(reset=True)
+        self._opp_score_base = self.full_ring.actor_records[:, 12:14].clone()
+
+    def _opponents_act(self, u, log=None):
+        """Step 1 of an environment step with a pool: every slot's network on its block's opponent.frames (encoder, fc,
+        LSTM step from the block's carried state, policy and draw with `u` [Bg]) -> opponent.actions (and `log` [Bg])."""
+        Bk = self.Bg // self.opponent_pool
+        for k, (net, ws, (opp, c, h)) in enumerate(zip(self.opponents, self._opp_ws, self._opp_views[self.group])):
+            net.begin_pass()
+            if self.use_lstm:
+                ops.copy_(ws.c0, c)
+                ops.copy_(ws.h0, h)
+            net.encode_rows(opp, ws, 0, Bk, lar_from_ring=False, save_c1=False, lstm_x=False)
+            if self.use_lstm:
+                net.lstm_step(ws, 0, Bk, fused_x=True)
+            feat, ld = net.features(ws, 0)
+            r0 = k * Bk
+            net.policy_step(Bk, feat, ld, u[r0:r0 + Bk], self.opp_pi[r0 * 4:(r0 + Bk) * 4], self.opp_v[r0:r0 + Bk],
+                            opp.actions)
+        if log is not None:
+            ops.copy_(log, self.environment.opponent.actions)
+
+    def _opponents_carry(self, terminals):
+        """Step 3: the opponents' LSTM state advances and is zeroed where `terminals` != 0 (flag 2 included).  The fill
+        passes the step's terminals; the rollout passes terminal_end, which stays set for the rest of the rollout once
+        an actor's match has ended, so the opponent of an actor that sits the remaining steps out starts the next call,
+        the next match's first step, from zero state."""
+        if not self.use_lstm:
+            return
+        Bk = self.Bg // self.opponent_pool
+        for k, (ws, (opp, c, h)) in enumerate(zip(self._opp_ws, self._opp_views[self.group])):
+            ops.copy_(c, ws.c[:Bk * 256])
+            ops.copy_(h, ws.h[:Bk * 256])
+            ops.reset_state(Bk, terminals[k * Bk:(k + 1) * Bk], c, h)
+
+    def _refresh_present_self(self):
+        """Slot 0 is the present self: at the start of every process() call it equals the learner's weights."""
+        self.opponents[0].sync_from(self.local_network)
+        self._opp_taken[0] = self.updates
+        for o in self.opponents:
+            o.refresh_shadows(only_if_stale=True)
+
+    def _snapshot_opponents(self):
+        """The end of a process() call: the pool's rule (opponent_snapshot)."""
+        slot, self.opponent_snapshots = self.opponent_snapshot(self.opponent_pool, self.opponent_snapshot_every,
+                                                               self.updates, self.opponent_snapshots)
+        if slot is not None:
+            self.opponents[slot].sync_from(self.local_network)
+            self._opp_taken[slot] = self.updates
+
+    def _need_pool(self):
+        if not self.opponent_pool or self.environment is None:
+            raise ValueError("needs a prepared trainer with an opponent pool (Trainer(opponent_pool=K > 0))")
+
+    def opponent(self, k):
+        """Slot k's frozen network, usable as Evaluate(net, arcade=name, versus=tr.opponent(k))."""
+        self._need_pool()
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < self.opponent_pool:
+            raise ValueError("opponent slot %r outside 0..%d" % (k, self.opponent_pool - 1))
+        return self.opponents[k]
+
+    def opponent_ages(self):
+        """Per slot: how many optimiser updates ago its weights were the learner's."""
+        self._need_pool()
+        return [self.updates - t for t in self._opp_taken]
+
+    def opponent_scores(self, reset=True):
+        """Per slot: matches won and lost by the learners of its blocks (this rank's, over every group) since the last
+        reset -> a list of dict(slot, won, lost), from the differences of record words 12 and 13.  One device read."""
+        self._need_pool()
+        rec = self.full_ring.actor_records[:, 12:14]
+        gain = (rec - self._opp_score_base).cpu().numpy().reshape(self.groups, self.opponent_pool, -1, 2)
+        if reset:
+            self._opp_score_base.copy_(rec)
+        return [dict(slot=k, won=int(gain[:, k, :, 0].sum()), lost=int(gain[:, k, :, 1].sum()))
+                for k in range(self.opponent_pool)]
+
+    def opponent_state(self):
+        """What a checkpoint carries of the pool: the K flat parameter vectors, the update count u and the snapshot
+        count s (and the update count every slot is from)."""
+        self._need_pool()
+        return dict(params=[o.params.flat.detach().cpu().clone() for o in self.opponents], updates=int(self.updates),
+                    snapshots=int(self.opponent_snapshots), taken=[int(t) for t in self._opp_taken])
+
+    def load_opponent_state(self, d):
+        """The inverse of opponent_state().  `d` None (a checkpoint written without a pool): every slot is refilled from
+        the network's present weights, with a warning."""
+        self._need_pool()
+        if d is None:
+            import warnings
+            warnings.warn("the checkpoint holds no opponent pool: every slot restarts from the restored weights")
+            for o in self.opponents:
+                o.sync_from(self.local_network)
+            self._opp_taken = [self.updates] * self.opponent_pool
+            self.opponent_snapshots = self.updates // self.opponent_snapshot_every
+            return
+        if len(d["params"]) != self.opponent_pool:
+            raise ValueError("the checkpoint's pool holds %d slots, this trainer's %d" % (len(d["params"]), self.opponent_pool))
+        for o, flat in zip(self.opponents, d["params"]):
+            if flat.numel() != o.params.flat.numel():
+                raise ValueError("the checkpoint's pool holds networks of %d parameters, not %d"
+                                 % (flat.numel(), o.params.flat.numel()))
+            o.params.flat.copy_(flat)
+            o.mark_params_changed()
+        self.updates, self.opponent_snapshots = int(d["updates"]), int(d["snapshots"])
+        self._opp_taken = [int(t) for t in d.get("taken", [self.updates] * self.opponent_pool)]
 
     def _alloc_pass(self, c, B, reuse):
         """The workspaces and buffers of the loss branches of one update over B actors, as attributes of `c`: the trainer
@@ -548,6 +744,9 @@ class Trainer(PassState):
         if self._own_draws:
             self.draws.batch = batch
             self.draws.col0 = self.rank * self.B + b0
+        if self.opponent_pool and batch == self.Bg and getattr(self, "opp_draws", None) is not None:
+            self.opp_draws.batch = batch             # (the opponents draw per group, never per minibatch block)
+            self.opp_draws.col0 = self.rank * self.B + b0
 
     def stop(self):
         if self.environment is not None:
@@ -638,12 +837,17 @@ class Trainer(PassState):
             ops.copy_(ws.c0, self.lstm_c)
             ops.copy_(ws.h0, self.lstm_h)
         self.draws.uniform(self.u_act[:B])
+        if self.opponent_pool:                 # the opponents move first
+            self.opp_draws.uniform(self.opp_u[:B])
+            self._opponents_act(self.opp_u[:B], self.opponent_actions[:B])
         self._policy_step(ws, 0, self.u_act[:B], self.actions[:B], self.pi[:B * self.action_size], self.v[:B])
         self.environment.process(self.actions[:B], None, self.rewards[:B], self.terminals[:B],
                                  reset_on_terminal=True, track_score=False)
         if self.use_lstm:                      # state advances; NOT reset on terminal here (:201-202)
             ops.copy_(self.lstm_c, ws.c[:B * 256])
             ops.copy_(self.lstm_h, ws.h[:B * 256])
+        if self.opponent_pool:
+            self._opponents_carry(self.terminals[:B])
 
     def _rollout_steps_overlapped(self):
         """The T rollout steps for host-fed actors in two half-batches: while the host steps / stages one half (its
@@ -719,6 +923,8 @@ class Trainer(PassState):
             return
         if self.bootstrap_timeouts:            # so does time-limit bootstrapping
             return
+        if self.opponent_pool:                 # and the opponent pool
+            return
         Bp = self.Bg // n_parts
         streams = [torch.cuda.Stream(device=self.device) for _ in range(n_parts)]
         self._split = []
@@ -777,6 +983,9 @@ class Trainer(PassState):
         self.n_steps.zero_()
         self.terminal_end.zero_()
         self.draws.uniform(self.u_act)
+        pool = self.opponent_pool > 0
+        if pool:
+            self.opp_draws.uniform(self.opp_u)
         if self.overlap_host:
             self._rollout_steps_overlapped()
         split = getattr(self, "_split", None) is not None
@@ -791,6 +1000,8 @@ class Trainer(PassState):
         encoded = False
         for t in range(0 if not (self.overlap_host or split) else T, T):
             s = slice(t * B, (t + 1) * B)
+            if pool:                           # the opponents move first; their state is carried after the step
+                self._opponents_act(self.opp_u[s], self.opponent_actions[s])
             feat, ld = self._policy_step(ws, t, self.u_act[s], self.actions[s], self.pi[t * B * A:(t + 1) * B * A],
                                          self.v[s], prefilled=fused and t > 0, heads=not fuse_policy, encoded=encoded)
             encoded = False
@@ -815,9 +1026,11 @@ class Trainer(PassState):
                                                          self.v[s], self.actions[s], self.rewards[s], self.terminals[s],
                                                          self.active, self.active_log[s], self.n_steps, self.terminal_end,
                                                          **nxt)
-                    continue
-                self.environment.rollout_step(self.actions[s], self.rewards[s], self.terminals[s], self.active,
-                                              self.active_log[s], self.n_steps, self.terminal_end, **nxt)
+                else:
+                    self.environment.rollout_step(self.actions[s], self.rewards[s], self.terminals[s], self.active,
+                                                  self.active_log[s], self.n_steps, self.terminal_end, **nxt)
+                if pool:
+                    self._opponents_carry(self.terminal_end)
                 continue
             self.environment.process(self.actions[s], self.active, self.rewards[s], self.terminals[s],
                                      reset_on_terminal=True, track_score=True)
@@ -1170,6 +1383,7 @@ class Trainer(PassState):
                 self._sync_events.append((e0, e1))
         self.last_grad_norm = self.grad_applier.step(net.params.flat, net.grads.flat, lr)
         net.mark_params_changed()
+        self.updates += 1
 
     def process(self, sess=None, global_t=0, summary_writer=None, summary_op_dict=None, score_input=None,
                 sr_input=None, eval_input=None, entropy_input=None, term_global_t=None, losses_input=None,
@@ -1181,6 +1395,8 @@ class Trainer(PassState):
             self._fill_experience(sess)
             return 0, None
         G, E, M = self.groups, self.reuse_epochs, self.reuse_minibatches
+        if self.opponent_pool:
+            self._refresh_present_self()
         if G > 1 or E > 1 or M > 1:
             self.loss_sum.zero_()
         if E > 1 or M > 1:
@@ -1222,6 +1438,8 @@ class Trainer(PassState):
                     torch.cuda.current_stream().synchronize()
         if G > 1:
             self._select_group(0)
+        if self.opponent_pool:
+            self._snapshot_opponents()
         if not sync_stats:                               # stats keep accumulating on the device
             return None, None
         steps, episodes, score_sum = self.read_stats()
