@@ -2,10 +2,12 @@
 produces its local mean gradient in the product's flat layout (the per-actor gradients come from the
 oracle here -- the HIP kernels need a GPU), and the product's exchange step (`parallel.all_reduce_sum`,
 the one collective of the path) must reproduce the single-process mean over ALL actors."""
+import inspect
 import os
 import socket
 
 import numpy as np
+import pytest
 import torch
 import torch.multiprocessing as mp
 
@@ -86,3 +88,135 @@ def test_two_rank_gradient_exchange_equals_global_mean():
         assert tot_steps == steps and mx == world - 1
     np.testing.assert_array_equal(res[0][1], res[1][1])       # replicas stay bit-identical
     assert np.abs(ref.numpy()).max() > 0
+
+
+# ---- the reference side of tests/test_sharded_gpu.py's family A ---------------------------------------------------------------
+# A rank > 0 shard is held against host_batch(conf, B, actor_base=B, actors_total=2B).  That is evidence only if the models'
+# own actor_base handling is right: the models B .. 2B-1 of one batch of 2B must be the same actors.
+_ROOMS = [["+++++++", "+++++++", "++--G++", "++-S-++", "++---++", "+++++++", "+++++++"],
+          ["+++++++", "++G--++", "++-S-++", "++---++", "++---++", "+++++++", "+++++++"],
+          ["+++++++", "+++++++", "+----++", "+--S-++", "+G---++", "+++++++", "+++++++"]]
+_NAV_ROOM = ["+++++++", "+++++++", "++A-G++", "++-SA++", "++A-A++", "+++++++", "+++++++"]
+_FORAGE_ROOM = ["+++++++", "+++++++", "++ABA++", "++-SB++", "++A-C++", "+++++++", "+++++++"]
+_NAV_KW = dict(view="first_person", goal_reward=10, apple_reward=1, hit_reward=0, action_set="lab", show_goal=True,
+               random_start=True, max_episode_steps=7)
+_STYLES = [(200, 100, 50, 0xAA), (0, 255, 0, 0x00), (255, 255, 255, 0xFF), (10, 20, 250, 0x0F)]
+_GEN_KW = dict(random_start=True, random_goal=True, view="first_person", generate=7, gen_loops=2, show_goal=True,
+               max_episode_steps=7)
+
+
+def _host_batch_cases():
+    """-> [(id, model module name, config factory, action count, extra host_batch keywords)]"""
+    def maze(layouts, **kw):
+        def make():
+            from unreal_amd.environment.maze_environment import MazeConfig
+            return MazeConfig(layouts, **kw)
+        return make
+
+    def arcade(**kw):
+        def make():
+            from unreal_amd.environment.arcade_environment import ArcadeConfig
+            return ArcadeConfig(**kw)
+        return make
+
+    def mix():
+        from unreal_amd.environment.arcade_environment import ArcadeConfig, ArcadeMix
+        import mix_model
+        return ArcadeMix([ArcadeConfig(**dict(s, max_episode_steps=m)) for s, m in zip(mix_model.MIX3, (9, 7, 8))])
+
+    def selfplay():
+        from unreal_amd.environment.arcade_environment import ArcadeSelfPlay
+        return ArcadeSelfPlay(points=2, paddle_width=24, ball_speed=4, serve_wait=1, win_reward=7, lose_reward=-3,
+                              max_episode_steps=9)
+    short = dict(paddle_width=24, ball_speed=4, serve_wait=1, max_episode_steps=12)
+    return [
+        ("topdown", "maze_model", maze(_ROOMS, random_start=True, random_goal=True, max_episode_steps=7), 4, {}),
+        ("first_person", "fp_maze_model", maze(_ROOMS, view="first_person", show_goal=True, random_start=True,
+                                               max_episode_steps=7), 4, {}),
+        ("navigation", "nav_maze_model", maze([_NAV_ROOM], goal_respawn=True, **_NAV_KW), 6, {}),
+        ("generated", "gen_maze_model", maze(None, **_GEN_KW), 4, {}),
+        ("styled", "styled_maze_model", maze(None, wall_styles=_STYLES, gen_landmark_density=128, **_GEN_KW), 4, {}),
+        ("goal_sense", "goal_maze_model", maze([_NAV_ROOM], goal_sense=True, progress_reward=1, **_NAV_KW), 6, {}),
+        ("forage", "forage_maze_model", maze([_FORAGE_ROOM], view="first_person", no_goal=True, apple_reward=1, hit_reward=0,
+                                             action_set="lab", random_start=True, max_episode_steps=7,
+                                             pickups=[(-1, (255, 255, 0), False), (20, (255, 0, 255), True)]), 6, {}),
+        ("breakout", "arcade_model", arcade(rows=2, row_rewards=(7, 1), lives=1, life_reward=-1, **short), 4, {}),
+        ("duel", "duel_model", arcade(game="duel", points=2, opponent_width=4, opponent_speed=1, win_reward=7, lose_reward=-1,
+                                      **short), 4, {}),
+        ("invaders", "invaders_model", arcade(game="invaders", alien_rows=1, lives=2, bomb_period=2, bomb_speed=4,
+                                              march_period=1, descend=8, alien_rewards=(7,), life_reward=-1, **short), 4, {}),
+        ("repeat4", "repeat_model", arcade(game="duel", points=2, opponent_width=4, opponent_speed=1, win_reward=7,
+                                           lose_reward=-1, action_repeat=4, return_reward=2, **short), 4, {}),
+        ("mixture", "mix_model", mix, 4, {}),
+        ("selfplay", "selfplay_model", selfplay, 4, {"scripts": True}),
+    ]
+
+
+def _signature(m):
+    """Everything a host model says about its actor's state."""
+    sig = [np.asarray(m.last_state["image"])]
+    for f in ("record", "actor_record", "style_ids", "objective"):
+        if hasattr(m, f):
+            sig.append(np.asarray(getattr(m, f)()))
+    sig.append(np.asarray([getattr(m, n, -1) for n in ("x", "y", "gx", "gy", "h", "layout", "episode", "ep_steps")]))
+    return sig
+
+
+def test_host_batch_cases_cover_every_model_module():
+    import glob
+    have = set()
+    for path in glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "*_model.py")):
+        with open(path) as f:
+            if "def host_batch" in f.read():
+                have.add(os.path.basename(path)[:-3])
+    assert have == set(c[1] for c in _host_batch_cases())
+
+
+@pytest.mark.parametrize("case", _host_batch_cases(), ids=[c[0] for c in _host_batch_cases()])
+def test_host_batch_shard_is_the_same_actors_as_the_whole_batch(case):
+    """host_batch(conf, B, actor_base=B, actors_total=2B) against models B .. 2B-1 of host_batch(conf, 2B, actors_total=2B):
+    the same action script for 60 steps, a reset after every terminal; rewards, terminals, pixel change, records and frames."""
+    import importlib
+    _, module, make_conf, A, extra = case
+    model = importlib.import_module(module)
+    B, seed, steps = 4, 0xA3C, 60
+    conf = make_conf()
+    kw_whole, kw_shard = {}, dict(actor_base=B)
+    if "actors_total" in inspect.signature(model.host_batch).parameters:
+        kw_whole, kw_shard = dict(actors_total=2 * B), dict(actor_base=B, actors_total=2 * B)
+    if extra.get("scripts"):
+        kw_whole["scripts"], kw_shard["scripts"] = [[] for _ in range(2 * B)], [[] for _ in range(B)]
+    whole = model.host_batch(conf, 2 * B, seed=seed, **kw_whole)
+    shard = model.host_batch(conf, B, seed=seed, **kw_shard)
+    first = model.host_batch(conf, B, seed=seed, **{k: v for k, v in kw_shard.items() if k != "actor_base"})
+    rs = np.random.RandomState(5)
+    acts = rs.randint(0, A, (steps, 2 * B))
+    n_term, differs_from_first = 0, False
+    for b in range(B):
+        for x, y in zip(_signature(shard[b]), _signature(whole[B + b])):
+            np.testing.assert_array_equal(x, y, err_msg="actor %d at reset" % b)
+    for s in range(steps):
+        for b in range(B):
+            pair = (shard[b], whole[B + b])
+            out = []
+            for m in pair:
+                if extra.get("scripts"):
+                    m.partner = [int(acts[s, B + (b ^ 1)])]
+                out.append(m.process(int(acts[s, B + b])))
+            (_, r0, t0, pc0), (_, r1, t1, pc1) = out
+            assert (r0, bool(t0)) == (r1, bool(t1)), (s, b)
+            np.testing.assert_array_equal(pc0, pc1, err_msg="step %d actor %d pixel change" % (s, b))
+            if t0:
+                n_term += 1
+                for m in pair:
+                    m.reset()
+            for x, y in zip(_signature(pair[0]), _signature(pair[1])):
+                np.testing.assert_array_equal(x, y, err_msg="step %d actor %d" % (s, b))
+            # the actors [0, B) fed the same actions are other actors (else the comparison above says nothing)
+            m = first[b]
+            if extra.get("scripts"):
+                m.partner = [int(acts[s, B + (b ^ 1)])]
+            if m.process(int(acts[s, B + b]))[2]:
+                m.reset()
+            differs_from_first |= any(not np.array_equal(x, y) for x, y in zip(_signature(m), _signature(pair[0])))
+    assert n_term > 0 and differs_from_first

@@ -59,7 +59,9 @@ def _cfg(use_lstm, aux, H, T):
                 initial_alpha_high=5e-3, initial_alpha_log_rate=0.5)
 
 
-def _build(cfg, B, seed, env_type="maze", simulator=None, frame_scale=None, env_name="", groups=1, overlap_host=None):
+def _build(cfg, B, seed, env_type="maze", simulator=None, frame_scale=None, env_name="", groups=1, overlap_host=None,
+           rank=0, world_size=1):
+    """rank / world_size: the shard the trainer is (tests/sharded_cases.py); the injected draws stay the plain stream."""
     from unreal_amd.environment.environment import Environment
     from unreal_amd.model.model import UnrealModel
     from unreal_amd.train.rmsprop_applier import RMSPropApplier
@@ -77,7 +79,7 @@ def _build(cfg, B, seed, env_type="maze", simulator=None, frame_scale=None, env_
                  cfg["use_value_replay"], cfg["use_reward_prediction"], cfg["pixel_change_lambda"],
                  cfg["entropy_beta"], cfg["local_t_max"], cfg["n_step_TD"], cfg["gamma"], cfg["gamma_pc"],
                  cfg["experience_history_size"], cfg["max_time_step"], DEV, batch_size=B, draws=draws,
-                 simulator=simulator, groups=groups, overlap_host=overlap_host)
+                 simulator=simulator, groups=groups, overlap_host=overlap_host, rank=rank, world_size=world_size)
     tr.prepare()
     return net, applier, tr, draws
 

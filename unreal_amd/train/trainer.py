@@ -1482,6 +1482,11 @@ class Trainer(PassState):
         # groups: mean over the call's groups; with reuse_epochs > 1 of every group's update 1 (process())
         M = self.reuse_minibatches
         l = (self.loss_sum if self.groups > 1 or self.reuse_epochs > 1 or M > 1 else self.losses).cpu().numpy()
+        # the loss kernels scale their sums by grad_scale = 1 / (Bg world_size), the gradient's scale: a rank reports the
+        # mean over ITS OWN actors, as a one-rank job does, not its 1 / world_size share of the job's mean
+        W = float(self.world_size)
+        if W > 1:
+            l = l * W
         net = self.local_network
         net.policy_loss, net.value_loss, net.entropy = float(l[0]), float(l[1]), float(l[2])
         net.base_loss = net.policy_loss + net.value_loss
@@ -1499,7 +1504,7 @@ class Trainer(PassState):
             self.last_losses.update(depth_loss=net.depth_loss, depth_accuracy=float(hits[0]) / max(int(hits[1]), 1))
         if self.reuse_epochs > 1 or M > 1:  # means over the call's reuse updates; the two counts are exact
             # (minibatches, DESIGN §7t: every update of the call is a reuse update, so the means above are theirs)
-            r = l if M > 1 else self.reuse_loss_sum.cpu().numpy()
+            r = l if M > 1 else self.reuse_loss_sum.cpu().numpy() * W
             si, sf = self.reuse_stats_i.cpu().numpy(), self.reuse_stats_f.cpu().numpy()
             n = max(int(si[1]), 1)
             self.last_losses.update(reuse_policy_loss=float(r[0]), reuse_value_loss=float(r[1]), reuse_entropy=float(r[2]),
