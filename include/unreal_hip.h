@@ -246,14 +246,14 @@ int unreal_maze_objective(int B, int H1, const int* count, const int* records, i
 #define UNREAL_DEPTH_CLASSES 8
 int unreal_maze_depth_labels(int B, int H1, int N, const int* count, const int* pos, const int* heading, int record_words,
                              const int* cfg, const int* layout /*nullable*/, uint8_t* r_depth, void* stream);
-/* Device arcade (csrc/arcade.hip, DESIGN §7k, §7l, §7m, §7n): games stepped and rendered on the device, one actor per workgroup.  The
+/* Device arcade (csrc/arcade.hip, DESIGN §7k, §7l, §7m, §7n, §7x): games stepped and rendered on the device, one actor per workgroup.  The
  * four entries take the ring and rollout arguments of the maze entries above (`pos` is accepted and never touched;
  * nullable) and commit through the same helpers; the maze tail is replaced by (cfg, actor_base, ep_steps[B], episode[B],
  * records[B][UNREAL_ARCADE_RECORD]).  There is one launch shape and no launch label.
  *
  * cfg: UNREAL_ARCADE_CFG_WORDS int32 words; word 0 is the game id, which the kernels read from the block (uniform):
- * UNREAL_ARCADE_BREAKOUT, UNREAL_ARCADE_DUEL or UNREAL_ARCADE_INVADERS (below); a kernel that reads another id (2 included)
- * writes nothing.
+ * UNREAL_ARCADE_BREAKOUT, UNREAL_ARCADE_DUEL, UNREAL_ARCADE_INVADERS or UNREAL_ARCADE_CROSSING (below); a kernel that reads
+ * another id (0, 2, 4 and negative ones included) writes nothing.
  * Breakout's block: [0] UNREAL_ARCADE_BREAKOUT  [1] action_repeat - 1, 0..7 (the kernel clamps it; see "An agent step"
  * below)  [2] rows 1..6  [3] max_episode_steps >= 1  [4..5] seed (lo, hi)  [6] paddle_width (even, 4..24)
  * [7] paddle_speed 1..8  [8] ball_speed 1..4  [9] lives 1..5  [10] serve_wait 0..255 (0: only fire serves)
@@ -371,15 +371,51 @@ int unreal_maze_depth_labels(int B, int H1, int N, const int* count, const int* 
  *     direction = +1, all lives, the full grid, march = bomb = draw_index = steps = 0, grace = serve_wait).  Without it
  *     the game goes on: lives fall below 0, the grid marches on (gy stops at 84), terminal stays set.
  *
+ * Crossing (UNREAL_ARCADE_CROSSING): a walker crosses up to eight lanes of traffic from the bottom of Breakout's
+ * field to its top; the reward is sparse.  Actions: 0 noop, 1 forward (up the screen), 2 right, 3 left (A = 4).
+ * cfg: [0] UNREAL_ARCADE_CROSSING  [1] ticks per agent step less one, 0..7, as above  [2] lanes L 1..8 (the kernel clamps it)
+ * [3] max_episode_steps >= 1  [4..5] seed (lo, hi)  [6] paddle_width, the walker's (even, 4..24)  [7] paddle_speed, its
+ * lateral speed, 1..8  [8] ball_speed, its forward speed, 1..4 (clamped)  [9] crossings 0..99, the episode's target (0:
+ * none, a purely timed game)  [10] serve_wait 0..255, the stun after a hit  [11] hit_reward -100..0  [12] cross_reward
+ * 0..100  [13] knock_back 1..70  [14] car_length 4..16 (clamped to 0..16)  [18] return_reward, 0 (never read)  [20..23] 0,
+ * and the lanes' four settings as bit fields, one word per setting over all eight lanes (lane l = 0 is the top one; the
+ * fields of lanes >= L are 0):  [15] log2(cars) at bit 2 l (cars 1, 2 or 4; the code 3 reads as 4)  [16] speed 0..4 at
+ * bit 3 l (0: parked; above 4 reads as 4)  [17] period - 1 at bit 2 l (period 1..4)  [19] bit l: the lane moves to the
+ * right (direction +1), else to the left.
+ * record: [0..1] px, py, the walker  [2] stun  [3] crossings of the episode  [4] tick counter, the ticks of the episode
+ * modulo 12  [5] the 7-bit offsets of lanes 0..3, lane l in byte l  [6] those of lanes 4..7, lane l in byte l - 4
+ * [7..9] 0  [10] crossings total  [11] hits total  [12] targets-reached total (the totals are never zeroed)  [13..15] 0.
+ * Frame, back to front: black; Breakout's border; one score block per crossing of the episode, the first 19, block k at
+ * x 4+4k..5+4k, y 2..3 in (236, 236, 236); the cars: lane l < L has cars on rows 12+8l..15+8l, `cars` of them, car_length
+ * px long and 128 / cars apart on a wrapped track of 128 px, car k from track x (offset + k 128 / cars) mod 128; screen
+ * x = track x - 22, drawn only on x 2..81, in Breakout's colour of brick row 1 + l mod 5; the walker, paddle_width x 4 px
+ * at (px, py) in (200, 72, 72).  One tick (an agent step is up to action_repeat ticks: "An agent step" above, where the
+ * game ends by its own condition when crossings > 0 and the episode's count >= crossings):
+ *  1. steps += 1; if stun > 0 at the start of the tick: stun -= 1, the walker does not move, and rules 3 and 4 are skipped
+ *     in this tick.  Else action 1: py -= ball_speed; action 2 / 3: px += / -= paddle_speed, clamped to [2, 82 - paddle_width].
+ *  2. Every lane l < L whose period divides the tick counter: offset = (offset + direction speed) mod 128.  Then the tick
+ *     counter grows by one, modulo 12.  (The lanes >= L keep the offset of the reset.)
+ *  3. If the walker's box meets a car's box (one lane at the most: the lanes are 4 rows high and 4 apart): the reward
+ *     gets hit_reward, the hits total grows, py = min(py + knock_back, 76), stun = serve_wait.  One hit per tick.
+ *  4. Else if py <= 6: the reward gets cross_reward, the episode's count and the crossings total grow, the
+ *     targets-reached total grows if the count now equals crossings, and the walker returns to (42 - paddle_width / 2, 76).
+ *  5. terminal: crossings > 0 and count >= crossings (the target is reached: success), or steps >= max_episode_steps.
+ *     With reset_on_terminal the next episode starts: episode += 1, the walker at (42 - paddle_width / 2, 76),
+ *     stun = count = tick counter = steps = 0, and u = Philox4x32-10(key = seed, counter = (actor_base + b, the new
+ *     episode, 0x43524F53, 0)) gives all eight offsets: word 5 = u[0] & 0x7F7F7F7F, word 6 = u[1] & 0x7F7F7F7F.  It is the
+ *     game's only draw.  Without it the game goes on: the count runs past crossings, terminal stays set.
+ *
  * -EINVAL without a launch: B <= 0, H1 < 2, a null or misaligned pointer the entry uses (cfg included), actor_base < 0,
  * and in the rollout entries A != 4 or a next_lar row too short for A + 1 columns. */
 #define UNREAL_ARCADE_BREAKOUT 1
 #define UNREAL_ARCADE_DUEL 3
 #define UNREAL_ARCADE_INVADERS 5
+#define UNREAL_ARCADE_CROSSING 7
 #define UNREAL_ARCADE_CFG_WORDS 24
 #define UNREAL_ARCADE_RECORD 16
 #define UNREAL_ARCADE_SERVE_STREAM 0x41524B53
 #define UNREAL_ARCADE_BOMB_STREAM 0x494E5642
+#define UNREAL_ARCADE_LANE_STREAM 0x43524F53
 int unreal_arcade_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward, const int* count,
                         uint8_t* frames, const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
                         void* stream);
@@ -409,7 +445,7 @@ int unreal_arcade_policy_rollout_step(int B, int H1, const float* X, int ldx, co
 /* Time-limit bootstrapping: the two rollout entries above with a final-observation store, as
  * unreal_maze_rollout_step_tl.  A step is a truncation when, after its last tick, steps >= max_episode_steps and the game
  * itself has not ended (Breakout: a life left and a brick left; duel: neither side at `points`; invaders: a life left and
- * an alien left); a step that ends the game and reaches the limit is a true end.  -EINVAL also for a null final_obs or
+ * an alien left; crossing: the target not reached); a step that ends the game and reaches the limit is a true end.  -EINVAL also for a null final_obs or
  * one not 16-byte aligned. */
 int unreal_arcade_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
                                   int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,

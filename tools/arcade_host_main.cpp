@@ -1,7 +1,7 @@
 // Stand-alone host program around the device arcade's own game, tick-loop and render functions.
 // tools/check_arcade_host.py cuts those functions unchanged out of unreal_amd/csrc/arcade.hip (and the Philox draw out of
 // maze_common.h) into arcade_functions.inc, builds this file with AddressSanitizer and UBSan, and compares what it writes
-// with tests/repeat_model.py and tests/invaders_model.py.  Nothing here runs on a GPU: the qualifiers of the device code are defined away.
+// with tests/repeat_model.py, tests/invaders_model.py and tests/crossing_model.py.  Nothing here runs on a GPU: the qualifiers of the device code are defined away.
 // With a third argument `selfplay` the block is the duel's and the actors are the seats of B / 2 self-play games:
 // every actor steps its pair's canonical game from its own record with the two-action tick loop and the mirror, as a
 // workgroup of the self-play kernels does, and is compared with tests/selfplay_model.py.
@@ -55,7 +55,7 @@ int run(const std::vector<int32_t>& in, FILE* out) {
   for (int b = 0; b < B; ++b) {                   // the constructor's reset: episode 0
     G g;
     load(cfg, &rec[(size_t)b * kArcadeRecord], rules, g);
-    store_game(&rec[(size_t)b * kArcadeRecord], reset_game(rules, g));
+    store_game(&rec[(size_t)b * kArcadeRecord], reset_episode(rules, g, base + b, 0));
   }
   for (int s = 0; s < S; ++s) {
     for (int b = 0; b < B; ++b) {
@@ -84,8 +84,8 @@ int run(const std::vector<int32_t>& in, FILE* out) {
         }
         fwrite(now.data(), 1, FRAME_BYTES, out);
       }
-      if (terminal == 1) {
-        g = reset_game(rules, g);
+      if (terminal == 1) {                        // (crossing's reset draws by the new episode's index)
+        g = reset_episode(rules, g, base + b, episode[b] + 1);
         steps[b] = 0;
         episode[b] += 1;
       }
@@ -274,6 +274,7 @@ int main(int argc, char** argv) {
   else if (in[0] == kArcadeBreakout) bad = run<Game, Rules>(in, out);
   else if (in[0] == kArcadeDuel) bad = run<DuelGame, DuelRules>(in, out);
   else if (in[0] == kArcadeInvaders) bad = run<InvGame, InvRules>(in, out);
+  else if (in[0] == kArcadeCrossing) bad = run<CrossGame, CrossRules>(in, out);
   fclose(out);
   return bad;
 }

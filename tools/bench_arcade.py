@@ -8,10 +8,11 @@
     first-person maze.
 
   python tools/bench_arcade.py [--launches 200] [--steps 10] [--warmup 3] [--history 100] [--repeat 2] [--skip-trainer]
-                               [--game breakout] [--action-repeat 1] [--mix breakout,duel,invaders] [--selfplay]
+                               [--game breakout] [--action-repeat 1] [--mix breakout,duel,invaders,crossing] [--selfplay]
                                [--versus]
 
-`--game duel` / `--game invaders` measures the two-paddle duel or invaders (§7n) on its default config instead
+`--game duel` / `--game invaders` / `--game crossing` measures the two-paddle duel, invaders (§7n) or crossing
+(§7x; with a walker 4 px wide, the tools' crossing config) on its default config instead
 of Breakout; its lines then also hold the game's name.  `--game A,B[,C]` times the step and the fused step of these games in
 turn in one process (lines of bench "arcade_games", keys <game>_us_<k> and <game>_fused_us_<k>; no maze kernels, no trainer).  `--action-repeat K` measures the game at K ticks per agent step; its lines then also hold
 action_repeat and, for the arcade kernels, µs per game tick: the launch's time over K (a step runs fewer ticks only where
@@ -95,13 +96,18 @@ def rollout_ms(env, B, launches, entry):
     return res["ms"] / launches
 
 
+def own_settings(game):
+    """What the tools' default config of a game sets beside the game's own defaults: crossing's walker is 4 px wide."""
+    return dict(paddle_width=4) if game == "crossing" else {}
+
+
 def bench_mix(args):
     from unreal_amd.environment.environment import Environment
     from unreal_amd.environment.arcade_environment import ArcadeMix, BatchedArcadeEnvironment
     games = args.mix.split(",")
     plain, mixed = "unreal_arcade_rollout_step", "unreal_arcade_mix_rollout_step"
     for g in sorted(set(games)):
-        Environment.register_arcade_config("bench_" + g, game=g)
+        Environment.register_arcade_config("bench_" + g, game=g, **own_settings(g))
     conf = {g: Environment.ARCADE_CONFIG["bench_" + g] for g in set(games)}
     Environment.register_arcade_mix("bench_mix", ["bench_" + g for g in games])
     for B in (4096, 64):                                            # (a) one task through the mix entry against the plain entry
@@ -247,9 +253,9 @@ def main():
     ap.add_argument("--history", type=int, default=100)
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--skip-trainer", action="store_true")
-    ap.add_argument("--game", default="breakout", help="breakout, duel, invaders, or several of them joined by commas")
+    ap.add_argument("--game", default="breakout", help="breakout, duel, invaders, crossing, or several of them joined by commas")
     ap.add_argument("--action-repeat", type=int, default=None, help="game ticks per agent step, 1..8 (DESIGN §7m)")
-    ap.add_argument("--mix", default="", help="a game mixture (DESIGN §7u): a comma list of breakout, duel, invaders")
+    ap.add_argument("--mix", default="", help="a game mixture (DESIGN §7u): a comma list of breakout, duel, invaders, crossing")
     ap.add_argument("--selfplay", action="store_true", help="the self-play duel beside the duel (DESIGN §7v)")
     ap.add_argument("--versus", action="store_true", help="the versus step beside self-play and the duel (DESIGN §7w)")
     args = ap.parse_args()
@@ -266,7 +272,8 @@ def main():
     games = args.game.split(",")
     if len(games) > 1:
         for g in games:
-            Environment.register_arcade_config("bench_" + g, game=g, action_repeat=1 if repeat is None else repeat)
+            Environment.register_arcade_config("bench_" + g, game=g, action_repeat=1 if repeat is None else repeat,
+                                               **own_settings(g))
         for rep in range(args.repeat):
             for B in (512, 4096):
                 envs = {g: BatchedArcadeEnvironment(B, 3, DEV, config=Environment.ARCADE_CONFIG["bench_" + g]) for g in games}
@@ -280,7 +287,8 @@ def main():
                 torch.cuda.empty_cache()
         return
     arcade = "bench_" + args.game
-    Environment.register_arcade_config(arcade, game=args.game, action_repeat=1 if repeat is None else repeat)
+    Environment.register_arcade_config(arcade, game=args.game, action_repeat=1 if repeat is None else repeat,
+                                       **own_settings(args.game))
     tag = {} if args.game == "breakout" else {"game": args.game}
     if repeat is not None:
         tag["action_repeat"] = repeat

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """The device arcade's own game functions, tick loop and render on the CPU, under AddressSanitizer and UBSan, against the
-host models of tests/repeat_model.py (Breakout and the duel), tests/invaders_model.py (invaders, §7n) and
+host models of tests/repeat_model.py (Breakout and the duel), tests/invaders_model.py (invaders, §7n),
+tests/crossing_model.py (crossing, §7x: five random traces, two scripted ones) and
 tests/selfplay_model.py (the self-play duel's two-action tick and mirror, §7v).  No GPU is used and nothing loaded into Python is sanitized.
 
 The functions are cut unchanged out of unreal_amd/csrc/arcade.hip (everything from its constants to `frame_chunk`:
 `load_rules`, `step_game`, `game_ended`, `game_over`, `reset_game`, `store_game`, `step_ticks`, `frame_dirty`, `diff_dword`, ...,
-of all three games) and the Philox draw out of maze_common.h, and compiled with tools/arcade_host_main.cpp into a stand-alone
+of all four games) and the Philox draw out of maze_common.h, and compiled with tools/arcade_host_main.cpp into a stand-alone
 program.  Over every trace of tests/repeat_model.py (six random ones of 200 actors x 300 agent steps, two scripted ones) and
 of tests/invaders_model.py (four random ones, one scripted) it is compared on every record, reward, terminal, ep_steps and episode, on every frame byte of the traces' watched actors, and
 inside the program every difference dword of the dirty-row path against the full byte-wise difference of the two frames.
@@ -124,6 +125,7 @@ def main():
     ap.add_argument("--cxx", default=os.environ.get("CXX") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++")
     ap.add_argument("--keep", default="", help="work in this directory and keep it")
     args = ap.parse_args()
+    import crossing_model as CM
     import invaders_model as IM
     import repeat_model as RM
     work = args.keep or tempfile.mkdtemp(prefix="arcade_host_")
@@ -140,7 +142,7 @@ def main():
                            "-I", work, os.path.join(ROOT, "tools", "arcade_host_main.cpp"), "-o", exe])
     total = 0
     traces = [(RM, k) for k in range(len(RM.TRACE_SETTINGS) + len(RM.SCRIPTED_SETTINGS))] + \
-             [(IM, k) for k in range(IM.N_TRACES)]
+             [(IM, k) for k in range(IM.N_TRACES)] + [(CM, k) for k in range(CM.N_TRACES)]
     for n, (mod, k) in enumerate(traces):
         conf, tr = mod.trace_config(k), mod.run_trace(k)
         S, B = tr["acts"].shape

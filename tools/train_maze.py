@@ -2,8 +2,8 @@
 """Train the maze agent with the batched Trainer and log episode returns (GPU box).
 
 usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] [--steps 2e7] [--log-every 10]
-                                  [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout|duel|invaders]
-                                  [--arcade-mix breakout,duel,invaders] [--arcade-selfplay]
+                                  [--lr-scale 1.0] [--max-time-step 0] [--out curve.jsonl] [--arcade breakout|duel|invaders|crossing]
+                                  [--arcade-mix breakout,duel,invaders,crossing] [--arcade-selfplay] [--knock-back K]
                                   [--opponent-pool K] [--snapshot-every N]
                                   [--opponent-speed N] [--action-repeat K] [--return-reward R] [--seed S]
                                   [--max-episode-steps N] [--bootstrap-timeouts] [--gae-lambda L]
@@ -18,7 +18,10 @@ usage: python tools/train_maze.py [--actors 4096] [--groups 1] [--history 2000] 
 bricks_per_episode and lives_lost_per_episode (differences of the records' totals over the episodes of the line); on the
 duel these are points_won_per_episode, points_lost_per_episode and matches_won_per_episode, and
 `--opponent-speed` overrides the opponent's 2 px per step; on invaders aliens_per_episode, lives_lost_per_episode
-and waves_cleared_per_episode.  `--action-repeat K` (1..8) and `--return-reward R` (0..100) are
+and waves_cleared_per_episode; on crossing (the tool's config: a walker 4 px wide, timed episodes of 2000 steps
+unless --max-episode-steps says otherwise) crossings_per_episode, hits_per_episode and targets_reached_per_episode, and
+`--knock-back K` (1..70) is how far a hit throws the walker back: 8 is Freeway-like, 70 Frogger-like (back to the start).
+`--action-repeat K` (1..8) and `--return-reward R` (0..100) are
 the arcade config's settings of those names: K game ticks per agent step, R paid for every ball the agent's
 paddle returns; steps, steps_per_s and episode lengths stay agent steps.  `--seed S` (arcade only) replaces the run's two
 seeds, the network's initial weights (1) and the trainer's draws and serve key (0xA3C), by S.
@@ -38,9 +41,9 @@ of DESIGN §7r (`--arcade` and `--gen-maze`): a line then also holds explore_bon
 `--optimizer adam [--adam-beta1 X] [--adam-beta2 X] [--adam-epsilon X] [--weight-decay X]` steps with AdamApplier instead of
 RMSPropApplier and `--normalize-advantages` is the Trainer's option of that name (every environment of this
 tool); a line then also holds adv_mean and adv_std of its last call, and the head line the optimizer.
-`--arcade-mix LIST` trains one agent on a game mixture: LIST is a comma list of breakout, duel and invaders with
+`--arcade-mix LIST` trains one agent on a game mixture: LIST is a comma list of breakout, duel, invaders and crossing with
 their default configs, repeats allowed (a game listed twice gets twice the actors); actor g plays entry g mod len(LIST).  The
-arcade's options apply to every entry (--return-reward not to invaders, which has no such event); a line then also holds
+arcade's options apply to every entry (--return-reward not to invaders and crossing, which have no such event); a line then also holds
 `tasks`, Trainer.task_scores() over the line's episodes: per entry its name, game, finished episodes and mean return.
 `--arcade-selfplay` trains on the self-play duel with its default config (the arcade's options apply; --actors
 and --actors / --groups must be even): actors 2 i and 2 i + 1 play game i against each other.  Before the first update and at
@@ -72,8 +75,9 @@ ap.add_argument("--lr-scale", type=float, default=1.0)
 ap.add_argument("--max-time-step", type=float, default=0)
 ap.add_argument("--entropy-beta", type=float, default=None, help="override options_lab's 0.001 (a stated deviation)")
 ap.add_argument("--out", default="")
-ap.add_argument("--arcade", default="", help="a device arcade game (breakout, duel, invaders) instead of the maze")
-ap.add_argument("--arcade-mix", default="", help="a game mixture: a comma list of breakout, duel, invaders (DESIGN 7u)")
+ap.add_argument("--arcade", default="", help="a device arcade game (breakout, duel, invaders, crossing) instead of the maze")
+ap.add_argument("--arcade-mix", default="", help="a game mixture: a comma list of breakout, duel, invaders, crossing (DESIGN 7u)")
+ap.add_argument("--knock-back", type=int, default=None, help="crossing: px a hit throws the walker back, 1..70 (default 8)")
 ap.add_argument("--arcade-selfplay", action="store_true", help="the self-play duel (DESIGN 7v)")
 ap.add_argument("--opponent-pool", type=int, default=0, help="with --arcade-selfplay: K frozen copies of the agent play the other paddle (DESIGN 7w)")
 ap.add_argument("--snapshot-every", type=int, default=100, help="optimiser updates between two snapshots into the pool")
@@ -103,7 +107,7 @@ ap.add_argument("--weight-decay", type=float, default=0.0, help="AdamW's decoupl
 ap.add_argument("--normalize-advantages", action="store_true",
                 help="the policy loss reads per-rollout normalised advantages (DESIGN 7s)")
 args = ap.parse_args()
-MIX_GAMES = ("breakout", "duel", "invaders")
+MIX_GAMES = ("breakout", "duel", "invaders", "crossing")
 mix = [g for g in args.arcade_mix.split(",")] if args.arcade_mix else []
 if mix and (args.arcade or args.gen_maze):
     ap.error("--arcade-mix, --arcade and --gen-maze are three environments")
@@ -118,6 +122,8 @@ if args.arcade_selfplay:
                                    (args.actors // args.groups) % 2):
         ap.error("--arcade-selfplay: actors come in pairs, --actors and --actors / --groups must be even")
     args.arcade = "selfplay"                              # the registered name; everything arcade below applies to it
+if args.knock_back is not None and args.arcade != "crossing" and "crossing" not in mix:
+    ap.error("--knock-back is a setting of --arcade crossing (or of a mixture that lists it)")
 if args.opponent_pool and not args.arcade_selfplay:
     ap.error("--opponent-pool needs --arcade-selfplay")
 if args.depth_prediction and not args.gen_maze:
@@ -158,9 +164,13 @@ def build_arcade_trainer(args, device):
         Environment.register_arcade_selfplay(args.arcade, opponent_speed=args.opponent_speed,
                                              action_repeat=args.action_repeat, return_reward=args.return_reward, **limit)
     for game in [] if args.arcade_selfplay else sorted(set(mix)) or [args.arcade]:
+        # the tool's crossing: a walker 4 px wide, a purely timed episode of 2000 steps (DESIGN §7x's baselines)
+        own = dict(dict(paddle_width=4, max_episode_steps=2000, knock_back=args.knock_back), **limit) \
+            if game == "crossing" else limit
         Environment.register_arcade_config(game, game=game, opponent_speed=args.opponent_speed if game == "duel" or not mix
                                            else None, action_repeat=args.action_repeat,
-                                           return_reward=0 if mix and game == "invaders" else args.return_reward, **limit)
+                                           return_reward=0 if mix and game in ("invaders", "crossing") else args.return_reward,
+                                           **own)
     if mix:
         Environment.register_arcade_mix(args.arcade, mix)
     flags = get_options("training", preset="lab", argv=["--env_type", "arcade", "--env_name", args.arcade])
@@ -295,7 +305,8 @@ global_t, t0, k = 0, time.time(), 0
 # the totals of the game's records (words 10 ..), never zeroed: per-line differences over the line's episodes
 TOTALS = {"breakout": ("bricks_per_episode", "lives_lost_per_episode"),
           "duel": ("points_won_per_episode", "points_lost_per_episode", "matches_won_per_episode"),
-          "invaders": ("aliens_per_episode", "lives_lost_per_episode", "waves_cleared_per_episode")}.get(args.arcade, ())
+          "invaders": ("aliens_per_episode", "lives_lost_per_episode", "waves_cleared_per_episode"),
+          "crossing": ("crossings_per_episode", "hits_per_episode", "targets_reached_per_episode")}.get(args.arcade, ())
 totals = tr.full_ring.actor_records[:, 10:10 + len(TOTALS)].sum(0).cpu() if args.arcade else None
 nav_totals = tr.full_ring.actor_records[:, 3:5].sum(0).cpu() if args.gen_maze else None      # goals_total, apples_total
 while global_t < args.steps:

@@ -1,10 +1,11 @@
-// Device arcade (DESIGN §7k, §7l, §7n): games stepped AND rendered on the GPU, behind the ring and rollout arguments of the
-// maze entries.  Three games, all with ALE's minimal action set (0 noop, 1 fire, 2 right, 3 left), integer-only and a pure
-// function of (config block, seed, global actor, episode, actions): Breakout (game id 1), the two-paddle duel (id 3),
-// which keeps Breakout's geometry, ball and serve and puts an opponent's paddle where the wall was, and invaders (id 5), a
-// fixed shooter on Breakout's field.  The rules, the 24-word config blocks and the 16-word per-actor records are documented
-// with the entries in include/unreal_hip.h; tests/arcade_model.py, tests/duel_model.py and tests/invaders_model.py are the
-// host models every kernel here is compared with bit for bit.
+// Device arcade (DESIGN §7k, §7l, §7n, §7x): games stepped AND rendered on the GPU, behind the ring and rollout arguments of the
+// maze entries.  Four games, all with four actions (ALE's minimal set: 0 noop, 1 fire, 2 right, 3 left), integer-only and a
+// pure function of (config block, seed, global actor, episode, actions): Breakout (game id 1), the two-paddle duel (id 3),
+// which keeps Breakout's geometry, ball and serve and puts an opponent's paddle where the wall was, invaders (id 5), a
+// fixed shooter on Breakout's field, and crossing (id 7), a walker that crosses lanes of traffic (action 1: forward).  The
+// rules, the 24-word config blocks and the 16-word per-actor records are documented with the entries in
+// include/unreal_hip.h; tests/arcade_model.py, tests/duel_model.py, tests/invaders_model.py and tests/crossing_model.py are
+// the host models every kernel here is compared with bit for bit.
 // The kernels read the game id from the block (uniform) and run that game's instance of one body.  The _mix entries at the
 // end of the file give every actor its own block of up to 16, chosen by its global index, through the same body.
 //
@@ -19,7 +20,7 @@
 
 namespace {
 
-constexpr int kArcadeBreakout = 1, kArcadeDuel = 3, kArcadeInvaders = 5;   // word 0 of the block
+constexpr int kArcadeBreakout = 1, kArcadeDuel = 3, kArcadeInvaders = 5, kArcadeCrossing = 7;   // word 0 of the block
 constexpr int kArcadeRecord = 16;                   // int32 words per actor (the block has 24)
 constexpr int kMaxRows = 6, kCols = 10, kMaxBallSpeed = 4;
 constexpr int kMaxRepeat = 8;                       // ticks of one agent step at the most (word 1 of the block + 1)
@@ -724,7 +725,209 @@ __device__ __forceinline__ bool row_differs(const InvDirty& d, int y) {
   return y < 64 ? (d.lo >> y) & 1ull : (d.hi >> (y - 64)) & 1u;
 }
 
+// ---- crossing (game id 7): a walker that crosses up to eight lanes of traffic, bottom to top -------------------
+// The lanes' settings are bit fields over all eight lanes, one word per setting, and the lanes' offsets one byte each of a
+// 64-bit word: what a frame row needs of its lane is a shift of a scalar word, never a load indexed by the row.
+constexpr int kMaxLanes = 8, kLaneY0 = 12, kLaneDY = 8, kCarH = 4, kTrackShift = 22, kMaxCarLen = 16;
+constexpr int kWalkerH = 4, kWalkerY0 = 76, kCrossY = 6, kMaxScoreBlocks = 19, kTickWrap = 12;
+// counter word 2 of the lane-phase draw of a reset (word 3: 0)
+constexpr uint32_t kArcadeLaneStream = 0x43524F53u;
+constexpr uint64_t kLaneBytes = 0x7F7F7F7F7F7F7F7Full;      // seven bits a lane
+// bit 12 (p - 1) + t: tick counter t in 0..11 is a multiple of period p in 1..4
+constexpr uint64_t kPeriodTicks = 0xFFFull | 0x555ull << 12 | 0x249ull << 24 | 0x111ull << 36;
+
+// What the render reads in every row has a register of its own; what only a tick reads is packed, three words in all, and
+// taken apart where it is used: the step kernels sit on a register tier's edge (§7n, §7x), and every scalar that lives
+// across the render counts.  All values are clamped to their fields as they are packed.
+struct CrossRules {
+  const int* cfg;         // (the seed is read by the reset alone)
+  int lanes, max_steps, w, car_len, target;
+  uint32_t cars;          // per lane l: log2(cars) at bit 2 l
+  uint32_t moves;         // per lane l: speed at bit 3 l; bit 24 + l: to the right
+  uint32_t walk;          // per lane l: period - 1 at bit 2 l; paddle_speed at 16 (4 bits), ball_speed at 20 (3), stun at 23 (8)
+  uint32_t pay;           // -hit_reward at 0 (7 bits), cross_reward at 7 (7), knock_back at 14 (7)
+  int repeat;             // as in Rules (word 1)
+  __device__ __forceinline__ int paddle_speed() const { return (int)(walk >> 16) & 15; }
+  __device__ __forceinline__ int ball_speed() const { return (int)(walk >> 20) & 7; }
+  __device__ __forceinline__ int stun() const { return (int)(walk >> 23) & 255; }
+  __device__ __forceinline__ int hit_reward() const { return -(int)(pay & 127u); }
+  __device__ __forceinline__ int cross_reward() const { return (int)(pay >> 7) & 127; }
+  __device__ __forceinline__ int knock_back() const { return (int)(pay >> 14) & 127; }
+  __device__ __forceinline__ uint32_t speed() const { return moves & 0xFFFFFFu; }
+  __device__ __forceinline__ uint32_t period() const { return walk & 0xFFFFu; }
+  __device__ __forceinline__ uint32_t dir() const { return moves >> 24; }
+  __device__ __forceinline__ uint64_t seed() const { return (uint64_t)(uint32_t)cfg[4] | ((uint64_t)(uint32_t)cfg[5] << 32); }
+};
+
+__device__ __forceinline__ uint32_t field(int v, int hi) { return (uint32_t)min(max(v, 0), hi); }
+
+__device__ __forceinline__ CrossRules load_cross_rules(const int* cfg) {
+  CrossRules r;
+  r.cfg = cfg;
+  r.repeat = min(max(cfg[1], 0), kMaxRepeat - 1);
+  r.lanes = min(max(cfg[2], 1), kMaxLanes);
+  r.max_steps = cfg[3];
+  r.w = cfg[6];
+  r.target = cfg[9];
+  r.car_len = min(max(cfg[14], 0), kMaxCarLen);
+  r.cars = (uint32_t)cfg[15];
+  r.moves = ((uint32_t)cfg[16] & 0xFFFFFFu) | ((uint32_t)cfg[19] & 255u) << 24;
+  r.walk = ((uint32_t)cfg[17] & 0xFFFFu) | field(cfg[7], 15) << 16 | field(cfg[8], kMaxBallSpeed) << 20 | field(cfg[10], 255) << 23;
+  r.pay = field(-cfg[11], 127) | field(cfg[12], 127) << 7 | field(cfg[13], 127) << 14;
+  return r;
+}
+
+struct CrossGame {
+  int px, py, stun;
+  int count;              // crossings of the running episode
+  int tick;               // ticks of the running episode modulo 12 (every period divides 12)
+  uint64_t off;           // the lanes' 7-bit offsets, lane l in byte l
+  int events;             // of this agent step: crossings | hits << 8 | target reached << 16 (store_game adds them to the
+                          // running totals of words 10..12, which are never zeroed and never held in registers)
+};
+
+__device__ __forceinline__ CrossGame load_cross_game(const int* rec) {
+  CrossGame g;
+  g.px = rec[0]; g.py = rec[1]; g.stun = rec[2]; g.count = rec[3]; g.tick = rec[4];
+  g.off = (uint64_t)(uint32_t)rec[5] | ((uint64_t)(uint32_t)rec[6] << 32);
+  g.events = 0;
+  return g;
+}
+
+__device__ __forceinline__ void store_game(int* rec, const CrossGame& g) {
+  rec[0] = g.px; rec[1] = g.py; rec[2] = g.stun; rec[3] = g.count; rec[4] = g.tick;
+  rec[5] = (int)(uint32_t)g.off; rec[6] = (int)(uint32_t)(g.off >> 32);
+  rec[7] = 0; rec[8] = 0; rec[9] = 0;
+  rec[10] += g.events & 255; rec[11] += (g.events >> 8) & 255; rec[12] += (g.events >> 16) & 255;
+  rec[13] = 0; rec[14] = 0; rec[15] = 0;
+}
+
+// lane l in 0..7: its offset, and the mask of its car spacing (128 / cars - 1)
+__device__ __forceinline__ int lane_offset(const CrossGame& g, int l) { return (int)(g.off >> (8 * l)) & 127; }
+__device__ __forceinline__ int lane_spacing_mask(const CrossRules& r, int l) { return (128 >> min((int)(r.cars >> (2 * l)) & 3, 2)) - 1; }
+
+// the walker at its start; the rest of the record stays
+__device__ __forceinline__ void walker_home(CrossGame& g, const CrossRules& r) { g.px = 42 - r.w / 2; g.py = kWalkerY0; }
+
+// the first state of episode `ep` of global actor `actor`: the walker at its start, the lanes at the phases of the one
+// draw of the episode; the totals run on
+__device__ __forceinline__ CrossGame reset_episode(const CrossRules& r, const CrossGame& old, int actor, int ep) {
+  CrossGame g = old;
+  walker_home(g, r);
+  g.stun = 0; g.count = 0; g.tick = 0;
+  uint32_t u[4];
+  philox4x32_10(r.seed(), (uint64_t)(uint32_t)actor | ((uint64_t)(uint32_t)ep << 32), (uint64_t)kArcadeLaneStream, u);
+  g.off = ((uint64_t)u[0] | ((uint64_t)u[1] << 32)) & kLaneBytes;
+  return g;
+}
+
+// One tick (crossing's rules 1..4 of the header); -> the tick's reward.  The draw is the reset's: none here.
+__device__ __forceinline__ int step_game(CrossGame& g, const CrossRules& r, int a, int, int) {
+  int reward = 0;
+  // 1. the walker
+  const bool stunned = g.stun > 0;
+  if (stunned) {
+    g.stun -= 1;
+  } else {
+    if (a == 1) g.py -= r.ball_speed();
+    if (a == 2) g.px = min(g.px + r.paddle_speed(), 82 - r.w);
+    if (a == 3) g.px = max(g.px - r.paddle_speed(), kFieldL);
+  }
+  // 2. the lanes: a lane moves in the ticks whose counter is a multiple of its period
+  const int t = min(max(g.tick, 0), kTickWrap - 1);
+  g.tick = t + 1 == kTickWrap ? 0 : t + 1;
+  const uint32_t period = r.period(), speed = r.speed(), dir = r.dir();
+  uint64_t moves = 0;     // byte l: what lane l's offset grows by, modulo 128 (two 7-bit values: no carry between bytes)
+#pragma unroll 1          // (scalar code; eight copies only add to what the step kernel has to keep)
+  for (int l = 0; l < kMaxLanes; ++l) {
+    const int pm1 = (int)(period >> (2 * l)) & 3;
+    if (l < r.lanes && ((kPeriodTicks >> (12 * pm1 + t)) & 1ull)) {
+      const int v = min((int)(speed >> (3 * l)) & 7, 4);
+      moves |= (uint64_t)((((dir >> l) & 1u) ? v : -v) & 127) << (8 * l);
+    }
+  }
+  g.off = (g.off + moves) & kLaneBytes;
+  if (stunned) return reward;
+  // 3. the hit: a walker of four rows meets one lane at the most; its box meets a car if it starts inside one or reaches
+  //    the next one's first pixel
+  const int ly = g.py - (kLaneY0 - kWalkerH + 1), l = ly >> 3;
+  bool hit = false;
+  if (ly >= 0 && l < r.lanes && (ly & 7) < kCarH + kWalkerH - 1) {
+    const int m = lane_spacing_mask(r, l);
+    const int d = (g.px + kTrackShift - lane_offset(g, l)) & m;
+    hit = d < r.car_len || d + r.w > m + 1;
+  }
+  if (hit) {
+    reward += r.hit_reward();
+    g.events += 1 << 8;
+    g.py = min(g.py + r.knock_back(), kWalkerY0);
+    g.stun = r.stun();
+  } else if (g.py <= kCrossY) {
+    // 4. the crossing
+    reward += r.cross_reward();
+    g.count += 1;
+    g.events += g.count == r.target ? 1 | 1 << 16 : 1;
+    walker_home(g, r);
+  }
+  return reward;
+}
+
+__device__ __forceinline__ bool game_ended(const CrossGame& g, const CrossRules& r) { return r.target > 0 && g.count >= r.target; }
+
+__device__ __forceinline__ bool game_over(const CrossGame& g, const CrossRules& r, int steps) {
+  return game_ended(g, r) || steps >= r.max_steps;
+}
+
+struct CrossRow {
+  bool walker, score, top;
+  int lane;               // the lane whose cars the row holds, or -1
+};
+
+__device__ __forceinline__ CrossRow frame_row(const CrossGame& g, const CrossRules& r, int y) {
+  CrossRow row;
+  row.walker = (unsigned)(y - g.py) < (unsigned)kWalkerH;
+  const int ly = y - kLaneY0;
+  row.lane = (ly >= 0 && (ly >> 3) < r.lanes && (ly & 7) < kCarH) ? ly >> 3 : -1;
+  row.score = (unsigned)(y - 2) < 2u;
+  row.top = y < kFieldTop;
+  return row;
+}
+
+// pixel x of that row: front to back walker, cars (clipped to the field), score blocks, border
+__device__ __forceinline__ uint32_t pixel(const CrossGame& g, const CrossRules& r, const CrossRow& row, int x) {
+  if (row.walker && x >= g.px && x < g.px + r.w) return kPaddle;
+  if (row.lane >= 0 && x >= kFieldL && x <= kFieldR &&
+      ((x + kTrackShift - lane_offset(g, row.lane)) & lane_spacing_mask(r, row.lane)) < r.car_len)
+    return row_colour(1 + row.lane % 5);        // never row 0's, the walker's
+  if (row.score && x >= 4 && x < 4 + 4 * min(max(g.count, 0), kMaxScoreBlocks) && ((x - 4) & 3) < 2) return kWhite;
+  if (row.top || x < kFieldL || x > kFieldR) return kBorder;
+  return 0u;
+}
+
+// The rows in which the frames of two states can differ, as InvDirty's set: the car rows of every lane whose offset changed,
+// the walker's rows in both states if it moved, the score rows if the count changed.
+__device__ __forceinline__ InvDirty frame_dirty(const CrossGame& a, const CrossGame& b, const CrossRules&) {
+  InvDirty d = {0ull, 0u};
+  // rows 12 + 8 l .. 15 + 8 l of every lane l whose offset changed: bit 8 l for a byte that differs (two 7-bit values: no
+  // carry between bytes), each spread over four rows and moved to row 12 (the lanes without traffic never move)
+  const uint64_t rows = ((((a.off ^ b.off) + kLaneBytes) >> 7) & 0x0101010101010101ull) * (uint64_t)((1 << kCarH) - 1);
+  d.lo = rows << kLaneY0;
+  d.hi = (uint32_t)(rows >> (64 - kLaneY0));
+  if (a.px != b.px || a.py != b.py) {
+    add_rows(d, a.py, a.py + kWalkerH);
+    add_rows(d, b.py, b.py + kWalkerH);
+  }
+  if (a.count != b.count) add_rows(d, 2, 4);
+  return d;
+}
+
 // what the one body below asks of a game by type
+__device__ __forceinline__ void load(const int* cfg, const int* rec, CrossRules& r, CrossGame& g) {
+  r = load_cross_rules(cfg); g = load_cross_game(rec);
+}
+// (the other games' resets make no draw)
+template <class G, class R>
+__device__ __forceinline__ G reset_episode(const R& r, const G& old, int, int) { return reset_game(r, old); }
 __device__ __forceinline__ void load(const int* cfg, const int* rec, Rules& r, Game& g) { r = load_rules(cfg); g = load_game(rec); }
 __device__ __forceinline__ void load(const int* cfg, const int* rec, DuelRules& r, DuelGame& g) {
   r = load_duel_rules(cfg); g = load_duel_game(rec);
@@ -870,7 +1073,7 @@ __device__ __forceinline__ void step_actor(const ArcadeArgs& p, uint4* diff, int
     }
   }
   if (ring.reset) {                             // (uniform) the next episode's first observation goes into the slot instead
-    g = reset_game(rules, g);
+    g = reset_episode(rules, g, p.actor_base + b, epi + 1);
     store_frame(dst, g, rules);
   }
   if (threadIdx.x == 0) {
@@ -896,6 +1099,7 @@ __global__ __launch_bounds__(256) void arcade_step_kernel(ArcadeArgs p) {
   if (game == kArcadeBreakout) step_actor<Game, Rules>(p, diff, &s_act);
   else if (game == kArcadeDuel) step_actor<DuelGame, DuelRules>(p, diff, &s_act);
   else if (game == kArcadeInvaders) step_actor<InvGame, InvRules>(p, diff, &s_act);
+  else if (game == kArcadeCrossing) step_actor<CrossGame, CrossRules>(p, diff, &s_act);
 }
 
 // the rollout step of the _tl entries
@@ -906,6 +1110,7 @@ __global__ __launch_bounds__(256) void arcade_step_tl_kernel(ArcadeArgs p) {
   if (game == kArcadeBreakout) step_actor<Game, Rules, true>(p, diff, &s_act);
   else if (game == kArcadeDuel) step_actor<DuelGame, DuelRules, true>(p, diff, &s_act);
   else if (game == kArcadeInvaders) step_actor<InvGame, InvRules, true>(p, diff, &s_act);
+  else if (game == kArcadeCrossing) step_actor<CrossGame, CrossRules, true>(p, diff, &s_act);
 }
 
 template <class G, class R>
@@ -918,7 +1123,7 @@ __device__ __forceinline__ void reset_actor(const ArcadeArgs& p) {
   load(p.cfg, rec, rules, old);
   const int epi = p.episode[b];
   __syncthreads();                              // every thread has read the record
-  const G g = reset_game(rules, old);
+  const G g = reset_episode(rules, old, p.actor_base + b, epi + 1);
   store_frame(p.frames + ((size_t)b * p.H1 + p.count[b] % p.H1) * FRAME_BYTES, g, rules);
   if (threadIdx.x == 0) {
     store_game(rec, g);
@@ -934,6 +1139,7 @@ __global__ __launch_bounds__(256) void arcade_reset_kernel(ArcadeArgs p) {
   if (game == kArcadeBreakout) reset_actor<Game, Rules>(p);
   else if (game == kArcadeDuel) reset_actor<DuelGame, DuelRules>(p);
   else if (game == kArcadeInvaders) reset_actor<InvGame, InvRules>(p);
+  else if (game == kArcadeCrossing) reset_actor<CrossGame, CrossRules>(p);
 }
 
 // ---- game mixtures: one config block per actor ------------------------------------------------------------
@@ -993,16 +1199,20 @@ __global__ __launch_bounds__(256) void arcade_mix_step_kernel(ArcadeMixArgs m) {
   if (game == kArcadeBreakout) mix_step_actor<Game, Rules, false>(m, p, diff, &s_act);
   else if (game == kArcadeDuel) mix_step_actor<DuelGame, DuelRules, false>(m, p, diff, &s_act);
   else if (game == kArcadeInvaders) mix_step_actor<InvGame, InvRules, false>(m, p, diff, &s_act);
+  else if (game == kArcadeCrossing) mix_step_actor<CrossGame, CrossRules, false>(m, p, diff, &s_act);
 }
 
 __global__ __launch_bounds__(256) void arcade_mix_step_tl_kernel(ArcadeMixArgs m) {
   __shared__ uint4 diff[kChunks];
   __shared__ int s_act;
-  const ArcadeArgs p = mix_actor_args(m);
+  ArcadeArgs p = mix_actor_args(m);
+  // the _tl entries are rollout forms: what every one of them passes is known here, and need not be kept
+  p.active = nullptr; p.reset_on_terminal = 1; p.track_score = 1;
   const int game = p.cfg[0];                    // (uniform per workgroup) as above
   if (game == kArcadeBreakout) mix_step_actor<Game, Rules, true>(m, p, diff, &s_act);
   else if (game == kArcadeDuel) mix_step_actor<DuelGame, DuelRules, true>(m, p, diff, &s_act);
   else if (game == kArcadeInvaders) mix_step_actor<InvGame, InvRules, true>(m, p, diff, &s_act);
+  else if (game == kArcadeCrossing) mix_step_actor<CrossGame, CrossRules, true>(m, p, diff, &s_act);
 }
 
 __global__ __launch_bounds__(256) void arcade_mix_reset_kernel(ArcadeMixArgs m) {
@@ -1011,6 +1221,7 @@ __global__ __launch_bounds__(256) void arcade_mix_reset_kernel(ArcadeMixArgs m) 
   if (game == kArcadeBreakout) reset_actor<Game, Rules>(p);
   else if (game == kArcadeDuel) reset_actor<DuelGame, DuelRules>(p);
   else if (game == kArcadeInvaders) reset_actor<InvGame, InvRules>(p);
+  else if (game == kArcadeCrossing) reset_actor<CrossGame, CrossRules>(p);
 }
 
 // ---- host side: one check and one launcher for the four entries -------------------------------------------------------

@@ -1,8 +1,9 @@
-"""Device arcade (csrc/arcade.hip, DESIGN §7k, §7l, §7m, §7n): games stepped and rendered on the GPU.  Three games with ALE's
+"""Device arcade (csrc/arcade.hip, DESIGN §7k, §7l, §7m, §7n, §7x): games stepped and rendered on the GPU.  Three games with ALE's
 minimal action set (0 noop, 1 fire, 2 right, 3 left): Breakout, the two-paddle duel that keeps Breakout's geometry, ball and
 serve and puts an opponent's paddle where the wall was, and invaders, a fixed shooter on Breakout's field: a marching grid
-of aliens that drop bombs, a cannon that shoots them.  All are integer-only and a pure function of (config, seed, global
-actor, episode, actions).  An agent step is `action_repeat` game ticks with one action (§7m).  The rules are written out
+of aliens that drop bombs, a cannon that shoots them.  The fourth, crossing, has a sparse reward: a walker crosses up to
+eight lanes of traffic from the bottom to the top (0 noop, 1 forward, 2 right, 3 left).  All are integer-only and a pure
+function of (config, seed, global actor, episode, actions).  An agent step is `action_repeat` game ticks with one action (§7m).  The rules are written out
 with the entries in include/unreal_hip.h.  ArcadeSelfPlay (§7v) is the duel with both paddles driven by actors: actors 2 i
 and 2 i + 1 are the two seats of game i."""
 import numpy as np
@@ -21,6 +22,13 @@ GAME_SETTINGS = {"breakout": dict(rows=6, row_rewards=None, lives=3, life_reward
                  "duel": dict(points=5, opponent_width=12, opponent_speed=2, win_reward=1, lose_reward=-1),
                  "invaders": dict(alien_rows=3, alien_rewards=None, lives=3, life_reward=0, march_period=4, descend=4,
                                   bomb_period=12, bomb_speed=1)}
+# crossing comes in through tables of its own: the three dictionaries above are pinned by tests as they are
+CROSSING_SETTINGS = dict(lanes=None, car_length=8, knock_back=8, crossings=0, cross_reward=1, hit_reward=0)
+ALL_GAME_IDS = dict(GAME_IDS, crossing=ops.ARCADE_CROSSING)
+ALL_GAME_SETTINGS = dict(GAME_SETTINGS, crossing=CROSSING_SETTINGS)
+# lanes=None: eight lanes, top lane first, as (cars, speed, period, direction): directions alternate, speeds are mixed
+DEFAULT_LANES = ((2, 1, 1, 1), (1, 2, 1, -1), (4, 1, 2, 1), (2, 3, 1, -1), (2, 1, 1, 1), (1, 4, 1, -1), (4, 1, 3, 1),
+                 (2, 2, 1, -1))
 
 
 def _int(name, v, lo, hi):
@@ -42,10 +50,19 @@ class ArcadeConfig(object):
     """Settings of one arcade game (Environment.register_arcade_config).  Raises ValueError outside the documented ranges,
     and for a setting of another game (rows, row_rewards are Breakout's; points, opponent_width, opponent_speed,
     win_reward, lose_reward the duel's; alien_rows, alien_rewards, march_period, descend, bomb_period, bomb_speed
-    invaders'; lives and life_reward are Breakout's and invaders'; None: the game's default).  Every game: action_repeat in
+    invaders'; lives and life_reward are Breakout's and invaders'; lanes, car_length, knock_back, crossings, cross_reward,
+    hit_reward crossing's; None: the game's default).  Every game: action_repeat in
     1..8 game ticks per agent step.  return_reward in 0..100 is paid when the agent's paddle returns the ball; invaders has
     no such event and takes only 0.  There paddle_width and paddle_speed are the cannon's, ball_speed the shot's, and
-    serve_wait the ticks after a reset or a lost life in which no bomb is dropped."""
+    serve_wait the ticks after a reset or a lost life in which no bomb is dropped.
+    game="crossing" (DESIGN §7x): paddle_width is the walker's width, paddle_speed its lateral and ball_speed its forward
+    speed in px per tick, serve_wait the ticks it is stunned after a hit; return_reward takes only 0.  lanes: a list of
+    1..8 (cars, speed, period, direction) tuples, top lane first, with cars in {1, 2, 4}, speed in 0..4 px (0: parked),
+    period in 1..4 ticks per move and direction +1 (to the right) or -1 (None: DEFAULT_LANES, eight lanes); car_length
+    in 4..16 px (None: 8); a hit throws the walker back by knock_back in 1..70 px (None: 8) and pays hit_reward in -100..0
+    (None: 0); a crossing pays cross_reward in 0..100 (None: 1); the episode ends with `crossings` in 0..99 crossings
+    (the success; None: 0, never: only max_episode_steps ends it)."""
+    MAX_LANES = 8
     ACTION_SIZE = 4
     MAX_ACTION_REPEAT = 8
     MAX_ROWS, COLUMNS = 6, 10
@@ -55,19 +72,21 @@ class ArcadeConfig(object):
     def __init__(self, game="breakout", rows=None, row_rewards=None, paddle_width=12, paddle_speed=3, ball_speed=2,
                  lives=None, serve_wait=8, life_reward=None, max_episode_steps=5000, points=None, opponent_width=None,
                  opponent_speed=None, win_reward=None, lose_reward=None, action_repeat=1, return_reward=0, alien_rows=None,
-                 alien_rewards=None, march_period=None, descend=None, bomb_period=None, bomb_speed=None):
-        if game not in GAME_IDS:
-            raise ValueError("arcade game %r: known games are %s" % (game, sorted(GAME_IDS)))
+                 alien_rewards=None, march_period=None, descend=None, bomb_period=None, bomb_speed=None, lanes=None,
+                 car_length=None, knock_back=None, crossings=None, cross_reward=None, hit_reward=None):
+        if game not in ALL_GAME_IDS:
+            raise ValueError("arcade game %r: known games are %s" % (game, sorted(ALL_GAME_IDS)))
         self.game = game
         own = dict(rows=rows, row_rewards=row_rewards, lives=lives, life_reward=life_reward, points=points,
                    opponent_width=opponent_width, opponent_speed=opponent_speed, win_reward=win_reward,
                    lose_reward=lose_reward, alien_rows=alien_rows, alien_rewards=alien_rewards, march_period=march_period,
-                   descend=descend, bomb_period=bomb_period, bomb_speed=bomb_speed)
-        for other, names in GAME_SETTINGS.items():
+                   descend=descend, bomb_period=bomb_period, bomb_speed=bomb_speed, lanes=lanes, car_length=car_length,
+                   knock_back=knock_back, crossings=crossings, cross_reward=cross_reward, hit_reward=hit_reward)
+        for other, names in ALL_GAME_SETTINGS.items():
             for name in names:
-                if other != game and name not in GAME_SETTINGS[game] and own[name] is not None:
+                if other != game and name not in ALL_GAME_SETTINGS[game] and own[name] is not None:
                     raise ValueError("%s is a setting of game %r, not of %r" % (name, other, game))
-        own = {k: (own[k] if own[k] is not None else v) for k, v in GAME_SETTINGS[game].items()}
+        own = {k: (own[k] if own[k] is not None else v) for k, v in ALL_GAME_SETTINGS[game].items()}
         if game == "breakout":
             self.rows = _int("rows", own["rows"], 1, self.MAX_ROWS)
             row_rewards = own["row_rewards"]
@@ -88,6 +107,29 @@ class ArcadeConfig(object):
             self.descend = _int("descend", own["descend"], 1, 8)
             self.bomb_period = _int("bomb_period", own["bomb_period"], 1, 64)
             self.bomb_speed = _int("bomb_speed", own["bomb_speed"], 1, 4)
+        elif game == "crossing":
+            lanes = DEFAULT_LANES if own["lanes"] is None else own["lanes"]
+            if isinstance(lanes, (str, bytes)) or not hasattr(lanes, "__len__") or not 1 <= len(lanes) <= self.MAX_LANES:
+                raise ValueError("lanes must hold 1..%d (cars, speed, period, direction) tuples, not %r"
+                                 % (self.MAX_LANES, lanes))
+            checked = []
+            for i, lane in enumerate(lanes):
+                if isinstance(lane, (str, bytes)) or not hasattr(lane, "__len__") or len(lane) != 4:
+                    raise ValueError("lanes[%d] must be (cars, speed, period, direction), not %r" % (i, lane))
+                cars = _int("lanes[%d] cars" % i, lane[0], 1, 4)
+                if cars == 3:
+                    raise ValueError("lanes[%d] cars = 3: a lane holds 1, 2 or 4 cars" % i)
+                direction = _int("lanes[%d] direction" % i, lane[3], -1, 1)
+                if direction == 0:
+                    raise ValueError("lanes[%d] direction = 0: +1 (to the right) or -1" % i)
+                checked.append((cars, _int("lanes[%d] speed" % i, lane[1], 0, 4), _int("lanes[%d] period" % i, lane[2], 1, 4),
+                                direction))
+            self.lanes = tuple(checked)
+            self.car_length = _int("car_length", own["car_length"], 4, 16)
+            self.knock_back = _int("knock_back", own["knock_back"], 1, 70)
+            self.crossings = _int("crossings", own["crossings"], 0, 99)
+            self.cross_reward = _int("cross_reward", own["cross_reward"], 0, 100)
+            self.hit_reward = _int("hit_reward", own["hit_reward"], -100, 0)
         else:
             self.points = _int("points", own["points"], 1, self.MAX_POINTS)
             self.opponent_width = _even("opponent_width", own["opponent_width"], 4, 24)
@@ -97,15 +139,15 @@ class ArcadeConfig(object):
         self.paddle_width = _even("paddle_width", paddle_width, 4, 24)
         self.paddle_speed = _int("paddle_speed", paddle_speed, 1, 8)
         self.ball_speed = _int("ball_speed", ball_speed, 1, 4)
-        if game != "duel":
+        if game not in ("duel", "crossing"):
             self.lives = _int("lives", own["lives"], 1, 5)
         self.serve_wait = _int("serve_wait", serve_wait, 0, 255)
-        if game != "duel":
+        if game not in ("duel", "crossing"):
             self.life_reward = _int("life_reward", own["life_reward"], -100, 0)
         # mandatory: a ball that loops between the walls never ends an episode on its own
         self.max_episode_steps = _int("max_episode_steps", max_episode_steps, 1, 2 ** 31 - 1)
         self.action_repeat = _int("action_repeat", action_repeat, 1, self.MAX_ACTION_REPEAT)
-        self.return_reward = _int("return_reward", return_reward, 0, 0 if game == "invaders" else 100)
+        self.return_reward = _int("return_reward", return_reward, 0, 0 if game in ("invaders", "crossing") else 100)
 
     @property
     def action_size(self):
@@ -115,7 +157,7 @@ class ArcadeConfig(object):
         """The int32 block of the kernels (UNREAL_ARCADE_CFG_WORDS words; the games' layouts: include/unreal_hip.h)."""
         seed = int(seed) & (2 ** 64 - 1)
         w = np.zeros(ops.ARCADE_CFG_WORDS, dtype=np.int64)
-        w[0] = GAME_IDS[self.game]
+        w[0] = ALL_GAME_IDS[self.game]
         w[1], w[18] = self.action_repeat - 1, self.return_reward
         w[3] = self.max_episode_steps
         w[4], w[5] = seed & 0xFFFFFFFF, seed >> 32
@@ -128,6 +170,14 @@ class ArcadeConfig(object):
             w[2], w[9], w[11] = self.alien_rows, self.lives, self.life_reward
             w[12:12 + self.alien_rows] = self.alien_rewards
             w[16], w[17], w[19], w[20] = self.march_period, self.descend, self.bomb_period, self.bomb_speed
+        elif self.game == "crossing":
+            w[2], w[9], w[11] = len(self.lanes), self.crossings, self.hit_reward
+            w[12], w[13], w[14] = self.cross_reward, self.knock_back, self.car_length
+            for l, (cars, speed, period, direction) in enumerate(self.lanes):      # one word per field over all lanes
+                w[15] |= (cars.bit_length() - 1) << (2 * l)
+                w[16] |= speed << (3 * l)
+                w[17] |= (period - 1) << (2 * l)
+                w[19] |= int(direction > 0) << l
         else:
             w[2], w[9], w[11] = self.points, self.opponent_width, self.lose_reward
             w[12], w[13] = self.win_reward, self.opponent_speed
@@ -327,6 +377,9 @@ class BatchedArcadeEnvironment(object):
         serve_index, then the running totals of points won, points lost and matches won.  Words 13..15 are 0.  Invaders: px,
         sx, sy (0: no shot), gx, gy, direction, lives, alien mask, march | bomb << 8 | grace << 16 counters, draw_index,
         then the running totals of aliens shot, lives lost and waves cleared, then the three bombs as x | y << 8 (0: free).
+        Crossing: px, py, stun, the episode's crossings, tick counter (modulo 12), the lanes' 7-bit offsets (lanes 0..3 in
+        the bytes of word 5, lanes 4..7 in those of word 6), words 7..9 0, then the running totals of crossings, hits and
+        targets reached; words 13..15 are 0.
         Self-play: one duel record per SEAT; rows 2 i hold game i's canonical record (seat 0 at the bottom),
         rows 2 i + 1 its mirror image, the game as seat 1 sees it (px and ox, mine and theirs, words 10 and 11, words 12
         and 13 swapped, by = 86 - by, vy = -vy); word 13 is the other seat's matches won, words 14..15 are 0.  Versus (DESIGN
@@ -388,6 +441,8 @@ class ArcadeEnvironment(environment.Environment):
         rec = self._env.current_records()[0]
         if self._env.config.game == "duel":            # the match is won
             success = terminal and int(rec[7]) >= self._env.config.points
+        elif self._env.config.game == "crossing":      # the target is reached
+            success = terminal and 0 < self._env.config.crossings <= int(rec[3])
         elif self._env.config.game == "invaders":      # the wave is cleared
             success = terminal and not rec[7]
         else:                                          # the wall is cleared

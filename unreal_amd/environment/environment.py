@@ -81,7 +81,8 @@ class Environment(object):
                                ball_speed=2, lives=None, serve_wait=8, life_reward=None, max_episode_steps=5000,
                                points=None, opponent_width=None, opponent_speed=None, win_reward=None, lose_reward=None,
                                action_repeat=1, return_reward=0, alien_rows=None, alien_rewards=None, march_period=None,
-                               descend=None, bomb_period=None, bomb_speed=None):
+                               descend=None, bomb_period=None, bomb_speed=None, lanes=None, car_length=None,
+                               knock_back=None, crossings=None, cross_reward=None, hit_reward=None):
         """Arcade game of `env_name` on the device (env_type 'arcade'), with ALE's minimal action set
         (0 noop, 1 fire, 2 right, 3 left) on an 84 x 84 RGB frame.  Both games: paddle_width even in 4..24 px;
         paddle_speed in 1..8 px per step; ball_speed in 1..4 micro-steps per step; serve_wait in 0..255: a waiting ball
@@ -104,13 +105,22 @@ class Environment(object):
         ball_speed the shot's, serve_wait the ticks without a new bomb after a reset or a lost life; return_reward must
         be 0.  An episode also ends with the last life, when the aliens reach the cannon's rows, or with the last alien
         (success).
+        game="crossing" (actions 0 noop, 1 forward, 2 right, 3 left): a walker of paddle_width x 4 px crosses
+        the lanes of traffic from the bottom to the top, ball_speed px per forward tick, paddle_speed px sideways.
+        lanes: 1..8 (cars, speed, period, direction) tuples, top lane first: cars in {1, 2, 4} of car_length in 4..16 px
+        (None: 8) move speed in 0..4 px every period in 1..4 ticks to the right (+1) or the left (-1) (None: eight lanes
+        of alternating directions and mixed speeds).  A car that hits the walker throws it back by knock_back in 1..70 px
+        (None: 8; 70: to the start), pays hit_reward in -100..0 (None: 0) and stuns it for serve_wait ticks; a crossing
+        pays cross_reward in 0..100 (None: 1).  `crossings` in 0..99 crossings end the episode (success; None: 0: only
+        max_episode_steps does); return_reward must be 0.
         Raises ValueError outside these ranges and for a setting of another game."""
         from .arcade_environment import ArcadeConfig
         Environment.ARCADE_CONFIG[env_name] = ArcadeConfig(game, rows, row_rewards, paddle_width, paddle_speed, ball_speed,
                                                            lives, serve_wait, life_reward, max_episode_steps, points,
                                                            opponent_width, opponent_speed, win_reward, lose_reward,
                                                            action_repeat, return_reward, alien_rows, alien_rewards,
-                                                           march_period, descend, bomb_period, bomb_speed)
+                                                           march_period, descend, bomb_period, bomb_speed, lanes,
+                                                           car_length, knock_back, crossings, cross_reward, hit_reward)
 
     @staticmethod
     def register_arcade_mix(env_name, tasks):

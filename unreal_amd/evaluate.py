@@ -20,7 +20,9 @@ other ending (last life, the config's max_episode_steps) counts under `timeouts`
  success is a match won, `timeouts` counts the episodes that ended at the step limit, `losses` those the opponent
 won, and the differences of the totals are `points_won_per_episode` and `points_lost_per_episode`.  On invaders
  success is a cleared wave, every other ending (last life, invasion, step limit) counts under `timeouts`, and the
-differences are `aliens_per_episode` and `lives_lost_per_episode` (an invasion counts the lives that were left).  On every game
+differences are `aliens_per_episode` and `lives_lost_per_episode` (an invasion counts the lives that were left).  On
+crossing success is the config's `crossings` reached, every other ending counts under `timeouts`, and the
+differences are `crossings_per_episode` and `hits_per_episode`.  On every game
 `mean_length` counts agent steps: with the config's `action_repeat = k` an episode of that length ran up to k
 game ticks per step.  With `arcade=` the name of a game mixture (Environment.register_arcade_mix) actor b plays
 task b mod K; the result keeps the overall keys over all counted episodes (`timeouts`: the sum of the tasks') and adds
@@ -166,6 +168,9 @@ class Evaluate(object):
             losses = sum(int(not e[4] and e[3] >= conf.points) for e in eps)
             res.update(timeouts=n - successes - losses, losses=losses, points_won_per_episode=sum(bricks) / float(n),
                        points_lost_per_episode=sum(lost) / float(n))
+        elif conf.game == "crossing":
+            res.update(timeouts=n - successes, crossings_per_episode=sum(bricks) / float(n),
+                       hits_per_episode=sum(lost) / float(n))
         elif conf.game == "invaders":
             res.update(timeouts=n - successes, aliens_per_episode=sum(bricks) / float(n),
                        lives_lost_per_episode=sum(lost) / float(n))
@@ -209,7 +214,7 @@ class Evaluate(object):
         evaluation of its game returns, over the episodes of the task's actors."""
         B, ring = self.B, self.env.ring
         # Breakout: bricks, lives lost, walls cleared; duel: points won, points lost, matches won; invaders: aliens shot,
-        # lives lost, waves cleared.  Never zeroed.
+        # lives lost, waves cleared; crossing: crossings, hits, targets reached.  Never zeroed.
         tot = ring.actor_records[:, 10:13]
         ep0 = tot.cpu().numpy().copy()
         steps, counted = [0] * B, [False] * B

@@ -249,6 +249,8 @@ def ring_view(ring, b0, b1):
 ARCADE_BREAKOUT, ARCADE_CFG_WORDS, ARCADE_RECORD = 1, 24, 16   # UNREAL_ARCADE_BREAKOUT / _CFG_WORDS / _RECORD
 ARCADE_DUEL = 3                              # UNREAL_ARCADE_DUEL (2 is no game: the kernels write nothing for it)
 ARCADE_INVADERS = 5                          # UNREAL_ARCADE_INVADERS
+ARCADE_CROSSING = 7                          # UNREAL_ARCADE_CROSSING
+ARCADE_LANE_STREAM = 0x43524F53              # counter word 2 of a crossing reset's lane-phase draw (UNREAL_ARCADE_LANE_STREAM)
 ARCADE_BOMB_STREAM = 0x494E5642              # counter word 2 of an invaders bomb draw (UNREAL_ARCADE_BOMB_STREAM)
 ARCADE_SERVE_STREAM = 0x41524B53             # counter word 2 of a serve draw (UNREAL_ARCADE_SERVE_STREAM)
 ARCADE_MIX_MAX = 16                          # config blocks of a game mixture at the most (UNREAL_ARCADE_MIX_MAX)
