@@ -1,13 +1,14 @@
-// Stand-alone host program around the device arcade's own game, tick-loop and render functions.
+// Stand-alone host program around the functions the device arcade's one step body and one reset body call.
 // tools/check_arcade_host.py cuts those functions unchanged out of unreal_amd/csrc/arcade.hip (and the Philox draw out of
 // maze_common.h) into arcade_functions.inc, builds this file with AddressSanitizer and UBSan, and compares what it writes
-// with tests/repeat_model.py, tests/invaders_model.py and tests/crossing_model.py.  Nothing here runs on a GPU: the qualifiers of the device code are defined away.
+// with tests/repeat_model.py, tests/invaders_model.py and tests/crossing_model.py.  Nothing here runs on a
+// GPU: the qualifiers of the device code are defined away.  One driver calls them in the bodies' order in all three modes.
 // With a third argument `selfplay` the block is the duel's and the actors are the seats of B / 2 self-play games:
-// every actor steps its pair's canonical game from its own record with the two-action tick loop and the mirror, as a
-// workgroup of the self-play kernels does, and is compared with tests/selfplay_model.py.
-// With `versus` the same input is read as B / 2 games of ONE learner each: a game is stepped once with the
-// learner's action (the even column) and the opponent's (the odd one) when both flags are set, as the one workgroup of
-// the versus kernels does, and both views are formed from the one canonical record.  OUT per agent step: for the first F
+// every actor steps SeatSide, its side of its pair's game, from its own record, as a workgroup of the self-play kernels
+// does, and is compared with tests/selfplay_model.py.
+// With `versus` the same input is read as B / 2 games of ONE learner each: a game is stepped once at seat 0
+// with the learner's action (the even column) and the opponent's (the odd one) when both flags are set, as the one workgroup
+// of the versus kernels does, and the opponent's view is formed from the same record.  OUT per agent step: for the first F
 // games the learner's frame (before a reset) and the opponent's frame (what opp_frames holds: after a reset), then per game
 // int32 x (record[16], reward, terminal, ep_steps, episode, opp_last_action, opp_last_reward).
 //
@@ -42,42 +43,81 @@ static inline int __ffs(int x) { return __builtin_ffs(x); }
 namespace {
 #include "arcade_functions.inc"
 
+// what only a seat's game has: M is an involution, and the frame the other seat sees
+template <class G>
+bool mirror_twice_differs(const G&) { return false; }
+bool mirror_twice_differs(const SeatSide& s) {
+  const SeatGame back = mirror(mirror(s.own));
+  return back.g.px != s.own.g.px || back.g.ox != s.own.g.ox || back.g.by != s.own.g.by || back.g.vy != s.own.g.vy ||
+         back.g.mine != s.own.g.mine || back.g.theirs != s.own.g.theirs || back.g.n_won != s.own.g.n_won ||
+         back.g.n_lost != s.own.g.n_lost || back.g.n_matches != s.own.g.n_matches || back.n_other != s.own.n_other;
+}
 template <class G, class R>
-int run(const std::vector<int32_t>& in, FILE* out) {
+void opponent_frame(const G&, const R&, uint32_t*) {}
+void opponent_frame(const SeatSide& s, const DuelRules& rules, uint32_t* now) {
+  const SeatGame opp = mirror(s.own);
+  for (int c = 0; c < kChunks; ++c) {
+    const uint4 v = frame_chunk(opp.g, rules, c);
+    now[4 * c] = v.x; now[4 * c + 1] = v.y; now[4 * c + 2] = v.z; now[4 * c + 3] = v.w;
+  }
+}
+
+enum Mode { kPlainMode, kSelfplayMode, kVersusMode };
+
+// One driver over the overloads the kernels' step and reset bodies call (load, step_ticks, game_over, shown, frame_dirty,
+// reset_episode, store_game), with the seat, the other action and the draws' key each mode's kernels take:
+// plain: actor n plays column n alone; selfplay: actor n is seat (base + n) & 1 of its pair and moves when both columns are
+// active; versus: game n is the learner of column 2 n at seat 0 against column 2 n + 1, keyed by 2 (base / 2 + n).
+// seat_of, key_of, `stepped` and `other` below mirror the views' view_seat, draw_key, view_active and other_action of
+// arcade.hip, which read the kernels' arguments and cannot be called here: a change to one of those belongs here too.
+template <class G, class R>
+int run(const std::vector<int32_t>& in, FILE* out, Mode mode) {
   const int32_t* cfg = in.data();
   const int B = in[24], S = in[25], F = in[26], base = in[27];
+  const int N = mode == kVersusMode ? B / 2 : B, W = mode == kVersusMode ? 22 : 20;
   const int32_t* acts = in.data() + 28;
   const int32_t* active = acts + (size_t)S * B;
-  std::vector<int32_t> rec((size_t)B * kArcadeRecord, 0), steps(B, 0), episode(B, 0), line((size_t)B * 20);
+  std::vector<int32_t> rec((size_t)N * kArcadeRecord, 0), steps(N, 0), episode(N, 0), line((size_t)N * W);
+  std::vector<int32_t> opp_la(N, 0), opp_lr(N, 0);
   std::vector<uint32_t> now(FRAME_BYTES / 4);
   R rules;
   int bad = 0;
-  for (int b = 0; b < B; ++b) {                   // the constructor's reset: episode 0
+  const auto seat_of = [&](int n) { return mode == kSelfplayMode ? (base + n) & 1 : 0; };
+  const auto key_of = [&](int n) {
+    return mode == kSelfplayMode ? (base + n) & ~1 : mode == kVersusMode ? 2 * (base / 2 + n) : base + n;
+  };
+  for (int n = 0; n < N; ++n) {                   // the constructor's reset: episode 0
     G g;
-    load(cfg, &rec[(size_t)b * kArcadeRecord], rules, g);
-    store_game(&rec[(size_t)b * kArcadeRecord], reset_episode(rules, g, base + b, 0));
+    load(cfg, &rec[(size_t)n * kArcadeRecord], seat_of(n), rules, g);
+    store_game(&rec[(size_t)n * kArcadeRecord], reset_episode(rules, g, key_of(n), 0));
   }
   for (int s = 0; s < S; ++s) {
-    for (int b = 0; b < B; ++b) {
-      int32_t* r = &rec[(size_t)b * kArcadeRecord];
+    const int32_t* a = acts + (size_t)s * B;
+    const int32_t* on = active + (size_t)s * B;
+    for (int n = 0; n < N; ++n) {
+      const int col = mode == kVersusMode ? 2 * n : n, ocol = col ^ 1;
+      const bool stepped = on[col] && (mode == kPlainMode || on[ocol]);
+      const int other = mode == kPlainMode ? 0 : a[ocol];
+      int32_t* r = &rec[(size_t)n * kArcadeRecord];
       G old;
-      load(cfg, r, rules, old);
+      load(cfg, r, seat_of(n), rules, old);
       G g = old;
       int32_t reward = -7, terminal = -7;
-      if (active[(size_t)s * B + b]) {
-        reward = step_ticks(g, rules, acts[(size_t)s * B + b], base + b, episode[b]);
-        steps[b] += 1;
-        terminal = game_over(g, rules, steps[b]);
+      int other_reward = 0;
+      if (stepped) {
+        reward = step_ticks(g, rules, a[col], other, key_of(n), episode[n], other_reward);
+        steps[n] += 1;
+        terminal = game_over(shown(g), rules, steps[n]);
       }
-      if (b < F) {                                // the step's render: the new frame, and the difference the kernel's way
-        const auto dirty = frame_dirty(old, g, rules);
+      if (n < F) {                                // the step's render: the new frame, and the difference the kernel's way
+        const auto dirty = frame_dirty(shown(old), shown(g), rules);
         for (int c = 0; c < kChunks; ++c) {
-          const uint4 v = frame_chunk(g, rules, c), o = frame_chunk(old, rules, c);
+          const uint4 v = frame_chunk(shown(g), rules, c), o = frame_chunk(shown(old), rules, c);
           const uint32_t vs[4] = {v.x, v.y, v.z, v.w}, os[4] = {o.x, o.y, o.z, o.w};
           for (int e = 0; e < 4; ++e) {
             now[4 * c + e] = vs[e];
-            if (diff_dword(old, rules, dirty, 4 * c + e, vs[e]) != absdiff_u8x4(vs[e], os[e])) {
-              if (!bad) fprintf(stderr, "step %d actor %d dword %d: the dirty rows miss a difference\n", s, b, 4 * c + e);
+            if (diff_dword(shown(old), rules, dirty, 4 * c + e, vs[e]) != absdiff_u8x4(vs[e], os[e])) {
+              if (!bad) fprintf(stderr, "step %d actor %d dword %d: the dirty rows miss a difference\n", s, n, 4 * c + e);
               bad = 1;
             }
           }
@@ -85,165 +125,27 @@ int run(const std::vector<int32_t>& in, FILE* out) {
         fwrite(now.data(), 1, FRAME_BYTES, out);
       }
       if (terminal == 1) {                        // (crossing's reset draws by the new episode's index)
-        g = reset_episode(rules, g, base + b, episode[b] + 1);
-        steps[b] = 0;
-        episode[b] += 1;
+        g = reset_episode(rules, g, key_of(n), episode[n] + 1);
+        steps[n] = 0;
+        episode[n] += 1;
+      }
+      if (stepped) {                              // what versus keeps of seat 1: zeroed with the learner's at a reset
+        opp_la[n] = terminal == 1 ? 0 : other;
+        opp_lr[n] = terminal == 1 ? 0 : other_reward;
       }
       store_game(r, g);
-      int32_t* l = &line[(size_t)b * 20];
-      std::copy(r, r + kArcadeRecord, l);
-      l[16] = reward; l[17] = terminal; l[18] = steps[b]; l[19] = episode[b];
-    }
-    fwrite(line.data(), 4, line.size(), out);
-  }
-  return bad;
-}
-
-// the seats of B / 2 self-play games: step_seat's game logic and render per actor (B and actor_base even)
-int run_selfplay(const std::vector<int32_t>& in, FILE* out) {
-  const int32_t* cfg = in.data();
-  const int B = in[24], S = in[25], F = in[26], base = in[27];
-  const int32_t* acts = in.data() + 28;
-  const int32_t* active = acts + (size_t)S * B;
-  std::vector<int32_t> rec((size_t)B * kArcadeRecord, 0), steps(B, 0), episode(B, 0), line((size_t)B * 20);
-  std::vector<uint32_t> now(FRAME_BYTES / 4);
-  const DuelRules rules = load_seat_rules(cfg);
-  int bad = 0;
-  for (int b = 0; b < B; ++b) {                   // the constructor's reset: episode 0
-    const int seat = (base + b) & 1;
-    int32_t* r = &rec[(size_t)b * kArcadeRecord];
-    const SeatGame stored = load_seat_game(r);
-    SeatGame canon = seat ? mirror(stored) : stored;
-    canon.g = reset_game(rules, canon.g);
-    store_seat_game(r, seat ? mirror(canon) : canon);
-  }
-  for (int s = 0; s < S; ++s) {
-    const int32_t* a = acts + (size_t)s * B;
-    const int32_t* on = active + (size_t)s * B;
-    for (int b = 0; b < B; ++b) {
-      const int seat = (base + b) & 1, pb = b ^ 1;
-      int32_t* r = &rec[(size_t)b * kArcadeRecord];
-      const SeatGame own_old = load_seat_game(r);
-      SeatGame canon = seat ? mirror(own_old) : own_old;
-      int32_t reward = -7, terminal = -7;
-      if (on[b] && on[pb]) {
-        const SeatRewards rw = step_ticks2(canon, rules, seat ? a[pb] : a[b], seat ? a[b] : a[pb], (base + b) & ~1, episode[b]);
-        reward = seat ? rw.r1 : rw.r0;
-        steps[b] += 1;
-        terminal = game_over(canon.g, rules, steps[b]);
-      }
-      SeatGame own = seat ? mirror(canon) : canon;
-      if (b < F) {                                // the seat's render of its own view, and the difference the kernel's way
-        const DuelGame& old = own_old.g;
-        const DuelGame& g = own.g;
-        const auto dirty = frame_dirty(old, g, rules);
-        for (int c = 0; c < kChunks; ++c) {
-          const uint4 v = frame_chunk(g, rules, c), o = frame_chunk(old, rules, c);
-          const uint32_t vs[4] = {v.x, v.y, v.z, v.w}, os[4] = {o.x, o.y, o.z, o.w};
-          for (int e = 0; e < 4; ++e) {
-            now[4 * c + e] = vs[e];
-            if (diff_dword(old, rules, dirty, 4 * c + e, vs[e]) != absdiff_u8x4(vs[e], os[e])) {
-              if (!bad) fprintf(stderr, "step %d seat %d dword %d: the dirty rows miss a difference\n", s, b, 4 * c + e);
-              bad = 1;
-            }
-          }
-        }
-        fwrite(now.data(), 1, FRAME_BYTES, out);
-      }
-      if (terminal == 1) {
-        canon.g = reset_game(rules, canon.g);
-        own = seat ? mirror(canon) : canon;
-        steps[b] = 0;
-        episode[b] += 1;
-      }
-      store_seat_game(r, own);
-      const SeatGame back = mirror(mirror(own));  // M is an involution
-      if (back.g.px != own.g.px || back.g.ox != own.g.ox || back.g.by != own.g.by || back.g.vy != own.g.vy ||
-          back.g.mine != own.g.mine || back.g.theirs != own.g.theirs || back.g.n_won != own.g.n_won ||
-          back.g.n_lost != own.g.n_lost || back.g.n_matches != own.g.n_matches || back.n_other != own.n_other) {
-        if (!bad) fprintf(stderr, "step %d seat %d: M(M(g)) != g\n", s, b);
+      if (mirror_twice_differs(g)) {
+        if (!bad) fprintf(stderr, "step %d seat %d: M(M(g)) != g\n", s, n);
         bad = 1;
       }
-      int32_t* l = &line[(size_t)b * 20];
-      std::copy(r, r + kArcadeRecord, l);
-      l[16] = reward; l[17] = terminal; l[18] = steps[b]; l[19] = episode[b];
-    }
-    fwrite(line.data(), 4, line.size(), out);
-  }
-  return bad;
-}
-
-// B / 2 games of one learner each: step_versus's game logic and its two renders per game (game i is keyed by 2 (base / 2 + i))
-int run_versus(const std::vector<int32_t>& in, FILE* out) {
-  const int32_t* cfg = in.data();
-  const int B = in[24], S = in[25], F = in[26], base = in[27], G = B / 2;
-  const int32_t* acts = in.data() + 28;
-  const int32_t* active = acts + (size_t)S * B;
-  std::vector<int32_t> rec((size_t)G * kArcadeRecord, 0), steps(G, 0), episode(G, 0), line((size_t)G * 22);
-  std::vector<int32_t> opp_la(G, 0), opp_lr(G, 0);
-  std::vector<uint32_t> now(FRAME_BYTES / 4);
-  const DuelRules rules = load_seat_rules(cfg);
-  int bad = 0;
-  for (int i = 0; i < G; ++i) {                   // the constructor's reset: episode 0
-    int32_t* r = &rec[(size_t)i * kArcadeRecord];
-    SeatGame canon = load_seat_game(r);
-    canon.g = reset_game(rules, canon.g);
-    store_seat_game(r, canon);
-  }
-  for (int s = 0; s < S; ++s) {
-    const int32_t* a = acts + (size_t)s * B;
-    const int32_t* on = active + (size_t)s * B;
-    for (int i = 0; i < G; ++i) {
-      int32_t* r = &rec[(size_t)i * kArcadeRecord];
-      const SeatGame own_old = load_seat_game(r);
-      SeatGame canon = own_old;
-      int32_t reward = -7, terminal = -7;
-      const bool stepped = on[2 * i] && on[2 * i + 1];
-      SeatRewards rw = {0, 0};
-      if (stepped) {
-        rw = step_ticks2(canon, rules, a[2 * i], a[2 * i + 1], 2 * (base / 2 + i), episode[i]);
-        reward = rw.r0;
-        steps[i] += 1;
-        terminal = game_over(canon.g, rules, steps[i]);
-      }
-      if (i < F) {                                // the learner's render, and the difference the kernel's way
-        const DuelGame& old = own_old.g;
-        const DuelGame& g = canon.g;
-        const auto dirty = frame_dirty(old, g, rules);
-        for (int c = 0; c < kChunks; ++c) {
-          const uint4 v = frame_chunk(g, rules, c), o = frame_chunk(old, rules, c);
-          const uint32_t vs[4] = {v.x, v.y, v.z, v.w}, os[4] = {o.x, o.y, o.z, o.w};
-          for (int e = 0; e < 4; ++e) {
-            now[4 * c + e] = vs[e];
-            if (diff_dword(old, rules, dirty, 4 * c + e, vs[e]) != absdiff_u8x4(vs[e], os[e])) {
-              if (!bad) fprintf(stderr, "step %d game %d dword %d: the dirty rows miss a difference\n", s, i, 4 * c + e);
-              bad = 1;
-            }
-          }
-        }
+      if (mode == kVersusMode && n < F) {         // the opponent's render, after the learner's: M of the stored record
+        opponent_frame(g, rules, now.data());
         fwrite(now.data(), 1, FRAME_BYTES, out);
       }
-      if (terminal == 1) {
-        canon.g = reset_game(rules, canon.g);
-        steps[i] = 0;
-        episode[i] += 1;
-      }
-      if (stepped) {
-        opp_la[i] = terminal == 1 ? 0 : a[2 * i + 1];
-        opp_lr[i] = terminal == 1 ? 0 : rw.r1;
-      }
-      store_seat_game(r, canon);
-      if (i < F) {                                // the opponent's render, after the learner's: M of the stored record
-        const SeatGame opp = mirror(canon);
-        for (int c = 0; c < kChunks; ++c) {
-          const uint4 v = frame_chunk(opp.g, rules, c);
-          now[4 * c] = v.x; now[4 * c + 1] = v.y; now[4 * c + 2] = v.z; now[4 * c + 3] = v.w;
-        }
-        fwrite(now.data(), 1, FRAME_BYTES, out);
-      }
-      int32_t* l = &line[(size_t)i * 22];
+      int32_t* l = &line[(size_t)n * W];
       std::copy(r, r + kArcadeRecord, l);
-      l[16] = reward; l[17] = terminal; l[18] = steps[i]; l[19] = episode[i]; l[20] = opp_la[i]; l[21] = opp_lr[i];
+      l[16] = reward; l[17] = terminal; l[18] = steps[n]; l[19] = episode[n];
+      if (mode == kVersusMode) { l[20] = opp_la[n]; l[21] = opp_lr[n]; }
     }
     fwrite(line.data(), 4, line.size(), out);
   }
@@ -269,12 +171,12 @@ int main(int argc, char** argv) {
   if (!out) return 2;
   int bad = 2;
   if (selfplay && !(in[0] == kArcadeDuel && in[24] % 2 == 0 && in[27] % 2 == 0)) bad = 2;
-  else if (versus) bad = in[26] <= in[24] / 2 ? run_versus(in, out) : 2;
-  else if (selfplay) bad = run_selfplay(in, out);
-  else if (in[0] == kArcadeBreakout) bad = run<Game, Rules>(in, out);
-  else if (in[0] == kArcadeDuel) bad = run<DuelGame, DuelRules>(in, out);
-  else if (in[0] == kArcadeInvaders) bad = run<InvGame, InvRules>(in, out);
-  else if (in[0] == kArcadeCrossing) bad = run<CrossGame, CrossRules>(in, out);
+  else if (versus) bad = in[26] <= in[24] / 2 ? run<SeatSide, DuelRules>(in, out, kVersusMode) : 2;
+  else if (selfplay) bad = run<SeatSide, DuelRules>(in, out, kSelfplayMode);
+  else if (in[0] == kArcadeBreakout) bad = run<Game, Rules>(in, out, kPlainMode);
+  else if (in[0] == kArcadeDuel) bad = run<DuelGame, DuelRules>(in, out, kPlainMode);
+  else if (in[0] == kArcadeInvaders) bad = run<InvGame, InvRules>(in, out, kPlainMode);
+  else if (in[0] == kArcadeCrossing) bad = run<CrossGame, CrossRules>(in, out, kPlainMode);
   fclose(out);
   return bad;
 }

@@ -4,14 +4,15 @@ host models of tests/repeat_model.py (Breakout and the duel), tests
 tests/crossing_model.py (crossing, §7x: five random traces, two scripted ones) and
 tests/selfplay_model.py (the self-play duel's two-action tick and mirror, §7v).  No GPU is used and nothing loaded into Python is sanitized.
 
-The functions are cut unchanged out of unreal_amd/csrc/arcade.hip (everything from its constants to `frame_chunk`:
-`load_rules`, `step_game`, `game_ended`, `game_over`, `reset_game`, `store_game`, `step_ticks`, `frame_dirty`, `diff_dword`, ...,
-of all four games) and the Philox draw out of maze_common.h, and compiled with tools/arcade_host_main.cpp into a stand-alone
-program.  Over every trace of tests/repeat_model.py (six random ones of 200 actors x 300 agent steps, two scripted ones) and
+The functions are cut unchanged out of unreal_amd/csrc/arcade.hip, one range from its constants to the last overload of
+`SeatSide` (everything in front of `store_frame`: `load`, `step_game`, `step_ticks`, `game_ended`, `game_over`, `shown`,
+`reset_episode`, `store_game`, `frame_dirty`, `diff_dword`, `frame_chunk`, ..., of all four games and of the two-seat duel),
+and the Philox draw out of maze_common.h, and compiled with tools/arcade_host_main.cpp into a stand-alone program whose one
+driver calls the overloads the kernels' one step body and one reset body call, in their order.  Over every trace of tests/repeat_model.py (six random ones of 200 actors x 300 agent steps, two scripted ones) and
 of tests/invaders_model.py (four random ones, one scripted) it is compared on every record, reward, terminal, ep_steps and episode, on every frame byte of the traces' watched actors, and
 inside the program every difference dword of the dirty-row path against the full byte-wise difference of the two frames.
-The self-play functions (`mirror`, `step_game2`, `step_ticks2`, from `struct SeatGame` to the seat body) are cut the same
-way; over the four traces of tests/selfplay_model.py (64 seats x 300 steps) every seat steps its pair's game from its own
+The self-play functions (`mirror`, `step_game2`, `step_ticks2` and the overloads of `SeatSide`) lie in the same range; over
+the four traces of tests/selfplay_model.py (64 seats x 300 steps) every seat steps its pair's game from its own
 record as a workgroup does and is compared on the same words, and on the frames of the first three pairs.
 The program's `versus` mode runs the one-workgroup two-view step over the same four traces as 32 games of one
 learner each (even columns the learner's actions, odd ones the opponent's): records, rewards, terminals, ep_steps, episode
@@ -136,7 +137,6 @@ def main():
     with open(os.path.join(work, "arcade_functions.inc"), "w") as f:
         f.write(cut(os.path.join(CSRC, "maze_common.h"), "// ---- Philox4x32-10", "// ---- maze configuration block"))
         f.write(src[begin:end])
-        f.write(src[src.index("// a seat's record:"):src.index("// One agent step of the seat of workgroup")])
     exe = os.path.join(work, "arcade_host_check")
     subprocess.check_call([args.cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I", work, os.path.join(ROOT, "tools", "arcade_host_main.cpp"), "-o", exe])

@@ -6,8 +6,17 @@
 // rules, the 24-word config blocks and the 16-word per-actor records are documented with the entries in
 // include/unreal_hip.h; tests/arcade_model.py, tests/duel_model.py, tests/invaders_model.py and tests/crossing_model.py are
 // the host models every kernel here is compared with bit for bit.
-// The kernels read the game id from the block (uniform) and run that game's instance of one body.  The _mix entries at the
-// end of the file give every actor its own block of up to 16, chosen by its global index, through the same body.
+//
+// One step body (step_view) and one reset body (reset_view) serve all twelve kernels.  What they ask of a game they ask by
+// type, through overloads (load, step_ticks, game_over, shown, frame_dirty, reset_episode, store_game): the four games,
+// and SeatSide, one side of the two-seat duel, which self-play (§7v) and versus (§7w) play.  What differs per launch is a
+// "view", a tag struct with overloads of its own: which rows get a policy wave, the active and mask flags, where the other
+// paddle's action comes from, the key of the draws, and what is stored after the actor's own words (versus: the
+// opponent's).  The plain kernels read the game id from the block (uniform) and run that game's instance of the body; the
+// _mix kernels (§7u) give every actor its own block of up to 16, chosen by its global index; the self-play and versus
+// kernels take the duel's block alone.  The file runs: games, the body's overloads, render, the two-seat duel (all pure:
+// compiled for the CPU by tools/check_arcade_host.py), views and bodies, kernels, then the host side: one argument check,
+// four argument builders, one launcher and the 24 entries.
 //
 // One actor per 256-thread workgroup.  The game logic is computed by every thread from the record (uniform: scalar
 // registers).  The stored frame of s_t is always the render of the pre-step record, so the step renders the new record
@@ -921,26 +930,32 @@ __device__ __forceinline__ InvDirty frame_dirty(const CrossGame& a, const CrossG
   return d;
 }
 
-// what the one body below asks of a game by type
-__device__ __forceinline__ void load(const int* cfg, const int* rec, CrossRules& r, CrossGame& g) {
+// What the one step body and the one reset body below ask of a game by type: load, step_ticks, game_over / game_ended,
+// shown, frame_dirty, reset_episode and store_game.  `seat`, `other` and `other_reward` are the two-seat duel's (SeatSide,
+// further down): a game with one actor ignores them.
+__device__ __forceinline__ void load(const int* cfg, const int* rec, int, CrossRules& r, CrossGame& g) {
   r = load_cross_rules(cfg); g = load_cross_game(rec);
 }
 // (the other games' resets make no draw)
 template <class G, class R>
 __device__ __forceinline__ G reset_episode(const R& r, const G& old, int, int) { return reset_game(r, old); }
-__device__ __forceinline__ void load(const int* cfg, const int* rec, Rules& r, Game& g) { r = load_rules(cfg); g = load_game(rec); }
-__device__ __forceinline__ void load(const int* cfg, const int* rec, DuelRules& r, DuelGame& g) {
+__device__ __forceinline__ void load(const int* cfg, const int* rec, int, Rules& r, Game& g) { r = load_rules(cfg); g = load_game(rec); }
+__device__ __forceinline__ void load(const int* cfg, const int* rec, int, DuelRules& r, DuelGame& g) {
   r = load_duel_rules(cfg); g = load_duel_game(rec);
 }
-__device__ __forceinline__ void load(const int* cfg, const int* rec, InvRules& r, InvGame& g) {
+__device__ __forceinline__ void load(const int* cfg, const int* rec, int, InvRules& r, InvGame& g) {
   r = load_inv_rules(cfg); g = load_inv_game(rec);
 }
+
+// the state whose frame the actor sees: the stored one
+template <class G>
+__device__ __forceinline__ const G& shown(const G& g) { return g; }
 
 // One agent step of global actor `actor` in episode `ep` ("An agent step" in the header): up to repeat + 1 ticks with the
 // same action, none after the tick that ends the game; -> the sum of the ticks' rewards.  The loop stays a loop: eight
 // inlined copies of a tick would not fit the step kernel's registers.
 template <class G, class R>
-__device__ __forceinline__ int step_ticks(G& g, const R& r, int a, int actor, int ep) {
+__device__ __forceinline__ int step_ticks(G& g, const R& r, int a, int /*other*/, int actor, int ep, int& /*other_reward*/) {
   int reward = 0;
 #pragma unroll 1
   for (int tick = 0;; ++tick) {
@@ -991,496 +1006,11 @@ __device__ __forceinline__ uint4 frame_chunk(const G& g, const R& r, int c) {
                     frame_dword(g, r, 4 * c + 3));
 }
 
-template <class G, class R>
-__device__ __forceinline__ void store_frame(uint8_t* dst, const G& g, const R& r) {
-  uint4* d4 = reinterpret_cast<uint4*>(dst);
-  for (int c = threadIdx.x; c < kChunks; c += 256) d4[c] = frame_chunk(g, r, c);
-}
-
-// One agent step of actor blockIdx.x of game (G, R).  `diff` (|s_{t+1} - s_t|, byte-wise) and `s_act` are the kernel's LDS.
-// TL (the _tl entries, DESIGN §7o): an episode that ends in this step only because of the step limit keeps its final
-// observation in final_obs[b] and is flagged 2 instead of 1.  An instance of its own: the step kernel sits on a register
-// tier's edge (§7n), so the plain instance's code stays what it is.
-template <class G, class R, bool TL = false>
-__device__ __forceinline__ void step_actor(const ArcadeArgs& p, uint4* diff, int* s_act) {
-  const int* cfg = p.cfg;
-  const int b = blockIdx.x;
-  const int H1 = p.H1;
-  if (p.pol_x && threadIdx.x < 64) {            // the policy of this actor on wave 0 (for idle actors too, as unreal_policy_step)
-    const int act = policy_row<4>(p.pol_x + (size_t)b * p.pol_ldx, p.Wp, p.bp, p.Wv, p.bv, p.pol_u + b,
-                                  p.pi_out + (size_t)b * 4, p.v_out + b, threadIdx.x);
-    if (threadIdx.x == 0) { *s_act = act; p.act_out[b] = act; }
-  }
-  const int cnt = p.count[b];
-  const int slot = cnt % H1;
-  const int act_flag = p.active_rw ? p.active_rw[b] : (p.active ? p.active[b] : 1);
-  const int la = p.last_action[b];
-  const float lr = p.last_reward[b];
-  if (!act_flag) {
-    if (threadIdx.x == 0) rollout_idle(p, b, slot, la, lr);
-    return;
-  }
-  int* rec = p.records + (size_t)kArcadeRecord * b;
-  R rules;
-  G old;
-  load(cfg, rec, rules, old);
-  const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
-  const int steps = p.ep_steps[b] + 1;
-  const int epi = p.episode[b];
-  const int ns = p.active_rw ? p.n_steps[b] : 0;
-  const float ep = p.track_score ? p.episode_reward[b] : 0.f;
-  __syncthreads();                              // the drawn action is in LDS; every thread has read the record
-  const int a = p.pol_x ? *s_act : p.actions[b];
-
-  // only the record after the agent step's last tick is drawn, so everything below sees two records, as with one tick
-  G g = old;
-  const float reward = (float)step_ticks(g, rules, a, p.actor_base + b, epi);
-  const bool terminal = game_over(g, rules, steps);
-  const RingStep ring = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
-  uint8_t* dst = p.frames + ((size_t)b * H1 + ring.nslot) * FRAME_BYTES;
-  const bool cut = TL && ring.reset && !game_ended(g, rules);      // (uniform) ended by the step limit alone
-  uint8_t* fin = TL ? p.final_obs + (size_t)b * FRAME_BYTES : nullptr;
-
-  // s_{t+1} and, in the rows where it can differ, s_t, 16 bytes per lane: the new chunk is stored unless the episode
-  // restarts, the difference goes to LDS
-  const auto dirty = frame_dirty(old, g, rules);
-#pragma unroll 1
-  for (int k = 0; k < kChunksPerThread; ++k) {
-    const int c = threadIdx.x + 256 * k;
-    if (c < kChunks) {
-      const uint4 v = frame_chunk(g, rules, c);
-      if (!ring.reset) reinterpret_cast<uint4*>(dst)[c] = v;
-      if constexpr (TL) {
-        if (cut) reinterpret_cast<uint4*>(fin)[c] = v;
-      }
-      diff[c] = make_uint4(diff_dword(old, rules, dirty, 4 * c, v.x), diff_dword(old, rules, dirty, 4 * c + 1, v.y),
-                           diff_dword(old, rules, dirty, 4 * c + 2, v.z), diff_dword(old, rules, dirty, 4 * c + 3, v.w));
-    }
-  }
-  __syncthreads();
-  // pixel change: cell (i, j) sums rows 4i+2..4i+5, bytes 12j+6..12j+17 of the difference (the [2:-2] crop, 4 x 4 blocks)
-  {
-    const uint32_t* d32 = reinterpret_cast<const uint32_t*>(diff);
-    for (int c = threadIdx.x; c < PC_CELLS; c += 256) {
-      const int i = c / 20, j = c - 20 * i;
-      int sum = 0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const uint32_t* q = d32 + (4 * i + 2 + r) * kRowDw + 3 * j + 1;
-        sum += bytesum(q[0] >> 16) + bytesum(q[1]) + bytesum(q[2]) + bytesum(q[3] & 0xFFFFu);
-      }
-      p.r_pc[ring.base * PC_CELLS + c] = (float)sum / kPcDenom;
-    }
-  }
-  if (ring.reset) {                             // (uniform) the next episode's first observation goes into the slot instead
-    g = reset_episode(rules, g, p.actor_base + b, epi + 1);
-    store_frame(dst, g, rules);
-  }
-  if (threadIdx.x == 0) {
-    ring_commit(p, b, ring, a, reward, reward, la, lr, ep);
-    store_game(rec, g);
-    p.ep_steps[b] = ring.reset ? 0 : steps;
-    p.episode[b] = epi + (ring.reset ? 1 : 0);
-    rollout_commit(p, b, ring, ns, a, reward);
-    if constexpr (TL) {
-      if (cut) {                                  // the three words the commits above have set to 1
-        p.r_terminal[ring.base] = 2;
-        if (p.out_terminal) p.out_terminal[b] = 2;
-        p.terminal_end[b] = 2;
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void arcade_step_kernel(ArcadeArgs p) {
-  __shared__ uint4 diff[kChunks];
-  __shared__ int s_act;
-  const int game = p.cfg[0];                    // (uniform) a block of another game: nothing is written
-  if (game == kArcadeBreakout) step_actor<Game, Rules>(p, diff, &s_act);
-  else if (game == kArcadeDuel) step_actor<DuelGame, DuelRules>(p, diff, &s_act);
-  else if (game == kArcadeInvaders) step_actor<InvGame, InvRules>(p, diff, &s_act);
-  else if (game == kArcadeCrossing) step_actor<CrossGame, CrossRules>(p, diff, &s_act);
-}
-
-// the rollout step of the _tl entries
-__global__ __launch_bounds__(256) void arcade_step_tl_kernel(ArcadeArgs p) {
-  __shared__ uint4 diff[kChunks];
-  __shared__ int s_act;
-  const int game = p.cfg[0];                    // (uniform) as above
-  if (game == kArcadeBreakout) step_actor<Game, Rules, true>(p, diff, &s_act);
-  else if (game == kArcadeDuel) step_actor<DuelGame, DuelRules, true>(p, diff, &s_act);
-  else if (game == kArcadeInvaders) step_actor<InvGame, InvRules, true>(p, diff, &s_act);
-  else if (game == kArcadeCrossing) step_actor<CrossGame, CrossRules, true>(p, diff, &s_act);
-}
-
-template <class G, class R>
-__device__ __forceinline__ void reset_actor(const ArcadeArgs& p) {
-  const int b = blockIdx.x;
-  if (p.mask && !p.mask[b]) return;
-  int* rec = p.records + (size_t)kArcadeRecord * b;
-  R rules;
-  G old;
-  load(p.cfg, rec, rules, old);
-  const int epi = p.episode[b];
-  __syncthreads();                              // every thread has read the record
-  const G g = reset_episode(rules, old, p.actor_base + b, epi + 1);
-  store_frame(p.frames + ((size_t)b * p.H1 + p.count[b] % p.H1) * FRAME_BYTES, g, rules);
-  if (threadIdx.x == 0) {
-    store_game(rec, g);
-    p.ep_steps[b] = 0;
-    p.episode[b] = epi + 1;
-    p.last_action[b] = 0;
-    p.last_reward[b] = 0.f;
-  }
-}
-
-__global__ __launch_bounds__(256) void arcade_reset_kernel(ArcadeArgs p) {
-  const int game = p.cfg[0];                    // (uniform) as in the step
-  if (game == kArcadeBreakout) reset_actor<Game, Rules>(p);
-  else if (game == kArcadeDuel) reset_actor<DuelGame, DuelRules>(p);
-  else if (game == kArcadeInvaders) reset_actor<InvGame, InvRules>(p);
-  else if (game == kArcadeCrossing) reset_actor<CrossGame, CrossRules>(p);
-}
-
-// ---- game mixtures (DESIGN §7u): one config block per actor ------------------------------------------------------------
-// Global actor g plays block g % n_blocks of `n_blocks` consecutive blocks.  The kernels below are the three above with
-// the block chosen per workgroup (one actor per workgroup: the game branch stays uniform); the bodies are the same
-// instances of step_actor / reset_actor, called on a copy of the arguments whose cfg points at the actor's block.  The
-// arguments the kernels above are compiled from stay what they were: the mixture's words travel in a wrapper.
-constexpr int kArcadeCfgWords = 24, kMaxMixBlocks = 16;
-
-struct ArcadeMixArgs {
-  ArcadeArgs a;
-  int n_blocks;          // 1..16
-  float* done_return;    // [B] (nullable, with done_episodes): the sum of the scores of the actor's finished episodes
-  int* done_episodes;    // [B] their number
-};
-
-__device__ __forceinline__ ArcadeArgs mix_actor_args(const ArcadeMixArgs& m) {
-  ArcadeArgs p = m.a;
-  p.cfg += kArcadeCfgWords * ((p.actor_base + (int)blockIdx.x) % m.n_blocks);
-  return p;
-}
-
-// step_actor, then the per-task statistics where the step ended an episode: the score is the value ring_commit has just
-// written to score_out[b] (thread 0's own stores, read back by thread 0).  Per-actor sums: no atomics.
-// Whether it did is read from what the step left.  A rollout form (active_rw; the _tl kernel serves only those) always
-// restarts a finished episode, so active_log_t[b] = 1 (the actor stepped) and ep_steps[b] = 0 say so, and nothing has to
-// be kept over the step, whose body sits on a register tier's edge.  The plain step may run without a restart: there the
-// slot an active actor commits is taken before the step, and that slot's terminal flag is read after it.
-template <class G, class R, bool TL>
-__device__ __forceinline__ void mix_step_actor(const ArcadeMixArgs& m, const ArcadeArgs& p, uint4* diff, int* s_act) {
-  const int b = blockIdx.x;
-  int slot = -1;                                // the slot of an active actor's plain step (-1: no statistics, or idle)
-  if constexpr (!TL) {
-    if (m.done_return && p.track_score && !p.active_rw && (p.active ? p.active[b] : 1)) slot = p.count[b] % p.H1;
-  }
-  step_actor<G, R, TL>(p, diff, s_act);
-  if constexpr (TL) {                           // (a rollout form: it tracks the score and has active_rw)
-    if (m.done_return && threadIdx.x == 0 && p.active_log_t[b] && p.ep_steps[b] == 0) {
-      m.done_return[b] += p.score_out[b];
-      m.done_episodes[b] += 1;
-    }
-  } else if (m.done_return && p.track_score && threadIdx.x == 0) {
-    const bool ended = p.active_rw ? p.active_log_t[b] && p.ep_steps[b] == 0
-                                   : slot >= 0 && p.r_terminal[(size_t)b * p.H1 + slot] != 0;
-    if (ended) {
-      m.done_return[b] += p.score_out[b];
-      m.done_episodes[b] += 1;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void arcade_mix_step_kernel(ArcadeMixArgs m) {
-  __shared__ uint4 diff[kChunks];
-  __shared__ int s_act;
-  const ArcadeArgs p = mix_actor_args(m);
-  const int game = p.cfg[0];                    // (uniform per workgroup) a block of another game: this actor writes nothing
-  if (game == kArcadeBreakout) mix_step_actor<Game, Rules, false>(m, p, diff, &s_act);
-  else if (game == kArcadeDuel) mix_step_actor<DuelGame, DuelRules, false>(m, p, diff, &s_act);
-  else if (game == kArcadeInvaders) mix_step_actor<InvGame, InvRules, false>(m, p, diff, &s_act);
-  else if (game == kArcadeCrossing) mix_step_actor<CrossGame, CrossRules, false>(m, p, diff, &s_act);
-}
-
-__global__ __launch_bounds__(256) void arcade_mix_step_tl_kernel(ArcadeMixArgs m) {
-  __shared__ uint4 diff[kChunks];
-  __shared__ int s_act;
-  ArcadeArgs p = mix_actor_args(m);
-  // the _tl entries are rollout forms: what every one of them passes is known here, and need not be kept
-  p.active = nullptr; p.reset_on_terminal = 1; p.track_score = 1;
-  const int game = p.cfg[0];                    // (uniform per workgroup) as above
-  if (game == kArcadeBreakout) mix_step_actor<Game, Rules, true>(m, p, diff, &s_act);
-  else if (game == kArcadeDuel) mix_step_actor<DuelGame, DuelRules, true>(m, p, diff, &s_act);
-  else if (game == kArcadeInvaders) mix_step_actor<InvGame, InvRules, true>(m, p, diff, &s_act);
-  else if (game == kArcadeCrossing) mix_step_actor<CrossGame, CrossRules, true>(m, p, diff, &s_act);
-}
-
-__global__ __launch_bounds__(256) void arcade_mix_reset_kernel(ArcadeMixArgs m) {
-  const ArcadeArgs p = mix_actor_args(m);
-  const int game = p.cfg[0];                    // (uniform per workgroup) as in the step
-  if (game == kArcadeBreakout) reset_actor<Game, Rules>(p);
-  else if (game == kArcadeDuel) reset_actor<DuelGame, DuelRules>(p);
-  else if (game == kArcadeInvaders) reset_actor<InvGame, InvRules>(p);
-  else if (game == kArcadeCrossing) reset_actor<CrossGame, CrossRules>(p);
-}
-
-// ---- host side: one check and one launcher for the four entries -------------------------------------------------------
-enum ArcadeEntry { kReset, kStep, kRollout, kPolicy };
-
-// Every pointer the kernels of the entry write through or read is non-null, frames are 16-byte aligned (16 B per lane),
-// and the game has four actions.  (The block lives in device memory: its words are checked by the kernels.)
-bool arcade_args_ok(ArcadeEntry e, const ArcadeArgs& p) {
-  if (p.B <= 0 || p.H1 < 2 || !p.last_action || !p.last_reward || !p.count || !p.frames) return false;
-  if ((uintptr_t)p.frames & 15) return false;
-  if (!p.cfg || ((uintptr_t)p.cfg & 3) || p.actor_base < 0 || !p.ep_steps || !p.episode || !p.records) return false;
-  if (e == kReset) return true;
-  if (!p.r_reward || !p.r_action || !p.r_terminal || !p.r_last_action || !p.r_last_reward || !p.r_pc) return false;
-  if (p.track_score && (!p.episode_reward || !p.score_out || !p.score_valid)) return false;
-  if (e != kPolicy && !p.actions) return false;
-  if (e == kStep) return true;
-  if (!p.active_rw || !p.active_log_t || !p.n_steps || !p.terminal_end || p.idx_base < 0) return false;
-  if (p.A != 4) return false;                   // the games' minimal action set
-  if (p.next_lar && (p.lar_col0 < 0 || p.lar_ld < p.lar_col0 + p.A + 1)) return false;
-  if (e == kRollout) return true;
-  return p.pol_x && p.pol_ldx >= LSTM_N && p.Wp && p.bp && p.Wv && p.bv && p.pol_u && p.pi_out && p.v_out && p.act_out;
-}
-
-// fills in the tail, checks and launches (one launch shape: no label is recorded)
-// `final_obs` (the _tl entries, which are rollout entries): [B] frames, 16-byte aligned; selects the kernel that keeps them
-int arcade_launch(ArcadeEntry e, ArcadeArgs& p, const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
-                  void* stream, bool tl = false, uint8_t* final_obs = nullptr) {
-  p.cfg = cfg; p.actor_base = actor_base; p.ep_steps = ep_steps; p.episode = episode; p.records = records;
-  if (tl) p.final_obs = final_obs;
-  if (!arcade_args_ok(e, p)) return UNREAL_EINVAL;
-  if (tl && (!final_obs || ((uintptr_t)final_obs & 15) || (e != kRollout && e != kPolicy))) return UNREAL_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  if (e == kReset) hipLaunchKernelGGL(arcade_reset_kernel, dim3(p.B), dim3(256), 0, s, p);
-  else if (tl) hipLaunchKernelGGL(arcade_step_tl_kernel, dim3(p.B), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(arcade_step_kernel, dim3(p.B), dim3(256), 0, s, p);
-  return unreal_launch_status();
-}
-
-// the mixture's launcher: arcade_launch's tail and checks, then n_blocks in 1..16 and both statistics arrays or neither
-int arcade_mix_launch(ArcadeEntry e, ArcadeArgs& p, const int* cfg, int n_blocks, int actor_base, int* ep_steps, int* episode,
-                      int* records, float* done_return, int* done_episodes, void* stream, bool tl = false,
-                      uint8_t* final_obs = nullptr) {
-  p.cfg = cfg; p.actor_base = actor_base; p.ep_steps = ep_steps; p.episode = episode; p.records = records;
-  if (tl) p.final_obs = final_obs;
-  if (!arcade_args_ok(e, p)) return UNREAL_EINVAL;
-  if (tl && (!final_obs || ((uintptr_t)final_obs & 15) || (e != kRollout && e != kPolicy))) return UNREAL_EINVAL;
-  if (n_blocks < 1 || n_blocks > kMaxMixBlocks || !done_return != !done_episodes) return UNREAL_EINVAL;
-  const ArcadeMixArgs m{p, n_blocks, done_return, done_episodes};
-  hipStream_t s = (hipStream_t)stream;
-  if (e == kReset) hipLaunchKernelGGL(arcade_mix_reset_kernel, dim3(p.B), dim3(256), 0, s, m);
-  else if (tl) hipLaunchKernelGGL(arcade_mix_step_tl_kernel, dim3(p.B), dim3(256), 0, s, m);
-  else hipLaunchKernelGGL(arcade_mix_step_kernel, dim3(p.B), dim3(256), 0, s, m);
-  return unreal_launch_status();
-}
-
-}  // namespace
-
-extern "C" {
-
-// `pos` is the maze's argument of that name: the arcade keeps its state in `records` and never touches it (nullable).
-
-int unreal_arcade_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward, const int* count,
-                        uint8_t* frames, const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
-                        void* stream) {
-  (void)pos;
-  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, const_cast<int*>(count), frames};
-  p.mask = mask;
-  return arcade_launch(kReset, p, cfg, actor_base, ep_steps, episode, records, stream);
-}
-
-int unreal_arcade_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
-                       float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
-                       int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
-                       float* episode_reward, float* score_out, int* score_valid, int reset_on_terminal, int track_score,
-                       const int* cfg, int actor_base, int* ep_steps, int* episode, int* records, void* stream) {
-  (void)pos;
-  ArcadeArgs p{B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid,
-               reset_on_terminal, track_score};
-  return arcade_launch(kStep, p, cfg, actor_base, ep_steps, episode, records, stream);
-}
-
-int unreal_arcade_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
-                               int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
-                               int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                               int* out_terminal, float* episode_reward, float* score_out, int* score_valid, int* active,
-                               int* active_log_t, int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
-                               int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg, int actor_base,
-                               int* ep_steps, int* episode, int* records, void* stream) {
-  (void)pos;
-  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
-  return arcade_launch(kRollout, p, cfg, actor_base, ep_steps, episode, records, stream);
-}
-
-int unreal_arcade_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
-                                      const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
-                                      int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
-                                      uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
-                                      int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                                      int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
-                                      int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
-                                      float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
-                                      int actor_base, int* ep_steps, int* episode, int* records, void* stream) {
-  (void)pos;
-  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
-               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
-  return arcade_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, stream);
-}
-
-// The two rollout entries with time-limit bootstrapping (DESIGN §7o): `final_obs` [B] frames.
-
-int unreal_arcade_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
-                                  int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
-                                  int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                                  int* out_terminal, float* episode_reward, float* score_out, int* score_valid, int* active,
-                                  int* active_log_t, int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
-                                  int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg, int actor_base,
-                                  int* ep_steps, int* episode, int* records, uint8_t* final_obs, void* stream) {
-  (void)pos;
-  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
-  return arcade_launch(kRollout, p, cfg, actor_base, ep_steps, episode, records, stream, true, final_obs);
-}
-
-int unreal_arcade_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
-                                         const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
-                                         int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
-                                         uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
-                                         int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                                         int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
-                                         int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
-                                         float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
-                                         const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
-                                         uint8_t* final_obs, void* stream) {
-  (void)pos;
-  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
-               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
-  return arcade_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, stream, true, final_obs);
-}
-
-// Game mixtures (DESIGN §7u): the six entries above over `n_blocks` consecutive blocks, actor g on block g % n_blocks;
-// done_return / done_episodes [B] (both or neither): the per-actor sums of finished episodes' scores and their number.
-
-int unreal_arcade_mix_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
-                            const int* count, uint8_t* frames, const int* cfg, int n_blocks, int actor_base,
-                            int* ep_steps, int* episode, int* records, void* stream) {
-  (void)pos;
-  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, const_cast<int*>(count), frames};
-  p.mask = mask;
-  return arcade_mix_launch(kReset, p, cfg, n_blocks, actor_base, ep_steps, episode, records, nullptr, nullptr, stream);
-}
-
-int unreal_arcade_mix_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
-                           float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
-                           int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                           int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
-                           int reset_on_terminal, int track_score, const int* cfg, int n_blocks, int actor_base,
-                           int* ep_steps, int* episode, int* records, float* done_return, int* done_episodes,
-                           void* stream) {
-  (void)pos;
-  ArcadeArgs p{B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid,
-               reset_on_terminal, track_score};
-  return arcade_mix_launch(kStep, p, cfg, n_blocks, actor_base, ep_steps, episode, records, done_return, done_episodes,
-                           stream);
-}
-
-int unreal_arcade_mix_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
-                                   int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
-                                   int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                                   int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
-                                   int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
-                                   float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
-                                   int n_blocks, int actor_base, int* ep_steps, int* episode, int* records,
-                                   float* done_return, int* done_episodes, void* stream) {
-  (void)pos;
-  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
-  return arcade_mix_launch(kRollout, p, cfg, n_blocks, actor_base, ep_steps, episode, records, done_return,
-                           done_episodes, stream);
-}
-
-int unreal_arcade_mix_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
-                                          const float* Wv, const float* bv, const double* u, float* pi_out,
-                                          float* v_out, int* actions_out, int* pos, int* last_action,
-                                          float* last_reward, int* count, uint8_t* frames, float* r_reward,
-                                          int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
-                                          float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
-                                          float* score_out, int* score_valid, int* active, int* active_log_t,
-                                          int* n_steps, int* terminal_end, int* next_idx, float* next_lar, int lar_ld,
-                                          int lar_col0, int A, int idx_base_actor, const int* cfg, int n_blocks,
-                                          int actor_base, int* ep_steps, int* episode, int* records, float* done_return,
-                                          int* done_episodes, void* stream) {
-  (void)pos;
-  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
-               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
-  return arcade_mix_launch(kPolicy, p, cfg, n_blocks, actor_base, ep_steps, episode, records, done_return,
-                           done_episodes, stream);
-}
-
-int unreal_arcade_mix_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
-                                      int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
-                                      int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                                      int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
-                                      int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
-                                      float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
-                                      const int* cfg, int n_blocks, int actor_base, int* ep_steps, int* episode,
-                                      int* records, uint8_t* final_obs, float* done_return, int* done_episodes,
-                                      void* stream) {
-  (void)pos;
-  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
-  return arcade_mix_launch(kRollout, p, cfg, n_blocks, actor_base, ep_steps, episode, records, done_return,
-                           done_episodes, stream, true, final_obs);
-}
-
-int unreal_arcade_mix_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
-                                             const float* Wv, const float* bv, const double* u, float* pi_out,
-                                             float* v_out, int* actions_out, int* pos, int* last_action,
-                                             float* last_reward, int* count, uint8_t* frames, float* r_reward,
-                                             int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
-                                             float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
-                                             float* score_out, int* score_valid, int* active, int* active_log_t,
-                                             int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
-                                             int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
-                                             int n_blocks, int actor_base, int* ep_steps, int* episode, int* records,
-                                             uint8_t* final_obs, float* done_return, int* done_episodes, void* stream) {
-  (void)pos;
-  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
-               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
-  return arcade_mix_launch(kPolicy, p, cfg, n_blocks, actor_base, ep_steps, episode, records, done_return,
-                           done_episodes, stream, true, final_obs);
-}
-
-}  // extern "C"
-
-// ---- self-play: both paddles of the duel driven by actors -------------------------------------------------
-// A launch of B actors holds B / 2 games: global actors 2 i and 2 i + 1 are seat 0 and seat 1 of game i.  The canonical
-// game is the duel with its top paddle moved by seat 1's action instead of the script, the width of the bottom one, and a
-// serve on either seat's fire, drawn with seat 0's global index.  Seat 0 stores the canonical record, seat 1 its mirror
-// image M (include/unreal_hip.h), so that the duel's render functions above, applied to a seat's own record, show every
-// seat itself at the bottom.  One workgroup per SEAT, as everywhere else: both workgroups of a pair step the same game
-// from their own copy of it with both actions and keep their own view, reward, frame and ring words.  No workgroup reads
-// a word another workgroup of the launch writes: of its partner it reads actions, the read-only active / mask flags and
-// the policy's input rows.  Everything above this line is what it was.
-namespace {
+// ---- the two-seat duel: both paddles of the duel moved by actions ------------------------------------
+// The canonical game is the duel with its top paddle moved by seat 1's action instead of the script, the width of the
+// bottom one, and a serve on either seat's fire.  Seat 0 stores the canonical record, seat 1 its mirror image M
+// (include/unreal_hip.h), so that the duel's render functions above, applied to a seat's own record, show every seat
+// itself at the bottom.
 
 // a seat's record: the duel's thirteen words and word 13, the other seat's matches won
 struct SeatGame {
@@ -1594,36 +1124,152 @@ __device__ __forceinline__ SeatRewards step_ticks2(SeatGame& s, const DuelRules&
   return rw;
 }
 
-// One agent step of the seat of workgroup blockIdx.x: step_actor with the canonical game between the seat's two views.
-// `s_act`: [2], the seat's own action and its partner's; `s_pol`: [5], the partner's pi and v, which nobody reads.
-template <bool TL>
-__device__ __forceinline__ void step_seat(const ArcadeArgs& p, uint4* diff, int* s_act, float* s_pol) {
-  const int b = blockIdx.x, pb = b ^ 1;         // (B and actor_base are even: the partner is in the launch)
-  const int seat = (p.actor_base + b) & 1;
+// One side of the two-seat duel as a game of its own, by the overloads the plain games have: what a seat stores and sees
+// is its own record; a step or a restart goes from it through the canonical game and back (M is an involution, and the
+// game's end is the same from both sides).  Versus is this game at seat 0.  Nothing down to here knows of threads,
+// kernel arguments or LDS: tools/check_arcade_host.py compiles everything from the constants to this point for the CPU.
+struct SeatSide {
+  SeatGame own;
+  int seat;
+};
+
+__device__ __forceinline__ void load(const int* cfg, const int* rec, int seat, DuelRules& r, SeatSide& s) {
+  r = load_seat_rules(cfg); s.own = load_seat_game(rec); s.seat = seat;
+}
+
+__device__ __forceinline__ const DuelGame& shown(const SeatSide& s) { return s.own.g; }
+
+// `actor` is the pair's seat 0; -> the seat's reward, and the other seat's in `other_reward`
+__device__ __forceinline__ int step_ticks(SeatSide& s, const DuelRules& r, int a, int other, int actor, int ep, int& other_reward) {
+  SeatGame canon = s.seat ? mirror(s.own) : s.own;
+  const SeatRewards rw = step_ticks2(canon, r, s.seat ? other : a, s.seat ? a : other, actor, ep);
+  s.own = s.seat ? mirror(canon) : canon;
+  other_reward = s.seat ? rw.r0 : rw.r1;
+  return s.seat ? rw.r1 : rw.r0;
+}
+
+__device__ __forceinline__ SeatSide reset_episode(const DuelRules& r, const SeatSide& old, int, int) {
+  SeatGame canon = old.seat ? mirror(old.own) : old.own;
+  canon.g = reset_game(r, canon.g);
+  return {old.seat ? mirror(canon) : canon, old.seat};
+}
+
+__device__ __forceinline__ void store_game(int* rec, const SeatSide& s) { store_seat_game(rec, s.own); }
+
+template <class G, class R>
+__device__ __forceinline__ void store_frame(uint8_t* dst, const G& g, const R& r) {
+  uint4* d4 = reinterpret_cast<uint4*>(dst);
+  for (int c = threadIdx.x; c < kChunks; c += 256) d4[c] = frame_chunk(g, r, c);
+}
+
+// ---- views, the launch half: where a workgroup finds what the pure half is given ----------------------------------------
+// One workgroup per actor.  Self-play (§7v): a launch of B actors holds B / 2 games, global actors 2 i and 2 i + 1 are seat 0
+// and seat 1 of game i, and both workgroups of a pair step the same game from their own copy of it with both actions and
+// keep their own view, reward, frame and ring words.  Versus (§7w): game b is game actor_base + b of a self-play
+// environment, the actor is its seat 0, and seat 1 is an input: its action is opp_actions[b], and of its side only the
+// frame it would see, its last action and its last reward are kept.  No workgroup reads a word another workgroup of the
+// launch writes: of a partner it reads actions, the read-only active / mask flags and the policy's input rows.
+template <class G, class R>
+struct PlainView {
+  using Game = G;
+  using Rules = R;
+  static constexpr int kPolicyWaves = 1;
+};
+
+struct SeatView {
+  using Game = SeatSide;
+  using Rules = DuelRules;
+  static constexpr int kPolicyWaves = 2;    // wave 1 draws the partner's action: the same instructions on the same inputs
+};                                          // as the partner's workgroup runs
+
+struct VersusView {
+  using Game = SeatSide;
+  using Rules = DuelRules;
+  static constexpr int kPolicyWaves = 1;
+  const int* opp_actions;   // [B] seat 1's action of this step
+  uint8_t* opp_frames;      // [B] frames, 16-byte aligned: seat 1's current observation
+  int* opp_last_action;     // [B]
+  float* opp_last_reward;   // [B]
+};
+
+template <class View>
+__device__ __forceinline__ int view_seat(const View&, const ArcadeArgs&, int) { return 0; }
+__device__ __forceinline__ int view_seat(const SeatView&, const ArcadeArgs& p, int b) { return (p.actor_base + b) & 1; }
+
+// the key of the draws: the global actor; of a pair, its seat 0; of a versus game, seat 0 of that self-play game
+template <class G, class R>
+__device__ __forceinline__ int draw_key(const PlainView<G, R>&, const ArcadeArgs& p, int b) { return p.actor_base + b; }
+__device__ __forceinline__ int draw_key(const SeatView&, const ArcadeArgs& p, int b) { return (p.actor_base + b) & ~1; }
+__device__ __forceinline__ int draw_key(const VersusView&, const ArcadeArgs& p, int b) { return 2 * (p.actor_base + b); }
+
+// a plain step's `active` and a reset's `mask` (non-null): a pair moves when both seats are active (a rollout form reads
+// its own flag: the pair's are equal) and is reset when either seat's mask is set
+template <class View>
+__device__ __forceinline__ int view_active(const View&, const ArcadeArgs& p, int b) { return p.active[b]; }
+__device__ __forceinline__ int view_active(const SeatView&, const ArcadeArgs& p, int b) { return p.active[b] && p.active[b ^ 1]; }
+template <class View>
+__device__ __forceinline__ int view_masked(const View&, const ArcadeArgs& p, int b) { return p.mask[b]; }
+__device__ __forceinline__ int view_masked(const SeatView&, const ArcadeArgs& p, int b) { return p.mask[b] || p.mask[b ^ 1]; }
+
+// the other paddle's action (B and actor_base of a self-play launch are even: the partner is in the launch)
+template <class View>
+__device__ __forceinline__ int other_action(const View&, const ArcadeArgs&, int, const int*) { return 0; }
+__device__ __forceinline__ int other_action(const SeatView&, const ArcadeArgs& p, int b, const int* s_act) {
+  return p.pol_x ? s_act[1] : p.actions[b ^ 1];
+}
+__device__ __forceinline__ int other_action(const VersusView& view, const ArcadeArgs&, int b, const int*) {
+  return view.opp_actions[b];
+}
+
+// After the actor's own stores.  Versus: what seat 1 keeps (zeroed with the learner's where the step resets), then the
+// frame seat 1 sees now, after the learner's, so that the two renders' values are not live together.
+template <class View, class G, class R>
+__device__ __forceinline__ void view_epilogue(const View&, int, const G&, const R&, int, float) {}
+__device__ __forceinline__ void view_epilogue(const VersusView& view, int b, const SeatSide& g, const DuelRules& rules, int other,
+                                              float other_reward) {
+  if (threadIdx.x == 0) {
+    view.opp_last_action[b] = other;
+    view.opp_last_reward[b] = other_reward;
+  }
+  const SeatGame opp = mirror(g.own);
+  store_frame(view.opp_frames + (size_t)b * FRAME_BYTES, opp.g, rules);
+}
+
+// One agent step of actor blockIdx.x through `view`.  `diff` (|s_{t+1} - s_t|, byte-wise), `s_act` (the drawn action, and
+// the partner's where two waves draw) and `s_pol` ([5], the partner's pi and v, which nobody reads) are the kernel's LDS.
+// TL (the _tl entries, DESIGN §7o): an episode that ends in this step only because of the step limit keeps its final
+// observation in final_obs[b] and is flagged 2 instead of 1.  The step kernels sit on a register tier's edge (§7n): what
+// differs between the views is resolved at compile time, the game's functions are called from here and not through
+// another layer (one more moved the plain kernels over the edge), and profiles/arcade_one_body.md keeps the counts.
+template <class View, bool TL>
+__device__ __forceinline__ void step_view(const View& view, const ArcadeArgs& p, uint4* diff, int* s_act, float* s_pol) {
+  constexpr bool kTwoWaves = View::kPolicyWaves > 1;
+  const int b = blockIdx.x;
   const int H1 = p.H1;
-  if (p.pol_x && threadIdx.x < 128) {           // the policy of this seat on wave 0, of its partner on wave 1: the same
-    const int w = threadIdx.x >> 6;             // instructions on the same inputs as the partner's workgroup runs
-    const int row = w ? pb : b;
+  if (p.pol_x && threadIdx.x < 64 * View::kPolicyWaves) {   // the policy of this actor on wave 0 (for idle actors too, as
+    const int w = kTwoWaves ? threadIdx.x >> 6 : 0;         // unreal_policy_step)
+    const int lane = kTwoWaves ? threadIdx.x & 63 : threadIdx.x;
+    const int row = w ? b ^ 1 : b;
     const int act = policy_row<4>(p.pol_x + (size_t)row * p.pol_ldx, p.Wp, p.bp, p.Wv, p.bv, p.pol_u + row,
-                                  w ? s_pol : p.pi_out + (size_t)b * 4, w ? s_pol + 4 : p.v_out + b, threadIdx.x & 63);
-    if ((threadIdx.x & 63) == 0) {
+                                  w ? s_pol : p.pi_out + (size_t)b * 4, w ? s_pol + 4 : p.v_out + b, lane);
+    if (lane == 0) {
       s_act[w] = act;
       if (w == 0) p.act_out[b] = act;
     }
   }
   const int cnt = p.count[b];
   const int slot = cnt % H1;
-  // a plain step moves a pair only when both seats are active; a rollout form reads its own flag (the pair's are equal)
-  const int act_flag = p.active_rw ? p.active_rw[b] : (p.active ? (p.active[b] && p.active[pb]) : 1);
+  const int act_flag = p.active_rw ? p.active_rw[b] : (p.active ? view_active(view, p, b) : 1);
   const int la = p.last_action[b];
   const float lr = p.last_reward[b];
-  if (!act_flag) {
+  if (!act_flag) {                              // (uniform) idle: nothing but the next step's rows is written
     if (threadIdx.x == 0) rollout_idle(p, b, slot, la, lr);
     return;
   }
   int* rec = p.records + (size_t)kArcadeRecord * b;
-  const DuelRules rules = load_seat_rules(p.cfg);
-  const SeatGame own_old = load_seat_game(rec);                     // the stored frame's state
+  typename View::Rules rules;
+  typename View::Game old;                      // the stored frame's state
+  load(p.cfg, rec, view_seat(view, p, b), rules, old);
   const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
   const int steps = p.ep_steps[b] + 1;
   const int epi = p.episode[b];
@@ -1631,36 +1277,37 @@ __device__ __forceinline__ void step_seat(const ArcadeArgs& p, uint4* diff, int*
   const float ep = p.track_score ? p.episode_reward[b] : 0.f;
   __syncthreads();                              // the drawn actions are in LDS; every thread has read the record
   const int a = p.pol_x ? s_act[0] : p.actions[b];
-  const int ap = p.pol_x ? s_act[1] : p.actions[pb];
+  const int other = other_action(view, p, b, s_act);
 
-  SeatGame canon = seat ? mirror(own_old) : own_old;
-  const SeatRewards rw = step_ticks2(canon, rules, seat ? ap : a, seat ? a : ap, (p.actor_base + b) & ~1, epi);
-  const float reward = (float)(seat ? rw.r1 : rw.r0);
-  const bool terminal = game_over(canon.g, rules, steps);
-  SeatGame own = seat ? mirror(canon) : canon;
-  const DuelGame& old = own_old.g;
-  const DuelGame& g = own.g;
+  // only the state after the agent step's last tick is drawn, so everything below sees two states, as with one tick
+  typename View::Game g = old;
+  int other_reward = 0;
+  const float reward = (float)step_ticks(g, rules, a, other, draw_key(view, p, b), epi, other_reward);
+  const bool terminal = game_over(shown(g), rules, steps);
   const RingStep ring = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
   uint8_t* dst = p.frames + ((size_t)b * H1 + ring.nslot) * FRAME_BYTES;
-  const bool cut = TL && ring.reset && !game_ended(g, rules);      // (uniform) ended by the step limit alone
+  const bool cut = TL && ring.reset && !game_ended(shown(g), rules);      // (uniform) ended by the step limit alone
   uint8_t* fin = TL ? p.final_obs + (size_t)b * FRAME_BYTES : nullptr;
 
-  const auto dirty = frame_dirty(old, g, rules);
+  // s_{t+1} and, in the rows where it can differ, s_t, 16 bytes per lane: the new chunk is stored unless the episode
+  // restarts, the difference goes to LDS
+  const auto dirty = frame_dirty(shown(old), shown(g), rules);
 #pragma unroll 1
   for (int k = 0; k < kChunksPerThread; ++k) {
     const int c = threadIdx.x + 256 * k;
     if (c < kChunks) {
-      const uint4 v = frame_chunk(g, rules, c);
+      const uint4 v = frame_chunk(shown(g), rules, c);
       if (!ring.reset) reinterpret_cast<uint4*>(dst)[c] = v;
       if constexpr (TL) {
         if (cut) reinterpret_cast<uint4*>(fin)[c] = v;
       }
-      diff[c] = make_uint4(diff_dword(old, rules, dirty, 4 * c, v.x), diff_dword(old, rules, dirty, 4 * c + 1, v.y),
-                           diff_dword(old, rules, dirty, 4 * c + 2, v.z), diff_dword(old, rules, dirty, 4 * c + 3, v.w));
+      diff[c] = make_uint4(diff_dword(shown(old), rules, dirty, 4 * c, v.x), diff_dword(shown(old), rules, dirty, 4 * c + 1, v.y),
+                           diff_dword(shown(old), rules, dirty, 4 * c + 2, v.z), diff_dword(shown(old), rules, dirty, 4 * c + 3, v.w));
     }
   }
   __syncthreads();
-  {                                             // pixel change, as in step_actor
+  // pixel change: cell (i, j) sums rows 4i+2..4i+5, bytes 12j+6..12j+17 of the difference (the [2:-2] crop, 4 x 4 blocks)
+  {
     const uint32_t* d32 = reinterpret_cast<const uint32_t*>(diff);
     for (int c = threadIdx.x; c < PC_CELLS; c += 256) {
       const int i = c / 20, j = c - 20 * i;
@@ -1673,14 +1320,13 @@ __device__ __forceinline__ void step_seat(const ArcadeArgs& p, uint4* diff, int*
       p.r_pc[ring.base * PC_CELLS + c] = (float)sum / kPcDenom;
     }
   }
-  if (ring.reset) {                             // (uniform) the next match's first observation goes into the slot instead
-    canon.g = reset_game(rules, canon.g);
-    own = seat ? mirror(canon) : canon;
-    store_frame(dst, own.g, rules);
+  if (ring.reset) {                             // (uniform) the next episode's first observation goes into the slot instead
+    g = reset_episode(rules, g, draw_key(view, p, b), epi + 1);
+    store_frame(dst, shown(g), rules);
   }
   if (threadIdx.x == 0) {
     ring_commit(p, b, ring, a, reward, reward, la, lr, ep);
-    store_seat_game(rec, own);
+    store_game(rec, g);
     p.ep_steps[b] = ring.reset ? 0 : steps;
     p.episode[b] = epi + (ring.reset ? 1 : 0);
     rollout_commit(p, b, ring, ns, a, reward);
@@ -1692,64 +1338,524 @@ __device__ __forceinline__ void step_seat(const ArcadeArgs& p, uint4* diff, int*
       }
     }
   }
+  view_epilogue(view, b, g, rules, ring.reset ? 0 : other, ring.reset ? 0.f : (float)other_reward);
 }
 
+// The first state of the next episode of actor blockIdx.x through `view`, into the slot its next step reads.
+template <class View>
+__device__ __forceinline__ void reset_view(const View& view, const ArcadeArgs& p) {
+  const int b = blockIdx.x;
+  if (p.mask && !view_masked(view, p, b)) return;
+  int* rec = p.records + (size_t)kArcadeRecord * b;
+  typename View::Rules rules;
+  typename View::Game old;
+  load(p.cfg, rec, view_seat(view, p, b), rules, old);
+  const int epi = p.episode[b];
+  __syncthreads();                              // every thread has read the record
+  const typename View::Game g = reset_episode(rules, old, draw_key(view, p, b), epi + 1);
+  store_frame(p.frames + ((size_t)b * p.H1 + p.count[b] % p.H1) * FRAME_BYTES, shown(g), rules);
+  if (threadIdx.x == 0) {
+    store_game(rec, g);
+    p.ep_steps[b] = 0;
+    p.episode[b] = epi + 1;
+    p.last_action[b] = 0;
+    p.last_reward[b] = 0.f;
+  }
+  view_epilogue(view, b, g, rules, 0, 0.f);
+}
+
+// ---- the plain games: the kernels read the game id from the block (uniform) and run that game's instance of the body ----
+template <class G, class R, bool TL = false>
+__device__ __forceinline__ void step_actor(const ArcadeArgs& p, uint4* diff, int* s_act) {
+  step_view<PlainView<G, R>, TL>({}, p, diff, s_act, nullptr);
+}
+
+template <class G, class R>
+__device__ __forceinline__ void reset_actor(const ArcadeArgs& p) { reset_view(PlainView<G, R>{}, p); }
+
+__global__ __launch_bounds__(256) void arcade_step_kernel(ArcadeArgs p) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act;
+  const int game = p.cfg[0];                    // (uniform) a block of another game: nothing is written
+  if (game == kArcadeBreakout) step_actor<Game, Rules>(p, diff, &s_act);
+  else if (game == kArcadeDuel) step_actor<DuelGame, DuelRules>(p, diff, &s_act);
+  else if (game == kArcadeInvaders) step_actor<InvGame, InvRules>(p, diff, &s_act);
+  else if (game == kArcadeCrossing) step_actor<CrossGame, CrossRules>(p, diff, &s_act);
+}
+
+// the rollout step of the _tl entries
+__global__ __launch_bounds__(256) void arcade_step_tl_kernel(ArcadeArgs p) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act;
+  const int game = p.cfg[0];                    // (uniform) as above
+  if (game == kArcadeBreakout) step_actor<Game, Rules, true>(p, diff, &s_act);
+  else if (game == kArcadeDuel) step_actor<DuelGame, DuelRules, true>(p, diff, &s_act);
+  else if (game == kArcadeInvaders) step_actor<InvGame, InvRules, true>(p, diff, &s_act);
+  else if (game == kArcadeCrossing) step_actor<CrossGame, CrossRules, true>(p, diff, &s_act);
+}
+
+__global__ __launch_bounds__(256) void arcade_reset_kernel(ArcadeArgs p) {
+  const int game = p.cfg[0];                    // (uniform) as in the step
+  if (game == kArcadeBreakout) reset_actor<Game, Rules>(p);
+  else if (game == kArcadeDuel) reset_actor<DuelGame, DuelRules>(p);
+  else if (game == kArcadeInvaders) reset_actor<InvGame, InvRules>(p);
+  else if (game == kArcadeCrossing) reset_actor<CrossGame, CrossRules>(p);
+}
+
+// ---- game mixtures (DESIGN §7u): one config block per actor ------------------------------------------------------------
+// Global actor g plays block g % n_blocks of `n_blocks` consecutive blocks.  The kernels below are the three above with
+// the block chosen per workgroup (one actor per workgroup: the game branch stays uniform), on a copy of the arguments
+// whose cfg points at the actor's block.
+constexpr int kArcadeCfgWords = 24, kMaxMixBlocks = 16;
+
+struct ArcadeMixArgs {
+  ArcadeArgs a;
+  int n_blocks;          // 1..16
+  float* done_return;    // [B] (nullable, with done_episodes): the sum of the scores of the actor's finished episodes
+  int* done_episodes;    // [B] their number
+};
+
+__device__ __forceinline__ ArcadeArgs mix_actor_args(const ArcadeMixArgs& m) {
+  ArcadeArgs p = m.a;
+  p.cfg += kArcadeCfgWords * ((p.actor_base + (int)blockIdx.x) % m.n_blocks);
+  return p;
+}
+
+// step_actor, then the per-task statistics where the step ended an episode: the score is the value ring_commit has just
+// written to score_out[b] (thread 0's own stores, read back by thread 0).  Per-actor sums: no atomics.
+// Whether it did is read from what the step left.  A rollout form (active_rw; the _tl kernel serves only those) always
+// restarts a finished episode, so active_log_t[b] = 1 (the actor stepped) and ep_steps[b] = 0 say so, and nothing has to
+// be kept over the step, whose body sits on a register tier's edge.  The plain step may run without a restart: there the
+// slot an active actor commits is taken before the step, and that slot's terminal flag is read after it.
+template <class G, class R, bool TL>
+__device__ __forceinline__ void mix_step_actor(const ArcadeMixArgs& m, const ArcadeArgs& p, uint4* diff, int* s_act) {
+  const int b = blockIdx.x;
+  int slot = -1;                                // the slot of an active actor's plain step (-1: no statistics, or idle)
+  if constexpr (!TL) {
+    if (m.done_return && p.track_score && !p.active_rw && (p.active ? p.active[b] : 1)) slot = p.count[b] % p.H1;
+  }
+  step_actor<G, R, TL>(p, diff, s_act);
+  if constexpr (TL) {                           // (a rollout form: it tracks the score and has active_rw)
+    if (m.done_return && threadIdx.x == 0 && p.active_log_t[b] && p.ep_steps[b] == 0) {
+      m.done_return[b] += p.score_out[b];
+      m.done_episodes[b] += 1;
+    }
+  } else if (m.done_return && p.track_score && threadIdx.x == 0) {
+    const bool ended = p.active_rw ? p.active_log_t[b] && p.ep_steps[b] == 0
+                                   : slot >= 0 && p.r_terminal[(size_t)b * p.H1 + slot] != 0;
+    if (ended) {
+      m.done_return[b] += p.score_out[b];
+      m.done_episodes[b] += 1;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void arcade_mix_step_kernel(ArcadeMixArgs m) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act;
+  const ArcadeArgs p = mix_actor_args(m);
+  const int game = p.cfg[0];                    // (uniform per workgroup) a block of another game: this actor writes nothing
+  if (game == kArcadeBreakout) mix_step_actor<Game, Rules, false>(m, p, diff, &s_act);
+  else if (game == kArcadeDuel) mix_step_actor<DuelGame, DuelRules, false>(m, p, diff, &s_act);
+  else if (game == kArcadeInvaders) mix_step_actor<InvGame, InvRules, false>(m, p, diff, &s_act);
+  else if (game == kArcadeCrossing) mix_step_actor<CrossGame, CrossRules, false>(m, p, diff, &s_act);
+}
+
+__global__ __launch_bounds__(256) void arcade_mix_step_tl_kernel(ArcadeMixArgs m) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act;
+  ArcadeArgs p = mix_actor_args(m);
+  // the _tl entries are rollout forms: what every one of them passes is known here, and need not be kept
+  p.active = nullptr; p.reset_on_terminal = 1; p.track_score = 1;
+  const int game = p.cfg[0];                    // (uniform per workgroup) as above
+  if (game == kArcadeBreakout) mix_step_actor<Game, Rules, true>(m, p, diff, &s_act);
+  else if (game == kArcadeDuel) mix_step_actor<DuelGame, DuelRules, true>(m, p, diff, &s_act);
+  else if (game == kArcadeInvaders) mix_step_actor<InvGame, InvRules, true>(m, p, diff, &s_act);
+  else if (game == kArcadeCrossing) mix_step_actor<CrossGame, CrossRules, true>(m, p, diff, &s_act);
+}
+
+__global__ __launch_bounds__(256) void arcade_mix_reset_kernel(ArcadeMixArgs m) {
+  const ArcadeArgs p = mix_actor_args(m);
+  const int game = p.cfg[0];                    // (uniform per workgroup) as in the step
+  if (game == kArcadeBreakout) reset_actor<Game, Rules>(p);
+  else if (game == kArcadeDuel) reset_actor<DuelGame, DuelRules>(p);
+  else if (game == kArcadeInvaders) reset_actor<InvGame, InvRules>(p);
+  else if (game == kArcadeCrossing) reset_actor<CrossGame, CrossRules>(p);
+}
+
+// ---- self-play and versus (§7w): the duel's block alone; another game's block: nothing is written ------------
 __global__ __launch_bounds__(256) void arcade_selfplay_step_kernel(ArcadeArgs p) {
   __shared__ uint4 diff[kChunks];
   __shared__ int s_act[2];
   __shared__ float s_pol[5];
-  if (p.cfg[0] == kArcadeDuel) step_seat<false>(p, diff, s_act, s_pol);   // (uniform) another game's block: nothing is written
+  if (p.cfg[0] == kArcadeDuel) step_view<SeatView, false>({}, p, diff, s_act, s_pol);   // (uniform)
 }
 
 __global__ __launch_bounds__(256) void arcade_selfplay_step_tl_kernel(ArcadeArgs p) {
   __shared__ uint4 diff[kChunks];
   __shared__ int s_act[2];
   __shared__ float s_pol[5];
-  if (p.cfg[0] == kArcadeDuel) step_seat<true>(p, diff, s_act, s_pol);
+  if (p.cfg[0] == kArcadeDuel) step_view<SeatView, true>({}, p, diff, s_act, s_pol);
 }
 
-// a pair is reset when either seat's mask is set: reset_game on the canonical record, then the seat's view
 __global__ __launch_bounds__(256) void arcade_selfplay_reset_kernel(ArcadeArgs p) {
-  if (p.cfg[0] != kArcadeDuel) return;          // (uniform) as in the step
-  const int b = blockIdx.x;
-  if (p.mask && !p.mask[b] && !p.mask[b ^ 1]) return;
-  const int seat = (p.actor_base + b) & 1;
-  int* rec = p.records + (size_t)kArcadeRecord * b;
-  const DuelRules rules = load_seat_rules(p.cfg);
-  const SeatGame stored = load_seat_game(rec);
-  const int epi = p.episode[b];
-  __syncthreads();                              // every thread has read the record
-  SeatGame canon = seat ? mirror(stored) : stored;
-  canon.g = reset_game(rules, canon.g);
-  const SeatGame own = seat ? mirror(canon) : canon;
-  store_frame(p.frames + ((size_t)b * p.H1 + p.count[b] % p.H1) * FRAME_BYTES, own.g, rules);
-  if (threadIdx.x == 0) {
-    store_seat_game(rec, own);
-    p.ep_steps[b] = 0;
-    p.episode[b] = epi + 1;
-    p.last_action[b] = 0;
-    p.last_reward[b] = 0.f;
-  }
+  if (p.cfg[0] == kArcadeDuel) reset_view(SeatView{}, p);
 }
 
-// the self-play launcher: arcade_launch's tail and checks, and whole pairs only (even B, even actor_base)
-int arcade_selfplay_launch(ArcadeEntry e, ArcadeArgs& p, const int* cfg, int actor_base, int* ep_steps, int* episode,
-                           int* records, void* stream, bool tl = false, uint8_t* final_obs = nullptr) {
+struct ArcadeVersusArgs {
+  ArcadeArgs a;
+  VersusView opp;
+};
+
+__global__ __launch_bounds__(256) void arcade_versus_step_kernel(ArcadeVersusArgs m) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act;
+  if (m.a.cfg[0] == kArcadeDuel) step_view<VersusView, false>(m.opp, m.a, diff, &s_act, nullptr);
+}
+
+__global__ __launch_bounds__(256) void arcade_versus_step_tl_kernel(ArcadeVersusArgs m) {
+  __shared__ uint4 diff[kChunks];
+  __shared__ int s_act;
+  if (m.a.cfg[0] == kArcadeDuel) step_view<VersusView, true>(m.opp, m.a, diff, &s_act, nullptr);
+}
+
+__global__ __launch_bounds__(256) void arcade_versus_reset_kernel(ArcadeVersusArgs m) {
+  if (m.a.cfg[0] == kArcadeDuel) reset_view(m.opp, m.a);
+}
+
+// ---- host side: one check, four argument builders and one launcher for the 24 entries ----------------------------------
+enum ArcadeEntry { kReset, kStep, kRollout, kPolicy };
+enum ArcadeFamily { kPlain, kMix, kSelfplay, kVersus };
+
+// Every pointer the kernels of the entry write through or read is non-null, frames are 16-byte aligned (16 B per lane),
+// and the game has four actions.  (The block lives in device memory: its words are checked by the kernels.)
+bool arcade_args_ok(ArcadeEntry e, const ArcadeArgs& p) {
+  if (p.B <= 0 || p.H1 < 2 || !p.last_action || !p.last_reward || !p.count || !p.frames) return false;
+  if ((uintptr_t)p.frames & 15) return false;
+  if (!p.cfg || ((uintptr_t)p.cfg & 3) || p.actor_base < 0 || !p.ep_steps || !p.episode || !p.records) return false;
+  if (e == kReset) return true;
+  if (!p.r_reward || !p.r_action || !p.r_terminal || !p.r_last_action || !p.r_last_reward || !p.r_pc) return false;
+  if (p.track_score && (!p.episode_reward || !p.score_out || !p.score_valid)) return false;
+  if (e != kPolicy && !p.actions) return false;
+  if (e == kStep) return true;
+  if (!p.active_rw || !p.active_log_t || !p.n_steps || !p.terminal_end || p.idx_base < 0) return false;
+  if (p.A != 4) return false;                   // the games' minimal action set
+  if (p.next_lar && (p.lar_col0 < 0 || p.lar_ld < p.lar_col0 + p.A + 1)) return false;
+  if (e == kRollout) return true;
+  return p.pol_x && p.pol_ldx >= LSTM_N && p.Wp && p.bp && p.Wv && p.bv && p.pol_u && p.pi_out && p.v_out && p.act_out;
+}
+
+// what a family's entries pass beyond the plain ones' arguments (zeros where it has none)
+struct ArcadeExtra {
+  VersusView opp;        // kVersus
+  int n_blocks;          // kMix, with the two below
+  float* done_return;
+  int* done_episodes;
+};
+
+ArcadeExtra mix_extra(int n_blocks, float* done_return, int* done_episodes) {
+  ArcadeExtra x{};
+  x.n_blocks = n_blocks; x.done_return = done_return; x.done_episodes = done_episodes;
+  return x;
+}
+
+ArcadeExtra versus_extra(const int* opp_actions, uint8_t* opp_frames, int* opp_last_action, float* opp_last_reward) {
+  ArcadeExtra x{};
+  x.opp.opp_actions = opp_actions; x.opp.opp_frames = opp_frames;
+  x.opp.opp_last_action = opp_last_action; x.opp.opp_last_reward = opp_last_reward;
+  return x;
+}
+
+// n_blocks in 1..16 and both statistics arrays or neither
+bool mix_ok(const ArcadeExtra& x) {
+  return x.n_blocks >= 1 && x.n_blocks <= kMaxMixBlocks && !x.done_return == !x.done_episodes;
+}
+
+// whole pairs only
+bool selfplay_ok(const ArcadeArgs& p) { return !(p.B & 1) && !(p.actor_base & 1); }
+
+// the opponent's four arrays (any B, any actor_base for which 2 (actor_base + b) is an int)
+bool versus_ok(ArcadeEntry e, const ArcadeArgs& p, const VersusView& o) {
+  if (!o.opp_frames || ((uintptr_t)o.opp_frames & 15) || !o.opp_last_action || !o.opp_last_reward) return false;
+  if (e != kReset && !o.opp_actions) return false;
+  return (long long)p.actor_base + p.B <= (1ll << 30);
+}
+
+// a family's reset, step and _tl step kernel on its argument (one launch shape: no label is recorded)
+template <class K>
+void launch_one(ArcadeEntry e, bool tl, void (*reset)(K), void (*step)(K), void (*step_tl)(K), const K& k, int B, void* stream) {
+  void (*const kernel)(K) = e == kReset ? reset : tl ? step_tl : step;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, k);
+}
+
+// The one launcher: fills in the tail, checks, and launches the family's kernel.
+// `final_obs` (the _tl entries, which are rollout entries): [B] frames, 16-byte aligned; selects the kernel that keeps them
+int arcade_launch(ArcadeFamily f, ArcadeEntry e, ArcadeArgs p, const int* cfg, int actor_base, int* ep_steps, int* episode,
+                  int* records, const ArcadeExtra& x, void* stream, bool tl = false, uint8_t* final_obs = nullptr) {
   p.cfg = cfg; p.actor_base = actor_base; p.ep_steps = ep_steps; p.episode = episode; p.records = records;
   if (tl) p.final_obs = final_obs;
   if (!arcade_args_ok(e, p)) return UNREAL_EINVAL;
   if (tl && (!final_obs || ((uintptr_t)final_obs & 15) || (e != kRollout && e != kPolicy))) return UNREAL_EINVAL;
-  if ((p.B & 1) || (actor_base & 1)) return UNREAL_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  if (e == kReset) hipLaunchKernelGGL(arcade_selfplay_reset_kernel, dim3(p.B), dim3(256), 0, s, p);
-  else if (tl) hipLaunchKernelGGL(arcade_selfplay_step_tl_kernel, dim3(p.B), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(arcade_selfplay_step_kernel, dim3(p.B), dim3(256), 0, s, p);
+  if (f == kMix && !mix_ok(x)) return UNREAL_EINVAL;
+  if (f == kSelfplay && !selfplay_ok(p)) return UNREAL_EINVAL;
+  if (f == kVersus && !versus_ok(e, p, x.opp)) return UNREAL_EINVAL;
+  if (f == kPlain) {
+    launch_one(e, tl, arcade_reset_kernel, arcade_step_kernel, arcade_step_tl_kernel, p, p.B, stream);
+  } else if (f == kMix) {
+    launch_one(e, tl, arcade_mix_reset_kernel, arcade_mix_step_kernel, arcade_mix_step_tl_kernel,
+               ArcadeMixArgs{p, x.n_blocks, x.done_return, x.done_episodes}, p.B, stream);
+  } else if (f == kSelfplay) {
+    launch_one(e, tl, arcade_selfplay_reset_kernel, arcade_selfplay_step_kernel, arcade_selfplay_step_tl_kernel, p, p.B, stream);
+  } else {
+    launch_one(e, tl, arcade_versus_reset_kernel, arcade_versus_step_kernel, arcade_versus_step_tl_kernel,
+               ArcadeVersusArgs{p, x.opp}, p.B, stream);
+  }
   return unreal_launch_status();
+}
+
+// The four argument groups of the entries -> the kernels' arguments without the tail.
+ArcadeArgs reset_args(int B, int H1, const int* mask, int* last_action, float* last_reward, const int* count,
+                      uint8_t* frames) {
+  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, const_cast<int*>(count), frames};
+  p.mask = mask;
+  return p;
+}
+
+ArcadeArgs step_args(int B, int H1, const int* actions, const int* active, int* last_action, float* last_reward, int* count,
+                     uint8_t* frames, float* r_reward, int* r_action, int* r_terminal, int* r_last_action,
+                     float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                     float* score_out, int* score_valid, int reset_on_terminal, int track_score) {
+  return {B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+          r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid,
+          reset_on_terminal, track_score};
+}
+
+// a rollout form always restarts a finished episode and tracks the score; its `active` is read and written
+ArcadeArgs rollout_args(int B, int H1, const int* actions, int* last_action, float* last_reward, int* count, uint8_t* frames,
+                        float* r_reward, int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+                        float* r_pc, float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
+                        int* score_valid, int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                        float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor) {
+  return {B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+          r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+          active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
+}
+
+// the rollout form that draws its actions: no `actions`, the policy's arguments in front
+ArcadeArgs policy_args(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp, const float* Wv,
+                       const float* bv, const double* u, float* pi_out, float* v_out, int* actions_out, int* last_action,
+                       float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                       int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                       float* episode_reward, float* score_out, int* score_valid, int* active, int* active_log_t,
+                       int* n_steps, int* terminal_end, int* next_idx, float* next_lar, int lar_ld, int lar_col0, int A,
+                       int idx_base_actor) {
+  return {B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+          r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
+          active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
+          Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
 }
 
 }  // namespace
 
 extern "C" {
+
+// Every entry: its argument list (the ABI), one builder and the launcher.  `pos` is the maze's argument of that name: the
+// arcade keeps its state in `records` and never touches it (nullable).
+
+int unreal_arcade_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward, const int* count,
+                        uint8_t* frames, const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
+                        void* stream) {
+  (void)pos;
+  return arcade_launch(kPlain, kReset, reset_args(B, H1, mask, last_action, last_reward, count, frames), cfg, actor_base,
+                       ep_steps, episode, records, {}, stream);
+}
+
+int unreal_arcade_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
+                       float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                       int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                       float* episode_reward, float* score_out, int* score_valid, int reset_on_terminal, int track_score,
+                       const int* cfg, int actor_base, int* ep_steps, int* episode, int* records, void* stream) {
+  (void)pos;
+  return arcade_launch(kPlain, kStep,
+                       step_args(B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action,
+                                 r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward,
+                                 score_out, score_valid, reset_on_terminal, track_score),
+                       cfg, actor_base, ep_steps, episode, records, {}, stream);
+}
+
+int unreal_arcade_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                               int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                               int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                               int* out_terminal, float* episode_reward, float* score_out, int* score_valid, int* active,
+                               int* active_log_t, int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
+                               int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg, int actor_base,
+                               int* ep_steps, int* episode, int* records, void* stream) {
+  (void)pos;
+  return arcade_launch(kPlain, kRollout,
+                       rollout_args(B, H1, actions, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+                                    r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out,
+                                    score_valid, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
+                                    lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records, {}, stream);
+}
+
+int unreal_arcade_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                      const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                      int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
+                                      uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                      int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                      int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                      int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                      float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                      int actor_base, int* ep_steps, int* episode, int* records, void* stream) {
+  (void)pos;
+  return arcade_launch(kPlain, kPolicy,
+                       policy_args(B, H1, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions_out, last_action, last_reward,
+                                   count, frames, r_reward, r_action, r_terminal, r_last_action, r_last_reward, r_pc,
+                                   out_reward, out_terminal, episode_reward, score_out, score_valid, active, active_log_t,
+                                   n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records, {}, stream);
+}
+
+// The two rollout entries with time-limit bootstrapping (DESIGN §7o): `final_obs` [B] frames.
+
+int unreal_arcade_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                  int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                  int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                  int* out_terminal, float* episode_reward, float* score_out, int* score_valid, int* active,
+                                  int* active_log_t, int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
+                                  int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg, int actor_base,
+                                  int* ep_steps, int* episode, int* records, uint8_t* final_obs, void* stream) {
+  (void)pos;
+  return arcade_launch(kPlain, kRollout,
+                       rollout_args(B, H1, actions, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+                                    r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out,
+                                    score_valid, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
+                                    lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records, {}, stream, true, final_obs);
+}
+
+int unreal_arcade_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                         const float* Wv, const float* bv, const double* u, float* pi_out, float* v_out,
+                                         int* actions_out, int* pos, int* last_action, float* last_reward, int* count,
+                                         uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                         int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                         int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                         int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                         float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                                         const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
+                                         uint8_t* final_obs, void* stream) {
+  (void)pos;
+  return arcade_launch(kPlain, kPolicy,
+                       policy_args(B, H1, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions_out, last_action, last_reward,
+                                   count, frames, r_reward, r_action, r_terminal, r_last_action, r_last_reward, r_pc,
+                                   out_reward, out_terminal, episode_reward, score_out, score_valid, active, active_log_t,
+                                   n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records, {}, stream, true, final_obs);
+}
+
+// Game mixtures (DESIGN §7u): the six entries above over `n_blocks` consecutive blocks, actor g on block g % n_blocks;
+// done_return / done_episodes [B] (both or neither): the per-actor sums of finished episodes' scores and their number.
+
+int unreal_arcade_mix_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
+                            const int* count, uint8_t* frames, const int* cfg, int n_blocks, int actor_base,
+                            int* ep_steps, int* episode, int* records, void* stream) {
+  (void)pos;
+  return arcade_launch(kMix, kReset, reset_args(B, H1, mask, last_action, last_reward, count, frames), cfg, actor_base,
+                       ep_steps, episode, records, mix_extra(n_blocks, nullptr, nullptr), stream);
+}
+
+int unreal_arcade_mix_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
+                           float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                           int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                           int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                           int reset_on_terminal, int track_score, const int* cfg, int n_blocks, int actor_base,
+                           int* ep_steps, int* episode, int* records, float* done_return, int* done_episodes,
+                           void* stream) {
+  (void)pos;
+  return arcade_launch(kMix, kStep,
+                       step_args(B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action,
+                                 r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward,
+                                 score_out, score_valid, reset_on_terminal, track_score),
+                       cfg, actor_base, ep_steps, episode, records, mix_extra(n_blocks, done_return, done_episodes), stream);
+}
+
+int unreal_arcade_mix_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                   int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                   int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                   int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                   int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                   float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                   int n_blocks, int actor_base, int* ep_steps, int* episode, int* records,
+                                   float* done_return, int* done_episodes, void* stream) {
+  (void)pos;
+  return arcade_launch(kMix, kRollout,
+                       rollout_args(B, H1, actions, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+                                    r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out,
+                                    score_valid, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
+                                    lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records, mix_extra(n_blocks, done_return, done_episodes), stream);
+}
+
+int unreal_arcade_mix_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                          const float* Wv, const float* bv, const double* u, float* pi_out,
+                                          float* v_out, int* actions_out, int* pos, int* last_action,
+                                          float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                          int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+                                          float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                                          float* score_out, int* score_valid, int* active, int* active_log_t,
+                                          int* n_steps, int* terminal_end, int* next_idx, float* next_lar, int lar_ld,
+                                          int lar_col0, int A, int idx_base_actor, const int* cfg, int n_blocks,
+                                          int actor_base, int* ep_steps, int* episode, int* records, float* done_return,
+                                          int* done_episodes, void* stream) {
+  (void)pos;
+  return arcade_launch(kMix, kPolicy,
+                       policy_args(B, H1, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions_out, last_action, last_reward,
+                                   count, frames, r_reward, r_action, r_terminal, r_last_action, r_last_reward, r_pc,
+                                   out_reward, out_terminal, episode_reward, score_out, score_valid, active, active_log_t,
+                                   n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records, mix_extra(n_blocks, done_return, done_episodes), stream);
+}
+
+int unreal_arcade_mix_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
+                                      int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                      int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                      int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                      int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                      float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                                      const int* cfg, int n_blocks, int actor_base, int* ep_steps, int* episode,
+                                      int* records, uint8_t* final_obs, float* done_return, int* done_episodes,
+                                      void* stream) {
+  (void)pos;
+  return arcade_launch(kMix, kRollout,
+                       rollout_args(B, H1, actions, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+                                    r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out,
+                                    score_valid, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
+                                    lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records, mix_extra(n_blocks, done_return, done_episodes), stream, true,
+                       final_obs);
+}
+
+int unreal_arcade_mix_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
+                                             const float* Wv, const float* bv, const double* u, float* pi_out,
+                                             float* v_out, int* actions_out, int* pos, int* last_action,
+                                             float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                             int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+                                             float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                                             float* score_out, int* score_valid, int* active, int* active_log_t,
+                                             int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
+                                             int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                             int n_blocks, int actor_base, int* ep_steps, int* episode, int* records,
+                                             uint8_t* final_obs, float* done_return, int* done_episodes, void* stream) {
+  (void)pos;
+  return arcade_launch(kMix, kPolicy,
+                       policy_args(B, H1, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions_out, last_action, last_reward,
+                                   count, frames, r_reward, r_action, r_terminal, r_last_action, r_last_reward, r_pc,
+                                   out_reward, out_terminal, episode_reward, score_out, score_valid, active, active_log_t,
+                                   n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records, mix_extra(n_blocks, done_return, done_episodes), stream, true,
+                       final_obs);
+}
 
 // Self-play: the six arcade entries with the arguments of the plain ones, over B / 2 games of two seats.
 
@@ -1757,9 +1863,8 @@ int unreal_arcade_selfplay_reset(int B, int H1, const int* mask, int* pos, int* 
                                  const int* count, uint8_t* frames, const int* cfg, int actor_base, int* ep_steps,
                                  int* episode, int* records, void* stream) {
   (void)pos;
-  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, const_cast<int*>(count), frames};
-  p.mask = mask;
-  return arcade_selfplay_launch(kReset, p, cfg, actor_base, ep_steps, episode, records, stream);
+  return arcade_launch(kSelfplay, kReset, reset_args(B, H1, mask, last_action, last_reward, count, frames), cfg, actor_base,
+                       ep_steps, episode, records, {}, stream);
 }
 
 int unreal_arcade_selfplay_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
@@ -1769,10 +1874,11 @@ int unreal_arcade_selfplay_step(int B, int H1, const int* actions, const int* ac
                                 int reset_on_terminal, int track_score, const int* cfg, int actor_base, int* ep_steps,
                                 int* episode, int* records, void* stream) {
   (void)pos;
-  ArcadeArgs p{B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid,
-               reset_on_terminal, track_score};
-  return arcade_selfplay_launch(kStep, p, cfg, actor_base, ep_steps, episode, records, stream);
+  return arcade_launch(kSelfplay, kStep,
+                       step_args(B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action,
+                                 r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward,
+                                 score_out, score_valid, reset_on_terminal, track_score),
+                       cfg, actor_base, ep_steps, episode, records, {}, stream);
 }
 
 int unreal_arcade_selfplay_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
@@ -1784,10 +1890,12 @@ int unreal_arcade_selfplay_rollout_step(int B, int H1, const int* actions, int* 
                                         const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
                                         void* stream) {
   (void)pos;
-  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
-  return arcade_selfplay_launch(kRollout, p, cfg, actor_base, ep_steps, episode, records, stream);
+  return arcade_launch(kSelfplay, kRollout,
+                       rollout_args(B, H1, actions, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+                                    r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out,
+                                    score_valid, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
+                                    lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records, {}, stream);
 }
 
 int unreal_arcade_selfplay_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
@@ -1801,11 +1909,12 @@ int unreal_arcade_selfplay_policy_rollout_step(int B, int H1, const float* X, in
                                                int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
                                                int actor_base, int* ep_steps, int* episode, int* records, void* stream) {
   (void)pos;
-  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
-               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
-  return arcade_selfplay_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, stream);
+  return arcade_launch(kSelfplay, kPolicy,
+                       policy_args(B, H1, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions_out, last_action, last_reward,
+                                   count, frames, r_reward, r_action, r_terminal, r_last_action, r_last_reward, r_pc,
+                                   out_reward, out_terminal, episode_reward, score_out, score_valid, active, active_log_t,
+                                   n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records, {}, stream);
 }
 
 int unreal_arcade_selfplay_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action,
@@ -1817,10 +1926,12 @@ int unreal_arcade_selfplay_rollout_step_tl(int B, int H1, const int* actions, in
                                            int A, int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
                                            int* episode, int* records, uint8_t* final_obs, void* stream) {
   (void)pos;
-  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
-  return arcade_selfplay_launch(kRollout, p, cfg, actor_base, ep_steps, episode, records, stream, true, final_obs);
+  return arcade_launch(kSelfplay, kRollout,
+                       rollout_args(B, H1, actions, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+                                    r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out,
+                                    score_valid, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
+                                    lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records, {}, stream, true, final_obs);
 }
 
 int unreal_arcade_selfplay_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
@@ -1835,294 +1946,124 @@ int unreal_arcade_selfplay_policy_rollout_step_tl(int B, int H1, const float* X,
                                                   const int* cfg, int actor_base, int* ep_steps, int* episode,
                                                   int* records, uint8_t* final_obs, void* stream) {
   (void)pos;
-  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
-               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
-  return arcade_selfplay_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, stream, true, final_obs);
+  return arcade_launch(kSelfplay, kPolicy,
+                       policy_args(B, H1, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions_out, last_action, last_reward,
+                                   count, frames, r_reward, r_action, r_terminal, r_last_action, r_last_reward, r_pc,
+                                   out_reward, out_terminal, episode_reward, score_out, score_valid, active, active_log_t,
+                                   n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records, {}, stream, true, final_obs);
 }
-
-}  // extern "C"
-
-// ---- versus: one learner per game, the other paddle an input ----------------------------------------------
-// A launch of B actors holds B games: game b is game actor_base + b of a self-play environment (§7v), its serve draws
-// keyed by 2 (actor_base + b), seat 0's global index there.  The actor is seat 0 and everything it keeps is what seat 0
-// of the self-play entries keeps.  Seat 1 is no actor: its action is opp_actions[b], and of its side only the frame it
-// would see, its last action and its last reward are kept, in three arrays of their own.  One workgroup per game computes
-// the game once and forms both views, the opponent's after the learner's, so that the two render loops' values are not
-// live together.  No workgroup reads a word another workgroup writes.  Everything above this line is what it was.
-namespace {
-
-struct ArcadeVersusArgs {
-  ArcadeArgs a;
-  const int* opp_actions;   // [B] seat 1's action of this step
-  uint8_t* opp_frames;      // [B] frames, 16-byte aligned: seat 1's current observation
-  int* opp_last_action;     // [B]
-  float* opp_last_reward;   // [B]
-};
-
-// step_seat with seat = 0 and the partner's action from opp_actions, then the opponent's three words
-template <bool TL>
-__device__ __forceinline__ void step_versus(const ArcadeVersusArgs& m, uint4* diff, int* s_act) {
-  const ArcadeArgs& p = m.a;
-  const int b = blockIdx.x;
-  const int H1 = p.H1;
-  if (p.pol_x && threadIdx.x < 64) {            // the learner's policy on wave 0, as step_actor
-    const int act = policy_row<4>(p.pol_x + (size_t)b * p.pol_ldx, p.Wp, p.bp, p.Wv, p.bv, p.pol_u + b,
-                                  p.pi_out + (size_t)b * 4, p.v_out + b, threadIdx.x);
-    if (threadIdx.x == 0) { *s_act = act; p.act_out[b] = act; }
-  }
-  const int cnt = p.count[b];
-  const int slot = cnt % H1;
-  const int act_flag = p.active_rw ? p.active_rw[b] : (p.active ? p.active[b] : 1);
-  const int la = p.last_action[b];
-  const float lr = p.last_reward[b];
-  if (!act_flag) {                              // (uniform) idle: the opponent's words stay, too
-    if (threadIdx.x == 0) rollout_idle(p, b, slot, la, lr);
-    return;
-  }
-  int* rec = p.records + (size_t)kArcadeRecord * b;
-  const DuelRules rules = load_seat_rules(p.cfg);
-  const SeatGame own_old = load_seat_game(rec);                     // the stored frame's state (canonical)
-  const int prev_term = cnt > 0 ? p.r_terminal[(size_t)b * H1 + (cnt - 1) % H1] : 0;
-  const int steps = p.ep_steps[b] + 1;
-  const int epi = p.episode[b];
-  const int ns = p.active_rw ? p.n_steps[b] : 0;
-  const float ep = p.track_score ? p.episode_reward[b] : 0.f;
-  __syncthreads();                              // the drawn action is in LDS; every thread has read the record
-  const int a = p.pol_x ? *s_act : p.actions[b];
-  const int ap = m.opp_actions[b];
-
-  SeatGame canon = own_old;
-  const SeatRewards rw = step_ticks2(canon, rules, a, ap, 2 * (p.actor_base + b), epi);
-  const float reward = (float)rw.r0;
-  const bool terminal = game_over(canon.g, rules, steps);
-  const DuelGame& old = own_old.g;
-  const DuelGame& g = canon.g;
-  const RingStep ring = ring_step(b, H1, cnt, prev_term, terminal, p.reset_on_terminal);
-  uint8_t* dst = p.frames + ((size_t)b * H1 + ring.nslot) * FRAME_BYTES;
-  const bool cut = TL && ring.reset && !game_ended(g, rules);      // (uniform) ended by the step limit alone
-  uint8_t* fin = TL ? p.final_obs + (size_t)b * FRAME_BYTES : nullptr;
-
-  const auto dirty = frame_dirty(old, g, rules);
-#pragma unroll 1
-  for (int k = 0; k < kChunksPerThread; ++k) {
-    const int c = threadIdx.x + 256 * k;
-    if (c < kChunks) {
-      const uint4 v = frame_chunk(g, rules, c);
-      if (!ring.reset) reinterpret_cast<uint4*>(dst)[c] = v;
-      if constexpr (TL) {
-        if (cut) reinterpret_cast<uint4*>(fin)[c] = v;
-      }
-      diff[c] = make_uint4(diff_dword(old, rules, dirty, 4 * c, v.x), diff_dword(old, rules, dirty, 4 * c + 1, v.y),
-                           diff_dword(old, rules, dirty, 4 * c + 2, v.z), diff_dword(old, rules, dirty, 4 * c + 3, v.w));
-    }
-  }
-  __syncthreads();
-  {                                             // pixel change, as in step_actor
-    const uint32_t* d32 = reinterpret_cast<const uint32_t*>(diff);
-    for (int c = threadIdx.x; c < PC_CELLS; c += 256) {
-      const int i = c / 20, j = c - 20 * i;
-      int sum = 0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const uint32_t* q = d32 + (4 * i + 2 + r) * kRowDw + 3 * j + 1;
-        sum += bytesum(q[0] >> 16) + bytesum(q[1]) + bytesum(q[2]) + bytesum(q[3] & 0xFFFFu);
-      }
-      p.r_pc[ring.base * PC_CELLS + c] = (float)sum / kPcDenom;
-    }
-  }
-  if (ring.reset) {                             // (uniform) the next match's first observation goes into the slot instead
-    canon.g = reset_game(rules, canon.g);
-    store_frame(dst, canon.g, rules);
-  }
-  if (threadIdx.x == 0) {
-    ring_commit(p, b, ring, a, reward, reward, la, lr, ep);
-    store_seat_game(rec, canon);
-    p.ep_steps[b] = ring.reset ? 0 : steps;
-    p.episode[b] = epi + (ring.reset ? 1 : 0);
-    rollout_commit(p, b, ring, ns, a, reward);
-    if constexpr (TL) {
-      if (cut) {                                  // the three words the commits above have set to 1
-        p.r_terminal[ring.base] = 2;
-        if (p.out_terminal) p.out_terminal[b] = 2;
-        p.terminal_end[b] = 2;
-      }
-    }
-    m.opp_last_action[b] = ring.reset ? 0 : ap;     // (zeroed with the learner's where the step resets: what seat 1 keeps)
-    m.opp_last_reward[b] = ring.reset ? 0.f : (float)rw.r1;
-  }
-  // the opponent's view, after the learner's: what seat 1 sees now (the next match's first frame where the step reset)
-  const SeatGame opp = mirror(canon);
-  store_frame(m.opp_frames + (size_t)b * FRAME_BYTES, opp.g, rules);
-}
-
-__global__ __launch_bounds__(256) void arcade_versus_step_kernel(ArcadeVersusArgs m) {
-  __shared__ uint4 diff[kChunks];
-  __shared__ int s_act;
-  if (m.a.cfg[0] == kArcadeDuel) step_versus<false>(m, diff, &s_act);   // (uniform) another game's block: nothing is written
-}
-
-__global__ __launch_bounds__(256) void arcade_versus_step_tl_kernel(ArcadeVersusArgs m) {
-  __shared__ uint4 diff[kChunks];
-  __shared__ int s_act;
-  if (m.a.cfg[0] == kArcadeDuel) step_versus<true>(m, diff, &s_act);
-}
-
-// reset_game on the canonical record, the learner's frame, then the opponent's mirrored one and its two zeroed words
-__global__ __launch_bounds__(256) void arcade_versus_reset_kernel(ArcadeVersusArgs m) {
-  const ArcadeArgs& p = m.a;
-  if (p.cfg[0] != kArcadeDuel) return;          // (uniform) as in the step
-  const int b = blockIdx.x;
-  if (p.mask && !p.mask[b]) return;
-  int* rec = p.records + (size_t)kArcadeRecord * b;
-  const DuelRules rules = load_seat_rules(p.cfg);
-  SeatGame canon = load_seat_game(rec);
-  const int epi = p.episode[b];
-  __syncthreads();                              // every thread has read the record
-  canon.g = reset_game(rules, canon.g);
-  store_frame(p.frames + ((size_t)b * p.H1 + p.count[b] % p.H1) * FRAME_BYTES, canon.g, rules);
-  if (threadIdx.x == 0) {
-    store_seat_game(rec, canon);
-    p.ep_steps[b] = 0;
-    p.episode[b] = epi + 1;
-    p.last_action[b] = 0;
-    p.last_reward[b] = 0.f;
-    m.opp_last_action[b] = 0;
-    m.opp_last_reward[b] = 0.f;
-  }
-  const SeatGame opp = mirror(canon);
-  store_frame(m.opp_frames + (size_t)b * FRAME_BYTES, opp.g, rules);
-}
-
-// the versus launcher: arcade_launch's tail and checks, and the opponent's four arrays (any B, any actor_base)
-int arcade_versus_launch(ArcadeEntry e, ArcadeArgs& p, const int* cfg, int actor_base, int* ep_steps, int* episode,
-                         int* records, const int* opp_actions, uint8_t* opp_frames, int* opp_last_action,
-                         float* opp_last_reward, void* stream, bool tl = false, uint8_t* final_obs = nullptr) {
-  p.cfg = cfg; p.actor_base = actor_base; p.ep_steps = ep_steps; p.episode = episode; p.records = records;
-  if (tl) p.final_obs = final_obs;
-  if (!arcade_args_ok(e, p)) return UNREAL_EINVAL;
-  if (tl && (!final_obs || ((uintptr_t)final_obs & 15) || (e != kRollout && e != kPolicy))) return UNREAL_EINVAL;
-  if (!opp_frames || ((uintptr_t)opp_frames & 15) || !opp_last_action || !opp_last_reward) return UNREAL_EINVAL;
-  if (e != kReset && !opp_actions) return UNREAL_EINVAL;
-  if ((long long)actor_base + p.B > (1ll << 30)) return UNREAL_EINVAL;   // 2 (actor_base + b) is an int
-  const ArcadeVersusArgs m{p, opp_actions, opp_frames, opp_last_action, opp_last_reward};
-  hipStream_t s = (hipStream_t)stream;
-  if (e == kReset) hipLaunchKernelGGL(arcade_versus_reset_kernel, dim3(p.B), dim3(256), 0, s, m);
-  else if (tl) hipLaunchKernelGGL(arcade_versus_step_tl_kernel, dim3(p.B), dim3(256), 0, s, m);
-  else hipLaunchKernelGGL(arcade_versus_step_kernel, dim3(p.B), dim3(256), 0, s, m);
-  return unreal_launch_status();
-}
-
-}  // namespace
-
-extern "C" {
 
 // Versus: the six arcade entries with the arguments of the plain ones and the opponent's four arrays
 // behind them.
 
 int unreal_arcade_versus_reset(int B, int H1, const int* mask, int* pos, int* last_action, float* last_reward,
                                const int* count, uint8_t* frames, const int* cfg, int actor_base, int* ep_steps,
-                                 int* episode, int* records, const int* opp_actions, uint8_t* opp_frames,
-                                 int* opp_last_action, float* opp_last_reward, void* stream) {
+                               int* episode, int* records, const int* opp_actions, uint8_t* opp_frames,
+                               int* opp_last_action, float* opp_last_reward, void* stream) {
   (void)pos;
-  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, const_cast<int*>(count), frames};
-  p.mask = mask;
-  return arcade_versus_launch(kReset, p, cfg, actor_base, ep_steps, episode, records, opp_actions, opp_frames,
-                              opp_last_action, opp_last_reward, stream);
+  return arcade_launch(kVersus, kReset, reset_args(B, H1, mask, last_action, last_reward, count, frames), cfg, actor_base,
+                       ep_steps, episode, records, versus_extra(opp_actions, opp_frames, opp_last_action, opp_last_reward), stream);
 }
 
 int unreal_arcade_versus_step(int B, int H1, const int* actions, const int* active, int* pos, int* last_action,
-                                float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
-                                int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                                int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
-                                int reset_on_terminal, int track_score, const int* cfg, int actor_base, int* ep_steps,
-                                int* episode, int* records, const int* opp_actions, uint8_t* opp_frames,
-                                int* opp_last_action, float* opp_last_reward, void* stream) {
+                              float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                              int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                              int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                              int reset_on_terminal, int track_score, const int* cfg, int actor_base, int* ep_steps,
+                              int* episode, int* records, const int* opp_actions, uint8_t* opp_frames,
+                              int* opp_last_action, float* opp_last_reward, void* stream) {
   (void)pos;
-  ArcadeArgs p{B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid,
-               reset_on_terminal, track_score};
-  return arcade_versus_launch(kStep, p, cfg, actor_base, ep_steps, episode, records, opp_actions, opp_frames,
-                              opp_last_action, opp_last_reward, stream);
+  return arcade_launch(kVersus, kStep,
+                       step_args(B, H1, actions, active, last_action, last_reward, count, frames, r_reward, r_action,
+                                 r_terminal, r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward,
+                                 score_out, score_valid, reset_on_terminal, track_score),
+                       cfg, actor_base, ep_steps, episode, records,
+                       versus_extra(opp_actions, opp_frames, opp_last_action, opp_last_reward), stream);
 }
 
 int unreal_arcade_versus_rollout_step(int B, int H1, const int* actions, int* pos, int* last_action, float* last_reward,
-                                        int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
-                                        int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
-                                        int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
-                                        int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
-                                        float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
-                                        const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
-                                        const int* opp_actions, uint8_t* opp_frames, int* opp_last_action,
-                                        float* opp_last_reward, void* stream) {
+                                      int* count, uint8_t* frames, float* r_reward, int* r_action, int* r_terminal,
+                                      int* r_last_action, float* r_last_reward, float* r_pc, float* out_reward,
+                                      int* out_terminal, float* episode_reward, float* score_out, int* score_valid,
+                                      int* active, int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                      float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                                      const int* cfg, int actor_base, int* ep_steps, int* episode, int* records,
+                                      const int* opp_actions, uint8_t* opp_frames, int* opp_last_action,
+                                      float* opp_last_reward, void* stream) {
   (void)pos;
-  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
-  return arcade_versus_launch(kRollout, p, cfg, actor_base, ep_steps, episode, records, opp_actions, opp_frames,
-                              opp_last_action, opp_last_reward, stream);
+  return arcade_launch(kVersus, kRollout,
+                       rollout_args(B, H1, actions, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+                                    r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out,
+                                    score_valid, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
+                                    lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records,
+                       versus_extra(opp_actions, opp_frames, opp_last_action, opp_last_reward), stream);
 }
 
 int unreal_arcade_versus_policy_rollout_step(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
-                                               const float* Wv, const float* bv, const double* u, float* pi_out,
-                                               float* v_out, int* actions_out, int* pos, int* last_action,
-                                               float* last_reward, int* count, uint8_t* frames, float* r_reward,
-                                               int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
-                                               float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
-                                               float* score_out, int* score_valid, int* active, int* active_log_t,
-                                               int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
-                                               int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
-                                               int actor_base, int* ep_steps, int* episode, int* records,
-                                               const int* opp_actions, uint8_t* opp_frames, int* opp_last_action,
-                                               float* opp_last_reward, void* stream) {
+                                             const float* Wv, const float* bv, const double* u, float* pi_out,
+                                             float* v_out, int* actions_out, int* pos, int* last_action,
+                                             float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                             int* r_action, int* r_terminal, int* r_last_action, float* r_last_reward,
+                                             float* r_pc, float* out_reward, int* out_terminal, float* episode_reward,
+                                             float* score_out, int* score_valid, int* active, int* active_log_t,
+                                             int* n_steps, int* terminal_end, int* next_idx, float* next_lar,
+                                             int lar_ld, int lar_col0, int A, int idx_base_actor, const int* cfg,
+                                             int actor_base, int* ep_steps, int* episode, int* records,
+                                             const int* opp_actions, uint8_t* opp_frames, int* opp_last_action,
+                                             float* opp_last_reward, void* stream) {
   (void)pos;
-  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
-               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
-  return arcade_versus_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, opp_actions, opp_frames,
-                              opp_last_action, opp_last_reward, stream);
+  return arcade_launch(kVersus, kPolicy,
+                       policy_args(B, H1, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions_out, last_action, last_reward,
+                                   count, frames, r_reward, r_action, r_terminal, r_last_action, r_last_reward, r_pc,
+                                   out_reward, out_terminal, episode_reward, score_out, score_valid, active, active_log_t,
+                                   n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records,
+                       versus_extra(opp_actions, opp_frames, opp_last_action, opp_last_reward), stream);
 }
 
 int unreal_arcade_versus_rollout_step_tl(int B, int H1, const int* actions, int* pos, int* last_action,
-                                           float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
-                                           int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc,
-                                           float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
-                                           int* score_valid, int* active, int* active_log_t, int* n_steps,
-                                           int* terminal_end, int* next_idx, float* next_lar, int lar_ld, int lar_col0,
-                                           int A, int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
-                                           int* episode, int* records, uint8_t* final_obs, const int* opp_actions,
-                                           uint8_t* opp_frames, int* opp_last_action, float* opp_last_reward,
-                                           void* stream) {
+                                         float* last_reward, int* count, uint8_t* frames, float* r_reward, int* r_action,
+                                         int* r_terminal, int* r_last_action, float* r_last_reward, float* r_pc,
+                                         float* out_reward, int* out_terminal, float* episode_reward, float* score_out,
+                                         int* score_valid, int* active, int* active_log_t, int* n_steps,
+                                         int* terminal_end, int* next_idx, float* next_lar, int lar_ld, int lar_col0,
+                                         int A, int idx_base_actor, const int* cfg, int actor_base, int* ep_steps,
+                                         int* episode, int* records, uint8_t* final_obs, const int* opp_actions,
+                                         uint8_t* opp_frames, int* opp_last_action, float* opp_last_reward,
+                                         void* stream) {
   (void)pos;
-  ArcadeArgs p{B, H1, actions, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor};
-  return arcade_versus_launch(kRollout, p, cfg, actor_base, ep_steps, episode, records, opp_actions, opp_frames,
-                              opp_last_action, opp_last_reward, stream, true, final_obs);
+  return arcade_launch(kVersus, kRollout,
+                       rollout_args(B, H1, actions, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
+                                    r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out,
+                                    score_valid, active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld,
+                                    lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records,
+                       versus_extra(opp_actions, opp_frames, opp_last_action, opp_last_reward), stream, true, final_obs);
 }
 
 int unreal_arcade_versus_policy_rollout_step_tl(int B, int H1, const float* X, int ldx, const float* Wp, const float* bp,
-                                                  const float* Wv, const float* bv, const double* u, float* pi_out,
-                                                  float* v_out, int* actions_out, int* pos, int* last_action,
-                                                  float* last_reward, int* count, uint8_t* frames, float* r_reward,
-                                                  int* r_action, int* r_terminal, int* r_last_action,
-                                                  float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
-                                                  float* episode_reward, float* score_out, int* score_valid, int* active,
-                                                  int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
-                                                  float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
-                                                  const int* cfg, int actor_base, int* ep_steps, int* episode,
-                                                  int* records, uint8_t* final_obs, const int* opp_actions,
-                                                  uint8_t* opp_frames, int* opp_last_action, float* opp_last_reward,
-                                                  void* stream) {
+                                                const float* Wv, const float* bv, const double* u, float* pi_out,
+                                                float* v_out, int* actions_out, int* pos, int* last_action,
+                                                float* last_reward, int* count, uint8_t* frames, float* r_reward,
+                                                int* r_action, int* r_terminal, int* r_last_action,
+                                                float* r_last_reward, float* r_pc, float* out_reward, int* out_terminal,
+                                                float* episode_reward, float* score_out, int* score_valid, int* active,
+                                                int* active_log_t, int* n_steps, int* terminal_end, int* next_idx,
+                                                float* next_lar, int lar_ld, int lar_col0, int A, int idx_base_actor,
+                                                const int* cfg, int actor_base, int* ep_steps, int* episode,
+                                                int* records, uint8_t* final_obs, const int* opp_actions,
+                                                uint8_t* opp_frames, int* opp_last_action, float* opp_last_reward,
+                                                void* stream) {
   (void)pos;
-  ArcadeArgs p{B, H1, nullptr, nullptr, last_action, last_reward, count, frames, r_reward, r_action, r_terminal,
-               r_last_action, r_last_reward, r_pc, out_reward, out_terminal, episode_reward, score_out, score_valid, 1, 1,
-               active, active_log_t, n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor, X, ldx,
-               Wp, bp, Wv, bv, u, pi_out, v_out, actions_out};
-  return arcade_versus_launch(kPolicy, p, cfg, actor_base, ep_steps, episode, records, opp_actions, opp_frames,
-                              opp_last_action, opp_last_reward, stream, true, final_obs);
+  return arcade_launch(kVersus, kPolicy,
+                       policy_args(B, H1, X, ldx, Wp, bp, Wv, bv, u, pi_out, v_out, actions_out, last_action, last_reward,
+                                   count, frames, r_reward, r_action, r_terminal, r_last_action, r_last_reward, r_pc,
+                                   out_reward, out_terminal, episode_reward, score_out, score_valid, active, active_log_t,
+                                   n_steps, terminal_end, next_idx, next_lar, lar_ld, lar_col0, A, idx_base_actor),
+                       cfg, actor_base, ep_steps, episode, records,
+                       versus_extra(opp_actions, opp_frames, opp_last_action, opp_last_reward), stream, true, final_obs);
 }
 
 }  // extern "C"
