@@ -283,13 +283,14 @@ MUST_REACH = {
 
 
 def _zero_state(tr):
-    """boot2_ws / aux2_ws start every replayed sequence from the zero LSTM state and trainer.py fills neither: nothing
-    may ever have written their c0 / h0 (bit for bit: -0.0 counts)."""
+    """Every replay workspace the trainer holds (Trainer._replay_set: the path and the bootstrap workspace of each width)
+    starts every replayed sequence from the zero LSTM state and trainer.py fills none of them: nothing may ever have
+    written their c0 / h0 (bit for bit: -0.0 counts)."""
     n = 0
     for c in (tr, getattr(tr, "mb", None)):
-        if c is None or not getattr(c, "batch_aux", False) or not tr.use_lstm:
+        if c is None or not tr.use_lstm:
             continue
-        for ws in (c.boot2_ws, c.aux2_ws):
+        for ws in [w for r in c.replay.values() for w in (r.boot_ws, r.ws)]:
             for name in ("c0", "h0"):
                 t = getattr(ws, name)
                 assert not bool(t.view(torch.int32).any()), "%s of a zero-state workspace was written" % name
@@ -347,7 +348,7 @@ def test_every_slot_of_a_training_pass_covers_its_operand(config, build, monkeyp
     assert any(p["operand"] == "W" for p in grown.pairs)                 # the weight shadows were audited as well
     if check is not None:
         check(truncated)
-    if tr.use_lstm and getattr(tr, "batch_aux", False):
+    if tr.use_lstm and tr.replay_width:
         assert _zero_state(tr) >= 4
     tr.stop()
 

@@ -124,7 +124,7 @@ def test_sampled_sequences_and_rp_triples(trained):
     term = ring.r_terminal.cpu().numpy().reshape(B, H1)
     rew = ring.r_reward.cpu().numpy().reshape(B, H1)
     # the samples of the last call: pixel-control and value-replay sequences (one batched pass), or the value-replay one
-    samples = list(zip(tr.seq_idx2, tr.seq_len2)) if getattr(tr, "batch_aux", False) else [(tr.seq_idx, tr.seq_len)]
+    samples = list(zip(tr.replay[tr.replay_width].seq_idx, tr.replay[tr.replay_width].seq_len))
     for seq_t, len_t in samples:
         seq = seq_t.cpu().numpy().reshape(L, B).astype(np.int64)
         ln = len_t.cpu().numpy()
@@ -140,9 +140,9 @@ def test_sampled_sequences_and_rp_triples(trained):
             t_flags = term[b, slots]
             assert not t_flags[:-1].any()                                      # stops at the first terminal, inclusive
             assert ln[b] == L or t_flags[-1] == 1
-    if getattr(tr, "batch_aux", False):
+    if tr.replay_width == 2:
         # the batched workspace lists sequence 2b = pixel-control sample of actor b, 2b + 1 = its value-replay sample
-        fi = tr.aux2_ws.frame_idx.cpu().numpy().reshape(T, B, 2)
+        fi = tr.replay[2].ws.frame_idx.cpu().numpy().reshape(T, B, 2)
         for s_, (seq_t, _) in enumerate(samples):
             np.testing.assert_array_equal(fi[:, :, s_], seq_t.cpu().numpy().reshape(L, B)[:T])
     rp = tr.rp_ws.frame_idx[:3 * B].cpu().numpy().reshape(B, 3).astype(np.int64)
@@ -236,7 +236,7 @@ def branches(trained):
     tr._rollout()
     net.grads.flat.zero_()
     tr.losses.zero_()
-    tr._train_base()
+    tr._train_base(tr)
     torch.cuda.synchronize()
     rs = np.random.RandomState(77)
     return flags, net, tr, rs.choice(B, size=N_ACT, replace=False), _p64(net)
@@ -451,10 +451,10 @@ def test_fullshape_split_gemms_not_worse_than_fp32_mfma_on_live_operands(branche
 def test_fullshape_pixel_control_rows_match_oracle(branches):
     import torch.nn.functional as F
     flags, net, tr, actors, p64 = branches
-    tr._train_pc()
+    tr._train_replay(tr, ("pc",))
     torch.cuda.synchronize()
-    ws, gws, A, Ta = tr.aux_ws, tr.gws, tr.action_size, tr.local_t_max
-    mask = tr.seq_mask.view(Ta, B).cpu().numpy()
+    ws, gws, A, Ta = tr.replay[1].ws, tr.gws, tr.action_size, tr.local_t_max
+    mask = tr.replay[1].seq_mask[0].view(Ta, B).cpu().numpy()
     z = torch.zeros(256, dtype=torch.float64)
     Wv = p64["W_pc_deconv_v"].permute(3, 2, 0, 1)
     Wa = p64["W_pc_deconv_a"].permute(3, 2, 0, 1)
@@ -493,11 +493,11 @@ def test_fullshape_pixel_control_rows_match_oracle(branches):
 def test_fullshape_value_replay_and_reward_prediction_rows_match_oracle(branches):
     from oracle import model as M
     flags, net, tr, actors, p64 = branches
-    tr._train_vr()
-    tr._train_rp()
+    tr._train_replay(tr, ("vr",))
+    tr._train_rp(tr)
     torch.cuda.synchronize()
-    ws, Ta = tr.aux_ws, tr.local_t_max
-    mask = tr.seq_mask.view(Ta, B).cpu().numpy()
+    ws, Ta = tr.replay[1].ws, tr.local_t_max
+    mask = tr.replay[1].seq_mask[0].view(Ta, B).cpu().numpy()
     z = torch.zeros(256, dtype=torch.float64)
     for b in actors:
         n = int(mask[:, b].sum())
@@ -525,17 +525,17 @@ def test_fullshape_batched_replay_pass_rows_match_oracle(branches):
     and the value-replay V that the heads read through the doubled leading dimension."""
     from oracle import model as M
     flags, net, tr, actors, p64 = branches
-    if not tr.batch_aux:
+    if tr.replay_width != 2:
         pytest.skip("per-branch schedule")
     net.grads.flat.zero_()                       # what the pass leaves in net.g is its own contribution (checked below)
-    tr._train_aux_batched()
+    tr._train_replay(tr, ("pc", "vr"))
     torch.cuda.synchronize()
-    ws, gws, Ta = tr.aux2_ws, tr.gws2, tr.local_t_max
+    ws, gws, Ta = tr.replay[2].ws, tr.replay[2].gws, tr.local_t_max
     z = torch.zeros(256, dtype=torch.float64)
     checked = 0
     for b in actors[:32]:
         for s_ in (0, 1):
-            mask = tr.seq_mask2[s_].view(Ta, B).cpu().numpy()
+            mask = tr.replay[2].seq_mask[s_].view(Ta, B).cpu().numpy()
             n = int(mask[:, b].sum())
             if n == 0:
                 continue
@@ -555,15 +555,15 @@ def test_fullshape_batched_replay_pass_rows_match_oracle(branches):
 
 def test_fullshape_batched_replay_pass_backward_matches_fp64(branches):
     """Backward of the product's replay schedule at production shape (runs after the test above: net.g holds exactly the
-    batched pass's contribution, its operands are live in aux2_ws / gws2): pixel-control deconv dgrad + wgrad on every
+    batched pass's contribution, its operands are live in replay[2].ws / replay[2].gws): pixel-control deconv dgrad + wgrad on every
     other row of the 2B-sequence batch, the pc fc wgrad read through the doubled leading dimension, the 163,840-row fc1
     wgrad (split-K TN, K = 163,840) / dgrad and the 163,840-frame encoder_bwd -- each against an fp64 evaluation on the
     device from the same live operands.  Tolerance: 5e-5 of the largest element (rounds 1-3: 2e-4)."""
     import torch.nn.functional as F
     flags, net, tr, actors, p64 = branches
-    if not tr.batch_aux:
+    if tr.replay_width != 2:
         pytest.skip("per-branch schedule")
-    ws, gws, ring, A, Ta = tr.aux2_ws, tr.gws2, tr.ring, tr.action_size, tr.local_t_max
+    ws, gws, ring, A, Ta = tr.replay[2].ws, tr.replay[2].gws, tr.ring, tr.action_size, tr.local_t_max
     rows, rows2 = Ta * B, 2 * Ta * B
     g = net.g
     # ---- pixel-control head: d_dec -> d_hp (dgrad, ReLU of the fc), dW / db of both deconvs --------------------------
@@ -660,7 +660,7 @@ def test_fullshape_reward_prediction_backward_matches_fp64(branches):
     net.begin_pass()
     net.grads.flat.zero_()
     tr.losses.zero_()
-    tr._train_rp()
+    tr._train_rp(tr)
     torch.cuda.synchronize()
     ws, gws, ring, g = tr.rp_ws, tr.gws, tr.ring, net.g
     f2 = ws.f2[:3 * B * 2592].view(B, 7776)

@@ -125,8 +125,8 @@ def _teleport(tr, orc, b, x, y):
 
 # flag sets: full UNREAL, config 1 (FF, no aux), and the partial sets the reference's own tests build
 # (model/model_test.py:22-66: PC only = 18 variables, VR only = 12, RP only = 14 with the LSTM on; PC only is also
-# BASELINE config 4's flag set).  With exactly one of PC / VR the trainer runs the per-branch schedule
-# (_train_pc / _train_vr on the single-width workspaces), with both the batched replay pass.
+# BASELINE config 4's flag set).  With exactly one of PC / VR the trainer runs the replay pass with that one lane
+# (_train_replay on the one-lane workspaces), with both the two-lane replay pass.
 @pytest.mark.parametrize("use_lstm,aux,n_vars", [(True, True, 20), (False, False, 10),
                                                  (True, (True, False, False), 18),
                                                  (True, (False, True, False), 12),
@@ -139,7 +139,7 @@ def test_process_matches_oracle(use_lstm, aux, n_vars):
     cfg["initial_learning_rate"] = 7.0711e-4
     net, applier, tr, draws = _build(cfg, B, seed=3)
     assert len(net.get_vars()) == n_vars                      # model/model_test.py:14-58
-    assert tr.batch_aux == (cfg["use_pixel_change"] and cfg["use_value_replay"])
+    assert (tr.replay_width == 2) == (cfg["use_pixel_change"] and cfg["use_value_replay"])
     named = net.export_named()
     params = {k: torch.tensor(v, dtype=torch.float64) for k, v in named.items()}
     edraws = [ExplicitDraws() for _ in range(B)]
@@ -415,7 +415,7 @@ def _hostfed_parity(cfg, B, H, T, tr, net, applier, draws, orc, edraws, check_fr
 
 
 # B = 4: two half-batches alternate between host and device (overlap_host).  aux (False, ...) = BASELINE config 4's own
-# flag set, "A3C-LSTM + pixel-control": no value replay, no reward prediction -> the per-branch _train_pc schedule
+# flag set, "A3C-LSTM + pixel-control": no value replay, no reward prediction -> the one-lane replay pass (_train_replay)
 @pytest.mark.parametrize("B,aux", [(3, True), (4, True), (3, (True, False, False)), (4, (True, False, False))])
 def test_hostfed_lab_contract_matches_oracle(B, aux):
     """SURVEY 8f-1 / BASELINE config 4: host simulators (synthetic stand-in for DeepMind Lab: uint8 frames, A = 6,
@@ -588,7 +588,7 @@ def test_one_launch_pixel_control_pass_is_the_two_launch_pass(batch_aux, monkeyp
         monkeypatch.setattr(Trainer, "fuse_pc_deconv", fused)
         monkeypatch.setattr(Trainer, "batch_aux_default", batch_aux)
         net, applier, tr, draws = _build(cfg, B, seed=11)
-        assert tr.batch_aux == batch_aux
+        assert (tr.replay_width == 2) == batch_aux
         while not tr._full:
             tr.process(None, 0)
         g, snaps = 0, []
@@ -597,7 +597,7 @@ def test_one_launch_pixel_control_pass_is_the_two_launch_pass(batch_aux, monkeyp
             g += steps
             snaps.append(dict(actions=tr.actions.cpu().numpy().copy(), losses=dict(tr.last_losses),
                               grads=net.grads.flat.cpu().numpy().copy(), params=net.params.flat.cpu().numpy().copy()))
-        assert ((tr.gws2 if batch_aux else tr.gws).d_dec is None) == fused
+        assert (tr.replay[tr.replay_width].gws.d_dec is None) == fused
         out.append(snaps)
     a, b = out[0][0], out[1][0]
     np.testing.assert_array_equal(a["actions"], b["actions"])

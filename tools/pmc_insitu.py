@@ -4,7 +4,7 @@ the TIMED region, mean counter value per launch.
   The timed region is found in the trace itself, not from constants: every learner update ends with exactly one
   `rmsprop_kernel` launch, bench.py makes `warmup` untimed and `steps` timed process() calls of `groups` updates each
   (bench_run.json, written by bench.py under UNREAL_BENCH_SIDECAR), so the timed dispatches are those after update number
-  warmup*groups and up to the last update -- whatever the schedule (batch_aux, groups, fuse_bptt) launches inside.
+  warmup*groups and up to the last update -- whatever the schedule (batch_aux_default, groups, fuse_bptt) launches inside.
   FETCH_SIZE is doubled (gfx950 reports half of a wide coalesced read, MI355X_MICROARCH.md HBM), WRITE_SIZE as is, both
   in KB -> hbm_bytes_per_launch.
 usage: tools/pmc_insitu.py <outdir of pmc_bench.sh> > profiles/rNN_pmc_bench.json"""

@@ -23,8 +23,18 @@ order in which hogwild threads would take the lock if there were one).
 
 Per-actor random draws come from a counter RNG (Philox) on the device; `draws` can be replaced to
 replay a recorded stream (parity tests).  TF-only arguments are accepted and ignored.
+
+How the schedule is laid out.  `_rollout` = prologue, exactly one of four step schedules (`_rollout_steps_device` /
+`_rollout_steps_host` in lock-step, `_rollout_steps_overlapped` / `_rollout_steps_split` as half-batches on two streams),
+`_rollout_bootstrap`, `_rollout_returns`; every schedule forwards rows [t B + b0, t B + b0 + n) through the one body
+`_policy_step`, reads the rows' buffers through `_block` and tells a device environment what to prepare of step t + 1
+through `_next_rows`.  The loss branches of an update (`_train_base`, `_train_replay`, `_train_rp`) take the `PassState` they
+work on explicitly: the trainer itself, or the minibatch twin `self.mb`.  Pixel control and value replay are lanes of ONE
+replay pass, `_train_replay(c, lanes)`: ("pc", "vr") by default, one lane per pass otherwise; a width's workspaces come from
+`_replay_set` and are never written in c0 / h0.
 """
 import time
+from types import SimpleNamespace
 
 import torch
 
@@ -72,16 +82,8 @@ class PassState(object):
     """What the loss branches of ONE update read and write, sized for `Bg` actors: the path and gradient workspaces, the
     replay samples' buffers, the heads' outputs and gradients, the ring the replay branches sample (`ring`) and the ring the
     base rows' frame indices point into (`base_ring`).  The Trainer is its own for a whole group; with reuse_minibatches > 1
-    a second one, sized for a block of the group's actors, also holds the block's compacted rollout rows."""
-
-    @property
-    def aux_ws(self):
-        """Workspace of the one-branch-at-a-time replay schedule (lazy: see Trainer.prepare())."""
-        if self._aux_ws is None and self._aux_ws_args is not None:
-            rows, B, dev, lstm, xld = self._aux_ws_args
-            self._aux_ws = PathWS(rows, B, dev, save_c1=True, lstm=lstm, xld=xld, **self.local_network.ws_kw)
-            self.gws.ensure_rows(rows, B, dev)
-        return self._aux_ws
+    a second one, sized for a block of the group's actors, also holds the block's compacted rollout rows.
+    The Trainer's pass methods take theirs as the argument `c`."""
 
 
 class Trainer(PassState):
@@ -632,26 +634,25 @@ class Trainer(PassState):
         c.Bg = B
         c.grad_scale = 1.0 / float(B * self.world_size)
         lstm = self.use_lstm
-        aux = self.use_pixel_change or self.use_value_replay
         xld = self.local_network.xld
         wkw = self.local_network.ws_kw                # conv activation sizes of the network's frame size
         c.base_ws = PathWS(T * B, B, dev, save_c1=True, lstm=lstm, xld=xld, **wkw)
         c.boot_ws = PathWS(B, B, dev, save_c1=False, lstm=lstm, xld=xld, **wkw)
         c.rp_ws = PathWS(3 * B, B, dev, save_c1=True, lstm=False, xld=xld, **wkw) if self.use_reward_prediction else None
-        # pixel control and value replay as ONE batch of 2B replayed sequences (actor 2b = pc sample of b, 2b + 1 = vr
-        # sample): see _train_aux_batched.  Decided HERE, once (the class default is read at prepare() time only).
-        c.batch_aux = bool(self.batch_aux_default and self.use_pixel_change and self.use_value_replay)
-        # per-branch workspaces (_train_pc / _train_vr: one of the two tasks on, or batch_aux off) are allocated on first
-        # use: with the batched pass they would be ~5 GB of dead HBM per rank at 4096 actors
-        c._aux_ws = None
-        c._aux_ws_args = (Ta * B, B, dev, lstm, xld) if aux else None
-        per_branch = aux and not c.batch_aux
-        rows = max(T, Ta if per_branch else 0, 3 if self.use_reward_prediction else 0) * B
-        c.gws = GradWS(rows, B, dev, lstm=lstm, pc=self.use_pixel_change and per_branch, A=A, f2_dim=wkw["f2_dim"])
-        if c.batch_aux:
-            c.aux2_ws = PathWS(Ta * 2 * B, 2 * B, dev, save_c1=True, lstm=lstm, xld=xld, **wkw)
-            c.boot2_ws = PathWS(2 * B, 2 * B, dev, save_c1=False, lstm=lstm, xld=xld, **wkw)
-            c.gws2 = GradWS(Ta * 2 * B, 2 * B, dev, lstm=lstm, pc=True, A=A, pc_rows=Ta * B, f2_dim=wkw["f2_dim"])
+        # the replay passes of an update (_train_replay): pixel control and value replay as the two lanes of ONE pass over
+        # 2B replayed sequences, or one pass of one lane per task that is on.  Decided HERE, once (the class default is
+        # read at prepare() time only).
+        lanes = tuple(n for n, on in (("pc", self.use_pixel_change), ("vr", self.use_value_replay)) if on)
+        c.replay_passes = (lanes,) if self.batch_aux_default and len(lanes) == 2 else tuple((n,) for n in lanes)
+        c.replay_width = len(c.replay_passes[0]) if lanes else 0
+        one_lane = c.replay_width == 1             # (a one-lane pass shares the update's gradient workspace)
+        rows = max(T, Ta if one_lane else 0, 3 if self.use_reward_prediction else 0) * B
+        c.gws = GradWS(rows, B, dev, lstm=lstm, pc=self.use_pixel_change and one_lane, A=A, f2_dim=wkw["f2_dim"])
+        # the configured width's workspaces; another width's are allocated on first use: next to the two-lane pass the
+        # one-lane workspaces would be ~5 GB of dead HBM per rank at 4096 actors
+        c.replay = {}
+        if lanes:
+            self._replay_set(c, c.replay_width)
         f = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
         i = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
         d = lambda n: torch.zeros(n, dtype=torch.float64, device=dev)
@@ -660,30 +661,54 @@ class Trainer(PassState):
             from ..model.model import DEPTH_HIDDEN, DEPTH_OUT
             c.dp_hidden, c.dp_d_hidden = f(T * B * DEPTH_HIDDEN), f(T * B * DEPTH_HIDDEN)
             c.dp_logits, c.dp_dlogits = f(T * B * DEPTH_OUT), f(T * B * DEPTH_OUT)
-        if aux:
-            L = Ta + 1
-            c.seq_idx, c.seq_len, c.seq_start = i(L * B), i(B), i(B)
-            c.seq_mask, c.seq_act = i(Ta * B), i(Ta * B)
+        if lanes:                     # what the lanes' heads write (a pass has at most one lane of a kind)
+            c.seq_act = i(Ta * B)
             c.aux_v, c.aux_R, c.aux_boot_v = f(Ta * B), f(Ta * B), f(B)
             if self.use_pixel_change:
                 c.boot_hp, c.boot_qmax = f(B * ops.F2_DIM), f(B * ops.PC_CELLS)
         if self.use_reward_prediction:
             c.rp_coin, c.rp_u, c.rp_class = i(B), d(B), i(B)
             c.rp_logits, c.rp_dlogits = f(B * 3), f(B * 3)
-        if c.batch_aux:
-            L = Ta + 1
-            c.seq_idx_cat = i(2 * L * B)
-            c.seq_idx2 = [c.seq_idx_cat[:L * B], c.seq_idx_cat[L * B:]]
-            c.seq_len2, c.seq_start2 = [i(B), i(B)], [i(B), i(B)]
-            c.seq_mask2 = [i(Ta * B), i(Ta * B)]
-            c.last2 = i(2 * B)
-            r = torch.arange(Ta * B, dtype=torch.int32)
-            c.map_seq = torch.stack([r, r + L * B], dim=1).reshape(-1).contiguous().to(dev)      # [2r + s] = s*L*B + r
-            b = torch.arange(B, dtype=torch.int32)
-            c.map_boot = torch.stack([b, b + B], dim=1).reshape(-1).contiguous().to(dev)          # [2b + s] = s*B + b
-            c.aux_dv = f(Ta * B)
         if reuse:                     # sample reuse: the re-evaluated heads
             c.pi_new, c.v_new = f(T * B * A), f(T * B)
+
+    def _replay_set(self, c, S):
+        """The workspaces and sample buffers of a replay pass over S lanes of pass state `c` -> c.replay[S]: allocated by
+        _alloc_pass for the configured width and on first use for another one (the full-size tests run one lane on a
+        trainer prepared for two).  Sequence S b + s of the path workspace `ws` and of the bootstrap workspace `boot_ws` is
+        lane s's sample of actor b.  Both belong to the replay pass alone and NOTHING ever writes their c0 / h0: they are
+        the zero state every replayed sequence starts from (model.py:395,461) as they were allocated, at every width.
+        One lane works in the update's own gradient workspace, grown to the pass's rows; more lanes have their own."""
+        r = c.replay.get(S)
+        if r is not None:
+            return r
+        B, Ta, A, dev, net = c.Bg, self.local_t_max, self.action_size, self.device, self.local_network
+        L, rows = Ta + 1, Ta * B
+        kw = dict(lstm=self.use_lstm, xld=net.xld, **net.ws_kw)
+        i = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+        r = c.replay[S] = SimpleNamespace()
+        r.ws = PathWS(S * rows, S * B, dev, save_c1=True, **kw)
+        r.boot_ws = PathWS(S * B, S * B, dev, save_c1=False, **kw)
+        if S == 1:
+            r.gws = c.gws
+            r.gws.ensure_rows(rows, B, dev)
+        else:
+            r.gws = GradWS(S * rows, S * B, dev, lstm=self.use_lstm, pc=self.use_pixel_change, A=A, pc_rows=rows,
+                           f2_dim=net.ws_kw["f2_dim"])
+        # lane s's sample: L frame indices per actor (seq_idx[s], a slice of seq_idx_cat), their count, the mask of its rows
+        r.seq_idx_cat = i(S * L * B)
+        r.seq_idx = [r.seq_idx_cat[s * L * B:(s + 1) * L * B] for s in range(S)]
+        r.seq_len, r.seq_start = [i(B) for _ in range(S)], [i(B) for _ in range(S)]
+        r.seq_mask = [i(Ta * B) for _ in range(S)]
+        lane = torch.arange(S, dtype=torch.int32)
+        q = torch.arange(rows, dtype=torch.int32)
+        r.map_seq = (q[:, None] + lane * (L * B)).reshape(-1).contiguous().to(dev)               # [S q + s] = s L B + q
+        # the bootstrap frames' indices, lane after lane, and their place in boot_ws (one lane: staged in place)
+        r.last, r.map_boot = r.boot_ws.frame_idx, None
+        if S > 1:
+            b = torch.arange(B, dtype=torch.int32)
+            r.last, r.map_boot = i(S * B), (b[:, None] + lane * B).reshape(-1).contiguous().to(dev)   # [S b + s] = s B + b
+        return r
 
     def _prepare_explore(self, rows, dev):
         """The exploration bonus's buffers: the hash's multipliers, ONE count table for this trainer (its
@@ -785,23 +810,52 @@ class Trainer(PassState):
         raise NotImplementedError("actions are drawn on the device; see ops.softmax_sample")
 
     # ---------------------------------------------------------------------------------------------------
-    def _policy_step(self, ws, t, u, actions_out, pi_out, v_out, prefilled=False, heads=True, encoded=False):
-        """Forward the current observations of all actors as time row-block t of `ws` and draw actions.  `prefilled`:
-        the previous environment step has already written this block's frame indices and last_action_reward columns.
-        `heads` False: the caller's environment step computes pi / V / action itself (fused launch); -> (feat, ld).
-        `encoded`: the previous environment step has also run the conv encoder on this block's frames (fuse_env_encoder)."""
-        B, A, net = self.Bg, self.action_size, self.local_network
+    def _block(self, t, b0=0, n=None):
+        """Rows [t B + b0, t B + b0 + n) of the rollout's buffers (n None: the whole time row-block t) -> the views
+        (u_act, pi, v, actions, rewards, terminals, active_log)."""
+        B, A = self.Bg, self.action_size
+        r0 = t * B + b0
+        r1 = r0 + (B if n is None else n)
+        s = slice(r0, r1)
+        return (self.u_act[s], self.pi[r0 * A:r1 * A], self.v[s], self.actions[s], self.rewards[s], self.terminals[s],
+                self.active_log[s])
+
+    def _next_rows(self, ws, t, b0=0, n=None):
+        """What a device environment's step t of the actors [b0, b0 + n) prepares of step t + 1, as the keywords of its
+        rollout_step: the rows' frame indices and, with the LSTM on, their [last action | last reward] columns; none
+        after the last step."""
+        B = self.Bg
+        if t + 1 >= self.n_step_TD:
+            return {}
+        r1 = (t + 1) * B + b0
+        nxt = dict(next_idx=ws.frame_idx[r1:r1 + (B if n is None else n)])
+        if self.use_lstm:
+            nxt.update(next_lar=ws.xcat[r1 * ws.xld:], lar_ld=ws.xld, lar_col0=256, A=self.action_size)
+        return nxt
+
+    def _policy_step(self, ws, t, b0=0, n=None, actor_ring=None, slots=None, prefilled=False, heads=True, encoded=False):
+        """Forward the current observations of the actors [b0, b0 + n) (n None: all) as rows [t B + b0, t B + b0 + n) of `ws`
+        and, unless the environment step does it, draw their actions into the rows' _block(); -> (feat, ld).
+        `actor_ring`: the ring view of exactly these actors (a half-batch on its own stream); `slots`: that stream's running
+        absmax pair (model.encode_rows).  `prefilled`: the previous environment step has already written the rows'
+        frame indices and last_action_reward columns.  `heads` False: the caller's environment step computes pi / V /
+        action itself (fused launch).  `encoded`: the previous environment step has also run the conv encoder on the rows'
+        frames (fuse_env_encoder)."""
+        B, net = self.Bg, self.local_network
+        n = B if n is None else n
+        r0 = t * B + b0
         if not prefilled:
-            self.ring.cur_idx(out=ws.frame_idx[t * B:(t + 1) * B])
+            (self.ring if actor_ring is None else actor_ring).cur_idx(out=ws.frame_idx[r0:r0 + n], base_actor=b0)
         # (a goal-sense maze's step has also written the objective columns: no objective_fill launch at t > 0)
-        net.encode_rows(self.ring, ws, t * B, B, lar_from_ring=False, save_c1=ws.c1 is not None,
-                        lar_prefilled=prefilled and self.use_lstm, lstm_x=False,
+        net.encode_rows(self.ring, ws, r0, n, lar_from_ring=False, save_c1=ws.c1 is not None, actor_ring=actor_ring,
+                        lar_prefilled=prefilled and self.use_lstm, lstm_x=False, slots=slots,
                         objective_prefilled=prefilled and self.use_lstm and self.device_env, encoded=encoded)
         if self.use_lstm:
-            net.lstm_step(ws, t, B, fused_x=True)
-        feat, ld = net.features(ws, t * B)
+            net.lstm_step(ws, t, B, b0, n, fused_x=True)
+        feat, ld = net.features(ws, r0)
         if heads:
-            net.policy_step(B, feat, ld, u, pi_out, v_out, actions_out)
+            u, pi, v, actions = self._block(t, b0, n)[:4]
+            net.policy_step(n, feat, ld, u, pi, v, actions)
         return feat, ld
 
     FILL_SYNC_EVERY = 64
@@ -840,7 +894,7 @@ class Trainer(PassState):
         if self.opponent_pool:                 # the opponents move first
             self.opp_draws.uniform(self.opp_u[:B])
             self._opponents_act(self.opp_u[:B], self.opponent_actions[:B])
-        self._policy_step(ws, 0, self.u_act[:B], self.actions[:B], self.pi[:B * self.action_size], self.v[:B])
+        self._policy_step(ws, 0)
         self.environment.process(self.actions[:B], None, self.rewards[:B], self.terminals[:B],
                                  reset_on_terminal=True, track_score=False)
         if self.use_lstm:                      # state advances; NOT reset on terminal here (:201-202)
@@ -853,8 +907,7 @@ class Trainer(PassState):
         """The T rollout steps for host-fed actors in two half-batches: while the host steps / stages one half (its
         simulators live on the CPU), the device ingests and forwards the other half on that half's own stream.  Same
         kernels, same rows, same draws as the lock-step loop -- only the schedule differs."""
-        B, T, A, ws, net = self.Bg, self.n_step_TD, self.action_size, self.base_ws, self.local_network
-        env = self.environment
+        T, ws, env = self.n_step_TD, self.base_ws, self.environment
         parts = env.parts
         main = torch.cuda.current_stream()
         start = torch.cuda.Event()
@@ -863,16 +916,8 @@ class Trainer(PassState):
         def forward(k, t):          # on part k's stream: policy forward of its actors for step t + action D2H request
             p = parts[k]
             b0, n = p["b0"], p["b1"] - p["b0"]
-            r0 = t * B + b0
-            p["ring"].cur_idx(out=ws.frame_idx[r0:r0 + n], base_actor=b0)
-            net.encode_rows(self.ring, ws, r0, n, lar_from_ring=False, save_c1=ws.c1 is not None, actor_ring=p["ring"],
-                            lstm_x=False)
-            if self.use_lstm:
-                net.lstm_step(ws, t, B, b0, n, fused_x=True)
-            feat, ld = net.features(ws, r0)
-            net.policy_step(n, feat, ld, self.u_act[r0:r0 + n], self.pi[r0 * A:(r0 + n) * A], self.v[r0:r0 + n],
-                            self.actions[r0:r0 + n])
-            env.part_request_actions(k, self.actions[r0:r0 + n], self.active[b0:b0 + n])
+            self._policy_step(ws, t, b0, n, actor_ring=p["ring"])
+            env.part_request_actions(k, self._block(t, b0, n)[3], self.active[b0:b0 + n])
 
         for k, p in enumerate(parts):
             with torch.cuda.stream(p["stream"]):
@@ -881,13 +926,13 @@ class Trainer(PassState):
         for t in range(T):
             for k, p in enumerate(parts):
                 b0, n = p["b0"], p["b1"] - p["b0"]
-                r0 = t * B + b0
+                _, _, _, actions, rewards, terminals, active_log = self._block(t, b0, n)
                 env.part_host_step(k, has_active=True)           # host: the other part's device work runs meanwhile
                 with torch.cuda.stream(p["stream"]):
-                    env.part_ingest(k, self.actions[r0:r0 + n], self.active[b0:b0 + n], self.rewards[r0:r0 + n],
-                                    self.terminals[r0:r0 + n], reset_on_terminal=True, track_score=True)
-                    ops.rollout_advance(n, self.terminals[r0:r0 + n], self.active[b0:b0 + n],
-                                        self.active_log[r0:r0 + n], self.n_steps[b0:b0 + n], self.terminal_end[b0:b0 + n])
+                    env.part_ingest(k, actions, self.active[b0:b0 + n], rewards, terminals, reset_on_terminal=True,
+                                    track_score=True)
+                    ops.rollout_advance(n, terminals, self.active[b0:b0 + n], active_log, self.n_steps[b0:b0 + n],
+                                        self.terminal_end[b0:b0 + n])
                     if t + 1 < T:
                         forward(k, t + 1)
         for p in parts:                                          # join: the learner continues on the caller's stream
@@ -933,7 +978,7 @@ class Trainer(PassState):
                                 for k in range(n_parts)])
 
     def _rollout_steps_split(self):
-        B, T, A, ws, net = self.Bg, self.n_step_TD, self.action_size, self.base_ws, self.local_network
+        T, ws, net = self.n_step_TD, self.base_ws, self.local_network
         parts = self._split[self.group]
         main = torch.cuda.current_stream()
         s_f2, s_x, _ = net.ws_slots(ws)
@@ -945,26 +990,12 @@ class Trainer(PassState):
         for t in range(T):
             for p in parts:
                 b0, n = p["b0"], p["n"]
-                r0 = t * B + b0
+                _, _, _, actions, rewards, terminals, active_log = self._block(t, b0, n)
                 with torch.cuda.stream(p["stream"]):
-                    if t == 0:
-                        p["env"].ring.cur_idx(out=ws.frame_idx[r0:r0 + n], base_actor=b0)
-                    net.encode_rows(self.ring, ws, r0, n, lar_from_ring=False, save_c1=ws.c1 is not None,
-                                    actor_ring=p["env"].ring, lar_prefilled=t > 0 and self.use_lstm, lstm_x=False,
-                                    slots=p["slots"])
-                    if self.use_lstm:
-                        net.lstm_step(ws, t, B, b0, n, fused_x=True)
-                    feat, ld = net.features(ws, r0)
-                    net.policy_step(n, feat, ld, self.u_act[r0:r0 + n], self.pi[r0 * A:(r0 + n) * A], self.v[r0:r0 + n],
-                                    self.actions[r0:r0 + n])
-                    nxt = {}
-                    if t + 1 < T:
-                        nxt = dict(next_idx=ws.frame_idx[r0 + B:r0 + B + n])
-                        if self.use_lstm:
-                            nxt.update(next_lar=ws.xcat[(r0 + B) * ws.xld:], lar_ld=ws.xld, lar_col0=256, A=A)
-                    p["env"].rollout_step(self.actions[r0:r0 + n], self.rewards[r0:r0 + n], self.terminals[r0:r0 + n],
-                                          self.active[b0:b0 + n], self.active_log[r0:r0 + n], self.n_steps[b0:b0 + n],
-                                          self.terminal_end[b0:b0 + n], index_parent=True, **nxt)
+                    self._policy_step(ws, t, b0, n, actor_ring=p["env"].ring, slots=p["slots"], prefilled=t > 0)
+                    p["env"].rollout_step(actions, rewards, terminals, self.active[b0:b0 + n], active_log,
+                                          self.n_steps[b0:b0 + n], self.terminal_end[b0:b0 + n], index_parent=True,
+                                          **self._next_rows(ws, t, b0, n))
         for p in parts:                                          # join: the learner continues on the caller's stream
             done = torch.cuda.Event()
             done.record(p["stream"])
@@ -974,8 +1005,10 @@ class Trainer(PassState):
             ops.absmax(1, 1, p["slots"][1], 1, s_x)
 
     def _rollout(self):
-        """[Base A3C] n_step_TD lock-step steps, bootstrap value, n-step returns (trainer.py:218-336)."""
-        B, T, A, ws, net = self.Bg, self.n_step_TD, self.action_size, self.base_ws, self.local_network
+        """[Base A3C] n_step_TD steps of every actor of the group, bootstrap value, n-step returns (trainer.py:218-336).
+        Exactly one schedule runs the steps: host-fed actors in lock-step or as two half-batches (overlap_host), device
+        actors in lock-step or as half-batches on two streams (_rollout_split_setup)."""
+        ws = self.base_ws
         if self.use_lstm:
             ops.copy_(ws.c0, self.lstm_c)           # start_lstm_state
             ops.copy_(ws.h0, self.lstm_h)
@@ -983,63 +1016,67 @@ class Trainer(PassState):
         self.n_steps.zero_()
         self.terminal_end.zero_()
         self.draws.uniform(self.u_act)
-        pool = self.opponent_pool > 0
-        if pool:
+        if self.opponent_pool:
             self.opp_draws.uniform(self.opp_u)
         if self.overlap_host:
             self._rollout_steps_overlapped()
-        split = getattr(self, "_split", None) is not None
-        if split:
+        elif self._split is not None:
             self._rollout_steps_split()
-        fused = self.device_env              # the maze / arcade step kernel also does the loop bookkeeping and prepares step t+1
-        fuse_policy = fused and self.fuse_policy_env     # policy head + draw inside the environment step's launch
-        # ... and the conv encoder of the next step's frames (rows t + 1 of ws: f2, saved conv1, ReLU bits, absmax slots)
+        elif self.device_env:
+            self._rollout_steps_device()
+        else:
+            self._rollout_steps_host()
+        self._rollout_bootstrap()
+        self._rollout_returns()
+
+    def _rollout_steps_device(self):
+        """The T lock-step steps of a device environment: the maze / arcade step kernel also does the loop bookkeeping and
+        prepares step t + 1 (_next_rows); with fuse_policy_env the policy head + draw run inside its launch, with
+        fuse_env_encoder also the conv encoder of the next step's frames (rows t + 1 of ws: f2, saved conv1, ReLU bits,
+        absmax slots)."""
+        B, T, A, ws, net, env = self.Bg, self.n_step_TD, self.action_size, self.base_ws, self.local_network, self.environment
+        pool = self.opponent_pool > 0
+        fuse_policy = self.fuse_policy_env
         fuse_encoder = (fuse_policy and self.fuse_env_encoder and B >= self.FUSE_ENV_ENCODER_MIN_ACTORS and A == 4 and
-                        getattr(self.environment, "fused_encoder_ok", False) and not net.hw and
+                        getattr(env, "fused_encoder_ok", False) and not net.hw and
                         net.enc_prepared is not None and ws.c1 is not None and ws.f2_bits is not None)
         encoded = False
-        for t in range(0 if not (self.overlap_host or split) else T, T):
-            s = slice(t * B, (t + 1) * B)
+        for t in range(T):
+            u, pi, v, actions, rewards, terminals, active_log = self._block(t)
             if pool:                           # the opponents move first; their state is carried after the step
-                self._opponents_act(self.opp_u[s], self.opponent_actions[s])
-            feat, ld = self._policy_step(ws, t, self.u_act[s], self.actions[s], self.pi[t * B * A:(t + 1) * B * A],
-                                         self.v[s], prefilled=fused and t > 0, heads=not fuse_policy, encoded=encoded)
-            encoded = False
-            if fused:
-                nxt = {}
-                if t + 1 < T:
-                    nxt = dict(next_idx=ws.frame_idx[(t + 1) * B:(t + 2) * B])
-                    if self.use_lstm:
-                        nxt.update(next_lar=ws.xcat[(t + 1) * B * ws.xld:], lar_ld=ws.xld, lar_col0=256, A=A)
-                if fuse_encoder and t + 1 < T:
-                    r1 = (t + 1) * B
-                    s_f2, _, s_c1 = net.ws_slots(ws)
-                    self.environment.policy_rollout_step_encode(
-                        net, feat, ld, self.u_act[s], self.pi[t * B * A:(t + 1) * B * A], self.v[s], self.actions[s],
-                        self.rewards[s], self.terminals[s], self.active, self.active_log[s], self.n_steps,
-                        self.terminal_end, ws.f2[r1 * net.F:], ws.c1[r1 * net.c1_dim:], ws.f2_bits[r1 * ops.RELU_WORDS:],
-                        s_f2, s_c1, **nxt)
-                    encoded = True
-                    continue
-                if fuse_policy:
-                    self.environment.policy_rollout_step(net, feat, ld, self.u_act[s], self.pi[t * B * A:(t + 1) * B * A],
-                                                         self.v[s], self.actions[s], self.rewards[s], self.terminals[s],
-                                                         self.active, self.active_log[s], self.n_steps, self.terminal_end,
-                                                         **nxt)
-                else:
-                    self.environment.rollout_step(self.actions[s], self.rewards[s], self.terminals[s], self.active,
-                                                  self.active_log[s], self.n_steps, self.terminal_end, **nxt)
-                if pool:
-                    self._opponents_carry(self.terminal_end)
-                continue
-            self.environment.process(self.actions[s], self.active, self.rewards[s], self.terminals[s],
-                                     reset_on_terminal=True, track_score=True)
-            ops.rollout_advance(B, self.terminals[s], self.active, self.active_log[s], self.n_steps,
-                                self.terminal_end)
+                self._opponents_act(self.opp_u[t * B:(t + 1) * B], self.opponent_actions[t * B:(t + 1) * B])
+            feat, ld = self._policy_step(ws, t, prefilled=t > 0, heads=not fuse_policy, encoded=encoded)
+            step = (rewards, terminals, self.active, active_log, self.n_steps, self.terminal_end)
+            nxt = self._next_rows(ws, t)
+            encoded = fuse_encoder and t + 1 < T
+            if encoded:
+                r1 = (t + 1) * B
+                s_f2, _, s_c1 = net.ws_slots(ws)
+                env.policy_rollout_step_encode(net, feat, ld, u, pi, v, actions, *step, ws.f2[r1 * net.F:],
+                                               ws.c1[r1 * net.c1_dim:], ws.f2_bits[r1 * ops.RELU_WORDS:], s_f2, s_c1, **nxt)
+            elif fuse_policy:
+                env.policy_rollout_step(net, feat, ld, u, pi, v, actions, *step, **nxt)
+            else:
+                env.rollout_step(actions, *step, **nxt)
+            if pool:
+                self._opponents_carry(self.terminal_end)
+
+    def _rollout_steps_host(self):
+        """The T lock-step steps of host-fed actors: policy step, the simulators' step, the loop bookkeeping."""
+        B, ws = self.Bg, self.base_ws
+        for t in range(self.n_step_TD):
+            _, _, _, actions, rewards, terminals, active_log = self._block(t)
+            self._policy_step(ws, t)
+            self.environment.process(actions, self.active, rewards, terminals, reset_on_terminal=True, track_score=True)
+            ops.rollout_advance(B, terminals, self.active, active_log, self.n_steps, self.terminal_end)
+
+    def _rollout_bootstrap(self):
+        """The carried LSTM state advances to the last step's; boot_v = V(s_T) for actors still running, with the LSTM
+        state NOT advanced (model.py:687-704); the state of an actor whose episode ended is reset (trainer.py:293)."""
+        B, T, A, ws, net = self.Bg, self.n_step_TD, self.action_size, self.base_ws, self.local_network
         if self.use_lstm:
             ops.copy_(self.lstm_c, ws.c[(T - 1) * B * 256:T * B * 256])
             ops.copy_(self.lstm_h, ws.h[(T - 1) * B * 256:T * B * 256])
-        # bootstrap R = V(s_T) for actors still running; LSTM state NOT advanced (model.py:687-704)
         bw = self.boot_ws
         if self.use_lstm:
             ops.copy_(bw.c0, self.lstm_c)
@@ -1063,6 +1100,10 @@ class Trainer(PassState):
         net.value_forward(B, feat, ld, self.boot_v)
         if self.use_lstm:                      # episode ended -> reset_state() (trainer.py:293)
             ops.reset_state(B, self.terminal_end, self.lstm_c, self.lstm_h)
+
+    def _rollout_returns(self):
+        """R and the advantages of the rollout's rows: n-step returns, or GAE(lambda) / time-limit bootstrapping."""
+        B, T = self.Bg, self.n_step_TD
         rewards = self.rewards
         if self.explore_beta > 0:              # the returns see rewards + bonus; self.rewards stays extrinsic (DESIGN §7r)
             self._explore_rewards()
@@ -1076,11 +1117,10 @@ class Trainer(PassState):
         if self.normalize_advantages:          # after GAE and the bonus have shaped self.adv, which stays raw
             ops.adv_normalize(T * B, self.adv, self.active_log, self.adv_norm_eps, self.adv_norm, self.adv_stats)
 
-    def _train_base(self, reuse=False, c=None):
-        """Loss and backward of the rollout's rows.  `reuse`: the rows have been re-evaluated with the current weights
-        (reuse_gradients): heads, clipped-surrogate loss against the rollout's policy c.pi and gradient in one launch.
-        `c`: the pass state holding the rows (the trainer's own by default; the minibatch twin: one block's rows)."""
-        c = self if c is None else c
+    def _train_base(self, c, reuse=False):
+        """Loss and backward of the rollout's rows.  `c`: the pass state holding the rows (the trainer itself; the minibatch
+        twin: one block's rows).  `reuse`: the rows have been re-evaluated with the current weights (reuse_gradients):
+        heads, clipped-surrogate loss against the rollout's policy c.pi and gradient in one launch."""
         B, T, A, ws, net, g, p = c.Bg, self.n_step_TD, self.action_size, c.base_ws, self.local_network, \
             self.local_network.g, self.local_network.p
         rows = T * B
@@ -1100,55 +1140,27 @@ class Trainer(PassState):
         ops.linear_small_bwd(rows, 256, 1, feat, ld, c.dv, 1, p["W_base_fc_v"], d_feat, 256, True,
                              g["W_base_fc_v"], g["b_base_fc_v"])
         if self.use_depth_prediction:
-            self._train_depth(rows, feat, ld, d_feat, c)
+            self._train_depth(c, rows, feat, ld, d_feat)
         net.trunk_backward(c.base_ring, ws, c.gws, T, B, d_feat, h0_nonzero=True)
 
-    def _train_depth(self, rows, feat, ld, d_feat, c=None):
+    def _train_depth(self, c, rows, feat, ld, d_feat):
         """[Depth prediction] on the rollout's rows: head forward, cross-entropy against the ring's labels of
         the frames the encoder read, head backward; the head's share of d(loss)/d(feat) is added into d_feat."""
         from ..model.model import DEPTH_OUT
-        c = self if c is None else c
         net, ws = self.local_network, c.base_ws
         net.depth_head_forward(rows, feat, ld, c.dp_hidden, c.dp_logits)
         ops.depth_loss_grad(rows, c.dp_logits, DEPTH_OUT, c.base_ring.r_depth, ws.frame_idx, c.active_log,
                             self.depth_lambda * c.grad_scale, c.dp_dlogits, c.losses[6:7], c.dp_hits)
         net.depth_head_backward(rows, feat, ld, c.dp_hidden, c.dp_dlogits, c.dp_d_hidden, d_feat, 256)
 
-    def _sample_sequence(self, c=None):
-        """experience.sample_sequence(local_t_max+1) for every actor + the bootstrap frame's features."""
-        c = self if c is None else c
-        B, Ta, net = c.Bg, self.local_t_max, self.local_network
-        L = Ta + 1
-        self.draws.randint(self.experience_history_size - L - 1, c.seq_start)
-        ops.replay_sample_seq(c.ring, L, c.seq_start, c.seq_idx, c.seq_len)
-        bw = c.boot_ws
-        ops.seq_last_idx(B, c.seq_idx, c.seq_len, bw.frame_idx[:B])
-        if self.use_lstm:
-            bw.c0.zero_()                      # aux networks always start from the zero state (model.py:395,461)
-            bw.h0.zero_()
-        feat, ld = net.trunk_forward(c.ring, bw, 1, B, lar_from_ring=True, save_c1=False)
-        return feat, ld
-
-    def _aux_forward(self, c=None):
-        c = self if c is None else c
-        B, Ta, net, ws = c.Bg, self.local_t_max, self.local_network, c.aux_ws
-        rows = Ta * B
-        ops.copy_(ws.frame_idx[:rows], c.seq_idx[:rows])
-        if self.use_lstm:
-            ws.c0.zero_()
-            ws.h0.zero_()
-        ops.seq_mask(B, Ta, c.seq_len, c.seq_mask)
-        return net.trunk_forward(c.ring, ws, Ta, B, lar_from_ring=True, save_c1=True)
-
     # Pixel-control head, training pass: loss + backward of the two deconvolutions in ONE launch (unreal_pc_deconv_train:
     # d_dec stays on chip, hp is staged once; 22 KB of HBM traffic per frame instead of 49).  False: the two-launch form.
     fuse_pc_deconv = True
     keep_d_dec = False       # True: the one-launch form also writes d_dec to gws.d_dec (the full-size tests read it)
 
-    def _pc_deconv_loss_backward(self, gws, rows, mask, d_hp, s_hp, c=None):
+    def _pc_deconv_loss_backward(self, c, gws, rows, mask, d_hp, s_hp):
         """gws.hp (relu(pc_fc1), max in slot s_hp), c.seq_act, gws.pc_R -> losses[3], d_hp, the deconv parameter
         gradients; returns the slot holding max |d_hp| (model.py:411-443, 542-557 and their gradients)."""
-        c = self if c is None else c
         A, net = self.action_size, self.local_network
         p, g = net.p, net.g
         s_dhp = net.new_slot()             # max |d_hp|: committed by the deconv backward, read by the pc_fc1 dgrad
@@ -1169,107 +1181,81 @@ class Trainer(PassState):
                           hp_max=s_hp, ddec_max=s_dd)
         return s_dhp
 
-    def _train_pc(self, c=None):
-        """[Pixel change] (trainer.py:339-380, model.py:411-443, 542-557)."""
-        c = self if c is None else c
-        B, Ta, A, net = c.Bg, self.local_t_max, self.action_size, self.local_network
-        p, g, gws = net.p, net.g, c.gws
-        rows = Ta * B
-        ws = c.aux_ws                              # (allocates the per-branch workspace on first use)
-        gws.ensure_pc(rows, A)
-        feat, ld = self._sample_sequence(c)
-        s_bhp = net.new_slot()             # max of the bootstrap frames' hp: committed by the pc_fc1 GEMM
-        net.pc_head_forward(B, feat, ld, c.boot_hp, ws=c.boot_ws, hp_max=s_bhp)
-        ops.pc_deconv_fwd(B, A, c.boot_hp, p["W_pc_deconv_v"], p["b_pc_deconv_v"], p["W_pc_deconv_a"],
-                          p["b_pc_deconv_a"], qmax=c.boot_qmax, hp_max=s_bhp)
-        ops.pc_returns(c.ring, Ta + 1, c.seq_idx, c.seq_len, c.boot_qmax, self.gamma_pc, gws.pc_R)
-        feat, ld = self._aux_forward(c)
-        s_hp = net.new_slot()              # max hp: committed by the pc_fc1 GEMM
-        net.pc_head_forward(rows, feat, ld, gws.hp, ws=c.aux_ws, hp_max=s_hp)
-        ops.gather_i32(c.ring.r_action, c.aux_ws.frame_idx[:rows], c.seq_act)
-        d_hp = gws.d_f2
-        s_dhp = self._pc_deconv_loss_backward(gws, rows, c.seq_mask, d_hp, s_hp, c)
-        from ..model.model import _splitk
-        ops.gemm_split_tn(256, 2592, rows, feat, ld, d_hp, 2592, g["W_pc_fc1"], 2592,
-                              splitk=_splitk(256, 2592, rows), colsum=g["b_pc_fc1"],
-                              a_max=net._one if self.use_lstm else c.aux_ws.s_x, b_max=s_dhp)
-        ops.gemm_split_nt(rows, 256, 2592, d_hp, 2592, net.shadow["pc_fc1_dgrad"], gws.d_feat, 256, a_max=s_dhp)
-        net.trunk_backward(c.ring, c.aux_ws, gws, Ta, B, gws.d_feat)
-
-    def _train_vr(self, c=None):
-        """[Value replay] (trainer.py:383-412, model.py:446-470, 559-566)."""
-        c = self if c is None else c
-        B, Ta, net = c.Bg, self.local_t_max, self.local_network
-        p, g, gws = net.p, net.g, c.gws
-        rows = Ta * B
-        ws = c.aux_ws                              # (allocates the per-branch workspace on first use)
-        feat, ld = self._sample_sequence(c)
-        net.value_forward(B, feat, ld, c.aux_boot_v)
-        ops.vr_returns(c.ring, Ta + 1, c.seq_idx, c.seq_len, c.aux_boot_v, self.gamma, c.aux_R, bonus=True)
-        feat, ld = self._aux_forward(c)
-        net.value_forward(rows, feat, ld, c.aux_v)
-        ops.vr_loss_grad(rows, c.aux_v, c.aux_R, c.seq_mask, c.grad_scale, c.dv, c.losses[4:5])
-        ops.linear_small_bwd(rows, 256, 1, feat, ld, c.dv, 1, p["W_base_fc_v"], gws.d_feat, 256, False,
-                             g["W_base_fc_v"], g["b_base_fc_v"])
-        net.trunk_backward(c.ring, c.aux_ws, gws, Ta, B, gws.d_feat)
-
     batch_aux_default = True       # class default, read by prepare() only (A/B tools build a second Trainer with it off)
 
-    def _train_aux_batched(self, c=None):
-        """[Pixel change] + [Value replay] (trainer.py:339-412) as ONE trunk pass over 2B replayed sequences: sequence
-        2b is actor b's pixel-control sample, 2b + 1 its value-replay sample, so a branch's rows are every other row of the
-        workspace (leading dimension doubled) and every trunk kernel -- encoder, fc, the T recurrent steps, their
-        backward -- runs once at twice the rows instead of twice.  Draws, sampling, targets, heads and losses are the
-        per-branch ones, in the reference's order (pc, vr)."""
-        c = self if c is None else c
-        B, Ta, A, net = c.Bg, self.local_t_max, self.action_size, self.local_network
-        p, g, gws, sh = net.p, net.g, c.gws2, net.shadow
-        L, rows = Ta + 1, Ta * B
-        for s in (0, 1):                                         # experience.sample_sequence(local_t_max + 1), pc then vr
-            self.draws.randint(self.experience_history_size - L - 1, c.seq_start2[s])
-            ops.replay_sample_seq(c.ring, L, c.seq_start2[s], c.seq_idx2[s], c.seq_len2[s])
-            ops.seq_last_idx(B, c.seq_idx2[s], c.seq_len2[s], c.last2[s * B:(s + 1) * B])
-            ops.seq_mask(B, Ta, c.seq_len2[s], c.seq_mask2[s])
-        # bootstrap frames of both samples (zero LSTM state, model.py:395,461)
-        bw = c.boot2_ws
-        ops.gather_i32(c.last2, c.map_boot, bw.frame_idx[:2 * B])
-        # (boot2_ws / aux2_ws belong to this pass alone and nothing ever writes their c0 / h0: they are the zero state they
-        # were allocated as -- model.py:395,461 -- so the four fills per pass the per-branch schedule needs are not issued)
-        feat, ld = net.trunk_forward(c.ring, bw, 1, 2 * B, lar_from_ring=True, save_c1=False)
-        s_bhp = net.new_slot()             # max of the bootstrap frames' hp: committed by the pc_fc1 GEMM
-        net.pc_head_forward(B, feat, 2 * ld, c.boot_hp, ws=c.boot2_ws, hp_max=s_bhp)
-        ops.pc_deconv_fwd(B, A, c.boot_hp, p["W_pc_deconv_v"], p["b_pc_deconv_v"], p["W_pc_deconv_a"],
-                          p["b_pc_deconv_a"], qmax=c.boot_qmax, hp_max=s_bhp)
-        ops.pc_returns(c.ring, L, c.seq_idx2[0], c.seq_len2[0], c.boot_qmax, self.gamma_pc, gws.pc_R)
-        net.value_forward(B, feat[ld:], 2 * ld, c.aux_boot_v)
-        ops.vr_returns(c.ring, L, c.seq_idx2[1], c.seq_len2[1], c.aux_boot_v, self.gamma, c.aux_R,
-                       bonus=True)
-        # the 2B sequences through the trunk
-        ws = c.aux2_ws
-        ops.gather_i32(c.seq_idx_cat, c.map_seq, ws.frame_idx[:2 * rows])
-        feat, ld = net.trunk_forward(c.ring, ws, Ta, 2 * B, lar_from_ring=True, save_c1=True)
-        d_feat = gws.d_feat
-        # pixel-control head on the even rows
-        s_hp = net.new_slot()              # max hp: committed by the pc_fc1 GEMM
-        net.pc_head_forward(rows, feat, 2 * ld, gws.hp, ws=c.aux2_ws, hp_max=s_hp)
-        ops.gather_i32(c.ring.r_action, c.seq_idx2[0][:rows], c.seq_act)
-        d_hp = gws.d_hp
-        s_dhp = self._pc_deconv_loss_backward(gws, rows, c.seq_mask2[0], d_hp, s_hp, c)
-        from ..model.model import _splitk
-        ops.gemm_split_tn(256, 2592, rows, feat, 2 * ld, d_hp, 2592, g["W_pc_fc1"], 2592,
-                          splitk=_splitk(256, 2592, rows), colsum=g["b_pc_fc1"],
-                          a_max=net._one if self.use_lstm else c.aux2_ws.s_x, b_max=s_dhp)
-        ops.gemm_split_nt(rows, 256, 2592, d_hp, 2592, sh["pc_fc1_dgrad"], d_feat, 2 * 256, a_max=s_dhp)
-        # value head on the odd rows
-        net.value_forward(rows, feat[ld:], 2 * ld, c.aux_v)
-        ops.vr_loss_grad(rows, c.aux_v, c.aux_R, c.seq_mask2[1], c.grad_scale, c.aux_dv, c.losses[4:5])
-        ops.linear_small_bwd(rows, 256, 1, feat[ld:], 2 * ld, c.aux_dv, 1, p["W_base_fc_v"], d_feat[256:], 2 * 256, False,
-                             g["W_base_fc_v"], g["b_base_fc_v"])
-        net.trunk_backward(c.ring, ws, gws, Ta, 2 * B, d_feat)
+    def _train_replay(self, c, lanes):
+        """[Pixel change] / [Value replay] (trainer.py:339-412) as ONE trunk pass over S = len(lanes) replayed sequences
+        per actor; `lanes`: "pc" / "vr" in the reference's order.  Sequence S b + s is actor b's sample for lane s, so a
+        lane's rows are every S-th row of the workspace: it reads them with the leading dimension times S from offset
+        s ld (d_feat: s 256), and every trunk kernel -- encoder, fc, the T recurrent steps, their backward -- runs once at
+        S times the rows.  Draws (one per lane, in lane order), sampling, targets, heads and losses are per lane.  The
+        default flag set runs ("pc", "vr"); one task alone, or batch_aux_default off, one lane per pass."""
+        B, Ta, net = c.Bg, self.local_t_max, self.local_network
+        S, L, rows = len(lanes), Ta + 1, Ta * B
+        r = self._replay_set(c, S)
+        ws, bw, gws = r.ws, r.boot_ws, r.gws
+        for s in range(S):                                       # experience.sample_sequence(local_t_max + 1)
+            self.draws.randint(self.experience_history_size - L - 1, r.seq_start[s])
+            ops.replay_sample_seq(c.ring, L, r.seq_start[s], r.seq_idx[s], r.seq_len[s])
+            ops.seq_last_idx(B, r.seq_idx[s], r.seq_len[s], r.last[s * B:(s + 1) * B])
+            ops.seq_mask(B, Ta, r.seq_len[s], r.seq_mask[s])
+        # bootstrap frames of every sample, from the zero LSTM state (_replay_set) -> the lanes' targets
+        if S > 1:
+            ops.gather_i32(r.last, r.map_boot, bw.frame_idx[:S * B])
+        feat, ld = net.trunk_forward(c.ring, bw, 1, S * B, lar_from_ring=True, save_c1=False)
+        for s, lane in enumerate(lanes):
+            (self._pc_targets if lane == "pc" else self._vr_targets)(c, r, s, feat[s * ld:], S * ld, B)
+        # the S B sequences through the trunk -> the lanes' heads, losses and d_feat
+        ops.gather_i32(r.seq_idx_cat, r.map_seq, ws.frame_idx[:S * rows])
+        feat, ld = net.trunk_forward(c.ring, ws, Ta, S * B, lar_from_ring=True, save_c1=True)
+        for s, lane in enumerate(lanes):
+            (self._pc_head if lane == "pc" else self._vr_head)(c, r, s, feat[s * ld:], S * ld, rows,
+                                                               gws.d_feat[s * 256:], S * 256)
+        net.trunk_backward(c.ring, ws, gws, Ta, S * B, gws.d_feat)
 
-    def _train_rp(self, c=None):
+    def _pc_targets(self, c, r, s, feat, ld, rows):
+        """Lane s's pixel-control targets r.gws.pc_R from the features of its `rows` bootstrap frames (model.py:411-443)."""
+        A, net, gws = self.action_size, self.local_network, r.gws
+        p = net.p
+        gws.ensure_pc(self.local_t_max * c.Bg, A)      # (a lane in the update's own gradient workspace: allocated once)
+        s_bhp = net.new_slot()             # max of the bootstrap frames' hp: committed by the pc_fc1 GEMM
+        net.pc_head_forward(rows, feat, ld, c.boot_hp, ws=r.boot_ws, hp_max=s_bhp)
+        ops.pc_deconv_fwd(rows, A, c.boot_hp, p["W_pc_deconv_v"], p["b_pc_deconv_v"], p["W_pc_deconv_a"],
+                          p["b_pc_deconv_a"], qmax=c.boot_qmax, hp_max=s_bhp)
+        ops.pc_returns(c.ring, self.local_t_max + 1, r.seq_idx[s], r.seq_len[s], c.boot_qmax, self.gamma_pc, gws.pc_R)
+
+    def _pc_head(self, c, r, s, feat, ld, rows, d_feat, ldd):
+        """Lane s's pixel-control head on its `rows` rows of the sequence trunk: loss, parameter gradients, d_feat."""
+        net, gws = self.local_network, r.gws
+        g = net.g
+        s_hp = net.new_slot()              # max hp: committed by the pc_fc1 GEMM
+        net.pc_head_forward(rows, feat, ld, gws.hp, ws=r.ws, hp_max=s_hp)
+        ops.gather_i32(c.ring.r_action, r.seq_idx[s][:rows], c.seq_act)
+        d_hp = gws.d_hp if gws.d_hp is not None else gws.d_f2
+        s_dhp = self._pc_deconv_loss_backward(c, gws, rows, r.seq_mask[s], d_hp, s_hp)
+        from ..model.model import _splitk
+        ops.gemm_split_tn(256, 2592, rows, feat, ld, d_hp, 2592, g["W_pc_fc1"], 2592,
+                          splitk=_splitk(256, 2592, rows), colsum=g["b_pc_fc1"],
+                          a_max=net._one if self.use_lstm else r.ws.s_x, b_max=s_dhp)
+        ops.gemm_split_nt(rows, 256, 2592, d_hp, 2592, net.shadow["pc_fc1_dgrad"], d_feat, ldd, a_max=s_dhp)
+
+    def _vr_targets(self, c, r, s, feat, ld, rows):
+        """Lane s's value-replay returns c.aux_R from the features of its `rows` bootstrap frames (model.py:446-470)."""
+        self.local_network.value_forward(rows, feat, ld, c.aux_boot_v)
+        ops.vr_returns(c.ring, self.local_t_max + 1, r.seq_idx[s], r.seq_len[s], c.aux_boot_v, self.gamma, c.aux_R,
+                       bonus=True)
+
+    def _vr_head(self, c, r, s, feat, ld, rows, d_feat, ldd):
+        """Lane s's value head on its `rows` rows of the sequence trunk: loss, parameter gradients, d_feat."""
+        net = self.local_network
+        p, g = net.p, net.g
+        net.value_forward(rows, feat, ld, c.aux_v)
+        ops.vr_loss_grad(rows, c.aux_v, c.aux_R, r.seq_mask[s], c.grad_scale, c.dv, c.losses[4:5])
+        ops.linear_small_bwd(rows, 256, 1, feat, ld, c.dv, 1, p["W_base_fc_v"], d_feat, ldd, False,
+                             g["W_base_fc_v"], g["b_base_fc_v"])
+
+    def _train_rp(self, c):
         """[Reward prediction] (trainer.py:415-436, model.py:473-488, 569-576)."""
-        c = self if c is None else c
         B, net, ws = c.Bg, self.local_network, c.rp_ws
         p, g, gws = net.p, net.g, c.gws
         self.draws.randint(2, c.rp_coin)
@@ -1300,8 +1286,8 @@ class Trainer(PassState):
             return
         net.grads.flat.zero_()
         self.losses.zero_()
-        self._train_base()
-        self._train_aux()
+        self._train_base(self)
+        self._train_aux(self)
 
     def minibatch_gradients(self, m):
         """The gradient of one minibatch update: §7q's reuse pass on block m of the selected group, the actors
@@ -1332,22 +1318,16 @@ class Trainer(PassState):
                           objective_prefilled=True)
         net.grads.flat.zero_()
         self.losses.zero_()
-        self._train_base(reuse=True, c=mb)
+        self._train_base(mb, reuse=True)
         self._point_draws(Bm, b0)                  # fresh draws for the block's Bm actors, at their own columns
         self._train_aux(mb)
         self._point_draws(Bg, self._group_views[self.group][3])
 
-    def _train_aux(self, c=None):
+    def _train_aux(self, c):
         """The auxiliary branches of one update, each with fresh draws, in the reference's order (pc, vr, rp); `c`: the
-        pass state they run on (the trainer's own by default; the minibatch twin: the block's actors and replay)."""
-        c = self if c is None else c
-        if c.batch_aux:
-            self._train_aux_batched(c)
-        else:
-            if self.use_pixel_change:
-                self._train_pc(c)
-            if self.use_value_replay:
-                self._train_vr(c)
+        pass state they run on (the trainer itself; the minibatch twin: the block's actors and replay)."""
+        for lanes in c.replay_passes:
+            self._train_replay(c, lanes)
         if self.use_reward_prediction:
             self._train_rp(c)
 
@@ -1366,8 +1346,8 @@ class Trainer(PassState):
                           lar_prefilled=True, objective_prefilled=True)
         net.grads.flat.zero_()
         self.losses.zero_()
-        self._train_base(reuse=True)
-        self._train_aux()
+        self._train_base(self, reuse=True)
+        self._train_aux(self)
 
     def _apply_update(self, lr):
         """Gradient exchange (multi-rank), global-norm clip + the grad_applier's step (RMSProp; Adam: DESIGN §7s) on
